@@ -5,16 +5,23 @@ A step = one synthetic KITTI-shaped frame (already resident in HBM as the 1x3xHx
 VGG-16 trunk + proposal heads (MFMA convs) -> BoxOutput (decode / top-2000 / NMS) -> 2 x ROIPooling -> roi_c1 + fc6 +
 cls/bbox heads -> final bbox transform + per-class NMS, with the detections delivered to the host.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--model M] [--regime dense|mid|sparse]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--model M] [--regime dense|mid|sparse] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   (one rank per GPU)
 A plain `python bench.py --gpus N` with N > 1 (no RANK / WORLD_SIZE in the environment) launches itself under
 torch.distributed.run with N ranks; with fewer than N devices visible it exits non-zero instead of measuring fewer GPUs.
+
+A plain run sets up, warms up, times the K steps and prints the line (headline figures only).  --full adds every side leg
+below (the other detect mode, the other regimes, robustness, roofline / per-stage passes, the CPU baseline and the full-size
+parity against it).  --dump-outputs DIR writes what the last timed step delivered to the host as DIR/<name>.npy (float64):
+detections [D, 5] (x y w h score), roi_ids [D] and num_rois [1], suffixed _rank<r> under the multi-GPU exchange and
+_image<b> for --batch B > 1.  Inputs and weights are seeded: the same arguments give the same inputs on every run.
 
 Multi-GPU: independent images per GPU (weak scaling, no data-path collective); per step ONE ncclAllGather of the
 device-resident detection pack of every rank (libmscnn_dist.so calls RCCL directly; mscnn_amd/dist.py).
 
 Rank 0 prints ONE JSON line:
   value / ms_per_step   whole-job images/sec over the K timed steps (max over ranks); step_ms = median / p10 / p90 per step
+(--full only, from here on)
   roofline              the DOMINANT kernel (wgemm_kernel: the 25 / 36 plane GEMMs of the Winograd layers): FLOPs its MFMAs
                         EXECUTE / its HIP-event time / 157.3 TFLOP/s (never above 1); the conv3_1..conv5_3 block the north star
                         names is reported beside it, executed and as algorithmic-equivalent rate
@@ -25,6 +32,7 @@ Rank 0 prints ONE JSON line:
                         1-thread row on a bounded sample; the same frame goes through the HIP path: parity_ok asserts it
 """
 import argparse
+import collections
 import json
 import os
 import subprocess
@@ -414,14 +422,28 @@ def _set_affinity_all_threads(mask):
             pass
 
 
+def _dump_outputs(path, taken, gathered, B):
+    """--dump-outputs: the last timed step's host results, one exchange per image (B of them), each holding every rank's
+    (dets [D, 5] float64, roi ids [D] int32, R) -> float64 .npy files."""
+    os.makedirs(path, exist_ok=True)
+    assert len(taken) == B, (len(taken), B)
+    for b, per_rank in enumerate(taken):
+        for r, (dets, ids, R) in enumerate(per_rank):
+            sfx = (f"_rank{r}" if gathered else "") + (f"_image{b}" if B > 1 else "")
+            np.save(os.path.join(path, f"detections{sfx}.npy"), np.asarray(dets, np.float64).reshape(-1, 5))
+            np.save(os.path.join(path, f"roi_ids{sfx}.npy"), np.asarray(ids, np.float64))
+            np.save(os.path.join(path, f"num_rois{sfx}.npy"), np.array([R], np.float64))
+
+
 def _refuse(msg):
     print("bench.py: " + msg, file=sys.stderr, flush=True)
     sys.exit(2)
 
 
 def _self_launch(args):
-    """`python bench.py --gpus N` (N > 1) outside a launcher: become `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
-    ... bench.py <same arguments>` -- one rank per GPU, rank 0 prints the one JSON line.  Never falls back to fewer GPUs."""
+    """`python bench.py --gpus N` (N > 1) outside a launcher: run `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
+    ... bench.py <same arguments>` as a child process and exit with its status -- one rank per GPU, rank 0 prints the one JSON
+    line.  Never falls back to fewer GPUs.  (A child, not an exec: this process may have opened the GPU to count devices.)"""
     if not args.launch_check:
         have = torch.cuda.device_count() if torch.cuda.is_available() else 0
         if have < args.gpus:
@@ -431,7 +453,7 @@ def _self_launch(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush(); sys.stderr.flush()
-    os.execv(sys.executable, cmd)
+    sys.exit(subprocess.call(cmd))
 
 
 def _launch_check(args, rank, world, local_rank):
@@ -513,13 +535,18 @@ def main():
                          "resident frames + B per-image final stages, value = B * steps / time; reported BESIDE the batch-1 line (one-round "
                          "layers of the 480 x 640 stream config become multi-round); N = 1 only")
     ap.add_argument("--regime", default="mid", choices=["dense", "mid", "sparse"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline loop, also run every side leg: the other detect mode, the other regimes, robustness, the "
+                         "roofline / per-stage passes, the CPU baseline and the full-size parity against it (off: the headline line only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step delivered to the host (detections, roi ids, ROI count) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--alt", action="store_true", help="opt-in (round 5): a second timed loop in the f16x3 mode, reported as alt_precision "
                                                        "(no SURVEY 8 row; the driver's wall time goes to the headline loop instead)")
     ap.add_argument("--no-alt", action="store_true", help="(accepted for old command lines: the f16x3 loop is opt-in now, see --alt)")
     ap.add_argument("--no-regimes", action="store_true", help="skip the dense / sparse legs (SURVEY 8d regimes beside the headline's)")
     ap.add_argument("--no-robust", action="store_true", help="skip the robustness leg (vgg_like weights: calibration fall-backs, all-direct floor)")
-    ap.add_argument("--layers", action="store_true", help="print the per-layer tables (caffe time format) to stderr")
+    ap.add_argument("--layers", action="store_true", help="print the per-layer tables (caffe time format) to stderr (runs the roofline passes)")
     ap.add_argument("--dump-steps", action="store_true", help="print the wall time of every timed step to stderr (outlier hunting)")
     ap.add_argument("--gather", default="rccl", choices=["rccl", "torch"],
                     help="multi-GPU exchange: libmscnn_dist's direct ncclAllGather (default), or torch.distributed's all_gather of the "
@@ -553,6 +580,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         _refuse(f"--gpus {args.gpus}")
+    if args.steps < 1:
+        _refuse(f"--steps {args.steps}")
     if args.batch < 1 or (args.batch > 1 and args.gpus > 1):
         _refuse(f"--batch {args.batch} with --gpus {args.gpus}: the batched mode is a single-GPU side table")
 
@@ -625,6 +654,7 @@ def main():
         dist.all_gather_object(allf, flags[0])
         assert all(f == allf[0] for f in allf), "ranks disagree on the gather route"
     stats = {"R": [], "D": []}
+    last_taken = collections.deque(maxlen=B)      # what the last step delivered: one exchange (all ranks' packs) per image
     pipe = {"on": False, "inflight": 0, "gather_s": []}
     local_pipe = gather is None and B == 1 and args.detect_mode == "pipelined"      # N = 1: the final stage pipelined like the exchange
     can_pipeline = (hasattr(gather, "begin") and args.gather_mode == "pipelined") or local_pipe
@@ -638,6 +668,7 @@ def main():
         # every exchange of the timed loop: as many packs as the communicator has ranks, slot r stamped by rank r (RcclGather._split
         # raises otherwise) -- the line can only be printed if RCCL really delivered N ranks' packs every step
         assert len(per_rank) == (world if gather is not None else 1), (len(per_rank), world)
+        last_taken.append(per_rank)
         dets, ids, R = per_rank[rank if gather is not None else 0]
         stats["R"].append(R); stats["D"].append(len(dets))
         return dets
@@ -747,6 +778,8 @@ def main():
     elapsed = time.perf_counter() - t0
     elapsed_local = elapsed
     gc.enable()
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, list(last_taken), gather is not None, B)
     if args.dump_steps and rank == 0:
         print("step_ms: " + " ".join(f"{1e3 * v:.2f}" for v in step_s), file=sys.stderr)
     if dist is not None:
@@ -769,7 +802,7 @@ def main():
 
     # ---- the other detect mode beside the headline (N = 1, batch 1): a short loop each way, same contract
     detect_modes = None
-    if gather is None and B == 1:
+    if args.full and gather is None and B == 1:
         ds = max(10, min(args.steps, 50))
         other = "sync" if local_pipe else "pipelined"
         keep = stats
@@ -832,7 +865,7 @@ def main():
     # "sparse": ~5 % pass (fewer candidates than the top-K).  Timed like the headline (a short loop each), R recorded; each regime's parity
     # against the reference's CPU layers is asserted in the cpu_baseline leg below (the trunk blobs of the reference run are shared).
     regimes, net_cap = None, None
-    if args.dtype == "f32" and world == 1 and B == 1 and not args.no_regimes:
+    if args.full and args.dtype == "f32" and world == 1 and B == 1 and not args.no_regimes:
         regimes = {args.regime: {"value": round(value, 3), "unit": "images/sec", "steps": args.steps, "mean_rois": round(float(np.mean(main_stats["R"])), 1),
                                  "mean_detections": round(float(np.mean(main_stats["D"])), 1), "headline": True}}
         rs = max(5, min(args.steps, 30))
@@ -871,7 +904,7 @@ def main():
     # error of the direct sum; the calibration step decides per layer on THIS data which ones stay.  Reported: the layers that fell
     # back, the images/sec that results, and the floor with every Winograd layer on the direct kernel.
     robust = None
-    if args.dtype == "f32" and world == 1 and not args.no_robust and B == 1:
+    if args.full and args.dtype == "f32" and world == 1 and not args.no_robust and B == 1:
         rs = max(5, min(args.steps, 20))
 
         def timed(nsteps):
@@ -908,89 +941,91 @@ def main():
     result = None
     rc = 0
     if rank == 0:
-        # ---- roofline: HIP events on the net's stream, outside the timed region --------------------------------------------
-        # two passes: per-layer times with plain HIP events around every layer, then the per-stage split of the convolution
-        # plans (their extra event records would inflate the small layers of the first table)
-        net.set_layer_timing(True)
-        L = len(net.layer_names)
-        acc = np.zeros(L); stage = np.zeros((L, 3)); reps = 5; stage_reps = []
-        for i in range(reps):
-            net.set_blob("data", frames[i % len(frames)])
-            net.forward()
-            acc += np.array(net.layer_ms())
-        net.set_conv_profiling(True)
-        for i in range(reps):
-            net.set_blob("data", frames[i % len(frames)])
-            net.forward()
-            stage_reps.append(np.array([net.layer_stage_ms(j) for j in range(L)]))
-            stage += stage_reps[-1]
-        net.set_layer_timing(False)
-        net.set_conv_profiling(False)
-        lay_ms, stage = acc / reps, stage / reps
-        flops = np.array([net.layer_flops(i) for i in range(L)])
-        xflops = np.array([net.layer_executed_flops(i) for i in range(L)])
-        kern = [net.layer_kernel(i) for i in range(L)]
-        wino = [i for i in range(L) if kern[i].startswith("winograd_f")]      # F(3x3,3x3) and F(4x4,3x3) layers: the same GEMM kernel
-        idx = [net.layer_names.index(nm) for nm in ROOFLINE_LAYERS]
-        dtypes = [net.layer_dtype(i) for i in range(L)]
-        conv16 = [i for i in range(L) if dtypes[i] == "f16" and net.layer_types[i] == "Convolution"]
-        if args.dtype == "f16":     # dominant kernel family = the fp16 implicit-GEMM 3x3 kernels (one launch per layer + fix-up)
-            wino = conv16
-        # dominant kernel = the MFMA GEMM of the F(3x3,3x3) layers: one launch per layer
-        g_flops, g_ms = float(xflops[wino].sum()), float(stage[wino, 1].sum())
-        achieved = g_flops / (g_ms * 1e-3) / 1e12 if g_ms > 0 else 0.0
-        # (per-layer device time: the plan's own stage events where it has them -- they bracket exactly the layer's kernels; the
-        # net-level per-layer events also contain the host's launch gap after each per-layer synchronisation)
-        dev_ms = np.where(stage.sum(axis=1) > 0, stage.sum(axis=1), lay_ms)
-        blk_ms = float(dev_ms[idx].sum())
-        blk_exec = float(xflops[idx].sum()) / (blk_ms * 1e-3) / 1e12
-        blk_alg = float(flops[idx].sum()) / (blk_ms * 1e-3) / 1e12
-        conv_idx = [i for i, t in enumerate(net.layer_types) if t == "Convolution"]
-        # HBM bytes of the dominant kernel are a PMC measurement (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes): not
-        # something this process can take of itself.  The line carries the latest such measurement (tools/pmc_traffic.py -> profiles/)
-        # only while the kernel sources it was taken on are byte-identical to the ones running now; else null.
-        traffic, tsrc, textra = _measured_traffic()
-        if args.model != DEFAULT_MODEL or args.dtype != "f32":      # (the measured launch is conv4_2 of the default model's fp32 path)
-            traffic, tsrc, textra = None, "the PMC measurement in profiles/ is of the default model's fp32 plane GEMM (conv4_2): not reported for this run", {}
-        peak = FP16_MFMA_PEAK_TFLOPS if args.dtype in ("f16", "f16x3") else FP32_MFMA_PEAK_TFLOPS
-        roofline = {
-            "bound": "mfma", "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
-            "frac": round(achieved / peak, 4), "traffic": traffic, "traffic_source": tsrc, **textra,
-            **(_measured_mfma_busy() if args.model == DEFAULT_MODEL and args.dtype == "f32" else {}),
-            **({"frac_of_measured_mfma_peak": round(achieved / FP32_MFMA_MEASURED_TFLOPS, 4),
-                "measured_mfma_peak": FP32_MFMA_MEASURED_TFLOPS} if args.dtype == "f32" else {}),
-            "kernel": ("igemm_kernel<Cfg<...,F16>> (igemm16_*): direct 3x3 implicit GEMM on v_mfma_f32_32x32x16_f16, operands rounded to "
-                       "fp16 while staged into LDS, fp32 accumulate (+ its stream-K fix-up)") if args.dtype == "f16" else
-                      ("x3_gemm_kernel<128|256> -- the 25 plane GEMMs of the Winograd F(3x3,3x3) layers on v_mfma_f32_32x32x16_f16 with "
-                       "every fp32 operand split exactly into fp16 hi + lo: three MFMAs per product pair (all three counted as "
-                       "executed FLOPs), fp32 accumulate") if args.dtype == "f16x3" else
-                      "wgemm_kernel<256x128 | 256x160 | 128x256 | 256x96 | 128x128, ck32> (mscnn_amd/csrc/wgemm.hip) -- the batched [Cout x Cin] x [Cin x tiles] GEMMs of the "
-                      "Winograd layers (25 planes F(3x3,3x3), 36 planes F(4x4,3x3)) on v_mfma_f32_32x32x2_f32: 8 waves per CU, operands by "
-                      "LDS-DMA into a 3-stage ring (+ its fix-up launch where the tile count is split stream-K style)",
-            "flops_note": "achieved = FLOPs the kernel's MFMAs execute for the real problem (2 * planes * Cout * Cin * tiles per launch) / "
-                          "its HIP-event time on the net's stream, summed over its launches of one image",
-            **({"fp32_equivalent_tflops": round(achieved / 3, 2),
-                "fp32_equivalent_vs_fp32_mfma_peak": round(achieved / 3 / FP32_MFMA_PEAK_TFLOPS, 4)} if args.dtype == "f16x3" else {}),
-            "launches_per_image": len(wino), "avg_launch_us": round(1e3 * g_ms / max(len(wino), 1), 1),
-            "gemm_ms_over_passes": {"min": round(float(min(r[wino, 1].sum() for r in stage_reps)), 4),
-                                    "max": round(float(max(r[wino, 1].sum() for r in stage_reps)), 4), "passes": reps},
-            "executed_gflop_per_image": round(g_flops / 1e9, 2),
-            "layers": [net.layer_names[i] for i in wino],
-            "conv3_5_block": {"layers": ROOFLINE_LAYERS, "ms_per_image": round(blk_ms, 4),
-                              "executed_tflops": round(blk_exec, 2), "executed_frac": round(blk_exec / peak, 4),
-                              "algorithmic_equiv_tflops": round(blk_alg, 2),
-                              "algorithmic_gflop_per_image": round(float(flops[idx].sum()) / 1e9, 2),
-                              "note": "all kernels of the nine layers (input transform + GEMM + output transform); executed = the MFMA "
-                                      "FLOPs really issued; algorithmic_equiv = the reference's direct-convolution 2*MACs / the same time"},
-            "winograd_stage_ms": {"input_transform": round(float(stage[wino, 0].sum()), 4), "gemm": round(g_ms, 4),
-                                  "output_transform": round(float(stage[wino, 2].sum()), 4)},
-            "all_conv_executed_tflops": round(float(xflops[conv_idx].sum()) / (float(lay_ms[conv_idx].sum()) * 1e-3) / 1e12, 2)}
-        if args.layers:
-            for i, nm in enumerate(net.layer_names):
-                if lay_ms[i] > 0:
-                    tf = xflops[i] / (lay_ms[i] * 1e-3) / 1e12 if xflops[i] else 0
-                    st = f" [in {stage[i, 0]*1e3:6.1f} gemm {stage[i, 1]*1e3:6.1f} out {stage[i, 2]*1e3:6.1f}]" if stage[i].sum() > 0 and kern[i].startswith("wino") else ""
-                    print(f"{nm:28s} {net.layer_types[i]:14s} {kern[i]:30s} {lay_ms[i]*1e3:9.1f} us {tf:7.1f} TF executed{st}", file=sys.stderr)
+        roofline, lay_ms = None, None
+        if args.full or args.layers:      # passes of their own: --full (or --layers) only
+            # ---- roofline: HIP events on the net's stream, outside the timed region --------------------------------------------
+            # two passes: per-layer times with plain HIP events around every layer, then the per-stage split of the convolution
+            # plans (their extra event records would inflate the small layers of the first table)
+            net.set_layer_timing(True)
+            L = len(net.layer_names)
+            acc = np.zeros(L); stage = np.zeros((L, 3)); reps = 5; stage_reps = []
+            for i in range(reps):
+                net.set_blob("data", frames[i % len(frames)])
+                net.forward()
+                acc += np.array(net.layer_ms())
+            net.set_conv_profiling(True)
+            for i in range(reps):
+                net.set_blob("data", frames[i % len(frames)])
+                net.forward()
+                stage_reps.append(np.array([net.layer_stage_ms(j) for j in range(L)]))
+                stage += stage_reps[-1]
+            net.set_layer_timing(False)
+            net.set_conv_profiling(False)
+            lay_ms, stage = acc / reps, stage / reps
+            flops = np.array([net.layer_flops(i) for i in range(L)])
+            xflops = np.array([net.layer_executed_flops(i) for i in range(L)])
+            kern = [net.layer_kernel(i) for i in range(L)]
+            wino = [i for i in range(L) if kern[i].startswith("winograd_f")]      # F(3x3,3x3) and F(4x4,3x3) layers: the same GEMM kernel
+            idx = [net.layer_names.index(nm) for nm in ROOFLINE_LAYERS]
+            dtypes = [net.layer_dtype(i) for i in range(L)]
+            conv16 = [i for i in range(L) if dtypes[i] == "f16" and net.layer_types[i] == "Convolution"]
+            if args.dtype == "f16":     # dominant kernel family = the fp16 implicit-GEMM 3x3 kernels (one launch per layer + fix-up)
+                wino = conv16
+            # dominant kernel = the MFMA GEMM of the F(3x3,3x3) layers: one launch per layer
+            g_flops, g_ms = float(xflops[wino].sum()), float(stage[wino, 1].sum())
+            achieved = g_flops / (g_ms * 1e-3) / 1e12 if g_ms > 0 else 0.0
+            # (per-layer device time: the plan's own stage events where it has them -- they bracket exactly the layer's kernels; the
+            # net-level per-layer events also contain the host's launch gap after each per-layer synchronisation)
+            dev_ms = np.where(stage.sum(axis=1) > 0, stage.sum(axis=1), lay_ms)
+            blk_ms = float(dev_ms[idx].sum())
+            blk_exec = float(xflops[idx].sum()) / (blk_ms * 1e-3) / 1e12
+            blk_alg = float(flops[idx].sum()) / (blk_ms * 1e-3) / 1e12
+            conv_idx = [i for i, t in enumerate(net.layer_types) if t == "Convolution"]
+            # HBM bytes of the dominant kernel are a PMC measurement (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes): not
+            # something this process can take of itself.  The line carries the latest such measurement (tools/pmc_traffic.py -> profiles/)
+            # only while the kernel sources it was taken on are byte-identical to the ones running now; else null.
+            traffic, tsrc, textra = _measured_traffic()
+            if args.model != DEFAULT_MODEL or args.dtype != "f32":      # (the measured launch is conv4_2 of the default model's fp32 path)
+                traffic, tsrc, textra = None, "the PMC measurement in profiles/ is of the default model's fp32 plane GEMM (conv4_2): not reported for this run", {}
+            peak = FP16_MFMA_PEAK_TFLOPS if args.dtype in ("f16", "f16x3") else FP32_MFMA_PEAK_TFLOPS
+            roofline = {
+                "bound": "mfma", "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
+                "frac": round(achieved / peak, 4), "traffic": traffic, "traffic_source": tsrc, **textra,
+                **(_measured_mfma_busy() if args.model == DEFAULT_MODEL and args.dtype == "f32" else {}),
+                **({"frac_of_measured_mfma_peak": round(achieved / FP32_MFMA_MEASURED_TFLOPS, 4),
+                    "measured_mfma_peak": FP32_MFMA_MEASURED_TFLOPS} if args.dtype == "f32" else {}),
+                "kernel": ("igemm_kernel<Cfg<...,F16>> (igemm16_*): direct 3x3 implicit GEMM on v_mfma_f32_32x32x16_f16, operands rounded to "
+                           "fp16 while staged into LDS, fp32 accumulate (+ its stream-K fix-up)") if args.dtype == "f16" else
+                          ("x3_gemm_kernel<128|256> -- the 25 plane GEMMs of the Winograd F(3x3,3x3) layers on v_mfma_f32_32x32x16_f16 with "
+                           "every fp32 operand split exactly into fp16 hi + lo: three MFMAs per product pair (all three counted as "
+                           "executed FLOPs), fp32 accumulate") if args.dtype == "f16x3" else
+                          "wgemm_kernel<256x128 | 256x160 | 128x256 | 256x96 | 128x128, ck32> (mscnn_amd/csrc/wgemm.hip) -- the batched [Cout x Cin] x [Cin x tiles] GEMMs of the "
+                          "Winograd layers (25 planes F(3x3,3x3), 36 planes F(4x4,3x3)) on v_mfma_f32_32x32x2_f32: 8 waves per CU, operands by "
+                          "LDS-DMA into a 3-stage ring (+ its fix-up launch where the tile count is split stream-K style)",
+                "flops_note": "achieved = FLOPs the kernel's MFMAs execute for the real problem (2 * planes * Cout * Cin * tiles per launch) / "
+                              "its HIP-event time on the net's stream, summed over its launches of one image",
+                **({"fp32_equivalent_tflops": round(achieved / 3, 2),
+                    "fp32_equivalent_vs_fp32_mfma_peak": round(achieved / 3 / FP32_MFMA_PEAK_TFLOPS, 4)} if args.dtype == "f16x3" else {}),
+                "launches_per_image": len(wino), "avg_launch_us": round(1e3 * g_ms / max(len(wino), 1), 1),
+                "gemm_ms_over_passes": {"min": round(float(min(r[wino, 1].sum() for r in stage_reps)), 4),
+                                        "max": round(float(max(r[wino, 1].sum() for r in stage_reps)), 4), "passes": reps},
+                "executed_gflop_per_image": round(g_flops / 1e9, 2),
+                "layers": [net.layer_names[i] for i in wino],
+                "conv3_5_block": {"layers": ROOFLINE_LAYERS, "ms_per_image": round(blk_ms, 4),
+                                  "executed_tflops": round(blk_exec, 2), "executed_frac": round(blk_exec / peak, 4),
+                                  "algorithmic_equiv_tflops": round(blk_alg, 2),
+                                  "algorithmic_gflop_per_image": round(float(flops[idx].sum()) / 1e9, 2),
+                                  "note": "all kernels of the nine layers (input transform + GEMM + output transform); executed = the MFMA "
+                                          "FLOPs really issued; algorithmic_equiv = the reference's direct-convolution 2*MACs / the same time"},
+                "winograd_stage_ms": {"input_transform": round(float(stage[wino, 0].sum()), 4), "gemm": round(g_ms, 4),
+                                      "output_transform": round(float(stage[wino, 2].sum()), 4)},
+                "all_conv_executed_tflops": round(float(xflops[conv_idx].sum()) / (float(lay_ms[conv_idx].sum()) * 1e-3) / 1e12, 2)}
+            if args.layers:
+                for i, nm in enumerate(net.layer_names):
+                    if lay_ms[i] > 0:
+                        tf = xflops[i] / (lay_ms[i] * 1e-3) / 1e12 if xflops[i] else 0
+                        st = f" [in {stage[i, 0]*1e3:6.1f} gemm {stage[i, 1]*1e3:6.1f} out {stage[i, 2]*1e3:6.1f}]" if stage[i].sum() > 0 and kern[i].startswith("wino") else ""
+                        print(f"{nm:28s} {net.layer_types[i]:14s} {kern[i]:30s} {lay_ms[i]*1e3:9.1f} us {tf:7.1f} TF executed{st}", file=sys.stderr)
         Rm = float(np.mean(main_stats["R"]))
         ss = np.sort(np.array(step_s)) * 1e3
         result = {"metric": f"images/sec {args.model.split('/')[-1]} {args.model.split('/')[0].replace('_', '-')} inference", "value": round(value, 3),
@@ -1022,11 +1057,13 @@ def main():
             # reference's CPU layers at full size: the batch-1 line's parity_ok, tests/test_gpu_net.py; the batched net against the
             # reference itself: test_whole_net_batch_n_vs_reference at reduced sizes)
             result["metric"] += f" (batch {B})"
-            result["roofline"]["flops_note"] += f"; one step = one forward of {B} images"
+            if roofline is not None:
+                result["roofline"]["flops_note"] += f"; one step = one forward of {B} images"
+        if B > 1 and args.full:
             result["batch_parity"] = _batch_parity(net, mnet, zoo, synth, args, host_frames[0], kw, B, local_rank)
             parity_ok = result["batch_parity"]["ok"]
             result["cpu_baseline"] = None      # (the reference's CPU path is timed beside the batch-1 line)
-        if not args.no_cpu_baseline and world == 1 and B == 1:      # rank 0 at N = 1 only (host work; other ranks would idle)
+        if args.full and not args.no_cpu_baseline and world == 1 and B == 1:      # rank 0 at N = 1 only (host work; other ranks would idle)
             table = []
             _set_affinity_all_threads(mask0)    # the reference's CPU path gets every core the process was given, not this rank's slice
             cb = cpu_baseline(args.model, args.regime, max(1, int(round(Rm))), net=net, kw=kw, layer_table=table, dtype=args.dtype,
@@ -1073,13 +1110,14 @@ def main():
             result["alt_precision"] = alt
         if robust:
             result["robustness"] = robust
-        stage_ms = {}
-        for i, nm in enumerate(net.layer_names):
-            t = net.layer_types[i]
-            key = ("trunk_conv" if t == "Convolution" and not nm.startswith(("LFCN_", "roi_c1")) else
-                   "head_conv" if nm.startswith("LFCN_") else nm if nm in ("roi_c1", "fc6") else t)
-            stage_ms[key] = stage_ms.get(key, 0.0) + float(lay_ms[i])
-        result["stage_ms"] = {k: round(v, 3) for k, v in sorted(stage_ms.items(), key=lambda kv: -kv[1]) if v > 0.0005}
+        if lay_ms is not None:      # (from the roofline passes)
+            stage_ms = {}
+            for i, nm in enumerate(net.layer_names):
+                t = net.layer_types[i]
+                key = ("trunk_conv" if t == "Convolution" and not nm.startswith(("LFCN_", "roi_c1")) else
+                       "head_conv" if nm.startswith("LFCN_") else nm if nm in ("roi_c1", "fc6") else t)
+                stage_ms[key] = stage_ms.get(key, 0.0) + float(lay_ms[i])
+            result["stage_ms"] = {k: round(v, 3) for k, v in sorted(stage_ms.items(), key=lambda kv: -kv[1]) if v > 0.0005}
         if parity_ok is False:
             rc = 3
         if result["config"]["handoff"]["status_word_changed"] and result["config"]["handoff"]["events_answered"] == 0:

@@ -7,7 +7,7 @@ the convolution paths on a GPU box -- not collected by pytest:
     MSCNN_WINOGRAD=0 python tests/e2e_margin.py                 # direct implicit GEMM only
 """
 import os, sys
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from mscnn_amd import net as mnet, synth, zoo
 from oracle import pynet

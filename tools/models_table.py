@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""One table row per bench.py JSON line (stdin or files): the per-config summary committed as profiles/rNN_models.txt."""
+"""One table row per `bench.py --full` JSON line (stdin or files): the per-config summary committed as profiles/rNN_models.txt."""
 import json, sys
 rows = []
 for path in sys.argv[1:] or ["/dev/stdin"]:
