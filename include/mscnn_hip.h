@@ -408,6 +408,23 @@ MSCNN_API int mscnn_detections_cascade_fwd(const mscnn_detections_desc* desc, fl
                                  const float* cls_prob, const float* props, int R, double* dets_out, int* ids_out,
                                  int* count_out_dev, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same stage for EVERY (image, class) segment of a batched forward in one pass (three launches per 32 segments, no host
+ * read).  props / bbox_pred / cls_pred hold the ROIs of num_images images, grouped by image with the image index in column 0 of
+ * props (BoxOutput's layout); each segment finds its own rows on the device.  desc[num_images * num_classes], indexed
+ * [image * num_classes + class]: per-segment cls_id, ratios, original size, thresholds (ncls equal in all).  max_rows_per_image:
+ * a host-known bound on any image's rows (BoxOutput's max_nms_num, or R_all), at most 4032 -- above that run mscnn_detections_fwd
+ * per segment.  Every segment is bit-identical to mscnn_detections_fwd on its row range, ids included.
+ * pack_dev (mscnn_detections_multi_pack_bytes(S, cap) bytes, S = num_images * num_classes, cap >= num_classes * R_all):
+ *   [int32 S, R_all, cap, 0][S x int32 {count, rows, row0, 0}][cap x 5 doubles x y w h prob][cap x int32 id]
+ * segment s = (image i, class c) owns pack rows [num_classes * row0 + c * rows, + rows), ids relative to its row0; count -1: the
+ * image had more rows than max_rows_per_image (nothing was run for it).  Every word of the header and table is written by the
+ * kernels; rows of a slot past its count are left as they were. */
+MSCNN_API size_t mscnn_detections_multi_pack_bytes(int num_segments, int cap);
+MSCNN_API size_t mscnn_detections_multi_workspace_bytes(int num_segments, int max_rows_per_image);   /* 0: over 4032 rows */
+MSCNN_API int mscnn_detections_multi_fwd(const mscnn_detections_desc* desc, int num_images, int num_classes, const float* bbox_pred,
+                                         const float* cls_pred, const float* props, int R_all, int max_rows_per_image, void* pack_dev,
+                                         int cap, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Image pre-processing in front of net.forward -- MATLAB `run_mscnn_detection.m:64-69`:
  * imresize(uint8 image, [H W]) (bicubic, uint8 after each 1-D pass), RGB -> BGR, single, subtract the

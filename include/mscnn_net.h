@@ -191,6 +191,25 @@ MSCNN_NET_API int mscnn_net_detect_end(mscnn_net* net, double* dets_host, int* i
  * proposals_score), *num_rois = the image's own ROI count. */
 MSCNN_NET_API int mscnn_net_detect_image(mscnn_net* net, const mscnn_detect_params* p, int image, double* dets_host, int* ids_host,
                                          int cap, int* num_dets, int* num_rois);
+/* The final stage of EVERY image and class of the last forward in one pass: one stream synchronisation per call instead of one per
+ * (image, class), three launches (mscnn_hip.h: mscnn_detections_multi_fwd) instead of three per pair.  p[num_images * num_classes],
+ * indexed [image * num_classes + class]: each image may carry its own ratios and original size.  num_images must equal the input's
+ * N (1 is legal and equals mscnn_net_detect).  Output segment after segment, image-major: seg_dets[s] detections of segment s in
+ * dets_host / ids_host (ids = rows of the net's ROI blobs, as mscnn_net_detect_image), image_rois[num_images] (may be NULL) = each
+ * image's ROI count.  More detections than cap is an error naming the numbers, never a truncation.  Every segment is bit-identical to
+ * mscnn_net_detect_image of its image and class.  A per-image row bound over 4032 (BoxOutput max_nms_num 0) runs the per-segment
+ * path into the same layout. */
+MSCNN_NET_API int mscnn_net_detect_multi(mscnn_net* net, const mscnn_detect_params* p, int num_images, int num_classes, double* dets_host,
+                                         int* ids_host, int cap, int* seg_dets, int* image_rois);
+/* The same into a device pack of mscnn_net_detect_multi_pack_bytes(num_images, num_classes, cap) bytes in HBM (layout: mscnn_hip.h,
+ * mscnn_detections_multi_fwd; cap >= num_classes x the forward's ROI count, else an error); asynchronous on the net's stream, *pack_dev
+ * valid until the next detect call on this net.  mscnn_net_unpack_detections_multi reads one host copy of it (out_cap = rows of
+ * dets_host / ids_host; refuses a pack of another shape or capacity and a corrupt one). */
+MSCNN_NET_API size_t mscnn_net_detect_multi_pack_bytes(int num_images, int num_classes, int cap);
+MSCNN_NET_API int mscnn_net_detect_multi_device(mscnn_net* net, const mscnn_detect_params* p, int num_images, int num_classes, int cap,
+                                                const void** pack_dev);
+MSCNN_NET_API int mscnn_net_unpack_detections_multi(const void* pack_host, int num_images, int num_classes, int cap, double* dets_host,
+                                                    int* ids_host, int out_cap, int* seg_dets, int* image_rois);
 
 
 /* Final stage of the cascade drivers (examples/kitti_car/run_cascademscnn.m:84-127) for ONE cascade output nn: the decoded boxes

@@ -93,11 +93,11 @@ __device__ __forceinline__ u64 det_key(float prob, int r) {
   return ((u64)orderable(prob) << 32) | (u64)(0xffffffffu - (unsigned)r);
 }
 
-// One workgroup: per-row transform + filter, key sort, write sorted boxes.
-__global__ __launch_bounds__(kSortThreads) void det_transform_sort_kernel(DetArgs a, DetBox* __restrict__ sbox,
-                                                                          double* __restrict__ sprob, int* __restrict__ ssrc,
-                                                                          DetBox* __restrict__ tmp_box,
-                                                                          float* __restrict__ tmp_prob, int* __restrict__ cnt) {
+// Per-row transform + filter, key sort, write sorted boxes: the body of one workgroup (kSortThreads threads).  *n_out = survivors.
+// (shared by det_transform_sort_kernel and the segmented det_multi_transform_sort_kernel: one code path, the same bits)
+__device__ __forceinline__ void det_transform_sort(const DetArgs& a, DetBox* __restrict__ sbox, double* __restrict__ sprob,
+                                                   int* __restrict__ ssrc, DetBox* __restrict__ tmp_box, float* __restrict__ tmp_prob,
+                                                   int* __restrict__ n_out) {
   __shared__ u64 sk[kSortCap];
   __shared__ int s_fill;
   const int tid = threadIdx.x;
@@ -114,7 +114,7 @@ __global__ __launch_bounds__(kSortThreads) void det_transform_sort_kernel(DetArg
   }
   __syncthreads();
   const int n = min(s_fill, kMaxK);
-  if (tid == 0) cnt[DC_N] = n;
+  if (tid == 0) *n_out = n;
   if (n == 0) return;
   int P = 1;
   while (P < n) P <<= 1;
@@ -127,6 +127,14 @@ __global__ __launch_bounds__(kSortThreads) void det_transform_sort_kernel(DetArg
     sprob[i] = (double)tmp_prob[r];
     ssrc[i] = r;
   }
+}
+
+// One workgroup: the whole list.
+__global__ __launch_bounds__(kSortThreads) void det_transform_sort_kernel(DetArgs a, DetBox* __restrict__ sbox,
+                                                                          double* __restrict__ sprob, int* __restrict__ ssrc,
+                                                                          DetBox* __restrict__ tmp_box,
+                                                                          float* __restrict__ tmp_prob, int* __restrict__ cnt) {
+  det_transform_sort(a, sbox, sprob, ssrc, tmp_box, tmp_prob, cnt + DC_N);
 }
 
 // ---- more than kMaxK rows (nms_large.h): the same three steps over HBM-resident lists -------------------------------------------
@@ -187,11 +195,10 @@ __global__ __launch_bounds__(256) void det_emit_big_kernel(const int* __restrict
   if (ids) ids[row] = ssrc[k];
 }
 
+// One 64 x 64 block (rb, cb) of the upper-triangular bit matrix over n sorted boxes.
 // (256 threads per 64 x 64 block, the four waves split the columns -- as nms_mask_kernel of boxoutput.hip)
-__global__ __launch_bounds__(256) void det_mask_kernel(const DetBox* __restrict__ boxes, const int* __restrict__ cnt,
-                                                       double overlap, u64* __restrict__ mask, int wpr) {
-  const int n = cnt[DC_N];
-  const int rb = blockIdx.y, cb = blockIdx.x;
+__device__ __forceinline__ void det_mask_block(const DetBox* __restrict__ boxes, int n, double overlap, u64* __restrict__ mask, int wpr,
+                                               int rb, int cb) {
   if (cb < rb || rb * 64 >= n || cb * 64 >= n) return;
   __shared__ DetBox cbox[64];
   __shared__ unsigned part[4][64];
@@ -224,16 +231,19 @@ __global__ __launch_bounds__(256) void det_mask_kernel(const DetBox* __restrict_
     mask[(size_t)i * wpr + cb] = (u64)part[0][t] | ((u64)part[1][t] << 16) | ((u64)part[2][t] << 32) | ((u64)part[3][t] << 48);
 }
 
-__global__ __launch_bounds__(256) void det_scan_emit_kernel(const u64* __restrict__ mask, int wpr,
-                                                            const DetBox* __restrict__ sbox, const double* __restrict__ sprob,
-                                                            const int* __restrict__ ssrc, double* __restrict__ dets,
-                                                            int* __restrict__ ids, const int* __restrict__ cnt,
-                                                            int* __restrict__ count_out) {
-  extern __shared__ __attribute__((aligned(16))) u64 dyn_lds[];
+__global__ __launch_bounds__(256) void det_mask_kernel(const DetBox* __restrict__ boxes, const int* __restrict__ cnt,
+                                                       double overlap, u64* __restrict__ mask, int wpr) {
+  det_mask_block(boxes, cnt[DC_N], overlap, mask, wpr, blockIdx.y, blockIdx.x);
+}
+
+// Greedy scan + emit of n sorted boxes by one 256-thread workgroup: kept box number k lands in dets[k] / ids[k], the count in
+// *count_out.  dyn_lds: 2 * 64 * wpr u64.
+__device__ __forceinline__ void det_scan_emit(const u64* __restrict__ mask, int wpr, int n, const DetBox* __restrict__ sbox,
+                                              const double* __restrict__ sprob, const int* __restrict__ ssrc, double* __restrict__ dets,
+                                              int* __restrict__ ids, int* __restrict__ count_out, u64* dyn_lds) {
   __shared__ u64 keepw[64];
   __shared__ int pre[64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int n = cnt[DC_N];
   if (n <= 0) { if (tid == 0) count_out[0] = 0; return; }
   const u64 mykeep = greedy_scan(mask, n, wpr, wpr, dyn_lds);
   if (wave == 0) {
@@ -258,6 +268,109 @@ __global__ __launch_bounds__(256) void det_scan_emit_kernel(const u64* __restric
     d[0] = b.x; d[1] = b.y; d[2] = b.w; d[3] = b.h; d[4] = sprob[k];
     if (ids) ids[row] = ssrc[k];
   }
+}
+
+__global__ __launch_bounds__(256) void det_scan_emit_kernel(const u64* __restrict__ mask, int wpr,
+                                                            const DetBox* __restrict__ sbox, const double* __restrict__ sprob,
+                                                            const int* __restrict__ ssrc, double* __restrict__ dets,
+                                                            int* __restrict__ ids, const int* __restrict__ cnt,
+                                                            int* __restrict__ count_out) {
+  extern __shared__ __attribute__((aligned(16))) u64 dyn_lds[];
+  det_scan_emit(mask, wpr, cnt[DC_N], sbox, sprob, ssrc, dets, ids, count_out, dyn_lds);
+}
+
+// ---- every (image, class) segment of a batched forward in one pass (mscnn_detections_multi_fwd) -------------------------------------
+// Segment s = image s / C, class slot s % C (image-major).  The ROI rows are grouped by image with the image index in column 0 of
+// props (box_output_layer.cpp:107, :156): each segment finds its [row0, row0 + rows) by binary search on the device and runs the
+// single-list path's three bodies above on that range, in a workspace slice of its own (max_rows rows).  Its detections go to pack
+// rows [C row0 + c rows, + rows): a slot it places without knowing any other segment; all slots tile [0, C R_all).
+constexpr int kSegsPerLaunch = 32;         // segment parameters travel as kernel arguments (2.1 KB of the 4 KB)
+struct DetSeg { float mean[4], stdv[4]; float proposal_thr, ratio_h, ratio_w, org_h, org_w; int cls_id; double nms_overlap; };
+struct DetMultiArgs {
+  const float* bbox_pred; const float* cls_pred; const float* props;
+  int R_all, ncls, num_classes, max_rows, wpr, cap, num_segs, s0;       // s0: first segment of this launch
+  char* ws; size_t seg_stride_box, seg_stride_mask;                     // workspace: per-segment slices (det_multi_layout)
+  int* hdr;                                                             // pack: header, table, dets, ids
+  double* dets; int* ids;
+  DetSeg seg[kSegsPerLaunch];
+};
+enum { SEG_N = 0, SEG_ROW0 = 1, SEG_ROWS = 2, SEG_BAD = 3, SEG_WORDS = 4 };   // workspace words per segment
+enum { PACK_HDR_WORDS = 4, PACK_SEG_WORDS = 4 };                              // {S, R_all, cap, 0}, {count, rows, row0, 0}
+
+struct DetMultiPtrs { int* cnt; DetBox* sbox; double* sprob; int* ssrc; DetBox* tbox; float* tprob; u64* mask; };
+__device__ __forceinline__ DetMultiPtrs det_multi_ptrs(const DetMultiArgs& a, int s) {
+  // slices: [cnt: S x SEG_WORDS ints][sbox][sprob][ssrc][tbox][tprob] per segment (max_rows each, 256-byte aligned), then the masks
+  const size_t M = (size_t)a.max_rows;
+  char* base = a.ws + 256 * (((size_t)a.num_segs * SEG_WORDS * sizeof(int) + 255) / 256) + (size_t)s * a.seg_stride_box;
+  DetMultiPtrs p;
+  p.cnt = reinterpret_cast<int*>(a.ws) + (size_t)s * SEG_WORDS;
+  const size_t a32 = (M * sizeof(DetBox) + 255) / 256 * 256, a8 = (M * sizeof(double) + 255) / 256 * 256,
+               a4 = (M * sizeof(int) + 255) / 256 * 256;
+  p.sbox = reinterpret_cast<DetBox*>(base);
+  p.sprob = reinterpret_cast<double*>(base + a32);
+  p.ssrc = reinterpret_cast<int*>(base + a32 + a8);
+  p.tbox = reinterpret_cast<DetBox*>(base + a32 + a8 + a4);
+  p.tprob = reinterpret_cast<float*>(base + 2 * a32 + a8 + a4);
+  p.mask = reinterpret_cast<u64*>(a.ws + 256 * (((size_t)a.num_segs * SEG_WORDS * sizeof(int) + 255) / 256) +
+                                  (size_t)a.num_segs * a.seg_stride_box + (size_t)s * a.seg_stride_mask);
+  return p;
+}
+
+// first row whose image (column 0) is >= img, over [0, R): rows are grouped by image in ascending order
+__device__ __forceinline__ int det_image_lower_bound(const float* __restrict__ props, int R, int img) {
+  int lo = 0, hi = R;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (props[(size_t)mid * 6] < (float)img) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// one workgroup per segment: find the rows, transform + filter + sort them
+__global__ __launch_bounds__(kSortThreads) void det_multi_transform_sort_kernel(DetMultiArgs a) {
+  const int j = blockIdx.x, s = a.s0 + j;
+  const int img = s / a.num_classes;
+  const DetMultiPtrs p = det_multi_ptrs(a, s);
+  __shared__ int s_range[2];
+  if (threadIdx.x < 2) s_range[threadIdx.x] = det_image_lower_bound(a.props, a.R_all, img + threadIdx.x);
+  if (s == 0 && threadIdx.x == 0) {
+    a.hdr[0] = a.num_segs; a.hdr[1] = a.R_all; a.hdr[2] = a.cap; a.hdr[3] = 0;
+  }
+  __syncthreads();
+  const int row0 = s_range[0], rows = s_range[1] - s_range[0];
+  // (more rows than the host-side bound the workspace is sized by: nothing is run, the table says so and the unpacker refuses it)
+  const bool bad = rows > a.max_rows;
+  if (threadIdx.x == 0) { p.cnt[SEG_ROW0] = row0; p.cnt[SEG_ROWS] = rows; p.cnt[SEG_BAD] = bad ? 1 : 0; }
+  if (bad) { if (threadIdx.x == 0) p.cnt[SEG_N] = 0; return; }
+  const DetSeg& g = a.seg[j];
+  DetArgs d;
+  d.bbox_pred = a.bbox_pred + (size_t)row0 * 4 * a.ncls; d.cls_pred = a.cls_pred + (size_t)row0 * a.ncls; d.props = a.props + (size_t)row0 * 6;
+  d.R = rows; d.ncls = a.ncls; d.cls_id = g.cls_id;
+  for (int k = 0; k < 4; ++k) { d.mean[k] = g.mean[k]; d.stdv[k] = g.stdv[k]; }
+  d.proposal_thr = g.proposal_thr; d.ratio_h = g.ratio_h; d.ratio_w = g.ratio_w; d.org_h = g.org_h; d.org_w = g.org_w;
+  d.cascade = 0;
+  det_transform_sort(d, p.sbox, p.sprob, p.ssrc, p.tbox, p.tprob, p.cnt + SEG_N);
+}
+
+// grid (wpr, wpr, segments): blocks past a segment's own n exit at once
+__global__ __launch_bounds__(256) void det_multi_mask_kernel(DetMultiArgs a) {
+  const int j = blockIdx.z, s = a.s0 + j;
+  const DetMultiPtrs p = det_multi_ptrs(a, s);
+  det_mask_block(p.sbox, p.cnt[SEG_N], a.seg[j].nms_overlap, p.mask, a.wpr, blockIdx.y, blockIdx.x);
+}
+
+// one workgroup per segment: greedy scan, emit into the segment's slot, its table entry {count (-1: rows over the bound), rows, row0, 0}
+__global__ __launch_bounds__(256) void det_multi_scan_emit_kernel(DetMultiArgs a) {
+  extern __shared__ __attribute__((aligned(16))) u64 dyn_lds[];
+  const int j = blockIdx.x, s = a.s0 + j;
+  const int c = s % a.num_classes;
+  const DetMultiPtrs p = det_multi_ptrs(a, s);
+  const int row0 = p.cnt[SEG_ROW0], rows = p.cnt[SEG_ROWS];
+  int* ent = a.hdr + PACK_HDR_WORDS + (size_t)s * PACK_SEG_WORDS;
+  if (threadIdx.x == 0) { ent[1] = rows; ent[2] = row0; ent[3] = 0; }
+  if (p.cnt[SEG_BAD]) { if (threadIdx.x == 0) ent[0] = -1; return; }
+  const size_t slot = (size_t)a.num_classes * row0 + (size_t)c * rows;
+  det_scan_emit(p.mask, a.wpr, p.cnt[SEG_N], p.sbox, p.sprob, p.ssrc, a.dets + 5 * slot, a.ids + slot, ent, dyn_lds);
 }
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -380,4 +493,80 @@ extern "C" int mscnn_detections_cascade_fwd(const mscnn_detections_desc* desc, f
                                             int* count_out_dev, void* workspace, size_t workspace_bytes, void* stream) {
   return detections_launch(desc, 1, det_thr, boxes, cls_prob, props, R, dets_out, ids_out, count_out_dev, workspace,
                            workspace_bytes, stream);
+}
+
+// ---- all (image, class) segments in one pass -----------------------------------------------------------------------------------------
+static size_t det_multi_seg_box_bytes(int M) {
+  const size_t m = (size_t)(M < 1 ? 1 : M);
+  return 2 * align_up(m * sizeof(DetBox), 256) + align_up(m * sizeof(double), 256) + align_up(m * sizeof(int), 256) +
+         align_up(m * sizeof(float), 256);
+}
+static size_t det_multi_seg_mask_bytes(int M) {
+  const size_t m = (size_t)(M < 1 ? 1 : M);
+  return align_up(m * (size_t)((m + 63) / 64) * sizeof(u64), 256);
+}
+
+extern "C" size_t mscnn_detections_multi_pack_bytes(int num_segments, int cap) {
+  const size_t S = (size_t)(num_segments > 0 ? num_segments : 0), rows = (size_t)(cap > 0 ? cap : 1);
+  return (sizeof(int) * (PACK_HDR_WORDS + PACK_SEG_WORDS * S) + rows * (5 * sizeof(double) + sizeof(int)) + 15) / 16 * 16;
+}
+
+extern "C" size_t mscnn_detections_multi_workspace_bytes(int num_segments, int max_rows_per_image) {
+  if (num_segments < 1 || max_rows_per_image > kMaxK) return 0;
+  const int M = max_rows_per_image < 1 ? 1 : max_rows_per_image;
+  return align_up((size_t)num_segments * SEG_WORDS * sizeof(int), 256) +
+         (size_t)num_segments * (det_multi_seg_box_bytes(M) + det_multi_seg_mask_bytes(M));
+}
+
+extern "C" int mscnn_detections_multi_fwd(const mscnn_detections_desc* desc, int num_images, int num_classes, const float* bbox_pred,
+                                          const float* cls_pred, const float* props, int R_all, int max_rows_per_image, void* pack_dev,
+                                          int cap, void* workspace, size_t workspace_bytes, void* stream) {
+  MSCNN_REQUIRE(desc && pack_dev && workspace, "detections_multi: null pointer");
+  MSCNN_REQUIRE(num_images >= 1 && num_classes >= 1, "detections_multi: %d images x %d classes", num_images, num_classes);
+  MSCNN_REQUIRE(R_all >= 1 && bbox_pred && cls_pred && props, "detections_multi: R_all = %d (BoxOutput emits at least one row)", R_all);
+  MSCNN_REQUIRE(max_rows_per_image >= 1 && max_rows_per_image <= kMaxK,
+                "detections_multi: %d rows per image > %d: run mscnn_detections_fwd per segment", max_rows_per_image, kMaxK);
+  MSCNN_REQUIRE((long)num_classes * R_all <= (long)cap, "detections_multi: pack capacity %d < %d classes x %d ROIs", cap, num_classes,
+                R_all);
+  const int S = num_images * num_classes;
+  const int ncls = desc[0].ncls;
+  for (int s = 0; s < S; ++s)
+    MSCNN_REQUIRE(desc[s].ncls == ncls && desc[s].cls_id >= 1 && desc[s].cls_id <= ncls && ncls >= 2,
+                  "detections_multi: segment %d: cls_id %d of %d", s, desc[s].cls_id, desc[s].ncls);
+  const size_t need = mscnn_detections_multi_workspace_bytes(S, max_rows_per_image);
+  if (workspace_bytes < need) {
+    set_error("detections_multi: workspace %zu < %zu", workspace_bytes, need);
+    return MSCNN_ERR_WORKSPACE;
+  }
+  hipStream_t st = as_stream(stream);
+  const int M = max_rows_per_image;
+  DetMultiArgs a;
+  a.bbox_pred = bbox_pred; a.cls_pred = cls_pred; a.props = props;
+  a.R_all = R_all; a.ncls = ncls; a.num_classes = num_classes; a.max_rows = M; a.wpr = (M + 63) / 64; a.cap = cap; a.num_segs = S;
+  a.ws = static_cast<char*>(workspace);
+  a.seg_stride_box = det_multi_seg_box_bytes(M); a.seg_stride_mask = det_multi_seg_mask_bytes(M);
+  char* pk = static_cast<char*>(pack_dev);
+  a.hdr = reinterpret_cast<int*>(pk);
+  const size_t rows = (size_t)(cap > 0 ? cap : 1), table = sizeof(int) * (PACK_HDR_WORDS + PACK_SEG_WORDS * (size_t)S);
+  a.dets = reinterpret_cast<double*>(pk + table);
+  a.ids = reinterpret_cast<int*>(pk + table + sizeof(double) * 5 * rows);
+  for (int s0 = 0; s0 < S; s0 += kSegsPerLaunch) {
+    const int ns = S - s0 < kSegsPerLaunch ? S - s0 : kSegsPerLaunch;
+    a.s0 = s0;
+    for (int j = 0; j < ns; ++j) {
+      const mscnn_detections_desc& d = desc[s0 + j];
+      DetSeg& g = a.seg[j];
+      for (int k = 0; k < 4; ++k) { g.mean[k] = d.bbox_mean[k]; g.stdv[k] = d.bbox_std[k]; }
+      g.proposal_thr = d.proposal_thr; g.cls_id = d.cls_id; g.nms_overlap = d.nms_overlap;
+      // MATLAB: single op double -> single (as detections_launch)
+      g.ratio_h = (float)d.ratio_h; g.ratio_w = (float)d.ratio_w; g.org_h = (float)d.org_h; g.org_w = (float)d.org_w;
+    }
+    det_multi_transform_sort_kernel<<<ns, kSortThreads, 0, st>>>(a);
+    MSCNN_POST_LAUNCH();
+    det_multi_mask_kernel<<<dim3(a.wpr, a.wpr, ns), 256, 0, st>>>(a);
+    MSCNN_POST_LAUNCH();
+    det_multi_scan_emit_kernel<<<ns, 256, (size_t)2 * 64 * a.wpr * sizeof(u64), st>>>(a);
+    MSCNN_POST_LAUNCH();
+  }
+  return MSCNN_OK;
 }

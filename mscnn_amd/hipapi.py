@@ -7,6 +7,7 @@ There is no CPU fallback: a missing library or a host tensor raises.
 import ctypes as C
 import os
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -150,6 +151,12 @@ def lib():
         L.mscnn_detections_workspace_bytes.restype = C.c_size_t
         L.mscnn_detections_workspace_bytes.argtypes = [C.c_int]
         L.mscnn_detections_fwd.argtypes = [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]
+        L.mscnn_detections_multi_pack_bytes.restype = C.c_size_t
+        L.mscnn_detections_multi_pack_bytes.argtypes = [C.c_int, C.c_int]
+        L.mscnn_detections_multi_workspace_bytes.restype = C.c_size_t
+        L.mscnn_detections_multi_workspace_bytes.argtypes = [C.c_int, C.c_int]
+        L.mscnn_detections_multi_fwd.argtypes = ([C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                                 C.c_void_p, C.c_size_t, C.c_void_p])
         _lib = L
     return _lib
 
@@ -628,6 +635,50 @@ def detections(bbox_pred, cls_pred, props, cls_id, bbox_mean=(0, 0, 0, 0), bbox_
                                       _dev(count), _dev(ws), wb, _stream()))
     D = int(count.item())
     return dets[:D], ids[:D]
+
+
+def detections_multi(bbox_pred, cls_pred, props, num_images, segments, max_rows_per_image=None):
+    """Every (image, class) segment in one pass (mscnn_detections_multi_fwd).  props: ROI rows grouped by image, image index in
+    column 0; segments: num_images * C dicts of detections() keyword arguments (cls_id, ratios, org_hw, ...), image-major.
+    Returns [(dets[D,5], ids relative to row0, row0, rows)] per segment."""
+    R = props.shape[0]
+    S = len(segments)
+    Cn = S // num_images
+    if Cn * num_images != S:
+        raise MscnnError(f"detections_multi: {S} segments for {num_images} images")
+    descs = (DetectionsDesc * S)()
+    for s, kw in enumerate(segments):
+        kw = dict(dict(bbox_mean=(0, 0, 0, 0), bbox_std=(0.1, 0.1, 0.2, 0.2), proposal_thr=-10.0, ratios=(1.0, 1.0), org_hw=(375, 1242),
+                       nms_overlap=0.5), **kw)
+        d = descs[s]
+        d.ncls = cls_pred.shape[1]; d.cls_id = kw["cls_id"]
+        for k in range(4):
+            d.bbox_mean[k] = kw["bbox_mean"][k]; d.bbox_std[k] = kw["bbox_std"][k]
+        d.proposal_thr = kw["proposal_thr"]
+        d.ratio_h, d.ratio_w = kw["ratios"]
+        d.org_h, d.org_w = kw["org_hw"]
+        d.nms_overlap = kw["nms_overlap"]
+    M = R if max_rows_per_image is None else max_rows_per_image
+    cap = Cn * R
+    dev = props.device
+    pack = torch.zeros(lib().mscnn_detections_multi_pack_bytes(S, cap), dtype=torch.uint8, device=dev)
+    wb = lib().mscnn_detections_multi_workspace_bytes(S, M)
+    ws = torch.empty(max(wb, 1), dtype=torch.uint8, device=dev)
+    _check(lib().mscnn_detections_multi_fwd(descs, num_images, Cn, _dev(bbox_pred), _dev(cls_pred), _dev(props), R, M, _dev(pack), cap,
+                                            _dev(ws), C.c_size_t(wb), _stream()))
+    h = pack.cpu().numpy()
+    hdr = h[:16 * (S + 1)].view(np.int32).reshape(S + 1, 4)
+    if list(hdr[0]) != [S, R, cap, 0]:
+        raise MscnnError(f"detections_multi: pack header {hdr[0].tolist()}")
+    table = 16 * (S + 1)
+    dets = h[table:table + 40 * max(cap, 1)].view(np.float64).reshape(-1, 5)
+    ids = h[table + 40 * max(cap, 1):table + 44 * max(cap, 1)].view(np.int32)
+    out = []
+    for s in range(S):
+        cnt, rows, row0, _ = (int(v) for v in hdr[1 + s])
+        slot = Cn * row0 + (s % Cn) * rows
+        out.append((dets[slot:slot + max(cnt, 0)].copy(), ids[slot:slot + max(cnt, 0)].copy(), row0, rows) if cnt >= 0 else (None, None, row0, rows))
+    return out
 
 
 # ---- health of the plane-GEMM kernel's stream-K hand-off (mscnn_hip.h) ----

@@ -450,6 +450,7 @@ class BoxOutputLayer : public Layer<Dtype> {
   virtual inline int MinTopBlobs() const { return 1; }
   virtual inline int MaxTopBlobs() const { return 2; }
   int last_num_rois() const { return last_rows_; }
+  int max_rows() const { return cap_; }      // row bound of the tops in the last forward: per-image bound x images (0 before it)
   // (round 6) Work that does not depend on the row count, enqueued between BoxOutput's kernels and the host's wait for {R, real rows}:
   // the device runs it while the host takes R, reshapes the tops and launches what follows -- the frame's one host round trip no
   // longer idles the GPU.  The Net puts the sliding-maximum maps of the fused ROI pooling there (they depend on conv4_3 only).

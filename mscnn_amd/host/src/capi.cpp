@@ -2,6 +2,7 @@
 // CHECK-failure exception of this build) and returns it as an error string instead of aborting the host process.
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -592,6 +593,179 @@ int mscnn_net_detect_image(mscnn_net* n, const mscnn_detect_params* p, int image
     }
     *num_dets = Dd;
     if (num_rois) *num_rois = R;
+  });
+}
+
+// ---- every (image, class) segment of the last forward in one pass ------------------------------------------------------------------
+// Bound on any image's ROI rows, known on the host: the row bound of the BoxOutput layer that wrote proposals_score (its max_nms_num /
+// max_post_nms_num, or its anchor count), per image.  Without such a layer: all rows.
+static int per_image_row_bound(mscnn_net* n, int num_images, int R_all) {
+  const auto& layers = n->net->layers();
+  const Blob<float>* props = n->net->blob_by_name("proposals_score").get();
+  for (size_t l = 0; l < layers.size(); ++l) {
+    auto* bo = dynamic_cast<caffe::BoxOutputLayer<float>*>(layers[l].get());
+    const auto& tops = n->net->top_vecs()[l];
+    if (bo && tops.size() == 2 && tops[1] == props && bo->max_rows() > 0)
+      return std::min(R_all, std::max(1, bo->max_rows() / num_images));
+  }
+  return R_all;
+}
+
+// The multi pack of the last forward (mscnn_hip.h: mscnn_detections_multi_fwd) with cap rows, at pack_at (device-addressable) or in
+// the net's device pack.  Returns false when it went to the device pack instead: a per-image bound over 4032 rows (max_nms_num 0)
+// runs the existing per-segment path -- the tiled kernels of nms_large.h -- image_rows' host read included, into the same layout.
+static bool detect_multi_into_pack(mscnn_net* n, const mscnn_detect_params* p, int num_images, int num_classes, int cap, char* pack_at,
+                                   char** pack_out) {
+  CHECK(p != nullptr);
+  CHECK(num_images >= 1 && num_classes >= 1) << num_images << " images x " << num_classes << " classes";
+  CHECK(n->net->has_blob("bbox_pred") && n->net->has_blob("cls_pred") && n->net->has_blob("proposals_score"))
+      << "net has no bbox_pred / cls_pred / proposals_score outputs";
+  const int num = n->net->num_inputs() > 0 && n->net->input_blobs()[0]->num_axes() == 4 ? n->net->input_blobs()[0]->num() : 1;
+  CHECK_EQ(num_images, num) << "detect_multi: num_images " << num_images << " but the net's input holds " << num << " images";
+  auto bbox = n->net->blob_by_name("bbox_pred");
+  auto cls = n->net->blob_by_name("cls_pred");
+  auto props = n->net->blob_by_name("proposals_score");
+  const int R_all = props->num();
+  CHECK_EQ(bbox->num(), R_all);
+  CHECK_EQ(cls->num(), R_all);
+  CHECK_GE(R_all, 1);
+  const int ncls = cls->count() / R_all;
+  CHECK_EQ(bbox->count() / R_all, 4 * ncls);
+  CHECK_GE((long)cap, (long)num_classes * R_all) << "detection pack capacity " << cap << " < " << num_classes << " classes x " << R_all
+                                                  << " ROIs (size it by BoxOutput's max_nms_num x images x classes)";
+  const int S = num_images * num_classes;
+  std::vector<mscnn_detections_desc> desc(S);
+  for (int s = 0; s < S; ++s) {
+    mscnn_detections_desc& d = desc[s];
+    d.ncls = ncls;
+    d.cls_id = p[s].cls_id;
+    CHECK(d.cls_id >= 1 && d.cls_id <= ncls) << "segment " << s << ": cls_id " << d.cls_id << " of " << ncls;
+    for (int k = 0; k < 4; ++k) { d.bbox_mean[k] = p[s].bbox_mean[k]; d.bbox_std[k] = p[s].bbox_std[k]; }
+    d.proposal_thr = p[s].proposal_thr;
+    d.ratio_h = p[s].ratio_h; d.ratio_w = p[s].ratio_w; d.org_h = p[s].org_h; d.org_w = p[s].org_w; d.nms_overlap = p[s].nms_overlap;
+  }
+  hipStream_t st = (hipStream_t)Caffe::stream();
+  const size_t total = mscnn_detections_multi_pack_bytes(S, cap);
+  const int bound = per_image_row_bound(n, num_images, R_all);
+  if (bound <= 4032) {
+    const size_t wb = mscnn_detections_multi_workspace_bytes(S, bound);
+    void* ws = n->det_ws.Reserve(wb);
+    char* pack = pack_at ? pack_at : static_cast<char*>(n->det_pack.Reserve(total));
+    MSCNN_CHECK(mscnn_detections_multi_fwd(desc.data(), num_images, num_classes, bbox->gpu_data(), cls->gpu_data(), props->gpu_data(),
+                                           R_all, bound, pack, cap, ws, wb, st));
+    *pack_out = pack;
+    return pack == pack_at;
+  }
+  char* pack = static_cast<char*>(n->det_pack.Reserve(total));
+  int* hdr = reinterpret_cast<int*>(pack);
+  const size_t rows_cap = (size_t)(cap > 0 ? cap : 1), table = sizeof(int) * (4 + 4 * (size_t)S);
+  double* dets = reinterpret_cast<double*>(pack + table);
+  int* ids = reinterpret_cast<int*>(pack + table + sizeof(double) * 5 * rows_cap);
+  std::vector<int> row0(num_images), rows(num_images);
+  int max_rows = 0;
+  for (int i = 0; i < num_images; ++i) {
+    image_rows(n, i, &row0[i], &rows[i]);
+    max_rows = std::max(max_rows, rows[i]);
+  }
+  const size_t wb = mscnn_detections_workspace_bytes(max_rows);
+  void* ws = n->det_ws.Reserve(wb);
+  const int words[4] = {S, R_all, cap, 0};
+  MSCNN_CHECK(mscnn_store_words_i32(hdr, words, 4, st));
+  for (int s = 0; s < S; ++s) {
+    const int i = s / num_classes, c = s % num_classes;
+    const size_t slot = (size_t)num_classes * row0[i] + (size_t)c * rows[i];
+    int* ent = hdr + 4 + 4 * (size_t)s;
+    const int e[3] = {rows[i], row0[i], 0};
+    MSCNN_CHECK(mscnn_store_words_i32(ent + 1, e, 3, st));
+    MSCNN_CHECK(mscnn_detections_fwd(&desc[s], bbox->gpu_data() + (size_t)row0[i] * 4 * ncls, cls->gpu_data() + (size_t)row0[i] * ncls,
+                                     props->gpu_data() + (size_t)row0[i] * 6, rows[i], dets + 5 * slot, ids + slot, ent, ws, wb, st));
+  }
+  *pack_out = pack;
+  return false;
+}
+
+size_t mscnn_net_detect_multi_pack_bytes(int num_images, int num_classes, int cap) {
+  return mscnn_detections_multi_pack_bytes(num_images * num_classes, cap);
+}
+
+int mscnn_net_detect_multi_device(mscnn_net* n, const mscnn_detect_params* p, int num_images, int num_classes, int cap,
+                                  const void** pack_dev) {
+  return guarded([&] {
+    CHECK(pack_dev != nullptr);
+    char* pack = nullptr;
+    detect_multi_into_pack(n, p, num_images, num_classes, cap, nullptr, &pack);
+    *pack_dev = pack;
+  });
+}
+
+int mscnn_net_unpack_detections_multi(const void* pack_host, int num_images, int num_classes, int cap, double* dets_host, int* ids_host,
+                                      int out_cap, int* seg_dets, int* image_rois) {
+  return guarded([&] {
+    CHECK(pack_host && seg_dets) << "unpack_detections_multi: null pointer";
+    CHECK(num_images >= 1 && num_classes >= 1) << num_images << " images x " << num_classes << " classes";
+    const int S = num_images * num_classes;
+    const char* hp = static_cast<const char*>(pack_host);
+    const int* hdr = reinterpret_cast<const int*>(hp);
+    CHECK_EQ(hdr[0], S) << "detection pack was written for another number of segments";
+    CHECK_EQ(hdr[2], cap) << "detection pack was written for another capacity";
+    const int R_all = hdr[1];
+    CHECK(R_all >= 0 && (long)num_classes * R_all <= (long)cap && hdr[3] == 0)
+        << "corrupt detection pack header: " << R_all << " ROIs, capacity " << cap;
+    long D = 0;
+    for (int s = 0; s < S; ++s) {
+      const int* e = hdr + 4 + 4 * (size_t)s;
+      const int i = s / num_classes;
+      CHECK(e[0] != -1) << "image " << i << " has " << e[1] << " ROIs, more than the per-image row bound the stage was sized by";
+      CHECK(e[0] >= 0 && e[0] <= e[1] && e[2] >= 0 && (long)e[2] + e[1] <= R_all && e[3] == 0)
+          << "corrupt detection pack: segment " << s << " has " << e[0] << " detections, rows [" << e[2] << ", +" << e[1] << ") of " << R_all;
+      const int* e0 = hdr + 4 + 4 * (size_t)(i * num_classes);
+      CHECK(e[1] == e0[1] && e[2] == e0[2]) << "corrupt detection pack: the segments of image " << i << " disagree on its rows";
+      D += e[0];
+    }
+    CHECK_LE(D, (long)out_cap) << "detections buffer holds " << out_cap << " rows, the " << S << " segments have " << D;
+    CHECK(D == 0 || dets_host) << "unpack_detections_multi: null dets buffer";
+    const size_t rows_cap = (size_t)(cap > 0 ? cap : 1), table = sizeof(int) * (4 + 4 * (size_t)S);
+    const double* pd = reinterpret_cast<const double*>(hp + table);
+    const int* pi = reinterpret_cast<const int*>(hp + table + sizeof(double) * 5 * rows_cap);
+    size_t o = 0;
+    for (int s = 0; s < S; ++s) {
+      const int* e = hdr + 4 + 4 * (size_t)s;
+      const int c = s % num_classes, cnt = e[0], rows = e[1], row0 = e[2];
+      const size_t slot = (size_t)num_classes * row0 + (size_t)c * rows;
+      if (cnt > 0) std::memcpy(dets_host + 5 * o, pd + 5 * slot, sizeof(double) * 5 * cnt);
+      if (cnt > 0 && ids_host)
+        for (int k = 0; k < cnt; ++k) ids_host[o + k] = pi[slot + k] + row0;      // rows of the net's ROI blobs, as detect_image
+      seg_dets[s] = cnt;
+      if (image_rois && c == 0) image_rois[s / num_classes] = rows;
+      o += cnt;
+    }
+  });
+}
+
+int mscnn_net_detect_multi(mscnn_net* n, const mscnn_detect_params* p, int num_images, int num_classes, double* dets_host, int* ids_host,
+                           int cap, int* seg_dets, int* image_rois) {
+  return guarded([&] {
+    CHECK(p && seg_dets) << "detect_multi: null pointer";
+    CHECK(num_images >= 1 && num_classes >= 1) << num_images << " images x " << num_classes << " classes";
+    // as mscnn_net_detect: the kernels write the pack straight into host-coherent pinned memory, one stream synchronisation, no copy;
+    // the per-segment fallback (a per-image bound over 4032 rows) leaves it in the device pack and copies it
+    hipStream_t st = (hipStream_t)Caffe::stream();
+    int pcap = 0;
+    auto run = [&]() {
+      CHECK(n->net->has_blob("proposals_score")) << "net has no proposals_score output";
+      pcap = num_classes * n->net->blob_by_name("proposals_score")->num();
+      const size_t total = mscnn_detections_multi_pack_bytes(num_images * num_classes, pcap);
+      ensure_det_host(n, total);
+      char* pack = nullptr;
+      if (!detect_multi_into_pack(n, p, num_images, num_classes, pcap, static_cast<char*>(n->det_host_dev), &pack))
+        HIP_CHECK(hipMemcpyAsync(n->det_host, pack, total, hipMemcpyDeviceToHost, st));
+      HIP_CHECK(hipStreamSynchronize(st));
+    };
+    run();
+    if (n->net->HandoffRecover()) run();      // (as mscnn_net_detect: the frame has been run again on whole tiles)
+    const int rc = mscnn_net_unpack_detections_multi(n->det_host, num_images, num_classes, pcap, dets_host, ids_host, cap, seg_dets,
+                                                     image_rois);
+    CHECK_EQ(rc, 0) << g_err;
   });
 }
 

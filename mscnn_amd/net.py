@@ -39,6 +39,7 @@ def lib():
         L.mscnn_net_blob_device_ptr.restype = C.c_void_p
         L.mscnn_net_destroy.restype = None
         L.mscnn_net_detect_pack_bytes.restype = C.c_size_t
+        L.mscnn_net_detect_multi_pack_bytes.restype = C.c_size_t
         vp, ci, cs = C.c_void_p, C.c_int, C.c_char_p
         sig = {
             "mscnn_net_create_from_file": [cs, ci, vp], "mscnn_net_create_from_string": [cs, ci, vp], "mscnn_net_destroy": [vp],
@@ -69,6 +70,9 @@ def lib():
             "mscnn_net_handoff_state": [vp, vp],
             "mscnn_net_detect_begin": [vp, vp, ci], "mscnn_net_detect_end": [vp, vp, vp, ci, vp, vp],
             "mscnn_net_reshape_input": [vp, cs, vp, ci], "mscnn_net_detect_image": [vp, vp, ci, vp, vp, ci, vp, vp],
+            "mscnn_net_detect_multi": [vp, vp, ci, ci, vp, vp, ci, vp, vp], "mscnn_net_detect_multi_pack_bytes": [ci, ci, ci],
+            "mscnn_net_detect_multi_device": [vp, vp, ci, ci, ci, vp],
+            "mscnn_net_unpack_detections_multi": [vp, ci, ci, ci, vp, vp, ci, vp, vp],
         }
         for name, args in sig.items():
             getattr(L, name).argtypes = args
@@ -347,6 +351,40 @@ class Net:
                                             C.byref(D), C.byref(R)))
         return dets[:D.value].copy(), ids[:D.value].copy(), R.value
 
+    @classmethod
+    def _multi_params(cls, params, classes):
+        """params: one dict per image (ratios, org_hw; optional bbox_mean, bbox_std, proposal_thr, nms_overlap), classes: cls_ids
+        -> the (image, class) parameter array of mscnn_net_detect_multi, image-major."""
+        arr = (DetectParams * (len(params) * len(classes)))()
+        for i, kw in enumerate(params):
+            kw = dict(dict(bbox_mean=(0, 0, 0, 0), bbox_std=(0.1, 0.1, 0.2, 0.2), proposal_thr=-10.0, nms_overlap=0.5), **kw)
+            for c, cls_id in enumerate(classes):
+                arr[i * len(classes) + c] = cls._params(cls_id, **kw)
+        return arr
+
+    def detect_multi(self, params, classes, cap=None):
+        """mscnn_net_detect_multi: the final stage of every image and class of the last forward in one pass.  params: one dict per
+        image of the batch (ratios, org_hw, optionally bbox_mean / bbox_std / proposal_thr / nms_overlap); classes: the cls_ids.
+        Returns ([[(dets[D,5], rows of the net's ROI blobs[D]) per class] per image], [ROI count per image]) -- each pair equal to
+        detect_image(image, cls_id, ...)."""
+        B, Cn = len(params), len(classes)
+        if cap is None:
+            cap = max(1, Cn * self.blob_shape("proposals_score")[0])
+        p = self._multi_params(params, classes)
+        dets = np.zeros((max(cap, 1), 5), np.float64); ids = np.zeros(max(cap, 1), np.int32)
+        seg = np.zeros(B * Cn, np.int32); rois = np.zeros(B, np.int32)
+        _check(lib().mscnn_net_detect_multi(self._h, p, B, Cn, dets.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p), cap,
+                                            seg.ctypes.data_as(C.c_void_p), rois.ctypes.data_as(C.c_void_p)))
+        return _split_segments(dets, ids, seg, B, Cn), rois.tolist()
+
+    def detect_multi_device(self, params, classes, cap):
+        """mscnn_net_detect_multi_device: the same into the device pack (detect_multi_pack_bytes(B, C, cap) bytes); asynchronous.
+        Returns its device address."""
+        p = self._multi_params(params, classes)
+        ptr = C.c_void_p()
+        _check(lib().mscnn_net_detect_multi_device(self._h, p, len(params), len(classes), cap, C.byref(ptr)))
+        return ptr.value
+
     def detect(self, cls_id, ratios, org_hw, bbox_mean=(0, 0, 0, 0), bbox_std=(0.1, 0.1, 0.2, 0.2), proposal_thr=-10.0,
                nms_overlap=0.5, cap=4096):
         """Final detection stage on the device; returns (dets[D,5] float64 [x y w h prob], roi ids[D], R)."""
@@ -379,3 +417,33 @@ def unpack_detections(pack_host, cap):
     _check(lib().mscnn_net_unpack_detections(buf.ctypes.data_as(C.c_void_p), cap, dets.ctypes.data_as(C.c_void_p),
                                              ids.ctypes.data_as(C.c_void_p), C.byref(D), C.byref(R)))
     return dets[:D.value].copy(), ids[:D.value].copy(), R.value
+
+
+def detect_multi_pack_bytes(num_images, num_classes, cap):
+    return lib().mscnn_net_detect_multi_pack_bytes(num_images, num_classes, cap)
+
+
+def _split_segments(dets, ids, seg, B, Cn):
+    out, o = [], 0
+    for i in range(B):
+        row = []
+        for c in range(Cn):
+            k = int(seg[i * Cn + c])
+            row.append((dets[o:o + k].copy(), ids[o:o + k].copy()))
+            o += k
+        out.append(row)
+    return out
+
+
+def unpack_detections_multi(pack_host, num_images, num_classes, cap, out_cap=None):
+    """One host copy of a multi pack (mscnn_net_detect_multi_device) -> ([[(dets, ids)] per class] per image, [ROI count per image])."""
+    buf = np.frombuffer(pack_host, np.uint8) if not isinstance(pack_host, np.ndarray) else pack_host
+    assert buf.nbytes >= detect_multi_pack_bytes(num_images, num_classes, cap)
+    buf = np.ascontiguousarray(buf)
+    out_cap = max(cap, 1) if out_cap is None else out_cap
+    dets = np.zeros((max(out_cap, 1), 5), np.float64); ids = np.zeros(max(out_cap, 1), np.int32)
+    seg = np.zeros(num_images * num_classes, np.int32); rois = np.zeros(num_images, np.int32)
+    _check(lib().mscnn_net_unpack_detections_multi(buf.ctypes.data_as(C.c_void_p), num_images, num_classes, cap,
+                                                   dets.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p), out_cap,
+                                                   seg.ctypes.data_as(C.c_void_p), rois.ctypes.data_as(C.c_void_p)))
+    return _split_segments(dets, ids, seg, num_images, num_classes), rois.tolist()
