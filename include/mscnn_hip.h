@@ -435,6 +435,15 @@ MSCNN_API int mscnn_detections_multi_fwd(const mscnn_detections_desc* desc, int 
 MSCNN_API size_t mscnn_preprocess_workspace_bytes(int org_h, int org_w, int H, int W);
 MSCNN_API int mscnn_preprocess_u8_f32(const unsigned char* img_rgb, int org_h, int org_w, float* out, int H, int W,
                             const float* mean_bgr, void* workspace, size_t workspace_bytes, void* stream);
+/* The same for a batch of `count` frames, each of its own size: imgs_rgb is a HOST array of `count` device pointers (frame b:
+ * uint8 [org_h[b]][org_w[b]][3]); out: device float [count][3][H][W] (frame b in slice b).  Every slice is bit-identical to
+ * mscnn_preprocess_u8_f32 on that frame.  Two launches per 32 frames.  The workspace holds every frame's intermediate at a
+ * 256-byte aligned offset, back to back: mscnn_preprocess_batch_workspace_bytes returns that size (0 for arguments the op refuses).
+ * Null pointers, count < 1, a size <= 0 or a too small workspace are refused before any launch. */
+MSCNN_API size_t mscnn_preprocess_batch_workspace_bytes(int count, const int* org_h, const int* org_w, int H, int W);
+MSCNN_API int mscnn_preprocess_batch_u8_f32(const unsigned char* const* imgs_rgb, const int* org_h, const int* org_w, int count,
+                                  float* out, int H, int W, const float* mean_bgr, void* workspace, size_t workspace_bytes,
+                                  void* stream);
 
 #ifdef __cplusplus
 }

@@ -135,6 +135,11 @@ MSCNN_NET_API int mscnn_net_set_blob_device(mscnn_net* net, const char* name, co
  * semantics), swapped to BGR, mean-subtracted (mean_bgr == NULL: {104,117,123}) and written into blob `name`. */
 MSCNN_NET_API int mscnn_net_set_image(mscnn_net* net, const char* name, const unsigned char* img_rgb, int on_device,
                                       int org_h, int org_w, const float* mean_bgr);
+/* The batched set_image: `count` frames, frame b uint8 [org_h[b]][org_w[b]][3] (imgs_rgb: a host array of host pointers, or of
+ * device pointers when on_device != 0), each resized to the blob's H x W and written into slice b of blob `name`.  Requires
+ * count == num() and channels() == 3; refused before anything is written. */
+MSCNN_NET_API int mscnn_net_set_images(mscnn_net* net, const char* name, const unsigned char* const* imgs_rgb, int on_device,
+                                       const int* org_h, const int* org_w, int count, const float* mean_bgr);
 MSCNN_NET_API int mscnn_net_get_blob(mscnn_net* net, const char* name, float* host, size_t capacity, size_t* count);
 MSCNN_NET_API const float* mscnn_net_blob_device_ptr(mscnn_net* net, const char* name);
 

@@ -7,9 +7,12 @@
 // after EACH 1-D pass) -- MATLAB itself is not available, so this stage is "parity unpinned" like the final detection stage;
 // it is bit-identical to oracle/pyoracle.py::preprocess (same double-precision operation order; -ffp-contract=off).
 // Two HBM-bound kernels: pass 1 resizes along the first dimension into a uint8 scratch image, pass 2 resizes along the
-// other one and fuses the RGB->BGR swap, the mean subtraction and the HWC -> NCHW layout change.
+// other one and fuses the RGB->BGR swap, the mean subtraction and the HWC -> NCHW layout change.  Both take a batch: a table of
+// up to kMaxImages frames of their own sizes (and so their own pass order and intermediate) passed by value as a kernel argument,
+// blockIdx.y = the frame's slot.  The single-frame op is a batch of one.
 #include "common.h"
 #include <cstdint>
+#include <vector>
 
 namespace {
 
@@ -51,42 +54,107 @@ __device__ __forceinline__ unsigned char to_u8(double v) {
   return (unsigned char)(v < 0.0 ? 0.0 : (v > 255.0 ? 255.0 : v));
 }
 
-// src [sh][sw][3] u8 -> dst [dh][sw][3] u8 (resize along H) or [sh][dw][3] (along W)
-__global__ __launch_bounds__(256) void resize_u8_kernel(const unsigned char* __restrict__ src, unsigned char* __restrict__ dst,
-                                                        int sh, int sw, int dh, int dw, int along_w) {
-  const long total = (long)dh * dw * 3;
-  for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    const int c = (int)(i % 3), x = (int)((i / 3) % dw), y = (int)(i / (3L * dw));
-    Taps t(along_w ? sw : sh, along_w ? dw : dh, along_w ? x : y);
-    double acc = 0.0;
-    for (int k = 0; k < t.P; ++k) {
-      const int s = t.index(k);
-      const double v = along_w ? (double)src[((long)y * sw + s) * 3 + c] : (double)src[((long)s * sw + x) * 3 + c];
-      acc = acc + (t.raw(k) / t.sum) * v;
-    }
-    dst[i] = to_u8(acc);
+// One image of a launch.  Pass 1 resizes src [org_h][org_w][3] into mid [mh][mw][3] along H (h_first) or along W; pass 2 resizes
+// mid along the other axis into the image's [3][H][W] slice of the output.
+struct PreImage {
+  const unsigned char* src;
+  unsigned char* mid;
+  int org_h, org_w, mh, mw, h_first;
+};
+constexpr int kMaxImages = 32;              // images per launch: the table is 32 x 40 B = 1280 B of kernel arguments
+struct PreTable { PreImage img[kMaxImages]; };
+
+// src [sh][sw][3] u8 -> dst [dh][sw][3] u8 (resize along H) or [sh][dw][3] (along W); element i of dst
+template <int ALONG_W>
+__device__ __forceinline__ void resize_u8_elem(const unsigned char* __restrict__ src, unsigned char* __restrict__ dst, int sh, int sw,
+                                               int dh, int dw, long i) {
+  const int c = (int)(i % 3), x = (int)((i / 3) % dw), y = (int)(i / (3L * dw));
+  Taps t(ALONG_W ? sw : sh, ALONG_W ? dw : dh, ALONG_W ? x : y);
+  double acc = 0.0;
+  for (int k = 0; k < t.P; ++k) {
+    const int s = t.index(k);
+    const double v = ALONG_W ? (double)src[((long)y * sw + s) * 3 + c] : (double)src[((long)s * sw + x) * 3 + c];
+    acc = acc + (t.raw(k) / t.sum) * v;
+  }
+  dst[i] = to_u8(acc);
+}
+
+// last pass fused with BGR swap + mean subtraction + layout: src [sh][sw][3] u8 RGB -> out [3][dh][dw] f32 (BGR planes); pixel i
+template <int ALONG_W>
+__device__ __forceinline__ void resize_finish_elem(const unsigned char* __restrict__ src, float* __restrict__ out, int sh, int sw,
+                                                   int dh, int dw, float mb, float mg, float mr, long i) {
+  const long total = (long)dh * dw;
+  const int x = (int)(i % dw), y = (int)(i / dw);
+  Taps t(ALONG_W ? sw : sh, ALONG_W ? dw : dh, ALONG_W ? x : y);
+  double acc[3] = {0.0, 0.0, 0.0};
+  for (int k = 0; k < t.P; ++k) {
+    const int s = t.index(k);
+    const unsigned char* p = ALONG_W ? src + ((long)y * sw + s) * 3 : src + ((long)s * sw + x) * 3;
+    const double w = t.raw(k) / t.sum;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) acc[c] = acc[c] + w * (double)p[c];
+  }
+  out[i] = (float)to_u8(acc[2]) - mb;                 // plane 0 = B
+  out[total + i] = (float)to_u8(acc[1]) - mg;         // plane 1 = G
+  out[2 * total + i] = (float)to_u8(acc[0]) - mr;     // plane 2 = R
+}
+
+// pass 1 of every image of the table: blockIdx.y = image slot, grid-stride over that image's intermediate along x
+__global__ __launch_bounds__(256) void resize_u8_batch_kernel(const PreTable tab) {
+  const PreImage& d = tab.img[blockIdx.y];
+  const long total = (long)d.mh * d.mw * 3;
+  const long step = (long)gridDim.x * 256;
+  if (d.h_first) {                                    // uniform per block
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += step) resize_u8_elem<0>(d.src, d.mid, d.org_h, d.org_w, d.mh, d.mw, i);
+  } else {
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += step) resize_u8_elem<1>(d.src, d.mid, d.org_h, d.org_w, d.mh, d.mw, i);
   }
 }
 
-// last pass fused with BGR swap + mean subtraction + layout: src [sh][sw][3] u8 RGB -> out [3][dh][dw] f32 (BGR planes)
-__global__ __launch_bounds__(256) void resize_finish_kernel(const unsigned char* __restrict__ src, float* __restrict__ out, int sh,
-                                                            int sw, int dh, int dw, int along_w, float mb, float mg, float mr) {
-  const long total = (long)dh * dw;
-  for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    const int x = (int)(i % dw), y = (int)(i / dw);
-    Taps t(along_w ? sw : sh, along_w ? dw : dh, along_w ? x : y);
-    double acc[3] = {0.0, 0.0, 0.0};
-    for (int k = 0; k < t.P; ++k) {
-      const int s = t.index(k);
-      const unsigned char* p = along_w ? src + ((long)y * sw + s) * 3 : src + ((long)s * sw + x) * 3;
-      const double w = t.raw(k) / t.sum;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) acc[c] = acc[c] + w * (double)p[c];
-    }
-    out[i] = (float)to_u8(acc[2]) - mb;                 // plane 0 = B
-    out[total + i] = (float)to_u8(acc[1]) - mg;         // plane 1 = G
-    out[2 * total + i] = (float)to_u8(acc[0]) - mr;     // plane 2 = R
+// pass 2 of every image of the table: slot s writes out + s * 3 * H * W
+__global__ __launch_bounds__(256) void resize_finish_batch_kernel(const PreTable tab, float* __restrict__ out, int H, int W, float mb,
+                                                                  float mg, float mr) {
+  const PreImage& d = tab.img[blockIdx.y];
+  const long total = (long)H * W;
+  const long step = (long)gridDim.x * 256;
+  float* o = out + (long)blockIdx.y * 3 * total;
+  if (d.h_first) {                                    // H done in pass 1: along W here
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += step) resize_finish_elem<1>(d.mid, o, d.mh, d.mw, H, W, mb, mg, mr, i);
+  } else {
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += step) resize_finish_elem<0>(d.mid, o, d.mh, d.mw, H, W, mb, mg, mr, i);
   }
+}
+
+// [~, order] = sort(scale): the smaller scale first
+inline bool h_first_of(int org_h, int org_w, int H, int W) { return (double)H / org_h <= (double)W / org_w; }
+
+size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// imgs[0..n) with their intermediates mid[0..n) -> out [n][3][H][W]: two launches per chunk of kMaxImages images
+int preprocess_launch(const unsigned char* const* imgs, unsigned char* const* mids, const int* org_h, const int* org_w, int n, float* out,
+                      int H, int W, const float* mean_bgr, hipStream_t st) {
+  for (int c0 = 0; c0 < n; c0 += kMaxImages) {
+    const int m = n - c0 < kMaxImages ? n - c0 : kMaxImages;
+    PreTable tab = {};
+    long mid_max = 0;
+    for (int s = 0; s < m; ++s) {
+      const int b = c0 + s;
+      const bool hf = h_first_of(org_h[b], org_w[b], H, W);
+      tab.img[s] = PreImage{imgs[b], mids[b], org_h[b], org_w[b], hf ? H : org_h[b], hf ? org_w[b] : W, hf ? 1 : 0};
+      const long e = (long)tab.img[s].mh * tab.img[s].mw * 3;
+      if (e > mid_max) mid_max = e;
+    }
+    long blocks = (mid_max + 255) / 256;
+    if (blocks > 65536) blocks = 65536;
+    resize_u8_batch_kernel<<<dim3((unsigned)blocks, (unsigned)m), 256, 0, st>>>(tab);
+    MSCNN_POST_LAUNCH();
+    blocks = ((long)H * W + 255) / 256;
+    if (blocks > 65536) blocks = 65536;
+    resize_finish_batch_kernel<<<dim3((unsigned)blocks, (unsigned)m), 256, 0, st>>>(tab, out + (long)c0 * 3 * H * W, H, W, mean_bgr[0],
+                                                                                   mean_bgr[1], mean_bgr[2]);
+    MSCNN_POST_LAUNCH();
+  }
+  return MSCNN_OK;
 }
 
 }  // namespace
@@ -95,8 +163,7 @@ using namespace mscnn;
 
 extern "C" size_t mscnn_preprocess_workspace_bytes(int org_h, int org_w, int H, int W) {
   // the intermediate image after the first 1-D pass
-  const double sh = (double)H / org_h, sw = (double)W / org_w;
-  return sh <= sw ? (size_t)H * org_w * 3 : (size_t)org_h * W * 3;
+  return h_first_of(org_h, org_w, H, W) ? (size_t)H * org_w * 3 : (size_t)org_h * W * 3;
 }
 
 extern "C" int mscnn_preprocess_u8_f32(const unsigned char* img_rgb, int org_h, int org_w, float* out, int H, int W,
@@ -104,18 +171,38 @@ extern "C" int mscnn_preprocess_u8_f32(const unsigned char* img_rgb, int org_h, 
   MSCNN_REQUIRE(img_rgb && out && mean_bgr, "preprocess: null pointer");
   MSCNN_REQUIRE(org_h > 0 && org_w > 0 && H > 0 && W > 0, "preprocess: bad shape");
   MSCNN_REQUIRE(workspace && workspace_bytes >= mscnn_preprocess_workspace_bytes(org_h, org_w, H, W), "preprocess: workspace too small");
-  hipStream_t st = as_stream(stream);
-  const double sh = (double)H / org_h, sw = (double)W / org_w;
-  unsigned char* tmp = static_cast<unsigned char*>(workspace);
-  const bool h_first = sh <= sw;                           // [~, order] = sort(scale)
-  const int mh = h_first ? H : org_h, mw = h_first ? org_w : W;
-  long blocks = ((long)mh * mw * 3 + 255) / 256;
-  if (blocks > 65536) blocks = 65536;
-  resize_u8_kernel<<<(int)blocks, 256, 0, st>>>(img_rgb, tmp, org_h, org_w, mh, mw, h_first ? 0 : 1);
-  MSCNN_POST_LAUNCH();
-  blocks = ((long)H * W + 255) / 256;
-  if (blocks > 65536) blocks = 65536;
-  resize_finish_kernel<<<(int)blocks, 256, 0, st>>>(tmp, out, mh, mw, H, W, h_first ? 1 : 0, mean_bgr[0], mean_bgr[1], mean_bgr[2]);
-  MSCNN_POST_LAUNCH();
-  return MSCNN_OK;
+  unsigned char* mid = static_cast<unsigned char*>(workspace);
+  return preprocess_launch(&img_rgb, &mid, &org_h, &org_w, 1, out, H, W, mean_bgr, as_stream(stream));
+}
+
+extern "C" size_t mscnn_preprocess_batch_workspace_bytes(int count, const int* org_h, const int* org_w, int H, int W) {
+  // every image's intermediate at a 256-byte aligned offset, back to back; 0 for arguments the op refuses
+  if (count < 1 || !org_h || !org_w || H <= 0 || W <= 0) return 0;
+  size_t total = 0;
+  for (int b = 0; b < count; ++b) {
+    if (org_h[b] <= 0 || org_w[b] <= 0) return 0;
+    total += align256(mscnn_preprocess_workspace_bytes(org_h[b], org_w[b], H, W));
+  }
+  return total;
+}
+
+extern "C" int mscnn_preprocess_batch_u8_f32(const unsigned char* const* imgs_rgb, const int* org_h, const int* org_w, int count,
+                                             float* out, int H, int W, const float* mean_bgr, void* workspace, size_t workspace_bytes,
+                                             void* stream) {
+  MSCNN_REQUIRE(imgs_rgb && org_h && org_w && out && mean_bgr && workspace, "preprocess_batch: null pointer");
+  MSCNN_REQUIRE(count >= 1, "preprocess_batch: count %d < 1", count);
+  MSCNN_REQUIRE(H > 0 && W > 0, "preprocess_batch: bad output shape %d x %d", H, W);
+  for (int b = 0; b < count; ++b) {
+    MSCNN_REQUIRE(org_h[b] > 0 && org_w[b] > 0, "preprocess_batch: image %d has bad shape %d x %d", b, org_h[b], org_w[b]);
+    MSCNN_REQUIRE(imgs_rgb[b], "preprocess_batch: image %d is a null pointer", b);
+  }
+  const size_t need = mscnn_preprocess_batch_workspace_bytes(count, org_h, org_w, H, W);
+  MSCNN_REQUIRE(workspace_bytes >= need, "preprocess_batch: workspace %zu bytes < %zu", workspace_bytes, need);
+  std::vector<unsigned char*> mids(count);
+  size_t off = 0;
+  for (int b = 0; b < count; ++b) {
+    mids[b] = static_cast<unsigned char*>(workspace) + off;
+    off += align256(mscnn_preprocess_workspace_bytes(org_h[b], org_w[b], H, W));
+  }
+  return preprocess_launch(imgs_rgb, mids.data(), org_h, org_w, count, out, H, W, mean_bgr, as_stream(stream));
 }

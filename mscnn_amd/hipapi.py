@@ -597,6 +597,32 @@ def preprocess(img_rgb_u8, out_h, out_w, mean_bgr=(104.0, 117.0, 123.0), out=Non
     return out
 
 
+def preprocess_batch(frames, out_h, out_w, mean_bgr=(104.0, 117.0, 123.0), out=None):
+    """preprocess() for a list of uint8 [h, w, 3] contiguous cuda tensors of their own sizes, in two launches per 32 frames ->
+    [B, 3, out_h, out_w]; slice b is bit-identical to preprocess(frames[b], out_h, out_w)."""
+    B = len(frames)
+    if B < 1:
+        raise MscnnError("preprocess_batch: no frames")
+    for b, f in enumerate(frames):
+        if f.dim() != 3 or f.shape[2] != 3 or f.dtype != torch.uint8 or not f.is_cuda or not f.is_contiguous():
+            raise MscnnError(f"preprocess_batch: frame {b} is not a contiguous uint8 [H, W, 3] cuda tensor")
+    dev = frames[0].device
+    if out is None:
+        out = torch.empty((B, 3, out_h, out_w), dtype=torch.float32, device=dev)
+    L = lib()
+    oh = (C.c_int * B)(*[int(f.shape[0]) for f in frames])
+    ow = (C.c_int * B)(*[int(f.shape[1]) for f in frames])
+    ptrs = (C.c_void_p * B)(*[f.data_ptr() for f in frames])
+    L.mscnn_preprocess_batch_workspace_bytes.restype = C.c_size_t
+    L.mscnn_preprocess_batch_workspace_bytes.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+    wb = L.mscnn_preprocess_batch_workspace_bytes(B, oh, ow, out_h, out_w)
+    ws = torch.empty(max(wb, 1), dtype=torch.uint8, device=dev)
+    m = (C.c_float * 3)(*mean_bgr)
+    _check(L.mscnn_preprocess_batch_u8_f32(ptrs, oh, ow, B, _dev(out), out_h, out_w, m, _dev(ws), C.c_size_t(wb), _stream()))
+    torch.cuda.current_stream().synchronize()     # ws dies with this batch
+    return out
+
+
 def nms_greedy(boxes_xywh, thr, mode="IOU"):
     n = boxes_xywh.shape[0]
     keep = torch.zeros(max(n, 1), dtype=torch.uint8, device=boxes_xywh.device)

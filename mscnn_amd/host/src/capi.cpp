@@ -308,6 +308,38 @@ int mscnn_net_set_image(mscnn_net* n, const char* name, const unsigned char* img
     CHECK_EQ(rc, 0) << mscnn_last_error();
   });
 }
+int mscnn_net_set_images(mscnn_net* n, const char* name, const unsigned char* const* imgs_rgb, int on_device, const int* org_h,
+                         const int* org_w, int count, const float* mean_bgr) {
+  return guarded([&] {
+    CHECK(n->net->has_blob(name)) << "Unknown blob name " << name;
+    auto b = n->net->blob_by_name(name);
+    CHECK(b->num_axes() == 4 && b->channels() == 3) << "set_images: blob " << name << " has shape " << b->shape_string();
+    CHECK(count == b->num()) << "set_images: " << count << " images for blob " << name << " of shape " << b->shape_string();
+    CHECK(imgs_rgb && org_h && org_w) << "set_images: null pointer";
+    const int H = b->height(), W = b->width();
+    for (int i = 0; i < count; ++i)
+      CHECK(imgs_rgb[i] && org_h[i] > 0 && org_w[i] > 0) << "set_images: image " << i << " is " << org_h[i] << " x " << org_w[i]
+                                                          << (imgs_rgb[i] ? "" : " at a null pointer");
+    n->net->MaterializePendingReadersOf(name);      // (as set_image)
+    hipStream_t st = (hipStream_t)Caffe::stream();
+    std::vector<const unsigned char*> dev(imgs_rgb, imgs_rgb + count);
+    if (!on_device) {                               // staged back to back into img_in (256-byte aligned offsets)
+      std::vector<size_t> off(count + 1, 0);
+      for (int i = 0; i < count; ++i) off[i + 1] = off[i] + (((size_t)org_h[i] * org_w[i] * 3 + 255) & ~(size_t)255);
+      unsigned char* d = static_cast<unsigned char*>(n->img_in.Reserve(off[count]));
+      for (int i = 0; i < count; ++i) {
+        HIP_CHECK(hipMemcpyAsync(d + off[i], imgs_rgb[i], (size_t)org_h[i] * org_w[i] * 3, hipMemcpyHostToDevice, st));
+        dev[i] = d + off[i];
+      }
+    }
+    const size_t wb = mscnn_preprocess_batch_workspace_bytes(count, org_h, org_w, H, W);
+    void* ws = n->img_ws.Reserve(wb);
+    static const float kMean[3] = {104.f, 117.f, 123.f};      // run_mscnn_detection.m:38
+    const int rc = mscnn_preprocess_batch_u8_f32(dev.data(), org_h, org_w, count, b->mutable_gpu_data(), H, W,
+                                                 mean_bgr ? mean_bgr : kMean, ws, wb, st);
+    CHECK_EQ(rc, 0) << mscnn_last_error();
+  });
+}
 int mscnn_net_get_blob(mscnn_net* n, const char* name, float* host, size_t capacity, size_t* count) {
   return guarded([&] {
     CHECK(n->net->has_blob(name)) << "Unknown blob name " << name;

@@ -60,6 +60,7 @@ def lib():
             "mscnn_net_set_param": [vp, ci, ci, vp, C.c_size_t], "mscnn_net_get_param": [vp, ci, ci, vp, C.c_size_t],
             "mscnn_net_set_blob": [vp, cs, vp, C.c_size_t], "mscnn_net_set_blob_device": [vp, cs, vp, C.c_size_t],
             "mscnn_net_set_image": [vp, cs, vp, ci, ci, ci, vp],
+            "mscnn_net_set_images": [vp, cs, vp, ci, vp, vp, ci, vp],
             "mscnn_net_get_blob": [vp, cs, vp, C.c_size_t, vp], "mscnn_net_blob_device_ptr": [vp, cs],
             "mscnn_net_forward": [vp], "mscnn_net_forward_from_to": [vp, ci, ci], "mscnn_net_reshape": [vp],
             "mscnn_net_set_layer_timing": [vp, ci], "mscnn_net_layer_ms": [vp, ci],
@@ -261,6 +262,37 @@ class Net:
         a = np.ascontiguousarray(img_rgb_u8, np.uint8)
         h, w, _ = a.shape
         _check(lib().mscnn_net_set_image(self._h, name.encode(), a.ctypes.data_as(C.c_void_p), 0, h, w, m))
+
+    def set_images(self, name, frames, mean_bgr=None):
+        """Batched set_image: frames is a list of uint8 [h, w, 3] numpy arrays or a list of contiguous uint8 torch CUDA tensors (one
+        frame per image of the blob, each of its own size).  Returns one dict per frame, {"ratios": (H / h, W / w), "org_hw": (h, w)}:
+        the params detect_multi takes."""
+        frames = list(frames)
+        on_dev = [hasattr(f, "is_cuda") and f.is_cuda for f in frames]
+        if any(on_dev) and not all(on_dev):
+            raise NetError("set_images: a list that mixes host and device frames")
+        device = any(on_dev)
+        if device:
+            for b, f in enumerate(frames):
+                if str(f.dtype) != "torch.uint8" or f.dim() != 3 or f.shape[2] != 3 or not f.is_contiguous():
+                    raise NetError(f"set_images: frame {b} is not a contiguous uint8 [h, w, 3] tensor")
+            keep = frames
+            ptrs = [f.data_ptr() for f in frames]
+        else:
+            keep = []
+            for b, f in enumerate(frames):
+                if not isinstance(f, np.ndarray) or f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3:
+                    raise NetError(f"set_images: frame {b} is not a uint8 [h, w, 3] array")
+                keep.append(np.ascontiguousarray(f))
+            ptrs = [a.ctypes.data for a in keep]
+        B = len(frames)
+        hs = [int(f.shape[0]) for f in keep]
+        ws = [int(f.shape[1]) for f in keep]
+        m = (C.c_float * 3)(*mean_bgr) if mean_bgr is not None else None
+        _check(lib().mscnn_net_set_images(self._h, name.encode(), (C.c_void_p * max(B, 1))(*ptrs), 1 if device else 0,
+                                          (C.c_int * max(B, 1))(*hs), (C.c_int * max(B, 1))(*ws), B, m))
+        H, W = self.blob_shape(name)[2:]
+        return [{"ratios": (H / float(h), W / float(w)), "org_hw": (h, w)} for h, w in zip(hs, ws)]
 
     def get_blob(self, name):
         a = np.empty(self.blob_shape(name), np.float32)

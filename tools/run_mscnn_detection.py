@@ -8,11 +8,16 @@ examples/kitti_result/writeDetForEval.m.
 
   python tools/run_mscnn_detection.py --prototxt mscnn_deploy.prototxt --weights model.caffemodel --images /KITTI/testing/image_2
          [--out detections] [--comp-id kitti_7s_576] [--cls-ids 2] [--names bg,car,van,truck,tram] [--precision f32|f16x3|f16]
-         [--labels-dir results/data] [--limit N]
+         [--labels-dir results/data] [--limit N] [--batch B]
   python tools/run_mscnn_detection.py --model kitti_car/mscnn-7s-576 --synthetic 8      # no dataset / weights at hand: the generated
                                                                                         # deploy net, seeded weights, synthetic frames
 
-Everything here is host glue over calls the test-suite covers one by one (Net.set_image, forward, detect, kitti.write_*)."""
+--batch B > 1 runs B frames per forward: the net's input is reshaped to (B, 3, H, W) (the last group to its own size), the group is
+pre-processed in one call (Net.set_images) and its final stage runs for every frame and class in one pass (Net.detect_multi); the
+output files are the same, avgtime stays per frame.
+
+Everything here is host glue over calls the test-suite covers one by one (Net.set_image / set_images, forward, detect / detect_multi,
+kitti.write_*)."""
 import argparse
 import glob
 import os
@@ -46,6 +51,14 @@ def frame_id(path, k):
     return int(stem) if stem.isdigit() else k - 1
 
 
+def load_frame(path, k):
+    """Frame k (1-based) of the run: the file, or a frame of KITTI's size from the seeded generator (uint8 RGB, HWC)."""
+    if path is None:
+        rng = np.random.default_rng(1701 + k)
+        return np.ascontiguousarray(rng.integers(0, 256, (375, 1242, 3), dtype=np.uint8))
+    return load_rgb_u8(path)
+
+
 def names_for(prototxt_text, names_arg):
     """Class names: --names, else from the width of cls_pred (5 = KITTI car nets, 3 = ped / cyc, 2 = pedestrian nets)."""
     if names_arg:
@@ -68,6 +81,7 @@ def main(argv=None):
     ap.add_argument("--precision", default="f32", choices=["f32", "f16x3", "f16"])
     ap.add_argument("--proposal-thr", type=float, default=-10.0); ap.add_argument("--nms-overlap", type=float, default=0.5)
     ap.add_argument("--limit", type=int, default=0); ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--batch", type=int, default=1, help="frames per forward (> 1: Net.set_images + one detect_multi per group)")
     a = ap.parse_args(argv)
     if not (a.prototxt or a.model) or not (a.images or a.synthetic):
         ap.error("need --prototxt or --model, and --images or --synthetic N")
@@ -89,14 +103,14 @@ def main(argv=None):
     files = list_images(a.images, a.limit) if a.images else [None] * a.synthetic
     if not files:
         sys.exit(f"no images in {a.images}")
+    if a.batch < 1:
+        ap.error("--batch must be >= 1")
     per_class = {c: [] for c in cls_ids}
+    if a.batch > 1:
+        return run_batched(a, net, files, names, cls_ids, imgH, imgW, per_class)
     used = 0.0
     for k, path in enumerate(files, start=1):
-        if path is None:                             # a frame of KITTI's size from the seeded generator (uint8 RGB, HWC)
-            rng = np.random.default_rng(1701 + k)
-            img = np.ascontiguousarray(rng.integers(0, 256, (375, 1242, 3), dtype=np.uint8))
-        else:
-            img = load_rgb_u8(path)
+        img = load_frame(path, k)
         orgH, orgW = img.shape[:2]
         ratios = (imgH / float(orgH), imgW / float(orgW))                      # :63
         dev_img = torch.from_numpy(img).cuda(a.device)                       # (kept referenced until the pre-processing has run)
@@ -115,11 +129,49 @@ def main(argv=None):
             kitti.write_kitti_labels(a.labels_dir, frame_id(path, k), by_type)
         if k % 100 == 0 or k == len(files):
             print(f"idx {k}/{len(files)}, avgtime={used / k:.4f}s")           # :147
+    write_results(a, names, cls_ids, per_class, len(files))
+    return 0
+
+
+def run_batched(a, net, files, names, cls_ids, imgH, imgW, per_class):
+    """--batch B: groups of B frames through set_images -> forward -> one detect_multi; results in frame order."""
+    import torch
+    from mscnn_amd import kitti
+    used, n_in = 0.0, None
+    for g0 in range(0, len(files), a.batch):
+        group = files[g0:g0 + a.batch]
+        if len(group) != n_in:                                                # the last group: the net at its own size
+            net.reshape_input("data", (len(group), 3, imgH, imgW))
+            n_in = len(group)
+        dev_imgs = [torch.from_numpy(load_frame(path, g0 + i + 1)).cuda(a.device) for i, path in enumerate(group)]
+        params = net.set_images("data", dev_imgs)                           # :63-69 for every frame of the group, on the device
+        torch.cuda.synchronize(a.device)
+        t0 = time.perf_counter()
+        net.forward()
+        torch.cuda.synchronize(a.device)
+        used += time.perf_counter() - t0                                      # :72-73: forward only
+        per_image, _ = net.detect_multi([dict(p, proposal_thr=a.proposal_thr, nms_overlap=a.nms_overlap) for p in params], cls_ids)
+        for i, path in enumerate(group):
+            k = g0 + i + 1
+            by_type = {}
+            for ci, c in enumerate(cls_ids):
+                dets = per_image[i][ci][0]
+                per_class[c].append(dets)
+                by_type[{"car": "Car", "ped": "Pedestrian", "cyc": "Cyclist"}.get(names[c - 1], names[c - 1])] = dets
+            if a.labels_dir:
+                kitti.write_kitti_labels(a.labels_dir, frame_id(path, k), by_type)
+            if k % 100 == 0 or k == len(files):
+                print(f"idx {k}/{len(files)}, avgtime={used / (g0 + len(group)):.4f}s")   # per frame
+    write_results(a, names, cls_ids, per_class, len(files))
+    return 0
+
+
+def write_results(a, names, cls_ids, per_class, n_files):
+    from mscnn_amd import kitti
     for c in cls_ids:
         out = os.path.join(a.out, f"{a.comp_id}_{names[c - 1]}.txt")
         kitti.write_detections_dlm(out, per_class[c])                         # :150-161
-        print(f"{out}: {sum(len(d) for d in per_class[c])} detections over {len(files)} images")
-    return 0
+        print(f"{out}: {sum(len(d) for d in per_class[c])} detections over {n_files} images")
 
 
 if __name__ == "__main__":
