@@ -126,6 +126,8 @@ class ConvolutionLayer : public Layer<Dtype> {
   // when it is off by more than the tolerance, puts the layer on the direct kernel for good and recomputes the tops before Forward
   // returns -- no caller ever sees an unchecked Winograd result.  kDefaultSelfcheckTol unless set_selfcheck says otherwise; 0 = off.
   static constexpr double kDefaultSelfcheckTol = 5e-5;
+  // every check applies where this holds: an algorithm other than direct / F16 whose planned kernel is a Winograd form
+  bool WinogradCheckApplies() const;
   void set_selfcheck(double tol) { selfcheck_tol_ = tol; selfcheck_pending_ = true; wino_checked_ = false; }
   double selfcheck_tol() const { return selfcheck_tol_; }
   // what the last self-check measured; `take` clears the "a check ran since the last take" mark (Net bookkeeping)
@@ -141,24 +143,25 @@ class ConvolutionLayer : public Layer<Dtype> {
   double ExecutedFlops() const;
   void set_profiling(bool on);
   bool StageMs(float ms[3]) const;
-  // max |y - y_direct| / max(1, |y_direct|) of the current algorithm against the direct kernel on the given bottom
-  // (device scratch only; the layer's tops are not touched).  0 when the layer already runs a direct kernel.
-  double ErrorAgainstDirect(const vector<Blob<Dtype>*>& bottom, const vector<Blob<Dtype>*>& top);
-  // The numerics watch's form of the same comparison (round 6): ONE BAND of the layer -- a few rows of the map with a one-row halo
-  // (3x3 / pad 1 trunk layers), or a few of the images / ROIs (small maps, roi_c1): ~30 us of direct-kernel work, at most an eighth of the layer -- is recomputed with
-  // the direct kernel and compared with the same rows of the top blob this Forward wrote, everything ENQUEUED behind the frame on the
-  // layer's stream: no host synchronisation, no second full-size convolution.  The verdict is read later (PollBandCheck), so a frame's
-  // latency never contains a check; it applies from the frame after it is known.
-  //   BeginBandCheck: false when there is nothing to check (a direct kernel, an empty or unwritten top, a check still in flight).
-  //   PollBandCheck: 0 nothing in flight, 1 still running (wait = false), 2 done: *err = max |dy| / max(1, |y|, rms(y)) over the band.
-  bool BeginBandCheck(const vector<Blob<Dtype>*>& bottom, const vector<Blob<Dtype>*>& top, int band_seq);
-  int PollBandCheck(double* err, bool wait);
-  // the last ErrorAgainstDirect compared two results of an all-zero bottom (a zero warm-up frame): it says nothing about the layer's
-  // numerics on data -- the first-forward check stays armed for the next bottom
-  bool last_check_vacuous() const { return last_check_vacuous_; }
-  // The checks' device scratch (the direct plan's packed weights + workspace + a copy of the largest checked top: up to ~0.6 GB for a
-  // 7s-576 net, kept per host thread and device so that a check on a live stream pays no hipMalloc / synchronising hipFree) is
-  // released by this call; Net::SetNumericsWatch(0, .) / SetAutoCalibrate(0) call it when both checks are switched off.
+  // The Winograd-vs-direct comparison, one for every policy (the first-forward check, Net::CalibrateNumerics, the numerics watch):
+  // a direct plan of the compared region's shape recomputes it from the same bottom with the same weights, and the metric
+  // max |dy| / max(1, |y|, rms(y)) of that region of the top is written, behind an event, into this layer's pinned record for the use.
+  // Everything is ENQUEUED on the layer's stream; BeginCheck returns false when there is nothing to compare (no Winograd form, an
+  // empty or unwritten top, a check of that use still in flight).  The two uses own their plan, event, record and scratch region:
+  //   kWhole: the whole layer (images [0, N)), also the bottom's sum of squares -- ErrorAgainstDirect waits for it at once;
+  //   kBand:  the layer's next band (round robin per layer: a few rows of the map with a one-row halo on 3x3 / pad 1 layers, else a few
+  //           images / ROIs; ~30 us of direct-kernel work, at most an eighth of the layer) -- the numerics watch, read a frame later.
+  //   PollCheck: 0 nothing in flight, 1 still running (wait = false), 2 done: *err = the metric, *vacuous = the bottom was all zero
+  //   (kWhole only: both forms return the bias -- a zero warm-up frame says nothing about the layer's numerics).
+  enum CheckUse { kWhole = 0, kBand = 1 };
+  bool BeginCheck(const vector<Blob<Dtype>*>& bottom, const vector<Blob<Dtype>*>& top, CheckUse use);
+  int PollCheck(CheckUse use, double* err, bool wait, bool* vacuous = nullptr);
+  // Plan + BeginCheck(kWhole) + PollCheck(wait): the metric on the given bottom (device scratch only; the layer's tops are not
+  // touched), 0 when no check applies.
+  double ErrorAgainstDirect(const vector<Blob<Dtype>*>& bottom, const vector<Blob<Dtype>*>& top, bool* vacuous = nullptr);
+  // The checks' device scratch (a direct plan's packed weights + workspace + the band and its direct output: up to ~0.6 GB for a 7s-576
+  // net, kept per host thread and device so that a check on a live stream pays no hipMalloc / synchronising hipFree) is released by
+  // this call; Net::SetNumericsWatch(0, .) / SetAutoCalibrate(0) call it when both checks are switched off.
   static void ReleaseCheckScratch();
   // max |x| hand-over for the split-fp16 algorithm (mscnn_conv2d_plan_set_amax_io), wired by the Net: `out` is this layer's
   // slot (written when some consumer asked for it: set_amax_wanted), `src` / `in` the layer whose output bounds this layer's
@@ -193,14 +196,19 @@ class ConvolutionLayer : public Layer<Dtype> {
   bool ChainableNow(int n, int h, int w);
   bool calibrated_direct_ = false;
   double selfcheck_tol_ = kDefaultSelfcheckTol, selfcheck_err_ = 0.0;
-  bool selfcheck_pending_ = true, selfcheck_ran_ = false, selfcheck_fell_back_ = false, last_check_vacuous_ = false;
+  bool selfcheck_pending_ = true, selfcheck_ran_ = false, selfcheck_fell_back_ = false;
   bool wino_checked_ = false;             // a Winograd result of the current weights / algorithm has been compared with the direct kernel
-  struct BandTicket {                     // a band check in flight: the direct plan it runs on, its completion event, the pinned verdict
+  // the region a check compares: rows [r0, r0 + rows) of images [n0, n0 + bn), recomputed from bottom rows [in0, in0 + bh)
+  struct CheckBand { bool by_rows; int n0, bn, r0, rows, in0, bh; };
+  CheckBand BandOf(int N, int H, int Ho, bool roi_pending, int band) const;      // band < 0: the whole layer
+  struct Check {                          // one use's check: the direct plan it runs on, its completion event
     mscnn_conv_plan* plan = nullptr;
     void* done = nullptr;                 // hipEvent_t
-    float* host = nullptr;                // this layer's word of the (thread, device)'s pinned verdict array: the metric
     bool inflight = false;
-  } band_;
+  } check_[2];
+  struct Verdict { double ssx; float err; };      // what a check brings back: the bottom's sum of squares (kWhole), the metric
+  Verdict* verdict_ = nullptr;            // pinned, one record per use (LayerSetUp .. ~ConvolutionLayer)
+  int next_band_ = 0;                     // the band the next kBand check compares
   bool profiling_;
   const ConvolutionLayer* amax_src_ = nullptr;
   const unsigned* amax_in_ = nullptr;

@@ -94,9 +94,9 @@ class Net {
     return out;
   }
   // Numerical calibration on representative data: call after a Forward.  Every Convolution layer that runs a Winograd
-  // form is re-computed with the direct k-ordered kernel on the same bottom; where max |dy| / max(1, |y|) exceeds `tol`
-  // the layer is switched to the direct kernel for good (ConvolutionLayer::set_algo).  Returns the layers switched;
-  // errors (per layer index, 0 for layers not checked) are left in calibration_err().
+  // form is re-computed with the direct k-ordered kernel on the same bottom (ConvolutionLayer::ErrorAgainstDirect); where
+  // max |dy| / max(1, |y|, rms(y)) exceeds `tol` the layer is switched to the direct kernel for good (FallBackIfStrayed).  Returns the
+  // layers switched; errors (per layer index, 0 for layers not checked) are left in calibration_err().
   vector<int> CalibrateNumerics(double tol);
   const vector<double>& calibration_err() const { return calib_err_; }
   // Safe by default (no call needed): every Convolution layer checks its Winograd result against the direct kernel by itself on the
@@ -107,9 +107,10 @@ class Net {
   int auto_calibrate_checks() const { return auto_checks_; }
   const vector<int>& auto_calibrate_switched() const { return auto_switched_; }
   // The same comparison while a stream of frames runs (the numerics watch): every `period`-th whole Forward looks at ONE Winograd
-  // layer (round robin) -- its bottom and top are written as blobs in that frame although it stays in its convolution chain, and one band of it (a few
-  // rows / images: ~30 us of direct-kernel work; round robin too) is recomputed with the direct kernel BEHIND the frame on the same stream, without a
-  // host synchronisation.  The verdict is collected by a later Forward (or by the state accessors below); a layer that strayed by more
+  // layer (round robin) -- its bottom and top are written as blobs in that frame although it stays in its convolution chain, and the
+  // layer's next band (a few rows / images: ~30 us of direct-kernel work; each layer goes round its own bands, one per visit) is
+  // recomputed with the direct kernel BEHIND the frame on the same stream (ConvolutionLayer::BeginCheck(kBand)), without a host
+  // synchronisation.  The verdict is collected by a later Forward (or by the state accessors below); a layer that strayed by more
   // than tol runs the direct kernel for good from the frame after.  A watch frame costs up to two extra blob writes plus that band
   // (2 - 8 % of a 7s-576 frame); no frame ever waits for a check.  ON by default (every
   // kDefaultWatchPeriod-th frame, tolerance 5e-5: ~0.1 % of a stream); period 0 turns it off.
@@ -173,8 +174,9 @@ class Net {
   int SplitSource(int blob) const;      // through Split layers (their tops share the bottom's data) to the blob that holds the data
   vector<double> calib_err_;
   int NextWatchLayer() const;
+  void FallBackIfStrayed(int layer, double err, double tol, const char* where, vector<int>* switched);
   int watch_period_ = kDefaultWatchPeriod, watch_frame_ = 0, watch_next_ = 0, watch_checks_ = 0;
-  int watch_pending_ = -1, watch_band_ = 0;      // layer whose band check is in flight (-1: none); band index (advances once per trip round the layers)
+  int watch_pending_ = -1;      // layer whose band check is in flight (-1: none)
   double watch_tol_ = 5e-5;
   int auto_checks_ = 0;
   double auto_tol_ = 5e-5;      // (= ConvolutionLayer::kDefaultSelfcheckTol; 0 once SetAutoCalibrate(0) opted out)

@@ -108,9 +108,12 @@ void SplitLayer<Dtype>::Forward_cpu(const vector<Blob<Dtype>*>& bottom, const ve
 // ------------------------------------------------------------------------------------------------ Convolution
 template <typename Dtype>
 ConvolutionLayer<Dtype>::~ConvolutionLayer() {
-  if (band_.inflight && band_.done) (void)hipEventSynchronize((hipEvent_t)band_.done);      // its kernels read this layer's weights
-  if (band_.plan) mscnn_conv2d_plan_destroy(band_.plan);
-  if (band_.done) (void)hipEventDestroy((hipEvent_t)band_.done);
+  for (Check& ck : check_) {
+    if (ck.inflight) (void)hipEventSynchronize((hipEvent_t)ck.done);      // its kernels read this layer's weights and write verdict_
+    if (ck.plan) mscnn_conv2d_plan_destroy(ck.plan);
+    if (ck.done) (void)hipEventDestroy((hipEvent_t)ck.done);
+  }
+  if (verdict_) (void)hipHostFree(verdict_);
   if (plan_) mscnn_conv2d_plan_destroy(plan_);
 }
 
@@ -140,6 +143,11 @@ void ConvolutionLayer<Dtype>::LayerSetUp(const vector<Blob<Dtype>*>& bottom, con
     }
   }
   weights_dirty_ = true;
+  // the checks' verdict records, here and not on a watch frame (no device: a net that is only ever built, never run, has none)
+  if (!verdict_ && hipHostMalloc(reinterpret_cast<void**>(&verdict_), sizeof(Verdict) * 2, hipHostMallocDefault) != hipSuccess) {
+    (void)hipGetLastError();
+    verdict_ = nullptr;
+  }
 }
 
 template <typename Dtype>
@@ -198,197 +206,173 @@ bool ConvolutionLayer<Dtype>::StageMs(float ms[3]) const {
 }
 
 namespace {
-// scratch shared by every check of this host thread on this device (kept: a check on a live stream -- the numerics watch -- must
-// not pay a hipMalloc + a synchronising hipFree of 100s of MB; ConvolutionLayer::ReleaseCheckScratch frees it, otherwise it is leaked
-// on thread exit like the shared conv workspace)
-struct CheckScratch { DeviceBuffer packed, ws, y, err; };
-thread_local CheckScratch* g_check_scratch[64] = {nullptr};
+// What the convolutions of one host thread share on one device.  Thread-local like the Caffe singleton itself (a thread is a device
+// context, common.cpp:13-20): two threads may drive nets on the same device without sharing scratch.  Leaked on thread exit on
+// purpose (a destructor could run after the HIP runtime has been torn down); ConvolutionLayer::ReleaseCheckScratch frees `check`.
+//   ws:    the transient workspace of every Forward (stream-K slabs, Winograd V / M planes: up to 0.8 GB for conv2_2) -- the layers of a
+//          net run one after the other on one stream, so they share ONE buffer instead of 3 GB of per-layer buffers;
+//   check: one region per use of the Winograd-vs-direct check (ConvolutionLayer::CheckUse), kept so that a check on a live stream pays
+//          no hipMalloc / synchronising hipFree.  Two regions: a band check may still be running on the device when a whole-layer
+//          check reserves -- and possibly re-allocates -- its buffers.
+struct CheckRegion {
+  DeviceBuffer x, packed, ws, y, scal;
+  void Release() { x.Release(); packed.Release(); ws.Release(); y.Release(); scal.Release(); }
+};
+struct ConvScratch { DeviceBuffer ws; CheckRegion check[2]; };
+thread_local ConvScratch* g_conv_scratch[64] = {nullptr};
+
+// this thread's scratch on the current device (create = false: nullptr where there is none yet, or no device)
+ConvScratch* Scratch(bool create = true) {
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess) (void)hipGetLastError();
+  if (!create && (dev < 0 || dev >= 64)) return nullptr;
+  CHECK(dev >= 0 && dev < 64) << "no usable HIP device (index " << dev << ")";
+  if (!g_conv_scratch[dev] && create) g_conv_scratch[dev] = new ConvScratch();
+  return g_conv_scratch[dev];
+}
 }  // namespace
 
 template <typename Dtype>
 void ConvolutionLayer<Dtype>::ReleaseCheckScratch() {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64 || !g_check_scratch[dev]) { (void)hipGetLastError(); return; }
-  delete g_check_scratch[dev];      // (DeviceBuffer's destructor frees)
-  g_check_scratch[dev] = nullptr;
+  if (ConvScratch* s = Scratch(false))
+    for (CheckRegion& r : s->check) r.Release();
 }
 
 template <typename Dtype>
-double ConvolutionLayer<Dtype>::ErrorAgainstDirect(const vector<Blob<Dtype>*>& bottom, const vector<Blob<Dtype>*>& top) {
-  last_check_vacuous_ = false;
-  Plan(bottom[0]->num(), bottom[0]->height(), bottom[0]->width());
-  const std::string kname = mscnn_conv2d_plan_kernel(plan_);
-  if (kname.compare(0, 8, "winograd") != 0 || bottom[0]->count() == 0) return 0.0;
-  if (roi_src_ && roi_src_->pending() && bottom[0] == roi_src_->window()) roi_src_->Materialize();      // the check reads the blob
-  // a second, direct plan of the same layer with its own packed weights and workspace; everything is released on return
-  mscnn_conv_desc d;
-  d.N = bottom[0]->num(); d.Cin = channels_; d.H = bottom[0]->height(); d.W = bottom[0]->width(); d.Cout = num_output_;
-  d.Kh = kernel_h_; d.Kw = kernel_w_; d.pad_h = pad_h_; d.pad_w = pad_w_; d.stride_h = stride_h_; d.stride_w = stride_w_;
-  d.group = group_; d.relu = relu_ ? 1 : 0; d.algo = MSCNN_CONV_ALGO_DIRECT; d.tune_variant = d.tune_grid = d.tune_flags = 0;
-  mscnn_conv_plan* dp = nullptr;
-  MSCNN_CHECK(mscnn_conv2d_plan_create(&d, &dp));
-  int sdev = 0;
-  HIP_CHECK(hipGetDevice(&sdev));
-  CHECK(sdev >= 0 && sdev < 64);
-  if (!g_check_scratch[sdev]) g_check_scratch[sdev] = new CheckScratch();
-  DeviceBuffer &packed = g_check_scratch[sdev]->packed, &ws = g_check_scratch[sdev]->ws, &y = g_check_scratch[sdev]->y, &err = g_check_scratch[sdev]->err;
-  const size_t pb = mscnn_conv2d_packed_weight_bytes(dp), wb = mscnn_conv2d_workspace_bytes(dp);
-  float* pk = pb ? static_cast<float*>(packed.Reserve(pb)) : nullptr;
-  const float* w = this->blobs_[0]->gpu_data();
-  MSCNN_CHECK(mscnn_conv2d_pack_weights(dp, w, pk, S()));
-  float* yd = static_cast<float*>(y.Reserve(sizeof(float) * top[0]->count()));
-  float* ed = static_cast<float*>(err.Reserve(sizeof(double) * 2));
-  double* sd = reinterpret_cast<double*>(ed) + 1;
-  MSCNN_CHECK(mscnn_conv2d_fwd_f32(dp, bottom[0]->gpu_data(), w, pk, bias_term_ ? this->blobs_[1]->gpu_data() : nullptr, yd,
-                                   wb ? ws.Reserve(wb) : nullptr, wb, S()));
-  // The metric: max |dy| / max(1, |y|, rms(y)).  On unit-scale activations this is the parity metric of the tests (rms ~ 1 .. 3); on
-  // hot ones (rms 10 .. 100, trained nets) an element near zero is the difference of partial sums far larger than itself, where
-  // two fp32 summation orders of the DIRECT form already differ by more than 1e-4 of 1 -- the floor follows the blob's scale.
-  MSCNN_CHECK(mscnn_sum_squares_f32(bottom[0]->gpu_data(), (size_t)bottom[0]->count(), sd, S()));
-  double ssx = 0.0;
-  HIP_CHECK(hipMemcpyAsync(&ssx, sd, sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)S()));
-  MSCNN_CHECK(mscnn_sum_squares_f32(yd, (size_t)top[0]->count(), sd, S()));
-  double ss = 0.0;
-  HIP_CHECK(hipMemcpyAsync(&ss, sd, sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)S()));
-  HIP_CHECK(hipStreamSynchronize((hipStream_t)S()));
-  last_check_vacuous_ = !(ssx > 0.0);      // an all-zero bottom: both forms return the bias, the comparison is empty
-  const float rms = (float)std::sqrt(ss / (double)top[0]->count());
-  MSCNN_CHECK(mscnn_max_rel_diff_f32(top[0]->gpu_data(), yd, (size_t)top[0]->count(), rms > 1.0f ? rms : 1.0f, ed, S()));
-  float e = 0.f;
-  HIP_CHECK(hipMemcpyAsync(&e, ed, sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)S()));
-  HIP_CHECK(hipStreamSynchronize((hipStream_t)S()));
-  mscnn_conv2d_plan_destroy(dp);
-  return e;
+bool ConvolutionLayer<Dtype>::WinogradCheckApplies() const {
+  return algo_ != MSCNN_CONV_ALGO_DIRECT && algo_ != MSCNN_CONV_ALGO_F16 && plan_ && std::strncmp(mscnn_conv2d_plan_kernel(plan_), "winograd", 8) == 0;
 }
 
-namespace {
-// the band checks' own scratch (separate from CheckScratch: a band check may still be running on the device when a first-forward
-// check of another layer reserves -- and possibly re-allocates -- its buffers)
-struct BandScratch {
-  DeviceBuffer x, packed, ws, y, scal;
-  float* host = nullptr;      // pinned: one verdict word per layer that ever ran a band check on this (thread, device)
-  int host_used = 0;
-  static constexpr int kHostWords = 1024;
-};
-thread_local BandScratch* g_band_scratch[64] = {nullptr};
-}  // namespace
-
 template <typename Dtype>
-bool ConvolutionLayer<Dtype>::BeginBandCheck(const vector<Blob<Dtype>*>& bottom, const vector<Blob<Dtype>*>& top, int band_seq) {
-  if (band_.inflight || bottom[0]->count() == 0 || top[0]->count() == 0 || top_stale_ || !plan_) return false;
-  if (std::strncmp(mscnn_conv2d_plan_kernel(plan_), "winograd", 8) != 0) return false;
-  const int N = bottom[0]->num(), H = bottom[0]->height(), W = bottom[0]->width();
-  const int Ho = top[0]->height(), Wo = top[0]->width();
-  const bool roi_pending = roi_src_ && roi_src_->pending() && bottom[0] == roi_src_->window();
+typename ConvolutionLayer<Dtype>::CheckBand ConvolutionLayer<Dtype>::BandOf(int N, int H, int Ho, bool roi_pending, int band) const {
+  CheckBand b = {false, 0, N, 0, Ho, 0, H};      // the whole layer
+  if (band < 0) return b;
   // the band: rows [r0, r0 + rows) of every image with a one-row halo (3x3 / pad 1 / stride 1 on a map of >= 32 rows), else
   // images [n0, n0 + bn) whole
-  const bool by_rows = kernel_h_ == 3 && kernel_w_ == 3 && pad_h_ == 1 && pad_w_ == 1 && stride_h_ == 1 && stride_w_ == 1 && H >= 32 && !roi_pending;
+  b.by_rows = kernel_h_ == 3 && kernel_w_ == 3 && pad_h_ == 1 && pad_w_ == 1 && stride_h_ == 1 && stride_w_ == 1 && H >= 32 && !roi_pending;
   // its size: what the direct kernel recomputes in ~30 us (kBandFlops of the layer's direct-convolution FLOPs; the halo rows count),
   // never more than an eighth of the layer -- conv2_2: 6 of 288 rows, conv4_x: 2 of 72, roi_c1: 10 ROIs
   const double kBandFlops = 2.5e9, flops = std::max(1.0, mscnn_conv2d_plan_flops(plan_));
-  int bn = N, n0 = 0, r0 = 0, rows = Ho, in0 = 0, bh = H;
-  if (by_rows) {
+  if (b.by_rows) {
     const int hb = std::max(2, std::min((H + 7) / 8, (int)(H * kBandFlops / flops) - 2)), nb = (H + hb - 1) / hb;
-    r0 = (band_seq % nb) * hb;
-    rows = std::min(hb, H - r0);
-    in0 = std::max(r0 - 1, 0);
-    bh = std::min(r0 + rows + 1, H) - in0;
+    b.r0 = (band % nb) * hb;
+    b.rows = std::min(hb, H - b.r0);
+    b.in0 = std::max(b.r0 - 1, 0);
+    b.bh = std::min(b.r0 + b.rows + 1, H) - b.in0;
   } else {
     const int per = std::max(1, std::min((N + 7) / 8, (int)(N * kBandFlops / flops))), nb = (N + per - 1) / per;
-    n0 = (band_seq % nb) * per;
-    bn = std::min(per, N - n0);
+    b.n0 = (band % nb) * per;
+    b.bn = std::min(per, N - b.n0);
   }
-  int dev = 0;
-  HIP_CHECK(hipGetDevice(&dev));
-  CHECK(dev >= 0 && dev < 64);
-  if (!g_band_scratch[dev]) {
+  return b;
+}
+
+template <typename Dtype>
+bool ConvolutionLayer<Dtype>::BeginCheck(const vector<Blob<Dtype>*>& bottom, const vector<Blob<Dtype>*>& top, CheckUse use) {
+  Check& ck = check_[use];
+  if (ck.inflight || bottom[0]->count() == 0 || top[0]->count() == 0 || top_stale_ || !WinogradCheckApplies()) return false;
+  CHECK(verdict_) << "layer " << this->layer_param_.name() << ": no pinned verdict record (no HIP device at LayerSetUp)";
+  bool roi_pending = roi_src_ && roi_src_->pending() && bottom[0] == roi_src_->window();
+  if (roi_pending && use == kWhole) { roi_src_->Materialize(); roi_pending = false; }      // the whole-layer check reads the blob
+  const int N = bottom[0]->num(), H = bottom[0]->height(), W = bottom[0]->width();
+  const int Ho = top[0]->height(), Wo = top[0]->width();
+  const CheckBand b = BandOf(N, H, Ho, roi_pending, use == kWhole ? -1 : next_band_);
+  CheckRegion& sc = Scratch()->check[use];
+  if (use == kBand && !sc.scal.get()) {
     // everything a band check of ANY layer of these nets needs, once (a watch frame must not pay an allocation -- and the device
     // synchronisation of the hipFree behind a growing buffer -- the first time each layer's turn comes: that was + 0.6 ms on four frames
-    // of the first trip round the layers, tools/sessions/r06_s13.sh): a 512 -> 512 / 1024 -> 512 direct plan's packed weights, the
-    // direct kernel's stream-K slabs, the band and its output
-    g_band_scratch[dev] = new BandScratch();
-    BandScratch& s0 = *g_band_scratch[dev];
-    s0.packed.Reserve((size_t)24 << 20); s0.ws.Reserve((size_t)96 << 20); s0.x.Reserve((size_t)8 << 20); s0.y.Reserve((size_t)8 << 20);
-    s0.scal.Reserve(32);
-    HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&s0.host), sizeof(float) * BandScratch::kHostWords, hipHostMallocDefault));
+    // of the first trip round the layers): a 512 -> 512 / 1024 -> 512 direct plan's packed weights, the direct kernel's stream-K slabs,
+    // the band and its output
+    sc.packed.Reserve((size_t)24 << 20); sc.ws.Reserve((size_t)96 << 20); sc.x.Reserve((size_t)8 << 20); sc.y.Reserve((size_t)8 << 20);
   }
-  BandScratch& sc = *g_band_scratch[dev];
   hipStream_t st = (hipStream_t)S();
-  // the band of the bottom, contiguous
-  const size_t plane_in = (size_t)H * W, band_in = (size_t)bh * W;
-  const float* xb = nullptr;
-  if (by_rows) {
+  // the compared images / rows of the bottom, contiguous
+  const size_t plane_in = (size_t)H * W, band_in = (size_t)b.bh * W;
+  const float* xb = bottom[0]->gpu_data() + (size_t)b.n0 * channels_ * plane_in;
+  if (b.by_rows) {
     float* xd = static_cast<float*>(sc.x.Reserve(sizeof(float) * (size_t)N * channels_ * band_in));
-    HIP_CHECK(hipMemcpy2DAsync(xd, sizeof(float) * band_in, bottom[0]->gpu_data() + (size_t)in0 * W, sizeof(float) * plane_in,
+    HIP_CHECK(hipMemcpy2DAsync(xd, sizeof(float) * band_in, bottom[0]->gpu_data() + (size_t)b.in0 * W, sizeof(float) * plane_in,
                                sizeof(float) * band_in, (size_t)N * channels_, hipMemcpyDeviceToDevice, st));
     xb = xd;
   } else if (roi_pending) {      // the R x 2C x ph x pw blob was never written (pooled inside roi_c1's input stage): pool the band's ROIs
     ROIPoolingLayer<Dtype>* a = roi_src_;
-    ROIPoolingLayer<Dtype>* b = roi_src_->partner();
+    ROIPoolingLayer<Dtype>* p = roi_src_->partner();
     const vector<Blob<Dtype>*>& pb = a->pending_bottoms();
-    if (!b || pb.size() != 2 || pb[1]->num() != N || a->channels() + b->channels() != channels_) return false;
-    float* xd = static_cast<float*>(sc.x.Reserve(sizeof(float) * (size_t)bn * channels_ * plane_in));
-    ROIPoolingLayer<Dtype>* both[2] = {a, b};
+    if (!p || pb.size() != 2 || pb[1]->num() != N || a->channels() + p->channels() != channels_) return false;
+    float* xd = static_cast<float*>(sc.x.Reserve(sizeof(float) * (size_t)b.bn * channels_ * plane_in));
+    ROIPoolingLayer<Dtype>* both[2] = {a, p};
     for (ROIPoolingLayer<Dtype>* r : both)
-      MSCNN_CHECK(mscnn_roipool_fwd_f32(pb[0]->gpu_data(), pb[1]->gpu_data() + (size_t)n0 * 5, xd, bn, pb[0]->num(), r->channels(), pb[0]->height(),
-                                        pb[0]->width(), r->pooled_height(), r->pooled_width(), r->spatial_scale(), r->pad_ratio(), channels_,
-                                        r->window_c_offset(), st));
+      MSCNN_CHECK(mscnn_roipool_fwd_f32(pb[0]->gpu_data(), pb[1]->gpu_data() + (size_t)b.n0 * 5, xd, b.bn, pb[0]->num(), r->channels(),
+                                        pb[0]->height(), pb[0]->width(), r->pooled_height(), r->pooled_width(), r->spatial_scale(),
+                                        r->pad_ratio(), channels_, r->window_c_offset(), st));
     xb = xd;
-  } else {
-    xb = bottom[0]->gpu_data() + (size_t)n0 * channels_ * plane_in;
   }
-  // a direct plan of the band's shape with its own packed weights and workspace
+  // a direct plan of the compared shape with its own packed weights and workspace
   mscnn_conv_desc d;
-  d.N = bn; d.Cin = channels_; d.H = bh; d.W = W; d.Cout = num_output_;
-  d.Kh = kernel_h_; d.Kw = kernel_w_; d.pad_h = pad_h_; d.pad_w = pad_w_; d.stride_h = stride_h_; d.stride_w = stride_w_;
-  d.group = group_; d.relu = relu_ ? 1 : 0; d.algo = MSCNN_CONV_ALGO_DIRECT; d.tune_variant = d.tune_grid = d.tune_flags = 0;
-  if (band_.plan) { mscnn_conv2d_plan_destroy(band_.plan); band_.plan = nullptr; }
-  MSCNN_CHECK(mscnn_conv2d_plan_create(&d, &band_.plan));
-  const size_t pbytes = mscnn_conv2d_packed_weight_bytes(band_.plan), wbytes = mscnn_conv2d_workspace_bytes(band_.plan);
+  d.N = b.bn; d.Cin = channels_; d.H = b.bh; d.W = W; d.Cout = num_output_; d.Kh = kernel_h_; d.Kw = kernel_w_;
+  d.pad_h = pad_h_; d.pad_w = pad_w_; d.stride_h = stride_h_; d.stride_w = stride_w_; d.group = group_; d.relu = relu_ ? 1 : 0;
+  d.algo = MSCNN_CONV_ALGO_DIRECT; d.tune_variant = d.tune_grid = d.tune_flags = 0;
+  if (ck.plan) { mscnn_conv2d_plan_destroy(ck.plan); ck.plan = nullptr; }
+  MSCNN_CHECK(mscnn_conv2d_plan_create(&d, &ck.plan));
+  const size_t pbytes = mscnn_conv2d_packed_weight_bytes(ck.plan), wbytes = mscnn_conv2d_workspace_bytes(ck.plan);
   float* pk = pbytes ? static_cast<float*>(sc.packed.Reserve(pbytes)) : nullptr;
   const float* w = this->blobs_[0]->gpu_data();
-  MSCNN_CHECK(mscnn_conv2d_pack_weights(band_.plan, w, pk, S()));
-  const int bho = by_rows ? bh : Ho;                                   // rows of the direct band's output
-  const size_t ycount = (size_t)bn * num_output_ * bho * Wo;
+  MSCNN_CHECK(mscnn_conv2d_pack_weights(ck.plan, w, pk, st));
+  const int bho = b.by_rows ? b.bh : Ho;                               // rows of the direct output
+  const size_t ycount = (size_t)b.bn * num_output_ * bho * Wo;
   float* yd = static_cast<float*>(sc.y.Reserve(sizeof(float) * ycount));
   unsigned char* scal = static_cast<unsigned char*>(sc.scal.Reserve(32));
   double* ss = reinterpret_cast<double*>(scal);
-  float* ed = reinterpret_cast<float*>(scal + 16);
-  MSCNN_CHECK(mscnn_conv2d_fwd_f32(band_.plan, xb, w, pk, bias_term_ ? this->blobs_[1]->gpu_data() : nullptr, yd, wbytes ? sc.ws.Reserve(wbytes) : nullptr,
-                                   wbytes, S()));
-  MSCNN_CHECK(mscnn_sum_squares_f32(yd, ycount, ss, S()));
-  // rows [r0 - in0, + rows) of the direct band are the ones whose halo is real (rows beside them saw the band's artificial zero padding)
-  const float* tb = top[0]->gpu_data() + (by_rows ? (size_t)r0 * Wo : (size_t)n0 * num_output_ * Ho * Wo);
-  if (by_rows)
-    MSCNN_CHECK(mscnn_max_rel_diff_strided_f32(tb, (size_t)Ho * Wo, yd + (size_t)(r0 - in0) * Wo, (size_t)bho * Wo, (size_t)N * num_output_,
-                                               (size_t)rows * Wo, ss, (double)ycount, ed, S()));
+  Verdict* vd = reinterpret_cast<Verdict*>(scal + 8);
+  MSCNN_CHECK(mscnn_conv2d_fwd_f32(ck.plan, xb, w, pk, bias_term_ ? this->blobs_[1]->gpu_data() : nullptr, yd, wbytes ? sc.ws.Reserve(wbytes) : nullptr,
+                                   wbytes, st));
+  // The metric: max |dy| / max(1, |y|, rms(y)).  On unit-scale activations this is the parity metric of the tests (rms ~ 1 .. 3); on
+  // hot ones (rms 10 .. 100, trained nets) an element near zero is the difference of partial sums far larger than itself, where
+  // two fp32 summation orders of the DIRECT form already differ by more than 1e-4 of 1 -- the floor follows the blob's scale, read on
+  // the device from the preceding reduction.
+  if (use == kWhole) MSCNN_CHECK(mscnn_sum_squares_f32(bottom[0]->gpu_data(), (size_t)bottom[0]->count(), &vd->ssx, st));
+  MSCNN_CHECK(mscnn_sum_squares_f32(yd, ycount, ss, st));
+  // rows [r0 - in0, + rows) of a band's direct output are the ones whose halo is real (rows beside them saw the band's artificial zero
+  // padding); images are compared whole
+  const float* tb = top[0]->gpu_data() + (b.by_rows ? (size_t)b.r0 * Wo : (size_t)b.n0 * num_output_ * Ho * Wo);
+  if (b.by_rows)
+    MSCNN_CHECK(mscnn_max_rel_diff_strided_f32(tb, (size_t)Ho * Wo, yd + (size_t)(b.r0 - b.in0) * Wo, (size_t)bho * Wo, (size_t)N * num_output_,
+                                               (size_t)b.rows * Wo, ss, (double)ycount, &vd->err, st));
   else
-    MSCNN_CHECK(mscnn_max_rel_diff_strided_f32(tb, ycount, yd, ycount, 1, ycount, ss, (double)ycount, ed, S()));
-  if (!band_.host) {      // this layer's word of the (thread, device)'s pinned verdict array
-    CHECK_LT(sc.host_used, BandScratch::kHostWords);
-    band_.host = sc.host + sc.host_used++;
-  }
-  if (!band_.done) { hipEvent_t e; HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); band_.done = e; }
-  HIP_CHECK(hipMemcpyAsync(band_.host, ed, sizeof(float), hipMemcpyDeviceToHost, st));
-  HIP_CHECK(hipEventRecord((hipEvent_t)band_.done, st));
-  band_.inflight = true;
+    MSCNN_CHECK(mscnn_max_rel_diff_strided_f32(tb, ycount, yd, ycount, 1, ycount, ss, (double)ycount, &vd->err, st));
+  if (!ck.done) { hipEvent_t e; HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); ck.done = e; }
+  HIP_CHECK(hipMemcpyAsync(verdict_ + use, vd, sizeof(Verdict), hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipEventRecord((hipEvent_t)ck.done, st));
+  ck.inflight = true;
+  if (use == kBand) ++next_band_;
   return true;
 }
 
 template <typename Dtype>
-int ConvolutionLayer<Dtype>::PollBandCheck(double* err, bool wait) {
-  if (!band_.inflight) return 0;
-  if (wait) HIP_CHECK(hipEventSynchronize((hipEvent_t)band_.done));
+int ConvolutionLayer<Dtype>::PollCheck(CheckUse use, double* err, bool wait, bool* vacuous) {
+  Check& ck = check_[use];
+  if (!ck.inflight) return 0;
+  if (wait) HIP_CHECK(hipEventSynchronize((hipEvent_t)ck.done));
   else {
-    const hipError_t q = hipEventQuery((hipEvent_t)band_.done);
+    const hipError_t q = hipEventQuery((hipEvent_t)ck.done);
     if (q == hipErrorNotReady) return 1;
     HIP_CHECK(q);
   }
-  band_.inflight = false;
-  *err = (double)band_.host[0];
-  mscnn_conv2d_plan_destroy(band_.plan);
-  band_.plan = nullptr;
+  ck.inflight = false;
+  *err = (double)verdict_[use].err;
+  if (vacuous) *vacuous = !(verdict_[use].ssx > 0.0);
+  mscnn_conv2d_plan_destroy(ck.plan);
+  ck.plan = nullptr;
   return 2;
+}
+
+template <typename Dtype>
+double ConvolutionLayer<Dtype>::ErrorAgainstDirect(const vector<Blob<Dtype>*>& bottom, const vector<Blob<Dtype>*>& top, bool* vacuous) {
+  if (vacuous) *vacuous = false;
+  Plan(bottom[0]->num(), bottom[0]->height(), bottom[0]->width());
+  double e = 0.0;
+  if (BeginCheck(bottom, top, kWhole)) PollCheck(kWhole, &e, true, vacuous);
+  return e;
 }
 
 template <typename Dtype>
@@ -434,9 +418,7 @@ void ConvolutionLayer<Dtype>::Forward_gpu(const vector<Blob<Dtype>*>& bottom, co
   Plan(bottom[0]->num(), bottom[0]->height(), bottom[0]->width());
   // AUTO plans per shape: a layer whose first bottoms ran a direct kernel (roi_c1 with a handful of ROIs) may get a Winograd form for a
   // later one -- the first Winograd result on these weights is checked whenever it comes, not only in the first Forward
-  if (!selfcheck_pending_ && !wino_checked_ && selfcheck_tol_ > 0 && algo_ != MSCNN_CONV_ALGO_DIRECT && algo_ != MSCNN_CONV_ALGO_F16 &&
-      std::strncmp(mscnn_conv2d_plan_kernel(plan_), "winograd", 8) == 0)
-    selfcheck_pending_ = true;
+  if (!selfcheck_pending_ && !wino_checked_ && selfcheck_tol_ > 0 && WinogradCheckApplies()) selfcheck_pending_ = true;
   const float* w = this->blobs_[0]->gpu_data();
   const size_t pbytes = mscnn_conv2d_packed_weight_bytes(plan_);
   float* packed = pbytes ? static_cast<float*>(packed_.Reserve(pbytes)) : nullptr;
@@ -444,16 +426,7 @@ void ConvolutionLayer<Dtype>::Forward_gpu(const vector<Blob<Dtype>*>& bottom, co
     MSCNN_CHECK(mscnn_conv2d_pack_weights(plan_, w, packed, S()));
     weights_dirty_ = false;
   }
-  // Transient workspace (stream-K slabs, Winograd V / M planes: up to 0.8 GB for conv2_2): the layers of a net run one after
-  // the other on one stream, so all conv layers of a host THREAD share ONE buffer per device instead of 3 GB of per-layer
-  // buffers.  Thread-local like the Caffe singleton itself (a thread is a device context, common.cpp:13-20): two threads may
-  // drive nets on the same device without sharing scratch.  (Leaked on thread exit on purpose: a destructor could run after
-  // the HIP runtime has been torn down.)
-  static thread_local DeviceBuffer* shared_ws[64] = {nullptr};
-  int dev = 0;
-  HIP_CHECK(hipGetDevice(&dev));
-  CHECK(dev >= 0 && dev < 64);
-  if (!shared_ws[dev]) shared_ws[dev] = new DeviceBuffer();
+  DeviceBuffer& shared_ws = Scratch()->ws;      // (one transient workspace for all conv layers of this thread on this device)
   const size_t wbytes = mscnn_conv2d_workspace_bytes(plan_);
   // A chain of same-resolution F(4x4,3x3) layers (ChainTo): the head -- the first member whose planes nobody prepared -- plans every
   // member, decides how far the chain goes this Forward and gives each member its own region of the shared buffer (a member's output
@@ -478,9 +451,9 @@ void ConvolutionLayer<Dtype>::Forward_gpu(const vector<Blob<Dtype>*>& bottom, co
         extent = std::max(extent, std::max(c->ws_off_ + cb, nx->ws_off_ + nb));
       }
     }
-    if (extent) shared_ws[dev]->Reserve(extent);
+    if (extent) shared_ws.Reserve(extent);
   }
-  void* ws = wbytes ? static_cast<unsigned char*>(shared_ws[dev]->Reserve(ws_off_ + wbytes)) + ws_off_ : nullptr;
+  void* ws = wbytes ? static_cast<unsigned char*>(shared_ws.Reserve(ws_off_ + wbytes)) + ws_off_ : nullptr;
   const float* bias = bias_term_ ? this->blobs_[1]->gpu_data() : nullptr;
   {
     const bool pub = amax_wanted_ && amax_out_ && mscnn_conv2d_plan_publishes_amax(plan_);
@@ -504,7 +477,7 @@ void ConvolutionLayer<Dtype>::Forward_gpu(const vector<Blob<Dtype>*>& bottom, co
                               ? static_cast<const float*>(roi_maps_.get()) : nullptr;
       roi_maps_feat_ = nullptr;
       const size_t fbytes = maps ? wbytes : mscnn_conv2d_roipool_workspace_bytes(plan_, pb[0]->num(), C, pb[0]->height(), pb[0]->width());
-      void* fws = shared_ws[dev]->Reserve(fbytes);
+      void* fws = shared_ws.Reserve(fbytes);
       MSCNN_CHECK(mscnn_conv2d_fwd_roipool_pair_f32(plan_, pb[0]->gpu_data(), maps, pb[0]->num(), C, pb[0]->height(), pb[0]->width(),
                                                     pb[1]->gpu_data(), a->spatial_scale(), lo->pad_ratio(), hi->pad_ratio(), packed, bias,
                                                     top[0]->mutable_gpu_data(), fws, fbytes, S()));
@@ -528,7 +501,7 @@ void ConvolutionLayer<Dtype>::Forward_gpu(const vector<Blob<Dtype>*>& bottom, co
     // is then NOT written: top_stale_)
     ConvolutionLayer* nx = fuse_next_now_ ? chain_next_ : nullptr;
     const size_t nb = nx ? mscnn_conv2d_workspace_bytes(nx->plan_) : 0;
-    void* nws = nx ? static_cast<unsigned char*>(shared_ws[dev]->Reserve(next_off_ + nb)) + next_off_ : nullptr;
+    void* nws = nx ? static_cast<unsigned char*>(shared_ws.Reserve(next_off_ + nb)) + next_off_ : nullptr;
     MSCNN_CHECK(mscnn_conv2d_fwd_chain_f32(plan_, nx ? nx->plan_ : nullptr, was_prepared ? nullptr : bottom[0]->gpu_data(), packed, bias,
                                            (nx && !keep_top_) || pool_only ? nullptr : top[0]->mutable_gpu_data(), nx ? nullptr : pooled, ws, wbytes, nws,
                                            nb, S()));
@@ -547,15 +520,15 @@ void ConvolutionLayer<Dtype>::Forward_gpu(const vector<Blob<Dtype>*>& bottom, co
   }
   // Safe by default (header): a Winograd result is never handed out unchecked on new weights -- compare it with the direct kernel
   // on this very bottom once; off by more than the tolerance => direct kernel from now on, tops recomputed before returning.
+  // (opted out, or nothing to check -- a direct kernel for THIS shape, see the re-arming at the top of Forward_gpu: disarmed)
   if (selfcheck_pending_ && bottom[0]->count() > 0) {
-    if (!(selfcheck_tol_ > 0 && algo_ != MSCNN_CONV_ALGO_DIRECT && algo_ != MSCNN_CONV_ALGO_F16)) {
-      selfcheck_pending_ = false;      // opted out / an algorithm with nothing to check
-    } else if (std::strncmp(mscnn_conv2d_plan_kernel(plan_), "winograd", 8) == 0) {
-      selfcheck_pending_ = false;
-      selfcheck_err_ = ErrorAgainstDirect(bottom, top);
-      if (last_check_vacuous_) selfcheck_pending_ = true;      // a zero warm-up frame checks nothing: the next bottom is checked again
+    selfcheck_pending_ = false;
+    if (selfcheck_tol_ > 0 && WinogradCheckApplies()) {
+      bool vacuous = false;
+      selfcheck_err_ = ErrorAgainstDirect(bottom, top, &vacuous);
+      if (vacuous) selfcheck_pending_ = true;      // a zero warm-up frame checks nothing: the next bottom is checked again
       else selfcheck_ran_ = wino_checked_ = true;
-      if (!last_check_vacuous_ && !(selfcheck_err_ <= selfcheck_tol_)) {      // (NaN counts as a failure)
+      if (!vacuous && !(selfcheck_err_ <= selfcheck_tol_)) {      // (NaN counts as a failure)
         LOG(WARNING) << "layer " << this->layer_param_.name() << ": Winograd result off the direct sum by " << selfcheck_err_ << " > "
                      << selfcheck_tol_ << " on the first input after a weight change: using the direct kernel";
         set_algo(MSCNN_CONV_ALGO_DIRECT);
@@ -564,7 +537,6 @@ void ConvolutionLayer<Dtype>::Forward_gpu(const vector<Blob<Dtype>*>& bottom, co
         Forward_gpu(bottom, top);
       }
     }
-    else selfcheck_pending_ = false;      // a direct kernel for THIS shape (see the re-arming at the top of Forward_gpu)
   }
 }
 

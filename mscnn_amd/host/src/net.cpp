@@ -501,19 +501,25 @@ vector<int> Net<Dtype>::CalibrateNumerics(double tol) {
   for (size_t i = 0; i < layers_.size(); ++i) {
     calib_err_[i] = 0.0;
     ConvolutionLayer<Dtype>* c = dynamic_cast<ConvolutionLayer<Dtype>*>(layers_[i].get());
-    if (!c || c->algo() == 1 || c->algo() == 4) continue;      // direct already / fp16 mode has its own tolerance policy
+    if (!c) continue;
     for (int bb : bottom_id_vecs_[i]) MaterializeBlob(bb);      // (blobs inside a convolution chain are written on demand)
     for (int tb : top_id_vecs_[i]) MaterializeBlob(tb);
-    calib_err_[i] = c->ErrorAgainstDirect(bottom_vecs_[i], top_vecs_[i]);
-    if (!(calib_err_[i] <= tol)) {      // (NaN counts as a failure)
-      LOG(WARNING) << "layer " << layer_names_[i] << ": Winograd result off the direct sum by " << calib_err_[i] << " > " << tol
-                   << " on the calibration input: using the direct kernel";
-      c->set_algo(1);
-      c->set_calibrated_direct(true);
-      switched.push_back((int)i);
-    }
+    calib_err_[i] = c->ErrorAgainstDirect(bottom_vecs_[i], top_vecs_[i]);      // (0: no Winograd form to check)
+    FallBackIfStrayed((int)i, calib_err_[i], tol, "on the calibration input", &switched);
   }
   return switched;
+}
+
+// the verdict of a calibration or watch check: a layer whose Winograd form strayed by more than tol runs the direct kernel for good
+template <typename Dtype>
+void Net<Dtype>::FallBackIfStrayed(int i, double err, double tol, const char* where, vector<int>* switched) {
+  ConvolutionLayer<Dtype>* c = static_cast<ConvolutionLayer<Dtype>*>(layers_[i].get());
+  if (err <= tol || c->algo() == MSCNN_CONV_ALGO_DIRECT) return;      // (NaN counts as a failure)
+  LOG(WARNING) << "layer " << layer_names_[i] << ": Winograd result off the direct sum by " << err << " > " << tol << " " << where
+               << ": using the direct kernel";
+  c->set_algo(MSCNN_CONV_ALGO_DIRECT);
+  c->set_calibrated_direct(true);
+  switched->push_back(i);
 }
 
 template <typename Dtype>
@@ -535,19 +541,18 @@ void Net<Dtype>::SetNumericsWatch(int period, double tol) {
 
 // The numerics watch (round 6 form: no check inside a frame's latency).  On a watch frame ONE Winograd layer -- round robin -- has its
 // bottom and top written as blobs although it stays in its convolution chain (the producers write y beside the next layer's planes
-// / the pooled map: ConvolutionLayer::set_keep_top), and one band of it (round robin as well) is recomputed with
-// the direct kernel BEHIND the frame on the same stream (ConvolutionLayer::BeginBandCheck: a copy of the band, a direct convolution of
-// that band -- ~30 us of work --, two reductions, 4 bytes to pinned memory, an event).  Nobody waits for it: the verdict is collected at
-// the end of a later whole forward (or when somebody asks for the watch's state) and, when the layer strayed, it runs the direct
-// kernel from the frame after that.
+// / the pooled map: ConvolutionLayer::set_keep_top), and the layer's next band (each layer goes round its own bands) is recomputed
+// with the direct kernel BEHIND the frame on the same stream (ConvolutionLayer::BeginCheck(kBand): a copy of the band, a direct
+// convolution of that band -- ~30 us of work --, two reductions, the verdict to pinned memory, an event).  Nobody waits for it: the
+// verdict is collected at the end of a later whole forward (or when somebody asks for the watch's state) and, when the layer strayed,
+// it runs the direct kernel from the frame after that.
 template <typename Dtype>
 int Net<Dtype>::NextWatchLayer() const {
   const int L = (int)layers_.size();
   for (int k = 0; k < L; ++k) {
     const int i = (watch_next_ + k) % L;
     ConvolutionLayer<Dtype>* c = dynamic_cast<ConvolutionLayer<Dtype>*>(layers_[i].get());
-    if (!c || fused_away_[i] || c->algo() == 1 || c->algo() == 4 || std::strncmp(c->kernel_name(), "winograd", 8) != 0) continue;
-    return i;
+    if (c && c->WinogradCheckApplies()) return i;
   }
   return -1;
 }
@@ -556,20 +561,13 @@ template <typename Dtype>
 void Net<Dtype>::WatchCollect(bool wait) {
   if (watch_pending_ < 0) return;
   const int i = watch_pending_;
-  ConvolutionLayer<Dtype>* c = static_cast<ConvolutionLayer<Dtype>*>(layers_[i].get());
   double e = 0.0;
-  const int r = c->PollBandCheck(&e, wait);
+  const int r = static_cast<ConvolutionLayer<Dtype>*>(layers_[i].get())->PollCheck(ConvolutionLayer<Dtype>::kBand, &e, wait);
   if (r == 1) return;
   watch_pending_ = -1;
   if (r != 2) return;
   calib_err_[i] = e;
-  if (!(e <= watch_tol_) && c->algo() != 1) {      // (NaN counts as a failure)
-    LOG(WARNING) << "layer " << layer_names_[i] << ": Winograd result off the direct sum by " << e << " > " << watch_tol_
-                 << " on a live frame: using the direct kernel from the next frame on";
-    c->set_algo(1);
-    c->set_calibrated_direct(true);
-    watch_switched_.push_back(i);
-  }
+  FallBackIfStrayed(i, e, watch_tol_, "on a live frame", &watch_switched_);
 }
 
 template <typename Dtype>
@@ -731,8 +729,7 @@ Dtype Net<Dtype>::ForwardFromTo(int start, int end) {
   if (watch_layer >= 0 && !handoff_restart) {
     ConvolutionLayer<Dtype>* c = static_cast<ConvolutionLayer<Dtype>*>(layers_[watch_layer].get());
     watch_next_ = (watch_layer + 1) % (int)layers_.size();
-    if (watch_next_ <= watch_layer) ++watch_band_;          // one band per trip round the layers
-    if (c->BeginBandCheck(bottom_vecs_[watch_layer], top_vecs_[watch_layer], watch_band_)) {
+    if (c->BeginCheck(bottom_vecs_[watch_layer], top_vecs_[watch_layer], ConvolutionLayer<Dtype>::kBand)) {
       watch_pending_ = watch_layer;
       ++watch_checks_;
     }

@@ -584,6 +584,53 @@ def test_numerics_watch_rechecks_one_layer_per_period_on_live_frames():
     assert n.numerics_watch_state()[0] == checks
 
 
+def test_numerics_watch_moves_each_layer_to_its_next_band():
+    """the watch compared band 0 of every layer on every visit.  Each layer now goes round its own bands, one per visit:
+    on one fixed frame, the second trip round the Winograd layers measures other rows / ROIs than the first, so most layers with
+    two or more bands (a map of >= 32 rows, or several images / ROIs) report another error on their second visit."""
+    n = mnet.Net(prototxt_text=zoo.prototxt("kitti_car/mscnn-7s-576", height=192, width=384, max_nms_num=100))
+    synth.load_into(n, "mid")
+    n.set_blob("data", synth.frame(192, 384))
+    n.forward()
+    wino = [i for i, t in enumerate(n.layer_types) if t == "Convolution" and n.layer_kernel(i).startswith("winograd")]
+    shape = lambda i: n.blob_shape(n.layer_bottoms(i)[0])      # noqa: E731
+    banded = [i for i in wino if shape(i)[2] >= 32 or shape(i)[0] >= 2]
+    n.set_numerics_watch(1, 1.0)
+    seen = {i: [] for i in wino}
+    for k in range(2 * len(wino)):      # round robin in net order: check k looks at wino[k % len(wino)]
+        n.forward()
+        assert n.numerics_watch_state() == (k + 1, [])
+        i = wino[k % len(wino)]
+        seen[i].append(mnet.lib().mscnn_net_layer_calibration_err(n._h, i))
+    moved = [n.layer_names[i] for i in banded if seen[i][0] != seen[i][1]]
+    assert len(banded) >= 4 and len(moved) > len(banded) // 2, (moved, [n.layer_names[i] for i in banded], seen)
+
+
+WINO_STACK = 'name: "wino_stack"\ninput: "data" input_dim: 1 input_dim: 128 input_dim: 32 input_dim: 64\n' + "".join(
+    'layer { name: "c%d" type: "Convolution" bottom: "%s" top: "c%d" convolution_param { num_output: 128 pad: 1 kernel_size: 3 '
+    'weight_filler { type: "gaussian" std: 0.03 } } }\n' % (k, "data" if k == 0 else "c%d" % (k - 1), k) for k in range(12))
+
+
+def test_numerics_watch_checks_any_number_of_layer_instances():
+    """every layer ever band-checked kept one word of a 1024-word pinned array per (thread, device) for good, so after about
+    1024 layer instances (~80 model reloads) every watch frame failed.  Each layer now owns its verdict record: nets of twelve Winograd
+    layers are built, watched once per layer and destroyed, well past 1024 layer instances."""
+    x = np.random.default_rng(7).standard_normal((1, 128, 32, 64)).astype(np.float32)
+    total = 0
+    while total <= 1100:
+        n = mnet.Net(prototxt_text=WINO_STACK)
+        n.set_numerics_watch(1, 1.0)
+        n.set_blob("data", x)
+        n.forward()      # (plans the layers: the watch looks at planned Winograd layers)
+        L = sum(n.layer_kernel(i).startswith("winograd") for i in range(len(n.layer_names)))
+        assert L == 12, [n.layer_kernel(i) for i in range(len(n.layer_names))]
+        for _ in range(L):
+            n.forward()
+        assert n.numerics_watch_state() == (L, [])
+        total += L
+        del n
+
+
 def test_dynamic_roi_count_across_forwards():
     """R changes from image to image; Reshape propagation (layer.hpp:451-456) must follow without reallocating downwards."""
     n = mnet.Net(prototxt_text=zoo.prototxt("kitti_car/mscnn-7s-576", height=128, width=256))

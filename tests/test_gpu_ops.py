@@ -76,7 +76,7 @@ def test_parity_metric_kernels_on_device(hip):
     assert abs(float(ss.cpu()[0]) - float((ref.astype(np.float64) ** 2).sum())) <= 1e-9 * float((ref.astype(np.float64) ** 2).sum())
     want = (np.abs(a.astype(np.float64) - ref) / np.maximum(1.0, np.abs(ref))).max()
     assert abs(float(hip.max_rel_diff(dev(a), dev(ref)).cpu()[0]) - want) <= 1e-6 * want
-    # rows [r0, r0 + rows) of every plane of `a` against a band that holds rows [r0 - 1, r0 + rows + 1): what BeginBandCheck compares
+    # rows [r0, r0 + rows) of every plane of `a` against a band that holds rows [r0 - 1, r0 + rows + 1): what a band check (ConvolutionLayer::BeginCheck) compares
     r0, rows = 6, 4
     band = np.ascontiguousarray(ref[:, r0 - 1:r0 + rows + 1])
     rms = np.sqrt((band.astype(np.float64) ** 2).mean())
