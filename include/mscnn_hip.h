@@ -425,6 +425,30 @@ MSCNN_API int mscnn_detections_multi_fwd(const mscnn_detections_desc* desc, int 
                                          const float* cls_pred, const float* props, int R_all, int max_rows_per_image, void* pack_dev,
                                          int cap, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The cascade stage (mscnn_detections_cascade_fwd) for EVERY (image, cascade output, class) segment of a batched forward in one
+ * pass: three launches per 32 segments, no host read.  outputs[num_outputs], 1 <= num_outputs <= 4: each cascade output's own blob
+ * triple (boxes [R_all][5], cls_prob [R_all][ncls], props [R_all][5]; R_all common to all) -- the triples travel as kernel arguments.
+ * Rows are grouped by image with the image index in column 0 of props (DecodeBBox carries BoxOutput's through); each segment finds
+ * its rows in ITS output's props on the device.  desc[num_images * num_outputs * num_classes], indexed
+ * [(image * num_outputs + output) * num_classes + class]: cls_id (1 .. that output's ncls), ratio_*, org_*, nms_overlap; the other
+ * fields (ncls included: it comes from outputs[]) are not read.  det_thr: one value per call.  max_rows_per_image: as
+ * mscnn_detections_multi_fwd, at most 4032 -- above that run mscnn_detections_cascade_fwd per segment.  Every segment is
+ * bit-identical to mscnn_detections_cascade_fwd on its row range of its output's blobs, ids included.
+ * pack_dev: the multi pack above with K = num_outputs * num_classes in the role of num_classes --
+ * mscnn_detections_multi_pack_bytes(S, cap) bytes, S = num_images * K, cap >= K * R_all; segment (i, o, c) owns pack rows
+ * [K * row0 + (o * num_classes + c) * rows, + rows), table entry {count (-1: over the bound), rows, row0, 0}. */
+typedef struct {
+  const float* boxes;
+  const float* cls_prob;
+  const float* props;
+  int ncls;
+} mscnn_cascade_output;
+MSCNN_API size_t mscnn_detections_cascade_multi_workspace_bytes(int num_segments, int max_rows_per_image);   /* 0: over 4032 rows */
+MSCNN_API int mscnn_detections_cascade_multi_fwd(const mscnn_detections_desc* desc, float det_thr, int num_images, int num_outputs,
+                                                 int num_classes, const mscnn_cascade_output* outputs, int R_all,
+                                                 int max_rows_per_image, void* pack_dev, int cap, void* workspace,
+                                                 size_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Image pre-processing in front of net.forward -- MATLAB `run_mscnn_detection.m:64-69`:
  * imresize(uint8 image, [H W]) (bicubic, uint8 after each 1-D pass), RGB -> BGR, single, subtract the

@@ -224,6 +224,28 @@ MSCNN_NET_API int mscnn_net_unpack_detections_multi(const void* pack_host, int n
 MSCNN_NET_API int mscnn_net_detect_cascade(mscnn_net* net, const mscnn_detect_params* p, float det_thr, const char* bbox_blob,
                                            const char* prob_blob, const char* proposal_blob, double* dets_host, int* ids_host,
                                            int cap, int* num_dets, int* num_rois);
+/* The cascade stage for EVERY image, cascade output and class of the last forward in one pass (the loops of
+ * run_cascademscnn.m:91-143 over a whole batch): three launches per 32 segments (mscnn_hip.h: mscnn_detections_cascade_multi_fwd)
+ * and one stream synchronisation, and -- unlike mscnn_net_detect_cascade, which treats the blobs as one list -- never an NMS across
+ * images.  bbox_blobs / prob_blobs / proposal_blobs[num_outputs], 1 <= num_outputs <= 4: the blob triple of each cascade output
+ * (equal row counts throughout).  p[num_images * num_outputs * num_classes], indexed [(image * num_outputs + output) * num_classes
+ * + class]: cls_id, ratios, original size, nms_overlap (bbox_mean / bbox_std / proposal_thr unused); det_thr: one value per call.
+ * num_images must equal the input's N.  Output segment after segment in that order, as mscnn_net_detect_multi with num_outputs *
+ * num_classes in the role of num_classes: seg_dets[s], ids = rows of the net's blobs, image_rois[num_images] (may be NULL).  Every
+ * segment is bit-identical to mscnn_detections_cascade_fwd on the image's rows of that output's blobs; at N = 1, one output and one
+ * class it equals mscnn_net_detect_cascade.  A per-image row bound over 4032 runs the per-segment path into the same layout. */
+MSCNN_NET_API int mscnn_net_detect_cascade_multi(mscnn_net* net, const mscnn_detect_params* p, int num_images, int num_outputs,
+                                                 int num_classes, const char* const* bbox_blobs, const char* const* prob_blobs,
+                                                 const char* const* proposal_blobs, float det_thr, double* dets_host, int* ids_host,
+                                                 int cap, int* seg_dets, int* image_rois);
+/* The same into a device pack of mscnn_net_detect_cascade_multi_pack_bytes(...) bytes in HBM (cap >= num_outputs x num_classes x the
+ * forward's ROI count, else an error); asynchronous on the net's stream, *pack_dev valid until the next detect call on this net.
+ * mscnn_net_unpack_detections_multi(pack, num_images, num_outputs * num_classes, cap, ...) reads one host copy of it. */
+MSCNN_NET_API size_t mscnn_net_detect_cascade_multi_pack_bytes(int num_images, int num_outputs, int num_classes, int cap);
+MSCNN_NET_API int mscnn_net_detect_cascade_multi_device(mscnn_net* net, const mscnn_detect_params* p, int num_images, int num_outputs,
+                                                        int num_classes, const char* const* bbox_blobs, const char* const* prob_blobs,
+                                                        const char* const* proposal_blobs, float det_thr, int cap,
+                                                        const void** pack_dev);
 
 /* Multi-GPU form of the same stage (include/mscnn_dist.h gathers its result over RCCL): the detections stay in HBM, in a
  * fixed-size pack  [int32 count, int32 num_rois, int32 cap, int32 0][cap x 5 doubles x y w h prob][cap x int32 roi row]

@@ -298,7 +298,8 @@ enum { SEG_N = 0, SEG_ROW0 = 1, SEG_ROWS = 2, SEG_BAD = 3, SEG_WORDS = 4 };   //
 enum { PACK_HDR_WORDS = 4, PACK_SEG_WORDS = 4 };                              // {S, R_all, cap, 0}, {count, rows, row0, 0}
 
 struct DetMultiPtrs { int* cnt; DetBox* sbox; double* sprob; int* ssrc; DetBox* tbox; float* tprob; u64* mask; };
-__device__ __forceinline__ DetMultiPtrs det_multi_ptrs(const DetMultiArgs& a, int s) {
+template <class Args>      // DetMultiArgs or DetCascadeMultiArgs: the same workspace fields
+__device__ __forceinline__ DetMultiPtrs det_multi_ptrs(const Args& a, int s) {
   // slices: [cnt: S x SEG_WORDS ints][sbox][sprob][ssrc][tbox][tprob] per segment (max_rows each, 256-byte aligned), then the masks
   const size_t M = (size_t)a.max_rows;
   char* base = a.ws + 256 * (((size_t)a.num_segs * SEG_WORDS * sizeof(int) + 255) / 256) + (size_t)s * a.seg_stride_box;
@@ -316,12 +317,12 @@ __device__ __forceinline__ DetMultiPtrs det_multi_ptrs(const DetMultiArgs& a, in
   return p;
 }
 
-// first row whose image (column 0) is >= img, over [0, R): rows are grouped by image in ascending order
-__device__ __forceinline__ int det_image_lower_bound(const float* __restrict__ props, int R, int img) {
+// first row whose image (column 0) is >= img, over [0, R): rows are grouped by image in ascending order (stride floats per row)
+__device__ __forceinline__ int det_image_lower_bound(const float* __restrict__ props, int R, int img, int stride) {
   int lo = 0, hi = R;
   while (lo < hi) {
     const int mid = (lo + hi) >> 1;
-    if (props[(size_t)mid * 6] < (float)img) lo = mid + 1; else hi = mid;
+    if (props[(size_t)mid * stride] < (float)img) lo = mid + 1; else hi = mid;
   }
   return lo;
 }
@@ -332,7 +333,7 @@ __global__ __launch_bounds__(kSortThreads) void det_multi_transform_sort_kernel(
   const int img = s / a.num_classes;
   const DetMultiPtrs p = det_multi_ptrs(a, s);
   __shared__ int s_range[2];
-  if (threadIdx.x < 2) s_range[threadIdx.x] = det_image_lower_bound(a.props, a.R_all, img + threadIdx.x);
+  if (threadIdx.x < 2) s_range[threadIdx.x] = det_image_lower_bound(a.props, a.R_all, img + threadIdx.x, 6);
   if (s == 0 && threadIdx.x == 0) {
     a.hdr[0] = a.num_segs; a.hdr[1] = a.R_all; a.hdr[2] = a.cap; a.hdr[3] = 0;
   }
@@ -370,6 +371,71 @@ __global__ __launch_bounds__(256) void det_multi_scan_emit_kernel(DetMultiArgs a
   if (threadIdx.x == 0) { ent[1] = rows; ent[2] = row0; ent[3] = 0; }
   if (p.cnt[SEG_BAD]) { if (threadIdx.x == 0) ent[0] = -1; return; }
   const size_t slot = (size_t)a.num_classes * row0 + (size_t)c * rows;
+  det_scan_emit(p.mask, a.wpr, p.cnt[SEG_N], p.sbox, p.sprob, p.ssrc, a.dets + 5 * slot, a.ids + slot, ent, dyn_lds);
+}
+
+// ---- every (image, cascade output, class) segment in one pass (mscnn_detections_cascade_multi_fwd) ---------------------------------
+// Segment s = image s / K, output (s % K) / C, class slot s % C, K = O C (image-major, then output, then class).  Every cascade
+// output is a blob triple of its own (decoded boxes [R_all][5], probabilities [R_all][ncls_o], proposals [R_all][5], image index in
+// column 0 of the proposals -- DecodeBBox copies it, decode_bbox_layer.cpp:110); the triples travel as kernel arguments beside the
+// segment table.  A segment finds its rows in ITS output's proposals and runs the same three bodies with cascade = 1; its detections
+// go to pack rows [K row0 + (o C + c) rows, + rows): the multi pack with K in the role of num_classes.
+constexpr int kCascadeMaxOutputs = 4;
+constexpr int kCascadeSegsPerLaunch = 32;  // 32 x 32 bytes of segments + 4 x 32 bytes of triples + 0.1 KB: 1.3 KB of the 4 KB
+struct DetCascadeSeg { float ratio_h, ratio_w, org_h, org_w; int cls_id, pad; double nms_overlap; };
+struct DetCascadeOut { const float* boxes; const float* cls_prob; const float* props; int ncls, pad; };
+struct DetCascadeMultiArgs {
+  int R_all, num_outputs, num_classes, max_rows, wpr, cap, num_segs, s0;
+  float det_thr;
+  char* ws; size_t seg_stride_box, seg_stride_mask;                     // workspace: as DetMultiArgs (det_multi_ptrs)
+  int* hdr; double* dets; int* ids;                                     // pack
+  DetCascadeOut out[kCascadeMaxOutputs];
+  DetCascadeSeg seg[kCascadeSegsPerLaunch];
+};
+
+__global__ __launch_bounds__(kSortThreads) void det_cascade_multi_transform_sort_kernel(DetCascadeMultiArgs a) {
+  const int j = blockIdx.x, s = a.s0 + j;
+  const int K = a.num_outputs * a.num_classes;
+  const int img = s / K, o = (s % K) / a.num_classes;
+  const DetCascadeOut& t = a.out[o];
+  const DetMultiPtrs p = det_multi_ptrs(a, s);
+  __shared__ int s_range[2];
+  if (threadIdx.x < 2) s_range[threadIdx.x] = det_image_lower_bound(t.props, a.R_all, img + threadIdx.x, 5);
+  if (s == 0 && threadIdx.x == 0) {
+    a.hdr[0] = a.num_segs; a.hdr[1] = a.R_all; a.hdr[2] = a.cap; a.hdr[3] = 0;
+  }
+  __syncthreads();
+  const int row0 = s_range[0], rows = s_range[1] - s_range[0];
+  const bool bad = rows > a.max_rows;      // (as det_multi_transform_sort_kernel: nothing is run, the table says so)
+  if (threadIdx.x == 0) { p.cnt[SEG_ROW0] = row0; p.cnt[SEG_ROWS] = rows; p.cnt[SEG_BAD] = bad ? 1 : 0; }
+  if (bad) { if (threadIdx.x == 0) p.cnt[SEG_N] = 0; return; }
+  const DetCascadeSeg& g = a.seg[j];
+  DetArgs d;
+  d.bbox_pred = t.boxes + (size_t)row0 * 5; d.cls_pred = t.cls_prob + (size_t)row0 * t.ncls; d.props = t.props + (size_t)row0 * 5;
+  d.R = rows; d.ncls = t.ncls; d.cls_id = g.cls_id;
+  for (int k = 0; k < 4; ++k) { d.mean[k] = 0.f; d.stdv[k] = 1.f; }      // (not read by the cascade row transform)
+  d.proposal_thr = a.det_thr; d.ratio_h = g.ratio_h; d.ratio_w = g.ratio_w; d.org_h = g.org_h; d.org_w = g.org_w;
+  d.cascade = 1;
+  det_transform_sort(d, p.sbox, p.sprob, p.ssrc, p.tbox, p.tprob, p.cnt + SEG_N);
+}
+
+__global__ __launch_bounds__(256) void det_cascade_multi_mask_kernel(DetCascadeMultiArgs a) {
+  const int j = blockIdx.z, s = a.s0 + j;
+  const DetMultiPtrs p = det_multi_ptrs(a, s);
+  det_mask_block(p.sbox, p.cnt[SEG_N], a.seg[j].nms_overlap, p.mask, a.wpr, blockIdx.y, blockIdx.x);
+}
+
+__global__ __launch_bounds__(256) void det_cascade_multi_scan_emit_kernel(DetCascadeMultiArgs a) {
+  extern __shared__ __attribute__((aligned(16))) u64 dyn_lds[];
+  const int j = blockIdx.x, s = a.s0 + j;
+  const int K = a.num_outputs * a.num_classes;
+  const int k = s % K;                     // o C + c
+  const DetMultiPtrs p = det_multi_ptrs(a, s);
+  const int row0 = p.cnt[SEG_ROW0], rows = p.cnt[SEG_ROWS];
+  int* ent = a.hdr + PACK_HDR_WORDS + (size_t)s * PACK_SEG_WORDS;
+  if (threadIdx.x == 0) { ent[1] = rows; ent[2] = row0; ent[3] = 0; }
+  if (p.cnt[SEG_BAD]) { if (threadIdx.x == 0) ent[0] = -1; return; }
+  const size_t slot = (size_t)K * row0 + (size_t)k * rows;
   det_scan_emit(p.mask, a.wpr, p.cnt[SEG_N], p.sbox, p.sprob, p.ssrc, a.dets + 5 * slot, a.ids + slot, ent, dyn_lds);
 }
 
@@ -566,6 +632,79 @@ extern "C" int mscnn_detections_multi_fwd(const mscnn_detections_desc* desc, int
     det_multi_mask_kernel<<<dim3(a.wpr, a.wpr, ns), 256, 0, st>>>(a);
     MSCNN_POST_LAUNCH();
     det_multi_scan_emit_kernel<<<ns, 256, (size_t)2 * 64 * a.wpr * sizeof(u64), st>>>(a);
+    MSCNN_POST_LAUNCH();
+  }
+  return MSCNN_OK;
+}
+
+// ---- all (image, cascade output, class) segments in one pass ---------------------------------------------------------------------------
+extern "C" size_t mscnn_detections_cascade_multi_workspace_bytes(int num_segments, int max_rows_per_image) {
+  return mscnn_detections_multi_workspace_bytes(num_segments, max_rows_per_image);
+}
+
+extern "C" int mscnn_detections_cascade_multi_fwd(const mscnn_detections_desc* desc, float det_thr, int num_images, int num_outputs,
+                                                  int num_classes, const mscnn_cascade_output* outputs, int R_all,
+                                                  int max_rows_per_image, void* pack_dev, int cap, void* workspace,
+                                                  size_t workspace_bytes, void* stream) {
+  MSCNN_REQUIRE(num_outputs >= 1 && num_outputs <= kCascadeMaxOutputs, "detections_cascade_multi: %d cascade outputs (1 .. %d)",
+                num_outputs, kCascadeMaxOutputs);
+  MSCNN_REQUIRE(desc && outputs && pack_dev && workspace, "detections_cascade_multi: null pointer");
+  MSCNN_REQUIRE(num_images >= 1 && num_classes >= 1, "detections_cascade_multi: %d images x %d classes", num_images, num_classes);
+  MSCNN_REQUIRE(R_all >= 1, "detections_cascade_multi: R_all = %d (BoxOutput emits at least one row)", R_all);
+  for (int o = 0; o < num_outputs; ++o) {
+    MSCNN_REQUIRE(outputs[o].boxes && outputs[o].cls_prob && outputs[o].props, "detections_cascade_multi: output %d of %d: null pointer",
+                  o, num_outputs);
+    MSCNN_REQUIRE(outputs[o].ncls >= 2, "detections_cascade_multi: output %d: %d probability columns", o, outputs[o].ncls);
+  }
+  MSCNN_REQUIRE(max_rows_per_image >= 1 && max_rows_per_image <= kMaxK,
+                "detections_cascade_multi: %d rows per image > %d: run mscnn_detections_cascade_fwd per segment", max_rows_per_image, kMaxK);
+  const int K = num_outputs * num_classes;
+  MSCNN_REQUIRE((long)K * R_all <= (long)cap, "detections_cascade_multi: pack capacity %d < %d outputs x %d classes x %d ROIs", cap,
+                num_outputs, num_classes, R_all);
+  MSCNN_REQUIRE((long)num_images * K <= (long)(1 << 24), "detections_cascade_multi: %d images x %d outputs x %d classes", num_images,
+                num_outputs, num_classes);
+  const int S = num_images * K;
+  for (int s = 0; s < S; ++s) {
+    const int o = (s % K) / num_classes;
+    MSCNN_REQUIRE(desc[s].cls_id >= 1 && desc[s].cls_id <= outputs[o].ncls, "detections_cascade_multi: segment %d (output %d): cls_id %d of %d",
+                  s, o, desc[s].cls_id, outputs[o].ncls);
+  }
+  const size_t need = mscnn_detections_cascade_multi_workspace_bytes(S, max_rows_per_image);
+  if (workspace_bytes < need) {
+    set_error("detections_cascade_multi: workspace %zu < %zu", workspace_bytes, need);
+    return MSCNN_ERR_WORKSPACE;
+  }
+  hipStream_t st = as_stream(stream);
+  const int M = max_rows_per_image;
+  DetCascadeMultiArgs a = {};
+  a.R_all = R_all; a.num_outputs = num_outputs; a.num_classes = num_classes; a.max_rows = M; a.wpr = (M + 63) / 64; a.cap = cap;
+  a.num_segs = S; a.det_thr = det_thr;
+  a.ws = static_cast<char*>(workspace);
+  a.seg_stride_box = det_multi_seg_box_bytes(M); a.seg_stride_mask = det_multi_seg_mask_bytes(M);
+  for (int o = 0; o < num_outputs; ++o) {
+    a.out[o].boxes = outputs[o].boxes; a.out[o].cls_prob = outputs[o].cls_prob; a.out[o].props = outputs[o].props;
+    a.out[o].ncls = outputs[o].ncls;
+  }
+  char* pk = static_cast<char*>(pack_dev);
+  a.hdr = reinterpret_cast<int*>(pk);
+  const size_t rows = (size_t)(cap > 0 ? cap : 1), table = sizeof(int) * (PACK_HDR_WORDS + PACK_SEG_WORDS * (size_t)S);
+  a.dets = reinterpret_cast<double*>(pk + table);
+  a.ids = reinterpret_cast<int*>(pk + table + sizeof(double) * 5 * rows);
+  for (int s0 = 0; s0 < S; s0 += kCascadeSegsPerLaunch) {
+    const int ns = S - s0 < kCascadeSegsPerLaunch ? S - s0 : kCascadeSegsPerLaunch;
+    a.s0 = s0;
+    for (int j = 0; j < ns; ++j) {
+      const mscnn_detections_desc& d = desc[s0 + j];
+      DetCascadeSeg& g = a.seg[j];
+      g.cls_id = d.cls_id; g.nms_overlap = d.nms_overlap;
+      // MATLAB: single op double -> single (as detections_launch)
+      g.ratio_h = (float)d.ratio_h; g.ratio_w = (float)d.ratio_w; g.org_h = (float)d.org_h; g.org_w = (float)d.org_w;
+    }
+    det_cascade_multi_transform_sort_kernel<<<ns, kSortThreads, 0, st>>>(a);
+    MSCNN_POST_LAUNCH();
+    det_cascade_multi_mask_kernel<<<dim3(a.wpr, a.wpr, ns), 256, 0, st>>>(a);
+    MSCNN_POST_LAUNCH();
+    det_cascade_multi_scan_emit_kernel<<<ns, 256, (size_t)2 * 64 * a.wpr * sizeof(u64), st>>>(a);
     MSCNN_POST_LAUNCH();
   }
   return MSCNN_OK;

@@ -157,6 +157,10 @@ def lib():
         L.mscnn_detections_multi_workspace_bytes.argtypes = [C.c_int, C.c_int]
         L.mscnn_detections_multi_fwd.argtypes = ([C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.c_int,
                                                  C.c_void_p, C.c_size_t, C.c_void_p])
+        L.mscnn_detections_cascade_multi_workspace_bytes.restype = C.c_size_t
+        L.mscnn_detections_cascade_multi_workspace_bytes.argtypes = [C.c_int, C.c_int]
+        L.mscnn_detections_cascade_multi_fwd.argtypes = ([C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                                         C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p])
         _lib = L
     return _lib
 
@@ -704,6 +708,60 @@ def detections_multi(bbox_pred, cls_pred, props, num_images, segments, max_rows_
         cnt, rows, row0, _ = (int(v) for v in hdr[1 + s])
         slot = Cn * row0 + (s % Cn) * rows
         out.append((dets[slot:slot + max(cnt, 0)].copy(), ids[slot:slot + max(cnt, 0)].copy(), row0, rows) if cnt >= 0 else (None, None, row0, rows))
+    return out
+
+
+class CascadeOutput(C.Structure):
+    """mscnn_cascade_output: the blob triple of one cascade output + its probability columns."""
+    _fields_ = [("boxes", C.c_void_p), ("cls_prob", C.c_void_p), ("props", C.c_void_p), ("ncls", C.c_int)]
+
+
+def detections_cascade_multi(outputs, num_images, segments, det_thr=0.0, max_rows_per_image=None):
+    """Every (image, cascade output, class) segment in one pass (mscnn_detections_cascade_multi_fwd).  outputs: [(boxes [R, 5],
+    cls_prob [R, ncls], props [R, 5])] per cascade output, rows grouped by image (image index in column 0 of props); segments:
+    num_images * O * C dicts of detections_cascade() keyword arguments (cls_id, ratios, org_hw, nms_overlap), image-major, then
+    output, then class.  Returns [(dets[D,5], ids relative to row0, row0, rows)] per segment ((None, None, row0, rows): the image
+    has more rows than max_rows_per_image)."""
+    O = len(outputs)
+    S = len(segments)
+    K = S // num_images
+    Cn = K // max(O, 1)
+    if O < 1 or Cn * O * num_images != S:
+        raise MscnnError(f"detections_cascade_multi: {S} segments for {num_images} images x {O} outputs")
+    R = outputs[0][2].shape[0]
+    outs = (CascadeOutput * O)()
+    for o, (boxes, cls_prob, props) in enumerate(outputs):
+        if boxes.shape != (R, 5) or props.shape != (R, 5) or cls_prob.shape[0] != R:
+            raise MscnnError(f"detections_cascade_multi: output {o}: shapes {tuple(boxes.shape)} {tuple(cls_prob.shape)} {tuple(props.shape)}")
+        outs[o].boxes, outs[o].cls_prob, outs[o].props, outs[o].ncls = _dev(boxes).value, _dev(cls_prob).value, _dev(props).value, cls_prob.shape[1]
+    descs = (DetectionsDesc * S)()
+    for s, kw in enumerate(segments):
+        kw = dict(dict(ratios=(1.0, 1.0), org_hw=(375, 1242), nms_overlap=0.5), **kw)
+        d = descs[s]
+        d.ncls = outs[(s % K) // Cn].ncls; d.cls_id = kw["cls_id"]
+        d.ratio_h, d.ratio_w = kw["ratios"]
+        d.org_h, d.org_w = kw["org_hw"]
+        d.nms_overlap = kw["nms_overlap"]
+    M = R if max_rows_per_image is None else max_rows_per_image
+    cap = K * R
+    dev = outputs[0][2].device
+    pack = torch.zeros(lib().mscnn_detections_multi_pack_bytes(S, cap), dtype=torch.uint8, device=dev)
+    wb = lib().mscnn_detections_cascade_multi_workspace_bytes(S, M)
+    ws = torch.empty(max(wb, 1), dtype=torch.uint8, device=dev)
+    _check(lib().mscnn_detections_cascade_multi_fwd(descs, C.c_float(det_thr), num_images, O, Cn, outs, R, M, _dev(pack), cap, _dev(ws),
+                                                    C.c_size_t(wb), _stream()))
+    h = pack.cpu().numpy()
+    hdr = h[:16 * (S + 1)].view(np.int32).reshape(S + 1, 4)
+    if list(hdr[0]) != [S, R, cap, 0]:
+        raise MscnnError(f"detections_cascade_multi: pack header {hdr[0].tolist()}")
+    table = 16 * (S + 1)
+    dets = h[table:table + 40 * max(cap, 1)].view(np.float64).reshape(-1, 5)
+    ids = h[table + 40 * max(cap, 1):table + 44 * max(cap, 1)].view(np.int32)
+    out = []
+    for s in range(S):
+        cnt, rows, row0, _ = (int(v) for v in hdr[1 + s])
+        slot = K * row0 + (s % K) * rows
+        out.append((dets[slot:slot + cnt].copy(), ids[slot:slot + cnt].copy(), row0, rows) if cnt >= 0 else (None, None, row0, rows))
     return out
 
 

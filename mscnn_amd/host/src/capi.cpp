@@ -857,4 +857,179 @@ int mscnn_net_detect_cascade(mscnn_net* n, const mscnn_detect_params* p, float d
   });
 }
 
+// ---- every (image, cascade output, class) segment of the last forward in one pass ------------------------------------------------------
+// The blob triples of the cascade outputs, checked: names, [R, 5] boxes and proposals, one row count throughout.
+struct CascadeBlobs {
+  std::vector<const Blob<float>*> boxes, prob, props;
+  std::vector<int> ncls;
+  int R_all = 0;
+};
+static CascadeBlobs cascade_blobs(mscnn_net* n, int num_outputs, const char* const* bbox_blobs, const char* const* prob_blobs,
+                                  const char* const* proposal_blobs) {
+  CHECK(num_outputs >= 1 && num_outputs <= 4) << "detect_cascade_multi: " << num_outputs << " cascade outputs (1 .. 4)";
+  CHECK(bbox_blobs && prob_blobs && proposal_blobs) << "detect_cascade_multi: null blob name list";
+  CascadeBlobs b;
+  for (int o = 0; o < num_outputs; ++o) {
+    CHECK(bbox_blobs[o] && prob_blobs[o] && proposal_blobs[o]) << "detect_cascade_multi: output " << o << " of " << num_outputs
+                                                               << ": null blob name";
+    for (const char* name : {bbox_blobs[o], prob_blobs[o], proposal_blobs[o]})
+      CHECK(n->net->has_blob(name)) << "Unknown blob name " << name << " (cascade output " << o << ")";
+    const Blob<float>* boxes = n->net->blob_by_name(bbox_blobs[o]).get();
+    const Blob<float>* prob = n->net->blob_by_name(prob_blobs[o]).get();
+    const Blob<float>* props = n->net->blob_by_name(proposal_blobs[o]).get();
+    const int R = boxes->num();
+    CHECK(prob->num() == R && props->num() == R) << "cascade output " << o << ": " << bbox_blobs[o] << " has " << R << " rows, "
+                                                 << prob_blobs[o] << " " << prob->num() << ", " << proposal_blobs[o] << " " << props->num();
+    if (o == 0) b.R_all = R;
+    CHECK_EQ(R, b.R_all) << "cascade output " << o << " has " << R << " rows, output 0 has " << b.R_all;
+    CHECK_GE(R, 1) << "cascade output " << o << " has no rows";
+    CHECK_EQ(boxes->count(), 5 * R) << bbox_blobs[o] << " is not an [R, 5] box blob (" << boxes->count() << " values in " << R << " rows)";
+    CHECK_EQ(props->count(), 5 * R) << proposal_blobs[o] << " is not an [R, 5] proposal blob (" << props->count() << " values in " << R
+                                    << " rows)";
+    b.boxes.push_back(boxes); b.prob.push_back(prob); b.props.push_back(props);
+    b.ncls.push_back(prob->count() / R);
+  }
+  return b;
+}
+
+// Everything that can be refused is refused here, before any device memory is reserved or a kernel launched.  Returns the descs.
+static std::vector<mscnn_detections_desc> cascade_descs(mscnn_net* n, const mscnn_detect_params* p, int num_images, int num_outputs,
+                                                        int num_classes, const CascadeBlobs& b, int cap) {
+  CHECK(p != nullptr) << "detect_cascade_multi: null pointer";
+  CHECK(num_images >= 1 && num_classes >= 1) << num_images << " images x " << num_classes << " classes";
+  const int num = n->net->num_inputs() > 0 && n->net->input_blobs()[0]->num_axes() == 4 ? n->net->input_blobs()[0]->num() : 1;
+  CHECK_EQ(num_images, num) << "detect_cascade_multi: num_images " << num_images << " but the net's input holds " << num << " images";
+  const int K = num_outputs * num_classes, S = num_images * K;
+  CHECK_GE((long)cap, (long)K * b.R_all) << "detection pack capacity " << cap << " < " << num_outputs << " outputs x " << num_classes
+                                         << " classes x " << b.R_all << " ROIs";
+  std::vector<mscnn_detections_desc> desc(S);
+  for (int s = 0; s < S; ++s) {
+    const int o = (s % K) / num_classes;
+    mscnn_detections_desc& d = desc[s];
+    std::memset(&d, 0, sizeof(d));
+    d.ncls = b.ncls[o];
+    d.cls_id = p[s].cls_id;
+    CHECK(d.cls_id >= 1 && d.cls_id <= d.ncls) << "segment " << s << " (output " << o << "): cls_id " << d.cls_id << " of " << d.ncls;
+    d.ratio_h = p[s].ratio_h; d.ratio_w = p[s].ratio_w; d.org_h = p[s].org_h; d.org_w = p[s].org_w; d.nms_overlap = p[s].nms_overlap;
+  }
+  return desc;
+}
+
+// The cascade multi pack (mscnn_hip.h: mscnn_detections_cascade_multi_fwd) of the last forward with cap rows, at pack_at
+// (device-addressable) or in the net's device pack.  Returns false when it went to the device pack instead: a per-image bound over
+// 4032 rows runs mscnn_detections_cascade_fwd per segment on ranges read from each output's proposals, into the same layout.
+static bool detect_cascade_multi_into_pack(mscnn_net* n, const std::vector<mscnn_detections_desc>& desc, int num_images, int num_outputs,
+                                           int num_classes, const CascadeBlobs& b, float det_thr, int cap, char* pack_at, char** pack_out) {
+  const int K = num_outputs * num_classes, S = num_images * K, R_all = b.R_all;
+  hipStream_t st = (hipStream_t)Caffe::stream();
+  const size_t total = mscnn_detections_multi_pack_bytes(S, cap);
+  const int bound = n->net->has_blob("proposals_score") ? per_image_row_bound(n, num_images, R_all) : R_all;
+  if (bound <= 4032) {
+    std::vector<mscnn_cascade_output> outs(num_outputs);
+    for (int o = 0; o < num_outputs; ++o)
+      outs[o] = mscnn_cascade_output{b.boxes[o]->gpu_data(), b.prob[o]->gpu_data(), b.props[o]->gpu_data(), b.ncls[o]};
+    const size_t wb = mscnn_detections_cascade_multi_workspace_bytes(S, bound);
+    void* ws = n->det_ws.Reserve(wb);
+    char* pack = pack_at ? pack_at : static_cast<char*>(n->det_pack.Reserve(total));
+    MSCNN_CHECK(mscnn_detections_cascade_multi_fwd(desc.data(), det_thr, num_images, num_outputs, num_classes, outs.data(), R_all, bound,
+                                                   pack, cap, ws, wb, st));
+    *pack_out = pack;
+    return pack == pack_at;
+  }
+  // rows of every image in every output's proposals (column 0 = image, ascending): one host read per output
+  std::vector<int> row0((size_t)num_outputs * num_images), rows((size_t)num_outputs * num_images);
+  int max_rows = 0;
+  for (int o = 0; o < num_outputs; ++o) {
+    const float* h = b.props[o]->cpu_data();      // (synchronises the stream)
+    std::vector<int> end(num_images, 0);
+    int prev = 0;
+    for (int r = 0; r < R_all; ++r) {
+      const int img = (int)h[(size_t)r * 5];
+      CHECK(img >= prev && img < num_images) << "the proposals of cascade output " << o << " are not grouped by image";
+      prev = img;
+      end[img] = r + 1;
+    }
+    for (int i = 1; i < num_images; ++i) if (end[i] < end[i - 1]) end[i] = end[i - 1];
+    for (int i = 0; i < num_images; ++i) {
+      row0[(size_t)o * num_images + i] = i > 0 ? end[i - 1] : 0;
+      rows[(size_t)o * num_images + i] = end[i] - row0[(size_t)o * num_images + i];
+      max_rows = std::max(max_rows, rows[(size_t)o * num_images + i]);
+    }
+  }
+  char* pack = static_cast<char*>(n->det_pack.Reserve(total));
+  int* hdr = reinterpret_cast<int*>(pack);
+  const size_t rows_cap = (size_t)(cap > 0 ? cap : 1), table = sizeof(int) * (4 + 4 * (size_t)S);
+  double* dets = reinterpret_cast<double*>(pack + table);
+  int* ids = reinterpret_cast<int*>(pack + table + sizeof(double) * 5 * rows_cap);
+  const size_t wb = mscnn_detections_workspace_bytes(max_rows);
+  void* ws = n->det_ws.Reserve(wb);
+  const int words[4] = {S, R_all, cap, 0};
+  MSCNN_CHECK(mscnn_store_words_i32(hdr, words, 4, st));
+  for (int s = 0; s < S; ++s) {
+    const int i = s / K, k = s % K, o = k / num_classes;
+    const int r0 = row0[(size_t)o * num_images + i], nr = rows[(size_t)o * num_images + i];
+    const size_t slot = (size_t)K * r0 + (size_t)k * nr;
+    int* ent = hdr + 4 + 4 * (size_t)s;
+    const int e[3] = {nr, r0, 0};
+    MSCNN_CHECK(mscnn_store_words_i32(ent + 1, e, 3, st));
+    MSCNN_CHECK(mscnn_detections_cascade_fwd(&desc[s], det_thr, b.boxes[o]->gpu_data() + (size_t)r0 * 5,
+                                             b.prob[o]->gpu_data() + (size_t)r0 * b.ncls[o], b.props[o]->gpu_data() + (size_t)r0 * 5, nr,
+                                             dets + 5 * slot, ids + slot, ent, ws, wb, st));
+  }
+  *pack_out = pack;
+  return false;
+}
+
+size_t mscnn_net_detect_cascade_multi_pack_bytes(int num_images, int num_outputs, int num_classes, int cap) {
+  return mscnn_detections_multi_pack_bytes(num_images * num_outputs * num_classes, cap);
+}
+
+int mscnn_net_detect_cascade_multi_device(mscnn_net* n, const mscnn_detect_params* p, int num_images, int num_outputs, int num_classes,
+                                          const char* const* bbox_blobs, const char* const* prob_blobs, const char* const* proposal_blobs,
+                                          float det_thr, int cap, const void** pack_dev) {
+  return guarded([&] {
+    CHECK(pack_dev != nullptr) << "detect_cascade_multi_device: null pointer";
+    const CascadeBlobs b = cascade_blobs(n, num_outputs, bbox_blobs, prob_blobs, proposal_blobs);
+    const auto desc = cascade_descs(n, p, num_images, num_outputs, num_classes, b, cap);
+    char* pack = nullptr;
+    detect_cascade_multi_into_pack(n, desc, num_images, num_outputs, num_classes, b, det_thr, cap, nullptr, &pack);
+    *pack_dev = pack;
+  });
+}
+
+int mscnn_net_detect_cascade_multi(mscnn_net* n, const mscnn_detect_params* p, int num_images, int num_outputs, int num_classes,
+                                   const char* const* bbox_blobs, const char* const* prob_blobs, const char* const* proposal_blobs,
+                                   float det_thr, double* dets_host, int* ids_host, int cap, int* seg_dets, int* image_rois) {
+  return guarded([&] {
+    CHECK(p && seg_dets) << "detect_cascade_multi: null pointer";
+    // as mscnn_net_detect_multi: the kernels write the pack straight into host-coherent pinned memory, one stream synchronisation, no
+    // copy; the per-segment fallback leaves it in the device pack and copies it
+    hipStream_t st = (hipStream_t)Caffe::stream();
+    int pcap = 0, S = 0;
+    auto run = [&]() {
+      const CascadeBlobs b = cascade_blobs(n, num_outputs, bbox_blobs, prob_blobs, proposal_blobs);
+      pcap = num_outputs * num_classes * b.R_all;
+      const auto desc = cascade_descs(n, p, num_images, num_outputs, num_classes, b, pcap);
+      S = (int)desc.size();
+      const size_t total = mscnn_detections_multi_pack_bytes(S, pcap);
+      ensure_det_host(n, total);
+      *static_cast<volatile int*>(n->det_host) = -1;      // the header's first word (S): the kernels must have written it
+      char* pack = nullptr;
+      if (!detect_cascade_multi_into_pack(n, desc, num_images, num_outputs, num_classes, b, det_thr, pcap,
+                                          static_cast<char*>(n->det_host_dev), &pack))
+        HIP_CHECK(hipMemcpyAsync(n->det_host, pack, total, hipMemcpyDeviceToHost, st));
+      HIP_CHECK(hipStreamSynchronize(st));
+    };
+    run();
+    if (n->net->HandoffRecover()) run();      // (as mscnn_net_detect: the frame has been run again on whole tiles)
+    const int* hdr = static_cast<const int*>(n->det_host);
+    CHECK_GE(hdr[0], 0) << "detect_cascade_multi: the pack header was not written (" << S << " segments, " << pcap << " pack rows)";
+    for (int s = 0; s < S; ++s)
+      CHECK_GE(hdr[4 + 4 * (size_t)s], -1) << "detect_cascade_multi: segment " << s << " has count " << hdr[4 + 4 * (size_t)s];
+    const int rc = mscnn_net_unpack_detections_multi(n->det_host, num_images, num_outputs * num_classes, pcap, dets_host, ids_host, cap,
+                                                     seg_dets, image_rois);
+    CHECK_EQ(rc, 0) << g_err;
+  });
+}
+
 }  // extern "C"

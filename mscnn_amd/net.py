@@ -40,6 +40,7 @@ def lib():
         L.mscnn_net_destroy.restype = None
         L.mscnn_net_detect_pack_bytes.restype = C.c_size_t
         L.mscnn_net_detect_multi_pack_bytes.restype = C.c_size_t
+        L.mscnn_net_detect_cascade_multi_pack_bytes.restype = C.c_size_t
         vp, ci, cs = C.c_void_p, C.c_int, C.c_char_p
         sig = {
             "mscnn_net_create_from_file": [cs, ci, vp], "mscnn_net_create_from_string": [cs, ci, vp], "mscnn_net_destroy": [vp],
@@ -74,6 +75,9 @@ def lib():
             "mscnn_net_detect_multi": [vp, vp, ci, ci, vp, vp, ci, vp, vp], "mscnn_net_detect_multi_pack_bytes": [ci, ci, ci],
             "mscnn_net_detect_multi_device": [vp, vp, ci, ci, ci, vp],
             "mscnn_net_unpack_detections_multi": [vp, ci, ci, ci, vp, vp, ci, vp, vp],
+            "mscnn_net_detect_cascade_multi": [vp, vp, ci, ci, ci, vp, vp, vp, C.c_float, vp, vp, ci, vp, vp],
+            "mscnn_net_detect_cascade_multi_pack_bytes": [ci, ci, ci, ci],
+            "mscnn_net_detect_cascade_multi_device": [vp, vp, ci, ci, ci, vp, vp, vp, C.c_float, ci, vp],
         }
         for name, args in sig.items():
             getattr(L, name).argtypes = args
@@ -373,6 +377,45 @@ class Net:
                                               dets.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p), cap, C.byref(D), C.byref(R)))
         return dets[:D.value].copy(), ids[:D.value].copy(), R.value
 
+    @classmethod
+    def _cascade_multi_args(cls, params, outputs, classes):
+        """-> (the (image, output, class) parameter array, the three blob name arrays) of mscnn_net_detect_cascade_multi."""
+        O, Cn = len(outputs), len(classes)
+        arr = (DetectParams * max(len(params) * O * Cn, 1))()
+        for i, kw in enumerate(params):
+            kw = dict(dict(nms_overlap=0.5), **kw)
+            for o in range(O):
+                for c, cls_id in enumerate(classes):
+                    arr[(i * O + o) * Cn + c] = cls._params(cls_id, kw["ratios"], kw["org_hw"], (0, 0, 0, 0), (1, 1, 1, 1), 0.0, kw["nms_overlap"])
+        names = [(C.c_char_p * max(O, 1))(*[None if t[k] is None else t[k].encode() for t in outputs]) for k in range(3)]
+        return arr, names
+
+    def detect_cascade_multi(self, params, outputs, classes, det_thr=0.0, cap=None):
+        """mscnn_net_detect_cascade_multi: the cascade final stage (run_cascademscnn.m:84-127) of every image, cascade output and
+        class of the last forward in one pass.  params: one dict per image of the batch (ratios, org_hw, optionally nms_overlap --
+        the dicts set_images returns work as they are); outputs: [(bbox_blob, prob_blob, proposal_blob)] per cascade output;
+        classes: the cls_ids.  Returns (per_image[i][o][c] = (dets[D,5], rows of the net's blobs[D]), [ROI count per image])."""
+        B, O, Cn = len(params), len(outputs), len(classes)
+        if cap is None:
+            cap = max(1, O * Cn * self.blob_shape(outputs[0][0])[0]) if O and outputs[0][0] in self.blob_names else 1
+        p, (bb, pb, qb) = self._cascade_multi_args(params, outputs, classes)
+        dets = np.zeros((max(cap, 1), 5), np.float64); ids = np.zeros(max(cap, 1), np.int32)
+        seg = np.zeros(max(B * O * Cn, 1), np.int32); rois = np.zeros(max(B, 1), np.int32)
+        _check(lib().mscnn_net_detect_cascade_multi(self._h, p, B, O, Cn, bb, pb, qb, det_thr, dets.ctypes.data_as(C.c_void_p),
+                                                    ids.ctypes.data_as(C.c_void_p), cap, seg.ctypes.data_as(C.c_void_p),
+                                                    rois.ctypes.data_as(C.c_void_p)))
+        flat = _split_segments(dets, ids, seg, B, O * Cn)
+        return [[row[o * Cn:(o + 1) * Cn] for o in range(O)] for row in flat], rois[:B].tolist()
+
+    def detect_cascade_multi_device(self, params, outputs, classes, cap, det_thr=0.0):
+        """mscnn_net_detect_cascade_multi_device: the same into the device pack (detect_cascade_multi_pack_bytes(B, O, C, cap)
+        bytes); asynchronous.  Returns its device address; unpack_detections_cascade_multi reads a host copy of it."""
+        p, (bb, pb, qb) = self._cascade_multi_args(params, outputs, classes)
+        ptr = C.c_void_p()
+        _check(lib().mscnn_net_detect_cascade_multi_device(self._h, p, len(params), len(outputs), len(classes), bb, pb, qb, det_thr, cap,
+                                                           C.byref(ptr)))
+        return ptr.value
+
     def detect_image(self, image, cls_id, ratios, org_hw, bbox_mean=(0, 0, 0, 0), bbox_std=(0.1, 0.1, 0.2, 0.2), proposal_thr=-10.0,
                      nms_overlap=0.5, cap=4096):
         """The final stage for image `image` of a batched forward; returns (dets[D,5], rows of the net's ROI blobs[D], the image's R)."""
@@ -479,3 +522,14 @@ def unpack_detections_multi(pack_host, num_images, num_classes, cap, out_cap=Non
                                                    dets.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p), out_cap,
                                                    seg.ctypes.data_as(C.c_void_p), rois.ctypes.data_as(C.c_void_p)))
     return _split_segments(dets, ids, seg, num_images, num_classes), rois.tolist()
+
+
+def detect_cascade_multi_pack_bytes(num_images, num_outputs, num_classes, cap):
+    return lib().mscnn_net_detect_cascade_multi_pack_bytes(num_images, num_outputs, num_classes, cap)
+
+
+def unpack_detections_cascade_multi(pack_host, num_images, num_outputs, num_classes, cap, out_cap=None):
+    """One host copy of a cascade multi pack -> (per_image[i][o][c] = (dets, ids), [ROI count per image]): the multi pack with
+    num_outputs * num_classes slots per image, output-major."""
+    flat, rois = unpack_detections_multi(pack_host, num_images, num_outputs * num_classes, cap, out_cap)
+    return [[row[o * num_classes:(o + 1) * num_classes] for o in range(num_outputs)] for row in flat], rois

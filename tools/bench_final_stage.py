@@ -2,7 +2,13 @@
 """The final detection stage alone, per step, in both forms on the same forward: B x C per-call stages (mscnn_net_detect_image, or
 mscnn_net_detect for a batch-1 net) against one mscnn_net_detect_multi.  Host wall time of each form (both end with the detections
 on the host), median over the steps; the two forms alternate which runs first.  Every step also checks that the two forms agree bit
-for bit.  Usage: python tools/bench_final_stage.py [--steps 30] [--warmup 5] [--case caltech-f32 ...]"""
+for bit.  Usage: python tools/bench_final_stage.py [--steps 30] [--warmup 5] [--case caltech-f32 ...]
+
+--cascade [--case kitti_car-cascade-b1 ...] is the same measurement for the cascade deploys: one call per (cascade output, class)
+against one mscnn_net_detect_cascade_multi.  At B = 1 the per-call form is mscnn_net_detect_cascade (like for like).  At B > 1
+mscnn_net_detect_cascade has no per-image form (it treats the blob as one list), so the per-call form there is a loop of per-range
+op calls (hipapi.detections_cascade on each image's rows of the device blobs, row ranges read from the one-pass result outside the
+timed region, each call ending with its detections on the host)."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -15,14 +21,86 @@ CASES = {   # name: model, batch, precision, classes, original image size
     "ped_cyc-b1-cls23": ("kitti_ped_cyc/mscnn-7s-576-2x", 1, "f32", [2, 3], (375, 1242)),
 }
 
+CASCADE_CASES = {   # name: model, batch, classes, original image size
+    "kitti_car-cascade-b1": ("kitti_car/cascade-mscnn-7s-576-2x", 1, [2], (375, 1242)),
+    "kitti_car-cascade-b2": ("kitti_car/cascade-mscnn-7s-576-2x", 2, [2], (375, 1242)),
+    "widerface-cascade-b1": ("widerface/cascade-mscnn-12s-align", 1, [2], (600, 720)),
+}
+
+
+def cascade_leg(a):
+    import torch
+    from mscnn_amd import hipapi
+    print(f"# cascade final stage per step, host wall ms (median over {a.steps} steps after {a.warmup} warm-up), regime {a.regime}, "
+          "outputs 1st,2nd,3rd")
+    print(f"# {'case':22s} {'B':>2s} {'O':>2s} {'C':>2s} {'ROIs':>6s} {'dets':>5s} {'per-call ms':>12s} {'calls':>5s} {'one-pass ms':>12s} {'calls':>5s} {'saved ms':>9s}")
+    for name in a.case or list(CASCADE_CASES):
+        model, B, classes, org = CASCADE_CASES[name]
+        n = mnet.Net(prototxt_text=zoo.prototxt(model, batch=B))
+        synth.load_into(n, a.regime)
+        _, _, H, W = n.blob_shape("data")
+        frames = [np.concatenate([synth.frame(H, W, seed=1701 + 13 * i + b, org_hw=org) for b in range(B)], 0) for i in range(2)]
+        kw = dict(ratios=(H / float(org[0]), W / float(org[1])), org_hw=org)
+        outputs = [("output_bbox_1st", "cls_prob_1st", "proposals"), ("output_bbox_2nd", "cls_prob_2nd", "proposals_2nd"),
+                   ("output_bbox_3rd", "cls_prob_3rd_avg" if "cls_prob_3rd_avg" in n.blob_names else "cls_prob_3rd", "proposals_3rd")]
+
+        def per_call(rois):
+            if B == 1:
+                return [[[n.detect_cascade(bb, pb, qb, cls_id=c, **kw)[:2] for c in classes] for bb, pb, qb in outputs]]
+            res, row0 = [], 0
+            for i in range(B):
+                sl = slice(row0, row0 + rois[i])
+                res.append([[tuple(t.cpu().numpy() for t in hipapi.detections_cascade(tb[sl], tp[sl], tq[sl], cls_id=c, **kw)) for c in classes]
+                            for tb, tp, tq in dev_blobs])
+                row0 += rois[i]
+            return res
+
+        t_call, t_multi, Rs, Ds = [], [], [], []
+        for step in range(a.warmup + a.steps):
+            n.set_blob("data", frames[step % 2])
+            n.forward()
+            _, rois = n.detect_cascade_multi([kw] * B, outputs, classes)      # (untimed: the row ranges; the forward has finished)
+            if B > 1:      # the blobs on the device for the per-range op calls (copied outside the timed region)
+                dev_blobs = [tuple(torch.from_numpy(n.get_blob(b).reshape(sum(rois), -1)).cuda() for b in t) for t in outputs]
+                torch.cuda.synchronize()
+            order = (0, 1) if step % 2 == 0 else (1, 0)
+            res = [None, None]
+            dt = [0.0, 0.0]
+            for f in order:
+                t0 = time.perf_counter()
+                res[f] = per_call(rois) if f == 0 else n.detect_cascade_multi([kw] * B, outputs, classes)[0]
+                dt[f] = time.perf_counter() - t0
+            row0 = 0
+            for i in range(B):
+                for o in range(len(outputs)):
+                    for c in range(len(classes)):
+                        (d0, i0), (d1, i1) = res[0][i][o][c], res[1][i][o][c]
+                        assert np.array_equal(d0.view(np.uint64), d1.view(np.uint64)) and np.array_equal(i0 + (row0 if B > 1 else 0), i1), (name, step, i, o, c)
+                row0 += rois[i]
+            if step >= a.warmup:
+                t_call.append(dt[0]); t_multi.append(dt[1])
+                Rs.append(sum(rois))
+                Ds.append(sum(len(d) for row in res[1] for q in row for d, _ in q))
+        mc, mm = 1e3 * float(np.median(t_call)), 1e3 * float(np.median(t_multi))
+        print(f"  {name:22s} {B:2d} {len(outputs):2d} {len(classes):2d} {np.mean(Rs):6.0f} {np.mean(Ds):5.0f} {mc:12.3f} {B * len(outputs) * len(classes):5d} "
+              f"{mm:12.3f} {1:5d} {mc - mm:9.3f}", flush=True)
+        del n
+
+
 ap = argparse.ArgumentParser()
+ap.add_argument("--cascade", action="store_true", help="the cascade deploys: per-call detect_cascade against one detect_cascade_multi")
 ap.add_argument("--steps", type=int, default=30)
 ap.add_argument("--warmup", type=int, default=5)
-ap.add_argument("--case", nargs="*", default=list(CASES))
+ap.add_argument("--case", nargs="*", default=None)
 ap.add_argument("--regime", default="mid")
 ap.add_argument("--form", choices=("both", "call", "multi"), default="both",
                 help="one form alone (under a tracer: the launches and synchronisations of that form per step)")
 a = ap.parse_args()
+if a.cascade:
+    cascade_leg(a)
+    sys.exit(0)
+if a.case is None:
+    a.case = list(CASES)
 
 print(f"# final stage per step, host wall ms (median over {a.steps} steps after {a.warmup} warm-up), regime {a.regime}")
 print(f"# {'case':20s} {'B':>2s} {'C':>2s} {'ROIs':>6s} {'dets':>5s} {'per-call ms':>12s} {'calls':>5s} {'one-pass ms':>12s} {'calls':>5s} {'saved ms':>9s}")

@@ -1,0 +1,182 @@
+#!/usr/bin/env python3
+"""The reference's second demo driver (examples/kitti_car/run_cascademscnn.m; the CityPersons and WiderFace copies differ in
+constants) on the MI355X path: net from a deploy prototxt + weight file, every frame resized / BGR / mean-subtracted ON THE DEVICE
+(:79-85), net.forward timed alone like the reference's tic / toc (:88-89), the post-processing loops over cascade outputs and
+classes (:91-143) as ONE call per group of frames (Net.detect_cascade_multi), the result files
+detections/<comp_id>_<class>_<output>_results.txt written as dlmwrite does (:148-158).
+
+  python tools/run_cascademscnn.py --prototxt mscnn_deploy.prototxt --weights model.caffemodel --images /KITTI/testing/image_2
+         [--outputs 1st,2nd,3rd] [--cls-ids 2] [--det-thr 0.05] [--nms-overlap 0.5] [--batch B] [--precision f32|f16x3|f16]
+         [--out detections] [--comp-id cascade_mscnn] [--names bg,car,van,truck,tram] [--limit N]
+  python tools/run_cascademscnn.py --model kitti_car/cascade-mscnn-7s-576-2x --synthetic 8 --batch 2      # no dataset / weights at
+                                                            # hand: the generated deploy net, seeded weights, synthetic frames
+  python tools/run_cascademscnn.py --model widerface/cascade-mscnn-12s-align --images faces/ --orig-size [--max-size 3072]
+
+--outputs: cascade outputs by the reference's names (1st, 2nd, 3rd, 3rd_avg), several at once if wanted.  Default: the last stage
+as the reference picks it (:36-48) -- 3rd_avg when the net has cls_prob_3rd_avg, else 3rd, and 1st for a net without cascade stages.
+--batch B runs B frames per forward (the net's input reshaped to (B, 3, H, W), the last group to its own size).
+--orig-size is the WiderFace flow (widerface/run_cascademscnn.m:55, 82-91): every frame runs at its own size rounded to multiples
+of 32 (scaled down to --max-size first when a side exceeds it), the net reshaped whenever that size changes; one frame per forward.
+
+Everything here is host glue over calls the test-suite covers one by one (Net.set_images, forward, detect_cascade_multi,
+reshape_input, kitti.write_detections_dlm)."""
+import argparse
+import math
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(1, os.path.dirname(os.path.abspath(__file__)))
+
+OUTPUT_BLOBS = {   # the reference's output name -> (bbox blob, probability blob, proposal blob)
+    "1st": ("output_bbox_1st", "cls_prob_1st", "proposals"),
+    "2nd": ("output_bbox_2nd", "cls_prob_2nd", "proposals_2nd"),
+    "3rd": ("output_bbox_3rd", "cls_prob_3rd", "proposals_3rd"),
+    "3rd_avg": ("output_bbox_3rd", "cls_prob_3rd_avg", "proposals_3rd"),
+}
+
+
+def matlab_round(x):
+    """MATLAB's round: halves away from zero (Python's round goes to the even neighbour: 22.5 -> 22)."""
+    return int(math.floor(abs(x) + 0.5)) * (1 if x >= 0 else -1)
+
+
+def net_input_size(org_h, org_w, max_size=3072):
+    """The net input (H, W) of the --orig-size flow for a frame of org_h x org_w (widerface/run_cascademscnn.m:82-91): each side
+    to the nearest multiple of 32; when either exceeds max_size, both scaled by max_size / the larger one and rounded again."""
+    rz_h = matlab_round(org_h / 32.0) * 32
+    rz_w = matlab_round(org_w / 32.0) * 32
+    if rz_h > max_size or rz_w > max_size:
+        t = max_size / float(max(rz_h, rz_w))
+        rz_h = matlab_round(rz_h * t / 32.0) * 32
+        rz_w = matlab_round(rz_w * t / 32.0) * 32
+    return rz_h, rz_w
+
+
+def default_outputs(blob_names):
+    """The last stage as the reference picks it (:36-48)."""
+    if "proposals_3rd" in blob_names:
+        return ["3rd_avg" if "cls_prob_3rd_avg" in blob_names else "3rd"]
+    return ["1st"]
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--prototxt"); ap.add_argument("--weights", help=".caffemodel (new or V1 layout) or .h5 snapshot")
+    ap.add_argument("--model", help="a deploy net of mscnn_amd.zoo instead of --prototxt (e.g. kitti_car/cascade-mscnn-7s-576-2x)")
+    ap.add_argument("--input-size", default="", help="H,W: build the --model net at this input size instead of the deploy file's")
+    ap.add_argument("--max-nms-num", type=int, default=0, help="BoxOutput's max_nms_num of the --model net (0: the deploy file's)")
+    ap.add_argument("--images", help="directory of *.png / *.jpg frames")
+    ap.add_argument("--synthetic", type=int, default=0, help="N synthetic frames instead of --images")
+    ap.add_argument("--synthetic-sizes", default="375x1242", help="HxW[,HxW ...]: sizes of the synthetic frames, taken in turn")
+    ap.add_argument("--outputs", default="", help="cascade outputs, comma separated: 1st, 2nd, 3rd, 3rd_avg (default: the last stage)")
+    ap.add_argument("--out", default="detections"); ap.add_argument("--comp-id", default="cascade_mscnn_mi355x")
+    ap.add_argument("--cls-ids", default="2", help="1-based class columns, comma separated (the reference's obj_ids)")
+    ap.add_argument("--names", default="")
+    ap.add_argument("--det-thr", type=float, default=0.0, help="> 0: drop detections under this probability before the NMS (:122-124)")
+    ap.add_argument("--nms-overlap", type=float, default=0.5)
+    ap.add_argument("--precision", default="f32", choices=["f32", "f16x3", "f16"])
+    ap.add_argument("--limit", type=int, default=0); ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--batch", type=int, default=1, help="frames per forward")
+    ap.add_argument("--orig-size", action="store_true", help="run every frame at its own size (multiples of 32), one frame per forward")
+    ap.add_argument("--max-size", type=int, default=3072, help="--orig-size: scale frames down to this side length first")
+    ap.add_argument("--dump-blobs", default="", help="directory: the cascade outputs' blobs and the frames' ratios / sizes of every "
+                    "forward as group_NNNN.npz (to re-run the final stage on exactly what a forward produced)")
+    a = ap.parse_args(argv)
+    if not (a.prototxt or a.model) or not (a.images or a.synthetic):
+        ap.error("need --prototxt or --model, and --images or --synthetic N")
+    if a.batch < 1:
+        ap.error("--batch must be >= 1")
+    if a.orig_size and a.batch > 1:
+        ap.error(f"--orig-size with --batch {a.batch}: every frame runs at its own input size, and the images of one forward share "
+                 "one; --orig-size runs one frame per forward (drop --batch)")
+    for o in [o for o in a.outputs.split(",") if o]:
+        if o not in OUTPUT_BLOBS:
+            ap.error(f"--outputs {o}: not one of {', '.join(OUTPUT_BLOBS)}")
+    if (a.input_size or a.max_nms_num) and not a.model:
+        ap.error("--input-size / --max-nms-num change the generated --model net; a --prototxt is taken as it is")
+    return a
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    import numpy as np
+    import torch
+    from mscnn_amd import kitti, net as mnet, synth, zoo
+    from run_mscnn_detection import list_images, load_rgb_u8, names_for
+
+    if a.prototxt:
+        text = open(a.prototxt).read()
+    else:
+        kw = {}
+        if a.input_size:
+            kw["height"], kw["width"] = (int(v) for v in a.input_size.split(","))
+        if a.max_nms_num:
+            kw["max_nms_num"] = a.max_nms_num
+        text = zoo.prototxt(a.model, **kw)
+    net = mnet.Net(prototxt_text=text, device=a.device)
+    if a.weights:
+        net.load_caffemodel(a.weights)
+    else:
+        print("no --weights: seeded He-normal weights (synth.load_into) -- detections are meaningless, timings are not", file=sys.stderr)
+        synth.load_into(net, "mid")
+    if a.precision != "f32":
+        net.set_precision(a.precision)
+    out_names = [o for o in a.outputs.split(",") if o] or default_outputs(net.blob_names)
+    outputs = [OUTPUT_BLOBS[o] for o in out_names]
+    for o, triple in zip(out_names, outputs):
+        missing = [b for b in triple if b not in net.blob_names]
+        if missing:
+            sys.exit(f"--outputs {o}: the net has no blob {', '.join(missing)}")
+    names = names_for(text, a.names)
+    cls_ids = [int(c) for c in a.cls_ids.split(",")]
+    files = list_images(a.images, a.limit) if a.images else [None] * a.synthetic
+    if not files:
+        sys.exit(f"no images in {a.images}")
+    syn_sizes = [tuple(int(v) for v in s.split("x")) for s in a.synthetic_sizes.split(",")]
+
+    def load_frame(path, k):      # frame k (1-based): the file, or a seeded uint8 RGB frame of the k-th synthetic size
+        if path is not None:
+            return load_rgb_u8(path)
+        h, w = syn_sizes[(k - 1) % len(syn_sizes)]
+        return np.ascontiguousarray(np.random.default_rng(1701 + k).integers(0, 256, (h, w, 3), dtype=np.uint8))
+
+    shape = tuple(net.blob_shape("data"))
+    results = {(o, c): [] for o in range(len(outputs)) for c in range(len(cls_ids))}
+    used, done = 0.0, 0
+    for g0 in range(0, len(files), a.batch):
+        group = files[g0:g0 + a.batch]
+        frames = [load_frame(path, g0 + i + 1) for i, path in enumerate(group)]
+        H, W = net_input_size(frames[0].shape[0], frames[0].shape[1], a.max_size) if a.orig_size else shape[2:]
+        if (len(group), 3, H, W) != shape:                                   # the last group, or --orig-size: another frame size
+            shape = (len(group), 3, H, W)
+            net.reshape_input("data", shape)
+        dev_imgs = [torch.from_numpy(f).cuda(a.device) for f in frames]
+        params = net.set_images("data", dev_imgs)                            # :77-85 for every frame of the group, on the device
+        torch.cuda.synchronize(a.device)
+        t0 = time.perf_counter()
+        net.forward()
+        torch.cuda.synchronize(a.device)
+        used += time.perf_counter() - t0                                     # :88-89: forward only
+        per_image, _ = net.detect_cascade_multi([dict(p, nms_overlap=a.nms_overlap) for p in params], outputs, cls_ids, det_thr=a.det_thr)
+        if a.dump_blobs:
+            os.makedirs(a.dump_blobs, exist_ok=True)
+            blobs = {b: net.get_blob(b) for t in outputs for b in t}
+            np.savez(os.path.join(a.dump_blobs, f"group_{g0 // a.batch:04d}.npz"), ratios=np.array([p["ratios"] for p in params], np.float64),
+                     org_hw=np.array([p["org_hw"] for p in params], np.float64), **blobs)
+        for i in range(len(group)):
+            for key in results:
+                results[key].append(per_image[i][key[0]][key[1]][0])
+        done += len(group)
+        if done // 100 != (done - len(group)) // 100 or done == len(files):
+            print(f"idx {done}/{len(files)}, avgtime={used / done:.4f}s")    # :145, per frame
+    for (o, c), dets in results.items():
+        path = os.path.join(a.out, f"{a.comp_id}_{names[cls_ids[c] - 1]}_{out_names[o]}_results.txt")
+        kitti.write_detections_dlm(path, dets)                               # :148-158
+        print(f"{path}: {sum(len(d) for d in dets)} detections over {len(files)} images")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
