@@ -368,6 +368,24 @@ MSCNN_API int mscnn_boxoutput_max_rows(const mscnn_boxoutput_desc* desc);
 MSCNN_API int mscnn_boxoutput_fwd_f32(const mscnn_boxoutput_desc* desc, const float* const* heads_host,
                             float* rois_out, float* props_out, int* anchor_ids_out, int cap,
                             int* count_out_dev, void* workspace, size_t workspace_bytes, void* stream);
+/*
+ * The same layer with every image of the batch side by side.  Arguments, contract and refusals are those of
+ * mscnn_boxoutput_fwd_f32, and every output word is bit-identical to it: rois, props, anchor ids, both count words, the rows
+ * grouped by image in image order, the dummy row only when no image of the batch keeps a box.  desc->num images run in groups of
+ * up to 32: five launches per group (decode + filter with the image on a grid axis, one select-and-sort workgroup per image, the
+ * NMS bit matrix with the image on blockIdx.z, one greedy-scan workgroup per image, then one small launch in which each image's
+ * workgroup sums the row counts of the images in front of it and writes its rows) where the per-image op takes four launches per
+ * image.  No workgroup waits for another; exactly one thread of the call's last launch stores count_out_dev[0..1], once, and
+ * nothing else stores there (it may be host-coherent memory that the host reads behind an event on `stream`; the words say how
+ * many rows the batch has, not that every image's rows have landed -- only the end of that launch does).  One image, and a
+ * descriptor on the large path (max_nms_num 0, or above 4032 with that many anchors), are served by mscnn_boxoutput_fwd_f32
+ * itself.  The workspace holds that op's workspace plus min(num, 32) per-image slices (1.9 MB each at 45,630 anchors and
+ * max_nms_num 2000); it is 0 with mscnn_last_error set for a bad descriptor.
+ */
+MSCNN_API size_t mscnn_boxoutput_batch_workspace_bytes(const mscnn_boxoutput_desc* desc);
+MSCNN_API int mscnn_boxoutput_batch_fwd_f32(const mscnn_boxoutput_desc* desc, const float* const* heads_host,
+                            float* rois_out, float* props_out, int* anchor_ids_out, int cap,
+                            int* count_out_dev, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Greedy NMS on already score-sorted boxes [n][4] = x y w h (nmsMax, greedy = true):
  * keep_out[n] bytes 0/1.  Exposed for the index-exactness parity tests. */

@@ -100,6 +100,10 @@ MSCNN_NET_API int mscnn_net_set_auto_calibrate(mscnn_net* net, double tol);
  * every reader that goes through this ABI).  ON by default (with the other Net-level fusions); on = 0 writes every blob in every
  * forward (MSCNN_NO_CHAIN=1 does the same process-wide). */
 MSCNN_NET_API int mscnn_net_set_chain_fusion(mscnn_net* net, int on);
+/* BoxOutput of a batched net (more than one image in its bottoms) runs every image side by side (mscnn_hip.h:
+ * mscnn_boxoutput_batch_fwd_f32): OFF by default (image after image, mscnn_boxoutput_fwd_f32) until the batched op has been timed; on = 1 selects it.  The tops are
+ * bit-identical either way, and a net of one image always takes mscnn_boxoutput_fwd_f32. */
+MSCNN_NET_API int mscnn_net_set_boxoutput_one_pass(mscnn_net* net, int on);
 /* The pairs the net registered at construction: producers[i] -> consumers[i] (layer indices; consumers[i] = -1: a top that only its
  * fused 2x2 pooling reads).  Returns their number and writes up to cap of them; whether a pair actually runs chained is decided per
  * forward (both planned kernels on the fp32 F(4x4,3x3) path, no numerical check pending, both layers inside the range). */

@@ -22,6 +22,10 @@
 //                             finally popcount-prefix compaction and emission of the output rows.
 // No MFMA anywhere here: integer / compare work, wave-level scans and ballots.
 //
+// A batch (mscnn_boxoutput_batch_fwd_f32): the same four device bodies with the image on a grid axis -- per-image counters and
+// workspace slices, groups of up to 32 images -- and a fifth launch that places the rows (row0 of an image = the rows of the images
+// in front of it); see "every image of a batch side by side" below.
+//
 // More than kMaxK = 4032 candidates into NMS (max_nms_num 0 -- the caffe.proto default, "no cap" -- or > 4032 while the heads
 // have that many anchors): steps 2-4 are replaced by a global-memory bitonic sort of all keys and the tiled greedy NMS of
 // nms_large.h (same predicate, same order: the same rows).  The deploy files of the reference set 2000-3000 and never get here.
@@ -75,11 +79,11 @@ struct DecodeArgs {
 // workspace counters
 enum { CNT_CAND = 0, CNT_ROWS = 1, CNT_REAL = 2, CNT_K = 3, CNT_BIG = 4 /* + BIG_STATE_WORDS */, CNT_WORDS = 8 };
 
-__global__ __launch_bounds__(256) void decode_filter_kernel(DecodeArgs a, u64* __restrict__ keys,
-                                                            float4* __restrict__ box_by_anchor,
-                                                            float* __restrict__ score_by_anchor, int* __restrict__ cnt) {
+// One anchor of image `image`: the body of decode_filter_kernel and of its batched form (same arithmetic, same order).
+__device__ __forceinline__ void decode_filter_anchor(const DecodeArgs& a, int image, int aid, u64* __restrict__ keys,
+                                                     float4* __restrict__ box_by_anchor, float* __restrict__ score_by_anchor,
+                                                     int* __restrict__ cnt) {
   const int total = a.head_off[a.num_heads];
-  const int aid = blockIdx.x * 256 + threadIdx.x;
   if (aid >= total) return;
   int j = 0;
   while (aid >= a.head_off[j + 1]) ++j;
@@ -87,7 +91,7 @@ __global__ __launch_bounds__(256) void decode_filter_kernel(DecodeArgs a, u64* _
   const int width = a.head_w[j], height = a.head_h[j];
   const int spatial = width * height;
   const int cls_num = a.channels - 4;
-  const float* d = a.head[j] + (size_t)a.image * a.channels * spatial + id;
+  const float* d = a.head[j] + (size_t)image * a.channels * spatial + id;
   const int h = id / width, w = id % width;
   // box_output_layer.cpp:120-127
   float fg = -FLT_MAX;
@@ -120,15 +124,18 @@ __global__ __launch_bounds__(256) void decode_filter_kernel(DecodeArgs a, u64* _
   }
 }
 
+__global__ __launch_bounds__(256) void decode_filter_kernel(DecodeArgs a, u64* __restrict__ keys,
+                                                            float4* __restrict__ box_by_anchor,
+                                                            float* __restrict__ score_by_anchor, int* __restrict__ cnt) {
+  decode_filter_anchor(a, a.image, blockIdx.x * 256 + threadIdx.x, keys, box_by_anchor, score_by_anchor, cnt);
+}
+
 // One workgroup.  keys[0..n) unordered, unique.  Output: sorted_box[k], sorted_score[k], sorted_aid[k],
-// cnt[CNT_K] = K.
-__global__ __launch_bounds__(kSortThreads) void select_sort_kernel(const u64* __restrict__ keys,
-                                                                   const float4* __restrict__ box_by_anchor,
-                                                                   const float* __restrict__ score_by_anchor,
-                                                                   float4* __restrict__ sorted_box,
-                                                                   float* __restrict__ sorted_score,
-                                                                   int* __restrict__ sorted_aid, int* __restrict__ cnt,
-                                                                   int max_nms_num) {
+// cnt[CNT_K] = K.  (The body of select_sort_kernel and of its batched form, one workgroup per image.)
+__device__ __forceinline__ void select_sort_body(const u64* __restrict__ keys, const float4* __restrict__ box_by_anchor,
+                                                 const float* __restrict__ score_by_anchor, float4* __restrict__ sorted_box,
+                                                 float* __restrict__ sorted_score, int* __restrict__ sorted_aid,
+                                                 int* __restrict__ cnt, int max_nms_num) {
   __shared__ u64 sk[kSortCap];
   __shared__ unsigned hist[256];
   __shared__ u64 s_prefix;
@@ -378,12 +385,21 @@ __global__ __launch_bounds__(kSortThreads) void select_sort_kernel(const u64* __
   BO_STAMP(5);
 }
 
+__global__ __launch_bounds__(kSortThreads) void select_sort_kernel(const u64* __restrict__ keys,
+                                                                   const float4* __restrict__ box_by_anchor,
+                                                                   const float* __restrict__ score_by_anchor,
+                                                                   float4* __restrict__ sorted_box,
+                                                                   float* __restrict__ sorted_score,
+                                                                   int* __restrict__ sorted_aid, int* __restrict__ cnt,
+                                                                   int max_nms_num) {
+  select_sort_body(keys, box_by_anchor, score_by_anchor, sorted_box, sorted_score, sorted_aid, cnt, max_nms_num);
+}
+
 // mask[i][cb] bit t set <=> j = cb*64+t > i and IoU(box_i, box_j) > thr.  Upper-triangle blocks only.
 // 256 threads per 64 x 64 block: wave v tests its 64 rows against columns 16v .. 16v+15 and the four 16-bit pieces meet in LDS
 // (one wave per block did 64 dependent IoUs -- with their divisions -- per lane, 2 waves per CU: 20 us for K = 2000; round 3).
-__global__ __launch_bounds__(256) void nms_mask_kernel(const float4* __restrict__ boxes, const int* __restrict__ cnt_k,
-                                                       int n_fixed, float thr, int mode, u64* __restrict__ mask, int wpr) {
-  const int n = cnt_k ? *cnt_k : n_fixed;
+__device__ __forceinline__ void nms_mask_block(const float4* __restrict__ boxes, int n, float thr, int mode,
+                                               u64* __restrict__ mask, int wpr) {
   const int rb = blockIdx.y, cb = blockIdx.x;
   if (cb < rb || rb * 64 >= n || cb * 64 >= n) return;
   __shared__ float4 cbox[64];
@@ -411,6 +427,11 @@ __global__ __launch_bounds__(256) void nms_mask_kernel(const float4* __restrict_
     mask[(size_t)i * wpr + cb] = (u64)part[0][t] | ((u64)part[1][t] << 16) | ((u64)part[2][t] << 32) | ((u64)part[3][t] << 48);
 }
 
+__global__ __launch_bounds__(256) void nms_mask_kernel(const float4* __restrict__ boxes, const int* __restrict__ cnt_k,
+                                                       int n_fixed, float thr, int mode, u64* __restrict__ mask, int wpr) {
+  nms_mask_block(boxes, cnt_k ? *cnt_k : n_fixed, thr, mode, mask, wpr);
+}
+
 struct EmitArgs {
   const float4* sorted_box;
   const float* sorted_score;
@@ -434,6 +455,42 @@ __device__ __forceinline__ void boxoutput_finish(int rows, float* rois, float* p
   }
 }
 
+// wave 0, lane c holding the keep-word of chunk c: the words, the exclusive prefix of their popcounts and the total, into LDS
+__device__ __forceinline__ void keep_prefix(u64 mykeep, int lane, u64* keepw, int* pre, int* total) {
+  keepw[lane] = mykeep;
+  // exclusive prefix of popcounts over chunks
+  const int mine = __popcll(mykeep);
+  int incl = mine;
+  for (int d = 1; d < 64; d <<= 1) {
+    const int v = __shfl_up(incl, d, 64);
+    if (lane >= d) incl += v;
+  }
+  pre[lane] = incl - mine;
+  if (lane == 63) *total = incl;
+}
+
+// rows row0 .. row0 + kept_total of image `image`: the first kept_total kept boxes of the n sorted ones (256 threads)
+__device__ __forceinline__ void emit_rows(const EmitArgs& e, int image, const u64* keepw, const int* pre, int n, int kept_total,
+                                          int row0) {
+  for (int k = threadIdx.x; k < n; k += 256) {
+    const int c = k >> 6, l = k & 63;
+    const u64 kw = keepw[c];
+    if (!((kw >> l) & 1ull)) continue;
+    const int local = pre[c] + __popcll(kw & ((1ull << l) - 1ull));
+    if (local >= kept_total) continue;
+    const int row = row0 + local;
+    if (row >= e.cap) continue;
+    const float4 b = e.sorted_box[k];
+    float* r = e.rois + 5 * (size_t)row;
+    r[0] = (float)image; r[1] = b.x; r[2] = b.y; r[3] = b.x + b.z; r[4] = b.y + b.w;   // :201-210
+    if (e.props) {
+      float* q = e.props + 6 * (size_t)row;
+      q[0] = (float)image; q[1] = b.x; q[2] = b.y; q[3] = b.x + b.z; q[4] = b.y + b.w; q[5] = e.sorted_score[k];
+    }
+    if (e.aids) e.aids[row] = e.sorted_aid[k];
+  }
+}
+
 __global__ __launch_bounds__(256) void nms_scan_emit_kernel(const u64* __restrict__ mask, int wpr, int W, EmitArgs e,
                                                             int* __restrict__ cnt) {
   extern __shared__ __attribute__((aligned(16))) u64 dyn_lds[];
@@ -449,44 +506,108 @@ __global__ __launch_bounds__(256) void nms_scan_emit_kernel(const u64* __restric
   }
   const u64 mykeep = greedy_scan(mask, n, wpr, W, dyn_lds);
   BO_STAMP(9);
-  if (wave == 0) {
-    keepw[lane] = mykeep;
-    // exclusive prefix of popcounts over chunks
-    const int mine = __popcll(mykeep);
-    int incl = mine;
-    for (int d = 1; d < 64; d <<= 1) {
-      const int v = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += v;
-    }
-    pre[lane] = incl - mine;
-    if (lane == 63) s_total = incl;
-  }
+  if (wave == 0) keep_prefix(mykeep, lane, keepw, pre, &s_total);
   __syncthreads();
   int kept_total = s_total;
   if (e.max_post > 0 && kept_total > e.max_post) kept_total = e.max_post;     // :184-186
   const int row0 = cnt[CNT_ROWS];
-  for (int k = tid; k < n; k += 256) {
-    const int c = k >> 6, l = k & 63;
-    const u64 kw = keepw[c];
-    if (!((kw >> l) & 1ull)) continue;
-    const int local = pre[c] + __popcll(kw & ((1ull << l) - 1ull));
-    if (local >= kept_total) continue;
-    const int row = row0 + local;
-    if (row >= e.cap) continue;
-    const float4 b = e.sorted_box[k];
-    float* r = e.rois + 5 * (size_t)row;
-    r[0] = (float)e.image; r[1] = b.x; r[2] = b.y; r[3] = b.x + b.z; r[4] = b.y + b.w;   // :201-210
-    if (e.props) {
-      float* q = e.props + 6 * (size_t)row;
-      q[0] = (float)e.image; q[1] = b.x; q[2] = b.y; q[3] = b.x + b.z; q[4] = b.y + b.w; q[5] = e.sorted_score[k];
-    }
-    if (e.aids) e.aids[row] = e.sorted_aid[k];
-  }
+  emit_rows(e, e.image, keepw, pre, n, kept_total, row0);
   __syncthreads();
   BO_STAMP(10);
   if (tid == 0) {
     cnt[CNT_ROWS] = row0 + kept_total; cnt[CNT_CAND] = 0;
     if (e.count_out) boxoutput_finish(row0 + kept_total, e.rois, e.props, e.aids, e.count_out);
+  }
+}
+
+// ---- every image of a batch side by side (mscnn_boxoutput_batch_fwd_f32) -----------------------------------------------------
+// Image g of a group of up to kBatchGroup images has its own counters (cnt + g * CNT_WORDS; CNT_ROWS holds the image's OWN row
+// count there, min(kept, max_post_nms_num)) and its own slice of the workspace.  The four kernels above run with the image on a grid
+// axis.  The one coupling between the images -- row0 of image g = the rows of the images before it -- is resolved by a fifth launch
+// behind the scan, so no workgroup ever waits for another inside a launch: each image's workgroup adds the at most 31 counts in
+// front of it to the rows of the earlier groups (row_base[parity]) and writes its rows.
+constexpr int kBatchGroup = 32;
+
+struct BatchSlices {
+  char* base;                 // slice g at base + g * stride
+  size_t stride, keys, box, score, sbox, sscore, said, mask, keepw;
+  int* cnt;                   // counters of image g at cnt + g * CNT_WORDS
+  int* row_base;              // [2]: rows of the groups before this one, read at [parity], written at [parity ^ 1]
+  template <typename T> __device__ __forceinline__ T* at(int g, size_t off) const {
+    return reinterpret_cast<T*>(base + (size_t)g * stride + off);
+  }
+};
+
+// a.image = the group's first image
+__global__ __launch_bounds__(256) void decode_filter_batch_kernel(DecodeArgs a, BatchSlices s) {
+  const int g = blockIdx.y;
+  decode_filter_anchor(a, a.image + g, blockIdx.x * 256 + threadIdx.x, s.at<u64>(g, s.keys), s.at<float4>(g, s.box),
+                       s.at<float>(g, s.score), s.cnt + g * CNT_WORDS);
+}
+
+__global__ __launch_bounds__(kSortThreads) void select_sort_batch_kernel(BatchSlices s, int max_nms_num) {
+  const int g = blockIdx.x;
+  select_sort_body(s.at<u64>(g, s.keys), s.at<float4>(g, s.box), s.at<float>(g, s.score), s.at<float4>(g, s.sbox),
+                   s.at<float>(g, s.sscore), s.at<int>(g, s.said), s.cnt + g * CNT_WORDS, max_nms_num);
+}
+
+__global__ __launch_bounds__(256) void nms_mask_batch_kernel(BatchSlices s, float thr, int mode, int wpr) {
+  const int g = blockIdx.z;
+  nms_mask_block(s.at<float4>(g, s.sbox), s.cnt[g * CNT_WORDS + CNT_K], thr, mode, s.at<u64>(g, s.mask), wpr);
+}
+
+// greedy scan of image g: its keep-words and its row count go to memory for the emit launch
+__global__ __launch_bounds__(256) void nms_scan_batch_kernel(BatchSlices s, int wpr, int W, int max_post) {
+  extern __shared__ __attribute__((aligned(16))) u64 dyn_lds[];
+  __shared__ u64 keepw[64];
+  __shared__ int pre[64];
+  __shared__ int s_total;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int g = blockIdx.x;
+  int* cnt = s.cnt + g * CNT_WORDS;
+  const int n = cnt[CNT_K];
+  if (n <= 0) {
+    if (tid == 0) cnt[CNT_ROWS] = 0;
+    return;
+  }
+  const u64 mykeep = greedy_scan(s.at<u64>(g, s.mask), n, wpr, W, dyn_lds);
+  if (wave == 0) {
+    keep_prefix(mykeep, lane, keepw, pre, &s_total);
+    s.at<u64>(g, s.keepw)[lane] = mykeep;
+    if (lane == 63) {
+      int kept_total = s_total;
+      if (max_post > 0 && kept_total > max_post) kept_total = max_post;     // :184-186
+      cnt[CNT_ROWS] = kept_total;
+    }
+  }
+}
+
+// e.image = the group's first image; e.count_out: the call's last group only -- thread 0 of its last workgroup writes {R, real rows}
+__global__ __launch_bounds__(256) void emit_batch_kernel(BatchSlices s, EmitArgs e, int parity) {
+  __shared__ u64 keepw[64];
+  __shared__ int pre[64];
+  __shared__ int s_total;
+  const int tid = threadIdx.x;
+  const int g = blockIdx.x;
+  int* cnt = s.cnt + g * CNT_WORDS;
+  const int n = cnt[CNT_K], kept_total = cnt[CNT_ROWS];
+  int row0 = s.row_base[parity];
+  for (int j = 0; j < g; ++j) row0 += s.cnt[j * CNT_WORDS + CNT_ROWS];     // (uniform: at most kBatchGroup - 1 scalar loads)
+  if (n > 0) {
+    if (tid < 64) keep_prefix(s.at<u64>(g, s.keepw)[tid], tid, keepw, pre, &s_total);
+    __syncthreads();
+    e.sorted_box = s.at<float4>(g, s.sbox); e.sorted_score = s.at<float>(g, s.sscore); e.sorted_aid = s.at<int>(g, s.said);
+    emit_rows(e, e.image + g, keepw, pre, n, kept_total, row0);
+  }
+  // (as in nms_scan_emit_kernel: this workgroup's rows are issued before the count words.  The other images' workgroups may
+  // still be writing theirs: {R, real rows} say how many rows the batch has, the END OF THE LAUNCH says that they are all there.)
+  __syncthreads();
+  if (tid == 0) {
+    cnt[CNT_CAND] = 0;                                 // (the next group's decode appends from 0; nobody else reads this word)
+    if (g == (int)gridDim.x - 1) {
+      s.row_base[parity ^ 1] = row0 + kept_total;
+      if (e.count_out) boxoutput_finish(row0 + kept_total, e.rois, e.props, e.aids, e.count_out);
+    }
   }
 }
 
@@ -593,6 +714,42 @@ WsLayout layout_for(int anchors, int max_nms_num) {
   return L;
 }
 
+// The batched op's workspace: the per-image op's own layout in front (the cases that fall through to it -- one image, the large
+// path -- use it as it is), then one counter block per image of a group plus one that holds row_base, and min(num, kBatchGroup)
+// slices.  A batched call never touches the front part (2.3 MB at 7s-576 size against 59 MB of slices); it stays in the batched size so
+// that the size grows with num from 1 on: a buffer sized for num images serves every smaller batch, the one-image fall-through
+// (which needs the 4032 x 63 mask of the per-image op, more than two small slices) included.  The mask of a slice has kblocks = ceil(min(kcap, kMaxK) / 64) words per row and
+// 64 * kblocks rows (512 KB at max_nms_num 2000, not the 2 MB of 4032 x 63): 1.9 MB per image at 7s-576 size, 59 MB a group.
+struct BatchLayout {
+  WsLayout one;
+  size_t cnt, slices, stride, keys, box, score, sbox, sscore, said, mask, keepw, total;
+  int group, kblocks;
+  bool batched;               // false: mscnn_boxoutput_fwd_f32 serves the call
+};
+
+BatchLayout batch_layout_for(int anchors, int max_nms_num, int num) {
+  BatchLayout B;
+  B.one = layout_for(anchors, max_nms_num);
+  B.batched = num > 1 && !B.one.big;
+  B.group = B.batched ? (num < kBatchGroup ? num : kBatchGroup) : 0;
+  B.kblocks = mscnn::cdiv(B.one.kcap < kMaxK ? B.one.kcap : kMaxK, 64);
+  const size_t rows = (size_t)B.kblocks * 64;
+  size_t o = 0;
+  B.keys = o; o += align_up((size_t)anchors * sizeof(u64), 256);
+  B.box = o; o += align_up((size_t)anchors * sizeof(float4), 256);
+  B.score = o; o += align_up((size_t)anchors * sizeof(float), 256);
+  B.sbox = o; o += align_up(rows * sizeof(float4), 256);
+  B.sscore = o; o += align_up(rows * sizeof(float), 256);
+  B.said = o; o += align_up(rows * sizeof(int), 256);
+  B.mask = o; o += align_up(rows * B.kblocks * sizeof(u64), 256);
+  B.keepw = o; o += align_up(64 * sizeof(u64), 256);
+  B.stride = o;
+  B.cnt = B.one.total;
+  B.slices = B.cnt + align_up((size_t)(kBatchGroup + 1) * CNT_WORDS * sizeof(int), 256);
+  B.total = B.batched ? B.slices + (size_t)B.group * B.stride : B.one.total;
+  return B;
+}
+
 int total_anchors(const mscnn_boxoutput_desc* d) {
   long t = 0;
   for (int j = 0; j < d->num_heads; ++j) t += (long)d->head_h[j] * d->head_w[j];
@@ -614,6 +771,29 @@ static int check_desc(const mscnn_boxoutput_desc* d) {
   MSCNN_REQUIRE(anchors > 0, "boxoutput: no anchors");
   MSCNN_REQUIRE(d->max_nms_num >= 0 && d->max_post_nms_num >= 0, "boxoutput: negative max_nms_num / max_post_nms_num");
   MSCNN_REQUIRE(anchors <= (1 << 26), "boxoutput: %d anchors", anchors);
+  return MSCNN_OK;
+}
+
+// the descriptor + head pointers as the decode kernels' argument (image left to the caller)
+static int fill_decode_args(const mscnn_boxoutput_desc* d, const float* const* heads_host, DecodeArgs* ap) {
+  DecodeArgs& a = *ap;
+  a.num_heads = d->num_heads;
+  a.channels = d->channels;
+  a.image = 0;
+  a.head_off[0] = 0;
+  for (int j = 0; j < d->num_heads; ++j) {
+    MSCNN_REQUIRE(heads_host[j], "boxoutput: head %d is null", j);
+    a.head[j] = heads_host[j];
+    a.head_h[j] = d->head_h[j]; a.head_w[j] = d->head_w[j];
+    a.head_off[j + 1] = a.head_off[j] + d->head_h[j] * d->head_w[j];
+    a.field_w[j] = d->field_w[j]; a.field_h[j] = d->field_h[j]; a.ds[j] = d->downsample_rate[j];
+  }
+  // box_output_layer.cpp:76-77 (host libm, like the reference layer)
+  a.min_whr = logf(1.f / d->field_whr); a.max_whr = logf(d->field_whr);
+  a.min_xyr = -1.f / d->field_xyr; a.max_xyr = 1.f / d->field_xyr;
+  a.fg_thr = d->fg_thr; a.min_size = d->min_size;
+  a.do_norm = d->do_bbox_norm;
+  for (int k = 0; k < 4; ++k) { a.mean[k] = d->bbox_mean[k]; a.stdv[k] = d->bbox_std[k]; }
   return MSCNN_OK;
 }
 
@@ -656,22 +836,8 @@ extern "C" int mscnn_boxoutput_fwd_f32(const mscnn_boxoutput_desc* d, const floa
   u64* mask = reinterpret_cast<u64*>(ws + L.mask);
 
   DecodeArgs a;
-  a.num_heads = d->num_heads;
-  a.channels = d->channels;
-  a.head_off[0] = 0;
-  for (int j = 0; j < d->num_heads; ++j) {
-    MSCNN_REQUIRE(heads_host[j], "boxoutput: head %d is null", j);
-    a.head[j] = heads_host[j];
-    a.head_h[j] = d->head_h[j]; a.head_w[j] = d->head_w[j];
-    a.head_off[j + 1] = a.head_off[j] + d->head_h[j] * d->head_w[j];
-    a.field_w[j] = d->field_w[j]; a.field_h[j] = d->field_h[j]; a.ds[j] = d->downsample_rate[j];
-  }
-  // box_output_layer.cpp:76-77 (host libm, like the reference layer)
-  a.min_whr = logf(1.f / d->field_whr); a.max_whr = logf(d->field_whr);
-  a.min_xyr = -1.f / d->field_xyr; a.max_xyr = 1.f / d->field_xyr;
-  a.fg_thr = d->fg_thr; a.min_size = d->min_size;
-  a.do_norm = d->do_bbox_norm;
-  for (int k = 0; k < 4; ++k) { a.mean[k] = d->bbox_mean[k]; a.stdv[k] = d->bbox_std[k]; }
+  rc = fill_decode_args(d, heads_host, &a);
+  if (rc != MSCNN_OK) return rc;
 
   MSCNN_HIP_TRY(hipMemsetAsync(cnt, 0, CNT_WORDS * sizeof(int), st));
   const int kcap = L.kcap;
@@ -710,6 +876,60 @@ extern "C" int mscnn_boxoutput_fwd_f32(const mscnn_boxoutput_desc* d, const floa
   }
   if (L.big || d->num <= 0) {          // (the one-workgroup path finished in its last scan kernel)
     boxoutput_finish_kernel<<<1, 1, 0, st>>>(cnt, rois_out, props_out, anchor_ids_out, count_out_dev);
+    MSCNN_POST_LAUNCH();
+  }
+  return MSCNN_OK;
+}
+
+extern "C" size_t mscnn_boxoutput_batch_workspace_bytes(const mscnn_boxoutput_desc* desc) {
+  if (check_desc(desc) != MSCNN_OK) return 0;
+  return batch_layout_for(total_anchors(desc), desc->max_nms_num, desc->num).total;
+}
+
+extern "C" int mscnn_boxoutput_batch_fwd_f32(const mscnn_boxoutput_desc* d, const float* const* heads_host, float* rois_out,
+                                             float* props_out, int* anchor_ids_out, int cap, int* count_out_dev, void* workspace,
+                                             size_t workspace_bytes, void* stream) {
+  int rc = check_desc(d);
+  if (rc != MSCNN_OK) return rc;
+  MSCNN_REQUIRE(heads_host && rois_out && count_out_dev && workspace, "boxoutput: null pointer");
+  MSCNN_REQUIRE(cap >= 1, "boxoutput: cap must be >= 1");
+  const int anchors = total_anchors(d);
+  const BatchLayout B = batch_layout_for(anchors, d->max_nms_num, d->num);
+  if (workspace_bytes < B.total) {
+    set_error("boxoutput: workspace %zu < %zu", workspace_bytes, B.total);
+    return MSCNN_ERR_WORKSPACE;
+  }
+  // one image has no row offset to resolve (its four launches are the whole op), the large path is serial by design
+  if (!B.batched)
+    return mscnn_boxoutput_fwd_f32(d, heads_host, rois_out, props_out, anchor_ids_out, cap, count_out_dev, workspace, workspace_bytes,
+                                   stream);
+  DecodeArgs a;
+  rc = fill_decode_args(d, heads_host, &a);
+  if (rc != MSCNN_OK) return rc;
+  hipStream_t st = as_stream(stream);
+  char* ws = static_cast<char*>(workspace);
+  BatchSlices s;
+  s.base = ws + B.slices; s.stride = B.stride;
+  s.keys = B.keys; s.box = B.box; s.score = B.score; s.sbox = B.sbox; s.sscore = B.sscore; s.said = B.said; s.mask = B.mask;
+  s.keepw = B.keepw;
+  s.cnt = reinterpret_cast<int*>(ws + B.cnt);
+  s.row_base = s.cnt + kBatchGroup * CNT_WORDS;
+  MSCNN_HIP_TRY(hipMemsetAsync(s.cnt, 0, (size_t)(kBatchGroup + 1) * CNT_WORDS * sizeof(int), st));      // the one clear of the call
+  const int kblocks = B.kblocks;
+  for (int img0 = 0, grp = 0; img0 < d->num; img0 += kBatchGroup, ++grp) {
+    const int G = d->num - img0 < kBatchGroup ? d->num - img0 : kBatchGroup;
+    a.image = img0;
+    decode_filter_batch_kernel<<<dim3(cdiv(anchors, 256), G), 256, 0, st>>>(a, s);
+    MSCNN_POST_LAUNCH();
+    select_sort_batch_kernel<<<G, kSortThreads, 0, st>>>(s, d->max_nms_num);
+    MSCNN_POST_LAUNCH();
+    nms_mask_batch_kernel<<<dim3(kblocks, kblocks, G), 256, 0, st>>>(s, d->iou_thr, d->nms_mode, kblocks);
+    MSCNN_POST_LAUNCH();
+    nms_scan_batch_kernel<<<G, 256, (size_t)2 * 64 * kblocks * sizeof(u64), st>>>(s, kblocks, kblocks, d->max_post_nms_num);
+    MSCNN_POST_LAUNCH();
+    EmitArgs e{nullptr, nullptr, nullptr, rois_out, props_out, anchor_ids_out, cap, img0, d->max_post_nms_num,
+               img0 + G == d->num ? count_out_dev : nullptr};
+    emit_batch_kernel<<<G, 256, 0, st>>>(s, e, grp & 1);
     MSCNN_POST_LAUNCH();
   }
   return MSCNN_OK;

@@ -143,6 +143,9 @@ def lib():
         L.mscnn_boxoutput_max_rows.argtypes = [C.c_void_p]
         L.mscnn_boxoutput_fwd_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                               C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.mscnn_boxoutput_batch_workspace_bytes.restype = C.c_size_t
+        L.mscnn_boxoutput_batch_workspace_bytes.argtypes = [C.c_void_p]
+        L.mscnn_boxoutput_batch_fwd_f32.argtypes = L.mscnn_boxoutput_fwd_f32.argtypes
         L.mscnn_nms_workspace_bytes.restype = C.c_size_t
         L.mscnn_nms_workspace_bytes.argtypes = [C.c_int]
         L.mscnn_nms_greedy_f32.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
@@ -536,11 +539,14 @@ def make_boxoutput_desc(head_shapes, num, channels, field_w, field_h, downsample
 
 
 class BoxOutput:
-    """Device-resident BoxOutput layer state: descriptor + workspace + output buffers."""
+    """Device-resident BoxOutput layer state: descriptor + workspace + output buffers.  one_pass: every image of the batch side
+    by side (mscnn_boxoutput_batch_fwd_f32) instead of image after image -- the same words either way."""
 
-    def __init__(self, desc, device="cuda"):
+    def __init__(self, desc, device="cuda", one_pass=False):
         self.desc = desc
-        wb = lib().mscnn_boxoutput_workspace_bytes(C.byref(desc))
+        L = lib()
+        self._fwd = L.mscnn_boxoutput_batch_fwd_f32 if one_pass else L.mscnn_boxoutput_fwd_f32
+        wb = (L.mscnn_boxoutput_batch_workspace_bytes if one_pass else L.mscnn_boxoutput_workspace_bytes)(C.byref(desc))
         if wb == 0:
             raise MscnnError(lib().mscnn_last_error().decode())
         self.cap = lib().mscnn_boxoutput_max_rows(C.byref(desc))
@@ -555,8 +561,8 @@ class BoxOutput:
         ptrs = (C.c_void_p * n)(*[h.data_ptr() for h in heads])
         for h in heads:
             _dev(h)
-        _check(lib().mscnn_boxoutput_fwd_f32(C.byref(self.desc), ptrs, _dev(self.rois), _dev(self.props), _dev(self.aids),
-                                             self.cap, _dev(self.count), _dev(self.ws), self.ws.numel(), _stream()))
+        _check(self._fwd(C.byref(self.desc), ptrs, _dev(self.rois), _dev(self.props), _dev(self.aids),
+                         self.cap, _dev(self.count), _dev(self.ws), self.ws.numel(), _stream()))
 
     def forward(self, heads):
         self.forward_async(heads)

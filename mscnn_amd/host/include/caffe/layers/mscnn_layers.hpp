@@ -463,6 +463,9 @@ class BoxOutputLayer : public Layer<Dtype> {
   // the device runs it while the host takes R, reshapes the tops and launches what follows -- the frame's one host round trip no
   // longer idles the GPU.  The Net puts the sliding-maximum maps of the fused ROI pooling there (they depend on conv4_3 only).
   void set_before_sync(std::function<void()> f) { before_sync_ = std::move(f); }
+  // more than one image: all of them side by side (mscnn_boxoutput_batch_fwd_f32) or image after image -- same tops.
+  // Off until the batched op has been timed against the per-image one
+  void set_one_pass(bool on) { one_pass_ = on; }
  protected:
   MSCNN_NO_CPU_PATH("BoxOutput")
   virtual void Forward_gpu(const vector<Blob<Dtype>*>& bottom, const vector<Blob<Dtype>*>& top);
@@ -472,6 +475,7 @@ class BoxOutputLayer : public Layer<Dtype> {
   DeviceBuffer workspace_;
   int cap_, last_rows_;
   bool forwarded_;
+  bool one_pass_ = false;
   std::function<void()> before_sync_;
   void* count_ready_ = nullptr;      // hipEvent_t behind BoxOutput's kernels
   int* host_count_ = nullptr;        // host-coherent pinned landing place of {R, real rows}, and the address the device writes it through

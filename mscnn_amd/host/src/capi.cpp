@@ -222,6 +222,12 @@ int mscnn_net_set_auto_calibrate(mscnn_net* n, double tol) {
 int mscnn_net_set_chain_fusion(mscnn_net* n, int on) {
   return guarded([&] { n->net->SetChainFusion(on != 0); });
 }
+int mscnn_net_set_boxoutput_one_pass(mscnn_net* n, int on) {
+  return guarded([&] {
+    for (const auto& layer : n->net->layers())
+      if (auto* bo = dynamic_cast<caffe::BoxOutputLayer<float>*>(layer.get())) bo->set_one_pass(on != 0);
+  });
+}
 int mscnn_net_chain_pairs(const mscnn_net* n, int* producers, int* consumers, int cap) {
   const auto pairs = n->net->chain_pairs();
   for (int i = 0; i < cap && i < (int)pairs.size(); ++i) {

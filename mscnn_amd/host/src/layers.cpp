@@ -965,7 +965,10 @@ void BoxOutputLayer<Dtype>::Forward_gpu(const vector<Blob<Dtype>*>& bottom, cons
   FillBoxOutputDesc(this->layer_param_, bottom, fg_thr_, iou_thr_, nms_type_, &d);
   const float* heads[MSCNN_BOXOUT_MAX_HEADS];
   for (int j = 0; j < n; ++j) heads[j] = bottom[j]->gpu_data();
-  const size_t wbytes = mscnn_boxoutput_workspace_bytes(&d);
+  // with the switch on (off by default) a batch runs every image side by side (the op itself keeps the large path -- max_nms_num 0 or above 4032 -- image after image);
+  // one image takes the per-image op exactly as before
+  const bool batch = one_pass_ && d.num > 1;
+  const size_t wbytes = batch ? mscnn_boxoutput_batch_workspace_bytes(&d) : mscnn_boxoutput_workspace_bytes(&d);
   CHECK_GT(wbytes, 0u) << mscnn_last_error();
   void* ws = workspace_.Reserve(wbytes);
   cap_ = mscnn_boxoutput_max_rows(&d);
@@ -988,7 +991,8 @@ void BoxOutputLayer<Dtype>::Forward_gpu(const vector<Blob<Dtype>*>& bottom, cons
     host_count_dev_ = static_cast<int*>(dp);
   }
   static_cast<volatile int*>(host_count_)[0] = -1;
-  MSCNN_CHECK(mscnn_boxoutput_fwd_f32(&d, heads, rois, props, nullptr, cap_, host_count_dev_, ws, wbytes, S()));
+  MSCNN_CHECK((batch ? mscnn_boxoutput_batch_fwd_f32 : mscnn_boxoutput_fwd_f32)(&d, heads, rois, props, nullptr, cap_, host_count_dev_,
+                                                                               ws, wbytes, S()));
   // The only host round trip of the layer: R (4 bytes) is needed to Reshape the tops (layer.hpp:451-456 propagates it
   // to ROIPooling and the detection sub-net).  The reference moves all 7 head blobs D2H and the ROIs H2D here.
   if (!count_ready_) { hipEvent_t e; HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); count_ready_ = e; }

@@ -50,7 +50,7 @@ def lib():
             "mscnn_net_set_conv_algo": [vp, ci, ci], "mscnn_net_set_inner_product_algo": [vp, ci, ci], "mscnn_net_set_conv_tuning": [vp, ci, ci, ci, ci],
             "mscnn_net_calibrate_numerics": [vp, C.c_double, vp], "mscnn_net_set_numerics_watch": [vp, ci, C.c_double],
             "mscnn_net_numerics_watch_state": [vp, vp, vp, ci], "mscnn_net_layer_calibration_err": [vp, ci],
-            "mscnn_net_set_auto_calibrate": [vp, C.c_double], "mscnn_net_set_chain_fusion": [vp, ci], "mscnn_net_chain_pairs": [vp, vp, vp, ci], "mscnn_net_auto_calibrate_state": [vp, vp, vp, ci],
+            "mscnn_net_set_auto_calibrate": [vp, C.c_double], "mscnn_net_set_chain_fusion": [vp, ci], "mscnn_net_set_boxoutput_one_pass": [vp, ci], "mscnn_net_chain_pairs": [vp, vp, vp, ci], "mscnn_net_auto_calibrate_state": [vp, vp, vp, ci],
             "mscnn_net_load_caffemodel": [vp, cs], "mscnn_net_set_stream": [vp], "mscnn_net_num_layers": [vp],
             "mscnn_net_layer_name": [vp, ci], "mscnn_net_layer_type": [vp, ci], "mscnn_net_layer_index": [vp, cs],
             "mscnn_net_layer_num_bottoms": [vp, ci], "mscnn_net_layer_num_tops": [vp, ci], "mscnn_net_layer_bottom": [vp, ci, ci],
@@ -205,6 +205,11 @@ class Net:
         """Chains of same-resolution F(4x4,3x3) convolutions keep the blob between two members out of HBM (on by default); off = every
         blob is written by every forward.  Reading such a blob re-runs its producer on demand -- same bytes either way."""
         _check(lib().mscnn_net_set_chain_fusion(self._h, int(on)))
+
+    def set_boxoutput_one_pass(self, on=True):
+        """BoxOutput of a batched net: every image side by side (on) or image after image (off, the default until the batched op has been timed) -- same bytes either way; a
+        net of one image always runs the per-image op."""
+        _check(lib().mscnn_net_set_boxoutput_one_pass(self._h, int(on)))
 
     def chain_pairs(self):
         """[(producer layer name, consumer layer name | None)]: convolutions whose top may stay unwritten while a forward runs
