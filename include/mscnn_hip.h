@@ -436,25 +436,37 @@ MSCNN_API int mscnn_detections_cascade_fwd(const mscnn_detections_desc* desc, fl
  *   [int32 S, R_all, cap, 0][S x int32 {count, rows, row0, 0}][cap x 5 doubles x y w h prob][cap x int32 id]
  * segment s = (image i, class c) owns pack rows [num_classes * row0 + c * rows, + rows), ids relative to its row0; count -1: the
  * image had more rows than max_rows_per_image (nothing was run for it).  Every word of the header and table is written by the
- * kernels; rows of a slot past its count are left as they were. */
+ * kernels; rows of a slot past its count are left as they were.  The layout below is the one definition every writer and
+ * reader of the pack uses (K = slots per image: num_classes here, num_outputs * num_classes in the cascade call). */
+enum { MSCNN_MULTI_PACK_WORDS = 4 };      /* int32 words of the header and of every table entry: entry s at word 4 * (1 + s) */
+typedef struct { size_t dets, ids, total; } mscnn_multi_pack_layout;      /* byte offsets of dets (= the table's bytes) and ids, pack bytes */
+static inline mscnn_multi_pack_layout mscnn_multi_pack_layout_of(int num_segments, int cap) {
+  const size_t S = (size_t)(num_segments > 0 ? num_segments : 0), rows = (size_t)(cap > 0 ? cap : 1);
+  mscnn_multi_pack_layout L;
+  L.dets = sizeof(int32_t) * MSCNN_MULTI_PACK_WORDS * (1 + S);
+  L.ids = L.dets + rows * 5 * sizeof(double);
+  L.total = (L.ids + rows * sizeof(int32_t) + 15) / 16 * 16;
+  return L;
+}
+#ifdef __HIPCC__      /* the kernels that write the pack place their slots with it too */
+__host__ __device__
+#endif
+static inline size_t mscnn_multi_pack_slot(int K, int row0, int k, int rows) {      /* first pack row of slot k of an image */
+  return (size_t)K * row0 + (size_t)k * rows;
+}
 MSCNN_API size_t mscnn_detections_multi_pack_bytes(int num_segments, int cap);
 MSCNN_API size_t mscnn_detections_multi_workspace_bytes(int num_segments, int max_rows_per_image);   /* 0: over 4032 rows */
 MSCNN_API int mscnn_detections_multi_fwd(const mscnn_detections_desc* desc, int num_images, int num_classes, const float* bbox_pred,
                                          const float* cls_pred, const float* props, int R_all, int max_rows_per_image, void* pack_dev,
                                          int cap, void* workspace, size_t workspace_bytes, void* stream);
 
-/* The cascade stage (mscnn_detections_cascade_fwd) for EVERY (image, cascade output, class) segment of a batched forward in one
- * pass: three launches per 32 segments, no host read.  outputs[num_outputs], 1 <= num_outputs <= 4: each cascade output's own blob
- * triple (boxes [R_all][5], cls_prob [R_all][ncls], props [R_all][5]; R_all common to all) -- the triples travel as kernel arguments.
- * Rows are grouped by image with the image index in column 0 of props (DecodeBBox carries BoxOutput's through); each segment finds
- * its rows in ITS output's props on the device.  desc[num_images * num_outputs * num_classes], indexed
- * [(image * num_outputs + output) * num_classes + class]: cls_id (1 .. that output's ncls), ratio_*, org_*, nms_overlap; the other
- * fields (ncls included: it comes from outputs[]) are not read.  det_thr: one value per call.  max_rows_per_image: as
- * mscnn_detections_multi_fwd, at most 4032 -- above that run mscnn_detections_cascade_fwd per segment.  Every segment is
- * bit-identical to mscnn_detections_cascade_fwd on its row range of its output's blobs, ids included.
- * pack_dev: the multi pack above with K = num_outputs * num_classes in the role of num_classes --
- * mscnn_detections_multi_pack_bytes(S, cap) bytes, S = num_images * K, cap >= K * R_all; segment (i, o, c) owns pack rows
- * [K * row0 + (o * num_classes + c) * rows, + rows), table entry {count (-1: over the bound), rows, row0, 0}. */
+/* The same one-pass stage for the cascade drivers (mscnn_detections_cascade_fwd per segment): several sources instead of one.
+ * outputs[num_outputs], 1 <= num_outputs <= 4: each cascade output's own blob triple (boxes [R_all][5], cls_prob [R_all][ncls],
+ * props [R_all][5]; R_all common to all); each segment finds its rows in ITS output's props.  desc[num_images * num_outputs *
+ * num_classes], indexed [(image * num_outputs + output) * num_classes + class]: cls_id (1 .. that output's ncls), ratio_*, org_*,
+ * nms_overlap; the other fields (ncls included: it comes from outputs[]) are not read.  det_thr: one value per call.  Every segment
+ * is bit-identical to mscnn_detections_cascade_fwd on its row range of its output's blobs, ids included.  pack_dev: the multi pack
+ * with K = num_outputs * num_classes slots per image, cap >= K * R_all; segment (i, o, c) owns slot k = o * num_classes + c. */
 typedef struct {
   const float* boxes;
   const float* cls_prob;

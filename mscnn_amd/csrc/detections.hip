@@ -94,7 +94,7 @@ __device__ __forceinline__ u64 det_key(float prob, int r) {
 }
 
 // Per-row transform + filter, key sort, write sorted boxes: the body of one workgroup (kSortThreads threads).  *n_out = survivors.
-// (shared by det_transform_sort_kernel and the segmented det_multi_transform_sort_kernel: one code path, the same bits)
+// (shared by det_transform_sort_kernel and the segmented det_seg_transform_sort_kernel: one code path, the same bits)
 __device__ __forceinline__ void det_transform_sort(const DetArgs& a, DetBox* __restrict__ sbox, double* __restrict__ sprob,
                                                    int* __restrict__ ssrc, DetBox* __restrict__ tmp_box, float* __restrict__ tmp_prob,
                                                    int* __restrict__ n_out) {
@@ -279,27 +279,30 @@ __global__ __launch_bounds__(256) void det_scan_emit_kernel(const u64* __restric
   det_scan_emit(mask, wpr, cnt[DC_N], sbox, sprob, ssrc, dets, ids, count_out, dyn_lds);
 }
 
-// ---- every (image, class) segment of a batched forward in one pass (mscnn_detections_multi_fwd) -------------------------------------
-// Segment s = image s / C, class slot s % C (image-major).  The ROI rows are grouped by image with the image index in column 0 of
-// props (box_output_layer.cpp:107, :156): each segment finds its [row0, row0 + rows) by binary search on the device and runs the
-// single-list path's three bodies above on that range, in a workspace slice of its own (max_rows rows).  Its detections go to pack
-// rows [C row0 + c rows, + rows): a slot it places without knowing any other segment; all slots tile [0, C R_all).
-constexpr int kSegsPerLaunch = 32;         // segment parameters travel as kernel arguments (2.1 KB of the 4 KB)
+// ---- every segment of a batched forward in one pass (mscnn_detections_multi_fwd, mscnn_detections_cascade_multi_fwd) ----------------
+// A source is a blob triple whose ROI rows are grouped by image, the image index in column 0 of props (box_output_layer.cpp:107,
+// :156; DecodeBBox copies it, decode_bbox_layer.cpp:110).  The plain stage has one (bbox_pred / cls_pred / proposals_score,
+// cascade = 0); the cascade stage one per cascade output (decoded boxes / probabilities / proposals, cascade = 1).  With K slots per
+// image and C classes per source, segment s = image s / K, source (s % K) / C, slot k = s % K (image-major, then source, then class).
+// Each segment finds its [row0, row0 + rows) in ITS source's props by binary search on the device and runs the single-list path's
+// three bodies above on that range, in a workspace slice of its own (max_rows rows).  Its detections go to pack rows
+// [K row0 + k rows, + rows): a slot it places without knowing any other segment; all slots tile [0, K R_all).
+constexpr int kSegsPerLaunch = 32;         // sources and segment parameters travel as kernel arguments (2.3 KB of the 4 KB)
+constexpr int kCascadeMaxOutputs = 4;
+struct DetSource { const float* boxes; const float* cls; const float* props; int ncls, cascade; };   // row strides: props 6 / 5, boxes 4 ncls / 5
 struct DetSeg { float mean[4], stdv[4]; float proposal_thr, ratio_h, ratio_w, org_h, org_w; int cls_id; double nms_overlap; };
-struct DetMultiArgs {
-  const float* bbox_pred; const float* cls_pred; const float* props;
-  int R_all, ncls, num_classes, max_rows, wpr, cap, num_segs, s0;       // s0: first segment of this launch
-  char* ws; size_t seg_stride_box, seg_stride_mask;                     // workspace: per-segment slices (det_multi_layout)
-  int* hdr;                                                             // pack: header, table, dets, ids
-  double* dets; int* ids;
+struct DetSegArgs {
+  int R_all, slots_per_image, classes_per_source, max_rows, wpr, cap, num_segs, s0;       // s0: first segment of this launch
+  char* ws; size_t seg_stride_box, seg_stride_mask;                     // workspace: per-segment slices (det_multi_ptrs)
+  int* hdr; double* dets; int* ids;                                     // pack: header + table, dets, ids (mscnn_multi_pack_layout)
+  DetSource src[kCascadeMaxOutputs];
   DetSeg seg[kSegsPerLaunch];
 };
+static_assert(sizeof(DetSegArgs) <= 4096, "DetSegArgs travels as kernel arguments");
 enum { SEG_N = 0, SEG_ROW0 = 1, SEG_ROWS = 2, SEG_BAD = 3, SEG_WORDS = 4 };   // workspace words per segment
-enum { PACK_HDR_WORDS = 4, PACK_SEG_WORDS = 4 };                              // {S, R_all, cap, 0}, {count, rows, row0, 0}
 
 struct DetMultiPtrs { int* cnt; DetBox* sbox; double* sprob; int* ssrc; DetBox* tbox; float* tprob; u64* mask; };
-template <class Args>      // DetMultiArgs or DetCascadeMultiArgs: the same workspace fields
-__device__ __forceinline__ DetMultiPtrs det_multi_ptrs(const Args& a, int s) {
+__device__ __forceinline__ DetMultiPtrs det_multi_ptrs(const DetSegArgs& a, int s) {
   // slices: [cnt: S x SEG_WORDS ints][sbox][sprob][ssrc][tbox][tprob] per segment (max_rows each, 256-byte aligned), then the masks
   const size_t M = (size_t)a.max_rows;
   char* base = a.ws + 256 * (((size_t)a.num_segs * SEG_WORDS * sizeof(int) + 255) / 256) + (size_t)s * a.seg_stride_box;
@@ -328,12 +331,14 @@ __device__ __forceinline__ int det_image_lower_bound(const float* __restrict__ p
 }
 
 // one workgroup per segment: find the rows, transform + filter + sort them
-__global__ __launch_bounds__(kSortThreads) void det_multi_transform_sort_kernel(DetMultiArgs a) {
+__global__ __launch_bounds__(kSortThreads) void det_seg_transform_sort_kernel(DetSegArgs a) {
   const int j = blockIdx.x, s = a.s0 + j;
-  const int img = s / a.num_classes;
+  const int img = s / a.slots_per_image;
+  const DetSource& t = a.src[(s % a.slots_per_image) / a.classes_per_source];
+  const int prop_stride = t.cascade ? 5 : 6, box_stride = t.cascade ? 5 : 4 * t.ncls;
   const DetMultiPtrs p = det_multi_ptrs(a, s);
   __shared__ int s_range[2];
-  if (threadIdx.x < 2) s_range[threadIdx.x] = det_image_lower_bound(a.props, a.R_all, img + threadIdx.x, 6);
+  if (threadIdx.x < 2) s_range[threadIdx.x] = det_image_lower_bound(t.props, a.R_all, img + threadIdx.x, prop_stride);
   if (s == 0 && threadIdx.x == 0) {
     a.hdr[0] = a.num_segs; a.hdr[1] = a.R_all; a.hdr[2] = a.cap; a.hdr[3] = 0;
   }
@@ -345,97 +350,31 @@ __global__ __launch_bounds__(kSortThreads) void det_multi_transform_sort_kernel(
   if (bad) { if (threadIdx.x == 0) p.cnt[SEG_N] = 0; return; }
   const DetSeg& g = a.seg[j];
   DetArgs d;
-  d.bbox_pred = a.bbox_pred + (size_t)row0 * 4 * a.ncls; d.cls_pred = a.cls_pred + (size_t)row0 * a.ncls; d.props = a.props + (size_t)row0 * 6;
-  d.R = rows; d.ncls = a.ncls; d.cls_id = g.cls_id;
+  d.bbox_pred = t.boxes + (size_t)row0 * box_stride; d.cls_pred = t.cls + (size_t)row0 * t.ncls; d.props = t.props + (size_t)row0 * prop_stride;
+  d.R = rows; d.ncls = t.ncls; d.cls_id = g.cls_id;
   for (int k = 0; k < 4; ++k) { d.mean[k] = g.mean[k]; d.stdv[k] = g.stdv[k]; }
   d.proposal_thr = g.proposal_thr; d.ratio_h = g.ratio_h; d.ratio_w = g.ratio_w; d.org_h = g.org_h; d.org_w = g.org_w;
-  d.cascade = 0;
+  d.cascade = t.cascade;
   det_transform_sort(d, p.sbox, p.sprob, p.ssrc, p.tbox, p.tprob, p.cnt + SEG_N);
 }
 
 // grid (wpr, wpr, segments): blocks past a segment's own n exit at once
-__global__ __launch_bounds__(256) void det_multi_mask_kernel(DetMultiArgs a) {
+__global__ __launch_bounds__(256) void det_seg_mask_kernel(DetSegArgs a) {
   const int j = blockIdx.z, s = a.s0 + j;
   const DetMultiPtrs p = det_multi_ptrs(a, s);
   det_mask_block(p.sbox, p.cnt[SEG_N], a.seg[j].nms_overlap, p.mask, a.wpr, blockIdx.y, blockIdx.x);
 }
 
 // one workgroup per segment: greedy scan, emit into the segment's slot, its table entry {count (-1: rows over the bound), rows, row0, 0}
-__global__ __launch_bounds__(256) void det_multi_scan_emit_kernel(DetMultiArgs a) {
+__global__ __launch_bounds__(256) void det_seg_scan_emit_kernel(DetSegArgs a) {
   extern __shared__ __attribute__((aligned(16))) u64 dyn_lds[];
   const int j = blockIdx.x, s = a.s0 + j;
-  const int c = s % a.num_classes;
   const DetMultiPtrs p = det_multi_ptrs(a, s);
   const int row0 = p.cnt[SEG_ROW0], rows = p.cnt[SEG_ROWS];
-  int* ent = a.hdr + PACK_HDR_WORDS + (size_t)s * PACK_SEG_WORDS;
+  int* ent = a.hdr + MSCNN_MULTI_PACK_WORDS * (size_t)(1 + s);
   if (threadIdx.x == 0) { ent[1] = rows; ent[2] = row0; ent[3] = 0; }
   if (p.cnt[SEG_BAD]) { if (threadIdx.x == 0) ent[0] = -1; return; }
-  const size_t slot = (size_t)a.num_classes * row0 + (size_t)c * rows;
-  det_scan_emit(p.mask, a.wpr, p.cnt[SEG_N], p.sbox, p.sprob, p.ssrc, a.dets + 5 * slot, a.ids + slot, ent, dyn_lds);
-}
-
-// ---- every (image, cascade output, class) segment in one pass (mscnn_detections_cascade_multi_fwd) ---------------------------------
-// Segment s = image s / K, output (s % K) / C, class slot s % C, K = O C (image-major, then output, then class).  Every cascade
-// output is a blob triple of its own (decoded boxes [R_all][5], probabilities [R_all][ncls_o], proposals [R_all][5], image index in
-// column 0 of the proposals -- DecodeBBox copies it, decode_bbox_layer.cpp:110); the triples travel as kernel arguments beside the
-// segment table.  A segment finds its rows in ITS output's proposals and runs the same three bodies with cascade = 1; its detections
-// go to pack rows [K row0 + (o C + c) rows, + rows): the multi pack with K in the role of num_classes.
-constexpr int kCascadeMaxOutputs = 4;
-constexpr int kCascadeSegsPerLaunch = 32;  // 32 x 32 bytes of segments + 4 x 32 bytes of triples + 0.1 KB: 1.3 KB of the 4 KB
-struct DetCascadeSeg { float ratio_h, ratio_w, org_h, org_w; int cls_id, pad; double nms_overlap; };
-struct DetCascadeOut { const float* boxes; const float* cls_prob; const float* props; int ncls, pad; };
-struct DetCascadeMultiArgs {
-  int R_all, num_outputs, num_classes, max_rows, wpr, cap, num_segs, s0;
-  float det_thr;
-  char* ws; size_t seg_stride_box, seg_stride_mask;                     // workspace: as DetMultiArgs (det_multi_ptrs)
-  int* hdr; double* dets; int* ids;                                     // pack
-  DetCascadeOut out[kCascadeMaxOutputs];
-  DetCascadeSeg seg[kCascadeSegsPerLaunch];
-};
-
-__global__ __launch_bounds__(kSortThreads) void det_cascade_multi_transform_sort_kernel(DetCascadeMultiArgs a) {
-  const int j = blockIdx.x, s = a.s0 + j;
-  const int K = a.num_outputs * a.num_classes;
-  const int img = s / K, o = (s % K) / a.num_classes;
-  const DetCascadeOut& t = a.out[o];
-  const DetMultiPtrs p = det_multi_ptrs(a, s);
-  __shared__ int s_range[2];
-  if (threadIdx.x < 2) s_range[threadIdx.x] = det_image_lower_bound(t.props, a.R_all, img + threadIdx.x, 5);
-  if (s == 0 && threadIdx.x == 0) {
-    a.hdr[0] = a.num_segs; a.hdr[1] = a.R_all; a.hdr[2] = a.cap; a.hdr[3] = 0;
-  }
-  __syncthreads();
-  const int row0 = s_range[0], rows = s_range[1] - s_range[0];
-  const bool bad = rows > a.max_rows;      // (as det_multi_transform_sort_kernel: nothing is run, the table says so)
-  if (threadIdx.x == 0) { p.cnt[SEG_ROW0] = row0; p.cnt[SEG_ROWS] = rows; p.cnt[SEG_BAD] = bad ? 1 : 0; }
-  if (bad) { if (threadIdx.x == 0) p.cnt[SEG_N] = 0; return; }
-  const DetCascadeSeg& g = a.seg[j];
-  DetArgs d;
-  d.bbox_pred = t.boxes + (size_t)row0 * 5; d.cls_pred = t.cls_prob + (size_t)row0 * t.ncls; d.props = t.props + (size_t)row0 * 5;
-  d.R = rows; d.ncls = t.ncls; d.cls_id = g.cls_id;
-  for (int k = 0; k < 4; ++k) { d.mean[k] = 0.f; d.stdv[k] = 1.f; }      // (not read by the cascade row transform)
-  d.proposal_thr = a.det_thr; d.ratio_h = g.ratio_h; d.ratio_w = g.ratio_w; d.org_h = g.org_h; d.org_w = g.org_w;
-  d.cascade = 1;
-  det_transform_sort(d, p.sbox, p.sprob, p.ssrc, p.tbox, p.tprob, p.cnt + SEG_N);
-}
-
-__global__ __launch_bounds__(256) void det_cascade_multi_mask_kernel(DetCascadeMultiArgs a) {
-  const int j = blockIdx.z, s = a.s0 + j;
-  const DetMultiPtrs p = det_multi_ptrs(a, s);
-  det_mask_block(p.sbox, p.cnt[SEG_N], a.seg[j].nms_overlap, p.mask, a.wpr, blockIdx.y, blockIdx.x);
-}
-
-__global__ __launch_bounds__(256) void det_cascade_multi_scan_emit_kernel(DetCascadeMultiArgs a) {
-  extern __shared__ __attribute__((aligned(16))) u64 dyn_lds[];
-  const int j = blockIdx.x, s = a.s0 + j;
-  const int K = a.num_outputs * a.num_classes;
-  const int k = s % K;                     // o C + c
-  const DetMultiPtrs p = det_multi_ptrs(a, s);
-  const int row0 = p.cnt[SEG_ROW0], rows = p.cnt[SEG_ROWS];
-  int* ent = a.hdr + PACK_HDR_WORDS + (size_t)s * PACK_SEG_WORDS;
-  if (threadIdx.x == 0) { ent[1] = rows; ent[2] = row0; ent[3] = 0; }
-  if (p.cnt[SEG_BAD]) { if (threadIdx.x == 0) ent[0] = -1; return; }
-  const size_t slot = (size_t)K * row0 + (size_t)k * rows;
+  const size_t slot = mscnn_multi_pack_slot(a.slots_per_image, row0, s % a.slots_per_image, rows);
   det_scan_emit(p.mask, a.wpr, p.cnt[SEG_N], p.sbox, p.sprob, p.ssrc, a.dets + 5 * slot, a.ids + slot, ent, dyn_lds);
 }
 
@@ -561,7 +500,7 @@ extern "C" int mscnn_detections_cascade_fwd(const mscnn_detections_desc* desc, f
                            workspace_bytes, stream);
 }
 
-// ---- all (image, class) segments in one pass -----------------------------------------------------------------------------------------
+// ---- all segments in one pass ----------------------------------------------------------------------------------------------------------
 static size_t det_multi_seg_box_bytes(int M) {
   const size_t m = (size_t)(M < 1 ? 1 : M);
   return 2 * align_up(m * sizeof(DetBox), 256) + align_up(m * sizeof(double), 256) + align_up(m * sizeof(int), 256) +
@@ -573,8 +512,7 @@ static size_t det_multi_seg_mask_bytes(int M) {
 }
 
 extern "C" size_t mscnn_detections_multi_pack_bytes(int num_segments, int cap) {
-  const size_t S = (size_t)(num_segments > 0 ? num_segments : 0), rows = (size_t)(cap > 0 ? cap : 1);
-  return (sizeof(int) * (PACK_HDR_WORDS + PACK_SEG_WORDS * S) + rows * (5 * sizeof(double) + sizeof(int)) + 15) / 16 * 16;
+  return mscnn_multi_pack_layout_of(num_segments, cap).total;
 }
 
 extern "C" size_t mscnn_detections_multi_workspace_bytes(int num_segments, int max_rows_per_image) {
@@ -582,6 +520,49 @@ extern "C" size_t mscnn_detections_multi_workspace_bytes(int num_segments, int m
   const int M = max_rows_per_image < 1 ? 1 : max_rows_per_image;
   return align_up((size_t)num_segments * SEG_WORDS * sizeof(int), 256) +
          (size_t)num_segments * (det_multi_seg_box_bytes(M) + det_multi_seg_mask_bytes(M));
+}
+extern "C" size_t mscnn_detections_cascade_multi_workspace_bytes(int num_segments, int max_rows_per_image) {
+  return mscnn_detections_multi_workspace_bytes(num_segments, max_rows_per_image);
+}
+
+// cascade: proposal_thr = det_thr (run_cascademscnn.m:115-117), mean 0 / std 1 (not read by the cascade row transform)
+static DetSeg det_seg_of(const mscnn_detections_desc& d, int cascade, float det_thr) {
+  DetSeg g;
+  for (int k = 0; k < 4; ++k) { g.mean[k] = cascade ? 0.f : d.bbox_mean[k]; g.stdv[k] = cascade ? 1.f : d.bbox_std[k]; }
+  g.proposal_thr = cascade ? det_thr : d.proposal_thr; g.cls_id = d.cls_id; g.nms_overlap = d.nms_overlap;
+  // MATLAB: single op double -> single (as detections_launch)
+  g.ratio_h = (float)d.ratio_h; g.ratio_w = (float)d.ratio_w; g.org_h = (float)d.org_h; g.org_w = (float)d.org_w;
+  return g;
+}
+
+// desc[num_images * num_sources * C] (validated by the caller, as the workspace is): carve the pack, three launches per 32 segments
+static int det_seg_launch(const DetSource* src, int num_sources, const mscnn_detections_desc* desc, float det_thr, int num_images, int C,
+                          int R_all, int M, void* pack_dev, int cap, void* workspace, void* stream) {
+  hipStream_t st = as_stream(stream);
+  const int S = num_images * num_sources * C;
+  DetSegArgs a = {};
+  a.R_all = R_all; a.slots_per_image = num_sources * C; a.classes_per_source = C; a.max_rows = M; a.wpr = (M + 63) / 64; a.cap = cap;
+  a.num_segs = S;
+  a.ws = static_cast<char*>(workspace);
+  a.seg_stride_box = det_multi_seg_box_bytes(M); a.seg_stride_mask = det_multi_seg_mask_bytes(M);
+  for (int o = 0; o < num_sources; ++o) a.src[o] = src[o];
+  const mscnn_multi_pack_layout L = mscnn_multi_pack_layout_of(S, cap);
+  char* pk = static_cast<char*>(pack_dev);
+  a.hdr = reinterpret_cast<int*>(pk);
+  a.dets = reinterpret_cast<double*>(pk + L.dets);
+  a.ids = reinterpret_cast<int*>(pk + L.ids);
+  for (int s0 = 0; s0 < S; s0 += kSegsPerLaunch) {
+    const int ns = S - s0 < kSegsPerLaunch ? S - s0 : kSegsPerLaunch;
+    a.s0 = s0;
+    for (int j = 0; j < ns; ++j) a.seg[j] = det_seg_of(desc[s0 + j], src[0].cascade, det_thr);
+    det_seg_transform_sort_kernel<<<ns, kSortThreads, 0, st>>>(a);
+    MSCNN_POST_LAUNCH();
+    det_seg_mask_kernel<<<dim3(a.wpr, a.wpr, ns), 256, 0, st>>>(a);
+    MSCNN_POST_LAUNCH();
+    det_seg_scan_emit_kernel<<<ns, 256, (size_t)2 * 64 * a.wpr * sizeof(u64), st>>>(a);
+    MSCNN_POST_LAUNCH();
+  }
+  return MSCNN_OK;
 }
 
 extern "C" int mscnn_detections_multi_fwd(const mscnn_detections_desc* desc, int num_images, int num_classes, const float* bbox_pred,
@@ -604,42 +585,8 @@ extern "C" int mscnn_detections_multi_fwd(const mscnn_detections_desc* desc, int
     set_error("detections_multi: workspace %zu < %zu", workspace_bytes, need);
     return MSCNN_ERR_WORKSPACE;
   }
-  hipStream_t st = as_stream(stream);
-  const int M = max_rows_per_image;
-  DetMultiArgs a;
-  a.bbox_pred = bbox_pred; a.cls_pred = cls_pred; a.props = props;
-  a.R_all = R_all; a.ncls = ncls; a.num_classes = num_classes; a.max_rows = M; a.wpr = (M + 63) / 64; a.cap = cap; a.num_segs = S;
-  a.ws = static_cast<char*>(workspace);
-  a.seg_stride_box = det_multi_seg_box_bytes(M); a.seg_stride_mask = det_multi_seg_mask_bytes(M);
-  char* pk = static_cast<char*>(pack_dev);
-  a.hdr = reinterpret_cast<int*>(pk);
-  const size_t rows = (size_t)(cap > 0 ? cap : 1), table = sizeof(int) * (PACK_HDR_WORDS + PACK_SEG_WORDS * (size_t)S);
-  a.dets = reinterpret_cast<double*>(pk + table);
-  a.ids = reinterpret_cast<int*>(pk + table + sizeof(double) * 5 * rows);
-  for (int s0 = 0; s0 < S; s0 += kSegsPerLaunch) {
-    const int ns = S - s0 < kSegsPerLaunch ? S - s0 : kSegsPerLaunch;
-    a.s0 = s0;
-    for (int j = 0; j < ns; ++j) {
-      const mscnn_detections_desc& d = desc[s0 + j];
-      DetSeg& g = a.seg[j];
-      for (int k = 0; k < 4; ++k) { g.mean[k] = d.bbox_mean[k]; g.stdv[k] = d.bbox_std[k]; }
-      g.proposal_thr = d.proposal_thr; g.cls_id = d.cls_id; g.nms_overlap = d.nms_overlap;
-      // MATLAB: single op double -> single (as detections_launch)
-      g.ratio_h = (float)d.ratio_h; g.ratio_w = (float)d.ratio_w; g.org_h = (float)d.org_h; g.org_w = (float)d.org_w;
-    }
-    det_multi_transform_sort_kernel<<<ns, kSortThreads, 0, st>>>(a);
-    MSCNN_POST_LAUNCH();
-    det_multi_mask_kernel<<<dim3(a.wpr, a.wpr, ns), 256, 0, st>>>(a);
-    MSCNN_POST_LAUNCH();
-    det_multi_scan_emit_kernel<<<ns, 256, (size_t)2 * 64 * a.wpr * sizeof(u64), st>>>(a);
-    MSCNN_POST_LAUNCH();
-  }
-  return MSCNN_OK;
-}
-
-// ---- all (image, cascade output, class) segments in one pass ---------------------------------------------------------------------------
-extern "C" size_t mscnn_detections_cascade_multi_workspace_bytes(int num_segments, int max_rows_per_image) {
-  return mscnn_detections_multi_workspace_bytes(num_segments, max_rows_per_image);
+  const DetSource src = {bbox_pred, cls_pred, props, ncls, 0};
+  return det_seg_launch(&src, 1, desc, 0.f, num_images, num_classes, R_all, max_rows_per_image, pack_dev, cap, workspace, stream);
 }
 
 extern "C" int mscnn_detections_cascade_multi_fwd(const mscnn_detections_desc* desc, float det_thr, int num_images, int num_outputs,
@@ -674,38 +621,7 @@ extern "C" int mscnn_detections_cascade_multi_fwd(const mscnn_detections_desc* d
     set_error("detections_cascade_multi: workspace %zu < %zu", workspace_bytes, need);
     return MSCNN_ERR_WORKSPACE;
   }
-  hipStream_t st = as_stream(stream);
-  const int M = max_rows_per_image;
-  DetCascadeMultiArgs a = {};
-  a.R_all = R_all; a.num_outputs = num_outputs; a.num_classes = num_classes; a.max_rows = M; a.wpr = (M + 63) / 64; a.cap = cap;
-  a.num_segs = S; a.det_thr = det_thr;
-  a.ws = static_cast<char*>(workspace);
-  a.seg_stride_box = det_multi_seg_box_bytes(M); a.seg_stride_mask = det_multi_seg_mask_bytes(M);
-  for (int o = 0; o < num_outputs; ++o) {
-    a.out[o].boxes = outputs[o].boxes; a.out[o].cls_prob = outputs[o].cls_prob; a.out[o].props = outputs[o].props;
-    a.out[o].ncls = outputs[o].ncls;
-  }
-  char* pk = static_cast<char*>(pack_dev);
-  a.hdr = reinterpret_cast<int*>(pk);
-  const size_t rows = (size_t)(cap > 0 ? cap : 1), table = sizeof(int) * (PACK_HDR_WORDS + PACK_SEG_WORDS * (size_t)S);
-  a.dets = reinterpret_cast<double*>(pk + table);
-  a.ids = reinterpret_cast<int*>(pk + table + sizeof(double) * 5 * rows);
-  for (int s0 = 0; s0 < S; s0 += kCascadeSegsPerLaunch) {
-    const int ns = S - s0 < kCascadeSegsPerLaunch ? S - s0 : kCascadeSegsPerLaunch;
-    a.s0 = s0;
-    for (int j = 0; j < ns; ++j) {
-      const mscnn_detections_desc& d = desc[s0 + j];
-      DetCascadeSeg& g = a.seg[j];
-      g.cls_id = d.cls_id; g.nms_overlap = d.nms_overlap;
-      // MATLAB: single op double -> single (as detections_launch)
-      g.ratio_h = (float)d.ratio_h; g.ratio_w = (float)d.ratio_w; g.org_h = (float)d.org_h; g.org_w = (float)d.org_w;
-    }
-    det_cascade_multi_transform_sort_kernel<<<ns, kSortThreads, 0, st>>>(a);
-    MSCNN_POST_LAUNCH();
-    det_cascade_multi_mask_kernel<<<dim3(a.wpr, a.wpr, ns), 256, 0, st>>>(a);
-    MSCNN_POST_LAUNCH();
-    det_cascade_multi_scan_emit_kernel<<<ns, 256, (size_t)2 * 64 * a.wpr * sizeof(u64), st>>>(a);
-    MSCNN_POST_LAUNCH();
-  }
-  return MSCNN_OK;
+  DetSource src[kCascadeMaxOutputs];
+  for (int o = 0; o < num_outputs; ++o) src[o] = DetSource{outputs[o].boxes, outputs[o].cls_prob, outputs[o].props, outputs[o].ncls, 1};
+  return det_seg_launch(src, num_outputs, desc, det_thr, num_images, num_classes, R_all, max_rows_per_image, pack_dev, cap, workspace, stream);
 }

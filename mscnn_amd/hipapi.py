@@ -570,14 +570,27 @@ class BoxOutput:
         return self.rois[:R], self.props[:R], self.aids[:R], nreal
 
 
+_DESC_DEFAULTS = dict(bbox_mean=(0, 0, 0, 0), bbox_std=(0.1, 0.1, 0.2, 0.2), proposal_thr=-10.0, ratios=(1.0, 1.0), org_hw=(375, 1242),
+                      nms_overlap=0.5)
+
+
+def _fill_desc(d, ncls, kw):
+    """mscnn_detections_desc d from the keyword arguments of detections() (missing ones: its defaults)."""
+    kw = dict(_DESC_DEFAULTS, **kw)
+    d.ncls = ncls; d.cls_id = kw["cls_id"]
+    for k in range(4):
+        d.bbox_mean[k] = kw["bbox_mean"][k]; d.bbox_std[k] = kw["bbox_std"][k]
+    d.proposal_thr = kw["proposal_thr"]
+    d.ratio_h, d.ratio_w = kw["ratios"]
+    d.org_h, d.org_w = kw["org_hw"]
+    d.nms_overlap = kw["nms_overlap"]
+
+
 def detections_cascade(boxes, cls_prob, props, cls_id, det_thr=0.0, ratios=(1.0, 1.0), org_hw=(375, 1242), nms_overlap=0.5):
     """Final stage of the cascade drivers (run_cascademscnn.m:84-117) for one cascade stage's blobs."""
     R = props.shape[0]
-    d = DetectionsDesc()
-    d.ncls = cls_prob.shape[1]; d.cls_id = cls_id
-    d.ratio_h, d.ratio_w = ratios
-    d.org_h, d.org_w = org_hw
-    d.nms_overlap = nms_overlap
+    d = DetectionsDesc()      # (of the desc, the cascade stage reads ncls, cls_id, ratio_*, org_* and nms_overlap)
+    _fill_desc(d, cls_prob.shape[1], dict(cls_id=cls_id, ratios=ratios, org_hw=org_hw, nms_overlap=nms_overlap))
     dev = props.device
     dets = torch.zeros((max(R, 1), 5), dtype=torch.float64, device=dev)
     ids = torch.zeros(max(R, 1), dtype=torch.int32, device=dev)
@@ -654,13 +667,8 @@ def detections(bbox_pred, cls_pred, props, cls_id, bbox_mean=(0, 0, 0, 0), bbox_
                proposal_thr=-10.0, ratios=(1.0, 1.0), org_hw=(375, 1242), nms_overlap=0.5):
     R = props.shape[0]
     d = DetectionsDesc()
-    d.ncls = cls_pred.shape[1]; d.cls_id = cls_id
-    for k in range(4):
-        d.bbox_mean[k] = bbox_mean[k]; d.bbox_std[k] = bbox_std[k]
-    d.proposal_thr = proposal_thr
-    d.ratio_h, d.ratio_w = ratios
-    d.org_h, d.org_w = org_hw
-    d.nms_overlap = nms_overlap
+    _fill_desc(d, cls_pred.shape[1], dict(cls_id=cls_id, bbox_mean=bbox_mean, bbox_std=bbox_std, proposal_thr=proposal_thr, ratios=ratios,
+                                          org_hw=org_hw, nms_overlap=nms_overlap))
     dev = props.device
     dets = torch.zeros((max(R, 1), 5), dtype=torch.float64, device=dev)
     ids = torch.zeros(max(R, 1), dtype=torch.int32, device=dev)
@@ -671,6 +679,24 @@ def detections(bbox_pred, cls_pred, props, cls_id, bbox_mean=(0, 0, 0, 0), bbox_
                                       _dev(count), _dev(ws), wb, _stream()))
     D = int(count.item())
     return dets[:D], ids[:D]
+
+
+def _read_multi_pack(pack, S, K, R, cap, name):
+    """The multi pack (mscnn_hip.h) read back: [(dets[D,5], ids relative to row0, row0, rows)] per segment, (None, None, row0, rows)
+    for a segment whose image has more rows than max_rows_per_image.  K: slots per image."""
+    h = pack.cpu().numpy()
+    table = 16 * (S + 1)
+    hdr = h[:table].view(np.int32).reshape(S + 1, 4)
+    if list(hdr[0]) != [S, R, cap, 0]:
+        raise MscnnError(f"{name}: pack header {hdr[0].tolist()}")
+    dets = h[table:table + 40 * max(cap, 1)].view(np.float64).reshape(-1, 5)
+    ids = h[table + 40 * max(cap, 1):table + 44 * max(cap, 1)].view(np.int32)
+    out = []
+    for s in range(S):
+        cnt, rows, row0, _ = (int(v) for v in hdr[1 + s])
+        slot = K * row0 + (s % K) * rows
+        out.append((dets[slot:slot + cnt].copy(), ids[slot:slot + cnt].copy(), row0, rows) if cnt >= 0 else (None, None, row0, rows))
+    return out
 
 
 def detections_multi(bbox_pred, cls_pred, props, num_images, segments, max_rows_per_image=None):
@@ -684,16 +710,7 @@ def detections_multi(bbox_pred, cls_pred, props, num_images, segments, max_rows_
         raise MscnnError(f"detections_multi: {S} segments for {num_images} images")
     descs = (DetectionsDesc * S)()
     for s, kw in enumerate(segments):
-        kw = dict(dict(bbox_mean=(0, 0, 0, 0), bbox_std=(0.1, 0.1, 0.2, 0.2), proposal_thr=-10.0, ratios=(1.0, 1.0), org_hw=(375, 1242),
-                       nms_overlap=0.5), **kw)
-        d = descs[s]
-        d.ncls = cls_pred.shape[1]; d.cls_id = kw["cls_id"]
-        for k in range(4):
-            d.bbox_mean[k] = kw["bbox_mean"][k]; d.bbox_std[k] = kw["bbox_std"][k]
-        d.proposal_thr = kw["proposal_thr"]
-        d.ratio_h, d.ratio_w = kw["ratios"]
-        d.org_h, d.org_w = kw["org_hw"]
-        d.nms_overlap = kw["nms_overlap"]
+        _fill_desc(descs[s], cls_pred.shape[1], kw)
     M = R if max_rows_per_image is None else max_rows_per_image
     cap = Cn * R
     dev = props.device
@@ -702,19 +719,7 @@ def detections_multi(bbox_pred, cls_pred, props, num_images, segments, max_rows_
     ws = torch.empty(max(wb, 1), dtype=torch.uint8, device=dev)
     _check(lib().mscnn_detections_multi_fwd(descs, num_images, Cn, _dev(bbox_pred), _dev(cls_pred), _dev(props), R, M, _dev(pack), cap,
                                             _dev(ws), C.c_size_t(wb), _stream()))
-    h = pack.cpu().numpy()
-    hdr = h[:16 * (S + 1)].view(np.int32).reshape(S + 1, 4)
-    if list(hdr[0]) != [S, R, cap, 0]:
-        raise MscnnError(f"detections_multi: pack header {hdr[0].tolist()}")
-    table = 16 * (S + 1)
-    dets = h[table:table + 40 * max(cap, 1)].view(np.float64).reshape(-1, 5)
-    ids = h[table + 40 * max(cap, 1):table + 44 * max(cap, 1)].view(np.int32)
-    out = []
-    for s in range(S):
-        cnt, rows, row0, _ = (int(v) for v in hdr[1 + s])
-        slot = Cn * row0 + (s % Cn) * rows
-        out.append((dets[slot:slot + max(cnt, 0)].copy(), ids[slot:slot + max(cnt, 0)].copy(), row0, rows) if cnt >= 0 else (None, None, row0, rows))
-    return out
+    return _read_multi_pack(pack, S, Cn, R, cap, "detections_multi")
 
 
 class CascadeOutput(C.Structure):
@@ -741,13 +746,8 @@ def detections_cascade_multi(outputs, num_images, segments, det_thr=0.0, max_row
             raise MscnnError(f"detections_cascade_multi: output {o}: shapes {tuple(boxes.shape)} {tuple(cls_prob.shape)} {tuple(props.shape)}")
         outs[o].boxes, outs[o].cls_prob, outs[o].props, outs[o].ncls = _dev(boxes).value, _dev(cls_prob).value, _dev(props).value, cls_prob.shape[1]
     descs = (DetectionsDesc * S)()
-    for s, kw in enumerate(segments):
-        kw = dict(dict(ratios=(1.0, 1.0), org_hw=(375, 1242), nms_overlap=0.5), **kw)
-        d = descs[s]
-        d.ncls = outs[(s % K) // Cn].ncls; d.cls_id = kw["cls_id"]
-        d.ratio_h, d.ratio_w = kw["ratios"]
-        d.org_h, d.org_w = kw["org_hw"]
-        d.nms_overlap = kw["nms_overlap"]
+    for s, kw in enumerate(segments):      # (of the desc, the cascade stage reads ncls, cls_id, ratio_*, org_* and nms_overlap)
+        _fill_desc(descs[s], outs[(s % K) // Cn].ncls, kw)
     M = R if max_rows_per_image is None else max_rows_per_image
     cap = K * R
     dev = outputs[0][2].device
@@ -756,19 +756,7 @@ def detections_cascade_multi(outputs, num_images, segments, det_thr=0.0, max_row
     ws = torch.empty(max(wb, 1), dtype=torch.uint8, device=dev)
     _check(lib().mscnn_detections_cascade_multi_fwd(descs, C.c_float(det_thr), num_images, O, Cn, outs, R, M, _dev(pack), cap, _dev(ws),
                                                     C.c_size_t(wb), _stream()))
-    h = pack.cpu().numpy()
-    hdr = h[:16 * (S + 1)].view(np.int32).reshape(S + 1, 4)
-    if list(hdr[0]) != [S, R, cap, 0]:
-        raise MscnnError(f"detections_cascade_multi: pack header {hdr[0].tolist()}")
-    table = 16 * (S + 1)
-    dets = h[table:table + 40 * max(cap, 1)].view(np.float64).reshape(-1, 5)
-    ids = h[table + 40 * max(cap, 1):table + 44 * max(cap, 1)].view(np.int32)
-    out = []
-    for s in range(S):
-        cnt, rows, row0, _ = (int(v) for v in hdr[1 + s])
-        slot = K * row0 + (s % K) * rows
-        out.append((dets[slot:slot + cnt].copy(), ids[slot:slot + cnt].copy(), row0, rows) if cnt >= 0 else (None, None, row0, rows))
-    return out
+    return _read_multi_pack(pack, S, K, R, cap, "detections_cascade_multi")
 
 
 # ---- health of the plane-GEMM kernel's stream-K hand-off (mscnn_hip.h) ----

@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -460,25 +461,30 @@ static void detect_into_pack(mscnn_net* n, const mscnn_detect_params* p, int cap
   if (R_out) *R_out = R;
 }
 
-// Row range of image `image` in the ROI blobs: BoxOutput emits image after image (box_output_layer.cpp:107), column 0 of every row
-// is its image (:156).  One small D2H read of the proposals blob per forward (cached until the next forward).
+// End row of every image in ROI rows grouped by image: BoxOutput emits image after image (box_output_layer.cpp:107), column 0 of every
+// row is its image (:156; DecodeBBox copies it).  Image i owns rows [end[i - 1], end[i]).
+static std::vector<int> image_ranges(const float* host_props, int R, int stride, int num_images, const std::string& what) {
+  std::vector<int> end(num_images, 0);
+  int prev = 0;
+  for (int r = 0; r < R; ++r) {
+    const int img = (int)host_props[(size_t)r * stride];
+    CHECK(img >= prev && img < num_images) << what << " are not grouped by image";
+    // (the dummy row [0 0 0 0 0 0] the layer emits when nothing survives in the whole batch carries score 0 and image 0)
+    prev = img;
+    end[img] = r + 1;
+  }
+  for (int i = 1; i < num_images; ++i) if (end[i] < end[i - 1]) end[i] = end[i - 1];
+  return end;
+}
+
+// Row range of image `image` in the ROI blobs.  One small D2H read of the proposals blob per forward (cached until the next forward).
 static void image_rows(mscnn_net* n, int image, int* row0, int* rows) {
   CHECK(n->net->has_blob("proposals_score")) << "net has no proposals_score output";
   auto props = n->net->blob_by_name("proposals_score");
-  const int R = props->num(), num = n->net->num_inputs() > 0 ? n->net->input_blobs()[0]->num() : 1;
+  const int num = n->net->num_inputs() > 0 ? n->net->input_blobs()[0]->num() : 1;
   CHECK(image >= 0 && image < num) << "image " << image << " of a batch of " << num;
   if (n->rows_forward != n->net->forward_count() || (int)n->row_end.size() != num) {
-    const float* h = props->cpu_data();      // (synchronises the stream)
-    n->row_end.assign(num, 0);
-    int prev = 0;
-    for (int r = 0; r < R; ++r) {
-      const int img = (int)h[(size_t)r * 6];
-      CHECK(img >= prev && img < num) << "proposals are not grouped by image";
-      // (the dummy row [0 0 0 0 0 0] the layer emits when nothing survives in the whole batch carries score 0 and image 0)
-      prev = img;
-      n->row_end[img] = r + 1;
-    }
-    for (int i = 1; i < num; ++i) if (n->row_end[i] < n->row_end[i - 1]) n->row_end[i] = n->row_end[i - 1];
+    n->row_end = image_ranges(props->cpu_data(), props->num(), 6, num, "proposals");      // (cpu_data synchronises the stream)
     n->rows_forward = n->net->forward_count();
   }
   *row0 = image > 0 ? n->row_end[image - 1] : 0;
@@ -649,9 +655,74 @@ static int per_image_row_bound(mscnn_net* n, int num_images, int R_all) {
   return R_all;
 }
 
-// The multi pack of the last forward (mscnn_hip.h: mscnn_detections_multi_fwd) with cap rows, at pack_at (device-addressable) or in
-// the net's device pack.  Returns false when it went to the device pack instead: a per-image bound over 4032 rows (max_nms_num 0)
-// runs the existing per-segment path -- the tiled kernels of nms_large.h -- image_rows' host read included, into the same layout.
+// One source of segments: the plain stage's bbox_pred / cls_pred / proposals_score, or one cascade output's blob triple.
+struct SegSource { const Blob<float>* boxes; const Blob<float>* cls; const Blob<float>* props; int ncls; bool cascade; };
+
+// The multi pack of the last forward (mscnn_hip.h: mscnn_detections_multi_fwd) with cap rows for desc[num_images x sources x C], at
+// pack_at (device-addressable) or in the net's device pack.  Returns false when it went to the device pack instead: a per-image bound
+// over 4032 rows (max_nms_num 0) runs the per-call op -- the tiled kernels of nms_large.h -- segment after segment on row ranges read
+// on the host (proposals_score's through image_rows' cache, one read per cascade output), into the same layout.
+static bool segments_into_pack(mscnn_net* n, const std::vector<SegSource>& src, const std::vector<mscnn_detections_desc>& desc,
+                               int num_images, int C, float det_thr, int cap, char* pack_at, char** pack_out) {
+  const int O = (int)src.size(), K = O * C, S = num_images * K, R_all = src[0].props->num();
+  hipStream_t st = (hipStream_t)Caffe::stream();
+  const mscnn_multi_pack_layout L = mscnn_multi_pack_layout_of(S, cap);
+  const int bound = n->net->has_blob("proposals_score") ? per_image_row_bound(n, num_images, R_all) : R_all;
+  if (bound <= 4032) {
+    const size_t wb = mscnn_detections_multi_workspace_bytes(S, bound);
+    void* ws = n->det_ws.Reserve(wb);
+    char* pack = pack_at ? pack_at : static_cast<char*>(n->det_pack.Reserve(L.total));
+    if (src[0].cascade) {
+      std::vector<mscnn_cascade_output> outs(O);
+      for (int o = 0; o < O; ++o)
+        outs[o] = mscnn_cascade_output{src[o].boxes->gpu_data(), src[o].cls->gpu_data(), src[o].props->gpu_data(), src[o].ncls};
+      MSCNN_CHECK(mscnn_detections_cascade_multi_fwd(desc.data(), det_thr, num_images, O, C, outs.data(), R_all, bound, pack, cap, ws, wb, st));
+    } else {
+      MSCNN_CHECK(mscnn_detections_multi_fwd(desc.data(), num_images, C, src[0].boxes->gpu_data(), src[0].cls->gpu_data(),
+                                             src[0].props->gpu_data(), R_all, bound, pack, cap, ws, wb, st));
+    }
+    *pack_out = pack;
+    return pack == pack_at;
+  }
+  std::vector<std::vector<int> > end(O);
+  int max_rows = 0;
+  for (int o = 0; o < O; ++o) {
+    if (src[o].cascade) {
+      end[o] = image_ranges(src[o].props->cpu_data(), R_all, 5, num_images, "the proposals of cascade output " + std::to_string(o));
+    } else {
+      int r0 = 0, nr = 0;
+      image_rows(n, 0, &r0, &nr);
+      end[o] = n->row_end;
+    }
+    for (int i = 0; i < num_images; ++i) max_rows = std::max(max_rows, end[o][i] - (i > 0 ? end[o][i - 1] : 0));
+  }
+  char* pack = static_cast<char*>(n->det_pack.Reserve(L.total));
+  int* hdr = reinterpret_cast<int*>(pack);
+  double* dets = reinterpret_cast<double*>(pack + L.dets);
+  int* ids = reinterpret_cast<int*>(pack + L.ids);
+  const size_t wb = mscnn_detections_workspace_bytes(max_rows);
+  void* ws = n->det_ws.Reserve(wb);
+  const int words[4] = {S, R_all, cap, 0};
+  MSCNN_CHECK(mscnn_store_words_i32(hdr, words, 4, st));
+  for (int s = 0; s < S; ++s) {
+    const int i = s / K, k = s % K, o = k / C;
+    const SegSource& t = src[o];
+    const int r0 = i > 0 ? end[o][i - 1] : 0, nr = end[o][i] - r0;
+    const size_t slot = mscnn_multi_pack_slot(K, r0, k, nr);
+    int* ent = hdr + MSCNN_MULTI_PACK_WORDS * (size_t)(1 + s);
+    const int e[3] = {nr, r0, 0};
+    MSCNN_CHECK(mscnn_store_words_i32(ent + 1, e, 3, st));
+    const float* boxes = t.boxes->gpu_data() + (size_t)r0 * (t.cascade ? 5 : 4 * t.ncls);
+    const float* cls = t.cls->gpu_data() + (size_t)r0 * t.ncls;
+    const float* props = t.props->gpu_data() + (size_t)r0 * (t.cascade ? 5 : 6);
+    if (t.cascade) MSCNN_CHECK(mscnn_detections_cascade_fwd(&desc[s], det_thr, boxes, cls, props, nr, dets + 5 * slot, ids + slot, ent, ws, wb, st));
+    else MSCNN_CHECK(mscnn_detections_fwd(&desc[s], boxes, cls, props, nr, dets + 5 * slot, ids + slot, ent, ws, wb, st));
+  }
+  *pack_out = pack;
+  return false;
+}
+
+// The plain one-pass stage: everything that can be refused is refused here, then the one source and the descs go to segments_into_pack.
 static bool detect_multi_into_pack(mscnn_net* n, const mscnn_detect_params* p, int num_images, int num_classes, int cap, char* pack_at,
                                    char** pack_out) {
   CHECK(p != nullptr);
@@ -682,44 +753,39 @@ static bool detect_multi_into_pack(mscnn_net* n, const mscnn_detect_params* p, i
     d.proposal_thr = p[s].proposal_thr;
     d.ratio_h = p[s].ratio_h; d.ratio_w = p[s].ratio_w; d.org_h = p[s].org_h; d.org_w = p[s].org_w; d.nms_overlap = p[s].nms_overlap;
   }
+  return segments_into_pack(n, {SegSource{bbox.get(), cls.get(), props.get(), ncls, false}}, desc, num_images, num_classes, 0.f, cap,
+                            pack_at, pack_out);
+}
+
+// The blocking form of both one-pass calls.  As mscnn_net_detect: the kernels write the pack straight into host-coherent pinned memory,
+// one stream synchronisation, no copy; the per-segment fallback leaves it in the device pack and copies it.  rows_all: validates and
+// returns R_all (the pack gets K R_all rows); into_pack(pack rows, pack_at, &pack): segments_into_pack's result.
+static void detect_segments_blocking(mscnn_net* n, const char* name, int num_images, int K, const std::function<int()>& rows_all,
+                                     const std::function<bool(int, char*, char**)>& into_pack, double* dets_host, int* ids_host, int cap,
+                                     int* seg_dets, int* image_rois) {
   hipStream_t st = (hipStream_t)Caffe::stream();
-  const size_t total = mscnn_detections_multi_pack_bytes(S, cap);
-  const int bound = per_image_row_bound(n, num_images, R_all);
-  if (bound <= 4032) {
-    const size_t wb = mscnn_detections_multi_workspace_bytes(S, bound);
-    void* ws = n->det_ws.Reserve(wb);
-    char* pack = pack_at ? pack_at : static_cast<char*>(n->det_pack.Reserve(total));
-    MSCNN_CHECK(mscnn_detections_multi_fwd(desc.data(), num_images, num_classes, bbox->gpu_data(), cls->gpu_data(), props->gpu_data(),
-                                           R_all, bound, pack, cap, ws, wb, st));
-    *pack_out = pack;
-    return pack == pack_at;
-  }
-  char* pack = static_cast<char*>(n->det_pack.Reserve(total));
-  int* hdr = reinterpret_cast<int*>(pack);
-  const size_t rows_cap = (size_t)(cap > 0 ? cap : 1), table = sizeof(int) * (4 + 4 * (size_t)S);
-  double* dets = reinterpret_cast<double*>(pack + table);
-  int* ids = reinterpret_cast<int*>(pack + table + sizeof(double) * 5 * rows_cap);
-  std::vector<int> row0(num_images), rows(num_images);
-  int max_rows = 0;
-  for (int i = 0; i < num_images; ++i) {
-    image_rows(n, i, &row0[i], &rows[i]);
-    max_rows = std::max(max_rows, rows[i]);
-  }
-  const size_t wb = mscnn_detections_workspace_bytes(max_rows);
-  void* ws = n->det_ws.Reserve(wb);
-  const int words[4] = {S, R_all, cap, 0};
-  MSCNN_CHECK(mscnn_store_words_i32(hdr, words, 4, st));
+  const int S = num_images * K;
+  int pcap = 0;
+  auto run = [&]() {
+    pcap = K * rows_all();
+    const size_t total = mscnn_multi_pack_layout_of(S, pcap).total;
+    ensure_det_host(n, total);
+    *static_cast<volatile int*>(n->det_host) = -1;      // the header's first word (S): the kernels must have written it
+    char* pack = nullptr;
+    if (!into_pack(pcap, static_cast<char*>(n->det_host_dev), &pack))
+      HIP_CHECK(hipMemcpyAsync(n->det_host, pack, total, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+  };
+  run();
+  if (n->net->HandoffRecover()) run();      // (as mscnn_net_detect: the frame has been run again on whole tiles)
+  const int* hdr = static_cast<const int*>(n->det_host);
+  CHECK_GE(hdr[0], 0) << name << ": the pack header was not written (" << S << " segments, " << pcap << " pack rows)";
   for (int s = 0; s < S; ++s) {
-    const int i = s / num_classes, c = s % num_classes;
-    const size_t slot = (size_t)num_classes * row0[i] + (size_t)c * rows[i];
-    int* ent = hdr + 4 + 4 * (size_t)s;
-    const int e[3] = {rows[i], row0[i], 0};
-    MSCNN_CHECK(mscnn_store_words_i32(ent + 1, e, 3, st));
-    MSCNN_CHECK(mscnn_detections_fwd(&desc[s], bbox->gpu_data() + (size_t)row0[i] * 4 * ncls, cls->gpu_data() + (size_t)row0[i] * ncls,
-                                     props->gpu_data() + (size_t)row0[i] * 6, rows[i], dets + 5 * slot, ids + slot, ent, ws, wb, st));
+    const int count = hdr[MSCNN_MULTI_PACK_WORDS * (size_t)(1 + s)];
+    CHECK_GE(count, -1) << name << ": segment " << s << " has count " << count;
   }
-  *pack_out = pack;
-  return false;
+  const int rc = mscnn_net_unpack_detections_multi(n->det_host, num_images, K, pcap, dets_host, ids_host, cap, seg_dets, image_rois);
+  CHECK_EQ(rc, 0) << g_err;
 }
 
 size_t mscnn_net_detect_multi_pack_bytes(int num_images, int num_classes, int cap) {
@@ -751,25 +817,25 @@ int mscnn_net_unpack_detections_multi(const void* pack_host, int num_images, int
         << "corrupt detection pack header: " << R_all << " ROIs, capacity " << cap;
     long D = 0;
     for (int s = 0; s < S; ++s) {
-      const int* e = hdr + 4 + 4 * (size_t)s;
+      const int* e = hdr + MSCNN_MULTI_PACK_WORDS * (size_t)(1 + s);
       const int i = s / num_classes;
       CHECK(e[0] != -1) << "image " << i << " has " << e[1] << " ROIs, more than the per-image row bound the stage was sized by";
       CHECK(e[0] >= 0 && e[0] <= e[1] && e[2] >= 0 && (long)e[2] + e[1] <= R_all && e[3] == 0)
           << "corrupt detection pack: segment " << s << " has " << e[0] << " detections, rows [" << e[2] << ", +" << e[1] << ") of " << R_all;
-      const int* e0 = hdr + 4 + 4 * (size_t)(i * num_classes);
+      const int* e0 = hdr + MSCNN_MULTI_PACK_WORDS * (size_t)(1 + i * num_classes);
       CHECK(e[1] == e0[1] && e[2] == e0[2]) << "corrupt detection pack: the segments of image " << i << " disagree on its rows";
       D += e[0];
     }
     CHECK_LE(D, (long)out_cap) << "detections buffer holds " << out_cap << " rows, the " << S << " segments have " << D;
     CHECK(D == 0 || dets_host) << "unpack_detections_multi: null dets buffer";
-    const size_t rows_cap = (size_t)(cap > 0 ? cap : 1), table = sizeof(int) * (4 + 4 * (size_t)S);
-    const double* pd = reinterpret_cast<const double*>(hp + table);
-    const int* pi = reinterpret_cast<const int*>(hp + table + sizeof(double) * 5 * rows_cap);
+    const mscnn_multi_pack_layout L = mscnn_multi_pack_layout_of(S, cap);
+    const double* pd = reinterpret_cast<const double*>(hp + L.dets);
+    const int* pi = reinterpret_cast<const int*>(hp + L.ids);
     size_t o = 0;
     for (int s = 0; s < S; ++s) {
-      const int* e = hdr + 4 + 4 * (size_t)s;
+      const int* e = hdr + MSCNN_MULTI_PACK_WORDS * (size_t)(1 + s);
       const int c = s % num_classes, cnt = e[0], rows = e[1], row0 = e[2];
-      const size_t slot = (size_t)num_classes * row0 + (size_t)c * rows;
+      const size_t slot = mscnn_multi_pack_slot(num_classes, row0, c, rows);
       if (cnt > 0) std::memcpy(dets_host + 5 * o, pd + 5 * slot, sizeof(double) * 5 * cnt);
       if (cnt > 0 && ids_host)
         for (int k = 0; k < cnt; ++k) ids_host[o + k] = pi[slot + k] + row0;      // rows of the net's ROI blobs, as detect_image
@@ -785,25 +851,14 @@ int mscnn_net_detect_multi(mscnn_net* n, const mscnn_detect_params* p, int num_i
   return guarded([&] {
     CHECK(p && seg_dets) << "detect_multi: null pointer";
     CHECK(num_images >= 1 && num_classes >= 1) << num_images << " images x " << num_classes << " classes";
-    // as mscnn_net_detect: the kernels write the pack straight into host-coherent pinned memory, one stream synchronisation, no copy;
-    // the per-segment fallback (a per-image bound over 4032 rows) leaves it in the device pack and copies it
-    hipStream_t st = (hipStream_t)Caffe::stream();
-    int pcap = 0;
-    auto run = [&]() {
-      CHECK(n->net->has_blob("proposals_score")) << "net has no proposals_score output";
-      pcap = num_classes * n->net->blob_by_name("proposals_score")->num();
-      const size_t total = mscnn_detections_multi_pack_bytes(num_images * num_classes, pcap);
-      ensure_det_host(n, total);
-      char* pack = nullptr;
-      if (!detect_multi_into_pack(n, p, num_images, num_classes, pcap, static_cast<char*>(n->det_host_dev), &pack))
-        HIP_CHECK(hipMemcpyAsync(n->det_host, pack, total, hipMemcpyDeviceToHost, st));
-      HIP_CHECK(hipStreamSynchronize(st));
-    };
-    run();
-    if (n->net->HandoffRecover()) run();      // (as mscnn_net_detect: the frame has been run again on whole tiles)
-    const int rc = mscnn_net_unpack_detections_multi(n->det_host, num_images, num_classes, pcap, dets_host, ids_host, cap, seg_dets,
-                                                     image_rois);
-    CHECK_EQ(rc, 0) << g_err;
+    detect_segments_blocking(
+        n, "detect_multi", num_images, num_classes,
+        [&] {
+          CHECK(n->net->has_blob("proposals_score")) << "net has no proposals_score output";
+          return n->net->blob_by_name("proposals_score")->num();
+        },
+        [&](int pcap, char* pack_at, char** pack) { return detect_multi_into_pack(n, p, num_images, num_classes, pcap, pack_at, pack); },
+        dets_host, ids_host, cap, seg_dets, image_rois);
   });
 }
 
@@ -866,8 +921,7 @@ int mscnn_net_detect_cascade(mscnn_net* n, const mscnn_detect_params* p, float d
 // ---- every (image, cascade output, class) segment of the last forward in one pass ------------------------------------------------------
 // The blob triples of the cascade outputs, checked: names, [R, 5] boxes and proposals, one row count throughout.
 struct CascadeBlobs {
-  std::vector<const Blob<float>*> boxes, prob, props;
-  std::vector<int> ncls;
+  std::vector<SegSource> src;
   int R_all = 0;
 };
 static CascadeBlobs cascade_blobs(mscnn_net* n, int num_outputs, const char* const* bbox_blobs, const char* const* prob_blobs,
@@ -892,8 +946,7 @@ static CascadeBlobs cascade_blobs(mscnn_net* n, int num_outputs, const char* con
     CHECK_EQ(boxes->count(), 5 * R) << bbox_blobs[o] << " is not an [R, 5] box blob (" << boxes->count() << " values in " << R << " rows)";
     CHECK_EQ(props->count(), 5 * R) << proposal_blobs[o] << " is not an [R, 5] proposal blob (" << props->count() << " values in " << R
                                     << " rows)";
-    b.boxes.push_back(boxes); b.prob.push_back(prob); b.props.push_back(props);
-    b.ncls.push_back(prob->count() / R);
+    b.src.push_back(SegSource{boxes, prob, props, prob->count() / R, true});
   }
   return b;
 }
@@ -913,77 +966,12 @@ static std::vector<mscnn_detections_desc> cascade_descs(mscnn_net* n, const mscn
     const int o = (s % K) / num_classes;
     mscnn_detections_desc& d = desc[s];
     std::memset(&d, 0, sizeof(d));
-    d.ncls = b.ncls[o];
+    d.ncls = b.src[o].ncls;
     d.cls_id = p[s].cls_id;
     CHECK(d.cls_id >= 1 && d.cls_id <= d.ncls) << "segment " << s << " (output " << o << "): cls_id " << d.cls_id << " of " << d.ncls;
     d.ratio_h = p[s].ratio_h; d.ratio_w = p[s].ratio_w; d.org_h = p[s].org_h; d.org_w = p[s].org_w; d.nms_overlap = p[s].nms_overlap;
   }
   return desc;
-}
-
-// The cascade multi pack (mscnn_hip.h: mscnn_detections_cascade_multi_fwd) of the last forward with cap rows, at pack_at
-// (device-addressable) or in the net's device pack.  Returns false when it went to the device pack instead: a per-image bound over
-// 4032 rows runs mscnn_detections_cascade_fwd per segment on ranges read from each output's proposals, into the same layout.
-static bool detect_cascade_multi_into_pack(mscnn_net* n, const std::vector<mscnn_detections_desc>& desc, int num_images, int num_outputs,
-                                           int num_classes, const CascadeBlobs& b, float det_thr, int cap, char* pack_at, char** pack_out) {
-  const int K = num_outputs * num_classes, S = num_images * K, R_all = b.R_all;
-  hipStream_t st = (hipStream_t)Caffe::stream();
-  const size_t total = mscnn_detections_multi_pack_bytes(S, cap);
-  const int bound = n->net->has_blob("proposals_score") ? per_image_row_bound(n, num_images, R_all) : R_all;
-  if (bound <= 4032) {
-    std::vector<mscnn_cascade_output> outs(num_outputs);
-    for (int o = 0; o < num_outputs; ++o)
-      outs[o] = mscnn_cascade_output{b.boxes[o]->gpu_data(), b.prob[o]->gpu_data(), b.props[o]->gpu_data(), b.ncls[o]};
-    const size_t wb = mscnn_detections_cascade_multi_workspace_bytes(S, bound);
-    void* ws = n->det_ws.Reserve(wb);
-    char* pack = pack_at ? pack_at : static_cast<char*>(n->det_pack.Reserve(total));
-    MSCNN_CHECK(mscnn_detections_cascade_multi_fwd(desc.data(), det_thr, num_images, num_outputs, num_classes, outs.data(), R_all, bound,
-                                                   pack, cap, ws, wb, st));
-    *pack_out = pack;
-    return pack == pack_at;
-  }
-  // rows of every image in every output's proposals (column 0 = image, ascending): one host read per output
-  std::vector<int> row0((size_t)num_outputs * num_images), rows((size_t)num_outputs * num_images);
-  int max_rows = 0;
-  for (int o = 0; o < num_outputs; ++o) {
-    const float* h = b.props[o]->cpu_data();      // (synchronises the stream)
-    std::vector<int> end(num_images, 0);
-    int prev = 0;
-    for (int r = 0; r < R_all; ++r) {
-      const int img = (int)h[(size_t)r * 5];
-      CHECK(img >= prev && img < num_images) << "the proposals of cascade output " << o << " are not grouped by image";
-      prev = img;
-      end[img] = r + 1;
-    }
-    for (int i = 1; i < num_images; ++i) if (end[i] < end[i - 1]) end[i] = end[i - 1];
-    for (int i = 0; i < num_images; ++i) {
-      row0[(size_t)o * num_images + i] = i > 0 ? end[i - 1] : 0;
-      rows[(size_t)o * num_images + i] = end[i] - row0[(size_t)o * num_images + i];
-      max_rows = std::max(max_rows, rows[(size_t)o * num_images + i]);
-    }
-  }
-  char* pack = static_cast<char*>(n->det_pack.Reserve(total));
-  int* hdr = reinterpret_cast<int*>(pack);
-  const size_t rows_cap = (size_t)(cap > 0 ? cap : 1), table = sizeof(int) * (4 + 4 * (size_t)S);
-  double* dets = reinterpret_cast<double*>(pack + table);
-  int* ids = reinterpret_cast<int*>(pack + table + sizeof(double) * 5 * rows_cap);
-  const size_t wb = mscnn_detections_workspace_bytes(max_rows);
-  void* ws = n->det_ws.Reserve(wb);
-  const int words[4] = {S, R_all, cap, 0};
-  MSCNN_CHECK(mscnn_store_words_i32(hdr, words, 4, st));
-  for (int s = 0; s < S; ++s) {
-    const int i = s / K, k = s % K, o = k / num_classes;
-    const int r0 = row0[(size_t)o * num_images + i], nr = rows[(size_t)o * num_images + i];
-    const size_t slot = (size_t)K * r0 + (size_t)k * nr;
-    int* ent = hdr + 4 + 4 * (size_t)s;
-    const int e[3] = {nr, r0, 0};
-    MSCNN_CHECK(mscnn_store_words_i32(ent + 1, e, 3, st));
-    MSCNN_CHECK(mscnn_detections_cascade_fwd(&desc[s], det_thr, b.boxes[o]->gpu_data() + (size_t)r0 * 5,
-                                             b.prob[o]->gpu_data() + (size_t)r0 * b.ncls[o], b.props[o]->gpu_data() + (size_t)r0 * 5, nr,
-                                             dets + 5 * slot, ids + slot, ent, ws, wb, st));
-  }
-  *pack_out = pack;
-  return false;
 }
 
 size_t mscnn_net_detect_cascade_multi_pack_bytes(int num_images, int num_outputs, int num_classes, int cap) {
@@ -998,7 +986,7 @@ int mscnn_net_detect_cascade_multi_device(mscnn_net* n, const mscnn_detect_param
     const CascadeBlobs b = cascade_blobs(n, num_outputs, bbox_blobs, prob_blobs, proposal_blobs);
     const auto desc = cascade_descs(n, p, num_images, num_outputs, num_classes, b, cap);
     char* pack = nullptr;
-    detect_cascade_multi_into_pack(n, desc, num_images, num_outputs, num_classes, b, det_thr, cap, nullptr, &pack);
+    segments_into_pack(n, b.src, desc, num_images, num_classes, det_thr, cap, nullptr, &pack);
     *pack_dev = pack;
   });
 }
@@ -1008,33 +996,17 @@ int mscnn_net_detect_cascade_multi(mscnn_net* n, const mscnn_detect_params* p, i
                                    float det_thr, double* dets_host, int* ids_host, int cap, int* seg_dets, int* image_rois) {
   return guarded([&] {
     CHECK(p && seg_dets) << "detect_cascade_multi: null pointer";
-    // as mscnn_net_detect_multi: the kernels write the pack straight into host-coherent pinned memory, one stream synchronisation, no
-    // copy; the per-segment fallback leaves it in the device pack and copies it
-    hipStream_t st = (hipStream_t)Caffe::stream();
-    int pcap = 0, S = 0;
-    auto run = [&]() {
-      const CascadeBlobs b = cascade_blobs(n, num_outputs, bbox_blobs, prob_blobs, proposal_blobs);
-      pcap = num_outputs * num_classes * b.R_all;
-      const auto desc = cascade_descs(n, p, num_images, num_outputs, num_classes, b, pcap);
-      S = (int)desc.size();
-      const size_t total = mscnn_detections_multi_pack_bytes(S, pcap);
-      ensure_det_host(n, total);
-      *static_cast<volatile int*>(n->det_host) = -1;      // the header's first word (S): the kernels must have written it
-      char* pack = nullptr;
-      if (!detect_cascade_multi_into_pack(n, desc, num_images, num_outputs, num_classes, b, det_thr, pcap,
-                                          static_cast<char*>(n->det_host_dev), &pack))
-        HIP_CHECK(hipMemcpyAsync(n->det_host, pack, total, hipMemcpyDeviceToHost, st));
-      HIP_CHECK(hipStreamSynchronize(st));
-    };
-    run();
-    if (n->net->HandoffRecover()) run();      // (as mscnn_net_detect: the frame has been run again on whole tiles)
-    const int* hdr = static_cast<const int*>(n->det_host);
-    CHECK_GE(hdr[0], 0) << "detect_cascade_multi: the pack header was not written (" << S << " segments, " << pcap << " pack rows)";
-    for (int s = 0; s < S; ++s)
-      CHECK_GE(hdr[4 + 4 * (size_t)s], -1) << "detect_cascade_multi: segment " << s << " has count " << hdr[4 + 4 * (size_t)s];
-    const int rc = mscnn_net_unpack_detections_multi(n->det_host, num_images, num_outputs * num_classes, pcap, dets_host, ids_host, cap,
-                                                     seg_dets, image_rois);
-    CHECK_EQ(rc, 0) << g_err;
+    CascadeBlobs b;
+    std::vector<mscnn_detections_desc> desc;
+    detect_segments_blocking(
+        n, "detect_cascade_multi", num_images, num_outputs * num_classes,
+        [&] {
+          b = cascade_blobs(n, num_outputs, bbox_blobs, prob_blobs, proposal_blobs);
+          desc = cascade_descs(n, p, num_images, num_outputs, num_classes, b, num_outputs * num_classes * b.R_all);
+          return b.R_all;
+        },
+        [&](int pcap, char* pack_at, char** pack) { return segments_into_pack(n, b.src, desc, num_images, num_classes, det_thr, pcap, pack_at, pack); },
+        dets_host, ids_host, cap, seg_dets, image_rois);
   });
 }
 

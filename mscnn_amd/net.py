@@ -383,15 +383,24 @@ class Net:
         return dets[:D.value].copy(), ids[:D.value].copy(), R.value
 
     @classmethod
+    def _multi_params(cls, params, classes, num_outputs=1, **defaults):
+        """params: one dict per image (ratios, org_hw; optional bbox_mean, bbox_std, proposal_thr, nms_overlap), classes: cls_ids
+        -> the (image, output, class) parameter array of mscnn_net_detect_multi / _cascade_multi, image-major."""
+        defaults = dict(dict(bbox_mean=(0, 0, 0, 0), bbox_std=(0.1, 0.1, 0.2, 0.2), proposal_thr=-10.0, nms_overlap=0.5), **defaults)
+        K = num_outputs * len(classes)
+        arr = (DetectParams * max(len(params) * K, 1))()
+        for i, kw in enumerate(params):
+            kw = dict(defaults, **kw)
+            for k in range(K):
+                arr[i * K + k] = cls._params(classes[k % len(classes)], **kw)
+        return arr
+
+    @classmethod
     def _cascade_multi_args(cls, params, outputs, classes):
         """-> (the (image, output, class) parameter array, the three blob name arrays) of mscnn_net_detect_cascade_multi."""
-        O, Cn = len(outputs), len(classes)
-        arr = (DetectParams * max(len(params) * O * Cn, 1))()
-        for i, kw in enumerate(params):
-            kw = dict(dict(nms_overlap=0.5), **kw)
-            for o in range(O):
-                for c, cls_id in enumerate(classes):
-                    arr[(i * O + o) * Cn + c] = cls._params(cls_id, kw["ratios"], kw["org_hw"], (0, 0, 0, 0), (1, 1, 1, 1), 0.0, kw["nms_overlap"])
+        O = len(outputs)
+        keep = ("ratios", "org_hw", "nms_overlap")
+        arr = cls._multi_params([{k: v for k, v in kw.items() if k in keep} for kw in params], classes, O, bbox_std=(1, 1, 1, 1), proposal_thr=0.0)
         names = [(C.c_char_p * max(O, 1))(*[None if t[k] is None else t[k].encode() for t in outputs]) for k in range(3)]
         return arr, names
 
@@ -431,17 +440,6 @@ class Net:
                                             C.byref(D), C.byref(R)))
         return dets[:D.value].copy(), ids[:D.value].copy(), R.value
 
-    @classmethod
-    def _multi_params(cls, params, classes):
-        """params: one dict per image (ratios, org_hw; optional bbox_mean, bbox_std, proposal_thr, nms_overlap), classes: cls_ids
-        -> the (image, class) parameter array of mscnn_net_detect_multi, image-major."""
-        arr = (DetectParams * (len(params) * len(classes)))()
-        for i, kw in enumerate(params):
-            kw = dict(dict(bbox_mean=(0, 0, 0, 0), bbox_std=(0.1, 0.1, 0.2, 0.2), proposal_thr=-10.0, nms_overlap=0.5), **kw)
-            for c, cls_id in enumerate(classes):
-                arr[i * len(classes) + c] = cls._params(cls_id, **kw)
-        return arr
-
     def detect_multi(self, params, classes, cap=None):
         """mscnn_net_detect_multi: the final stage of every image and class of the last forward in one pass.  params: one dict per
         image of the batch (ratios, org_hw, optionally bbox_mean / bbox_std / proposal_thr / nms_overlap); classes: the cls_ids.
@@ -468,14 +466,7 @@ class Net:
     def detect(self, cls_id, ratios, org_hw, bbox_mean=(0, 0, 0, 0), bbox_std=(0.1, 0.1, 0.2, 0.2), proposal_thr=-10.0,
                nms_overlap=0.5, cap=4096):
         """Final detection stage on the device; returns (dets[D,5] float64 [x y w h prob], roi ids[D], R)."""
-        p = DetectParams()
-        p.cls_id = cls_id
-        for k in range(4):
-            p.bbox_mean[k] = bbox_mean[k]; p.bbox_std[k] = bbox_std[k]
-        p.proposal_thr = proposal_thr
-        p.ratio_h, p.ratio_w = ratios
-        p.org_h, p.org_w = org_hw
-        p.nms_overlap = nms_overlap
+        p = self._params(cls_id, ratios, org_hw, bbox_mean, bbox_std, proposal_thr, nms_overlap)
         dets = np.zeros((cap, 5), np.float64); ids = np.zeros(cap, np.int32)
         D = C.c_int(); R = C.c_int()
         _check(lib().mscnn_net_detect(self._h, C.byref(p), dets.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p), cap,

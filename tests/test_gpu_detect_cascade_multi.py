@@ -39,7 +39,7 @@ def cascade_outputs(rows_per_image, num_outputs, ncls, seed):
     """[(boxes [R, 5], cls_prob [R, ncls], props [R, 5])] per cascade output, rows grouped by image (column 0 ascending): per image
     clusters of overlapping boxes; every output has boxes, probabilities and proposals of its own (a later stage's proposals are
     the earlier one's boxes, as DecodeBBox chains them); in every output some proposals have x2 = x1 - 1 (zero width, :104-107) or
-    y2 = y1 - 1."""
+    y2 = y1 - 1.  ncls: one number, or one per output."""
     rng = np.random.default_rng(seed)
     img = np.concatenate([np.full(n, i, np.float32) for i, n in enumerate(rows_per_image)]) if len(rows_per_image) else np.zeros(0, np.float32)
     R = len(img)
@@ -54,7 +54,7 @@ def cascade_outputs(rows_per_image, num_outputs, ncls, seed):
     for o in range(num_outputs):
         props = np.concatenate([img[:, None], prev], 1).astype(np.float32)
         boxes = np.concatenate([img[:, None], prev + rng.normal(0, 6, (R, 4)).astype(np.float32)], 1).astype(np.float32)
-        logits = rng.standard_normal((R, ncls)) * 1.5
+        logits = rng.standard_normal((R, ncls[o] if isinstance(ncls, (list, tuple)) else ncls)) * 1.5
         prob = (np.exp(logits) / np.exp(logits).sum(1, keepdims=True)).astype(np.float32)
         prob[3::11] = prob[2::11][: len(prob[3::11])]                    # exact ties: the sort is stable
         props[4 + o::13, 3] = props[4 + o::13, 1] - 1                    # zero width
@@ -80,23 +80,24 @@ def survivors(prob, props, cls_id, det_thr):
     return ok & (p >= np.float32(det_thr)) if det_thr > 0 else ok
 
 
-def oracle_segments(orc, outs, num_images, classes, det_thr, kw_of=image_kw):
-    """[(dets, ids, row0, rows, survivors)] per segment, image-major, then output, then class, from the CPU oracle."""
+def oracle_segments(orc, outs, num_images, classes, det_thr, kw_of=image_kw, seg_kw=lambda i, o, c: {}):
+    """[(dets, ids, row0, rows, survivors)] per segment, image-major, then output, then class, from the CPU oracle.  seg_kw(image,
+    output, cls_id): keyword arguments of that one segment, over kw_of(image)'s."""
     res = []
     for i in range(num_images):
-        for boxes, prob, props in outs:
+        for o, (boxes, prob, props) in enumerate(outs):
             row0, rows = ranges_of(props, num_images)[i]
             sl = slice(row0, row0 + rows)
             for c in classes:
-                d, ids = orc.detections_cascade(boxes[sl], prob[sl], props[sl], cls_id=c, det_thr=det_thr, **kw_of(i))
+                d, ids = orc.detections_cascade(boxes[sl], prob[sl], props[sl], cls_id=c, det_thr=det_thr, **dict(kw_of(i), **seg_kw(i, o, c)))
                 res.append((d, ids, row0, rows, int(survivors(prob[sl], props[sl], c, det_thr).sum())))
     return res
 
 
-def check_op(hip, outs, num_images, classes, det_thr, want, max_rows=None, kw_of=image_kw):
+def check_op(hip, outs, num_images, classes, det_thr, want, max_rows=None, kw_of=image_kw, seg_kw=lambda i, o, c: {}):
     """The one-pass op against the per-range op (bit for bit) and against the oracle's segments `want` (ids and dets equal: the
     assertion of test_gpu_net._check_cascade)."""
-    segs = [dict(cls_id=c, **kw_of(i)) for i in range(num_images) for _ in outs for c in classes]
+    segs = [dict(kw_of(i), cls_id=c, **seg_kw(i, o, c)) for i in range(num_images) for o in range(len(outs)) for c in classes]
     douts = [tuple(dev(t) for t in o) for o in outs]
     got = hip.detections_cascade_multi(douts, num_images, segs, det_thr=det_thr, max_rows_per_image=max_rows)
     assert len(got) == len(want) == len(segs)
@@ -147,6 +148,27 @@ def test_cascade_multi_op_every_segment_equals_the_per_range_stage(hip, orc, row
     check_op(hip, outs, B, classes, det_thr, want, max_rows=max(rows))
     if O == 3 and len(classes) == 1:                 # the loosest host bound: every row of the batch
         check_op(hip, outs, B, classes, det_thr, want)
+
+
+def test_cascade_multi_op_chunk_boundary_inside_an_image_and_outputs_of_different_width(hip, orc):
+    """2 images x 3 outputs x 6 classes = 36 segments: the second chunk of launches starts at segment 32 = (image 1, output 2, third
+    class), inside an image and between two classes of one output, so the chunk-local segment index differs from the global one.  The
+    outputs have 7, 7 and 8 probability columns (the segment's source decides the row stride); the images have 65 rows (one past a
+    64-bit mask word) and 1 row; one segment of each image has an nms_overlap of its own."""
+    rows, classes, ncls = [65, 1], [2, 3, 4, 5, 6, 7], (7, 7, 8)
+    outs = cascade_outputs(rows, 3, ncls, 301)
+    assert [o[1].shape[1] for o in outs] == list(ncls)
+    own = lambda i, o, c: dict(nms_overlap=0.2) if (o, c) == (1, 4) else {}      # noqa: E731
+    want = oracle_segments(orc, outs, 2, classes, 0.0, seg_kw=own)
+    assert len(want) == 36 and 32 // 18 == 1 and (32 % 18) // 6 == 2 and 32 % 6 == 2
+    # not vacuous, on the oracle's output: the NMS suppresses in every segment of image 0, the single row of image 1 is a detection
+    # everywhere, and the segment with its own overlap differs from what its image's overlap gives
+    assert all(0 < len(d) < surv for d, _, _, _, surv in want[:18])
+    assert all(len(d) == 1 and (row0, n) == (65, 1) for d, _, row0, n, _ in want[18:])
+    plain = oracle_segments(orc, outs, 2, classes, 0.0)
+    assert len(want[6 + 2][0]) < len(plain[6 + 2][0])
+    assert all(np.array_equal(a[0], b[0]) for s, (a, b) in enumerate(zip(want, plain)) if s % 18 != 8)
+    check_op(hip, outs, 2, classes, 0.0, want, max_rows=65, seg_kw=own)
 
 
 def test_cascade_multi_op_edge_rows(hip, orc):

@@ -104,6 +104,27 @@ def test_multi_op_whole_batch_dummy_row_and_segment_chunks(hip, orc):
     check_op(hip, orc, bbox_pred, cls_pred, props, len(rows), [2, 3], max_rows=70)
 
 
+def test_multi_op_mask_word_boundary_empty_image_and_an_image_over_the_bound(hip, orc):
+    """Images of 64, 0 and 65 rows (both sides of a 64-bit mask word, nothing in between), classes [2, 3], through the one-source
+    path; then the same inputs with max_rows_per_image = 64: the segments of the 65-row image come back as over the bound (count -1:
+    (None, None, row0, rows)), every other segment unchanged."""
+    rows, classes = [64, 0, 65], [2, 3]
+    bbox_pred, cls_pred, props = batch_rois(rows, 23)
+    # not vacuous, on the oracle's output: every non-empty segment has a detection and a suppressed box
+    passed = (props[:, 5] >= -10.0) & (props[:, 3] - props[:, 1] != 0) & (props[:, 4] - props[:, 2] != 0)
+    for i, sl in ((0, slice(0, 64)), (2, slice(64, 129))):
+        for c in classes:
+            dref, _ = orc.detections(bbox_pred[sl], cls_pred[sl], props[sl], cls_id=c, **image_kw(i))
+            assert 0 < len(dref) < int(passed[sl].sum()), (i, c)
+    out, _ = check_op(hip, orc, bbox_pred, cls_pred, props, 3, classes, max_rows=65)
+    assert [(o[2], o[3]) for o in out] == [(0, 64)] * 2 + [(64, 0)] * 2 + [(64, 65)] * 2
+    segs = [dict(cls_id=c, **image_kw(i)) for i in range(3) for c in classes]
+    over = hip.detections_multi(dev(bbox_pred), dev(cls_pred), dev(props), 3, segs, 64)
+    assert over[4:] == [(None, None, 64, 65)] * 2
+    for a, b in zip(over[:4], out[:4]):
+        assert np.array_equal(a[0].view(np.uint64), b[0].view(np.uint64)) and np.array_equal(a[1], b[1]) and a[2:] == b[2:]
+
+
 # ---- the net entries ---------------------------------------------------------------------------------------------------------------
 NETS = [   # model, reduced input, batch, classes
     ("kitti_car/mscnn-7s-576", dict(height=96, width=320, max_nms_num=120), 4, [2]),
