@@ -414,9 +414,49 @@ typedef struct {
   double ratio_h, ratio_w, org_h, org_w, nms_overlap;
 } mscnn_detections_desc;
 MSCNN_API size_t mscnn_detections_workspace_bytes(int R);
+
+/* bbNms's user knobs (utils/bbNms.m:49-56, `pNms` at the top of every reference driver), one setting per call.  The calls without
+ * this struct, a NULL pointer and the all-default struct are the same thing: nmsMax(greedy = 1, ovrDnm = union), thr = -inf, and
+ * their results are byte-identical.
+ *   type     'maxg' (greedy: a suppressed box suppresses nothing) or 'max' (box j goes when ANY higher-scored box overlaps it,
+ *            suppressed or not: bbNms.m:117 with greedy = 0 -- on the device a column-OR of the overlap bit matrix instead of the
+ *            serial scan).  Refused, naming the value: 'ms' (mean shift needs nonMaxSuprList, which the reference does not ship),
+ *            'cover' (its scores come from a BLAS mat-vec, N * bbs(:,5), whose summation order can not be pinned, so no bit-exact
+ *            restatement exists) and 'none' (read the ROI rows instead).
+ *   ovr_dnm  'union': o / (as_i + as_j - o); 'min': o / min(as_i, as_j) (bbNms.m:121).  Doubles, the same operation order, strict
+ *            o > nms_overlap (nms_overlap stays in mscnn_detections_desc).
+ *   thr      rows with !(prob > thr) are dropped before the NMS (bbNms.m:85, strict).  Encoding: the value itself, a double;
+ *            the default is -HUGE_VAL (-inf, bbNms's own default), any other non-NaN value is a threshold (+inf drops every row).
+ *   det_thr  plain stage only (examples/widerface/run_mscnn_detection.m:139-143): when > 0, rows with !(prob >= det_thr) are
+ *            dropped before the NMS.  0 = off.  The cascade calls keep their own det_thr argument and refuse a non-zero one here.
+ * Not covered: maxn (split-and-recurse, a heuristic that changes results: only its default inf -- mscnn_nms_params_from_names
+ * refuses a finite one), radii ('ms' only), resize and separate (no reference driver sets them).
+ * More than 4032 rows in one list (the tiled path) run with the default setting only; anything else is refused there. */
+enum { MSCNN_NMS_TYPE_MAXG = 0, MSCNN_NMS_TYPE_MAX = 1, MSCNN_NMS_TYPE_MS = 2, MSCNN_NMS_TYPE_COVER = 3, MSCNN_NMS_TYPE_NONE = 4 };
+enum { MSCNN_NMS_OVR_UNION = 0, MSCNN_NMS_OVR_MIN = 1 };
+#ifndef MSCNN_NMS_PARAMS_DEFINED
+#define MSCNN_NMS_PARAMS_DEFINED
+typedef struct {
+  int type;          /* 0 = 'maxg', 1 = 'max' */
+  int ovr_dnm;       /* 0 = 'union', 1 = 'min' */
+  double thr;        /* -HUGE_VAL = bbNms's default -inf */
+  float det_thr;     /* 0 = off; plain stage only */
+} mscnn_nms_params;
+#endif
+/* Validates *nms (NULL: the defaults) and writes the setting the kernels will run with to *out, every byte of it (padding zero):
+ * everything a nms pointer contributes to a launch.  Fails, naming the value, on a refused or out-of-range field. */
+MSCNN_API int mscnn_nms_params_resolve(const mscnn_nms_params* nms, mscnn_nms_params* out);
+/* The same from bbNms's own spelling: type 'maxg' / 'max', ovr_dnm 'union' / 'min' (NULL: the default), thr, maxn (must be
+ * HUGE_VAL = inf), det_thr. */
+MSCNN_API int mscnn_nms_params_from_names(const char* type, const char* ovr_dnm, double thr, double maxn, float det_thr,
+                                          mscnn_nms_params* out);
 MSCNN_API int mscnn_detections_fwd(const mscnn_detections_desc* desc, const float* bbox_pred, const float* cls_pred,
                          const float* props, int R, double* dets_out, int* ids_out, int* count_out_dev,
                          void* workspace, size_t workspace_bytes, void* stream);
+
+MSCNN_API int mscnn_detections_nms_fwd(const mscnn_detections_desc* desc, const mscnn_nms_params* nms, const float* bbox_pred,
+                                       const float* cls_pred, const float* props, int R, double* dets_out, int* ids_out,
+                                       int* count_out_dev, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Final stage of the cascade drivers (examples/kitti_car/run_cascademscnn.m:84-117): `boxes` = the decoded box blob of a
  * cascade stage [R][5] = [img x1 y1 x2 y2] (DecodeBBox output), `cls_prob` = that stage's in-net probabilities [R][ncls]
@@ -425,6 +465,9 @@ MSCNN_API int mscnn_detections_fwd(const mscnn_detections_desc* desc, const floa
 MSCNN_API int mscnn_detections_cascade_fwd(const mscnn_detections_desc* desc, float det_thr, const float* boxes,
                                  const float* cls_prob, const float* props, int R, double* dets_out, int* ids_out,
                                  int* count_out_dev, void* workspace, size_t workspace_bytes, void* stream);
+MSCNN_API int mscnn_detections_cascade_nms_fwd(const mscnn_detections_desc* desc, float det_thr, const mscnn_nms_params* nms,
+                                               const float* boxes, const float* cls_prob, const float* props, int R, double* dets_out,
+                                               int* ids_out, int* count_out_dev, void* workspace, size_t workspace_bytes, void* stream);
 
 /* The same stage for EVERY (image, class) segment of a batched forward in one pass (three launches per 32 segments, no host
  * read).  props / bbox_pred / cls_pred hold the ROIs of num_images images, grouped by image with the image index in column 0 of
@@ -459,6 +502,11 @@ MSCNN_API size_t mscnn_detections_multi_workspace_bytes(int num_segments, int ma
 MSCNN_API int mscnn_detections_multi_fwd(const mscnn_detections_desc* desc, int num_images, int num_classes, const float* bbox_pred,
                                          const float* cls_pred, const float* props, int R_all, int max_rows_per_image, void* pack_dev,
                                          int cap, void* workspace, size_t workspace_bytes, void* stream);
+/* ... with bbNms's knobs (one setting for all segments); mscnn_detections_multi_fwd is this call with nms = NULL. */
+MSCNN_API int mscnn_detections_multi_nms_fwd(const mscnn_detections_desc* desc, const mscnn_nms_params* nms, int num_images,
+                                             int num_classes, const float* bbox_pred, const float* cls_pred, const float* props,
+                                             int R_all, int max_rows_per_image, void* pack_dev, int cap, void* workspace,
+                                             size_t workspace_bytes, void* stream);
 
 /* The same one-pass stage for the cascade drivers (mscnn_detections_cascade_fwd per segment): several sources instead of one.
  * outputs[num_outputs], 1 <= num_outputs <= 4: each cascade output's own blob triple (boxes [R_all][5], cls_prob [R_all][ncls],
@@ -478,6 +526,11 @@ MSCNN_API int mscnn_detections_cascade_multi_fwd(const mscnn_detections_desc* de
                                                  int num_classes, const mscnn_cascade_output* outputs, int R_all,
                                                  int max_rows_per_image, void* pack_dev, int cap, void* workspace,
                                                  size_t workspace_bytes, void* stream);
+/* ... with bbNms's knobs; mscnn_detections_cascade_multi_fwd is this call with nms = NULL. */
+MSCNN_API int mscnn_detections_cascade_multi_nms_fwd(const mscnn_detections_desc* desc, float det_thr, const mscnn_nms_params* nms,
+                                                     int num_images, int num_outputs, int num_classes,
+                                                     const mscnn_cascade_output* outputs, int R_all, int max_rows_per_image,
+                                                     void* pack_dev, int cap, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Image pre-processing in front of net.forward -- MATLAB `run_mscnn_detection.m:64-69`:

@@ -183,6 +183,25 @@ typedef struct {
   double org_h, org_w;              /* original image size (clip bounds) */
   double nms_overlap;               /* 0.5 */
 } mscnn_detect_params;
+/* bbNms's user knobs for EVERY detect call on this net from now on -- `pNms.type / pNms.ovrDnm` (and bbNms's thr) at the top of the
+ * reference scripts; pNms.overlap stays in mscnn_detect_params.  The struct, its field encodings and what is refused ('ms', 'cover',
+ * 'none', out-of-range values: an error naming the value, the setting unchanged) are those of include/mscnn_hip.h, repeated here
+ * so that this header stands alone.  NULL = the defaults (nmsMax greedy, union, thr -inf, no det_thr), under which every call runs
+ * exactly the kernels it ran before this setting existed.  det_thr is the plain stage's (widerface/run_mscnn_detection.m:139-143);
+ * the cascade calls take theirs as an argument and fail, naming the value, while the setting's det_thr is not 0.  A forward with more than 4032 ROI rows per image runs the tiled
+ * per-segment path, which has the default setting only: a detect call fails there, naming the limit, instead of ignoring the
+ * setting.  The new modes have not been timed on the full nets. */
+#ifndef MSCNN_NMS_PARAMS_DEFINED
+#define MSCNN_NMS_PARAMS_DEFINED
+typedef struct {
+  int type;          /* 0 = 'maxg', 1 = 'max' */
+  int ovr_dnm;       /* 0 = 'union', 1 = 'min' */
+  double thr;        /* -HUGE_VAL = bbNms's default -inf; rows with !(prob > thr) are dropped */
+  float det_thr;     /* 0 = off; > 0: rows with !(prob >= det_thr) are dropped (plain stage only) */
+} mscnn_nms_params;
+#endif
+MSCNN_NET_API int mscnn_net_set_nms(mscnn_net* net, const mscnn_nms_params* nms);
+MSCNN_NET_API int mscnn_net_get_nms(const mscnn_net* net, mscnn_nms_params* out);
 MSCNN_NET_API int mscnn_net_detect(mscnn_net* net, const mscnn_detect_params* p, double* dets_host, int* ids_host,
                                    int cap, int* num_dets, int* num_rois);
 /* The same stage for a STREAM of frames (batch-1 nets), pipelined: _begin runs the final stage of the forward just done into the

@@ -8,6 +8,11 @@
 //   arithmetic until `double([...])`, stable descending sort on prob (ties: lower row first), IoU and
 //   threshold test in double, pairs with iw <= 0 or ih <= 0 skipped.
 // Same kernel structure as BoxOutput's NMS: parallel bit-matrix + one-wavefront greedy scan.
+// bbNms's user knobs (mscnn_nms_params): ovrDnm = 'min' is another denominator in the bit matrix (bbNms.m:121), type = 'max' a
+// column-OR of that matrix instead of the greedy scan (bbNms.m:117 with greedy = 0), thr the strict prob > thr of bbNms.m:85.
+#include <cfloat>
+#include <cmath>
+#include <cstring>
 #include "common.h"
 #include "box_device.h"
 #include "nms_large.h"
@@ -41,11 +46,19 @@ struct DetArgs {
   float proposal_thr, ratio_h, ratio_w, org_h, org_w;
   int cascade;        // 1: run_cascademscnn.m:84-117 -- bbox_pred = decoded boxes [R][5], cls_pred = in-net probabilities,
                       //    props = proposal rows [R][5]; proposal_thr = det_thr
+  double nms_thr;     // bbNms's thr (bbNms.m:85, strict >); -inf by default
+  float det_thr;      // plain stage only: examples/widerface/run_mscnn_detection.m:139-143 (> 0: rows with !(prob >= det_thr) go)
 };
+
+// mscnn_nms_params as the kernels take it (resolved: NULL -> the defaults)
+struct DetNms { double thr; float det_thr; int type, ovr_dnm; };
 
 enum { DC_N = 0, DC_WORDS = 4, DC_BIG = 4 /* + BIG_STATE_WORDS (nms_large.h) */ };
 
 // One input row -> box and prob in MATLAB's types.  false: the row is filtered out.
+// kThr: bbNms's thr / the plain det_thr are set (mscnn_nms_params); without them the default thr = -inf is the literal it always was,
+// so the default kernels are the instructions they were before the params existed.
+template <bool kThr>
 __device__ __forceinline__ bool det_row(const DetArgs& a, int r, DetBox* box, float* prob_out) {
   if (a.cascade) {
     const float* q = a.props + 5 * (size_t)r;
@@ -59,7 +72,7 @@ __device__ __forceinline__ bool det_row(const DetArgs& a, int r, DetBox* box, fl
     const float w = x2 - x1 + 1.f, h = y2 - y1 + 1.f;                                // :93
     const float prob = a.cls_pred[(size_t)r * a.ncls + (a.cls_id - 1)];              // :113
     if (a.proposal_thr > 0 && !(prob >= a.proposal_thr)) return false;               // :115-117 (det_thr)
-    if (!(prob > -INFINITY)) return false;
+    if (kThr ? !((double)prob > a.nms_thr) : !(prob > -INFINITY)) return false;      // bbNms.m:85
     *box = DetBox{(double)x1, (double)y1, (double)w, (double)h};
     *prob_out = prob;
     return true;
@@ -82,7 +95,8 @@ __device__ __forceinline__ bool det_row(const DetArgs& a, int r, DetBox* box, fl
   ty = ty / a.ratio_h; th = th / a.ratio_h;
   tx = fmaxf(0.f, tx); ty = fmaxf(0.f, ty);
   tw = fminf(tw, a.org_w - tx); th = fminf(th, a.org_h - ty);
-  if (!(prob > -INFINITY)) return false;                                             // bbNms.m:76 (NaN drops out)
+  if (kThr && a.det_thr > 0 && !(prob >= a.det_thr)) return false;                   // widerface/run_mscnn_detection.m:139-143
+  if (kThr ? !((double)prob > a.nms_thr) : !(prob > -INFINITY)) return false;        // bbNms.m:85 (NaN drops out)
   *box = DetBox{(double)tx, (double)ty, (double)tw, (double)th};
   *prob_out = prob;
   return true;
@@ -95,6 +109,7 @@ __device__ __forceinline__ u64 det_key(float prob, int r) {
 
 // Per-row transform + filter, key sort, write sorted boxes: the body of one workgroup (kSortThreads threads).  *n_out = survivors.
 // (shared by det_transform_sort_kernel and the segmented det_seg_transform_sort_kernel: one code path, the same bits)
+template <bool kThr>
 __device__ __forceinline__ void det_transform_sort(const DetArgs& a, DetBox* __restrict__ sbox, double* __restrict__ sprob,
                                                    int* __restrict__ ssrc, DetBox* __restrict__ tmp_box, float* __restrict__ tmp_prob,
                                                    int* __restrict__ n_out) {
@@ -106,7 +121,7 @@ __device__ __forceinline__ void det_transform_sort(const DetArgs& a, DetBox* __r
   for (int r = tid; r < a.R; r += kSortThreads) {
     DetBox b;
     float prob;
-    if (!det_row(a, r, &b, &prob)) continue;
+    if (!det_row<kThr>(a, r, &b, &prob)) continue;
     tmp_box[r] = b;
     tmp_prob[r] = prob;
     const int pos = atomicAdd(&s_fill, 1);
@@ -134,7 +149,13 @@ __global__ __launch_bounds__(kSortThreads) void det_transform_sort_kernel(DetArg
                                                                           double* __restrict__ sprob, int* __restrict__ ssrc,
                                                                           DetBox* __restrict__ tmp_box,
                                                                           float* __restrict__ tmp_prob, int* __restrict__ cnt) {
-  det_transform_sort(a, sbox, sprob, ssrc, tmp_box, tmp_prob, cnt + DC_N);
+  det_transform_sort<false>(a, sbox, sprob, ssrc, tmp_box, tmp_prob, cnt + DC_N);
+}
+__global__ __launch_bounds__(kSortThreads) void det_transform_sort_thr_kernel(DetArgs a, DetBox* __restrict__ sbox,
+                                                                              double* __restrict__ sprob, int* __restrict__ ssrc,
+                                                                              DetBox* __restrict__ tmp_box,
+                                                                              float* __restrict__ tmp_prob, int* __restrict__ cnt) {
+  det_transform_sort<true>(a, sbox, sprob, ssrc, tmp_box, tmp_prob, cnt + DC_N);
 }
 
 // ---- more than kMaxK rows (nms_large.h): the same three steps over HBM-resident lists -------------------------------------------
@@ -145,7 +166,7 @@ __global__ __launch_bounds__(256) void det_transform_big_kernel(DetArgs a, u64* 
   if (r >= a.R) return;
   DetBox b;
   float prob;
-  if (!det_row(a, r, &b, &prob)) return;          // keys[] was cleared
+  if (!det_row<false>(a, r, &b, &prob)) return;   // keys[] was cleared (the tiled path runs with the default nms params only)
   tmp_box[r] = b;
   tmp_prob[r] = prob;
   keys[r] = det_key(prob, r);
@@ -197,6 +218,9 @@ __global__ __launch_bounds__(256) void det_emit_big_kernel(const int* __restrict
 
 // One 64 x 64 block (rb, cb) of the upper-triangular bit matrix over n sorted boxes.
 // (256 threads per 64 x 64 block, the four waves split the columns -- as nms_mask_kernel of boxoutput.hip)
+// kDnmMin: ovrDnm = 'min' -- the denominator is the smaller of the two areas instead of the union (bbNms.m:121).  (A template
+// parameter: the union kernels keep the instructions they had.)
+template <bool kDnmMin>
 __device__ __forceinline__ void det_mask_block(const DetBox* __restrict__ boxes, int n, double overlap, u64* __restrict__ mask, int wpr,
                                                int rb, int cb) {
   if (cb < rb || rb * 64 >= n || cb * 64 >= n) return;
@@ -220,7 +244,7 @@ __device__ __forceinline__ void det_mask_block(const DetBox* __restrict__ boxes,
       const double ih = fmin(ye_a, B.y + B.h) - fmax(A.y, B.y);
       if (ih <= 0) continue;
       double o = iw * ih;
-      const double u = as_a + B.w * B.h - o;
+      const double u = kDnmMin ? fmin(as_a, B.w * B.h) : as_a + B.w * B.h - o;
       o = o / u;
       if (o > overlap) bits |= 1u << (q & 15);
     }
@@ -233,19 +257,21 @@ __device__ __forceinline__ void det_mask_block(const DetBox* __restrict__ boxes,
 
 __global__ __launch_bounds__(256) void det_mask_kernel(const DetBox* __restrict__ boxes, const int* __restrict__ cnt,
                                                        double overlap, u64* __restrict__ mask, int wpr) {
-  det_mask_block(boxes, cnt[DC_N], overlap, mask, wpr, blockIdx.y, blockIdx.x);
+  det_mask_block<false>(boxes, cnt[DC_N], overlap, mask, wpr, blockIdx.y, blockIdx.x);
+}
+__global__ __launch_bounds__(256) void det_mask_min_kernel(const DetBox* __restrict__ boxes, const int* __restrict__ cnt,
+                                                           double overlap, u64* __restrict__ mask, int wpr) {
+  det_mask_block<true>(boxes, cnt[DC_N], overlap, mask, wpr, blockIdx.y, blockIdx.x);
 }
 
-// Greedy scan + emit of n sorted boxes by one 256-thread workgroup: kept box number k lands in dets[k] / ids[k], the count in
-// *count_out.  dyn_lds: 2 * 64 * wpr u64.
-__device__ __forceinline__ void det_scan_emit(const u64* __restrict__ mask, int wpr, int n, const DetBox* __restrict__ sbox,
-                                              const double* __restrict__ sprob, const int* __restrict__ ssrc, double* __restrict__ dets,
-                                              int* __restrict__ ids, int* __restrict__ count_out, u64* dyn_lds) {
+// Prefix count + emit of the keep words of n sorted boxes (lane c of wave 0 holds the keep word of boxes [64 c, 64 c + 64)) by one
+// 256-thread workgroup: kept box number k lands in dets[k] / ids[k], the count in *count_out.
+__device__ __forceinline__ void det_emit_kept(u64 mykeep, int n, const DetBox* __restrict__ sbox, const double* __restrict__ sprob,
+                                              const int* __restrict__ ssrc, double* __restrict__ dets, int* __restrict__ ids,
+                                              int* __restrict__ count_out) {
   __shared__ u64 keepw[64];
   __shared__ int pre[64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (n <= 0) { if (tid == 0) count_out[0] = 0; return; }
-  const u64 mykeep = greedy_scan(mask, n, wpr, wpr, dyn_lds);
   if (wave == 0) {
     keepw[lane] = mykeep;
     const int mine = __popcll(mykeep);
@@ -270,6 +296,40 @@ __device__ __forceinline__ void det_scan_emit(const u64* __restrict__ mask, int 
   }
 }
 
+// Greedy scan (type = 'maxg') + emit of n sorted boxes by one 256-thread workgroup.  dyn_lds: 2 * 64 * wpr u64.
+__device__ __forceinline__ void det_scan_emit(const u64* __restrict__ mask, int wpr, int n, const DetBox* __restrict__ sbox,
+                                              const double* __restrict__ sprob, const int* __restrict__ ssrc, double* __restrict__ dets,
+                                              int* __restrict__ ids, int* __restrict__ count_out, u64* dyn_lds) {
+  if (n <= 0) { if (threadIdx.x == 0) count_out[0] = 0; return; }
+  const u64 mykeep = greedy_scan(mask, n, wpr, wpr, dyn_lds);
+  det_emit_kept(mykeep, n, sbox, sprob, ssrc, dets, ids, count_out);
+}
+
+// type = 'max' (nmsMax with greedy = 0, bbNms.m:117-123): box j goes exactly when some i < j has bit (i, j) set, whether or not i
+// itself went -- the OR of column j over the rows above it, no serial dependency.  Lane = word of the row (coalesced), wave w takes
+// rows w, w + 4, ...; only words on or right of the diagonal block are read (the others were never written), rows >= n never.  The
+// four partial ORs meet in the first 4 * wpr words of det_scan_emit's dynamic LDS (2 * 64 * wpr); then the same emit.
+__device__ __forceinline__ void det_color_emit(const u64* __restrict__ mask, int wpr, int n, const DetBox* __restrict__ sbox,
+                                               const double* __restrict__ sprob, const int* __restrict__ ssrc, double* __restrict__ dets,
+                                               int* __restrict__ ids, int* __restrict__ count_out, u64* dyn_lds) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (n <= 0) { if (tid == 0) count_out[0] = 0; return; }
+  const int nw = (n + 63) >> 6;                            // words in use (<= wpr <= 63)
+  u64 acc = 0;
+  if (lane < nw)
+    for (int i = wave; i < n && (i >> 6) <= lane; i += 4) acc |= mask[(size_t)i * wpr + lane];
+  if (lane < nw) dyn_lds[wave * wpr + lane] = acc;
+  __syncthreads();
+  u64 mykeep = 0;
+  if (wave == 0 && lane < nw) {
+    const u64 removed = (dyn_lds[lane] | dyn_lds[wpr + lane]) | (dyn_lds[2 * wpr + lane] | dyn_lds[3 * wpr + lane]);
+    const int valid = min(64, n - lane * 64);
+    mykeep = ~removed;
+    if (valid < 64) mykeep &= (1ull << valid) - 1ull;
+  }
+  det_emit_kept(mykeep, n, sbox, sprob, ssrc, dets, ids, count_out);
+}
+
 __global__ __launch_bounds__(256) void det_scan_emit_kernel(const u64* __restrict__ mask, int wpr,
                                                             const DetBox* __restrict__ sbox, const double* __restrict__ sprob,
                                                             const int* __restrict__ ssrc, double* __restrict__ dets,
@@ -277,6 +337,15 @@ __global__ __launch_bounds__(256) void det_scan_emit_kernel(const u64* __restric
                                                             int* __restrict__ count_out) {
   extern __shared__ __attribute__((aligned(16))) u64 dyn_lds[];
   det_scan_emit(mask, wpr, cnt[DC_N], sbox, sprob, ssrc, dets, ids, count_out, dyn_lds);
+}
+
+__global__ __launch_bounds__(256) void det_color_emit_kernel(const u64* __restrict__ mask, int wpr,
+                                                             const DetBox* __restrict__ sbox, const double* __restrict__ sprob,
+                                                             const int* __restrict__ ssrc, double* __restrict__ dets,
+                                                             int* __restrict__ ids, const int* __restrict__ cnt,
+                                                             int* __restrict__ count_out) {
+  extern __shared__ __attribute__((aligned(16))) u64 dyn_lds[];
+  det_color_emit(mask, wpr, cnt[DC_N], sbox, sprob, ssrc, dets, ids, count_out, dyn_lds);
 }
 
 // ---- every segment of a batched forward in one pass (mscnn_detections_multi_fwd, mscnn_detections_cascade_multi_fwd) ----------------
@@ -295,6 +364,7 @@ struct DetSegArgs {
   int R_all, slots_per_image, classes_per_source, max_rows, wpr, cap, num_segs, s0;       // s0: first segment of this launch
   char* ws; size_t seg_stride_box, seg_stride_mask;                     // workspace: per-segment slices (det_multi_ptrs)
   int* hdr; double* dets; int* ids;                                     // pack: header + table, dets, ids (mscnn_multi_pack_layout)
+  DetNms nms;                                                           // one setting per call (mscnn_nms_params)
   DetSource src[kCascadeMaxOutputs];
   DetSeg seg[kSegsPerLaunch];
 };
@@ -331,7 +401,8 @@ __device__ __forceinline__ int det_image_lower_bound(const float* __restrict__ p
 }
 
 // one workgroup per segment: find the rows, transform + filter + sort them
-__global__ __launch_bounds__(kSortThreads) void det_seg_transform_sort_kernel(DetSegArgs a) {
+template <bool kThr>
+__device__ __forceinline__ void det_seg_transform_sort(const DetSegArgs& a) {
   const int j = blockIdx.x, s = a.s0 + j;
   const int img = s / a.slots_per_image;
   const DetSource& t = a.src[(s % a.slots_per_image) / a.classes_per_source];
@@ -355,19 +426,26 @@ __global__ __launch_bounds__(kSortThreads) void det_seg_transform_sort_kernel(De
   for (int k = 0; k < 4; ++k) { d.mean[k] = g.mean[k]; d.stdv[k] = g.stdv[k]; }
   d.proposal_thr = g.proposal_thr; d.ratio_h = g.ratio_h; d.ratio_w = g.ratio_w; d.org_h = g.org_h; d.org_w = g.org_w;
   d.cascade = t.cascade;
-  det_transform_sort(d, p.sbox, p.sprob, p.ssrc, p.tbox, p.tprob, p.cnt + SEG_N);
+  d.nms_thr = a.nms.thr; d.det_thr = t.cascade ? 0.f : a.nms.det_thr;
+  det_transform_sort<kThr>(d, p.sbox, p.sprob, p.ssrc, p.tbox, p.tprob, p.cnt + SEG_N);
 }
+__global__ __launch_bounds__(kSortThreads) void det_seg_transform_sort_kernel(DetSegArgs a) { det_seg_transform_sort<false>(a); }
+__global__ __launch_bounds__(kSortThreads) void det_seg_transform_sort_thr_kernel(DetSegArgs a) { det_seg_transform_sort<true>(a); }
 
 // grid (wpr, wpr, segments): blocks past a segment's own n exit at once
-__global__ __launch_bounds__(256) void det_seg_mask_kernel(DetSegArgs a) {
+template <bool kDnmMin>
+__device__ __forceinline__ void det_seg_mask(const DetSegArgs& a) {
   const int j = blockIdx.z, s = a.s0 + j;
   const DetMultiPtrs p = det_multi_ptrs(a, s);
-  det_mask_block(p.sbox, p.cnt[SEG_N], a.seg[j].nms_overlap, p.mask, a.wpr, blockIdx.y, blockIdx.x);
+  det_mask_block<kDnmMin>(p.sbox, p.cnt[SEG_N], a.seg[j].nms_overlap, p.mask, a.wpr, blockIdx.y, blockIdx.x);
 }
+__global__ __launch_bounds__(256) void det_seg_mask_kernel(DetSegArgs a) { det_seg_mask<false>(a); }
+__global__ __launch_bounds__(256) void det_seg_mask_min_kernel(DetSegArgs a) { det_seg_mask<true>(a); }
 
-// one workgroup per segment: greedy scan, emit into the segment's slot, its table entry {count (-1: rows over the bound), rows, row0, 0}
-__global__ __launch_bounds__(256) void det_seg_scan_emit_kernel(DetSegArgs a) {
-  extern __shared__ __attribute__((aligned(16))) u64 dyn_lds[];
+// one workgroup per segment: greedy scan (kGreedy) or column-OR, emit into the segment's slot, its table entry
+// {count (-1: rows over the bound), rows, row0, 0}
+template <bool kGreedy>
+__device__ __forceinline__ void det_seg_emit(const DetSegArgs& a, u64* dyn_lds) {
   const int j = blockIdx.x, s = a.s0 + j;
   const DetMultiPtrs p = det_multi_ptrs(a, s);
   const int row0 = p.cnt[SEG_ROW0], rows = p.cnt[SEG_ROWS];
@@ -375,7 +453,16 @@ __global__ __launch_bounds__(256) void det_seg_scan_emit_kernel(DetSegArgs a) {
   if (threadIdx.x == 0) { ent[1] = rows; ent[2] = row0; ent[3] = 0; }
   if (p.cnt[SEG_BAD]) { if (threadIdx.x == 0) ent[0] = -1; return; }
   const size_t slot = mscnn_multi_pack_slot(a.slots_per_image, row0, s % a.slots_per_image, rows);
-  det_scan_emit(p.mask, a.wpr, p.cnt[SEG_N], p.sbox, p.sprob, p.ssrc, a.dets + 5 * slot, a.ids + slot, ent, dyn_lds);
+  if (kGreedy) det_scan_emit(p.mask, a.wpr, p.cnt[SEG_N], p.sbox, p.sprob, p.ssrc, a.dets + 5 * slot, a.ids + slot, ent, dyn_lds);
+  else det_color_emit(p.mask, a.wpr, p.cnt[SEG_N], p.sbox, p.sprob, p.ssrc, a.dets + 5 * slot, a.ids + slot, ent, dyn_lds);
+}
+__global__ __launch_bounds__(256) void det_seg_scan_emit_kernel(DetSegArgs a) {
+  extern __shared__ __attribute__((aligned(16))) u64 dyn_lds[];
+  det_seg_emit<true>(a, dyn_lds);
+}
+__global__ __launch_bounds__(256) void det_seg_color_emit_kernel(DetSegArgs a) {
+  extern __shared__ __attribute__((aligned(16))) u64 dyn_lds[];
+  det_seg_emit<false>(a, dyn_lds);
 }
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -420,9 +507,59 @@ extern "C" int mscnn_decodebbox_fwd_f32(const float* bbox, const float* prior, f
 
 extern "C" size_t mscnn_detections_workspace_bytes(int R) { return det_layout(R).total; }
 
-static int detections_launch(const mscnn_detections_desc* desc, int cascade, float det_thr, const float* bbox_pred,
-                             const float* cls_pred, const float* props, int R, double* dets_out, int* ids_out,
+// NULL -> the defaults; every field checked, the offending value named.  *out is written whole (padding included: zero).
+extern "C" int mscnn_nms_params_resolve(const mscnn_nms_params* nms, mscnn_nms_params* out) {
+  MSCNN_REQUIRE(out, "nms params: null output");
+  mscnn_nms_params r;
+  std::memset(&r, 0, sizeof(r));
+  r.type = MSCNN_NMS_TYPE_MAXG; r.ovr_dnm = MSCNN_NMS_OVR_UNION; r.thr = -HUGE_VAL; r.det_thr = 0.f;
+  if (nms) {
+    MSCNN_REQUIRE(nms->type != MSCNN_NMS_TYPE_MS, "nms params: type %d ('ms') is not supported: it needs nonMaxSuprList", nms->type);
+    MSCNN_REQUIRE(nms->type != MSCNN_NMS_TYPE_COVER, "nms params: type %d ('cover') is not supported: its scores come from a BLAS "
+                  "mat-vec whose summation order is not pinned", nms->type);
+    MSCNN_REQUIRE(nms->type != MSCNN_NMS_TYPE_NONE, "nms params: type %d ('none') is not supported: read the rows without a final stage",
+                  nms->type);
+    MSCNN_REQUIRE(nms->type == MSCNN_NMS_TYPE_MAXG || nms->type == MSCNN_NMS_TYPE_MAX, "nms params: type %d (0 = 'maxg', 1 = 'max')",
+                  nms->type);
+    MSCNN_REQUIRE(nms->ovr_dnm == MSCNN_NMS_OVR_UNION || nms->ovr_dnm == MSCNN_NMS_OVR_MIN,
+                  "nms params: ovr_dnm %d (0 = 'union', 1 = 'min')", nms->ovr_dnm);
+    MSCNN_REQUIRE(!(nms->thr != nms->thr), "nms params: thr is NaN");
+    MSCNN_REQUIRE(nms->det_thr >= 0.f && nms->det_thr <= FLT_MAX, "nms params: det_thr %g (0 = off, else a finite positive probability)",
+                  (double)nms->det_thr);
+    r.type = nms->type; r.ovr_dnm = nms->ovr_dnm; r.thr = nms->thr; r.det_thr = nms->det_thr;
+  }
+  *out = r;
+  return MSCNN_OK;
+}
+// bbNms's own spelling of the knobs (type / ovrDnm strings, thr, maxn) -> mscnn_nms_params; NULL strings: the defaults
+extern "C" int mscnn_nms_params_from_names(const char* type, const char* ovr_dnm, double thr, double maxn, float det_thr,
+                                           mscnn_nms_params* out) {
+  MSCNN_REQUIRE(out, "nms params: null output");
+  mscnn_nms_params r;
+  std::memset(&r, 0, sizeof(r));
+  const char* const types[] = {"maxg", "max", "ms", "cover", "none"};
+  r.type = -1;
+  for (int k = 0; k < 5; ++k) if (!type ? k == 0 : std::strcmp(type, types[k]) == 0) r.type = k;
+  MSCNN_REQUIRE(r.type >= 0, "nms params: unknown type '%s' ('maxg' or 'max')", type);
+  r.ovr_dnm = !ovr_dnm || std::strcmp(ovr_dnm, "union") == 0 ? MSCNN_NMS_OVR_UNION : std::strcmp(ovr_dnm, "min") == 0 ? MSCNN_NMS_OVR_MIN : -1;
+  MSCNN_REQUIRE(r.ovr_dnm >= 0, "nms params: unknown ovr_dnm '%s' ('union' or 'min')", ovr_dnm);
+  MSCNN_REQUIRE(maxn == HUGE_VAL, "nms params: maxn %g: only maxn = inf (bbNms's default, no split-and-recurse) is supported", maxn);
+  r.thr = thr; r.det_thr = det_thr;
+  return mscnn_nms_params_resolve(&r, out);
+}
+static bool nms_is_default(const mscnn_nms_params& r) {
+  return r.type == MSCNN_NMS_TYPE_MAXG && r.ovr_dnm == MSCNN_NMS_OVR_UNION && r.thr == -HUGE_VAL && r.det_thr == 0.f;
+}
+static bool nms_has_thr(const mscnn_nms_params& r) { return r.thr != -HUGE_VAL || r.det_thr != 0.f; }
+static DetNms det_nms_of(const mscnn_nms_params& r) { return DetNms{r.thr, r.det_thr, r.type, r.ovr_dnm}; }
+
+static int detections_launch(const mscnn_detections_desc* desc, int cascade, float det_thr, const mscnn_nms_params* nms_in,
+                             const float* bbox_pred, const float* cls_pred, const float* props, int R, double* dets_out, int* ids_out,
                              int* count_out_dev, void* workspace, size_t workspace_bytes, void* stream) {
+  mscnn_nms_params nms;
+  if (int rc = mscnn_nms_params_resolve(nms_in, &nms)) return rc;
+  MSCNN_REQUIRE(!cascade || nms.det_thr == 0.f, "detections: nms params det_thr %g is the plain stage's: the cascade stage takes its "
+                "det_thr as an argument", (double)nms.det_thr);
   MSCNN_REQUIRE(desc && count_out_dev && workspace, "detections: null pointer");
   MSCNN_REQUIRE(R >= 0, "detections: R < 0");
   MSCNN_REQUIRE(desc->ncls >= 2 && desc->cls_id >= 1 && desc->cls_id <= desc->ncls, "detections: cls_id %d of %d",
@@ -453,10 +590,14 @@ static int detections_launch(const mscnn_detections_desc* desc, int cascade, flo
   for (int k = 0; k < 4; ++k) { a.mean[k] = desc->bbox_mean[k]; a.stdv[k] = desc->bbox_std[k]; }
   a.proposal_thr = cascade ? det_thr : desc->proposal_thr;
   a.cascade = cascade;
+  a.nms_thr = nms.thr; a.det_thr = cascade ? 0.f : nms.det_thr;
   // MATLAB: single op double -> single (the double operand is converted to single first)
   a.ratio_h = (float)desc->ratio_h; a.ratio_w = (float)desc->ratio_w;
   a.org_h = (float)desc->org_h; a.org_w = (float)desc->org_w;
   if (L.big) {
+    // (the tiled path of nms_large.h is the greedy scan over union overlaps, tile after tile)
+    MSCNN_REQUIRE(nms_is_default(nms), "detections: %d rows > %d run the tiled path, which has the default nms params only (got type %d, "
+                  "ovr_dnm %d, thr %g, det_thr %g)", R, kMaxK, nms.type, nms.ovr_dnm, nms.thr, (double)nms.det_thr);
     u64* keys = reinterpret_cast<u64*>(ws + L.keys);
     int* kidx = reinterpret_cast<int*>(ws + L.kidx);
     MSCNN_HIP_TRY(hipMemsetAsync(cnt, 0, 256, st));
@@ -476,12 +617,18 @@ static int detections_launch(const mscnn_detections_desc* desc, int cascade, flo
     MSCNN_POST_LAUNCH();
     return MSCNN_OK;
   }
-  det_transform_sort_kernel<<<1, kSortThreads, 0, st>>>(a, sbox, sprob, ssrc, tbox, tprob, cnt);
+  // (the default setting runs the three kernels it always ran; thr / det_thr, 'min' and 'max' each swap one of them)
+  if (nms_has_thr(nms)) det_transform_sort_thr_kernel<<<1, kSortThreads, 0, st>>>(a, sbox, sprob, ssrc, tbox, tprob, cnt);
+  else det_transform_sort_kernel<<<1, kSortThreads, 0, st>>>(a, sbox, sprob, ssrc, tbox, tprob, cnt);
   MSCNN_POST_LAUNCH();
-  det_mask_kernel<<<dim3(L.wpr, L.wpr), 256, 0, st>>>(sbox, cnt, desc->nms_overlap, mask, L.wpr);
+  if (nms.ovr_dnm == MSCNN_NMS_OVR_MIN) det_mask_min_kernel<<<dim3(L.wpr, L.wpr), 256, 0, st>>>(sbox, cnt, desc->nms_overlap, mask, L.wpr);
+  else det_mask_kernel<<<dim3(L.wpr, L.wpr), 256, 0, st>>>(sbox, cnt, desc->nms_overlap, mask, L.wpr);
   MSCNN_POST_LAUNCH();
-  det_scan_emit_kernel<<<1, 256, (size_t)2 * 64 * L.wpr * sizeof(u64), st>>>(mask, L.wpr, sbox, sprob, ssrc, dets_out, ids_out, cnt,
-                                                                                count_out_dev);
+  const size_t lds = (size_t)2 * 64 * L.wpr * sizeof(u64);
+  if (nms.type == MSCNN_NMS_TYPE_MAXG)
+    det_scan_emit_kernel<<<1, 256, lds, st>>>(mask, L.wpr, sbox, sprob, ssrc, dets_out, ids_out, cnt, count_out_dev);
+  else
+    det_color_emit_kernel<<<1, 256, lds, st>>>(mask, L.wpr, sbox, sprob, ssrc, dets_out, ids_out, cnt, count_out_dev);
   MSCNN_POST_LAUNCH();
   return MSCNN_OK;
 }
@@ -489,14 +636,28 @@ static int detections_launch(const mscnn_detections_desc* desc, int cascade, flo
 extern "C" int mscnn_detections_fwd(const mscnn_detections_desc* desc, const float* bbox_pred, const float* cls_pred,
                                     const float* props, int R, double* dets_out, int* ids_out, int* count_out_dev,
                                     void* workspace, size_t workspace_bytes, void* stream) {
-  return detections_launch(desc, 0, 0.f, bbox_pred, cls_pred, props, R, dets_out, ids_out, count_out_dev, workspace,
+  return detections_launch(desc, 0, 0.f, nullptr, bbox_pred, cls_pred, props, R, dets_out, ids_out, count_out_dev, workspace,
+                           workspace_bytes, stream);
+}
+
+extern "C" int mscnn_detections_nms_fwd(const mscnn_detections_desc* desc, const mscnn_nms_params* nms, const float* bbox_pred,
+                                        const float* cls_pred, const float* props, int R, double* dets_out, int* ids_out,
+                                        int* count_out_dev, void* workspace, size_t workspace_bytes, void* stream) {
+  return detections_launch(desc, 0, 0.f, nms, bbox_pred, cls_pred, props, R, dets_out, ids_out, count_out_dev, workspace,
                            workspace_bytes, stream);
 }
 
 extern "C" int mscnn_detections_cascade_fwd(const mscnn_detections_desc* desc, float det_thr, const float* boxes,
                                             const float* cls_prob, const float* props, int R, double* dets_out, int* ids_out,
                                             int* count_out_dev, void* workspace, size_t workspace_bytes, void* stream) {
-  return detections_launch(desc, 1, det_thr, boxes, cls_prob, props, R, dets_out, ids_out, count_out_dev, workspace,
+  return detections_launch(desc, 1, det_thr, nullptr, boxes, cls_prob, props, R, dets_out, ids_out, count_out_dev, workspace,
+                           workspace_bytes, stream);
+}
+
+extern "C" int mscnn_detections_cascade_nms_fwd(const mscnn_detections_desc* desc, float det_thr, const mscnn_nms_params* nms,
+                                                const float* boxes, const float* cls_prob, const float* props, int R, double* dets_out,
+                                                int* ids_out, int* count_out_dev, void* workspace, size_t workspace_bytes, void* stream) {
+  return detections_launch(desc, 1, det_thr, nms, boxes, cls_prob, props, R, dets_out, ids_out, count_out_dev, workspace,
                            workspace_bytes, stream);
 }
 
@@ -536,13 +697,15 @@ static DetSeg det_seg_of(const mscnn_detections_desc& d, int cascade, float det_
 }
 
 // desc[num_images * num_sources * C] (validated by the caller, as the workspace is): carve the pack, three launches per 32 segments
-static int det_seg_launch(const DetSource* src, int num_sources, const mscnn_detections_desc* desc, float det_thr, int num_images, int C,
-                          int R_all, int M, void* pack_dev, int cap, void* workspace, void* stream) {
+static int det_seg_launch(const DetSource* src, int num_sources, const mscnn_detections_desc* desc, float det_thr,
+                          const mscnn_nms_params& nms, int num_images, int C, int R_all, int M, void* pack_dev, int cap, void* workspace,
+                          void* stream) {
   hipStream_t st = as_stream(stream);
   const int S = num_images * num_sources * C;
   DetSegArgs a = {};
   a.R_all = R_all; a.slots_per_image = num_sources * C; a.classes_per_source = C; a.max_rows = M; a.wpr = (M + 63) / 64; a.cap = cap;
   a.num_segs = S;
+  a.nms = det_nms_of(nms);
   a.ws = static_cast<char*>(workspace);
   a.seg_stride_box = det_multi_seg_box_bytes(M); a.seg_stride_mask = det_multi_seg_mask_bytes(M);
   for (int o = 0; o < num_sources; ++o) a.src[o] = src[o];
@@ -555,19 +718,26 @@ static int det_seg_launch(const DetSource* src, int num_sources, const mscnn_det
     const int ns = S - s0 < kSegsPerLaunch ? S - s0 : kSegsPerLaunch;
     a.s0 = s0;
     for (int j = 0; j < ns; ++j) a.seg[j] = det_seg_of(desc[s0 + j], src[0].cascade, det_thr);
-    det_seg_transform_sort_kernel<<<ns, kSortThreads, 0, st>>>(a);
+    if (nms_has_thr(nms)) det_seg_transform_sort_thr_kernel<<<ns, kSortThreads, 0, st>>>(a);
+    else det_seg_transform_sort_kernel<<<ns, kSortThreads, 0, st>>>(a);
     MSCNN_POST_LAUNCH();
-    det_seg_mask_kernel<<<dim3(a.wpr, a.wpr, ns), 256, 0, st>>>(a);
+    if (nms.ovr_dnm == MSCNN_NMS_OVR_MIN) det_seg_mask_min_kernel<<<dim3(a.wpr, a.wpr, ns), 256, 0, st>>>(a);
+    else det_seg_mask_kernel<<<dim3(a.wpr, a.wpr, ns), 256, 0, st>>>(a);
     MSCNN_POST_LAUNCH();
-    det_seg_scan_emit_kernel<<<ns, 256, (size_t)2 * 64 * a.wpr * sizeof(u64), st>>>(a);
+    const size_t lds = (size_t)2 * 64 * a.wpr * sizeof(u64);
+    if (nms.type == MSCNN_NMS_TYPE_MAXG) det_seg_scan_emit_kernel<<<ns, 256, lds, st>>>(a);
+    else det_seg_color_emit_kernel<<<ns, 256, lds, st>>>(a);
     MSCNN_POST_LAUNCH();
   }
   return MSCNN_OK;
 }
 
-extern "C" int mscnn_detections_multi_fwd(const mscnn_detections_desc* desc, int num_images, int num_classes, const float* bbox_pred,
-                                          const float* cls_pred, const float* props, int R_all, int max_rows_per_image, void* pack_dev,
-                                          int cap, void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int mscnn_detections_multi_nms_fwd(const mscnn_detections_desc* desc, const mscnn_nms_params* nms_in, int num_images,
+                                              int num_classes, const float* bbox_pred, const float* cls_pred, const float* props,
+                                              int R_all, int max_rows_per_image, void* pack_dev, int cap, void* workspace,
+                                              size_t workspace_bytes, void* stream) {
+  mscnn_nms_params nms;
+  if (int rc = mscnn_nms_params_resolve(nms_in, &nms)) return rc;
   MSCNN_REQUIRE(desc && pack_dev && workspace, "detections_multi: null pointer");
   MSCNN_REQUIRE(num_images >= 1 && num_classes >= 1, "detections_multi: %d images x %d classes", num_images, num_classes);
   MSCNN_REQUIRE(R_all >= 1 && bbox_pred && cls_pred && props, "detections_multi: R_all = %d (BoxOutput emits at least one row)", R_all);
@@ -586,13 +756,24 @@ extern "C" int mscnn_detections_multi_fwd(const mscnn_detections_desc* desc, int
     return MSCNN_ERR_WORKSPACE;
   }
   const DetSource src = {bbox_pred, cls_pred, props, ncls, 0};
-  return det_seg_launch(&src, 1, desc, 0.f, num_images, num_classes, R_all, max_rows_per_image, pack_dev, cap, workspace, stream);
+  return det_seg_launch(&src, 1, desc, 0.f, nms, num_images, num_classes, R_all, max_rows_per_image, pack_dev, cap, workspace, stream);
 }
 
-extern "C" int mscnn_detections_cascade_multi_fwd(const mscnn_detections_desc* desc, float det_thr, int num_images, int num_outputs,
-                                                  int num_classes, const mscnn_cascade_output* outputs, int R_all,
-                                                  int max_rows_per_image, void* pack_dev, int cap, void* workspace,
-                                                  size_t workspace_bytes, void* stream) {
+extern "C" int mscnn_detections_multi_fwd(const mscnn_detections_desc* desc, int num_images, int num_classes, const float* bbox_pred,
+                                          const float* cls_pred, const float* props, int R_all, int max_rows_per_image, void* pack_dev,
+                                          int cap, void* workspace, size_t workspace_bytes, void* stream) {
+  return mscnn_detections_multi_nms_fwd(desc, nullptr, num_images, num_classes, bbox_pred, cls_pred, props, R_all, max_rows_per_image,
+                                        pack_dev, cap, workspace, workspace_bytes, stream);
+}
+
+extern "C" int mscnn_detections_cascade_multi_nms_fwd(const mscnn_detections_desc* desc, float det_thr, const mscnn_nms_params* nms_in,
+                                                      int num_images, int num_outputs, int num_classes,
+                                                      const mscnn_cascade_output* outputs, int R_all, int max_rows_per_image,
+                                                      void* pack_dev, int cap, void* workspace, size_t workspace_bytes, void* stream) {
+  mscnn_nms_params nms;
+  if (int rc = mscnn_nms_params_resolve(nms_in, &nms)) return rc;
+  MSCNN_REQUIRE(nms.det_thr == 0.f, "detections_cascade_multi: nms params det_thr %g is the plain stage's: the cascade stage takes its "
+                "det_thr as an argument", (double)nms.det_thr);
   MSCNN_REQUIRE(num_outputs >= 1 && num_outputs <= kCascadeMaxOutputs, "detections_cascade_multi: %d cascade outputs (1 .. %d)",
                 num_outputs, kCascadeMaxOutputs);
   MSCNN_REQUIRE(desc && outputs && pack_dev && workspace, "detections_cascade_multi: null pointer");
@@ -623,5 +804,14 @@ extern "C" int mscnn_detections_cascade_multi_fwd(const mscnn_detections_desc* d
   }
   DetSource src[kCascadeMaxOutputs];
   for (int o = 0; o < num_outputs; ++o) src[o] = DetSource{outputs[o].boxes, outputs[o].cls_prob, outputs[o].props, outputs[o].ncls, 1};
-  return det_seg_launch(src, num_outputs, desc, det_thr, num_images, num_classes, R_all, max_rows_per_image, pack_dev, cap, workspace, stream);
+  return det_seg_launch(src, num_outputs, desc, det_thr, nms, num_images, num_classes, R_all, max_rows_per_image, pack_dev, cap, workspace,
+                        stream);
+}
+
+extern "C" int mscnn_detections_cascade_multi_fwd(const mscnn_detections_desc* desc, float det_thr, int num_images, int num_outputs,
+                                                  int num_classes, const mscnn_cascade_output* outputs, int R_all,
+                                                  int max_rows_per_image, void* pack_dev, int cap, void* workspace,
+                                                  size_t workspace_bytes, void* stream) {
+  return mscnn_detections_cascade_multi_nms_fwd(desc, det_thr, nullptr, num_images, num_outputs, num_classes, outputs, R_all,
+                                                max_rows_per_image, pack_dev, cap, workspace, workspace_bytes, stream);
 }

@@ -49,7 +49,32 @@ class DetectionsDesc(C.Structure):
                 ("org_h", C.c_double), ("org_w", C.c_double), ("nms_overlap", C.c_double)]
 
 
+class NmsParams(C.Structure):
+    """mscnn_nms_params (include/mscnn_hip.h): bbNms's type / ovrDnm / thr and the plain stage's det_thr."""
+    _fields_ = [("type", C.c_int), ("ovr_dnm", C.c_int), ("thr", C.c_double), ("det_thr", C.c_float)]
+
+
 NMS_MODES = {"IOU": 0, "IOMU": 1, "IOFU": 2}
+
+
+def nms_params(type="maxg", ovr_dnm="union", thr=None, det_thr=0.0, maxn=None):
+    """bbNms's knobs as the scripts spell them -> NmsParams (mscnn_nms_params_from_names: 'ms', 'cover', 'none', a finite maxn and
+    out-of-range values are refused, naming the value).  thr None: bbNms's default, -inf."""
+    out = NmsParams()
+    _check(lib().mscnn_nms_params_from_names(None if type is None else str(type).encode(), None if ovr_dnm is None else str(ovr_dnm).encode(),
+                                             float("-inf") if thr is None else float(thr), float("inf") if maxn is None else float(maxn),
+                                             float(det_thr), C.byref(out)))
+    return out
+
+
+NMS_NULL = object()      # nms=NMS_NULL: the *_nms_fwd entry point with a NULL params pointer (nms=None: the entry point without params)
+
+
+def _nms_ref(nms):
+    """nms: NMS_NULL, an NmsParams or a dict of nms_params() keyword arguments -> the pointer argument (NMS_NULL: NULL)."""
+    if nms is NMS_NULL:
+        return None
+    return C.byref(nms if isinstance(nms, NmsParams) else nms_params(**nms))
 
 
 def lib():
@@ -164,6 +189,15 @@ def lib():
         L.mscnn_detections_cascade_multi_workspace_bytes.argtypes = [C.c_int, C.c_int]
         L.mscnn_detections_cascade_multi_fwd.argtypes = ([C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                                          C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p])
+        L.mscnn_nms_params_resolve.argtypes = [C.c_void_p, C.c_void_p]
+        L.mscnn_nms_params_from_names.argtypes = [C.c_char_p, C.c_char_p, C.c_double, C.c_double, C.c_float, C.c_void_p]
+        L.mscnn_detections_nms_fwd.argtypes = [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]
+        L.mscnn_detections_cascade_nms_fwd.argtypes = ([C.c_void_p, C.c_float] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4 +
+                                                       [C.c_size_t, C.c_void_p])
+        L.mscnn_detections_multi_nms_fwd.argtypes = ([C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3 +
+                                                     [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p])
+        L.mscnn_detections_cascade_multi_nms_fwd.argtypes = ([C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                              C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p])
         _lib = L
     return _lib
 
@@ -586,8 +620,9 @@ def _fill_desc(d, ncls, kw):
     d.nms_overlap = kw["nms_overlap"]
 
 
-def detections_cascade(boxes, cls_prob, props, cls_id, det_thr=0.0, ratios=(1.0, 1.0), org_hw=(375, 1242), nms_overlap=0.5):
-    """Final stage of the cascade drivers (run_cascademscnn.m:84-117) for one cascade stage's blobs."""
+def detections_cascade(boxes, cls_prob, props, cls_id, det_thr=0.0, ratios=(1.0, 1.0), org_hw=(375, 1242), nms_overlap=0.5, nms=None):
+    """Final stage of the cascade drivers (run_cascademscnn.m:84-117) for one cascade stage's blobs.  nms: None (the existing
+    entry point), an NmsParams or a dict of nms_params() arguments (mscnn_detections_cascade_nms_fwd)."""
     R = props.shape[0]
     d = DetectionsDesc()      # (of the desc, the cascade stage reads ncls, cls_id, ratio_*, org_* and nms_overlap)
     _fill_desc(d, cls_prob.shape[1], dict(cls_id=cls_id, ratios=ratios, org_hw=org_hw, nms_overlap=nms_overlap))
@@ -597,8 +632,12 @@ def detections_cascade(boxes, cls_prob, props, cls_id, det_thr=0.0, ratios=(1.0,
     count = torch.zeros(1, dtype=torch.int32, device=dev)
     wb = lib().mscnn_detections_workspace_bytes(R)
     ws = torch.empty(wb, dtype=torch.uint8, device=dev)
-    _check(lib().mscnn_detections_cascade_fwd(C.byref(d), C.c_float(det_thr), _dev(boxes), _dev(cls_prob), _dev(props), R,
-                                              _dev(dets), _dev(ids), _dev(count), _dev(ws), C.c_size_t(wb), _stream()))
+    if nms is None:
+        _check(lib().mscnn_detections_cascade_fwd(C.byref(d), C.c_float(det_thr), _dev(boxes), _dev(cls_prob), _dev(props), R,
+                                                  _dev(dets), _dev(ids), _dev(count), _dev(ws), C.c_size_t(wb), _stream()))
+    else:
+        _check(lib().mscnn_detections_cascade_nms_fwd(C.byref(d), C.c_float(det_thr), _nms_ref(nms), _dev(boxes), _dev(cls_prob), _dev(props),
+                                                      R, _dev(dets), _dev(ids), _dev(count), _dev(ws), C.c_size_t(wb), _stream()))
     D = int(count.item())
     return dets[:D], ids[:D]
 
@@ -664,7 +703,8 @@ def decode_bbox(bbox, prior, mean=(0, 0, 0, 0), std=(1, 1, 1, 1)):
 
 
 def detections(bbox_pred, cls_pred, props, cls_id, bbox_mean=(0, 0, 0, 0), bbox_std=(0.1, 0.1, 0.2, 0.2),
-               proposal_thr=-10.0, ratios=(1.0, 1.0), org_hw=(375, 1242), nms_overlap=0.5):
+               proposal_thr=-10.0, ratios=(1.0, 1.0), org_hw=(375, 1242), nms_overlap=0.5, nms=None):
+    """nms: None (the existing entry point), an NmsParams or a dict of nms_params() arguments (mscnn_detections_nms_fwd)."""
     R = props.shape[0]
     d = DetectionsDesc()
     _fill_desc(d, cls_pred.shape[1], dict(cls_id=cls_id, bbox_mean=bbox_mean, bbox_std=bbox_std, proposal_thr=proposal_thr, ratios=ratios,
@@ -675,8 +715,12 @@ def detections(bbox_pred, cls_pred, props, cls_id, bbox_mean=(0, 0, 0, 0), bbox_
     count = torch.zeros(1, dtype=torch.int32, device=dev)
     wb = lib().mscnn_detections_workspace_bytes(R)
     ws = torch.empty(wb, dtype=torch.uint8, device=dev)
-    _check(lib().mscnn_detections_fwd(C.byref(d), _dev(bbox_pred), _dev(cls_pred), _dev(props), R, _dev(dets), _dev(ids),
-                                      _dev(count), _dev(ws), wb, _stream()))
+    if nms is None:
+        _check(lib().mscnn_detections_fwd(C.byref(d), _dev(bbox_pred), _dev(cls_pred), _dev(props), R, _dev(dets), _dev(ids),
+                                          _dev(count), _dev(ws), wb, _stream()))
+    else:
+        _check(lib().mscnn_detections_nms_fwd(C.byref(d), _nms_ref(nms), _dev(bbox_pred), _dev(cls_pred), _dev(props), R, _dev(dets),
+                                              _dev(ids), _dev(count), _dev(ws), wb, _stream()))
     D = int(count.item())
     return dets[:D], ids[:D]
 
@@ -699,10 +743,12 @@ def _read_multi_pack(pack, S, K, R, cap, name):
     return out
 
 
-def detections_multi(bbox_pred, cls_pred, props, num_images, segments, max_rows_per_image=None):
+def detections_multi(bbox_pred, cls_pred, props, num_images, segments, max_rows_per_image=None, nms=None, raw_pack=False):
     """Every (image, class) segment in one pass (mscnn_detections_multi_fwd).  props: ROI rows grouped by image, image index in
     column 0; segments: num_images * C dicts of detections() keyword arguments (cls_id, ratios, org_hw, ...), image-major.
-    Returns [(dets[D,5], ids relative to row0, row0, rows)] per segment."""
+    nms: None (mscnn_detections_multi_fwd), an NmsParams or a dict of nms_params() arguments (mscnn_detections_multi_nms_fwd), one
+    setting for all segments.  Returns [(dets[D,5], ids relative to row0, row0, rows)] per segment; raw_pack: (that, the pack's
+    bytes as a numpy array -- it was zero-filled before the call)."""
     R = props.shape[0]
     S = len(segments)
     Cn = S // num_images
@@ -717,9 +763,14 @@ def detections_multi(bbox_pred, cls_pred, props, num_images, segments, max_rows_
     pack = torch.zeros(lib().mscnn_detections_multi_pack_bytes(S, cap), dtype=torch.uint8, device=dev)
     wb = lib().mscnn_detections_multi_workspace_bytes(S, M)
     ws = torch.empty(max(wb, 1), dtype=torch.uint8, device=dev)
-    _check(lib().mscnn_detections_multi_fwd(descs, num_images, Cn, _dev(bbox_pred), _dev(cls_pred), _dev(props), R, M, _dev(pack), cap,
-                                            _dev(ws), C.c_size_t(wb), _stream()))
-    return _read_multi_pack(pack, S, Cn, R, cap, "detections_multi")
+    if nms is None:
+        _check(lib().mscnn_detections_multi_fwd(descs, num_images, Cn, _dev(bbox_pred), _dev(cls_pred), _dev(props), R, M, _dev(pack), cap,
+                                                _dev(ws), C.c_size_t(wb), _stream()))
+    else:
+        _check(lib().mscnn_detections_multi_nms_fwd(descs, _nms_ref(nms), num_images, Cn, _dev(bbox_pred), _dev(cls_pred), _dev(props), R, M,
+                                                    _dev(pack), cap, _dev(ws), C.c_size_t(wb), _stream()))
+    out = _read_multi_pack(pack, S, Cn, R, cap, "detections_multi")
+    return (out, pack.cpu().numpy()) if raw_pack else out
 
 
 class CascadeOutput(C.Structure):
@@ -727,12 +778,12 @@ class CascadeOutput(C.Structure):
     _fields_ = [("boxes", C.c_void_p), ("cls_prob", C.c_void_p), ("props", C.c_void_p), ("ncls", C.c_int)]
 
 
-def detections_cascade_multi(outputs, num_images, segments, det_thr=0.0, max_rows_per_image=None):
+def detections_cascade_multi(outputs, num_images, segments, det_thr=0.0, max_rows_per_image=None, nms=None, raw_pack=False):
     """Every (image, cascade output, class) segment in one pass (mscnn_detections_cascade_multi_fwd).  outputs: [(boxes [R, 5],
     cls_prob [R, ncls], props [R, 5])] per cascade output, rows grouped by image (image index in column 0 of props); segments:
     num_images * O * C dicts of detections_cascade() keyword arguments (cls_id, ratios, org_hw, nms_overlap), image-major, then
     output, then class.  Returns [(dets[D,5], ids relative to row0, row0, rows)] per segment ((None, None, row0, rows): the image
-    has more rows than max_rows_per_image)."""
+    has more rows than max_rows_per_image).  nms, raw_pack: as detections_multi (mscnn_detections_cascade_multi_nms_fwd)."""
     O = len(outputs)
     S = len(segments)
     K = S // num_images
@@ -754,9 +805,14 @@ def detections_cascade_multi(outputs, num_images, segments, det_thr=0.0, max_row
     pack = torch.zeros(lib().mscnn_detections_multi_pack_bytes(S, cap), dtype=torch.uint8, device=dev)
     wb = lib().mscnn_detections_cascade_multi_workspace_bytes(S, M)
     ws = torch.empty(max(wb, 1), dtype=torch.uint8, device=dev)
-    _check(lib().mscnn_detections_cascade_multi_fwd(descs, C.c_float(det_thr), num_images, O, Cn, outs, R, M, _dev(pack), cap, _dev(ws),
-                                                    C.c_size_t(wb), _stream()))
-    return _read_multi_pack(pack, S, K, R, cap, "detections_cascade_multi")
+    if nms is None:
+        _check(lib().mscnn_detections_cascade_multi_fwd(descs, C.c_float(det_thr), num_images, O, Cn, outs, R, M, _dev(pack), cap, _dev(ws),
+                                                        C.c_size_t(wb), _stream()))
+    else:
+        _check(lib().mscnn_detections_cascade_multi_nms_fwd(descs, C.c_float(det_thr), _nms_ref(nms), num_images, O, Cn, outs, R, M, _dev(pack),
+                                                            cap, _dev(ws), C.c_size_t(wb), _stream()))
+    out = _read_multi_pack(pack, S, K, R, cap, "detections_cascade_multi")
+    return (out, pack.cpu().numpy()) if raw_pack else out
 
 
 # ---- health of the plane-GEMM kernel's stream-K hand-off (mscnn_hip.h) ----

@@ -30,6 +30,9 @@ struct mscnn_net {
   // detect_begin / detect_end: two pinned slots, each behind an event on the net's stream
   struct Slot { caffe::DeviceBuffer pack; void* host = nullptr; size_t bytes = 0; hipEvent_t done = nullptr; int cap = 0, handoff_errors = 0; } slot[2];
   int slot_head = 0, slot_tail = 0, slots_inflight = 0;
+  // mscnn_net_set_nms: bbNms's knobs for every detect call from now on (pNms at the top of the reference scripts)
+  mscnn_nms_params nms;
+  bool nms_set = false;                    // false: the defaults -- the calls hand the ops NULL and run what they always ran
   ~mscnn_net() {
     if (det_host) (void)hipHostFree(det_host);
     for (Slot& sl : slot) {
@@ -382,6 +385,34 @@ int mscnn_net_handoff_state(const mscnn_net* n, int* whole_tiles_forced) {
 int mscnn_net_set_layer_timing(mscnn_net* n, int on) { n->net->set_layer_timing(on != 0); return 0; }
 float mscnn_net_layer_ms(const mscnn_net* n, int l) { return n->net->layer_ms()[l]; }
 
+// What the detect calls hand to the ops: NULL for the defaults.  The cascade calls carry their own det_thr argument; a setting
+// whose det_thr (the plain stage's, mscnn_net.h) is set is refused there by name, as the ops refuse it -- never ignored.
+static const mscnn_nms_params* nms_arg(const mscnn_net* n, bool cascade) {
+  if (!n->nms_set) return nullptr;
+  CHECK(!cascade || n->nms.det_thr == 0.f) << "the net's nms setting has det_thr " << n->nms.det_thr << ", which is the plain stage's: the "
+                                              "cascade calls take det_thr as an argument (mscnn_net_set_nms with det_thr = 0)";
+  return &n->nms;
+}
+
+int mscnn_net_set_nms(mscnn_net* n, const mscnn_nms_params* nms) {
+  return guarded([&] {
+    CHECK(n != nullptr);
+    mscnn_nms_params r, dflt;
+    MSCNN_CHECK(mscnn_nms_params_resolve(nms, &r));      // (refuses 'ms' / 'cover' / 'none' and out-of-range fields, naming the value)
+    MSCNN_CHECK(mscnn_nms_params_resolve(nullptr, &dflt));
+    n->nms = r;
+    n->nms_set = std::memcmp(&r, &dflt, sizeof(r)) != 0;
+  });
+}
+
+int mscnn_net_get_nms(const mscnn_net* n, mscnn_nms_params* out) {
+  return guarded([&] {
+    CHECK(n && out);
+    if (n->nms_set) *out = n->nms;
+    else MSCNN_CHECK(mscnn_nms_params_resolve(nullptr, out));
+  });
+}
+
 size_t mscnn_net_detect_pack_bytes(int cap) {
   const size_t rows = (size_t)(cap > 0 ? cap : 1);
   return (16 + rows * (5 * sizeof(double) + sizeof(int)) + 15) / 16 * 16;
@@ -456,8 +487,9 @@ static void detect_into_pack(mscnn_net* n, const mscnn_detect_params* p, int cap
     const int words[3] = {R, cap, 0};
     MSCNN_CHECK(mscnn_store_words_i32(hdr + 1, words, 3, st));      // (one launch; three 4-byte memsets were three)
   }
-  MSCNN_CHECK(mscnn_detections_fwd(&d, bbox->gpu_data() + (size_t)row0 * per_row_box, cls->gpu_data() + (size_t)row0 * per_row_cls,
-                                   props->gpu_data() + (size_t)row0 * 6, R, dets, ids, hdr, ws, wb, st));
+  MSCNN_CHECK(mscnn_detections_nms_fwd(&d, nms_arg(n, false), bbox->gpu_data() + (size_t)row0 * per_row_box,
+                                       cls->gpu_data() + (size_t)row0 * per_row_cls, props->gpu_data() + (size_t)row0 * 6, R, dets, ids,
+                                       hdr, ws, wb, st));
   if (R_out) *R_out = R;
 }
 
@@ -668,6 +700,7 @@ static bool segments_into_pack(mscnn_net* n, const std::vector<SegSource>& src, 
   hipStream_t st = (hipStream_t)Caffe::stream();
   const mscnn_multi_pack_layout L = mscnn_multi_pack_layout_of(S, cap);
   const int bound = n->net->has_blob("proposals_score") ? per_image_row_bound(n, num_images, R_all) : R_all;
+  const mscnn_nms_params* nms = nms_arg(n, src[0].cascade);
   if (bound <= 4032) {
     const size_t wb = mscnn_detections_multi_workspace_bytes(S, bound);
     void* ws = n->det_ws.Reserve(wb);
@@ -676,14 +709,16 @@ static bool segments_into_pack(mscnn_net* n, const std::vector<SegSource>& src, 
       std::vector<mscnn_cascade_output> outs(O);
       for (int o = 0; o < O; ++o)
         outs[o] = mscnn_cascade_output{src[o].boxes->gpu_data(), src[o].cls->gpu_data(), src[o].props->gpu_data(), src[o].ncls};
-      MSCNN_CHECK(mscnn_detections_cascade_multi_fwd(desc.data(), det_thr, num_images, O, C, outs.data(), R_all, bound, pack, cap, ws, wb, st));
+      MSCNN_CHECK(mscnn_detections_cascade_multi_nms_fwd(desc.data(), det_thr, nms, num_images, O, C, outs.data(), R_all, bound, pack, cap, ws,
+                                                         wb, st));
     } else {
-      MSCNN_CHECK(mscnn_detections_multi_fwd(desc.data(), num_images, C, src[0].boxes->gpu_data(), src[0].cls->gpu_data(),
-                                             src[0].props->gpu_data(), R_all, bound, pack, cap, ws, wb, st));
+      MSCNN_CHECK(mscnn_detections_multi_nms_fwd(desc.data(), nms, num_images, C, src[0].boxes->gpu_data(), src[0].cls->gpu_data(),
+                                                 src[0].props->gpu_data(), R_all, bound, pack, cap, ws, wb, st));
     }
     *pack_out = pack;
     return pack == pack_at;
   }
+  // (the per-segment path: lists over 4032 rows run the tiled kernels, which refuse a non-default nms setting, naming the limit)
   std::vector<std::vector<int> > end(O);
   int max_rows = 0;
   for (int o = 0; o < O; ++o) {
@@ -715,8 +750,8 @@ static bool segments_into_pack(mscnn_net* n, const std::vector<SegSource>& src, 
     const float* boxes = t.boxes->gpu_data() + (size_t)r0 * (t.cascade ? 5 : 4 * t.ncls);
     const float* cls = t.cls->gpu_data() + (size_t)r0 * t.ncls;
     const float* props = t.props->gpu_data() + (size_t)r0 * (t.cascade ? 5 : 6);
-    if (t.cascade) MSCNN_CHECK(mscnn_detections_cascade_fwd(&desc[s], det_thr, boxes, cls, props, nr, dets + 5 * slot, ids + slot, ent, ws, wb, st));
-    else MSCNN_CHECK(mscnn_detections_fwd(&desc[s], boxes, cls, props, nr, dets + 5 * slot, ids + slot, ent, ws, wb, st));
+    if (t.cascade) MSCNN_CHECK(mscnn_detections_cascade_nms_fwd(&desc[s], det_thr, nms, boxes, cls, props, nr, dets + 5 * slot, ids + slot, ent, ws, wb, st));
+    else MSCNN_CHECK(mscnn_detections_nms_fwd(&desc[s], nms, boxes, cls, props, nr, dets + 5 * slot, ids + slot, ent, ws, wb, st));
   }
   *pack_out = pack;
   return false;
@@ -900,9 +935,9 @@ int mscnn_net_detect_cascade(mscnn_net* n, const mscnn_detect_params* p, float d
     const size_t rows = (size_t)(R > 0 ? R : 1), total = mscnn_net_detect_pack_bytes((int)rows);
     char* pack = static_cast<char*>(n->det_pack.Reserve(total));
     hipStream_t st = (hipStream_t)Caffe::stream();
-    MSCNN_CHECK(mscnn_detections_cascade_fwd(&d, det_thr, boxes->gpu_data(), prob->gpu_data(), props->gpu_data(), R,
-                                             reinterpret_cast<double*>(pack + 16), reinterpret_cast<int*>(pack + 16 + sizeof(double) * 5 * rows),
-                                             reinterpret_cast<int*>(pack), ws, wb, st));
+    MSCNN_CHECK(mscnn_detections_cascade_nms_fwd(&d, det_thr, nms_arg(n, true), boxes->gpu_data(), prob->gpu_data(), props->gpu_data(), R,
+                                                 reinterpret_cast<double*>(pack + 16), reinterpret_cast<int*>(pack + 16 + sizeof(double) * 5 * rows),
+                                                 reinterpret_cast<int*>(pack), ws, wb, st));
     ensure_det_host(n, total);
     HIP_CHECK(hipMemcpyAsync(n->det_host, pack, total, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));

@@ -10,6 +10,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmscnn_caffe.so")
 _lib = None
+_hip = None
 
 
 class NetError(RuntimeError):
@@ -22,12 +23,24 @@ class DetectParams(C.Structure):
                 ("nms_overlap", C.c_double)]
 
 
+class NmsParams(C.Structure):
+    """mscnn_nms_params (include/mscnn_net.h): bbNms's type / ovrDnm / thr and the plain stage's det_thr."""
+    _fields_ = [("type", C.c_int), ("ovr_dnm", C.c_int), ("thr", C.c_double), ("det_thr", C.c_float)]
+
+
+NMS_TYPES = ("maxg", "max", "ms", "cover", "none")      # (the last three exist to be refused by name)
+OVR_DNMS = ("union", "min")
+
+
 def lib():
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise NetError(f"{LIB_PATH} not built: run `python -c 'import __graft_entry__ as g; g.build()'`")
-        C.CDLL(os.path.join(_HERE, "libmscnn_hip.so"), mode=C.RTLD_GLOBAL)
+        global _hip
+        _hip = C.CDLL(os.path.join(_HERE, "libmscnn_hip.so"), mode=C.RTLD_GLOBAL)
+        _hip.mscnn_last_error.restype = C.c_char_p
+        _hip.mscnn_nms_params_from_names.argtypes = [C.c_char_p, C.c_char_p, C.c_double, C.c_double, C.c_float, C.c_void_p]
         L = C.CDLL(LIB_PATH)
         for f in ("mscnn_net_last_error", "mscnn_net_layer_name", "mscnn_net_layer_type", "mscnn_net_layer_bottom",
                   "mscnn_net_layer_top", "mscnn_net_layer_kernel", "mscnn_net_layer_dtype", "mscnn_net_layer_param_text", "mscnn_net_blob_name", "mscnn_net_output_name"):
@@ -65,6 +78,7 @@ def lib():
             "mscnn_net_get_blob": [vp, cs, vp, C.c_size_t, vp], "mscnn_net_blob_device_ptr": [vp, cs],
             "mscnn_net_forward": [vp], "mscnn_net_forward_from_to": [vp, ci, ci], "mscnn_net_reshape": [vp],
             "mscnn_net_set_layer_timing": [vp, ci], "mscnn_net_layer_ms": [vp, ci],
+            "mscnn_net_set_nms": [vp, vp], "mscnn_net_get_nms": [vp, vp],
             "mscnn_net_detect": [vp, vp, vp, vp, ci, vp, vp],
             "mscnn_net_detect_cascade": [vp, vp, C.c_float, cs, cs, cs, vp, vp, ci, vp, vp],
             "mscnn_net_detect_pack_bytes": [ci], "mscnn_net_detect_device": [vp, vp, ci, vp],
@@ -334,6 +348,27 @@ class Net:
 
     def layer_ms(self):
         return [lib().mscnn_net_layer_ms(self._h, i) for i in range(len(self.layer_names))]
+
+    def set_nms(self, type="maxg", ovr_dnm="union", thr=None, det_thr=0.0, maxn=None):
+        """mscnn_net_set_nms: bbNms's knobs for every detect call on this net from now on, spelled as in the reference scripts
+        (pNms.type = 'maxg' | 'max', pNms.ovrDnm = 'union' | 'min'; thr None = bbNms's default -inf; det_thr: the plain stage's,
+        widerface/run_mscnn_detection.m:139-143, 0 = off).  set_nms(None) restores the defaults.  'ms', 'cover', 'none', a finite
+        maxn and out-of-range values are refused, naming the value; the setting then stays as it was."""
+        if type is None:
+            _check(lib().mscnn_net_set_nms(self._h, None))
+            return
+        L = lib()
+        p = NmsParams()      # (the names, maxn and the ranges are checked in one place: mscnn_nms_params_from_names)
+        if _hip.mscnn_nms_params_from_names(str(type).encode(), str(ovr_dnm).encode(), float("-inf") if thr is None else float(thr),
+                                            float("inf") if maxn is None else float(maxn), float(det_thr), C.byref(p)) != 0:
+            raise NetError("set_nms: " + _hip.mscnn_last_error().decode())
+        _check(L.mscnn_net_set_nms(self._h, C.byref(p)))
+
+    def get_nms(self):
+        """mscnn_net_get_nms: the current setting as set_nms's keyword arguments (thr None = -inf)."""
+        p = NmsParams()
+        _check(lib().mscnn_net_get_nms(self._h, C.byref(p)))
+        return dict(type=NMS_TYPES[p.type], ovr_dnm=OVR_DNMS[p.ovr_dnm], thr=None if p.thr == float("-inf") else p.thr, det_thr=p.det_thr)
 
     @staticmethod
     def _params(cls_id, ratios, org_hw, bbox_mean, bbox_std, proposal_thr, nms_overlap):

@@ -8,7 +8,10 @@ for bit.  Usage: python tools/bench_final_stage.py [--steps 30] [--warmup 5] [--
 against one mscnn_net_detect_cascade_multi.  At B = 1 the per-call form is mscnn_net_detect_cascade (like for like).  At B > 1
 mscnn_net_detect_cascade has no per-image form (it treats the blob as one list), so the per-call form there is a loop of per-range
 op calls (hipapi.detections_cascade on each image's rows of the device blobs, row ranges read from the one-pass result outside the
-timed region, each call ending with its detections on the host)."""
+timed region, each call ending with its detections on the host).
+
+--nms-type max / --ovr-dnm min set bbNms's knobs on the net first (Net.set_nms; both forms honour the setting, so the bit-for-bit check
+between them stays) and name the setting in the table's header; without them no set_nms call is made at all."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -28,16 +31,28 @@ CASCADE_CASES = {   # name: model, batch, classes, original image size
 }
 
 
+def nms_set(a):
+    return (a.nms_type, a.ovr_dnm) != ("maxg", "union")
+
+
+def nms_label(a):
+    return f", nms type {a.nms_type} / ovr_dnm {a.ovr_dnm}" if nms_set(a) else ""
+
+
 def cascade_leg(a):
     import torch
     from mscnn_amd import hipapi
     print(f"# cascade final stage per step, host wall ms (median over {a.steps} steps after {a.warmup} warm-up), regime {a.regime}, "
-          "outputs 1st,2nd,3rd")
+          f"outputs 1st,2nd,3rd{nms_label(a)}")
     print(f"# {'case':22s} {'B':>2s} {'O':>2s} {'C':>2s} {'ROIs':>6s} {'dets':>5s} {'per-call ms':>12s} {'calls':>5s} {'one-pass ms':>12s} {'calls':>5s} {'saved ms':>9s}")
     for name in a.case or list(CASCADE_CASES):
         model, B, classes, org = CASCADE_CASES[name]
         n = mnet.Net(prototxt_text=zoo.prototxt(model, batch=B))
         synth.load_into(n, a.regime)
+        if nms_set(a):
+            if B > 1:
+                sys.exit("--nms-type / --ovr-dnm with a batched cascade case: the per-call form there is the op without the net's setting")
+            n.set_nms(type=a.nms_type, ovr_dnm=a.ovr_dnm)
         _, _, H, W = n.blob_shape("data")
         frames = [np.concatenate([synth.frame(H, W, seed=1701 + 13 * i + b, org_hw=org) for b in range(B)], 0) for i in range(2)]
         kw = dict(ratios=(H / float(org[0]), W / float(org[1])), org_hw=org)
@@ -95,6 +110,8 @@ ap.add_argument("--case", nargs="*", default=None)
 ap.add_argument("--regime", default="mid")
 ap.add_argument("--form", choices=("both", "call", "multi"), default="both",
                 help="one form alone (under a tracer: the launches and synchronisations of that form per step)")
+ap.add_argument("--nms-type", default="maxg", choices=("maxg", "max"), help="bbNms's type for both forms (Net.set_nms)")
+ap.add_argument("--ovr-dnm", default="union", choices=("union", "min"), help="bbNms's overlap denominator for both forms")
 a = ap.parse_args()
 if a.cascade:
     cascade_leg(a)
@@ -102,7 +119,7 @@ if a.cascade:
 if a.case is None:
     a.case = list(CASES)
 
-print(f"# final stage per step, host wall ms (median over {a.steps} steps after {a.warmup} warm-up), regime {a.regime}")
+print(f"# final stage per step, host wall ms (median over {a.steps} steps after {a.warmup} warm-up), regime {a.regime}{nms_label(a)}")
 print(f"# {'case':20s} {'B':>2s} {'C':>2s} {'ROIs':>6s} {'dets':>5s} {'per-call ms':>12s} {'calls':>5s} {'one-pass ms':>12s} {'calls':>5s} {'saved ms':>9s}")
 for name in a.case:
     model, B, dtype, classes, org = CASES[name]
@@ -110,6 +127,8 @@ for name in a.case:
     synth.load_into(n, a.regime)
     if dtype != "f32":
         n.set_precision(dtype)
+    if nms_set(a):
+        n.set_nms(type=a.nms_type, ovr_dnm=a.ovr_dnm)
     _, _, H, W = n.blob_shape("data")
     frames = [np.concatenate([synth.frame(H, W, seed=1701 + 13 * i + b, org_hw=org) for b in range(B)], 0) for i in range(2)]
     kw = dict(ratios=(H / float(org[0]), W / float(org[1])), org_hw=org)

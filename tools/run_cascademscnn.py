@@ -8,6 +8,7 @@ detections/<comp_id>_<class>_<output>_results.txt written as dlmwrite does (:148
   python tools/run_cascademscnn.py --prototxt mscnn_deploy.prototxt --weights model.caffemodel --images /KITTI/testing/image_2
          [--outputs 1st,2nd,3rd] [--cls-ids 2] [--det-thr 0.05] [--nms-overlap 0.5] [--batch B] [--precision f32|f16x3|f16]
          [--out detections] [--comp-id cascade_mscnn] [--names bg,car,van,truck,tram] [--limit N]
+         [--nms-type maxg|max] [--ovr-dnm union|min] [--nms-thr T]      # pNms.type / pNms.ovrDnm / bbNms's thr (Net.set_nms)
   python tools/run_cascademscnn.py --model kitti_car/cascade-mscnn-7s-576-2x --synthetic 8 --batch 2      # no dataset / weights at
                                                             # hand: the generated deploy net, seeded weights, synthetic frames
   python tools/run_cascademscnn.py --model widerface/cascade-mscnn-12s-align --images faces/ --orig-size [--max-size 3072]
@@ -76,6 +77,9 @@ def parse_args(argv=None):
     ap.add_argument("--names", default="")
     ap.add_argument("--det-thr", type=float, default=0.0, help="> 0: drop detections under this probability before the NMS (:122-124)")
     ap.add_argument("--nms-overlap", type=float, default=0.5)
+    ap.add_argument("--nms-type", default="maxg", choices=["maxg", "max"], help="pNms.type (bbNms.m: greedy or not)")
+    ap.add_argument("--ovr-dnm", default="union", choices=["union", "min"], help="pNms.ovrDnm: the overlap's denominator")
+    ap.add_argument("--nms-thr", type=float, default=None, help="bbNms's thr: drop rows with prob <= this before the NMS (default -inf)")
     ap.add_argument("--precision", default="f32", choices=["f32", "f16x3", "f16"])
     ap.add_argument("--limit", type=int, default=0); ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--batch", type=int, default=1, help="frames per forward")
@@ -116,6 +120,7 @@ def main(argv=None):
             kw["max_nms_num"] = a.max_nms_num
         text = zoo.prototxt(a.model, **kw)
     net = mnet.Net(prototxt_text=text, device=a.device)
+    net.set_nms(type=a.nms_type, ovr_dnm=a.ovr_dnm, thr=a.nms_thr)      # sticky, like pNms at the top of the script
     if a.weights:
         net.load_caffemodel(a.weights)
     else:

@@ -9,6 +9,8 @@ examples/kitti_result/writeDetForEval.m.
   python tools/run_mscnn_detection.py --prototxt mscnn_deploy.prototxt --weights model.caffemodel --images /KITTI/testing/image_2
          [--out detections] [--comp-id kitti_7s_576] [--cls-ids 2] [--names bg,car,van,truck,tram] [--precision f32|f16x3|f16]
          [--labels-dir results/data] [--limit N] [--batch B]
+         [--nms-type maxg|max] [--ovr-dnm union|min] [--nms-thr T] [--det-thr T]      # pNms.type / pNms.ovrDnm / bbNms's thr, and
+                                                             # the det_thr of the WiderFace plain flow (Net.set_nms, once per run)
   python tools/run_mscnn_detection.py --model kitti_car/mscnn-7s-576 --synthetic 8      # no dataset / weights at hand: the generated
                                                                                         # deploy net, seeded weights, synthetic frames
 
@@ -69,7 +71,7 @@ def names_for(prototxt_text, names_arg):
     return {5: KITTI_NAMES["car"], 3: KITTI_NAMES["ped_cyc"], 2: KITTI_NAMES["caltech"]}.get(n, ["bg"] + [f"class{i}" for i in range(1, n)])
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--prototxt"); ap.add_argument("--weights", help=".caffemodel (new or V1 layout) or .h5 snapshot")
     ap.add_argument("--model", help="a deploy net of mscnn_amd.zoo instead of --prototxt (e.g. kitti_car/mscnn-7s-576)")
@@ -82,14 +84,25 @@ def main(argv=None):
     ap.add_argument("--proposal-thr", type=float, default=-10.0); ap.add_argument("--nms-overlap", type=float, default=0.5)
     ap.add_argument("--limit", type=int, default=0); ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--batch", type=int, default=1, help="frames per forward (> 1: Net.set_images + one detect_multi per group)")
+    ap.add_argument("--nms-type", default="maxg", choices=["maxg", "max"], help="pNms.type (bbNms.m: greedy or not)")
+    ap.add_argument("--ovr-dnm", default="union", choices=["union", "min"], help="pNms.ovrDnm: the overlap's denominator")
+    ap.add_argument("--nms-thr", type=float, default=None, help="bbNms's thr: drop rows with prob <= this before the NMS (default -inf)")
+    ap.add_argument("--det-thr", type=float, default=0.0, help="> 0: drop rows under this probability before the NMS "
+                    "(widerface/run_mscnn_detection.m:139-143)")
     a = ap.parse_args(argv)
     if not (a.prototxt or a.model) or not (a.images or a.synthetic):
         ap.error("need --prototxt or --model, and --images or --synthetic N")
+    return a
+
+
+def main(argv=None):
+    a = parse_args(argv)
 
     import torch
     from mscnn_amd import kitti, net as mnet, synth, zoo
     text = open(a.prototxt).read() if a.prototxt else zoo.prototxt(a.model)
     net = mnet.Net(prototxt_text=text, device=a.device)
+    net.set_nms(type=a.nms_type, ovr_dnm=a.ovr_dnm, thr=a.nms_thr, det_thr=a.det_thr)      # sticky, like pNms at the top of the script
     if a.weights:
         net.load_caffemodel(a.weights)              # net.cpp:788-795: ".h5" -> HDF5 snapshot, else binary NetParameter
     else:
