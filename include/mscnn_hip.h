@@ -101,7 +101,7 @@ typedef struct {
    * slower than the head kernel: opt-in), bit 5 = never that form, bit 6 = AUTO keeps F(3x3,3x3) where it would take F(4x4,3x3),
    * bit 7 = the Winograd plane GEMMs on the round-2 igemm kernel instead of wgemm.hip's, bit 8 = the scalar (host-checked)
    * F(4x4,3x3) transform kernels instead of the vectorised ones and the generic F(3x3,3x3) output transform on ROI maps instead of the LDS-staged one, bit 9 = never / bit 10 = wherever legal: proposal heads with the
-   * kernel's columns folded into M (KH x 1 convolution with KW * Cout channels + shift-and-add), bit 11 = a Cin = 3 layer (conv1_1) on the MFMA igemm kernel instead of its VALU kernel, bit 12 = F(4x4,3x3) input transform with one tile per lane instead of two, bit 15 = a 3x3 / pad 1 layer with 64 output channels on whole 4 x 128 tiles (conv1_2) stays on the igemm kernel instead of the ring kernel of wconv.hip (bit-identical for whole tiles; A/B, second witness), bit 16 = (round 5) a 3x3 / pad 1 layer with 64 output channels on a full-resolution map (conv1_2: whole 8 x 32 blocks, >= 512 of them) stays on the direct ring kernel of wconv.hip instead of the one-launch Winograd F(2x2,3x3) kernel of wf2conv.hip that AUTO takes there (A/B, the direct witness; tune_variant 403 also plans smaller maps on it: tests), bit 14 = inverts the wave priority of the direct MFMA kernel's tile epilogue (raised by default on the 64 x 256 3x3 tile = conv1_2 only), bit 13 = (witness build only, `make -C mscnn_amd/csrc witness`; ignored by the product library) proposal heads on the packed-FMA kernel of tools/micro/headvalu.hip instead of the M = 4 MFMA kernel (headconv.hip); tune_variant with WINO_F3_X3: 1 = 128-row, 2 = 256-row GEMM tiles;
+   * kernel's columns folded into M (KH x 1 convolution with KW * Cout channels + shift-and-add), bit 11 = a Cin = 3 layer (conv1_1) on the MFMA igemm kernel instead of its VALU kernel, bit 12 = F(4x4,3x3) input transform with one tile per lane instead of two, bit 15 = a 3x3 / pad 1 layer with 64 output channels on whole 4 x 128 tiles (conv1_2) stays on the igemm kernel instead of the ring kernel of wconv.hip (bit-identical for whole tiles; A/B, second witness), bit 16 = (round 5) a 3x3 / pad 1 layer with 64 output channels on a full-resolution map (conv1_2: whole 8 x 32 blocks, >= 512 of them) stays on the direct ring kernel of wconv.hip instead of the one-launch Winograd F(2x2,3x3) kernel of wf2conv.hip that AUTO takes there (A/B, the direct witness; tune_variant 403 also plans smaller maps on it: tests), bit 14 = inverts the wave priority of the direct MFMA kernel's tile epilogue (raised by default on the 64 x 256 3x3 tile = conv1_2 only), bit 13 = (witness build only, `make -C mscnn_amd/csrc witness`; ignored by the product library) proposal heads on the packed-FMA kernel of tools/micro/headvalu.hip instead of the M = 4 MFMA kernel (headconv.hip), bit 17 = a small-map F(3x3,3x3) plan whose planes would be ragged (mscnn_conv2d_plan_plane_columns) keeps uniform planes (A/B; bit-identical under whole tiles); tune_variant with WINO_F3_X3: 1 = 128-row, 2 = 256-row GEMM tiles;
    * tune_variant 300 + v with a Winograd algo: wgemm tile variant v (1: 256 x 128, 2: 128 x 256, 3: 128 x 128, 4: 256 x 96, 5: 256 x 160; + 256 forces the
    * stream-K split, + 512 whole tiles).  Proposal heads (headconv.hip, round 5): tune_variant 500 / 501 = full / half channel chunks
    * whatever the map (AUTO: half chunks on maps of <= 16 tiles of 16 x 32 pixels and for the 5-row kernels everywhere); tune_grid > 0 = that many workgroups, clamped to the
@@ -131,8 +131,16 @@ MSCNN_API double mscnn_conv2d_plan_flops(const mscnn_conv_plan* plan);
 /* "f32" | "f16" | "f16x3": the arithmetic type of the plan's MFMA operands (accumulation is fp32 in all of them). */
 MSCNN_API const char* mscnn_conv2d_plan_dtype(const mscnn_conv_plan* plan);
 /* FLOPs the MFMA pipe really executes for the real (unpadded) problem: equal to the algorithmic count for the direct
- * kernels, 2 * planes * Cout * Cin * tiles for the Winograd forms (25/81 resp. 16/36 of it on exactly tiled planes). */
+ * kernels, 2 * planes * Cout * Cin * tiles for the Winograd forms (25/81 resp. 16/36 of it on exactly tiled planes);
+ * 2 * Cout * Cin * (sum of the planes' columns) where the planes are ragged. */
 MSCNN_API double mscnn_conv2d_plan_executed_flops(const mscnn_conv_plan* plan);
+/* Live GEMM columns of each transform plane of a Winograd plan: cols[p], p < min(n, planes); returns the number of planes (0: not
+ * a Winograd plan).  N * tiles_h * tiles_w for every plane, except on a ragged plan: a small-map (H * W <= 64) fp32 F(3x3,3x3)
+ * plan on the wgemm kernel, without a pooled output, whose output is no whole number of 3 x 3 tiles.  There plane (i, j) has its
+ * own tile grid (tiles_h - [i == 4 and Ho % 3 != 0]) x (tiles_w - [j == 4 and Wo % 3 != 0]): plane index 4 feeds only a tile's
+ * third output row / column, and the products no kept output reads are not computed (81 of 100 per ROI for 5 x 5 outputs).
+ * tune_flags bit 17 and bit 7 keep uniform planes. */
+MSCNN_API int mscnn_conv2d_plan_plane_columns(const mscnn_conv_plan* plan, int* cols, int n);
 /* Roofline accounting: with profiling on, every forward brackets the plan's stages with HIP events on the call's stream;
  * mscnn_conv2d_plan_stage_ms waits for the last forward and returns {input transform, MFMA GEMM kernel(s) incl. the
  * stream-K fix-up, output transform} in milliseconds (direct / head kernels: {0, total, 0}). */
@@ -214,6 +222,12 @@ MSCNN_API unsigned long long mscnn_wgemm_handoff_event(void);
 MSCNN_API void mscnn_wgemm_force_whole_tiles(int on);
 MSCNN_API int mscnn_wgemm_whole_tiles_forced(void);
 MSCNN_API void mscnn_debug_wgemm_handoff_fault(int drop_publish, unsigned spin_limit);
+/* Host-side replay of the plane GEMM's schedule for a Winograd plan on the wgemm kernel (tests; runs nothing on a device): every
+ * segment the persistent grid's slots are handed, in slot order, as rows {slot, plane, column tile, row tile, k0, k1, part} of 7
+ * ints through the kernel's own tile decode (part -1: whole tile); whole_tiles != 0: as after mscnn_wgemm_force_whole_tiles.
+ * info[8] = {tiles, MT, KI, G, full_q, planes, BN, ragged}.  Returns the number of segments (rows == NULL: count only), -1 when
+ * max_rows is too small or the plan has no such GEMM. */
+MSCNN_API long mscnn_debug_wgemm_schedule(const mscnn_conv_plan* plan, int whole_tiles, int* rows, long max_rows, int info[8]);
 /* fp16-operand InnerProduct (the counterpart of MSCNN_CONV_ALGO_F16; no reference counterpart): w16 = the weights converted
  * once to fp16 [N][K] (mscnn_inner_product_pack_f16, N * K * 2 bytes), x rounded to fp16 on its way into LDS, fp32 accumulate.
  * Needs N >= 64 and K % 8 == 0 (mscnn_inner_product_f16_supported); smaller layers stay on the fp32 entry point. */

@@ -34,6 +34,7 @@
 #include "wino_x3.h"
 #include "wgemm.h"
 #include "roipool_wino.h"
+#include "wino33_device.h"
 #include "conv_c3.h"
 #include "wconv.h"
 #include "wf2conv.h"
@@ -1033,6 +1034,11 @@ struct mscnn_conv_plan {
   mscnn::Wf2Plan wf;
   int wino_m = 2;        // output tile edge: 2 = F(2x2,3x3) (16 planes), 3 = F(3x3,3x3) (25 planes; small ROI maps)
   int tiles_h = 0, tiles_w = 0, T_pad = 0;
+  // Ragged planes (wino33_device.h; != 0: the grid description handed to the transform kernels and the per-plane column counts of
+  // wg): a small-map F(3x3,3x3) plan on the wgemm kernel whose output is no whole number of 3 x 3 tiles drops the (plane, tile)
+  // products no kept output reads -- 81 of 100 per ROI for roi_c1's 5 x 5 outputs.  Decided from the shape alone (tune_flags bit 17
+  // keeps uniform planes, A/B); V and M keep their shape and strides, so the workspace is that of the uniform plan.
+  int ragged = 0;
   // split-fp16 form of the F(3x3,3x3) path (MSCNN_CONV_ALGO_WINO_F3_X3, wino_x3.hip): x3.BM > 0, wino == nullptr.
   // Workspace layout: [4 KB: max |x| slots, used when nobody hands the bound over][V16][M: 25 x Cout x T_pad floats]
   mscnn::X3Plan x3;
@@ -1133,6 +1139,9 @@ static bool head_gemm_plan(mscnn_conv_plan* p) {
 // conv4_2 (256) 407 vs 617 -> threshold 100.
 // desc.algo: DIRECT disables the path, WINO_F2 / WINO_F3 force that form wherever it is legal (tests, A/B runs, and the
 // per-layer numerical fall-back of the host runtime: Net::CalibrateNumerics).
+// The fused 2x2 max pooling of a Winograd plan's output transform (mscnn_conv2d_plan_can_pool; a ragged plan must have none)
+static bool wino_can_pool(int m, int tiles_h, int tiles_w, int H) { return m == 2 || m == 4 || (tiles_h % 2 == 0 && tiles_w % 2 == 0 && H > 8); }
+
 static bool wino_plan(mscnn_conv_plan* p) {
   const mscnn_conv_desc& d = p->d;
   const int algo = tune_env("MSCNN_CONV_ALGO", d.algo);
@@ -1202,11 +1211,35 @@ static bool wino_plan(mscnn_conv_plan* p) {
   p->ws_bytes = (size_t)planes * ((size_t)d.Cin + d.Cout) * T_pad * sizeof(float) + g->ws_bytes;
   // the plane GEMMs on wgemm.hip's kernel where it covers the shape (F(3x3,3x3) / F(4x4,3x3); Cin % 32 == 0, Cout % 32 == 0)
   p->use_wg = false;
-  if (m >= 3 && !(d.tune_flags & 128) && mscnn::wgemm_plan(planes, d.Cout, d.Cin, (int)T, (d.tune_variant >= 300 && d.tune_variant < 1100) ? d.tune_variant - 300 : 0, &p->wg)) {
+  p->ragged = 0;
+  const int wg_variant = (d.tune_variant >= 300 && d.tune_variant < 1100) ? d.tune_variant - 300 : 0;
+  if (m >= 3 && !(d.tune_flags & 128) && mscnn::wgemm_plan(planes, d.Cout, d.Cin, (int)T, wg_variant, &p->wg)) {
     p->use_wg = true;
     p->T_pad = p->wg.T_pad;
     p->packed_bytes = p->wg.packed_bytes;
     p->ws_bytes = (size_t)planes * ((size_t)d.Cin + d.Cout) * p->wg.T_pad * sizeof(float) + p->wg.ws_bytes;
+    // Ragged planes: the maps that run the small-map transform kernels (wino33_input_kernel / the fused ROI pooling in,
+    // wino33_output_roi_kernel out), no pooled output, an output that is no whole number of tiles.  The shape decides, not the
+    // transform kernels' A/B bit 8: both sides of that comparison run the same GEMM schedule.
+    const int mode = mscnn::wino33_ragged_mode(p->Ho, p->Wo);
+    if (m == 3 && d.H * d.W <= mscnn::kWino33SmallMapHW && !wino_can_pool(m, th, tw, d.H) && mode != 0) {
+      int cols[25];
+      for (int i = 0; i < 5; ++i)
+        for (int j = 0; j < 5; ++j) cols[i * 5 + j] = d.N * mscnn::wino33_plane_th(mode, i, th) * mscnn::wino33_plane_tw(mode, j, tw);
+      mscnn::WgemmPlan rg;
+      if (mscnn::wgemm_plan(planes, d.Cout, d.Cin, (int)T, wg_variant, &rg, cols)) {
+        // ONE workspace and packed size for the shape, whichever of the two plans runs (the tile shape -- T_pad -- and the
+        // whole-or-split choice follow the tile count): the larger of the two
+        const size_t ws_r = (size_t)planes * ((size_t)d.Cin + d.Cout) * rg.T_pad * sizeof(float) + rg.ws_bytes;
+        if (ws_r > p->ws_bytes) p->ws_bytes = ws_r;
+        if (rg.packed_bytes > p->packed_bytes) p->packed_bytes = rg.packed_bytes;
+        if (!(d.tune_flags & 131072)) {      // bit 17: keep uniform planes (A/B runs, the identity test)
+          p->wg = rg;
+          p->T_pad = rg.T_pad;
+          p->ragged = mode;
+        }
+      }
+    }
   }
   return true;
 }
@@ -1439,8 +1472,27 @@ extern "C" double mscnn_conv2d_plan_executed_flops(const mscnn_conv_plan* p) {
   if (!p->wino && !p->x3.BM)
     return mscnn_conv2d_plan_flops(p) * ((p->head.entry < 0 && p->entry >= 0 && kTable[p->entry].variant == 210) ? 3.0 : 1.0);
   const mscnn_conv_desc& d = p->d;
+  if (p->ragged) {      // the products of the live (plane, tile) pairs only
+    double cols = 0;
+    for (int i = 0; i < p->wg.P; ++i) cols += p->wg.cols[i];
+    return 2.0 * d.Cout * d.Cin * cols;
+  }
   const double planes = (double)((p->wino_m + 2) * (p->wino_m + 2)) * (p->x3.BM ? 3.0 : 1.0);    // x3: three fp16 MFMA products per pair
   return 2.0 * planes * d.Cout * d.Cin * ((double)d.N * p->tiles_h * p->tiles_w);
+}
+extern "C" int mscnn_conv2d_plan_plane_columns(const mscnn_conv_plan* p, int* cols, int n) {
+  if (!p || (!p->wino && !p->x3.BM)) return 0;
+  const int planes = (p->wino_m + 2) * (p->wino_m + 2);
+  for (int i = 0; i < planes && i < n && cols; ++i) cols[i] = p->ragged ? p->wg.cols[i] : p->d.N * p->tiles_h * p->tiles_w;
+  return planes;
+}
+extern "C" long mscnn_debug_wgemm_schedule(const mscnn_conv_plan* p, int whole_tiles, int* rows, long max_rows, int info[8]) {
+  if (!p || !p->wino || !p->use_wg) return -1;
+  if (info) {
+    const int v[8] = {p->wg.tiles, p->wg.MT, p->wg.KI, p->wg.G, p->wg.full_q, p->wg.P, p->wg.BN, p->wg.ragged};
+    for (int i = 0; i < 8; ++i) info[i] = v[i];
+  }
+  return mscnn::wgemm_debug_schedule(p->wg, whole_tiles, rows, max_rows);
 }
 extern "C" int mscnn_conv2d_plan_set_profiling(mscnn_conv_plan* p, int on) {
   MSCNN_REQUIRE(p, "conv plan: null");
@@ -1603,7 +1655,7 @@ static int launch_igemm(const mscnn_conv_plan* p, const float* x, const float* p
 
 extern "C" int mscnn_conv2d_plan_can_pool(const mscnn_conv_plan* p) {
   if (!p || p->head.entry >= 0 || p->x3h.rows || p->hg) return 0;
-  if (p->wino || p->x3.BM) return p->wino_m == 2 || p->wino_m == 4 || (p->tiles_h % 2 == 0 && p->tiles_w % 2 == 0 && p->d.H > 8);
+  if (p->wino || p->x3.BM) return wino_can_pool(p->wino_m, p->tiles_h, p->tiles_w, p->d.H);
   return p->entry >= 0 && kTable[p->entry].fix_pool_fn != nullptr;
 }
 
@@ -1655,7 +1707,7 @@ static int wino_forward(const mscnn_conv_plan* p, const float* packed, const flo
   const mscnn_conv_desc& d = p->d;
   return wino_forward_stages(p, packed, workspace, workspace_bytes, st, input_stage, [&](const float* M) {
     return wino_output_transform(p->wino_m, M, bias, y, y_pool, d.N, d.Cout, p->Ho, p->Wo, p->tiles_h, p->tiles_w, p->T_pad, d.relu, st,
-                                 p->wino_m >= 3 ? p->amax_out : nullptr, (d.tune_flags & 256) != 0);
+                                 p->wino_m >= 3 ? p->amax_out : nullptr, (d.tune_flags & 256) != 0, p->ragged);
   });
 }
 
@@ -1690,7 +1742,7 @@ extern "C" int mscnn_conv2d_fwd_pool_f32(const mscnn_conv_plan* p, const float* 
     if (rc != MSCNN_OK) return rc;
     MSCNN_STAGE_EVENT(2);
     rc = wino_output_transform(3, M, bias, y, y_pool, d.N, d.Cout, p->Ho, p->Wo, p->tiles_h, p->tiles_w, p->T_pad, d.relu, st,
-                               p->amax_out);
+                               p->amax_out, false, 0);      // (uniform planes: ragged ones exist on the fp32 wgemm path only)
     if (rc != MSCNN_OK) return rc;
     MSCNN_STAGE_EVENT(3);
     p->ev_valid = p->profiling;
@@ -1706,7 +1758,7 @@ extern "C" int mscnn_conv2d_fwd_pool_f32(const mscnn_conv_plan* p, const float* 
   }
   return wino_forward(p, packed, bias, y, y_pool, workspace, workspace_bytes, st, [&](float* V) {
     return wino_input_transform(p->wino_m, x, V, d.N, d.Cin, d.H, d.W, d.pad_h, d.pad_w, p->tiles_h, p->tiles_w, p->T_pad, st,
-                                (d.tune_flags & 256) != 0, (d.tune_flags & 4096) != 0);
+                                (d.tune_flags & 256) != 0, (d.tune_flags & 4096) != 0, p->ragged);
   });
 #undef MSCNN_STAGE_EVENT
 }
@@ -1752,7 +1804,7 @@ extern "C" int mscnn_conv2d_fwd_chain_f32(const mscnn_conv_plan* p, const mscnn_
   auto input_stage = [&](float* V) {
     if (!x) return (int)MSCNN_OK;      // prepared by the previous layer of the chain
     return wino_input_transform(p->wino_m, x, V, d.N, d.Cin, d.H, d.W, d.pad_h, d.pad_w, p->tiles_h, p->tiles_w, p->T_pad, st,
-                                (d.tune_flags & 256) != 0, (d.tune_flags & 4096) != 0);
+                                (d.tune_flags & 256) != 0, (d.tune_flags & 4096) != 0, p->ragged);
   };
   if (!next) return wino_forward(p, packed, bias, y, y_pool, workspace, workspace_bytes, st, input_stage);
   return wino_forward_stages(p, packed, workspace, workspace_bytes, st, input_stage, [&](const float* M) {
@@ -1796,7 +1848,7 @@ extern "C" int mscnn_conv2d_fwd_roipool_pair_f32(const mscnn_conv_plan* p, const
       if (rc != MSCNN_OK) return rc;
     }
     return mscnn::roipool_wino33_forward(prepared_maps ? prepared_maps : own_maps, rois, V, p->d.N, N, C, H, W, p->T_pad, spatial_scale,
-                                         pad_ratio_a, pad_ratio_b, st);
+                                         pad_ratio_a, pad_ratio_b, st, p->ragged);
   });
 }
 

@@ -14,8 +14,9 @@ size_t roipool_wino33_scratch_bytes(int N, int C, int H, int W);
 // maps early, on another stream, while the proposals are still being selected
 int roipool_wino33_build_maps(const float* feat, float* maps, int N, int C, int H, int W, hipStream_t st);
 // maps -> V[25][2C][T_pad]: rows [0, C) from the window with pad_a, rows [C, 2C) from the window with pad_b; column 4 r + (2 ty + tx)
-// = tile (ty, tx) of ROI r.  Columns >= 4 R are not written.
+// = tile (ty, tx) of ROI r.  Columns >= 4 R are not written.  ragged (the grid description of wino33_device.h): 0, or both axes -- then
+// plane (i, j) holds the ROI's tiles at column (r th + ty) tw + tx of its own grid th = 2 - [i == 4], tw = 2 - [j == 4], and only those.
 int roipool_wino33_forward(const float* maps, const float* rois, float* V, int R, int N, int C, int H, int W, int T_pad,
-                           float spatial_scale, float pad_a, float pad_b, hipStream_t st);
+                           float spatial_scale, float pad_a, float pad_b, hipStream_t st, int ragged);
 
 }  // namespace mscnn

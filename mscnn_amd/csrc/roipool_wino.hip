@@ -31,6 +31,7 @@
 namespace {
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kNB = 4;        // bins whose 8 squares are loaded together (32 loads in flight per lane)
 constexpr int kLevels = 4;    // L0 (the map itself, channel-last) + sliding maxima over 2 x 2, 4 x 4, 8 x 8
@@ -65,7 +66,11 @@ __device__ __forceinline__ void launder(float& v) { asm volatile("" : "+v"(v)); 
 constexpr int kRois = 8;
 constexpr int kLdsRow = kRois * 4 + 4;      // floats per (plane, channel) row in LDS: 32 + 4 of padding (lane stride 144 B: no bank conflicts)
 
-template <int PH, int PW>
+// RAG: ragged planes (wino33_device.h; 7 x 7 bins -> 5 x 5 outputs: both axes).  A ROI's unit in plane (i, j) is its tiles with a
+// column there -- 4 floats (i < 4, j < 4), 2 (i < 4, j == 4: tiles (0,0), (1,0); i == 4, j < 4: tiles (0,0), (0,1)) or 1 ((4,4): tile
+// (0,0)) -- and the workgroup's runs are kRois of them: 128 / 64 / 32 bytes.  The tiles of the last tile row are
+// skipped for plane row 4; of the last tile column only the plane (., 4) value itself is unused (its column transforms feed j < 4).
+template <int PH, int PW, bool RAG>
 __global__ __launch_bounds__(kRois * 64) void roipool_wino33_kernel(RpwArgs a) {
   static_assert(PH == 7 && PW == 7, "tiles per ROI: 2 x 2 tiles of 3 x 3 outputs (a 16-byte unit of V per plane)");
   __shared__ __attribute__((aligned(16))) float s_out[5 * 64 * kLdsRow];
@@ -200,6 +205,7 @@ __global__ __launch_bounds__(kRois * 64) void roipool_wino33_kernel(RpwArgs a) {
     // ---- V = B^T d B of the ROI's 2 x 2 tiles (patch rows / columns 3 t .. 3 t + 4 of the 7 x 7 map, zero beyond it): the operation
     // order of wino33_input_kernel.  Plane row i at a time: every wave parks its five 16-byte units (plane (i, j), tiles 0 .. 3) in
     // LDS as s_out[j][channel][4 wave ..], then the workgroup writes the 5 x 64 rows of kRois x 4 columns as 128-byte runs of V.
+    // (RAG: a unit is the ROI's 4 / 2 / 1 live tiles of the plane, at the front of the same 16-byte slot; the runs are 128 / 64 / 32 bytes)
     const unsigned plane_bytes = (unsigned)(2 * C) * (unsigned)a.T_pad * 4u;
 #pragma unroll
     for (int i = 0; i < 5; ++i) {
@@ -211,6 +217,7 @@ __global__ __launch_bounds__(kRois * 64) void roipool_wino33_kernel(RpwArgs a) {
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         const int ty = t >> 1, tx = t & 1;
+        if (RAG && i == 4 && ty == 1) continue;                // (plane row 4 has no column for the tiles of the last tile row)
         float rr[5];
 #pragma unroll
         for (int j = 0; j < 5; ++j) {
@@ -230,28 +237,47 @@ __global__ __launch_bounds__(kRois * 64) void roipool_wino33_kernel(RpwArgs a) {
       }
       __syncthreads();                                         // (the previous plane row has left s_out)
 #pragma unroll
-      for (int j = 0; j < 5; ++j)
-        *reinterpret_cast<float4*>(&s_out[(j * 64 + lane) * kLdsRow + wave * 4]) = make_float4(out[j][0], out[j][1], out[j][2], out[j][3]);
+      for (int j = 0; j < 5; ++j) {
+        float* slot_ = &s_out[(j * 64 + lane) * kLdsRow + wave * 4];       // (a ragged unit sits at the front of the wave's 16 bytes)
+        if (!RAG || (i < 4 && j < 4)) *reinterpret_cast<float4*>(slot_) = make_float4(out[j][0], out[j][1], out[j][2], out[j][3]);
+        else if (i < 4) *reinterpret_cast<float2*>(slot_) = make_float2(out[j][0], out[j][2]);
+        else if (j < 4) *reinterpret_cast<float2*>(slot_) = make_float2(out[j][0], out[j][1]);
+        else *slot_ = out[j][0];
+      }
       __syncthreads();
-      // 5 planes x 64 channels x kRois units; consecutive threads take consecutive ROIs of one (plane, channel) row
+      // 5 planes x 64 channels x kRois units; consecutive threads take consecutive ROIs of one (plane, channel) row: pass j of the
+      // workgroup's kRois * 64 threads is plane (i, j)
+      static_assert(kRois == 8, "thread = (channel, roi) of a pass");
 #pragma unroll
-      for (int n = 0; n < 5 * 64 * kRois / (kRois * 64); ++n) {
-        const int item = tid + n * (kRois * 64);
-        const int rq = item % kRois, ch = (item / kRois) % 64, j = item / (kRois * 64);
+      for (int j = 0; j < 5; ++j) {
+        const int rq = tid % kRois, ch = tid / kRois;
         if (r0 + rq < a.R) {
-          const float4 u = *reinterpret_cast<const float4*>(&s_out[(j * 64 + ch) * kLdsRow + rq * 4]);
-          u32x4 pk;
-          pk.x = __builtin_bit_cast(unsigned, u.x); pk.y = __builtin_bit_cast(unsigned, u.y);
-          pk.z = __builtin_bit_cast(unsigned, u.z); pk.w = __builtin_bit_cast(unsigned, u.w);
+          const float* unit = &s_out[(j * 64 + ch) * kLdsRow + rq * 4];
+          const int uw = RAG ? (i < 4 ? 2 : 1) * (j < 4 ? 2 : 1) : 4;      // floats per ROI in this plane
           // (the whole offset in the VGPR, SOFFSET = 0: with a 16-byte store whose SOFFSET is an SGPR the compiler's hazard recogniser
           // assumes no store-data hazard and lets the next VALU instruction overwrite the data registers one cycle later -- on gfx950
-          // that clobbered dword 1 of lanes 12 .. 15 of every 16 before the store had read them (tools/sessions/r04_s5.sh))
-          const unsigned off = (unsigned)(i * 5 + j) * plane_bytes + ((unsigned)(q * C + c0 + ch) * (unsigned)a.T_pad + (unsigned)(r0 + rq) * 4u) * 4u;
-#ifndef RPW_NO_STORE
-          __builtin_amdgcn_raw_buffer_store_b128(pk, rV, off, 0u, 0);
-#else
-          if (a.T_pad < 0) __builtin_amdgcn_raw_buffer_store_b128(pk, rV, off, 0u, 0);
+          // that clobbered dword 1 of lanes 12 .. 15 of every 16 before the store had read them (tools/sessions/r04_s5.sh); the
+          // narrower stores of the ragged planes keep the same form)
+          const unsigned off = (unsigned)(i * 5 + j) * plane_bytes + ((unsigned)(q * C + c0 + ch) * (unsigned)a.T_pad + (unsigned)(r0 + rq) * (unsigned)uw) * 4u;
+#ifdef RPW_NO_STORE
+          if (a.T_pad < 0)
 #endif
+          {
+            if (uw == 4) {
+              const float4 u = *reinterpret_cast<const float4*>(unit);
+              u32x4 pk;
+              pk.x = __builtin_bit_cast(unsigned, u.x); pk.y = __builtin_bit_cast(unsigned, u.y);
+              pk.z = __builtin_bit_cast(unsigned, u.z); pk.w = __builtin_bit_cast(unsigned, u.w);
+              __builtin_amdgcn_raw_buffer_store_b128(pk, rV, off, 0u, 0);
+            } else if (uw == 2) {
+              const float2 u = *reinterpret_cast<const float2*>(unit);
+              u32x2 pk;
+              pk.x = __builtin_bit_cast(unsigned, u.x); pk.y = __builtin_bit_cast(unsigned, u.y);
+              __builtin_amdgcn_raw_buffer_store_b64(pk, rV, off, 0u, 0);
+            } else {
+              __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, unit[0]), rV, off, 0u, 0);
+            }
+          }
         }
       }
     }
@@ -329,8 +355,9 @@ int roipool_wino33_build_maps(const float* feat, float* maps, int N, int C, int 
 }
 
 int roipool_wino33_forward(const float* maps, const float* rois, float* V, int R, int N, int C, int H, int W, int T_pad,
-                           float spatial_scale, float pad_a, float pad_b, hipStream_t st) {
+                           float spatial_scale, float pad_a, float pad_b, hipStream_t st, int ragged) {
   MSCNN_REQUIRE(maps && rois && V, "roipool+transform: null pointer");
+  MSCNN_REQUIRE(ragged == 0 || ragged == wino33_ragged_mode(5, 5), "roipool+transform: the planes are uniform or ragged on both axes (5 x 5 outputs)");
   MSCNN_REQUIRE(R > 0 && N > 0 && C % 64 == 0 && H > 0 && W > 0 && T_pad >= 4 * R && T_pad % 4 == 0, "roipool+transform: bad shape");
   const double lb = (double)N * C * H * W * 4.0, vb = 25.0 * 2.0 * C * (double)T_pad * 4.0;
   MSCNN_REQUIRE(kLevels * lb < 4.0e9 && vb < 4.0e9, "roipool+transform: feature maps or transform planes beyond a 32-bit buffer window");
@@ -342,7 +369,8 @@ int roipool_wino33_forward(const float* maps, const float* rois, float* V, int R
   a.spatial_scale = spatial_scale; a.pad_a = pad_a; a.pad_b = pad_b;
   // channel block on grid.x: workgroups go round-robin over the 8 XCDs by linear id, so XCD j only ever touches channel blocks
   // == j (mod 8) of the maps -- with C = 512 exactly one 64-channel slice (4 x 4.4 MB) per XCD's L2
-  roipool_wino33_kernel<7, 7><<<dim3(C / 64, cdiv(R, kRois), 2), kRois * 64, 0, st>>>(a);
+  if (ragged) roipool_wino33_kernel<7, 7, true><<<dim3(C / 64, cdiv(R, kRois), 2), kRois * 64, 0, st>>>(a);
+  else roipool_wino33_kernel<7, 7, false><<<dim3(C / 64, cdiv(R, kRois), 2), kRois * 64, 0, st>>>(a);
   MSCNN_POST_LAUNCH();
   return MSCNN_OK;
 }

@@ -30,6 +30,14 @@
 // K chunks): a workgroup that holds later chunks of a split tile publishes its partial sum as a write-through fp32 slab + flag,
 // the workgroup that holds the tile's FIRST chunks (it gets to them last in time) adds the slabs in k order and stores the tile
 // (deterministic: fixed order, no atomics on data; hand-off = the release / acquire recipe of the CDNA programming guide, G16).
+//
+// Ragged planes (the RAG instantiations; WgemmPlan::ragged).  The small-map F(3x3,3x3) layers (roi_c1: 5 x 5 outputs as 2 x 2 tiles
+// of 3 x 3) never read the planes (4, .) / (., 4) for a tile whose third output row / column lies outside the map (wino33_device.h),
+// so those planes hold fewer live columns -- 4R / 2R / R for roi_c1 -- at the front of the same [Cin][T_pad] rows, and the GEMM gives
+// plane p only ceil(cols[p] / BN) column tiles: t = (nt_off[p] + nt) * MT + mt with the prefix table nt_off passed by value.  Only
+// the decode t -> (p, nt, mt) differs (wgemm_tile_decode in wgemm.h: ONE function for the producer, the consumer and the host-side
+// replay of the schedule); slots, segments, the stream-K ranges, slabs, flags and the time-out path work on t and the tile count and
+// are the uniform kernel's.  The uniform instantiations are untouched (same registers, LDS and hot loop).
 #include "wgemm.h"
 #include "common.h"
 #include <atomic>
@@ -54,6 +62,8 @@ struct WgemmArgs {
   unsigned long long* status;
   unsigned spin_limit;
   int drop_publish;             // fault injection (mscnn_debug_wgemm_handoff_fault): contributors never set their flag
+  // ragged planes only (RAG kernels; last, so that every other field keeps its place): column tiles before plane p
+  int nt_off[mscnn::kWgemmMaxPlanes + 1];
 };
 
 template <int BM_, int BN_, int WGM_, int WGN_, int CK_, int ST_, int DPG_ = 1, int SK_ = 0>
@@ -133,15 +143,17 @@ struct SegCursor {
   int slot, G, KI, full_q, rem_tile0, r;
   int it, re;
   int nparts;
-  __device__ __forceinline__ void init(const WgemmArgs& a, int slot_) {
-    slot = slot_; G = a.G; KI = a.KI; rem_tile0 = a.full_q * a.G; r = 0; nparts = 0;
+  __device__ __forceinline__ void init(const WgemmArgs& a, int slot_) { init(a.tiles, a.G, a.KI, a.full_q, slot_); }
+  __device__ __host__ __forceinline__ void init(int tiles, int G_, int KI_, int a_full_q, int slot_) {
+    slot = slot_; G = G_; KI = KI_; rem_tile0 = a_full_q * G_; r = 0; nparts = 0;
     // whole tiles of this slot: rounds r < full_q whose tile exists (with whole-tile scheduling the last round is not full)
-    full_q = slot_ < a.tiles ? min(a.full_q, (a.tiles - slot_ + a.G - 1) / a.G) : 0;
-    if (a.tiles > rem_tile0) wg_range((a.tiles - rem_tile0) * a.KI, a.G, slot_, it, re);
+    const int rounds = slot_ < tiles ? (tiles - slot_ + G_ - 1) / G_ : 0;
+    full_q = a_full_q < rounds ? a_full_q : rounds;
+    if (tiles > rem_tile0) wg_range((tiles - rem_tile0) * KI_, G_, slot_, it, re);
     else it = re = 0;
   }
   __device__ __forceinline__ int units() const { return full_q * KI + (re - it); }
-  __device__ __forceinline__ bool next(int& t, int& k0, int& k1, int& part) {
+  __device__ __host__ __forceinline__ bool next(int& t, int& k0, int& k1, int& part) {
     if (r < full_q) { t = slot + r * G; k0 = 0; k1 = KI; part = -1; ++r; return true; }
     if (it >= re) return false;
     t = rem_tile0 + it / KI;
@@ -154,7 +166,8 @@ struct SegCursor {
   }
 };
 
-template <class C, int ABL, int EPI = 0>
+// RAG: the planes have their own column-tile counts (a.nt_off); everything but the tile decode is the uniform kernel
+template <class C, int ABL, int EPI = 0, bool RAG = false>
 __global__ __launch_bounds__(C::THREADS, C::NW / 4) void wgemm_kernel(WgemmArgs a) {
   __shared__ __attribute__((aligned(1024))) float lds[C::LDS_FLOATS];
   __shared__ unsigned s_handoff_timeout;
@@ -204,7 +217,8 @@ __global__ __launch_bounds__(C::THREADS, C::NW / 4) void wgemm_kernel(WgemmArgs 
     if (p_kc == p_k1 && pu < nunits) {  // next segment
       int t, part;
       pcur.next(t, p_kc, p_k1, part);
-      const int mt = t % a.MT, nt = (t / a.MT) % a.NT, p = t / (a.MT * a.NT);
+      int mt, nt, p;
+      mscnn::wgemm_tile_decode(t, a.MT, a.NT, a.P, RAG ? a.nt_off : nullptr, p, nt, mt);
       // (the compiler does the divisions on the vector ALU: pin the results back to scalars -- the LDS-DMA statement needs SGPR operands)
       p_kc = __builtin_amdgcn_readfirstlane(p_kc); p_k1 = __builtin_amdgcn_readfirstlane(p_k1);
       p_a = __builtin_amdgcn_readfirstlane((unsigned)((p * a.MT + mt) * a.KI) * (unsigned)C::A_BYTES);
@@ -394,7 +408,8 @@ __global__ __launch_bounds__(C::THREADS, C::NW / 4) void wgemm_kernel(WgemmArgs 
     chunk(par_c, std::true_type{}, next_stage_addr());
     if (old_pub) { publish_flag(); old_pub = false; }
     for (int kc = k0 + 1; kc < k1; ++kc) chunk(par_c, std::false_type{}, next_stage_addr());
-    const int mt = t % a.MT, nt = (t / a.MT) % a.NT, p = t / (a.MT * a.NT);
+    int mt, nt, p;
+    mscnn::wgemm_tile_decode(t, a.MT, a.NT, a.P, RAG ? a.nt_off : nullptr, p, nt, mt);
     const bool pub = part >= 0 && k0 > 0;
     if (part >= 0 && k0 == 0) fin_tile = t;
     old_pub = pub;
@@ -493,17 +508,19 @@ __global__ __launch_bounds__(C::THREADS, C::NW / 4) void wgemm_kernel(WgemmArgs 
 }
 
 typedef void (*WgemmFn)(WgemmArgs);
-struct WEntry { const char* name; int variant, abl, BM, BN, CK, threads; WgemmFn fn; };
+struct WEntry { const char* name; int variant, abl, BM, BN, CK, threads; WgemmFn fn; WgemmFn fn_ragged = nullptr; };
 #define WG_ENTRY(name, v, abl, BM, BN, WGM, WGN, CK) {name, v, abl, BM, BN, CK, WGM * WGN * 64, wgemm_kernel<WCfg<BM, BN, WGM, WGN, CK, 3>, abl>}
+// ... with the ragged-plane instantiation beside it (the product tile shapes a small-map F(3x3,3x3) plan can pick at some ROI count)
+#define WG_ENTRY_R(name, v, BM, BN, WGM, WGN, CK) {name, v, 0, BM, BN, CK, WGM * WGN * 64, wgemm_kernel<WCfg<BM, BN, WGM, WGN, CK, 3>, 0>, wgemm_kernel<WCfg<BM, BN, WGM, WGN, CK, 3>, 0, 0, true>}
 // variant + 64: the same tile with the bias / ReLU epilogue (abl field 64: never matched by the ablation look-up): InnerProduct on this kernel
 #define WG_ENTRY_EPI(name, v, BM, BN, WGM, WGN, CK) {name, v + 64, 0, BM, BN, CK, WGM * WGN * 64, wgemm_kernel<WCfg<BM, BN, WGM, WGN, CK, 3>, 0, 1>}
 #define WG_ENTRY_S(name, v, BM, BN, WGM, WGN, CK, DPG, SK) {name, v, 0, BM, BN, CK, WGM * WGN * 64, wgemm_kernel<WCfg<BM, BN, WGM, WGN, CK, 3, DPG, SK>, 0>}
 const WEntry kW[] = {
-    WG_ENTRY("wgemm_256x128_ck32", 1, 0, 256, 128, 4, 2, 32),
-    WG_ENTRY("wgemm_128x256_ck32", 2, 0, 128, 256, 2, 4, 32),
-    WG_ENTRY("wgemm_128x128_ck32", 3, 0, 128, 128, 2, 4, 32),
-    WG_ENTRY("wgemm_256x96_ck32", 4, 0, 256, 96, 8, 1, 32),       // conv5_x: 480 tile columns = 5 x 96, 250 tiles in one full round
-    WG_ENTRY("wgemm_256x160_ck32", 5, 0, 256, 160, 8, 1, 32),
+    WG_ENTRY_R("wgemm_256x128_ck32", 1, 256, 128, 4, 2, 32),
+    WG_ENTRY_R("wgemm_128x256_ck32", 2, 128, 256, 2, 4, 32),
+    WG_ENTRY_R("wgemm_128x128_ck32", 3, 128, 128, 2, 4, 32),
+    WG_ENTRY_R("wgemm_256x96_ck32", 4, 256, 96, 8, 1, 32),        // conv5_x: 480 tile columns = 5 x 96, 250 tiles in one full round
+    WG_ENTRY_R("wgemm_256x160_ck32", 5, 256, 160, 8, 1, 32),
     WG_ENTRY_EPI("wgemm_256x128_ck32_epi", 1, 256, 128, 4, 2, 32),     // conv4_x F(4x4,3x3): 1080 columns = 6.75 x 160 -> 504 tiles = 1.97 rounds (r4)
 #ifdef MSCNN_WGEMM_DEV      // schedule A/B (pieces per group, first store group)
     WG_ENTRY_S("wgemm_256x128_ck32_d2", 25, 256, 128, 4, 2, 32, 2, 0),
@@ -582,7 +599,11 @@ void wgemm_debug_handoff_fault(int drop_publish, unsigned spin_limit) {
   g_spin_limit.store(spin_limit ? spin_limit : (1u << 22));
 }
 
-bool wgemm_plan(int P, int Cout, int Cin, int T, int variant, WgemmPlan* o) {
+bool wgemm_plan(int P, int Cout, int Cin, int T, int variant, WgemmPlan* o, const int* plane_cols) {
+  if (P < 1 || P > kWgemmMaxPlanes) return false;
+  if (plane_cols)
+    for (int p = 0; p < P; ++p)
+      if (plane_cols[p] < 0 || plane_cols[p] > T) return false;
   const int variant_flags = variant >> 8;
   variant &= 255;
   if (variant == 0) {
@@ -594,14 +615,14 @@ bool wgemm_plan(int P, int Cout, int Cin, int T, int variant, WgemmPlan* o) {
     // (the three share BM = 256, i.e. one packed-weight layout: a per-frame ROI count may flip the choice without a re-pack)
     if (variant == 1 && !variant_flags) {
       WgemmPlan p1, pc;
-      if (wgemm_plan(P, Cout, Cin, T, 1, &p1)) {
+      if (wgemm_plan(P, Cout, Cin, T, 1, &p1, plane_cols)) {
         double best = 0.95 * p1.model_us;
         for (int cand : {4, 5})
-          if (wgemm_plan(P, Cout, Cin, T, cand, &pc) && pc.model_us < best) { best = pc.model_us; variant = cand; }
+          if (wgemm_plan(P, Cout, Cin, T, cand, &pc, plane_cols) && pc.model_us < best) { best = pc.model_us; variant = cand; }
         // a problem that does not even give every other CU a 256 x 128 tile (conv6_1: 50 tiles): 128 x 128 tiles, split stream-K style,
         // put four times as many workgroups on useful chunks -- 39.7 -> 27.4 us stand-alone (profiles/r04_ab_wgemm_tiles.txt).  Only
         // there: per FLOP the small tile moves twice the operands, which the model's MFMA-bound chunk time does not see.
-        if ((long)P * p1.MT * p1.NT * 2 < p1.G && wgemm_plan(P, Cout, Cin, T, 3, &pc) && pc.model_us < best) { best = pc.model_us; variant = 3; }
+        if ((long)p1.tiles * 2 < p1.G && wgemm_plan(P, Cout, Cin, T, 3, &pc, plane_cols) && pc.model_us < best) { best = pc.model_us; variant = 3; }
       }
     }
   }
@@ -613,7 +634,15 @@ bool wgemm_plan(int P, int Cout, int Cin, int T, int variant, WgemmPlan* o) {
   o->T_pad = (T + e->BN - 1) / e->BN * e->BN;
   o->MT = (Cout + e->BM - 1) / e->BM; o->NT = o->T_pad / e->BN; o->KI = Cin / e->CK;
   o->G = device_cus(&o->device);          // one 512-thread workgroup per CU (of the device that is current NOW: the launch checks it)
-  const long tiles = (long)P * o->MT * o->NT;
+  // column tiles per plane: NT, or what the plane's live columns need
+  o->ragged = plane_cols ? 1 : 0;
+  o->nt_off[0] = 0;
+  for (int p = 0; p < kWgemmMaxPlanes; ++p) {
+    o->cols[p] = p < P ? (plane_cols ? plane_cols[p] : T) : 0;
+    o->nt_off[p + 1] = o->nt_off[p] + (p < P ? (plane_cols ? (plane_cols[p] + e->BN - 1) / e->BN : o->NT) : 0);
+  }
+  const long tiles = (long)o->MT * o->nt_off[P];
+  o->tiles = (int)tiles;
   // Whole tiles (ceil(tiles / G) rounds) or the hybrid stream-K split of the last partial round?  Fitted to the measurements of
   // profiles/r03_wgemm.txt (256 x 128 x 32 chunks: 3.7 us each at the sustained clock, ~6 us per tile for its ride-along stores,
   // ~18 us for a workgroup's slab hand-off): the split wins for conv4_2 / conv4_3 / loss1 in the F(4x4,3x3) form (648 tiles = 2.53
@@ -646,7 +675,7 @@ int wgemm_launch(const WgemmPlan& p, const float* Up, const float* V, float* M, 
                  const float* bias, int relu, size_t m_valid_bytes) {
   const WEntry* e = nullptr;
   for (const WEntry& w : kW) if (w.variant == p.variant && w.abl == abl) e = &w;
-  if (!e) return MSCNN_ERR_BAD_ARG;
+  if (!e || (p.ragged && !e->fn_ragged)) return MSCNN_ERR_BAD_ARG;
   // The persistent grid (and the co-residency the stream-K hand-off relies on) was sized for the device that was current when the
   // plan was made: a plan is not portable between devices / partitions.
   int dev = -1;
@@ -658,7 +687,9 @@ int wgemm_launch(const WgemmPlan& p, const float* Up, const float* V, float* M, 
   WgemmArgs a;
   a.Up = Up; a.V = V; a.M = M; a.ws = ws;
   a.P = p.P; a.MT = p.MT; a.NT = p.NT; a.KI = p.KI; a.Cin = p.Cin; a.Cout = p.Cout; a.T_pad = p.T_pad;
-  a.tiles = p.P * p.MT * p.NT; a.G = p.G; a.abl = abl; a.dbg = dbg;
+  a.tiles = p.tiles; a.G = p.G;
+  a.abl = abl; a.dbg = dbg;
+  for (int i = 0; i <= kWgemmMaxPlanes; ++i) a.nt_off[i] = p.nt_off[i];
   a.full_q = p.full_q; a.ws_bytes = (unsigned)p.ws_bytes;
   // (after a reported hand-off time-out the host forces whole tiles: the last round is then simply not full and nothing is handed over)
   if (g_whole_tiles.load(std::memory_order_relaxed)) a.full_q = (a.tiles + p.G - 1) / p.G;
@@ -676,9 +707,30 @@ int wgemm_launch(const WgemmPlan& p, const float* Up, const float* V, float* M, 
   unsigned ep = ++g_epoch;
   if (ep == 0) ep = ++g_epoch;
   a.epoch = ep;
-  e->fn<<<p.G, e->threads, 0, st>>>(a);
+  (p.ragged ? e->fn_ragged : e->fn)<<<p.G, e->threads, 0, st>>>(a);
   MSCNN_POST_LAUNCH();
   return MSCNN_OK;
+}
+
+long wgemm_debug_schedule(const WgemmPlan& p, int whole_tiles, int* out, long max_rows) {
+  const int full_q = whole_tiles ? (p.tiles + p.G - 1) / p.G : p.full_q;
+  long n = 0;
+  for (int slot = 0; slot < p.G; ++slot) {
+    SegCursor c;
+    c.init(p.tiles, p.G, p.KI, full_q, slot);
+    int t, k0, k1, part;
+    while (c.next(t, k0, k1, part)) {
+      if (out) {
+        if (n >= max_rows) return -1;
+        int pl, nt, mt;
+        wgemm_tile_decode(t, p.MT, p.NT, p.P, p.ragged ? p.nt_off : nullptr, pl, nt, mt);
+        const int row[7] = {slot, pl, nt, mt, k0, k1, part};
+        for (int i = 0; i < 7; ++i) out[n * 7 + i] = row[i];
+      }
+      ++n;
+    }
+  }
+  return n;
 }
 
 }  // namespace mscnn

@@ -229,10 +229,11 @@ __global__ __launch_bounds__(256) void wino33_weight_kernel(const float* __restr
 // with tiles fastest do the 5x5 transform, so every one of the 25 planes V[xinu][ci][t] is written as 128-byte runs
 // (8 ROIs x tiles-per-ROI consecutive t).  157 -> see DESIGN.md (the per-(channel, tile) gather form read 64 cache lines per
 // load instruction).
-constexpr int kW33Rois = 8, kW33Ch = 16, kW33MaxHW = 64;
+constexpr int kW33Rois = 8, kW33Ch = 16, kW33MaxHW = mscnn::kWino33SmallMapHW;
 
 __global__ __launch_bounds__(256) void wino33_input_kernel(const float* __restrict__ x, float* __restrict__ V, int N, int Cin, int H,
-                                                           int W, int pad_h, int pad_w, int tiles_h, int tiles_w, int T, int T_pad) {
+                                                           int W, int pad_h, int pad_w, int tiles_h, int tiles_w, int T, int T_pad,
+                                                           int ragged) {
   __shared__ __attribute__((aligned(16))) float sm[kW33Rois * kW33Ch * kW33MaxHW];
   const int tid = threadIdx.x;
   const int r0 = blockIdx.x * kW33Rois, c0 = blockIdx.y * kW33Ch;
@@ -288,12 +289,25 @@ __global__ __launch_bounds__(256) void wino33_input_kernel(const float* __restri
     for (int i = 0; i < 5; ++i) {
       float o[5];
       bt5(rr[i], o);     // (B^T d) B: the same combination along the row
+      if (!ragged) {
 #pragma unroll
-      for (int j = 0; j < 5; ++j) dst[(i * 5 + j) * plane_stride] = o[j];
+        for (int j = 0; j < 5; ++j) dst[(i * 5 + j) * plane_stride] = o[j];
+      } else {
+        // ragged planes (wino33_device.h): the column inside plane (i, j) counts the plane's own tile grid; a (plane, tile) pair no
+        // output reads is not written
+        const int th = mscnn::wino33_plane_th(ragged, i, tiles_h);
+#pragma unroll
+        for (int j = 0; j < 5; ++j) {
+          const int tw = mscnn::wino33_plane_tw(ragged, j, tiles_w);
+          if (ty < th && tx < tw) V[(i * 5 + j) * plane_stride + (long)(c0 + c) * T_pad + ((long)r * th + ty) * tw + tx] = o[j];
+        }
+      }
     }
   }
-  // columns T .. T_pad of every plane (GEMM padding) must be zero: the last ROI block writes them
-  if (blockIdx.x == gridDim.x - 1) {
+  // columns T .. T_pad of every plane (GEMM padding) are zero: the last ROI block writes them.  (Nothing needs it -- a column of M
+  // depends on its own column of V only and no output transform reads a padding column; the fused ROI-pooling input stage never wrote
+  // them -- so the ragged form, whose planes end at different columns, writes its live columns only.)
+  if (blockIdx.x == gridDim.x - 1 && !ragged) {
     for (int i = tid; i < nch * (T_pad - T); i += 256) {
       const int c = i / (T_pad - T), t = T + i % (T_pad - T);
 #pragma unroll 1
@@ -350,26 +364,49 @@ __global__ __launch_bounds__(256) void wino33_input_plane_kernel(const float* __
   }
 }
 
+// Ragged planes (wino33_device.h): m[0 .. 4] = planes (i, j), i < 5, of tile (n, ty, tx) from a channel's rows `row`.  A plane the
+// tile has no column in -- (4, .) for a tile of the last tile row, (., 4) for one of the last tile column -- is not loaded: it only
+// feeds the tile's third output row / column, which lies outside the map and is never stored (its m stays 0 in a sum nobody keeps).
+__device__ __forceinline__ void wino33_load_ragged_column(const float* __restrict__ row, long plane_stride, int ragged, int j, int n, int ty,
+                                                          int tx, int tiles_h, int tiles_w, float& m0, float& m1, float& m2, float& m3,
+                                                          float& m4) {
+  const int tw = mscnn::wino33_plane_tw(ragged, j, tiles_w);
+  const int th4 = mscnn::wino33_plane_th(ragged, 4, tiles_h);
+  m0 = m1 = m2 = m3 = m4 = 0.f;
+  if (tx < tw) {
+    const long col = ((long)n * tiles_h + ty) * tw + tx;
+    m0 = row[(0 * 5 + j) * plane_stride + col]; m1 = row[(1 * 5 + j) * plane_stride + col]; m2 = row[(2 * 5 + j) * plane_stride + col];
+    m3 = row[(3 * 5 + j) * plane_stride + col];
+    if (ty < th4) m4 = row[(4 * 5 + j) * plane_stride + ((long)n * th4 + ty) * tw + tx];
+  }
+}
+
 __global__ __launch_bounds__(256) void wino33_output_kernel(const float* __restrict__ M, const float* __restrict__ bias,
                                                             float* __restrict__ y, int N, int Cout, int Ho, int Wo, int tiles_h,
-                                                            int tiles_w, int T, int T_pad, int relu, unsigned* __restrict__ amax) {
+                                                            int tiles_w, int T, int T_pad, int relu, unsigned* __restrict__ amax,
+                                                            int ragged) {
   const int t = blockIdx.x * 256 + threadIdx.x;
   const int co = blockIdx.y;
   unsigned am = 0;
   if (t < T) {
   const long plane_stride = (long)Cout * T_pad;
   const float* src = M + (long)co * T_pad + t;
+  const int tx = t % tiles_w, ty = (t / tiles_w) % tiles_h, n = t / (tiles_w * tiles_h);
   float r[3][5];   // A^T m
 #pragma unroll
   for (int j = 0; j < 5; ++j) {
-    const float m0 = src[(0 * 5 + j) * plane_stride], m1 = src[(1 * 5 + j) * plane_stride], m2 = src[(2 * 5 + j) * plane_stride];
-    const float m3 = src[(3 * 5 + j) * plane_stride], m4 = src[(4 * 5 + j) * plane_stride];
+    float m0, m1, m2, m3, m4;
+    if (!ragged) {
+      m0 = src[(0 * 5 + j) * plane_stride]; m1 = src[(1 * 5 + j) * plane_stride]; m2 = src[(2 * 5 + j) * plane_stride];
+      m3 = src[(3 * 5 + j) * plane_stride]; m4 = src[(4 * 5 + j) * plane_stride];
+    } else {
+      wino33_load_ragged_column(M + (long)co * T_pad, plane_stride, ragged, j, n, ty, tx, tiles_h, tiles_w, m0, m1, m2, m3, m4);
+    }
     r[0][j] = m0 + m1 + m2 + m3;
     r[1][j] = m1 - m2 + 2.f * m3;
     r[2][j] = m1 + m2 + 4.f * m3 + m4;
   }
   const float b = bias ? bias[co] : 0.f;
-  const int tx = t % tiles_w, ty = (t / tiles_w) % tiles_h, n = t / (tiles_w * tiles_h);
   float* dst = y + ((long)n * Cout + co) * Ho * Wo;
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
@@ -404,7 +441,8 @@ constexpr int kW33ORois = 16, kW33OCh = 8;
 
 __global__ __launch_bounds__(256) void wino33_output_roi_kernel(const float* __restrict__ M, const float* __restrict__ bias,
                                                                 float* __restrict__ y, int N, int Cout, int Ho, int Wo, int tiles_h,
-                                                                int tiles_w, int T_pad, int relu, unsigned* __restrict__ amax) {
+                                                                int tiles_w, int T_pad, int relu, unsigned* __restrict__ amax,
+                                                                int ragged) {
   __shared__ __attribute__((aligned(16))) float sm[kW33ORois * kW33OCh * kW33MaxHW];
   const int tid = threadIdx.x;
   const int r0 = blockIdx.x * kW33ORois, c0 = blockIdx.y * kW33OCh;
@@ -421,8 +459,13 @@ __global__ __launch_bounds__(256) void wino33_output_roi_kernel(const float* __r
     float r[3][5];   // A^T m
 #pragma unroll
     for (int j = 0; j < 5; ++j) {
-      const float m0 = src[(0 * 5 + j) * plane_stride], m1 = src[(1 * 5 + j) * plane_stride], m2 = src[(2 * 5 + j) * plane_stride];
-      const float m3 = src[(3 * 5 + j) * plane_stride], m4 = src[(4 * 5 + j) * plane_stride];
+      float m0, m1, m2, m3, m4;
+      if (!ragged) {
+        m0 = src[(0 * 5 + j) * plane_stride]; m1 = src[(1 * 5 + j) * plane_stride]; m2 = src[(2 * 5 + j) * plane_stride];
+        m3 = src[(3 * 5 + j) * plane_stride]; m4 = src[(4 * 5 + j) * plane_stride];
+      } else {
+        wino33_load_ragged_column(M + (long)(c0 + c) * T_pad, plane_stride, ragged, j, r0 + rl, ty, tx, tiles_h, tiles_w, m0, m1, m2, m3, m4);
+      }
       r[0][j] = m0 + m1 + m2 + m3;
       r[1][j] = m1 - m2 + 2.f * m3;
       r[2][j] = m1 + m2 + 4.f * m3 + m4;
@@ -914,7 +957,8 @@ int wino_pack_weights(int m, const float* w, float* packed, int Cout, int Cin, i
 }
 
 int wino_input_transform(int m, const float* x, float* V, int N, int Cin, int H, int W, int pad_h, int pad_w, int tiles_h,
-                         int tiles_w, int T_pad, hipStream_t st, bool scalar_f4, bool one_tile_per_lane) {
+                         int tiles_w, int T_pad, hipStream_t st, bool scalar_f4, bool one_tile_per_lane, int ragged) {
+  MSCNN_REQUIRE(!ragged || (m == 3 && H * W <= kW33MaxHW), "winograd: ragged planes exist for the small-map F(3x3,3x3) kernels only");
   const int T = N * tiles_h * tiles_w;
   dim3 grid(cdiv(T_pad, 256), Cin);
   if (m == 4 && pad_w == 1 && W % 4 == 0 && tiles_w * 4 == W && reinterpret_cast<uintptr_t>(x) % 16 == 0 && !scalar_f4) {
@@ -934,7 +978,7 @@ int wino_input_transform(int m, const float* x, float* V, int N, int Cin, int H,
     wino44_input_plane_kernel<<<grid, 256, 0, st>>>(x, V, N, Cin, H, W, pad_h, pad_w, tiles_h, tiles_w, T, T_pad);
   } else if (m == 3 && H * W <= kW33MaxHW) {
     dim3 g3(cdiv(N, kW33Rois), cdiv(Cin, kW33Ch));
-    wino33_input_kernel<<<g3, 256, 0, st>>>(x, V, N, Cin, H, W, pad_h, pad_w, tiles_h, tiles_w, T, T_pad);
+    wino33_input_kernel<<<g3, 256, 0, st>>>(x, V, N, Cin, H, W, pad_h, pad_w, tiles_h, tiles_w, T, T_pad, ragged);
   } else if (m == 3) {
     wino33_input_plane_kernel<<<grid, 256, 0, st>>>(x, V, N, Cin, H, W, pad_h, pad_w, tiles_h, tiles_w, T, T_pad);
   } else wino_input_kernel<<<grid, 256, 0, st>>>(x, V, N, Cin, H, W, pad_h, pad_w, tiles_h, tiles_w, T, T_pad);
@@ -943,7 +987,10 @@ int wino_input_transform(int m, const float* x, float* V, int N, int Cin, int H,
 }
 
 int wino_output_transform(int m, const float* M, const float* bias, float* y, float* y_pool, int N, int Cout, int Ho, int Wo,
-                          int tiles_h, int tiles_w, int T_pad, int relu, hipStream_t st, unsigned* amax, bool scalar_f4) {
+                          int tiles_h, int tiles_w, int T_pad, int relu, hipStream_t st, unsigned* amax, bool scalar_f4, int ragged) {
+  // (a small INPUT map with a large padding has an output beyond the LDS-staged kernel's maps: the generic kernel reads ragged planes too)
+  MSCNN_REQUIRE(!ragged || (m == 3 && !y_pool && ragged == mscnn::wino33_ragged_mode(Ho, Wo)),
+                "winograd: ragged planes exist for the F(3x3,3x3) output transforms without pooling only, with the mode of the output shape");
   MSCNN_REQUIRE(!amax || m >= 3, "winograd: max |y| is published by the F(3x3,3x3) / F(4x4,3x3) output transforms only");
   // ONE predicate for "the vector F(4x4,3x3) kernel runs": the pool-only mode (y == NULL) exists in that kernel alone, so the check
   // below and the dispatch cannot drift apart (a y_pool that is only 4-byte aligned used to pass the check and fall through to the
@@ -963,9 +1010,9 @@ int wino_output_transform(int m, const float* M, const float* bias, float* y, fl
     wino33_output_pool_kernel<<<gp, 256, 0, st>>>(M, bias, y, y_pool, N, Cout, Ho, Wo, tiles_h, tiles_w, T_pad, relu, amax);
   } else if (m == 3 && Ho * Wo <= kW33MaxHW && !scalar_f4) {
     // (sm rows are packed [roi][nch][HW]: a float4 read of row rl needs rl * run * 4 bytes 16-aligned -- run % 4 == 0 is checked in the kernel)
-    wino33_output_roi_kernel<<<dim3(cdiv(N, kW33ORois), cdiv(Cout, kW33OCh)), 256, 0, st>>>(M, bias, y, N, Cout, Ho, Wo, tiles_h, tiles_w, T_pad, relu, amax);
+    wino33_output_roi_kernel<<<dim3(cdiv(N, kW33ORois), cdiv(Cout, kW33OCh)), 256, 0, st>>>(M, bias, y, N, Cout, Ho, Wo, tiles_h, tiles_w, T_pad, relu, amax, ragged);
   } else if (m == 3) {
-    wino33_output_kernel<<<grid, 256, 0, st>>>(M, bias, y, N, Cout, Ho, Wo, tiles_h, tiles_w, T, T_pad, relu, amax);
+    wino33_output_kernel<<<grid, 256, 0, st>>>(M, bias, y, N, Cout, Ho, Wo, tiles_h, tiles_w, T, T_pad, relu, amax, ragged);
   } else {
     wino_output_kernel<<<grid, 256, 0, st>>>(M, bias, y, y_pool, N, Cout, Ho, Wo, tiles_h, tiles_w, T, T_pad, relu);
   }

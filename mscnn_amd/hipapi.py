@@ -127,6 +127,9 @@ def lib():
             getattr(L, f).restype = C.c_double
             getattr(L, f).argtypes = [C.c_void_p]
         L.mscnn_conv2d_plan_set_profiling.argtypes = [C.c_void_p, C.c_int]
+        L.mscnn_conv2d_plan_plane_columns.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.mscnn_debug_wgemm_schedule.restype = C.c_long
+        L.mscnn_debug_wgemm_schedule.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_long, C.c_void_p]
         L.mscnn_conv2d_plan_stage_ms.argtypes = [C.c_void_p, C.c_void_p]
         for f in ("mscnn_conv2d_packed_weight_bytes", "mscnn_conv2d_workspace_bytes"):
             getattr(L, f).restype = C.c_size_t
@@ -259,6 +262,26 @@ class ConvPlan:
     @property
     def executed_flops(self):
         return lib().mscnn_conv2d_plan_executed_flops(self._p)
+
+    def plane_columns(self):
+        """Live GEMM columns of each transform plane (mscnn_conv2d_plan_plane_columns); [] for a plan that is not Winograd."""
+        out = (C.c_int * 36)()
+        n = lib().mscnn_conv2d_plan_plane_columns(self._p, out, 36)
+        return [int(out[i]) for i in range(n)]
+
+    def debug_wgemm_schedule(self, whole_tiles=False):
+        """Host replay of the plane GEMM's schedule (mscnn_debug_wgemm_schedule): (info dict, rows [n][7] as a numpy array of
+        {slot, plane, column tile, row tile, k0, k1, part}), or None where the plan has no wgemm GEMM."""
+        import numpy as np
+        info = (C.c_int * 8)()
+        n = lib().mscnn_debug_wgemm_schedule(self._p, int(bool(whole_tiles)), None, 0, info)
+        if n < 0:
+            return None
+        rows = np.zeros((max(n, 1), 7), dtype=np.int32)
+        got = lib().mscnn_debug_wgemm_schedule(self._p, int(bool(whole_tiles)), rows.ctypes.data_as(C.c_void_p), n, info)
+        assert got == n
+        keys = ("tiles", "MT", "KI", "G", "full_q", "planes", "BN", "ragged")
+        return {k: int(info[i]) for i, k in enumerate(keys)}, rows[:n]
 
     def set_profiling(self, on=True):
         _check(lib().mscnn_conv2d_plan_set_profiling(self._p, int(on)))
