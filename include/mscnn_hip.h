@@ -546,6 +546,27 @@ MSCNN_API int mscnn_detections_cascade_multi_nms_fwd(const mscnn_detections_desc
                                                      const mscnn_cascade_output* outputs, int R_all, int max_rows_per_image,
                                                      void* pack_dev, int cap, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The proposal half of the scripts' result (run_mscnn_detection.m:75-91, `final_proposals{k}`) for every image of a batched forward
+ * in one pass.  props [R_all][6] = BoxOutput's proposals_score, rows [img x1 y1 x2 y2 score] grouped by image in ascending order;
+ * desc[num_images], one per image.  Per image, in the script's types and order: w = x2 - x1, h = y2 - y1 in fp32 (no + 1); a row
+ * stays iff score >= proposal_thr && w != 0 && h != 0 -- the very predicate the final stage applies to the same rows (a NaN score
+ * goes, -0.0 is zero, a negative extent stays); kept rows go to double and THEN x / ratio_w, w / ratio_w, y / ratio_h, h / ratio_h in
+ * double (unlike the final stage, which divides in fp32: there the script divides before its double()).  Kept rows keep their input
+ * order (BoxOutput's: by score within an image); their places come from a ballot / popcount prefix, never from atomics.
+ * pack_dev: the multi pack above with one slot per image (mscnn_multi_pack_layout_of(num_images, cap), cap >= R_all):
+ *   [int32 num_images, R_all, cap, 0][num_images x int32 {count, rows, row0, 0}][cap x 5 doubles x y w h score][cap x int32 row]
+ * image i owns pack rows [row0_i, row0_i + rows_i) and fills the first count_i; the int column is the ROI row relative to row0_i.
+ * Every word of header and table is written by the kernel, rows of a slot past its count are left as they were.  One launch per
+ * MSCNN_PROPOSALS_IMAGES_PER_LAUNCH images, one workgroup per image, no workspace, no host read, any number of rows per image.
+ * Refused before any launch, naming the value: null pointers, num_images < 1, R_all < 1, cap < R_all, a NaN or non-positive ratio,
+ * a NaN proposal_thr (and a props pointer that is not 8-byte aligned).  This stage has no pin on the reference: its check is a numpy
+ * restatement written from the script. */
+enum { MSCNN_PROPOSALS_IMAGES_PER_LAUNCH = 64 };
+typedef struct { float proposal_thr; double ratio_h, ratio_w; } mscnn_proposals_desc;
+MSCNN_API size_t mscnn_proposals_multi_pack_bytes(int num_images, int cap);
+MSCNN_API int mscnn_proposals_multi_fwd(const mscnn_proposals_desc* desc, int num_images, const float* props, int R_all, void* pack_dev,
+                                        int cap, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Image pre-processing in front of net.forward -- MATLAB `run_mscnn_detection.m:64-69`:
  * imresize(uint8 image, [H W]) (bicubic, uint8 after each 1-D pass), RGB -> BGR, single, subtract the

@@ -239,6 +239,31 @@ MSCNN_NET_API int mscnn_net_detect_multi_device(mscnn_net* net, const mscnn_dete
 MSCNN_NET_API int mscnn_net_unpack_detections_multi(const void* pack_host, int num_images, int num_classes, int cap, double* dets_host,
                                                     int* ids_host, int out_cap, int* seg_dets, int* image_rois);
 
+/* The proposal half of the scripts' result (run_mscnn_detection.m:75-91: `final_proposals{k}`, what the drivers would write to
+ * proposals/<comp_id>.txt and what their `show` path indexes with the detections' ids) for EVERY image of the last forward in one
+ * pass (mscnn_hip.h: mscnn_proposals_multi_fwd), from the net's proposals_score blob on the device.  p[num_images]: of each image's
+ * params only proposal_thr, ratio_h and ratio_w are read.  num_images must equal the input's N.  Output image after image:
+ * props_host[cap][5] doubles [x y w h score] (fp32 extents, filtered as the final stage filters, then divided by the ratios in
+ * double), rows_host[cap] = the row of the net's ROI blobs each came from -- the convention of mscnn_net_detect_multi's ids, so the
+ * script's proposals(bbs_show(:,6),:) is a join on that column --, image_props[num_images] = rows of each image, image_rois[num_images]
+ * (may be NULL) = its ROI count.  Blocking: the kernel writes the pack into host-coherent pinned memory and the call synchronises
+ * once.  More rows than cap is an error naming the numbers.  A net without a proposals_score blob is refused, naming the blob, and
+ * so is a cascade deploy (a net with a DecodeBBox layer, named in the error): its BoxOutput has the blob, but the cascade drivers
+ * output no proposals.  No pin on the reference (no MATLAB): the check is a numpy restatement. */
+MSCNN_NET_API int mscnn_net_proposals_multi(mscnn_net* net, const mscnn_detect_params* p, int num_images, double* props_host,
+                                            int* rows_host, int cap, int* image_props, int* image_rois);
+/* The same into a device pack of mscnn_net_detect_multi_pack_bytes(num_images, 1, cap) bytes (cap >= the forward's ROI count, else an
+ * error); asynchronous on the net's stream, *pack_dev valid until the next detect / proposals call on this net.
+ * mscnn_net_unpack_detections_multi(pack, num_images, 1, cap, ...) reads one host copy of it. */
+MSCNN_NET_API int mscnn_net_proposals_multi_device(mscnn_net* net, const mscnn_detect_params* p, int num_images, int cap,
+                                                   const void** pack_dev);
+/* The RPN-only run: Net::ForwardFromTo(0, L), L = the BoxOutput layer whose second top is proposals_score (written to *last_layer,
+ * may be NULL) -- MS-CNN as a proposal generator, without the detection sub-network.  The ROI pooling's maps are not enqueued under
+ * BoxOutput (nothing of this call reads them), the call is not a whole forward for the numerics watch, and a later mscnn_net_forward
+ * is bit-identical to one on a fresh net.  mscnn_net_proposals_multi then reads the blob as after a whole forward; the detect calls
+ * would read the sub-net's blobs of an EARLIER forward. */
+MSCNN_NET_API int mscnn_net_forward_proposals(mscnn_net* net, int* last_layer);
+
 
 /* Final stage of the cascade drivers (examples/kitti_car/run_cascademscnn.m:84-127) for ONE cascade output nn: the decoded boxes
  * of stage nn (`bbox_blob`, e.g. "output_bbox_3rd"), its in-net probabilities (`prob_blob`, "cls_prob_3rd" / "cls_prob_3rd_avg")

@@ -15,6 +15,7 @@
 #include <cstring>
 #include "common.h"
 #include "box_device.h"
+#include "det_rows.h"
 #include "nms_large.h"
 
 namespace {
@@ -79,7 +80,7 @@ __device__ __forceinline__ bool det_row(const DetArgs& a, int r, DetBox* box, fl
   }
   const float* q = a.props + 6 * (size_t)r;
   const float px = q[1], py = q[2], pw = q[3] - q[1], ph = q[4] - q[2], sc = q[5];
-  if (!(sc >= a.proposal_thr && pw != 0 && ph != 0)) return false;                   // :82
+  if (!det_keep_proposal(sc, pw, ph, a.proposal_thr)) return false;                  // :82 (det_rows.h: shared with proposals.hip)
   const float* bp = a.bbox_pred + (size_t)r * 4 * a.ncls + 4 * (a.cls_id - 1);      // :95
   float b0 = bp[0] * a.stdv[0], b1 = bp[1] * a.stdv[1], b2 = bp[2] * a.stdv[2], b3 = bp[3] * a.stdv[3];
   b0 += a.mean[0]; b1 += a.mean[1]; b2 += a.mean[2]; b3 += a.mean[3];
@@ -388,16 +389,6 @@ __device__ __forceinline__ DetMultiPtrs det_multi_ptrs(const DetSegArgs& a, int 
   p.mask = reinterpret_cast<u64*>(a.ws + 256 * (((size_t)a.num_segs * SEG_WORDS * sizeof(int) + 255) / 256) +
                                   (size_t)a.num_segs * a.seg_stride_box + (size_t)s * a.seg_stride_mask);
   return p;
-}
-
-// first row whose image (column 0) is >= img, over [0, R): rows are grouped by image in ascending order (stride floats per row)
-__device__ __forceinline__ int det_image_lower_bound(const float* __restrict__ props, int R, int img, int stride) {
-  int lo = 0, hi = R;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (props[(size_t)mid * stride] < (float)img) lo = mid + 1; else hi = mid;
-  }
-  return lo;
 }
 
 // one workgroup per segment: find the rows, transform + filter + sort them

@@ -49,6 +49,14 @@ class DetectionsDesc(C.Structure):
                 ("org_h", C.c_double), ("org_w", C.c_double), ("nms_overlap", C.c_double)]
 
 
+class ProposalsDesc(C.Structure):
+    """mscnn_proposals_desc (include/mscnn_hip.h): one per image."""
+    _fields_ = [("proposal_thr", C.c_float), ("ratio_h", C.c_double), ("ratio_w", C.c_double)]
+
+
+PROPOSALS_IMAGES_PER_LAUNCH = 64      # MSCNN_PROPOSALS_IMAGES_PER_LAUNCH
+
+
 class NmsParams(C.Structure):
     """mscnn_nms_params (include/mscnn_hip.h): bbNms's type / ovrDnm / thr and the plain stage's det_thr."""
     _fields_ = [("type", C.c_int), ("ovr_dnm", C.c_int), ("thr", C.c_double), ("det_thr", C.c_float)]
@@ -201,6 +209,9 @@ def lib():
                                                      [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p])
         L.mscnn_detections_cascade_multi_nms_fwd.argtypes = ([C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                                               C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p])
+        L.mscnn_proposals_multi_pack_bytes.restype = C.c_size_t
+        L.mscnn_proposals_multi_pack_bytes.argtypes = [C.c_int, C.c_int]
+        L.mscnn_proposals_multi_fwd.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         _lib = L
     return _lib
 
@@ -793,6 +804,29 @@ def detections_multi(bbox_pred, cls_pred, props, num_images, segments, max_rows_
         _check(lib().mscnn_detections_multi_nms_fwd(descs, _nms_ref(nms), num_images, Cn, _dev(bbox_pred), _dev(cls_pred), _dev(props), R, M,
                                                     _dev(pack), cap, _dev(ws), C.c_size_t(wb), _stream()))
     out = _read_multi_pack(pack, S, Cn, R, cap, "detections_multi")
+    return (out, pack.cpu().numpy()) if raw_pack else out
+
+
+def proposals_multi(props, images, raw_pack=False, pack=None):
+    """The proposal half of the scripts' result for every image in one pass (mscnn_proposals_multi_fwd).  props: [R, 6] cuda tensor,
+    BoxOutput's proposals_score layout, rows grouped by image; images: one dict per image, ratios=(ratio_h, ratio_w) and optionally
+    proposal_thr (-10).  Returns [(props[n,5] float64 x y w h score, rows relative to row0, row0, rows)] per image; raw_pack: (that,
+    the pack's bytes as a numpy array).  pack: a uint8 cuda tensor to write into (at least the pack's bytes; default: a zero-filled
+    one of exactly that size) -- what lies behind the pack's bytes is the caller's."""
+    R = props.shape[0]
+    B = len(images)
+    descs = (ProposalsDesc * max(B, 1))()
+    for i, kw in enumerate(images):
+        descs[i].proposal_thr = kw.get("proposal_thr", -10.0)
+        descs[i].ratio_h, descs[i].ratio_w = kw.get("ratios", (1.0, 1.0))
+    cap = R
+    nbytes = lib().mscnn_proposals_multi_pack_bytes(B, cap)
+    if pack is None:
+        pack = torch.zeros(nbytes, dtype=torch.uint8, device=props.device)
+    elif pack.numel() < nbytes or pack.dtype != torch.uint8:
+        raise MscnnError(f"proposals_multi: the pack needs {nbytes} uint8, got {pack.numel()} {pack.dtype}")
+    _check(lib().mscnn_proposals_multi_fwd(descs, B, _dev(props), R, _dev(pack), cap, _stream()))
+    out = _read_multi_pack(pack[:nbytes], B, 1, R, cap, "proposals_multi")
     return (out, pack.cpu().numpy()) if raw_pack else out
 
 

@@ -897,6 +897,78 @@ int mscnn_net_detect_multi(mscnn_net* n, const mscnn_detect_params* p, int num_i
   });
 }
 
+// The nets whose drivers have a proposal result: a proposals_score blob, and no cascade stage behind it.  (The cascade deploys carry
+// the blob too -- their BoxOutput is the plain nets' --, but run_cascademscnn.m never reads it: proposals for the cascade outputs are
+// not restated, so a net with a DecodeBBox layer is refused by that layer's name instead of being answered with the first stage's.)
+static int proposals_rows_checked(const mscnn_net* n) {
+  CHECK(n->net->has_blob("proposals_score")) << "net has no proposals_score blob: nothing to take the proposals from";
+  const auto& layers = n->net->layers();
+  for (size_t l = 0; l < layers.size(); ++l)
+    CHECK(std::strcmp(layers[l]->type(), "DecodeBBox") != 0)
+        << "net is a cascade deploy (DecodeBBox layer " << n->net->layer_names()[l] << "): the cascade drivers output no proposals, "
+        << "its proposals_score is not restated";
+  return n->net->blob_by_name("proposals_score")->num();
+}
+
+// The proposal result of the last forward (mscnn_hip.h: mscnn_proposals_multi_fwd) into the multi pack with one slot per image, at
+// pack_at (device-addressable) or in the net's device pack.  Everything that can be refused is refused before the launch.
+static bool proposals_into_pack(mscnn_net* n, const mscnn_detect_params* p, int num_images, int cap, char* pack_at, char** pack_out) {
+  CHECK(p != nullptr) << "proposals_multi: null params";
+  CHECK_GE(num_images, 1) << "proposals_multi: " << num_images << " images";
+  proposals_rows_checked(n);
+  const int num = n->net->num_inputs() > 0 && n->net->input_blobs()[0]->num_axes() == 4 ? n->net->input_blobs()[0]->num() : 1;
+  CHECK_EQ(num_images, num) << "proposals_multi: num_images " << num_images << " but the net's input holds " << num << " images";
+  auto props = n->net->blob_by_name("proposals_score");
+  const int R_all = props->num();
+  CHECK_GE(R_all, 1) << "proposals_score has no rows: no forward has run";
+  CHECK_EQ(props->count() / R_all, 6) << "proposals_score rows are [img x1 y1 x2 y2 score]";
+  CHECK_GE(cap, R_all) << "proposal pack capacity " << cap << " < " << R_all << " ROIs (size it by BoxOutput's max_nms_num x images)";
+  std::vector<mscnn_proposals_desc> desc(num_images);
+  for (int i = 0; i < num_images; ++i) desc[i] = mscnn_proposals_desc{p[i].proposal_thr, p[i].ratio_h, p[i].ratio_w};
+  char* pack = pack_at ? pack_at : static_cast<char*>(n->det_pack.Reserve(mscnn_multi_pack_layout_of(num_images, cap).total));
+  MSCNN_CHECK(mscnn_proposals_multi_fwd(desc.data(), num_images, props->gpu_data(), R_all, pack, cap, Caffe::stream()));
+  *pack_out = pack;
+  return pack == pack_at;
+}
+
+int mscnn_net_proposals_multi(mscnn_net* n, const mscnn_detect_params* p, int num_images, double* props_host, int* rows_host, int cap,
+                              int* image_props, int* image_rois) {
+  return guarded([&] {
+    CHECK(p && image_props) << "proposals_multi: null pointer";
+    CHECK_GE(num_images, 1) << "proposals_multi: " << num_images << " images";
+    detect_segments_blocking(
+        n, "proposals_multi", num_images, 1,
+        [&] { return proposals_rows_checked(n); },
+        [&](int pcap, char* pack_at, char** pack) { return proposals_into_pack(n, p, num_images, pcap, pack_at, pack); }, props_host,
+        rows_host, cap, image_props, image_rois);
+  });
+}
+
+int mscnn_net_proposals_multi_device(mscnn_net* n, const mscnn_detect_params* p, int num_images, int cap, const void** pack_dev) {
+  return guarded([&] {
+    CHECK(pack_dev != nullptr);
+    char* pack = nullptr;
+    proposals_into_pack(n, p, num_images, cap, nullptr, &pack);
+    *pack_dev = pack;
+  });
+}
+
+int mscnn_net_forward_proposals(mscnn_net* n, int* last_layer) {
+  return guarded([&] {
+    int L = -1;
+    const auto& layers = n->net->layers();
+    const Blob<float>* want = n->net->has_blob("proposals_score") ? n->net->blob_by_name("proposals_score").get() : nullptr;
+    for (size_t l = 0; l < layers.size() && L < 0 && want; ++l)
+      if (std::strcmp(layers[l]->type(), "BoxOutput") == 0 && n->net->top_vecs()[l].size() >= 2 && n->net->top_vecs()[l][1] == want)
+        L = (int)l;
+    CHECK_GE(L, 0) << "net has no BoxOutput layer whose second top is proposals_score";
+    // (a range that ends in front of the sub-net: BoxOutput's before-sync hook sees last_end_ < its convolution and builds no ROI
+    // maps, and `whole` is false for the numerics watch -- Net::ForwardFromTo)
+    n->net->ForwardFromTo(0, L);
+    if (last_layer) *last_layer = L;
+  });
+}
+
 int mscnn_net_reshape_input(mscnn_net* n, const char* name, const int* dims, int ndim) {
   return guarded([&] {
     CHECK(n->net->has_blob(name)) << "Unknown blob name " << name;

@@ -92,6 +92,8 @@ def lib():
             "mscnn_net_detect_cascade_multi": [vp, vp, ci, ci, ci, vp, vp, vp, C.c_float, vp, vp, ci, vp, vp],
             "mscnn_net_detect_cascade_multi_pack_bytes": [ci, ci, ci, ci],
             "mscnn_net_detect_cascade_multi_device": [vp, vp, ci, ci, ci, vp, vp, vp, C.c_float, ci, vp],
+            "mscnn_net_proposals_multi": [vp, vp, ci, vp, vp, ci, vp, vp], "mscnn_net_proposals_multi_device": [vp, vp, ci, ci, vp],
+            "mscnn_net_forward_proposals": [vp, vp],
         }
         for name, args in sig.items():
             getattr(L, name).argtypes = args
@@ -329,6 +331,13 @@ class Net:
         else:
             _check(lib().mscnn_net_forward_from_to(self._h, start, end))
 
+    def forward_proposals(self):
+        """mscnn_net_forward_proposals: the RPN-only run -- the layers up to the BoxOutput layer that writes proposals_score, without
+        the detection sub-network.  Returns that layer's index.  proposals_multi then reads the blob as after a whole forward."""
+        last = C.c_int(-1)
+        _check(lib().mscnn_net_forward_proposals(self._h, C.byref(last)))
+        return last.value
+
     def reshape(self):
         _check(lib().mscnn_net_reshape(self._h))
 
@@ -496,6 +505,29 @@ class Net:
         p = self._multi_params(params, classes)
         ptr = C.c_void_p()
         _check(lib().mscnn_net_detect_multi_device(self._h, p, len(params), len(classes), cap, C.byref(ptr)))
+        return ptr.value
+
+    def proposals_multi(self, params, cap=None):
+        """mscnn_net_proposals_multi: the proposal half of the scripts' result (run_mscnn_detection.m:75-91, final_proposals{k}) of
+        every image of the last forward in one pass.  params: one dict per image of the batch (ratios, optionally proposal_thr; the
+        dicts set_images returns work as they are).  Returns ([(props [n, 5] float64 [x y w h score], rows [n] int32 = rows of the
+        net's ROI blobs, the convention of detect_multi's ids) per image], [ROI count per image])."""
+        B = len(params)
+        if cap is None:
+            cap = max(1, self.blob_shape("proposals_score")[0]) if "proposals_score" in self.blob_names else 1
+        p = self._multi_params([{k: v for k, v in kw.items() if k in ("ratios", "proposal_thr")} for kw in params], [1], org_hw=(0, 0))
+        props = np.zeros((max(cap, 1), 5), np.float64); rows = np.zeros(max(cap, 1), np.int32)
+        cnt = np.zeros(max(B, 1), np.int32); rois = np.zeros(max(B, 1), np.int32)
+        _check(lib().mscnn_net_proposals_multi(self._h, p, B, props.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p), cap,
+                                               cnt.ctypes.data_as(C.c_void_p), rois.ctypes.data_as(C.c_void_p)))
+        return [seg[0] for seg in _split_segments(props, rows, cnt, B, 1)], rois[:B].tolist()
+
+    def proposals_multi_device(self, params, cap):
+        """mscnn_net_proposals_multi_device: the same into the device pack (detect_multi_pack_bytes(B, 1, cap) bytes); asynchronous.
+        Returns its device address; unpack_detections_multi(pack, B, 1, cap) reads a host copy of it."""
+        p = self._multi_params([{k: v for k, v in kw.items() if k in ("ratios", "proposal_thr")} for kw in params], [1], org_hw=(0, 0))
+        ptr = C.c_void_p()
+        _check(lib().mscnn_net_proposals_multi_device(self._h, p, len(params), cap, C.byref(ptr)))
         return ptr.value
 
     def detect(self, cls_id, ratios, org_hw, bbox_mean=(0, 0, 0, 0), bbox_std=(0.1, 0.1, 0.2, 0.2), proposal_thr=-10.0,

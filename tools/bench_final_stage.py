@@ -11,7 +11,13 @@ op calls (hipapi.detections_cascade on each image's rows of the device blobs, ro
 timed region, each call ending with its detections on the host).
 
 --nms-type max / --ovr-dnm min set bbNms's knobs on the net first (Net.set_nms; both forms honour the setting, so the bit-for-bit check
-between them stays) and name the setting in the table's header; without them no set_nms call is made at all."""
+between them stays) and name the setting in the table's header; without them no set_nms call is made at all.
+
+--proposals is the proposal half of the scripts' result (run_mscnn_detection.m:75-91) on the same forwards: the copy of the blob to the
+host (get_blob("proposals_score")) + the numpy restatement of those lines, image after image, against one mscnn_net_proposals_multi --
+both end with every image's proposals on the host, are checked bit for bit every step, and alternate which runs first.  Cases:
+caltech B = 8 and kitti_car 7s-576 B = 2.  Then the step time of the RPN-only run (mscnn_net_forward_proposals) against the whole
+forward on kitti_car 7s-576, B = 1, device idle before and synchronised after each, the two alternating."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -102,7 +108,80 @@ def cascade_leg(a):
         del n
 
 
+def proposals_numpy(ps, params):
+    """run_mscnn_detection.m:75-91 in numpy on the host copy of proposals_score [R, 6], image after image -> [(props, rows)]."""
+    ps = ps.reshape(-1, 6)
+    img = ps[:, 0]
+    out = []
+    for i, kw in enumerate(params):
+        row0, row1 = np.searchsorted(img, np.float32(i), "left"), np.searchsorted(img, np.float32(i + 1), "left")
+        tmp = ps[row0:row1, 1:].copy()
+        tmp[:, 2] -= tmp[:, 0]; tmp[:, 3] -= tmp[:, 1]                                     # :78, single
+        keep = np.flatnonzero((tmp[:, 4] >= np.float32(kw.get("proposal_thr", -10.0))) & (tmp[:, 2] != 0) & (tmp[:, 3] != 0))   # :82
+        pr = tmp[keep].astype(np.float64)                                                  # :86
+        pr[:, 0] /= kw["ratios"][1]; pr[:, 2] /= kw["ratios"][1]                          # :87-90
+        pr[:, 1] /= kw["ratios"][0]; pr[:, 3] /= kw["ratios"][0]
+        out.append((pr, (keep + row0).astype(np.int32)))
+    return out
+
+
+def proposals_leg(a):
+    import torch
+    print(f"# proposal result per step, host wall ms (median over {a.steps} steps after {a.warmup} warm-up), regime {a.regime}")
+    print(f"# {'case':20s} {'B':>2s} {'ROIs':>6s} {'props':>6s} {'get_blob + numpy ms':>20s} {'one-pass ms':>12s} {'saved ms':>9s}")
+    for name in a.case or ["caltech-f32-b8", "kitti_car-7s576-b2"]:
+        model, B, dtype, _, org = CASES[name]
+        n = mnet.Net(prototxt_text=zoo.prototxt(model, batch=B))
+        synth.load_into(n, a.regime)
+        if dtype != "f32":
+            n.set_precision(dtype)
+        _, _, H, W = n.blob_shape("data")
+        frames = [np.concatenate([synth.frame(H, W, seed=1701 + 13 * i + b, org_hw=org) for b in range(B)], 0) for i in range(2)]
+        params = [dict(ratios=(H / float(org[0]), W / float(org[1])))] * B
+        t_np, t_one, Rs, Ps = [], [], [], []
+        for step in range(a.warmup + a.steps):
+            n.set_blob("data", frames[step % 2])
+            n.forward()
+            n.get_blob("proposals")        # (the forward has finished before either form starts)
+            res = [None, None]
+            dt = [0.0, 0.0]
+            for f in (0, 1) if step % 2 == 0 else (1, 0):
+                t0 = time.perf_counter()
+                res[f] = proposals_numpy(n.get_blob("proposals_score"), params) if f == 0 else n.proposals_multi(params)[0]
+                dt[f] = time.perf_counter() - t0
+            for (p0, r0), (p1, r1) in zip(*res):
+                assert np.array_equal(p0.view(np.uint64), p1.view(np.uint64)) and np.array_equal(r0, r1), (name, step)
+            if step >= a.warmup:
+                t_np.append(dt[0]); t_one.append(dt[1])
+                Rs.append(n.blob_shape("proposals_score")[0]); Ps.append(sum(len(p) for p, _ in res[1]))
+        m0, m1 = 1e3 * float(np.median(t_np)), 1e3 * float(np.median(t_one))
+        print(f"  {name:20s} {B:2d} {np.mean(Rs):6.0f} {np.mean(Ps):6.0f} {m0:20.3f} {m1:12.3f} {m0 - m1:9.3f}", flush=True)
+        del n
+    model, org = "kitti_car/mscnn-7s-576", (375, 1242)
+    n = mnet.Net(prototxt_text=zoo.prototxt(model))
+    synth.load_into(n, a.regime)
+    _, _, H, W = n.blob_shape("data")
+    frames = [synth.frame(H, W, seed=1701 + 13 * i, org_hw=org) for i in range(2)]
+    t = [[], []]
+    for step in range(a.warmup + a.steps):
+        for f in (0, 1) if step % 2 == 0 else (1, 0):
+            n.set_blob("data", frames[step % 2])
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            n.forward() if f == 0 else n.forward_proposals()
+            torch.cuda.synchronize()
+            if step >= a.warmup:
+                t[f].append(time.perf_counter() - t0)
+    m0, m1 = 1e3 * float(np.median(t[0])), 1e3 * float(np.median(t[1]))
+    print(f"# step time, host wall ms from an idle device to a synchronised one (median over {a.steps} steps after {a.warmup} warm-up), "
+          f"{model} B = 1, regime {a.regime}, {n.blob_shape('proposals_score')[0]} ROIs")
+    print(f"# {'whole forward ms':>18s} {'forward_proposals ms':>22s} {'saved ms':>9s}")
+    print(f"  {m0:18.3f} {m1:22.3f} {m0 - m1:9.3f}", flush=True)
+
+
 ap = argparse.ArgumentParser()
+ap.add_argument("--proposals", action="store_true", help="the proposal result: get_blob + numpy against one proposals_multi, and the "
+                "RPN-only run against the whole forward")
 ap.add_argument("--cascade", action="store_true", help="the cascade deploys: per-call detect_cascade against one detect_cascade_multi")
 ap.add_argument("--steps", type=int, default=30)
 ap.add_argument("--warmup", type=int, default=5)
@@ -115,6 +194,9 @@ ap.add_argument("--ovr-dnm", default="union", choices=("union", "min"), help="bb
 a = ap.parse_args()
 if a.cascade:
     cascade_leg(a)
+    sys.exit(0)
+if a.proposals:
+    proposals_leg(a)
     sys.exit(0)
 if a.case is None:
     a.case = list(CASES)

@@ -9,6 +9,7 @@ examples/kitti_result/writeDetForEval.m.
   python tools/run_mscnn_detection.py --prototxt mscnn_deploy.prototxt --weights model.caffemodel --images /KITTI/testing/image_2
          [--out detections] [--comp-id kitti_7s_576] [--cls-ids 2] [--names bg,car,van,truck,tram] [--precision f32|f16x3|f16]
          [--labels-dir results/data] [--limit N] [--batch B]
+         [--proposals-out proposals] [--proposals-only]      # the proposal half of the result: proposals/<comp_id>.txt (:154, :161-162)
          [--nms-type maxg|max] [--ovr-dnm union|min] [--nms-thr T] [--det-thr T]      # pNms.type / pNms.ovrDnm / bbNms's thr, and
                                                              # the det_thr of the WiderFace plain flow (Net.set_nms, once per run)
   python tools/run_mscnn_detection.py --model kitti_car/mscnn-7s-576 --synthetic 8      # no dataset / weights at hand: the generated
@@ -18,8 +19,13 @@ examples/kitti_result/writeDetForEval.m.
 pre-processed in one call (Net.set_images) and its final stage runs for every frame and class in one pass (Net.detect_multi); the
 output files are the same, avgtime stays per frame.
 
+--proposals-out DIR also writes what the scripts build as final_proposals (:75-91, :154, :161-162 -- the dlmwrite the reference ships
+commented out): DIR/<comp_id>.txt, rows [image_index x y w h score], every image's proposals filtered as the final stage filters them
+and rescaled to the original image (Net.proposals_multi: one pass per forward, batch 1 and --batch B).  --proposals-only runs MS-CNN
+as a proposal generator: the layers up to BoxOutput (Net.forward_proposals), no detect call, no detection files.
+
 Everything here is host glue over calls the test-suite covers one by one (Net.set_image / set_images, forward, detect / detect_multi,
-kitti.write_*)."""
+proposals_multi, kitti.write_*)."""
 import argparse
 import glob
 import os
@@ -89,7 +95,13 @@ def parse_args(argv=None):
     ap.add_argument("--nms-thr", type=float, default=None, help="bbNms's thr: drop rows with prob <= this before the NMS (default -inf)")
     ap.add_argument("--det-thr", type=float, default=0.0, help="> 0: drop rows under this probability before the NMS "
                     "(widerface/run_mscnn_detection.m:139-143)")
+    ap.add_argument("--proposals-out", default="", help="directory for <comp_id>.txt: rows [image_index x y w h score] of every image's "
+                    "filtered, rescaled proposals (final_proposals of the scripts)")
+    ap.add_argument("--proposals-only", action="store_true", help="run the net up to BoxOutput only (Net.forward_proposals): no detect "
+                    "call, no detection files; needs --proposals-out")
     a = ap.parse_args(argv)
+    if a.proposals_only and not a.proposals_out:
+        ap.error("--proposals-only needs --proposals-out DIR")
     if not (a.prototxt or a.model) or not (a.images or a.synthetic):
         ap.error("need --prototxt or --model, and --images or --synthetic N")
     return a
@@ -119,8 +131,10 @@ def main(argv=None):
     if a.batch < 1:
         ap.error("--batch must be >= 1")
     per_class = {c: [] for c in cls_ids}
+    per_image_props = []
+    forward = net.forward_proposals if a.proposals_only else net.forward
     if a.batch > 1:
-        return run_batched(a, net, files, names, cls_ids, imgH, imgW, per_class)
+        return run_batched(a, net, files, names, cls_ids, imgH, imgW, per_class, per_image_props, forward)
     used = 0.0
     for k, path in enumerate(files, start=1):
         img = load_frame(path, k)
@@ -130,23 +144,25 @@ def main(argv=None):
         net.set_image("data", dev_img)                                       # :64-69 on the device
         torch.cuda.synchronize(a.device)
         t0 = time.perf_counter()
-        net.forward()
+        forward()
         torch.cuda.synchronize(a.device)
         used += time.perf_counter() - t0                                      # :72-73: forward only
+        if a.proposals_out:                                                   # :75-91
+            per_image_props.append(net.proposals_multi([dict(ratios=ratios, proposal_thr=a.proposal_thr)])[0][0][0])
         by_type = {}
-        for c in cls_ids:
+        for c in () if a.proposals_only else cls_ids:
             dets, _, _ = net.detect(cls_id=c, ratios=ratios, org_hw=(orgH, orgW), proposal_thr=a.proposal_thr, nms_overlap=a.nms_overlap)
             per_class[c].append(dets)
             by_type[{"car": "Car", "ped": "Pedestrian", "cyc": "Cyclist"}.get(names[c - 1], names[c - 1])] = dets
-        if a.labels_dir:                                                      # writeDetForEval.m:88-89: the frame's own KITTI id
+        if a.labels_dir and not a.proposals_only:                             # writeDetForEval.m:88-89: the frame's own KITTI id
             kitti.write_kitti_labels(a.labels_dir, frame_id(path, k), by_type)
         if k % 100 == 0 or k == len(files):
             print(f"idx {k}/{len(files)}, avgtime={used / k:.4f}s")           # :147
-    write_results(a, names, cls_ids, per_class, len(files))
+    finish(a, names, cls_ids, per_class, per_image_props, len(files))
     return 0
 
 
-def run_batched(a, net, files, names, cls_ids, imgH, imgW, per_class):
+def run_batched(a, net, files, names, cls_ids, imgH, imgW, per_class, per_image_props, forward):
     """--batch B: groups of B frames through set_images -> forward -> one detect_multi; results in frame order."""
     import torch
     from mscnn_amd import kitti
@@ -160,9 +176,16 @@ def run_batched(a, net, files, names, cls_ids, imgH, imgW, per_class):
         params = net.set_images("data", dev_imgs)                           # :63-69 for every frame of the group, on the device
         torch.cuda.synchronize(a.device)
         t0 = time.perf_counter()
-        net.forward()
+        forward()
         torch.cuda.synchronize(a.device)
         used += time.perf_counter() - t0                                      # :72-73: forward only
+        if a.proposals_out:                                                   # :75-91 for every frame of the group
+            per_image_props += [pr for pr, _ in net.proposals_multi([dict(p, proposal_thr=a.proposal_thr) for p in params])[0]]
+        if a.proposals_only:
+            k = g0 + len(group)
+            if k % 100 < len(group) or k == len(files):
+                print(f"idx {k}/{len(files)}, avgtime={used / k:.4f}s")
+            continue
         per_image, _ = net.detect_multi([dict(p, proposal_thr=a.proposal_thr, nms_overlap=a.nms_overlap) for p in params], cls_ids)
         for i, path in enumerate(group):
             k = g0 + i + 1
@@ -175,8 +198,24 @@ def run_batched(a, net, files, names, cls_ids, imgH, imgW, per_class):
                 kitti.write_kitti_labels(a.labels_dir, frame_id(path, k), by_type)
             if k % 100 == 0 or k == len(files):
                 print(f"idx {k}/{len(files)}, avgtime={used / (g0 + len(group)):.4f}s")   # per frame
-    write_results(a, names, cls_ids, per_class, len(files))
+    finish(a, names, cls_ids, per_class, per_image_props, len(files))
     return 0
+
+
+def finish(a, names, cls_ids, per_class, per_image_props, n_files):
+    if not a.proposals_only:
+        write_results(a, names, cls_ids, per_class, n_files)
+    if a.proposals_out:
+        out = write_proposals(a.proposals_out, a.comp_id, per_image_props)
+        print(f"{out}: {sum(len(p) for p in per_image_props)} proposals over {n_files} images")
+
+
+def write_proposals(out_dir, comp_id, per_image_props):
+    """dlmwrite(['proposals/' comp_id '.txt'], final_proposals) (:154, :161-162): rows [image_index x y w h score], %.5g."""
+    from mscnn_amd import kitti
+    out = os.path.join(out_dir, f"{comp_id}.txt")
+    kitti.write_detections_dlm(out, per_image_props)
+    return out
 
 
 def write_results(a, names, cls_ids, per_class, n_files):
