@@ -12,6 +12,44 @@
  * reference's glog convention (device_alternate.hpp:48-67).
  *
  * There is NO CPU fallback behind any of these functions.
+ *
+ * BUFFER CONTRACT (tests/test_gpu_buffer_contract.py holds every op to it, between guard bands and on poisoned memory):
+ * workspaces and outputs may hold anything on entry -- an op initialises, on its own stream, every word it later reads, and
+ * writes every element of its output (exceptions are stated at the op: pack rows past a slot's count, rows past count_out);
+ * no op writes outside [p, p + bytes) of any buffer, where bytes is the tensor's size or what the op's *_bytes() query
+ * returned, and none reads outside its inputs; no op writes through a const pointer.  Nothing waits on workspace contents of an
+ * earlier call (the stream-K hand-off flags of the plane GEMM are tagged per launch and polled a bounded number of times).
+ *
+ * ALIGNMENT.  hipMalloc's 256 bytes satisfy every op.  Tighter than that, every pointer is in one of three classes: it needs only
+ * its element type's own alignment (4 bytes for a float blob; "4" below); the op FALLS BACK to a slower kernel with the same result;
+ * or the op REFUSES it with MSCNN_ERR_BAD_ARG before its first launch, so that nothing is stored through it and no workspace is touched.
+ *   every op                   workspaces, packed weights (packed, wt, w16), prepared_maps, pack_dev: 16, refuses
+ *   conv2d_fwd / _fwd_pool / _fwd_chain / _fwd_roipool_pair, by the plan's kernel (mscnn_conv2d_plan_kernel); w, bias, y_pool 4
+ *     igemm_* (direct, ROI mode), igemm16_*, head4x4_*, head_kwfold_*, wconv_64x512_k3x3, direct_f32     x, y 4
+ *     igemm16x3_* (split-fp16 direct)   y 4; x 16 for its max |x| pass, refuses (x 4 where in_bound hands max |x| over)
+ *     igemm_*_vec (a 1x1 layer on 128-pixel rows), head_gemm_shiftadd_f32 on such rows                                 x 16: refuses
+ *     conv3x3_c3_valu_f32        x, y 16: refuses
+ *     winograd2x2_fused_k3x3_c64 x 16, y 8: refuses
+ *     winograd_f4x4_3x3          x 16, y 16, y_pool 8: falls back to its scalar transforms; _fwd_chain with a next plan: y 16, refuses
+ *     winograd_f3x3_3x3          x, y 4 on whole planes; on maps of <= 64 pixels x 16, y 16: falls back (scalar staging);
+ *                                with y_pool: y 8 where Wo is even, refuses
+ *     winograd_f2x2_3x3          x 4; y 8 where Wo is even: refuses
+ *     winograd_f3x3_3x3_x3f16_*, head_gemm_shiftadd_x3f16   x 16 (the max |x| pass), refuses; y as winograd_f3x3_3x3
+ *   conv2d_pack_weights        w 4; for a split-fp16 plan w 16 (the max |w| pass): refuses
+ *   roipool_maps_build         feat 4
+ *   relu_fwd                   4; the float4 kernel runs when x, y are 16-byte aligned and count % 4 == 0: falls back
+ *   pool2d_fwd                 4; the 2x2 / stride 2 fast path needs x 16, y 8: falls back
+ *   inner_product_fwd_f32      4; the MFMA GEMM (N >= 64) needs x, w 16 and K % 4 == 0: falls back to the row-wise / generic kernel
+ *   inner_product_fwd_f16      x 16: refuses; y, bias 4
+ *   inner_product_x3_fwd / _pack   x resp. w 16: refuses; y, bias 4
+ *   inner_product_wg_fwd       x 16: refuses; y, bias 4; _wg_pack: w 4
+ *   deconv_depthwise_fwd       4; the 4x4 / stride 2 / pad 1 quad kernel needs y 8: falls back to the per-output kernel
+ *   concat_channels, softmax, eltwise, deconv2d (generic), roipool, roipool_pair, roialign, decodebbox, preprocess* (images, out),
+ *   max_rel_diff*, sum_squares, store_words      4 (doubles 8)
+ *   nms_greedy                 boxes 16: refuses; keep_out 1
+ *   boxoutput*                 heads, rois_out, props_out, anchor_ids_out, count_out_dev 4
+ *   detections*                blobs, ids_out, count_out_dev 4; dets_out 8: refuses
+ *   proposals_multi_fwd        props 8: refuses
  */
 #ifndef MSCNN_HIP_H_
 #define MSCNN_HIP_H_
@@ -164,7 +202,9 @@ MSCNN_API int mscnn_conv2d_plan_set_batch(mscnn_conv_plan* plan, int N);
  * mscnn_conv2d_plan_set_batch may select a different kernel family for the new batch (e.g. ROI count crossing the
  * Winograd threshold): when this value changes, call mscnn_conv2d_pack_weights again before the next forward. */
 MSCNN_API unsigned long long mscnn_conv2d_plan_weight_layout(const mscnn_conv_plan* plan);
+/* Alignment: packed 16 (refused); w 4, split-fp16 plans 16 (refused). */
 MSCNN_API int mscnn_conv2d_pack_weights(const mscnn_conv_plan* plan, const float* w, float* packed, void* stream);
+/* Alignment: packed, workspace 16 (refused); x, y by the plan's kernel -- 4 for the direct kernels, see ALIGNMENT at the top. */
 MSCNN_API int mscnn_conv2d_fwd_f32(const mscnn_conv_plan* plan, const float* x, const float* w, const float* packed,
                          const float* bias, float* y, void* workspace, size_t workspace_bytes, void* stream);
 /* Convolution (+ the plan's ReLU) with the following PoolingLayer (MAX, kernel 2, stride 2, pad 0, ceil mode:
@@ -172,22 +212,26 @@ MSCNN_API int mscnn_conv2d_fwd_f32(const mscnn_conv_plan* plan, const float* x, 
  * y_pool[N][Cout][ceil(Ho/2)][ceil(Wo/2)].  Only for plans where mscnn_conv2d_plan_can_pool() is 1 (the trunk
  * kernels); bit-identical to mscnn_conv2d_fwd_f32 followed by mscnn_pool2d_fwd_f32.  y_pool == NULL: plain forward. */
 MSCNN_API int mscnn_conv2d_plan_can_pool(const mscnn_conv_plan* plan);
+/* Alignment: as mscnn_conv2d_fwd_f32; y_pool 4 (F(4x4,3x3): 8, falls back). */
 MSCNN_API int mscnn_conv2d_fwd_pool_f32(const mscnn_conv_plan* plan, const float* x, const float* w, const float* packed,
                               const float* bias, float* y, float* y_pool, void* workspace, size_t workspace_bytes,
                               void* stream);
 
 /* ReLU -- ReLULayer::Forward_gpu (relu_layer.cu:9-26); in place allowed (y == x). */
+/* Alignment: 4; falls back from the float4 kernel. */
 MSCNN_API int mscnn_relu_fwd_f32(const float* x, float* y, size_t count, float negative_slope, void* stream);
 
 /* Pooling -- PoolingLayer::Forward_gpu (pooling_layer.cu:11-47 MAX, :50-81 AVE; output size
  * pooling_layer.cpp:90-107, ceil mode).  method: 0 MAX, 1 AVE.  The argmax mask the reference
  * also writes is not produced (unused at TEST). */
 MSCNN_API int mscnn_pool_out_dim(int in, int kernel, int pad, int stride);
+/* Alignment: 4; the 2x2 / stride 2 fast path (x 16, y 8) falls back. */
 MSCNN_API int mscnn_pool2d_fwd_f32(const float* x, float* y, int N, int C, int H, int W, int kernel_h, int kernel_w,
                          int pad_h, int pad_w, int stride_h, int stride_w, int method, void* stream);
 
 /* InnerProduct -- InnerProductLayer::Forward_gpu (inner_product_layer.cu:10-31):
  * y[M,N] = x[M,K] * w[N,K]^T + bias[N]  (transpose_ = false), optional fused ReLU. */
+/* Alignment: 4; the MFMA GEMM (x, w 16) falls back to the row-wise / generic kernel. */
 MSCNN_API int mscnn_inner_product_fwd_f32(const float* x, const float* w, const float* bias, float* y,
                                 int M, int N, int K, int relu, void* stream);
 /* dev / test knob of the small-N kernel behind it (cls_pred / bbox_pred): rows of x per workgroup, 2, 4 or 8 (0 = the default: 4 for
@@ -203,6 +247,7 @@ MSCNN_API int mscnn_inner_product_wg_supported(int M, int N, int K);
 MSCNN_API size_t mscnn_inner_product_wg_packed_bytes(int N, int K);
 MSCNN_API size_t mscnn_inner_product_wg_workspace_bytes(int M, int N, int K);
 MSCNN_API int mscnn_inner_product_wg_pack(const float* w, float* wt, int N, int K, void* stream);
+/* Alignment: x, wt, workspace 16 (refused); y, bias 4. */
 MSCNN_API int mscnn_inner_product_wg_fwd(const float* x, const float* wt, const float* bias, float* y, int M, int N, int K, int relu,
                                          void* workspace, size_t workspace_bytes, void* stream);
 /* Health of the plane-GEMM kernel's stream-K hand-off (the Winograd layers and the _wg InnerProduct above).  Where a launch splits
@@ -240,25 +285,30 @@ MSCNN_API int mscnn_inner_product_x3_supported(int N, int K);
 MSCNN_API size_t mscnn_inner_product_x3_packed_bytes(int N, int K);
 MSCNN_API size_t mscnn_inner_product_x3_workspace_bytes(int M, int N, int K);
 MSCNN_API int mscnn_inner_product_x3_pack(const float* w, void* packed, int N, int K, void* stream);
+/* Alignment: x, packed, workspace 16 (refused; _pack: w, packed 16); y, bias 4. */
 MSCNN_API int mscnn_inner_product_x3_fwd(const float* x, const void* packed, const float* bias, float* y, int M, int N, int K, int relu,
                                const uint32_t* in_bound, void* workspace, size_t workspace_bytes, void* stream);
 MSCNN_API int mscnn_inner_product_f16_supported(int N, int K);
 MSCNN_API int mscnn_inner_product_pack_f16(const float* w, void* w16, int N, int K, void* stream);
+/* Alignment: x, w16 16 (refused); y, bias 4. */
 MSCNN_API int mscnn_inner_product_fwd_f16(const float* x, const void* w16, const float* bias, float* y, int M, int N, int K, int relu,
                                           void* stream);
 
 /* Concat along channels -- ConcatLayer::Forward_gpu (concat_layer.cu:9-46).
  * Copies x[N, C, inner] into y[N, C_total, inner] at channel offset c_offset. */
+/* Alignment: 4. */
 MSCNN_API int mscnn_concat_channels_f32(const float* x, float* y, int N, int C, int inner, int C_total, int c_offset, void* stream);
 
 /* Deconvolution -- DeconvolutionLayer::Forward_gpu (deconv_layer.cu:8-23), depthwise case used by the
  * "-2x" deploy nets (group == Cin == Cout, w[C][1][Kh][Kw], no bias or bias[C]). */
+/* Alignment: 4; the 4x4 / stride 2 / pad 1 quad kernel (y 8) falls back. */
 MSCNN_API int mscnn_deconv_depthwise_fwd_f32(const float* x, const float* w, const float* bias, float* y,
                                    int N, int C, int H, int W, int Kh, int Kw, int pad_h, int pad_w,
                                    int stride_h, int stride_w, void* stream);
 
 /* Deconvolution, general case (any group / stride / pad; w[Cin][Cout/group][Kh][Kw], base_conv_layer.cpp:135-140 with
  * reverse_dimensions()); routes the depthwise case to the kernel above. */
+/* Alignment: 4 (the depthwise case as above). */
 MSCNN_API int mscnn_deconv2d_fwd_f32(const float* x, const float* w, const float* bias, float* y, int N, int Cin, int H, int W,
                                      int Cout, int Kh, int Kw, int pad_h, int pad_w, int stride_h, int stride_w, int group,
                                      void* stream);
@@ -277,6 +327,7 @@ MSCNN_API int mscnn_store_words_i32(int* dst_dev, const int* values_host, int n,
 MSCNN_API int mscnn_sum_squares_f32(const float* x, size_t count, double* out_dev, void* stream);
 
 /* Softmax over axis 1 of x[outer][C][inner] -- SoftmaxLayer::Forward_gpu (softmax_layer.cu:83-120). */
+/* Alignment: 4. */
 MSCNN_API int mscnn_softmax_fwd_f32(const float* x, float* y, int outer, int C, int inner, void* stream);
 
 /* ------------------------------------------------------------------------------------------
@@ -287,12 +338,14 @@ MSCNN_API int mscnn_softmax_fwd_f32(const float* x, float* y, int outer, int C, 
  * for the stand-alone layer).  A roi's batch index outside [0, N) is NOT checked on the device
  * (the reference CHECKs it on the CPU path only, roi_pooling_layer.cpp:64-65).
  * ------------------------------------------------------------------------------------------ */
+/* Alignment: 4. */
 MSCNN_API int mscnn_roipool_fwd_f32(const float* feat, const float* rois, float* out, int R, int N, int C, int H, int W,
                           int pooled_h, int pooled_w, float spatial_scale, float pad_ratio,
                           int C_total, int c_offset, void* stream);
 /* The same ROIs pooled twice over the same map with two context paddings (roi_pool_org + roi_pool_ctx of the deploy nets,
  * roi_pooling_layer.cu:19-104 twice) into two disjoint channel windows [c_offset_x, c_offset_x + C) of one [R][C_total][ph][pw]
  * output, in one launch. */
+/* Alignment: 4. */
 MSCNN_API int mscnn_roipool_pair_fwd_f32(const float* feat, const float* rois, float* out, int R, int N, int C, int H, int W,
                                          int pooled_h, int pooled_w, float spatial_scale, float pad_ratio_a, int c_offset_a,
                                          float pad_ratio_b, int c_offset_b, int C_total, void* stream);
@@ -313,6 +366,7 @@ MSCNN_API int mscnn_roipool_pair_fwd_f32(const float* feat, const float* rois, f
  *     conv3_3 of the trunk, whose only reader is the pooling layer (283 + 142 + 71 MB per 7s-576 frame not written). */
 MSCNN_API int mscnn_conv2d_plan_can_chain(const mscnn_conv_plan* plan, const mscnn_conv_plan* next);
 MSCNN_API int mscnn_conv2d_plan_can_pool_only(const mscnn_conv_plan* plan);
+/* Alignment: both workspaces 16, y 16 with a next plan (refused); x: falls back. */
 MSCNN_API int mscnn_conv2d_fwd_chain_f32(const mscnn_conv_plan* plan, const mscnn_conv_plan* next, const float* x, const float* packed,
                                const float* bias, float* y, float* y_pool, void* workspace, size_t workspace_bytes,
                                void* next_workspace, size_t next_workspace_bytes, void* stream);
@@ -331,7 +385,9 @@ MSCNN_API int mscnn_conv2d_fwd_chain_f32(const mscnn_conv_plan* plan, const mscn
 MSCNN_API int mscnn_conv2d_plan_can_fuse_roipool(const mscnn_conv_plan* plan, int C, int pooled_h, int pooled_w);
 MSCNN_API size_t mscnn_conv2d_roipool_workspace_bytes(const mscnn_conv_plan* plan, int N, int C, int H, int W);
 MSCNN_API size_t mscnn_roipool_maps_bytes(int N, int C, int H, int W);
+/* Alignment: maps 16 (refused); feat 4. */
 MSCNN_API int mscnn_roipool_maps_build_f32(const float* feat, float* maps, int N, int C, int H, int W, void* stream);
+/* Alignment: prepared_maps, workspace, packed_w 16 (refused); feat, rois, y 4 (y: scalar staging where it is not 16-byte aligned). */
 MSCNN_API int mscnn_conv2d_fwd_roipool_pair_f32(const mscnn_conv_plan* plan, const float* feat, const float* prepared_maps, int N, int C,
                                                 int H, int W, const float* rois, float spatial_scale, float pad_ratio_a,
                                                 float pad_ratio_b, const float* packed_w, const float* bias, float* y, void* workspace,
@@ -339,11 +395,13 @@ MSCNN_API int mscnn_conv2d_fwd_roipool_pair_f32(const mscnn_conv_plan* plan, con
 
 /* ROIAlign -- ROIAlignLayer<Dtype>::Forward_gpu (roi_align_layer.cu:21-112): out[R][C][pooled_h+1][pooled_w+1] bilinear
  * samples on the grid of the (context-padded) roi; the WiderFace cascade deploy follows it with a 2x2 stride-1 AVE Pooling. */
+/* Alignment: 4. */
 MSCNN_API int mscnn_roialign_fwd_f32(const float* feat, const float* rois, float* out, int R, int N, int C, int H, int W,
                                      int pooled_h, int pooled_w, float spatial_scale, float pad_ratio, void* stream);
 
 /* Eltwise -- EltwiseLayer<Dtype>::Forward_gpu (eltwise_layer.cu): op 0 PROD, 1 SUM (coeffs_host[num_bottoms], NULL = all 1),
  * 2 MAX.  bottoms_host: host array of num_bottoms (2..8) device pointers of `count` floats each. */
+/* Alignment: 4. */
 MSCNN_API int mscnn_eltwise_fwd_f32(const float* const* bottoms_host, int num_bottoms, const float* coeffs_host, float* y,
                                     size_t count, int op, void* stream);
 
@@ -379,6 +437,7 @@ MSCNN_API int mscnn_boxoutput_max_rows(const mscnn_boxoutput_desc* desc);
  * (R includes the dummy row [0 1 1 10 10] emitted when nothing survives, :195-199).
  * Asynchronous on `stream`; the caller copies count_out_dev back when it needs R on the host.
  */
+/* Alignment: workspace 16 (refused); everything else 4. */
 MSCNN_API int mscnn_boxoutput_fwd_f32(const mscnn_boxoutput_desc* desc, const float* const* heads_host,
                             float* rois_out, float* props_out, int* anchor_ids_out, int cap,
                             int* count_out_dev, void* workspace, size_t workspace_bytes, void* stream);
@@ -397,6 +456,7 @@ MSCNN_API int mscnn_boxoutput_fwd_f32(const mscnn_boxoutput_desc* desc, const fl
  * max_nms_num 2000); it is 0 with mscnn_last_error set for a bad descriptor.
  */
 MSCNN_API size_t mscnn_boxoutput_batch_workspace_bytes(const mscnn_boxoutput_desc* desc);
+/* Alignment: workspace 16 (refused); everything else 4. */
 MSCNN_API int mscnn_boxoutput_batch_fwd_f32(const mscnn_boxoutput_desc* desc, const float* const* heads_host,
                             float* rois_out, float* props_out, int* anchor_ids_out, int cap,
                             int* count_out_dev, void* workspace, size_t workspace_bytes, void* stream);
@@ -404,12 +464,14 @@ MSCNN_API int mscnn_boxoutput_batch_fwd_f32(const mscnn_boxoutput_desc* desc, co
 /* Greedy NMS on already score-sorted boxes [n][4] = x y w h (nmsMax, greedy = true):
  * keep_out[n] bytes 0/1.  Exposed for the index-exactness parity tests. */
 MSCNN_API size_t mscnn_nms_workspace_bytes(int n);
+/* Alignment: boxes_xywh, workspace 16 (refused). */
 MSCNN_API int mscnn_nms_greedy_f32(const float* boxes_xywh, int n, float iou_thr, int nms_mode, unsigned char* keep_out,
                          void* workspace, size_t workspace_bytes, void* stream);
 
 /* DecodeBBox (TEST phase) -- DecodeBBoxLayer<Dtype>::Forward_cpu (decode_bbox_layer.cpp:54-123,
  * DecodeBBoxesWithPrior math_functions.cpp:46-75); bbox[R][8] (columns 4..7 used), prior[R][5],
  * mean/std host arrays of 4. */
+/* Alignment: 4. */
 MSCNN_API int mscnn_decodebbox_fwd_f32(const float* bbox, const float* prior, float* out, int R, int bbox_dim,
                              const float* mean_host, const float* std_host, void* stream);
 
@@ -464,6 +526,7 @@ MSCNN_API int mscnn_nms_params_resolve(const mscnn_nms_params* nms, mscnn_nms_pa
  * HUGE_VAL = inf), det_thr. */
 MSCNN_API int mscnn_nms_params_from_names(const char* type, const char* ovr_dnm, double thr, double maxn, float det_thr,
                                           mscnn_nms_params* out);
+/* Alignment (all mscnn_detections_* calls): workspace, pack_dev 16, dets_out 8 (refused); the blobs, ids_out, count_out_dev 4. */
 MSCNN_API int mscnn_detections_fwd(const mscnn_detections_desc* desc, const float* bbox_pred, const float* cls_pred,
                          const float* props, int R, double* dets_out, int* ids_out, int* count_out_dev,
                          void* workspace, size_t workspace_bytes, void* stream);
@@ -564,6 +627,7 @@ MSCNN_API int mscnn_detections_cascade_multi_nms_fwd(const mscnn_detections_desc
 enum { MSCNN_PROPOSALS_IMAGES_PER_LAUNCH = 64 };
 typedef struct { float proposal_thr; double ratio_h, ratio_w; } mscnn_proposals_desc;
 MSCNN_API size_t mscnn_proposals_multi_pack_bytes(int num_images, int cap);
+/* Alignment: props 8, pack_dev 16 (refused). */
 MSCNN_API int mscnn_proposals_multi_fwd(const mscnn_proposals_desc* desc, int num_images, const float* props, int R_all, void* pack_dev,
                                         int cap, void* stream);
 
@@ -575,6 +639,7 @@ MSCNN_API int mscnn_proposals_multi_fwd(const mscnn_proposals_desc* desc, int nu
  * out: device float [3][H][W] (planes B, G, R); mean_bgr: host float[3] ({104,117,123} in the reference).
  * ------------------------------------------------------------------------------------------ */
 MSCNN_API size_t mscnn_preprocess_workspace_bytes(int org_h, int org_w, int H, int W);
+/* Alignment: workspace 16 (refused); img_rgb 1, out 4. */
 MSCNN_API int mscnn_preprocess_u8_f32(const unsigned char* img_rgb, int org_h, int org_w, float* out, int H, int W,
                             const float* mean_bgr, void* workspace, size_t workspace_bytes, void* stream);
 /* The same for a batch of `count` frames, each of its own size: imgs_rgb is a HOST array of `count` device pointers (frame b:
@@ -583,6 +648,7 @@ MSCNN_API int mscnn_preprocess_u8_f32(const unsigned char* img_rgb, int org_h, i
  * 256-byte aligned offset, back to back: mscnn_preprocess_batch_workspace_bytes returns that size (0 for arguments the op refuses).
  * Null pointers, count < 1, a size <= 0 or a too small workspace are refused before any launch. */
 MSCNN_API size_t mscnn_preprocess_batch_workspace_bytes(int count, const int* org_h, const int* org_w, int H, int W);
+/* Alignment: workspace 16 (refused); frames 1, out 4. */
 MSCNN_API int mscnn_preprocess_batch_u8_f32(const unsigned char* const* imgs_rgb, const int* org_h, const int* org_w, int count,
                                   float* out, int H, int W, const float* mean_bgr, void* workspace, size_t workspace_bytes,
                                   void* stream);

@@ -817,6 +817,7 @@ extern "C" int mscnn_boxoutput_fwd_f32(const mscnn_boxoutput_desc* d, const floa
   int rc = check_desc(d);
   if (rc != MSCNN_OK) return rc;
   MSCNN_REQUIRE(heads_host && rois_out && count_out_dev && workspace, "boxoutput: null pointer");
+  MSCNN_REQUIRE_ALIGNED(workspace, 16, "boxoutput: workspace");
   MSCNN_REQUIRE(cap >= 1, "boxoutput: cap must be >= 1");
   const int anchors = total_anchors(d);
   const WsLayout L = layout_for(anchors, d->max_nms_num);
@@ -892,6 +893,7 @@ extern "C" int mscnn_boxoutput_batch_fwd_f32(const mscnn_boxoutput_desc* d, cons
   int rc = check_desc(d);
   if (rc != MSCNN_OK) return rc;
   MSCNN_REQUIRE(heads_host && rois_out && count_out_dev && workspace, "boxoutput: null pointer");
+  MSCNN_REQUIRE_ALIGNED(workspace, 16, "boxoutput: workspace");
   MSCNN_REQUIRE(cap >= 1, "boxoutput: cap must be >= 1");
   const int anchors = total_anchors(d);
   const BatchLayout B = batch_layout_for(anchors, d->max_nms_num, d->num);
@@ -963,6 +965,7 @@ extern "C" int mscnn_nms_greedy_f32(const float* boxes_xywh, int n, float iou_th
   if (n == 0) return MSCNN_OK;
   MSCNN_REQUIRE(boxes_xywh && keep_out && workspace, "nms: null pointer");
   MSCNN_REQUIRE(reinterpret_cast<uintptr_t>(boxes_xywh) % 16 == 0, "nms: boxes must be 16-byte aligned");
+  MSCNN_REQUIRE_ALIGNED(workspace, 16, "nms: workspace");
   if (workspace_bytes < mscnn_nms_workspace_bytes(n)) {
     set_error("nms: workspace too small");
     return MSCNN_ERR_WORKSPACE;

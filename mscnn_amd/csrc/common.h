@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
 #include "../../include/mscnn_hip.h"
 
@@ -31,6 +32,10 @@ inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s);
       return MSCNN_ERR_BAD_ARG;                  \
     }                                            \
   } while (0)
+
+// An operand the kernels read or write with vector instructions: refused before anything is launched (mscnn_hip.h, ALIGNMENT).
+#define MSCNN_REQUIRE_ALIGNED(ptr, bytes, what)                                                                       \
+  MSCNN_REQUIRE((ptr) == nullptr || reinterpret_cast<uintptr_t>(ptr) % (bytes) == 0, "%s must be %d-byte aligned", what, (int)(bytes))
 
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 

@@ -29,6 +29,7 @@
 // every fp32 operand as fp16 hi + lo, three MFMAs per pair, fp32-grade; x3_device.h, wino_x3.hip).  Every kernel of the family
 // can publish max |y| of what it stores for a split-fp16 consumer (IgemmArgs::amax_out).
 #include "common.h"
+#include <cstring>
 #include "headconv.h"
 #include "winograd.h"
 #include "wino_x3.h"
@@ -1536,6 +1537,7 @@ extern "C" int mscnn_conv2d_plan_set_batch(mscnn_conv_plan* p, int N) {
 
 extern "C" int mscnn_conv2d_pack_weights(const mscnn_conv_plan* p, const float* w, float* packed, void* stream) {
   MSCNN_REQUIRE(p, "conv pack: null plan");
+  MSCNN_REQUIRE_ALIGNED(packed, 16, "conv pack: packed");
   if (p->x3h.rows) {
     MSCNN_REQUIRE(w && packed, "conv pack: null pointer");
     return x3_head_pack(p->x3h, w, packed, as_stream(stream));
@@ -1670,6 +1672,24 @@ extern "C" int mscnn_conv2d_fwd_f32(const mscnn_conv_plan* p, const float* x, co
 // The fp32 Winograd path: {input stage -> V | plane GEMM V -> M | output stage M -> y}; the input stage is the plan's own
 // transform of x, the fused ROI pooling (mscnn_conv2d_fwd_roipool_pair_f32) or nothing (planes prepared by the previous layer of a
 // chain); the output stage the plan's own transform or the one that writes the next layer's planes (mscnn_conv2d_fwd_chain_f32).
+// What the plan's kernels need of the caller's pointers beyond a float's own 4 bytes (mscnn_hip.h, ALIGNMENT), checked before the
+// first launch of a forward.  Packed weights and workspaces are read and written with 16-byte accesses by every family.  x: the
+// split-fp16 forms measure max |x| with uint4 loads (and stage small maps with float4), the vectorised 1x1 igemm kernels load it
+// with b128; every other kernel loads x with b32 or has a scalar path of its own (winograd.hip).  y: the F(2x2,3x3) and the pooling
+// F(3x3,3x3) output transforms store float2 pairs where Wo is even; the other stores are b32 or have a scalar path.  (The Cin = 3,
+// one-launch F(2x2,3x3) and chain kernels check their own operands in front of their single launch.)
+static bool entry_is_vec(const mscnn_conv_plan* q) { return q && q->entry >= 0 && strstr(kTable[q->entry].name, "_vec") != nullptr; }
+static int conv_check_pointers(const mscnn_conv_plan* p, const float* x, const float* packed, const float* y, const float* y_pool,
+                               const void* workspace) {
+  MSCNN_REQUIRE_ALIGNED(packed, 16, "conv: packed");
+  MSCNN_REQUIRE_ALIGNED(workspace, 16, "conv: workspace");
+  if (p->x3.BM || p->x3h.rows) MSCNN_REQUIRE_ALIGNED(x, 16, "conv (split-fp16): x");
+  if ((!p->wino && !p->x3.BM && !p->hg && entry_is_vec(p)) || entry_is_vec(p->hg)) MSCNN_REQUIRE_ALIGNED(x, 16, "conv (vectorised 1x1 kernel): x");
+  const int m = p->x3.BM ? 3 : (p->wino ? p->wino_m : 0);
+  if ((m == 2 || (m == 3 && y_pool)) && p->Wo % 2 == 0) MSCNN_REQUIRE_ALIGNED(y, 8, "conv (winograd output transform): y");
+  return MSCNN_OK;
+}
+
 template <class InputStage, class OutputStage>
 static int wino_forward_stages(const mscnn_conv_plan* p, const float* packed, void* workspace, size_t workspace_bytes, hipStream_t st,
                                InputStage&& input_stage, OutputStage&& output_stage) {
@@ -1721,6 +1741,10 @@ extern "C" int mscnn_conv2d_fwd_pool_f32(const mscnn_conv_plan* p, const float* 
   MSCNN_REQUIRE(x && (y || (y_pool && mscnn_conv2d_plan_can_pool_only(p))),
                 "conv: null pointer (y may be NULL only with y_pool on a plan where mscnn_conv2d_plan_can_pool_only)");
   hipStream_t st = as_stream(stream);
+  {
+    const int rc = conv_check_pointers(p, x, packed, y, y_pool, workspace);
+    if (rc != MSCNN_OK) return rc;
+  }
 #define MSCNN_STAGE_EVENT(i) do { if (p->profiling) MSCNN_HIP_TRY(hipEventRecord(p->ev[i], st)); } while (0)
   if (p->x3.BM) {        // split-fp16 Winograd: {amax + input transform | GEMM | output transform}
     MSCNN_REQUIRE(packed, "conv: Winograd path needs packed weights (mscnn_conv2d_pack_weights)");
@@ -1791,7 +1815,14 @@ extern "C" int mscnn_conv2d_fwd_chain_f32(const mscnn_conv_plan* p, const mscnn_
   MSCNN_REQUIRE(!y_pool || mscnn_conv2d_plan_can_pool(p), "conv: this plan has no fused 2x2 max-pooling epilogue");
   const mscnn_conv_desc& d = p->d;
   hipStream_t st = as_stream(stream);
+  {
+    int rc = conv_check_pointers(p, x, packed, y, y_pool, workspace);
+    if (rc == MSCNN_OK && next) rc = conv_check_pointers(next, nullptr, nullptr, nullptr, nullptr, next_workspace);
+    if (rc != MSCNN_OK) return rc;
+  }
   if (next) {
+    // (wino44_output_into_input refuses it too, but only after the input transform and the plane GEMM have been launched)
+    MSCNN_REQUIRE(y == nullptr || reinterpret_cast<uintptr_t>(y) % 16 == 0, "conv(chain): y must be 16-byte aligned");
     const size_t vbytes = sizeof(float) * 36 * (size_t)next->d.Cin * next->T_pad;
     if (!next_workspace || next_workspace_bytes < next->ws_bytes) {
       set_error("conv(chain): next workspace %zu < %zu", next_workspace_bytes, next->ws_bytes);
@@ -1841,6 +1872,11 @@ extern "C" int mscnn_conv2d_fwd_roipool_pair_f32(const mscnn_conv_plan* p, const
     return MSCNN_ERR_WORKSPACE;
   }
   hipStream_t st = as_stream(stream);
+  {
+    const int rc = conv_check_pointers(p, nullptr, packed, y, nullptr, workspace);
+    if (rc != MSCNN_OK) return rc;
+  }
+  MSCNN_REQUIRE_ALIGNED(prepared_maps, 16, "conv(roipool): prepared_maps");
   float* own_maps = reinterpret_cast<float*>(static_cast<unsigned char*>(workspace) + roipool_scratch_offset(p));
   return wino_forward(p, packed, bias, y, nullptr, workspace, workspace_bytes, st, [&](float* V) {
     if (!prepared_maps) {

@@ -552,6 +552,8 @@ static int detections_launch(const mscnn_detections_desc* desc, int cascade, flo
   MSCNN_REQUIRE(!cascade || nms.det_thr == 0.f, "detections: nms params det_thr %g is the plain stage's: the cascade stage takes its "
                 "det_thr as an argument", (double)nms.det_thr);
   MSCNN_REQUIRE(desc && count_out_dev && workspace, "detections: null pointer");
+  MSCNN_REQUIRE_ALIGNED(workspace, 16, "detections: workspace");
+  MSCNN_REQUIRE_ALIGNED(dets_out, 8, "detections: dets_out");
   MSCNN_REQUIRE(R >= 0, "detections: R < 0");
   MSCNN_REQUIRE(desc->ncls >= 2 && desc->cls_id >= 1 && desc->cls_id <= desc->ncls, "detections: cls_id %d of %d",
                 desc->cls_id, desc->ncls);
@@ -730,6 +732,8 @@ extern "C" int mscnn_detections_multi_nms_fwd(const mscnn_detections_desc* desc,
   mscnn_nms_params nms;
   if (int rc = mscnn_nms_params_resolve(nms_in, &nms)) return rc;
   MSCNN_REQUIRE(desc && pack_dev && workspace, "detections_multi: null pointer");
+  MSCNN_REQUIRE_ALIGNED(pack_dev, 16, "detections_multi: pack_dev");
+  MSCNN_REQUIRE_ALIGNED(workspace, 16, "detections_multi: workspace");
   MSCNN_REQUIRE(num_images >= 1 && num_classes >= 1, "detections_multi: %d images x %d classes", num_images, num_classes);
   MSCNN_REQUIRE(R_all >= 1 && bbox_pred && cls_pred && props, "detections_multi: R_all = %d (BoxOutput emits at least one row)", R_all);
   MSCNN_REQUIRE(max_rows_per_image >= 1 && max_rows_per_image <= kMaxK,
@@ -768,6 +772,8 @@ extern "C" int mscnn_detections_cascade_multi_nms_fwd(const mscnn_detections_des
   MSCNN_REQUIRE(num_outputs >= 1 && num_outputs <= kCascadeMaxOutputs, "detections_cascade_multi: %d cascade outputs (1 .. %d)",
                 num_outputs, kCascadeMaxOutputs);
   MSCNN_REQUIRE(desc && outputs && pack_dev && workspace, "detections_cascade_multi: null pointer");
+  MSCNN_REQUIRE_ALIGNED(pack_dev, 16, "detections_cascade_multi: pack_dev");
+  MSCNN_REQUIRE_ALIGNED(workspace, 16, "detections_cascade_multi: workspace");
   MSCNN_REQUIRE(num_images >= 1 && num_classes >= 1, "detections_cascade_multi: %d images x %d classes", num_images, num_classes);
   MSCNN_REQUIRE(R_all >= 1, "detections_cascade_multi: R_all = %d (BoxOutput emits at least one row)", R_all);
   for (int o = 0; o < num_outputs; ++o) {

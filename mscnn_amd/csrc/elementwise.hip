@@ -438,7 +438,9 @@ extern "C" int mscnn_deconv_depthwise_fwd_f32(const float* x, const float* w, co
   MSCNN_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0 && Kh > 0 && Kw > 0 && stride_h > 0 && stride_w > 0, "deconv: bad shape");
   const int Ho = stride_h * (H - 1) + Kh - 2 * pad_h, Wo = stride_w * (W - 1) + Kw - 2 * pad_w;
   MSCNN_REQUIRE(Ho > 0 && Wo > 0, "deconv: empty output");
-  if (Kh == 4 && Kw == 4 && stride_h == 2 && stride_w == 2 && pad_h == 1 && pad_w == 1 && (long)N * C <= 65535 && H <= 65535) {
+  // (the quad kernel stores float2 pairs: a y that is only 4-byte aligned takes the per-output kernel below)
+  if (Kh == 4 && Kw == 4 && stride_h == 2 && stride_w == 2 && pad_h == 1 && pad_w == 1 && (long)N * C <= 65535 && H <= 65535 &&
+      reinterpret_cast<uintptr_t>(y) % 8 == 0) {
     deconv_dw_up2_kernel<<<dim3((W + kThreads - 1) / kThreads, H, N * C), kThreads, 0, as_stream(stream)>>>(x, w, bias, y, C, H, W);
     MSCNN_POST_LAUNCH();
     return MSCNN_OK;

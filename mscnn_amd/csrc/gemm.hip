@@ -592,6 +592,8 @@ extern "C" int mscnn_inner_product_wg_fwd(const float* x, const float* wt, const
   mscnn::WgemmPlan pl;
   MSCNN_REQUIRE(ip_wg_plan(M, N, K, &pl), "inner_product wg: shape M=%d N=%d K=%d is not one the plane-GEMM kernel takes", M, N, K);
   MSCNN_REQUIRE(x && wt && y && reinterpret_cast<uintptr_t>(x) % 16 == 0, "inner_product wg: null or unaligned pointer");
+  MSCNN_REQUIRE_ALIGNED(wt, 16, "inner_product wg: wt");
+  MSCNN_REQUIRE_ALIGNED(workspace, 16, "inner_product wg: workspace");
   const size_t need = mscnn_inner_product_wg_workspace_bytes(M, N, K);
   if (!workspace || workspace_bytes < need) {
     set_error("inner_product wg: workspace %zu < %zu", workspace_bytes, need);

@@ -171,6 +171,7 @@ extern "C" int mscnn_preprocess_u8_f32(const unsigned char* img_rgb, int org_h, 
   MSCNN_REQUIRE(img_rgb && out && mean_bgr, "preprocess: null pointer");
   MSCNN_REQUIRE(org_h > 0 && org_w > 0 && H > 0 && W > 0, "preprocess: bad shape");
   MSCNN_REQUIRE(workspace && workspace_bytes >= mscnn_preprocess_workspace_bytes(org_h, org_w, H, W), "preprocess: workspace too small");
+  MSCNN_REQUIRE_ALIGNED(workspace, 16, "preprocess: workspace");
   unsigned char* mid = static_cast<unsigned char*>(workspace);
   return preprocess_launch(&img_rgb, &mid, &org_h, &org_w, 1, out, H, W, mean_bgr, as_stream(stream));
 }
@@ -191,6 +192,7 @@ extern "C" int mscnn_preprocess_batch_u8_f32(const unsigned char* const* imgs_rg
                                              void* stream) {
   MSCNN_REQUIRE(imgs_rgb && org_h && org_w && out && mean_bgr && workspace, "preprocess_batch: null pointer");
   MSCNN_REQUIRE(count >= 1, "preprocess_batch: count %d < 1", count);
+  MSCNN_REQUIRE_ALIGNED(workspace, 16, "preprocess_batch: workspace");
   MSCNN_REQUIRE(H > 0 && W > 0, "preprocess_batch: bad output shape %d x %d", H, W);
   for (int b = 0; b < count; ++b) {
     MSCNN_REQUIRE(org_h[b] > 0 && org_w[b] > 0, "preprocess_batch: image %d has bad shape %d x %d", b, org_h[b], org_w[b]);

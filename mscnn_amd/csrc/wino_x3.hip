@@ -624,6 +624,7 @@ bool x3_plan(int Cin, int Cout, long T_pad, int tune_variant, X3Plan* out) {
 }
 
 int x3_amax(const float* x, long n, unsigned* scal, hipStream_t st) {
+  MSCNN_REQUIRE_ALIGNED(x, 16, "split-fp16 max |x| pass: the tensor");      // (amax_kernel reads it as uint4)
   MSCNN_HIP_TRY(hipMemsetAsync(scal, 0, sizeof(unsigned) * kAmaxSlots, st));
   long blocks = (n / 4 + 255) / 256;
   if (blocks > kAmaxSlots) blocks = kAmaxSlots;       // one atomic per slot
@@ -710,6 +711,8 @@ extern "C" size_t mscnn_inner_product_x3_workspace_bytes(int M, int N, int K) {
 
 extern "C" int mscnn_inner_product_x3_pack(const float* w, void* packed, int N, int K, void* stream) {
   MSCNN_REQUIRE(w && packed && mscnn_inner_product_x3_supported(N, K), "inner_product x3 pack: bad argument (N=%d K=%d)", N, K);
+  MSCNN_REQUIRE_ALIGNED(w, 16, "inner_product x3 pack: w");
+  MSCNN_REQUIRE_ALIGNED(packed, 16, "inner_product x3 pack: packed");
   hipStream_t st = as_stream(stream);
   unsigned char* pk = static_cast<unsigned char*>(packed);
   unsigned* slots = reinterpret_cast<unsigned*>(pk + kHdrBytes / 2);
@@ -728,6 +731,8 @@ extern "C" int mscnn_inner_product_x3_fwd(const float* x, const void* packed, co
   if (M == 0) return MSCNN_OK;
   MSCNN_REQUIRE(x && packed && y && mscnn_inner_product_x3_supported(N, K) && reinterpret_cast<uintptr_t>(x) % 16 == 0,
                 "inner_product x3: needs N >= 128, K %% 32 == 0, 16-byte aligned x (N=%d K=%d)", N, K);
+  MSCNN_REQUIRE_ALIGNED(packed, 16, "inner_product x3: packed");
+  MSCNN_REQUIRE_ALIGNED(workspace, 16, "inner_product x3: workspace");
   const IpShape s = ip_shape(M, N, K);
   if (!workspace || workspace_bytes < 8192 + s.x_bytes + s.slab_bytes) {
     set_error("inner_product x3: workspace %zu < %zu", workspace_bytes, 8192 + s.x_bytes + s.slab_bytes);

@@ -246,7 +246,7 @@ __global__ __launch_bounds__(256) void wino33_input_kernel(const float* __restri
     if (r >= N) break;
     const float* src = x + ((long)r * Cin + c0) * HW;
     float* dst = sm + rl * (kW33Ch * HW);
-    if ((run & 3) == 0 && ((((long)r * Cin + c0) * HW) & 3) == 0) {
+    if ((run & 3) == 0 && ((((long)r * Cin + c0) * HW) & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {
       for (int i = tid; i < run / 4; i += 256) reinterpret_cast<float4*>(dst)[i] = reinterpret_cast<const float4*>(src)[i];
     } else {
       for (int i = tid; i < run; i += 256) dst[i] = src[i];
@@ -998,6 +998,9 @@ int wino_output_transform(int m, const float* M, const float* bias, float* y, fl
   const bool use_vec44 = m == 4 && Wo % 4 == 0 && tiles_w * 4 == Wo && reinterpret_cast<uintptr_t>(y) % 16 == 0 &&
                          (!y_pool || reinterpret_cast<uintptr_t>(y_pool) % 8 == 0) && !scalar_f4;
   MSCNN_REQUIRE(y || (y_pool && use_vec44), "winograd: only the vector F(4x4,3x3) output transform with fused pooling (8-byte aligned pooled map) runs without y");
+  // (wino_output_kernel and wino33_output_pool_kernel store float2 pairs of y where Wo is even)
+  MSCNN_REQUIRE(!(m == 2 || (m == 3 && y_pool)) || Wo % 2 != 0 || reinterpret_cast<uintptr_t>(y) % 8 == 0,
+                "winograd F(%dx%d,3x3): y must be 8-byte aligned", m, m);
   const int T = N * tiles_h * tiles_w;
   dim3 grid(cdiv(T, 256), Cout);
   if (use_vec44) {
