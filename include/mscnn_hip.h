@@ -44,7 +44,7 @@
  *   inner_product_x3_fwd / _pack   x resp. w 16: refuses; y, bias 4
  *   inner_product_wg_fwd       x 16: refuses; y, bias 4; _wg_pack: w 4
  *   deconv_depthwise_fwd       4; the 4x4 / stride 2 / pad 1 quad kernel needs y 8: falls back to the per-output kernel
- *   concat_channels, softmax, eltwise, deconv2d (generic), roipool, roipool_pair, roialign, decodebbox, preprocess* (images, out),
+ *   concat_channels, softmax, eltwise, deconv2d (generic), roipool, roipool_pair, roialign, roialign_ave, roialign_ave_pair, decodebbox, preprocess* (images, out),
  *   max_rel_diff*, sum_squares, store_words      4 (doubles 8)
  *   nms_greedy                 boxes 16: refuses; keep_out 1
  *   boxoutput*                 heads, rois_out, props_out, anchor_ids_out, count_out_dev 4
@@ -398,6 +398,24 @@ MSCNN_API int mscnn_conv2d_fwd_roipool_pair_f32(const mscnn_conv_plan* plan, con
 /* Alignment: 4. */
 MSCNN_API int mscnn_roialign_fwd_f32(const float* feat, const float* rois, float* out, int R, int N, int C, int H, int W,
                                      int pooled_h, int pooled_w, float spatial_scale, float pad_ratio, void* stream);
+/* ROIAlign (roi_align_layer.cu:21-98) + the 2x2 / stride 1 / pad 0 AVE Pooling that follows it in the deploy
+ * (pooling_layer.cu:50-81), written into channels [c_offset, c_offset + C) of out[R][C_total][pooled_h][pooled_w].  The grid of samples
+ * stays in LDS.  Every value is bit-identical to mscnn_roialign_fwd_f32 -> mscnn_pool2d_fwd_f32 (AVE, 2, 2, pad 0, stride 1) ->
+ * mscnn_concat_channels_f32: the sample is the same device function, the average is the pooling kernel's sum order and division.
+ * Refused before any launch (MSCNN_ERR_BAD_ARG, the text names the argument): a null pointer, a non-positive shape, a channel window
+ * outside [0, C_total), and a grid of more than 256 points: (pooled_h + 1) * (pooled_w + 1) <= 256, i.e. up to 15 x 15 bins.
+ * R == 0 returns MSCNN_OK and touches nothing.  A roi's batch index outside [0, N) is NOT checked, as in ROIPooling and ROIAlign. */
+/* Alignment: 4. */
+MSCNN_API int mscnn_roialign_ave_fwd_f32(const float* feat, const float* rois, float* out, int R, int N, int C, int H, int W,
+                                         int pooled_h, int pooled_w, float spatial_scale, float pad_ratio,
+                                         int C_total, int c_offset, void* stream);
+/* The same ROIs sampled with two context paddings into two disjoint channel windows of one output: the five layers
+ * roi_grid_org / roi_pool_org / roi_grid_ctx / roi_pool_ctx / roi_pool (Concat) of the WiderFace cascade in one launch.
+ * Refusals as above, plus windows that overlap. */
+/* Alignment: 4. */
+MSCNN_API int mscnn_roialign_ave_pair_fwd_f32(const float* feat, const float* rois, float* out, int R, int N, int C, int H, int W,
+                                              int pooled_h, int pooled_w, float spatial_scale, float pad_ratio_a, int c_offset_a,
+                                              float pad_ratio_b, int c_offset_b, int C_total, void* stream);
 
 /* Eltwise -- EltwiseLayer<Dtype>::Forward_gpu (eltwise_layer.cu): op 0 PROD, 1 SUM (coeffs_host[num_bottoms], NULL = all 1),
  * 2 MAX.  bottoms_host: host array of num_bottoms (2..8) device pointers of `count` floats each. */

@@ -57,7 +57,7 @@ MSCNN_NET_API int mscnn_net_layer_param_shape(const mscnn_net* net, int layer, i
 /* The layer's LayerParameter in prototxt text form (valid until the next call on this thread). */
 MSCNN_NET_API const char* mscnn_net_layer_param_text(const mscnn_net* net, int layer);
 MSCNN_NET_API int mscnn_net_layer_fused_away(const mscnn_net* net, int layer);              /* 1: ReLU folded into its producer */
-MSCNN_NET_API const char* mscnn_net_layer_kernel(const mscnn_net* net, int layer);          /* conv / InnerProduct kernel family, "" otherwise */
+MSCNN_NET_API const char* mscnn_net_layer_kernel(const mscnn_net* net, int layer);          /* conv / InnerProduct kernel family; "roialign_ave_pair" for the first ROIAlign layer of a head the last forward ran in one pass; "" otherwise */
 MSCNN_NET_API double mscnn_net_layer_flops(const mscnn_net* net, int layer);                /* of the last forward */
 /* Roofline accounting of Convolution layers: FLOPs the MFMA pipe executes (Winograd forms: fewer than the algorithmic
  * count above) and, with conv profiling on, the HIP-event time of the last forward split into {input transform, MFMA GEMM
@@ -104,6 +104,18 @@ MSCNN_NET_API int mscnn_net_set_chain_fusion(mscnn_net* net, int on);
  * mscnn_boxoutput_batch_fwd_f32): OFF by default (image after image, mscnn_boxoutput_fwd_f32) until the batched op has been timed; on = 1 selects it.  The tops are
  * bit-identical either way, and a net of one image always takes mscnn_boxoutput_fwd_f32. */
 MSCNN_NET_API int mscnn_net_set_boxoutput_one_pass(mscnn_net* net, int on);
+/* The ROIAlign head of the WiderFace cascade -- roi_grid_org / roi_pool_org / roi_grid_ctx / roi_pool_ctx / roi_pool, once per stage --
+ * in one launch (mscnn_hip.h: mscnn_roialign_ave_pair_fwd_f32).  A head is registered at construction: two ROIAlign layers that read
+ * the same feature blob and the same ROI blob (through Split layers) with equal pooled_h / pooled_w / spatial_scale, each top read by
+ * exactly one Pooling layer that is AVE, kernel 2, stride 1, pad 0, those two tops read only by one Concat on axis 1.  OFF by default
+ * until the one-pass form has been timed against the chain on the frames that matter: a net that never calls this runs the launches it
+ * always ran.  on = 1: in a forward whose range holds all five layers the first ROIAlign layer writes the Concat's top and the other
+ * four launch nothing; a range that holds part of a head runs its layers stand-alone.  The tops are bit-identical either way, and so
+ * is every blob read through this ABI: mscnn_net_get_blob / _blob_device on a grid or pooled blob the forward did not write run the
+ * skipped layers on the same bottoms first, and so do a weight change, a reshape and a partial forward that does not run the head.
+ *   mscnn_net_roialign_pairs: how many heads the net registered; writes up to cap indices of their first ROIAlign layers. */
+MSCNN_NET_API int mscnn_net_set_roialign_one_pass(mscnn_net* net, int on);
+MSCNN_NET_API int mscnn_net_roialign_pairs(const mscnn_net* net, int* first_layers, int cap);
 /* The pairs the net registered at construction: producers[i] -> consumers[i] (layer indices; consumers[i] = -1: a top that only its
  * fused 2x2 pooling reads).  Returns their number and writes up to cap of them; whether a pair actually runs chained is decided per
  * forward (both planned kernels on the fp32 F(4x4,3x3) path, no numerical check pending, both layers inside the range). */

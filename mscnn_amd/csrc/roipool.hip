@@ -253,6 +253,73 @@ __global__ __launch_bounds__(kThreads) void roipool_rows_kernel(const float* __r
 }
 
 // ROIAlign: (PH+1) x (PW+1) bilinear samples per (roi, channel) -- roi_align_layer.cu:21-98, same operation order.
+// The sample's arithmetic lives in align_roi / align_point / align_sum below and nowhere else: roialign_kernel and roialign_ave_kernel both call them,
+// so the stand-alone layer and the one-pass head cannot drift apart (the library is built with -ffp-contract=off).
+struct AlignRoi {      // one ROI under one context padding (roi_align_layer.cu:33-50)
+  float start_h, start_w, height, width, bin_h, bin_w;
+};
+struct AlignTap {      // one grid point of it: the four clamped cells as offsets into a feature plane, their weights; !inside: the sample is 0
+  int o00, o10, o01, o11;
+  float w00, w10, w01, w11;
+  bool inside;
+};
+
+__device__ __forceinline__ AlignRoi align_roi(const float* __restrict__ roi, float pad_ratio, float spatial_scale, int PH, int PW) {
+  const float pad_w = (roi[3] - roi[1] + 1) * pad_ratio, pad_h = (roi[4] - roi[2] + 1) * pad_ratio;
+  float roi_start_w = (roi[1] - pad_w) * spatial_scale, roi_start_h = (roi[2] - pad_h) * spatial_scale;
+  float roi_end_w = (roi[3] + pad_w) * spatial_scale, roi_end_h = (roi[4] + pad_h) * spatial_scale;
+  roi_start_w -= 0.5f; roi_start_h -= 0.5f; roi_end_w -= 0.5f; roi_end_h -= 0.5f;
+  AlignRoi a;
+  a.start_h = roi_start_h; a.start_w = roi_start_w;
+  a.height = roi_end_h - roi_start_h; a.width = roi_end_w - roi_start_w;
+  a.bin_h = a.height / (float)PH; a.bin_w = a.width / (float)PW;
+  return a;
+}
+
+// Grid point (ph, pw) of the roi: outside (an empty roi, or a point off the map by the reference's -0.5 .. H - 0.5 test) nothing happens
+// and the sample is 0; inside, `use` gets the four clamped cells as offsets into a feature plane and their weights.
+template <typename F>
+__device__ __forceinline__ void align_point(const AlignRoi& a, int ph, int pw, int H, int W, F&& use) {
+  if (!(a.height <= 0 || a.width <= 0)) {
+    float hfloat = a.start_h + (float)ph * a.bin_h, wfloat = a.start_w + (float)pw * a.bin_w;
+    if (!(hfloat < -0.5f || hfloat > (H - 0.5f) || wfloat < -0.5f || wfloat > (W - 0.5f))) {
+      int hfloor = (int)floorf(hfloat), wfloor = (int)floorf(wfloat);
+      int hceil = hfloor + 1, wceil = wfloor + 1;
+      hfloat = fminf(fmaxf(hfloat, 0.f), (float)(H - 1)); wfloat = fminf(fmaxf(wfloat, 0.f), (float)(W - 1));
+      hfloor = min(max(hfloor, 0), H - 1); wfloor = min(max(wfloor, 0), W - 1);
+      hceil = min(max(hceil, 0), H - 1); wceil = min(max(wceil, 0), W - 1);
+      const float lh = hfloat - hfloor, lw = wfloat - wfloor, hh = 1 - lh, hw = 1 - lw;
+      const float w00 = hw * hh, w10 = lw * hh, w01 = hw * lh, w11 = lw * lh;
+      use(hfloor * W + wfloor, hfloor * W + wceil, hceil * W + wfloor, hceil * W + wceil, w00, w10, w01, w11);
+    }
+  }
+}
+
+// the sample of an inside point on one feature plane
+__device__ __forceinline__ float align_sum(const float* __restrict__ plane, int o00, int o10, int o01, int o11, float w00, float w10,
+                                            float w01, float w11) {
+  const float v00 = plane[o00], v10 = plane[o10];
+  const float v01 = plane[o01], v11 = plane[o11];
+  return w00 * v00 + w10 * v10 + w01 * v01 + w11 * v11;
+}
+
+__device__ __forceinline__ AlignTap align_tap(const AlignRoi& a, int ph, int pw, int H, int W) {
+  AlignTap t;
+  t.o00 = t.o10 = t.o01 = t.o11 = 0;
+  t.w00 = t.w10 = t.w01 = t.w11 = 0.f;
+  t.inside = false;
+  align_point(a, ph, pw, H, W, [&](int o00, int o10, int o01, int o11, float w00, float w10, float w01, float w11) {
+    t.o00 = o00; t.o10 = o10; t.o01 = o01; t.o11 = o11;
+    t.w00 = w00; t.w10 = w10; t.w01 = w01; t.w11 = w11;
+    t.inside = true;
+  });
+  return t;
+}
+
+__device__ __forceinline__ float align_sample(const AlignTap& t, const float* __restrict__ plane) {
+  return t.inside ? align_sum(plane, t.o00, t.o10, t.o01, t.o11, t.w00, t.w10, t.w01, t.w11) : 0.f;
+}
+
 __global__ __launch_bounds__(kThreads) void roialign_kernel(const float* __restrict__ feat, const float* __restrict__ rois,
                                                             float* __restrict__ out, int C, int H, int W, int PH, int PW,
                                                             float spatial_scale, float pad_ratio, int chan_per_block) {
@@ -262,12 +329,7 @@ __global__ __launch_bounds__(kThreads) void roialign_kernel(const float* __restr
   const int GH = PH + 1, GW = PW + 1, pts = GH * GW;
   const float* roi = rois + 5 * (size_t)r;
   const int b = (int)roi[0];
-  const float pad_w = (roi[3] - roi[1] + 1) * pad_ratio, pad_h = (roi[4] - roi[2] + 1) * pad_ratio;
-  float roi_start_w = (roi[1] - pad_w) * spatial_scale, roi_start_h = (roi[2] - pad_h) * spatial_scale;
-  float roi_end_w = (roi[3] + pad_w) * spatial_scale, roi_end_h = (roi[4] + pad_h) * spatial_scale;
-  roi_start_w -= 0.5f; roi_start_h -= 0.5f; roi_end_w -= 0.5f; roi_end_h -= 0.5f;
-  const float roi_height = roi_end_h - roi_start_h, roi_width = roi_end_w - roi_start_w;
-  const float bin_size_h = roi_height / (float)PH, bin_size_w = roi_width / (float)PW;
+  const AlignRoi a = align_roi(roi, pad_ratio, spatial_scale, PH, PW);
   const float* fbase = feat + (size_t)b * C * H * W;
   float* obase = out + (size_t)r * C * pts;
   const int work = (c_end - c_begin) * pts;
@@ -275,23 +337,106 @@ __global__ __launch_bounds__(kThreads) void roialign_kernel(const float* __restr
     const int c = c_begin + i / pts, g = i % pts;
     const int ph = g / GW, pw = g % GW;
     float val = 0.f;
-    if (!(roi_height <= 0 || roi_width <= 0)) {
-      float hfloat = roi_start_h + (float)ph * bin_size_h, wfloat = roi_start_w + (float)pw * bin_size_w;
-      if (!(hfloat < -0.5f || hfloat > (H - 0.5f) || wfloat < -0.5f || wfloat > (W - 0.5f))) {
-        int hfloor = (int)floorf(hfloat), wfloor = (int)floorf(wfloat);
-        int hceil = hfloor + 1, wceil = wfloor + 1;
-        hfloat = fminf(fmaxf(hfloat, 0.f), (float)(H - 1)); wfloat = fminf(fmaxf(wfloat, 0.f), (float)(W - 1));
-        hfloor = min(max(hfloor, 0), H - 1); wfloor = min(max(wfloor, 0), W - 1);
-        hceil = min(max(hceil, 0), H - 1); wceil = min(max(wceil, 0), W - 1);
-        const float lh = hfloat - hfloor, lw = wfloat - wfloor, hh = 1 - lh, hw = 1 - lw;
-        const float w00 = hw * hh, w10 = lw * hh, w01 = hw * lh, w11 = lw * lh;
-        const float* plane = fbase + (size_t)c * H * W;
-        const float v00 = plane[hfloor * W + wfloor], v10 = plane[hfloor * W + wceil];
-        const float v01 = plane[hceil * W + wfloor], v11 = plane[hceil * W + wceil];
-        val = w00 * v00 + w10 * v10 + w01 * v01 + w11 * v11;
+    align_point(a, ph, pw, H, W, [&](int o00, int o10, int o01, int o11, float w00, float w10, float w01, float w11) {
+      val = align_sum(fbase + (size_t)c * H * W, o00, o10, o01, o11, w00, w10, w01, w11);
+    });
+    obase[(size_t)c * pts + g] = val;
+  }
+}
+
+// ---- ROIAlign + 2x2 / stride 1 AVE Pooling (+ Concat) in one pass ------------------------------------------------------------------
+// The deploy's head (roi_grid_org / roi_pool_org / roi_grid_ctx / roi_pool_ctx / roi_pool) as one launch: one workgroup per (channel
+// group, roi), as above.  What does not depend on the channel is done once per workgroup: the first (PH+1)(PW+1) lanes compute each
+// window's taps into an LDS table.  Then a SLOT of `pts` lanes owns one channel at a time -- lane g keeps its grid point's taps of
+// every window in registers and samples channel after channel into LDS (the grid blob never exists in memory) -- and, after one
+// barrier, a slot of PH * PW lanes averages a channel's bins from its four samples in the pooling kernel's order (acc = 0; += g[ph][pw],
+// g[ph][pw+1], g[ph+1][pw], g[ph+1][pw+1]; / 4: pool_general_kernel's AVE branch with a whole 2 x 2 window) and stores them: the
+// workgroup's channels x bins of a window are one contiguous run of out[r][c_offset + c_begin ..][:][:].
+struct AlignPass { float pad_ratio; int c_offset; };
+constexpr int kAlignMaxPts = kThreads;      // grid points per ROI the tap table (and the lane-per-point mapping) holds: bins up to 15 x 15
+
+inline size_t align_ave_lds_bytes(int NP, int pts, int chan_per_block) {
+  return sizeof(float) * NP * pts * (9 + (size_t)chan_per_block);
+}
+
+template <int NP>
+__global__ __launch_bounds__(kThreads) void roialign_ave_kernel(const float* __restrict__ feat, const float* __restrict__ rois,
+                                                                float* __restrict__ out, int C, int H, int W, int PH, int PW,
+                                                                float spatial_scale, AlignPass pass0, AlignPass pass1, int C_total,
+                                                                int chan_per_block) {
+  extern __shared__ float s_align[];
+  const int tid = threadIdx.x;
+  const int r = blockIdx.y;
+  const int c_begin = blockIdx.x * chan_per_block;
+  const int nchan = min(C, c_begin + chan_per_block) - c_begin;
+  const int GW = PW + 1, pts = (PH + 1) * GW, bins = PH * PW;
+  // LDS: the tap table [NP][pts] of (4 weights, 4 offsets, inside), then the samples [NP][chan_per_block][pts]
+  float* s_w = s_align;
+  int* s_o = reinterpret_cast<int*>(s_align + NP * pts * 4);
+  int* s_in = s_o + NP * pts * 4;
+  float* s_g = reinterpret_cast<float*>(s_in + NP * pts);
+
+  const float* roi = rois + 5 * (size_t)r;
+  const int b = (int)roi[0];
+  if (tid < pts) {
+    const int ph = tid / GW, pw = tid - ph * GW;
+#pragma unroll
+    for (int q = 0; q < NP; ++q) {
+      const AlignRoi a = align_roi(roi, q == 0 ? pass0.pad_ratio : pass1.pad_ratio, spatial_scale, PH, PW);
+      const AlignTap t = align_tap(a, ph, pw, H, W);
+      float* w = s_w + (q * pts + tid) * 4;
+      int* o = s_o + (q * pts + tid) * 4;
+      w[0] = t.w00; w[1] = t.w10; w[2] = t.w01; w[3] = t.w11;
+      o[0] = t.o00; o[1] = t.o10; o[2] = t.o01; o[3] = t.o11;
+      s_in[q * pts + tid] = t.inside ? 1 : 0;
+    }
+  }
+  __syncthreads();
+
+  const size_t HW = (size_t)H * W;
+  const float* fbase = feat + ((size_t)b * C + c_begin) * HW;
+  {
+    const int slots = kThreads / pts;               // >= 1: pts <= kAlignMaxPts
+    const int slot = tid / pts, g = tid - slot * pts;
+    if (slot < slots) {
+      AlignTap t[NP];
+#pragma unroll
+      for (int q = 0; q < NP; ++q) {
+        const float* w = s_w + (q * pts + g) * 4;
+        const int* o = s_o + (q * pts + g) * 4;
+        t[q].w00 = w[0]; t[q].w10 = w[1]; t[q].w01 = w[2]; t[q].w11 = w[3];
+        t[q].o00 = o[0]; t[q].o10 = o[1]; t[q].o01 = o[2]; t[q].o11 = o[3];
+        t[q].inside = s_in[q * pts + g] != 0;
+      }
+      for (int c = slot; c < nchan; c += slots) {
+        const float* plane = fbase + (size_t)c * HW;
+#pragma unroll
+        for (int q = 0; q < NP; ++q) s_g[(q * chan_per_block + c) * pts + g] = align_sample(t[q], plane);
       }
     }
-    obase[(size_t)c * pts + g] = val;
+  }
+  __syncthreads();
+  {
+    const int slots = kThreads / bins;              // bins < pts
+    const int slot = tid / bins, bin = tid - slot * bins;
+    if (slot < slots) {
+      const int ph = bin / PW, pw = bin - ph * PW;
+      const int g0 = ph * GW + pw;
+#pragma unroll
+      for (int q = 0; q < NP; ++q) {
+        const int c_offset = q == 0 ? pass0.c_offset : pass1.c_offset;
+        float* obase = out + ((size_t)r * C_total + c_offset + c_begin) * bins;
+        for (int c = slot; c < nchan; c += slots) {
+          const float* p = s_g + (q * chan_per_block + c) * pts + g0;
+          float acc = 0.f;
+          acc += p[0];
+          acc += p[1];
+          acc += p[GW];
+          acc += p[GW + 1];
+          obase[c * bins + bin] = acc / 4;
+        }
+      }
+    }
   }
 }
 
@@ -312,6 +457,70 @@ extern "C" int mscnn_roialign_fwd_f32(const float* feat, const float* rois, floa
   return MSCNN_OK;
 }
 
+
+namespace {
+// what both one-pass ROIAlign ops refuse before any launch; the texts name the argument
+int align_ave_check(const char* op, const float* feat, const float* rois, const float* out, int R, int N, int C, int H, int W,
+                    int pooled_h, int pooled_w) {
+  MSCNN_REQUIRE(feat, "%s: feat is a null pointer", op);
+  MSCNN_REQUIRE(rois, "%s: rois is a null pointer", op);
+  MSCNN_REQUIRE(out, "%s: out is a null pointer", op);
+  MSCNN_REQUIRE(R >= 0, "%s: R = %d must be >= 0", op, R);
+  MSCNN_REQUIRE(N > 0, "%s: N = %d must be > 0", op, N);
+  MSCNN_REQUIRE(C > 0, "%s: C = %d must be > 0", op, C);
+  MSCNN_REQUIRE(H > 0, "%s: H = %d must be > 0", op, H);
+  MSCNN_REQUIRE(W > 0, "%s: W = %d must be > 0", op, W);
+  MSCNN_REQUIRE(pooled_h > 0, "%s: pooled_h = %d must be > 0", op, pooled_h);
+  MSCNN_REQUIRE(pooled_w > 0, "%s: pooled_w = %d must be > 0", op, pooled_w);
+  MSCNN_REQUIRE((long)(pooled_h + 1L) * (pooled_w + 1L) <= kAlignMaxPts,
+                "%s: pooled_h x pooled_w = %d x %d is a grid of more than %d points ((pooled_h + 1) * (pooled_w + 1))", op, pooled_h,
+                pooled_w, kAlignMaxPts);
+  MSCNN_REQUIRE((size_t)H * W < (1u << 31), "%s: H x W = %d x %d: a feature plane of 2^31 elements or more", op, H, W);
+  return MSCNN_OK;
+}
+
+int align_ave_chan_per_block(int C) { return (C % 128 == 0) ? 16 : max(1, min(C, 16)); }      // as mscnn_roialign_fwd_f32
+}  // namespace
+
+extern "C" int mscnn_roialign_ave_fwd_f32(const float* feat, const float* rois, float* out, int R, int N, int C, int H, int W,
+                                          int pooled_h, int pooled_w, float spatial_scale, float pad_ratio, int C_total, int c_offset,
+                                          void* stream) {
+  const int rc = align_ave_check("roialign_ave", feat, rois, out, R, N, C, H, W, pooled_h, pooled_w);
+  if (rc != MSCNN_OK) return rc;
+  MSCNN_REQUIRE(c_offset >= 0, "roialign_ave: c_offset = %d is negative", c_offset);
+  MSCNN_REQUIRE((long)c_offset + C <= C_total, "roialign_ave: c_offset + C = %d + %d exceeds C_total = %d", c_offset, C, C_total);
+  if (R == 0) return MSCNN_OK;
+  const int chan_per_block = align_ave_chan_per_block(C);
+  const int pts = (pooled_h + 1) * (pooled_w + 1);
+  dim3 grid(cdiv(C, chan_per_block), R);   // channel group on grid.x: XCD-local feature planes, as in ROIPooling
+  roialign_ave_kernel<1><<<grid, kThreads, align_ave_lds_bytes(1, pts, chan_per_block), as_stream(stream)>>>(
+      feat, rois, out, C, H, W, pooled_h, pooled_w, spatial_scale, AlignPass{pad_ratio, c_offset}, AlignPass{0.f, 0}, C_total,
+      chan_per_block);
+  MSCNN_POST_LAUNCH();
+  return MSCNN_OK;
+}
+
+extern "C" int mscnn_roialign_ave_pair_fwd_f32(const float* feat, const float* rois, float* out, int R, int N, int C, int H, int W,
+                                               int pooled_h, int pooled_w, float spatial_scale, float pad_ratio_a, int c_offset_a,
+                                               float pad_ratio_b, int c_offset_b, int C_total, void* stream) {
+  const int rc = align_ave_check("roialign_ave_pair", feat, rois, out, R, N, C, H, W, pooled_h, pooled_w);
+  if (rc != MSCNN_OK) return rc;
+  MSCNN_REQUIRE(c_offset_a >= 0, "roialign_ave_pair: c_offset_a = %d is negative", c_offset_a);
+  MSCNN_REQUIRE(c_offset_b >= 0, "roialign_ave_pair: c_offset_b = %d is negative", c_offset_b);
+  MSCNN_REQUIRE((long)c_offset_a + C <= C_total, "roialign_ave_pair: c_offset_a + C = %d + %d exceeds C_total = %d", c_offset_a, C, C_total);
+  MSCNN_REQUIRE((long)c_offset_b + C <= C_total, "roialign_ave_pair: c_offset_b + C = %d + %d exceeds C_total = %d", c_offset_b, C, C_total);
+  MSCNN_REQUIRE((long)c_offset_a + C <= c_offset_b || (long)c_offset_b + C <= c_offset_a,
+                "roialign_ave_pair: the channel windows at c_offset_a = %d and c_offset_b = %d (C = %d) overlap", c_offset_a, c_offset_b, C);
+  if (R == 0) return MSCNN_OK;
+  const int chan_per_block = align_ave_chan_per_block(C);
+  const int pts = (pooled_h + 1) * (pooled_w + 1);
+  dim3 grid(cdiv(C, chan_per_block), R);
+  roialign_ave_kernel<2><<<grid, kThreads, align_ave_lds_bytes(2, pts, chan_per_block), as_stream(stream)>>>(
+      feat, rois, out, C, H, W, pooled_h, pooled_w, spatial_scale, AlignPass{pad_ratio_a, c_offset_a}, AlignPass{pad_ratio_b, c_offset_b},
+      C_total, chan_per_block);
+  MSCNN_POST_LAUNCH();
+  return MSCNN_OK;
+}
 
 extern "C" int mscnn_roipool_fwd_f32(const float* feat, const float* rois, float* out, int R, int N, int C, int H, int W,
                                      int pooled_h, int pooled_w, float spatial_scale, float pad_ratio, int C_total,

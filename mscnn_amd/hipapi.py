@@ -173,6 +173,10 @@ def lib():
         L.mscnn_roipool_pair_fwd_f32.argtypes = ([C.c_void_p] * 3 + [C.c_int] * 7 + [C.c_float, C.c_float, C.c_int, C.c_float, C.c_int, C.c_int]
                                                  + [C.c_void_p])
         L.mscnn_roialign_fwd_f32.argtypes = [C.c_void_p] * 3 + [C.c_int] * 7 + [C.c_float, C.c_float, C.c_void_p]
+        L.mscnn_roialign_ave_fwd_f32.argtypes = ([C.c_void_p] * 3 + [C.c_int] * 7 + [C.c_float, C.c_float] + [C.c_int] * 2
+                                                 + [C.c_void_p])
+        L.mscnn_roialign_ave_pair_fwd_f32.argtypes = ([C.c_void_p] * 3 + [C.c_int] * 7
+                                                      + [C.c_float, C.c_float, C.c_int, C.c_float, C.c_int, C.c_int] + [C.c_void_p])
         L.mscnn_eltwise_fwd_f32.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
         L.mscnn_boxoutput_workspace_bytes.restype = C.c_size_t
         L.mscnn_boxoutput_workspace_bytes.argtypes = [C.c_void_p]
@@ -574,6 +578,33 @@ def roialign(feat, rois, pooled_h, pooled_w, spatial_scale, pad_ratio=0.0):
     out = torch.empty((R, Cc, pooled_h + 1, pooled_w + 1), dtype=torch.float32, device=feat.device)
     _check(lib().mscnn_roialign_fwd_f32(_dev(feat), _dev(rois), _dev(out), R, N, Cc, H, W, pooled_h, pooled_w, spatial_scale,
                                         pad_ratio, _stream()))
+    return out
+
+
+def roialign_ave(feat, rois, ph, pw, scale, pad, out=None, c_total=None, c_offset=0):
+    """ROIAlign + the 2x2 / stride 1 AVE pooling in one launch, into channels [c_offset, c_offset + C) of out[R][c_total][ph][pw]."""
+    N, Cc, H, W = feat.shape
+    R = rois.shape[0]
+    c_total = c_total or Cc
+    if out is None:
+        out = torch.empty((R, c_total, ph, pw), dtype=torch.float32, device=feat.device)
+    _check(lib().mscnn_roialign_ave_fwd_f32(_dev(feat), _dev(rois), _dev(out), R, N, Cc, H, W, ph, pw, scale, pad, c_total, c_offset,
+                                            _stream()))
+    return out
+
+
+def roialign_ave_pair(feat, rois, ph, pw, scale, pad_a, pad_b, out=None, c_total=None, c_offset_a=0, c_offset_b=None):
+    """The ROIAlign head in one launch: both context windows, the 2x2 AVE pooling and the Concat (pad_a -> channels
+    [c_offset_a, + C), pad_b -> [c_offset_b, + C); c_offset_b defaults to the window behind a's)."""
+    N, Cc, H, W = feat.shape
+    R = rois.shape[0]
+    if c_offset_b is None:
+        c_offset_b = c_offset_a + Cc
+    c_total = c_total or max(c_offset_a, c_offset_b) + Cc
+    if out is None:
+        out = torch.empty((R, c_total, ph, pw), dtype=torch.float32, device=feat.device)
+    _check(lib().mscnn_roialign_ave_pair_fwd_f32(_dev(feat), _dev(rois), _dev(out), R, N, Cc, H, W, ph, pw, scale, pad_a, c_offset_a,
+                                                 pad_b, c_offset_b, c_total, _stream()))
     return out
 
 

@@ -246,6 +246,10 @@ class PoolingLayer : public Layer<Dtype> {
   virtual bool IsMaxPool2x2() const {
     return method_ == 0 && !global_pooling_ && kernel_h_ == 2 && kernel_w_ == 2 && stride_h_ == 2 && stride_w_ == 2 && pad_h_ == 0 && pad_w_ == 0;
   }
+  // the AVE 2x2 / stride 1 / pad 0 pooling that follows ROIAlign in the WiderFace cascade (Net's one-pass ROIAlign head)
+  bool IsAvePool2x2Stride1() const {
+    return method_ == 1 && !global_pooling_ && kernel_h_ == 2 && kernel_w_ == 2 && stride_h_ == 1 && stride_w_ == 1 && pad_h_ == 0 && pad_w_ == 0;
+  }
  protected:
   MSCNN_NO_CPU_PATH("Pooling")
   virtual void Forward_gpu(const vector<Blob<Dtype>*>& bottom, const vector<Blob<Dtype>*>& top);
@@ -415,6 +419,24 @@ template <typename Dtype>
 class ROIAlignLayer : public Layer<Dtype> {
  public:
   explicit ROIAlignLayer(const LayerParameter& param) : Layer<Dtype>(param) {}
+  // Net-level one-pass head (Net::SetRoiAlignOnePass): two ROIAlign layers over the same map and ROIs, each followed by the AVE 2x2 /
+  // stride 1 pooling, whose pooled tops feed one Concat (roi_grid_org / roi_pool_org / roi_grid_ctx / roi_pool_ctx / roi_pool).  The
+  // first layer of the pair is told where the Concat's top is and which channel windows the two poolings own; while the Net marks the
+  // pair live (all five layers run in one ForwardFromTo and the switch is on) its Forward shapes that blob and fills it with one
+  // mscnn_roialign_ave_pair_fwd_f32 launch, and the Net skips the other four layers.  Otherwise Forward is the stand-alone layer.
+  void PairWith(ROIAlignLayer* partner, Blob<Dtype>* head_top, int c_total, int c_offset, int partner_c_offset) {
+    partner_ = partner; head_top_ = head_top; head_c_total_ = c_total; head_c_offset_ = c_offset; partner_c_offset_ = partner_c_offset;
+  }
+  void set_pair_live(bool on) { pair_live_ = on; }
+  // what the last Forward ran: "roialign_ave_pair" when it was the one-pass head, "" for the stand-alone layer
+  const char* kernel_name() const { return last_fused_ ? "roialign_ave_pair" : ""; }
+  // the stand-alone layer on these bottoms, whatever the pair's state (Net::MaterializeBlob: a grid blob the fused forward did not
+  // write); kernel_name() keeps reporting the forward
+  void ForwardStandalone(const vector<Blob<Dtype>*>& bottom, const vector<Blob<Dtype>*>& top);
+  int pooled_height() const { return pooled_height_; }
+  int pooled_width() const { return pooled_width_; }
+  Dtype spatial_scale() const { return spatial_scale_; }
+  Dtype pad_ratio() const { return pad_ratio_; }
   virtual void LayerSetUp(const vector<Blob<Dtype>*>& bottom, const vector<Blob<Dtype>*>& top);
   virtual void Reshape(const vector<Blob<Dtype>*>& bottom, const vector<Blob<Dtype>*>& top);
   virtual inline const char* type() const { return "ROIAlign"; }
@@ -426,6 +448,10 @@ class ROIAlignLayer : public Layer<Dtype> {
   virtual void Forward_gpu(const vector<Blob<Dtype>*>& bottom, const vector<Blob<Dtype>*>& top);
   int channels_, height_, width_, pooled_height_, pooled_width_;
   Dtype spatial_scale_, pad_ratio_;
+  ROIAlignLayer* partner_ = nullptr;
+  Blob<Dtype>* head_top_ = nullptr;
+  int head_c_total_ = 0, head_c_offset_ = 0, partner_c_offset_ = 0;
+  bool pair_live_ = false, last_fused_ = false;
 };
 
 // include/caffe/layers/eltwise_layer.hpp

@@ -93,6 +93,23 @@ class Net {
     for (size_t k = 0; k < chain_pairs_.size(); ++k) out.push_back(std::make_pair(chain_pairs_[k].producer, chain_pairs_[k].consumer));
     return out;
   }
+  // The ROIAlign head in one pass.  A head is registered at construction (with or without `fusion`): two ROIAlign layers that read
+  // the same feature blob and the same ROI blob (through Split layers) with equal pooled_h / pooled_w / spatial_scale, each top read by
+  // exactly one Pooling layer that is AVE 2x2 / stride 1 / pad 0, those two tops read only by one Concat on axis 1 (roi_grid_org /
+  // roi_pool_org / roi_grid_ctx / roi_pool_ctx / roi_pool of the WiderFace cascade, once per stage).  OFF by default: nothing changes
+  // for a net that never calls this.  ON: in a ForwardFromTo whose range holds all five layers the first ROIAlign layer writes the
+  // Concat's top with one launch (ROIAlignLayer::PairWith) and the other four launch nothing; the two grid blobs and the two pooled
+  // blobs are then written on demand -- blob_by_name() / MaterializeBlob() / MaterializeStale() run the four skipped layers on the same
+  // bottoms, the very kernels the switch-off path runs --, and before a later call that does not run the whole head could change what
+  // they read.  A range that holds only part of a head runs its layers stand-alone.
+  void SetRoiAlignOnePass(bool on) { roialign_one_pass_ = on; }
+  bool roialign_one_pass() const { return roialign_one_pass_; }
+  // the first ROIAlign layer of every registered head
+  vector<int> roialign_pairs() const {
+    vector<int> out;
+    for (size_t k = 0; k < align_heads_.size(); ++k) out.push_back(align_heads_[k].layer[0]);
+    return out;
+  }
   // Numerical calibration on representative data: call after a Forward.  Every Convolution layer that runs a Winograd
   // form is re-computed with the direct k-ordered kernel on the same bottom (ConvolutionLayer::ErrorAgainstDirect); where
   // max |dy| / max(1, |y|, rms(y)) exceeds `tol` the layer is switched to the direct kernel for good (FallBackIfStrayed).  Returns the
@@ -171,6 +188,13 @@ class Net {
   struct ChainPair { int producer, consumer, blob; };              // convolution -> its only reader, a same-resolution 3x3 convolution (-1: read by its fused pooling only)
   vector<ChainPair> chain_pairs_;
   bool chain_fusion_ = true;
+  // layer: ROIAlign, ROIAlign, their Pooling layers, the Concat (the ROIAlign layers in net order); blob: the two grid blobs and the
+  // two pooled blobs; stale: the last forward of the head was the one-pass launch and those four blobs have not been written since
+  struct AlignHead { int layer[5]; int blob[4]; int first, last; mutable bool stale; bool live; };
+  vector<AlignHead> align_heads_;
+  bool roialign_one_pass_ = false;
+  void FindRoiAlignHeads();
+  void MaterializeAlignHead(const AlignHead& h) const;
   int SplitSource(int blob) const;      // through Split layers (their tops share the bottom's data) to the blob that holds the data
   vector<double> calib_err_;
   int NextWatchLayer() const;

@@ -139,7 +139,9 @@ const char* mscnn_net_layer_kernel(const mscnn_net* n, int l) {
   auto* c = dynamic_cast<caffe::ConvolutionLayer<float>*>(n->net->layers()[l].get());
   if (c) return c->kernel_name();
   auto* ip = dynamic_cast<caffe::InnerProductLayer<float>*>(n->net->layers()[l].get());
-  return ip ? ip->kernel_name() : "";
+  if (ip) return ip->kernel_name();
+  auto* ra = dynamic_cast<caffe::ROIAlignLayer<float>*>(n->net->layers()[l].get());
+  return ra ? ra->kernel_name() : "";
 }
 int mscnn_net_set_inner_product_algo(mscnn_net* n, int layer, int algo) {
   return guarded([&] {
@@ -231,6 +233,14 @@ int mscnn_net_set_boxoutput_one_pass(mscnn_net* n, int on) {
     for (const auto& layer : n->net->layers())
       if (auto* bo = dynamic_cast<caffe::BoxOutputLayer<float>*>(layer.get())) bo->set_one_pass(on != 0);
   });
+}
+int mscnn_net_set_roialign_one_pass(mscnn_net* n, int on) {
+  return guarded([&] { n->net->SetRoiAlignOnePass(on != 0); });
+}
+int mscnn_net_roialign_pairs(const mscnn_net* n, int* first_layers, int cap) {
+  const std::vector<int> heads = n->net->roialign_pairs();
+  for (int i = 0; first_layers && i < cap && i < (int)heads.size(); ++i) first_layers[i] = heads[i];
+  return (int)heads.size();
 }
 int mscnn_net_chain_pairs(const mscnn_net* n, int* producers, int* consumers, int cap) {
   const auto pairs = n->net->chain_pairs();

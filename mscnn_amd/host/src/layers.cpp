@@ -865,10 +865,21 @@ void ROIAlignLayer<Dtype>::Reshape(const vector<Blob<Dtype>*>& bottom, const vec
   top[0]->Reshape(bottom[1]->num(), channels_, pooled_height_ + 1, pooled_width_ + 1);   // :40-46 grid_height_/grid_width_
 }
 template <typename Dtype>
-void ROIAlignLayer<Dtype>::Forward_gpu(const vector<Blob<Dtype>*>& bottom, const vector<Blob<Dtype>*>& top) {
+void ROIAlignLayer<Dtype>::ForwardStandalone(const vector<Blob<Dtype>*>& bottom, const vector<Blob<Dtype>*>& top) {
+  Reshape(bottom, top);
   MSCNN_CHECK(mscnn_roialign_fwd_f32(bottom[0]->gpu_data(), bottom[1]->gpu_data(), top[0]->mutable_gpu_data(), bottom[1]->num(),
                                      bottom[0]->num(), channels_, height_, width_, pooled_height_, pooled_width_, spatial_scale_,
                                      pad_ratio_, S()));
+}
+template <typename Dtype>
+void ROIAlignLayer<Dtype>::Forward_gpu(const vector<Blob<Dtype>*>& bottom, const vector<Blob<Dtype>*>& top) {
+  last_fused_ = pair_live_ && partner_ && head_top_;
+  if (!last_fused_) { ForwardStandalone(bottom, top); return; }
+  // the one-pass head: both windows, the 2x2 average and the Concat, straight into the Concat's top
+  head_top_->Reshape(bottom[1]->num(), head_c_total_, pooled_height_, pooled_width_);
+  MSCNN_CHECK(mscnn_roialign_ave_pair_fwd_f32(bottom[0]->gpu_data(), bottom[1]->gpu_data(), head_top_->mutable_gpu_data(), bottom[1]->num(),
+                                              bottom[0]->num(), channels_, height_, width_, pooled_height_, pooled_width_, spatial_scale_,
+                                              pad_ratio_, head_c_offset_, partner_->pad_ratio_, partner_c_offset_, head_c_total_, S()));
 }
 
 // ------------------------------------------------------------------------------------------------ Eltwise

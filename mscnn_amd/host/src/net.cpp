@@ -208,6 +208,7 @@ void Net<Dtype>::Init(const NetParameter& in_param) {
   calib_err_.assign(layers_.size(), 0.0);
   layer_ms_.assign(layers_.size(), 0.f);
   if (fusion_) ApplyFusion();
+  FindRoiAlignHeads();
   WireAmax();
   handoff_seen_ = mscnn_wgemm_handoff_event();      // (events of launches before this net existed are not its business)
   LOG(INFO) << "Network initialization done.";
@@ -414,6 +415,79 @@ void Net<Dtype>::ApplyFusion() {
   }
 }
 
+// The ROIAlign heads of the net (net.hpp: SetRoiAlignOnePass).  Registration changes nothing by itself: the layers are paired, the
+// switch decides per ForwardFromTo.
+template <typename Dtype>
+void Net<Dtype>::FindRoiAlignHeads() {
+  // the one layer that reads `blob`, or -1 when there is none or more than one (a net output counts as a reader)
+  auto only_reader = [&](int blob) {
+    int reader = -1, readers = 0;
+    for (size_t l = 0; l < layers_.size(); ++l)
+      for (int bb : bottom_id_vecs_[l]) if (bb == blob) { reader = (int)l; ++readers; }
+    for (int ob : net_output_blob_indices_) if (ob == blob) ++readers;
+    return readers == 1 ? reader : -1;
+  };
+  auto writers = [&](int blob) {
+    int n = 0;
+    for (size_t l = 0; l < layers_.size(); ++l)
+      for (int t : top_id_vecs_[l]) if (t == blob) ++n;
+    return n;
+  };
+  vector<bool> taken(layers_.size(), false);
+  for (size_t i = 0; i < layers_.size(); ++i) {
+    ROIAlignLayer<Dtype>* a = taken[i] ? nullptr : dynamic_cast<ROIAlignLayer<Dtype>*>(layers_[i].get());
+    if (!a || bottom_id_vecs_[i].size() != 2 || fused_away_[i]) continue;
+    for (size_t j = i + 1; j < layers_.size(); ++j) {
+      ROIAlignLayer<Dtype>* b = taken[j] ? nullptr : dynamic_cast<ROIAlignLayer<Dtype>*>(layers_[j].get());
+      if (!b || bottom_id_vecs_[j].size() != 2 || fused_away_[j]) continue;
+      if (SplitSource(bottom_id_vecs_[i][0]) != SplitSource(bottom_id_vecs_[j][0]) ||
+          SplitSource(bottom_id_vecs_[i][1]) != SplitSource(bottom_id_vecs_[j][1])) continue;
+      if (a->pooled_height() != b->pooled_height() || a->pooled_width() != b->pooled_width() || a->spatial_scale() != b->spatial_scale())
+        continue;
+      const int ga = top_id_vecs_[i][0], gb = top_id_vecs_[j][0];
+      const int pa = only_reader(ga), pb = only_reader(gb);
+      if (pa < 0 || pb < 0 || pa == pb || pa < (int)i || pb < (int)j) continue;      // (each pooling behind its ROIAlign layer)
+      PoolingLayer<Dtype>* la = dynamic_cast<PoolingLayer<Dtype>*>(layers_[pa].get());
+      PoolingLayer<Dtype>* lb = dynamic_cast<PoolingLayer<Dtype>*>(layers_[pb].get());
+      if (!la || !lb || !la->IsAvePool2x2Stride1() || !lb->IsAvePool2x2Stride1() || fused_away_[pa] || fused_away_[pb]) continue;
+      const int ta = top_id_vecs_[pa][0], tb = top_id_vecs_[pb][0];
+      if (ta == ga || tb == gb) continue;                                             // (an in-place pooling: no blob of its own)
+      const int cc = only_reader(ta);
+      if (cc < 0 || cc != only_reader(tb) || cc < std::max(pa, pb) || fused_away_[cc]) continue;
+      if (string(layers_[cc]->type()) != "Concat" || bottom_id_vecs_[cc].size() != 2 || top_id_vecs_[cc].size() != 1) continue;
+      const ConcatParameter cp = layers_[cc]->layer_param().concat_param();
+      if ((cp.has_concat_dim() ? (int)cp.concat_dim() : cp.axis()) != 1) continue;
+      const int out = top_id_vecs_[cc][0];
+      // every blob of the head has one writer (nothing rewrites a grid or a pooled blob in place, nothing else fills the Concat's top)
+      if (writers(ga) != 1 || writers(gb) != 1 || writers(ta) != 1 || writers(tb) != 1 || writers(out) != 1) continue;
+      const int C = bottom_vecs_[i][0]->channels();
+      const bool a_first = bottom_id_vecs_[cc][0] == ta;      // the order of the Concat's bottoms gives the two channel offsets
+      a->PairWith(b, top_vecs_[cc][0], 2 * C, a_first ? 0 : C, a_first ? C : 0);
+      AlignHead h;
+      h.layer[0] = (int)i; h.layer[1] = (int)j; h.layer[2] = pa; h.layer[3] = pb; h.layer[4] = cc;
+      h.blob[0] = ga; h.blob[1] = gb; h.blob[2] = ta; h.blob[3] = tb;
+      h.first = (int)i; h.last = cc;
+      h.stale = false; h.live = false;
+      align_heads_.push_back(h);
+      taken[i] = taken[j] = true;
+      break;
+    }
+  }
+}
+
+// the four blobs a one-pass forward of the head did not write, from the bottoms its layers were given: the stand-alone layers themselves
+template <typename Dtype>
+void Net<Dtype>::MaterializeAlignHead(const AlignHead& h) const {
+  if (!h.stale) return;
+  h.stale = false;
+  for (int k = 0; k < 2; ++k) {
+    const int l = h.layer[k];
+    for (int bb : bottom_id_vecs_[l]) MaterializeBlob(bb);
+    static_cast<ROIAlignLayer<Dtype>*>(layers_[l].get())->ForwardStandalone(bottom_vecs_[l], top_vecs_[l]);
+  }
+  for (int k = 2; k < 4; ++k) layers_[h.layer[k]]->Forward(bottom_vecs_[h.layer[k]], top_vecs_[h.layer[k]]);
+}
+
 template <typename Dtype>
 int Net<Dtype>::SplitSource(int blob) const {
   for (bool moved = true; moved;) {
@@ -444,6 +518,11 @@ void Net<Dtype>::MaterializePendingReadersOf(const string& blob_name) const {
       }
     for (size_t a = 1; a < affected.size(); ++a) MaterializeBlob(affected[a]);
   }
+  // a ROIAlign head's unwritten blobs hang on its feature and ROI blobs
+  for (size_t k = 0; k < align_heads_.size(); ++k)
+    if (align_heads_[k].stale)
+      for (int bb : bottom_id_vecs_[align_heads_[k].first])
+        if (SplitSource(bb) == SplitSource(blob_names_index_.find(blob_name)->second)) MaterializeAlignHead(align_heads_[k]);
   if (deferred_pools_.empty()) return;
   const int src = SplitSource(blob_names_index_.find(blob_name)->second);
   for (size_t k = 0; k < deferred_pools_.size(); ++k) {
@@ -456,6 +535,7 @@ void Net<Dtype>::MaterializePendingReadersOf(const string& blob_name) const {
 template <typename Dtype>
 void Net<Dtype>::MaterializeStale() const {
   for (size_t k = 0; k < chain_pairs_.size(); ++k) MaterializeBlob(chain_pairs_[k].blob);
+  for (size_t k = 0; k < align_heads_.size(); ++k) MaterializeAlignHead(align_heads_[k]);
 }
 
 template <typename Dtype>
@@ -477,6 +557,11 @@ void Net<Dtype>::MaterializeBlob(int blob_id) const {
         c->ForwardUnchained(bottom_vecs_[i], top_vecs_[i]);
       }
     }
+  // a grid or pooled blob of a ROIAlign head whose last forward was the one-pass launch
+  for (size_t k = 0; k < align_heads_.size(); ++k)
+    if (align_heads_[k].stale)
+      for (int q = 0; q < 4; ++q)
+        if (align_heads_[k].blob[q] == blob_id) MaterializeAlignHead(align_heads_[k]);
   typename std::map<int, Redirect>::const_iterator it = redirect_.find(blob_id);
   // a deferred ROIPooling pair's blob (asked for directly, or as the home of a redirected roi_pool_org / roi_pool_ctx): write it now
   for (size_t k = 0; k < deferred_pools_.size(); ++k)
@@ -665,6 +750,15 @@ Dtype Net<Dtype>::ForwardFromTo(int start, int end) {
     }
     if (any) HIP_CHECK(hipMemsetAsync(amax_slots_, 0, sizeof(unsigned) * MSCNN_AMAX_SLOTS * layers_.size(), (hipStream_t)Caffe::stream()));
   }
+  // ROIAlign heads: one pass when the switch is on and all five layers run in this call.  Blobs an earlier one-pass forward left
+  // unwritten are written first unless this call writes them itself: it may rewrite what they are computed from
+  for (size_t k = 0; k < align_heads_.size(); ++k) {
+    AlignHead& h = align_heads_[k];
+    const bool whole_head = start <= h.first && h.last <= end;
+    h.live = roialign_one_pass_ && whole_head;
+    if (!whole_head) MaterializeAlignHead(h);
+    else if (!h.live) h.stale = false;      // (the stand-alone layers of this call write all four)
+  }
   // convolution chains: a pair is live when both members run in this call; a consumer that runs WITHOUT its producer reads a blob
   // the last whole Forward may not have written
   for (size_t k = 0; k < chain_pairs_.size(); ++k) {
@@ -703,9 +797,28 @@ Dtype Net<Dtype>::ForwardFromTo(int start, int end) {
       else
         layers_[i]->Reshape(bottom_vecs_[i], top_vecs_[i]);      // shapes follow the bottoms exactly as Layer::Forward would
     }
+    // a live ROIAlign head: its first layer does the work of all five, the other four only take their shapes
+    int head_role = -1;
+    const AlignHead* head = nullptr;
+    for (size_t k = 0; k < align_heads_.size() && !head; ++k)
+      if (align_heads_[k].live)
+        for (int q = 0; q < 5; ++q)
+          if (align_heads_[k].layer[q] == i) { head = &align_heads_[k]; head_role = q; }
+    if (head && head_role > 0) {
+      layers_[i]->Reshape(bottom_vecs_[i], top_vecs_[i]);
+      run = false;
+    }
     if (!run) { layer_ms_[i] = 0.f; continue; }
     if (timing_) HIP_CHECK(hipEventRecord(e0, (hipStream_t)Caffe::stream()));
-    layers_[i]->Forward(bottom_vecs_[i], top_vecs_[i]);
+    if (head) {
+      ROIAlignLayer<Dtype>* ra = static_cast<ROIAlignLayer<Dtype>*>(layers_[i].get());
+      ra->set_pair_live(true);
+      ra->Forward(bottom_vecs_[i], top_vecs_[i]);
+      ra->set_pair_live(false);
+      head->stale = true;
+    } else {
+      layers_[i]->Forward(bottom_vecs_[i], top_vecs_[i]);
+    }
     for (size_t t = 0; t < top_id_vecs_[i].size(); ++t)
       if (redirect_.count(top_id_vecs_[i][t])) redirect_dirty_[top_id_vecs_[i][t]] = true;
     if (timing_) {

@@ -63,7 +63,7 @@ def lib():
             "mscnn_net_set_conv_algo": [vp, ci, ci], "mscnn_net_set_inner_product_algo": [vp, ci, ci], "mscnn_net_set_conv_tuning": [vp, ci, ci, ci, ci],
             "mscnn_net_calibrate_numerics": [vp, C.c_double, vp], "mscnn_net_set_numerics_watch": [vp, ci, C.c_double],
             "mscnn_net_numerics_watch_state": [vp, vp, vp, ci], "mscnn_net_layer_calibration_err": [vp, ci],
-            "mscnn_net_set_auto_calibrate": [vp, C.c_double], "mscnn_net_set_chain_fusion": [vp, ci], "mscnn_net_set_boxoutput_one_pass": [vp, ci], "mscnn_net_chain_pairs": [vp, vp, vp, ci], "mscnn_net_auto_calibrate_state": [vp, vp, vp, ci],
+            "mscnn_net_set_auto_calibrate": [vp, C.c_double], "mscnn_net_set_chain_fusion": [vp, ci], "mscnn_net_set_boxoutput_one_pass": [vp, ci], "mscnn_net_set_roialign_one_pass": [vp, ci], "mscnn_net_roialign_pairs": [vp, vp, ci], "mscnn_net_chain_pairs": [vp, vp, vp, ci], "mscnn_net_auto_calibrate_state": [vp, vp, vp, ci],
             "mscnn_net_load_caffemodel": [vp, cs], "mscnn_net_set_stream": [vp], "mscnn_net_num_layers": [vp],
             "mscnn_net_layer_name": [vp, ci], "mscnn_net_layer_type": [vp, ci], "mscnn_net_layer_index": [vp, cs],
             "mscnn_net_layer_num_bottoms": [vp, ci], "mscnn_net_layer_num_tops": [vp, ci], "mscnn_net_layer_bottom": [vp, ci, ci],
@@ -226,6 +226,18 @@ class Net:
         """BoxOutput of a batched net: every image side by side (on) or image after image (off, the default until the batched op has been timed) -- same bytes either way; a
         net of one image always runs the per-image op."""
         _check(lib().mscnn_net_set_boxoutput_one_pass(self._h, int(on)))
+
+    def set_roialign_one_pass(self, on=True):
+        """The ROIAlign head (two ROIAlign layers, their 2x2 AVE poolings and the Concat; the WiderFace cascade has one per stage) as one
+        launch (on) or as its five layers (off, the default) -- same bytes either way, also for the grid and pooled blobs, which are
+        written on demand when the head ran in one pass."""
+        _check(lib().mscnn_net_set_roialign_one_pass(self._h, int(on)))
+
+    def roialign_pairs(self):
+        """[index of the first ROIAlign layer] of every head the net registered at construction."""
+        a = (C.c_int * 64)()
+        k = lib().mscnn_net_roialign_pairs(self._h, a, 64)
+        return [a[i] for i in range(min(k, 64))]
 
     def chain_pairs(self):
         """[(producer layer name, consumer layer name | None)]: convolutions whose top may stay unwritten while a forward runs

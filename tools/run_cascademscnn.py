@@ -9,6 +9,7 @@ detections/<comp_id>_<class>_<output>_results.txt written as dlmwrite does (:148
          [--outputs 1st,2nd,3rd] [--cls-ids 2] [--det-thr 0.05] [--nms-overlap 0.5] [--batch B] [--precision f32|f16x3|f16]
          [--out detections] [--comp-id cascade_mscnn] [--names bg,car,van,truck,tram] [--limit N]
          [--nms-type maxg|max] [--ovr-dnm union|min] [--nms-thr T]      # pNms.type / pNms.ovrDnm / bbNms's thr (Net.set_nms)
+         [--roialign-one-pass]      # the ROIAlign heads of the net as one launch each (Net.set_roialign_one_pass; same results)
   python tools/run_cascademscnn.py --model kitti_car/cascade-mscnn-7s-576-2x --synthetic 8 --batch 2      # no dataset / weights at
                                                             # hand: the generated deploy net, seeded weights, synthetic frames
   python tools/run_cascademscnn.py --model widerface/cascade-mscnn-12s-align --images faces/ --orig-size [--max-size 3072]
@@ -87,6 +88,8 @@ def parse_args(argv=None):
     ap.add_argument("--max-size", type=int, default=3072, help="--orig-size: scale frames down to this side length first")
     ap.add_argument("--dump-blobs", default="", help="directory: the cascade outputs' blobs and the frames' ratios / sizes of every "
                     "forward as group_NNNN.npz (to re-run the final stage on exactly what a forward produced)")
+    ap.add_argument("--roialign-one-pass", action="store_true", help="run every ROIAlign head (two ROIAlign layers, their 2x2 AVE "
+                    "poolings, the Concat: the WiderFace cascade's) as one launch (Net.set_roialign_one_pass); off: the five layers")
     a = ap.parse_args(argv)
     if not (a.prototxt or a.model) or not (a.images or a.synthetic):
         ap.error("need --prototxt or --model, and --images or --synthetic N")
@@ -128,6 +131,8 @@ def main(argv=None):
         synth.load_into(net, "mid")
     if a.precision != "f32":
         net.set_precision(a.precision)
+    if a.roialign_one_pass:
+        net.set_roialign_one_pass(True)
     out_names = [o for o in a.outputs.split(",") if o] or default_outputs(net.blob_names)
     outputs = [OUTPUT_BLOBS[o] for o in out_names]
     for o, triple in zip(out_names, outputs):
