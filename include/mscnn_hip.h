@@ -50,6 +50,7 @@
  *   boxoutput*                 heads, rois_out, props_out, anchor_ids_out, count_out_dev 4
  *   detections*                blobs, ids_out, count_out_dev 4; dets_out 8: refuses
  *   proposals_multi_fwd        props 8: refuses
+ *   rois_ingest                rows 8: refuses; rois, props, image_rows, status 4
  */
 #ifndef MSCNN_HIP_H_
 #define MSCNN_HIP_H_
@@ -648,6 +649,39 @@ MSCNN_API size_t mscnn_proposals_multi_pack_bytes(int num_images, int cap);
 /* Alignment: props 8, pack_dev 16 (refused). */
 MSCNN_API int mscnn_proposals_multi_fwd(const mscnn_proposals_desc* desc, int num_images, const float* props, int R_all, void* pack_dev,
                                         int cap, void* stream);
+
+/* Caller-supplied ROIs: R rows become the two blobs BoxOutput would have written -- rois [R][5] = (image, x1, y1, x2, y2) and
+ * props [R][6] = the same plus the score (props may be NULL: a BoxOutput with one top) -- in one launch, checked on the device
+ * because the rows may live there.  Two input forms:
+ *   MSCNN_ROIS_NET    fp32 rows [image x1 y1 x2 y2 score] in net-input coordinates, the layout of proposals_score: copied bit for bit.
+ *   MSCNN_ROIS_IMAGE  double rows [image x y w h score] in original-image pixels with a 0-based image index, the row convention of
+ *                     mscnn_net_proposals_multi; ratio_h / ratio_w: host arrays [num_images] (net input size / original image size):
+ *                       x1 = (float)(x * ratio_w)          y1 = (float)(y * ratio_h)
+ *                       x2 = (float)((x + w) * ratio_w)    y2 = (float)((y + h) * ratio_h)
+ *                     sums and products in double, each result rounded to fp32 once; image and score are (float) of the double.
+ *                     At most MSCNN_ROIS_MAX_RATIO_IMAGES images (the ratios travel with the launch); ratio_h / ratio_w are not read
+ *                     in the NET form and may be NULL there.
+ * Every row must hold finite values only (in the IMAGE form the fp32 results too), an image index that is a whole number in
+ * [0, num_images), and an image index not smaller than the row's in front of it: rows are grouped by image, as BoxOutput emits them
+ * (box_output_layer.cpp:107,156) and every reader of the blobs assumes.  An image may have no rows.
+ * Outputs: image_rows [num_images] = rows of each image (written only when every row is good) and status [4] =
+ *   {1, -1, 0, 0}                          every row is good, rois / props / image_rows are complete
+ *   {0, first bad row, reason, 0}          reason: MSCNN_ROIS_BAD_* below, the first that applies to that row in their order
+ * One workgroup walks the rows in steps of 256 and stops at the first bad row's verdict: the rows of the steps in front of that
+ * row's step have been written, no row of its step and none behind it; bad input never makes the kernel read or write outside
+ * its operands.  status and image_rows are written with ordinary stores and never read: they may be host-coherent pinned memory
+ * (the caller then needs no copy: an event behind the launch, and the words are there).
+ * Refused before the launch, naming the argument: a null rows / rois / image_rows / status, a coords value that is neither form,
+ * R < 1, num_images < 1, a rows pointer that is not 8-byte aligned (the other pointers: 4), in the IMAGE form null ratios, more
+ * images than the limit, a ratio that is not a positive finite number.  No pin on the reference (it has no such entry): the check
+ * is a numpy restatement of the formulas above. */
+enum { MSCNN_ROIS_NET = 0, MSCNN_ROIS_IMAGE = 1 };
+enum { MSCNN_ROIS_BAD_NONFINITE = 1, MSCNN_ROIS_BAD_IMAGE = 2, MSCNN_ROIS_BAD_ORDER = 3 };
+enum { MSCNN_ROIS_MAX_RATIO_IMAGES = 128 };
+MSCNN_API const char* mscnn_rois_reason_text(int reason);
+/* Alignment: rows 8 (refused); rois, props, image_rows, status 4. */
+MSCNN_API int mscnn_rois_ingest_f32(const void* rows, int coords, int R, int num_images, const double* ratio_h, const double* ratio_w,
+                                    float* rois, float* props, int* image_rows, int* status, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Image pre-processing in front of net.forward -- MATLAB `run_mscnn_detection.m:64-69`:

@@ -275,6 +275,40 @@ MSCNN_NET_API int mscnn_net_proposals_multi_device(mscnn_net* net, const mscnn_d
  * is bit-identical to one on a fresh net.  mscnn_net_proposals_multi then reads the blob as after a whole forward; the detect calls
  * would read the sub-net's blobs of an EARLIER forward. */
 MSCNN_NET_API int mscnn_net_forward_proposals(mscnn_net* net, int* last_layer);
+/* The opposite half: the detection sub-network on caller-supplied ROIs -- a tracker's predictions, another detector's proposals,
+ * ground-truth boxes, a proposals file --, without conv5_x / conv6_1 / the LFCN heads / pool6 / BoxOutput.  rows: R rows in host memory,
+ * or in device memory when on_device != 0, in one of the two forms of mscnn_rois_ingest_f32 (include/mscnn_hip.h), repeated here
+ * so that this header stands alone:
+ *   coords 0 (MSCNN_ROIS_NET)    fp32 [image x1 y1 x2 y2 score] in net-input coordinates, the layout of proposals_score; copied bit
+ *                                for bit; p may be NULL
+ *   coords 1 (MSCNN_ROIS_IMAGE)  double [image x y w h score] in original-image pixels, 0-based image index, the rows of
+ *                                mscnn_net_proposals_multi; p[num_images]: of each image's params only ratio_h and ratio_w are read;
+ *                                x1 = (float)(x * ratio_w), x2 = (float)((x + w) * ratio_w), y likewise with ratio_h
+ * Rows must be finite, carry a whole image index in [0, num_images) and be grouped by image in ascending order (an image may have
+ * none): they are checked on the device, and a bad row fails the call naming the row and the reason; the sub-net is then not run, the
+ * ROI blobs hold the one all-zero row BoxOutput emits when nothing survives, and the sub-net's blobs are those of an earlier forward.
+ * L = the BoxOutput layer mscnn_net_forward_proposals looks up (or a BoxOutput layer with one top that feeds the ROI layers), K = the
+ * last layer in front of L that a layer behind L depends on other than through L's tops (relu4_3 and its Split in the KITTI / Caltech
+ * deploys; the "-2x" nets' Deconvolution sits behind L).  The call writes the rows into L's tops as L itself would have (one launch,
+ * R is known before anything is enqueued: no host round trip inside the frame), runs layers 0 .. K when run_trunk != 0, then layers
+ * L + 1 .. last.  With run_trunk = 0 the feature blobs of the previous forward are used as they are: the caller vouches that they belong
+ * to the frame these ROIs are meant for.  image_rois [num_images] (may be NULL) = rows of each image.
+ * Refused before anything is enqueued, naming the value: R above the row bound of L (its max_nms_num x images: detection packs and
+ * workspaces are sized by it) or below 1, num_images other than the input's N, a net without ROI layers, a net built with device < 0.
+ * Afterwards every blob from L's tops to the net's outputs holds, bit for bit, what mscnn_net_forward writes when BoxOutput itself
+ * selects these rows -- blobs a fusion leaves unwritten and mscnn_net_get_blob materialises on demand included --, and the detect,
+ * detect_multi, detect_cascade_multi and proposals_multi calls work on the result unchanged.  (Under set_precision "f16x3" the
+ * sub-net measures max |x| of its input itself, as in any partial forward: the same gates, not the same bits.)  The layers between K
+ * and L are not run: their blobs, and with run_trunk = 0 the trunk's, are those of an EARLIER forward.  The ROI pooling's maps are not
+ * enqueued ahead (roi_c1 builds them itself), the call is not a whole forward for the numerics watch, and a later mscnn_net_forward is
+ * bit-identical to one on a fresh net.  A stream-K hand-off time-out noticed behind such a frame (mscnn_net_handoff_state) runs the
+ * same two ranges again around the rows, which are still in L's tops -- never a range that holds L.  Measured once (profiles/forward_rois.txt): slower than mscnn_net_forward today. */
+MSCNN_NET_API int mscnn_net_forward_rois(mscnn_net* net, const void* rows, int on_device, int coords, int R,
+                                         const mscnn_detect_params* p /* num_images of them; NULL for net-input coordinates */,
+                                         int num_images, int run_trunk, int* image_rois /* may be NULL */);
+/* L and K of mscnn_net_forward_rois for this net (layer indices; K = -1: nothing in front of L is needed).  Fails, as the call itself
+ * does, for a net without ROI layers.  Works on a net built with device < 0. */
+MSCNN_NET_API int mscnn_net_forward_rois_layers(const mscnn_net* net, int* L, int* K);
 
 
 /* Final stage of the cascade drivers (examples/kitti_car/run_cascademscnn.m:84-127) for ONE cascade output nn: the decoded boxes

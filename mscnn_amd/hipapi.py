@@ -216,6 +216,9 @@ def lib():
         L.mscnn_proposals_multi_pack_bytes.restype = C.c_size_t
         L.mscnn_proposals_multi_pack_bytes.argtypes = [C.c_int, C.c_int]
         L.mscnn_proposals_multi_fwd.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.mscnn_rois_reason_text.restype = C.c_char_p
+        L.mscnn_rois_reason_text.argtypes = [C.c_int]
+        L.mscnn_rois_ingest_f32.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 7
         _lib = L
     return _lib
 
@@ -859,6 +862,34 @@ def proposals_multi(props, images, raw_pack=False, pack=None):
     _check(lib().mscnn_proposals_multi_fwd(descs, B, _dev(props), R, _dev(pack), cap, _stream()))
     out = _read_multi_pack(pack[:nbytes], B, 1, R, cap, "proposals_multi")
     return (out, pack.cpu().numpy()) if raw_pack else out
+
+
+ROIS_NET, ROIS_IMAGE = 0, 1                                       # mscnn_rois_ingest_f32's coords
+ROIS_BAD_NONFINITE, ROIS_BAD_IMAGE, ROIS_BAD_ORDER = 1, 2, 3      # ... and the reasons of its status word
+ROIS_MAX_RATIO_IMAGES = 128
+
+
+def rois_ingest(rows, coords, num_images, ratios=None, with_props=True):
+    """Caller-supplied ROIs as BoxOutput's two blobs (mscnn_rois_ingest_f32).  rows: [R, 6] cuda tensor -- float32
+    [image x1 y1 x2 y2 score] for ROIS_NET, float64 [image x y w h score] for ROIS_IMAGE with ratios = [(ratio_h, ratio_w)] per image.
+    Returns (rois [R, 5], props [R, 6] or None, image_rows [N], status [4]) as numpy arrays after one synchronisation; rois and props
+    start as NaN and image_rows as -1, so what a refused list left unwritten shows."""
+    R = int(rows.shape[0])
+    want = torch.float64 if coords == ROIS_IMAGE else torch.float32
+    if rows.dtype != want or rows.dim() != 2 or rows.shape[1] != 6:
+        raise MscnnError(f"rois_ingest: rows must be [R, 6] {want}, got {tuple(rows.shape)} {rows.dtype}")
+    rois = torch.full((max(R, 1), 5), float("nan"), dtype=torch.float32, device=rows.device)
+    props = torch.full((max(R, 1), 6), float("nan"), dtype=torch.float32, device=rows.device) if with_props else None
+    image_rows = torch.full((max(num_images, 1),), -1, dtype=torch.int32, device=rows.device)
+    status = torch.full((4,), -1, dtype=torch.int32, device=rows.device)
+    rh = rw = None
+    if ratios is not None:
+        rh = (C.c_double * max(len(ratios), 1))(*[float(r[0]) for r in ratios])
+        rw = (C.c_double * max(len(ratios), 1))(*[float(r[1]) for r in ratios])
+    _check(lib().mscnn_rois_ingest_f32(_dev(rows), coords, R, num_images, rh, rw, _dev(rois), _dev(props), _dev(image_rows), _dev(status),
+                                       _stream()))
+    torch.cuda.synchronize()
+    return (rois.cpu().numpy(), None if props is None else props.cpu().numpy(), image_rows.cpu().numpy(), status.cpu().numpy())
 
 
 class CascadeOutput(C.Structure):

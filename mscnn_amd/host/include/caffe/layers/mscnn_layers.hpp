@@ -492,6 +492,19 @@ class BoxOutputLayer : public Layer<Dtype> {
   // more than one image: all of them side by side (mscnn_boxoutput_batch_fwd_f32) or image after image -- same tops.
   // Off until the batched op has been timed against the per-image one
   void set_one_pass(bool on) { one_pass_ = on; }
+  // Caller-supplied ROIs in place of the layer's own selection (Net::ForwardRois; include/mscnn_hip.h: mscnn_rois_ingest_f32).
+  //   RowBound: the row bound Forward_gpu would size the tops to for these bottoms (max_rows() is 0 before the first forward).
+  //   IngestBegin: sizes the tops to that bound as Forward_gpu does, stages host rows, enqueues the one launch that writes both
+  //   tops and records an event behind it; nothing waits.  ratio_h / ratio_w [num_images]: MSCNN_ROIS_IMAGE only.
+  //   IngestEnd: waits for that event (not for the stream) and reads the verdict from pinned memory.  true: the tops are cut to R rows,
+  //   image_rows [num_images] (may be null) holds every image's count.  false: *bad_row / *reason name the first bad row, and the tops
+  //   are the one all-zero row the layer itself emits when nothing survives (no reader ever sees a rejected row).
+  int RowBound(const vector<Blob<Dtype>*>& bottom) const;
+  void IngestBegin(const vector<Blob<Dtype>*>& bottom, const vector<Blob<Dtype>*>& top, const void* rows, bool on_device, int coords,
+                   int R, const double* ratio_h, const double* ratio_w, int num_images);
+  bool IngestEnd(const vector<Blob<Dtype>*>& top, int* bad_row, int* reason, int* image_rows);
+  // largest row count of one image among ingested rows (they need not respect the layer's own per-image bound); 0 after Forward_gpu
+  int max_image_rows() const { return max_image_rows_; }
  protected:
   MSCNN_NO_CPU_PATH("BoxOutput")
   virtual void Forward_gpu(const vector<Blob<Dtype>*>& bottom, const vector<Blob<Dtype>*>& top);
@@ -506,6 +519,11 @@ class BoxOutputLayer : public Layer<Dtype> {
   void* count_ready_ = nullptr;      // hipEvent_t behind BoxOutput's kernels
   int* host_count_ = nullptr;        // host-coherent pinned landing place of {R, real rows}, and the address the device writes it through
   int* host_count_dev_ = nullptr;
+  DeviceBuffer ingest_stage_;        // host rows of IngestBegin on their way to the kernel
+  void* ingest_ready_ = nullptr;     // hipEvent_t behind the ingest launch
+  int* ingest_host_ = nullptr;       // host-coherent pinned {status[4], image_rows[num_images]}, and the address the device writes it through
+  int* ingest_host_dev_ = nullptr;
+  int ingest_words_ = 0, ingest_rows_ = 0, ingest_images_ = 0, max_image_rows_ = 0;
 };
 
 // include/caffe/layers/decode_bbox_layer.hpp (TEST phase)

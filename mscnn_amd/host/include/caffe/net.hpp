@@ -146,6 +146,18 @@ class Net {
   //   HandoffRecover(): call right after synchronising Caffe::stream() on outputs of the last ForwardFromTo.  false = nothing was
   //   reported; true = the range has been run again (asynchronously, like any Forward): read the outputs again.
   bool HandoffRecover();
+  // The detection sub-net on caller-supplied ROIs (include/mscnn_net.h: mscnn_net_forward_rois).  L = the BoxOutput layer that feeds
+  // the ROI layers, K = the last layer in front of L that a layer behind L depends on other than through L's tops (relu4_3 and the
+  // Split behind it in the KITTI / Caltech deploys).  Order of work: the ingest into L's tops (BoxOutputLayer::IngestBegin; blobs that
+  // an earlier forward left pending on the ROI blob are written first), ForwardFromTo(0, K) when run_trunk, the wait for the ingest's
+  // verdict -- a bad row is a CHECK failure naming row and reason, and the sub-net does not run --, ForwardFromTo(L + 1, last).  The layers
+  // between K and L never run.  rows / coords / ratios: mscnn_rois_ingest_f32's; image_rois [num_images] may be null.  Everything
+  // that can be refused is refused before anything is enqueued.  While such a frame is the last one run, HandoffRecover() runs the
+  // same two ranges again around the ingested rows (they are still in L's tops) instead of one range that would hold L.
+  void ForwardRois(const void* rows, bool on_device, int coords, int R, const double* ratio_h, const double* ratio_w, int num_images,
+                   bool run_trunk, int* image_rois);
+  // L and K of ForwardRois (-1, -1 for a net that has no ROI layer fed by a BoxOutput layer)
+  void RoisLayers(int* L, int* K) const;
   // For callers that pipeline frames and therefore can NOT have a range run again (mscnn_net_detect_end): true when a hand-off event
   // was raised since the last look -- whole tiles are forced and the event is counted as in HandoffRecover, nothing is re-run.
   // (the stream is synchronised only up to the frame being collected: what was enqueued behind it stays "unchecked in flight")
@@ -212,6 +224,9 @@ class Net {
   int last_start_ = 0, last_end_ = -1;
   int suspect_start_ = -1;      // smallest `start` of the ranges run since the last synchronisation point that saw no hand-off event (-1: none)
   long forward_count_ = 0;
+  // the frame in flight is a ForwardRois: its two ranges (rois_trunk_: the first one ran) for HandoffRecover
+  bool rois_frame_ = false, rois_trunk_ = false, in_rois_call_ = false;
+  int rois_K_ = -1, rois_L_ = -1;
   DISABLE_COPY_AND_ASSIGN(Net);
 };
 

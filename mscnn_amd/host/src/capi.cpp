@@ -691,8 +691,11 @@ static int per_image_row_bound(mscnn_net* n, int num_images, int R_all) {
   for (size_t l = 0; l < layers.size(); ++l) {
     auto* bo = dynamic_cast<caffe::BoxOutputLayer<float>*>(layers[l].get());
     const auto& tops = n->net->top_vecs()[l];
-    if (bo && tops.size() == 2 && tops[1] == props && bo->max_rows() > 0)
+    if (bo && tops.size() == 2 && tops[1] == props && bo->max_rows() > 0) {
+      // (rows handed in through mscnn_net_forward_rois need not respect the layer's own per-image bound: their largest image counts)
+      if (bo->max_image_rows() > 0) return std::min(R_all, bo->max_image_rows());
       return std::min(R_all, std::max(1, bo->max_rows() / num_images));
+    }
   }
   return R_all;
 }
@@ -976,6 +979,31 @@ int mscnn_net_forward_proposals(mscnn_net* n, int* last_layer) {
     // maps, and `whole` is false for the numerics watch -- Net::ForwardFromTo)
     n->net->ForwardFromTo(0, L);
     if (last_layer) *last_layer = L;
+  });
+}
+
+int mscnn_net_forward_rois_layers(const mscnn_net* n, int* L, int* K) {
+  return guarded([&] {
+    CHECK(n && L && K) << "forward_rois_layers: null pointer";
+    n->net->RoisLayers(L, K);
+    CHECK_GE(*L, 0) << "forward_rois: net has no ROIPooling / ROIAlign layer fed by a BoxOutput layer: nothing to run on caller-supplied ROIs";
+  });
+}
+
+int mscnn_net_forward_rois(mscnn_net* n, const void* rows, int on_device, int coords, int R, const mscnn_detect_params* p, int num_images,
+                           int run_trunk, int* image_rois) {
+  return guarded([&] {
+    CHECK(n != nullptr) << "forward_rois: null net";
+    CHECK_GE(n->device, 0) << "forward_rois: the net was built with device " << n->device << " (graph only): nothing can run";
+    CHECK(rows != nullptr) << "forward_rois: null rows";
+    CHECK_GE(num_images, 1) << "forward_rois: num_images = " << num_images;
+    CHECK(coords == MSCNN_ROIS_NET || p != nullptr) << "forward_rois: original-image coordinates need params (num_images of them: "
+                                                       "ratio_h, ratio_w)";
+    std::vector<double> rh, rw;
+    if (coords != MSCNN_ROIS_NET && p)
+      for (int i = 0; i < num_images; ++i) { rh.push_back(p[i].ratio_h); rw.push_back(p[i].ratio_w); }
+    n->net->ForwardRois(rows, on_device != 0, coords, R, rh.empty() ? nullptr : rh.data(), rw.empty() ? nullptr : rw.data(), num_images,
+                        run_trunk != 0, image_rois);
   });
 }
 

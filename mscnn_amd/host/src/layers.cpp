@@ -967,6 +967,8 @@ template <typename Dtype>
 BoxOutputLayer<Dtype>::~BoxOutputLayer() {
   if (count_ready_) (void)hipEventDestroy((hipEvent_t)count_ready_);
   if (host_count_) (void)hipHostFree(host_count_);
+  if (ingest_ready_) (void)hipEventDestroy((hipEvent_t)ingest_ready_);
+  if (ingest_host_) (void)hipHostFree(ingest_host_);
 }
 
 template <typename Dtype>
@@ -983,6 +985,7 @@ void BoxOutputLayer<Dtype>::Forward_gpu(const vector<Blob<Dtype>*>& bottom, cons
   CHECK_GT(wbytes, 0u) << mscnn_last_error();
   void* ws = workspace_.Reserve(wbytes);
   cap_ = mscnn_boxoutput_max_rows(&d);
+  max_image_rows_ = 0;
   // the kernels write the tops themselves: the blobs are sized for the layer's row bound first (Blob::Reshape keeps the larger
   // allocation) and cut to R rows below -- the two D2D copies behind the host round trip are gone (r5)
   top[0]->Reshape(cap_, 5, 1, 1);
@@ -1017,6 +1020,84 @@ void BoxOutputLayer<Dtype>::Forward_gpu(const vector<Blob<Dtype>*>& bottom, cons
   last_rows_ = R;
   top[0]->Reshape(R, 5, 1, 1);
   if (output_proposal_with_score_) top[1]->Reshape(R, 6, 1, 1);
+}
+
+template <typename Dtype>
+int BoxOutputLayer<Dtype>::RowBound(const vector<Blob<Dtype>*>& bottom) const {
+  mscnn_boxoutput_desc d;
+  FillBoxOutputDesc(this->layer_param_, bottom, fg_thr_, iou_thr_, nms_type_, &d);
+  return mscnn_boxoutput_max_rows(&d);
+}
+
+template <typename Dtype>
+void BoxOutputLayer<Dtype>::IngestBegin(const vector<Blob<Dtype>*>& bottom, const vector<Blob<Dtype>*>& top, const void* rows, bool on_device,
+                                        int coords, int R, const double* ratio_h, const double* ratio_w, int num_images) {
+  CHECK(rows != nullptr) << "null rows";
+  CHECK_GE(num_images, 1);
+  cap_ = RowBound(bottom);
+  CHECK(R >= 1 && R <= cap_) << R << " rows, the layer's row bound is " << cap_;
+  // the tops exactly as Forward_gpu leaves them: sized for the row bound first, cut to R rows in IngestEnd
+  top[0]->Reshape(cap_, 5, 1, 1);
+  float* rois = top[0]->mutable_gpu_data();
+  float* props = nullptr;
+  if (output_proposal_with_score_) {
+    top[1]->Reshape(cap_, 6, 1, 1);
+    props = top[1]->mutable_gpu_data();
+  }
+  if (ingest_words_ < 4 + num_images) {
+    if (ingest_host_) HIP_CHECK(hipHostFree(ingest_host_));
+    ingest_host_ = nullptr; ingest_words_ = 0;
+    HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&ingest_host_), sizeof(int) * (4 + num_images),
+                            hipHostMallocPortable | hipHostMallocMapped | hipHostMallocCoherent));
+    void* dp = nullptr;
+    HIP_CHECK(hipHostGetDevicePointer(&dp, ingest_host_, 0));
+    ingest_host_dev_ = static_cast<int*>(dp);
+    ingest_words_ = 4 + num_images;
+  }
+  static_cast<volatile int*>(ingest_host_)[0] = -1;
+  const void* src = rows;
+  if (!on_device) {
+    const size_t bytes = (size_t)R * 6 * (coords == MSCNN_ROIS_IMAGE ? sizeof(double) : sizeof(float));
+    void* stage = ingest_stage_.Reserve(bytes);
+    HIP_CHECK(hipMemcpyAsync(stage, rows, bytes, hipMemcpyHostToDevice, (hipStream_t)S()));
+    src = stage;
+  }
+  MSCNN_CHECK(mscnn_rois_ingest_f32(src, coords, R, num_images, ratio_h, ratio_w, rois, props, ingest_host_dev_ + 4, ingest_host_dev_, S()));
+  if (!ingest_ready_) { hipEvent_t e; HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); ingest_ready_ = e; }
+  HIP_CHECK(hipEventRecord((hipEvent_t)ingest_ready_, (hipStream_t)S()));
+  ingest_rows_ = R; ingest_images_ = num_images;
+}
+
+template <typename Dtype>
+bool BoxOutputLayer<Dtype>::IngestEnd(const vector<Blob<Dtype>*>& top, int* bad_row, int* reason, int* image_rows) {
+  CHECK(ingest_ready_ != nullptr && ingest_rows_ > 0) << "IngestEnd without IngestBegin";
+  HIP_CHECK(hipEventSynchronize((hipEvent_t)ingest_ready_));
+  const volatile int* st = ingest_host_;
+  const int ok = st[0], R = ingest_rows_;
+  ingest_rows_ = 0;
+  CHECK(ok == 0 || ok == 1) << "the ROI ingest left no verdict (status word " << ok << ")";
+  if (ok == 1) {
+    max_image_rows_ = 0;
+    for (int i = 0; i < ingest_images_; ++i) {
+      max_image_rows_ = std::max(max_image_rows_, (int)st[4 + i]);
+      if (image_rows) image_rows[i] = st[4 + i];
+    }
+    last_rows_ = R;
+    top[0]->Reshape(R, 5, 1, 1);
+    if (output_proposal_with_score_) top[1]->Reshape(R, 6, 1, 1);
+    return true;
+  }
+  if (bad_row) *bad_row = st[1];
+  if (reason) *reason = st[2];
+  // rows in front of the bad one's step have been written, the others not: leave the layer's own "nothing survived" row instead
+  last_rows_ = 1; max_image_rows_ = 0;
+  top[0]->Reshape(1, 5, 1, 1);
+  HIP_CHECK(hipMemsetAsync(top[0]->mutable_gpu_data(), 0, sizeof(float) * 5, (hipStream_t)S()));
+  if (output_proposal_with_score_) {
+    top[1]->Reshape(1, 6, 1, 1);
+    HIP_CHECK(hipMemsetAsync(top[1]->mutable_gpu_data(), 0, sizeof(float) * 6, (hipStream_t)S()));
+  }
+  return false;
 }
 
 // ------------------------------------------------------------------------------------------------ DecodeBBox

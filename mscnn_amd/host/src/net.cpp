@@ -676,8 +676,96 @@ bool Net<Dtype>::HandoffRecover() {
   if (!HandoffEventPending()) { suspect_start_ = -1; return false; }
   const int from = suspect_start_ >= 0 ? suspect_start_ : last_start_, to = last_end_;
   suspect_start_ = -1;
+  if (rois_frame_) {
+    // the frame in flight ran 0 .. K and L + 1 .. last around caller-supplied ROIs: one range from the smallest start would run
+    // BoxOutput and replace them with its own.  The ingested rows are still in L's tops: the same two ranges again
+    in_rois_call_ = true;
+    if (rois_trunk_ && from <= rois_K_) ForwardFromTo(0, rois_K_);
+    ForwardFromTo(rois_L_ + 1, (int)layers_.size() - 1);
+    in_rois_call_ = false;
+    return true;
+  }
   if (to >= from) ForwardFromTo(from, to);
   return true;
+}
+
+template <typename Dtype>
+void Net<Dtype>::RoisLayers(int* L_out, int* K_out) const {
+  *L_out = *K_out = -1;
+  const int n = (int)layers_.size();
+  // the ROI blobs the ROI layers read, through Split layers
+  std::set<int> roi_blobs;
+  for (int l = 0; l < n; ++l) {
+    const string t = layers_[l]->type();
+    if ((t == "ROIPooling" || t == "ROIAlign") && bottom_id_vecs_[l].size() >= 2) roi_blobs.insert(SplitSource(bottom_id_vecs_[l][1]));
+  }
+  if (roi_blobs.empty()) return;
+  // L: the lookup of mscnn_net_forward_proposals (the BoxOutput layer whose second top is proposals_score), or a BoxOutput layer with
+  // one top that feeds the ROI layers
+  int L = -1;
+  const int want = has_blob("proposals_score") ? blob_names_index_.find("proposals_score")->second : -1;
+  for (int l = 0; l < n && L < 0; ++l)
+    if (string(layers_[l]->type()) == "BoxOutput" && top_id_vecs_[l].size() >= 2 && top_id_vecs_[l][1] == want &&
+        roi_blobs.count(top_id_vecs_[l][0]))
+      L = l;
+  for (int l = 0; l < n && L < 0; ++l)
+    if (string(layers_[l]->type()) == "BoxOutput" && top_id_vecs_[l].size() == 1 && roi_blobs.count(top_id_vecs_[l][0])) L = l;
+  if (L < 0) return;
+  // K: walking back from every layer behind L, never through L's tops
+  std::set<int> needed;
+  for (int l = L + 1; l < n; ++l)
+    for (int bb : bottom_id_vecs_[l]) needed.insert(bb);
+  for (int t : top_id_vecs_[L]) needed.erase(t);
+  int K = -1;
+  for (int l = L - 1; l >= 0; --l) {
+    bool feeds = false;
+    for (int t : top_id_vecs_[l]) feeds = feeds || needed.count(t) > 0;
+    if (!feeds) continue;
+    if (K < 0) K = l;
+    for (int bb : bottom_id_vecs_[l]) needed.insert(bb);
+  }
+  *L_out = L; *K_out = K;
+}
+
+template <typename Dtype>
+void Net<Dtype>::ForwardRois(const void* rows, bool on_device, int coords, int R, const double* ratio_h, const double* ratio_w,
+                             int num_images, bool run_trunk, int* image_rois) {
+  int L = -1, K = -1;
+  RoisLayers(&L, &K);
+  CHECK_GE(L, 0) << "forward_rois: net has no ROIPooling / ROIAlign layer fed by a BoxOutput layer: nothing to run on caller-supplied ROIs";
+  CHECK(rows != nullptr) << "forward_rois: null rows";
+  CHECK(coords == MSCNN_ROIS_NET || coords == MSCNN_ROIS_IMAGE) << "forward_rois: coords = " << coords << " (0 net-input, 1 original-image)";
+  BoxOutputLayer<Dtype>* bo = static_cast<BoxOutputLayer<Dtype>*>(layers_[L].get());
+  const int num = bottom_vecs_[L][0]->num();
+  CHECK_EQ(num_images, num) << "forward_rois: num_images " << num_images << " but the net's input holds " << num << " images";
+  const int bound = bo->RowBound(bottom_vecs_[L]);
+  CHECK_GE(R, 1) << "forward_rois: R = " << R << " (at least one row)";
+  CHECK_LE(R, bound) << "forward_rois: " << R << " rows, but BoxOutput layer " << layer_names_[L] << " bounds a forward to " << bound
+                     << " (its max_nms_num x images: detection packs and workspaces are sized by it)";
+  CHECK(coords == MSCNN_ROIS_NET || (ratio_h && ratio_w)) << "forward_rois: original-image coordinates need the per-image ratios";
+  // blobs an earlier forward left unwritten that hang on the ROI blob (a deferred ROI pooling, a one-pass ROIAlign head) are written
+  // now, from the rows they were computed for
+  MaterializePendingReadersOf(blob_names_[top_id_vecs_[L][0]]);
+  bo->IngestBegin(bottom_vecs_[L], top_vecs_[L], rows, on_device, coords, R, ratio_h, ratio_w, num_images);
+  const int last = (int)layers_.size() - 1;
+  in_rois_call_ = true;
+  rois_frame_ = false;
+  try {
+    if (run_trunk && K >= 0) ForwardFromTo(0, K);
+    // (by now the ingest is long done: the wait is for its event, not for the trunk)
+    int bad_row = -1, reason = 0;
+    const bool ok = bo->IngestEnd(top_vecs_[L], &bad_row, &reason, image_rois);
+    CHECK(ok) << "forward_rois: row " << bad_row << " of " << R << ": " << mscnn_rois_reason_text(reason) << " (reason " << reason
+              << "); the detection sub-net was not run";
+    // (the ROI pooling's maps: BoxOutput's before-sync hook has not run, roi_c1 builds them itself -- ConvolutionLayer::InvalidateRoiMaps
+    // at the head of every ForwardFromTo)
+    ForwardFromTo(L + 1, last);
+  } catch (...) {
+    in_rois_call_ = false;
+    throw;
+  }
+  in_rois_call_ = false;
+  rois_frame_ = true; rois_trunk_ = run_trunk && K >= 0; rois_K_ = K; rois_L_ = L;
 }
 
 template <typename Dtype>
@@ -691,6 +779,7 @@ Dtype Net<Dtype>::ForwardFromTo(int start, int end) {
     suspect_start_ = start;
   } else if (start < suspect_start_) suspect_start_ = start;
   last_start_ = start; last_end_ = end;
+  if (!in_rois_call_) rois_frame_ = false;      // (any other range ends a ForwardRois frame: HandoffRecover's one-range answer holds again)
   ++forward_count_;
   bool handoff_restart = false;
   // a watch frame: the verdict still out (if any) is taken first -- its kernels ran in front of everything this call will enqueue --,

@@ -94,6 +94,7 @@ def lib():
             "mscnn_net_detect_cascade_multi_device": [vp, vp, ci, ci, ci, vp, vp, vp, C.c_float, ci, vp],
             "mscnn_net_proposals_multi": [vp, vp, ci, vp, vp, ci, vp, vp], "mscnn_net_proposals_multi_device": [vp, vp, ci, ci, vp],
             "mscnn_net_forward_proposals": [vp, vp],
+            "mscnn_net_forward_rois": [vp, vp, ci, ci, ci, vp, ci, ci, vp], "mscnn_net_forward_rois_layers": [vp, vp, vp],
         }
         for name, args in sig.items():
             getattr(L, name).argtypes = args
@@ -349,6 +350,47 @@ class Net:
         last = C.c_int(-1)
         _check(lib().mscnn_net_forward_proposals(self._h, C.byref(last)))
         return last.value
+
+    def forward_rois_layers(self):
+        """mscnn_net_forward_rois_layers: (L, K) -- forward_rois writes the rows into layer L's tops (the BoxOutput layer) and runs
+        layers 0 .. K and L + 1 .. last."""
+        L, K = C.c_int(-1), C.c_int(-1)
+        _check(lib().mscnn_net_forward_rois_layers(self._h, C.byref(L), C.byref(K)))
+        return L.value, K.value
+
+    def forward_rois(self, rows, coords="net", params=None, run_trunk=True, num_images=None):
+        """mscnn_net_forward_rois: the detection sub-net on caller-supplied ROIs.  rows: [R, 6] numpy array or contiguous torch CUDA
+        tensor -- coords "net": float32 [image x1 y1 x2 y2 score] in net-input coordinates (the layout of proposals_score, copied bit
+        for bit); coords "image": float64 [image x y w h score] in original-image pixels with a 0-based image index (the rows of
+        proposals_multi) and params = one dict per image with ratios=(ratio_h, ratio_w) (the dicts set_images returns work as they
+        are).  Rows grouped by image; num_images defaults to len(params), else to the input blob's N.  run_trunk=False reuses the feature blobs of the
+        previous forward: the caller vouches for them.  Returns [rows per image]; detect* / proposals_multi then work as after
+        forward()."""
+        if coords not in ("net", "image"):
+            raise NetError(f"forward_rois: coords {coords!r} ('net' or 'image')")
+        code, dt, tdt = (0, np.float32, "torch.float32") if coords == "net" else (1, np.float64, "torch.float64")
+        if hasattr(rows, "is_cuda"):
+            if not rows.is_cuda or not rows.is_contiguous() or str(rows.dtype) != tdt or rows.dim() != 2 or rows.shape[1] != 6:
+                raise NetError(f"forward_rois: rows must be a contiguous [R, 6] {tdt} CUDA tensor for coords {coords!r}")
+            ptr, on_dev, R, keep = C.c_void_p(rows.data_ptr()), 1, int(rows.shape[0]), rows
+        else:
+            keep = np.ascontiguousarray(rows, dt)
+            if keep.ndim != 2 or keep.shape[1] != 6:
+                raise NetError(f"forward_rois: rows must be [R, 6], got {keep.shape}")
+            ptr, on_dev, R = keep.ctypes.data_as(C.c_void_p), 0, int(keep.shape[0])
+        if num_images is not None:
+            N = int(num_images)
+        elif params is not None:
+            N = len(params)
+        else:
+            N = self.blob_shape(self.layer_tops(0)[0])[0]      # (the Input layer's top)
+        p = None
+        if params is not None:
+            p = self._multi_params([{k: v for k, v in kw.items() if k == "ratios"} for kw in params], [1], org_hw=(0, 0))
+        out = np.zeros(max(N, 1), np.int32)
+        _check(lib().mscnn_net_forward_rois(self._h, ptr, on_dev, code, R, p, N, 1 if run_trunk else 0, out.ctypes.data_as(C.c_void_p)))
+        del keep
+        return out[:N].tolist()
 
     def reshape(self):
         _check(lib().mscnn_net_reshape(self._h))

@@ -10,6 +10,7 @@ examples/kitti_result/writeDetForEval.m.
          [--out detections] [--comp-id kitti_7s_576] [--cls-ids 2] [--names bg,car,van,truck,tram] [--precision f32|f16x3|f16]
          [--labels-dir results/data] [--limit N] [--batch B]
          [--proposals-out proposals] [--proposals-only]      # the proposal half of the result: proposals/<comp_id>.txt (:154, :161-162)
+         [--rois-in FILE]                                    # the detection sub-net on these boxes instead of the net's own proposals
          [--nms-type maxg|max] [--ovr-dnm union|min] [--nms-thr T] [--det-thr T]      # pNms.type / pNms.ovrDnm / bbNms's thr, and
                                                              # the det_thr of the WiderFace plain flow (Net.set_nms, once per run)
   python tools/run_mscnn_detection.py --model kitti_car/mscnn-7s-576 --synthetic 8      # no dataset / weights at hand: the generated
@@ -23,6 +24,11 @@ output files are the same, avgtime stays per frame.
 commented out): DIR/<comp_id>.txt, rows [image_index x y w h score], every image's proposals filtered as the final stage filters them
 and rescaled to the original image (Net.proposals_multi: one pass per forward, batch 1 and --batch B).  --proposals-only runs MS-CNN
 as a proposal generator: the layers up to BoxOutput (Net.forward_proposals), no detect call, no detection files.
+
+--rois-in FILE runs the other half alone: rows [image_index x y w h score] in original-image pixels, image_index 1-based over the
+frames of the run in ascending order -- the format --proposals-out writes -- go through Net.forward_rois instead of Net.forward, per
+frame or per --batch group (conv5_x, the proposal heads and BoxOutput never run); everything behind the forward is unchanged.  A frame
+without rows gets no detections; a group in which no frame has rows is not forwarded at all.  Not together with --proposals-only.
 
 Everything here is host glue over calls the test-suite covers one by one (Net.set_image / set_images, forward, detect / detect_multi,
 proposals_multi, kitti.write_*)."""
@@ -99,12 +105,40 @@ def parse_args(argv=None):
                     "filtered, rescaled proposals (final_proposals of the scripts)")
     ap.add_argument("--proposals-only", action="store_true", help="run the net up to BoxOutput only (Net.forward_proposals): no detect "
                     "call, no detection files; needs --proposals-out")
+    ap.add_argument("--rois-in", default="", help="file of rows [image_index x y w h score] (1-based index, original-image pixels: what "
+                    "--proposals-out writes): run the detection sub-net on these boxes (Net.forward_rois) instead of the whole net")
     a = ap.parse_args(argv)
     if a.proposals_only and not a.proposals_out:
         ap.error("--proposals-only needs --proposals-out DIR")
+    if a.proposals_only and a.rois_in:
+        ap.error("--rois-in runs the detection sub-net on given boxes, --proposals-only stops in front of it: not both")
     if not (a.prototxt or a.model) or not (a.images or a.synthetic):
         ap.error("need --prototxt or --model, and --images or --synthetic N")
     return a
+
+
+def read_rois(path, n_frames):
+    """--rois-in: the file's rows [image_index x y w h score] (1-based index, ascending: the layout of --proposals-out) as one float64
+    array [n, 5] = [x y w h score] per frame of the run; a frame the file does not mention has 0 rows."""
+    from mscnn_amd import kitti
+    per_frame = [[] for _ in range(n_frames)]
+    prev = 1
+    for ln, row in enumerate(kitti.read_detections_dlm(path), start=1):
+        if len(row) != 6:
+            raise ValueError(f"{path}: row {ln} has {len(row)} values, not [image_index x y w h score]")
+        k = int(row[0])
+        if k != row[0] or k < 1 or k > n_frames:
+            raise ValueError(f"{path}: row {ln}: image index {row[0]:g} outside 1 .. {n_frames}")
+        if k < prev:
+            raise ValueError(f"{path}: row {ln}: image index {k} after {prev}: rows must be grouped by image in ascending order")
+        prev = k
+        per_frame[k - 1].append(row[1:])
+    return [np.asarray(r, np.float64).reshape(-1, 5) for r in per_frame]
+
+
+def group_rois(per_frame):
+    """The frames of one forward -> forward_rois' "image" rows [R, 6] float64 with the 0-based index inside the group."""
+    return np.concatenate([np.concatenate([np.full((len(r), 1), float(i)), r], axis=1) for i, r in enumerate(per_frame)], axis=0)
 
 
 def main(argv=None):
@@ -133,8 +167,9 @@ def main(argv=None):
     per_class = {c: [] for c in cls_ids}
     per_image_props = []
     forward = net.forward_proposals if a.proposals_only else net.forward
+    rois = read_rois(a.rois_in, len(files)) if a.rois_in else None
     if a.batch > 1:
-        return run_batched(a, net, files, names, cls_ids, imgH, imgW, per_class, per_image_props, forward)
+        return run_batched(a, net, files, names, cls_ids, imgH, imgW, per_class, per_image_props, forward, rois)
     used = 0.0
     for k, path in enumerate(files, start=1):
         img = load_frame(path, k)
@@ -144,14 +179,23 @@ def main(argv=None):
         net.set_image("data", dev_img)                                       # :64-69 on the device
         torch.cuda.synchronize(a.device)
         t0 = time.perf_counter()
-        forward()
+        ran = True
+        if rois is None:
+            forward()
+        elif len(rois[k - 1]):
+            net.forward_rois(group_rois([rois[k - 1]]), "image", [dict(ratios=ratios)])
+        else:
+            ran = False                                                       # no box for this frame: nothing to run, no detections
         torch.cuda.synchronize(a.device)
         used += time.perf_counter() - t0                                      # :72-73: forward only
         if a.proposals_out:                                                   # :75-91
-            per_image_props.append(net.proposals_multi([dict(ratios=ratios, proposal_thr=a.proposal_thr)])[0][0][0])
+            per_image_props.append(net.proposals_multi([dict(ratios=ratios, proposal_thr=a.proposal_thr)])[0][0][0] if ran
+                                   else np.zeros((0, 5)))
         by_type = {}
         for c in () if a.proposals_only else cls_ids:
-            dets, _, _ = net.detect(cls_id=c, ratios=ratios, org_hw=(orgH, orgW), proposal_thr=a.proposal_thr, nms_overlap=a.nms_overlap)
+            dets = np.zeros((0, 5))
+            if ran:
+                dets, _, _ = net.detect(cls_id=c, ratios=ratios, org_hw=(orgH, orgW), proposal_thr=a.proposal_thr, nms_overlap=a.nms_overlap)
             per_class[c].append(dets)
             by_type[{"car": "Car", "ped": "Pedestrian", "cyc": "Cyclist"}.get(names[c - 1], names[c - 1])] = dets
         if a.labels_dir and not a.proposals_only:                             # writeDetForEval.m:88-89: the frame's own KITTI id
@@ -162,7 +206,7 @@ def main(argv=None):
     return 0
 
 
-def run_batched(a, net, files, names, cls_ids, imgH, imgW, per_class, per_image_props, forward):
+def run_batched(a, net, files, names, cls_ids, imgH, imgW, per_class, per_image_props, forward, rois=None):
     """--batch B: groups of B frames through set_images -> forward -> one detect_multi; results in frame order."""
     import torch
     from mscnn_amd import kitti
@@ -176,17 +220,28 @@ def run_batched(a, net, files, names, cls_ids, imgH, imgW, per_class, per_image_
         params = net.set_images("data", dev_imgs)                           # :63-69 for every frame of the group, on the device
         torch.cuda.synchronize(a.device)
         t0 = time.perf_counter()
-        forward()
+        ran = True
+        if rois is None:
+            forward()
+        elif sum(len(r) for r in rois[g0:g0 + len(group)]):
+            net.forward_rois(group_rois(rois[g0:g0 + len(group)]), "image", params)
+        else:
+            ran = False                                                       # no frame of the group has a box
         torch.cuda.synchronize(a.device)
         used += time.perf_counter() - t0                                      # :72-73: forward only
-        if a.proposals_out:                                                   # :75-91 for every frame of the group
+        if a.proposals_out and not ran:
+            per_image_props += [np.zeros((0, 5))] * len(group)
+        elif a.proposals_out:                                                 # :75-91 for every frame of the group
             per_image_props += [pr for pr, _ in net.proposals_multi([dict(p, proposal_thr=a.proposal_thr) for p in params])[0]]
         if a.proposals_only:
             k = g0 + len(group)
             if k % 100 < len(group) or k == len(files):
                 print(f"idx {k}/{len(files)}, avgtime={used / k:.4f}s")
             continue
-        per_image, _ = net.detect_multi([dict(p, proposal_thr=a.proposal_thr, nms_overlap=a.nms_overlap) for p in params], cls_ids)
+        if ran:
+            per_image, _ = net.detect_multi([dict(p, proposal_thr=a.proposal_thr, nms_overlap=a.nms_overlap) for p in params], cls_ids)
+        else:
+            per_image = [[(np.zeros((0, 5)), None)] * len(cls_ids)] * len(group)
         for i, path in enumerate(group):
             k = g0 + i + 1
             by_type = {}
