@@ -17,6 +17,10 @@
 
 namespace caffe {
 
+template <typename Dtype> class ConvolutionLayer;
+template <typename Dtype> class InnerProductLayer;
+template <typename Dtype> class ROIPoolingLayer;
+
 // Applied by Net::Init before layers are created (mirrors UpgradeNetInput + InsertSplits).
 void UpgradeNetInput(const NetParameter& in, vector<LayerParameter>* layers);
 void InsertSplits(const vector<LayerParameter>& in, vector<LayerParameter>* out);
@@ -73,10 +77,9 @@ class Net {
   // blob_by_name() copies the channel window back into the blob's own storage when the producer has run since the last
   // copy.  Code that reaches into blobs() directly must call this first.
   void MaterializeBlob(int blob_id) const;
-  // Deferred ROI pooling (ROIPoolingLayer::set_deferred): the pair's blob is written now if it is still pending.  Call before writing
-  // -- from outside the Net -- into a blob the pooling reads (the C ABI's blob setters do).
-  void MaterializePending() const;
-  // ... only where `blob_name` is (or shares its data, through Split layers, with) a blob the pending pooling reads
+  // Deferred ROI pooling (ROIPoolingLayer::set_deferred): the pair's blob is written now if it is still pending and `blob_name` is
+  // (or shares its data, through Split layers, with) a blob the pooling reads; likewise the unwritten blobs of convolution chains and
+  // ROIAlign heads that hang on it.  Call before writing -- from outside the Net -- into a blob (the C ABI's blob setters do).
   void MaterializePendingReadersOf(const string& blob_name) const;
   // Chains of same-resolution F(4x4,3x3) convolutions (ConvolutionLayer::ChainTo: conv2_1 -> conv2_2, conv3_1 -> 3_2 -> 3_3,
   // conv4_1 -> 4_2 -> 4_3): the blob between two members is not written while both run in one ForwardFromTo call; blob_by_name()
@@ -166,7 +169,38 @@ class Net {
 
  protected:
   void Init(const NetParameter& param);
+  // The graph index: built once by Init behind the wiring loop (BuildGraphIndex), never changed afterwards.  Every pass below that asks
+  // "who writes / reads this blob" looks it up here; the predicates on top of it (before which layer, with or without fused-away
+  // layers, a net output as a reader) differ from site to site and stay at the sites.
+  void BuildGraphIndex();
+  vector<vector<int> > blob_writers_;      // blob -> the layers that write it, ascending, in-place writers included
+  vector<vector<int> > blob_readers_;      // blob -> the layers that read it, ascending, one entry per bottom occurrence
+  vector<bool> blob_is_output_;            // blob -> it is a net output
+  vector<int> split_source_;               // blob -> through Split layers (their tops share the bottom's data) the blob that holds the data
+  template <typename L> struct Typed { int index; L* layer; };
+  vector<Typed<ConvolutionLayer<Dtype> > > conv_layers_;
+  vector<Typed<InnerProductLayer<Dtype> > > ip_layers_;
+  vector<Typed<ROIPoolingLayer<Dtype> > > roipool_layers_;
+  int LastWriter(int blob) const { return blob_writers_[blob].empty() ? -1 : blob_writers_[blob].back(); }
+  int LastWriterBefore(int blob, int layer) const;
+  // the readers of `blob` that still run (not fused away), `except` left out: their number, the last one in *reader (-1: none)
+  int RunningReaders(int blob, int except, int* reader) const;
+  int SplitSource(int blob) const { return split_source_[blob]; }
+  bool SameData(int blob_a, int blob_b) const { return split_source_[blob_a] == split_source_[blob_b]; }
+  // Net-level fusion: four passes in this order (each reads fused_away_ as the earlier ones left it)
   void ApplyFusion();
+  void FuseReLUs();
+  void FuseMaxPools();
+  void FuseRoiPoolConcats();
+  void PairRoiPools(int concat_layer);
+  void DeferRoiPoolPair(int first, int second, int concat_blob);
+  void PrebuildRoiMapsUnderBoxOutput(int pool_layer, int conv_layer);
+  void ChainConvolutions();
+  // the per-call marks of ForwardFromTo (ROIPooling skip, deferred poolings, max |x| hand-over, ROIAlign heads, convolution chains,
+  // the watch layer's keep_top): armed for a range at the head of a call, cleared at its end -- and at its head, for a call that
+  // follows one a CHECK failure cut short
+  void ArmCallMarks(int start, int end, int watch_layer);
+  void ClearCallMarks();
   // max |x| hand-over for split-fp16 convolutions (ConvolutionLayer::set_amax_io): one device slot per layer; a blob's bound
   // follows it through Split / in-place ReLU / Dropout / MAX pooling / ROIPooling / Concat of blobs with one common source.
   void WireAmax();
@@ -192,9 +226,9 @@ class Net {
   vector<float> layer_ms_;
   // fused layer i -> the layers that now produce its top(s) (ReLU / Pooling: one convolution; Concat: the ROIPooling layers)
   vector<vector<int> > fused_producers_;
-  struct Redirect { int target_blob, c_total, c_offset; };
+  // (dirty: the producer ran since the last MaterializeBlob)
+  struct Redirect { int target_blob, c_total, c_offset; mutable bool dirty; };
   std::map<int, Redirect> redirect_;               // blob id -> where its data really lives
-  mutable std::map<int, bool> redirect_dirty_;     // producer ran since the last MaterializeBlob
   struct DeferredPool { int first_layer, conv_layer, blob; };      // a ROIPooling pair whose only reader pools in its own input stage
   vector<DeferredPool> deferred_pools_;
   struct ChainPair { int producer, consumer, blob; };              // convolution -> its only reader, a same-resolution 3x3 convolution (-1: read by its fused pooling only)
@@ -204,10 +238,10 @@ class Net {
   // two pooled blobs; stale: the last forward of the head was the one-pass launch and those four blobs have not been written since
   struct AlignHead { int layer[5]; int blob[4]; int first, last; mutable bool stale; bool live; };
   vector<AlignHead> align_heads_;
+  vector<int> layer_head_, layer_head_role_;      // layer -> its head in align_heads_ and its place in AlignHead::layer, or -1
   bool roialign_one_pass_ = false;
   void FindRoiAlignHeads();
   void MaterializeAlignHead(const AlignHead& h) const;
-  int SplitSource(int blob) const;      // through Split layers (their tops share the bottom's data) to the blob that holds the data
   vector<double> calib_err_;
   int NextWatchLayer() const;
   void FallBackIfStrayed(int layer, double err, double tol, const char* where, vector<int>* switched);
@@ -226,7 +260,8 @@ class Net {
   long forward_count_ = 0;
   // the frame in flight is a ForwardRois: its two ranges (rois_trunk_: the first one ran) for HandoffRecover
   bool rois_frame_ = false, rois_trunk_ = false, in_rois_call_ = false;
-  int rois_K_ = -1, rois_L_ = -1;
+  void FindRoisLayers();
+  int rois_K_ = -1, rois_L_ = -1;      // L and K of ForwardRois: the graph's, found once by Init
   DISABLE_COPY_AND_ASSIGN(Net);
 };
 

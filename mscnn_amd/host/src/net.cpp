@@ -18,13 +18,10 @@
 #include "caffe/layer_factory.hpp"
 #include "caffe/layers/mscnn_layers.hpp"
 #include "caffe/net.hpp"
-#include <algorithm>
 
 namespace caffe {
 
-using std::make_pair;
 using std::map;
-using std::pair;
 using std::set;
 
 void UpgradeNetInput(const NetParameter& in, vector<LayerParameter>* layers) {
@@ -203,12 +200,14 @@ void Net<Dtype>::Init(const NetParameter& in_param) {
   }
   for (size_t i = 0; i < blob_names_.size(); ++i) blob_names_index_[blob_names_[i]] = (int)i;
   for (size_t i = 0; i < layer_names_.size(); ++i) layer_names_index_[layer_names_[i]] = (int)i;
+  BuildGraphIndex();
   fused_away_.assign(layers_.size(), false);
   fused_producers_.assign(layers_.size(), vector<int>());
   calib_err_.assign(layers_.size(), 0.0);
   layer_ms_.assign(layers_.size(), 0.f);
   if (fusion_) ApplyFusion();
   FindRoiAlignHeads();
+  FindRoisLayers();
   WireAmax();
   handoff_seen_ = mscnn_wgemm_handoff_event();      // (events of launches before this net existed are not its business)
   LOG(INFO) << "Network initialization done.";
@@ -217,6 +216,41 @@ void Net<Dtype>::Init(const NetParameter& in_param) {
 template <typename Dtype>
 Net<Dtype>::~Net() {
   if (amax_slots_) (void)hipFree(amax_slots_);
+}
+
+template <typename Dtype>
+void Net<Dtype>::BuildGraphIndex() {
+  blob_writers_.assign(blobs_.size(), vector<int>());
+  blob_readers_.assign(blobs_.size(), vector<int>());
+  blob_is_output_.assign(blobs_.size(), false);
+  split_source_.resize(blobs_.size());
+  for (size_t b = 0; b < blobs_.size(); ++b) split_source_[b] = (int)b;
+  for (size_t l = 0; l < layers_.size(); ++l) {
+    for (int b : bottom_id_vecs_[l]) blob_readers_[b].push_back((int)l);
+    for (int t : top_id_vecs_[l]) blob_writers_[t].push_back((int)l);
+    // a Split top's source is its bottom's source (layer order: the bottom's own source is final by now)
+    if (string(layers_[l]->type()) == "Split")
+      for (int t : top_id_vecs_[l]) split_source_[t] = split_source_[bottom_id_vecs_[l][0]];
+    if (ConvolutionLayer<Dtype>* c = dynamic_cast<ConvolutionLayer<Dtype>*>(layers_[l].get())) conv_layers_.push_back({(int)l, c});
+    if (InnerProductLayer<Dtype>* ip = dynamic_cast<InnerProductLayer<Dtype>*>(layers_[l].get())) ip_layers_.push_back({(int)l, ip});
+    if (string(layers_[l]->type()) == "ROIPooling") roipool_layers_.push_back({(int)l, static_cast<ROIPoolingLayer<Dtype>*>(layers_[l].get())});
+  }
+  for (int b : net_output_blob_indices_) blob_is_output_[b] = true;
+}
+
+template <typename Dtype>
+int Net<Dtype>::LastWriterBefore(int blob, int layer) const {
+  int l = -1;
+  for (int w : blob_writers_[blob]) if (w < layer) l = w;
+  return l;
+}
+
+template <typename Dtype>
+int Net<Dtype>::RunningReaders(int blob, int except, int* reader) const {
+  int n = 0;
+  *reader = -1;
+  for (int l : blob_readers_[blob]) if (l != except && !fused_away_[l]) { *reader = l; ++n; }
+  return n;
 }
 
 template <typename Dtype>
@@ -247,10 +281,19 @@ void Net<Dtype>::WireAmax() {
   }
 }
 
+template <typename Dtype>
+void Net<Dtype>::ApplyFusion() {
+  FuseReLUs();
+  FuseMaxPools();
+  FuseRoiPoolConcats();
+  if (const char* e = getenv("MSCNN_NO_CHAIN")) chain_fusion_ = !(e[0] && e[0] != '0');
+  ChainConvolutions();
+}
+
 // Conv / InnerProduct followed by an in-place ReLU on its top (every trunk conv of the deploy nets): the ReLU is
 // applied in the producer's epilogue and the ReLU layer becomes a no-op.  Bit-identical to the unfused pair.
 template <typename Dtype>
-void Net<Dtype>::ApplyFusion() {
+void Net<Dtype>::FuseReLUs() {
   for (size_t i = 0; i + 1 < layers_.size(); ++i) {
     const string t = layers_[i]->type();
     if (t != "Convolution" && t != "InnerProduct") continue;
@@ -260,34 +303,40 @@ void Net<Dtype>::ApplyFusion() {
     const Dtype slope = layers_[i + 1]->layer_param().relu_param().negative_slope();
     if (layers_[i]->FuseReLU(slope)) { fused_away_[i + 1] = true; fused_producers_[i + 1].push_back((int)i); }
   }
-  // Convolution (+ fused ReLU) -> [Split ->] Pooling(MAX 2x2 / 2): the convolution's epilogue also writes the pooled blob
-  // (pool1..pool6 of the VGG trunk); the Pooling layer becomes a no-op.  The convolution's own top is still written.
+}
+
+// Convolution (+ fused ReLU) -> [Split ->] Pooling(MAX 2x2 / 2): the convolution's epilogue also writes the pooled blob
+// (pool1..pool6 of the VGG trunk); the Pooling layer becomes a no-op.  The convolution's own top is still written.
+template <typename Dtype>
+void Net<Dtype>::FuseMaxPools() {
   for (size_t i = 0; i < layers_.size(); ++i) {
     if (string(layers_[i]->type()) != "Pooling" || !layers_[i]->IsMaxPool2x2()) continue;
     if (bottom_vecs_[i].size() != 1 || top_vecs_[i].size() != 1) continue;
-    Blob<Dtype>* src = bottom_vecs_[i][0];
+    int src = bottom_id_vecs_[i][0];
     int prod = -1;
     for (int hop = 0; hop < 2 && prod < 0; ++hop) {          // look through one Split
-      int l = -1;
-      for (size_t k = 0; k < i; ++k)
-        for (Blob<Dtype>* t : top_vecs_[k]) if (t == src) l = (int)k;      // last writer before the pooling layer
+      // the last writer BEFORE the pooling layer (not the last overall: an in-place layer behind the pooling re-issues the blob)
+      int l = LastWriterBefore(src, (int)i);
       if (l < 0) break;
       while (l > 0 && fused_away_[l]) --l;                                  // an in-place ReLU that was fused away
-      if (string(layers_[l]->type()) == "Split") { src = bottom_vecs_[l][0]; continue; }
-      if (string(layers_[l]->type()) == "Convolution" && top_vecs_[l].size() == 1 && top_vecs_[l][0] == src) prod = l;
+      if (string(layers_[l]->type()) == "Split") { src = bottom_id_vecs_[l][0]; continue; }
+      if (string(layers_[l]->type()) == "Convolution" && top_id_vecs_[l].size() == 1 && top_id_vecs_[l][0] == src) prod = l;
       break;
     }
     if (prod < 0) continue;
     // nothing between the convolution and the pooling layer may rewrite the blob (only its fused in-place ReLU does)
     bool clean = true;
-    for (size_t k = prod + 1; k < i && clean; ++k)
-      for (Blob<Dtype>* t : top_vecs_[k]) if (t == top_vecs_[prod][0] && !fused_away_[k]) clean = false;
+    for (int k : blob_writers_[top_id_vecs_[prod][0]]) if (k > prod && k < (int)i && !fused_away_[k]) clean = false;
     if (!clean) continue;
     if (layers_[prod]->FusePool2x2(top_vecs_[i][0])) { fused_away_[i] = true; fused_producers_[i].push_back(prod); }
   }
-  // Channel Concat whose bottoms all come straight from ROIPooling layers (roi_pool_org + roi_pool_ctx -> roi_pool): the
-  // producers write their channel window of the concatenated blob and the copy layer disappears (concat_layer.cu:28-46
-  // moves R x 1024 x 49 floats per image otherwise).  The individual ROIPooling tops are then not materialised.
+}
+
+// Channel Concat whose bottoms all come straight from ROIPooling layers (roi_pool_org + roi_pool_ctx -> roi_pool): the
+// producers write their channel window of the concatenated blob and the copy layer disappears (concat_layer.cu:28-46
+// moves R x 1024 x 49 floats per image otherwise).  The individual ROIPooling tops are then not materialised.
+template <typename Dtype>
+void Net<Dtype>::FuseRoiPoolConcats() {
   for (size_t i = 0; i < layers_.size(); ++i) {
     if (string(layers_[i]->type()) != "Concat" || bottom_vecs_[i].size() < 2 || top_vecs_[i].size() != 1) continue;
     const ConcatParameter cp = layers_[i]->layer_param().concat_param();
@@ -296,11 +345,9 @@ void Net<Dtype>::ApplyFusion() {
     int c_total = 0;
     bool ok = true;
     for (size_t b = 0; b < bottom_vecs_[i].size() && ok; ++b) {
-      int prod = -1, consumers = 0;
-      for (size_t l = 0; l < layers_.size(); ++l) {
-        for (Blob<Dtype>* t : top_vecs_[l]) if (t == bottom_vecs_[i][b]) prod = (int)l;
-        for (Blob<Dtype>* bb : bottom_vecs_[l]) if (bb == bottom_vecs_[i][b]) ++consumers;
-      }
+      // the last writer OVERALL, and every reader counts, fused-away ones included: the window is the producer's only output, so
+      // nobody else may write or want the blob, wherever in the net
+      const int blob = bottom_id_vecs_[i][b], prod = LastWriter(blob), consumers = (int)blob_readers_[blob].size();
       ok = prod >= 0 && consumers == 1 && string(layers_[prod]->type()) == "ROIPooling" && top_vecs_[prod].size() == 1;
       producers.push_back(prod);
       if (ok) c_total += bottom_vecs_[i][b]->channels();
@@ -310,107 +357,102 @@ void Net<Dtype>::ApplyFusion() {
     for (size_t b = 0; b < producers.size(); ++b) {
       CHECK(layers_[producers[b]]->SetOutputWindow(top_vecs_[i][0], c_total, off));
       Redirect rd;
-      rd.target_blob = top_id_vecs_[i][0]; rd.c_total = c_total; rd.c_offset = off;
+      rd.target_blob = top_id_vecs_[i][0]; rd.c_total = c_total; rd.c_offset = off; rd.dirty = false;
       redirect_[bottom_id_vecs_[i][b]] = rd;
-      redirect_dirty_[bottom_id_vecs_[i][b]] = false;
       off += bottom_vecs_[i][b]->channels();
     }
     fused_away_[i] = true;
     fused_producers_[i] = producers;
-    // two poolings of the same map and ROIs: one launch (ROIPoolingLayer::PairWith)
-    auto source = [&](int blob) {      // through Split layers (their tops share the bottom's data) to the blob that holds the data
-      for (bool moved = true; moved;) {
-        moved = false;
-        for (size_t l = 0; l < layers_.size() && !moved; ++l)
-          if (string(layers_[l]->type()) == "Split")
-            for (int t : top_id_vecs_[l])
-              if (t == blob) { blob = bottom_id_vecs_[l][0]; moved = true; break; }
-      }
-      return blob;
-    };
-    if (producers.size() == 2 && bottom_id_vecs_[producers[0]].size() == 2 && bottom_id_vecs_[producers[1]].size() == 2 &&
-        source(bottom_id_vecs_[producers[0]][0]) == source(bottom_id_vecs_[producers[1]][0]) &&
-        source(bottom_id_vecs_[producers[0]][1]) == source(bottom_id_vecs_[producers[1]][1])) {
-      const int first = std::min(producers[0], producers[1]), second = std::max(producers[0], producers[1]);
-      ROIPoolingLayer<Dtype>* fl = static_cast<ROIPoolingLayer<Dtype>*>(layers_[first].get());
-      if (fl->PairWith(static_cast<ROIPoolingLayer<Dtype>*>(layers_[second].get()))) {
-        // the concatenated blob has ONE reader and it is a Convolution (roi_pool -> roi_c1): the pooling is deferred to that layer's
-        // input stage (ConvolutionLayer::FuseRoiPoolInput); the blob itself is written on demand (MaterializeBlob)
-        const int tb = top_id_vecs_[i][0];
-        int reader = -1, readers = 0;
-        for (size_t l = 0; l < layers_.size(); ++l)
-          for (int bb : bottom_id_vecs_[l]) if (bb == tb && !fused_away_[l]) { reader = (int)l; ++readers; }
-        bool is_output = false;
-        for (int ob : net_output_blob_indices_) is_output = is_output || ob == tb;
-        ConvolutionLayer<Dtype>* conv = readers == 1 ? dynamic_cast<ConvolutionLayer<Dtype>*>(layers_[reader].get()) : nullptr;
-        if (conv && !is_output && reader > second) {
-          fl->set_deferred(true);
-          conv->FuseRoiPoolInput(fl);
-          DeferredPool dp;
-          dp.first_layer = first; dp.conv_layer = reader; dp.blob = tb;
-          deferred_pools_.push_back(dp);
-          // The pooling's maps depend on the feature blob only.  When that blob is complete before the BoxOutput layer that selects
-          // the ROIs runs (conv4_3 of the plain nets; not the "-2x" nets' Deconvolution, which follows BoxOutput), they are built
-          // UNDER BoxOutput's host round trip: enqueued behind BoxOutput's kernels and in front of the host's wait, they keep the device busy while the host
-          // takes R, reshapes and launches the sub-net (29 us of idle device per 7s-576 frame otherwise: profiles/r06_kernel_gaps.txt).
-          const int feat_blob = source(bottom_id_vecs_[first][0]), rois_blob = source(bottom_id_vecs_[first][1]);
-          int feat_layer = -1, rois_layer = -1;
-          for (size_t l = 0; l < layers_.size(); ++l)
-            for (int t : top_id_vecs_[l]) {
-              if (t == feat_blob) feat_layer = (int)l;      // (the LAST writer: in-place layers re-issue the blob)
-              if (t == rois_blob) rois_layer = (int)l;
-            }
-          if (feat_layer >= 0 && rois_layer > feat_layer && string(layers_[rois_layer]->type()) == "BoxOutput") {
-            const int conv_layer = reader, pool_layer = first;
-            static_cast<BoxOutputLayer<Dtype>*>(layers_[rois_layer].get())->set_before_sync([this, conv_layer, pool_layer]() {
-              if (!fusion_ || last_end_ < conv_layer) return;      // (the sub-net is not part of this call)
-              static_cast<ConvolutionLayer<Dtype>*>(layers_[conv_layer].get())->PrebuildRoiMaps(bottom_vecs_[pool_layer][0]);
-            });
-          }
-        }
-      }
-    }
+    PairRoiPools((int)i);
   }
-  // Chains of convolutions (ConvolutionLayer::ChainTo): the top of convolution i is read by exactly one layer that still runs -- a
-  // 3x3 convolution j > i with nothing running in between (the in-place ReLU is fused away) -- and is not a net output.
-  if (const char* e = getenv("MSCNN_NO_CHAIN")) chain_fusion_ = !(e[0] && e[0] != '0');
-  for (size_t i = 0; i < layers_.size(); ++i) {
-    ConvolutionLayer<Dtype>* ci = fused_away_[i] ? nullptr : dynamic_cast<ConvolutionLayer<Dtype>*>(layers_[i].get());
-    if (!ci || top_id_vecs_[i].size() != 1) continue;
+}
+
+// two poolings of the same map and ROIs behind one fused Concat: one launch (ROIPoolingLayer::PairWith)
+template <typename Dtype>
+void Net<Dtype>::PairRoiPools(int concat_layer) {
+  const vector<int>& producers = fused_producers_[concat_layer];
+  if (producers.size() != 2) return;
+  const vector<int>& b0 = bottom_id_vecs_[producers[0]];
+  const vector<int>& b1 = bottom_id_vecs_[producers[1]];
+  if (b0.size() != 2 || b1.size() != 2 || !SameData(b0[0], b1[0]) || !SameData(b0[1], b1[1])) return;
+  const int first = std::min(producers[0], producers[1]), second = std::max(producers[0], producers[1]);
+  ROIPoolingLayer<Dtype>* fl = static_cast<ROIPoolingLayer<Dtype>*>(layers_[first].get());
+  if (fl->PairWith(static_cast<ROIPoolingLayer<Dtype>*>(layers_[second].get()))) DeferRoiPoolPair(first, second, top_id_vecs_[concat_layer][0]);
+}
+
+// the concatenated blob of a pair has ONE reader and it is a Convolution (roi_pool -> roi_c1): the pooling is deferred to that layer's
+// input stage (ConvolutionLayer::FuseRoiPoolInput); the blob itself is written on demand (MaterializeBlob)
+template <typename Dtype>
+void Net<Dtype>::DeferRoiPoolPair(int first, int second, int concat_blob) {
+  // only readers that still run count (the Concat itself has just been fused away, as may have other readers before it)
+  int reader = -1;
+  const int readers = RunningReaders(concat_blob, -1, &reader);
+  ConvolutionLayer<Dtype>* conv = readers == 1 ? dynamic_cast<ConvolutionLayer<Dtype>*>(layers_[reader].get()) : nullptr;
+  if (!conv || blob_is_output_[concat_blob] || reader <= second) return;
+  ROIPoolingLayer<Dtype>* fl = static_cast<ROIPoolingLayer<Dtype>*>(layers_[first].get());
+  fl->set_deferred(true);
+  conv->FuseRoiPoolInput(fl);
+  DeferredPool dp;
+  dp.first_layer = first; dp.conv_layer = reader; dp.blob = concat_blob;
+  deferred_pools_.push_back(dp);
+  PrebuildRoiMapsUnderBoxOutput(first, reader);
+}
+
+// The pooling's maps depend on the feature blob only.  When that blob is complete before the BoxOutput layer that selects
+// the ROIs runs (conv4_3 of the plain nets; not the "-2x" nets' Deconvolution, which follows BoxOutput), they are built
+// UNDER BoxOutput's host round trip: enqueued behind BoxOutput's kernels and in front of the host's wait, they keep the device busy while the host
+// takes R, reshapes and launches the sub-net (29 us of idle device per 7s-576 frame otherwise: profiles/r06_kernel_gaps.txt).
+template <typename Dtype>
+void Net<Dtype>::PrebuildRoiMapsUnderBoxOutput(int pool_layer, int conv_layer) {
+  // (the LAST writer overall: in-place layers re-issue the blob)
+  const int feat_layer = LastWriter(SplitSource(bottom_id_vecs_[pool_layer][0]));
+  const int rois_layer = LastWriter(SplitSource(bottom_id_vecs_[pool_layer][1]));
+  if (feat_layer < 0 || rois_layer <= feat_layer || string(layers_[rois_layer]->type()) != "BoxOutput") return;
+  static_cast<BoxOutputLayer<Dtype>*>(layers_[rois_layer].get())->set_before_sync([this, conv_layer, pool_layer]() {
+    if (!fusion_ || last_end_ < conv_layer) return;      // (the sub-net is not part of this call)
+    static_cast<ConvolutionLayer<Dtype>*>(layers_[conv_layer].get())->PrebuildRoiMaps(bottom_vecs_[pool_layer][0]);
+  });
+}
+
+// Chains of convolutions (ConvolutionLayer::ChainTo): the top of convolution i is read by exactly one layer that still runs -- a
+// 3x3 convolution j > i with nothing running in between (the in-place ReLU is fused away) -- and is not a net output.
+template <typename Dtype>
+void Net<Dtype>::ChainConvolutions() {
+  for (size_t q = 0; q < conv_layers_.size(); ++q) {
+    const int i = conv_layers_[q].index;
+    ConvolutionLayer<Dtype>* ci = conv_layers_[q].layer;
+    if (fused_away_[i] || top_id_vecs_[i].size() != 1) continue;
     const int tb = top_id_vecs_[i][0];
-    int reader = -1, readers = 0;
+    // readers that still run, this layer itself left out; the fused-away ones must all be ReLU (a fused-away pooling or Concat takes
+    // the blob from this layer's epilogue in a way the chain does not provide)
+    int reader = -1;
+    const int readers = RunningReaders(tb, i, &reader);
     bool only_relu = true;
-    for (size_t l = 0; l < layers_.size(); ++l) {
-      if (l == i) continue;
-      for (int bb : bottom_id_vecs_[l]) {
-        if (bb != tb) continue;
-        if (fused_away_[l]) only_relu = only_relu && string(layers_[l]->type()) == "ReLU";
-        else { reader = (int)l; ++readers; }
-      }
-    }
-    bool is_output = false;
-    for (int ob : net_output_blob_indices_) is_output = is_output || ob == tb;
+    for (int l : blob_readers_[tb])
+      if (l != i && fused_away_[l]) only_relu = only_relu && string(layers_[l]->type()) == "ReLU";
+    const bool is_output = blob_is_output_[tb];
     if (readers == 0 && !is_output && !redirect_.count(tb)) {
       // read by fused-away layers only (its ReLU, the 2x2 pooling in this convolution's epilogue): the top need not be written
+      // (no reader runs, so no Split stands between: a pooling fused into this layer is among the blob's own readers)
       bool pooled_here = false;
-      for (size_t l = 0; l < layers_.size(); ++l)
+      for (int l : blob_readers_[tb])
         if (fused_away_[l] && string(layers_[l]->type()) == "Pooling")
-          for (int p : fused_producers_[l]) pooled_here = pooled_here || p == (int)i;
+          for (int p : fused_producers_[l]) pooled_here = pooled_here || p == i;
       if (pooled_here) {
         ChainPair cp;
-        cp.producer = (int)i; cp.consumer = -1; cp.blob = tb;
+        cp.producer = i; cp.consumer = -1; cp.blob = tb;
         chain_pairs_.push_back(cp);
       }
       continue;
     }
-    if (readers != 1 || !only_relu || is_output || reader <= (int)i || redirect_.count(tb)) continue;
+    if (readers != 1 || !only_relu || is_output || reader <= i || redirect_.count(tb)) continue;
     ConvolutionLayer<Dtype>* cj = dynamic_cast<ConvolutionLayer<Dtype>*>(layers_[reader].get());
     bool adjacent = cj != nullptr;
-    for (int l = (int)i + 1; l < reader && adjacent; ++l) adjacent = fused_away_[l];
+    for (int l = i + 1; l < reader && adjacent; ++l) adjacent = fused_away_[l];
     if (!adjacent) continue;
     ci->ChainTo(cj);
     ChainPair cp;
-    cp.producer = (int)i; cp.consumer = reader; cp.blob = tb;
+    cp.producer = i; cp.consumer = reader; cp.blob = tb;
     chain_pairs_.push_back(cp);
   }
 }
@@ -419,20 +461,15 @@ void Net<Dtype>::ApplyFusion() {
 // switch decides per ForwardFromTo.
 template <typename Dtype>
 void Net<Dtype>::FindRoiAlignHeads() {
-  // the one layer that reads `blob`, or -1 when there is none or more than one (a net output counts as a reader)
+  // the one layer that reads `blob`, or -1 when there is none or more than one (a net output counts as a reader: a blob somebody
+  // outside the net reads has to be written)
   auto only_reader = [&](int blob) {
-    int reader = -1, readers = 0;
-    for (size_t l = 0; l < layers_.size(); ++l)
-      for (int bb : bottom_id_vecs_[l]) if (bb == blob) { reader = (int)l; ++readers; }
-    for (int ob : net_output_blob_indices_) if (ob == blob) ++readers;
-    return readers == 1 ? reader : -1;
+    const vector<int>& r = blob_readers_[blob];
+    return r.size() + (blob_is_output_[blob] ? 1 : 0) == 1 && !r.empty() ? r.back() : -1;
   };
-  auto writers = [&](int blob) {
-    int n = 0;
-    for (size_t l = 0; l < layers_.size(); ++l)
-      for (int t : top_id_vecs_[l]) if (t == blob) ++n;
-    return n;
-  };
+  auto writers = [&](int blob) { return (int)blob_writers_[blob].size(); };
+  layer_head_.assign(layers_.size(), -1);
+  layer_head_role_.assign(layers_.size(), -1);
   vector<bool> taken(layers_.size(), false);
   for (size_t i = 0; i < layers_.size(); ++i) {
     ROIAlignLayer<Dtype>* a = taken[i] ? nullptr : dynamic_cast<ROIAlignLayer<Dtype>*>(layers_[i].get());
@@ -440,8 +477,7 @@ void Net<Dtype>::FindRoiAlignHeads() {
     for (size_t j = i + 1; j < layers_.size(); ++j) {
       ROIAlignLayer<Dtype>* b = taken[j] ? nullptr : dynamic_cast<ROIAlignLayer<Dtype>*>(layers_[j].get());
       if (!b || bottom_id_vecs_[j].size() != 2 || fused_away_[j]) continue;
-      if (SplitSource(bottom_id_vecs_[i][0]) != SplitSource(bottom_id_vecs_[j][0]) ||
-          SplitSource(bottom_id_vecs_[i][1]) != SplitSource(bottom_id_vecs_[j][1])) continue;
+      if (!SameData(bottom_id_vecs_[i][0], bottom_id_vecs_[j][0]) || !SameData(bottom_id_vecs_[i][1], bottom_id_vecs_[j][1])) continue;
       if (a->pooled_height() != b->pooled_height() || a->pooled_width() != b->pooled_width() || a->spatial_scale() != b->spatial_scale())
         continue;
       const int ga = top_id_vecs_[i][0], gb = top_id_vecs_[j][0];
@@ -468,6 +504,8 @@ void Net<Dtype>::FindRoiAlignHeads() {
       h.blob[0] = ga; h.blob[1] = gb; h.blob[2] = ta; h.blob[3] = tb;
       h.first = (int)i; h.last = cc;
       h.stale = false; h.live = false;
+      // (a Pooling layer has one bottom and the Concat two: no layer can be part of a second head)
+      for (int q = 0; q < 5; ++q) { layer_head_[h.layer[q]] = (int)align_heads_.size(); layer_head_role_[h.layer[q]] = q; }
       align_heads_.push_back(h);
       taken[i] = taken[j] = true;
       break;
@@ -489,31 +527,20 @@ void Net<Dtype>::MaterializeAlignHead(const AlignHead& h) const {
 }
 
 template <typename Dtype>
-int Net<Dtype>::SplitSource(int blob) const {
-  for (bool moved = true; moved;) {
-    moved = false;
-    for (size_t l = 0; l < layers_.size() && !moved; ++l)
-      if (string(layers_[l]->type()) == "Split")
-        for (int t : top_id_vecs_[l])
-          if (t == blob) { blob = bottom_id_vecs_[l][0]; moved = true; break; }
-  }
-  return blob;
-}
-
-template <typename Dtype>
 void Net<Dtype>::MaterializePendingReadersOf(const string& blob_name) const {
-  if (!has_blob(blob_name)) return;
+  const map<string, int>::const_iterator it = blob_names_index_.find(blob_name);
+  if (it == blob_names_index_.end()) return;
+  const int blob = it->second;
   {
     // blobs inside convolution chains that the last Forward did not write and whose value hangs on this blob: written now, from the
     // bottoms their layers were given (the reference's blobs hold exactly that)
-    std::vector<int> affected(1, blob_names_index_.find(blob_name)->second);
+    std::vector<int> affected(1, blob);
     for (size_t a = 0; a < affected.size(); ++a)
       for (size_t k = 0; k < chain_pairs_.size(); ++k) {
         const int i = chain_pairs_[k].producer;
         if (!static_cast<ConvolutionLayer<Dtype>*>(layers_[i].get())->top_stale()) continue;
         for (int bb : bottom_id_vecs_[i])
-          if ((bb == affected[a] || SplitSource(bb) == SplitSource(affected[a])) &&
-              std::find(affected.begin(), affected.end(), chain_pairs_[k].blob) == affected.end())
+          if (SameData(bb, affected[a]) && std::find(affected.begin(), affected.end(), chain_pairs_[k].blob) == affected.end())
             affected.push_back(chain_pairs_[k].blob);
       }
     for (size_t a = 1; a < affected.size(); ++a) MaterializeBlob(affected[a]);
@@ -522,13 +549,11 @@ void Net<Dtype>::MaterializePendingReadersOf(const string& blob_name) const {
   for (size_t k = 0; k < align_heads_.size(); ++k)
     if (align_heads_[k].stale)
       for (int bb : bottom_id_vecs_[align_heads_[k].first])
-        if (SplitSource(bb) == SplitSource(blob_names_index_.find(blob_name)->second)) MaterializeAlignHead(align_heads_[k]);
-  if (deferred_pools_.empty()) return;
-  const int src = SplitSource(blob_names_index_.find(blob_name)->second);
+        if (SameData(bb, blob)) MaterializeAlignHead(align_heads_[k]);
   for (size_t k = 0; k < deferred_pools_.size(); ++k) {
     const int fl = deferred_pools_[k].first_layer;
     for (int bb : bottom_id_vecs_[fl])
-      if (SplitSource(bb) == src) static_cast<ROIPoolingLayer<Dtype>*>(layers_[fl].get())->Materialize();
+      if (SameData(bb, blob)) static_cast<ROIPoolingLayer<Dtype>*>(layers_[fl].get())->Materialize();
   }
 }
 
@@ -536,12 +561,6 @@ template <typename Dtype>
 void Net<Dtype>::MaterializeStale() const {
   for (size_t k = 0; k < chain_pairs_.size(); ++k) MaterializeBlob(chain_pairs_[k].blob);
   for (size_t k = 0; k < align_heads_.size(); ++k) MaterializeAlignHead(align_heads_[k]);
-}
-
-template <typename Dtype>
-void Net<Dtype>::MaterializePending() const {
-  for (size_t k = 0; k < deferred_pools_.size(); ++k)
-    static_cast<ROIPoolingLayer<Dtype>*>(layers_[deferred_pools_[k].first_layer].get())->Materialize();
 }
 
 template <typename Dtype>
@@ -567,7 +586,7 @@ void Net<Dtype>::MaterializeBlob(int blob_id) const {
   for (size_t k = 0; k < deferred_pools_.size(); ++k)
     if (deferred_pools_[k].blob == blob_id || (it != redirect_.end() && it->second.target_blob == deferred_pools_[k].blob))
       static_cast<ROIPoolingLayer<Dtype>*>(layers_[deferred_pools_[k].first_layer].get())->Materialize();
-  if (it == redirect_.end() || !redirect_dirty_[blob_id]) return;
+  if (it == redirect_.end() || !it->second.dirty) return;
   const Redirect& rd = it->second;
   const Blob<Dtype>* src = blobs_[rd.target_blob].get();
   Blob<Dtype>* dst = blobs_[blob_id].get();
@@ -577,20 +596,20 @@ void Net<Dtype>::MaterializeBlob(int blob_id) const {
     HIP_CHECK(hipMemcpy2DAsync(dst->mutable_gpu_data(), sizeof(Dtype) * c * inner, src->gpu_data() + (size_t)rd.c_offset * inner,
                                sizeof(Dtype) * rd.c_total * inner, sizeof(Dtype) * c * inner, R, hipMemcpyDeviceToDevice,
                                (hipStream_t)Caffe::stream()));
-  redirect_dirty_[blob_id] = false;
+  rd.dirty = false;
 }
 
 template <typename Dtype>
 vector<int> Net<Dtype>::CalibrateNumerics(double tol) {
   vector<int> switched;
-  for (size_t i = 0; i < layers_.size(); ++i) {
-    calib_err_[i] = 0.0;
-    ConvolutionLayer<Dtype>* c = dynamic_cast<ConvolutionLayer<Dtype>*>(layers_[i].get());
-    if (!c) continue;
+  std::fill(calib_err_.begin(), calib_err_.end(), 0.0);
+  for (size_t q = 0; q < conv_layers_.size(); ++q) {
+    const int i = conv_layers_[q].index;
+    ConvolutionLayer<Dtype>* c = conv_layers_[q].layer;
     for (int bb : bottom_id_vecs_[i]) MaterializeBlob(bb);      // (blobs inside a convolution chain are written on demand)
     for (int tb : top_id_vecs_[i]) MaterializeBlob(tb);
     calib_err_[i] = c->ErrorAgainstDirect(bottom_vecs_[i], top_vecs_[i]);      // (0: no Winograd form to check)
-    FallBackIfStrayed((int)i, calib_err_[i], tol, "on the calibration input", &switched);
+    FallBackIfStrayed(i, calib_err_[i], tol, "on the calibration input", &switched);
   }
   return switched;
 }
@@ -610,8 +629,7 @@ void Net<Dtype>::FallBackIfStrayed(int i, double err, double tol, const char* wh
 template <typename Dtype>
 void Net<Dtype>::SetAutoCalibrate(double tol) {
   CHECK_GE(tol, 0.0);
-  for (size_t i = 0; i < layers_.size(); ++i)
-    if (ConvolutionLayer<Dtype>* c = dynamic_cast<ConvolutionLayer<Dtype>*>(layers_[i].get())) c->set_selfcheck(tol);
+  for (size_t q = 0; q < conv_layers_.size(); ++q) conv_layers_[q].layer->set_selfcheck(tol);
   auto_tol_ = tol;
   // both checks off: give the checks' device scratch back (a direct plan's workspace + a copy of the largest checked top)
   if (tol == 0.0 && watch_period_ == 0) ConvolutionLayer<Dtype>::ReleaseCheckScratch();
@@ -633,12 +651,10 @@ void Net<Dtype>::SetNumericsWatch(int period, double tol) {
 // it runs the direct kernel from the frame after that.
 template <typename Dtype>
 int Net<Dtype>::NextWatchLayer() const {
-  const int L = (int)layers_.size();
-  for (int k = 0; k < L; ++k) {
-    const int i = (watch_next_ + k) % L;
-    ConvolutionLayer<Dtype>* c = dynamic_cast<ConvolutionLayer<Dtype>*>(layers_[i].get());
-    if (c && c->WinogradCheckApplies()) return i;
-  }
+  // round robin from watch_next_: the convolutions at or behind it first, then those in front of it
+  for (int pass = 0; pass < 2; ++pass)
+    for (size_t q = 0; q < conv_layers_.size(); ++q)
+      if ((conv_layers_[q].index >= watch_next_) == (pass == 0) && conv_layers_[q].layer->WinogradCheckApplies()) return conv_layers_[q].index;
   return -1;
 }
 
@@ -667,6 +683,16 @@ bool Net<Dtype>::HandoffEventPending() {
   return true;
 }
 
+namespace {
+// sets a flag for a scope: a CHECK failure thrown through the scope leaves the flag as it was found
+struct FlagScope {
+  bool& flag;
+  const bool before;
+  explicit FlagScope(bool& f) : flag(f), before(f) { flag = true; }
+  ~FlagScope() { flag = before; }
+};
+}  // namespace
+
 // Called where the caller has just synchronised the stream.  No event: everything this net launched so far is known good (the ranges run
 // since are forgotten).  An event: EVERY range run since the last known-good point is suspect -- a caller that forwards 0 .. k and then
 // k + 1 .. end and only then synchronises may have the poisoned tile in the first range -- so the re-run goes from the smallest start
@@ -679,10 +705,9 @@ bool Net<Dtype>::HandoffRecover() {
   if (rois_frame_) {
     // the frame in flight ran 0 .. K and L + 1 .. last around caller-supplied ROIs: one range from the smallest start would run
     // BoxOutput and replace them with its own.  The ingested rows are still in L's tops: the same two ranges again
-    in_rois_call_ = true;
+    FlagScope in_call(in_rois_call_);
     if (rois_trunk_ && from <= rois_K_) ForwardFromTo(0, rois_K_);
     ForwardFromTo(rois_L_ + 1, (int)layers_.size() - 1);
-    in_rois_call_ = false;
     return true;
   }
   if (to >= from) ForwardFromTo(from, to);
@@ -691,7 +716,12 @@ bool Net<Dtype>::HandoffRecover() {
 
 template <typename Dtype>
 void Net<Dtype>::RoisLayers(int* L_out, int* K_out) const {
-  *L_out = *K_out = -1;
+  *L_out = rois_L_; *K_out = rois_K_;
+}
+
+template <typename Dtype>
+void Net<Dtype>::FindRoisLayers() {
+  rois_L_ = rois_K_ = -1;
   const int n = (int)layers_.size();
   // the ROI blobs the ROI layers read, through Split layers
   std::set<int> roi_blobs;
@@ -711,27 +741,24 @@ void Net<Dtype>::RoisLayers(int* L_out, int* K_out) const {
   for (int l = 0; l < n && L < 0; ++l)
     if (string(layers_[l]->type()) == "BoxOutput" && top_id_vecs_[l].size() == 1 && roi_blobs.count(top_id_vecs_[l][0])) L = l;
   if (L < 0) return;
-  // K: walking back from every layer behind L, never through L's tops
-  std::set<int> needed;
-  for (int l = L + 1; l < n; ++l)
-    for (int bb : bottom_id_vecs_[l]) needed.insert(bb);
-  for (int t : top_id_vecs_[L]) needed.erase(t);
+  // K: walking back from L, never through L's tops.  A layer in front of L is needed when a later layer other than L reads one of its
+  // tops and is itself behind L or needed
+  vector<bool> needed(n, false);
   int K = -1;
   for (int l = L - 1; l >= 0; --l) {
-    bool feeds = false;
-    for (int t : top_id_vecs_[l]) feeds = feeds || needed.count(t) > 0;
-    if (!feeds) continue;
-    if (K < 0) K = l;
-    for (int bb : bottom_id_vecs_[l]) needed.insert(bb);
+    for (int t : top_id_vecs_[l]) {
+      if (std::find(top_id_vecs_[L].begin(), top_id_vecs_[L].end(), t) != top_id_vecs_[L].end()) continue;
+      for (int r : blob_readers_[t]) needed[l] = needed[l] || (r > l && r != L && (r > L || needed[r]));
+    }
+    if (needed[l] && K < 0) K = l;
   }
-  *L_out = L; *K_out = K;
+  rois_L_ = L; rois_K_ = K;
 }
 
 template <typename Dtype>
 void Net<Dtype>::ForwardRois(const void* rows, bool on_device, int coords, int R, const double* ratio_h, const double* ratio_w,
                              int num_images, bool run_trunk, int* image_rois) {
-  int L = -1, K = -1;
-  RoisLayers(&L, &K);
+  const int L = rois_L_, K = rois_K_;
   CHECK_GE(L, 0) << "forward_rois: net has no ROIPooling / ROIAlign layer fed by a BoxOutput layer: nothing to run on caller-supplied ROIs";
   CHECK(rows != nullptr) << "forward_rois: null rows";
   CHECK(coords == MSCNN_ROIS_NET || coords == MSCNN_ROIS_IMAGE) << "forward_rois: coords = " << coords << " (0 net-input, 1 original-image)";
@@ -748,9 +775,9 @@ void Net<Dtype>::ForwardRois(const void* rows, bool on_device, int coords, int R
   MaterializePendingReadersOf(blob_names_[top_id_vecs_[L][0]]);
   bo->IngestBegin(bottom_vecs_[L], top_vecs_[L], rows, on_device, coords, R, ratio_h, ratio_w, num_images);
   const int last = (int)layers_.size() - 1;
-  in_rois_call_ = true;
   rois_frame_ = false;
-  try {
+  {
+    FlagScope in_call(in_rois_call_);
     if (run_trunk && K >= 0) ForwardFromTo(0, K);
     // (by now the ingest is long done: the wait is for its event, not for the trunk)
     int bad_row = -1, reason = 0;
@@ -760,12 +787,100 @@ void Net<Dtype>::ForwardRois(const void* rows, bool on_device, int coords, int R
     // (the ROI pooling's maps: BoxOutput's before-sync hook has not run, roi_c1 builds them itself -- ConvolutionLayer::InvalidateRoiMaps
     // at the head of every ForwardFromTo)
     ForwardFromTo(L + 1, last);
-  } catch (...) {
-    in_rois_call_ = false;
-    throw;
   }
-  in_rois_call_ = false;
-  rois_frame_ = true; rois_trunk_ = run_trunk && K >= 0; rois_K_ = K; rois_L_ = L;
+  // (only a call that got here leaves a ForwardRois frame behind)
+  rois_frame_ = true; rois_trunk_ = run_trunk && K >= 0;
+}
+
+template <typename Dtype>
+void Net<Dtype>::ClearCallMarks() {
+  // a paired ROIPooling's skip mark must not outlive the call in which its partner ran (a range that ends between the two, then a
+  // direct Layer::Forward on the second: it has to pool, not skip)
+  for (size_t q = 0; q < roipool_layers_.size(); ++q) roipool_layers_[q].layer->set_skip(false);
+  // every chain member passes through set_chain_live(false) between two calls: that also drops the "planes prepared" mark a call cut
+  // short between two members would leave on the second
+  for (size_t k = 0; k < chain_pairs_.size(); ++k) {
+    ConvolutionLayer<Dtype>* p = static_cast<ConvolutionLayer<Dtype>*>(layers_[chain_pairs_[k].producer].get());
+    p->set_chain_live(false);
+    p->set_pool_only_live(false);
+    p->set_keep_top(false);
+    if (chain_pairs_[k].consumer >= 0) static_cast<ConvolutionLayer<Dtype>*>(layers_[chain_pairs_[k].consumer].get())->set_chain_live(false);
+  }
+  // The max |x| slots a split-fp16 layer takes from its producer are only valid inside this call: a later Layer::Forward called
+  // directly on a layer (caffe time, user code, the boundary tests) must measure its bottom itself instead of trusting the slots of
+  // the frame that went through here.
+  for (size_t q = 0; q < conv_layers_.size(); ++q) conv_layers_[q].layer->set_amax_trusted(false);
+  for (size_t q = 0; q < ip_layers_.size(); ++q) ip_layers_[q].layer->set_amax_trusted(false);
+}
+
+// (everything here that enqueues device work does so in this order: deferred poolings, the slots' memset, ROIAlign heads, chain blobs)
+template <typename Dtype>
+void Net<Dtype>::ArmCallMarks(int start, int end, int watch_layer) {
+  ClearCallMarks();      // (a paired ROIPooling skips only inside the call in which its partner ran)
+  // a deferred ROI pooling still pending from an earlier call reads blobs this range is about to rewrite without re-running the
+  // pooling itself: write its blob first, from the bottoms it was given (the reference's blob would hold exactly that)
+  for (size_t k = 0; k < deferred_pools_.size(); ++k) {
+    if (start <= deferred_pools_[k].first_layer && end < deferred_pools_[k].first_layer)
+      static_cast<ROIPoolingLayer<Dtype>*>(layers_[deferred_pools_[k].first_layer].get())->Materialize();
+    // maps built early for an earlier frame's feature blob are never carried into this call (BoxOutput's hook rebuilds them)
+    static_cast<ConvolutionLayer<Dtype>*>(layers_[deferred_pools_[k].conv_layer].get())->InvalidateRoiMaps();
+  }
+  {
+    // split-fp16 convolutions take the bound of their input from the producing convolution when it runs in this same call
+    // from the top (slots zeroed here, once); a partial range makes them measure it themselves
+    const bool from_top = start == 0;
+    bool any = false;
+    auto conv_at = [this](int i) { return static_cast<ConvolutionLayer<Dtype>*>(layers_[i].get()); };
+    for (size_t q = 0; q < conv_layers_.size(); ++q) conv_layers_[q].layer->set_amax_wanted(false);
+    for (size_t q = 0; q < ip_layers_.size(); ++q) {
+      const int i = ip_layers_[q].index;
+      ip_layers_[q].layer->set_amax_trusted(from_top);
+      if (ip_layers_[q].layer->x3() && amax_src_[i] >= 0 && from_top) { conv_at(amax_src_[i])->set_amax_wanted(true); any = true; }
+    }
+    for (size_t q = 0; q < conv_layers_.size(); ++q) {
+      const int i = conv_layers_[q].index;
+      conv_layers_[q].layer->set_amax_trusted(from_top);
+      if (conv_layers_[q].layer->algo() == MSCNN_CONV_ALGO_WINO_F3_X3 && amax_src_[i] >= 0 && from_top) { conv_at(amax_src_[i])->set_amax_wanted(true); any = true; }
+    }
+    if (any && !amax_slots_) {
+      HIP_CHECK(hipMalloc(&amax_slots_, sizeof(unsigned) * MSCNN_AMAX_SLOTS * layers_.size()));
+      unsigned* slots = static_cast<unsigned*>(amax_slots_);
+      for (size_t q = 0; q < conv_layers_.size(); ++q) {
+        const int i = conv_layers_[q].index, b = amax_src_[i];
+        conv_layers_[q].layer->set_amax_io(b >= 0 ? conv_at(b) : nullptr, b >= 0 ? slots + (size_t)b * MSCNN_AMAX_SLOTS : nullptr,
+                                           slots + (size_t)i * MSCNN_AMAX_SLOTS);
+      }
+      for (size_t q = 0; q < ip_layers_.size(); ++q) {
+        const int b = amax_src_[ip_layers_[q].index];
+        if (b >= 0) ip_layers_[q].layer->set_amax_in(conv_at(b), slots + (size_t)b * MSCNN_AMAX_SLOTS);
+      }
+    }
+    if (any) HIP_CHECK(hipMemsetAsync(amax_slots_, 0, sizeof(unsigned) * MSCNN_AMAX_SLOTS * layers_.size(), (hipStream_t)Caffe::stream()));
+  }
+  // ROIAlign heads: one pass when the switch is on and all five layers run in this call.  Blobs an earlier one-pass forward left
+  // unwritten are written first unless this call writes them itself: it may rewrite what they are computed from
+  for (size_t k = 0; k < align_heads_.size(); ++k) {
+    AlignHead& h = align_heads_[k];
+    const bool whole_head = start <= h.first && h.last <= end;
+    h.live = roialign_one_pass_ && whole_head;
+    if (!whole_head) MaterializeAlignHead(h);
+    else if (!h.live) h.stale = false;      // (the stand-alone layers of this call write all four)
+  }
+  // convolution chains: a pair is live when both members run in this call; a consumer that runs WITHOUT its producer reads a blob
+  // the last whole Forward may not have written.  Every member's marks are down (ClearCallMarks): only the producers' are raised
+  const bool chains = fusion_ && chain_fusion_;
+  for (size_t k = 0; k < chain_pairs_.size(); ++k) {
+    const ChainPair& cp = chain_pairs_[k];
+    ConvolutionLayer<Dtype>* c = static_cast<ConvolutionLayer<Dtype>*>(layers_[cp.producer].get());
+    const bool producer_runs = start <= cp.producer && cp.producer <= end;
+    // (the layer under watch needs its bottom and its top as blobs: the producer of either writes y beside the planes / the pooled map)
+    c->set_keep_top(watch_layer >= 0 && (cp.producer == watch_layer || cp.consumer == watch_layer));
+    if (cp.consumer < 0) c->set_pool_only_live(chains && producer_runs);      // (a top read by the fused pooling only)
+    else if (chains && start <= cp.producer && cp.consumer <= end) c->set_chain_live(true);
+    // a blob the last Forward left unwritten whose producer does not run in this call: write it now, from the bottom its layer was
+    // given -- this call may rewrite that bottom, or run the consumer from the blob
+    if (!producer_runs) MaterializeBlob(cp.blob);
+  }
 }
 
 template <typename Dtype>
@@ -792,87 +907,7 @@ Dtype Net<Dtype>::ForwardFromTo(int start, int end) {
   }
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (timing_) { HIP_CHECK(hipEventCreate(&e0)); HIP_CHECK(hipEventCreate(&e1)); }
-  for (size_t i = 0; i < layers_.size(); ++i)      // (a paired ROIPooling skips only inside the call in which its partner ran)
-    if (string(layers_[i]->type()) == "ROIPooling") static_cast<ROIPoolingLayer<Dtype>*>(layers_[i].get())->set_skip(false);
-  // a deferred ROI pooling still pending from an earlier call reads blobs this range is about to rewrite without re-running the
-  // pooling itself: write its blob first, from the bottoms it was given (the reference's blob would hold exactly that)
-  for (size_t k = 0; k < deferred_pools_.size(); ++k) {
-    if (start <= deferred_pools_[k].first_layer && end < deferred_pools_[k].first_layer)
-      static_cast<ROIPoolingLayer<Dtype>*>(layers_[deferred_pools_[k].first_layer].get())->Materialize();
-    // maps built early for an earlier frame's feature blob are never carried into this call (BoxOutput's hook rebuilds them)
-    static_cast<ConvolutionLayer<Dtype>*>(layers_[deferred_pools_[k].conv_layer].get())->InvalidateRoiMaps();
-  }
-  {
-    // split-fp16 convolutions take the bound of their input from the producing convolution when it runs in this same call
-    // from the top (slots zeroed here, once); a partial range makes them measure it themselves
-    bool any = false;
-    for (size_t i = 0; i < layers_.size(); ++i)
-      if (ConvolutionLayer<Dtype>* c = dynamic_cast<ConvolutionLayer<Dtype>*>(layers_[i].get())) c->set_amax_wanted(false);
-    for (size_t i = 0; i < layers_.size(); ++i) {
-      if (InnerProductLayer<Dtype>* ip = dynamic_cast<InnerProductLayer<Dtype>*>(layers_[i].get())) {
-        ip->set_amax_trusted(start == 0);
-        if (ip->x3() && amax_src_[i] >= 0 && start == 0) {
-          static_cast<ConvolutionLayer<Dtype>*>(layers_[amax_src_[i]].get())->set_amax_wanted(true);
-          any = true;
-        }
-      }
-      ConvolutionLayer<Dtype>* c = dynamic_cast<ConvolutionLayer<Dtype>*>(layers_[i].get());
-      if (!c) continue;
-      c->set_amax_trusted(start == 0);
-      if (c->algo() == MSCNN_CONV_ALGO_WINO_F3_X3 && amax_src_[i] >= 0 && start == 0) {
-        static_cast<ConvolutionLayer<Dtype>*>(layers_[amax_src_[i]].get())->set_amax_wanted(true);
-        any = true;
-      }
-    }
-    if (any && !amax_slots_) {
-      HIP_CHECK(hipMalloc(&amax_slots_, sizeof(unsigned) * MSCNN_AMAX_SLOTS * layers_.size()));
-      unsigned* slots = static_cast<unsigned*>(amax_slots_);
-      for (size_t i = 0; i < layers_.size(); ++i)
-        if (ConvolutionLayer<Dtype>* c = dynamic_cast<ConvolutionLayer<Dtype>*>(layers_[i].get())) {
-          const int b = amax_src_[i];
-          c->set_amax_io(b >= 0 ? static_cast<const ConvolutionLayer<Dtype>*>(layers_[b].get()) : nullptr,
-                         b >= 0 ? slots + (size_t)b * MSCNN_AMAX_SLOTS : nullptr, slots + i * MSCNN_AMAX_SLOTS);
-        } else if (InnerProductLayer<Dtype>* ip = dynamic_cast<InnerProductLayer<Dtype>*>(layers_[i].get())) {
-          const int b = amax_src_[i];
-          if (b >= 0) ip->set_amax_in(static_cast<const ConvolutionLayer<Dtype>*>(layers_[b].get()), slots + (size_t)b * MSCNN_AMAX_SLOTS);
-        }
-    }
-    if (any) HIP_CHECK(hipMemsetAsync(amax_slots_, 0, sizeof(unsigned) * MSCNN_AMAX_SLOTS * layers_.size(), (hipStream_t)Caffe::stream()));
-  }
-  // ROIAlign heads: one pass when the switch is on and all five layers run in this call.  Blobs an earlier one-pass forward left
-  // unwritten are written first unless this call writes them itself: it may rewrite what they are computed from
-  for (size_t k = 0; k < align_heads_.size(); ++k) {
-    AlignHead& h = align_heads_[k];
-    const bool whole_head = start <= h.first && h.last <= end;
-    h.live = roialign_one_pass_ && whole_head;
-    if (!whole_head) MaterializeAlignHead(h);
-    else if (!h.live) h.stale = false;      // (the stand-alone layers of this call write all four)
-  }
-  // convolution chains: a pair is live when both members run in this call; a consumer that runs WITHOUT its producer reads a blob
-  // the last whole Forward may not have written
-  for (size_t k = 0; k < chain_pairs_.size(); ++k) {
-    const ChainPair& cp = chain_pairs_[k];
-    ConvolutionLayer<Dtype>* c = static_cast<ConvolutionLayer<Dtype>*>(layers_[cp.producer].get());
-    // (the layer under watch needs its bottom and its top as blobs: the producer of either writes y beside the planes / the pooled map)
-    c->set_keep_top(watch_layer >= 0 && (cp.producer == watch_layer || cp.consumer == watch_layer));
-    if (cp.consumer < 0) {      // (a top read by the fused pooling only)
-      c->set_pool_only_live(fusion_ && chain_fusion_ && start <= cp.producer && cp.producer <= end);
-      if (!(start <= cp.producer && cp.producer <= end)) MaterializeBlob(cp.blob);
-      continue;
-    }
-    const bool both = start <= cp.producer && cp.consumer <= end;
-    c->set_chain_live(fusion_ && chain_fusion_ && both);
-    static_cast<ConvolutionLayer<Dtype>*>(layers_[cp.consumer].get())->set_chain_live(false);
-    // a blob the last Forward left unwritten whose producer does not run in this call: write it now, from the bottom its layer was
-    // given -- this call may rewrite that bottom, or run the consumer from the blob
-    if (!(start <= cp.producer && cp.producer <= end)) MaterializeBlob(cp.blob);
-  }
-  for (size_t k = 0; k < chain_pairs_.size(); ++k) {      // (a consumer that is itself a producer: its own live mark, set above, stands)
-    const ChainPair& cp = chain_pairs_[k];
-    if (cp.consumer < 0) continue;
-    const bool both = start <= cp.producer && cp.consumer <= end;
-    static_cast<ConvolutionLayer<Dtype>*>(layers_[cp.producer].get())->set_chain_live(fusion_ && chain_fusion_ && both);
-  }
+  ArmCallMarks(start, end, watch_layer);
   for (int i = start; i <= end; ++i) {
     bool run = !fused_away_[i];
     if (fused_away_[i]) {
@@ -887,13 +922,8 @@ Dtype Net<Dtype>::ForwardFromTo(int start, int end) {
         layers_[i]->Reshape(bottom_vecs_[i], top_vecs_[i]);      // shapes follow the bottoms exactly as Layer::Forward would
     }
     // a live ROIAlign head: its first layer does the work of all five, the other four only take their shapes
-    int head_role = -1;
-    const AlignHead* head = nullptr;
-    for (size_t k = 0; k < align_heads_.size() && !head; ++k)
-      if (align_heads_[k].live)
-        for (int q = 0; q < 5; ++q)
-          if (align_heads_[k].layer[q] == i) { head = &align_heads_[k]; head_role = q; }
-    if (head && head_role > 0) {
+    const AlignHead* head = layer_head_[i] >= 0 && align_heads_[layer_head_[i]].live ? &align_heads_[layer_head_[i]] : nullptr;
+    if (head && layer_head_role_[i] > 0) {
       layers_[i]->Reshape(bottom_vecs_[i], top_vecs_[i]);
       run = false;
     }
@@ -908,8 +938,10 @@ Dtype Net<Dtype>::ForwardFromTo(int start, int end) {
     } else {
       layers_[i]->Forward(bottom_vecs_[i], top_vecs_[i]);
     }
-    for (size_t t = 0; t < top_id_vecs_[i].size(); ++t)
-      if (redirect_.count(top_id_vecs_[i][t])) redirect_dirty_[top_id_vecs_[i][t]] = true;
+    for (size_t t = 0; t < top_id_vecs_[i].size(); ++t) {
+      const typename std::map<int, Redirect>::const_iterator rd = redirect_.find(top_id_vecs_[i][t]);
+      if (rd != redirect_.end()) rd->second.dirty = true;
+    }
     if (timing_) {
       HIP_CHECK(hipEventRecord(e1, (hipStream_t)Caffe::stream()));
       HIP_CHECK(hipEventSynchronize(e1));
@@ -936,33 +968,16 @@ Dtype Net<Dtype>::ForwardFromTo(int start, int end) {
       ++watch_checks_;
     }
   }
-  // a paired ROIPooling's skip mark must not outlive the call in which its partner ran (a range that ends between the two, then a
-  // direct Layer::Forward on the second: it has to pool, not skip)
-  for (size_t i = 0; i < layers_.size(); ++i)
-    if (string(layers_[i]->type()) == "ROIPooling") static_cast<ROIPoolingLayer<Dtype>*>(layers_[i].get())->set_skip(false);
-  for (size_t k = 0; k < chain_pairs_.size(); ++k) {
-    static_cast<ConvolutionLayer<Dtype>*>(layers_[chain_pairs_[k].producer].get())->set_chain_live(false);
-    static_cast<ConvolutionLayer<Dtype>*>(layers_[chain_pairs_[k].producer].get())->set_pool_only_live(false);
-    static_cast<ConvolutionLayer<Dtype>*>(layers_[chain_pairs_[k].producer].get())->set_keep_top(false);
-    if (chain_pairs_[k].consumer >= 0) static_cast<ConvolutionLayer<Dtype>*>(layers_[chain_pairs_[k].consumer].get())->set_chain_live(false);
-  }
+  ClearCallMarks();
   // books of the layers' own first-forward checks (safe-by-default numerics: ConvolutionLayer::set_selfcheck)
-  for (int i = start; i <= end; ++i)
-    if (ConvolutionLayer<Dtype>* c = dynamic_cast<ConvolutionLayer<Dtype>*>(layers_[i].get())) {
-      double e = 0.0;
-      bool fell = false;
-      if (c->take_selfcheck(&e, &fell)) {
-        calib_err_[i] = e;
-        ++auto_checks_;
-        if (fell) auto_switched_.push_back(i);
-      }
-    }
-  // The max |x| slots a split-fp16 layer takes from its producer are only valid inside this call: a later Layer::Forward called
-  // directly on a layer (caffe time, user code, the boundary tests) must measure its bottom itself instead of trusting the slots of
-  // the frame that went through here.
-  for (size_t i = 0; i < layers_.size(); ++i) {
-    if (ConvolutionLayer<Dtype>* c = dynamic_cast<ConvolutionLayer<Dtype>*>(layers_[i].get())) c->set_amax_trusted(false);
-    else if (InnerProductLayer<Dtype>* ip = dynamic_cast<InnerProductLayer<Dtype>*>(layers_[i].get())) ip->set_amax_trusted(false);
+  for (size_t q = 0; q < conv_layers_.size(); ++q) {
+    const int i = conv_layers_[q].index;
+    double e = 0.0;
+    bool fell = false;
+    if (i < start || i > end || !conv_layers_[q].layer->take_selfcheck(&e, &fell)) continue;
+    calib_err_[i] = e;
+    ++auto_checks_;
+    if (fell) auto_switched_.push_back(i);
   }
   if (handoff_restart) {
     // (whole-tile scheduling is forced by now: the second pass cannot raise the event again, so this recursion is one level deep.  The
@@ -977,6 +992,7 @@ Dtype Net<Dtype>::ForwardFromTo(int start, int end) {
   }
   return 0;
 }
+
 
 template <typename Dtype>
 const vector<Blob<Dtype>*>& Net<Dtype>::Forward(Dtype* loss) {

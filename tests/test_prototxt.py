@@ -498,3 +498,27 @@ def test_hdf5_weights_written_by_libhdf5(tmp_path):
     f = h5.H5Fcreate(os.fsencode(str(p5)), 2, 0, 0); g = h5.H5Gcreate2(f, b"weights", 0, 0, 0); h5.H5Gclose(g); h5.H5Fclose(f)
     with pytest.raises(mnet.NetError, match='no group "data"'):
         n.load_caffemodel(p5)
+
+
+def _wiring(n):
+    try:
+        lk = list(n.forward_rois_layers())
+    except mnet.NetError:
+        lk = None
+    return {"fused_away": [n.layer_names[i] for i in range(len(n.layer_names)) if n.fused_away(i)],
+            "chain_pairs": [list(p) for p in n.chain_pairs()],
+            "roialign_pairs": list(n.roialign_pairs()),
+            "forward_rois_layers": lk}
+
+
+@pytest.mark.parametrize("fusion", [True, False])
+@pytest.mark.parametrize("model", sorted(zoo.MODELS))
+def test_construction_time_wiring_matches_the_recorded_fixture(model, fusion):
+    """What Net::Init decides from the graph alone -- the fused-away layers, the convolution chains, the ROIAlign heads, L and K of
+    forward_rois -- for every deploy of the zoo with and without the Net-level fusion, against tests/golden/net_wiring.json (recorded
+    from the Net as it was before the graph index replaced the per-pass scans; never regenerated from the code under test)."""
+    import json
+    want = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "net_wiring.json")))
+    assert len(want) == 2 * len(zoo.MODELS)
+    n = mnet.Net(prototxt_text=zoo.prototxt(model), device=-1, fusion=fusion)
+    assert _wiring(n) == want["%s fusion=%d" % (model, fusion)]
