@@ -49,6 +49,7 @@
  *   nms_greedy                 boxes 16: refuses; keep_out 1
  *   boxoutput*                 heads, rois_out, props_out, anchor_ids_out, count_out_dev 4
  *   detections*                blobs, ids_out, count_out_dev 4; dets_out 8: refuses
+ *   detections_candidates_*, detections_merge_fwd   cand, workspace, pack_dev 16: refuses; the blobs 4
  *   proposals_multi_fwd        props 8: refuses
  *   rois_ingest                rows 8: refuses; rois, props, image_rows, status 4
  */
@@ -627,6 +628,63 @@ MSCNN_API int mscnn_detections_cascade_multi_nms_fwd(const mscnn_detections_desc
                                                      int num_images, int num_outputs, int num_classes,
                                                      const mscnn_cascade_output* outputs, int R_all, int max_rows_per_image,
                                                      void* pack_dev, int cap, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Several forwards of an image, ONE NMS: input sizes (multi-scale testing), a mirrored frame, tiles of a frame too large for one
+ * forward.  The rows that survive the final stage's row transform stay on the device, per segment, in original-image coordinates
+ * (the candidates); the sort, bit matrix and scan of the calls above then run once over each list (the merge).
+ * A segment is (image, class) for the plain stage and (image, cascade output, class) for the cascade stage, S of them, indexed as
+ * the desc of the multi calls above.  cand: one device buffer of mscnn_detections_candidates_bytes(S, cand_cap) bytes (0: refused
+ * arguments) -- per segment two int32 {rows that wanted in, overflow flag} and cand_cap slots of box (4 doubles), prob (float) and
+ * tag (int32).  Layout, each array at the next multiple of 256 bytes, list s in slots [s * cand_cap, + cand_cap) of each:
+ *   [S x int32 {wanted, overflow}][S cand_cap x 4 doubles x y w h][S cand_cap x float prob][S cand_cap x int32 tag]
+ * mscnn_detections_candidates_reset zeroes every count and flag (the slots are left as they are).
+ *
+ * mscnn_detections_candidates_add / _cascade_add take the arguments of mscnn_detections_multi_nms_fwd /
+ * mscnn_detections_cascade_multi_nms_fwd for ONE forward: each segment finds its image's rows in props, every row goes through the
+ * very row transform and filters of those calls (proposal filter, thr / det_thr of nms included), and the forward's view is applied
+ * in double to the box [x y w h] that came out:
+ *     x' = flip_x ? (double)org_w - (x + w) : x        org_w = the desc's, as the float the row was clipped against
+ *     x' = x' + off_x,  y' = y + off_y                  w, h and prob are untouched
+ * view[num_images], one per image; NULL = the identity (the box bit for bit).  The desc's org_h / org_w and ratios describe the
+ * VIEW -- the tile or the whole frame at this forward's input size --, the offsets place it in the original image.  The cascade
+ * rows keep their w = x2 - x1 + 1 convention; the same formula applies to them.  Survivors are appended behind the segment's
+ * count in row order (one workgroup per segment, steps of 256 rows, ballot / popcount prefix, no atomics), so a list's order is
+ * (order of the add calls, row) whatever the timing.  tag = (pass << 24) | row, row = the row of that forward's ROI blobs
+ * (absolute in the batch: the convention of the multi calls' ids + row0).  A list that would pass cand_cap stores nothing past the
+ * cap, sets its overflow flag and keeps counting the rows that wanted in: never a silent truncation.  One launch per 32 segments.
+ *
+ * mscnn_detections_merge_fwd: the NMS over each list.  Sort key: larger prob first, then the earlier candidate -- a tie between
+ * two passes goes to the pass added first, inside a pass to the lower row.  nms_overlap[S]: a HOST array, one per segment.  Of nms,
+ * type and ovr_dnm are read here (thr and det_thr were applied by the add calls).  cand_cap <= 4032: all segments in one pass, three
+ * launches per 32 segments, no host read.  cand_cap > 4032: list after list on the tiled kernels, each list's length read from its
+ * device count; the default type / ovr_dnm only, anything else is refused naming the limit.
+ * pack_dev: the multi pack, mscnn_multi_pack_layout_of(S, S * cand_cap):
+ *   [int32 S, cand_cap, S * cand_cap, 0][S x int32 {count, candidates, s * cand_cap, 0}][S cand_cap x 5 doubles][S cand_cap x int32 tag]
+ * segment s owns pack rows [s * cand_cap, + cand_cap) and fills the first count; count -1: the list overflowed (candidates = the
+ * rows that wanted in, nothing was run).  The kernels write every header and table word; rows of a slot past its count are left as
+ * they were.  workspace: mscnn_detections_merge_workspace_bytes(S, cand_cap) bytes (0: refused arguments).
+ * Refused before any launch, naming the value: null pointers, S < 1, cand_cap < 1 (or S * cand_cap past 2^31 - 1), pass outside
+ * [0, 127], R_all < 1 or >= 2^24, a NaN or non-positive ratio, a NaN overlap, a non-finite offset, a flip_x that is neither 0 nor 1,
+ * a workspace that is too small, cand / workspace / pack_dev not 16-byte aligned, a non-zero nms det_thr in the cascade add.
+ * No pin on the reference: its scripts run one forward per image.  The check is a numpy restatement (tests/merge_witness.py), and
+ * one add + merge is bit-identical to mscnn_detections_multi_nms_fwd / mscnn_detections_cascade_multi_nms_fwd on the same blobs. */
+#ifndef MSCNN_DETECTIONS_VIEW_DEFINED
+#define MSCNN_DETECTIONS_VIEW_DEFINED
+typedef struct { double off_x, off_y; int flip_x; } mscnn_detections_view;
+#endif
+MSCNN_API size_t mscnn_detections_candidates_bytes(int num_segments, int cand_cap);
+MSCNN_API int mscnn_detections_candidates_reset(void* cand, int num_segments, int cand_cap, void* stream);
+MSCNN_API int mscnn_detections_candidates_add(const mscnn_detections_desc* desc, const mscnn_detections_view* view,
+                                              const mscnn_nms_params* nms, int pass, int num_images, int num_classes,
+                                              const float* bbox_pred, const float* cls_pred, const float* props, int R_all, void* cand,
+                                              int cand_cap, void* stream);
+MSCNN_API int mscnn_detections_candidates_cascade_add(const mscnn_detections_desc* desc, const mscnn_detections_view* view, float det_thr,
+                                                      const mscnn_nms_params* nms, int pass, int num_images, int num_outputs,
+                                                      int num_classes, const mscnn_cascade_output* outputs, int R_all, void* cand,
+                                                      int cand_cap, void* stream);
+MSCNN_API size_t mscnn_detections_merge_workspace_bytes(int num_segments, int cand_cap);
+MSCNN_API int mscnn_detections_merge_fwd(const double* nms_overlap, const mscnn_nms_params* nms, int num_segments, void* cand,
+                                         int cand_cap, void* pack_dev, void* workspace, size_t workspace_bytes, void* stream);
 
 /* The proposal half of the scripts' result (run_mscnn_detection.m:75-91, `final_proposals{k}`) for every image of a batched forward
  * in one pass.  props [R_all][6] = BoxOutput's proposals_score, rows [img x1 y1 x2 y2 score] grouped by image in ascending order;

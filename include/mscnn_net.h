@@ -341,6 +341,46 @@ MSCNN_NET_API int mscnn_net_detect_cascade_multi_device(mscnn_net* net, const ms
                                                         const char* const* proposal_blobs, float det_thr, int cap,
                                                         const void** pack_dev);
 
+/* Several forwards of a frame, ONE NMS: input sizes (multi-scale testing), a mirrored frame, tiles of a frame too large for one
+ * forward (mscnn_hip.h: mscnn_detections_candidates_*, mscnn_detections_merge_fwd).  Between _begin and _end the caller may
+ * reshape_input, set_image(s), forward, forward_rois -- everything that leaves the three blobs behind -- and calls one _add after each
+ * forward: the rows that survive the final stage's row transform (its filters and the net's sticky set_nms thr / det_thr included)
+ * stay on the device, per segment, in original-image coordinates.  _end runs the sort and the NMS once over each segment's list.
+ *   _begin   reserves and resets the lists: num_images x num_classes segments of cand_cap candidate slots each.  For the cascade
+ *            form num_classes stands for num_outputs x num_classes.
+ *   _add     p[num_images * num_classes] as in mscnn_net_detect_multi, describing THIS forward's view of each image: ratios = the
+ *            net's input size / the view's size, org_h / org_w = the view's size (the tile, or the whole frame).  view[num_images]
+ *            (NULL: the identity) places the view in the original image, in double, on the box [x y w h] the row transform returned:
+ *                x' = flip_x ? (double)(float)org_w - (x + w) : x;   x' += off_x;   y' = y + off_y;   w, h, prob untouched
+ *            (a frame mirrored with [:, ::-1] has flip_x = 1; a tile has its corner as the offset).  The cascade rows keep their
+ *            w = x2 - x1 + 1 convention under the same formula.  The pass index is the number of adds since _begin (at most 128).
+ *            Refused before anything is enqueued, naming the values: the sum over the adds so far of each forward's ROI row count
+ *            could pass cand_cap (the host knows every R_all: never a truncation); an nms_overlap other than the one the segment
+ *            had at the first add (both values named); a NaN overlap, a non-positive ratio, a non-finite offset, a flip_x that is
+ *            neither 0 nor 1; num_images other than the input's N; no merge open.
+ *   _cascade_add   the same for the cascade deploys: blob triples and det_thr as in mscnn_net_detect_cascade_multi.
+ *   _end     one synchronisation.  Output segment after segment: dets_host[cap][5] doubles, pass_host[cap] / row_host[cap] (may be
+ *            NULL) = the forward (0-based add index) and the row of THAT forward's ROI blobs each detection came from, seg_dets[S],
+ *            seg_candidates[S] (may be NULL) = candidates of each list.  Sort: larger prob first; a tie goes to the forward added
+ *            first, inside a forward to the lower row.  More detections than cap is an error naming the numbers; a list that
+ *            overflowed is an error naming the segment and the count.  The merge is closed afterwards, also when _end fails.
+ *            Lists of more than 4032 slots run list after list on the tiled kernels, which take the default nms type / ovr_dnm only.
+ * A _begin while a merge is open, and an _add or _end without _begin, are errors.  A stream-K hand-off time-out in one of the forwards
+ * can not be answered by a re-run here: _end FAILS as mscnn_net_detect_end does, and the forwards are run and added again.
+ * One forward added and merged is bit-identical to mscnn_net_detect_multi / mscnn_net_detect_cascade_multi.  No pin on the
+ * reference: its scripts run one forward per image; the check is a numpy restatement (tests/merge_witness.py). */
+#ifndef MSCNN_DETECTIONS_VIEW_DEFINED
+#define MSCNN_DETECTIONS_VIEW_DEFINED
+typedef struct { double off_x, off_y; int flip_x; } mscnn_detections_view;
+#endif
+MSCNN_NET_API int mscnn_net_detect_merge_begin(mscnn_net* net, int num_images, int num_classes, int cand_cap);
+MSCNN_NET_API int mscnn_net_detect_merge_add(mscnn_net* net, const mscnn_detect_params* p, const mscnn_detections_view* view);
+MSCNN_NET_API int mscnn_net_detect_cascade_merge_add(mscnn_net* net, const mscnn_detect_params* p, const mscnn_detections_view* view,
+                                                     int num_outputs, const char* const* bbox_blobs, const char* const* prob_blobs,
+                                                     const char* const* proposal_blobs, float det_thr);
+MSCNN_NET_API int mscnn_net_detect_merge_end(mscnn_net* net, double* dets_host, int* pass_host, int* row_host, int cap, int* seg_dets,
+                                             int* seg_candidates);
+
 /* Multi-GPU form of the same stage (include/mscnn_dist.h gathers its result over RCCL): the detections stay in HBM, in a
  * fixed-size pack  [int32 count, int32 num_rois, int32 cap, int32 0][cap x 5 doubles x y w h prob][cap x int32 roi row]
  * of mscnn_net_detect_pack_bytes(cap) bytes (a multiple of 16).  cap must be >= the net's ROI count (BoxOutput's

@@ -456,6 +456,223 @@ __global__ __launch_bounds__(256) void det_seg_color_emit_kernel(DetSegArgs a) {
   det_seg_emit<false>(a, dyn_lds);
 }
 
+// ---- the candidates of several forwards of an image, merged before the NMS (mscnn_detections_candidates_*, mscnn_detections_merge_fwd) ----
+// A segment's list: cand_cap slots of box / prob / tag and two ints {rows that wanted in, overflow flag}.  `add` runs the rows of one
+// forward through det_row above -- the final stage's own row transform -- applies the forward's view in double and appends the
+// survivors behind the list's count in row order; `merge` sorts each list by det_key(prob, candidate index) and runs the bit matrix
+// and the scan / column-OR above over it.  One workgroup owns a segment's list in every kernel: no atomics on global memory, no
+// workgroup waits on another, the order of a list is (order of the add calls, row) whatever the timing.
+enum { CAND_WANTED = 0, CAND_OVER = 1, CAND_WORDS = 2 };
+struct DetCand { int* cnt; DetBox* box; float* prob; int* tag; };      // cnt: CAND_WORDS ints per segment; the lists: cand_cap slots per segment
+__host__ __device__ __forceinline__ size_t cand_al(size_t v) { return (v + 255) / 256 * 256; }
+__host__ __device__ __forceinline__ size_t det_cand_bytes(int S, int cap) {
+  const size_t n = (size_t)S * (size_t)cap;
+  return cand_al((size_t)S * CAND_WORDS * sizeof(int)) + cand_al(n * sizeof(DetBox)) + 2 * cand_al(n * sizeof(int));
+}
+__host__ __device__ __forceinline__ DetCand det_cand_of(char* cand, int S, int cap) {
+  const size_t n = (size_t)S * (size_t)cap;
+  DetCand c;
+  c.cnt = reinterpret_cast<int*>(cand);
+  char* p = cand + cand_al((size_t)S * CAND_WORDS * sizeof(int));
+  c.box = reinterpret_cast<DetBox*>(p); p += cand_al(n * sizeof(DetBox));
+  c.prob = reinterpret_cast<float*>(p); p += cand_al(n * sizeof(float));
+  c.tag = reinterpret_cast<int*>(p);
+  return c;
+}
+
+struct DetView { double off_x, off_y; int flip_x, on; };      // on = 0: view == NULL, the box leaves as det_row returned it
+struct DetCandArgs {
+  int R_all, slots_per_image, classes_per_source, cand_cap, num_segs, s0, pass;
+  char* cand;
+  DetNms nms;
+  DetSource src[kCascadeMaxOutputs];
+  DetSeg seg[kSegsPerLaunch];
+  DetView view[kSegsPerLaunch];
+};
+static_assert(sizeof(DetCandArgs) <= 4096, "DetCandArgs travels as kernel arguments");
+constexpr int kCandThreads = 256;
+
+// one workgroup per segment; steps of 256 rows, a kept row's place = the list's count + the kept rows of the waves before its own +
+// those of the lower lanes of its wave (ballot / popcount, as proposals.hip).  The count is read and stored by this workgroup alone.
+template <bool kThr>
+__device__ __forceinline__ void det_cand_add(const DetCandArgs& a) {
+  const int j = blockIdx.x, s = a.s0 + j, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int img = s / a.slots_per_image;
+  const DetSource& t = a.src[(s % a.slots_per_image) / a.classes_per_source];
+  const int prop_stride = t.cascade ? 5 : 6, box_stride = t.cascade ? 5 : 4 * t.ncls;
+  const DetCand c = det_cand_of(a.cand, a.num_segs, a.cand_cap);
+  __shared__ int s_range[2];
+  __shared__ int s_base;
+  __shared__ int s_cnt[kCandThreads / 64];
+  if (tid < 2) s_range[tid] = det_image_lower_bound(t.props, a.R_all, img + tid, prop_stride);
+  if (tid == 2) s_base = c.cnt[CAND_WORDS * (size_t)s + CAND_WANTED];
+  __syncthreads();
+  const int row0 = s_range[0], rows = s_range[1] - s_range[0];
+  int base = s_base;
+  const DetSeg& g = a.seg[j];
+  DetArgs d;
+  d.bbox_pred = t.boxes + (size_t)row0 * box_stride; d.cls_pred = t.cls + (size_t)row0 * t.ncls; d.props = t.props + (size_t)row0 * prop_stride;
+  d.R = rows; d.ncls = t.ncls; d.cls_id = g.cls_id;
+  for (int k = 0; k < 4; ++k) { d.mean[k] = g.mean[k]; d.stdv[k] = g.stdv[k]; }
+  d.proposal_thr = g.proposal_thr; d.ratio_h = g.ratio_h; d.ratio_w = g.ratio_w; d.org_h = g.org_h; d.org_w = g.org_w;
+  d.cascade = t.cascade;
+  d.nms_thr = a.nms.thr; d.det_thr = t.cascade ? 0.f : a.nms.det_thr;
+  const DetView v = a.view[j];
+  const size_t list = (size_t)s * (size_t)a.cand_cap;
+  for (int r0 = 0; r0 < rows; r0 += kCandThreads) {
+    const int r = r0 + tid;
+    DetBox b;
+    float prob = 0.f;
+    bool keep = false;
+    if (r < rows) keep = det_row<kThr>(d, r, &b, &prob);
+    const u64 m = __ballot(keep);
+    if (lane == 0) s_cnt[wave] = __popcll(m);
+    __syncthreads();
+    int before = 0, total = 0;
+    for (int w = 0; w < kCandThreads / 64; ++w) {
+      if (w < wave) before += s_cnt[w];
+      total += s_cnt[w];
+    }
+    if (keep) {
+      const long pos = (long)base + before + __popcll(m & ((1ull << lane) - 1ull));
+      if (pos < (long)a.cand_cap) {                     // (past the cap nothing is stored: the count below says how many wanted in)
+        if (v.on) {
+          if (v.flip_x) b.x = (double)d.org_w - (b.x + b.w);
+          b.x = b.x + v.off_x;
+          b.y = b.y + v.off_y;
+        }
+        c.box[list + pos] = b;
+        c.prob[list + pos] = prob;
+        c.tag[list + pos] = (a.pass << 24) | (row0 + r);
+      }
+    }
+    const long nb = (long)base + total;
+    base = nb > 0x7fffffffL ? 0x7fffffff : (int)nb;
+    __syncthreads();      // (every thread has read s_cnt before the next step writes it)
+  }
+  if (tid == 0) {
+    c.cnt[CAND_WORDS * (size_t)s + CAND_WANTED] = base;
+    if (base > a.cand_cap) c.cnt[CAND_WORDS * (size_t)s + CAND_OVER] = 1;
+  }
+}
+__global__ __launch_bounds__(kCandThreads) void det_cand_add_kernel(DetCandArgs a) { det_cand_add<false>(a); }
+__global__ __launch_bounds__(kCandThreads) void det_cand_add_thr_kernel(DetCandArgs a) { det_cand_add<true>(a); }
+
+// -- merge, lists of at most kMaxK slots: every segment in one pass, three launches per kSegsPerLaunch segments
+struct DetMergeArgs {
+  int cand_cap, wpr, num_segs, s0;
+  char* cand; char* ws; size_t seg_stride_box, seg_stride_mask;
+  int* hdr; double* dets; int* ids;
+  double overlap[kSegsPerLaunch];
+};
+enum { MRG_N = 0, MRG_WANTED = 1, MRG_OVER = 2, MRG_WORDS = 4 };      // workspace words per segment
+struct DetMergePtrs { int* cnt; DetBox* sbox; double* sprob; int* ssrc; u64* mask; };
+__host__ __device__ __forceinline__ size_t det_merge_seg_box_bytes(int cap) {
+  return cand_al((size_t)cap * sizeof(DetBox)) + cand_al((size_t)cap * sizeof(double)) + cand_al((size_t)cap * sizeof(int));
+}
+__host__ __device__ __forceinline__ size_t det_merge_seg_mask_bytes(int cap) {
+  return cand_al((size_t)cap * (size_t)((cap + 63) / 64) * sizeof(u64));
+}
+__device__ __forceinline__ DetMergePtrs det_merge_ptrs(const DetMergeArgs& a, int s) {
+  const size_t M = (size_t)a.cand_cap;
+  char* base = a.ws + cand_al((size_t)a.num_segs * MRG_WORDS * sizeof(int));
+  char* b = base + (size_t)s * a.seg_stride_box;
+  DetMergePtrs p;
+  p.cnt = reinterpret_cast<int*>(a.ws) + (size_t)s * MRG_WORDS;
+  p.sbox = reinterpret_cast<DetBox*>(b);
+  p.sprob = reinterpret_cast<double*>(b + cand_al(M * sizeof(DetBox)));
+  p.ssrc = reinterpret_cast<int*>(b + cand_al(M * sizeof(DetBox)) + cand_al(M * sizeof(double)));
+  p.mask = reinterpret_cast<u64*>(base + (size_t)a.num_segs * a.seg_stride_box + (size_t)s * a.seg_stride_mask);
+  return p;
+}
+
+// one workgroup per segment: keys of the list's candidates, sort, the sorted boxes.  A list that overflowed is not run (n = 0).
+__global__ __launch_bounds__(kSortThreads) void det_merge_sort_kernel(DetMergeArgs a) {
+  __shared__ u64 sk[kSortCap];
+  const int j = blockIdx.x, s = a.s0 + j, tid = threadIdx.x;
+  const DetCand c = det_cand_of(a.cand, a.num_segs, a.cand_cap);
+  const DetMergePtrs p = det_merge_ptrs(a, s);
+  const int wanted = c.cnt[CAND_WORDS * (size_t)s + CAND_WANTED], over = c.cnt[CAND_WORDS * (size_t)s + CAND_OVER];
+  const int n = (over || wanted > a.cand_cap) ? 0 : (wanted < 0 ? 0 : wanted);
+  if (s == 0 && tid == 0) { a.hdr[0] = a.num_segs; a.hdr[1] = a.cand_cap; a.hdr[2] = a.num_segs * a.cand_cap; a.hdr[3] = 0; }
+  if (tid == 0) { p.cnt[MRG_N] = n; p.cnt[MRG_WANTED] = wanted; p.cnt[MRG_OVER] = (over || wanted > a.cand_cap) ? 1 : 0; }
+  if (n == 0) return;
+  const size_t list = (size_t)s * (size_t)a.cand_cap;
+  int P = 1;
+  while (P < n) P <<= 1;
+  for (int i = tid; i < P; i += kSortThreads) sk[i] = i < n ? det_key(c.prob[list + i], i) : 0ull;
+  __syncthreads();
+  bitonic_desc(sk, P, tid, kSortThreads);
+  for (int i = tid; i < n; i += kSortThreads) {
+    const int k = (int)(0xffffffffu - (unsigned)(sk[i] & 0xffffffffull));
+    p.sbox[i] = c.box[list + k];
+    p.sprob[i] = (double)c.prob[list + k];
+    p.ssrc[i] = c.tag[list + k];
+  }
+}
+
+template <bool kDnmMin>
+__device__ __forceinline__ void det_merge_mask(const DetMergeArgs& a) {
+  const int j = blockIdx.z, s = a.s0 + j;
+  const DetMergePtrs p = det_merge_ptrs(a, s);
+  det_mask_block<kDnmMin>(p.sbox, p.cnt[MRG_N], a.overlap[j], p.mask, a.wpr, blockIdx.y, blockIdx.x);
+}
+__global__ __launch_bounds__(256) void det_merge_mask_kernel(DetMergeArgs a) { det_merge_mask<false>(a); }
+__global__ __launch_bounds__(256) void det_merge_mask_min_kernel(DetMergeArgs a) { det_merge_mask<true>(a); }
+
+// table entry {count (-1: the list overflowed), rows that wanted in, first pack row, 0}
+template <bool kGreedy>
+__device__ __forceinline__ void det_merge_emit(const DetMergeArgs& a, u64* dyn_lds) {
+  const int j = blockIdx.x, s = a.s0 + j;
+  const DetMergePtrs p = det_merge_ptrs(a, s);
+  int* ent = a.hdr + MSCNN_MULTI_PACK_WORDS * (size_t)(1 + s);
+  const size_t slot = (size_t)s * (size_t)a.cand_cap;
+  if (threadIdx.x == 0) { ent[1] = p.cnt[MRG_WANTED]; ent[2] = (int)slot; ent[3] = 0; }
+  if (p.cnt[MRG_OVER]) { if (threadIdx.x == 0) ent[0] = -1; return; }
+  if (kGreedy) det_scan_emit(p.mask, a.wpr, p.cnt[MRG_N], p.sbox, p.sprob, p.ssrc, a.dets + 5 * slot, a.ids + slot, ent, dyn_lds);
+  else det_color_emit(p.mask, a.wpr, p.cnt[MRG_N], p.sbox, p.sprob, p.ssrc, a.dets + 5 * slot, a.ids + slot, ent, dyn_lds);
+}
+__global__ __launch_bounds__(256) void det_merge_scan_emit_kernel(DetMergeArgs a) {
+  extern __shared__ __attribute__((aligned(16))) u64 dyn_lds[];
+  det_merge_emit<true>(a, dyn_lds);
+}
+__global__ __launch_bounds__(256) void det_merge_color_emit_kernel(DetMergeArgs a) {
+  extern __shared__ __attribute__((aligned(16))) u64 dyn_lds[];
+  det_merge_emit<false>(a, dyn_lds);
+}
+
+// -- merge, lists of more than kMaxK slots: one list at a time on the tiled kernels (nms_large.h)
+// keys[0 .. P): the list's keys, then zero padding; cnt[DC_N] = the list's length (0 when it overflowed), the tiled path's state cleared
+__global__ __launch_bounds__(256) void det_merge_keys_big_kernel(const int* __restrict__ lcnt, const float* __restrict__ prob, int cap,
+                                                                 u64* __restrict__ keys, int P, int* __restrict__ cnt) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int wanted = lcnt[CAND_WANTED];
+  const int n = (lcnt[CAND_OVER] || wanted > cap || wanted < 0) ? 0 : wanted;
+  if (i == 0) { cnt[DC_N] = n; cnt[DC_BIG + BIG_TILE_N] = 0; cnt[DC_BIG + BIG_NKEPT] = 0; }
+  if (i < P) keys[i] = i < n ? det_key(prob[i], i) : 0ull;
+}
+__global__ __launch_bounds__(256) void det_merge_gather_big_kernel(const u64* __restrict__ keys, const DetBox* __restrict__ box,
+                                                                   const float* __restrict__ prob, const int* __restrict__ tag,
+                                                                   DetBox* __restrict__ sbox, double* __restrict__ sprob,
+                                                                   int* __restrict__ ssrc, const int* __restrict__ cnt) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= cnt[DC_N]) return;
+  const int k = (int)(0xffffffffu - (unsigned)(keys[i] & 0xffffffffull));
+  sbox[i] = box[k];
+  sprob[i] = (double)prob[k];
+  ssrc[i] = tag[k];
+}
+// header and the table words the emit kernel does not write; runs behind the last list's emit (which stored every count)
+__global__ __launch_bounds__(256) void det_merge_table_big_kernel(const int* __restrict__ lcnt, int S, int cap, int* __restrict__ hdr) {
+  const int s = blockIdx.x * 256 + threadIdx.x;
+  if (s == 0) { hdr[0] = S; hdr[1] = cap; hdr[2] = S * cap; hdr[3] = 0; }
+  if (s >= S) return;
+  const int wanted = lcnt[CAND_WORDS * (size_t)s + CAND_WANTED];
+  int* ent = hdr + MSCNN_MULTI_PACK_WORDS * (size_t)(1 + s);
+  if (lcnt[CAND_WORDS * (size_t)s + CAND_OVER] || wanted > cap) ent[0] = -1;
+  ent[1] = wanted; ent[2] = s * cap; ent[3] = 0;
+}
+
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 struct DetLayout { size_t cnt, sbox, sprob, ssrc, tbox, tprob, mask, keys, rinit, kidx, kbox, total; int wpr, sortP; bool big; };
 DetLayout det_layout(int R) {
@@ -811,4 +1028,207 @@ extern "C" int mscnn_detections_cascade_multi_fwd(const mscnn_detections_desc* d
                                                   size_t workspace_bytes, void* stream) {
   return mscnn_detections_cascade_multi_nms_fwd(desc, det_thr, nullptr, num_images, num_outputs, num_classes, outputs, R_all,
                                                 max_rows_per_image, pack_dev, cap, workspace, workspace_bytes, stream);
+}
+
+// ---- candidate lists of several forwards, one NMS over each (mscnn_hip.h) -------------------------------------------------------------
+static bool cand_shape_ok(int S, int cand_cap) { return S >= 1 && cand_cap >= 1 && (long)S * (long)cand_cap <= 0x7fffffffL; }
+
+extern "C" size_t mscnn_detections_candidates_bytes(int num_segments, int cand_cap) {
+  return cand_shape_ok(num_segments, cand_cap) ? det_cand_bytes(num_segments, cand_cap) : 0;
+}
+
+extern "C" int mscnn_detections_candidates_reset(void* cand, int num_segments, int cand_cap, void* stream) {
+  MSCNN_REQUIRE(cand, "detections_candidates_reset: null pointer");
+  MSCNN_REQUIRE(num_segments >= 1, "detections_candidates_reset: %d segments", num_segments);
+  MSCNN_REQUIRE(cand_cap >= 1, "detections_candidates_reset: cand_cap %d", cand_cap);
+  MSCNN_REQUIRE(cand_shape_ok(num_segments, cand_cap), "detections_candidates_reset: %d segments x %d slots is past 2^31 - 1", num_segments,
+                cand_cap);
+  MSCNN_REQUIRE_ALIGNED(cand, 16, "detections_candidates_reset: cand");
+  MSCNN_HIP_TRY(hipMemsetAsync(cand, 0, (size_t)num_segments * CAND_WORDS * sizeof(int), as_stream(stream)));
+  return MSCNN_OK;
+}
+
+// everything the two add calls refuse alike, then one launch per 32 segments
+static int det_cand_launch(const char* name, const DetSource* src, int num_sources, const mscnn_detections_desc* desc,
+                           const mscnn_detections_view* view, float det_thr, const mscnn_nms_params& nms, int pass, int num_images, int C,
+                           int R_all, void* cand, int cand_cap, void* stream) {
+  const int K = num_sources * C;
+  MSCNN_REQUIRE((long)num_images * K <= (long)(1 << 24), "%s: %d images x %d slots", name, num_images, K);
+  const int S = num_images * K;
+  MSCNN_REQUIRE(cand_cap >= 1, "%s: cand_cap %d", name, cand_cap);
+  MSCNN_REQUIRE(cand_shape_ok(S, cand_cap), "%s: %d segments x %d slots is past 2^31 - 1", name, S, cand_cap);
+  MSCNN_REQUIRE_ALIGNED(cand, 16, "detections_candidates: cand");
+  MSCNN_REQUIRE(pass >= 0 && pass <= 127, "%s: pass %d (0 .. 127: the tag is (pass << 24) | row)", name, pass);
+  MSCNN_REQUIRE(R_all >= 1, "%s: R_all = %d (BoxOutput emits at least one row)", name, R_all);
+  MSCNN_REQUIRE(R_all < (1 << 24), "%s: R_all = %d rows do not fit the tag's 24 row bits", name, R_all);
+  for (int s = 0; s < S; ++s) {
+    MSCNN_REQUIRE(desc[s].ratio_h > 0 && desc[s].ratio_w > 0, "%s: segment %d: ratios %g x %g (positive numbers)", name, s, desc[s].ratio_h,
+                  desc[s].ratio_w);
+  }
+  for (int i = 0; view && i < num_images; ++i) {
+    MSCNN_REQUIRE(std::isfinite(view[i].off_x) && std::isfinite(view[i].off_y), "%s: image %d: view offset (%g, %g) is not finite", name, i,
+                  view[i].off_x, view[i].off_y);
+    MSCNN_REQUIRE(view[i].flip_x == 0 || view[i].flip_x == 1, "%s: image %d: flip_x %d (0 or 1)", name, i, view[i].flip_x);
+  }
+  hipStream_t st = as_stream(stream);
+  DetCandArgs a = {};
+  a.R_all = R_all; a.slots_per_image = K; a.classes_per_source = C; a.cand_cap = cand_cap; a.num_segs = S; a.pass = pass;
+  a.cand = static_cast<char*>(cand);
+  a.nms = det_nms_of(nms);
+  for (int o = 0; o < num_sources; ++o) a.src[o] = src[o];
+  for (int s0 = 0; s0 < S; s0 += kSegsPerLaunch) {
+    const int ns = S - s0 < kSegsPerLaunch ? S - s0 : kSegsPerLaunch;
+    a.s0 = s0;
+    for (int j = 0; j < ns; ++j) {
+      a.seg[j] = det_seg_of(desc[s0 + j], src[0].cascade, det_thr);
+      a.view[j] = DetView{0.0, 0.0, 0, 0};
+      if (view) { const mscnn_detections_view& v = view[(s0 + j) / K]; a.view[j] = DetView{v.off_x, v.off_y, v.flip_x, 1}; }
+    }
+    if (nms_has_thr(nms)) det_cand_add_thr_kernel<<<ns, kCandThreads, 0, st>>>(a);
+    else det_cand_add_kernel<<<ns, kCandThreads, 0, st>>>(a);
+    MSCNN_POST_LAUNCH();
+  }
+  return MSCNN_OK;
+}
+
+extern "C" int mscnn_detections_candidates_add(const mscnn_detections_desc* desc, const mscnn_detections_view* view,
+                                               const mscnn_nms_params* nms_in, int pass, int num_images, int num_classes,
+                                               const float* bbox_pred, const float* cls_pred, const float* props, int R_all, void* cand,
+                                               int cand_cap, void* stream) {
+  mscnn_nms_params nms;
+  if (int rc = mscnn_nms_params_resolve(nms_in, &nms)) return rc;
+  MSCNN_REQUIRE(desc && cand && bbox_pred && cls_pred && props, "detections_candidates_add: null pointer");
+  MSCNN_REQUIRE(num_images >= 1 && num_classes >= 1, "detections_candidates_add: %d images x %d classes", num_images, num_classes);
+  MSCNN_REQUIRE((long)num_images * num_classes <= (long)(1 << 24), "detections_candidates_add: %d images x %d classes", num_images, num_classes);
+  const int S = num_images * num_classes;
+  const int ncls = desc[0].ncls;
+  for (int s = 0; s < S; ++s)
+    MSCNN_REQUIRE(desc[s].ncls == ncls && desc[s].cls_id >= 1 && desc[s].cls_id <= ncls && ncls >= 2,
+                  "detections_candidates_add: segment %d: cls_id %d of %d", s, desc[s].cls_id, desc[s].ncls);
+  const DetSource src = {bbox_pred, cls_pred, props, ncls, 0};
+  return det_cand_launch("detections_candidates_add", &src, 1, desc, view, 0.f, nms, pass, num_images, num_classes, R_all, cand, cand_cap,
+                         stream);
+}
+
+extern "C" int mscnn_detections_candidates_cascade_add(const mscnn_detections_desc* desc, const mscnn_detections_view* view, float det_thr,
+                                                       const mscnn_nms_params* nms_in, int pass, int num_images, int num_outputs,
+                                                       int num_classes, const mscnn_cascade_output* outputs, int R_all, void* cand,
+                                                       int cand_cap, void* stream) {
+  mscnn_nms_params nms;
+  if (int rc = mscnn_nms_params_resolve(nms_in, &nms)) return rc;
+  MSCNN_REQUIRE(nms.det_thr == 0.f, "detections_candidates_cascade_add: nms params det_thr %g is the plain stage's: the cascade stage takes "
+                "its det_thr as an argument", (double)nms.det_thr);
+  MSCNN_REQUIRE(num_outputs >= 1 && num_outputs <= kCascadeMaxOutputs, "detections_candidates_cascade_add: %d cascade outputs (1 .. %d)",
+                num_outputs, kCascadeMaxOutputs);
+  MSCNN_REQUIRE(desc && outputs && cand, "detections_candidates_cascade_add: null pointer");
+  MSCNN_REQUIRE(num_images >= 1 && num_classes >= 1, "detections_candidates_cascade_add: %d images x %d classes", num_images, num_classes);
+  for (int o = 0; o < num_outputs; ++o) {
+    MSCNN_REQUIRE(outputs[o].boxes && outputs[o].cls_prob && outputs[o].props, "detections_candidates_cascade_add: output %d of %d: null pointer",
+                  o, num_outputs);
+    MSCNN_REQUIRE(outputs[o].ncls >= 2, "detections_candidates_cascade_add: output %d: %d probability columns", o, outputs[o].ncls);
+  }
+  const int K = num_outputs * num_classes;
+  MSCNN_REQUIRE((long)num_images * K <= (long)(1 << 24), "detections_candidates_cascade_add: %d images x %d outputs x %d classes", num_images,
+                num_outputs, num_classes);
+  const int S = num_images * K;
+  for (int s = 0; s < S; ++s) {
+    const int o = (s % K) / num_classes;
+    MSCNN_REQUIRE(desc[s].cls_id >= 1 && desc[s].cls_id <= outputs[o].ncls,
+                  "detections_candidates_cascade_add: segment %d (output %d): cls_id %d of %d", s, o, desc[s].cls_id, outputs[o].ncls);
+  }
+  DetSource src[kCascadeMaxOutputs];
+  for (int o = 0; o < num_outputs; ++o) src[o] = DetSource{outputs[o].boxes, outputs[o].cls_prob, outputs[o].props, outputs[o].ncls, 1};
+  return det_cand_launch("detections_candidates_cascade_add", src, num_outputs, desc, view, det_thr, nms, pass, num_images, num_classes, R_all,
+                         cand, cand_cap, stream);
+}
+
+extern "C" size_t mscnn_detections_merge_workspace_bytes(int num_segments, int cand_cap) {
+  if (!cand_shape_ok(num_segments, cand_cap)) return 0;
+  if (cand_cap > kMaxK) return det_layout(cand_cap).total;      // one list at a time
+  return cand_al((size_t)num_segments * MRG_WORDS * sizeof(int)) +
+         (size_t)num_segments * (det_merge_seg_box_bytes(cand_cap) + det_merge_seg_mask_bytes(cand_cap));
+}
+
+extern "C" int mscnn_detections_merge_fwd(const double* nms_overlap, const mscnn_nms_params* nms_in, int num_segments, void* cand,
+                                          int cand_cap, void* pack_dev, void* workspace, size_t workspace_bytes, void* stream) {
+  mscnn_nms_params nms;
+  if (int rc = mscnn_nms_params_resolve(nms_in, &nms)) return rc;
+  MSCNN_REQUIRE(nms_overlap && cand && pack_dev && workspace, "detections_merge: null pointer");
+  const int S = num_segments;
+  MSCNN_REQUIRE(S >= 1, "detections_merge: %d segments", S);
+  MSCNN_REQUIRE(cand_cap >= 1, "detections_merge: cand_cap %d", cand_cap);
+  MSCNN_REQUIRE(cand_shape_ok(S, cand_cap), "detections_merge: %d segments x %d slots is past 2^31 - 1", S, cand_cap);
+  for (int s = 0; s < S; ++s) MSCNN_REQUIRE(!(nms_overlap[s] != nms_overlap[s]), "detections_merge: segment %d: nms_overlap is NaN", s);
+  MSCNN_REQUIRE_ALIGNED(cand, 16, "detections_merge: cand");
+  MSCNN_REQUIRE_ALIGNED(workspace, 16, "detections_merge: workspace");
+  MSCNN_REQUIRE_ALIGNED(pack_dev, 16, "detections_merge: pack_dev");
+  const bool big = cand_cap > kMaxK;
+  // (thr and det_thr were applied by the add calls: of the setting, type and ovr_dnm are read here)
+  MSCNN_REQUIRE(!big || (nms.type == MSCNN_NMS_TYPE_MAXG && nms.ovr_dnm == MSCNN_NMS_OVR_UNION),
+                "detections_merge: lists of %d slots > %d run the tiled path, which has the default type and ovr_dnm only (got type %d, "
+                "ovr_dnm %d)", cand_cap, kMaxK, nms.type, nms.ovr_dnm);
+  const size_t need = mscnn_detections_merge_workspace_bytes(S, cand_cap);
+  if (workspace_bytes < need) {
+    set_error("detections_merge: workspace %zu < %zu", workspace_bytes, need);
+    return MSCNN_ERR_WORKSPACE;
+  }
+  hipStream_t st = as_stream(stream);
+  const mscnn_multi_pack_layout PL = mscnn_multi_pack_layout_of(S, S * cand_cap);
+  char* pk = static_cast<char*>(pack_dev);
+  int* hdr = reinterpret_cast<int*>(pk);
+  double* dets = reinterpret_cast<double*>(pk + PL.dets);
+  int* ids = reinterpret_cast<int*>(pk + PL.ids);
+  char* ws = static_cast<char*>(workspace);
+  if (!big) {
+    DetMergeArgs a = {};
+    a.cand_cap = cand_cap; a.wpr = (cand_cap + 63) / 64; a.num_segs = S;
+    a.cand = static_cast<char*>(cand); a.ws = ws;
+    a.seg_stride_box = det_merge_seg_box_bytes(cand_cap); a.seg_stride_mask = det_merge_seg_mask_bytes(cand_cap);
+    a.hdr = hdr; a.dets = dets; a.ids = ids;
+    for (int s0 = 0; s0 < S; s0 += kSegsPerLaunch) {
+      const int ns = S - s0 < kSegsPerLaunch ? S - s0 : kSegsPerLaunch;
+      a.s0 = s0;
+      for (int j = 0; j < ns; ++j) a.overlap[j] = nms_overlap[s0 + j];
+      det_merge_sort_kernel<<<ns, kSortThreads, 0, st>>>(a);
+      MSCNN_POST_LAUNCH();
+      if (nms.ovr_dnm == MSCNN_NMS_OVR_MIN) det_merge_mask_min_kernel<<<dim3(a.wpr, a.wpr, ns), 256, 0, st>>>(a);
+      else det_merge_mask_kernel<<<dim3(a.wpr, a.wpr, ns), 256, 0, st>>>(a);
+      MSCNN_POST_LAUNCH();
+      const size_t lds = (size_t)2 * 64 * a.wpr * sizeof(u64);
+      if (nms.type == MSCNN_NMS_TYPE_MAXG) det_merge_scan_emit_kernel<<<ns, 256, lds, st>>>(a);
+      else det_merge_color_emit_kernel<<<ns, 256, lds, st>>>(a);
+      MSCNN_POST_LAUNCH();
+    }
+    return MSCNN_OK;
+  }
+  // one list at a time on the tiled kernels; the list's length comes from its device count (big_nms_tiles' total_k)
+  const DetLayout L = det_layout(cand_cap);
+  const DetCand c = det_cand_of(static_cast<char*>(cand), S, cand_cap);
+  int* cnt = reinterpret_cast<int*>(ws + L.cnt);
+  DetBox* sbox = reinterpret_cast<DetBox*>(ws + L.sbox);
+  double* sprob = reinterpret_cast<double*>(ws + L.sprob);
+  int* ssrc = reinterpret_cast<int*>(ws + L.ssrc);
+  u64* mask = reinterpret_cast<u64*>(ws + L.mask);
+  u64* keys = reinterpret_cast<u64*>(ws + L.keys);
+  int* kidx = reinterpret_cast<int*>(ws + L.kidx);
+  for (int s = 0; s < S; ++s) {
+    const size_t list = (size_t)s * (size_t)cand_cap;
+    det_merge_keys_big_kernel<<<cdiv(L.sortP, 256), 256, 0, st>>>(c.cnt + CAND_WORDS * (size_t)s, c.prob + list, cand_cap, keys, L.sortP, cnt);
+    MSCNN_POST_LAUNCH();
+    MSCNN_HIP_TRY(big_sort_desc(keys, L.sortP, st));
+    det_merge_gather_big_kernel<<<cdiv(cand_cap, 256), 256, 0, st>>>(keys, c.box + list, c.prob + list, c.tag + list, sbox, sprob, ssrc, cnt);
+    MSCNN_POST_LAUNCH();
+    const double overlap = nms_overlap[s];
+    auto launch_mask = [&](const DetBox* tile, const int* tile_n) {
+      det_mask_kernel<<<dim3(kTileWords, kTileWords), 256, 0, st>>>(tile, tile_n, overlap, mask, kTileWords);
+    };
+    MSCNN_HIP_TRY((big_nms_tiles<DetTr>(sbox, cnt + DC_N, 0, cand_cap, DetTr::Params{overlap}, mask, reinterpret_cast<u64*>(ws + L.rinit), kidx,
+                                        reinterpret_cast<DetBox*>(ws + L.kbox), cnt + DC_BIG, launch_mask, st)));
+    det_emit_big_kernel<<<cdiv(cand_cap, 256), 256, 0, st>>>(kidx, cnt + DC_BIG, sbox, sprob, ssrc, dets + 5 * list, ids + list,
+                                                             hdr + MSCNN_MULTI_PACK_WORDS * (size_t)(1 + s));
+    MSCNN_POST_LAUNCH();
+  }
+  det_merge_table_big_kernel<<<cdiv(S, 256), 256, 0, st>>>(c.cnt, S, cand_cap, hdr);
+  MSCNN_POST_LAUNCH();
+  return MSCNN_OK;
 }

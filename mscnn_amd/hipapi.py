@@ -213,6 +213,17 @@ def lib():
                                                      [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p])
         L.mscnn_detections_cascade_multi_nms_fwd.argtypes = ([C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                                               C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p])
+        L.mscnn_detections_candidates_bytes.restype = C.c_size_t
+        L.mscnn_detections_candidates_bytes.argtypes = [C.c_int, C.c_int]
+        L.mscnn_detections_candidates_reset.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.mscnn_detections_candidates_add.argtypes = ([C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p] * 3 +
+                                                      [C.c_int, C.c_void_p, C.c_int, C.c_void_p])
+        L.mscnn_detections_candidates_cascade_add.argtypes = ([C.c_void_p, C.c_void_p, C.c_float, C.c_void_p] + [C.c_int] * 4 +
+                                                              [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p])
+        L.mscnn_detections_merge_workspace_bytes.restype = C.c_size_t
+        L.mscnn_detections_merge_workspace_bytes.argtypes = [C.c_int, C.c_int]
+        L.mscnn_detections_merge_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                 C.c_void_p]
         L.mscnn_proposals_multi_pack_bytes.restype = C.c_size_t
         L.mscnn_proposals_multi_pack_bytes.argtypes = [C.c_int, C.c_int]
         L.mscnn_proposals_multi_fwd.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
@@ -932,6 +943,104 @@ def detections_cascade_multi(outputs, num_images, segments, det_thr=0.0, max_row
                                                             cap, _dev(ws), C.c_size_t(wb), _stream()))
     out = _read_multi_pack(pack, S, K, R, cap, "detections_cascade_multi")
     return (out, pack.cpu().numpy()) if raw_pack else out
+
+
+# ---- several forwards of an image, one NMS (mscnn_detections_candidates_*, mscnn_detections_merge_fwd) ----
+class DetectionsView(C.Structure):
+    """mscnn_detections_view: where a forward's view of an image lies in the original image."""
+    _fields_ = [("off_x", C.c_double), ("off_y", C.c_double), ("flip_x", C.c_int)]
+
+
+def _view_array(views, num_images):
+    """views: None (NULL, the identity) or one (off_x, off_y, flip_x) per image."""
+    if views is None:
+        return None
+    if len(views) != num_images:
+        raise MscnnError(f"candidates: {len(views)} views for {num_images} images")
+    arr = (DetectionsView * max(num_images, 1))()
+    for i, (ox, oy, fl) in enumerate(views):
+        arr[i].off_x, arr[i].off_y, arr[i].flip_x = float(ox), float(oy), int(fl)
+    return arr
+
+
+class Candidates:
+    """The candidate lists of S segments with cand_cap slots each: reset on creation; add() / cascade_add() after each forward (the
+    pass index counts them), merge() runs the NMS over each list.  Every buffer comes from `torch` of this module."""
+
+    def __init__(self, num_segments, cand_cap, device="cuda"):
+        self.S, self.cap, self.passes = num_segments, cand_cap, 0
+        nbytes = lib().mscnn_detections_candidates_bytes(num_segments, cand_cap)
+        if nbytes == 0:
+            raise MscnnError(f"candidates: {num_segments} segments x {cand_cap} slots")
+        self.buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        _check(lib().mscnn_detections_candidates_reset(_dev(self.buf), num_segments, cand_cap, _stream()))
+        self.overlap = None
+
+    def _descs(self, segments, ncls_of):
+        if len(segments) != self.S:
+            raise MscnnError(f"candidates: {len(segments)} segments, the lists were made for {self.S}")
+        descs = (DetectionsDesc * self.S)()
+        for s, kw in enumerate(segments):
+            _fill_desc(descs[s], ncls_of(s), kw)
+        if self.overlap is None:
+            self.overlap = [d.nms_overlap for d in descs]
+        return descs
+
+    def add(self, bbox_pred, cls_pred, props, num_images, segments, views=None, nms=NMS_NULL, pass_index=None):
+        """mscnn_detections_candidates_add: segments as in detections_multi; views: None or [(off_x, off_y, flip_x)] per image."""
+        descs = self._descs(segments, lambda s: cls_pred.shape[1])
+        k = self.passes if pass_index is None else pass_index
+        _check(lib().mscnn_detections_candidates_add(descs, _view_array(views, num_images), _nms_ref(nms), k, num_images, self.S // num_images,
+                                                     _dev(bbox_pred), _dev(cls_pred), _dev(props), props.shape[0], _dev(self.buf), self.cap,
+                                                     _stream()))
+        self.passes += 1
+
+    def cascade_add(self, outputs, num_images, segments, det_thr=0.0, views=None, nms=NMS_NULL, pass_index=None):
+        """mscnn_detections_candidates_cascade_add: outputs and segments as in detections_cascade_multi."""
+        O = len(outputs)
+        K = self.S // num_images
+        Cn = K // max(O, 1)
+        outs = (CascadeOutput * max(O, 1))()
+        for o, (boxes, cls_prob, props) in enumerate(outputs):
+            outs[o].boxes, outs[o].cls_prob, outs[o].props, outs[o].ncls = _dev(boxes).value, _dev(cls_prob).value, _dev(props).value, cls_prob.shape[1]
+        descs = self._descs(segments, lambda s: outs[(s % K) // Cn].ncls)
+        k = self.passes if pass_index is None else pass_index
+        _check(lib().mscnn_detections_candidates_cascade_add(descs, _view_array(views, num_images), C.c_float(det_thr), _nms_ref(nms), k,
+                                                             num_images, O, Cn, outs, outputs[0][2].shape[0], _dev(self.buf), self.cap, _stream()))
+        self.passes += 1
+
+    def counts(self):
+        """[(rows that wanted in, overflow flag)] per segment, read from the device."""
+        return self.buf[:8 * self.S].cpu().numpy().view(np.int32).reshape(self.S, 2).tolist()
+
+    def merge(self, nms=NMS_NULL, nms_overlap=None, raw_pack=False, pack=None, ws=None):
+        """mscnn_detections_merge_fwd.  Returns [(dets[D,5], tags[D], candidates)] per segment ((None, None, candidates): the list
+        overflowed); raw_pack: (that, the pack's bytes as a numpy array -- zero-filled before the call unless `pack` is given)."""
+        S, cap = self.S, self.cap
+        ov = self.overlap if nms_overlap is None else nms_overlap
+        ov = (C.c_double * S)(*[float(v) for v in (ov if ov is not None else [0.5] * S)])
+        nbytes = lib().mscnn_detections_multi_pack_bytes(S, S * cap)
+        if pack is None:
+            pack = torch.zeros(nbytes, dtype=torch.uint8, device=self.buf.device)
+        wb = lib().mscnn_detections_merge_workspace_bytes(S, cap)
+        if ws is None:
+            ws = torch.empty(max(wb, 1), dtype=torch.uint8, device=self.buf.device)
+        _check(lib().mscnn_detections_merge_fwd(ov, _nms_ref(nms), S, _dev(self.buf), cap, _dev(pack), _dev(ws), C.c_size_t(ws.numel()),
+                                                _stream()))
+        h = pack[:nbytes].cpu().numpy()
+        table = 16 * (S + 1)
+        hdr = h[:table].view(np.int32).reshape(S + 1, 4)
+        if list(hdr[0]) != [S, cap, S * cap, 0]:
+            raise MscnnError(f"detections_merge: pack header {hdr[0].tolist()}")
+        dets = h[table:table + 40 * S * cap].view(np.float64).reshape(-1, 5)
+        tags = h[table + 40 * S * cap:table + 44 * S * cap].view(np.int32)
+        out = []
+        for s in range(S):
+            cnt, cands, row0, zero = (int(v) for v in hdr[1 + s])
+            if row0 != s * cap or zero != 0:
+                raise MscnnError(f"detections_merge: table entry {s}: {hdr[1 + s].tolist()}")
+            out.append((dets[row0:row0 + cnt].copy(), tags[row0:row0 + cnt].copy(), cands) if cnt >= 0 else (None, None, cands))
+        return (out, h) if raw_pack else out
 
 
 # ---- health of the plane-GEMM kernel's stream-K hand-off (mscnn_hip.h) ----

@@ -33,6 +33,14 @@ struct mscnn_net {
   // mscnn_net_set_nms: bbNms's knobs for every detect call from now on (pNms at the top of the reference scripts)
   mscnn_nms_params nms;
   bool nms_set = false;                    // false: the defaults -- the calls hand the ops NULL and run what they always ran
+  // mscnn_net_detect_merge_*: the candidate lists of the forwards added since _begin (mscnn_hip.h: mscnn_detections_candidates_*)
+  struct Merge {
+    bool open = false;
+    int images = 0, slots = 0, cand_cap = 0, passes = 0, handoff_errors = 0;      // slots: per image (classes, or outputs x classes)
+    long rows = 0;                         // sum of R_all over the adds so far: the host-known bound on any list
+    std::vector<double> overlap;           // per segment, from the first add
+    caffe::DeviceBuffer cand;
+  } merge;
   ~mscnn_net() {
     if (det_host) (void)hipHostFree(det_host);
     for (Slot& sl : slot) {
@@ -1152,6 +1160,176 @@ int mscnn_net_detect_cascade_multi(mscnn_net* n, const mscnn_detect_params* p, i
         },
         [&](int pcap, char* pack_at, char** pack) { return segments_into_pack(n, b.src, desc, num_images, num_classes, det_thr, pcap, pack_at, pack); },
         dets_host, ids_host, cap, seg_dets, image_rois);
+  });
+}
+
+// ---- several forwards of an image, one NMS (mscnn_hip.h: mscnn_detections_candidates_*, mscnn_detections_merge_fwd) -------------------
+int mscnn_net_detect_merge_begin(mscnn_net* n, int num_images, int num_classes, int cand_cap) {
+  return guarded([&] {
+    mscnn_net::Merge& m = n->merge;
+    CHECK(!m.open) << "detect_merge_begin: a merge of " << m.images << " images x " << m.slots << " slots with " << m.passes
+                   << " forwards added is open (call mscnn_net_detect_merge_end first)";
+    CHECK(num_images >= 1 && num_classes >= 1) << "detect_merge_begin: " << num_images << " images x " << num_classes << " classes";
+    CHECK_GE(cand_cap, 1) << "detect_merge_begin: cand_cap " << cand_cap;
+    const int S = num_images * num_classes;
+    const size_t bytes = mscnn_detections_candidates_bytes(S, cand_cap);
+    CHECK_GT(bytes, 0u) << "detect_merge_begin: " << S << " segments x " << cand_cap << " candidate slots";
+    CHECK_GE(n->device, 0) << "detect_merge_begin: the net was built with device " << n->device << " (graph only): no candidate lists";
+    MSCNN_CHECK(mscnn_detections_candidates_reset(m.cand.Reserve(bytes), S, cand_cap, Caffe::stream()));
+    m.open = true; m.images = num_images; m.slots = num_classes; m.cand_cap = cand_cap; m.passes = 0; m.rows = 0;
+    m.handoff_errors = n->net->handoff_errors();
+    m.overlap.clear();
+  });
+}
+
+// What both add calls check alike before anything is enqueued; R_all = the rows of this forward's ROI blobs.
+static void merge_add_checked(mscnn_net* n, const char* name, const mscnn_detect_params* p, int num_images, int slots, int R_all) {
+  mscnn_net::Merge& m = n->merge;
+  CHECK(p != nullptr) << name << ": null params";
+  CHECK_EQ(slots, m.slots) << name << ": " << slots << " slots per image, the merge was begun with " << m.slots;
+  CHECK_LT(m.passes, 128) << name << ": " << m.passes << " forwards have been added, the tag holds 7 bits of pass";
+  CHECK_LE(m.rows + R_all, (long)m.cand_cap) << name << ": the " << m.passes << " forwards added so far have " << m.rows
+                                             << " ROI rows, this one " << R_all << ": more than cand_cap " << m.cand_cap;
+  const int S = num_images * slots;
+  for (int s = 0; s < S; ++s) {
+    CHECK(!(p[s].nms_overlap != p[s].nms_overlap)) << name << ": segment " << s << ": nms_overlap is NaN";
+    if (m.passes > 0)
+      CHECK(p[s].nms_overlap == m.overlap[s]) << name << ": segment " << s << ": nms_overlap " << p[s].nms_overlap
+                                              << ", the first forward of this merge was added with " << m.overlap[s];
+  }
+}
+static void merge_added(mscnn_net* n, const mscnn_detect_params* p, int S, int R_all) {
+  mscnn_net::Merge& m = n->merge;
+  if (m.passes == 0) { m.overlap.resize(S); for (int s = 0; s < S; ++s) m.overlap[s] = p[s].nms_overlap; }
+  ++m.passes;
+  m.rows += R_all;
+}
+static int merge_input_images(mscnn_net* n) {
+  return n->net->num_inputs() > 0 && n->net->input_blobs()[0]->num_axes() == 4 ? n->net->input_blobs()[0]->num() : 1;
+}
+
+int mscnn_net_detect_merge_add(mscnn_net* n, const mscnn_detect_params* p, const mscnn_detections_view* view) {
+  return guarded([&] {
+    mscnn_net::Merge& m = n->merge;
+    CHECK(m.open) << "detect_merge_add: no merge is open (call mscnn_net_detect_merge_begin first)";
+    const int num = merge_input_images(n);
+    CHECK_EQ(m.images, num) << "detect_merge_add: the merge was begun with " << m.images << " images but the net's input holds " << num;
+    CHECK(n->net->has_blob("bbox_pred") && n->net->has_blob("cls_pred") && n->net->has_blob("proposals_score"))
+        << "detect_merge_add: net has no bbox_pred / cls_pred / proposals_score outputs";
+    auto bbox = n->net->blob_by_name("bbox_pred");
+    auto cls = n->net->blob_by_name("cls_pred");
+    auto props = n->net->blob_by_name("proposals_score");
+    const int R_all = props->num();
+    CHECK_GE(R_all, 1);
+    CHECK(bbox->num() == R_all && cls->num() == R_all) << "detect_merge_add: bbox_pred has " << bbox->num() << " rows, cls_pred " << cls->num()
+                                                        << ", proposals_score " << R_all;
+    const int ncls = cls->count() / R_all;
+    CHECK_EQ(bbox->count() / R_all, 4 * ncls);
+    merge_add_checked(n, "detect_merge_add", p, m.images, m.slots, R_all);
+    const int S = m.images * m.slots;
+    std::vector<mscnn_detections_desc> desc(S);
+    for (int s = 0; s < S; ++s) {
+      mscnn_detections_desc& d = desc[s];
+      d.ncls = ncls;
+      d.cls_id = p[s].cls_id;
+      CHECK(d.cls_id >= 1 && d.cls_id <= ncls) << "detect_merge_add: segment " << s << ": cls_id " << d.cls_id << " of " << ncls;
+      for (int k = 0; k < 4; ++k) { d.bbox_mean[k] = p[s].bbox_mean[k]; d.bbox_std[k] = p[s].bbox_std[k]; }
+      d.proposal_thr = p[s].proposal_thr;
+      d.ratio_h = p[s].ratio_h; d.ratio_w = p[s].ratio_w; d.org_h = p[s].org_h; d.org_w = p[s].org_w; d.nms_overlap = p[s].nms_overlap;
+    }
+    MSCNN_CHECK(mscnn_detections_candidates_add(desc.data(), view, nms_arg(n, false), m.passes, m.images, m.slots, bbox->gpu_data(),
+                                                cls->gpu_data(), props->gpu_data(), R_all, m.cand.get(), m.cand_cap, Caffe::stream()));
+    merge_added(n, p, S, R_all);
+  });
+}
+
+int mscnn_net_detect_cascade_merge_add(mscnn_net* n, const mscnn_detect_params* p, const mscnn_detections_view* view, int num_outputs,
+                                       const char* const* bbox_blobs, const char* const* prob_blobs, const char* const* proposal_blobs,
+                                       float det_thr) {
+  return guarded([&] {
+    mscnn_net::Merge& m = n->merge;
+    CHECK(m.open) << "detect_cascade_merge_add: no merge is open (call mscnn_net_detect_merge_begin first)";
+    const int num = merge_input_images(n);
+    CHECK_EQ(m.images, num) << "detect_cascade_merge_add: the merge was begun with " << m.images << " images but the net's input holds " << num;
+    const CascadeBlobs b = cascade_blobs(n, num_outputs, bbox_blobs, prob_blobs, proposal_blobs);
+    CHECK_EQ(m.slots % num_outputs, 0) << "detect_cascade_merge_add: the merge was begun with " << m.slots << " slots per image, not a multiple of "
+                                       << num_outputs << " cascade outputs";
+    const int C = m.slots / num_outputs;
+    merge_add_checked(n, "detect_cascade_merge_add", p, m.images, m.slots, b.R_all);
+    const int S = m.images * m.slots;
+    const auto desc = cascade_descs(n, p, m.images, num_outputs, C, b, m.slots * b.R_all);
+    std::vector<mscnn_cascade_output> outs(num_outputs);
+    for (int o = 0; o < num_outputs; ++o)
+      outs[o] = mscnn_cascade_output{b.src[o].boxes->gpu_data(), b.src[o].cls->gpu_data(), b.src[o].props->gpu_data(), b.src[o].ncls};
+    MSCNN_CHECK(mscnn_detections_candidates_cascade_add(desc.data(), view, det_thr, nms_arg(n, true), m.passes, m.images, num_outputs, C,
+                                                        outs.data(), b.R_all, m.cand.get(), m.cand_cap, Caffe::stream()));
+    merge_added(n, p, S, b.R_all);
+  });
+}
+
+// The merge pack on the host -> segment after segment; the int column is a tag (pass << 24 | row), which mscnn_net_unpack_detections_multi
+// would take for an id relative to row0: this pack has its own reader.
+static void unpack_merge(const void* pack_host, int S, int cand_cap, double* dets_host, int* pass_host, int* row_host, int out_cap,
+                         int* seg_dets, int* seg_candidates) {
+  const char* hp = static_cast<const char*>(pack_host);
+  const int* hdr = reinterpret_cast<const int*>(hp);
+  CHECK(hdr[0] == S && hdr[1] == cand_cap && hdr[2] == S * cand_cap && hdr[3] == 0)
+      << "detect_merge_end: the pack header was not written or is another merge's: {" << hdr[0] << ", " << hdr[1] << ", " << hdr[2] << ", "
+      << hdr[3] << "} for " << S << " segments x " << cand_cap << " slots";
+  long D = 0;
+  for (int s = 0; s < S; ++s) {
+    const int* e = hdr + MSCNN_MULTI_PACK_WORDS * (size_t)(1 + s);
+    CHECK(e[0] != -1) << "detect_merge_end: segment " << s << ": " << e[1] << " candidates wanted into a list of " << cand_cap << " slots";
+    CHECK(e[0] >= 0 && e[0] <= e[1] && e[1] <= cand_cap && e[2] == s * cand_cap && e[3] == 0)
+        << "corrupt merge pack: segment " << s << " has " << e[0] << " detections of " << e[1] << " candidates at row " << e[2];
+    D += e[0];
+  }
+  CHECK_LE(D, (long)out_cap) << "detect_merge_end: detections buffer holds " << out_cap << " rows, the " << S << " segments have " << D;
+  CHECK(D == 0 || dets_host) << "detect_merge_end: null dets buffer";
+  const mscnn_multi_pack_layout L = mscnn_multi_pack_layout_of(S, S * cand_cap);
+  const double* pd = reinterpret_cast<const double*>(hp + L.dets);
+  const int* pi = reinterpret_cast<const int*>(hp + L.ids);
+  size_t o = 0;
+  for (int s = 0; s < S; ++s) {
+    const int* e = hdr + MSCNN_MULTI_PACK_WORDS * (size_t)(1 + s);
+    const int cnt = e[0];
+    const size_t slot = (size_t)e[2];
+    if (cnt > 0) std::memcpy(dets_host + 5 * o, pd + 5 * slot, sizeof(double) * 5 * cnt);
+    for (int k = 0; k < cnt; ++k) {
+      const int tag = pi[slot + k];
+      if (pass_host) pass_host[o + k] = tag >> 24;
+      if (row_host) row_host[o + k] = tag & 0xffffff;
+    }
+    seg_dets[s] = cnt;
+    if (seg_candidates) seg_candidates[s] = e[1];
+    o += cnt;
+  }
+}
+
+int mscnn_net_detect_merge_end(mscnn_net* n, double* dets_host, int* pass_host, int* row_host, int cap, int* seg_dets, int* seg_candidates) {
+  return guarded([&] {
+    mscnn_net::Merge& m = n->merge;
+    CHECK(m.open) << "detect_merge_end: no merge is open (call mscnn_net_detect_merge_begin first)";
+    m.open = false;      // (whatever happens from here on: the merge is closed)
+    CHECK(seg_dets != nullptr) << "detect_merge_end: null seg_dets";
+    CHECK_GE(m.passes, 1) << "detect_merge_end: no forward has been added since mscnn_net_detect_merge_begin";
+    const int S = m.images * m.slots;
+    hipStream_t st = (hipStream_t)Caffe::stream();
+    const size_t total = mscnn_multi_pack_layout_of(S, S * m.cand_cap).total;
+    ensure_det_host(n, total);
+    *static_cast<volatile int*>(n->det_host) = -1;      // the header's first word: the kernels must have written it
+    const size_t wb = mscnn_detections_merge_workspace_bytes(S, m.cand_cap);
+    void* ws = n->det_ws.Reserve(wb);
+    // (the kernels only ever WRITE the pack: they write it straight into host-coherent pinned memory, as the blocking detect calls do)
+    MSCNN_CHECK(mscnn_detections_merge_fwd(m.overlap.data(), nms_arg(n, false), S, m.cand.get(), m.cand_cap, n->det_host_dev, ws, wb, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    // A stream-K hand-off that timed out in one of the forwards of this merge can not be answered by a re-run here: the input blob
+    // holds the last forward only.  As mscnn_net_detect_end: whole tiles from now on, and the caller submits the forwards again.
+    const bool seen_now = n->net->HandoffEventSeen();
+    CHECK(!seen_now && n->net->handoff_errors() == m.handoff_errors)
+        << "a stream-K hand-off timed out in a forward of this merge (mscnn_net_handoff_state): whole-tile scheduling from now on; the "
+           "forwards added since mscnn_net_detect_merge_begin must be run and added again";
+    unpack_merge(n->det_host, S, m.cand_cap, dets_host, pass_host, row_host, cap, seg_dets, seg_candidates);
   });
 }
 

@@ -28,6 +28,11 @@ class NmsParams(C.Structure):
     _fields_ = [("type", C.c_int), ("ovr_dnm", C.c_int), ("thr", C.c_double), ("det_thr", C.c_float)]
 
 
+class DetectionsView(C.Structure):
+    """mscnn_detections_view (include/mscnn_net.h): where a forward's view of an image lies in the original image."""
+    _fields_ = [("off_x", C.c_double), ("off_y", C.c_double), ("flip_x", C.c_int)]
+
+
 NMS_TYPES = ("maxg", "max", "ms", "cover", "none")      # (the last three exist to be refused by name)
 OVR_DNMS = ("union", "min")
 
@@ -95,6 +100,9 @@ def lib():
             "mscnn_net_proposals_multi": [vp, vp, ci, vp, vp, ci, vp, vp], "mscnn_net_proposals_multi_device": [vp, vp, ci, ci, vp],
             "mscnn_net_forward_proposals": [vp, vp],
             "mscnn_net_forward_rois": [vp, vp, ci, ci, ci, vp, ci, ci, vp], "mscnn_net_forward_rois_layers": [vp, vp, vp],
+            "mscnn_net_detect_merge_begin": [vp, ci, ci, ci], "mscnn_net_detect_merge_add": [vp, vp, vp],
+            "mscnn_net_detect_cascade_merge_add": [vp, vp, vp, ci, vp, vp, vp, C.c_float],
+            "mscnn_net_detect_merge_end": [vp, vp, vp, vp, ci, vp, vp],
         }
         for name, args in sig.items():
             getattr(L, name).argtypes = args
@@ -552,6 +560,62 @@ class Net:
         _check(lib().mscnn_net_detect_multi(self._h, p, B, Cn, dets.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p), cap,
                                             seg.ctypes.data_as(C.c_void_p), rois.ctypes.data_as(C.c_void_p)))
         return _split_segments(dets, ids, seg, B, Cn), rois.tolist()
+
+    # ---- several forwards of a frame, one NMS (mscnn_net_detect_merge_*)
+    @staticmethod
+    def _views(views, B):
+        """views: None (the identity), or one dict per image with off_x / off_y / flip_x (missing: 0) -> the view array or None."""
+        if views is None:
+            return None
+        if len(views) != B:
+            raise NetError(f"detect_merge: {len(views)} views for {B} images")
+        arr = (DetectionsView * max(B, 1))()
+        for i, v in enumerate(views):
+            arr[i].off_x, arr[i].off_y, arr[i].flip_x = float(v.get("off_x", 0.0)), float(v.get("off_y", 0.0)), int(v.get("flip_x", 0))
+        return arr
+
+    def detect_merge_begin(self, num_images, num_classes, cand_cap):
+        """mscnn_net_detect_merge_begin: reserve and reset num_images x num_classes candidate lists of cand_cap slots (for the cascade
+        form num_classes = outputs x classes).  Then, per forward, detect_merge_add / detect_cascade_merge_add, and detect_merge_end."""
+        _check(lib().mscnn_net_detect_merge_begin(self._h, num_images, num_classes, cand_cap))
+        self._merge_shape = (num_images, num_classes, cand_cap)
+
+    def detect_merge_add(self, params, classes, views=None):
+        """mscnn_net_detect_merge_add after a forward.  params: one dict per image as in detect_multi, describing THIS forward's view
+        (ratios = input size / view size, org_hw = the view's size); views: None or one dict per image (off_x, off_y, flip_x)."""
+        p = self._multi_params(params, classes)
+        _check(lib().mscnn_net_detect_merge_add(self._h, p, self._views(views, len(params))))
+
+    def detect_cascade_merge_add(self, params, outputs, classes, det_thr=0.0, views=None):
+        """mscnn_net_detect_cascade_merge_add: the same for a cascade deploy; outputs, classes, det_thr as in detect_cascade_multi."""
+        p, (bb, pb, qb) = self._cascade_multi_args(params, outputs, classes)
+        _check(lib().mscnn_net_detect_cascade_merge_add(self._h, p, self._views(views, len(params)), len(outputs), bb, pb, qb, det_thr))
+
+    def detect_merge_end(self, cap=None):
+        """mscnn_net_detect_merge_end: one NMS over each list.  Returns ([[(dets[D,5], pass[D], row[D]) per slot] per image],
+        [[candidates per slot] per image]); pass = the add (0-based) a detection came from, row = the row of that forward's ROI
+        blobs.  cap: rows of the host buffers (default: every candidate slot)."""
+        shape = getattr(self, "_merge_shape", None)
+        B, K, cand_cap = shape if shape else (1, 1, 1)
+        self._merge_shape = None
+        S = B * K
+        if cap is None:
+            cap = S * cand_cap
+        dets = np.zeros((max(cap, 1), 5), np.float64)
+        pas = np.zeros(max(cap, 1), np.int32); row = np.zeros(max(cap, 1), np.int32)
+        seg = np.zeros(S, np.int32); cands = np.zeros(S, np.int32)
+        vp = C.c_void_p
+        _check(lib().mscnn_net_detect_merge_end(self._h, dets.ctypes.data_as(vp), pas.ctypes.data_as(vp), row.ctypes.data_as(vp), cap,
+                                                seg.ctypes.data_as(vp), cands.ctypes.data_as(vp)))
+        out, o = [], 0
+        for i in range(B):
+            per = []
+            for k in range(K):
+                d = int(seg[i * K + k])
+                per.append((dets[o:o + d].copy(), pas[o:o + d].copy(), row[o:o + d].copy()))
+                o += d
+            out.append(per)
+        return out, cands.reshape(B, K).tolist()
 
     def detect_multi_device(self, params, classes, cap):
         """mscnn_net_detect_multi_device: the same into the device pack (detect_multi_pack_bytes(B, C, cap) bytes); asynchronous.

@@ -17,7 +17,20 @@ between them stays) and name the setting in the table's header; without them no 
 host (get_blob("proposals_score")) + the numpy restatement of those lines, image after image, against one mscnn_net_proposals_multi --
 both end with every image's proposals on the host, are checked bit for bit every step, and alternate which runs first.  Cases:
 caltech B = 8 and kitti_car 7s-576 B = 2.  Then the step time of the RPN-only run (mscnn_net_forward_proposals) against the whole
-forward on kitti_car 7s-576, B = 1, device idle before and synchronised after each, the two alternating."""
+forward on kitti_car 7s-576, B = 1, device idle before and synchronised after each, the two alternating.
+
+--merge is the merged final stage (several forwards of a frame, one NMS: Net.detect_merge_*) against the host path it replaces, on the
+same forwards: per forward get_blob of the three blobs + the numpy row transform of tests/merge_witness.py (with numpy's own exp: the
+fast form a caller would write), then its sort and NMS -- against one detect_merge_add per forward and one detect_merge_end.  Only the
+final-stage work is timed (host wall time, the device idle before either form starts; the forwards themselves are not), the two forms
+alternate which runs first, and the whole measurement is repeated --rounds times: median of the rounds' medians and their spread.
+Cases: kitti_car 7s-576 at two input sizes plus a mirrored forward, caltech 7s-480 with B = 8 likewise.
+
+--lib path/to/libmscnn_hip.so runs whatever leg is selected with THAT build's kernels under the Net (it is loaded first, so the Net's
+calls bind to it; the per-range op calls of the batched cascade case's per-call form go through hipapi's own handle and stay this
+build's).  --parent-lib path/to/libmscnn_hip.so repeats the selected leg --rounds times in child processes, this build and
+that one alternating, and prints for every timed column both medians, both spreads (max - min over the rounds) and whether this
+build is at or below the parent's median plus the parent's own spread."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -179,7 +192,134 @@ def proposals_leg(a):
     print(f"  {m0:18.3f} {m1:22.3f} {m0 - m1:9.3f}", flush=True)
 
 
+MERGE_CASES = {   # name: model, batch, classes, original image size, the forwards of a frame (H, W, mirrored)
+    "kitti_car-7s576-2scales-flip": ("kitti_car/mscnn-7s-576", 1, [2], (375, 1242), [(576, 1920, False), (576, 1920, True), (384, 1280, False)]),
+    "caltech-7s480-b8-2scales-flip": ("caltech/mscnn-7s-480", 8, [2], (480, 640), [(480, 640, False), (480, 640, True), (384, 512, False)]),
+}
+
+
+def merge_leg(a):
+    import torch
+    sys.path.insert(1, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import merge_witness as mw
+    print(f"# merged final stage per frame group, host wall ms (median over {a.steps} steps after {a.warmup} warm-up; {a.rounds} rounds: median of "
+          f"the medians, spread = max - min), regime {a.regime}{nms_label(a)}")
+    print(f"# {'case':30s} {'B':>2s} {'fwd':>3s} {'cands':>6s} {'dets':>5s} {'get_blob + numpy ms':>20s} {'spread':>7s} {'add x fwd + merge ms':>21s} {'spread':>7s}")
+    for name in a.case or list(MERGE_CASES):
+        model, B, classes, org, forwards = MERGE_CASES[name]
+        n = mnet.Net(prototxt_text=zoo.prototxt(model, batch=B))
+        synth.load_into(n, a.regime)
+        if nms_set(a):
+            n.set_nms(type=a.nms_type, ovr_dnm=a.ovr_dnm)
+        bound = 2000 * B * len(forwards)
+        frames = {}
+        for H, W, flipped in forwards:
+            f = np.concatenate([synth.frame(H, W, seed=1701 + b, org_hw=org) for b in range(B)], 0)
+            frames[(H, W, flipped)] = np.ascontiguousarray(f[..., ::-1]) if flipped else f
+        med = [[], []]
+        cands = dets = 0
+        for rnd in range(a.rounds):
+            t = [[], []]
+            for step in range(a.warmup + a.steps):
+                order = (0, 1) if step % 2 == 0 else (1, 0)
+                dt = [0.0, 0.0]
+                lists = [[[] for _ in classes] for _ in range(B)]
+                n.detect_merge_begin(B, len(classes), bound)
+                for H, W, flipped in forwards:
+                    n.reshape_input("data", (B, 3, H, W))
+                    n.set_blob("data", frames[(H, W, flipped)])
+                    n.forward()
+                    kw = dict(ratios=(H / float(org[0]), W / float(org[1])), org_hw=org)
+                    view = (0.0, 0.0, 1) if flipped else None
+                    for f in order:
+                        torch.cuda.synchronize()      # (untimed: either form starts on an idle device)
+                        t0 = time.perf_counter()
+                        if f == 1:
+                            n.detect_merge_add([kw] * B, classes, views=[dict(flip_x=1)] * B if flipped else None)
+                        else:
+                            R = n.blob_shape("proposals_score")[0]
+                            bp, cp, ps = (n.get_blob(b).reshape(R, -1) for b in ("bbox_pred", "cls_pred", "proposals_score"))
+                            for i in range(B):
+                                r0, r1 = np.searchsorted(ps[:, 0], np.float32(i), "left"), np.searchsorted(ps[:, 0], np.float32(i + 1), "left")
+                                for ci, c in enumerate(classes):
+                                    rows, ids = mw.plain_rows(bp[r0:r1], cp[r0:r1], ps[r0:r1], c, exp=np.exp, **kw)
+                                    lists[i][ci].append((mw.apply_view(rows, org[1], view), ids + r0))
+                        dt[f] += time.perf_counter() - t0
+                res = [None, None]
+                for f in order:
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    if f == 1:
+                        res[1] = n.detect_merge_end()
+                    else:
+                        res[0] = [[mw.merge(lists[i][ci], 0.5, a.nms_type, a.ovr_dnm) for ci in range(len(classes))] for i in range(B)]
+                    dt[f] += time.perf_counter() - t0
+                if step >= a.warmup:
+                    t[0].append(dt[0]); t[1].append(dt[1])
+                    cands = sum(c for row in res[1][1] for c in row)
+                    dets = sum(len(d) for row in res[1][0] for d, _, _ in row)
+                    assert cands == sum(w[3] for row in res[0] for w in row), (name, step)      # (the same rows reach both NMS)
+            for f in (0, 1):
+                med[f].append(1e3 * float(np.median(t[f])))
+        m = [float(np.median(v)) for v in med]
+        sp = [max(v) - min(v) for v in med]
+        print(f"  {name:30s} {B:2d} {len(forwards):3d} {cands:6d} {dets:5d} {m[0]:20.3f} {sp[0]:7.3f} {m[1]:21.3f} {sp[1]:7.3f}", flush=True)
+        del n
+
+
+def use_lib(path):
+    """The kernels of another build of libmscnn_hip.so under this build's Net: loaded first and globally, the Net library's calls bind
+    to it (checked on one final-stage symbol)."""
+    import ctypes as C
+    path = os.path.abspath(path)
+    other = C.CDLL(path, mode=C.RTLD_GLOBAL)
+    mnet.lib()
+    addr = lambda h: C.cast(h.mscnn_detections_multi_nms_fwd, C.c_void_p).value      # noqa: E731
+    assert addr(C.CDLL(None)) == addr(other), "the process did not bind the final stage to " + path
+    print(f"# kernels of {path}")
+
+
+def ab_leg(a, argv):
+    """--parent-lib: the selected leg in child processes, this build and the parent's alternating; every timed column of every row."""
+    import subprocess
+    child = [x for i, x in enumerate(argv) if x != "--parent-lib" and (i == 0 or argv[i - 1] != "--parent-lib")]
+    runs = {"new": [], "parent": []}
+    labels = None
+    for rnd in range(a.rounds):
+        for which in (("new", "parent") if rnd % 2 == 0 else ("parent", "new")):
+            cmd = [sys.executable, os.path.abspath(__file__)] + child + (["--lib", a.parent_lib] if which == "parent" else [])
+            r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+            if r.returncode != 0:
+                sys.exit(f"{' '.join(cmd)} failed with status {r.returncode}:\n{r.stderr[-2000:]}")
+            out = r.stdout
+            rows = {}
+            for line in out.splitlines():
+                tok = line.split()
+                if line.startswith("  ") and tok:
+                    vals = [float(v) for v in tok if "." in v]
+                    rows[tok[0] if "." not in tok[0] else "step-time"] = vals[:-1]      # (the last column is the difference of the others)
+            runs[which].append(rows)
+            labels = labels or list(rows)
+    print(f"# {' '.join(child) or '(plain leg)'}: {a.rounds} rounds per build, alternating; ms; spread = max - min over the rounds")
+    print(f"# {'row':24s} {'col':>3s} {'new median':>11s} {'spread':>7s} {'parent median':>14s} {'spread':>7s}  at or below parent median + spread")
+    ok = True
+    for row in labels:
+        for col in range(len(runs["new"][0][row])):
+            v = {w: [r[row][col] for r in runs[w]] for w in runs}
+            mn, mp = float(np.median(v["new"])), float(np.median(v["parent"]))
+            sn, spp = max(v["new"]) - min(v["new"]), max(v["parent"]) - min(v["parent"])
+            good = mn <= mp + spp
+            ok &= good
+            print(f"  {row:24s} {col:3d} {mn:11.3f} {sn:7.3f} {mp:14.3f} {spp:7.3f}  {'yes' if good else 'NO'}", flush=True)
+    print("# every row at or below the parent's median + spread" if ok else "# NOT every row is at or below the parent's median + spread")
+
+
 ap = argparse.ArgumentParser()
+ap.add_argument("--merge", action="store_true", help="several forwards of a frame, one NMS: get_blob + numpy per forward against "
+                "detect_merge_add per forward + detect_merge_end")
+ap.add_argument("--rounds", type=int, default=3, help="--merge / --parent-lib: repetitions of the whole measurement")
+ap.add_argument("--lib", default="", help="run with the kernels of this libmscnn_hip.so under the Net")
+ap.add_argument("--parent-lib", default="", help="A/B of the selected leg against this libmscnn_hip.so, alternating child processes")
 ap.add_argument("--proposals", action="store_true", help="the proposal result: get_blob + numpy against one proposals_multi, and the "
                 "RPN-only run against the whole forward")
 ap.add_argument("--cascade", action="store_true", help="the cascade deploys: per-call detect_cascade against one detect_cascade_multi")
@@ -192,6 +332,14 @@ ap.add_argument("--form", choices=("both", "call", "multi"), default="both",
 ap.add_argument("--nms-type", default="maxg", choices=("maxg", "max"), help="bbNms's type for both forms (Net.set_nms)")
 ap.add_argument("--ovr-dnm", default="union", choices=("union", "min"), help="bbNms's overlap denominator for both forms")
 a = ap.parse_args()
+if a.parent_lib:
+    ab_leg(a, sys.argv[1:])
+    sys.exit(0)
+if a.lib:
+    use_lib(a.lib)
+if a.merge:
+    merge_leg(a)
+    sys.exit(0)
 if a.cascade:
     cascade_leg(a)
     sys.exit(0)

@@ -8,6 +8,7 @@ detections/<comp_id>_<class>_<output>_results.txt written as dlmwrite does (:148
   python tools/run_cascademscnn.py --prototxt mscnn_deploy.prototxt --weights model.caffemodel --images /KITTI/testing/image_2
          [--outputs 1st,2nd,3rd] [--cls-ids 2] [--det-thr 0.05] [--nms-overlap 0.5] [--batch B] [--precision f32|f16x3|f16]
          [--out detections] [--comp-id cascade_mscnn] [--names bg,car,van,truck,tram] [--limit N]
+         [--scales H1xW1,H2xW2,...] [--flip] [--merge-cap N]      # several forwards per frame, one NMS (Net.detect_merge_*)
          [--nms-type maxg|max] [--ovr-dnm union|min] [--nms-thr T]      # pNms.type / pNms.ovrDnm / bbNms's thr (Net.set_nms)
          [--roialign-one-pass]      # the ROIAlign heads of the net as one launch each (Net.set_roialign_one_pass; same results)
   python tools/run_cascademscnn.py --model kitti_car/cascade-mscnn-7s-576-2x --synthetic 8 --batch 2      # no dataset / weights at
@@ -19,6 +20,11 @@ as the reference picks it (:36-48) -- 3rd_avg when the net has cls_prob_3rd_avg,
 --batch B runs B frames per forward (the net's input reshaped to (B, 3, H, W), the last group to its own size).
 --orig-size is the WiderFace flow (widerface/run_cascademscnn.m:55, 82-91): every frame runs at its own size rounded to multiples
 of 32 (scaled down to --max-size first when a side exceeds it), the net reshaped whenever that size changes; one frame per forward.
+--scales / --flip run every frame at each of the given input sizes, with --flip a second time mirrored on the host ([:, ::-1]), and
+merge the candidates of all those forwards before ONE NMS per cascade output and class (per frame Net.detect_merge_begin, per forward
+Net.detect_cascade_merge_add, then Net.detect_merge_end; list size: forwards per frame x max_nms_num, or --merge-cap).  One frame per
+forward, the same result files.  No reference script does this: there is no pin on the reference for it.  Without these flags the
+driver runs exactly the calls it ran before they existed.
 
 Everything here is host glue over calls the test-suite covers one by one (Net.set_images, forward, detect_cascade_multi,
 reshape_input, kitti.write_detections_dlm)."""
@@ -90,7 +96,12 @@ def parse_args(argv=None):
                     "forward as group_NNNN.npz (to re-run the final stage on exactly what a forward produced)")
     ap.add_argument("--roialign-one-pass", action="store_true", help="run every ROIAlign head (two ROIAlign layers, their 2x2 AVE "
                     "poolings, the Concat: the WiderFace cascade's) as one launch (Net.set_roialign_one_pass); off: the five layers")
+    from run_mscnn_detection import add_merge_flags, check_merge_flags
+    add_merge_flags(ap)
     a = ap.parse_args(argv)
+    check_merge_flags(ap, a)
+    if (a.scales or a.flip) and (a.orig_size or a.dump_blobs):
+        ap.error("--scales / --flip name the input sizes themselves and keep no single forward's blobs: not with --orig-size / --dump-blobs")
     if not (a.prototxt or a.model) or not (a.images or a.synthetic):
         ap.error("need --prototxt or --model, and --images or --synthetic N")
     if a.batch < 1:
@@ -111,7 +122,7 @@ def main(argv=None):
     import numpy as np
     import torch
     from mscnn_amd import kitti, net as mnet, synth, zoo
-    from run_mscnn_detection import list_images, load_rgb_u8, names_for
+    from run_mscnn_detection import list_images, load_rgb_u8, merge_cand_cap, merge_passes, names_for
 
     if a.prototxt:
         text = open(a.prototxt).read()
@@ -155,7 +166,31 @@ def main(argv=None):
     shape = tuple(net.blob_shape("data"))
     results = {(o, c): [] for o in range(len(outputs)) for c in range(len(cls_ids))}
     used, done = 0.0, 0
-    for g0 in range(0, len(files), a.batch):
+    # --scales / --flip: several forwards per frame, one NMS per (output, class): one detect_merge_begin per frame, after every forward a
+    # detect_cascade_merge_add (the mirrored forward with the view flip_x = 1), then one detect_merge_end
+    passes = merge_passes(a, shape[2:]) if (a.scales or a.flip) else []
+    for k, path in enumerate(files if passes else [], start=1):
+        img = load_frame(path, k)
+        net.detect_merge_begin(1, len(outputs) * len(cls_ids), merge_cand_cap(text, len(passes), a.merge_cap))
+        for H, W, flipped in passes:
+            if (1, 3, H, W) != shape:
+                shape = (1, 3, H, W)
+                net.reshape_input("data", shape)
+            dev_imgs = [torch.from_numpy(np.ascontiguousarray(img[:, ::-1]) if flipped else img).cuda(a.device)]
+            params = net.set_images("data", dev_imgs)
+            torch.cuda.synchronize(a.device)
+            t0 = time.perf_counter()
+            net.forward()
+            torch.cuda.synchronize(a.device)
+            used += time.perf_counter() - t0
+            net.detect_cascade_merge_add([dict(p, nms_overlap=a.nms_overlap) for p in params], outputs, cls_ids, det_thr=a.det_thr,
+                                         views=[dict(flip_x=1)] if flipped else None)
+        per_image, _ = net.detect_merge_end()
+        for (o, c) in results:
+            results[(o, c)].append(per_image[0][o * len(cls_ids) + c][0])
+        if k % 100 == 0 or k == len(files):
+            print(f"idx {k}/{len(files)}, avgtime={used / k:.4f}s ({len(passes)} forwards per frame)")
+    for g0 in range(0, len(files) if not passes else 0, a.batch):
         group = files[g0:g0 + a.batch]
         frames = [load_frame(path, g0 + i + 1) for i, path in enumerate(group)]
         H, W = net_input_size(frames[0].shape[0], frames[0].shape[1], a.max_size) if a.orig_size else shape[2:]

@@ -13,6 +13,7 @@ examples/kitti_result/writeDetForEval.m.
          [--rois-in FILE]                                    # the detection sub-net on these boxes instead of the net's own proposals
          [--nms-type maxg|max] [--ovr-dnm union|min] [--nms-thr T] [--det-thr T]      # pNms.type / pNms.ovrDnm / bbNms's thr, and
                                                              # the det_thr of the WiderFace plain flow (Net.set_nms, once per run)
+         [--scales H1xW1,H2xW2,...] [--flip] [--merge-cap N] # several forwards per frame, one NMS (Net.detect_merge_*)
   python tools/run_mscnn_detection.py --model kitti_car/mscnn-7s-576 --synthetic 8      # no dataset / weights at hand: the generated
                                                                                         # deploy net, seeded weights, synthetic frames
 
@@ -29,6 +30,14 @@ as a proposal generator: the layers up to BoxOutput (Net.forward_proposals), no 
 frames of the run in ascending order -- the format --proposals-out writes -- go through Net.forward_rois instead of Net.forward, per
 frame or per --batch group (conv5_x, the proposal heads and BoxOutput never run); everything behind the forward is unchanged.  A frame
 without rows gets no detections; a group in which no frame has rows is not forwarded at all.  Not together with --proposals-only.
+
+--scales / --flip run every frame more than once -- at each of the given input sizes (the net's input is reshaped), and with --flip
+a second time mirrored on the host ([:, ::-1]) -- and merge the candidates of all those forwards before ONE NMS per class: per frame one
+Net.detect_merge_begin, per forward set_image + forward + Net.detect_merge_add (the mirrored one with the view flip_x = 1), then one
+Net.detect_merge_end.  The candidate lists hold (forwards per frame) x BoxOutput's max_nms_num rows (--merge-cap N: another number; it
+is needed for a deploy without a max_nms_num).  One frame per forward; not with --batch, --rois-in or the proposal outputs.  The
+result files have the same layout.  No reference script does this: there is no pin on the reference for it.  Without these flags the
+driver runs exactly the calls it ran before they existed.
 
 Everything here is host glue over calls the test-suite covers one by one (Net.set_image / set_images, forward, detect / detect_multi,
 proposals_multi, kitti.write_*)."""
@@ -83,6 +92,54 @@ def names_for(prototxt_text, names_arg):
     return {5: KITTI_NAMES["car"], 3: KITTI_NAMES["ped_cyc"], 2: KITTI_NAMES["caltech"]}.get(n, ["bg"] + [f"class{i}" for i in range(1, n)])
 
 
+def parse_scales(text):
+    """--scales H1xW1,H2xW2,... -> [(H1, W1), (H2, W2), ...]; raises ValueError on anything else."""
+    import re
+    out = []
+    for part in text.split(","):
+        m = re.fullmatch(r"(\d+)x(\d+)", part.strip())
+        if not m or int(m.group(1)) < 1 or int(m.group(2)) < 1:
+            raise ValueError(f"--scales {text!r}: {part!r} is not HxW with positive integers")
+        out.append((int(m.group(1)), int(m.group(2))))
+    return out
+
+
+def add_merge_flags(ap):
+    """The flags both drivers share for several forwards per frame (Net.detect_merge_*)."""
+    ap.add_argument("--scales", default=None, help="H1xW1,H2xW2,...: run every frame at each of these net input sizes and merge the "
+                    "candidates of all forwards before one NMS (Net.detect_merge_*)")
+    ap.add_argument("--flip", action="store_true", help="also run every frame mirrored ([:, ::-1]) and merge its candidates in")
+    ap.add_argument("--merge-cap", type=int, default=0, help="candidate slots per class and frame (default: forwards per frame x "
+                    "BoxOutput's max_nms_num)")
+
+
+def check_merge_flags(ap, a):
+    if a.scales is not None:
+        try:
+            a.scales = parse_scales(a.scales)
+        except ValueError as e:
+            ap.error(str(e))
+    if (a.scales or a.flip) and a.batch > 1:
+        ap.error("--scales / --flip run one frame per forward (drop --batch)")
+
+
+def merge_cand_cap(prototxt_text, passes, merge_cap):
+    """Slots of a candidate list: --merge-cap, else forwards per frame x the largest max_nms_num of the deploy (BoxOutput's row bound
+    of one forward of one frame)."""
+    import re
+    if merge_cap > 0:
+        return merge_cap
+    bounds = [int(v) for v in re.findall(r"max_nms_num:\s*(\d+)", prototxt_text)]
+    if not bounds or max(bounds) < 1:
+        sys.exit("--scales / --flip: the deploy has no max_nms_num > 0 to size the candidate lists by: give --merge-cap N")
+    return passes * max(bounds)
+
+
+def merge_passes(a, net_hw):
+    """[(H, W, flipped)] of the forwards of one frame, in add order: every scale, each followed by its mirrored twin."""
+    return [(H, W, f) for H, W in (a.scales or [net_hw]) for f in ((False, True) if a.flip else (False,))]
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--prototxt"); ap.add_argument("--weights", help=".caffemodel (new or V1 layout) or .h5 snapshot")
@@ -107,7 +164,11 @@ def parse_args(argv=None):
                     "call, no detection files; needs --proposals-out")
     ap.add_argument("--rois-in", default="", help="file of rows [image_index x y w h score] (1-based index, original-image pixels: what "
                     "--proposals-out writes): run the detection sub-net on these boxes (Net.forward_rois) instead of the whole net")
+    add_merge_flags(ap)
     a = ap.parse_args(argv)
+    check_merge_flags(ap, a)
+    if (a.scales or a.flip) and (a.rois_in or a.proposals_out or a.proposals_only):
+        ap.error("--scales / --flip merge detections: not with --rois-in, --proposals-out or --proposals-only")
     if a.proposals_only and not a.proposals_out:
         ap.error("--proposals-only needs --proposals-out DIR")
     if a.proposals_only and a.rois_in:
@@ -170,6 +231,8 @@ def main(argv=None):
     rois = read_rois(a.rois_in, len(files)) if a.rois_in else None
     if a.batch > 1:
         return run_batched(a, net, files, names, cls_ids, imgH, imgW, per_class, per_image_props, forward, rois)
+    if a.scales or a.flip:
+        return run_merged(a, net, text, files, names, cls_ids, imgH, imgW, per_class)
     used = 0.0
     for k, path in enumerate(files, start=1):
         img = load_frame(path, k)
@@ -203,6 +266,46 @@ def main(argv=None):
         if k % 100 == 0 or k == len(files):
             print(f"idx {k}/{len(files)}, avgtime={used / k:.4f}s")           # :147
     finish(a, names, cls_ids, per_class, per_image_props, len(files))
+    return 0
+
+
+def run_merged(a, net, text, files, names, cls_ids, imgH, imgW, per_class):
+    """--scales / --flip: per frame one detect_merge_begin, per forward set_image + forward + detect_merge_add, one detect_merge_end."""
+    import torch
+    from mscnn_amd import kitti
+    passes = merge_passes(a, (imgH, imgW))
+    cand_cap = merge_cand_cap(text, len(passes), a.merge_cap)
+    shape = (1, 3, imgH, imgW)
+    used = 0.0
+    for k, path in enumerate(files, start=1):
+        img = load_frame(path, k)
+        orgH, orgW = img.shape[:2]
+        net.detect_merge_begin(1, len(cls_ids), cand_cap)
+        for H, W, flipped in passes:
+            if (1, 3, H, W) != shape:
+                shape = (1, 3, H, W)
+                net.reshape_input("data", shape)
+            frame = np.ascontiguousarray(img[:, ::-1]) if flipped else img
+            dev_img = torch.from_numpy(frame).cuda(a.device)
+            net.set_image("data", dev_img)
+            torch.cuda.synchronize(a.device)
+            t0 = time.perf_counter()
+            net.forward()
+            torch.cuda.synchronize(a.device)
+            used += time.perf_counter() - t0                                  # forwards only, as :72-73
+            p = dict(ratios=(H / float(orgH), W / float(orgW)), org_hw=(orgH, orgW), proposal_thr=a.proposal_thr, nms_overlap=a.nms_overlap)
+            net.detect_merge_add([p], cls_ids, views=[dict(flip_x=1)] if flipped else None)
+        per_image, _ = net.detect_merge_end()
+        by_type = {}
+        for ci, c in enumerate(cls_ids):
+            dets = per_image[0][ci][0]
+            per_class[c].append(dets)
+            by_type[{"car": "Car", "ped": "Pedestrian", "cyc": "Cyclist"}.get(names[c - 1], names[c - 1])] = dets
+        if a.labels_dir:
+            kitti.write_kitti_labels(a.labels_dir, frame_id(path, k), by_type)
+        if k % 100 == 0 or k == len(files):
+            print(f"idx {k}/{len(files)}, avgtime={used / k:.4f}s ({len(passes)} forwards per frame)")
+    finish(a, names, cls_ids, per_class, [], len(files))
     return 0
 
 
