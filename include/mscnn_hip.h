@@ -682,6 +682,31 @@ MSCNN_API int mscnn_detections_candidates_cascade_add(const mscnn_detections_des
                                                       const mscnn_nms_params* nms, int pass, int num_images, int num_outputs,
                                                       int num_classes, const mscnn_cascade_output* outputs, int R_all, void* cand,
                                                       int cand_cap, void* stream);
+/* The images of ONE batched forward into the lists of the FRAMES they are views of: a frame and its mirror, or the tiles of a frame,
+ * run as the batch they naturally are.  desc[num_images * K] and view[num_images] describe the images of THIS forward exactly as in
+ * _add / _cascade_add (K = num_classes, resp. num_outputs x num_classes); list_of[num_images] is a HOST array: the rows of image b
+ * go to the lists of frame list_of[b], cand has S = num_lists * K lists (list = list_of[b] * K + slot).  Every row goes through the
+ * one row transform and the view arithmetic of _add (flip_x against the desc's org_w, then + off_x, + off_y, in double); the tag is
+ * (pass << 24) | row with row absolute in the batch.
+ * ORDER of a list: (add call, image index ascending, row) -- never a matter of timing.  One workgroup owns a list and walks its
+ * images in turn (the table of a launch holds 32 (image, slot) pairs, grouped by list): no atomics on global memory, no workgroup
+ * waits on another, nothing spins.  With more pairs than one launch holds, later launches continue the lists in stream order, the
+ * count read from the device.  Counts, the overflow flag and "nothing stored past the cap" are those of _add: a list keeps counting
+ * the rows that wanted in.  list_of = {0, 1, ..., N - 1} with num_lists == num_images leaves the whole cand buffer byte-identical
+ * to _add.
+ * Refused before any launch, naming the value: everything _add / _cascade_add refuse, a null list_of, num_lists < 1, an entry of
+ * list_of outside [0, num_lists).  mscnn_detections_merge_fwd then runs as it is (its limit above 4032 slots included).
+ * No pin on the reference (its scripts have neither views nor a merge): the check is tests/merge_witness.py with the passes listed
+ * in (add, image) order. */
+MSCNN_API int mscnn_detections_candidates_add_views(const mscnn_detections_desc* desc, const mscnn_detections_view* view, const int* list_of,
+                                                    const mscnn_nms_params* nms, int pass, int num_images, int num_lists, int num_classes,
+                                                    const float* bbox_pred, const float* cls_pred, const float* props, int R_all,
+                                                    void* cand, int cand_cap, void* stream);
+MSCNN_API int mscnn_detections_candidates_cascade_add_views(const mscnn_detections_desc* desc, const mscnn_detections_view* view,
+                                                            const int* list_of, float det_thr, const mscnn_nms_params* nms, int pass,
+                                                            int num_images, int num_lists, int num_outputs, int num_classes,
+                                                            const mscnn_cascade_output* outputs, int R_all, void* cand, int cand_cap,
+                                                            void* stream);
 MSCNN_API size_t mscnn_detections_merge_workspace_bytes(int num_segments, int cand_cap);
 MSCNN_API int mscnn_detections_merge_fwd(const double* nms_overlap, const mscnn_nms_params* nms, int num_segments, void* cand,
                                          int cand_cap, void* pack_dev, void* workspace, size_t workspace_bytes, void* stream);
@@ -762,6 +787,30 @@ MSCNN_API size_t mscnn_preprocess_batch_workspace_bytes(int count, const int* or
 MSCNN_API int mscnn_preprocess_batch_u8_f32(const unsigned char* const* imgs_rgb, const int* org_h, const int* org_w, int count,
                                   float* out, int H, int W, const float* mean_bgr, void* workspace, size_t workspace_bytes,
                                   void* stream);
+/* VIEWS of uploaded frames as the images of one batch: a frame and its mirror, the tiles of a frame too large for one forward.
+ * frames_rgb: a HOST array of num_frames device pointers (frame f: uint8 [org_h[f]][org_w[f]][3]); view v reads the window
+ * [y0, y0 + h) x [x0, x0 + w) of frame views[v].frame, reversed along x when flip_x, and writes slice v of out [count][3][H][W].
+ * Definition: slice v is bit-identical to mscnn_preprocess_u8_f32 on a contiguous copy of that window (mirrored with [:, ::-1] when
+ * flip_x) -- the resize mirrors at the WINDOW's borders, the pass order (smaller scale first) is decided by the window's size, and no
+ * pixel outside the window is ever read.  No copy of the window is made: its offset, the frame's row pitch (org_w * 3 bytes) and the
+ * mirrored column are part of the first pass's source index; the second pass reads the window's intermediate only.  Two launches
+ * per 32 views, the table of a chunk travels as a kernel argument; any number of views may name the same frame.  The workspace holds
+ * every view's intermediate at a 256-byte aligned offset, back to back: mscnn_preprocess_views_workspace_bytes returns that size (0
+ * for arguments the op refuses: null views, count < 1, a size <= 0, an empty window).
+ * Refused before any launch, naming the value: null pointers (a null frame included), count < 1, num_frames < 1, a frame of size
+ * <= 0, a view's frame outside [0, num_frames), a window with w < 1 or h < 1 or one that is not inside its frame, a flip_x that is
+ * neither 0 nor 1, H or W <= 0, a workspace that is too small or not 16-byte aligned.
+ * No pin on the reference (its scripts pre-process whole frames only): the check is the single-frame op on a host copy of the window
+ * and a numpy restatement (tests/views_witness.py). */
+#ifndef MSCNN_PREPROCESS_VIEW_DEFINED
+#define MSCNN_PREPROCESS_VIEW_DEFINED
+typedef struct { int frame; int x0, y0, w, h; int flip_x; } mscnn_preprocess_view;
+#endif
+MSCNN_API size_t mscnn_preprocess_views_workspace_bytes(const mscnn_preprocess_view* views, int count, int H, int W);
+/* Alignment: workspace 16 (refused); frames 1, out 4. */
+MSCNN_API int mscnn_preprocess_views_u8_f32(const unsigned char* const* frames_rgb, const int* org_h, const int* org_w, int num_frames,
+                                            const mscnn_preprocess_view* views, int count, float* out, int H, int W,
+                                            const float* mean_bgr, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

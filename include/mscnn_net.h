@@ -156,6 +156,22 @@ MSCNN_NET_API int mscnn_net_set_image(mscnn_net* net, const char* name, const un
  * count == num() and channels() == 3; refused before anything is written. */
 MSCNN_NET_API int mscnn_net_set_images(mscnn_net* net, const char* name, const unsigned char* const* imgs_rgb, int on_device,
                                        const int* org_h, const int* org_w, int count, const float* mean_bgr);
+/* VIEWS of one or more frames as the images of the blob: a frame and its mirror, the tiles of a frame too large for one forward
+ * (mscnn_hip.h: mscnn_preprocess_views_u8_f32; the struct is repeated here so that this header stands alone).  frames_rgb: a host
+ * array of num_frames host pointers (device pointers when on_device != 0), frame f uint8 [org_h[f]][org_w[f]][3]; view v = the window
+ * [y0, y0 + h) x [x0, x0 + w) of frame views[v].frame, reversed along x when flip_x, resized to the blob's H x W and written into
+ * slice v -- bit for bit what mscnn_net_set_image writes for a contiguous host copy of that window (mirrored with [:, ::-1]).  A host
+ * frame is uploaded ONCE, whatever the number of its views.  Requires count == num() and channels() == 3.  Refused before anything
+ * is uploaded or written, naming the value: a null pointer, num_frames < 1, a frame of size <= 0, a view's frame outside
+ * [0, num_frames), a window that is empty or not inside its frame, a flip_x that is neither 0 nor 1, a net built with device < 0.
+ * No pin on the reference: its scripts pre-process whole frames only. */
+#ifndef MSCNN_PREPROCESS_VIEW_DEFINED
+#define MSCNN_PREPROCESS_VIEW_DEFINED
+typedef struct { int frame; int x0, y0, w, h; int flip_x; } mscnn_preprocess_view;
+#endif
+MSCNN_NET_API int mscnn_net_set_image_views(mscnn_net* net, const char* name, const unsigned char* const* frames_rgb, int on_device,
+                                            const int* org_h, const int* org_w, int num_frames, const mscnn_preprocess_view* views,
+                                            int count, const float* mean_bgr);
 MSCNN_NET_API int mscnn_net_get_blob(mscnn_net* net, const char* name, float* host, size_t capacity, size_t* count);
 MSCNN_NET_API const float* mscnn_net_blob_device_ptr(mscnn_net* net, const char* name);
 
@@ -380,6 +396,20 @@ MSCNN_NET_API int mscnn_net_detect_cascade_merge_add(mscnn_net* net, const mscnn
                                                      const char* const* proposal_blobs, float det_thr);
 MSCNN_NET_API int mscnn_net_detect_merge_end(mscnn_net* net, double* dets_host, int* pass_host, int* row_host, int cap, int* seg_dets,
                                              int* seg_candidates);
+/* The views of a frame as ONE batched forward (mscnn_hip.h: mscnn_detections_candidates_add_views): the merge was opened with
+ * _begin(num_frames, ...), the input holds N images -- the views mscnn_net_set_image_views wrote --, p[N * K] and view[N] describe
+ * them as in _add, and list_of[N] (host) names the frame of each: the rows of image b go to the lists of frame list_of[b].  One
+ * call is ONE pass (the tag's row is absolute in the batch).  Order of a list: (add call, image index ascending, row), whatever the
+ * timing.  Refused before anything is enqueued, naming the value: everything _add refuses but its num_images rule, a null list_of,
+ * an entry outside [0, num_frames).  The row bound (the sum of the forwards' ROI row counts against cand_cap) applies unchanged; the
+ * nms_overlap rule is per LIST: every image that reaches a list, in this call or an earlier one, carries the overlap the list got
+ * first.  _end and its reader are unchanged.  No pin on the reference: its scripts have neither views nor a merge; the check is
+ * tests/merge_witness.py with the passes listed in (add, image) order. */
+MSCNN_NET_API int mscnn_net_detect_merge_add_views(mscnn_net* net, const mscnn_detect_params* p, const mscnn_detections_view* view,
+                                                   const int* list_of);
+MSCNN_NET_API int mscnn_net_detect_cascade_merge_add_views(mscnn_net* net, const mscnn_detect_params* p, const mscnn_detections_view* view,
+                                                           const int* list_of, int num_outputs, const char* const* bbox_blobs,
+                                                           const char* const* prob_blobs, const char* const* proposal_blobs, float det_thr);
 
 /* Multi-GPU form of the same stage (include/mscnn_dist.h gathers its result over RCCL): the detections stay in HBM, in a
  * fixed-size pack  [int32 count, int32 num_rois, int32 cap, int32 0][cap x 5 doubles x y w h prob][cap x int32 roi row]

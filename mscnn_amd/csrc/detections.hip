@@ -13,6 +13,7 @@
 #include <cfloat>
 #include <cmath>
 #include <cstring>
+#include <vector>
 #include "common.h"
 #include "box_device.h"
 #include "det_rows.h"
@@ -558,6 +559,90 @@ __device__ __forceinline__ void det_cand_add(const DetCandArgs& a) {
 __global__ __launch_bounds__(kCandThreads) void det_cand_add_kernel(DetCandArgs a) { det_cand_add<false>(a); }
 __global__ __launch_bounds__(kCandThreads) void det_cand_add_thr_kernel(DetCandArgs a) { det_cand_add<true>(a); }
 
+// -- the images of a batched forward into their FRAMES' lists (mscnn_detections_candidates_add_views).  A launch carries up to
+// kSegsPerLaunch ENTRIES, one per (image, slot) pair, sorted by list and then by image; workgroup q owns list `list[q]` and walks its
+// entries [first[q], first[q + 1]) in turn: each entry is det_cand_add's walk over that image's rows (the same det_row, view
+// arithmetic, ballot / popcount places and tag) behind the count the entries before it left.  The count is read once and stored once,
+// by this workgroup alone; a list whose entries do not fit one launch goes on in the next one, in stream order.
+struct DetCandViewsArgs {
+  int R_all, classes_per_source, cand_cap, num_segs, pass, num_blocks;      // num_segs: lists of the cand buffer
+  char* cand;
+  DetNms nms;
+  DetSource src[kCascadeMaxOutputs];
+  DetSeg seg[kSegsPerLaunch];
+  DetView view[kSegsPerLaunch];
+  int img[kSegsPerLaunch], slot[kSegsPerLaunch];      // entry -> its image of the batch and its slot of the image
+  int list[kSegsPerLaunch], first[kSegsPerLaunch + 1];      // workgroup -> its list and its entries
+};
+static_assert(sizeof(DetCandViewsArgs) <= 4096, "DetCandViewsArgs travels as kernel arguments");
+
+template <bool kThr>
+__device__ __forceinline__ void det_cand_add_views(const DetCandViewsArgs& a) {
+  const int q = blockIdx.x, s = a.list[q], tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const DetCand c = det_cand_of(a.cand, a.num_segs, a.cand_cap);
+  __shared__ int s_range[2];
+  __shared__ int s_base;
+  __shared__ int s_cnt[kCandThreads / 64];
+  if (tid == 0) s_base = c.cnt[CAND_WORDS * (size_t)s + CAND_WANTED];
+  __syncthreads();
+  int base = s_base;
+  const size_t list = (size_t)s * (size_t)a.cand_cap;
+  for (int e = a.first[q]; e < a.first[q + 1]; ++e) {
+    const DetSource& t = a.src[a.slot[e] / a.classes_per_source];
+    const int prop_stride = t.cascade ? 5 : 6, box_stride = t.cascade ? 5 : 4 * t.ncls;
+    __syncthreads();      // (every thread has read the range of the entry before)
+    if (tid < 2) s_range[tid] = det_image_lower_bound(t.props, a.R_all, a.img[e] + tid, prop_stride);
+    __syncthreads();
+    const int row0 = s_range[0], rows = s_range[1] - s_range[0];
+    const DetSeg& g = a.seg[e];
+    DetArgs d;
+    d.bbox_pred = t.boxes + (size_t)row0 * box_stride; d.cls_pred = t.cls + (size_t)row0 * t.ncls; d.props = t.props + (size_t)row0 * prop_stride;
+    d.R = rows; d.ncls = t.ncls; d.cls_id = g.cls_id;
+    for (int k = 0; k < 4; ++k) { d.mean[k] = g.mean[k]; d.stdv[k] = g.stdv[k]; }
+    d.proposal_thr = g.proposal_thr; d.ratio_h = g.ratio_h; d.ratio_w = g.ratio_w; d.org_h = g.org_h; d.org_w = g.org_w;
+    d.cascade = t.cascade;
+    d.nms_thr = a.nms.thr; d.det_thr = t.cascade ? 0.f : a.nms.det_thr;
+    const DetView v = a.view[e];
+    for (int r0 = 0; r0 < rows; r0 += kCandThreads) {
+      const int r = r0 + tid;
+      DetBox b;
+      float prob = 0.f;
+      bool keep = false;
+      if (r < rows) keep = det_row<kThr>(d, r, &b, &prob);
+      const u64 m = __ballot(keep);
+      if (lane == 0) s_cnt[wave] = __popcll(m);
+      __syncthreads();
+      int before = 0, total = 0;
+      for (int w = 0; w < kCandThreads / 64; ++w) {
+        if (w < wave) before += s_cnt[w];
+        total += s_cnt[w];
+      }
+      if (keep) {
+        const long pos = (long)base + before + __popcll(m & ((1ull << lane) - 1ull));
+        if (pos < (long)a.cand_cap) {                     // (past the cap nothing is stored: the count below says how many wanted in)
+          if (v.on) {
+            if (v.flip_x) b.x = (double)d.org_w - (b.x + b.w);
+            b.x = b.x + v.off_x;
+            b.y = b.y + v.off_y;
+          }
+          c.box[list + pos] = b;
+          c.prob[list + pos] = prob;
+          c.tag[list + pos] = (a.pass << 24) | (row0 + r);
+        }
+      }
+      const long nb = (long)base + total;
+      base = nb > 0x7fffffffL ? 0x7fffffff : (int)nb;
+      __syncthreads();      // (every thread has read s_cnt before the next step writes it)
+    }
+  }
+  if (tid == 0) {
+    c.cnt[CAND_WORDS * (size_t)s + CAND_WANTED] = base;
+    if (base > a.cand_cap) c.cnt[CAND_WORDS * (size_t)s + CAND_OVER] = 1;
+  }
+}
+__global__ __launch_bounds__(kCandThreads) void det_cand_add_views_kernel(DetCandViewsArgs a) { det_cand_add_views<false>(a); }
+__global__ __launch_bounds__(kCandThreads) void det_cand_add_views_thr_kernel(DetCandViewsArgs a) { det_cand_add_views<true>(a); }
+
 // -- merge, lists of at most kMaxK slots: every segment in one pass, three launches per kSegsPerLaunch segments
 struct DetMergeArgs {
   int cand_cap, wpr, num_segs, s0;
@@ -1048,20 +1133,59 @@ extern "C" int mscnn_detections_candidates_reset(void* cand, int num_segments, i
   return MSCNN_OK;
 }
 
-// everything the two add calls refuse alike, then one launch per 32 segments
+// the views form: entries (image, slot) sorted by list and then by image, 32 per launch, one workgroup per list of a launch
+static int det_cand_views_launch(const DetSource* src, int num_sources, const mscnn_detections_desc* desc, const mscnn_detections_view* view,
+                                 const int* list_of, float det_thr, const mscnn_nms_params& nms, int pass, int num_images, int num_lists,
+                                 int C, int R_all, void* cand, int cand_cap, hipStream_t st) {
+  const int K = num_sources * C;
+  DetCandViewsArgs a = {};
+  a.R_all = R_all; a.classes_per_source = C; a.cand_cap = cand_cap; a.num_segs = num_lists * K; a.pass = pass;
+  a.cand = static_cast<char*>(cand);
+  a.nms = det_nms_of(nms);
+  for (int o = 0; o < num_sources; ++o) a.src[o] = src[o];
+  // (list-major, then the image index ascending: per frame its images in turn, each with its K slots)
+  std::vector<std::vector<int> > images_of(num_lists);
+  for (int b = 0; b < num_images; ++b) images_of[list_of[b]].push_back(b);
+  int n = 0, last_list = -1;
+  auto flush = [&]() -> int {
+    if (n == 0) return MSCNN_OK;
+    a.first[a.num_blocks] = n;
+    if (nms_has_thr(nms)) det_cand_add_views_thr_kernel<<<a.num_blocks, kCandThreads, 0, st>>>(a);
+    else det_cand_add_views_kernel<<<a.num_blocks, kCandThreads, 0, st>>>(a);
+    MSCNN_POST_LAUNCH();
+    n = 0; a.num_blocks = 0; last_list = -1;
+    return MSCNN_OK;
+  };
+  for (int f = 0; f < num_lists; ++f) {
+    for (int k = 0; k < K; ++k) {
+      for (int b : images_of[f]) {
+        const int s = f * K + k;
+        if (s != last_list) { a.list[a.num_blocks] = s; a.first[a.num_blocks] = n; ++a.num_blocks; last_list = s; }
+        a.seg[n] = det_seg_of(desc[b * K + k], src[0].cascade, det_thr);
+        a.view[n] = view ? DetView{view[b].off_x, view[b].off_y, view[b].flip_x, 1} : DetView{0.0, 0.0, 0, 0};
+        a.img[n] = b; a.slot[n] = k;
+        if (++n == kSegsPerLaunch) { if (int rc = flush()) return rc; }
+      }
+    }
+  }
+  return flush();
+}
+
+// everything the add calls refuse alike, then one launch per 32 segments.  list_of != NULL: the views form (S lists = num_lists x K)
 static int det_cand_launch(const char* name, const DetSource* src, int num_sources, const mscnn_detections_desc* desc,
                            const mscnn_detections_view* view, float det_thr, const mscnn_nms_params& nms, int pass, int num_images, int C,
-                           int R_all, void* cand, int cand_cap, void* stream) {
+                           int R_all, void* cand, int cand_cap, void* stream, const int* list_of = nullptr, int num_lists = 0) {
   const int K = num_sources * C;
   MSCNN_REQUIRE((long)num_images * K <= (long)(1 << 24), "%s: %d images x %d slots", name, num_images, K);
-  const int S = num_images * K;
+  MSCNN_REQUIRE(!list_of || (long)num_lists * K <= (long)(1 << 24), "%s: %d lists x %d slots", name, num_lists, K);
+  const int S = (list_of ? num_lists : num_images) * K;
   MSCNN_REQUIRE(cand_cap >= 1, "%s: cand_cap %d", name, cand_cap);
   MSCNN_REQUIRE(cand_shape_ok(S, cand_cap), "%s: %d segments x %d slots is past 2^31 - 1", name, S, cand_cap);
   MSCNN_REQUIRE_ALIGNED(cand, 16, "detections_candidates: cand");
   MSCNN_REQUIRE(pass >= 0 && pass <= 127, "%s: pass %d (0 .. 127: the tag is (pass << 24) | row)", name, pass);
   MSCNN_REQUIRE(R_all >= 1, "%s: R_all = %d (BoxOutput emits at least one row)", name, R_all);
   MSCNN_REQUIRE(R_all < (1 << 24), "%s: R_all = %d rows do not fit the tag's 24 row bits", name, R_all);
-  for (int s = 0; s < S; ++s) {
+  for (int s = 0; s < num_images * K; ++s) {
     MSCNN_REQUIRE(desc[s].ratio_h > 0 && desc[s].ratio_w > 0, "%s: segment %d: ratios %g x %g (positive numbers)", name, s, desc[s].ratio_h,
                   desc[s].ratio_w);
   }
@@ -1071,6 +1195,8 @@ static int det_cand_launch(const char* name, const DetSource* src, int num_sourc
     MSCNN_REQUIRE(view[i].flip_x == 0 || view[i].flip_x == 1, "%s: image %d: flip_x %d (0 or 1)", name, i, view[i].flip_x);
   }
   hipStream_t st = as_stream(stream);
+  if (list_of)
+    return det_cand_views_launch(src, num_sources, desc, view, list_of, det_thr, nms, pass, num_images, num_lists, C, R_all, cand, cand_cap, st);
   DetCandArgs a = {};
   a.R_all = R_all; a.slots_per_image = K; a.classes_per_source = C; a.cand_cap = cand_cap; a.num_segs = S; a.pass = pass;
   a.cand = static_cast<char*>(cand);
@@ -1091,55 +1217,101 @@ static int det_cand_launch(const char* name, const DetSource* src, int num_sourc
   return MSCNN_OK;
 }
 
+// what list_of must be in the views forms (checked in front of everything the plain forms check)
+static int det_list_of_checked(const char* name, const int* list_of, int num_images, int num_lists) {
+  MSCNN_REQUIRE(list_of, "%s: null pointer (list_of)", name);
+  MSCNN_REQUIRE(num_lists >= 1, "%s: num_lists %d < 1", name, num_lists);
+  for (int b = 0; b < num_images; ++b)
+    MSCNN_REQUIRE(list_of[b] >= 0 && list_of[b] < num_lists, "%s: image %d: list_of %d outside [0, %d)", name, b, list_of[b], num_lists);
+  return MSCNN_OK;
+}
+
+// the plain add and its views form (list_of != NULL)
+static int det_cand_add_plain(const char* name, const mscnn_detections_desc* desc, const mscnn_detections_view* view, const int* list_of,
+                              int num_lists, const mscnn_nms_params* nms_in, int pass, int num_images, int num_classes,
+                              const float* bbox_pred, const float* cls_pred, const float* props, int R_all, void* cand, int cand_cap,
+                              void* stream) {
+  mscnn_nms_params nms;
+  if (int rc = mscnn_nms_params_resolve(nms_in, &nms)) return rc;
+  MSCNN_REQUIRE(desc && cand && bbox_pred && cls_pred && props, "%s: null pointer", name);
+  MSCNN_REQUIRE(num_images >= 1 && num_classes >= 1, "%s: %d images x %d classes", name, num_images, num_classes);
+  MSCNN_REQUIRE((long)num_images * num_classes <= (long)(1 << 24), "%s: %d images x %d classes", name, num_images, num_classes);
+  const int S = num_images * num_classes;
+  const int ncls = desc[0].ncls;
+  for (int s = 0; s < S; ++s)
+    MSCNN_REQUIRE(desc[s].ncls == ncls && desc[s].cls_id >= 1 && desc[s].cls_id <= ncls && ncls >= 2, "%s: segment %d: cls_id %d of %d", name, s,
+                  desc[s].cls_id, desc[s].ncls);
+  const DetSource src = {bbox_pred, cls_pred, props, ncls, 0};
+  return det_cand_launch(name, &src, 1, desc, view, 0.f, nms, pass, num_images, num_classes, R_all, cand, cand_cap, stream, list_of, num_lists);
+}
+
 extern "C" int mscnn_detections_candidates_add(const mscnn_detections_desc* desc, const mscnn_detections_view* view,
                                                const mscnn_nms_params* nms_in, int pass, int num_images, int num_classes,
                                                const float* bbox_pred, const float* cls_pred, const float* props, int R_all, void* cand,
                                                int cand_cap, void* stream) {
+  return det_cand_add_plain("detections_candidates_add", desc, view, nullptr, 0, nms_in, pass, num_images, num_classes, bbox_pred, cls_pred,
+                            props, R_all, cand, cand_cap, stream);
+}
+
+extern "C" int mscnn_detections_candidates_add_views(const mscnn_detections_desc* desc, const mscnn_detections_view* view, const int* list_of,
+                                                     const mscnn_nms_params* nms_in, int pass, int num_images, int num_lists, int num_classes,
+                                                     const float* bbox_pred, const float* cls_pred, const float* props, int R_all, void* cand,
+                                                     int cand_cap, void* stream) {
+  const char* name = "detections_candidates_add_views";
+  MSCNN_REQUIRE(num_images >= 1 && num_classes >= 1, "%s: %d images x %d classes", name, num_images, num_classes);
+  if (int rc = det_list_of_checked(name, list_of, num_images, num_lists)) return rc;
+  return det_cand_add_plain(name, desc, view, list_of, num_lists, nms_in, pass, num_images, num_classes, bbox_pred, cls_pred, props, R_all, cand,
+                            cand_cap, stream);
+}
+
+// the cascade add and its views form (list_of != NULL)
+static int det_cand_add_cascade(const char* name, const mscnn_detections_desc* desc, const mscnn_detections_view* view, const int* list_of,
+                                int num_lists, float det_thr, const mscnn_nms_params* nms_in, int pass, int num_images, int num_outputs,
+                                int num_classes, const mscnn_cascade_output* outputs, int R_all, void* cand, int cand_cap, void* stream) {
   mscnn_nms_params nms;
   if (int rc = mscnn_nms_params_resolve(nms_in, &nms)) return rc;
-  MSCNN_REQUIRE(desc && cand && bbox_pred && cls_pred && props, "detections_candidates_add: null pointer");
-  MSCNN_REQUIRE(num_images >= 1 && num_classes >= 1, "detections_candidates_add: %d images x %d classes", num_images, num_classes);
-  MSCNN_REQUIRE((long)num_images * num_classes <= (long)(1 << 24), "detections_candidates_add: %d images x %d classes", num_images, num_classes);
-  const int S = num_images * num_classes;
-  const int ncls = desc[0].ncls;
-  for (int s = 0; s < S; ++s)
-    MSCNN_REQUIRE(desc[s].ncls == ncls && desc[s].cls_id >= 1 && desc[s].cls_id <= ncls && ncls >= 2,
-                  "detections_candidates_add: segment %d: cls_id %d of %d", s, desc[s].cls_id, desc[s].ncls);
-  const DetSource src = {bbox_pred, cls_pred, props, ncls, 0};
-  return det_cand_launch("detections_candidates_add", &src, 1, desc, view, 0.f, nms, pass, num_images, num_classes, R_all, cand, cand_cap,
-                         stream);
+  MSCNN_REQUIRE(nms.det_thr == 0.f, "%s: nms params det_thr %g is the plain stage's: the cascade stage takes its det_thr as an argument", name,
+                (double)nms.det_thr);
+  MSCNN_REQUIRE(num_outputs >= 1 && num_outputs <= kCascadeMaxOutputs, "%s: %d cascade outputs (1 .. %d)", name, num_outputs,
+                kCascadeMaxOutputs);
+  MSCNN_REQUIRE(desc && outputs && cand, "%s: null pointer", name);
+  MSCNN_REQUIRE(num_images >= 1 && num_classes >= 1, "%s: %d images x %d classes", name, num_images, num_classes);
+  for (int o = 0; o < num_outputs; ++o) {
+    MSCNN_REQUIRE(outputs[o].boxes && outputs[o].cls_prob && outputs[o].props, "%s: output %d of %d: null pointer", name, o, num_outputs);
+    MSCNN_REQUIRE(outputs[o].ncls >= 2, "%s: output %d: %d probability columns", name, o, outputs[o].ncls);
+  }
+  const int K = num_outputs * num_classes;
+  MSCNN_REQUIRE((long)num_images * K <= (long)(1 << 24), "%s: %d images x %d outputs x %d classes", name, num_images, num_outputs, num_classes);
+  const int S = num_images * K;
+  for (int s = 0; s < S; ++s) {
+    const int o = (s % K) / num_classes;
+    MSCNN_REQUIRE(desc[s].cls_id >= 1 && desc[s].cls_id <= outputs[o].ncls, "%s: segment %d (output %d): cls_id %d of %d", name, s, o,
+                  desc[s].cls_id, outputs[o].ncls);
+  }
+  DetSource src[kCascadeMaxOutputs];
+  for (int o = 0; o < num_outputs; ++o) src[o] = DetSource{outputs[o].boxes, outputs[o].cls_prob, outputs[o].props, outputs[o].ncls, 1};
+  return det_cand_launch(name, src, num_outputs, desc, view, det_thr, nms, pass, num_images, num_classes, R_all, cand, cand_cap, stream, list_of,
+                         num_lists);
 }
 
 extern "C" int mscnn_detections_candidates_cascade_add(const mscnn_detections_desc* desc, const mscnn_detections_view* view, float det_thr,
                                                        const mscnn_nms_params* nms_in, int pass, int num_images, int num_outputs,
                                                        int num_classes, const mscnn_cascade_output* outputs, int R_all, void* cand,
                                                        int cand_cap, void* stream) {
-  mscnn_nms_params nms;
-  if (int rc = mscnn_nms_params_resolve(nms_in, &nms)) return rc;
-  MSCNN_REQUIRE(nms.det_thr == 0.f, "detections_candidates_cascade_add: nms params det_thr %g is the plain stage's: the cascade stage takes "
-                "its det_thr as an argument", (double)nms.det_thr);
-  MSCNN_REQUIRE(num_outputs >= 1 && num_outputs <= kCascadeMaxOutputs, "detections_candidates_cascade_add: %d cascade outputs (1 .. %d)",
-                num_outputs, kCascadeMaxOutputs);
-  MSCNN_REQUIRE(desc && outputs && cand, "detections_candidates_cascade_add: null pointer");
-  MSCNN_REQUIRE(num_images >= 1 && num_classes >= 1, "detections_candidates_cascade_add: %d images x %d classes", num_images, num_classes);
-  for (int o = 0; o < num_outputs; ++o) {
-    MSCNN_REQUIRE(outputs[o].boxes && outputs[o].cls_prob && outputs[o].props, "detections_candidates_cascade_add: output %d of %d: null pointer",
-                  o, num_outputs);
-    MSCNN_REQUIRE(outputs[o].ncls >= 2, "detections_candidates_cascade_add: output %d: %d probability columns", o, outputs[o].ncls);
-  }
-  const int K = num_outputs * num_classes;
-  MSCNN_REQUIRE((long)num_images * K <= (long)(1 << 24), "detections_candidates_cascade_add: %d images x %d outputs x %d classes", num_images,
-                num_outputs, num_classes);
-  const int S = num_images * K;
-  for (int s = 0; s < S; ++s) {
-    const int o = (s % K) / num_classes;
-    MSCNN_REQUIRE(desc[s].cls_id >= 1 && desc[s].cls_id <= outputs[o].ncls,
-                  "detections_candidates_cascade_add: segment %d (output %d): cls_id %d of %d", s, o, desc[s].cls_id, outputs[o].ncls);
-  }
-  DetSource src[kCascadeMaxOutputs];
-  for (int o = 0; o < num_outputs; ++o) src[o] = DetSource{outputs[o].boxes, outputs[o].cls_prob, outputs[o].props, outputs[o].ncls, 1};
-  return det_cand_launch("detections_candidates_cascade_add", src, num_outputs, desc, view, det_thr, nms, pass, num_images, num_classes, R_all,
-                         cand, cand_cap, stream);
+  return det_cand_add_cascade("detections_candidates_cascade_add", desc, view, nullptr, 0, det_thr, nms_in, pass, num_images, num_outputs,
+                              num_classes, outputs, R_all, cand, cand_cap, stream);
+}
+
+extern "C" int mscnn_detections_candidates_cascade_add_views(const mscnn_detections_desc* desc, const mscnn_detections_view* view,
+                                                             const int* list_of, float det_thr, const mscnn_nms_params* nms_in, int pass,
+                                                             int num_images, int num_lists, int num_outputs, int num_classes,
+                                                             const mscnn_cascade_output* outputs, int R_all, void* cand, int cand_cap,
+                                                             void* stream) {
+  const char* name = "detections_candidates_cascade_add_views";
+  MSCNN_REQUIRE(num_images >= 1 && num_classes >= 1, "%s: %d images x %d classes", name, num_images, num_classes);
+  if (int rc = det_list_of_checked(name, list_of, num_images, num_lists)) return rc;
+  return det_cand_add_cascade(name, desc, view, list_of, num_lists, det_thr, nms_in, pass, num_images, num_outputs, num_classes, outputs, R_all,
+                              cand, cand_cap, stream);
 }
 
 extern "C" size_t mscnn_detections_merge_workspace_bytes(int num_segments, int cand_cap) {

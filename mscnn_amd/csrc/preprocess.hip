@@ -157,6 +157,49 @@ int preprocess_launch(const unsigned char* const* imgs, unsigned char* const* mi
   return MSCNN_OK;
 }
 
+// ---- views: windows of uploaded frames, optionally mirrored, as the images of one batch (mscnn_preprocess_views_u8_f32) -------------
+// A view's first pass reads its window where it lies: win = the window's first pixel in its frame, pitch = the frame's row in
+// pixels, and the mirrored column is part of the tap's source index.  The taps are those of a w x h image (Taps mirrors at the
+// window's own borders, so no pixel outside the window is read), the intermediate is the window's own, and the second pass is
+// resize_finish_batch_kernel above on that intermediate: it never sees the frame.
+struct PreView {
+  const unsigned char* win;
+  unsigned char* mid;
+  int pitch, w, h, mh, mw, h_first, flip_x;
+};
+struct PreViewTable { PreView view[kMaxImages]; };      // 32 x 48 B = 1536 B of kernel arguments
+
+// window [h][w] of a frame -> mid [mh][w][3] (resize along H) or [h][mw][3] (along W); element i of mid
+template <int ALONG_W>
+__device__ __forceinline__ void resize_u8_view_elem(const PreView& d, long i) {
+  const int c = (int)(i % 3), x = (int)((i / 3) % d.mw), y = (int)(i / (3L * d.mw));
+  Taps t(ALONG_W ? d.w : d.h, ALONG_W ? d.mw : d.mh, ALONG_W ? x : y);
+  double acc = 0.0;
+  for (int k = 0; k < t.P; ++k) {
+    const int s = t.index(k);
+    const int row = ALONG_W ? y : s, col = ALONG_W ? s : x;
+    const double v = (double)d.win[((long)row * d.pitch + (d.flip_x ? d.w - 1 - col : col)) * 3 + c];
+    acc = acc + (t.raw(k) / t.sum) * v;
+  }
+  d.mid[i] = to_u8(acc);
+}
+
+// pass 1 of every view of the table: blockIdx.y = the view's slot, grid-stride over that view's intermediate along x
+__global__ __launch_bounds__(256) void resize_u8_views_kernel(const PreViewTable tab) {
+  const PreView& d = tab.view[blockIdx.y];
+  const long total = (long)d.mh * d.mw * 3;
+  const long step = (long)gridDim.x * 256;
+  if (d.h_first) {                                    // uniform per block
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += step) resize_u8_view_elem<0>(d, i);
+  } else {
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += step) resize_u8_view_elem<1>(d, i);
+  }
+}
+
+size_t view_mid_bytes(const mscnn_preprocess_view& v, int H, int W) {
+  return h_first_of(v.h, v.w, H, W) ? (size_t)H * v.w * 3 : (size_t)v.h * W * 3;
+}
+
 }  // namespace
 
 using namespace mscnn;
@@ -207,4 +250,70 @@ extern "C" int mscnn_preprocess_batch_u8_f32(const unsigned char* const* imgs_rg
     off += align256(mscnn_preprocess_workspace_bytes(org_h[b], org_w[b], H, W));
   }
   return preprocess_launch(imgs_rgb, mids.data(), org_h, org_w, count, out, H, W, mean_bgr, as_stream(stream));
+}
+
+extern "C" size_t mscnn_preprocess_views_workspace_bytes(const mscnn_preprocess_view* views, int count, int H, int W) {
+  // every view's intermediate at a 256-byte aligned offset, back to back; 0 for arguments the op refuses
+  if (count < 1 || !views || H <= 0 || W <= 0) return 0;
+  size_t total = 0;
+  for (int v = 0; v < count; ++v) {
+    if (views[v].w < 1 || views[v].h < 1) return 0;
+    total += align256(view_mid_bytes(views[v], H, W));
+  }
+  return total;
+}
+
+extern "C" int mscnn_preprocess_views_u8_f32(const unsigned char* const* frames_rgb, const int* org_h, const int* org_w, int num_frames,
+                                             const mscnn_preprocess_view* views, int count, float* out, int H, int W,
+                                             const float* mean_bgr, void* workspace, size_t workspace_bytes, void* stream) {
+  MSCNN_REQUIRE(frames_rgb && org_h && org_w && views && out && mean_bgr && workspace, "preprocess_views: null pointer");
+  MSCNN_REQUIRE(count >= 1, "preprocess_views: count %d < 1", count);
+  MSCNN_REQUIRE(num_frames >= 1, "preprocess_views: num_frames %d < 1", num_frames);
+  MSCNN_REQUIRE_ALIGNED(workspace, 16, "preprocess_views: workspace");
+  MSCNN_REQUIRE(H > 0 && W > 0, "preprocess_views: bad output shape %d x %d", H, W);
+  for (int f = 0; f < num_frames; ++f) {
+    MSCNN_REQUIRE(org_h[f] > 0 && org_w[f] > 0, "preprocess_views: frame %d has bad shape %d x %d", f, org_h[f], org_w[f]);
+    MSCNN_REQUIRE(frames_rgb[f], "preprocess_views: frame %d is a null pointer", f);
+  }
+  for (int v = 0; v < count; ++v) {
+    const mscnn_preprocess_view& q = views[v];
+    MSCNN_REQUIRE(q.frame >= 0 && q.frame < num_frames, "preprocess_views: view %d: frame %d outside [0, %d)", v, q.frame, num_frames);
+    MSCNN_REQUIRE(q.w >= 1 && q.h >= 1, "preprocess_views: view %d: window %d x %d (h x w) is empty", v, q.h, q.w);
+    MSCNN_REQUIRE(q.x0 >= 0 && q.y0 >= 0 && (long)q.x0 + q.w <= (long)org_w[q.frame] && (long)q.y0 + q.h <= (long)org_h[q.frame],
+                  "preprocess_views: view %d: window %d x %d (h x w) at (x0 %d, y0 %d) is not inside frame %d of %d x %d", v, q.h, q.w, q.x0,
+                  q.y0, q.frame, org_h[q.frame], org_w[q.frame]);
+    MSCNN_REQUIRE(q.flip_x == 0 || q.flip_x == 1, "preprocess_views: view %d: flip_x %d (0 or 1)", v, q.flip_x);
+  }
+  const size_t need = mscnn_preprocess_views_workspace_bytes(views, count, H, W);
+  MSCNN_REQUIRE(workspace_bytes >= need, "preprocess_views: workspace %zu bytes < %zu", workspace_bytes, need);
+  hipStream_t st = as_stream(stream);
+  size_t off = 0;
+  for (int c0 = 0; c0 < count; c0 += kMaxImages) {
+    const int m = count - c0 < kMaxImages ? count - c0 : kMaxImages;
+    PreViewTable vt = {};
+    PreTable tab = {};
+    long mid_max = 0;
+    for (int s = 0; s < m; ++s) {
+      const mscnn_preprocess_view& q = views[c0 + s];
+      const bool hf = h_first_of(q.h, q.w, H, W);
+      const int pitch = org_w[q.frame];
+      unsigned char* mid = static_cast<unsigned char*>(workspace) + off;
+      off += align256(view_mid_bytes(q, H, W));
+      vt.view[s] = PreView{frames_rgb[q.frame] + ((long)q.y0 * pitch + q.x0) * 3, mid, pitch, q.w, q.h, hf ? H : q.h, hf ? q.w : W, hf ? 1 : 0,
+                           q.flip_x};
+      tab.img[s] = PreImage{nullptr, mid, q.h, q.w, vt.view[s].mh, vt.view[s].mw, hf ? 1 : 0};      // (the second pass reads mid only)
+      const long e = (long)vt.view[s].mh * vt.view[s].mw * 3;
+      if (e > mid_max) mid_max = e;
+    }
+    long blocks = (mid_max + 255) / 256;
+    if (blocks > 65536) blocks = 65536;
+    resize_u8_views_kernel<<<dim3((unsigned)blocks, (unsigned)m), 256, 0, st>>>(vt);
+    MSCNN_POST_LAUNCH();
+    blocks = ((long)H * W + 255) / 256;
+    if (blocks > 65536) blocks = 65536;
+    resize_finish_batch_kernel<<<dim3((unsigned)blocks, (unsigned)m), 256, 0, st>>>(tab, out + (long)c0 * 3 * H * W, H, W, mean_bgr[0],
+                                                                                   mean_bgr[1], mean_bgr[2]);
+    MSCNN_POST_LAUNCH();
+  }
+  return MSCNN_OK;
 }

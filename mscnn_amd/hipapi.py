@@ -220,6 +220,14 @@ def lib():
                                                       [C.c_int, C.c_void_p, C.c_int, C.c_void_p])
         L.mscnn_detections_candidates_cascade_add.argtypes = ([C.c_void_p, C.c_void_p, C.c_float, C.c_void_p] + [C.c_int] * 4 +
                                                               [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p])
+        L.mscnn_detections_candidates_add_views.argtypes = ([C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p] * 3 +
+                                                            [C.c_int, C.c_void_p, C.c_int, C.c_void_p])
+        L.mscnn_detections_candidates_cascade_add_views.argtypes = ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p] + [C.c_int] * 5 +
+                                                                    [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p])
+        L.mscnn_preprocess_views_workspace_bytes.restype = C.c_size_t
+        L.mscnn_preprocess_views_workspace_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+        L.mscnn_preprocess_views_u8_f32.argtypes = ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                                     C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p])
         L.mscnn_detections_merge_workspace_bytes.restype = C.c_size_t
         L.mscnn_detections_merge_workspace_bytes.argtypes = [C.c_int, C.c_int]
         L.mscnn_detections_merge_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
@@ -764,6 +772,45 @@ def preprocess_batch(frames, out_h, out_w, mean_bgr=(104.0, 117.0, 123.0), out=N
     return out
 
 
+class PreprocessView(C.Structure):
+    """mscnn_preprocess_view: window [y0, y0 + h) x [x0, x0 + w) of frame `frame`, reversed along x when flip_x."""
+    _fields_ = [("frame", C.c_int), ("x0", C.c_int), ("y0", C.c_int), ("w", C.c_int), ("h", C.c_int), ("flip_x", C.c_int)]
+
+
+def view_array(views):
+    """views: dicts with frame (0), x0, y0, w, h, flip_x (0) -> the PreprocessView array."""
+    arr = (PreprocessView * max(len(views), 1))()
+    for i, v in enumerate(views):
+        arr[i].frame, arr[i].x0, arr[i].y0, arr[i].w, arr[i].h = int(v.get("frame", 0)), int(v["x0"]), int(v["y0"]), int(v["w"]), int(v["h"])
+        arr[i].flip_x = int(v.get("flip_x", 0))
+    return arr
+
+
+def preprocess_views(frames, views, out_h, out_w, mean_bgr=(104.0, 117.0, 123.0), out=None, ws=None):
+    """mscnn_preprocess_views_u8_f32: frames is a list of contiguous uint8 [h, w, 3] cuda tensors, views a list of dicts (frame, x0,
+    y0, w, h, flip_x) -> [len(views), 3, out_h, out_w]; slice v is bit-identical to preprocess() of a contiguous copy of the window
+    (mirrored when flip_x).  Two launches per 32 views; no copy of a window is made."""
+    F, V = len(frames), len(views)
+    for b, f in enumerate(frames):
+        if f.dim() != 3 or f.shape[2] != 3 or f.dtype != torch.uint8 or not f.is_cuda or not f.is_contiguous():
+            raise MscnnError(f"preprocess_views: frame {b} is not a contiguous uint8 [H, W, 3] cuda tensor")
+    dev = frames[0].device if F else "cuda"
+    if out is None:
+        out = torch.empty((max(V, 1), 3, out_h, out_w), dtype=torch.float32, device=dev)
+    L = lib()
+    oh = (C.c_int * max(F, 1))(*[int(f.shape[0]) for f in frames])
+    ow = (C.c_int * max(F, 1))(*[int(f.shape[1]) for f in frames])
+    ptrs = (C.c_void_p * max(F, 1))(*[f.data_ptr() for f in frames])
+    va = view_array(views)
+    wb = L.mscnn_preprocess_views_workspace_bytes(va, V, out_h, out_w)
+    if ws is None:
+        ws = torch.empty(max(wb, 1), dtype=torch.uint8, device=dev)
+    m = (C.c_float * 3)(*mean_bgr)
+    _check(L.mscnn_preprocess_views_u8_f32(ptrs, oh, ow, F, va, V, _dev(out), out_h, out_w, m, _dev(ws), C.c_size_t(ws.numel()), _stream()))
+    torch.cuda.current_stream().synchronize()     # ws dies with this batch
+    return out
+
+
 def nms_greedy(boxes_xywh, thr, mode="IOU"):
     n = boxes_xywh.shape[0]
     keep = torch.zeros(max(n, 1), dtype=torch.uint8, device=boxes_xywh.device)
@@ -1007,6 +1054,50 @@ class Candidates:
         k = self.passes if pass_index is None else pass_index
         _check(lib().mscnn_detections_candidates_cascade_add(descs, _view_array(views, num_images), C.c_float(det_thr), _nms_ref(nms), k,
                                                              num_images, O, Cn, outs, outputs[0][2].shape[0], _dev(self.buf), self.cap, _stream()))
+        self.passes += 1
+
+    def _view_descs(self, segments, ncls_of, num_images, list_of):
+        """The descs of the views forms: one per (image, slot) of THIS forward, K = slots per image; S = frames x K.  A list's overlap
+        for merge() is the one of the first image that reached it (0.5 for a list nothing reached)."""
+        K = len(segments) // max(num_images, 1)
+        if K < 1 or len(segments) != num_images * K or len(list_of) != num_images or self.S % K:
+            raise MscnnError(f"candidates: {len(segments)} segments and {len(list_of)} list_of entries for {num_images} images, {self.S} lists")
+        descs = (DetectionsDesc * len(segments))()
+        for s, kw in enumerate(segments):
+            _fill_desc(descs[s], ncls_of(s % K), kw)
+        if self.overlap is None:
+            self.overlap, self._overlap_known = [0.5] * self.S, set()
+        for s in range(len(segments)):
+            l = list_of[s // K] * K + s % K
+            if 0 <= l < self.S and l not in self._overlap_known:
+                self.overlap[l] = descs[s].nms_overlap
+                self._overlap_known.add(l)
+        return descs, K
+
+    def add_views(self, bbox_pred, cls_pred, props, num_images, segments, list_of, views=None, nms=NMS_NULL, pass_index=None):
+        """mscnn_detections_candidates_add_views: the images of ONE batched forward into the lists of their frames.  segments: one dict
+        per (image, class) of this forward; list_of: the frame of each image; the lists were made for frames x classes segments."""
+        descs, K = self._view_descs(segments, lambda k: cls_pred.shape[1], num_images, list_of)
+        k = self.passes if pass_index is None else pass_index
+        lo = (C.c_int * num_images)(*[int(v) for v in list_of])
+        _check(lib().mscnn_detections_candidates_add_views(descs, _view_array(views, num_images), lo, _nms_ref(nms), k, num_images,
+                                                           self.S // K, K, _dev(bbox_pred), _dev(cls_pred), _dev(props), props.shape[0],
+                                                           _dev(self.buf), self.cap, _stream()))
+        self.passes += 1
+
+    def cascade_add_views(self, outputs, num_images, segments, list_of, det_thr=0.0, views=None, nms=NMS_NULL, pass_index=None):
+        """mscnn_detections_candidates_cascade_add_views: outputs and segments as in cascade_add, for the images of this forward."""
+        O = len(outputs)
+        outs = (CascadeOutput * max(O, 1))()
+        for o, (boxes, cls_prob, props) in enumerate(outputs):
+            outs[o].boxes, outs[o].cls_prob, outs[o].props, outs[o].ncls = _dev(boxes).value, _dev(cls_prob).value, _dev(props).value, cls_prob.shape[1]
+        Cn = len(segments) // max(num_images * O, 1)
+        descs, K = self._view_descs(segments, lambda k: outs[k // max(Cn, 1)].ncls, num_images, list_of)
+        k = self.passes if pass_index is None else pass_index
+        lo = (C.c_int * num_images)(*[int(v) for v in list_of])
+        _check(lib().mscnn_detections_candidates_cascade_add_views(descs, _view_array(views, num_images), lo, C.c_float(det_thr), _nms_ref(nms), k,
+                                                                   num_images, self.S // K, O, Cn, outs, outputs[0][2].shape[0], _dev(self.buf),
+                                                                   self.cap, _stream()))
         self.passes += 1
 
     def counts(self):

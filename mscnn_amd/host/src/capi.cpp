@@ -38,7 +38,8 @@ struct mscnn_net {
     bool open = false;
     int images = 0, slots = 0, cand_cap = 0, passes = 0, handoff_errors = 0;      // slots: per image (classes, or outputs x classes)
     long rows = 0;                         // sum of R_all over the adds so far: the host-known bound on any list
-    std::vector<double> overlap;           // per segment, from the first add
+    std::vector<double> overlap;           // per segment, from the first add that reached the segment's list
+    std::vector<char> overlap_known;       // (the views adds may leave a list without an image for a while)
     caffe::DeviceBuffer cand;
   } merge;
   ~mscnn_net() {
@@ -364,6 +365,48 @@ int mscnn_net_set_images(mscnn_net* n, const char* name, const unsigned char* co
     void* ws = n->img_ws.Reserve(wb);
     static const float kMean[3] = {104.f, 117.f, 123.f};      // run_mscnn_detection.m:38
     const int rc = mscnn_preprocess_batch_u8_f32(dev.data(), org_h, org_w, count, b->mutable_gpu_data(), H, W,
+                                                 mean_bgr ? mean_bgr : kMean, ws, wb, st);
+    CHECK_EQ(rc, 0) << mscnn_last_error();
+  });
+}
+int mscnn_net_set_image_views(mscnn_net* n, const char* name, const unsigned char* const* frames_rgb, int on_device, const int* org_h,
+                              const int* org_w, int num_frames, const mscnn_preprocess_view* views, int count, const float* mean_bgr) {
+  return guarded([&] {
+    CHECK(n->net->has_blob(name)) << "Unknown blob name " << name;
+    auto b = n->net->blob_by_name(name);
+    CHECK(b->num_axes() == 4 && b->channels() == 3) << "set_image_views: blob " << name << " has shape " << b->shape_string();
+    CHECK(count == b->num()) << "set_image_views: " << count << " views for blob " << name << " of shape " << b->shape_string();
+    CHECK(frames_rgb && org_h && org_w && views) << "set_image_views: null pointer";
+    CHECK_GE(num_frames, 1) << "set_image_views: num_frames " << num_frames;
+    const int H = b->height(), W = b->width();
+    for (int f = 0; f < num_frames; ++f)
+      CHECK(frames_rgb[f] && org_h[f] > 0 && org_w[f] > 0) << "set_image_views: frame " << f << " is " << org_h[f] << " x " << org_w[f]
+                                                          << (frames_rgb[f] ? "" : " at a null pointer");
+    for (int v = 0; v < count; ++v) {      // (the op refuses the same: here nothing has been uploaded yet)
+      const mscnn_preprocess_view& q = views[v];
+      CHECK(q.frame >= 0 && q.frame < num_frames) << "set_image_views: view " << v << ": frame " << q.frame << " outside [0, " << num_frames << ")";
+      CHECK(q.w >= 1 && q.h >= 1 && q.x0 >= 0 && q.y0 >= 0 && (long)q.x0 + q.w <= (long)org_w[q.frame] && (long)q.y0 + q.h <= (long)org_h[q.frame])
+          << "set_image_views: view " << v << ": window " << q.h << " x " << q.w << " (h x w) at (x0 " << q.x0 << ", y0 " << q.y0
+          << ") is empty or not inside frame " << q.frame << " of " << org_h[q.frame] << " x " << org_w[q.frame];
+      CHECK(q.flip_x == 0 || q.flip_x == 1) << "set_image_views: view " << v << ": flip_x " << q.flip_x << " (0 or 1)";
+    }
+    CHECK_GE(n->device, 0) << "set_image_views: the net was built with device " << n->device << " (graph only)";
+    n->net->MaterializePendingReadersOf(name);      // (as set_image)
+    hipStream_t st = (hipStream_t)Caffe::stream();
+    std::vector<const unsigned char*> dev(frames_rgb, frames_rgb + num_frames);
+    if (!on_device) {                               // every frame once, whatever the number of its views (256-byte aligned offsets)
+      std::vector<size_t> off(num_frames + 1, 0);
+      for (int f = 0; f < num_frames; ++f) off[f + 1] = off[f] + (((size_t)org_h[f] * org_w[f] * 3 + 255) & ~(size_t)255);
+      unsigned char* d = static_cast<unsigned char*>(n->img_in.Reserve(off[num_frames]));
+      for (int f = 0; f < num_frames; ++f) {
+        HIP_CHECK(hipMemcpyAsync(d + off[f], frames_rgb[f], (size_t)org_h[f] * org_w[f] * 3, hipMemcpyHostToDevice, st));
+        dev[f] = d + off[f];
+      }
+    }
+    const size_t wb = mscnn_preprocess_views_workspace_bytes(views, count, H, W);
+    void* ws = n->img_ws.Reserve(wb);
+    static const float kMean[3] = {104.f, 117.f, 123.f};      // run_mscnn_detection.m:38
+    const int rc = mscnn_preprocess_views_u8_f32(dev.data(), org_h, org_w, num_frames, views, count, b->mutable_gpu_data(), H, W,
                                                  mean_bgr ? mean_bgr : kMean, ws, wb, st);
     CHECK_EQ(rc, 0) << mscnn_last_error();
   });
@@ -1178,12 +1221,15 @@ int mscnn_net_detect_merge_begin(mscnn_net* n, int num_images, int num_classes, 
     MSCNN_CHECK(mscnn_detections_candidates_reset(m.cand.Reserve(bytes), S, cand_cap, Caffe::stream()));
     m.open = true; m.images = num_images; m.slots = num_classes; m.cand_cap = cand_cap; m.passes = 0; m.rows = 0;
     m.handoff_errors = n->net->handoff_errors();
-    m.overlap.clear();
+    m.overlap.assign(S, 0.5);      // (a list no add ever reaches stays empty: its overlap is never applied)
+    m.overlap_known.assign(S, 0);
   });
 }
 
-// What both add calls check alike before anything is enqueued; R_all = the rows of this forward's ROI blobs.
-static void merge_add_checked(mscnn_net* n, const char* name, const mscnn_detect_params* p, int num_images, int slots, int R_all) {
+// What the add calls check alike before anything is enqueued; R_all = the rows of this forward's ROI blobs.  list_of (NULL: image i
+// is list i): the lists of which frame each of the num_images images of this forward goes to.
+static void merge_add_checked(mscnn_net* n, const char* name, const mscnn_detect_params* p, int num_images, int slots, int R_all,
+                              const int* list_of = nullptr) {
   mscnn_net::Merge& m = n->merge;
   CHECK(p != nullptr) << name << ": null params";
   CHECK_EQ(slots, m.slots) << name << ": " << slots << " slots per image, the merge was begun with " << m.slots;
@@ -1191,79 +1237,125 @@ static void merge_add_checked(mscnn_net* n, const char* name, const mscnn_detect
   CHECK_LE(m.rows + R_all, (long)m.cand_cap) << name << ": the " << m.passes << " forwards added so far have " << m.rows
                                              << " ROI rows, this one " << R_all << ": more than cand_cap " << m.cand_cap;
   const int S = num_images * slots;
+  std::vector<double> seen(m.overlap);
+  std::vector<char> known(m.overlap_known);
   for (int s = 0; s < S; ++s) {
     CHECK(!(p[s].nms_overlap != p[s].nms_overlap)) << name << ": segment " << s << ": nms_overlap is NaN";
-    if (m.passes > 0)
-      CHECK(p[s].nms_overlap == m.overlap[s]) << name << ": segment " << s << ": nms_overlap " << p[s].nms_overlap
-                                              << ", the first forward of this merge was added with " << m.overlap[s];
+    const int l = (list_of ? list_of[s / slots] : s / slots) * slots + s % slots;
+    if (known[l])
+      CHECK(p[s].nms_overlap == seen[l]) << name << ": segment " << s << ": nms_overlap " << p[s].nms_overlap
+                                         << (m.overlap_known[l] ? ", the first forward of this merge was added with " : ", an image of this forward in front of it goes to the same list with ")
+                                         << seen[l];
+    seen[l] = p[s].nms_overlap; known[l] = 1;
   }
 }
-static void merge_added(mscnn_net* n, const mscnn_detect_params* p, int S, int R_all) {
+static void merge_added(mscnn_net* n, const mscnn_detect_params* p, int S, int R_all, const int* list_of = nullptr) {
   mscnn_net::Merge& m = n->merge;
-  if (m.passes == 0) { m.overlap.resize(S); for (int s = 0; s < S; ++s) m.overlap[s] = p[s].nms_overlap; }
+  for (int s = 0; s < S; ++s) {
+    const int l = (list_of ? list_of[s / m.slots] : s / m.slots) * m.slots + s % m.slots;
+    if (!m.overlap_known[l]) { m.overlap[l] = p[s].nms_overlap; m.overlap_known[l] = 1; }
+  }
   ++m.passes;
   m.rows += R_all;
+}
+// list_of of the views adds: one entry per image of the input, each a frame of the open merge
+static void merge_list_of_checked(mscnn_net* n, const char* name, const int* list_of, int num_images) {
+  CHECK(list_of != nullptr) << name << ": null list_of";
+  for (int b = 0; b < num_images; ++b)
+    CHECK(list_of[b] >= 0 && list_of[b] < n->merge.images) << name << ": image " << b << ": list_of " << list_of[b] << " outside [0, "
+                                                           << n->merge.images << "): the merge was begun with " << n->merge.images << " frames";
 }
 static int merge_input_images(mscnn_net* n) {
   return n->net->num_inputs() > 0 && n->net->input_blobs()[0]->num_axes() == 4 ? n->net->input_blobs()[0]->num() : 1;
 }
 
-int mscnn_net_detect_merge_add(mscnn_net* n, const mscnn_detect_params* p, const mscnn_detections_view* view) {
-  return guarded([&] {
-    mscnn_net::Merge& m = n->merge;
-    CHECK(m.open) << "detect_merge_add: no merge is open (call mscnn_net_detect_merge_begin first)";
-    const int num = merge_input_images(n);
-    CHECK_EQ(m.images, num) << "detect_merge_add: the merge was begun with " << m.images << " images but the net's input holds " << num;
-    CHECK(n->net->has_blob("bbox_pred") && n->net->has_blob("cls_pred") && n->net->has_blob("proposals_score"))
-        << "detect_merge_add: net has no bbox_pred / cls_pred / proposals_score outputs";
-    auto bbox = n->net->blob_by_name("bbox_pred");
-    auto cls = n->net->blob_by_name("cls_pred");
-    auto props = n->net->blob_by_name("proposals_score");
-    const int R_all = props->num();
-    CHECK_GE(R_all, 1);
-    CHECK(bbox->num() == R_all && cls->num() == R_all) << "detect_merge_add: bbox_pred has " << bbox->num() << " rows, cls_pred " << cls->num()
-                                                        << ", proposals_score " << R_all;
-    const int ncls = cls->count() / R_all;
-    CHECK_EQ(bbox->count() / R_all, 4 * ncls);
-    merge_add_checked(n, "detect_merge_add", p, m.images, m.slots, R_all);
-    const int S = m.images * m.slots;
-    std::vector<mscnn_detections_desc> desc(S);
-    for (int s = 0; s < S; ++s) {
-      mscnn_detections_desc& d = desc[s];
-      d.ncls = ncls;
-      d.cls_id = p[s].cls_id;
-      CHECK(d.cls_id >= 1 && d.cls_id <= ncls) << "detect_merge_add: segment " << s << ": cls_id " << d.cls_id << " of " << ncls;
-      for (int k = 0; k < 4; ++k) { d.bbox_mean[k] = p[s].bbox_mean[k]; d.bbox_std[k] = p[s].bbox_std[k]; }
-      d.proposal_thr = p[s].proposal_thr;
-      d.ratio_h = p[s].ratio_h; d.ratio_w = p[s].ratio_w; d.org_h = p[s].org_h; d.org_w = p[s].org_w; d.nms_overlap = p[s].nms_overlap;
-    }
+// the plain add (list_of NULL: the merge's images are the input's) and its views form (any N, image b to the lists of frame list_of[b])
+static void merge_add_plain(mscnn_net* n, const char* name, const mscnn_detect_params* p, const mscnn_detections_view* view, bool views,
+                            const int* list_of) {
+  const std::string nm(name);
+  mscnn_net::Merge& m = n->merge;
+  CHECK(m.open) << nm << ": no merge is open (call mscnn_net_detect_merge_begin first)";
+  const int num = merge_input_images(n);
+  if (views) merge_list_of_checked(n, name, list_of, num);
+  else CHECK_EQ(m.images, num) << nm << ": the merge was begun with " << m.images << " images but the net's input holds " << num;
+  CHECK(n->net->has_blob("bbox_pred") && n->net->has_blob("cls_pred") && n->net->has_blob("proposals_score"))
+      << nm << ": net has no bbox_pred / cls_pred / proposals_score outputs";
+  auto bbox = n->net->blob_by_name("bbox_pred");
+  auto cls = n->net->blob_by_name("cls_pred");
+  auto props = n->net->blob_by_name("proposals_score");
+  const int R_all = props->num();
+  CHECK_GE(R_all, 1);
+  CHECK(bbox->num() == R_all && cls->num() == R_all) << nm << ": bbox_pred has " << bbox->num() << " rows, cls_pred " << cls->num()
+                                                      << ", proposals_score " << R_all;
+  const int ncls = cls->count() / R_all;
+  CHECK_EQ(bbox->count() / R_all, 4 * ncls);
+  merge_add_checked(n, name, p, num, m.slots, R_all, list_of);
+  const int S = num * m.slots;
+  std::vector<mscnn_detections_desc> desc(S);
+  for (int s = 0; s < S; ++s) {
+    mscnn_detections_desc& d = desc[s];
+    d.ncls = ncls;
+    d.cls_id = p[s].cls_id;
+    CHECK(d.cls_id >= 1 && d.cls_id <= ncls) << nm << ": segment " << s << ": cls_id " << d.cls_id << " of " << ncls;
+    for (int k = 0; k < 4; ++k) { d.bbox_mean[k] = p[s].bbox_mean[k]; d.bbox_std[k] = p[s].bbox_std[k]; }
+    d.proposal_thr = p[s].proposal_thr;
+    d.ratio_h = p[s].ratio_h; d.ratio_w = p[s].ratio_w; d.org_h = p[s].org_h; d.org_w = p[s].org_w; d.nms_overlap = p[s].nms_overlap;
+  }
+  if (list_of)
+    MSCNN_CHECK(mscnn_detections_candidates_add_views(desc.data(), view, list_of, nms_arg(n, false), m.passes, num, m.images, m.slots,
+                                                      bbox->gpu_data(), cls->gpu_data(), props->gpu_data(), R_all, m.cand.get(), m.cand_cap,
+                                                      Caffe::stream()));
+  else
     MSCNN_CHECK(mscnn_detections_candidates_add(desc.data(), view, nms_arg(n, false), m.passes, m.images, m.slots, bbox->gpu_data(),
                                                 cls->gpu_data(), props->gpu_data(), R_all, m.cand.get(), m.cand_cap, Caffe::stream()));
-    merge_added(n, p, S, R_all);
-  });
+  merge_added(n, p, S, R_all, list_of);
+}
+
+int mscnn_net_detect_merge_add(mscnn_net* n, const mscnn_detect_params* p, const mscnn_detections_view* view) {
+  return guarded([&] { merge_add_plain(n, "detect_merge_add", p, view, false, nullptr); });
+}
+int mscnn_net_detect_merge_add_views(mscnn_net* n, const mscnn_detect_params* p, const mscnn_detections_view* view, const int* list_of) {
+  return guarded([&] { merge_add_plain(n, "detect_merge_add_views", p, view, true, list_of); });
+}
+
+static void merge_add_cascade(mscnn_net* n, const char* name, const mscnn_detect_params* p, const mscnn_detections_view* view,
+                              bool views, const int* list_of, int num_outputs, const char* const* bbox_blobs,
+                              const char* const* prob_blobs, const char* const* proposal_blobs, float det_thr) {
+  const std::string nm(name);
+  mscnn_net::Merge& m = n->merge;
+  CHECK(m.open) << nm << ": no merge is open (call mscnn_net_detect_merge_begin first)";
+  const int num = merge_input_images(n);
+  if (views) merge_list_of_checked(n, name, list_of, num);
+  else CHECK_EQ(m.images, num) << nm << ": the merge was begun with " << m.images << " images but the net's input holds " << num;
+  const CascadeBlobs b = cascade_blobs(n, num_outputs, bbox_blobs, prob_blobs, proposal_blobs);
+  CHECK_EQ(m.slots % num_outputs, 0) << nm << ": the merge was begun with " << m.slots << " slots per image, not a multiple of "
+                                     << num_outputs << " cascade outputs";
+  const int C = m.slots / num_outputs;
+  merge_add_checked(n, name, p, num, m.slots, b.R_all, list_of);
+  const int S = num * m.slots;
+  const auto desc = cascade_descs(n, p, num, num_outputs, C, b, m.slots * b.R_all);
+  std::vector<mscnn_cascade_output> outs(num_outputs);
+  for (int o = 0; o < num_outputs; ++o)
+    outs[o] = mscnn_cascade_output{b.src[o].boxes->gpu_data(), b.src[o].cls->gpu_data(), b.src[o].props->gpu_data(), b.src[o].ncls};
+  if (list_of)
+    MSCNN_CHECK(mscnn_detections_candidates_cascade_add_views(desc.data(), view, list_of, det_thr, nms_arg(n, true), m.passes, num, m.images,
+                                                              num_outputs, C, outs.data(), b.R_all, m.cand.get(), m.cand_cap, Caffe::stream()));
+  else
+    MSCNN_CHECK(mscnn_detections_candidates_cascade_add(desc.data(), view, det_thr, nms_arg(n, true), m.passes, m.images, num_outputs, C,
+                                                        outs.data(), b.R_all, m.cand.get(), m.cand_cap, Caffe::stream()));
+  merge_added(n, p, S, b.R_all, list_of);
 }
 
 int mscnn_net_detect_cascade_merge_add(mscnn_net* n, const mscnn_detect_params* p, const mscnn_detections_view* view, int num_outputs,
                                        const char* const* bbox_blobs, const char* const* prob_blobs, const char* const* proposal_blobs,
                                        float det_thr) {
+  return guarded([&] { merge_add_cascade(n, "detect_cascade_merge_add", p, view, false, nullptr, num_outputs, bbox_blobs, prob_blobs, proposal_blobs, det_thr); });
+}
+int mscnn_net_detect_cascade_merge_add_views(mscnn_net* n, const mscnn_detect_params* p, const mscnn_detections_view* view, const int* list_of,
+                                             int num_outputs, const char* const* bbox_blobs, const char* const* prob_blobs,
+                                             const char* const* proposal_blobs, float det_thr) {
   return guarded([&] {
-    mscnn_net::Merge& m = n->merge;
-    CHECK(m.open) << "detect_cascade_merge_add: no merge is open (call mscnn_net_detect_merge_begin first)";
-    const int num = merge_input_images(n);
-    CHECK_EQ(m.images, num) << "detect_cascade_merge_add: the merge was begun with " << m.images << " images but the net's input holds " << num;
-    const CascadeBlobs b = cascade_blobs(n, num_outputs, bbox_blobs, prob_blobs, proposal_blobs);
-    CHECK_EQ(m.slots % num_outputs, 0) << "detect_cascade_merge_add: the merge was begun with " << m.slots << " slots per image, not a multiple of "
-                                       << num_outputs << " cascade outputs";
-    const int C = m.slots / num_outputs;
-    merge_add_checked(n, "detect_cascade_merge_add", p, m.images, m.slots, b.R_all);
-    const int S = m.images * m.slots;
-    const auto desc = cascade_descs(n, p, m.images, num_outputs, C, b, m.slots * b.R_all);
-    std::vector<mscnn_cascade_output> outs(num_outputs);
-    for (int o = 0; o < num_outputs; ++o)
-      outs[o] = mscnn_cascade_output{b.src[o].boxes->gpu_data(), b.src[o].cls->gpu_data(), b.src[o].props->gpu_data(), b.src[o].ncls};
-    MSCNN_CHECK(mscnn_detections_candidates_cascade_add(desc.data(), view, det_thr, nms_arg(n, true), m.passes, m.images, num_outputs, C,
-                                                        outs.data(), b.R_all, m.cand.get(), m.cand_cap, Caffe::stream()));
-    merge_added(n, p, S, b.R_all);
+    merge_add_cascade(n, "detect_cascade_merge_add_views", p, view, true, list_of, num_outputs, bbox_blobs, prob_blobs, proposal_blobs, det_thr);
   });
 }
 

@@ -33,6 +33,11 @@ class DetectionsView(C.Structure):
     _fields_ = [("off_x", C.c_double), ("off_y", C.c_double), ("flip_x", C.c_int)]
 
 
+class PreprocessView(C.Structure):
+    """mscnn_preprocess_view (include/mscnn_net.h): window [y0, y0 + h) x [x0, x0 + w) of frame `frame`, reversed along x when flip_x."""
+    _fields_ = [("frame", C.c_int), ("x0", C.c_int), ("y0", C.c_int), ("w", C.c_int), ("h", C.c_int), ("flip_x", C.c_int)]
+
+
 NMS_TYPES = ("maxg", "max", "ms", "cover", "none")      # (the last three exist to be refused by name)
 OVR_DNMS = ("union", "min")
 
@@ -80,6 +85,7 @@ def lib():
             "mscnn_net_set_blob": [vp, cs, vp, C.c_size_t], "mscnn_net_set_blob_device": [vp, cs, vp, C.c_size_t],
             "mscnn_net_set_image": [vp, cs, vp, ci, ci, ci, vp],
             "mscnn_net_set_images": [vp, cs, vp, ci, vp, vp, ci, vp],
+            "mscnn_net_set_image_views": [vp, cs, vp, ci, vp, vp, ci, vp, ci, vp],
             "mscnn_net_get_blob": [vp, cs, vp, C.c_size_t, vp], "mscnn_net_blob_device_ptr": [vp, cs],
             "mscnn_net_forward": [vp], "mscnn_net_forward_from_to": [vp, ci, ci], "mscnn_net_reshape": [vp],
             "mscnn_net_set_layer_timing": [vp, ci], "mscnn_net_layer_ms": [vp, ci],
@@ -103,6 +109,8 @@ def lib():
             "mscnn_net_detect_merge_begin": [vp, ci, ci, ci], "mscnn_net_detect_merge_add": [vp, vp, vp],
             "mscnn_net_detect_cascade_merge_add": [vp, vp, vp, ci, vp, vp, vp, C.c_float],
             "mscnn_net_detect_merge_end": [vp, vp, vp, vp, ci, vp, vp],
+            "mscnn_net_detect_merge_add_views": [vp, vp, vp, vp],
+            "mscnn_net_detect_cascade_merge_add_views": [vp, vp, vp, vp, ci, vp, vp, vp, C.c_float],
         }
         for name, args in sig.items():
             getattr(L, name).argtypes = args
@@ -113,6 +121,38 @@ def lib():
 def _check(rc):
     if rc != 0:
         raise NetError(lib().mscnn_net_last_error().decode())
+
+
+def tile_views(org_hw, rows, cols, overlap=0, flip=False, input_hw=None, frame=0):
+    """The views that cut a frame of org_hw = (h, w) into rows x cols tiles which overlap by `overlap` pixels, and with flip their
+    mirrors behind them.  Pure: no net, no device.  Every window has ONE size -- ceil((extent + (n - 1) * overlap) / n) per axis --,
+    lies inside the frame, and together they cover it: the last row and column are shifted inwards, not shrunk.
+    Returns (views, params, merge_views), one entry per view:
+      views        dicts frame, x0, y0, w, h, flip_x                     for Net.set_image_views
+      params       dicts org_hw = the window's size, and with input_hw   for detect_merge_add: ratios = net input / window size
+                   = (H, W) of the net's input also ratios
+      merge_views  dicts off_x = x0, off_y = y0, flip_x                  for detect_merge_add(..., views=, list_of=)"""
+    H, W = int(org_hw[0]), int(org_hw[1])
+    rows, cols, overlap = int(rows), int(cols), int(overlap)
+    if H < 1 or W < 1 or rows < 1 or cols < 1 or rows > H or cols > W or overlap < 0:
+        raise ValueError(f"tile_views: a {H} x {W} frame in {rows} x {cols} tiles with {overlap} pixels of overlap")
+    th = -(-(H + (rows - 1) * overlap) // rows)
+    tw = -(-(W + (cols - 1) * overlap) // cols)
+    if th > H or tw > W or (rows > 1 and overlap >= th) or (cols > 1 and overlap >= tw):
+        raise ValueError(f"tile_views: {rows} x {cols} tiles of a {H} x {W} frame with {overlap} pixels of overlap would be {th} x {tw}")
+    ys = [min(r * (th - overlap), H - th) for r in range(rows)]
+    xs = [min(c * (tw - overlap), W - tw) for c in range(cols)]
+    views, params, merge_views = [], [], []
+    for fl in ((0, 1) if flip else (0,)):
+        for y0 in ys:
+            for x0 in xs:
+                views.append(dict(frame=frame, x0=x0, y0=y0, w=tw, h=th, flip_x=fl))
+                p = dict(org_hw=(th, tw))
+                if input_hw is not None:
+                    p["ratios"] = (input_hw[0] / float(th), input_hw[1] / float(tw))
+                params.append(p)
+                merge_views.append(dict(off_x=float(x0), off_y=float(y0), flip_x=fl))
+    return views, params, merge_views
 
 
 class Net:
@@ -339,6 +379,39 @@ class Net:
                                           (C.c_int * max(B, 1))(*hs), (C.c_int * max(B, 1))(*ws), B, m))
         H, W = self.blob_shape(name)[2:]
         return [{"ratios": (H / float(h), W / float(w)), "org_hw": (h, w)} for h, w in zip(hs, ws)]
+
+    def set_image_views(self, name, frames, views, mean_bgr=None):
+        """mscnn_net_set_image_views: views of one or more frames as the images of blob `name`.  frames: a list of uint8 [h, w, 3]
+        numpy arrays (each uploaded once) or of contiguous uint8 torch CUDA tensors; views: one dict per image of the blob with
+        frame (0), x0, y0, w, h, flip_x (0) -- tile_views makes them.  Slice v is what set_image writes for a contiguous copy of the
+        window.  Returns one dict per view, {"ratios": (H / h, W / w), "org_hw": (h, w)}: the params detect_merge_add takes."""
+        frames = list(frames)
+        on_dev = [hasattr(f, "is_cuda") and f.is_cuda for f in frames]
+        if any(on_dev) and not all(on_dev):
+            raise NetError("set_image_views: a list that mixes host and device frames")
+        device = any(on_dev)
+        keep = []
+        for b, f in enumerate(frames):
+            if device:
+                if str(f.dtype) != "torch.uint8" or f.dim() != 3 or f.shape[2] != 3 or not f.is_contiguous():
+                    raise NetError(f"set_image_views: frame {b} is not a contiguous uint8 [h, w, 3] tensor")
+                keep.append(f)
+            else:
+                if not isinstance(f, np.ndarray) or f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3:
+                    raise NetError(f"set_image_views: frame {b} is not a uint8 [h, w, 3] array")
+                keep.append(np.ascontiguousarray(f))
+        ptrs = [f.data_ptr() for f in keep] if device else [a.ctypes.data for a in keep]
+        F, V = len(keep), len(views)
+        va = (PreprocessView * max(V, 1))()
+        for i, v in enumerate(views):
+            va[i].frame, va[i].x0, va[i].y0, va[i].w, va[i].h = int(v.get("frame", 0)), int(v["x0"]), int(v["y0"]), int(v["w"]), int(v["h"])
+            va[i].flip_x = int(v.get("flip_x", 0))
+        m = (C.c_float * 3)(*mean_bgr) if mean_bgr is not None else None
+        _check(lib().mscnn_net_set_image_views(self._h, name.encode(), (C.c_void_p * max(F, 1))(*ptrs), 1 if device else 0,
+                                               (C.c_int * max(F, 1))(*[int(f.shape[0]) for f in keep]),
+                                               (C.c_int * max(F, 1))(*[int(f.shape[1]) for f in keep]), F, va, V, m))
+        H, W = self.blob_shape(name)[2:]
+        return [{"ratios": (H / float(va[i].h), W / float(va[i].w)), "org_hw": (va[i].h, va[i].w)} for i in range(V)]
 
     def get_blob(self, name):
         a = np.empty(self.blob_shape(name), np.float32)
@@ -580,16 +653,32 @@ class Net:
         _check(lib().mscnn_net_detect_merge_begin(self._h, num_images, num_classes, cand_cap))
         self._merge_shape = (num_images, num_classes, cand_cap)
 
-    def detect_merge_add(self, params, classes, views=None):
+    def detect_merge_add(self, params, classes, views=None, *, list_of=None):
         """mscnn_net_detect_merge_add after a forward.  params: one dict per image as in detect_multi, describing THIS forward's view
-        (ratios = input size / view size, org_hw = the view's size); views: None or one dict per image (off_x, off_y, flip_x)."""
+        (ratios = input size / view size, org_hw = the view's size); views: None or one dict per image (off_x, off_y, flip_x).
+        list_of (keyword only): mscnn_net_detect_merge_add_views -- the input's images are views of the merge's frames, image b goes to
+        the lists of frame list_of[b]; one call is one pass, a list's order (add call, image, row)."""
         p = self._multi_params(params, classes)
-        _check(lib().mscnn_net_detect_merge_add(self._h, p, self._views(views, len(params))))
+        if list_of is None:
+            _check(lib().mscnn_net_detect_merge_add(self._h, p, self._views(views, len(params))))
+            return
+        _check(lib().mscnn_net_detect_merge_add_views(self._h, p, self._views(views, len(params)), self._list_of(list_of, len(params))))
 
-    def detect_cascade_merge_add(self, params, outputs, classes, det_thr=0.0, views=None):
-        """mscnn_net_detect_cascade_merge_add: the same for a cascade deploy; outputs, classes, det_thr as in detect_cascade_multi."""
+    @staticmethod
+    def _list_of(list_of, B):
+        if len(list_of) != B:
+            raise NetError(f"detect_merge: {len(list_of)} list_of entries for {B} images")
+        return (C.c_int * max(B, 1))(*[int(v) for v in list_of])
+
+    def detect_cascade_merge_add(self, params, outputs, classes, det_thr=0.0, views=None, *, list_of=None):
+        """mscnn_net_detect_cascade_merge_add: the same for a cascade deploy; outputs, classes, det_thr as in detect_cascade_multi.
+        list_of (keyword only): mscnn_net_detect_cascade_merge_add_views, as in detect_merge_add."""
         p, (bb, pb, qb) = self._cascade_multi_args(params, outputs, classes)
-        _check(lib().mscnn_net_detect_cascade_merge_add(self._h, p, self._views(views, len(params)), len(outputs), bb, pb, qb, det_thr))
+        if list_of is None:
+            _check(lib().mscnn_net_detect_cascade_merge_add(self._h, p, self._views(views, len(params)), len(outputs), bb, pb, qb, det_thr))
+            return
+        _check(lib().mscnn_net_detect_cascade_merge_add_views(self._h, p, self._views(views, len(params)), self._list_of(list_of, len(params)),
+                                                              len(outputs), bb, pb, qb, det_thr))
 
     def detect_merge_end(self, cap=None):
         """mscnn_net_detect_merge_end: one NMS over each list.  Returns ([[(dets[D,5], pass[D], row[D]) per slot] per image],

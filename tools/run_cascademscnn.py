@@ -9,6 +9,7 @@ detections/<comp_id>_<class>_<output>_results.txt written as dlmwrite does (:148
          [--outputs 1st,2nd,3rd] [--cls-ids 2] [--det-thr 0.05] [--nms-overlap 0.5] [--batch B] [--precision f32|f16x3|f16]
          [--out detections] [--comp-id cascade_mscnn] [--names bg,car,van,truck,tram] [--limit N]
          [--scales H1xW1,H2xW2,...] [--flip] [--merge-cap N]      # several forwards per frame, one NMS (Net.detect_merge_*)
+         [--tiles RxC[:overlap_px]] [--views-batch]               # the frame cut into tiles; all views of a frame as ONE batched forward
          [--nms-type maxg|max] [--ovr-dnm union|min] [--nms-thr T]      # pNms.type / pNms.ovrDnm / bbNms's thr (Net.set_nms)
          [--roialign-one-pass]      # the ROIAlign heads of the net as one launch each (Net.set_roialign_one_pass; same results)
   python tools/run_cascademscnn.py --model kitti_car/cascade-mscnn-7s-576-2x --synthetic 8 --batch 2      # no dataset / weights at
@@ -25,6 +26,10 @@ merge the candidates of all those forwards before ONE NMS per cascade output and
 Net.detect_cascade_merge_add, then Net.detect_merge_end; list size: forwards per frame x max_nms_num, or --merge-cap).  One frame per
 forward, the same result files.  No reference script does this: there is no pin on the reference for it.  Without these flags the
 driver runs exactly the calls it ran before they existed.
+--tiles RxC[:overlap_px] cuts every frame into R x C equal, overlapping windows (mscnn_amd.net.tile_views) and runs each as a view,
+resized on the device straight out of the uploaded frame (Net.set_image_views), with --flip each tile's mirror too; --views-batch
+(with --flip and/or --tiles) runs all views of a frame in ONE forward: the input reshaped to N images, one set_image_views, one
+forward, one detect_cascade_merge_add(..., list_of=), one detect_merge_end.  As tools/run_mscnn_detection.py; no pin on the reference.
 
 Everything here is host glue over calls the test-suite covers one by one (Net.set_images, forward, detect_cascade_multi,
 reshape_input, kitti.write_detections_dlm)."""
@@ -100,8 +105,9 @@ def parse_args(argv=None):
     add_merge_flags(ap)
     a = ap.parse_args(argv)
     check_merge_flags(ap, a)
-    if (a.scales or a.flip) and (a.orig_size or a.dump_blobs):
-        ap.error("--scales / --flip name the input sizes themselves and keep no single forward's blobs: not with --orig-size / --dump-blobs")
+    if (a.scales or a.flip or a.tiles) and (a.orig_size or a.dump_blobs):
+        ap.error("--scales / --flip / --tiles name the input sizes themselves and keep no single forward's blobs: not with --orig-size / "
+                 "--dump-blobs")
     if not (a.prototxt or a.model) or not (a.images or a.synthetic):
         ap.error("need --prototxt or --model, and --images or --synthetic N")
     if a.batch < 1:
@@ -122,7 +128,7 @@ def main(argv=None):
     import numpy as np
     import torch
     from mscnn_amd import kitti, net as mnet, synth, zoo
-    from run_mscnn_detection import list_images, load_rgb_u8, merge_cand_cap, merge_passes, names_for
+    from run_mscnn_detection import list_images, load_rgb_u8, merge_cand_cap, merge_passes, names_for, run_frame_views, views_per_frame
 
     if a.prototxt:
         text = open(a.prototxt).read()
@@ -168,11 +174,23 @@ def main(argv=None):
     used, done = 0.0, 0
     # --scales / --flip: several forwards per frame, one NMS per (output, class): one detect_merge_begin per frame, after every forward a
     # detect_cascade_merge_add (the mirrored forward with the view flip_x = 1), then one detect_merge_end
-    passes = merge_passes(a, shape[2:]) if (a.scales or a.flip) else []
+    # --tiles / --views-batch: the views come straight out of the frame uploaded once (Net.set_image_views), with --views-batch all of
+    # them in ONE forward and one detect_cascade_merge_add(..., list_of=)
+    passes = merge_passes(a, shape[2:]) if (a.scales or a.flip or a.tiles) else []
+    by_views = bool(a.tiles or a.views_batch)
+    n_fwd = len(a.scales or [0]) * views_per_frame(a) if by_views else len(passes)
+
+    def add(params, mviews, list_of):
+        net.detect_cascade_merge_add([dict(p, nms_overlap=a.nms_overlap) for p in params], outputs, cls_ids, det_thr=a.det_thr, views=mviews,
+                                     **({} if list_of is None else dict(list_of=list_of)))
+
     for k, path in enumerate(files if passes else [], start=1):
         img = load_frame(path, k)
-        net.detect_merge_begin(1, len(outputs) * len(cls_ids), merge_cand_cap(text, len(passes), a.merge_cap))
-        for H, W, flipped in passes:
+        net.detect_merge_begin(1, len(outputs) * len(cls_ids), merge_cand_cap(text, n_fwd, a.merge_cap))
+        if by_views:
+            shape, dt = run_frame_views(a, net, img, a.scales or [tuple(shape[2:])], shape, add)
+            used += dt
+        for H, W, flipped in () if by_views else passes:
             if (1, 3, H, W) != shape:
                 shape = (1, 3, H, W)
                 net.reshape_input("data", shape)
@@ -189,7 +207,8 @@ def main(argv=None):
         for (o, c) in results:
             results[(o, c)].append(per_image[0][o * len(cls_ids) + c][0])
         if k % 100 == 0 or k == len(files):
-            print(f"idx {k}/{len(files)}, avgtime={used / k:.4f}s ({len(passes)} forwards per frame)")
+            what = f"{n_fwd} views per frame, batched" if a.views_batch else f"{n_fwd} forwards per frame"
+            print(f"idx {k}/{len(files)}, avgtime={used / k:.4f}s ({what})")
     for g0 in range(0, len(files) if not passes else 0, a.batch):
         group = files[g0:g0 + a.batch]
         frames = [load_frame(path, g0 + i + 1) for i, path in enumerate(group)]

@@ -14,6 +14,7 @@ examples/kitti_result/writeDetForEval.m.
          [--nms-type maxg|max] [--ovr-dnm union|min] [--nms-thr T] [--det-thr T]      # pNms.type / pNms.ovrDnm / bbNms's thr, and
                                                              # the det_thr of the WiderFace plain flow (Net.set_nms, once per run)
          [--scales H1xW1,H2xW2,...] [--flip] [--merge-cap N] # several forwards per frame, one NMS (Net.detect_merge_*)
+         [--tiles RxC[:overlap_px]] [--views-batch]          # the frame cut into tiles; all views of a frame as ONE batched forward
   python tools/run_mscnn_detection.py --model kitti_car/mscnn-7s-576 --synthetic 8      # no dataset / weights at hand: the generated
                                                                                         # deploy net, seeded weights, synthetic frames
 
@@ -39,8 +40,16 @@ is needed for a deploy without a max_nms_num).  One frame per forward; not with 
 result files have the same layout.  No reference script does this: there is no pin on the reference for it.  Without these flags the
 driver runs exactly the calls it ran before they existed.
 
-Everything here is host glue over calls the test-suite covers one by one (Net.set_image / set_images, forward, detect / detect_multi,
-proposals_multi, kitti.write_*)."""
+--tiles RxC[:overlap_px] cuts every frame into R x C equal windows that overlap by that many pixels (mscnn_amd.net.tile_views: the
+last row and column are shifted inwards, not shrunk), runs each as a view -- the window is resized to the net's input on the device
+straight out of the uploaded frame (Net.set_image_views), no crop on the host --, with --flip each tile's mirror too, and merges all
+of them before ONE NMS per class.  --views-batch (with --flip and/or --tiles) runs all views of a frame in ONE forward: the input is
+reshaped to N images, one set_image_views (the frame is uploaded once), one forward, one detect_merge_add(..., list_of=), one
+detect_merge_end; without it the views run as single forwards.  With --scales the same per input size.  No reference script has
+views: there is no pin on the reference for them either.
+
+Everything here is host glue over calls the test-suite covers one by one (Net.set_image / set_images / set_image_views, forward,
+detect / detect_multi, detect_merge_*, proposals_multi, kitti.write_*)."""
 import argparse
 import glob
 import os
@@ -104,6 +113,15 @@ def parse_scales(text):
     return out
 
 
+def parse_tiles(text):
+    """--tiles RxC[:overlap_px] -> (R, C, overlap); raises ValueError on anything else."""
+    import re
+    m = re.fullmatch(r"(\d+)x(\d+)(?::(\d+))?", text.strip())
+    if not m or int(m.group(1)) < 1 or int(m.group(2)) < 1:
+        raise ValueError(f"--tiles {text!r} is not RxC or RxC:overlap with positive R, C and an overlap >= 0")
+    return int(m.group(1)), int(m.group(2)), int(m.group(3) or 0)
+
+
 def add_merge_flags(ap):
     """The flags both drivers share for several forwards per frame (Net.detect_merge_*)."""
     ap.add_argument("--scales", default=None, help="H1xW1,H2xW2,...: run every frame at each of these net input sizes and merge the "
@@ -111,6 +129,10 @@ def add_merge_flags(ap):
     ap.add_argument("--flip", action="store_true", help="also run every frame mirrored ([:, ::-1]) and merge its candidates in")
     ap.add_argument("--merge-cap", type=int, default=0, help="candidate slots per class and frame (default: forwards per frame x "
                     "BoxOutput's max_nms_num)")
+    ap.add_argument("--tiles", default=None, help="RxC[:overlap_px]: cut every frame into R x C equal, overlapping windows, run each "
+                    "as a view (Net.set_image_views) and merge their candidates before one NMS")
+    ap.add_argument("--views-batch", action="store_true", help="with --flip and/or --tiles: all views of a frame as the images of ONE "
+                    "forward (one set_image_views, one forward, one detect_merge_add(..., list_of=))")
 
 
 def check_merge_flags(ap, a):
@@ -119,8 +141,15 @@ def check_merge_flags(ap, a):
             a.scales = parse_scales(a.scales)
         except ValueError as e:
             ap.error(str(e))
-    if (a.scales or a.flip) and a.batch > 1:
-        ap.error("--scales / --flip run one frame per forward (drop --batch)")
+    if a.tiles is not None:
+        try:
+            a.tiles = parse_tiles(a.tiles)
+        except ValueError as e:
+            ap.error(str(e))
+    if a.views_batch and not (a.flip or a.tiles):
+        ap.error("--views-batch batches the views of a frame: give --flip and/or --tiles")
+    if (a.scales or a.flip or a.tiles) and a.batch > 1:
+        ap.error("--scales / --flip / --tiles run one frame per forward (drop --batch; --views-batch batches a frame's views)")
 
 
 def merge_cand_cap(prototxt_text, passes, merge_cap):
@@ -138,6 +167,43 @@ def merge_cand_cap(prototxt_text, passes, merge_cap):
 def merge_passes(a, net_hw):
     """[(H, W, flipped)] of the forwards of one frame, in add order: every scale, each followed by its mirrored twin."""
     return [(H, W, f) for H, W in (a.scales or [net_hw]) for f in ((False, True) if a.flip else (False,))]
+
+
+def frame_views(a, org_hw):
+    """--tiles / --views-batch: (views, merge views) of one frame -- its tiles, or the whole frame, with --flip the mirrors behind them."""
+    from mscnn_amd import net as mnet
+    rows, cols, overlap = a.tiles or (1, 1, 0)
+    views, _, mviews = mnet.tile_views(org_hw, rows, cols, overlap=overlap, flip=a.flip)
+    return views, mviews
+
+
+def views_per_frame(a):
+    rows, cols, _ = a.tiles or (1, 1, 0)
+    return rows * cols * (2 if a.flip else 1)
+
+
+def run_frame_views(a, net, img, scales, shape, add):
+    """--tiles / --views-batch for ONE frame between detect_merge_begin and _end: per input size either one batched forward over all
+    views (--views-batch) or one forward per view, each straight out of the frame uploaded here once (Net.set_image_views).
+    add(params, merge views, list_of or None) is the driver's detect_merge_add.  Returns (the input's shape now, seconds in forwards)."""
+    import torch
+    views, mviews = frame_views(a, img.shape[:2])
+    dev_img = torch.from_numpy(img).cuda(a.device)                            # (kept referenced until the pre-processing has run)
+    groups = [list(range(len(views)))] if a.views_batch else [[v] for v in range(len(views))]
+    used = 0.0
+    for H, W in scales:
+        for g in groups:
+            if (len(g), 3, H, W) != tuple(shape):
+                shape = (len(g), 3, H, W)
+                net.reshape_input("data", shape)
+            params = net.set_image_views("data", [dev_img], [views[v] for v in g])
+            torch.cuda.synchronize(a.device)
+            t0 = time.perf_counter()
+            net.forward()
+            torch.cuda.synchronize(a.device)
+            used += time.perf_counter() - t0                                  # forwards only, as :72-73
+            add(params, [mviews[v] for v in g], [0] * len(g) if a.views_batch else None)
+    return shape, used
 
 
 def parse_args(argv=None):
@@ -167,8 +233,8 @@ def parse_args(argv=None):
     add_merge_flags(ap)
     a = ap.parse_args(argv)
     check_merge_flags(ap, a)
-    if (a.scales or a.flip) and (a.rois_in or a.proposals_out or a.proposals_only):
-        ap.error("--scales / --flip merge detections: not with --rois-in, --proposals-out or --proposals-only")
+    if (a.scales or a.flip or a.tiles) and (a.rois_in or a.proposals_out or a.proposals_only):
+        ap.error("--scales / --flip / --tiles merge detections: not with --rois-in, --proposals-out or --proposals-only")
     if a.proposals_only and not a.proposals_out:
         ap.error("--proposals-only needs --proposals-out DIR")
     if a.proposals_only and a.rois_in:
@@ -231,7 +297,7 @@ def main(argv=None):
     rois = read_rois(a.rois_in, len(files)) if a.rois_in else None
     if a.batch > 1:
         return run_batched(a, net, files, names, cls_ids, imgH, imgW, per_class, per_image_props, forward, rois)
-    if a.scales or a.flip:
+    if a.scales or a.flip or a.tiles:
         return run_merged(a, net, text, files, names, cls_ids, imgH, imgW, per_class)
     used = 0.0
     for k, path in enumerate(files, start=1):
@@ -274,14 +340,24 @@ def run_merged(a, net, text, files, names, cls_ids, imgH, imgW, per_class):
     import torch
     from mscnn_amd import kitti
     passes = merge_passes(a, (imgH, imgW))
-    cand_cap = merge_cand_cap(text, len(passes), a.merge_cap)
+    by_views = bool(a.tiles or a.views_batch)                                 # the views paths: set_image_views instead of a host mirror
+    n_fwd = len(a.scales or [0]) * views_per_frame(a) if by_views else len(passes)
+    cand_cap = merge_cand_cap(text, n_fwd, a.merge_cap)
     shape = (1, 3, imgH, imgW)
     used = 0.0
+
+    def add(params, mviews, list_of):
+        p = [dict(q, proposal_thr=a.proposal_thr, nms_overlap=a.nms_overlap) for q in params]
+        net.detect_merge_add(p, cls_ids, views=mviews, **({} if list_of is None else dict(list_of=list_of)))
+
     for k, path in enumerate(files, start=1):
         img = load_frame(path, k)
         orgH, orgW = img.shape[:2]
         net.detect_merge_begin(1, len(cls_ids), cand_cap)
-        for H, W, flipped in passes:
+        if by_views:
+            shape, dt = run_frame_views(a, net, img, a.scales or [(imgH, imgW)], shape, add)
+            used += dt
+        for H, W, flipped in () if by_views else passes:
             if (1, 3, H, W) != shape:
                 shape = (1, 3, H, W)
                 net.reshape_input("data", shape)
@@ -304,7 +380,8 @@ def run_merged(a, net, text, files, names, cls_ids, imgH, imgW, per_class):
         if a.labels_dir:
             kitti.write_kitti_labels(a.labels_dir, frame_id(path, k), by_type)
         if k % 100 == 0 or k == len(files):
-            print(f"idx {k}/{len(files)}, avgtime={used / k:.4f}s ({len(passes)} forwards per frame)")
+            what = f"{n_fwd} views per frame, batched" if a.views_batch else f"{n_fwd} forwards per frame"
+            print(f"idx {k}/{len(files)}, avgtime={used / k:.4f}s ({what})")
     finish(a, names, cls_ids, per_class, [], len(files))
     return 0
 
