@@ -50,6 +50,7 @@
  *   boxoutput*                 heads, rois_out, props_out, anchor_ids_out, count_out_dev 4
  *   detections*                blobs, ids_out, count_out_dev 4; dets_out 8: refuses
  *   detections_candidates_*, detections_merge_fwd   cand, workspace, pack_dev 16: refuses; the blobs 4
+ *   detections_merge_vote_fwd  cand, pack_dev 16: refuses
  *   proposals_multi_fwd        props 8: refuses
  *   rois_ingest                rows 8: refuses; rois, props, image_rows, status 4
  */
@@ -710,6 +711,33 @@ MSCNN_API int mscnn_detections_candidates_cascade_add_views(const mscnn_detectio
 MSCNN_API size_t mscnn_detections_merge_workspace_bytes(int num_segments, int cand_cap);
 MSCNN_API int mscnn_detections_merge_fwd(const double* nms_overlap, const mscnn_nms_params* nms, int num_segments, void* cand,
                                          int cand_cap, void* pack_dev, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Box voting, the other half of the multi-scale / flip / tiled testing recipe: the merge above SELECTS one box per cluster, this op
+ * then REFINES each kept box from everything the forwards said about it.  Call it after mscnn_detections_merge_fwd with the same
+ * cand, cand_cap and pack_dev (either merge path: the op reads the candidate buffer and the pack only, and needs no workspace).
+ * Per segment s with table count D >= 0, for every kept row k < D with box A = [x y w h] as it stands in the pack: candidate
+ * j = 0 .. min(wanted, cand_cap) - 1 of the list, box B and prob p_j, VOTES when o / u >= thr, o and u in double exactly as the NMS
+ * computes them for ovr_dnm = union --
+ *     iw = fmin(A.x + A.w, B.x + B.w) - fmax(A.x, B.x)   (iw <= 0: no vote);   ih likewise;   o = iw * ih;   u = A.w * A.h + B.w * B.h - o
+ * -- a NaN ratio does not vote; the union form always, whatever ovr_dnm the NMS ran with.  With weights (double)p_j the row's box
+ * becomes [sum p x / sum p, sum p y / sum p, sum p w / sum p, sum p h / sum p], written IN PLACE over the four box doubles of pack
+ * row s * cand_cap + k.  The vote runs on x y w h as they are: the cascade rows keep their w = x2 - x1 + 1 convention.
+ * A kept row with fewer than two voters stays bit for bit as it was, and so does one whose sum p is not > 0.  Nothing else is
+ * written: not the prob column, the tags, the header, the table, rows past a count, nor any slot of a segment with count -1.
+ * A row reads the candidates, never other pack rows, so in place is safe; calling the op TWICE votes again around the moved boxes:
+ * it is not idempotent.
+ * SUMMATION ORDER, part of the contract (fixed by the slot index alone, never by grid size, scheduling or timing): 64 partial sums
+ * per quantity; partial l adds the voters among slots l, l + 64, l + 128, ... in ascending order, each term p * v rounded, then
+ * added (no fma), starting from +0.0; the partials v[0 .. 63] are combined by an xor butterfly, for m = 32, 16, 8, 4, 2, 1:
+ * v[l] = v[l] + v[l ^ m] for all l at once; the result is v[0] (every v[l] holds the same bits); then the four divisions.
+ * One launch for all segments, a fixed grid, no host read, no atomics.
+ * Refused before the launch, naming the value: a null pointer, S < 1, cand_cap < 1 (or S * cand_cap past 2^31 - 1), a thr that is
+ * NaN or outside (0, 1), cand or pack_dev not 16-byte aligned.
+ * No pin on the reference: its scripts neither merge nor vote.  The check is tests/vote_witness.py: a numpy restatement with this
+ * summation order, compared bit for bit, and an exact-rational mean over the same voters. */
+typedef struct { double thr; } mscnn_vote_params;     /* 0 < thr < 1 */
+MSCNN_API int mscnn_detections_merge_vote_fwd(const mscnn_vote_params* vote, int num_segments, const void* cand, int cand_cap,
+                                              void* pack_dev, void* stream);
 
 /* The proposal half of the scripts' result (run_mscnn_detection.m:75-91, `final_proposals{k}`) for every image of a batched forward
  * in one pass.  props [R_all][6] = BoxOutput's proposals_score, rows [img x1 y1 x2 y2 score] grouped by image in ascending order;

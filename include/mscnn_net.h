@@ -396,6 +396,15 @@ MSCNN_NET_API int mscnn_net_detect_cascade_merge_add(mscnn_net* net, const mscnn
                                                      const char* const* proposal_blobs, float det_thr);
 MSCNN_NET_API int mscnn_net_detect_merge_end(mscnn_net* net, double* dets_host, int* pass_host, int* row_host, int cap, int* seg_dets,
                                              int* seg_candidates);
+/* Box voting behind the merge (mscnn_hip.h: mscnn_detections_merge_vote_fwd): while it is on, mscnn_net_detect_merge_end enqueues the
+ * vote between the merge and the one synchronisation, and every detection's box [x y w h] comes back as the prob-weighted mean of
+ * the candidates of its list -- all forwards' -- whose union overlap with it is >= thr; prob, pass and row stay those of the kept
+ * box, and a box with fewer than two voters comes back bit for bit.  Sticky, like mscnn_net_set_nms: thr = 0 is off (the default;
+ * _end then enqueues exactly what it always did), any other value must lie inside (0, 1) or the call fails naming the value and
+ * changes nothing.  Both calls work on a net built with device -1.  No pin on the reference: its scripts neither merge nor vote;
+ * the check is tests/vote_witness.py (the op's documented summation order, bit for bit). */
+MSCNN_NET_API int mscnn_net_set_box_voting(mscnn_net* net, double thr);
+MSCNN_NET_API int mscnn_net_get_box_voting(const mscnn_net* net, double* thr);
 /* The views of a frame as ONE batched forward (mscnn_hip.h: mscnn_detections_candidates_add_views): the merge was opened with
  * _begin(num_frames, ...), the input holds N images -- the views mscnn_net_set_image_views wrote --, p[N * K] and view[N] describe
  * them as in _add, and list_of[N] (host) names the frame of each: the rows of image b go to the lists of frame list_of[b].  One

@@ -758,6 +758,75 @@ __global__ __launch_bounds__(256) void det_merge_table_big_kernel(const int* __r
   ent[1] = wanted; ent[2] = s * cap; ent[3] = 0;
 }
 
+// -- box voting behind the merge (mscnn_detections_merge_vote_fwd): every kept row of the pack becomes the prob-weighted mean of the
+// list's candidates that overlap it.  One wave64 per kept row, the kVoteRows waves of a workgroup share the tile of kVoteThreads
+// candidates they stream through LDS.  SUMMATION ORDER (mscnn_hip.h): lane l adds the voters among slots l, l + 64, ... in ascending
+// order, then an xor butterfly over 32, 16, ..., 1 -- IEEE addition commutes, so both lanes of a pair get the same bits and no lane
+// has to broadcast.  The order is a function of the slot index alone: which workgroup takes a row (the groups of four rows of all
+// segments, counted through, go round the fixed grid) decides nothing about it.  A row reads the candidates and itself, and is
+// written by its own wave: in place is safe.  No atomics, no workgroup waits on another.
+constexpr int kVoteThreads = 256, kVoteRows = kVoteThreads / 64, kVoteBlocks = 256;
+struct DetVoteArgs { int num_segs, cand_cap; double thr; char* cand; const int* hdr; double* dets; };
+
+__global__ __launch_bounds__(kVoteThreads) void det_merge_vote_kernel(DetVoteArgs a) {
+  __shared__ DetBox tbox[kVoteThreads];
+  __shared__ float tprob[kVoteThreads];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int grid = (int)gridDim.x;
+  const DetCand c = det_cand_of(a.cand, a.num_segs, a.cand_cap);      // (read only)
+  int first = (int)blockIdx.x;      // this workgroup's first group of the segment at hand: the groups of all segments go round the grid
+  for (int s = 0; s < a.num_segs; ++s) {
+    // (every value that bounds a loop or guards a barrier below is the same in all threads of the workgroup)
+    const int D = min(a.hdr[MSCNN_MULTI_PACK_WORDS * (size_t)(1 + s)], a.cand_cap);      // -1: the list overflowed, nothing of it is touched
+    if (D <= 0) continue;
+    const int wanted = c.cnt[CAND_WORDS * (size_t)s + CAND_WANTED];
+    const int n = wanted < 0 ? 0 : min(wanted, a.cand_cap);
+    const int groups = (D + kVoteRows - 1) / kVoteRows;
+    const size_t list = (size_t)s * (size_t)a.cand_cap;
+    int g = first;
+    first = (int)(((long)first + grid - groups % grid) % grid);
+    for (; g < groups; g += grid) {
+      const int k = g * kVoteRows + wave;
+      const bool live = k < D;
+      double* row = a.dets + 5 * (list + (size_t)(live ? k : 0));
+      DetBox A = DetBox{0.0, 0.0, 0.0, 0.0};
+      if (live) A = DetBox{row[0], row[1], row[2], row[3]};
+      const double as_a = A.w * A.h, xe_a = A.x + A.w, ye_a = A.y + A.h;
+      double sp = 0.0, sx = 0.0, sy = 0.0, sw = 0.0, sh = 0.0;
+      int voters = 0;
+      for (int t0 = 0; t0 < n; t0 += kVoteThreads) {
+        __syncthreads();      // (every wave is done with the tile before)
+        if (t0 + tid < n) { tbox[tid] = c.box[list + t0 + tid]; tprob[tid] = c.prob[list + t0 + tid]; }
+        __syncthreads();
+        if (!live) continue;
+        const int tn = min(kVoteThreads, n - t0);
+        for (int q = lane; q < tn; q += 64) {
+          const DetBox B = tbox[q];
+          const double iw = fmin(xe_a, B.x + B.w) - fmax(A.x, B.x);      // DetTr::over / det_mask_block, the union form
+          if (iw <= 0) continue;
+          const double ih = fmin(ye_a, B.y + B.h) - fmax(A.y, B.y);
+          if (ih <= 0) continue;
+          double o = iw * ih;
+          const double u = as_a + B.w * B.h - o;
+          o = o / u;
+          if (!(o >= a.thr)) continue;      // (a NaN ratio does not vote)
+          const double p = (double)tprob[q];
+          sp = sp + p;
+          sx = sx + p * B.x; sy = sy + p * B.y; sw = sw + p * B.w; sh = sh + p * B.h;
+          ++voters;
+        }
+      }
+      for (int m = 32; m >= 1; m >>= 1) {
+        sp = sp + __shfl_xor(sp, m); sx = sx + __shfl_xor(sx, m); sy = sy + __shfl_xor(sy, m);
+        sw = sw + __shfl_xor(sw, m); sh = sh + __shfl_xor(sh, m);
+        voters += __shfl_xor(voters, m);
+      }
+      // fewer than two voters (the row itself, as a rule), or weights that do not sum above zero: the row stays bit for bit
+      if (live && lane == 0 && voters >= 2 && sp > 0) { row[0] = sx / sp; row[1] = sy / sp; row[2] = sw / sp; row[3] = sh / sp; }
+    }
+  }
+}
+
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 struct DetLayout { size_t cnt, sbox, sprob, ssrc, tbox, tprob, mask, keys, rinit, kidx, kbox, total; int wpr, sortP; bool big; };
 DetLayout det_layout(int R) {
@@ -1401,6 +1470,28 @@ extern "C" int mscnn_detections_merge_fwd(const double* nms_overlap, const mscnn
     MSCNN_POST_LAUNCH();
   }
   det_merge_table_big_kernel<<<cdiv(S, 256), 256, 0, st>>>(c.cnt, S, cand_cap, hdr);
+  MSCNN_POST_LAUNCH();
+  return MSCNN_OK;
+}
+
+extern "C" int mscnn_detections_merge_vote_fwd(const mscnn_vote_params* vote, int num_segments, const void* cand, int cand_cap,
+                                               void* pack_dev, void* stream) {
+  MSCNN_REQUIRE(vote && cand && pack_dev, "detections_merge_vote: null pointer");
+  const int S = num_segments;
+  MSCNN_REQUIRE(S >= 1, "detections_merge_vote: %d segments", S);
+  MSCNN_REQUIRE(cand_cap >= 1, "detections_merge_vote: cand_cap %d", cand_cap);
+  MSCNN_REQUIRE(cand_shape_ok(S, cand_cap), "detections_merge_vote: %d segments x %d slots is past 2^31 - 1", S, cand_cap);
+  MSCNN_REQUIRE(vote->thr > 0 && vote->thr < 1, "detections_merge_vote: thr %g is outside (0, 1)", vote->thr);      // (NaN included)
+  MSCNN_REQUIRE_ALIGNED(cand, 16, "detections_merge_vote: cand");
+  MSCNN_REQUIRE_ALIGNED(pack_dev, 16, "detections_merge_vote: pack_dev");
+  const mscnn_multi_pack_layout PL = mscnn_multi_pack_layout_of(S, S * cand_cap);
+  char* pk = static_cast<char*>(pack_dev);
+  DetVoteArgs a;
+  a.num_segs = S; a.cand_cap = cand_cap; a.thr = vote->thr;
+  a.cand = const_cast<char*>(static_cast<const char*>(cand));
+  a.hdr = reinterpret_cast<const int*>(pk);
+  a.dets = reinterpret_cast<double*>(pk + PL.dets);
+  det_merge_vote_kernel<<<kVoteBlocks, kVoteThreads, 0, as_stream(stream)>>>(a);
   MSCNN_POST_LAUNCH();
   return MSCNN_OK;
 }

@@ -232,6 +232,7 @@ def lib():
         L.mscnn_detections_merge_workspace_bytes.argtypes = [C.c_int, C.c_int]
         L.mscnn_detections_merge_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                                  C.c_void_p]
+        L.mscnn_detections_merge_vote_fwd.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.mscnn_proposals_multi_pack_bytes.restype = C.c_size_t
         L.mscnn_proposals_multi_pack_bytes.argtypes = [C.c_int, C.c_int]
         L.mscnn_proposals_multi_fwd.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
@@ -998,6 +999,11 @@ class DetectionsView(C.Structure):
     _fields_ = [("off_x", C.c_double), ("off_y", C.c_double), ("flip_x", C.c_int)]
 
 
+class VoteParams(C.Structure):
+    """mscnn_vote_params: the overlap threshold of the box vote, 0 < thr < 1."""
+    _fields_ = [("thr", C.c_double)]
+
+
 def _view_array(views, num_images):
     """views: None (NULL, the identity) or one (off_x, off_y, flip_x) per image."""
     if views is None:
@@ -1104,9 +1110,15 @@ class Candidates:
         """[(rows that wanted in, overflow flag)] per segment, read from the device."""
         return self.buf[:8 * self.S].cpu().numpy().view(np.int32).reshape(self.S, 2).tolist()
 
-    def merge(self, nms=NMS_NULL, nms_overlap=None, raw_pack=False, pack=None, ws=None):
+    def vote(self, pack, thr):
+        """mscnn_detections_merge_vote_fwd on the device pack a merge() of these lists filled: every kept row's box becomes the
+        prob-weighted mean of the list's candidates whose union overlap with it is >= thr, in place.  Not idempotent."""
+        _check(lib().mscnn_detections_merge_vote_fwd(C.byref(VoteParams(float(thr))), self.S, _dev(self.buf), self.cap, _dev(pack), _stream()))
+
+    def merge(self, nms=NMS_NULL, nms_overlap=None, raw_pack=False, pack=None, ws=None, vote_thr=None):
         """mscnn_detections_merge_fwd.  Returns [(dets[D,5], tags[D], candidates)] per segment ((None, None, candidates): the list
-        overflowed); raw_pack: (that, the pack's bytes as a numpy array -- zero-filled before the call unless `pack` is given)."""
+        overflowed); raw_pack: (that, the pack's bytes as a numpy array -- zero-filled before the call unless `pack` is given).
+        vote_thr: vote(pack, vote_thr) runs on the pack before it is read."""
         S, cap = self.S, self.cap
         ov = self.overlap if nms_overlap is None else nms_overlap
         ov = (C.c_double * S)(*[float(v) for v in (ov if ov is not None else [0.5] * S)])
@@ -1118,6 +1130,8 @@ class Candidates:
             ws = torch.empty(max(wb, 1), dtype=torch.uint8, device=self.buf.device)
         _check(lib().mscnn_detections_merge_fwd(ov, _nms_ref(nms), S, _dev(self.buf), cap, _dev(pack), _dev(ws), C.c_size_t(ws.numel()),
                                                 _stream()))
+        if vote_thr is not None:
+            self.vote(pack, vote_thr)
         h = pack[:nbytes].cpu().numpy()
         table = 16 * (S + 1)
         hdr = h[:table].view(np.int32).reshape(S + 1, 4)

@@ -33,6 +33,8 @@ struct mscnn_net {
   // mscnn_net_set_nms: bbNms's knobs for every detect call from now on (pNms at the top of the reference scripts)
   mscnn_nms_params nms;
   bool nms_set = false;                    // false: the defaults -- the calls hand the ops NULL and run what they always ran
+  // mscnn_net_set_box_voting: 0 = off (detect_merge_end enqueues what it always did), else the vote's overlap threshold in (0, 1)
+  double vote_thr = 0.0;
   // mscnn_net_detect_merge_*: the candidate lists of the forwards added since _begin (mscnn_hip.h: mscnn_detections_candidates_*)
   struct Merge {
     bool open = false;
@@ -471,6 +473,21 @@ int mscnn_net_get_nms(const mscnn_net* n, mscnn_nms_params* out) {
     CHECK(n && out);
     if (n->nms_set) *out = n->nms;
     else MSCNN_CHECK(mscnn_nms_params_resolve(nullptr, out));
+  });
+}
+
+int mscnn_net_set_box_voting(mscnn_net* n, double thr) {
+  return guarded([&] {
+    CHECK(n != nullptr);
+    CHECK(thr == 0.0 || (thr > 0.0 && thr < 1.0)) << "set_box_voting: thr " << thr << " is neither 0 (off) nor inside (0, 1)";
+    n->vote_thr = thr == 0.0 ? 0.0 : thr;      // (-0.0 is off too)
+  });
+}
+
+int mscnn_net_get_box_voting(const mscnn_net* n, double* thr) {
+  return guarded([&] {
+    CHECK(n && thr);
+    *thr = n->vote_thr;
   });
 }
 
@@ -1412,8 +1429,13 @@ int mscnn_net_detect_merge_end(mscnn_net* n, double* dets_host, int* pass_host, 
     *static_cast<volatile int*>(n->det_host) = -1;      // the header's first word: the kernels must have written it
     const size_t wb = mscnn_detections_merge_workspace_bytes(S, m.cand_cap);
     void* ws = n->det_ws.Reserve(wb);
-    // (the kernels only ever WRITE the pack: they write it straight into host-coherent pinned memory, as the blocking detect calls do)
+    // (the merge kernels only ever WRITE the pack: they write it straight into host-coherent pinned memory, as the blocking detect
+    // calls do; the vote reads back the table and each kept row's own box from there, in stream order, and nothing else)
     MSCNN_CHECK(mscnn_detections_merge_fwd(m.overlap.data(), nms_arg(n, false), S, m.cand.get(), m.cand_cap, n->det_host_dev, ws, wb, st));
+    if (n->vote_thr != 0.0) {      // box voting (mscnn_net_set_box_voting): the kept rows of that pack, refined in place from the lists
+      const mscnn_vote_params vote = {n->vote_thr};
+      MSCNN_CHECK(mscnn_detections_merge_vote_fwd(&vote, S, m.cand.get(), m.cand_cap, n->det_host_dev, st));
+    }
     HIP_CHECK(hipStreamSynchronize(st));
     // A stream-K hand-off that timed out in one of the forwards of this merge can not be answered by a re-run here: the input blob
     // holds the last forward only.  As mscnn_net_detect_end: whole tiles from now on, and the caller submits the forwards again.

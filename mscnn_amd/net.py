@@ -111,6 +111,7 @@ def lib():
             "mscnn_net_detect_merge_end": [vp, vp, vp, vp, ci, vp, vp],
             "mscnn_net_detect_merge_add_views": [vp, vp, vp, vp],
             "mscnn_net_detect_cascade_merge_add_views": [vp, vp, vp, vp, ci, vp, vp, vp, C.c_float],
+            "mscnn_net_set_box_voting": [vp, C.c_double], "mscnn_net_get_box_voting": [vp, vp],
         }
         for name, args in sig.items():
             getattr(L, name).argtypes = args
@@ -513,6 +514,18 @@ class Net:
         p = NmsParams()
         _check(lib().mscnn_net_get_nms(self._h, C.byref(p)))
         return dict(type=NMS_TYPES[p.type], ovr_dnm=OVR_DNMS[p.ovr_dnm], thr=None if p.thr == float("-inf") else p.thr, det_thr=p.det_thr)
+
+    def set_box_voting(self, thr=None):
+        """mscnn_net_set_box_voting: from now on detect_merge_end replaces every kept box by the prob-weighted mean of its list's
+        candidates whose union overlap with it is >= thr (mscnn_detections_merge_vote_fwd).  thr None or 0 = off (the default); any
+        other value must lie inside (0, 1), else the call fails naming the value and the setting stays as it was."""
+        _check(lib().mscnn_net_set_box_voting(self._h, 0.0 if thr is None else float(thr)))
+
+    def get_box_voting(self):
+        """mscnn_net_get_box_voting: the current threshold, None = off."""
+        thr = C.c_double()
+        _check(lib().mscnn_net_get_box_voting(self._h, C.byref(thr)))
+        return None if thr.value == 0.0 else thr.value
 
     @staticmethod
     def _params(cls_id, ratios, org_hw, bbox_mean, bbox_std, proposal_thr, nms_overlap):

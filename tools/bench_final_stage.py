@@ -26,6 +26,10 @@ final-stage work is timed (host wall time, the device idle before either form st
 alternate which runs first, and the whole measurement is repeated --rounds times: median of the rounds' medians and their spread.
 Cases: kitti_car 7s-576 at two input sizes plus a mirrored forward, caltech 7s-480 with B = 8 likewise.
 
+--merge --vote [THR] is box voting behind that merge (mscnn_detections_merge_vote_fwd), on the candidate lists of the same forwards:
+the merge alone, the merge + the vote op, and the merge + a copy of every candidate list to the host + voting in numpy there -- what a
+caller has without the op.  Each form runs from an idle device to the detections on the host; the three rotate which runs first.
+
 --lib path/to/libmscnn_hip.so runs whatever leg is selected with THAT build's kernels under the Net (it is loaded first, so the Net's
 calls bind to it; the per-range op calls of the batched cascade case's per-call form go through hipapi's own handle and stay this
 build's).  --parent-lib path/to/libmscnn_hip.so repeats the selected leg --rounds times in child processes, this build and
@@ -267,6 +271,91 @@ def merge_leg(a):
         del n
 
 
+def host_vote(dets, cand, thr):
+    """Box voting as a caller writes it in numpy today: per kept row the union overlap with every candidate of the list, then the
+    prob-weighted mean of those at or over thr (at least two).  Vectorised per row; not the summation order of the device op."""
+    out = dets.copy()
+    xe, ye, area = cand[:, 0] + cand[:, 2], cand[:, 1] + cand[:, 3], cand[:, 2] * cand[:, 3]
+    for k, A in enumerate(dets):
+        iw = np.minimum(A[0] + A[2], xe) - np.maximum(A[0], cand[:, 0])
+        ih = np.minimum(A[1] + A[3], ye) - np.maximum(A[1], cand[:, 1])
+        o = iw * ih
+        with np.errstate(divide="ignore", invalid="ignore"):
+            v = (iw > 0) & (ih > 0) & (o / (A[2] * A[3] + area - o) >= thr)
+        if np.count_nonzero(v) >= 2 and cand[v, 4].sum() > 0:
+            out[k, :4] = (cand[v, 4:5] * cand[v, :4]).sum(0) / cand[v, 4].sum()
+    return out
+
+
+def merge_vote_leg(a):
+    """--merge --vote: behind the same adds, (the merge alone) against (the merge + the vote op) against (the merge + a copy of every
+    candidate list to the host + numpy voting there: what a caller has without the op).  All three end with the detections on the
+    host; the candidate lists are those of the net's own forwards, held by hipapi.Candidates so that the host form can reach them."""
+    import torch
+    from mscnn_amd import hipapi
+    thr = a.vote
+    print(f"# box voting behind the merge (thr {thr:g}) per frame group, host wall ms from an idle device to the detections on the host (median "
+          f"over {a.steps} steps after {a.warmup} warm-up; {a.rounds} rounds: median of the medians, spread = max - min), regime {a.regime}")
+    print(f"# {'case':30s} {'B':>2s} {'fwd':>3s} {'cands':>6s} {'dets':>5s} {'moved':>5s} {'merge ms':>9s} {'spread':>7s} {'merge + vote ms':>16s} {'spread':>7s} "
+          f"{'merge + lists to host + numpy vote ms':>38s} {'spread':>7s}")
+    for name in a.case or list(MERGE_CASES):
+        model, B, classes, org, forwards = MERGE_CASES[name]
+        n = mnet.Net(prototxt_text=zoo.prototxt(model, batch=B))
+        synth.load_into(n, a.regime)
+        S, cap = B * len(classes), 2000 * B * len(forwards)
+        cand = hipapi.Candidates(S, cap)
+        for H, W, flipped in forwards:
+            f = np.concatenate([synth.frame(H, W, seed=1701 + b, org_hw=org) for b in range(B)], 0)
+            n.reshape_input("data", (B, 3, H, W))
+            n.set_blob("data", np.ascontiguousarray(f[..., ::-1]) if flipped else f)
+            n.forward()
+            R = n.blob_shape("proposals_score")[0]
+            blobs = [torch.from_numpy(n.get_blob(b).reshape(R, -1)).cuda() for b in ("bbox_pred", "cls_pred", "proposals_score")]
+            segs = [dict(cls_id=c, ratios=(H / float(org[0]), W / float(org[1])), org_hw=org, nms_overlap=0.5) for _ in range(B) for c in classes]
+            cand.add(*blobs, B, segs, views=[(0.0, 0.0, 1)] * B if flipped else None)
+        pack = torch.zeros(hipapi.lib().mscnn_detections_multi_pack_bytes(S, S * cap), dtype=torch.uint8, device="cuda")
+        ws = torch.empty(max(hipapi.lib().mscnn_detections_merge_workspace_bytes(S, cap), 1), dtype=torch.uint8, device="cuda")
+        al = lambda v: (v + 255) // 256 * 256      # noqa: E731  (the candidate buffer's layout: include/mscnn_hip.h)
+        o0 = al(8 * S); o1 = o0 + al(32 * S * cap)
+
+        def on_host():
+            out = cand.merge(pack=pack, ws=ws)
+            cnt = cand.counts()                           # (one small copy; then of every list the filled slots only: boxes, probs)
+            res = []
+            for s, (dets, tags, cands) in enumerate(out):
+                m = min(cnt[s][0], cap)
+                box = cand.buf[o0 + 32 * s * cap:o0 + 32 * (s * cap + m)].cpu().numpy().view(np.float64).reshape(m, 4)
+                prob = cand.buf[o1 + 4 * s * cap:o1 + 4 * (s * cap + m)].cpu().numpy().view(np.float32)
+                res.append((host_vote(dets, np.concatenate([box, prob[:, None].astype(np.float64)], 1), thr), tags, cands))
+            return res
+
+        forms = [lambda: cand.merge(pack=pack, ws=ws), lambda: cand.merge(pack=pack, ws=ws, vote_thr=thr), on_host]
+        med = [[], [], []]
+        for rnd in range(a.rounds):
+            t = [[], [], []]
+            for step in range(a.warmup + a.steps):
+                res = [None] * 3
+                for f in [(0, 1, 2), (1, 2, 0), (2, 0, 1)][step % 3]:
+                    torch.cuda.synchronize()      # (untimed: every form starts on an idle device)
+                    t0 = time.perf_counter()
+                    res[f] = forms[f]()
+                    dt = time.perf_counter() - t0
+                    if step >= a.warmup:
+                        t[f].append(dt)
+                for (d0, _, _), (d1, _, c1), (d2, _, _) in zip(*res):      # the op against the host form: the same boxes up to the summation order
+                    assert np.array_equal(d0[:, 4], d1[:, 4]) and np.allclose(d1, d2, rtol=1e-12, atol=0), (name, step)
+            for f in range(3):
+                med[f].append(1e3 * float(np.median(t[f])))
+        cands = sum(c for _, _, c in res[1])
+        dets = sum(len(d) for d, _, _ in res[1])
+        moved = sum(int(np.count_nonzero(np.any(d0[:, :4] != d1[:, :4], 1))) for (d0, _, _), (d1, _, _) in zip(res[0], res[1]))
+        m = [float(np.median(v)) for v in med]
+        sp = [max(v) - min(v) for v in med]
+        print(f"  {name:30s} {B:2d} {len(forwards):3d} {cands:6d} {dets:5d} {moved:5d} {m[0]:9.3f} {sp[0]:7.3f} {m[1]:16.3f} {sp[1]:7.3f} {m[2]:38.3f} {sp[2]:7.3f}",
+              flush=True)
+        del n
+
+
 def use_lib(path):
     """The kernels of another build of libmscnn_hip.so under this build's Net: loaded first and globally, the Net library's calls bind
     to it (checked on one final-stage symbol)."""
@@ -317,6 +406,8 @@ def ab_leg(a, argv):
 ap = argparse.ArgumentParser()
 ap.add_argument("--merge", action="store_true", help="several forwards of a frame, one NMS: get_blob + numpy per forward against "
                 "detect_merge_add per forward + detect_merge_end")
+ap.add_argument("--vote", nargs="?", type=float, const=0.5, default=None, metavar="THR", help="with --merge: the merge alone, the merge "
+                "+ the vote op, and the merge + every candidate list to the host + numpy voting")
 ap.add_argument("--rounds", type=int, default=3, help="--merge / --parent-lib: repetitions of the whole measurement")
 ap.add_argument("--lib", default="", help="run with the kernels of this libmscnn_hip.so under the Net")
 ap.add_argument("--parent-lib", default="", help="A/B of the selected leg against this libmscnn_hip.so, alternating child processes")
@@ -337,6 +428,9 @@ if a.parent_lib:
     sys.exit(0)
 if a.lib:
     use_lib(a.lib)
+if a.merge and a.vote is not None:
+    merge_vote_leg(a)
+    sys.exit(0)
 if a.merge:
     merge_leg(a)
     sys.exit(0)

@@ -10,6 +10,7 @@ detections/<comp_id>_<class>_<output>_results.txt written as dlmwrite does (:148
          [--out detections] [--comp-id cascade_mscnn] [--names bg,car,van,truck,tram] [--limit N]
          [--scales H1xW1,H2xW2,...] [--flip] [--merge-cap N]      # several forwards per frame, one NMS (Net.detect_merge_*)
          [--tiles RxC[:overlap_px]] [--views-batch]               # the frame cut into tiles; all views of a frame as ONE batched forward
+         [--vote [THR]]                                           # box voting behind the merged NMS (Net.set_box_voting, THR default 0.5)
          [--nms-type maxg|max] [--ovr-dnm union|min] [--nms-thr T]      # pNms.type / pNms.ovrDnm / bbNms's thr (Net.set_nms)
          [--roialign-one-pass]      # the ROIAlign heads of the net as one launch each (Net.set_roialign_one_pass; same results)
   python tools/run_cascademscnn.py --model kitti_car/cascade-mscnn-7s-576-2x --synthetic 8 --batch 2      # no dataset / weights at
@@ -30,6 +31,10 @@ driver runs exactly the calls it ran before they existed.
 resized on the device straight out of the uploaded frame (Net.set_image_views), with --flip each tile's mirror too; --views-batch
 (with --flip and/or --tiles) runs all views of a frame in ONE forward: the input reshaped to N images, one set_image_views, one
 forward, one detect_cascade_merge_add(..., list_of=), one detect_merge_end.  As tools/run_mscnn_detection.py; no pin on the reference.
+--vote [THR] (default 0.5): every kept box becomes the score-weighted mean of all candidates of its output, class and frame whose IoU
+with it is >= THR (Net.set_box_voting; on the device, between the merge and its read-back).  Alongside --scales / --flip / --tiles it
+votes over their forwards; without them the frame runs as a merge of ONE forward.  As tools/run_mscnn_detection.py; no pin on the
+reference, whose scripts neither merge nor vote.
 
 Everything here is host glue over calls the test-suite covers one by one (Net.set_images, forward, detect_cascade_multi,
 reshape_input, kitti.write_detections_dlm)."""
@@ -105,8 +110,8 @@ def parse_args(argv=None):
     add_merge_flags(ap)
     a = ap.parse_args(argv)
     check_merge_flags(ap, a)
-    if (a.scales or a.flip or a.tiles) and (a.orig_size or a.dump_blobs):
-        ap.error("--scales / --flip / --tiles name the input sizes themselves and keep no single forward's blobs: not with --orig-size / "
+    if (a.scales or a.flip or a.tiles or a.vote is not None) and (a.orig_size or a.dump_blobs):
+        ap.error("--scales / --flip / --tiles / --vote name the input sizes themselves and keep no single forward's blobs: not with --orig-size / "
                  "--dump-blobs")
     if not (a.prototxt or a.model) or not (a.images or a.synthetic):
         ap.error("need --prototxt or --model, and --images or --synthetic N")
@@ -176,7 +181,10 @@ def main(argv=None):
     # detect_cascade_merge_add (the mirrored forward with the view flip_x = 1), then one detect_merge_end
     # --tiles / --views-batch: the views come straight out of the frame uploaded once (Net.set_image_views), with --views-batch all of
     # them in ONE forward and one detect_cascade_merge_add(..., list_of=)
-    passes = merge_passes(a, shape[2:]) if (a.scales or a.flip or a.tiles) else []
+    # --vote: sticky box voting in every detect_merge_end; on its own the frame is a merge of one forward
+    passes = merge_passes(a, shape[2:]) if (a.scales or a.flip or a.tiles or a.vote is not None) else []
+    if a.vote is not None:
+        net.set_box_voting(a.vote)
     by_views = bool(a.tiles or a.views_batch)
     n_fwd = len(a.scales or [0]) * views_per_frame(a) if by_views else len(passes)
 

@@ -15,6 +15,7 @@ examples/kitti_result/writeDetForEval.m.
                                                              # the det_thr of the WiderFace plain flow (Net.set_nms, once per run)
          [--scales H1xW1,H2xW2,...] [--flip] [--merge-cap N] # several forwards per frame, one NMS (Net.detect_merge_*)
          [--tiles RxC[:overlap_px]] [--views-batch]          # the frame cut into tiles; all views of a frame as ONE batched forward
+         [--vote [THR]]                                      # box voting behind the merged NMS (Net.set_box_voting, THR default 0.5)
   python tools/run_mscnn_detection.py --model kitti_car/mscnn-7s-576 --synthetic 8      # no dataset / weights at hand: the generated
                                                                                         # deploy net, seeded weights, synthetic frames
 
@@ -47,6 +48,12 @@ of them before ONE NMS per class.  --views-batch (with --flip and/or --tiles) ru
 reshaped to N images, one set_image_views (the frame is uploaded once), one forward, one detect_merge_add(..., list_of=), one
 detect_merge_end; without it the views run as single forwards.  With --scales the same per input size.  No reference script has
 views: there is no pin on the reference for them either.
+
+--vote [THR] (default 0.5) refines every kept box behind the merged NMS: it becomes the score-weighted mean of all candidates of its
+class and frame -- from every forward -- whose IoU with it is >= THR (Net.set_box_voting, once per run; the vote runs on the device
+between the merge and its read-back).  Alongside --scales / --flip / --tiles it votes over their forwards; without them the frame
+runs as a merge of ONE forward, so the vote is there for a single forward too (its candidates are the rows the NMS suppressed).  No
+reference script votes: there is no pin on the reference for it.
 
 Everything here is host glue over calls the test-suite covers one by one (Net.set_image / set_images / set_image_views, forward,
 detect / detect_multi, detect_merge_*, proposals_multi, kitti.write_*)."""
@@ -133,6 +140,9 @@ def add_merge_flags(ap):
                     "as a view (Net.set_image_views) and merge their candidates before one NMS")
     ap.add_argument("--views-batch", action="store_true", help="with --flip and/or --tiles: all views of a frame as the images of ONE "
                     "forward (one set_image_views, one forward, one detect_merge_add(..., list_of=))")
+    ap.add_argument("--vote", nargs="?", type=float, const=0.5, default=None, metavar="THR", help="box voting behind the merged NMS "
+                    "(Net.set_box_voting): every kept box becomes the score-weighted mean of the candidates whose IoU with it is >= THR "
+                    "(default 0.5); without --scales / --flip / --tiles the frame runs as a merge of one forward")
 
 
 def check_merge_flags(ap, a):
@@ -148,8 +158,10 @@ def check_merge_flags(ap, a):
             ap.error(str(e))
     if a.views_batch and not (a.flip or a.tiles):
         ap.error("--views-batch batches the views of a frame: give --flip and/or --tiles")
-    if (a.scales or a.flip or a.tiles) and a.batch > 1:
-        ap.error("--scales / --flip / --tiles run one frame per forward (drop --batch; --views-batch batches a frame's views)")
+    if a.vote is not None and not 0.0 < a.vote < 1.0:
+        ap.error(f"--vote {a.vote:g}: the threshold must lie inside (0, 1)")
+    if (a.scales or a.flip or a.tiles or a.vote is not None) and a.batch > 1:
+        ap.error("--scales / --flip / --tiles / --vote run one frame per forward (drop --batch; --views-batch batches a frame's views)")
 
 
 def merge_cand_cap(prototxt_text, passes, merge_cap):
@@ -233,8 +245,8 @@ def parse_args(argv=None):
     add_merge_flags(ap)
     a = ap.parse_args(argv)
     check_merge_flags(ap, a)
-    if (a.scales or a.flip or a.tiles) and (a.rois_in or a.proposals_out or a.proposals_only):
-        ap.error("--scales / --flip / --tiles merge detections: not with --rois-in, --proposals-out or --proposals-only")
+    if (a.scales or a.flip or a.tiles or a.vote is not None) and (a.rois_in or a.proposals_out or a.proposals_only):
+        ap.error("--scales / --flip / --tiles / --vote merge detections: not with --rois-in, --proposals-out or --proposals-only")
     if a.proposals_only and not a.proposals_out:
         ap.error("--proposals-only needs --proposals-out DIR")
     if a.proposals_only and a.rois_in:
@@ -297,7 +309,7 @@ def main(argv=None):
     rois = read_rois(a.rois_in, len(files)) if a.rois_in else None
     if a.batch > 1:
         return run_batched(a, net, files, names, cls_ids, imgH, imgW, per_class, per_image_props, forward, rois)
-    if a.scales or a.flip or a.tiles:
+    if a.scales or a.flip or a.tiles or a.vote is not None:
         return run_merged(a, net, text, files, names, cls_ids, imgH, imgW, per_class)
     used = 0.0
     for k, path in enumerate(files, start=1):
@@ -345,6 +357,8 @@ def run_merged(a, net, text, files, names, cls_ids, imgH, imgW, per_class):
     cand_cap = merge_cand_cap(text, n_fwd, a.merge_cap)
     shape = (1, 3, imgH, imgW)
     used = 0.0
+    if a.vote is not None:
+        net.set_box_voting(a.vote)                                            # sticky: every detect_merge_end below votes
 
     def add(params, mviews, list_of):
         p = [dict(q, proposal_thr=a.proposal_thr, nms_overlap=a.nms_overlap) for q in params]
