@@ -51,6 +51,7 @@
  *   detections*                blobs, ids_out, count_out_dev 4; dets_out 8: refuses
  *   detections_candidates_*, detections_merge_fwd   cand, workspace, pack_dev 16: refuses; the blobs 4
  *   detections_merge_vote_fwd  cand, pack_dev 16: refuses
+ *   detections_merge_soft_fwd  cand, workspace, pack_dev 16: refuses
  *   proposals_multi_fwd        props 8: refuses
  *   rois_ingest                rows 8: refuses; rois, props, image_rows, status 4
  */
@@ -738,6 +739,43 @@ MSCNN_API int mscnn_detections_merge_fwd(const double* nms_overlap, const mscnn_
 typedef struct { double thr; } mscnn_vote_params;     /* 0 < thr < 1 */
 MSCNN_API int mscnn_detections_merge_vote_fwd(const mscnn_vote_params* vote, int num_segments, const void* cand, int cand_cap,
                                               void* pack_dev, void* stream);
+
+/* Soft-NMS over the merged candidates (Bodla et al., 2017), beside mscnn_detections_merge_fwd: where the hard NMS deletes every
+ * candidate that overlaps a kept box, this op DECAYS its score -- the form the multi-scale / flip / tiled recipe is most often run
+ * with in crowded scenes, where two true objects overlap by more than the NMS threshold and N forwards make every cluster N times
+ * denser.  It reads the candidate buffer exactly as mscnn_detections_merge_fwd does and writes the same multi pack,
+ * mscnn_multi_pack_layout_of(S, S * cand_cap): header {S, cand_cap, S * cand_cap, 0}, table entry {count, wanted, s * cand_cap, 0}
+ * (count -1: the list overflowed, nothing else of it is written), rows [x y w h score] + tag in PICK order -- so
+ * mscnn_detections_merge_vote_fwd and every reader of the merge's pack work on it unchanged.  The kernels write every header and
+ * table word; rows of a slot past its count are left as they were; cand is read only.
+ * Per segment s, with n = min(wanted, cand_cap) candidates in slot order (wanted < 0: n = 0), s_j = (double)prob_j, all live, D = 0:
+ *   1. stop when nothing is live, or when max_out > 0 && D == max_out;
+ *   2. m = the live candidate with the largest s; among equal s the lowest slot index wins -- the merge's own tie rule: the pass
+ *      added first, then the lower row.  A NaN s ranks below every number (and with the NaNs and -inf, again the lowest slot);
+ *   3. stop when !(s_m >= score_thr);
+ *   4. pack row s * cand_cap + D = box m bit for bit, s_m, tag m; m is dead; D = D + 1;
+ *   5. for every live j, with A = box m and B = box j, in double, the vote's overlap statements, the union form always:
+ *          iw = fmin(A.x + A.w, B.x + B.w) - fmax(A.x, B.x)   (iw <= 0: no decay);   ih likewise;
+ *          o = iw * ih;   u = A.w * A.h + B.w * B.h - o;   r = o / u                  (a NaN r: no decay)
+ *          MSCNN_SOFT_NMS_LINEAR:    if (r > nms_overlap[s]) s_j = s_j * (1.0 - r)
+ *          MSCNN_SOFT_NMS_GAUSSIAN:  s_j = s_j * exp(-(r * r) / sigma)                (nms_overlap is not read)
+ *      every operation rounded, no fma; back to 1.
+ * The argmax is a maximum under a TOTAL order (score, then the lower slot), so the result depends on no reduction shape, grid size,
+ * scheduling or timing; no atomics.  The linear method is IEEE operations only and is bit-exact against tests/soft_witness.py; the
+ * gaussian one calls the device library's exp (picks and counts exact while no two scores lie within a few ulps of each other).
+ * ANY cand_cap is served: one workgroup of 1024 threads owns a list; a list whose count is <= 4096 lives in registers, a longer one
+ * keeps its scores and live flags in the workspace and reads the boxes from cand -- the same arithmetic per candidate, the same bits.
+ * workspace: mscnn_detections_merge_soft_workspace_bytes(S, cand_cap) bytes (0: refused arguments).  nms_overlap[S]: a HOST array.
+ * Refused before any launch, naming the value: null pointers, S < 1, cand_cap < 1 (or S * cand_cap past 2^31 - 1), a method outside
+ * {1, 2}, gaussian with a sigma that is not finite or not > 0, a score_thr that is NaN, infinite or < 0, max_out < 0, a NaN overlap
+ * with linear, cand / workspace / pack_dev not 16-byte aligned, a workspace that is too small (MSCNN_ERR_WORKSPACE).
+ * No pin on the reference: its scripts neither merge nor decay a score.  The check is tests/soft_witness.py: a float64 numpy
+ * restatement of the five steps (linear: bit for bit) and the linear method in exact rationals. */
+enum { MSCNN_SOFT_NMS_LINEAR = 1, MSCNN_SOFT_NMS_GAUSSIAN = 2 };
+typedef struct { int method; double sigma; double score_thr; int max_out; } mscnn_soft_nms_params;
+MSCNN_API size_t mscnn_detections_merge_soft_workspace_bytes(int num_segments, int cand_cap);
+MSCNN_API int mscnn_detections_merge_soft_fwd(const double* nms_overlap, const mscnn_soft_nms_params* soft, int num_segments, void* cand,
+                                              int cand_cap, void* pack_dev, void* workspace, size_t workspace_bytes, void* stream);
 
 /* The proposal half of the scripts' result (run_mscnn_detection.m:75-91, `final_proposals{k}`) for every image of a batched forward
  * in one pass.  props [R_all][6] = BoxOutput's proposals_score, rows [img x1 y1 x2 y2 score] grouped by image in ascending order;

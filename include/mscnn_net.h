@@ -405,6 +405,18 @@ MSCNN_NET_API int mscnn_net_detect_merge_end(mscnn_net* net, double* dets_host, 
  * the check is tests/vote_witness.py (the op's documented summation order, bit for bit). */
 MSCNN_NET_API int mscnn_net_set_box_voting(mscnn_net* net, double thr);
 MSCNN_NET_API int mscnn_net_get_box_voting(const mscnn_net* net, double* thr);
+/* Soft-NMS in place of the merge's hard NMS (mscnn_hip.h: mscnn_detections_merge_soft_fwd; Bodla et al., 2017): while it is on,
+ * mscnn_net_detect_merge_end enqueues the soft op where it enqueued mscnn_detections_merge_fwd -- a candidate that overlaps a picked
+ * box is not deleted, its score is decayed (method 1, linear: by 1 - IoU above the list's nms_overlap; method 2, gaussian: by
+ * exp(-IoU^2 / sigma)) -- and every detection comes back with its decayed score, in pick order; candidates are picked until the best
+ * live score is below score_thr or, with max_out > 0, max_out are out.  The sticky set_nms type / ovr_dnm are not read by the soft
+ * op (the union form always; thr / det_thr were applied by the adds).  With box voting on, the vote runs behind it; the read-back is
+ * unchanged.  Sticky, like mscnn_net_set_box_voting: method 0 is off (the default; _end then enqueues exactly what it always did; the
+ * other three values are stored as given).  Refused, naming the value and changing nothing: a method outside {0, 1, 2}, gaussian
+ * with a sigma that is not finite or not > 0, a score_thr that is NaN, infinite or < 0, max_out < 0.  Both calls work on a net built
+ * with device -1.  No pin on the reference: its scripts neither merge nor decay a score; the check is tests/soft_witness.py. */
+MSCNN_NET_API int mscnn_net_set_soft_nms(mscnn_net* net, int method, double sigma, double score_thr, int max_out);
+MSCNN_NET_API int mscnn_net_get_soft_nms(const mscnn_net* net, int* method, double* sigma, double* score_thr, int* max_out);
 /* The views of a frame as ONE batched forward (mscnn_hip.h: mscnn_detections_candidates_add_views): the merge was opened with
  * _begin(num_frames, ...), the input holds N images -- the views mscnn_net_set_image_views wrote --, p[N * K] and view[N] describe
  * them as in _add, and list_of[N] (host) names the frame of each: the rows of image b go to the lists of frame list_of[b].  One

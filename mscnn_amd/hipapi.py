@@ -233,6 +233,10 @@ def lib():
         L.mscnn_detections_merge_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                                  C.c_void_p]
         L.mscnn_detections_merge_vote_fwd.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.mscnn_detections_merge_soft_workspace_bytes.restype = C.c_size_t
+        L.mscnn_detections_merge_soft_workspace_bytes.argtypes = [C.c_int, C.c_int]
+        L.mscnn_detections_merge_soft_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                      C.c_void_p]
         L.mscnn_proposals_multi_pack_bytes.restype = C.c_size_t
         L.mscnn_proposals_multi_pack_bytes.argtypes = [C.c_int, C.c_int]
         L.mscnn_proposals_multi_fwd.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
@@ -1004,6 +1008,23 @@ class VoteParams(C.Structure):
     _fields_ = [("thr", C.c_double)]
 
 
+SOFT_NMS_METHODS = {"linear": 1, "gaussian": 2}      # MSCNN_SOFT_NMS_LINEAR / _GAUSSIAN
+
+
+class SoftNmsParams(C.Structure):
+    """mscnn_soft_nms_params: method 1 = linear, 2 = gaussian; sigma (gaussian only) > 0; score_thr >= 0; max_out 0 = no bound."""
+    _fields_ = [("method", C.c_int), ("sigma", C.c_double), ("score_thr", C.c_double), ("max_out", C.c_int)]
+
+
+def soft_nms_method(method):
+    """A method's number from its name ("linear", "gaussian"); a number passes through for the library to judge."""
+    if isinstance(method, str):
+        if method not in SOFT_NMS_METHODS:
+            raise MscnnError(f"soft nms: method {method!r} is none of {sorted(SOFT_NMS_METHODS)}")
+        return SOFT_NMS_METHODS[method]
+    return int(method)
+
+
 def _view_array(views, num_images):
     """views: None (NULL, the identity) or one (off_x, off_y, flip_x) per image."""
     if views is None:
@@ -1132,18 +1153,43 @@ class Candidates:
                                                 _stream()))
         if vote_thr is not None:
             self.vote(pack, vote_thr)
+        return self._read_pack(pack, nbytes, raw_pack, "detections_merge")
+
+    def merge_soft(self, method, sigma=0.5, score_thr=0.001, max_out=0, nms_overlap=None, raw_pack=False, pack=None, ws=None, vote_thr=None):
+        """mscnn_detections_merge_soft_fwd: Soft-NMS over each list in place of merge()'s hard NMS -- method "linear" (decay by 1 - IoU
+        above the list's nms_overlap) or "gaussian" (by exp(-IoU^2 / sigma)); picks until the best live score is below score_thr or,
+        with max_out > 0, max_out are out.  Returns what merge() returns, the rows in pick order with their decayed scores."""
+        S, cap = self.S, self.cap
+        ov = self.overlap if nms_overlap is None else nms_overlap
+        ov = (C.c_double * S)(*[float(v) for v in (ov if ov is not None else [0.5] * S)])
+        nbytes = lib().mscnn_detections_multi_pack_bytes(S, S * cap)
+        if pack is None:
+            pack = torch.zeros(nbytes, dtype=torch.uint8, device=self.buf.device)
+        wb = lib().mscnn_detections_merge_soft_workspace_bytes(S, cap)
+        if ws is None:
+            ws = torch.empty(max(wb, 1), dtype=torch.uint8, device=self.buf.device)
+        soft = SoftNmsParams(soft_nms_method(method), float(sigma), float(score_thr), int(max_out))
+        _check(lib().mscnn_detections_merge_soft_fwd(ov, C.byref(soft), S, _dev(self.buf), cap, _dev(pack), _dev(ws), C.c_size_t(ws.numel()),
+                                                     _stream()))
+        if vote_thr is not None:
+            self.vote(pack, vote_thr)
+        return self._read_pack(pack, nbytes, raw_pack, "detections_merge_soft")
+
+    def _read_pack(self, pack, nbytes, raw_pack, what):
+        """The merge's multi pack on the host: [(dets, tags, candidates)] per segment, with raw_pack also its bytes."""
+        S, cap = self.S, self.cap
         h = pack[:nbytes].cpu().numpy()
         table = 16 * (S + 1)
         hdr = h[:table].view(np.int32).reshape(S + 1, 4)
         if list(hdr[0]) != [S, cap, S * cap, 0]:
-            raise MscnnError(f"detections_merge: pack header {hdr[0].tolist()}")
+            raise MscnnError(f"{what}: pack header {hdr[0].tolist()}")
         dets = h[table:table + 40 * S * cap].view(np.float64).reshape(-1, 5)
         tags = h[table + 40 * S * cap:table + 44 * S * cap].view(np.int32)
         out = []
         for s in range(S):
             cnt, cands, row0, zero = (int(v) for v in hdr[1 + s])
             if row0 != s * cap or zero != 0:
-                raise MscnnError(f"detections_merge: table entry {s}: {hdr[1 + s].tolist()}")
+                raise MscnnError(f"{what}: table entry {s}: {hdr[1 + s].tolist()}")
             out.append((dets[row0:row0 + cnt].copy(), tags[row0:row0 + cnt].copy(), cands) if cnt >= 0 else (None, None, cands))
         return (out, h) if raw_pack else out
 

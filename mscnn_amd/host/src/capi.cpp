@@ -3,6 +3,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <functional>
 #include <string>
@@ -35,6 +36,8 @@ struct mscnn_net {
   bool nms_set = false;                    // false: the defaults -- the calls hand the ops NULL and run what they always ran
   // mscnn_net_set_box_voting: 0 = off (detect_merge_end enqueues what it always did), else the vote's overlap threshold in (0, 1)
   double vote_thr = 0.0;
+  // mscnn_net_set_soft_nms: method 0 = off (detect_merge_end runs mscnn_detections_merge_fwd, as it always did), else the soft op's knobs
+  mscnn_soft_nms_params soft = {0, 0.5, 0.001, 0};
   // mscnn_net_detect_merge_*: the candidate lists of the forwards added since _begin (mscnn_hip.h: mscnn_detections_candidates_*)
   struct Merge {
     bool open = false;
@@ -488,6 +491,27 @@ int mscnn_net_get_box_voting(const mscnn_net* n, double* thr) {
   return guarded([&] {
     CHECK(n && thr);
     *thr = n->vote_thr;
+  });
+}
+
+int mscnn_net_set_soft_nms(mscnn_net* n, int method, double sigma, double score_thr, int max_out) {
+  return guarded([&] {
+    CHECK(n != nullptr);
+    // (the op's own refusals, made here so that a refused value changes nothing and is named at the call that brought it)
+    CHECK(method == 0 || method == MSCNN_SOFT_NMS_LINEAR || method == MSCNN_SOFT_NMS_GAUSSIAN)
+        << "set_soft_nms: method " << method << " is neither 0 (off), " << MSCNN_SOFT_NMS_LINEAR << " (linear) nor " << MSCNN_SOFT_NMS_GAUSSIAN
+        << " (gaussian)";
+    CHECK(method != MSCNN_SOFT_NMS_GAUSSIAN || (sigma > 0 && sigma < HUGE_VAL)) << "set_soft_nms: sigma " << sigma << " is not a finite value > 0";
+    CHECK(score_thr >= 0 && score_thr < HUGE_VAL) << "set_soft_nms: score_thr " << score_thr << " is not a finite value >= 0";
+    CHECK_GE(max_out, 0) << "set_soft_nms: max_out " << max_out;
+    n->soft = mscnn_soft_nms_params{method, sigma, score_thr, max_out};
+  });
+}
+
+int mscnn_net_get_soft_nms(const mscnn_net* n, int* method, double* sigma, double* score_thr, int* max_out) {
+  return guarded([&] {
+    CHECK(n && method && sigma && score_thr && max_out);
+    *method = n->soft.method; *sigma = n->soft.sigma; *score_thr = n->soft.score_thr; *max_out = n->soft.max_out;
   });
 }
 
@@ -1427,11 +1451,13 @@ int mscnn_net_detect_merge_end(mscnn_net* n, double* dets_host, int* pass_host, 
     const size_t total = mscnn_multi_pack_layout_of(S, S * m.cand_cap).total;
     ensure_det_host(n, total);
     *static_cast<volatile int*>(n->det_host) = -1;      // the header's first word: the kernels must have written it
-    const size_t wb = mscnn_detections_merge_workspace_bytes(S, m.cand_cap);
+    const bool soft = n->soft.method != 0;      // Soft-NMS (mscnn_net_set_soft_nms) in place of the hard merge: the same pack
+    const size_t wb = soft ? mscnn_detections_merge_soft_workspace_bytes(S, m.cand_cap) : mscnn_detections_merge_workspace_bytes(S, m.cand_cap);
     void* ws = n->det_ws.Reserve(wb);
     // (the merge kernels only ever WRITE the pack: they write it straight into host-coherent pinned memory, as the blocking detect
     // calls do; the vote reads back the table and each kept row's own box from there, in stream order, and nothing else)
-    MSCNN_CHECK(mscnn_detections_merge_fwd(m.overlap.data(), nms_arg(n, false), S, m.cand.get(), m.cand_cap, n->det_host_dev, ws, wb, st));
+    if (soft) MSCNN_CHECK(mscnn_detections_merge_soft_fwd(m.overlap.data(), &n->soft, S, m.cand.get(), m.cand_cap, n->det_host_dev, ws, wb, st));
+    else MSCNN_CHECK(mscnn_detections_merge_fwd(m.overlap.data(), nms_arg(n, false), S, m.cand.get(), m.cand_cap, n->det_host_dev, ws, wb, st));
     if (n->vote_thr != 0.0) {      // box voting (mscnn_net_set_box_voting): the kept rows of that pack, refined in place from the lists
       const mscnn_vote_params vote = {n->vote_thr};
       MSCNN_CHECK(mscnn_detections_merge_vote_fwd(&vote, S, m.cand.get(), m.cand_cap, n->det_host_dev, st));

@@ -112,6 +112,7 @@ def lib():
             "mscnn_net_detect_merge_add_views": [vp, vp, vp, vp],
             "mscnn_net_detect_cascade_merge_add_views": [vp, vp, vp, vp, ci, vp, vp, vp, C.c_float],
             "mscnn_net_set_box_voting": [vp, C.c_double], "mscnn_net_get_box_voting": [vp, vp],
+            "mscnn_net_set_soft_nms": [vp, ci, C.c_double, C.c_double, ci], "mscnn_net_get_soft_nms": [vp, vp, vp, vp, vp],
         }
         for name, args in sig.items():
             getattr(L, name).argtypes = args
@@ -526,6 +527,26 @@ class Net:
         thr = C.c_double()
         _check(lib().mscnn_net_get_box_voting(self._h, C.byref(thr)))
         return None if thr.value == 0.0 else thr.value
+
+    SOFT_NMS_METHODS = {None: 0, "off": 0, "linear": 1, "gaussian": 2}
+
+    def set_soft_nms(self, method=None, sigma=0.5, score_thr=0.001, max_out=0):
+        """mscnn_net_set_soft_nms: from now on detect_merge_end runs Soft-NMS (mscnn_detections_merge_soft_fwd) in place of the hard
+        NMS: a candidate that overlaps a picked box keeps living with a decayed score -- method "linear" (by 1 - IoU above nms_overlap)
+        or "gaussian" (by exp(-IoU^2 / sigma)) --, picks end below score_thr or, with max_out > 0, after max_out.  method None = off
+        (the default).  A refused value fails naming it and the setting stays as it was."""
+        m = self.SOFT_NMS_METHODS.get(method, method) if isinstance(method, (str, type(None))) else method
+        if isinstance(m, str):
+            raise NetError(f"set_soft_nms: method {method!r} is none of 'linear', 'gaussian', None")
+        _check(lib().mscnn_net_set_soft_nms(self._h, int(m), float(sigma), float(score_thr), int(max_out)))
+
+    def get_soft_nms(self):
+        """mscnn_net_get_soft_nms: None = off, else dict(method, sigma, score_thr, max_out)."""
+        m, mo, sg, th = C.c_int(), C.c_int(), C.c_double(), C.c_double()
+        _check(lib().mscnn_net_get_soft_nms(self._h, C.byref(m), C.byref(sg), C.byref(th), C.byref(mo)))
+        if m.value == 0:
+            return None
+        return dict(method={1: "linear", 2: "gaussian"}[m.value], sigma=sg.value, score_thr=th.value, max_out=mo.value)
 
     @staticmethod
     def _params(cls_id, ratios, org_hw, bbox_mean, bbox_std, proposal_thr, nms_overlap):

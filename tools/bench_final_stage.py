@@ -30,6 +30,11 @@ Cases: kitti_car 7s-576 at two input sizes plus a mirrored forward, caltech 7s-4
 the merge alone, the merge + the vote op, and the merge + a copy of every candidate list to the host + voting in numpy there -- what a
 caller has without the op.  Each form runs from an idle device to the detections on the host; the three rotate which runs first.
 
+--merge --soft is Soft-NMS over those candidate lists (mscnn_detections_merge_soft_fwd): the hard merge, the soft op with both methods,
+unbounded and with --max-dets 300, and a copy of every candidate list to the host + a vectorised numpy Soft-NMS there -- what a caller
+has without the op.  Each form runs from an idle device to the detections on the host, the forms rotate which runs first; the table
+gives us per pick, and two synthetic one-list cases (4096 and 8000 candidates) price the kernel's register and streaming paths.
+
 --lib path/to/libmscnn_hip.so runs whatever leg is selected with THAT build's kernels under the Net (it is loaded first, so the Net's
 calls bind to it; the per-range op calls of the batched cascade case's per-call form go through hipapi's own handle and stay this
 build's).  --parent-lib path/to/libmscnn_hip.so repeats the selected leg --rounds times in child processes, this build and
@@ -356,6 +361,129 @@ def merge_vote_leg(a):
         del n
 
 
+def host_soft(cand, method, overlap, sigma, thr, max_out):
+    """Soft-NMS as a caller writes it in numpy today: one pick per iteration, the decay of all live candidates vectorised."""
+    box, s = cand[:, :4], cand[:, 4].copy()
+    xe, ye, area = box[:, 0] + box[:, 2], box[:, 1] + box[:, 3], box[:, 2] * box[:, 3]
+    live = np.ones(len(cand), bool)
+    picks, scores = [], []
+    while live.any() and not (max_out and len(picks) == max_out):
+        m = int(np.argmax(np.where(live, s, -np.inf)))
+        if not s[m] >= thr:
+            break
+        picks.append(m); scores.append(s[m])
+        live[m] = False
+        iw = np.minimum(xe[m], xe) - np.maximum(box[m, 0], box[:, 0])
+        ih = np.minimum(ye[m], ye) - np.maximum(box[m, 1], box[:, 1])
+        o = iw * ih
+        with np.errstate(divide="ignore", invalid="ignore"):
+            r = np.where((iw > 0) & (ih > 0), o / (area[m] + area - o), 0.0)
+        if method == "linear":
+            s = np.where(live & (r > overlap), s * (1.0 - r), s)
+        else:
+            s = np.where(live & (r > 0), s * np.exp(-(r * r) / sigma), s)
+    return np.concatenate([box[picks], np.array(scores)[:, None]], 1) if picks else np.zeros((0, 5))
+
+
+def synthetic_lists(hipapi, n, seed=31):
+    """One list of n candidates out of two adds: clusters of about five boxes on a 16-column grid, every row a survivor."""
+    import torch
+    cand = hipapi.Candidates(1, n)
+    kw = dict(cls_id=2, bbox_mean=(0, 0, 0, 0), bbox_std=(0.1, 0.1, 0.2, 0.2), proposal_thr=-10.0, ratios=(1.0, 1.0), org_hw=(20000, 20000),
+              nms_overlap=0.5)
+    for k, rows in enumerate((n - n // 2, n // 2)):
+        rng = np.random.default_rng(seed + k)
+        m = rng.integers(0, max(1, rows // 5), rows)
+        xy = np.stack([120 * (m % 16) + 20, 120 * (m // 16) + 20], 1) + rng.integers(-6, 7, (rows, 2))
+        wh = rng.choice([14, 20, 32, 48], (rows, 2))
+        props = np.concatenate([np.zeros((rows, 1)), xy, xy + wh, rng.uniform(-1, 1, (rows, 1))], 1).astype(np.float32)
+        blobs = ((rng.standard_normal((rows, 8)) * 0.3).astype(np.float32), (rng.standard_normal((rows, 2)) * 2).astype(np.float32), props)
+        cand.add(*[torch.from_numpy(np.ascontiguousarray(b)).cuda() for b in blobs], 1, [kw])
+    return cand
+
+
+SOFT_SYNTHETIC = {"synthetic-1x4096-registers": 4096, "synthetic-1x8000-streamed": 8000}      # both paths of the kernel, one list each
+
+
+def merge_soft_leg(a):
+    """--merge --soft: behind the same adds, the hard merge against the soft op (both methods, unbounded and with --max-dets 300)
+    against the lists copied to the host + a vectorised numpy Soft-NMS there (linear, unbounded): what a caller has without the op.
+    All forms end with the detections on the host.  us / pick = a form's time over the picks of its LONGEST list (the lists run side
+    by side, one workgroup each); it includes the launch and the read-back.  Two synthetic one-list cases price the kernel's two
+    paths: 4096 candidates (the list in registers) and 8000 (scores and live flags streamed through the workspace)."""
+    import torch
+    from mscnn_amd import hipapi
+    thr, sigma, md = a.soft_thr, 0.5, 300
+    names = ["hard merge", "soft linear", "soft gaussian", f"linear max {md}", f"gaussian max {md}", "lists to host + numpy linear"]
+    print(f"# Soft-NMS over the merged candidates (score_thr {thr:g}, sigma {sigma:g}) per frame group, host wall ms from an idle device to the "
+          f"detections on the host (median over {a.steps} steps after {a.warmup} warm-up; {a.rounds} rounds: median of the medians, spread = max "
+          f"- min), regime {a.regime}; picks = those of the longest list; us/pick = ms * 1000 / picks")
+    print(f"# {'case':30s} {'B':>2s} {'cands':>6s} {'longest':>7s} | " + " | ".join(f"{nm:>28s} {'picks':>5s} {'spread':>6s} {'us/pick':>7s}" for nm in names))
+    for name in a.case or (list(MERGE_CASES) + list(SOFT_SYNTHETIC)):
+        if name in SOFT_SYNTHETIC:
+            B, S, cap = 1, 1, SOFT_SYNTHETIC[name]
+            cand = synthetic_lists(hipapi, cap)
+        else:
+            model, B, classes, org, forwards = MERGE_CASES[name]
+            n = mnet.Net(prototxt_text=zoo.prototxt(model, batch=B))
+            synth.load_into(n, a.regime)
+            S, cap = B * len(classes), 2000 * B * len(forwards)
+            cand = hipapi.Candidates(S, cap)
+            for H, W, flipped in forwards:
+                f = np.concatenate([synth.frame(H, W, seed=1701 + b, org_hw=org) for b in range(B)], 0)
+                n.reshape_input("data", (B, 3, H, W))
+                n.set_blob("data", np.ascontiguousarray(f[..., ::-1]) if flipped else f)
+                n.forward()
+                R = n.blob_shape("proposals_score")[0]
+                blobs = [torch.from_numpy(n.get_blob(b).reshape(R, -1)).cuda() for b in ("bbox_pred", "cls_pred", "proposals_score")]
+                segs = [dict(cls_id=c, ratios=(H / float(org[0]), W / float(org[1])), org_hw=org, nms_overlap=0.5) for _ in range(B) for c in classes]
+                cand.add(*blobs, B, segs, views=[(0.0, 0.0, 1)] * B if flipped else None)
+            del n
+        pack = torch.zeros(hipapi.lib().mscnn_detections_multi_pack_bytes(S, S * cap), dtype=torch.uint8, device="cuda")
+        ws = torch.empty(max(hipapi.lib().mscnn_detections_merge_workspace_bytes(S, cap), 1), dtype=torch.uint8, device="cuda")
+        wss = torch.empty(hipapi.lib().mscnn_detections_merge_soft_workspace_bytes(S, cap), dtype=torch.uint8, device="cuda")
+        al = lambda v: (v + 255) // 256 * 256      # noqa: E731  (the candidate buffer's layout: include/mscnn_hip.h)
+        o0 = al(8 * S); o1 = o0 + al(32 * S * cap)
+
+        def on_host():
+            cnt = cand.counts()                           # (one small copy; then of every list the filled slots only: boxes, probs)
+            res = []
+            for s in range(S):
+                m = min(cnt[s][0], cap)
+                box = cand.buf[o0 + 32 * s * cap:o0 + 32 * (s * cap + m)].cpu().numpy().view(np.float64).reshape(m, 4)
+                prob = cand.buf[o1 + 4 * s * cap:o1 + 4 * (s * cap + m)].cpu().numpy().view(np.float32)
+                res.append((host_soft(np.concatenate([box, prob[:, None].astype(np.float64)], 1), "linear", 0.5, sigma, thr, 0), None, m))
+            return res
+
+        soft = lambda method, mo: (lambda: cand.merge_soft(method, sigma=sigma, score_thr=thr, max_out=mo, pack=pack, ws=wss))      # noqa: E731
+        forms = [lambda: cand.merge(pack=pack, ws=ws), soft("linear", 0), soft("gaussian", 0), soft("linear", md), soft("gaussian", md), on_host]
+        F = len(forms)
+        med = [[] for _ in range(F)]
+        for rnd in range(a.rounds):
+            t = [[] for _ in range(F)]
+            for step in range(a.warmup + a.steps):
+                res = [None] * F
+                for k in range(F):
+                    f = (k + step) % F
+                    torch.cuda.synchronize()      # (untimed: every form starts on an idle device)
+                    t0 = time.perf_counter()
+                    res[f] = forms[f]()
+                    dt = time.perf_counter() - t0
+                    if step >= a.warmup:
+                        t[f].append(dt)
+                for (d1, _, _), (d3, _, _), (d5, _, _) in zip(res[1], res[3], res[5]):      # the op against the host form, and max_out a prefix
+                    assert len(d1) == len(d5) and np.allclose(d1, d5, rtol=1e-12, atol=0) and np.array_equal(d3, d1[:md]), (name, step)
+            for f in range(F):
+                med[f].append(1e3 * float(np.median(t[f])))
+        cands = sum(c for _, _, c in res[1])
+        longest = max(c for _, _, c in res[1])
+        picks = [max(len(d) for d, _, _ in res[f]) for f in range(F)]
+        m = [float(np.median(v)) for v in med]
+        sp = [max(v) - min(v) for v in med]
+        print(f"  {name:30s} {B:2d} {cands:6d} {longest:7d} | " +
+              " | ".join(f"{m[f]:28.3f} {picks[f]:5d} {sp[f]:6.3f} {1e3 * m[f] / max(picks[f], 1):7.2f}" for f in range(F)), flush=True)
+
+
 def use_lib(path):
     """The kernels of another build of libmscnn_hip.so under this build's Net: loaded first and globally, the Net library's calls bind
     to it (checked on one final-stage symbol)."""
@@ -408,6 +536,9 @@ ap.add_argument("--merge", action="store_true", help="several forwards of a fram
                 "detect_merge_add per forward + detect_merge_end")
 ap.add_argument("--vote", nargs="?", type=float, const=0.5, default=None, metavar="THR", help="with --merge: the merge alone, the merge "
                 "+ the vote op, and the merge + every candidate list to the host + numpy voting")
+ap.add_argument("--soft", action="store_true", help="with --merge: the hard merge, the Soft-NMS op (linear and gaussian, unbounded and with "
+                "--max-dets 300) and every candidate list to the host + a vectorised numpy Soft-NMS; us per pick")
+ap.add_argument("--soft-thr", type=float, default=0.001, help="--merge --soft: the score threshold that ends the picking")
 ap.add_argument("--rounds", type=int, default=3, help="--merge / --parent-lib: repetitions of the whole measurement")
 ap.add_argument("--lib", default="", help="run with the kernels of this libmscnn_hip.so under the Net")
 ap.add_argument("--parent-lib", default="", help="A/B of the selected leg against this libmscnn_hip.so, alternating child processes")
@@ -430,6 +561,9 @@ if a.lib:
     use_lib(a.lib)
 if a.merge and a.vote is not None:
     merge_vote_leg(a)
+    sys.exit(0)
+if a.merge and a.soft:
+    merge_soft_leg(a)
     sys.exit(0)
 if a.merge:
     merge_leg(a)

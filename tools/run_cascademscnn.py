@@ -11,6 +11,7 @@ detections/<comp_id>_<class>_<output>_results.txt written as dlmwrite does (:148
          [--scales H1xW1,H2xW2,...] [--flip] [--merge-cap N]      # several forwards per frame, one NMS (Net.detect_merge_*)
          [--tiles RxC[:overlap_px]] [--views-batch]               # the frame cut into tiles; all views of a frame as ONE batched forward
          [--vote [THR]]                                           # box voting behind the merged NMS (Net.set_box_voting, THR default 0.5)
+         [--soft-nms linear|gaussian[:SIGMA]] [--soft-thr T] [--max-dets N]      # Soft-NMS in place of the merged NMS (Net.set_soft_nms)
          [--nms-type maxg|max] [--ovr-dnm union|min] [--nms-thr T]      # pNms.type / pNms.ovrDnm / bbNms's thr (Net.set_nms)
          [--roialign-one-pass]      # the ROIAlign heads of the net as one launch each (Net.set_roialign_one_pass; same results)
   python tools/run_cascademscnn.py --model kitti_car/cascade-mscnn-7s-576-2x --synthetic 8 --batch 2      # no dataset / weights at
@@ -35,6 +36,9 @@ forward, one detect_cascade_merge_add(..., list_of=), one detect_merge_end.  As 
 with it is >= THR (Net.set_box_voting; on the device, between the merge and its read-back).  Alongside --scales / --flip / --tiles it
 votes over their forwards; without them the frame runs as a merge of ONE forward.  As tools/run_mscnn_detection.py; no pin on the
 reference, whose scripts neither merge nor vote.
+--soft-nms linear|gaussian[:SIGMA] [--soft-thr T] [--max-dets N]: Soft-NMS in place of the merged hard NMS (Net.set_soft_nms; on the
+device): overlapping candidates keep living with decayed scores.  As tools/run_mscnn_detection.py; alone a merge of ONE forward; no
+pin on the reference, whose scripts neither merge nor decay a score.
 
 Everything here is host glue over calls the test-suite covers one by one (Net.set_images, forward, detect_cascade_multi,
 reshape_input, kitti.write_detections_dlm)."""
@@ -106,12 +110,12 @@ def parse_args(argv=None):
                     "forward as group_NNNN.npz (to re-run the final stage on exactly what a forward produced)")
     ap.add_argument("--roialign-one-pass", action="store_true", help="run every ROIAlign head (two ROIAlign layers, their 2x2 AVE "
                     "poolings, the Concat: the WiderFace cascade's) as one launch (Net.set_roialign_one_pass); off: the five layers")
-    from run_mscnn_detection import add_merge_flags, check_merge_flags
+    from run_mscnn_detection import add_merge_flags, check_merge_flags, one_forward_merge
     add_merge_flags(ap)
     a = ap.parse_args(argv)
     check_merge_flags(ap, a)
-    if (a.scales or a.flip or a.tiles or a.vote is not None) and (a.orig_size or a.dump_blobs):
-        ap.error("--scales / --flip / --tiles / --vote name the input sizes themselves and keep no single forward's blobs: not with --orig-size / "
+    if (a.scales or a.flip or a.tiles or one_forward_merge(a)) and (a.orig_size or a.dump_blobs):
+        ap.error("--scales / --flip / --tiles / --vote / --soft-nms name the input sizes themselves and keep no single forward's blobs: not with --orig-size / "
                  "--dump-blobs")
     if not (a.prototxt or a.model) or not (a.images or a.synthetic):
         ap.error("need --prototxt or --model, and --images or --synthetic N")
@@ -133,7 +137,8 @@ def main(argv=None):
     import numpy as np
     import torch
     from mscnn_amd import kitti, net as mnet, synth, zoo
-    from run_mscnn_detection import list_images, load_rgb_u8, merge_cand_cap, merge_passes, names_for, run_frame_views, views_per_frame
+    from run_mscnn_detection import (apply_merge_settings, list_images, load_rgb_u8, merge_cand_cap, merge_passes, names_for, one_forward_merge,
+                                     run_frame_views, views_per_frame)
 
     if a.prototxt:
         text = open(a.prototxt).read()
@@ -182,9 +187,9 @@ def main(argv=None):
     # --tiles / --views-batch: the views come straight out of the frame uploaded once (Net.set_image_views), with --views-batch all of
     # them in ONE forward and one detect_cascade_merge_add(..., list_of=)
     # --vote: sticky box voting in every detect_merge_end; on its own the frame is a merge of one forward
-    passes = merge_passes(a, shape[2:]) if (a.scales or a.flip or a.tiles or a.vote is not None) else []
-    if a.vote is not None:
-        net.set_box_voting(a.vote)
+    # --soft-nms: sticky Soft-NMS in place of that NMS; on its own a merge of one forward too
+    passes = merge_passes(a, shape[2:]) if (a.scales or a.flip or a.tiles or one_forward_merge(a)) else []
+    apply_merge_settings(net, a)
     by_views = bool(a.tiles or a.views_batch)
     n_fwd = len(a.scales or [0]) * views_per_frame(a) if by_views else len(passes)
 

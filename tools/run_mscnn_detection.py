@@ -16,6 +16,7 @@ examples/kitti_result/writeDetForEval.m.
          [--scales H1xW1,H2xW2,...] [--flip] [--merge-cap N] # several forwards per frame, one NMS (Net.detect_merge_*)
          [--tiles RxC[:overlap_px]] [--views-batch]          # the frame cut into tiles; all views of a frame as ONE batched forward
          [--vote [THR]]                                      # box voting behind the merged NMS (Net.set_box_voting, THR default 0.5)
+         [--soft-nms linear|gaussian[:SIGMA]] [--soft-thr T] [--max-dets N]      # Soft-NMS in place of the merged NMS (Net.set_soft_nms)
   python tools/run_mscnn_detection.py --model kitti_car/mscnn-7s-576 --synthetic 8      # no dataset / weights at hand: the generated
                                                                                         # deploy net, seeded weights, synthetic frames
 
@@ -54,6 +55,13 @@ class and frame -- from every forward -- whose IoU with it is >= THR (Net.set_bo
 between the merge and its read-back).  Alongside --scales / --flip / --tiles it votes over their forwards; without them the frame
 runs as a merge of ONE forward, so the vote is there for a single forward too (its candidates are the rows the NMS suppressed).  No
 reference script votes: there is no pin on the reference for it.
+
+--soft-nms linear|gaussian[:SIGMA] runs Soft-NMS (Bodla et al., 2017) in place of the merged hard NMS, on the device
+(Net.set_soft_nms, once per run): a candidate that overlaps a picked box is not deleted, its score is decayed -- linear: by 1 - IoU
+where the IoU is above --nms-overlap; gaussian: by exp(-IoU^2 / SIGMA), SIGMA defaults to 0.5 -- and the detections come out with
+their decayed scores; --soft-thr T (default 0.001) ends the picking, --max-dets N bounds it.  Alongside --scales / --flip / --tiles it
+runs over their forwards' candidates; alone the frame runs as a merge of ONE forward; with --vote the vote runs behind it.  No
+reference script decays a score: there is no pin on the reference for it.
 
 Everything here is host glue over calls the test-suite covers one by one (Net.set_image / set_images / set_image_views, forward,
 detect / detect_multi, detect_merge_*, proposals_multi, kitti.write_*)."""
@@ -143,6 +151,40 @@ def add_merge_flags(ap):
     ap.add_argument("--vote", nargs="?", type=float, const=0.5, default=None, metavar="THR", help="box voting behind the merged NMS "
                     "(Net.set_box_voting): every kept box becomes the score-weighted mean of the candidates whose IoU with it is >= THR "
                     "(default 0.5); without --scales / --flip / --tiles the frame runs as a merge of one forward")
+    ap.add_argument("--soft-nms", default=None, metavar="linear|gaussian[:SIGMA]", help="Soft-NMS in place of the merged hard NMS "
+                    "(Net.set_soft_nms): a candidate that overlaps a picked box keeps living with a decayed score -- linear: by 1 - IoU above "
+                    "--nms-overlap; gaussian: by exp(-IoU^2 / SIGMA), SIGMA default 0.5; without --scales / --flip / --tiles the frame runs "
+                    "as a merge of one forward")
+    ap.add_argument("--soft-thr", type=float, default=0.001, metavar="T", help="with --soft-nms: stop picking when the best live score is below T "
+                    "(default 0.001)")
+    ap.add_argument("--max-dets", type=int, default=0, metavar="N", help="with --soft-nms: at most N detections per class and frame (default 0: no "
+                    "bound)")
+
+
+def parse_soft_nms(text):
+    """'linear' | 'gaussian' | 'gaussian:SIGMA' -> (method, sigma)."""
+    import re
+    m = re.fullmatch(r"(linear|gaussian)(?::([^:]+))?", text.strip())
+    try:
+        sigma = float(m.group(2)) if m and m.group(2) else 0.5
+    except ValueError:
+        m = None
+    if not m or (m.group(1) == "linear" and m.group(2)) or not 0.0 < sigma < float("inf"):
+        raise ValueError(f"--soft-nms {text!r} is not linear, gaussian or gaussian:SIGMA with a finite SIGMA > 0")
+    return m.group(1), sigma
+
+
+def one_forward_merge(a):
+    """--vote and --soft-nms live in detect_merge_end: on their own they run the frame as a merge of one forward."""
+    return a.vote is not None or a.soft_nms is not None
+
+
+def apply_merge_settings(net, a):
+    """The sticky settings of every detect_merge_end of the run."""
+    if a.vote is not None:
+        net.set_box_voting(a.vote)
+    if a.soft_nms is not None:
+        net.set_soft_nms(a.soft_nms[0], sigma=a.soft_nms[1], score_thr=a.soft_thr, max_out=a.max_dets)
 
 
 def check_merge_flags(ap, a):
@@ -160,8 +202,20 @@ def check_merge_flags(ap, a):
         ap.error("--views-batch batches the views of a frame: give --flip and/or --tiles")
     if a.vote is not None and not 0.0 < a.vote < 1.0:
         ap.error(f"--vote {a.vote:g}: the threshold must lie inside (0, 1)")
-    if (a.scales or a.flip or a.tiles or a.vote is not None) and a.batch > 1:
-        ap.error("--scales / --flip / --tiles / --vote run one frame per forward (drop --batch; --views-batch batches a frame's views)")
+    if a.soft_nms is not None:
+        try:
+            a.soft_nms = parse_soft_nms(a.soft_nms)
+        except ValueError as e:
+            ap.error(str(e))
+    if not 0.0 <= a.soft_thr < float("inf"):
+        ap.error(f"--soft-thr {a.soft_thr:g}: the threshold must be a finite value >= 0")
+    if a.max_dets < 0:
+        ap.error(f"--max-dets {a.max_dets}: must be >= 0")
+    if a.soft_nms is None and (a.soft_thr != 0.001 or a.max_dets != 0):
+        ap.error("--soft-thr / --max-dets belong to --soft-nms")
+    if (a.scales or a.flip or a.tiles or one_forward_merge(a)) and a.batch > 1:
+        ap.error("--scales / --flip / --tiles / --vote / --soft-nms run one frame per forward (drop --batch; --views-batch batches a frame's "
+                 "views)")
 
 
 def merge_cand_cap(prototxt_text, passes, merge_cap):
@@ -245,8 +299,8 @@ def parse_args(argv=None):
     add_merge_flags(ap)
     a = ap.parse_args(argv)
     check_merge_flags(ap, a)
-    if (a.scales or a.flip or a.tiles or a.vote is not None) and (a.rois_in or a.proposals_out or a.proposals_only):
-        ap.error("--scales / --flip / --tiles / --vote merge detections: not with --rois-in, --proposals-out or --proposals-only")
+    if (a.scales or a.flip or a.tiles or one_forward_merge(a)) and (a.rois_in or a.proposals_out or a.proposals_only):
+        ap.error("--scales / --flip / --tiles / --vote / --soft-nms merge detections: not with --rois-in, --proposals-out or --proposals-only")
     if a.proposals_only and not a.proposals_out:
         ap.error("--proposals-only needs --proposals-out DIR")
     if a.proposals_only and a.rois_in:
@@ -309,7 +363,7 @@ def main(argv=None):
     rois = read_rois(a.rois_in, len(files)) if a.rois_in else None
     if a.batch > 1:
         return run_batched(a, net, files, names, cls_ids, imgH, imgW, per_class, per_image_props, forward, rois)
-    if a.scales or a.flip or a.tiles or a.vote is not None:
+    if a.scales or a.flip or a.tiles or one_forward_merge(a):
         return run_merged(a, net, text, files, names, cls_ids, imgH, imgW, per_class)
     used = 0.0
     for k, path in enumerate(files, start=1):
@@ -357,8 +411,7 @@ def run_merged(a, net, text, files, names, cls_ids, imgH, imgW, per_class):
     cand_cap = merge_cand_cap(text, n_fwd, a.merge_cap)
     shape = (1, 3, imgH, imgW)
     used = 0.0
-    if a.vote is not None:
-        net.set_box_voting(a.vote)                                            # sticky: every detect_merge_end below votes
+    apply_merge_settings(net, a)                                              # sticky: every detect_merge_end below votes / runs Soft-NMS
 
     def add(params, mviews, list_of):
         p = [dict(q, proposal_thr=a.proposal_thr, nms_overlap=a.nms_overlap) for q in params]
