@@ -1,4 +1,4 @@
-// Device helpers shared by boxoutput.hip and detections.hip (gfx950).
+// Device helpers shared by boxoutput.hip and the final stage (det_device.h and the files on it) (gfx950).
 #pragma once
 #include <type_traits>
 #include <hip/hip_runtime.h>

@@ -1,4 +1,4 @@
-// What detections.hip (the final stage) and proposals.hip (the proposal result) must agree on about BoxOutput's proposals_score rows
+// What det_device.h (the final stage's row transform) and proposals.hip (the proposal result) must agree on about BoxOutput's proposals_score rows
 // [img x1 y1 x2 y2 score]: where an image's rows are, and which of them the scripts keep.  One definition each, so the two stages can
 // not disagree about which ROI rows survive.
 #pragma once

@@ -1,6 +1,6 @@
 // More boxes than the LDS-resident fast path holds (K > kMaxK = 4032): a global-memory bitonic sort and a TILED greedy NMS.
 // Shared by boxoutput.hip (BoxOutput with max_nms_num 0 = "no cap" -- the caffe.proto default -- or > 4032, and the stand-alone
-// NMS entry) and detections.hip (final stage over more than 4032 ROIs).  The fast paths are untouched; these run only when the
+// NMS entry) and detections.hip (final stage over more than 4032 ROIs or merged candidates: det_tiled_nms).  The fast paths are untouched; these run only when the
 // host-side bound on K exceeds kMaxK.
 //
 // Greedy NMS (nmsMax, box_output_layer.cpp:38-63; bbNms.m:112-126) walks the boxes in sorted order, but a box only ever

@@ -384,6 +384,88 @@ def test_4032_candidates_take_the_one_pass_path_and_4033_the_tiled_one(hip, n0, 
         assert_equals_witness(got, witness_case(passes, [2], 0.5, "max", "min")[0])
 
 
+# ---- the plain adds on the list kernel: everything that can meet in one call, the buffer byte for byte ------------------------------------
+ROWS17 = [257, 0, 5, 64, 1, 63, 65, 3, 0, 256, 6, 4, 2, 5, 3, 6, 4]      # one step past 256, images without rows, 17 images
+VIEWS17 = [FLIP if i % 3 == 1 else (0.0, 0.0, 0) for i in range(17)]      # mirrored images among plain ones
+
+
+def expected_buffer(hip, S, cap, lists):
+    """The bytes of a candidate buffer that was poisoned, reset and given lists[s] = [(rows [n, 5] float64, tags [n])] in add order:
+    counts {n, 0}, the slots in order, every other byte still 0xFF."""
+    al = lambda v: (v + 255) // 256 * 256      # noqa: E731
+    o0 = al(8 * S); o1 = o0 + al(32 * S * cap); o2 = o1 + al(4 * S * cap); o3 = o2 + al(4 * S * cap)
+    assert o3 == hip.lib().mscnn_detections_candidates_bytes(S, cap)
+    buf = np.full(o3, 0xFF, np.uint8)
+    for s, passes in enumerate(lists):
+        rows = np.concatenate([r for r, _ in passes])
+        tags = np.concatenate([t for _, t in passes]).astype(np.int32)
+        n = len(rows)
+        assert n <= cap
+        buf[8 * s:8 * s + 8] = np.array([n, 0], np.int32).view(np.uint8)
+        buf[o0 + 32 * s * cap:o0 + 32 * (s * cap + n)] = np.ascontiguousarray(rows[:, :4]).view(np.uint8).ravel()
+        buf[o1 + 4 * s * cap:o1 + 4 * (s * cap + n)] = rows[:, 4].astype(np.float32).view(np.uint8)
+        buf[o2 + 4 * s * cap:o2 + 4 * (s * cap + n)] = tags.view(np.uint8)
+    return buf
+
+
+def poisoned_candidates(hip, S, cap):
+    cand = hip.Candidates(S, cap)
+    cand.buf.fill_(0xFF)
+    hip._check(hip.lib().mscnn_detections_candidates_reset(hip._dev(cand.buf), S, cap, hip._stream()))
+    return cand
+
+
+def test_plain_add_of_34_segments_with_views_thr_and_257_rows_fills_the_buffer_like_the_witness(hip):
+    """17 images x 2 classes = 34 lists (two launches), images of 257 and of 0 rows, a flip on some images, thr and det_thr set, two
+    forwards: every byte of the candidate buffer is the witness's."""
+    classes, thr = [2, 3], 0.2
+    passes = [Pass(0, ROWS17, 4, ratios=(1.5, 1.25), seed=51), Pass(1, ROWS17[::-1], 4, ratios=(1.0, 0.75), seed=51)]
+    passes[0].cls_pred[256] = [0.0, 5.0, 0.0, 0.0]      # (the one row of image 0's second step of 256 is kept for class 2)
+    det_thr = float(np.float32(0.25))
+    S, cap = 17 * len(classes), 2 * 257
+    cand = poisoned_candidates(hip, S, cap)
+    lists = [[] for _ in range(S)]
+    for k, p in enumerate(passes):
+        segs = [p.seg_kw(c) for _ in range(17) for c in classes]
+        cand.add(dev(p.bbox_pred), dev(p.cls_pred), dev(p.props), 17, segs, views=VIEWS17, nms=dict(thr=thr, det_thr=det_thr))
+        for i in range(17):
+            for ci, c in enumerate(classes):
+                p.view = VIEWS17[i]
+                rows, ids = p.witness_rows(i, c, thr, det_thr)
+                lists[i * len(classes) + ci].append((rows, (k << 24) | ids))
+    kept = [sum(len(r) for r, _ in l) for l in lists]
+    unfiltered = sum(len(p.witness_rows(0, 2)[0]) for p in passes)
+    assert 0 < kept[0] < unfiltered and kept[16] == kept[17] == 0 and 256 in (lists[0][0][1] & 0xffffff), \
+        "the thresholds, the empty image or the second step show nothing"
+    assert np.array_equal(cand.buf.cpu().numpy(), expected_buffer(hip, S, cap, lists))
+
+
+def test_cascade_add_of_68_segments_with_views_thr_and_257_rows_fills_the_buffer_like_the_witness(hip):
+    """The same meeting for _cascade_add: 17 images x 2 outputs x 2 classes = 68 lists (three launches)."""
+    classes, O, thr, det_thr = [1, 2], 2, 0.3, 0.1
+    specs = [dict(ratios=(1.5, 1.25)), dict(ratios=(1.0, 0.75))]
+    fw = [cascade_pass(k, ROWS17, O, 2, seed=53, **sp) for k, sp in enumerate(specs)]
+    fw[0][0][1][256] = 0.9                                # (the one row of image 0's second step of 256 is kept)
+    K = O * len(classes)
+    S, cap = 17 * K, 2 * 257
+    cand = poisoned_candidates(hip, S, cap)
+    row0 = np.concatenate([[0], np.cumsum(ROWS17)])
+    lists = [[] for _ in range(S)]
+    for k, sp in enumerate(specs):
+        segs = [dict(cls_id=c, ratios=sp["ratios"], org_hw=FRAME, nms_overlap=0.5) for _ in range(17) for _ in range(O) for c in classes]
+        cand.cascade_add([tuple(dev(b) for b in o) for o in fw[k]], 17, segs, det_thr=det_thr, views=VIEWS17, nms=dict(thr=thr))
+        for s in range(S):
+            i, o, c = s // K, (s % K) // len(classes), classes[s % len(classes)]
+            boxes, prob, props = fw[k][o]
+            sl = slice(row0[i], row0[i + 1])
+            r, ids = mw.cascade_rows(boxes[sl], prob[sl], props[sl], c, ratios=sp["ratios"], org_hw=FRAME, det_thr=det_thr, thr=thr)
+            lists[s].append((mw.apply_view(r, FRAME[1], VIEWS17[i]), (k << 24) | (ids + row0[i])))
+    kept = [sum(len(r) for r, _ in l) for l in lists]
+    assert 0 < kept[0] < 2 * 256 and kept[K] == 0 and kept[-1] > 0 and 256 in (lists[0][0][1] & 0xffffff), \
+        "the threshold, the empty image or the second step show nothing"
+    assert np.array_equal(cand.buf.cpu().numpy(), expected_buffer(hip, S, cap, lists))
+
+
 # ---- the buffer contract of the three ops ----------------------------------------------------------------------------------------------------
 @pytest.fixture
 def arena(hip, monkeypatch):
