@@ -52,6 +52,7 @@
  *   detections_candidates_*, detections_merge_fwd   cand, workspace, pack_dev 16: refuses; the blobs 4
  *   detections_merge_vote_fwd  cand, pack_dev 16: refuses
  *   detections_merge_soft_fwd  cand, workspace, pack_dev 16: refuses
+ *   detections_merge_matrix_fwd  cand, workspace, pack_dev 16: refuses
  *   proposals_multi_fwd        props 8: refuses
  *   rois_ingest                rows 8: refuses; rois, props, image_rows, status 4
  */
@@ -776,6 +777,53 @@ typedef struct { int method; double sigma; double score_thr; int max_out; } mscn
 MSCNN_API size_t mscnn_detections_merge_soft_workspace_bytes(int num_segments, int cand_cap);
 MSCNN_API int mscnn_detections_merge_soft_fwd(const double* nms_overlap, const mscnn_soft_nms_params* soft, int num_segments, void* cand,
                                               int cand_cap, void* pack_dev, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Matrix NMS over the merged candidates (Wang et al., "SOLOv2", NeurIPS 2020, Algorithm 1), beside mscnn_detections_merge_fwd and
+ * mscnn_detections_merge_soft_fwd: a score decay like Soft-NMS's, but with NO pick loop -- every candidate's decay is a min over
+ * the candidates ranked above it, compensated by their column maxima of the same IoU matrix: two parallel passes over the upper
+ * triangle instead of n serial picks.  It does NOT return Soft-NMS's scores: a decay here is the worst single pair, compensated,
+ * not a product over picks.  The op reads the candidate buffer exactly as the merge does and only reads it, and writes the same
+ * multi pack, mscnn_multi_pack_layout_of(S, S * cand_cap): header {S, cand_cap, S * cand_cap, 0}, table entry {count, wanted,
+ * s * cand_cap, 0} (count -1: the list overflowed, nothing else of it is written), rows [x y w h score'] + tag; rows past a count
+ * are left as they were; the kernels write every header and table word; mscnn_detections_merge_vote_fwd and every reader of the
+ * pack work on the result unchanged.  Per segment (-ffp-contract=off holds for the library: no fma):
+ *   1. n = min(wanted, cand_cap), and n = 0 when wanted < 0.  The candidates are put in the merge's own order: larger prob first,
+ *      then the earlier slot (det_key(prob, slot)).  Call the sorted positions 0 .. n-1, with s_j = (double)prob_j.
+ *   2. For i < j, with A = box i and B = box j, the overlap uses the vote's and Soft-NMS's statements, always in union form:
+ *          iw = fmin(A.x + A.w, B.x + B.w) - fmax(A.x, B.x);   ih likewise;
+ *          o = iw * ih;   u = A.w * A.h + B.w * B.h - o;   r_ij = o / u;
+ *      r_ij = 0.0 where iw <= 0, ih <= 0 or the ratio is a NaN.
+ *   3. Compensation is the column maximum: c_i = max over k < i of r_ki, and c_0 = 0.0.
+ *   4. Decay of j >= 1, MSCNN_MATRIX_NMS_LINEAR: d_j = min over i < j of (1.0 - r_ij) / (1.0 - c_i), starting from 1.0.  A term
+ *      whose 1.0 - c_i is not > 0 is skipped (such an i is an exact duplicate of a higher-ranked box, and that box already
+ *      contributes the same term; the skip also keeps 0/0 out).  A NaN term is skipped, which is fmin's rule.  score'_j = s_j * d_j.
+ *   5. Decay of j >= 1, MSCNN_MATRIX_NMS_GAUSSIAN: g_j = max over i < j of (r_ij * r_ij - c_i * c_i) / sigma, starting from 0.0; a
+ *      NaN term is skipped.  score'_j = s_j * exp(-g_j): ONE exp per candidate, not one per pair (min_i exp(a_i) = exp(min_i a_i)).
+ *      sigma divides, as in mscnn_soft_nms_params, so 0.5 means the same thing in both ops.
+ *   6. score'_0 = s_0.
+ *   7. The candidates with score' >= score_thr are kept (a NaN fails the test).  They come out in descending score' order, equal
+ *      scores ordered by the lower sorted position.  The first max_out are taken when max_out > 0.  count is their number.  Pack
+ *      row s * cand_cap + k holds box k of that order bit for bit, then score', then the tag.
+ * The order in 7 is a total order and the reductions in 3 to 5 are exact (min and max of non-NaN doubles), so no reduction shape,
+ * grid size, scheduling or timing decides a bit.  No atomics on global memory, nothing spins, no workgroup waits on another.  The
+ * linear method is IEEE operations only and is bit-exact against tests/matrix_witness.py; the gaussian one calls the device
+ * library's exp once per candidate.
+ * Lists of at most 4032 slots are sorted by the merge's one-pass sort, all segments side by side, 32 per launch; longer ones go list
+ * after list through the tiled path's key kernel, sort and gather (cand_cap up to 2^30, the sort's largest power of two).  Then, per
+ * 32 segments: compensation pass, decay pass (r_ij recomputed: no n x n matrix of doubles is stored), one score launch, a rank pass
+ * (the output position of j = the number of kept candidates before it in the order of 7) and the emit.
+ * workspace: mscnn_detections_merge_matrix_workspace_bytes(S, cand_cap) bytes, linear in cand_cap (0: refused arguments).
+ * Refused before any launch, naming the value: null pointers, S < 1, cand_cap < 1 (or S * cand_cap past 2^31 - 1, or cand_cap past
+ * 2^30), a method outside {1, 2}, gaussian with a sigma that is not finite or not > 0, a score_thr that is NaN, infinite or < 0,
+ * max_out < 0, cand / workspace / pack_dev not 16-byte aligned, a workspace that is too small (MSCNN_ERR_WORKSPACE).
+ * No pin on the reference: its scripts neither merge nor decay a score.  The check is tests/matrix_witness.py: a float64 numpy
+ * restatement of the seven steps (linear: bit for bit), a plain triple loop, and the linear method in exact rationals.  The accuracy
+ * of Matrix NMS against Soft-NMS was not evaluated: there are no labels here. */
+enum { MSCNN_MATRIX_NMS_LINEAR = 1, MSCNN_MATRIX_NMS_GAUSSIAN = 2 };
+typedef struct { int method; double sigma; double score_thr; int max_out; } mscnn_matrix_nms_params;
+MSCNN_API size_t mscnn_detections_merge_matrix_workspace_bytes(int num_segments, int cand_cap);   /* 0: refused arguments */
+MSCNN_API int mscnn_detections_merge_matrix_fwd(const mscnn_matrix_nms_params* mx, int num_segments, void* cand, int cand_cap,
+                                                void* pack_dev, void* workspace, size_t workspace_bytes, void* stream);
 
 /* The proposal half of the scripts' result (run_mscnn_detection.m:75-91, `final_proposals{k}`) for every image of a batched forward
  * in one pass.  props [R_all][6] = BoxOutput's proposals_score, rows [img x1 y1 x2 y2 score] grouped by image in ascending order;

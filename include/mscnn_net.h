@@ -417,6 +417,21 @@ MSCNN_NET_API int mscnn_net_get_box_voting(const mscnn_net* net, double* thr);
  * with device -1.  No pin on the reference: its scripts neither merge nor decay a score; the check is tests/soft_witness.py. */
 MSCNN_NET_API int mscnn_net_set_soft_nms(mscnn_net* net, int method, double sigma, double score_thr, int max_out);
 MSCNN_NET_API int mscnn_net_get_soft_nms(const mscnn_net* net, int* method, double* sigma, double* score_thr, int* max_out);
+/* Matrix NMS in place of the merge's hard NMS (mscnn_hip.h: mscnn_detections_merge_matrix_fwd; Wang et al., SOLOv2, 2020): while it
+ * is on, mscnn_net_detect_merge_end calls the matrix op where it calls mscnn_detections_merge_fwd -- every candidate's score is
+ * decayed by its worst overlap with a higher-ranked candidate, compensated by that candidate's own worst overlap (method 1, linear:
+ * min (1 - IoU) / (1 - comp); method 2, gaussian: exp(-max (IoU^2 - comp^2) / sigma)), with no serial pick loop -- and the candidates
+ * with score' >= score_thr come back in descending score' order, the first max_out of them when max_out > 0.  These are NOT
+ * Soft-NMS's scores: a decay is the worst single pair, compensated, not a product over picks.  The segment's nms_overlap and the
+ * sticky set_nms type / ovr_dnm are not read by the op (thr / det_thr were applied by the adds).  With box voting on, the vote runs
+ * behind it; the read-back is unchanged.  Sticky: method 0 is off (the default; _end then enqueues exactly what it always did).
+ * Matrix NMS and Soft-NMS exclude each other: turning one on while the other is on fails, naming both, and changes nothing.
+ * Refused, naming the value and changing nothing: a method outside {0, 1, 2}, gaussian with a sigma that is not finite or not > 0,
+ * a score_thr that is NaN, infinite or < 0, max_out < 0.  Both calls work on a net built with device -1.  No pin on the reference:
+ * its scripts neither merge nor decay a score; the check is tests/matrix_witness.py.  The accuracy of Matrix NMS against Soft-NMS
+ * was not evaluated (no labels here). */
+MSCNN_NET_API int mscnn_net_set_matrix_nms(mscnn_net* net, int method, double sigma, double score_thr, int max_out);
+MSCNN_NET_API int mscnn_net_get_matrix_nms(const mscnn_net* net, int* method, double* sigma, double* score_thr, int* max_out);
 /* The views of a frame as ONE batched forward (mscnn_hip.h: mscnn_detections_candidates_add_views): the merge was opened with
  * _begin(num_frames, ...), the input holds N images -- the views mscnn_net_set_image_views wrote --, p[N * K] and view[N] describe
  * them as in _add, and list_of[N] (host) names the frame of each: the rows of image b go to the lists of frame list_of[b].  One

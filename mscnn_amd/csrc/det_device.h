@@ -1,7 +1,7 @@
 // What the files of the final detection stage share (gfx950): the row transform, the overlap, the bit matrix, the scan / column-OR and
 // the emit as device functions, the candidate buffer's and the per-segment workspace's layout, and the host helpers the entry points
-// have in common.  detections.hip (single list, segmented, tiled), det_candidates.hip (the adds), det_merge.hip (merge, vote) and
-// det_soft.hip (Soft-NMS) compile from these lines: one definition each, so no two of them can disagree about a bit.
+// have in common.  detections.hip (single list, segmented, tiled), det_candidates.hip (the adds), det_merge.hip (merge, vote),
+// det_soft.hip (Soft-NMS) and det_matrix.hip (Matrix NMS) compile from these lines: one definition each, so no two of them can disagree about a bit.
 //
 // Final stage: the MATLAB post-processing of the net outputs, examples/kitti_car/run_mscnn_detection.m:75-120
 //   + utils/bbNms.m:112-126 (nmsMax, greedy, union).  MATLAB semantics restated: single-precision
@@ -331,5 +331,25 @@ struct DetTiled { u64* keys; int P; int* cnt; DetBox* tbox; float* tprob; };    
 DetTiled det_tiled_of(void* workspace, int kcap);
 int det_tiled_nms(void* workspace, int kcap, const DetBox* box, const float* prob, const int* tag, double overlap, double* dets,
                   int* ids, int* count_out, hipStream_t st);
+// the gather of the tiled path alone (detections.hip): sbox / sprob / ssrc[i] = box / prob / tag of det_key_row(keys[i]), i < cnt[DC_N]
+void det_tiled_gather(const u64* keys, const DetBox* box, const float* prob, const int* tag, DetBox* sbox, double* sprob, int* ssrc,
+                      const int* cnt, int kcap, hipStream_t st);
+
+// ---- the merge's sort, shared with the Matrix NMS (det_merge.hip launches; det_matrix.hip reads the slices) --------------------------
+// lists of at most kMaxK slots: every segment in one pass, kSegsPerLaunch segments per launch
+struct DetMergeArgs {
+  int cand_cap, wpr, num_segs, s0;
+  char* cand; char* ws; size_t seg_stride_box, seg_stride_mask;      // workspace: per-segment slices (det_slice_of)
+  DetPack pack;
+  double overlap[kSegsPerLaunch];
+};
+enum { MRG_N = 0, MRG_WANTED = 1, MRG_OVER = 2 };      // the segment's kSliceWords workspace words
+__device__ __forceinline__ DetSlice det_merge_slice(const DetMergeArgs& a, int s) {
+  return det_slice_of<false>(a.ws, a.num_segs, a.cand_cap, a.seg_stride_box, a.seg_stride_mask, s);
+}
+// det_merge_sort_kernel on segments [a.s0, a.s0 + ns): the slice's cnt words, sbox / sprob / ssrc in det_key order, the pack's header
+void det_merge_sort_launch(const DetMergeArgs& a, int ns, hipStream_t st);
+// det_merge_keys_big_kernel on one list of more than kMaxK slots: keys[0 .. P), cnt[DC_N], cnt[DC_BIG ..] = 0
+void det_merge_keys_big_launch(const int* lcnt, const float* prob, int cap, u64* keys, int P, int* cnt, hipStream_t st);
 
 }  // namespace mscnn_dev

@@ -7,17 +7,8 @@
 namespace {
 using namespace mscnn_dev;
 
-// -- merge, lists of at most kMaxK slots: every segment in one pass, three launches per kSegsPerLaunch segments
-struct DetMergeArgs {
-  int cand_cap, wpr, num_segs, s0;
-  char* cand; char* ws; size_t seg_stride_box, seg_stride_mask;      // workspace: per-segment slices (det_slice_of)
-  DetPack pack;
-  double overlap[kSegsPerLaunch];
-};
-enum { MRG_N = 0, MRG_WANTED = 1, MRG_OVER = 2 };      // the segment's kSliceWords workspace words
-__device__ __forceinline__ DetSlice det_merge_slice(const DetMergeArgs& a, int s) {
-  return det_slice_of<false>(a.ws, a.num_segs, a.cand_cap, a.seg_stride_box, a.seg_stride_mask, s);
-}
+// -- merge, lists of at most kMaxK slots: every segment in one pass, three launches per kSegsPerLaunch segments (DetMergeArgs:
+// det_device.h)
 
 // one workgroup per segment: keys of the list's candidates, sort, the sorted boxes.  A list that overflowed is not run (n = 0).
 __global__ __launch_bounds__(kSortThreads) void det_merge_sort_kernel(DetMergeArgs a) {
@@ -161,6 +152,13 @@ __global__ __launch_bounds__(kVoteThreads) void det_merge_vote_kernel(DetVoteArg
 }  // namespace
 
 using namespace mscnn;
+
+namespace mscnn_dev {
+void det_merge_sort_launch(const DetMergeArgs& a, int ns, hipStream_t st) { det_merge_sort_kernel<<<ns, kSortThreads, 0, st>>>(a); }
+void det_merge_keys_big_launch(const int* lcnt, const float* prob, int cap, u64* keys, int P, int* cnt, hipStream_t st) {
+  det_merge_keys_big_kernel<<<cdiv(P, 256), 256, 0, st>>>(lcnt, prob, cap, keys, P, cnt);
+}
+}  // namespace mscnn_dev
 
 extern "C" size_t mscnn_detections_merge_workspace_bytes(int num_segments, int cand_cap) {
   if (!cand_shape_ok(num_segments, cand_cap)) return 0;

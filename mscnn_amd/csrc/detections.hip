@@ -269,6 +269,11 @@ DetTiled det_tiled_of(void* workspace, int kcap) {
                   reinterpret_cast<float*>(ws + L.tprob)};
 }
 
+void det_tiled_gather(const u64* keys, const DetBox* box, const float* prob, const int* tag, DetBox* sbox, double* sprob, int* ssrc,
+                      const int* cnt, int kcap, hipStream_t st) {
+  det_gather_big_kernel<<<cdiv(kcap, 256), 256, 0, st>>>(keys, box, prob, tag, sbox, sprob, ssrc, cnt);
+}
+
 int det_tiled_nms(void* workspace, int kcap, const DetBox* box, const float* prob, const int* tag, double overlap, double* dets,
                   int* ids, int* count_out, hipStream_t st) {
   const DetLayout L = det_layout(kcap);

@@ -237,6 +237,9 @@ def lib():
         L.mscnn_detections_merge_soft_workspace_bytes.argtypes = [C.c_int, C.c_int]
         L.mscnn_detections_merge_soft_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                                       C.c_void_p]
+        L.mscnn_detections_merge_matrix_workspace_bytes.restype = C.c_size_t
+        L.mscnn_detections_merge_matrix_workspace_bytes.argtypes = [C.c_int, C.c_int]
+        L.mscnn_detections_merge_matrix_fwd.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.mscnn_proposals_multi_pack_bytes.restype = C.c_size_t
         L.mscnn_proposals_multi_pack_bytes.argtypes = [C.c_int, C.c_int]
         L.mscnn_proposals_multi_fwd.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
@@ -1025,6 +1028,23 @@ def soft_nms_method(method):
     return int(method)
 
 
+MATRIX_NMS_METHODS = {"linear": 1, "gaussian": 2}      # MSCNN_MATRIX_NMS_LINEAR / _GAUSSIAN
+
+
+class MatrixNmsParams(C.Structure):
+    """mscnn_matrix_nms_params: method 1 = linear, 2 = gaussian; sigma (gaussian only) > 0; score_thr >= 0; max_out 0 = no bound."""
+    _fields_ = [("method", C.c_int), ("sigma", C.c_double), ("score_thr", C.c_double), ("max_out", C.c_int)]
+
+
+def matrix_nms_method(method):
+    """A method's number from its name ("linear", "gaussian"); a number passes through for the library to judge."""
+    if isinstance(method, str):
+        if method not in MATRIX_NMS_METHODS:
+            raise MscnnError(f"matrix nms: method {method!r} is none of {sorted(MATRIX_NMS_METHODS)}")
+        return MATRIX_NMS_METHODS[method]
+    return int(method)
+
+
 def _view_array(views, num_images):
     """views: None (NULL, the identity) or one (off_x, off_y, flip_x) per image."""
     if views is None:
@@ -1174,6 +1194,25 @@ class Candidates:
         if vote_thr is not None:
             self.vote(pack, vote_thr)
         return self._read_pack(pack, nbytes, raw_pack, "detections_merge_soft")
+
+    def merge_matrix(self, method, sigma=0.5, score_thr=0.001, max_out=0, raw_pack=False, pack=None, ws=None, vote_thr=None):
+        """mscnn_detections_merge_matrix_fwd: Matrix NMS over each list in place of merge()'s hard NMS -- every score decayed by its
+        worst compensated overlap with a higher-ranked candidate, method "linear" (min (1 - IoU) / (1 - comp)) or "gaussian"
+        (exp(-max (IoU^2 - comp^2) / sigma)), no pick loop; the candidates with score' >= score_thr, the first max_out of them when
+        max_out > 0.  Returns what merge() returns, the rows in descending score' order.  No nms_overlap is read."""
+        S, cap = self.S, self.cap
+        nbytes = lib().mscnn_detections_multi_pack_bytes(S, S * cap)
+        if pack is None:
+            pack = torch.zeros(nbytes, dtype=torch.uint8, device=self.buf.device)
+        wb = lib().mscnn_detections_merge_matrix_workspace_bytes(S, cap)
+        if ws is None:
+            ws = torch.empty(max(wb, 1), dtype=torch.uint8, device=self.buf.device)
+        mx = MatrixNmsParams(matrix_nms_method(method), float(sigma), float(score_thr), int(max_out))
+        _check(lib().mscnn_detections_merge_matrix_fwd(C.byref(mx), S, _dev(self.buf), cap, _dev(pack), _dev(ws), C.c_size_t(ws.numel()),
+                                                       _stream()))
+        if vote_thr is not None:
+            self.vote(pack, vote_thr)
+        return self._read_pack(pack, nbytes, raw_pack, "detections_merge_matrix")
 
     def _read_pack(self, pack, nbytes, raw_pack, what):
         """The merge's multi pack on the host: [(dets, tags, candidates)] per segment, with raw_pack also its bytes."""

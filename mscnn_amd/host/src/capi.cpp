@@ -38,6 +38,8 @@ struct mscnn_net {
   double vote_thr = 0.0;
   // mscnn_net_set_soft_nms: method 0 = off (detect_merge_end runs mscnn_detections_merge_fwd, as it always did), else the soft op's knobs
   mscnn_soft_nms_params soft = {0, 0.5, 0.001, 0};
+  // mscnn_net_set_matrix_nms: method 0 = off, else detect_merge_end runs mscnn_detections_merge_matrix_fwd (never on together with soft)
+  mscnn_matrix_nms_params matrix = {0, 0.5, 0.001, 0};
   // mscnn_net_detect_merge_*: the candidate lists of the forwards added since _begin (mscnn_hip.h: mscnn_detections_candidates_*)
   struct Merge {
     bool open = false;
@@ -504,6 +506,8 @@ int mscnn_net_set_soft_nms(mscnn_net* n, int method, double sigma, double score_
     CHECK(method != MSCNN_SOFT_NMS_GAUSSIAN || (sigma > 0 && sigma < HUGE_VAL)) << "set_soft_nms: sigma " << sigma << " is not a finite value > 0";
     CHECK(score_thr >= 0 && score_thr < HUGE_VAL) << "set_soft_nms: score_thr " << score_thr << " is not a finite value >= 0";
     CHECK_GE(max_out, 0) << "set_soft_nms: max_out " << max_out;
+    CHECK(method == 0 || n->matrix.method == 0) << "set_soft_nms: method " << method << " while Matrix NMS is on (set_matrix_nms method "
+                                                << n->matrix.method << "): the two exclude each other, turn that one off first";
     n->soft = mscnn_soft_nms_params{method, sigma, score_thr, max_out};
   });
 }
@@ -512,6 +516,29 @@ int mscnn_net_get_soft_nms(const mscnn_net* n, int* method, double* sigma, doubl
   return guarded([&] {
     CHECK(n && method && sigma && score_thr && max_out);
     *method = n->soft.method; *sigma = n->soft.sigma; *score_thr = n->soft.score_thr; *max_out = n->soft.max_out;
+  });
+}
+
+int mscnn_net_set_matrix_nms(mscnn_net* n, int method, double sigma, double score_thr, int max_out) {
+  return guarded([&] {
+    CHECK(n != nullptr);
+    // (the op's own refusals, made here so that a refused value changes nothing and is named at the call that brought it)
+    CHECK(method == 0 || method == MSCNN_MATRIX_NMS_LINEAR || method == MSCNN_MATRIX_NMS_GAUSSIAN)
+        << "set_matrix_nms: method " << method << " is neither 0 (off), " << MSCNN_MATRIX_NMS_LINEAR << " (linear) nor "
+        << MSCNN_MATRIX_NMS_GAUSSIAN << " (gaussian)";
+    CHECK(method != MSCNN_MATRIX_NMS_GAUSSIAN || (sigma > 0 && sigma < HUGE_VAL)) << "set_matrix_nms: sigma " << sigma << " is not a finite value > 0";
+    CHECK(score_thr >= 0 && score_thr < HUGE_VAL) << "set_matrix_nms: score_thr " << score_thr << " is not a finite value >= 0";
+    CHECK_GE(max_out, 0) << "set_matrix_nms: max_out " << max_out;
+    CHECK(method == 0 || n->soft.method == 0) << "set_matrix_nms: method " << method << " while Soft-NMS is on (set_soft_nms method "
+                                              << n->soft.method << "): the two exclude each other, turn that one off first";
+    n->matrix = mscnn_matrix_nms_params{method, sigma, score_thr, max_out};
+  });
+}
+
+int mscnn_net_get_matrix_nms(const mscnn_net* n, int* method, double* sigma, double* score_thr, int* max_out) {
+  return guarded([&] {
+    CHECK(n && method && sigma && score_thr && max_out);
+    *method = n->matrix.method; *sigma = n->matrix.sigma; *score_thr = n->matrix.score_thr; *max_out = n->matrix.max_out;
   });
 }
 
@@ -1452,11 +1479,14 @@ int mscnn_net_detect_merge_end(mscnn_net* n, double* dets_host, int* pass_host, 
     ensure_det_host(n, total);
     *static_cast<volatile int*>(n->det_host) = -1;      // the header's first word: the kernels must have written it
     const bool soft = n->soft.method != 0;      // Soft-NMS (mscnn_net_set_soft_nms) in place of the hard merge: the same pack
-    const size_t wb = soft ? mscnn_detections_merge_soft_workspace_bytes(S, m.cand_cap) : mscnn_detections_merge_workspace_bytes(S, m.cand_cap);
+    const bool matrix = n->matrix.method != 0;      // Matrix NMS (mscnn_net_set_matrix_nms), likewise; never on together with soft
+    const size_t wb = matrix ? mscnn_detections_merge_matrix_workspace_bytes(S, m.cand_cap)
+                      : soft ? mscnn_detections_merge_soft_workspace_bytes(S, m.cand_cap) : mscnn_detections_merge_workspace_bytes(S, m.cand_cap);
     void* ws = n->det_ws.Reserve(wb);
     // (the merge kernels only ever WRITE the pack: they write it straight into host-coherent pinned memory, as the blocking detect
     // calls do; the vote reads back the table and each kept row's own box from there, in stream order, and nothing else)
-    if (soft) MSCNN_CHECK(mscnn_detections_merge_soft_fwd(m.overlap.data(), &n->soft, S, m.cand.get(), m.cand_cap, n->det_host_dev, ws, wb, st));
+    if (matrix) MSCNN_CHECK(mscnn_detections_merge_matrix_fwd(&n->matrix, S, m.cand.get(), m.cand_cap, n->det_host_dev, ws, wb, st));
+    else if (soft) MSCNN_CHECK(mscnn_detections_merge_soft_fwd(m.overlap.data(), &n->soft, S, m.cand.get(), m.cand_cap, n->det_host_dev, ws, wb, st));
     else MSCNN_CHECK(mscnn_detections_merge_fwd(m.overlap.data(), nms_arg(n, false), S, m.cand.get(), m.cand_cap, n->det_host_dev, ws, wb, st));
     if (n->vote_thr != 0.0) {      // box voting (mscnn_net_set_box_voting): the kept rows of that pack, refined in place from the lists
       const mscnn_vote_params vote = {n->vote_thr};

@@ -113,6 +113,7 @@ def lib():
             "mscnn_net_detect_cascade_merge_add_views": [vp, vp, vp, vp, ci, vp, vp, vp, C.c_float],
             "mscnn_net_set_box_voting": [vp, C.c_double], "mscnn_net_get_box_voting": [vp, vp],
             "mscnn_net_set_soft_nms": [vp, ci, C.c_double, C.c_double, ci], "mscnn_net_get_soft_nms": [vp, vp, vp, vp, vp],
+            "mscnn_net_set_matrix_nms": [vp, ci, C.c_double, C.c_double, ci], "mscnn_net_get_matrix_nms": [vp, vp, vp, vp, vp],
         }
         for name, args in sig.items():
             getattr(L, name).argtypes = args
@@ -544,6 +545,24 @@ class Net:
         """mscnn_net_get_soft_nms: None = off, else dict(method, sigma, score_thr, max_out)."""
         m, mo, sg, th = C.c_int(), C.c_int(), C.c_double(), C.c_double()
         _check(lib().mscnn_net_get_soft_nms(self._h, C.byref(m), C.byref(sg), C.byref(th), C.byref(mo)))
+        if m.value == 0:
+            return None
+        return dict(method={1: "linear", 2: "gaussian"}[m.value], sigma=sg.value, score_thr=th.value, max_out=mo.value)
+
+    def set_matrix_nms(self, method=None, sigma=0.5, score_thr=0.001, max_out=0):
+        """mscnn_net_set_matrix_nms: from now on detect_merge_end runs Matrix NMS (mscnn_detections_merge_matrix_fwd) in place of the
+        hard NMS: every candidate's score decayed by its worst compensated overlap with a higher-ranked one -- method "linear" or
+        "gaussian" (sigma) --, no pick loop; the candidates with score' >= score_thr come back, the first max_out when max_out > 0.
+        method None = off (the default).  Refused while Soft-NMS is on; a refused value fails naming it and the setting stays."""
+        m = self.SOFT_NMS_METHODS.get(method, method) if isinstance(method, (str, type(None))) else method
+        if isinstance(m, str):
+            raise NetError(f"set_matrix_nms: method {method!r} is none of 'linear', 'gaussian', None")
+        _check(lib().mscnn_net_set_matrix_nms(self._h, int(m), float(sigma), float(score_thr), int(max_out)))
+
+    def get_matrix_nms(self):
+        """mscnn_net_get_matrix_nms: None = off, else dict(method, sigma, score_thr, max_out)."""
+        m, mo, sg, th = C.c_int(), C.c_int(), C.c_double(), C.c_double()
+        _check(lib().mscnn_net_get_matrix_nms(self._h, C.byref(m), C.byref(sg), C.byref(th), C.byref(mo)))
         if m.value == 0:
             return None
         return dict(method={1: "linear", 2: "gaussian"}[m.value], sigma=sg.value, score_thr=th.value, max_out=mo.value)

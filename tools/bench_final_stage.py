@@ -35,6 +35,11 @@ unbounded and with --max-dets 300, and a copy of every candidate list to the hos
 has without the op.  Each form runs from an idle device to the detections on the host, the forms rotate which runs first; the table
 gives us per pick, and two synthetic one-list cases (4096 and 8000 candidates) price the kernel's register and streaming paths.
 
+--merge --matrix is Matrix NMS over those candidate lists (mscnn_detections_merge_matrix_fwd): the hard merge, Soft-NMS linear, the
+matrix op linear, gaussian and linear with --max-dets 300, on the two --merge --soft cases and two synthetic one-list cases (4096 and
+8000 candidates); the forms rotate which runs first, and every case says whether matrix linear is below Soft-NMS linear by more than
+the two spreads added, and its ratio to the hard merge.
+
 --lib path/to/libmscnn_hip.so runs whatever leg is selected with THAT build's kernels under the Net (it is loaded first, so the Net's
 calls bind to it; the per-range op calls of the batched cascade case's per-call form go through hipapi's own handle and stay this
 build's).  --parent-lib path/to/libmscnn_hip.so repeats the selected leg --rounds times in child processes, this build and
@@ -402,6 +407,29 @@ def synthetic_lists(hipapi, n, seed=31):
     return cand
 
 
+def case_lists(a, hipapi, name, synthetic):
+    """(B, S, cap, the filled candidate lists) of a MERGE_CASES case (its forwards run once, here) or of a synthetic one-list case."""
+    import torch
+    if name in synthetic:
+        return 1, 1, synthetic[name], synthetic_lists(hipapi, synthetic[name])
+    model, B, classes, org, forwards = MERGE_CASES[name]
+    n = mnet.Net(prototxt_text=zoo.prototxt(model, batch=B))
+    synth.load_into(n, a.regime)
+    S, cap = B * len(classes), 2000 * B * len(forwards)
+    cand = hipapi.Candidates(S, cap)
+    for H, W, flipped in forwards:
+        f = np.concatenate([synth.frame(H, W, seed=1701 + b, org_hw=org) for b in range(B)], 0)
+        n.reshape_input("data", (B, 3, H, W))
+        n.set_blob("data", np.ascontiguousarray(f[..., ::-1]) if flipped else f)
+        n.forward()
+        R = n.blob_shape("proposals_score")[0]
+        blobs = [torch.from_numpy(n.get_blob(b).reshape(R, -1)).cuda() for b in ("bbox_pred", "cls_pred", "proposals_score")]
+        segs = [dict(cls_id=c, ratios=(H / float(org[0]), W / float(org[1])), org_hw=org, nms_overlap=0.5) for _ in range(B) for c in classes]
+        cand.add(*blobs, B, segs, views=[(0.0, 0.0, 1)] * B if flipped else None)
+    del n
+    return B, S, cap, cand
+
+
 SOFT_SYNTHETIC = {"synthetic-1x4096-registers": 4096, "synthetic-1x8000-streamed": 8000}      # both paths of the kernel, one list each
 
 
@@ -420,25 +448,7 @@ def merge_soft_leg(a):
           f"- min), regime {a.regime}; picks = those of the longest list; us/pick = ms * 1000 / picks")
     print(f"# {'case':30s} {'B':>2s} {'cands':>6s} {'longest':>7s} | " + " | ".join(f"{nm:>28s} {'picks':>5s} {'spread':>6s} {'us/pick':>7s}" for nm in names))
     for name in a.case or (list(MERGE_CASES) + list(SOFT_SYNTHETIC)):
-        if name in SOFT_SYNTHETIC:
-            B, S, cap = 1, 1, SOFT_SYNTHETIC[name]
-            cand = synthetic_lists(hipapi, cap)
-        else:
-            model, B, classes, org, forwards = MERGE_CASES[name]
-            n = mnet.Net(prototxt_text=zoo.prototxt(model, batch=B))
-            synth.load_into(n, a.regime)
-            S, cap = B * len(classes), 2000 * B * len(forwards)
-            cand = hipapi.Candidates(S, cap)
-            for H, W, flipped in forwards:
-                f = np.concatenate([synth.frame(H, W, seed=1701 + b, org_hw=org) for b in range(B)], 0)
-                n.reshape_input("data", (B, 3, H, W))
-                n.set_blob("data", np.ascontiguousarray(f[..., ::-1]) if flipped else f)
-                n.forward()
-                R = n.blob_shape("proposals_score")[0]
-                blobs = [torch.from_numpy(n.get_blob(b).reshape(R, -1)).cuda() for b in ("bbox_pred", "cls_pred", "proposals_score")]
-                segs = [dict(cls_id=c, ratios=(H / float(org[0]), W / float(org[1])), org_hw=org, nms_overlap=0.5) for _ in range(B) for c in classes]
-                cand.add(*blobs, B, segs, views=[(0.0, 0.0, 1)] * B if flipped else None)
-            del n
+        B, S, cap, cand = case_lists(a, hipapi, name, SOFT_SYNTHETIC)
         pack = torch.zeros(hipapi.lib().mscnn_detections_multi_pack_bytes(S, S * cap), dtype=torch.uint8, device="cuda")
         ws = torch.empty(max(hipapi.lib().mscnn_detections_merge_workspace_bytes(S, cap), 1), dtype=torch.uint8, device="cuda")
         wss = torch.empty(hipapi.lib().mscnn_detections_merge_soft_workspace_bytes(S, cap), dtype=torch.uint8, device="cuda")
@@ -482,6 +492,59 @@ def merge_soft_leg(a):
         sp = [max(v) - min(v) for v in med]
         print(f"  {name:30s} {B:2d} {cands:6d} {longest:7d} | " +
               " | ".join(f"{m[f]:28.3f} {picks[f]:5d} {sp[f]:6.3f} {1e3 * m[f] / max(picks[f], 1):7.2f}" for f in range(F)), flush=True)
+
+
+MATRIX_SYNTHETIC = {"synthetic-1x4096": 4096, "synthetic-1x8000": 8000}      # one list each: the tiled sort's first sizes
+
+
+def merge_matrix_leg(a):
+    """--merge --matrix: behind the same adds, the hard merge, Soft-NMS linear and Matrix NMS (mscnn_detections_merge_matrix_fwd):
+    linear, gaussian, and linear with --max-dets 300.  All forms end with the detections on the host; they rotate within a step."""
+    import torch
+    from mscnn_amd import hipapi
+    thr, sigma, md = a.soft_thr, 0.5, 300
+    names = ["hard merge", "soft linear", "matrix linear", "matrix gaussian", f"matrix linear max {md}"]
+    print(f"# Matrix NMS over the merged candidates (score_thr {thr:g}, sigma {sigma:g}) per frame group, host wall ms from an idle device to "
+          f"the detections on the host (median over {a.steps} steps after {a.warmup} warm-up; {a.rounds} rounds: median of the medians, spread = "
+          f"max - min), regime {a.regime}; dets = those of the longest list")
+    print(f"# {'case':30s} {'B':>2s} {'cands':>6s} {'longest':>7s} | " + " | ".join(f"{nm:>22s} {'dets':>5s} {'spread':>6s}" for nm in names))
+    for name in a.case or (list(MERGE_CASES) + list(MATRIX_SYNTHETIC)):
+        B, S, cap, cand = case_lists(a, hipapi, name, MATRIX_SYNTHETIC)
+        L = hipapi.lib()
+        pack = torch.zeros(L.mscnn_detections_multi_pack_bytes(S, S * cap), dtype=torch.uint8, device="cuda")
+        ws = torch.empty(max(L.mscnn_detections_merge_workspace_bytes(S, cap), 1), dtype=torch.uint8, device="cuda")
+        wss = torch.empty(L.mscnn_detections_merge_soft_workspace_bytes(S, cap), dtype=torch.uint8, device="cuda")
+        wsm = torch.empty(L.mscnn_detections_merge_matrix_workspace_bytes(S, cap), dtype=torch.uint8, device="cuda")
+        matrix = lambda method, mo: (lambda: cand.merge_matrix(method, sigma=sigma, score_thr=thr, max_out=mo, pack=pack, ws=wsm))      # noqa: E731
+        forms = [lambda: cand.merge(pack=pack, ws=ws), lambda: cand.merge_soft("linear", sigma=sigma, score_thr=thr, pack=pack, ws=wss),
+                 matrix("linear", 0), matrix("gaussian", 0), matrix("linear", md)]
+        F = len(forms)
+        med = [[] for _ in range(F)]
+        for rnd in range(a.rounds):
+            t = [[] for _ in range(F)]
+            for step in range(a.warmup + a.steps):
+                res = [None] * F
+                for k in range(F):
+                    f = (k + step) % F
+                    torch.cuda.synchronize()      # (untimed: every form starts on an idle device)
+                    t0 = time.perf_counter()
+                    res[f] = forms[f]()
+                    dt = time.perf_counter() - t0
+                    if step >= a.warmup:
+                        t[f].append(dt)
+                for (d2, _, _), (d4, _, _) in zip(res[2], res[4]):      # max_out cuts the order, it does not change it
+                    assert np.array_equal(d4, d2[:md]), (name, step)
+            for f in range(F):
+                med[f].append(1e3 * float(np.median(t[f])))
+        cands = sum(c for _, _, c in res[0])
+        longest = max(c for _, _, c in res[0])
+        dets = [max(len(d) for d, _, _ in res[f]) for f in range(F)]
+        m = [float(np.median(v)) for v in med]
+        sp = [max(v) - min(v) for v in med]
+        print(f"  {name:30s} {B:2d} {cands:6d} {longest:7d} | " + " | ".join(f"{m[f]:22.3f} {dets[f]:5d} {sp[f]:6.3f}" for f in range(F)), flush=True)
+        gap, both = m[1] - m[2], sp[1] + sp[2]
+        print(f"# {name}: matrix linear is {'below' if gap > both else 'NOT below'} soft linear by more than the two spreads added "
+              f"({m[1]:.3f} - {m[2]:.3f} = {gap:.3f} ms against {both:.3f}); matrix linear / hard merge = {m[2] / m[0]:.2f}", flush=True)
 
 
 def use_lib(path):
@@ -538,7 +601,9 @@ ap.add_argument("--vote", nargs="?", type=float, const=0.5, default=None, metava
                 "+ the vote op, and the merge + every candidate list to the host + numpy voting")
 ap.add_argument("--soft", action="store_true", help="with --merge: the hard merge, the Soft-NMS op (linear and gaussian, unbounded and with "
                 "--max-dets 300) and every candidate list to the host + a vectorised numpy Soft-NMS; us per pick")
-ap.add_argument("--soft-thr", type=float, default=0.001, help="--merge --soft: the score threshold that ends the picking")
+ap.add_argument("--matrix", action="store_true", help="with --merge: the hard merge, Soft-NMS linear and the Matrix NMS op (linear, gaussian, "
+                "linear with --max-dets 300) on the --merge --soft cases and two synthetic lists")
+ap.add_argument("--soft-thr", type=float, default=0.001, help="--merge --soft / --matrix: the score threshold")
 ap.add_argument("--rounds", type=int, default=3, help="--merge / --parent-lib: repetitions of the whole measurement")
 ap.add_argument("--lib", default="", help="run with the kernels of this libmscnn_hip.so under the Net")
 ap.add_argument("--parent-lib", default="", help="A/B of the selected leg against this libmscnn_hip.so, alternating child processes")
@@ -564,6 +629,9 @@ if a.merge and a.vote is not None:
     sys.exit(0)
 if a.merge and a.soft:
     merge_soft_leg(a)
+    sys.exit(0)
+if a.merge and a.matrix:
+    merge_matrix_leg(a)
     sys.exit(0)
 if a.merge:
     merge_leg(a)

@@ -17,6 +17,7 @@ examples/kitti_result/writeDetForEval.m.
          [--tiles RxC[:overlap_px]] [--views-batch]          # the frame cut into tiles; all views of a frame as ONE batched forward
          [--vote [THR]]                                      # box voting behind the merged NMS (Net.set_box_voting, THR default 0.5)
          [--soft-nms linear|gaussian[:SIGMA]] [--soft-thr T] [--max-dets N]      # Soft-NMS in place of the merged NMS (Net.set_soft_nms)
+         [--matrix-nms linear|gaussian[:SIGMA]]              # Matrix NMS in its place instead (Net.set_matrix_nms); --soft-thr / --max-dets serve it
   python tools/run_mscnn_detection.py --model kitti_car/mscnn-7s-576 --synthetic 8      # no dataset / weights at hand: the generated
                                                                                         # deploy net, seeded weights, synthetic frames
 
@@ -62,6 +63,13 @@ where the IoU is above --nms-overlap; gaussian: by exp(-IoU^2 / SIGMA), SIGMA de
 their decayed scores; --soft-thr T (default 0.001) ends the picking, --max-dets N bounds it.  Alongside --scales / --flip / --tiles it
 runs over their forwards' candidates; alone the frame runs as a merge of ONE forward; with --vote the vote runs behind it.  No
 reference script decays a score: there is no pin on the reference for it.
+
+--matrix-nms linear|gaussian[:SIGMA] runs Matrix NMS (Wang et al., SOLOv2, 2020) in that place instead (Net.set_matrix_nms, once per
+run): every candidate's score is decayed by its worst overlap with a higher-ranked candidate, compensated by that candidate's own
+worst overlap -- no pick loop, so its cost does not grow with the detections that come out.  --soft-thr T and --max-dets N serve
+whichever of the two is on; the flag is refused together with --soft-nms; alone it runs the frame as a merge of ONE forward.  These
+are not Soft-NMS's scores (a decay is the worst single pair, compensated, not a product over picks), there is no pin on the
+reference for it, and its accuracy against Soft-NMS was not evaluated (no labels here).
 
 Everything here is host glue over calls the test-suite covers one by one (Net.set_image / set_images / set_image_views, forward,
 detect / detect_multi, detect_merge_*, proposals_multi, kitti.write_*)."""
@@ -155,13 +163,17 @@ def add_merge_flags(ap):
                     "(Net.set_soft_nms): a candidate that overlaps a picked box keeps living with a decayed score -- linear: by 1 - IoU above "
                     "--nms-overlap; gaussian: by exp(-IoU^2 / SIGMA), SIGMA default 0.5; without --scales / --flip / --tiles the frame runs "
                     "as a merge of one forward")
-    ap.add_argument("--soft-thr", type=float, default=0.001, metavar="T", help="with --soft-nms: stop picking when the best live score is below T "
-                    "(default 0.001)")
-    ap.add_argument("--max-dets", type=int, default=0, metavar="N", help="with --soft-nms: at most N detections per class and frame (default 0: no "
-                    "bound)")
+    ap.add_argument("--matrix-nms", default=None, metavar="linear|gaussian[:SIGMA]", help="Matrix NMS in place of the merged hard NMS "
+                    "(Net.set_matrix_nms): every score decayed by its worst compensated overlap with a higher-ranked candidate, no pick "
+                    "loop -- linear: min (1 - IoU) / (1 - comp); gaussian: exp(-max (IoU^2 - comp^2) / SIGMA), SIGMA default 0.5; not with "
+                    "--soft-nms; without --scales / --flip / --tiles the frame runs as a merge of one forward")
+    ap.add_argument("--soft-thr", type=float, default=0.001, metavar="T", help="with --soft-nms: stop picking when the best live score is below T; "
+                    "with --matrix-nms: keep the scores >= T (default 0.001)")
+    ap.add_argument("--max-dets", type=int, default=0, metavar="N", help="with --soft-nms / --matrix-nms: at most N detections per class and "
+                    "frame (default 0: no bound)")
 
 
-def parse_soft_nms(text):
+def parse_soft_nms(text, flag="--soft-nms"):
     """'linear' | 'gaussian' | 'gaussian:SIGMA' -> (method, sigma)."""
     import re
     m = re.fullmatch(r"(linear|gaussian)(?::([^:]+))?", text.strip())
@@ -170,13 +182,13 @@ def parse_soft_nms(text):
     except ValueError:
         m = None
     if not m or (m.group(1) == "linear" and m.group(2)) or not 0.0 < sigma < float("inf"):
-        raise ValueError(f"--soft-nms {text!r} is not linear, gaussian or gaussian:SIGMA with a finite SIGMA > 0")
+        raise ValueError(f"{flag} {text!r} is not linear, gaussian or gaussian:SIGMA with a finite SIGMA > 0")
     return m.group(1), sigma
 
 
 def one_forward_merge(a):
-    """--vote and --soft-nms live in detect_merge_end: on their own they run the frame as a merge of one forward."""
-    return a.vote is not None or a.soft_nms is not None
+    """--vote, --soft-nms and --matrix-nms live in detect_merge_end: on their own they run the frame as a merge of one forward."""
+    return a.vote is not None or a.soft_nms is not None or a.matrix_nms is not None
 
 
 def apply_merge_settings(net, a):
@@ -185,6 +197,8 @@ def apply_merge_settings(net, a):
         net.set_box_voting(a.vote)
     if a.soft_nms is not None:
         net.set_soft_nms(a.soft_nms[0], sigma=a.soft_nms[1], score_thr=a.soft_thr, max_out=a.max_dets)
+    if a.matrix_nms is not None:
+        net.set_matrix_nms(a.matrix_nms[0], sigma=a.matrix_nms[1], score_thr=a.soft_thr, max_out=a.max_dets)
 
 
 def check_merge_flags(ap, a):
@@ -207,14 +221,21 @@ def check_merge_flags(ap, a):
             a.soft_nms = parse_soft_nms(a.soft_nms)
         except ValueError as e:
             ap.error(str(e))
+    if a.matrix_nms is not None:
+        if a.soft_nms is not None:
+            ap.error("--matrix-nms and --soft-nms exclude each other: one of them replaces the merged NMS")
+        try:
+            a.matrix_nms = parse_soft_nms(a.matrix_nms, "--matrix-nms")
+        except ValueError as e:
+            ap.error(str(e))
     if not 0.0 <= a.soft_thr < float("inf"):
         ap.error(f"--soft-thr {a.soft_thr:g}: the threshold must be a finite value >= 0")
     if a.max_dets < 0:
         ap.error(f"--max-dets {a.max_dets}: must be >= 0")
-    if a.soft_nms is None and (a.soft_thr != 0.001 or a.max_dets != 0):
-        ap.error("--soft-thr / --max-dets belong to --soft-nms")
+    if a.soft_nms is None and a.matrix_nms is None and (a.soft_thr != 0.001 or a.max_dets != 0):
+        ap.error("--soft-thr / --max-dets belong to --soft-nms or --matrix-nms")
     if (a.scales or a.flip or a.tiles or one_forward_merge(a)) and a.batch > 1:
-        ap.error("--scales / --flip / --tiles / --vote / --soft-nms run one frame per forward (drop --batch; --views-batch batches a frame's "
+        ap.error("--scales / --flip / --tiles / --vote / --soft-nms / --matrix-nms run one frame per forward (drop --batch; --views-batch batches a frame's "
                  "views)")
 
 
@@ -300,7 +321,7 @@ def parse_args(argv=None):
     a = ap.parse_args(argv)
     check_merge_flags(ap, a)
     if (a.scales or a.flip or a.tiles or one_forward_merge(a)) and (a.rois_in or a.proposals_out or a.proposals_only):
-        ap.error("--scales / --flip / --tiles / --vote / --soft-nms merge detections: not with --rois-in, --proposals-out or --proposals-only")
+        ap.error("--scales / --flip / --tiles / --vote / --soft-nms / --matrix-nms merge detections: not with --rois-in, --proposals-out or --proposals-only")
     if a.proposals_only and not a.proposals_out:
         ap.error("--proposals-only needs --proposals-out DIR")
     if a.proposals_only and a.rois_in:
