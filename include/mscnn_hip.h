@@ -53,6 +53,7 @@
  *   detections_merge_vote_fwd  cand, pack_dev 16: refuses
  *   detections_merge_soft_fwd  cand, workspace, pack_dev 16: refuses
  *   detections_merge_matrix_fwd  cand, workspace, pack_dev 16: refuses
+ *   detections_merge_wbf_fwd   cand, workspace, pack_dev 16, members_dev 4: refuses
  *   proposals_multi_fwd        props 8: refuses
  *   rois_ingest                rows 8: refuses; rois, props, image_rows, status 4
  */
@@ -824,6 +825,65 @@ typedef struct { int method; double sigma; double score_thr; int max_out; } mscn
 MSCNN_API size_t mscnn_detections_merge_matrix_workspace_bytes(int num_segments, int cand_cap);   /* 0: refused arguments */
 MSCNN_API int mscnn_detections_merge_matrix_fwd(const mscnn_matrix_nms_params* mx, int num_segments, void* cand, int cand_cap,
                                                 void* pack_dev, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Weighted boxes fusion over the merged candidates (WBF; Solovyev, Wang, Gabruseva, "Weighted boxes fusion: Ensembling boxes from
+ * different object detection models", 2019 / Image and Vision Computing 2021), beside mscnn_detections_merge_fwd, _soft_fwd and
+ * _matrix_fwd.  Those three SELECT or RE-SCORE single candidates; this op builds CLUSTERS while it walks the list in score order:
+ * a cluster's box is the score-weighted mean of all its members, that mean is what the next candidate is matched against, and a
+ * cluster's confidence is scaled by how many of the forwards agreed on it, min(members, T) / T.  Box voting is not a substitute: it
+ * refines boxes the hard NMS already picked, against the picked box, and never touches a score.  The op reads the candidate buffer
+ * exactly as the merge does and only reads it, and writes the same multi pack, mscnn_multi_pack_layout_of(S, S * cand_cap): header
+ * {S, cand_cap, S * cand_cap, 0}, table entry {count, wanted, s * cand_cap, 0} (count -1: the list overflowed, nothing else of it is
+ * written), rows [x y w h conf] + tag; rows past a count are left as they were; the kernels write every header and table word, so
+ * every reader of the merge's pack works on the result unchanged.  Per segment s, everything in double (-ffp-contract=off holds for
+ * the library: every operation rounded, no fma):
+ *   1. n = min(wanted, cand_cap), and n = 0 when wanted < 0.  The candidates are walked in the merge's own order, det_key(prob, slot):
+ *      larger prob first, then the lower slot; a NaN prob ranks below every number.  s_i = (double)prob_i.
+ *   2. Candidate i ENTERS while s_i >= skip_thr && s_i > 0; the walk ends at the first candidate that fails this test (the order
+ *      makes that the same as filtering).
+ *   3. Its box B is matched against the fused boxes F_c of the clusters that exist, c = 0 .. C-1 in creation order.  The overlap uses
+ *      the vote's, Soft-NMS's and Matrix NMS's statements with A = F_c, the union form always:
+ *          iw = fmin(A.x + A.w, B.x + B.w) - fmax(A.x, B.x)   (iw <= 0: no match);   ih likewise;
+ *          o = iw * ih;   u = A.w * A.h + B.w * B.h - o;   r = o / u                  (a NaN r: no match)
+ *      The candidate joins the cluster with the largest r among those with r > thr; among equal r the lowest c.  nms_overlap and
+ *      the sticky nms type / ovr_dnm are not read.
+ *   4. No such cluster: a new cluster C with members = 1, sw = s_i, sx = s_i * B.x (sy, sW, sH likewise), F_C = B BIT FOR BIT -- a
+ *      cluster of one gives back its candidate's box unchanged --, first = i: its tag and its s_i are the cluster's own.
+ *   5. Otherwise sw = sw + s_i; sx = sx + s_i * B.x -- the product rounded, then the sum -- and the same for y, w, h; members += 1;
+ *      F_c = [sx / sw, sy / sw, sW / sw, sH / sw].  The sums run in walk order: the summation order is part of the contract and is
+ *      fixed by the list alone.  The cascade rows keep their w = x2 - x1 + 1 convention (a mean of x y w h is the mean of the corners).
+ *   6. After the walk, per cluster: conf = sw / (double)members (MSCNN_WBF_CONF_AVG) or conf = s_first (MSCNN_WBF_CONF_MAX: the walk
+ *      is in descending score, so the first member is the largest); then conf = conf * (double)min(members, expected[s]) /
+ *      (double)expected[s].
+ *   7. The clusters come out in descending conf, equal conf ordered by the lower cluster index; with max_out > 0 only the first
+ *      max_out.  count is their number.  Pack row s * cand_cap + k holds the fused box, conf and the tag of the cluster's first member;
+ *      with a non-NULL members_dev, members_dev[s * cand_cap + k] holds its member count.  Entries past a count and entries of an
+ *      overflowed list are not written.
+ * The match in 3 and the order in 7 are maxima under total orders, so no reduction shape, grid size, scheduling or timing decides a
+ * bit; IEEE operations only: bit-exact against tests/wbf_witness.py.  No atomics on global memory, nothing spins, no workgroup
+ * waits on another.
+ * ANY cand_cap up to 2^30 (the sort's largest power of two) is served.  Lists of at most 4032 slots are sorted by the merge's
+ * one-pass sort, 32 segments per launch; longer ones go list after list through the tiled path's key kernel, sort and gather.  One
+ * workgroup of 1024 threads then owns a list and walks it, a step = one overlap per existing cluster spread over the lanes and one
+ * argmax over (r, lower c), reduced over the waves that own a cluster.  A list whose count is <= 4096 keeps the fused boxes of its
+ * clusters in registers; a longer one reads them from the workspace -- the same arithmetic, the same bits.  The five running sums of
+ * a cluster are touched by one lane per step and live in the workspace.
+ * expected[S]: a HOST array, each >= 1 (the number of forwards that looked at the list).  workspace:
+ * mscnn_detections_merge_wbf_workspace_bytes(S, cand_cap) bytes, linear in cand_cap (0: refused arguments).
+ * Refused before any launch, naming the value: a null wbf / expected / cand / pack_dev / workspace (members_dev may be NULL), S < 1,
+ * cand_cap < 1 (or S * cand_cap past 2^31 - 1, or cand_cap past 2^30), a thr that is NaN or outside (0, 1), a skip_thr that is NaN,
+ * infinite or < 0, a conf_type outside {1, 2}, max_out < 0, an expected[s] < 1, cand / workspace / pack_dev not 16-byte aligned,
+ * members_dev not 4-byte aligned, a workspace that is too small (MSCNN_ERR_WORKSPACE).
+ * No pin on the reference: its scripts run one forward per image and neither merge nor fuse.  The check is tests/wbf_witness.py: a
+ * float64 numpy restatement of the seven steps (bit for bit) and the same walk in exact rationals.  The accuracy of WBF against the
+ * hard merge, Soft-NMS and Matrix NMS was NOT evaluated: there are no labels here. */
+enum { MSCNN_WBF_CONF_AVG = 1, MSCNN_WBF_CONF_MAX = 2 };
+typedef struct { double thr; double skip_thr; int conf_type; int max_out; } mscnn_wbf_params;
+MSCNN_API size_t mscnn_detections_merge_wbf_workspace_bytes(int num_segments, int cand_cap);      /* 0: refused arguments */
+MSCNN_API int mscnn_detections_merge_wbf_fwd(const mscnn_wbf_params* wbf, const int* expected /* HOST, [S], each >= 1 */,
+                                             int num_segments, void* cand, int cand_cap, void* pack_dev,
+                                             int* members_dev /* may be NULL; [S * cand_cap] int32 */, void* workspace,
+                                             size_t workspace_bytes, void* stream);
 
 /* The proposal half of the scripts' result (run_mscnn_detection.m:75-91, `final_proposals{k}`) for every image of a batched forward
  * in one pass.  props [R_all][6] = BoxOutput's proposals_score, rows [img x1 y1 x2 y2 score] grouped by image in ascending order;

@@ -432,6 +432,28 @@ MSCNN_NET_API int mscnn_net_get_soft_nms(const mscnn_net* net, int* method, doub
  * was not evaluated (no labels here). */
 MSCNN_NET_API int mscnn_net_set_matrix_nms(mscnn_net* net, int method, double sigma, double score_thr, int max_out);
 MSCNN_NET_API int mscnn_net_get_matrix_nms(const mscnn_net* net, int* method, double* sigma, double* score_thr, int* max_out);
+/* Weighted boxes fusion in place of the merge's hard NMS (mscnn_hip.h: mscnn_detections_merge_wbf_fwd; Solovyev, Wang, Gabruseva,
+ * 2019 / 2021): while it is on, mscnn_net_detect_merge_end enqueues the WBF op where it enqueues mscnn_detections_merge_fwd -- the
+ * candidates are walked in score order into clusters, a cluster's box is the score-weighted mean of all its members (and is what the
+ * next candidate is matched against, union overlap > thr), its confidence the mean (conf_type 1, avg) or the largest (2, max) member
+ * score times min(members, expected) / expected -- and the clusters come back in descending confidence, the first max_out of them
+ * when max_out > 0; candidates with a score below skip_thr (or not > 0) do not enter.  The read-back is the one there is: pass / row
+ * are those of the cluster's FIRST member.  expected = 0 means the number of views that were added to the frame's lists since _begin,
+ * which the host counts per frame: + 1 per image for _add / _cascade_add, + 1 per b with list_of[b] == frame for the _views forms;
+ * any other value >= 1 is used for every list.  The segment's nms_overlap and the sticky set_nms type / ovr_dnm are not read by the op
+ * (thr / det_thr were applied by the adds).  Sticky: thr = 0 is off (the default; _end then enqueues exactly what it always did).
+ * WBF, Soft-NMS, Matrix NMS and box voting exclude one another where WBF is one of the two (a vote behind a fusion would average
+ * twice): turning one on while the other is on fails, naming both, and changes nothing.  Refused, naming the value and changing
+ * nothing: a thr that is neither 0 nor inside (0, 1), a skip_thr that is NaN, infinite or < 0, a conf_type outside {1, 2},
+ * expected < 0, max_out < 0.  Both calls work on a net built with device -1.
+ * mscnn_net_detect_merge_members: after an _end that ran WBF, the member count of every detection that _end returned, segment after
+ * segment in the order of dets_host (seg_dets[S] as _end filled it; cap = the ints members_host holds).  The counts came over with the
+ * pack in that _end's one synchronisation.  It is an error, naming the reason, when the last _end did not run WBF (or failed).
+ * No pin on the reference: its scripts neither merge nor fuse; the check is tests/wbf_witness.py.  The accuracy of WBF against the
+ * hard merge, Soft-NMS and Matrix NMS was not evaluated (no labels here). */
+MSCNN_NET_API int mscnn_net_set_wbf(mscnn_net* net, double thr, double skip_thr, int conf_type, int expected, int max_out);
+MSCNN_NET_API int mscnn_net_get_wbf(const mscnn_net* net, double* thr, double* skip_thr, int* conf_type, int* expected, int* max_out);
+MSCNN_NET_API int mscnn_net_detect_merge_members(mscnn_net* net, int* members_host, int cap, const int* seg_dets);
 /* The views of a frame as ONE batched forward (mscnn_hip.h: mscnn_detections_candidates_add_views): the merge was opened with
  * _begin(num_frames, ...), the input holds N images -- the views mscnn_net_set_image_views wrote --, p[N * K] and view[N] describe
  * them as in _add, and list_of[N] (host) names the frame of each: the rows of image b go to the lists of frame list_of[b].  One

@@ -240,6 +240,10 @@ def lib():
         L.mscnn_detections_merge_matrix_workspace_bytes.restype = C.c_size_t
         L.mscnn_detections_merge_matrix_workspace_bytes.argtypes = [C.c_int, C.c_int]
         L.mscnn_detections_merge_matrix_fwd.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.mscnn_detections_merge_wbf_workspace_bytes.restype = C.c_size_t
+        L.mscnn_detections_merge_wbf_workspace_bytes.argtypes = [C.c_int, C.c_int]
+        L.mscnn_detections_merge_wbf_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_size_t, C.c_void_p]
         L.mscnn_proposals_multi_pack_bytes.restype = C.c_size_t
         L.mscnn_proposals_multi_pack_bytes.argtypes = [C.c_int, C.c_int]
         L.mscnn_proposals_multi_fwd.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
@@ -1045,6 +1049,23 @@ def matrix_nms_method(method):
     return int(method)
 
 
+WBF_CONF_TYPES = {"avg": 1, "max": 2}      # MSCNN_WBF_CONF_AVG / _MAX
+
+
+class WbfParams(C.Structure):
+    """mscnn_wbf_params: thr inside (0, 1); skip_thr >= 0; conf_type 1 = avg, 2 = max; max_out 0 = no bound."""
+    _fields_ = [("thr", C.c_double), ("skip_thr", C.c_double), ("conf_type", C.c_int), ("max_out", C.c_int)]
+
+
+def wbf_conf_type(conf):
+    """A confidence type's number from its name ("avg", "max"); a number passes through for the library to judge."""
+    if isinstance(conf, str):
+        if conf not in WBF_CONF_TYPES:
+            raise MscnnError(f"wbf: conf {conf!r} is none of {sorted(WBF_CONF_TYPES)}")
+        return WBF_CONF_TYPES[conf]
+    return int(conf)
+
+
 def _view_array(views, num_images):
     """views: None (NULL, the identity) or one (off_x, off_y, flip_x) per image."""
     if views is None:
@@ -1213,6 +1234,31 @@ class Candidates:
         if vote_thr is not None:
             self.vote(pack, vote_thr)
         return self._read_pack(pack, nbytes, raw_pack, "detections_merge_matrix")
+
+    def merge_wbf(self, thr, skip_thr=0.0, conf="avg", expected=1, max_out=0, raw_pack=False, pack=None, ws=None, members=None):
+        """mscnn_detections_merge_wbf_fwd: weighted boxes fusion over each list in place of merge()'s hard NMS -- the candidates with a
+        score >= skip_thr walked in score order into clusters (union overlap with the cluster's fused box > thr), a cluster's box the
+        score-weighted mean of its members, its confidence their mean ("avg") or largest ("max") score times min(members, expected) /
+        expected; expected: one int for every list or one per list.  Returns (what merge() returns -- the rows in descending confidence,
+        the tag the first member's --, [members[D] int32 per segment, None for an overflowed list]).  members: an int32 device tensor of
+        S * cand_cap entries to use (zero-filled otherwise).  No nms_overlap is read."""
+        S, cap = self.S, self.cap
+        nbytes = lib().mscnn_detections_multi_pack_bytes(S, S * cap)
+        if pack is None:
+            pack = torch.zeros(nbytes, dtype=torch.uint8, device=self.buf.device)
+        wb = lib().mscnn_detections_merge_wbf_workspace_bytes(S, cap)
+        if ws is None:
+            ws = torch.empty(max(wb, 1), dtype=torch.uint8, device=self.buf.device)
+        if members is None:
+            members = torch.zeros(S * cap, dtype=torch.int32, device=self.buf.device)
+        ex = (C.c_int * S)(*([int(expected)] * S if isinstance(expected, int) else [int(v) for v in expected]))
+        wbf = WbfParams(float(thr), float(skip_thr), wbf_conf_type(conf), int(max_out))
+        _check(lib().mscnn_detections_merge_wbf_fwd(C.byref(wbf), ex, S, _dev(self.buf), cap, _dev(pack), _dev(members), _dev(ws),
+                                                    C.c_size_t(ws.numel()), _stream()))
+        out = self._read_pack(pack, nbytes, raw_pack, "detections_merge_wbf")
+        mh = members.cpu().numpy().reshape(S, cap)
+        segs = out[0] if raw_pack else out
+        return out, [None if d is None else mh[s, :len(d)].copy() for s, (d, _, _) in enumerate(segs)]
 
     def _read_pack(self, pack, nbytes, raw_pack, what):
         """The merge's multi pack on the host: [(dets, tags, candidates)] per segment, with raw_pack also its bytes."""

@@ -40,6 +40,12 @@ struct mscnn_net {
   mscnn_soft_nms_params soft = {0, 0.5, 0.001, 0};
   // mscnn_net_set_matrix_nms: method 0 = off, else detect_merge_end runs mscnn_detections_merge_matrix_fwd (never on together with soft)
   mscnn_matrix_nms_params matrix = {0, 0.5, 0.001, 0};
+  // mscnn_net_set_wbf: thr 0 = off, else detect_merge_end runs mscnn_detections_merge_wbf_fwd (never on together with soft, matrix or
+  // the vote); wbf_expected 0 = the views added to the frame's lists since _begin
+  mscnn_wbf_params wbf = {0.0, 0.0, MSCNN_WBF_CONF_AVG, 0};
+  int wbf_expected = 0;
+  bool members_valid = false;              // the last detect_merge_end ran WBF and succeeded: wbf_members are its detections' counts
+  std::vector<int> wbf_members, wbf_seg_dets;
   // mscnn_net_detect_merge_*: the candidate lists of the forwards added since _begin (mscnn_hip.h: mscnn_detections_candidates_*)
   struct Merge {
     bool open = false;
@@ -47,6 +53,7 @@ struct mscnn_net {
     long rows = 0;                         // sum of R_all over the adds so far: the host-known bound on any list
     std::vector<double> overlap;           // per segment, from the first add that reached the segment's list
     std::vector<char> overlap_known;       // (the views adds may leave a list without an image for a while)
+    std::vector<int> views;                // per frame: the views added to its lists since _begin (WBF's expected = 0)
     caffe::DeviceBuffer cand;
   } merge;
   ~mscnn_net() {
@@ -485,6 +492,8 @@ int mscnn_net_set_box_voting(mscnn_net* n, double thr) {
   return guarded([&] {
     CHECK(n != nullptr);
     CHECK(thr == 0.0 || (thr > 0.0 && thr < 1.0)) << "set_box_voting: thr " << thr << " is neither 0 (off) nor inside (0, 1)";
+    CHECK(thr == 0.0 || n->wbf.thr == 0.0) << "set_box_voting: thr " << thr << " while weighted boxes fusion is on (set_wbf thr " << n->wbf.thr
+                                           << "): the two exclude each other, turn that one off first";
     n->vote_thr = thr == 0.0 ? 0.0 : thr;      // (-0.0 is off too)
   });
 }
@@ -508,6 +517,8 @@ int mscnn_net_set_soft_nms(mscnn_net* n, int method, double sigma, double score_
     CHECK_GE(max_out, 0) << "set_soft_nms: max_out " << max_out;
     CHECK(method == 0 || n->matrix.method == 0) << "set_soft_nms: method " << method << " while Matrix NMS is on (set_matrix_nms method "
                                                 << n->matrix.method << "): the two exclude each other, turn that one off first";
+    CHECK(method == 0 || n->wbf.thr == 0.0) << "set_soft_nms: method " << method << " while weighted boxes fusion is on (set_wbf thr "
+                                            << n->wbf.thr << "): the two exclude each other, turn that one off first";
     n->soft = mscnn_soft_nms_params{method, sigma, score_thr, max_out};
   });
 }
@@ -531,6 +542,8 @@ int mscnn_net_set_matrix_nms(mscnn_net* n, int method, double sigma, double scor
     CHECK_GE(max_out, 0) << "set_matrix_nms: max_out " << max_out;
     CHECK(method == 0 || n->soft.method == 0) << "set_matrix_nms: method " << method << " while Soft-NMS is on (set_soft_nms method "
                                               << n->soft.method << "): the two exclude each other, turn that one off first";
+    CHECK(method == 0 || n->wbf.thr == 0.0) << "set_matrix_nms: method " << method << " while weighted boxes fusion is on (set_wbf thr "
+                                            << n->wbf.thr << "): the two exclude each other, turn that one off first";
     n->matrix = mscnn_matrix_nms_params{method, sigma, score_thr, max_out};
   });
 }
@@ -539,6 +552,35 @@ int mscnn_net_get_matrix_nms(const mscnn_net* n, int* method, double* sigma, dou
   return guarded([&] {
     CHECK(n && method && sigma && score_thr && max_out);
     *method = n->matrix.method; *sigma = n->matrix.sigma; *score_thr = n->matrix.score_thr; *max_out = n->matrix.max_out;
+  });
+}
+
+int mscnn_net_set_wbf(mscnn_net* n, double thr, double skip_thr, int conf_type, int expected, int max_out) {
+  return guarded([&] {
+    CHECK(n != nullptr);
+    // (the op's own refusals, made here so that a refused value changes nothing and is named at the call that brought it)
+    CHECK(thr == 0.0 || (thr > 0.0 && thr < 1.0)) << "set_wbf: thr " << thr << " is neither 0 (off) nor inside (0, 1)";
+    CHECK(skip_thr >= 0 && skip_thr < HUGE_VAL) << "set_wbf: skip_thr " << skip_thr << " is not a finite value >= 0";
+    CHECK(conf_type == MSCNN_WBF_CONF_AVG || conf_type == MSCNN_WBF_CONF_MAX)
+        << "set_wbf: conf_type " << conf_type << " is neither " << MSCNN_WBF_CONF_AVG << " (avg) nor " << MSCNN_WBF_CONF_MAX << " (max)";
+    CHECK_GE(expected, 0) << "set_wbf: expected " << expected << " is neither 0 (the views added) nor >= 1";
+    CHECK_GE(max_out, 0) << "set_wbf: max_out " << max_out;
+    const bool on = thr != 0.0;
+    CHECK(!on || n->soft.method == 0) << "set_wbf: thr " << thr << " while Soft-NMS is on (set_soft_nms method " << n->soft.method
+                                      << "): the two exclude each other, turn that one off first";
+    CHECK(!on || n->matrix.method == 0) << "set_wbf: thr " << thr << " while Matrix NMS is on (set_matrix_nms method " << n->matrix.method
+                                        << "): the two exclude each other, turn that one off first";
+    CHECK(!on || n->vote_thr == 0.0) << "set_wbf: thr " << thr << " while box voting is on (set_box_voting thr " << n->vote_thr
+                                     << "): the two exclude each other, turn that one off first";
+    n->wbf = mscnn_wbf_params{on ? thr : 0.0, skip_thr, conf_type, max_out};      // (-0.0 is off too)
+    n->wbf_expected = expected;
+  });
+}
+
+int mscnn_net_get_wbf(const mscnn_net* n, double* thr, double* skip_thr, int* conf_type, int* expected, int* max_out) {
+  return guarded([&] {
+    CHECK(n && thr && skip_thr && conf_type && expected && max_out);
+    *thr = n->wbf.thr; *skip_thr = n->wbf.skip_thr; *conf_type = n->wbf.conf_type; *expected = n->wbf_expected; *max_out = n->wbf.max_out;
   });
 }
 
@@ -1291,6 +1333,7 @@ int mscnn_net_detect_merge_begin(mscnn_net* n, int num_images, int num_classes, 
     m.handoff_errors = n->net->handoff_errors();
     m.overlap.assign(S, 0.5);      // (a list no add ever reaches stays empty: its overlap is never applied)
     m.overlap_known.assign(S, 0);
+    m.views.assign(num_images, 0);
   });
 }
 
@@ -1323,6 +1366,7 @@ static void merge_added(mscnn_net* n, const mscnn_detect_params* p, int S, int R
     const int l = (list_of ? list_of[s / m.slots] : s / m.slots) * m.slots + s % m.slots;
     if (!m.overlap_known[l]) { m.overlap[l] = p[s].nms_overlap; m.overlap_known[l] = 1; }
   }
+  for (int b = 0; b < S / m.slots; ++b) ++m.views[list_of ? list_of[b] : b];
   ++m.passes;
   m.rows += R_all;
 }
@@ -1476,16 +1520,25 @@ int mscnn_net_detect_merge_end(mscnn_net* n, double* dets_host, int* pass_host, 
     const int S = m.images * m.slots;
     hipStream_t st = (hipStream_t)Caffe::stream();
     const size_t total = mscnn_multi_pack_layout_of(S, S * m.cand_cap).total;
-    ensure_det_host(n, total);
+    const bool wbf = n->wbf.thr != 0.0;      // weighted boxes fusion (mscnn_net_set_wbf) in place of the hard merge: the same pack, and
+    n->members_valid = false;                // behind it in the same pinned block the member counts, which come over with it
+    const size_t members_at = (total + 15) / 16 * 16;
+    ensure_det_host(n, wbf ? members_at + (size_t)S * m.cand_cap * sizeof(int) : total);
     *static_cast<volatile int*>(n->det_host) = -1;      // the header's first word: the kernels must have written it
     const bool soft = n->soft.method != 0;      // Soft-NMS (mscnn_net_set_soft_nms) in place of the hard merge: the same pack
     const bool matrix = n->matrix.method != 0;      // Matrix NMS (mscnn_net_set_matrix_nms), likewise; never on together with soft
-    const size_t wb = matrix ? mscnn_detections_merge_matrix_workspace_bytes(S, m.cand_cap)
+    const size_t wb = wbf ? mscnn_detections_merge_wbf_workspace_bytes(S, m.cand_cap)
+                      : matrix ? mscnn_detections_merge_matrix_workspace_bytes(S, m.cand_cap)
                       : soft ? mscnn_detections_merge_soft_workspace_bytes(S, m.cand_cap) : mscnn_detections_merge_workspace_bytes(S, m.cand_cap);
     void* ws = n->det_ws.Reserve(wb);
     // (the merge kernels only ever WRITE the pack: they write it straight into host-coherent pinned memory, as the blocking detect
     // calls do; the vote reads back the table and each kept row's own box from there, in stream order, and nothing else)
-    if (matrix) MSCNN_CHECK(mscnn_detections_merge_matrix_fwd(&n->matrix, S, m.cand.get(), m.cand_cap, n->det_host_dev, ws, wb, st));
+    if (wbf) {
+      std::vector<int> expected(S);
+      for (int s = 0; s < S; ++s) expected[s] = n->wbf_expected ? n->wbf_expected : std::max(1, m.views[s / m.slots]);
+      MSCNN_CHECK(mscnn_detections_merge_wbf_fwd(&n->wbf, expected.data(), S, m.cand.get(), m.cand_cap, n->det_host_dev,
+                                                 reinterpret_cast<int*>(static_cast<char*>(n->det_host_dev) + members_at), ws, wb, st));
+    } else if (matrix) MSCNN_CHECK(mscnn_detections_merge_matrix_fwd(&n->matrix, S, m.cand.get(), m.cand_cap, n->det_host_dev, ws, wb, st));
     else if (soft) MSCNN_CHECK(mscnn_detections_merge_soft_fwd(m.overlap.data(), &n->soft, S, m.cand.get(), m.cand_cap, n->det_host_dev, ws, wb, st));
     else MSCNN_CHECK(mscnn_detections_merge_fwd(m.overlap.data(), nms_arg(n, false), S, m.cand.get(), m.cand_cap, n->det_host_dev, ws, wb, st));
     if (n->vote_thr != 0.0) {      // box voting (mscnn_net_set_box_voting): the kept rows of that pack, refined in place from the lists
@@ -1500,6 +1553,30 @@ int mscnn_net_detect_merge_end(mscnn_net* n, double* dets_host, int* pass_host, 
         << "a stream-K hand-off timed out in a forward of this merge (mscnn_net_handoff_state): whole-tile scheduling from now on; the "
            "forwards added since mscnn_net_detect_merge_begin must be run and added again";
     unpack_merge(n->det_host, S, m.cand_cap, dets_host, pass_host, row_host, cap, seg_dets, seg_candidates);
+    if (wbf) {      // the counts of the detections just returned, in their order (mscnn_net_detect_merge_members)
+      const int* mh = reinterpret_cast<const int*>(static_cast<const char*>(n->det_host) + members_at);
+      n->wbf_members.clear();
+      for (int s = 0; s < S; ++s) n->wbf_members.insert(n->wbf_members.end(), mh + (size_t)s * m.cand_cap, mh + (size_t)s * m.cand_cap + seg_dets[s]);
+      n->wbf_seg_dets.assign(seg_dets, seg_dets + S);
+      n->members_valid = true;
+    }
+  });
+}
+
+int mscnn_net_detect_merge_members(mscnn_net* n, int* members_host, int cap, const int* seg_dets) {
+  return guarded([&] {
+    CHECK(n != nullptr);
+    CHECK(n->members_valid) << "detect_merge_members: the last mscnn_net_detect_merge_end did not run weighted boxes fusion (mscnn_net_set_wbf "
+                               "was off, the call failed, or there was none)";
+    CHECK(seg_dets != nullptr) << "detect_merge_members: null seg_dets";
+    const size_t S = n->wbf_seg_dets.size();
+    for (size_t s = 0; s < S; ++s)
+      CHECK_EQ(seg_dets[s], n->wbf_seg_dets[s]) << "detect_merge_members: segment " << s << ": seg_dets " << seg_dets[s] << ", that _end returned "
+                                                << n->wbf_seg_dets[s];
+    const size_t D = n->wbf_members.size();
+    CHECK_LE(D, (size_t)(cap < 0 ? 0 : cap)) << "detect_merge_members: the buffer holds " << cap << " counts, that _end returned " << D << " detections";
+    CHECK(D == 0 || members_host) << "detect_merge_members: null members buffer";
+    if (D) std::memcpy(members_host, n->wbf_members.data(), D * sizeof(int));
   });
 }
 

@@ -114,6 +114,8 @@ def lib():
             "mscnn_net_set_box_voting": [vp, C.c_double], "mscnn_net_get_box_voting": [vp, vp],
             "mscnn_net_set_soft_nms": [vp, ci, C.c_double, C.c_double, ci], "mscnn_net_get_soft_nms": [vp, vp, vp, vp, vp],
             "mscnn_net_set_matrix_nms": [vp, ci, C.c_double, C.c_double, ci], "mscnn_net_get_matrix_nms": [vp, vp, vp, vp, vp],
+            "mscnn_net_set_wbf": [vp, C.c_double, C.c_double, ci, ci, ci], "mscnn_net_get_wbf": [vp, vp, vp, vp, vp, vp],
+            "mscnn_net_detect_merge_members": [vp, vp, ci, vp],
         }
         for name, args in sig.items():
             getattr(L, name).argtypes = args
@@ -567,6 +569,29 @@ class Net:
             return None
         return dict(method={1: "linear", 2: "gaussian"}[m.value], sigma=sg.value, score_thr=th.value, max_out=mo.value)
 
+    WBF_CONF_TYPES = {"avg": 1, "max": 2}
+
+    def set_wbf(self, thr=None, skip_thr=0.0, conf="avg", expected=0, max_out=0):
+        """mscnn_net_set_wbf: from now on detect_merge_end runs weighted boxes fusion (mscnn_detections_merge_wbf_fwd) in place of the
+        hard NMS: the candidates with a score >= skip_thr are walked in score order into clusters (union overlap with the cluster's
+        fused box > thr), a cluster's box is the score-weighted mean of its members, its confidence their mean (conf "avg") or largest
+        ("max") score times min(members, expected) / expected; the first max_out clusters come back when max_out > 0, and
+        detect_merge_members() gives their member counts.  expected 0 = the views added to the frame's lists since detect_merge_begin.
+        thr None or 0 = off (the default).  Refused while Soft-NMS, Matrix NMS or box voting is on; a refused value fails naming it and
+        the setting stays as it was."""
+        c = self.WBF_CONF_TYPES.get(conf, conf) if isinstance(conf, str) else conf
+        if isinstance(c, str):
+            raise NetError(f"set_wbf: conf {conf!r} is none of 'avg', 'max'")
+        _check(lib().mscnn_net_set_wbf(self._h, 0.0 if thr is None else float(thr), float(skip_thr), int(c), int(expected), int(max_out)))
+
+    def get_wbf(self):
+        """mscnn_net_get_wbf: None = off, else dict(thr, skip_thr, conf, expected, max_out)."""
+        th, sk, ct, ex, mo = C.c_double(), C.c_double(), C.c_int(), C.c_int(), C.c_int()
+        _check(lib().mscnn_net_get_wbf(self._h, C.byref(th), C.byref(sk), C.byref(ct), C.byref(ex), C.byref(mo)))
+        if th.value == 0.0:
+            return None
+        return dict(thr=th.value, skip_thr=sk.value, conf={1: "avg", 2: "max"}[ct.value], expected=ex.value, max_out=mo.value)
+
     @staticmethod
     def _params(cls_id, ratios, org_hw, bbox_mean, bbox_std, proposal_thr, nms_overlap):
         p = DetectParams()
@@ -749,6 +774,7 @@ class Net:
         vp = C.c_void_p
         _check(lib().mscnn_net_detect_merge_end(self._h, dets.ctypes.data_as(vp), pas.ctypes.data_as(vp), row.ctypes.data_as(vp), cap,
                                                 seg.ctypes.data_as(vp), cands.ctypes.data_as(vp)))
+        self._merge_seg = (B, K, seg.copy())
         out, o = [], 0
         for i in range(B):
             per = []
@@ -758,6 +784,16 @@ class Net:
                 o += d
             out.append(per)
         return out, cands.reshape(B, K).tolist()
+
+    def detect_merge_members(self):
+        """mscnn_net_detect_merge_members: after a detect_merge_end that ran weighted boxes fusion (set_wbf), the member count of every
+        detection it returned: [[members[D] int32 per slot] per image], in the order of its dets.  An error when it ran no WBF."""
+        B, K, seg = getattr(self, "_merge_seg", None) or (1, 1, np.zeros(1, np.int32))
+        D = int(seg.sum())
+        mem = np.zeros(max(D, 1), np.int32)
+        _check(lib().mscnn_net_detect_merge_members(self._h, mem.ctypes.data_as(C.c_void_p), D, seg.ctypes.data_as(C.c_void_p)))
+        ends = np.cumsum(seg)
+        return [[mem[ends[i * K + k] - seg[i * K + k]:ends[i * K + k]].copy() for k in range(K)] for i in range(B)]
 
     def detect_multi_device(self, params, classes, cap):
         """mscnn_net_detect_multi_device: the same into the device pack (detect_multi_pack_bytes(B, C, cap) bytes); asynchronous.

@@ -40,6 +40,12 @@ matrix op linear, gaussian and linear with --max-dets 300, on the two --merge --
 8000 candidates); the forms rotate which runs first, and every case says whether matrix linear is below Soft-NMS linear by more than
 the two spreads added, and its ratio to the hard merge.
 
+--merge --wbf is weighted boxes fusion over those candidate lists (mscnn_detections_merge_wbf_fwd), on the cases of --merge --matrix:
+the hard merge, Soft-NMS linear, Matrix NMS linear, WBF (conf avg, thr 0.55) at skip_thr 0.001, at skip_thr 0.05 and with --max-dets
+300, and a copy of every candidate list to the host + a numpy WBF there (the witness's walk, the overlap vectorised over the
+clusters) -- the only route there was.  The table gives the walked candidates and us per walked candidate, and every case says whether
+the op is below the host route by more than the two spreads; the rows are also written to --out (profiles/detect_merge_wbf.txt).
+
 --lib path/to/libmscnn_hip.so runs whatever leg is selected with THAT build's kernels under the Net (it is loaded first, so the Net's
 calls bind to it; the per-range op calls of the batched cascade case's per-call form go through hipapi's own handle and stay this
 build's).  --parent-lib path/to/libmscnn_hip.so repeats the selected leg --rounds times in child processes, this build and
@@ -547,6 +553,132 @@ def merge_matrix_leg(a):
               f"({m[1]:.3f} - {m[2]:.3f} = {gap:.3f} ms against {both:.3f}); matrix linear / hard merge = {m[2] / m[0]:.2f}", flush=True)
 
 
+def host_wbf(cand, thr, skip_thr, expected, max_out=0):
+    """Weighted boxes fusion of one list [n, 5] on the host: the walk of tests/wbf_witness.py with the overlap vectorised over the
+    clusters (conf avg).  Returns (dets [D, 5], members [D])."""
+    n = len(cand)
+    s = cand[:, 4]
+    order = np.lexsort((np.arange(n), -s))
+    F, sums, members = np.zeros((n, 4)), np.zeros((n, 5)), np.zeros(n, np.int64)
+    C = 0
+    for i in order:
+        si, B = s[i], cand[i, :4]
+        if not (si >= skip_thr and si > 0):
+            break
+        A = F[:C]
+        iw = np.minimum(A[:, 0] + A[:, 2], B[0] + B[2]) - np.maximum(A[:, 0], B[0])
+        ih = np.minimum(A[:, 1] + A[:, 3], B[1] + B[3]) - np.maximum(A[:, 1], B[1])
+        o = iw * ih
+        with np.errstate(divide="ignore", invalid="ignore"):
+            r = np.where((iw > 0) & (ih > 0), o / (A[:, 2] * A[:, 3] + B[2] * B[3] - o), 0.0)
+        c = int(np.argmax(r)) if C else -1
+        if c < 0 or not r[c] > thr:
+            sums[C] = [si, si * B[0], si * B[1], si * B[2], si * B[3]]
+            members[C] = 1
+            F[C] = B
+            C += 1
+        else:
+            sums[c, 0] = sums[c, 0] + si
+            sums[c, 1:] = sums[c, 1:] + si * B
+            members[c] += 1
+            F[c] = sums[c, 1:] / sums[c, 0]
+    conf = sums[:C, 0] / members[:C] * np.minimum(members[:C], expected) / expected
+    out = np.lexsort((np.arange(C), -conf))
+    out = out[:max_out] if max_out > 0 else out
+    return np.concatenate([F[out], conf[out, None]], 1), members[out]
+
+
+def merge_wbf_leg(a):
+    """--merge --wbf: behind the same adds, the hard merge, Soft-NMS linear, Matrix NMS linear and weighted boxes fusion
+    (mscnn_detections_merge_wbf_fwd, conf avg, thr 0.55, expected = the forwards of the case): at skip_thr 0.001, at skip_thr 0.05, with
+    --max-dets 300, and the lists copied to the host + a numpy WBF there (skip_thr 0.001) -- the only route there was.  All forms end
+    with the detections on the host; they rotate within a step.  walked = the candidates that entered the longest walk of a form (the
+    lists run side by side, one workgroup each); us/walked = ms * 1000 / walked includes the sort, the launches and the read-back."""
+    import torch
+    from mscnn_amd import hipapi
+    thr, sigma, md, wthr = a.soft_thr, 0.5, 300, 0.55
+    names = ["hard merge", "soft linear", "matrix linear", "wbf skip 0.001", "wbf skip 0.05", f"wbf max {md}", "lists to host + numpy wbf"]
+    lines = []
+
+    def say(line):
+        print(line, flush=True)
+        lines.append(line)
+
+    say(f"# Weighted boxes fusion over the merged candidates (thr {wthr:g}, conf avg; soft / matrix score_thr {thr:g}) per frame group, host wall ms "
+        f"from an idle device to the detections on the host (median over {a.steps} steps after {a.warmup} warm-up; {a.rounds} rounds: median of "
+        f"the medians, spread = max - min), regime {a.regime}; dets = those of the longest output; walked = the candidates that entered the "
+        f"longest walk; us/walked = ms * 1000 / walked")
+    say(f"# {'case':30s} {'B':>2s} {'cands':>6s} {'longest':>7s} | " + " | ".join(f"{nm:>24s} {'dets':>5s} {'spread':>6s}" for nm in names) +
+        " | walked(.001) us/walked walked(.05) us/walked")
+    for name in a.case or (list(MERGE_CASES) + list(MATRIX_SYNTHETIC)):
+        B, S, cap, cand = case_lists(a, hipapi, name, MATRIX_SYNTHETIC)
+        T = 2 if name in MATRIX_SYNTHETIC else len(MERGE_CASES[name][4])
+        L = hipapi.lib()
+        pack = torch.zeros(L.mscnn_detections_multi_pack_bytes(S, S * cap), dtype=torch.uint8, device="cuda")
+        members = torch.zeros(S * cap, dtype=torch.int32, device="cuda")
+        ws = torch.empty(max(L.mscnn_detections_merge_workspace_bytes(S, cap), 1), dtype=torch.uint8, device="cuda")
+        wss = torch.empty(L.mscnn_detections_merge_soft_workspace_bytes(S, cap), dtype=torch.uint8, device="cuda")
+        wsm = torch.empty(L.mscnn_detections_merge_matrix_workspace_bytes(S, cap), dtype=torch.uint8, device="cuda")
+        wsw = torch.empty(L.mscnn_detections_merge_wbf_workspace_bytes(S, cap), dtype=torch.uint8, device="cuda")
+        al = lambda v: (v + 255) // 256 * 256      # noqa: E731  (the candidate buffer's layout: include/mscnn_hip.h)
+        o0 = al(8 * S); o1 = o0 + al(32 * S * cap)
+
+        def on_host():
+            cnt = cand.counts()                           # (one small copy; then of every list the filled slots only: boxes, probs)
+            res, mem = [], []
+            for s in range(S):
+                m = min(cnt[s][0], cap)
+                box = cand.buf[o0 + 32 * s * cap:o0 + 32 * (s * cap + m)].cpu().numpy().view(np.float64).reshape(m, 4)
+                prob = cand.buf[o1 + 4 * s * cap:o1 + 4 * (s * cap + m)].cpu().numpy().view(np.float32)
+                d, mm = host_wbf(np.concatenate([box, prob[:, None].astype(np.float64)], 1), wthr, 0.001, T)
+                res.append((d, None, m)); mem.append(mm)
+            return res, mem
+
+        wbf = lambda skip, mo: (lambda: cand.merge_wbf(wthr, skip_thr=skip, conf="avg", expected=T, max_out=mo, pack=pack, ws=wsw, members=members))      # noqa: E731
+        forms = [lambda: (cand.merge(pack=pack, ws=ws), None), lambda: (cand.merge_soft("linear", sigma=sigma, score_thr=thr, pack=pack, ws=wss), None),
+                 lambda: (cand.merge_matrix("linear", sigma=sigma, score_thr=thr, pack=pack, ws=wsm), None), wbf(0.001, 0), wbf(0.05, 0), wbf(0.001, md),
+                 on_host]
+        F = len(forms)
+        med = [[] for _ in range(F)]
+        for rnd in range(a.rounds):
+            t = [[] for _ in range(F)]
+            for step in range(a.warmup + a.steps):
+                res = [None] * F
+                for k in range(F):
+                    f = (k + step) % F
+                    torch.cuda.synchronize()      # (untimed: every form starts on an idle device)
+                    t0 = time.perf_counter()
+                    res[f] = forms[f]()
+                    dt = time.perf_counter() - t0
+                    if step >= a.warmup:
+                        t[f].append(dt)
+                for (d3, _, _), (d5, _, _), (d6, _, _), m3, m6 in zip(res[3][0], res[5][0], res[6][0], res[3][1], res[6][1]):
+                    # the op against the host form (bit for bit: the same statements), and max_out a prefix
+                    assert np.array_equal(d3, d6) and np.array_equal(m3, m6) and np.array_equal(d5, d3[:md]), (name, step)
+            for f in range(F):
+                med[f].append(1e3 * float(np.median(t[f])))
+        cands = sum(c for _, _, c in res[0][0])
+        longest = max(c for _, _, c in res[0][0])
+        dets = [max(len(d) for d, _, _ in res[f][0]) for f in range(F)]
+        walked = [max(int(m.sum()) for m in res[f][1]) for f in (3, 4)]
+        m = [float(np.median(v)) for v in med]
+        sp = [max(v) - min(v) for v in med]
+        say(f"  {name:30s} {B:2d} {cands:6d} {longest:7d} | " + " | ".join(f"{m[f]:24.3f} {dets[f]:5d} {sp[f]:6.3f}" for f in range(F)) +
+            f" | {walked[0]:12d} {1e3 * m[3] / max(walked[0], 1):9.2f} {walked[1]:11d} {1e3 * m[4] / max(walked[1], 1):9.2f}")
+        say(f"# {name}: wbf skip 0.001 / lists to host + numpy wbf = {m[3] / m[6]:.3f} ({'the op is below' if m[3] + sp[3] < m[6] - sp[6] else 'the op is NOT below'} "
+            f"the host route by more than the two spreads); wbf skip 0.001 / hard merge = {m[3] / m[0]:.2f}; / soft linear = {m[3] / m[1]:.2f}; "
+            f"/ matrix linear = {m[3] / m[2]:.2f}")
+    say("# python tools/bench_final_stage.py --merge --wbf" + f" --steps {a.steps} --warmup {a.warmup} --rounds {a.rounds}: MI355X (gfx950), one GPU, seeded "
+        "weights, synthetic frames; the forwards and the add calls are not timed.  cand_cap = 2000 x B x forwards (the caltech lists are past the "
+        "one-pass sort's 4032 slots and run list after list); the synthetic lists are one list each, clusters of about five boxes.")
+    say("# every step asserts that the op's detections and member counts equal the host form's bit for bit, and that max_out is a prefix.")
+    say("# NOT measured: the kernels alone (device events or a profiler), conf max, cascade lists, the drivers end to end, accuracy (no labels).")
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+
 def use_lib(path):
     """The kernels of another build of libmscnn_hip.so under this build's Net: loaded first and globally, the Net library's calls bind
     to it (checked on one final-stage symbol)."""
@@ -603,7 +735,12 @@ ap.add_argument("--soft", action="store_true", help="with --merge: the hard merg
                 "--max-dets 300) and every candidate list to the host + a vectorised numpy Soft-NMS; us per pick")
 ap.add_argument("--matrix", action="store_true", help="with --merge: the hard merge, Soft-NMS linear and the Matrix NMS op (linear, gaussian, "
                 "linear with --max-dets 300) on the --merge --soft cases and two synthetic lists")
-ap.add_argument("--soft-thr", type=float, default=0.001, help="--merge --soft / --matrix: the score threshold")
+ap.add_argument("--wbf", action="store_true", help="with --merge: the hard merge, Soft-NMS linear, Matrix NMS linear and the weighted boxes "
+                "fusion op (skip_thr 0.001 and 0.05, and with --max-dets 300) against every candidate list to the host + a numpy WBF; us per "
+                "walked candidate; the rows also go to --out")
+ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "detect_merge_wbf.txt"),
+                help="--merge --wbf: the file the rows are written to")
+ap.add_argument("--soft-thr", type=float, default=0.001, help="--merge --soft / --matrix / --wbf: the score threshold of Soft-NMS and Matrix NMS")
 ap.add_argument("--rounds", type=int, default=3, help="--merge / --parent-lib: repetitions of the whole measurement")
 ap.add_argument("--lib", default="", help="run with the kernels of this libmscnn_hip.so under the Net")
 ap.add_argument("--parent-lib", default="", help="A/B of the selected leg against this libmscnn_hip.so, alternating child processes")
@@ -632,6 +769,9 @@ if a.merge and a.soft:
     sys.exit(0)
 if a.merge and a.matrix:
     merge_matrix_leg(a)
+    sys.exit(0)
+if a.merge and a.wbf:
+    merge_wbf_leg(a)
     sys.exit(0)
 if a.merge:
     merge_leg(a)

@@ -13,6 +13,7 @@ detections/<comp_id>_<class>_<output>_results.txt written as dlmwrite does (:148
          [--vote [THR]]                                           # box voting behind the merged NMS (Net.set_box_voting, THR default 0.5)
          [--soft-nms linear|gaussian[:SIGMA]] [--soft-thr T] [--max-dets N]      # Soft-NMS in place of the merged NMS (Net.set_soft_nms)
          [--matrix-nms linear|gaussian[:SIGMA]]              # Matrix NMS in its place instead (Net.set_matrix_nms); --soft-thr / --max-dets serve it
+         [--wbf [THR]] [--wbf-skip T] [--wbf-conf avg|max] [--wbf-expected N]      # weighted boxes fusion in its place instead (Net.set_wbf)
          [--nms-type maxg|max] [--ovr-dnm union|min] [--nms-thr T]      # pNms.type / pNms.ovrDnm / bbNms's thr (Net.set_nms)
          [--roialign-one-pass]      # the ROIAlign heads of the net as one launch each (Net.set_roialign_one_pass; same results)
   python tools/run_cascademscnn.py --model kitti_car/cascade-mscnn-7s-576-2x --synthetic 8 --batch 2      # no dataset / weights at
@@ -43,6 +44,10 @@ pin on the reference, whose scripts neither merge nor decay a score.
 --matrix-nms linear|gaussian[:SIGMA]: Matrix NMS in that place instead (Net.set_matrix_nms): every score decayed by its worst
 compensated overlap with a higher-ranked candidate, no pick loop; --soft-thr / --max-dets serve it, not together with --soft-nms.  As
 tools/run_mscnn_detection.py; alone a merge of ONE forward; not Soft-NMS's scores, no pin on the reference, accuracy not evaluated.
+--wbf [THR] (default 0.55) [--wbf-skip T] [--wbf-conf avg|max] [--wbf-expected N]: weighted boxes fusion in that place instead
+(Net.set_wbf): the candidates walked in score order into clusters, a cluster's box the score-weighted mean of its members, its
+confidence scaled by min(members, N) / N; --max-dets serves it too; not together with --soft-nms, --matrix-nms or --vote.  As
+tools/run_mscnn_detection.py; alone a merge of ONE forward; no pin on the reference, accuracy not evaluated.
 
 Everything here is host glue over calls the test-suite covers one by one (Net.set_images, forward, detect_cascade_multi,
 reshape_input, kitti.write_detections_dlm)."""
@@ -119,7 +124,7 @@ def parse_args(argv=None):
     a = ap.parse_args(argv)
     check_merge_flags(ap, a)
     if (a.scales or a.flip or a.tiles or one_forward_merge(a)) and (a.orig_size or a.dump_blobs):
-        ap.error("--scales / --flip / --tiles / --vote / --soft-nms / --matrix-nms name the input sizes themselves and keep no single forward's blobs: not with --orig-size / "
+        ap.error("--scales / --flip / --tiles / --vote / --soft-nms / --matrix-nms / --wbf name the input sizes themselves and keep no single forward's blobs: not with --orig-size / "
                  "--dump-blobs")
     if not (a.prototxt or a.model) or not (a.images or a.synthetic):
         ap.error("need --prototxt or --model, and --images or --synthetic N")

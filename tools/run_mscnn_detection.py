@@ -18,6 +18,7 @@ examples/kitti_result/writeDetForEval.m.
          [--vote [THR]]                                      # box voting behind the merged NMS (Net.set_box_voting, THR default 0.5)
          [--soft-nms linear|gaussian[:SIGMA]] [--soft-thr T] [--max-dets N]      # Soft-NMS in place of the merged NMS (Net.set_soft_nms)
          [--matrix-nms linear|gaussian[:SIGMA]]              # Matrix NMS in its place instead (Net.set_matrix_nms); --soft-thr / --max-dets serve it
+         [--wbf [THR]] [--wbf-skip T] [--wbf-conf avg|max] [--wbf-expected N]      # weighted boxes fusion in its place instead (Net.set_wbf)
   python tools/run_mscnn_detection.py --model kitti_car/mscnn-7s-576 --synthetic 8      # no dataset / weights at hand: the generated
                                                                                         # deploy net, seeded weights, synthetic frames
 
@@ -70,6 +71,15 @@ worst overlap -- no pick loop, so its cost does not grow with the detections tha
 whichever of the two is on; the flag is refused together with --soft-nms; alone it runs the frame as a merge of ONE forward.  These
 are not Soft-NMS's scores (a decay is the worst single pair, compensated, not a product over picks), there is no pin on the
 reference for it, and its accuracy against Soft-NMS was not evaluated (no labels here).
+
+--wbf [THR] (default 0.55) runs weighted boxes fusion (Solovyev, Wang, Gabruseva, 2019 / 2021) in that place instead (Net.set_wbf,
+once per run): the candidates are walked in score order into clusters -- a candidate joins the cluster whose fused box it overlaps
+most, above THR --, a cluster's box is the score-weighted mean of ALL its members and its confidence their mean score (--wbf-conf
+max: the largest) times min(members, N) / N, N = the forwards that looked at the frame (--wbf-expected N: another number; default 0
+counts the views added), so an object one view out of four found is marked down.  --wbf-skip T (default 0) keeps candidates with a
+score below T out, --max-dets N bounds the output.  Refused together with --soft-nms, --matrix-nms and --vote (a vote behind a fusion
+would average twice); alone it runs the frame as a merge of ONE forward.  The result files are unchanged (the member counts are not
+written).  There is no pin on the reference for it, and its accuracy against the other three was not evaluated (no labels here).
 
 Everything here is host glue over calls the test-suite covers one by one (Net.set_image / set_images / set_image_views, forward,
 detect / detect_multi, detect_merge_*, proposals_multi, kitti.write_*)."""
@@ -167,9 +177,18 @@ def add_merge_flags(ap):
                     "(Net.set_matrix_nms): every score decayed by its worst compensated overlap with a higher-ranked candidate, no pick "
                     "loop -- linear: min (1 - IoU) / (1 - comp); gaussian: exp(-max (IoU^2 - comp^2) / SIGMA), SIGMA default 0.5; not with "
                     "--soft-nms; without --scales / --flip / --tiles the frame runs as a merge of one forward")
+    ap.add_argument("--wbf", nargs="?", type=float, const=0.55, default=None, metavar="THR", help="weighted boxes fusion in place of the merged "
+                    "hard NMS (Net.set_wbf): candidates walked in score order into clusters (IoU with the cluster's fused box > THR, default "
+                    "0.55), a cluster's box the score-weighted mean of its members, its confidence scaled by min(members, N) / N; not with "
+                    "--soft-nms / --matrix-nms / --vote; without --scales / --flip / --tiles the frame runs as a merge of one forward")
+    ap.add_argument("--wbf-skip", type=float, default=0.0, metavar="T", help="with --wbf: candidates with a score below T do not enter (default 0)")
+    ap.add_argument("--wbf-conf", choices=["avg", "max"], default="avg", help="with --wbf: a cluster's confidence is its members' mean (avg, the "
+                    "default) or largest (max) score")
+    ap.add_argument("--wbf-expected", type=int, default=0, metavar="N", help="with --wbf: the N of min(members, N) / N (default 0: the views "
+                    "added to the frame)")
     ap.add_argument("--soft-thr", type=float, default=0.001, metavar="T", help="with --soft-nms: stop picking when the best live score is below T; "
                     "with --matrix-nms: keep the scores >= T (default 0.001)")
-    ap.add_argument("--max-dets", type=int, default=0, metavar="N", help="with --soft-nms / --matrix-nms: at most N detections per class and "
+    ap.add_argument("--max-dets", type=int, default=0, metavar="N", help="with --soft-nms / --matrix-nms / --wbf: at most N detections per class and "
                     "frame (default 0: no bound)")
 
 
@@ -187,8 +206,8 @@ def parse_soft_nms(text, flag="--soft-nms"):
 
 
 def one_forward_merge(a):
-    """--vote, --soft-nms and --matrix-nms live in detect_merge_end: on their own they run the frame as a merge of one forward."""
-    return a.vote is not None or a.soft_nms is not None or a.matrix_nms is not None
+    """--vote, --soft-nms, --matrix-nms and --wbf live in detect_merge_end: on their own they run the frame as a merge of one forward."""
+    return a.vote is not None or a.soft_nms is not None or a.matrix_nms is not None or a.wbf is not None
 
 
 def apply_merge_settings(net, a):
@@ -199,6 +218,8 @@ def apply_merge_settings(net, a):
         net.set_soft_nms(a.soft_nms[0], sigma=a.soft_nms[1], score_thr=a.soft_thr, max_out=a.max_dets)
     if a.matrix_nms is not None:
         net.set_matrix_nms(a.matrix_nms[0], sigma=a.matrix_nms[1], score_thr=a.soft_thr, max_out=a.max_dets)
+    if a.wbf is not None:
+        net.set_wbf(a.wbf, skip_thr=a.wbf_skip, conf=a.wbf_conf, expected=a.wbf_expected, max_out=a.max_dets)
 
 
 def check_merge_flags(ap, a):
@@ -228,14 +249,26 @@ def check_merge_flags(ap, a):
             a.matrix_nms = parse_soft_nms(a.matrix_nms, "--matrix-nms")
         except ValueError as e:
             ap.error(str(e))
+    if a.wbf is not None:
+        for flag, on in (("--soft-nms", a.soft_nms is not None), ("--matrix-nms", a.matrix_nms is not None), ("--vote", a.vote is not None)):
+            if on:
+                ap.error(f"--wbf and {flag} exclude each other: the fusion replaces the merged NMS and averages the boxes itself")
+        if not 0.0 < a.wbf < 1.0:
+            ap.error(f"--wbf {a.wbf:g}: the threshold must lie inside (0, 1)")
+        if not 0.0 <= a.wbf_skip < float("inf"):
+            ap.error(f"--wbf-skip {a.wbf_skip:g}: the threshold must be a finite value >= 0")
+        if a.wbf_expected < 0:
+            ap.error(f"--wbf-expected {a.wbf_expected}: must be >= 0")
+    elif a.wbf_skip != 0.0 or a.wbf_conf != "avg" or a.wbf_expected != 0:
+        ap.error("--wbf-skip / --wbf-conf / --wbf-expected belong to --wbf")
     if not 0.0 <= a.soft_thr < float("inf"):
         ap.error(f"--soft-thr {a.soft_thr:g}: the threshold must be a finite value >= 0")
     if a.max_dets < 0:
         ap.error(f"--max-dets {a.max_dets}: must be >= 0")
-    if a.soft_nms is None and a.matrix_nms is None and (a.soft_thr != 0.001 or a.max_dets != 0):
-        ap.error("--soft-thr / --max-dets belong to --soft-nms or --matrix-nms")
+    if a.soft_nms is None and a.matrix_nms is None and (a.soft_thr != 0.001 or (a.max_dets != 0 and a.wbf is None)):
+        ap.error("--soft-thr belongs to --soft-nms or --matrix-nms, --max-dets to one of them or to --wbf")
     if (a.scales or a.flip or a.tiles or one_forward_merge(a)) and a.batch > 1:
-        ap.error("--scales / --flip / --tiles / --vote / --soft-nms / --matrix-nms run one frame per forward (drop --batch; --views-batch batches a frame's "
+        ap.error("--scales / --flip / --tiles / --vote / --soft-nms / --matrix-nms / --wbf run one frame per forward (drop --batch; --views-batch batches a frame's "
                  "views)")
 
 
