@@ -54,6 +54,7 @@
  *   detections_merge_soft_fwd  cand, workspace, pack_dev 16: refuses
  *   detections_merge_matrix_fwd  cand, workspace, pack_dev 16: refuses
  *   detections_merge_wbf_fwd   cand, workspace, pack_dev 16, members_dev 4: refuses
+ *   detections_merge_seq_fwd   cand, workspace, pack_dev 16, seq_dev 4: refuses
  *   proposals_multi_fwd        props 8: refuses
  *   rois_ingest                rows 8: refuses; rois, props, image_rows, status 4
  */
@@ -883,6 +884,70 @@ MSCNN_API size_t mscnn_detections_merge_wbf_workspace_bytes(int num_segments, in
 MSCNN_API int mscnn_detections_merge_wbf_fwd(const mscnn_wbf_params* wbf, const int* expected /* HOST, [S], each >= 1 */,
                                              int num_segments, void* cand, int cand_cap, void* pack_dev,
                                              int* members_dev /* may be NULL; [S * cand_cap] int32 */, void* workspace,
+                                             size_t workspace_bytes, void* stream);
+
+/* Seq-NMS over the candidate lists of a clip's frames (Han, Khorrami, Paine et al., "Seq-NMS for Video Object Detection", 2016),
+ * beside mscnn_detections_merge_fwd, _soft_fwd, _matrix_fwd and _wbf_fwd.  Those combine the views of ONE frame; this op lets the
+ * frames of a clip inform one another: it links the boxes of neighbouring frames by overlap, repeatedly takes the chain of boxes
+ * with the largest score sum, gives every box of the chain the chain's score, and suppresses what the chain's boxes overlap in their
+ * own frames.  Every detection also gets a sequence id (a tubelet).  S = num_frames * num_slots segments; segment s = t * K + k is the
+ * list of frame t, slot k -- the layout the candidate adds produce (list = frame x K + slot; K = classes, or outputs x classes for the
+ * cascade).  Chain k is the segments k, K + k, ..., (T - 1) K + k; chains never interact.  The op reads the candidate buffer exactly
+ * as the merge does and only reads it, and writes the same multi pack, mscnn_multi_pack_layout_of(S, S * cand_cap): header
+ * {S, cand_cap, S * cand_cap, 0}, table entry {count, wanted, s * cand_cap, 0}, rows [x y w h score'] + tag; every header and table
+ * word is written, rows past a count are left as they were.  Per chain, everything in double (-ffp-contract=off holds for the
+ * library: every operation rounded, no fma, IEEE operations only):
+ *   1. Entry.  Per segment n = min(wanted, cand_cap), and n = 0 when wanted < 0.  An overflowed list gets table count -1, nothing
+ *      else of it is written, and it takes part as an EMPTY frame.  The list is put in the merge's own order, det_key(prob, slot):
+ *      larger prob first, then the lower slot; a NaN ranks below every number.  s_i = (double)prob_i.  The candidates that ENTER are
+ *      the leading ones with s_i >= score_thr (a NaN fails), at most top_k of them: boxes 0 .. m_t - 1 of frame t.
+ *   2. Links.  For t >= 1, box (t-1, i) and box (t, j) are linked iff the overlap with A = box (t-1, i), B = box (t, j) is > link_thr,
+ *      in the vote's, Soft-NMS's, Matrix NMS's and WBF's statements, the union form:
+ *          iw = fmin(A.x + A.w, B.x + B.w) - fmax(A.x, B.x)   (iw <= 0: no link);   ih likewise;
+ *          o = iw * ih;   u = A.w * A.h + B.w * B.h - o;   r = o / u                  (a NaN r: no link)
+ *   3. Start.  All entered boxes are live, q = 0.  Steps 4 - 10 repeat while the chain has a live box.
+ *   4. DP, frames ascending.  For a live (t, j) let P be the live boxes i of frame t - 1 linked to j.  t = 0 or P empty: V = s_tj,
+ *      len = 1, prev = -1.  Otherwise p = the member of P with the largest V(t-1, .), among equal V the lowest i; V(t, j) =
+ *      V(t-1, p) + s_tj -- one rounded add, so a path's sum runs in frame order from its first box --, len = len_p + 1, prev = p.
+ *      (Scores are >= score_thr >= 0: a path is always extended when it can be.)
+ *   5. The end of the best path: the live box with the largest V; among equal V the lower t, then the lower j.  The path is the end
+ *      box followed back through prev.
+ *   6. score' = V_end / (double)len_end (MSCNN_SEQ_NMS_AVG) or the largest s on the path (MSCNN_SEQ_NMS_MAX).
+ *   7. Every box of the path is OUT: its own box bit for bit, score', its own tag, sequence id q.  It is dead from then on.
+ *   8. Suppression.  For every path box (t, j*), every live j of frame t whose overlap with A = box j*, B = box j is
+ *      > nms_overlap[t * K + k] dies and is never output.  The union form always: the sticky nms type / ovr_dnm are not read, thr /
+ *      det_thr were applied by the adds.
+ *   9. q = q + 1.
+ *  10. Every iteration kills at least the end box: at most sum m_t iterations, a bound the kernel's loop carries.  Nothing spins, no
+ *      workgroup waits on another, no atomics on global memory.
+ *  11. The rows of a segment: its output boxes in descending score', equal scores ordered by the lower sorted position; with
+ *      max_out > 0 only the first max_out.  count is their number.  With a non-NULL seq_dev, seq_dev[s * cand_cap + row] holds the
+ *      sequence id.  Entries past a count and entries of an overflowed list are not written.  max_out cuts the OUTPUT only: it does
+ *      not shorten the loop, every sequence is still formed and suppresses.
+ * Steps 4, 5 and 11 take maxima under total orders and every sum has its order fixed by the path, so no reduction shape, grid size,
+ * scheduling or timing decides a bit: bit-exact against tests/seq_witness.py.
+ * Lists of at most 4032 slots are sorted by the merge's one-pass sort, 32 segments per launch; longer ones go list after list through
+ * the tiled path's key kernel, sort and gather.  One parallel launch builds the link bits of every (chain, frame pair): row j of frame
+ * t holds top_k bits over frame t - 1.  One workgroup of 1024 threads then owns a chain, a thread = a box of the frame at hand (hence
+ * top_k <= 1024); the live masks of all frames and the previous frame's V / len sit in LDS (59 KB), prev in the workspace; an
+ * iteration costs num_frames + 3 workgroup barriers and a serial walk back through prev.  The DP restarts at frame 0 in every
+ * iteration; the overlaps of step 8 are recomputed, not stored.  A last launch, a workgroup per segment, ranks and writes the rows.
+ * nms_overlap[S]: a HOST array.  workspace: mscnn_detections_merge_seq_workspace_bytes(num_frames, num_slots, cand_cap, top_k)
+ * bytes = the sort's need + S * top_k * (8 * ceil(top_k / 64) + 60) and a few rounded-up tables (0: refused arguments).
+ * Refused before any launch, naming the value: a null nms_overlap / sq / cand / pack_dev / workspace (seq_dev may be NULL),
+ * num_frames outside [1, 256], num_slots < 1, cand_cap < 1 (or S * cand_cap past 2^31 - 1, or cand_cap past 2^30), top_k outside
+ * [1, 1024], a link_thr that is NaN or outside (0, 1), a score_thr that is NaN, infinite or < 0, a rescore outside {1, 2},
+ * max_out < 0, a NaN nms_overlap[s], cand / workspace / pack_dev not 16-byte aligned, seq_dev not 4-byte aligned, a workspace that
+ * is too small (MSCNN_ERR_WORKSPACE).
+ * No pin on the reference: its scripts run one forward per image and look at no other frame.  The check is tests/seq_witness.py: a
+ * float64 numpy restatement of the eleven steps (bit for bit), the same loop in exact rationals and a brute force over every linked
+ * path of tiny chains.  The accuracy of Seq-NMS was NOT evaluated: there are no labels here. */
+enum { MSCNN_SEQ_NMS_AVG = 1, MSCNN_SEQ_NMS_MAX = 2 };
+typedef struct { double link_thr; double score_thr; int top_k; int rescore; int max_out; } mscnn_seq_nms_params;
+MSCNN_API size_t mscnn_detections_merge_seq_workspace_bytes(int num_frames, int num_slots, int cand_cap, int top_k); /* 0: refused */
+MSCNN_API int mscnn_detections_merge_seq_fwd(const double* nms_overlap /* HOST, [S] */, const mscnn_seq_nms_params* sq,
+                                             int num_frames, int num_slots, void* cand, int cand_cap, void* pack_dev,
+                                             int* seq_dev /* may be NULL; [S * cand_cap] int32 */, void* workspace,
                                              size_t workspace_bytes, void* stream);
 
 /* The proposal half of the scripts' result (run_mscnn_detection.m:75-91, `final_proposals{k}`) for every image of a batched forward

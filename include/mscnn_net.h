@@ -454,6 +454,30 @@ MSCNN_NET_API int mscnn_net_get_matrix_nms(const mscnn_net* net, int* method, do
 MSCNN_NET_API int mscnn_net_set_wbf(mscnn_net* net, double thr, double skip_thr, int conf_type, int expected, int max_out);
 MSCNN_NET_API int mscnn_net_get_wbf(const mscnn_net* net, double* thr, double* skip_thr, int* conf_type, int* expected, int* max_out);
 MSCNN_NET_API int mscnn_net_detect_merge_members(mscnn_net* net, int* members_host, int cap, const int* seg_dets);
+/* Seq-NMS over the frames of a clip in place of the merge's hard NMS (mscnn_hip.h: mscnn_detections_merge_seq_fwd; Han, Khorrami, Paine
+ * et al., 2016).  While it is on, the lists of the open merge ARE the consecutive frames of one clip, in list order --
+ * _begin(num_frames, K, cand_cap) is unchanged, num_frames <= 256 -- and mscnn_net_detect_merge_end enqueues the seq op where it
+ * enqueues mscnn_detections_merge_fwd: per slot, the boxes of neighbouring frames whose union overlap is > link_thr are linked, the
+ * chain of boxes with the largest score sum comes out with the chain's mean (rescore 1, avg) or largest (2, max) score on every box,
+ * and suppresses what its boxes overlap by more than the segment's nms_overlap in their own frames; again until no box is left.  Of each
+ * list the leading candidates with a score >= score_thr take part, at most top_k (<= 1024); the first max_out rows of a list come back
+ * when max_out > 0.  The read-back, pass_host / row_host, the overflow error and the single synchronisation are unchanged.  The
+ * frames' views still go to the frame's list (_add_views with list_of): the multi-view recipe and the clip recipe compose.  The
+ * sticky set_nms type / ovr_dnm are not read by the op (thr / det_thr were applied by the adds).  Sticky: link_thr = 0 is off (the
+ * default; _end then enqueues exactly what it always did).  Seq-NMS excludes Soft-NMS, Matrix NMS and WBF: turning one on while the
+ * other is on fails, naming both, and changes nothing; box voting runs behind it as behind Soft-NMS and Matrix NMS.  Refused, naming
+ * the value and changing nothing: a link_thr that is neither 0 nor inside (0, 1), a score_thr that is NaN, infinite or < 0, a top_k
+ * outside [1, 1024], a rescore outside {1, 2}, max_out < 0; and, while it is on, a _begin with num_frames > 256 (nothing is opened) or an
+ * _end of a merge begun with more (the setting was turned on behind _begin).  All three calls work on a net built with device -1.
+ * mscnn_net_detect_merge_sequences: after an _end that ran Seq-NMS, the sequence id of every detection that _end returned, segment
+ * after segment in the order of dets_host (seg_dets[S] as _end filled it; cap = the ints seq_host holds); an id is unique within a clip
+ * and slot.  The ids came over with the pack in that _end's one synchronisation.  It is an error, naming the reason, when the last
+ * _end did not run Seq-NMS or failed, at whatever point.
+ * No pin on the reference: its scripts run one forward per image and look at no other frame; the check is tests/seq_witness.py.  The
+ * accuracy of Seq-NMS was not evaluated (no labels here). */
+MSCNN_NET_API int mscnn_net_set_seq_nms(mscnn_net* net, double link_thr, double score_thr, int top_k, int rescore, int max_out);
+MSCNN_NET_API int mscnn_net_get_seq_nms(const mscnn_net* net, double* link_thr, double* score_thr, int* top_k, int* rescore, int* max_out);
+MSCNN_NET_API int mscnn_net_detect_merge_sequences(mscnn_net* net, int* seq_host, int cap, const int* seg_dets);
 /* The views of a frame as ONE batched forward (mscnn_hip.h: mscnn_detections_candidates_add_views): the merge was opened with
  * _begin(num_frames, ...), the input holds N images -- the views mscnn_net_set_image_views wrote --, p[N * K] and view[N] describe
  * them as in _add, and list_of[N] (host) names the frame of each: the rows of image b go to the lists of frame list_of[b].  One

@@ -1,7 +1,7 @@
 // What the files of the final detection stage share (gfx950): the row transform, the overlap, the bit matrix, the scan / column-OR and
 // the emit as device functions, the candidate buffer's and the per-segment workspace's layout, and the host helpers the entry points
 // have in common.  detections.hip (single list, segmented, tiled), det_candidates.hip (the adds), det_merge.hip (merge, vote),
-// det_soft.hip (Soft-NMS), det_matrix.hip (Matrix NMS) and det_wbf.hip (weighted boxes fusion) compile from these lines: one definition each, so no
+// det_soft.hip (Soft-NMS), det_matrix.hip (Matrix NMS), det_wbf.hip (weighted boxes fusion) and det_seq.hip (Seq-NMS) compile from these lines: one definition each, so no
 // two of them can disagree about a bit.
 //
 // Final stage: the MATLAB post-processing of the net outputs, examples/kitti_car/run_mscnn_detection.m:75-120
@@ -336,7 +336,7 @@ int det_tiled_nms(void* workspace, int kcap, const DetBox* box, const float* pro
 void det_tiled_gather(const u64* keys, const DetBox* box, const float* prob, const int* tag, DetBox* sbox, double* sprob, int* ssrc,
                       const int* cnt, int kcap, hipStream_t st);
 
-// ---- the merge's sort, shared with the Matrix NMS and the WBF (det_merge.hip launches; det_matrix.hip and det_wbf.hip read the slices) ----
+// ---- the merge's sort, shared with the Matrix NMS, the WBF and Seq-NMS (det_merge.hip launches; det_matrix.hip, det_wbf.hip and det_seq.hip read the slices) ----
 // lists of at most kMaxK slots: every segment in one pass, kSegsPerLaunch segments per launch
 struct DetMergeArgs {
   int cand_cap, wpr, num_segs, s0;

@@ -244,6 +244,10 @@ def lib():
         L.mscnn_detections_merge_wbf_workspace_bytes.argtypes = [C.c_int, C.c_int]
         L.mscnn_detections_merge_wbf_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                      C.c_size_t, C.c_void_p]
+        L.mscnn_detections_merge_seq_workspace_bytes.restype = C.c_size_t
+        L.mscnn_detections_merge_seq_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+        L.mscnn_detections_merge_seq_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.c_size_t, C.c_void_p]
         L.mscnn_proposals_multi_pack_bytes.restype = C.c_size_t
         L.mscnn_proposals_multi_pack_bytes.argtypes = [C.c_int, C.c_int]
         L.mscnn_proposals_multi_fwd.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
@@ -1066,6 +1070,23 @@ def wbf_conf_type(conf):
     return int(conf)
 
 
+SEQ_NMS_RESCORES = {"avg": 1, "max": 2}      # MSCNN_SEQ_NMS_AVG / _MAX
+
+
+class SeqNmsParams(C.Structure):
+    """mscnn_seq_nms_params: link_thr inside (0, 1); score_thr >= 0; top_k in [1, 1024]; rescore 1 = avg, 2 = max; max_out 0 = no bound."""
+    _fields_ = [("link_thr", C.c_double), ("score_thr", C.c_double), ("top_k", C.c_int), ("rescore", C.c_int), ("max_out", C.c_int)]
+
+
+def seq_nms_rescore(rescore):
+    """A rescoring's number from its name ("avg", "max"); a number passes through for the library to judge."""
+    if isinstance(rescore, str):
+        if rescore not in SEQ_NMS_RESCORES:
+            raise MscnnError(f"seq nms: rescore {rescore!r} is none of {sorted(SEQ_NMS_RESCORES)}")
+        return SEQ_NMS_RESCORES[rescore]
+    return int(rescore)
+
+
 def _view_array(views, num_images):
     """views: None (NULL, the identity) or one (off_x, off_y, flip_x) per image."""
     if views is None:
@@ -1259,6 +1280,41 @@ class Candidates:
         mh = members.cpu().numpy().reshape(S, cap)
         segs = out[0] if raw_pack else out
         return out, [None if d is None else mh[s, :len(d)].copy() for s, (d, _, _) in enumerate(segs)]
+
+    def merge_seq(self, link_thr, num_frames, score_thr=0.001, top_k=300, rescore="avg", max_out=0, nms_overlap=None, raw_pack=False,
+                  pack=None, ws=None, seq=None, vote_thr=None):
+        """mscnn_detections_merge_seq_fwd: Seq-NMS in place of merge()'s hard NMS -- the lists are the num_frames consecutive frames of
+        one clip (list = frame x K + slot): per slot, the boxes of neighbouring frames with a union overlap > link_thr are linked, the
+        chain with the largest score sum comes out with its mean ("avg") or largest ("max") score on every box and suppresses what its
+        boxes overlap (the list's nms_overlap) in their own frames, until no box is left.  Of each list the leading candidates with a
+        score >= score_thr take part, at most top_k.  Returns (what merge() returns -- the rows in descending score' --, [seq[D] int32
+        per segment, None for an overflowed list]): seq is the sequence (tubelet) id, unique within a slot.  seq: an int32 device
+        tensor of S * cand_cap entries to use (zero-filled otherwise), or False for the op's NULL (then the second result is None).
+        vote_thr: vote(pack, vote_thr) runs on the pack before it is read."""
+        S, cap = self.S, self.cap
+        if num_frames < 1 or S % num_frames:
+            raise MscnnError(f"candidates: {S} lists are not {num_frames} frames of equally many slots")
+        ov = self.overlap if nms_overlap is None else nms_overlap
+        ov = (C.c_double * S)(*[float(v) for v in (ov if ov is not None else [0.5] * S)])
+        nbytes = lib().mscnn_detections_multi_pack_bytes(S, S * cap)
+        if pack is None:
+            pack = torch.zeros(nbytes, dtype=torch.uint8, device=self.buf.device)
+        sq = SeqNmsParams(float(link_thr), float(score_thr), int(top_k), seq_nms_rescore(rescore), int(max_out))
+        wb = lib().mscnn_detections_merge_seq_workspace_bytes(num_frames, S // num_frames, cap, sq.top_k)
+        if ws is None:
+            ws = torch.empty(max(wb, 1), dtype=torch.uint8, device=self.buf.device)
+        if seq is None:
+            seq = torch.zeros(S * cap, dtype=torch.int32, device=self.buf.device)
+        _check(lib().mscnn_detections_merge_seq_fwd(ov, C.byref(sq), num_frames, S // num_frames, _dev(self.buf), cap, _dev(pack),
+                                                    None if seq is False else _dev(seq), _dev(ws), C.c_size_t(ws.numel()), _stream()))
+        if vote_thr is not None:
+            self.vote(pack, vote_thr)
+        out = self._read_pack(pack, nbytes, raw_pack, "detections_merge_seq")
+        if seq is False:
+            return out, None
+        sh = seq.cpu().numpy().reshape(S, cap)
+        segs = out[0] if raw_pack else out
+        return out, [None if d is None else sh[s, :len(d)].copy() for s, (d, _, _) in enumerate(segs)]
 
     def _read_pack(self, pack, nbytes, raw_pack, what):
         """The merge's multi pack on the host: [(dets, tags, candidates)] per segment, with raw_pack also its bytes."""

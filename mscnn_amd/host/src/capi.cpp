@@ -46,6 +46,11 @@ struct mscnn_net {
   int wbf_expected = 0;
   bool members_valid = false;              // the last detect_merge_end ran WBF and succeeded: wbf_members are its detections' counts
   std::vector<int> wbf_members, wbf_seg_dets;
+  // mscnn_net_set_seq_nms: link_thr 0 = off, else detect_merge_end runs mscnn_detections_merge_seq_fwd over the lists as the frames of
+  // one clip (never on together with soft, matrix or wbf; the vote runs behind it)
+  mscnn_seq_nms_params seq = {0.0, 0.001, 300, MSCNN_SEQ_NMS_AVG, 0};
+  bool sequences_valid = false;            // the last detect_merge_end ran Seq-NMS and succeeded: seq_ids are its detections' sequence ids
+  std::vector<int> seq_ids, seq_seg_dets;
   // mscnn_net_detect_merge_*: the candidate lists of the forwards added since _begin (mscnn_hip.h: mscnn_detections_candidates_*)
   struct Merge {
     bool open = false;
@@ -519,6 +524,8 @@ int mscnn_net_set_soft_nms(mscnn_net* n, int method, double sigma, double score_
                                                 << n->matrix.method << "): the two exclude each other, turn that one off first";
     CHECK(method == 0 || n->wbf.thr == 0.0) << "set_soft_nms: method " << method << " while weighted boxes fusion is on (set_wbf thr "
                                             << n->wbf.thr << "): the two exclude each other, turn that one off first";
+    CHECK(method == 0 || n->seq.link_thr == 0.0) << "set_soft_nms: method " << method << " while Seq-NMS is on (set_seq_nms link_thr "
+                                                 << n->seq.link_thr << "): the two exclude each other, turn that one off first";
     n->soft = mscnn_soft_nms_params{method, sigma, score_thr, max_out};
   });
 }
@@ -544,6 +551,8 @@ int mscnn_net_set_matrix_nms(mscnn_net* n, int method, double sigma, double scor
                                               << n->soft.method << "): the two exclude each other, turn that one off first";
     CHECK(method == 0 || n->wbf.thr == 0.0) << "set_matrix_nms: method " << method << " while weighted boxes fusion is on (set_wbf thr "
                                             << n->wbf.thr << "): the two exclude each other, turn that one off first";
+    CHECK(method == 0 || n->seq.link_thr == 0.0) << "set_matrix_nms: method " << method << " while Seq-NMS is on (set_seq_nms link_thr "
+                                                 << n->seq.link_thr << "): the two exclude each other, turn that one off first";
     n->matrix = mscnn_matrix_nms_params{method, sigma, score_thr, max_out};
   });
 }
@@ -572,6 +581,8 @@ int mscnn_net_set_wbf(mscnn_net* n, double thr, double skip_thr, int conf_type, 
                                         << "): the two exclude each other, turn that one off first";
     CHECK(!on || n->vote_thr == 0.0) << "set_wbf: thr " << thr << " while box voting is on (set_box_voting thr " << n->vote_thr
                                      << "): the two exclude each other, turn that one off first";
+    CHECK(!on || n->seq.link_thr == 0.0) << "set_wbf: thr " << thr << " while Seq-NMS is on (set_seq_nms link_thr " << n->seq.link_thr
+                                         << "): the two exclude each other, turn that one off first";
     n->wbf = mscnn_wbf_params{on ? thr : 0.0, skip_thr, conf_type, max_out};      // (-0.0 is off too)
     n->wbf_expected = expected;
   });
@@ -581,6 +592,34 @@ int mscnn_net_get_wbf(const mscnn_net* n, double* thr, double* skip_thr, int* co
   return guarded([&] {
     CHECK(n && thr && skip_thr && conf_type && expected && max_out);
     *thr = n->wbf.thr; *skip_thr = n->wbf.skip_thr; *conf_type = n->wbf.conf_type; *expected = n->wbf_expected; *max_out = n->wbf.max_out;
+  });
+}
+
+int mscnn_net_set_seq_nms(mscnn_net* n, double link_thr, double score_thr, int top_k, int rescore, int max_out) {
+  return guarded([&] {
+    CHECK(n != nullptr);
+    // (the op's own refusals, made here so that a refused value changes nothing and is named at the call that brought it)
+    CHECK(link_thr == 0.0 || (link_thr > 0.0 && link_thr < 1.0)) << "set_seq_nms: link_thr " << link_thr << " is neither 0 (off) nor inside (0, 1)";
+    CHECK(score_thr >= 0 && score_thr < HUGE_VAL) << "set_seq_nms: score_thr " << score_thr << " is not a finite value >= 0";
+    CHECK(top_k >= 1 && top_k <= 1024) << "set_seq_nms: top_k " << top_k << " is outside [1, 1024]";
+    CHECK(rescore == MSCNN_SEQ_NMS_AVG || rescore == MSCNN_SEQ_NMS_MAX)
+        << "set_seq_nms: rescore " << rescore << " is neither " << MSCNN_SEQ_NMS_AVG << " (avg) nor " << MSCNN_SEQ_NMS_MAX << " (max)";
+    CHECK_GE(max_out, 0) << "set_seq_nms: max_out " << max_out;
+    const bool on = link_thr != 0.0;
+    CHECK(!on || n->soft.method == 0) << "set_seq_nms: link_thr " << link_thr << " while Soft-NMS is on (set_soft_nms method " << n->soft.method
+                                      << "): the two exclude each other, turn that one off first";
+    CHECK(!on || n->matrix.method == 0) << "set_seq_nms: link_thr " << link_thr << " while Matrix NMS is on (set_matrix_nms method "
+                                        << n->matrix.method << "): the two exclude each other, turn that one off first";
+    CHECK(!on || n->wbf.thr == 0.0) << "set_seq_nms: link_thr " << link_thr << " while weighted boxes fusion is on (set_wbf thr " << n->wbf.thr
+                                    << "): the two exclude each other, turn that one off first";
+    n->seq = mscnn_seq_nms_params{on ? link_thr : 0.0, score_thr, top_k, rescore, max_out};      // (-0.0 is off too)
+  });
+}
+
+int mscnn_net_get_seq_nms(const mscnn_net* n, double* link_thr, double* score_thr, int* top_k, int* rescore, int* max_out) {
+  return guarded([&] {
+    CHECK(n && link_thr && score_thr && top_k && rescore && max_out);
+    *link_thr = n->seq.link_thr; *score_thr = n->seq.score_thr; *top_k = n->seq.top_k; *rescore = n->seq.rescore; *max_out = n->seq.max_out;
   });
 }
 
@@ -1324,6 +1363,9 @@ int mscnn_net_detect_merge_begin(mscnn_net* n, int num_images, int num_classes, 
                    << " forwards added is open (call mscnn_net_detect_merge_end first)";
     CHECK(num_images >= 1 && num_classes >= 1) << "detect_merge_begin: " << num_images << " images x " << num_classes << " classes";
     CHECK_GE(cand_cap, 1) << "detect_merge_begin: cand_cap " << cand_cap;
+    // (while Seq-NMS is on the lists are the frames of a clip: what the op would refuse at _end is refused here, and nothing is opened)
+    CHECK(n->seq.link_thr == 0.0 || num_images <= 256) << "detect_merge_begin: num_frames " << num_images << " is outside [1, 256] while Seq-NMS is on "
+                                                          "(set_seq_nms link_thr " << n->seq.link_thr << ")";
     const int S = num_images * num_classes;
     const size_t bytes = mscnn_detections_candidates_bytes(S, cand_cap);
     CHECK_GT(bytes, 0u) << "detect_merge_begin: " << S << " segments x " << cand_cap << " candidate slots";
@@ -1513,8 +1555,12 @@ static void unpack_merge(const void* pack_host, int S, int cand_cap, double* det
 int mscnn_net_detect_merge_end(mscnn_net* n, double* dets_host, int* pass_host, int* row_host, int cap, int* seg_dets, int* seg_candidates) {
   return guarded([&] {
     mscnn_net::Merge& m = n->merge;
+    n->sequences_valid = false;      // (whatever happens from here on: detect_merge_sequences answers for THIS _end only)
     CHECK(m.open) << "detect_merge_end: no merge is open (call mscnn_net_detect_merge_begin first)";
     m.open = false;      // (whatever happens from here on: the merge is closed)
+    // (the setting may have been turned on behind _begin: the op's own refusal of the shape, made here so that it names the value)
+    CHECK(n->seq.link_thr == 0.0 || m.images <= 256) << "detect_merge_end: num_frames " << m.images << " is outside [1, 256] while Seq-NMS is on (set_seq_nms link_thr "
+                                   << n->seq.link_thr << "): the merge was begun with " << m.images << " lists per slot";
     CHECK(seg_dets != nullptr) << "detect_merge_end: null seg_dets";
     CHECK_GE(m.passes, 1) << "detect_merge_end: no forward has been added since mscnn_net_detect_merge_begin";
     const int S = m.images * m.slots;
@@ -1522,18 +1568,24 @@ int mscnn_net_detect_merge_end(mscnn_net* n, double* dets_host, int* pass_host, 
     const size_t total = mscnn_multi_pack_layout_of(S, S * m.cand_cap).total;
     const bool wbf = n->wbf.thr != 0.0;      // weighted boxes fusion (mscnn_net_set_wbf) in place of the hard merge: the same pack, and
     n->members_valid = false;                // behind it in the same pinned block the member counts, which come over with it
+    const bool seq = n->seq.link_thr != 0.0;      // Seq-NMS (mscnn_net_set_seq_nms): the lists are the frames of one clip; the same pack,
+                                                  // and the sequence ids where WBF has its member counts (the two are never on together)
     const size_t members_at = (total + 15) / 16 * 16;
-    ensure_det_host(n, wbf ? members_at + (size_t)S * m.cand_cap * sizeof(int) : total);
+    ensure_det_host(n, (wbf || seq) ? members_at + (size_t)S * m.cand_cap * sizeof(int) : total);
     *static_cast<volatile int*>(n->det_host) = -1;      // the header's first word: the kernels must have written it
     const bool soft = n->soft.method != 0;      // Soft-NMS (mscnn_net_set_soft_nms) in place of the hard merge: the same pack
     const bool matrix = n->matrix.method != 0;      // Matrix NMS (mscnn_net_set_matrix_nms), likewise; never on together with soft
-    const size_t wb = wbf ? mscnn_detections_merge_wbf_workspace_bytes(S, m.cand_cap)
+    const size_t wb = seq ? mscnn_detections_merge_seq_workspace_bytes(m.images, m.slots, m.cand_cap, n->seq.top_k)
+                      : wbf ? mscnn_detections_merge_wbf_workspace_bytes(S, m.cand_cap)
                       : matrix ? mscnn_detections_merge_matrix_workspace_bytes(S, m.cand_cap)
                       : soft ? mscnn_detections_merge_soft_workspace_bytes(S, m.cand_cap) : mscnn_detections_merge_workspace_bytes(S, m.cand_cap);
     void* ws = n->det_ws.Reserve(wb);
     // (the merge kernels only ever WRITE the pack: they write it straight into host-coherent pinned memory, as the blocking detect
     // calls do; the vote reads back the table and each kept row's own box from there, in stream order, and nothing else)
-    if (wbf) {
+    if (seq) {
+      MSCNN_CHECK(mscnn_detections_merge_seq_fwd(m.overlap.data(), &n->seq, m.images, m.slots, m.cand.get(), m.cand_cap, n->det_host_dev,
+                                                 reinterpret_cast<int*>(static_cast<char*>(n->det_host_dev) + members_at), ws, wb, st));
+    } else if (wbf) {
       std::vector<int> expected(S);
       for (int s = 0; s < S; ++s) expected[s] = n->wbf_expected ? n->wbf_expected : std::max(1, m.views[s / m.slots]);
       MSCNN_CHECK(mscnn_detections_merge_wbf_fwd(&n->wbf, expected.data(), S, m.cand.get(), m.cand_cap, n->det_host_dev,
@@ -1560,6 +1612,30 @@ int mscnn_net_detect_merge_end(mscnn_net* n, double* dets_host, int* pass_host, 
       n->wbf_seg_dets.assign(seg_dets, seg_dets + S);
       n->members_valid = true;
     }
+    if (seq) {      // the sequence ids of the detections just returned, in their order (mscnn_net_detect_merge_sequences)
+      const int* qh = reinterpret_cast<const int*>(static_cast<const char*>(n->det_host) + members_at);
+      n->seq_ids.clear();
+      for (int s = 0; s < S; ++s) n->seq_ids.insert(n->seq_ids.end(), qh + (size_t)s * m.cand_cap, qh + (size_t)s * m.cand_cap + seg_dets[s]);
+      n->seq_seg_dets.assign(seg_dets, seg_dets + S);
+      n->sequences_valid = true;
+    }
+  });
+}
+
+int mscnn_net_detect_merge_sequences(mscnn_net* n, int* seq_host, int cap, const int* seg_dets) {
+  return guarded([&] {
+    CHECK(n != nullptr);
+    CHECK(n->sequences_valid) << "detect_merge_sequences: the last mscnn_net_detect_merge_end did not run Seq-NMS (mscnn_net_set_seq_nms was "
+                                 "off, the call failed, or there was none)";
+    CHECK(seg_dets != nullptr) << "detect_merge_sequences: null seg_dets";
+    const size_t S = n->seq_seg_dets.size();
+    for (size_t s = 0; s < S; ++s)
+      CHECK_EQ(seg_dets[s], n->seq_seg_dets[s]) << "detect_merge_sequences: segment " << s << ": seg_dets " << seg_dets[s]
+                                                << ", that _end returned " << n->seq_seg_dets[s];
+    const size_t D = n->seq_ids.size();
+    CHECK_LE(D, (size_t)(cap < 0 ? 0 : cap)) << "detect_merge_sequences: the buffer holds " << cap << " ids, that _end returned " << D << " detections";
+    CHECK(D == 0 || seq_host) << "detect_merge_sequences: null sequence buffer";
+    if (D) std::memcpy(seq_host, n->seq_ids.data(), D * sizeof(int));
   });
 }
 

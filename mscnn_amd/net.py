@@ -116,6 +116,8 @@ def lib():
             "mscnn_net_set_matrix_nms": [vp, ci, C.c_double, C.c_double, ci], "mscnn_net_get_matrix_nms": [vp, vp, vp, vp, vp],
             "mscnn_net_set_wbf": [vp, C.c_double, C.c_double, ci, ci, ci], "mscnn_net_get_wbf": [vp, vp, vp, vp, vp, vp],
             "mscnn_net_detect_merge_members": [vp, vp, ci, vp],
+            "mscnn_net_set_seq_nms": [vp, C.c_double, C.c_double, ci, ci, ci], "mscnn_net_get_seq_nms": [vp, vp, vp, vp, vp, vp],
+            "mscnn_net_detect_merge_sequences": [vp, vp, ci, vp],
         }
         for name, args in sig.items():
             getattr(L, name).argtypes = args
@@ -592,6 +594,29 @@ class Net:
             return None
         return dict(thr=th.value, skip_thr=sk.value, conf={1: "avg", 2: "max"}[ct.value], expected=ex.value, max_out=mo.value)
 
+    SEQ_NMS_RESCORES = {"avg": 1, "max": 2}
+
+    def set_seq_nms(self, link_thr=None, score_thr=0.001, top_k=300, rescore="avg", max_out=0):
+        """mscnn_net_set_seq_nms: from now on the lists of a merge are the consecutive frames of one clip and detect_merge_end runs
+        Seq-NMS (mscnn_detections_merge_seq_fwd) in place of the hard NMS: per slot the boxes of neighbouring frames with a union
+        overlap > link_thr are linked, the chain with the largest score sum comes out with its mean (rescore "avg") or largest ("max")
+        score on every box and suppresses what its boxes overlap in their own frames, until no box is left.  Of each list the leading
+        candidates with a score >= score_thr take part, at most top_k (<= 1024); the first max_out rows of a list come back when
+        max_out > 0, and detect_merge_sequences() gives the sequence ids.  link_thr None or 0 = off (the default).  Refused while
+        Soft-NMS, Matrix NMS or WBF is on; a refused value fails naming it and the setting stays as it was."""
+        r = self.SEQ_NMS_RESCORES.get(rescore, rescore) if isinstance(rescore, str) else rescore
+        if isinstance(r, str):
+            raise NetError(f"set_seq_nms: rescore {rescore!r} is none of 'avg', 'max'")
+        _check(lib().mscnn_net_set_seq_nms(self._h, 0.0 if link_thr is None else float(link_thr), float(score_thr), int(top_k), int(r), int(max_out)))
+
+    def get_seq_nms(self):
+        """mscnn_net_get_seq_nms: None = off, else dict(link_thr, score_thr, top_k, rescore, max_out)."""
+        lt, st, tk, rs, mo = C.c_double(), C.c_double(), C.c_int(), C.c_int(), C.c_int()
+        _check(lib().mscnn_net_get_seq_nms(self._h, C.byref(lt), C.byref(st), C.byref(tk), C.byref(rs), C.byref(mo)))
+        if lt.value == 0.0:
+            return None
+        return dict(link_thr=lt.value, score_thr=st.value, top_k=tk.value, rescore={1: "avg", 2: "max"}[rs.value], max_out=mo.value)
+
     @staticmethod
     def _params(cls_id, ratios, org_hw, bbox_mean, bbox_std, proposal_thr, nms_overlap):
         p = DetectParams()
@@ -794,6 +819,17 @@ class Net:
         _check(lib().mscnn_net_detect_merge_members(self._h, mem.ctypes.data_as(C.c_void_p), D, seg.ctypes.data_as(C.c_void_p)))
         ends = np.cumsum(seg)
         return [[mem[ends[i * K + k] - seg[i * K + k]:ends[i * K + k]].copy() for k in range(K)] for i in range(B)]
+
+    def detect_merge_sequences(self):
+        """mscnn_net_detect_merge_sequences: after a detect_merge_end that ran Seq-NMS (set_seq_nms), the sequence id of every detection
+        it returned: [[seq[D] int32 per slot] per frame], in the order of its dets; an id is unique within the clip and slot.  An error
+        when it ran no Seq-NMS."""
+        B, K, seg = getattr(self, "_merge_seg", None) or (1, 1, np.zeros(1, np.int32))
+        D = int(seg.sum())
+        ids = np.zeros(max(D, 1), np.int32)
+        _check(lib().mscnn_net_detect_merge_sequences(self._h, ids.ctypes.data_as(C.c_void_p), D, seg.ctypes.data_as(C.c_void_p)))
+        ends = np.cumsum(seg)
+        return [[ids[ends[i * K + k] - seg[i * K + k]:ends[i * K + k]].copy() for k in range(K)] for i in range(B)]
 
     def detect_multi_device(self, params, classes, cap):
         """mscnn_net_detect_multi_device: the same into the device pack (detect_multi_pack_bytes(B, C, cap) bytes); asynchronous.

@@ -46,6 +46,13 @@ the hard merge, Soft-NMS linear, Matrix NMS linear, WBF (conf avg, thr 0.55) at 
 clusters) -- the only route there was.  The table gives the walked candidates and us per walked candidate, and every case says whether
 the op is below the host route by more than the two spreads; the rows are also written to --out (profiles/detect_merge_wbf.txt).
 
+--merge --seq is Seq-NMS over the candidate lists of a clip's frames (mscnn_detections_merge_seq_fwd): a clip is ONE forward of 8
+images (kitti_car 7s-576, caltech 7s-480), frame t the seeded frame shifted 4 t pixels; the hard merge of every frame, Seq-NMS avg at
+top_k 300 and 1024, and a copy of every candidate list to the host + the vectorised numpy Seq-NMS of tests/seq_witness.py there -- the
+only route there was.  The table gives the boxes that entered, the iterations (sequences) and us per iteration, and every case says
+whether the op is below the host route by more than the two spreads; the rows are also written to --out
+(profiles/detect_merge_seq.txt).
+
 --lib path/to/libmscnn_hip.so runs whatever leg is selected with THAT build's kernels under the Net (it is loaded first, so the Net's
 calls bind to it; the per-range op calls of the batched cascade case's per-call form go through hipapi's own handle and stay this
 build's).  --parent-lib path/to/libmscnn_hip.so repeats the selected leg --rounds times in child processes, this build and
@@ -679,6 +686,138 @@ def merge_wbf_leg(a):
             fh.write("\n".join(lines) + "\n")
 
 
+SEQ_CASES = {   # name: model, frames of the clip (one forward of B = T images), classes, original image size, net input size
+    "kitti_car-7s576-clip8": ("kitti_car/mscnn-7s-576", 8, [2], (375, 1242), (576, 1920)),
+    "caltech-7s480-b8-clip8": ("caltech/mscnn-7s-480", 8, [2], (480, 640), (480, 640)),
+}
+
+
+def seq_clip_lists(a, hipapi, name):
+    """(T, K, cap, the filled candidate lists) of a SEQ_CASES case: ONE forward of T images, frame t the seeded frame shifted 4 t pixels
+    to the right (a camera that pans), added once; list = frame x K + class."""
+    import torch
+    model, T, classes, org, (H, W) = SEQ_CASES[name]
+    n = mnet.Net(prototxt_text=zoo.prototxt(model, batch=T))
+    synth.load_into(n, a.regime)
+    f0 = synth.frame(H, W, seed=1701, org_hw=org)
+    n.reshape_input("data", (T, 3, H, W))
+    n.set_blob("data", np.ascontiguousarray(np.concatenate([np.roll(f0, 4 * t, axis=-1) for t in range(T)], 0)))
+    n.forward()
+    R = n.blob_shape("proposals_score")[0]
+    cap = 2000
+    cand = hipapi.Candidates(T * len(classes), cap)
+    blobs = [torch.from_numpy(n.get_blob(b).reshape(R, -1)).cuda() for b in ("bbox_pred", "cls_pred", "proposals_score")]
+    segs = [dict(cls_id=c, ratios=(H / float(org[0]), W / float(org[1])), org_hw=org, nms_overlap=0.5) for _ in range(T) for c in classes]
+    cand.add(*blobs, T, segs)
+    del n
+    return T, len(classes), cap, cand
+
+
+def merge_seq_leg(a):
+    """--merge --seq: behind one add of a clip's T frames, the hard merge of every frame, Seq-NMS over the clip
+    (mscnn_detections_merge_seq_fwd, avg, link_thr 0.5) with top_k 300 and 1024, and the lists copied to the host + the vectorised numpy
+    Seq-NMS of tests/seq_witness.py there (top_k 300) -- the only route there was.  All forms end with the detections on the host; they
+    rotate within a step.  iters = the sequences of the chain (one chain per class: the loop's iterations); us/iter = ms * 1000 / iters
+    includes the sort, the link launch, the launches and the read-back."""
+    import torch
+    from mscnn_amd import hipapi
+    sys.path.insert(1, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import seq_witness as sq
+    thr, link = a.soft_thr, 0.5
+    names = ["hard merge", "seq avg top_k 300", "seq avg top_k 1024", "lists to host + numpy seq"]
+    lines = []
+
+    def say(line):
+        print(line, flush=True)
+        lines.append(line)
+
+    say(f"# Seq-NMS over a clip's candidate lists (link_thr {link:g}, score_thr {thr:g}, rescore avg, nms_overlap 0.5) per clip, host wall ms from an "
+        f"idle device to the detections on the host (median over {a.steps} steps after {a.warmup} warm-up; {a.rounds} rounds: median of the medians, "
+        f"spread = max - min), regime {a.regime}; dets = those of the longest output; entered = the boxes of all frames that entered (top_k 300 / "
+        f"1024); iters = the chain's sequences; us/iter = ms * 1000 / iters")
+    say(f"# {'case':24s} {'T':>2s} {'cands':>6s} {'longest':>7s} | " + " | ".join(f"{nm:>25s} {'dets':>5s} {'spread':>6s}" for nm in names) +
+        " | entered(300) iters us/iter entered(1024) iters us/iter longest-path")
+    for name in a.case or list(SEQ_CASES):
+        T, K, cap, cand = seq_clip_lists(a, hipapi, name)
+        S = T * K
+        L = hipapi.lib()
+        pack = torch.zeros(L.mscnn_detections_multi_pack_bytes(S, S * cap), dtype=torch.uint8, device="cuda")
+        ids = torch.zeros(S * cap, dtype=torch.int32, device="cuda")
+        ws = torch.empty(max(L.mscnn_detections_merge_workspace_bytes(S, cap), 1), dtype=torch.uint8, device="cuda")
+        wsq = torch.empty(L.mscnn_detections_merge_seq_workspace_bytes(T, K, cap, 1024), dtype=torch.uint8, device="cuda")
+        al = lambda v: (v + 255) // 256 * 256      # noqa: E731  (the candidate buffer's layout: include/mscnn_hip.h)
+        o0 = al(8 * S); o1 = o0 + al(32 * S * cap)
+        info = {}
+
+        def on_host():
+            cnt = cand.counts()                           # (one small copy; then of every list the filled slots only: boxes, probs)
+            lists = []
+            for s in range(S):
+                m = min(cnt[s][0], cap)
+                box = cand.buf[o0 + 32 * s * cap:o0 + 32 * (s * cap + m)].cpu().numpy().view(np.float64).reshape(m, 4)
+                prob = cand.buf[o1 + 4 * s * cap:o1 + 4 * (s * cap + m)].cpu().numpy().view(np.float32)
+                lists.append(np.concatenate([box, prob[:, None].astype(np.float64)], 1))
+            res, seqs = [None] * S, [None] * S
+            for k in range(K):
+                rows, tr = sq.seq_nms(lists[k::K], link, [0.5] * T, thr, 300, sq.AVG, 0)
+                info["longest"] = max(info.get("longest", 0), max(len(p) for p in tr["paths"]))
+                for t, (d, slots, q) in enumerate(rows):
+                    res[t * K + k], seqs[t * K + k] = (d, None, len(lists[t * K + k])), q.astype(np.int32)
+            return res, seqs
+
+        seq = lambda top_k: (lambda: cand.merge_seq(link, T, score_thr=thr, top_k=top_k, rescore="avg", pack=pack, ws=wsq, seq=ids))      # noqa: E731
+        forms = [lambda: (cand.merge(pack=pack, ws=ws), None), seq(300), seq(1024), on_host]
+        F = len(forms)
+        med = [[] for _ in range(F)]
+        for rnd in range(a.rounds):
+            t = [[] for _ in range(F)]
+            for step in range(a.warmup + a.steps):
+                res = [None] * F
+                for k in range(F):
+                    f = (k + step) % F
+                    torch.cuda.synchronize()      # (untimed: every form starts on an idle device)
+                    t0 = time.perf_counter()
+                    res[f] = forms[f]()
+                    dt = time.perf_counter() - t0
+                    if step >= a.warmup:
+                        t[f].append(dt)
+                for (d1, _, _), (d3, _, _), q1, q3 in zip(res[1][0], res[3][0], res[1][1], res[3][1]):
+                    assert np.array_equal(d1, d3) and np.array_equal(q1, q3), (name, step)      # the op against the host form, bit for bit
+            for f in range(F):
+                med[f].append(1e3 * float(np.median(t[f])))
+        cands = sum(c for _, _, c in res[0][0])
+        longest = max(c for _, _, c in res[0][0])
+        dets = [max(len(d) for d, _, _ in res[f][0]) for f in range(F)]
+        iters = [max(max([int(q.max()) + 1 for q in res[f][1][k::K] if len(q)] or [0]) for k in range(K)) for f in (1, 2)]
+        cnt = cand.counts()
+        entered = []
+        for top_k in (300, 1024):
+            e = 0
+            for s in range(S):
+                m = min(cnt[s][0], cap)
+                prob = cand.buf[o1 + 4 * s * cap:o1 + 4 * (s * cap + m)].cpu().numpy().view(np.float32)
+                e += min(int(np.count_nonzero(prob.astype(np.float64) >= thr)), top_k)
+            entered.append(e)
+        m = [float(np.median(v)) for v in med]
+        sp = [max(v) - min(v) for v in med]
+        say(f"  {name:24s} {T:2d} {cands:6d} {longest:7d} | " + " | ".join(f"{m[f]:25.3f} {dets[f]:5d} {sp[f]:6.3f}" for f in range(F)) +
+            f" | {entered[0]:12d} {iters[0]:5d} {1e3 * m[1] / max(iters[0], 1):7.2f} {entered[1]:13d} {iters[1]:5d} {1e3 * m[2] / max(iters[1], 1):7.2f}"
+            f" {info.get('longest', 0):12d}")
+        say(f"# {name}: seq top_k 300 / lists to host + numpy seq = {m[1] / m[3]:.3f} ({'the op is below' if m[1] + sp[1] < m[3] - sp[3] else 'the op is NOT below'} "
+            f"the host route by more than the two spreads); seq top_k 300 / hard merge = {m[1] / m[0]:.2f}; top_k 1024 / top_k 300 = {m[2] / m[1]:.2f}")
+    say("# python tools/bench_final_stage.py --merge --seq" + f" --steps {a.steps} --warmup {a.warmup} --rounds {a.rounds}: MI355X (gfx950), one GPU, seeded "
+        "weights; a clip is ONE forward of T = 8 images, frame t the seeded synthetic frame shifted 4 t pixels (a panning camera); the forward and the "
+        "add call are not timed.  cand_cap = 2000 per frame and class (the one-pass sort).")
+    say("# every step asserts that the op's detections and sequence ids (top_k 300) equal the host form's bit for bit.")
+    say("# NOT measured: the kernels alone (device events or a profiler), rescore max, clips of other lengths, more than one class (chains run side by "
+        "side, one workgroup each), lists past 4032 slots (sorted list after list), the cascade lists, the drivers end to end, real video, accuracy "
+        "(no labels).")
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+
 def use_lib(path):
     """The kernels of another build of libmscnn_hip.so under this build's Net: loaded first and globally, the Net library's calls bind
     to it (checked on one final-stage symbol)."""
@@ -738,8 +877,10 @@ ap.add_argument("--matrix", action="store_true", help="with --merge: the hard me
 ap.add_argument("--wbf", action="store_true", help="with --merge: the hard merge, Soft-NMS linear, Matrix NMS linear and the weighted boxes "
                 "fusion op (skip_thr 0.001 and 0.05, and with --max-dets 300) against every candidate list to the host + a numpy WBF; us per "
                 "walked candidate; the rows also go to --out")
-ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "detect_merge_wbf.txt"),
-                help="--merge --wbf: the file the rows are written to")
+ap.add_argument("--seq", action="store_true", help="with --merge: per clip of 8 frames the hard merge, the Seq-NMS op (avg, top_k 300 and 1024) "
+                "and every candidate list to the host + a vectorised numpy Seq-NMS; us per iteration; the rows also go to --out")
+ap.add_argument("--out", default=None, help="--merge --wbf / --merge --seq: the file the rows are written to (default: "
+                "profiles/detect_merge_wbf.txt / profiles/detect_merge_seq.txt; '' = none)")
 ap.add_argument("--soft-thr", type=float, default=0.001, help="--merge --soft / --matrix / --wbf: the score threshold of Soft-NMS and Matrix NMS")
 ap.add_argument("--rounds", type=int, default=3, help="--merge / --parent-lib: repetitions of the whole measurement")
 ap.add_argument("--lib", default="", help="run with the kernels of this libmscnn_hip.so under the Net")
@@ -756,6 +897,8 @@ ap.add_argument("--form", choices=("both", "call", "multi"), default="both",
 ap.add_argument("--nms-type", default="maxg", choices=("maxg", "max"), help="bbNms's type for both forms (Net.set_nms)")
 ap.add_argument("--ovr-dnm", default="union", choices=("union", "min"), help="bbNms's overlap denominator for both forms")
 a = ap.parse_args()
+if a.out is None:
+    a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "detect_merge_seq.txt" if a.seq else "detect_merge_wbf.txt")
 if a.parent_lib:
     ab_leg(a, sys.argv[1:])
     sys.exit(0)
@@ -772,6 +915,9 @@ if a.merge and a.matrix:
     sys.exit(0)
 if a.merge and a.wbf:
     merge_wbf_leg(a)
+    sys.exit(0)
+if a.merge and a.seq:
+    merge_seq_leg(a)
     sys.exit(0)
 if a.merge:
     merge_leg(a)

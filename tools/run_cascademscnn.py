@@ -48,6 +48,12 @@ tools/run_mscnn_detection.py; alone a merge of ONE forward; not Soft-NMS's score
 (Net.set_wbf): the candidates walked in score order into clusters, a cluster's box the score-weighted mean of its members, its
 confidence scaled by min(members, N) / N; --max-dets serves it too; not together with --soft-nms, --matrix-nms or --vote.  As
 tools/run_mscnn_detection.py; alone a merge of ONE forward; no pin on the reference, accuracy not evaluated.
+--seq-nms [avg|max] [--clip T] [--seq-link THR] [--seq-top-k N] [--tubelets-out DIR]: Seq-NMS over clips of T frames (Net.set_seq_nms;
+Han, Khorrami, Paine et al., 2016): one merge per clip with T lists per (output, class), every forward of --batch B frames added with
+list_of naming its frames' places in the clip, the views of --flip / --scales / --tiles to their frame's list; --soft-thr, --max-dets
+and --vote serve it; not together with --soft-nms, --matrix-nms or --wbf.  As tools/run_mscnn_detection.py; the result files keep their
+format, --tubelets-out adds DIR/<comp_id>_<class>_<output>.txt with rows [image_index sequence x y w h score]; no pin on the reference,
+accuracy not evaluated.
 
 Everything here is host glue over calls the test-suite covers one by one (Net.set_images, forward, detect_cascade_multi,
 reshape_input, kitti.write_detections_dlm)."""
@@ -119,11 +125,11 @@ def parse_args(argv=None):
                     "forward as group_NNNN.npz (to re-run the final stage on exactly what a forward produced)")
     ap.add_argument("--roialign-one-pass", action="store_true", help="run every ROIAlign head (two ROIAlign layers, their 2x2 AVE "
                     "poolings, the Concat: the WiderFace cascade's) as one launch (Net.set_roialign_one_pass); off: the five layers")
-    from run_mscnn_detection import add_merge_flags, check_merge_flags, one_forward_merge
+    from run_mscnn_detection import add_merge_flags, check_merge_flags, one_forward_merge, seq_on
     add_merge_flags(ap)
     a = ap.parse_args(argv)
     check_merge_flags(ap, a)
-    if (a.scales or a.flip or a.tiles or one_forward_merge(a)) and (a.orig_size or a.dump_blobs):
+    if (a.scales or a.flip or a.tiles or one_forward_merge(a) or seq_on(a)) and (a.orig_size or a.dump_blobs):
         ap.error("--scales / --flip / --tiles / --vote / --soft-nms / --matrix-nms / --wbf name the input sizes themselves and keep no single forward's blobs: not with --orig-size / "
                  "--dump-blobs")
     if not (a.prototxt or a.model) or not (a.images or a.synthetic):
@@ -147,7 +153,7 @@ def main(argv=None):
     import torch
     from mscnn_amd import kitti, net as mnet, synth, zoo
     from run_mscnn_detection import (apply_merge_settings, list_images, load_rgb_u8, merge_cand_cap, merge_passes, names_for, one_forward_merge,
-                                     run_frame_views, views_per_frame)
+                                     run_frame_views, run_seq_clips, seq_on, views_per_frame, write_tubelets)
 
     if a.prototxt:
         text = open(a.prototxt).read()
@@ -197,8 +203,10 @@ def main(argv=None):
     # them in ONE forward and one detect_cascade_merge_add(..., list_of=)
     # --vote: sticky box voting in every detect_merge_end; on its own the frame is a merge of one forward
     # --soft-nms: sticky Soft-NMS in place of that NMS; on its own a merge of one forward too
-    passes = merge_passes(a, shape[2:]) if (a.scales or a.flip or a.tiles or one_forward_merge(a)) else []
-    apply_merge_settings(net, a)
+    # --seq-nms: the frames a clip at a time (run_seq_clips), every forward's rows to the lists of its frames' places in the clip
+    passes = merge_passes(a, shape[2:]) if (a.scales or a.flip or a.tiles or one_forward_merge(a)) and not seq_on(a) else []
+    if not seq_on(a):
+        apply_merge_settings(net, a)
     by_views = bool(a.tiles or a.views_batch)
     n_fwd = len(a.scales or [0]) * views_per_frame(a) if by_views else len(passes)
 
@@ -206,6 +214,14 @@ def main(argv=None):
         net.detect_cascade_merge_add([dict(p, nms_overlap=a.nms_overlap) for p in params], outputs, cls_ids, det_thr=a.det_thr, views=mviews,
                                      **({} if list_of is None else dict(list_of=list_of)))
 
+    tubes = {key: [] for key in results}
+    if seq_on(a):
+        frames, shape, used = run_seq_clips(a, net, text, files, tuple(shape[2:]), shape, len(outputs) * len(cls_ids), load_frame,
+                                            lambda params, mviews, list_of: add(params, mviews, list_of))
+        for dets, seqs in frames:
+            for (o, c) in results:
+                results[(o, c)].append(dets[o * len(cls_ids) + c])
+                tubes[(o, c)].append(seqs[o * len(cls_ids) + c])
     for k, path in enumerate(files if passes else [], start=1):
         img = load_frame(path, k)
         net.detect_merge_begin(1, len(outputs) * len(cls_ids), merge_cand_cap(text, n_fwd, a.merge_cap))
@@ -231,7 +247,7 @@ def main(argv=None):
         if k % 100 == 0 or k == len(files):
             what = f"{n_fwd} views per frame, batched" if a.views_batch else f"{n_fwd} forwards per frame"
             print(f"idx {k}/{len(files)}, avgtime={used / k:.4f}s ({what})")
-    for g0 in range(0, len(files) if not passes else 0, a.batch):
+    for g0 in range(0, len(files) if not passes and not seq_on(a) else 0, a.batch):
         group = files[g0:g0 + a.batch]
         frames = [load_frame(path, g0 + i + 1) for i, path in enumerate(group)]
         H, W = net_input_size(frames[0].shape[0], frames[0].shape[1], a.max_size) if a.orig_size else shape[2:]
@@ -261,6 +277,8 @@ def main(argv=None):
         path = os.path.join(a.out, f"{a.comp_id}_{names[cls_ids[c] - 1]}_{out_names[o]}_results.txt")
         kitti.write_detections_dlm(path, dets)                               # :148-158
         print(f"{path}: {sum(len(d) for d in dets)} detections over {len(files)} images")
+        if a.tubelets_out:
+            write_tubelets(os.path.join(a.tubelets_out, f"{a.comp_id}_{names[cls_ids[c] - 1]}_{out_names[o]}.txt"), dets, tubes[(o, c)])
     return 0
 
 

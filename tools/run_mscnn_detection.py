@@ -19,6 +19,7 @@ examples/kitti_result/writeDetForEval.m.
          [--soft-nms linear|gaussian[:SIGMA]] [--soft-thr T] [--max-dets N]      # Soft-NMS in place of the merged NMS (Net.set_soft_nms)
          [--matrix-nms linear|gaussian[:SIGMA]]              # Matrix NMS in its place instead (Net.set_matrix_nms); --soft-thr / --max-dets serve it
          [--wbf [THR]] [--wbf-skip T] [--wbf-conf avg|max] [--wbf-expected N]      # weighted boxes fusion in its place instead (Net.set_wbf)
+         [--seq-nms [avg|max]] [--clip T] [--seq-link THR] [--seq-top-k N] [--tubelets-out DIR]      # Seq-NMS over clips of T frames (Net.set_seq_nms)
   python tools/run_mscnn_detection.py --model kitti_car/mscnn-7s-576 --synthetic 8      # no dataset / weights at hand: the generated
                                                                                         # deploy net, seeded weights, synthetic frames
 
@@ -80,6 +81,17 @@ counts the views added), so an object one view out of four found is marked down.
 score below T out, --max-dets N bounds the output.  Refused together with --soft-nms, --matrix-nms and --vote (a vote behind a fusion
 would average twice); alone it runs the frame as a merge of ONE forward.  The result files are unchanged (the member counts are not
 written).  There is no pin on the reference for it, and its accuracy against the other three was not evaluated (no labels here).
+
+--seq-nms [avg|max] runs Seq-NMS (Han, Khorrami, Paine et al., 2016) over the frames of a stream (Net.set_seq_nms, once per run): the
+input frames are taken --clip T (default 8) at a time in their order, the last clip may be shorter; one merge is opened per clip with T
+lists per class, each forward of --batch B frames is added with list_of naming its frames' places in the clip, and the views of
+--flip / --scales / --tiles go to their frame's list.  Per class, the boxes of neighbouring frames with an IoU above --seq-link THR
+(default 0.5) are linked, the chain with the largest score sum comes out with its mean (avg, the default) or largest (max) score on
+every box, and suppresses what its boxes overlap by more than --nms-overlap in their own frames.  --soft-thr T keeps candidates under
+T out, --seq-top-k N (default 300, at most 1024) bounds the candidates of a frame and class, --max-dets N the output; --vote runs
+behind it.  Refused together with --soft-nms, --matrix-nms and --wbf.  The result files keep their format; --tubelets-out DIR adds
+DIR/<comp_id>_<class>.txt with rows [image_index sequence x y w h score], `sequence` unique within a clip and class.  No pin on the
+reference, whose scripts run one forward per image and look at no other frame; accuracy was not evaluated (no labels here).
 
 Everything here is host glue over calls the test-suite covers one by one (Net.set_image / set_images / set_image_views, forward,
 detect / detect_multi, detect_merge_*, proposals_multi, kitti.write_*)."""
@@ -186,6 +198,18 @@ def add_merge_flags(ap):
                     "default) or largest (max) score")
     ap.add_argument("--wbf-expected", type=int, default=0, metavar="N", help="with --wbf: the N of min(members, N) / N (default 0: the views "
                     "added to the frame)")
+    ap.add_argument("--seq-nms", nargs="?", const="avg", default=None, choices=["avg", "max"], help="Seq-NMS over clips of --clip frames in "
+                    "place of the per-frame NMS (Net.set_seq_nms): the boxes of neighbouring frames are linked by IoU, the chain with the largest "
+                    "score sum comes out with its mean (avg) or largest (max) score and suppresses what it overlaps; not with --soft-nms / "
+                    "--matrix-nms / --wbf; --batch B frames share a forward")
+    ap.add_argument("--clip", type=int, default=8, metavar="T", help="with --seq-nms: frames per clip, 1 .. 256 (default 8; the last clip may be "
+                    "shorter)")
+    ap.add_argument("--seq-link", type=float, default=0.5, metavar="THR", help="with --seq-nms: boxes of neighbouring frames with an IoU above THR "
+                    "are linked (default 0.5)")
+    ap.add_argument("--seq-top-k", type=int, default=300, metavar="N", help="with --seq-nms: at most N candidates per frame and class take part, "
+                    "1 .. 1024 (default 300)")
+    ap.add_argument("--tubelets-out", default=None, metavar="DIR", help="with --seq-nms: DIR/<comp_id>_<class>.txt with rows [image_index sequence "
+                    "x y w h score]; sequence is unique within a clip and class")
     ap.add_argument("--soft-thr", type=float, default=0.001, metavar="T", help="with --soft-nms: stop picking when the best live score is below T; "
                     "with --matrix-nms: keep the scores >= T (default 0.001)")
     ap.add_argument("--max-dets", type=int, default=0, metavar="N", help="with --soft-nms / --matrix-nms / --wbf: at most N detections per class and "
@@ -210,6 +234,11 @@ def one_forward_merge(a):
     return a.vote is not None or a.soft_nms is not None or a.matrix_nms is not None or a.wbf is not None
 
 
+def seq_on(a):
+    """--seq-nms: the run goes clip by clip (run_seq_clips), whatever else is set."""
+    return getattr(a, "seq_nms", None) is not None
+
+
 def apply_merge_settings(net, a):
     """The sticky settings of every detect_merge_end of the run."""
     if a.vote is not None:
@@ -220,6 +249,8 @@ def apply_merge_settings(net, a):
         net.set_matrix_nms(a.matrix_nms[0], sigma=a.matrix_nms[1], score_thr=a.soft_thr, max_out=a.max_dets)
     if a.wbf is not None:
         net.set_wbf(a.wbf, skip_thr=a.wbf_skip, conf=a.wbf_conf, expected=a.wbf_expected, max_out=a.max_dets)
+    if seq_on(a):
+        net.set_seq_nms(a.seq_link, score_thr=a.soft_thr, top_k=a.seq_top_k, rescore=a.seq_nms, max_out=a.max_dets)
 
 
 def check_merge_flags(ap, a):
@@ -261,13 +292,27 @@ def check_merge_flags(ap, a):
             ap.error(f"--wbf-expected {a.wbf_expected}: must be >= 0")
     elif a.wbf_skip != 0.0 or a.wbf_conf != "avg" or a.wbf_expected != 0:
         ap.error("--wbf-skip / --wbf-conf / --wbf-expected belong to --wbf")
+    if seq_on(a):
+        for flag, on in (("--soft-nms", a.soft_nms is not None), ("--matrix-nms", a.matrix_nms is not None), ("--wbf", a.wbf is not None)):
+            if on:
+                ap.error(f"--seq-nms and {flag} exclude each other: one of them replaces the merged NMS")
+        if not 1 <= a.clip <= 256:
+            ap.error(f"--clip {a.clip}: a clip has 1 .. 256 frames")
+        if not 0.0 < a.seq_link < 1.0:
+            ap.error(f"--seq-link {a.seq_link:g}: the threshold must lie inside (0, 1)")
+        if not 1 <= a.seq_top_k <= 1024:
+            ap.error(f"--seq-top-k {a.seq_top_k}: must be 1 .. 1024")
+        if a.batch > 1 and (a.tiles or a.views_batch):
+            ap.error("--seq-nms with --tiles / --views-batch runs one frame's views per forward (drop --batch)")
+    elif a.clip != 8 or a.seq_link != 0.5 or a.seq_top_k != 300 or a.tubelets_out is not None:
+        ap.error("--clip / --seq-link / --seq-top-k / --tubelets-out belong to --seq-nms")
     if not 0.0 <= a.soft_thr < float("inf"):
         ap.error(f"--soft-thr {a.soft_thr:g}: the threshold must be a finite value >= 0")
     if a.max_dets < 0:
         ap.error(f"--max-dets {a.max_dets}: must be >= 0")
-    if a.soft_nms is None and a.matrix_nms is None and (a.soft_thr != 0.001 or (a.max_dets != 0 and a.wbf is None)):
-        ap.error("--soft-thr belongs to --soft-nms or --matrix-nms, --max-dets to one of them or to --wbf")
-    if (a.scales or a.flip or a.tiles or one_forward_merge(a)) and a.batch > 1:
+    if a.soft_nms is None and a.matrix_nms is None and not seq_on(a) and (a.soft_thr != 0.001 or (a.max_dets != 0 and a.wbf is None)):
+        ap.error("--soft-thr belongs to --soft-nms, --matrix-nms or --seq-nms, --max-dets to one of them or to --wbf")
+    if (a.scales or a.flip or a.tiles or one_forward_merge(a)) and a.batch > 1 and not seq_on(a):
         ap.error("--scales / --flip / --tiles / --vote / --soft-nms / --matrix-nms / --wbf run one frame per forward (drop --batch; --views-batch batches a frame's "
                  "views)")
 
@@ -326,6 +371,56 @@ def run_frame_views(a, net, img, scales, shape, add):
     return shape, used
 
 
+def run_seq_clips(a, net, text, files, net_hw, shape, slots, load, add):
+    """--seq-nms for both drivers: the frames --clip T at a time; per clip one detect_merge_begin with T lists per slot, per input size
+    (and mirror) one forward per --batch B frames of the clip, added with list_of = the frames' places in the clip -- with --tiles /
+    --views-batch the views of every frame, to that frame's list --, one detect_merge_end and its detect_merge_sequences.
+    add(params, merge views or None, list_of) is the driver's detect_merge_add.  Returns (per frame of the run ([dets per slot],
+    [sequence ids per slot]), the input's shape now, seconds in forwards)."""
+    import torch
+    passes = merge_passes(a, net_hw)
+    by_views = bool(a.tiles or a.views_batch)
+    n_fwd = len(a.scales or [0]) * views_per_frame(a) if by_views else len(passes)
+    cand_cap = merge_cand_cap(text, n_fwd, a.merge_cap)
+    apply_merge_settings(net, a)                                              # sticky: every detect_merge_end below runs Seq-NMS
+    out, used = [], 0.0
+    for c0 in range(0, len(files), a.clip):
+        imgs = [load(path, c0 + i + 1) for i, path in enumerate(files[c0:c0 + a.clip])]
+        net.detect_merge_begin(len(imgs), slots, cand_cap)
+        for t, img in enumerate(imgs if by_views else []):
+            shape, dt = run_frame_views(a, net, img, a.scales or [tuple(net_hw)], shape, lambda p, mv, lo, t=t: add(p, mv, [t] * len(p)))
+            used += dt
+        for H, W, flipped in () if by_views else passes:
+            for g0 in range(0, len(imgs), a.batch):
+                group = imgs[g0:g0 + a.batch]
+                if (len(group), 3, H, W) != tuple(shape):
+                    shape = (len(group), 3, H, W)
+                    net.reshape_input("data", shape)
+                dev_imgs = [torch.from_numpy(np.ascontiguousarray(f[:, ::-1]) if flipped else f).cuda(a.device) for f in group]
+                params = net.set_images("data", dev_imgs)
+                torch.cuda.synchronize(a.device)
+                t0 = time.perf_counter()
+                net.forward()
+                torch.cuda.synchronize(a.device)
+                used += time.perf_counter() - t0                              # forwards only, as :72-73
+                add(params, [dict(flip_x=1)] * len(group) if flipped else None, list(range(g0, g0 + len(group))))
+        per_image, _ = net.detect_merge_end()
+        seqs = net.detect_merge_sequences()
+        out += [([per_image[t][s][0] for s in range(slots)], [seqs[t][s] for s in range(slots)]) for t in range(len(imgs))]
+        k = c0 + len(imgs)
+        print(f"idx {k}/{len(files)}, avgtime={used / k:.4f}s (clips of {a.clip} frames, {n_fwd} forwards per frame)")
+    return out, shape, used
+
+
+def write_tubelets(path, per_frame_dets, per_frame_seq):
+    """--tubelets-out: rows [image_index sequence x y w h score] (1-based index, %.5g as the result files) of one class."""
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        for i, (dets, seq) in enumerate(zip(per_frame_dets, per_frame_seq), start=1):
+            for d, q in zip(dets, seq):
+                f.write(",".join(["%.5g" % float(v) for v in [i, q] + list(d[:5])]) + "\n")
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--prototxt"); ap.add_argument("--weights", help=".caffemodel (new or V1 layout) or .h5 snapshot")
@@ -353,7 +448,7 @@ def parse_args(argv=None):
     add_merge_flags(ap)
     a = ap.parse_args(argv)
     check_merge_flags(ap, a)
-    if (a.scales or a.flip or a.tiles or one_forward_merge(a)) and (a.rois_in or a.proposals_out or a.proposals_only):
+    if (a.scales or a.flip or a.tiles or one_forward_merge(a) or seq_on(a)) and (a.rois_in or a.proposals_out or a.proposals_only):
         ap.error("--scales / --flip / --tiles / --vote / --soft-nms / --matrix-nms merge detections: not with --rois-in, --proposals-out or --proposals-only")
     if a.proposals_only and not a.proposals_out:
         ap.error("--proposals-only needs --proposals-out DIR")
@@ -415,6 +510,8 @@ def main(argv=None):
     per_image_props = []
     forward = net.forward_proposals if a.proposals_only else net.forward
     rois = read_rois(a.rois_in, len(files)) if a.rois_in else None
+    if seq_on(a):
+        return run_seq(a, net, text, files, names, cls_ids, imgH, imgW, per_class)
     if a.batch > 1:
         return run_batched(a, net, files, names, cls_ids, imgH, imgW, per_class, per_image_props, forward, rois)
     if a.scales or a.flip or a.tiles or one_forward_merge(a):
@@ -452,6 +549,30 @@ def main(argv=None):
         if k % 100 == 0 or k == len(files):
             print(f"idx {k}/{len(files)}, avgtime={used / k:.4f}s")           # :147
     finish(a, names, cls_ids, per_class, per_image_props, len(files))
+    return 0
+
+
+def run_seq(a, net, text, files, names, cls_ids, imgH, imgW, per_class):
+    """--seq-nms: run_seq_clips with the plain stage's detect_merge_add; the result files as ever, --tubelets-out beside them."""
+    from mscnn_amd import kitti
+
+    def add(params, mviews, list_of):
+        p = [dict(q, proposal_thr=a.proposal_thr, nms_overlap=a.nms_overlap) for q in params]
+        net.detect_merge_add(p, cls_ids, views=mviews, list_of=list_of)
+
+    frames, _, _ = run_seq_clips(a, net, text, files, (imgH, imgW), (1, 3, imgH, imgW), len(cls_ids), load_frame, add)
+    for k, (path, (dets, _)) in enumerate(zip(files, frames), start=1):
+        by_type = {}
+        for ci, c in enumerate(cls_ids):
+            per_class[c].append(dets[ci])
+            by_type[{"car": "Car", "ped": "Pedestrian", "cyc": "Cyclist"}.get(names[c - 1], names[c - 1])] = dets[ci]
+        if a.labels_dir:
+            kitti.write_kitti_labels(a.labels_dir, frame_id(path, k), by_type)
+    finish(a, names, cls_ids, per_class, [], len(files))
+    for ci, c in enumerate(cls_ids if a.tubelets_out else []):
+        out = os.path.join(a.tubelets_out, f"{a.comp_id}_{names[c - 1]}.txt")
+        write_tubelets(out, [d[ci] for d, _ in frames], [q[ci] for _, q in frames])
+        print(f"{out}: {len(set((k // a.clip, int(v)) for k, (_, q) in enumerate(frames) for v in q[ci]))} tubelets over {len(files)} images")
     return 0
 
 
