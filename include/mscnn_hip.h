@@ -55,6 +55,7 @@
  *   detections_merge_matrix_fwd  cand, workspace, pack_dev 16: refuses
  *   detections_merge_wbf_fwd   cand, workspace, pack_dev 16, members_dev 4: refuses
  *   detections_merge_seq_fwd   cand, workspace, pack_dev 16, seq_dev 4: refuses
+ *   tracks_update_fwd, tracks_state_reset   pack_dev, state_in, state_out (state) 16, track_ids_dev 4: refuses
  *   proposals_multi_fwd        props 8: refuses
  *   rois_ingest                rows 8: refuses; rois, props, image_rows, status 4
  */
@@ -949,6 +950,88 @@ MSCNN_API int mscnn_detections_merge_seq_fwd(const double* nms_overlap /* HOST, 
                                              int num_frames, int num_slots, void* cand, int cand_cap, void* pack_dev,
                                              int* seq_dev /* may be NULL; [S * cand_cap] int32 */, void* workspace,
                                              size_t workspace_bytes, void* stream);
+
+/* A streaming multi-object tracker behind the final stage: BYTE association on the device (Zhang et al., "ByteTrack: Multi-Object
+ * Tracking by Associating Every Detection Box", 2022).  A small table of tracks per slot (class, or output x class) lives in device
+ * memory from call to call; every new frame's detections are associated with the tracks in two passes -- the high-score detections
+ * first, then the low-score detections against the tracks still unmatched -- and every detection row gets a persistent track id.
+ * Two deliberate departures from the paper: the motion is a constant-velocity prediction of the box centre in place of the Kalman
+ * filter, and the matching is greedy by descending overlap under a total order in place of the Hungarian solver.  Both make the
+ * result independent of reduction shape and scheduling: bit-exact against tests/track_witness.py.
+ * pack_dev: a multi pack as mscnn_detections_multi_fwd, the merge ops and Seq-NMS write it, mscnn_multi_pack_layout_of(S, cap) with
+ * S = num_frames * num_slots; segment s = t * K + k is frame t, slot k.  The op only reads it.  The segment's rows [x y w h score]
+ * start at its ROW OFFSET: table word 2 as the merge ops write it (s * cand_cap); in the pack of a batched forward, where the K
+ * slots of an image carry the same {rows, row0} -- told apart on the device by the first two entries of the frame having the same
+ * word 2, which no merged pack has --, mscnn_multi_pack_slot(K, row0, k, rows).  The frames of a call are consecutive frames of the
+ * stream in ascending t; the calls follow each other in stream order.  Slots never interact.
+ * state: per slot a header of MSCNN_TRACKS_HEADER_WORDS int32 {n, next_id, frame, dropped, skipped, 0, 0, 0}, behind it max_tracks
+ * records (mscnn_track_record); mscnn_tracks_state_layout_of names the offsets.  mscnn_tracks_state_reset sets n = 0, next_id = 1,
+ * frame = 0, dropped = skipped = 0.  state_in == state_out (in place) and two distinct buffers both work; records at index >= n of
+ * state_out are left as they were.  track_ids_dev: cap int32, one per pack row.
+ * Per slot and frame, all in double, every operation rounded (no fma):
+ *   1. frame += 1.
+ *   2. Entry.  count = the segment's table count.  count < 0 (an overflowed list) is an EMPTY frame: m = 0 and its track ids are not
+ *      written (so is a segment whose rows [offset, offset + count) do not lie inside the pack's cap rows).  Otherwise m = min(count,
+ *      1024), skipped += count - m.  Detection j = pack row j of the segment, s_j its score.  H = {j: s_j >= high_thr}, L = {j:
+ *      low_thr <= s_j < high_thr}; a NaN score is in neither.
+ *   3. Predict.  MSCNN_TRACK_MOTION_LINEAR: box.x += vel.x, box.y += vel.y for every track.  MSCNN_TRACK_MOTION_NONE: nothing.
+ *   4. Pass 1.  Every track i with every j in H: r(i, j) = the overlap with A = the track's box, B = the detection, in the vote's,
+ *      Soft-NMS's, Matrix NMS's, WBF's and Seq-NMS's statements, the union form:
+ *          iw = fmin(A.x + A.w, B.x + B.w) - fmax(A.x, B.x)   (iw <= 0: no pair);   ih likewise;
+ *          o = iw * ih;   u = A.w * A.h + B.w * B.h - o;   r = o / u                  (a NaN r: no pair)
+ *      A pair is eligible iff r > match_thr.  The eligible pairs are walked in the total order larger r, then the lower i, then the
+ *      lower j; a pair whose track and detection are both still free is matched.
+ *   5. Pass 2 (BYTE).  The tracks unmatched after pass 1 with misses == 0 and confirmed != 0 (seen in the previous frame) with every
+ *      j in L, eligible iff r > match_thr_low, the same walk.  low_thr == high_thr: L is empty, a plain greedy IoU tracker.
+ *   6. Matched (i, j).  g = misses + 1.  With MOTION_LINEAR dx = ((B.x + B.w / 2) - (obs.x + obs.w / 2)) / (double)g, dy likewise;
+ *      hits == 1: vel = (dx, dy); otherwise vel.x = vel.x + vel_gain * (dx - vel.x), vel.y likewise.  Then box = obs = B bit for bit,
+ *      score = s_j, hits += 1, misses = 0, confirmed |= (hits >= min_hits).
+ *   7. Unmatched track.  misses += 1; it keeps its predicted box, obs unchanged; it dies when confirmed == 0 or misses > max_age.
+ *   8. Births.  Every unmatched j in H with s_j >= new_thr, in ascending j: box = obs = B, vel = 0, score = s_j, hits = 1, misses = 0,
+ *      confirmed = (min_hits <= 1).
+ *   9. Compaction.  The survivors in their old order, then the births in ascending j; the first max_tracks are kept.  Births that do
+ *      not fit are dropped (dropped += their number, no id); the kept births take id = next_id++ in their order.  Table order is
+ *      age order, which is what the tie-break of step 4 reads.
+ *  10. track_ids_dev[row offset + j], j < count: the id of the track detection j was matched to or started, if that track is
+ *      confirmed after this frame, else 0.  Entries past count are not written.
+ * The walk of steps 4 and 5 runs as rounds of "match every mutually-best pair": the order on pairs is total, so a pair that is the
+ * best remaining pair of both its track and its detection is picked by the walk before any other pair that uses either, and the
+ * rounds give the same matching (tests/track_witness.py does both).  The loop carries its own bound, min(tracks, detections)
+ * rounds.  One launch per call, one workgroup of 1024 threads per slot looping over the frames, a thread = a track and a detection
+ * (hence the two 1024 bounds); one 32 KB box buffer in LDS holds the tracks' and the detections' boxes in turn (58 KB in all); the
+ * table is loaded once per call and stored once.  Nothing spins, no workgroup waits on another, no atomics.
+ * Refused before any launch, naming the value: a null params / pack_dev / state_in / state_out / track_ids_dev, num_frames < 1,
+ * num_slots < 1, cap < 1 (or S * cap past 2^31 - 1), max_tracks outside [1, 1024], a NaN high_thr / low_thr / new_thr, a match_thr
+ * or match_thr_low that is NaN or outside [0, 1), low_thr > high_thr, new_thr < high_thr, vel_gain outside (0, 1], a motion outside
+ * {1, 2}, max_age < 0, min_hits < 1, pack_dev / state_in / state_out not 16-byte aligned, track_ids_dev not 4-byte aligned, state_in
+ * and state_out overlapping without being equal.
+ * No pin on the reference: its scripts run one forward per image and look at no other frame.  The check is tests/track_witness.py: a
+ * float64 numpy restatement of the ten steps (bit for bit), with the walk done literally and by mutually-best rounds.  The accuracy
+ * of the tracker was NOT evaluated: there are no labels here. */
+enum { MSCNN_TRACK_MOTION_NONE = 1, MSCNN_TRACK_MOTION_LINEAR = 2 };
+#ifndef MSCNN_TRACK_PARAMS_DEFINED
+#define MSCNN_TRACK_PARAMS_DEFINED
+typedef struct { double high_thr, low_thr, new_thr, match_thr, match_thr_low, vel_gain;
+                 int motion, max_age, min_hits; } mscnn_track_params;
+#endif
+enum { MSCNN_TRACKS_N = 0, MSCNN_TRACKS_NEXT_ID = 1, MSCNN_TRACKS_FRAME = 2, MSCNN_TRACKS_DROPPED = 3, MSCNN_TRACKS_SKIPPED = 4,
+       MSCNN_TRACKS_HEADER_WORDS = 8 };      /* int32 words of a slot's header */
+typedef struct { double box[4], obs[4], vel[2], score; int32_t id, hits, misses, confirmed; } mscnn_track_record;      /* 104 bytes */
+typedef struct { size_t records, record, slot, total; } mscnn_tracks_state_layout;   /* byte offset of a slot's records, bytes of a record, of a slot, of the state */
+static inline mscnn_tracks_state_layout mscnn_tracks_state_layout_of(int num_slots, int max_tracks) {
+  const size_t K = (size_t)(num_slots > 0 ? num_slots : 0), M = (size_t)(max_tracks > 0 ? max_tracks : 0);
+  mscnn_tracks_state_layout L;
+  L.records = sizeof(int32_t) * MSCNN_TRACKS_HEADER_WORDS;
+  L.record = sizeof(mscnn_track_record);
+  L.slot = L.records + M * L.record;
+  L.total = (K * L.slot + 15) / 16 * 16;
+  return L;
+}
+MSCNN_API size_t mscnn_tracks_state_bytes(int num_slots, int max_tracks);      /* 0: refused arguments */
+MSCNN_API int mscnn_tracks_state_reset(void* state, int num_slots, int max_tracks, void* stream);
+MSCNN_API int mscnn_tracks_update_fwd(const mscnn_track_params* params, int num_frames, int num_slots, const void* pack_dev, int cap,
+                                      const void* state_in, void* state_out, int max_tracks,
+                                      int* track_ids_dev /* [cap] int32, one per pack row */, void* stream);
 
 /* The proposal half of the scripts' result (run_mscnn_detection.m:75-91, `final_proposals{k}`) for every image of a batched forward
  * in one pass.  props [R_all][6] = BoxOutput's proposals_score, rows [img x1 y1 x2 y2 score] grouped by image in ascending order;

@@ -478,6 +478,42 @@ MSCNN_NET_API int mscnn_net_detect_merge_members(mscnn_net* net, int* members_ho
 MSCNN_NET_API int mscnn_net_set_seq_nms(mscnn_net* net, double link_thr, double score_thr, int top_k, int rescore, int max_out);
 MSCNN_NET_API int mscnn_net_get_seq_nms(const mscnn_net* net, double* link_thr, double* score_thr, int* top_k, int* rescore, int* max_out);
 MSCNN_NET_API int mscnn_net_detect_merge_sequences(mscnn_net* net, int* seq_host, int cap, const int* seg_dets);
+/* Track ids across the frames of a stream (mscnn_hip.h: mscnn_tracks_update_fwd; BYTE association, Zhang et al., 2022, with a
+ * constant-velocity prediction in place of the Kalman filter and a greedy walk under a total order in place of the Hungarian solver).
+ * While the tracker is on, mscnn_net_detect_multi, mscnn_net_detect_cascade_multi and mscnn_net_detect_merge_end enqueue the update
+ * behind their pack -- on _end behind whichever merge op is on, and behind the vote --, on the same stream, in front of the one
+ * synchronisation those calls already have; the ids go behind the pack in the same pinned block, where WBF's member counts and (in
+ * front of them) Seq-NMS's sequence ids go, and come over with it.  The detections those calls return are unchanged.  The images of
+ * the call, or the frames (lists) of the merge, are consecutive frames of the stream in ascending order; a slot (class, or output x
+ * class) has a table of at most max_tracks tracks of its own.  K, the slots per frame, is fixed by the first call after a reset; a
+ * call with another K is refused, naming both values.
+ * The Net keeps two tables: a call reads the committed one and writes the other, and they are swapped only after the call has
+ * succeeded -- a call whose body runs twice (a stream-K hand-off recovery) or that fails steps the tracks neither twice nor half.
+ * mscnn_net_set_tracker: params NULL = off (the default: no call does anything it did not do before, no allocation, no launch);
+ * otherwise on with these values and a FRESH table (the next call starts at id 1).  Sticky.  Refused, naming the value and changing
+ * nothing: everything mscnn_tracks_update_fwd refuses about params and max_tracks; and turning it on while weighted boxes fusion is
+ * on, or set_wbf while it is on (the ids go where WBF's member counts go).  While it is on, the single-segment and the asynchronous
+ * forms -- mscnn_net_detect, _detect_image, _detect_begin, _detect_device, _detect_multi_device, _detect_cascade,
+ * _detect_cascade_multi_device -- are refused, naming the setting: no frame goes by untracked without a word.
+ * mscnn_net_get_tracker: on (0 / 1), the values, and num_slots = the K the table was made for (0: not fixed yet).
+ * mscnn_net_tracker_reset: a new stream -- the next call makes a fresh table (ids from 1) and fixes K again.
+ * mscnn_net_detect_tracks: after a tracked call, the track id of every detection that call returned, segment after segment in the
+ * order of dets_host (seg_dets[S] as the call filled it; cap = the ints ids_host holds); 0 = the detection belongs to no confirmed
+ * track.  It is an error, naming the reason, when the last of the three calls did not run the tracker or failed.
+ * mscnn_net_tracker_state: a host copy of the committed table (mscnn_tracks_state_layout_of(num_slots, max_tracks); bytes = what
+ * state_host holds).  set / get / reset work on a net built with device -1.
+ * No pin on the reference: its scripts run one forward per image and look at no other frame; the check is tests/track_witness.py.
+ * The accuracy of the tracker was not evaluated (no labels here). */
+#ifndef MSCNN_TRACK_PARAMS_DEFINED      /* include/mscnn_hip.h's struct, repeated here so that this header stands alone */
+#define MSCNN_TRACK_PARAMS_DEFINED
+typedef struct { double high_thr, low_thr, new_thr, match_thr, match_thr_low, vel_gain;
+                 int motion, max_age, min_hits; } mscnn_track_params;
+#endif
+MSCNN_NET_API int mscnn_net_set_tracker(mscnn_net* net, const mscnn_track_params* params /* NULL: off */, int max_tracks);
+MSCNN_NET_API int mscnn_net_get_tracker(const mscnn_net* net, int* on, mscnn_track_params* params, int* max_tracks, int* num_slots);
+MSCNN_NET_API int mscnn_net_tracker_reset(mscnn_net* net);
+MSCNN_NET_API int mscnn_net_detect_tracks(mscnn_net* net, int* ids_host, int cap, const int* seg_dets);
+MSCNN_NET_API int mscnn_net_tracker_state(mscnn_net* net, void* state_host, size_t bytes);
 /* The views of a frame as ONE batched forward (mscnn_hip.h: mscnn_detections_candidates_add_views): the merge was opened with
  * _begin(num_frames, ...), the input holds N images -- the views mscnn_net_set_image_views wrote --, p[N * K] and view[N] describe
  * them as in _add, and list_of[N] (host) names the frame of each: the rows of image b go to the lists of frame list_of[b].  One

@@ -1,0 +1,316 @@
+// A streaming multi-object tracker behind the final stage (mscnn_tracks_update_fwd): BYTE's two association passes (Zhang et al.,
+// "ByteTrack: Multi-Object Tracking by Associating Every Detection Box", 2022) over the multi pack's rows, a small table of tracks per
+// slot kept in device memory from call to call, a persistent track id for every detection row.  Two deliberate departures from the
+// paper: the motion is a constant-velocity prediction of the box centre in place of the Kalman filter, and the matching is greedy by
+// descending overlap under a total order (larger r, then the lower track, then the lower detection) in place of the Hungarian solver.
+// ONE workgroup of kTrackThreads owns a slot for the whole call and loops over the call's frames; thread i is track i AND detection i
+// of the frame at hand (hence max_tracks <= 1024 and the 1024 detections that enter).  A thread keeps its track's record and its
+// detection's row in registers: the table is loaded once per call and stored once.
+// The greedy walk runs as rounds of "match every mutually-best pair": because the order on pairs is total, a pair that is the best
+// remaining pair of both its track and its detection is picked by the walk before any other pair that uses either of them, so the
+// rounds give the walk's matching (tests/track_witness.py does both and compares).  A round: the free tracks' boxes go to LDS and every
+// free detection scans them for its best track (strict > over ascending i: the lower i among equal r); the free detections' boxes go
+// to the SAME 32 KB of LDS and every free track scans them for its best detection; a track whose best detection names it back is
+// matched.  A thread scans again only when the partner it found is no longer free: the free sets only shrink, so a best partner that
+// is still free is still the best.  r(i, j) is det_overlap<false>(track box, detection) from both sides: the same statements, the same
+// bits.  The loop carries its own bound, min(tracks, detections) rounds, and ends earlier at the first round that matches nothing.
+// Every loop bound and every value that guards a barrier is a kernel argument, a word of the pack or the state every thread reads
+// alike, a count every thread sums alike out of LDS, or the round's "any" word read behind a barrier.  No atomics at all, nothing
+// spins, no workgroup waits on another.  The compaction's places come from ballots and popcounts, the records move through the LDS box buffer field by
+// field.  All arithmetic is double, one statement per operation (-ffp-contract=off): bit-exact against tests/track_witness.py.
+#include "det_device.h"
+
+namespace {
+using namespace mscnn_dev;
+
+constexpr int kTrackThreads = 1024, kTrackWaves = kTrackThreads / 64;      // a thread is a track and a detection
+
+struct TrackArgs {
+  mscnn_track_params p;
+  int num_frames, num_slots, cap, max_tracks;
+  size_t dets_at, slot_bytes, records_at;      // the pack's rows; the state's slot stride and the records behind a slot's header
+  const char* pack;
+  const char* state_in; char* state_out;
+  int* ids;
+};
+
+// the places of the set flags among the workgroup's threads, and their number (every thread calls it; two barriers)
+__device__ __forceinline__ int track_rank(bool on, int* wsum, int* total_out) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const u64 bits = __ballot(on);
+  if (lane == 0) wsum[wave] = __popcll(bits);
+  __syncthreads();
+  int before = 0, total = 0;
+  for (int c = 0; c < kTrackWaves; ++c) {
+    const int v = wsum[c];
+    before += c < wave ? v : 0;
+    total += v;
+  }
+  __syncthreads();      // (wsum is free again)
+  *total_out = total;
+  return before + __popcll(bits & ((1ull << lane) - 1ull));
+}
+
+// One association pass.  tact: this thread's track takes part (and is free); dact: this thread's detection does.  tbox / dbox: the
+// thread's own track box and detection.  n tracks, m detections.  Returns through tmatch (the detection matched to this thread's
+// track) and dmatch (the track matched to this thread's detection); both stay as they were for the unmatched.
+__device__ __forceinline__ void track_pass(bool tact, bool dact, const DetBox& tbox, const DetBox& dbox, int n, int m, double thr,
+                                           DetBox* buf, int* best_d, int* dmatch_l, unsigned char* tfree, unsigned char* dfree, int* any,
+                                           int* tmatch, int* dmatch) {
+  const int tid = threadIdx.x;
+  tfree[tid] = tact ? 1 : 0;
+  dfree[tid] = dact ? 1 : 0;
+  best_d[tid] = -1;
+  dmatch_l[tid] = -1;
+  int my_bt = -2, my_bd = -2;      // the best track of my detection / the best detection of my track (-2: not scanned, -1: none)
+  const int rounds = n < m ? n : m;
+  for (int q = 0; q < rounds; ++q) {
+    if (tid == 0) *any = 0;
+    if (tid < n) buf[tid] = tbox;
+    __syncthreads();      // (the flags of the last round and the track boxes are written)
+    if (dact && dfree[tid] && (my_bt == -2 || (my_bt >= 0 && !tfree[my_bt]))) {
+      double br = 0.0;
+      my_bt = -1;
+      for (int i = 0; i < n; ++i) {
+        if (!tfree[i]) continue;
+        const DetBox A = buf[i];
+        const double r = det_overlap<false>(A, A.w * A.h, A.x + A.w, A.y + A.h, dbox);
+        if (r > thr && (my_bt < 0 || r > br)) { br = r; my_bt = i; }      // (no overlap or a NaN r: no pair)
+      }
+      best_d[tid] = my_bt;
+    }
+    __syncthreads();      // (every scan of the track boxes is done)
+    if (tid < m) buf[tid] = dbox;
+    __syncthreads();
+    if (tact && tfree[tid] && (my_bd == -2 || (my_bd >= 0 && !dfree[my_bd]))) {
+      const double as_a = tbox.w * tbox.h, xe_a = tbox.x + tbox.w, ye_a = tbox.y + tbox.h;
+      double br = 0.0;
+      my_bd = -1;
+      for (int j = 0; j < m; ++j) {
+        if (!dfree[j]) continue;
+        const double r = det_overlap<false>(tbox, as_a, xe_a, ye_a, buf[j]);
+        if (r > thr && (my_bd < 0 || r > br)) { br = r; my_bd = j; }
+      }
+    }
+    __syncthreads();      // (every scan has read the flags: they may change now)
+    if (tact && tfree[tid] && my_bd >= 0 && best_d[my_bd] == tid) {      // mutually best: the walk takes this pair first
+      tfree[tid] = 0; dfree[my_bd] = 0; dmatch_l[my_bd] = tid;
+      *tmatch = my_bd;
+      *any = 1;
+    }
+    __syncthreads();
+    if (!*any) break;      // (the same word in every thread; it is written again only behind the next barrier)
+    __syncthreads();
+  }
+  __syncthreads();
+  if (dact && dmatch_l[tid] >= 0) *dmatch = dmatch_l[tid];
+  __syncthreads();      // (the arrays are free again)
+}
+
+__global__ __launch_bounds__(kTrackThreads) void det_track_kernel(TrackArgs a) {
+  __shared__ DetBox buf[kTrackThreads];
+  __shared__ double sbuf[kTrackThreads];
+  __shared__ int best_d[kTrackThreads], dmatch_l[kTrackThreads], xa[kTrackThreads], xb[kTrackThreads];
+  __shared__ unsigned char tfree[kTrackThreads], dfree[kTrackThreads];
+  __shared__ int wsum[kTrackWaves];
+  __shared__ int any;
+  const int k = blockIdx.x, tid = threadIdx.x;
+  const int K = a.num_slots;
+  const int* hdr = reinterpret_cast<const int*>(a.pack);
+  const double* rows = reinterpret_cast<const double*>(a.pack + a.dets_at);
+  const bool linear = a.p.motion == MSCNN_TRACK_MOTION_LINEAR;
+
+  // the slot's header and this thread's record
+  const int* hin = reinterpret_cast<const int*>(a.state_in + a.slot_bytes * (size_t)k);
+  int n = hin[MSCNN_TRACKS_N], next_id = hin[MSCNN_TRACKS_NEXT_ID], frame = hin[MSCNN_TRACKS_FRAME];
+  int dropped = hin[MSCNN_TRACKS_DROPPED], skipped = hin[MSCNN_TRACKS_SKIPPED];
+  n = n < 0 ? 0 : (n > a.max_tracks ? a.max_tracks : n);      // (a table that was never reset: nothing past max_tracks is touched)
+  mscnn_track_record R = {};
+  if (tid < n) R = reinterpret_cast<const mscnn_track_record*>(a.state_in + a.slot_bytes * (size_t)k + a.records_at)[tid];
+
+  for (int t = 0; t < a.num_frames; ++t) {
+    frame += 1;                                                                               // step 1
+    // step 2: the segment's entry and this thread's detection
+    const int s = t * K + k;
+    const int* ent = hdr + MSCNN_MULTI_PACK_WORDS * (size_t)(1 + s);
+    const int count = ent[0];
+    long long off = ent[2];
+    if (K >= 2) {      // an image's slots share row0 (mscnn_detections_multi_fwd); a merged list has a row offset of its own
+      const int* e0 = hdr + MSCNN_MULTI_PACK_WORDS * (size_t)(1 + t * K);
+      if (e0[2] == e0[MSCNN_MULTI_PACK_WORDS + 2]) off = (long long)mscnn_multi_pack_slot(K, ent[2], k, ent[1]);
+    }
+    const bool fits = count >= 0 && off >= 0 && off + (long long)count <= (long long)a.cap;      // (else: an empty frame, no id written)
+    const int m = !fits ? 0 : (count < kTrackThreads ? count : kTrackThreads);
+    if (fits) skipped += count - m;
+    DetBox B = {0.0, 0.0, 0.0, 0.0};
+    double sc = 0.0;
+    int cls = 0;      // 1: in H, 2: in L
+    if (tid < m) {
+      const double* d = rows + 5 * ((size_t)off + (size_t)tid);
+      B.x = d[0]; B.y = d[1]; B.w = d[2]; B.h = d[3]; sc = d[4];
+      cls = sc >= a.p.high_thr ? 1 : (sc >= a.p.low_thr ? 2 : 0);      // (a NaN score is in neither set)
+    }
+    const bool have = tid < n;
+    if (linear && have) { R.box[0] += R.vel[0]; R.box[1] += R.vel[1]; }                       // step 3
+    const DetBox T = {R.box[0], R.box[1], R.box[2], R.box[3]};
+    int tmatch = -1, dmatch = -1;
+    track_pass(have, cls == 1, T, B, n, m, a.p.match_thr, buf, best_d, dmatch_l, tfree, dfree, &any, &tmatch, &dmatch);      // step 4
+    if (a.p.low_thr < a.p.high_thr)                                                           // step 5 (L is empty otherwise)
+      track_pass(have && tmatch < 0 && R.misses == 0 && R.confirmed != 0, cls == 2, T, B, n, m, a.p.match_thr_low, buf, best_d,
+                 dmatch_l, tfree, dfree, &any, &tmatch, &dmatch);
+    // steps 6 and 7: a matched detection hands its row to its track through LDS
+    if (dmatch >= 0) { buf[dmatch] = B; sbuf[dmatch] = sc; }
+    __syncthreads();
+    bool alive = false;
+    if (have) {
+      if (tmatch >= 0) {
+        const DetBox D = buf[tid];
+        if (linear) {
+          const double g = (double)(R.misses + 1);
+          const double hw = D.w / 2, hx = D.x + hw, ow = R.obs[2] / 2, ox = R.obs[0] + ow;
+          const double dx = (hx - ox) / g;
+          const double hh = D.h / 2, hy = D.y + hh, oh = R.obs[3] / 2, oy = R.obs[1] + oh;
+          const double dy = (hy - oy) / g;
+          if (R.hits == 1) {
+            R.vel[0] = dx; R.vel[1] = dy;
+          } else {
+            const double ex = dx - R.vel[0], gx = a.p.vel_gain * ex;
+            R.vel[0] = R.vel[0] + gx;
+            const double ey = dy - R.vel[1], gy = a.p.vel_gain * ey;
+            R.vel[1] = R.vel[1] + gy;
+          }
+        }
+        R.box[0] = D.x; R.box[1] = D.y; R.box[2] = D.w; R.box[3] = D.h;
+        R.obs[0] = D.x; R.obs[1] = D.y; R.obs[2] = D.w; R.obs[3] = D.h;
+        R.score = sbuf[tid];
+        R.hits += 1; R.misses = 0;
+        if (R.hits >= a.p.min_hits) R.confirmed |= 1;
+        alive = true;
+      } else {
+        R.misses += 1;
+        alive = R.confirmed != 0 && R.misses <= a.p.max_age;
+      }
+      xa[tid] = R.confirmed != 0 ? R.id : 0;      // what a detection matched to this track is given
+    }
+    const bool born = cls == 1 && dmatch < 0 && sc >= a.p.new_thr;                            // step 8
+    // step 9: the survivors in their old order, then the births in ascending j; the first max_tracks
+    int nsurv = 0, nborn = 0;
+    const int ps = track_rank(alive, wsum, &nsurv);      // (its barriers also publish xa)
+    const int pb = track_rank(born, wsum, &nborn);
+    const int room = a.max_tracks - nsurv;               // (>= 0: nsurv <= n <= max_tracks)
+    const int kept = nborn < room ? nborn : room;
+    const bool born_kept = born && pb < kept;
+    // step 10
+    if (tid < m) {
+      int id = 0;
+      if (dmatch >= 0) id = xa[dmatch];
+      else if (born_kept && a.p.min_hits <= 1) id = next_id + pb;
+      a.ids[(size_t)off + (size_t)tid] = id;
+    }
+    if (fits)
+      for (int j = kTrackThreads + tid; j < count; j += kTrackThreads) a.ids[(size_t)off + (size_t)j] = 0;      // (never entered)
+    __syncthreads();      // (xa is free again)
+    if (nsurv != n || kept > 0) {      // the records move to their new places, field by field through LDS
+      const int pd = nsurv + pb;
+      if (alive) { buf[ps] = DetBox{R.box[0], R.box[1], R.box[2], R.box[3]}; sbuf[ps] = R.score; xa[ps] = R.id; xb[ps] = R.hits; }
+      if (born_kept) { buf[pd] = B; sbuf[pd] = sc; xa[pd] = next_id + pb; xb[pd] = 1; }
+      __syncthreads();
+      const int n2 = nsurv + kept;
+      mscnn_track_record N = {};
+      if (tid < n2) { const DetBox D = buf[tid]; N.box[0] = D.x; N.box[1] = D.y; N.box[2] = D.w; N.box[3] = D.h; N.score = sbuf[tid]; N.id = xa[tid]; N.hits = xb[tid]; }
+      __syncthreads();
+      if (alive) { buf[ps] = DetBox{R.obs[0], R.obs[1], R.obs[2], R.obs[3]}; sbuf[ps] = R.vel[0]; xa[ps] = R.misses; xb[ps] = R.confirmed; }
+      if (born_kept) { buf[pd] = B; sbuf[pd] = 0.0; xa[pd] = 0; xb[pd] = a.p.min_hits <= 1 ? 1 : 0; }
+      __syncthreads();
+      if (tid < n2) { const DetBox D = buf[tid]; N.obs[0] = D.x; N.obs[1] = D.y; N.obs[2] = D.w; N.obs[3] = D.h; N.vel[0] = sbuf[tid]; N.misses = xa[tid]; N.confirmed = xb[tid]; }
+      __syncthreads();
+      if (alive) sbuf[ps] = R.vel[1];
+      if (born_kept) sbuf[pd] = 0.0;
+      __syncthreads();
+      if (tid < n2) N.vel[1] = sbuf[tid];
+      __syncthreads();
+      R = N;
+      n = n2;
+    }
+    dropped += nborn - kept;
+    next_id += kept;
+  }
+
+  char* so = a.state_out + a.slot_bytes * (size_t)k;
+  if (tid == 0) {
+    int* h = reinterpret_cast<int*>(so);
+    h[MSCNN_TRACKS_N] = n; h[MSCNN_TRACKS_NEXT_ID] = next_id; h[MSCNN_TRACKS_FRAME] = frame; h[MSCNN_TRACKS_DROPPED] = dropped;
+    h[MSCNN_TRACKS_SKIPPED] = skipped; h[5] = 0; h[6] = 0; h[7] = 0;
+  }
+  if (tid < n) reinterpret_cast<mscnn_track_record*>(so + a.records_at)[tid] = R;      // (records at index >= n stay as they were)
+}
+
+__global__ void det_track_reset_kernel(char* state, size_t slot_bytes, int num_slots) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= num_slots) return;
+  int* h = reinterpret_cast<int*>(state + slot_bytes * (size_t)k);
+  h[MSCNN_TRACKS_N] = 0; h[MSCNN_TRACKS_NEXT_ID] = 1; h[MSCNN_TRACKS_FRAME] = 0; h[MSCNN_TRACKS_DROPPED] = 0; h[MSCNN_TRACKS_SKIPPED] = 0;
+  h[5] = 0; h[6] = 0; h[7] = 0;
+}
+
+inline bool track_shape_ok(int K, int max_tracks) { return K >= 1 && max_tracks >= 1 && max_tracks <= kTrackThreads; }
+}  // namespace
+
+using namespace mscnn;
+
+extern "C" size_t mscnn_tracks_state_bytes(int num_slots, int max_tracks) {
+  if (!track_shape_ok(num_slots, max_tracks)) return 0;
+  return mscnn_tracks_state_layout_of(num_slots, max_tracks).total;
+}
+
+extern "C" int mscnn_tracks_state_reset(void* state, int num_slots, int max_tracks, void* stream) {
+  MSCNN_REQUIRE(state, "tracks_state_reset: null state");
+  MSCNN_REQUIRE(num_slots >= 1, "tracks_state_reset: num_slots %d", num_slots);
+  MSCNN_REQUIRE(max_tracks >= 1 && max_tracks <= kTrackThreads, "tracks_state_reset: max_tracks %d is outside [1, %d]", max_tracks, kTrackThreads);
+  MSCNN_REQUIRE_ALIGNED(state, 16, "tracks_state_reset: state");
+  const mscnn_tracks_state_layout L = mscnn_tracks_state_layout_of(num_slots, max_tracks);
+  det_track_reset_kernel<<<cdiv(num_slots, 256), 256, 0, as_stream(stream)>>>(static_cast<char*>(state), L.slot, num_slots);
+  MSCNN_POST_LAUNCH();
+  return MSCNN_OK;
+}
+
+extern "C" int mscnn_tracks_update_fwd(const mscnn_track_params* p, int num_frames, int num_slots, const void* pack_dev, int cap,
+                                       const void* state_in, void* state_out, int max_tracks, int* track_ids_dev, void* stream) {
+  MSCNN_REQUIRE(p && pack_dev && state_in && state_out && track_ids_dev, "tracks_update: null pointer");
+  const int T = num_frames, K = num_slots;
+  MSCNN_REQUIRE(T >= 1, "tracks_update: num_frames %d", T);
+  MSCNN_REQUIRE(K >= 1, "tracks_update: num_slots %d", K);
+  MSCNN_REQUIRE(cap >= 1, "tracks_update: cap %d", cap);
+  MSCNN_REQUIRE((long)T * (long)K <= 0x7fffffffL && (long)T * (long)K * (long)cap <= 0x7fffffffL,
+                "tracks_update: %d frames x %d slots x %d pack rows is past 2^31 - 1", T, K, cap);
+  MSCNN_REQUIRE(max_tracks >= 1 && max_tracks <= kTrackThreads, "tracks_update: max_tracks %d is outside [1, %d]", max_tracks, kTrackThreads);
+  MSCNN_REQUIRE(!(p->high_thr != p->high_thr), "tracks_update: high_thr is NaN");
+  MSCNN_REQUIRE(!(p->low_thr != p->low_thr), "tracks_update: low_thr is NaN");
+  MSCNN_REQUIRE(!(p->new_thr != p->new_thr), "tracks_update: new_thr is NaN");
+  MSCNN_REQUIRE(p->match_thr >= 0 && p->match_thr < 1, "tracks_update: match_thr %g is not inside [0, 1)", p->match_thr);      // (NaN included)
+  MSCNN_REQUIRE(p->match_thr_low >= 0 && p->match_thr_low < 1, "tracks_update: match_thr_low %g is not inside [0, 1)", p->match_thr_low);
+  MSCNN_REQUIRE(p->low_thr <= p->high_thr, "tracks_update: low_thr %g is above high_thr %g", p->low_thr, p->high_thr);
+  MSCNN_REQUIRE(p->new_thr >= p->high_thr, "tracks_update: new_thr %g is below high_thr %g", p->new_thr, p->high_thr);
+  MSCNN_REQUIRE(p->vel_gain > 0 && p->vel_gain <= 1, "tracks_update: vel_gain %g is not inside (0, 1]", p->vel_gain);
+  MSCNN_REQUIRE(p->motion == MSCNN_TRACK_MOTION_NONE || p->motion == MSCNN_TRACK_MOTION_LINEAR,
+                "tracks_update: motion %d is neither %d (none) nor %d (linear)", p->motion, MSCNN_TRACK_MOTION_NONE, MSCNN_TRACK_MOTION_LINEAR);
+  MSCNN_REQUIRE(p->max_age >= 0, "tracks_update: max_age %d", p->max_age);
+  MSCNN_REQUIRE(p->min_hits >= 1, "tracks_update: min_hits %d", p->min_hits);
+  MSCNN_REQUIRE_ALIGNED(pack_dev, 16, "tracks_update: pack_dev");
+  MSCNN_REQUIRE_ALIGNED(state_in, 16, "tracks_update: state_in");
+  MSCNN_REQUIRE_ALIGNED(state_out, 16, "tracks_update: state_out");
+  MSCNN_REQUIRE_ALIGNED(track_ids_dev, 4, "tracks_update: track_ids_dev");
+  const mscnn_tracks_state_layout SL = mscnn_tracks_state_layout_of(K, max_tracks);
+  const size_t bytes = SL.total;
+  const uintptr_t si = reinterpret_cast<uintptr_t>(state_in), so = reinterpret_cast<uintptr_t>(state_out);
+  MSCNN_REQUIRE(si == so || si + bytes <= so || so + bytes <= si, "tracks_update: state_in and state_out overlap (%zu bytes each) without being equal",
+                bytes);
+  TrackArgs a = {};
+  a.p = *p; a.num_frames = T; a.num_slots = K; a.cap = cap; a.max_tracks = max_tracks;
+  a.pack = static_cast<const char*>(pack_dev); a.state_in = static_cast<const char*>(state_in); a.state_out = static_cast<char*>(state_out);
+  a.ids = track_ids_dev;
+  a.dets_at = mscnn_multi_pack_layout_of(T * K, cap).dets; a.slot_bytes = SL.slot; a.records_at = SL.records;
+  det_track_kernel<<<K, kTrackThreads, 0, as_stream(stream)>>>(a);
+  MSCNN_POST_LAUNCH();
+  return MSCNN_OK;
+}

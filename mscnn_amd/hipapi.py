@@ -248,6 +248,11 @@ def lib():
         L.mscnn_detections_merge_seq_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
         L.mscnn_detections_merge_seq_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                                      C.c_void_p, C.c_size_t, C.c_void_p]
+        L.mscnn_tracks_state_bytes.restype = C.c_size_t
+        L.mscnn_tracks_state_bytes.argtypes = [C.c_int, C.c_int]
+        L.mscnn_tracks_state_reset.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.mscnn_tracks_update_fwd.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                              C.c_void_p]
         L.mscnn_proposals_multi_pack_bytes.restype = C.c_size_t
         L.mscnn_proposals_multi_pack_bytes.argtypes = [C.c_int, C.c_int]
         L.mscnn_proposals_multi_fwd.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
@@ -1333,6 +1338,93 @@ class Candidates:
                 raise MscnnError(f"{what}: table entry {s}: {hdr[1 + s].tolist()}")
             out.append((dets[row0:row0 + cnt].copy(), tags[row0:row0 + cnt].copy(), cands) if cnt >= 0 else (None, None, cands))
         return (out, h) if raw_pack else out
+
+
+# ---- the tracker behind the final stage (mscnn_hip.h: mscnn_tracks_update_fwd) ----
+TRACK_MOTIONS = {"none": 1, "linear": 2}      # MSCNN_TRACK_MOTION_NONE / _LINEAR
+TRACKS_HEADER_WORDS = 8                       # MSCNN_TRACKS_HEADER_WORDS: {n, next_id, frame, dropped, skipped, 0, 0, 0}
+TRACKS_MAX = 1024                             # max_tracks' bound, and the detections of a frame that enter
+
+
+class TrackParams(C.Structure):
+    """mscnn_track_params: low_thr <= high_thr <= new_thr; match_thr, match_thr_low inside [0, 1); vel_gain inside (0, 1]; motion 1 =
+    none, 2 = linear; max_age >= 0; min_hits >= 1."""
+    _fields_ = [("high_thr", C.c_double), ("low_thr", C.c_double), ("new_thr", C.c_double), ("match_thr", C.c_double),
+                ("match_thr_low", C.c_double), ("vel_gain", C.c_double), ("motion", C.c_int), ("max_age", C.c_int), ("min_hits", C.c_int)]
+
+
+class TrackRecord(C.Structure):
+    """mscnn_track_record (104 bytes)."""
+    _fields_ = [("box", C.c_double * 4), ("obs", C.c_double * 4), ("vel", C.c_double * 2), ("score", C.c_double), ("id", C.c_int32),
+                ("hits", C.c_int32), ("misses", C.c_int32), ("confirmed", C.c_int32)]
+
+
+TRACK_RECORD = np.dtype([("box", "<f8", 4), ("obs", "<f8", 4), ("vel", "<f8", 2), ("score", "<f8"), ("id", "<i4"), ("hits", "<i4"),
+                         ("misses", "<i4"), ("confirmed", "<i4")])
+assert TRACK_RECORD.itemsize == C.sizeof(TrackRecord) == 104
+
+
+def track_motion(motion):
+    """A motion's number from its name ("none", "linear"); a number passes through for the library to judge."""
+    if isinstance(motion, str):
+        if motion not in TRACK_MOTIONS:
+            raise MscnnError(f"tracker: motion {motion!r} is none of {sorted(TRACK_MOTIONS)}")
+        return TRACK_MOTIONS[motion]
+    return int(motion)
+
+
+def track_params(high_thr=0.5, low_thr=0.1, new_thr=None, match_thr=0.3, match_thr_low=0.5, motion="linear", vel_gain=0.5, max_age=30,
+                 min_hits=1):
+    """A TrackParams; new_thr None: high_thr."""
+    return TrackParams(float(high_thr), float(low_thr), float(high_thr if new_thr is None else new_thr), float(match_thr),
+                       float(match_thr_low), float(vel_gain), track_motion(motion), int(max_age), int(min_hits))
+
+
+def tracks_state_layout(num_slots, max_tracks):
+    """mscnn_tracks_state_layout_of: (byte offset of a slot's records, bytes of a record, of a slot, of the state)."""
+    slot = 4 * TRACKS_HEADER_WORDS + max(max_tracks, 0) * TRACK_RECORD.itemsize
+    return 4 * TRACKS_HEADER_WORDS, TRACK_RECORD.itemsize, slot, (max(num_slots, 0) * slot + 15) // 16 * 16
+
+
+def tracks_state_parse(state, num_slots, max_tracks):
+    """A state buffer (uint8, host) as one dict per slot: n, next_id, frame, dropped, skipped and tracks = the first n records as a
+    numpy record array (box, obs, vel, score, id, hits, misses, confirmed)."""
+    rec_at, rec, slot, total = tracks_state_layout(num_slots, max_tracks)
+    b = np.ascontiguousarray(state, dtype=np.uint8).reshape(-1)
+    if b.size < total:
+        raise MscnnError(f"tracker: a state of {b.size} bytes, {num_slots} slots x {max_tracks} tracks need {total}")
+    out = []
+    for k in range(num_slots):
+        h = b[k * slot:k * slot + rec_at].view(np.int32)
+        n = int(h[0])
+        if not 0 <= n <= max_tracks:
+            raise MscnnError(f"tracker: slot {k} holds {n} tracks of {max_tracks} (a state that was never reset?)")
+        recs = b[k * slot + rec_at:k * slot + rec_at + n * rec].view(TRACK_RECORD).copy()
+        out.append(dict(n=n, next_id=int(h[1]), frame=int(h[2]), dropped=int(h[3]), skipped=int(h[4]), tracks=recs))
+    return out
+
+
+def tracks_state_new(num_slots, max_tracks, device="cuda"):
+    """A reset state buffer (uint8 device tensor of mscnn_tracks_state_bytes)."""
+    nbytes = lib().mscnn_tracks_state_bytes(num_slots, max_tracks)
+    if nbytes == 0:
+        raise MscnnError(f"tracker: {num_slots} slots x {max_tracks} tracks (max_tracks inside [1, {TRACKS_MAX}])")
+    state = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    _check(lib().mscnn_tracks_state_reset(_dev(state), num_slots, max_tracks, _stream()))
+    return state
+
+
+def tracks_update(params, num_frames, num_slots, pack, cap, state_in, max_tracks, state_out=None, ids=None):
+    """mscnn_tracks_update_fwd on a multi pack of num_frames x num_slots segments with cap rows (a uint8 device tensor, only read):
+    steps the tracks of state_in through the frames into state_out (None: in place) and writes one track id per detection row into
+    ids (int32 [cap]; zero-filled when None).  Returns (state_out, ids); a segment's ids start at its row offset."""
+    if state_out is None:
+        state_out = state_in
+    if ids is None:
+        ids = torch.zeros(max(cap, 1), dtype=torch.int32, device=pack.device)
+    _check(lib().mscnn_tracks_update_fwd(C.byref(params), num_frames, num_slots, _dev(pack), cap, _dev(state_in), _dev(state_out),
+                                         max_tracks, _dev(ids), _stream()))
+    return state_out, ids
 
 
 # ---- health of the plane-GEMM kernel's stream-K hand-off (mscnn_hip.h) ----

@@ -51,6 +51,17 @@ struct mscnn_net {
   mscnn_seq_nms_params seq = {0.0, 0.001, 300, MSCNN_SEQ_NMS_AVG, 0};
   bool sequences_valid = false;            // the last detect_merge_end ran Seq-NMS and succeeded: seq_ids are its detections' sequence ids
   std::vector<int> seq_ids, seq_seg_dets;
+  // mscnn_net_set_tracker: off by default; while on, detect_multi / detect_cascade_multi / detect_merge_end enqueue
+  // mscnn_tracks_update_fwd behind their pack.  Two state buffers: a call reads the committed one (track_cur) and writes the other, and
+  // they are swapped only after the call has succeeded, so a call that is run twice (a hand-off recovery) or fails steps nothing.
+  bool track_on = false;
+  mscnn_track_params track = {0.5, 0.1, 0.5, 0.3, 0.5, 0.5, MSCNN_TRACK_MOTION_LINEAR, 30, 1};
+  int track_max = 256;
+  int track_K = 0;                         // slots per frame, fixed by the first call after a reset (0: not fixed, no state yet)
+  int track_cur = 0;
+  caffe::DeviceBuffer track_state[2];
+  bool tracks_valid = false;               // the last tracked call succeeded: track_ids are its detections' track ids
+  std::vector<int> track_ids, track_seg_dets;
   // mscnn_net_detect_merge_*: the candidate lists of the forwards added since _begin (mscnn_hip.h: mscnn_detections_candidates_*)
   struct Merge {
     bool open = false;
@@ -583,6 +594,8 @@ int mscnn_net_set_wbf(mscnn_net* n, double thr, double skip_thr, int conf_type, 
                                      << "): the two exclude each other, turn that one off first";
     CHECK(!on || n->seq.link_thr == 0.0) << "set_wbf: thr " << thr << " while Seq-NMS is on (set_seq_nms link_thr " << n->seq.link_thr
                                          << "): the two exclude each other, turn that one off first";
+    CHECK(!on || !n->track_on) << "set_wbf: thr " << thr << " while the tracker is on (set_tracker high_thr " << n->track.high_thr
+                               << "): the two exclude each other (the track ids go where WBF's member counts go), turn that one off first";
     n->wbf = mscnn_wbf_params{on ? thr : 0.0, skip_thr, conf_type, max_out};      // (-0.0 is off too)
     n->wbf_expected = expected;
   });
@@ -622,6 +635,108 @@ int mscnn_net_get_seq_nms(const mscnn_net* n, double* link_thr, double* score_th
     *link_thr = n->seq.link_thr; *score_thr = n->seq.score_thr; *top_k = n->seq.top_k; *rescore = n->seq.rescore; *max_out = n->seq.max_out;
   });
 }
+
+int mscnn_net_set_tracker(mscnn_net* n, const mscnn_track_params* p, int max_tracks) {
+  return guarded([&] {
+    CHECK(n != nullptr);
+    if (p == nullptr) {      // off: the state is dropped with the setting
+      n->track_on = false; n->track_K = 0; n->tracks_valid = false;
+      return;
+    }
+    // (the op's own refusals, made here so that a refused value changes nothing and is named at the call that brought it)
+    CHECK(max_tracks >= 1 && max_tracks <= 1024) << "set_tracker: max_tracks " << max_tracks << " is outside [1, 1024]";
+    CHECK(!(p->high_thr != p->high_thr) && !(p->low_thr != p->low_thr) && !(p->new_thr != p->new_thr))
+        << "set_tracker: a NaN threshold (high_thr " << p->high_thr << ", low_thr " << p->low_thr << ", new_thr " << p->new_thr << ")";
+    CHECK(p->match_thr >= 0 && p->match_thr < 1) << "set_tracker: match_thr " << p->match_thr << " is not inside [0, 1)";
+    CHECK(p->match_thr_low >= 0 && p->match_thr_low < 1) << "set_tracker: match_thr_low " << p->match_thr_low << " is not inside [0, 1)";
+    CHECK(p->low_thr <= p->high_thr) << "set_tracker: low_thr " << p->low_thr << " is above high_thr " << p->high_thr;
+    CHECK(p->new_thr >= p->high_thr) << "set_tracker: new_thr " << p->new_thr << " is below high_thr " << p->high_thr;
+    CHECK(p->vel_gain > 0 && p->vel_gain <= 1) << "set_tracker: vel_gain " << p->vel_gain << " is not inside (0, 1]";
+    CHECK(p->motion == MSCNN_TRACK_MOTION_NONE || p->motion == MSCNN_TRACK_MOTION_LINEAR)
+        << "set_tracker: motion " << p->motion << " is neither " << MSCNN_TRACK_MOTION_NONE << " (none) nor " << MSCNN_TRACK_MOTION_LINEAR << " (linear)";
+    CHECK_GE(p->max_age, 0) << "set_tracker: max_age " << p->max_age;
+    CHECK_GE(p->min_hits, 1) << "set_tracker: min_hits " << p->min_hits;
+    CHECK(n->wbf.thr == 0.0) << "set_tracker: high_thr " << p->high_thr << " while weighted boxes fusion is on (set_wbf thr " << n->wbf.thr
+                             << "): the two exclude each other (the track ids go where WBF's member counts go), turn that one off first";
+    n->track = *p; n->track_max = max_tracks; n->track_on = true;
+    n->track_K = 0; n->tracks_valid = false;      // a new setting is a new stream: the next call starts at id 1
+  });
+}
+
+int mscnn_net_get_tracker(const mscnn_net* n, int* on, mscnn_track_params* p, int* max_tracks, int* num_slots) {
+  return guarded([&] {
+    CHECK(n && on && p && max_tracks && num_slots);
+    *on = n->track_on ? 1 : 0; *p = n->track; *max_tracks = n->track_max; *num_slots = n->track_K;
+  });
+}
+
+int mscnn_net_tracker_reset(mscnn_net* n) {
+  return guarded([&] {
+    CHECK(n != nullptr);
+    CHECK(n->track_on) << "tracker_reset: the tracker is off (mscnn_net_set_tracker)";
+    n->track_K = 0; n->tracks_valid = false;      // (the next tracked call resets the table on its stream, in front of its update)
+  });
+}
+
+int mscnn_net_tracker_state(mscnn_net* n, void* state_host, size_t bytes) {
+  return guarded([&] {
+    CHECK(n != nullptr);
+    CHECK(n->track_on) << "tracker_state: the tracker is off (mscnn_net_set_tracker)";
+    CHECK(n->track_K >= 1) << "tracker_state: no tracked call has succeeded since the tracker was set or reset: the number of slots is not fixed yet";
+    const size_t need = mscnn_tracks_state_bytes(n->track_K, n->track_max);
+    CHECK(state_host != nullptr && bytes >= need) << "tracker_state: a buffer of " << bytes << " bytes, " << n->track_K << " slots x " << n->track_max
+                                                   << " tracks need " << need;
+    hipStream_t st = (hipStream_t)Caffe::stream();
+    HIP_CHECK(hipMemcpyAsync(state_host, n->track_state[n->track_cur].get(), need, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+  });
+}
+
+int mscnn_net_detect_tracks(mscnn_net* n, int* ids_host, int cap, const int* seg_dets) {
+  return guarded([&] {
+    CHECK(n != nullptr);
+    CHECK(n->tracks_valid) << "detect_tracks: the last detect call did not run the tracker (mscnn_net_set_tracker was off, the call failed, "
+                              "or there was none)";
+    CHECK(seg_dets != nullptr) << "detect_tracks: null seg_dets";
+    const size_t S = n->track_seg_dets.size();
+    for (size_t s = 0; s < S; ++s)
+      CHECK_EQ(seg_dets[s], n->track_seg_dets[s]) << "detect_tracks: segment " << s << ": seg_dets " << seg_dets[s] << ", that call returned "
+                                                  << n->track_seg_dets[s];
+    const size_t D = n->track_ids.size();
+    CHECK_LE(D, (size_t)(cap < 0 ? 0 : cap)) << "detect_tracks: the buffer holds " << cap << " ids, that call returned " << D << " detections";
+    CHECK(D == 0 || ids_host) << "detect_tracks: null id buffer";
+    if (D) std::memcpy(ids_host, n->track_ids.data(), D * sizeof(int));
+  });
+}
+
+// The single-segment and the asynchronous forms leave no place for a frame's track ids: refused while the tracker is on, so that no
+// frame of the stream goes by untracked without a word.
+static void track_refuses(const mscnn_net* n, const char* name) {
+  CHECK(!n->track_on) << name << ": refused while the tracker is on (set_tracker high_thr " << n->track.high_thr
+                      << "): only detect_multi, detect_cascade_multi and detect_merge_end step the tracks; turn the tracker off first";
+}
+// K of a tracked call against the K the first call after a reset fixed; before anything is enqueued
+static void track_slots_checked(const mscnn_net* n, const char* name, int K) {
+  CHECK(!n->track_on || n->track_K == 0 || n->track_K == K)
+      << name << ": " << K << " slots per frame, the tracker's table was made for " << n->track_K
+      << " by the first call after its reset (mscnn_net_tracker_reset starts a new stream)";
+}
+// mscnn_tracks_update_fwd behind the pack of T frames x K slots with pack_rows rows at `pack` (device-addressable), ids to ids_dev:
+// reads the committed table, writes the other one.  The first call after a reset makes and resets the tables, on the same stream.
+static void track_enqueue(mscnn_net* n, const char* name, int T, int K, const void* pack, int pack_rows, int* ids_dev) {
+  track_slots_checked(n, name, K);
+  hipStream_t st = (hipStream_t)Caffe::stream();
+  const size_t bytes = mscnn_tracks_state_bytes(K, n->track_max);
+  CHECK_GT(bytes, 0u) << name << ": the tracker's table for " << K << " slots x " << n->track_max << " tracks";
+  if (n->track_K == 0) {
+    for (caffe::DeviceBuffer& b : n->track_state) b.Reserve(bytes);
+    MSCNN_CHECK(mscnn_tracks_state_reset(n->track_state[n->track_cur].get(), K, n->track_max, st));
+  }
+  MSCNN_CHECK(mscnn_tracks_update_fwd(&n->track, T, K, pack, pack_rows, n->track_state[n->track_cur].get(),
+                                      n->track_state[n->track_cur ^ 1].get(), n->track_max, ids_dev, st));
+}
+// the call has succeeded: the table it wrote is the committed one
+static void track_commit(mscnn_net* n, int K) { n->track_cur ^= 1; n->track_K = K; }
 
 size_t mscnn_net_detect_pack_bytes(int cap) {
   const size_t rows = (size_t)(cap > 0 ? cap : 1);
@@ -736,6 +851,7 @@ static void image_rows(mscnn_net* n, int image, int* row0, int* rows) {
 int mscnn_net_detect_device(mscnn_net* n, const mscnn_detect_params* p, int cap, const void** pack_dev) {
   return guarded([&] {
     CHECK(pack_dev != nullptr);
+    track_refuses(n, "detect_device");
     detect_into_pack(n, p, cap, nullptr, true);
     *pack_dev = n->det_pack.get();
   });
@@ -744,6 +860,7 @@ int mscnn_net_detect_device(mscnn_net* n, const mscnn_detect_params* p, int cap,
 // ---- the final stage of a STREAM of frames: frame i's detections travel to the host under frame i + 1's trunk ----------------------
 int mscnn_net_detect_begin(mscnn_net* n, const mscnn_detect_params* p, int cap) {
   return guarded([&] {
+    track_refuses(n, "detect_begin");
     CHECK(n->slots_inflight < 2) << "detect_begin: two frames already in flight (call mscnn_net_detect_end)";
     mscnn_net::Slot& sl = n->slot[n->slot_head];
     detect_into_pack(n, p, cap, nullptr, true, 0, -1, &sl.pack);      // (a device pack per slot: its copy may still run when the next frame's stage starts)
@@ -809,6 +926,7 @@ int mscnn_net_detect(mscnn_net* n, const mscnn_detect_params* p, double* dets_ho
                      int* num_rois) {
   return guarded([&] {
     CHECK(p && dets_host && num_dets);
+    track_refuses(n, "detect");
     // single-GPU form: the pack is sized by this image's ROI count (16 + 44 R bytes) and -- round 6 -- lives in host-coherent pinned
     // memory that the final stage's kernels write directly (they only ever store into the pack): no D2H copy behind them, the host
     // waits for the stream and reads.  (An in-stream copy cost ~11 us of copy-engine start-up + its own time per frame:
@@ -851,6 +969,7 @@ int mscnn_net_detect_image(mscnn_net* n, const mscnn_detect_params* p, int image
                            int* num_dets, int* num_rois) {
   return guarded([&] {
     CHECK(p && dets_host && num_dets);
+    track_refuses(n, "detect_image");
     int row0 = 0, rows = 0, R = 0;
     image_rows(n, image, &row0, &rows);
     if (n->net->HandoffRecover()) image_rows(n, image, &row0, &rows);      // (image_rows synchronised the stream: see mscnn_net_handoff_state)
@@ -1010,18 +1129,26 @@ static bool detect_multi_into_pack(mscnn_net* n, const mscnn_detect_params* p, i
 // returns R_all (the pack gets K R_all rows); into_pack(pack rows, pack_at, &pack): segments_into_pack's result.
 static void detect_segments_blocking(mscnn_net* n, const char* name, int num_images, int K, const std::function<int()>& rows_all,
                                      const std::function<bool(int, char*, char**)>& into_pack, double* dets_host, int* ids_host, int cap,
-                                     int* seg_dets, int* image_rois) {
+                                     int* seg_dets, int* image_rois, bool tracked = false) {
   hipStream_t st = (hipStream_t)Caffe::stream();
   const int S = num_images * K;
   int pcap = 0;
+  // the tracker (mscnn_net_set_tracker): the images are consecutive frames of the stream; the update runs behind the pack on the same
+  // stream, its ids go behind the pack in the same pinned block and come over with it
+  const bool track = tracked && n->track_on;
+  if (tracked) n->tracks_valid = false;
+  if (track) track_slots_checked(n, name, K);
+  size_t ids_at = 0;
   auto run = [&]() {
     pcap = K * rows_all();
     const size_t total = mscnn_multi_pack_layout_of(S, pcap).total;
-    ensure_det_host(n, total);
+    ids_at = (total + 15) / 16 * 16;
+    ensure_det_host(n, track ? ids_at + (size_t)(pcap > 0 ? pcap : 1) * sizeof(int) : total);
     *static_cast<volatile int*>(n->det_host) = -1;      // the header's first word (S): the kernels must have written it
     char* pack = nullptr;
-    if (!into_pack(pcap, static_cast<char*>(n->det_host_dev), &pack))
-      HIP_CHECK(hipMemcpyAsync(n->det_host, pack, total, hipMemcpyDeviceToHost, st));
+    const bool there = into_pack(pcap, static_cast<char*>(n->det_host_dev), &pack);
+    if (track) track_enqueue(n, name, num_images, K, pack, pcap, reinterpret_cast<int*>(static_cast<char*>(n->det_host_dev) + ids_at));
+    if (!there) HIP_CHECK(hipMemcpyAsync(n->det_host, pack, total, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
   };
   run();
@@ -1034,6 +1161,18 @@ static void detect_segments_blocking(mscnn_net* n, const char* name, int num_ima
   }
   const int rc = mscnn_net_unpack_detections_multi(n->det_host, num_images, K, pcap, dets_host, ids_host, cap, seg_dets, image_rois);
   CHECK_EQ(rc, 0) << g_err;
+  if (track) {      // the call has succeeded: commit the table, keep the ids of the detections just returned, in their order
+    track_commit(n, K);
+    const int* th = reinterpret_cast<const int*>(static_cast<const char*>(n->det_host) + ids_at);
+    n->track_ids.clear();
+    for (int s = 0; s < S; ++s) {
+      const int* e = hdr + MSCNN_MULTI_PACK_WORDS * (size_t)(1 + s);
+      const size_t slot = mscnn_multi_pack_slot(K, e[2], s % K, e[1]);
+      n->track_ids.insert(n->track_ids.end(), th + slot, th + slot + seg_dets[s]);
+    }
+    n->track_seg_dets.assign(seg_dets, seg_dets + S);
+    n->tracks_valid = true;
+  }
 }
 
 size_t mscnn_net_detect_multi_pack_bytes(int num_images, int num_classes, int cap) {
@@ -1044,6 +1183,7 @@ int mscnn_net_detect_multi_device(mscnn_net* n, const mscnn_detect_params* p, in
                                   const void** pack_dev) {
   return guarded([&] {
     CHECK(pack_dev != nullptr);
+    track_refuses(n, "detect_multi_device");
     char* pack = nullptr;
     detect_multi_into_pack(n, p, num_images, num_classes, cap, nullptr, &pack);
     *pack_dev = pack;
@@ -1106,7 +1246,7 @@ int mscnn_net_detect_multi(mscnn_net* n, const mscnn_detect_params* p, int num_i
           return n->net->blob_by_name("proposals_score")->num();
         },
         [&](int pcap, char* pack_at, char** pack) { return detect_multi_into_pack(n, p, num_images, num_classes, pcap, pack_at, pack); },
-        dets_host, ids_host, cap, seg_dets, image_rois);
+        dets_host, ids_host, cap, seg_dets, image_rois, true);
   });
 }
 
@@ -1227,6 +1367,7 @@ int mscnn_net_detect_cascade(mscnn_net* n, const mscnn_detect_params* p, float d
                              const char* proposal_blob, double* dets_host, int* ids_host, int cap, int* num_dets, int* num_rois) {
   return guarded([&] {
     CHECK(p && dets_host && num_dets && bbox_blob && prob_blob && proposal_blob);
+    track_refuses(n, "detect_cascade");
     for (const char* b : {bbox_blob, prob_blob, proposal_blob}) CHECK(n->net->has_blob(b)) << "Unknown blob name " << b;
     auto boxes = n->net->blob_by_name(bbox_blob);
     auto prob = n->net->blob_by_name(prob_blob);
@@ -1328,6 +1469,7 @@ int mscnn_net_detect_cascade_multi_device(mscnn_net* n, const mscnn_detect_param
                                           float det_thr, int cap, const void** pack_dev) {
   return guarded([&] {
     CHECK(pack_dev != nullptr) << "detect_cascade_multi_device: null pointer";
+    track_refuses(n, "detect_cascade_multi_device");
     const CascadeBlobs b = cascade_blobs(n, num_outputs, bbox_blobs, prob_blobs, proposal_blobs);
     const auto desc = cascade_descs(n, p, num_images, num_outputs, num_classes, b, cap);
     char* pack = nullptr;
@@ -1351,7 +1493,7 @@ int mscnn_net_detect_cascade_multi(mscnn_net* n, const mscnn_detect_params* p, i
           return b.R_all;
         },
         [&](int pcap, char* pack_at, char** pack) { return segments_into_pack(n, b.src, desc, num_images, num_classes, det_thr, pcap, pack_at, pack); },
-        dets_host, ids_host, cap, seg_dets, image_rois);
+        dets_host, ids_host, cap, seg_dets, image_rois, true);
   });
 }
 
@@ -1556,6 +1698,7 @@ int mscnn_net_detect_merge_end(mscnn_net* n, double* dets_host, int* pass_host, 
   return guarded([&] {
     mscnn_net::Merge& m = n->merge;
     n->sequences_valid = false;      // (whatever happens from here on: detect_merge_sequences answers for THIS _end only)
+    n->tracks_valid = false;         // (and detect_tracks)
     CHECK(m.open) << "detect_merge_end: no merge is open (call mscnn_net_detect_merge_begin first)";
     m.open = false;      // (whatever happens from here on: the merge is closed)
     // (the setting may have been turned on behind _begin: the op's own refusal of the shape, made here so that it names the value)
@@ -1571,7 +1714,13 @@ int mscnn_net_detect_merge_end(mscnn_net* n, double* dets_host, int* pass_host, 
     const bool seq = n->seq.link_thr != 0.0;      // Seq-NMS (mscnn_net_set_seq_nms): the lists are the frames of one clip; the same pack,
                                                   // and the sequence ids where WBF has its member counts (the two are never on together)
     const size_t members_at = (total + 15) / 16 * 16;
-    ensure_det_host(n, (wbf || seq) ? members_at + (size_t)S * m.cand_cap * sizeof(int) : total);
+    // the tracker (mscnn_net_set_tracker; never on together with WBF): the lists are consecutive frames of the stream; its ids go
+    // behind the pack too, behind Seq-NMS's sequence ids when that is on
+    const bool track = n->track_on;
+    if (track) track_slots_checked(n, "detect_merge_end", m.slots);
+    const size_t per_row = (size_t)S * m.cand_cap * sizeof(int);
+    const size_t tracks_at = seq ? (members_at + per_row + 15) / 16 * 16 : members_at;
+    ensure_det_host(n, track ? tracks_at + per_row : (wbf || seq) ? members_at + per_row : total);
     *static_cast<volatile int*>(n->det_host) = -1;      // the header's first word: the kernels must have written it
     const bool soft = n->soft.method != 0;      // Soft-NMS (mscnn_net_set_soft_nms) in place of the hard merge: the same pack
     const bool matrix = n->matrix.method != 0;      // Matrix NMS (mscnn_net_set_matrix_nms), likewise; never on together with soft
@@ -1597,6 +1746,9 @@ int mscnn_net_detect_merge_end(mscnn_net* n, double* dets_host, int* pass_host, 
       const mscnn_vote_params vote = {n->vote_thr};
       MSCNN_CHECK(mscnn_detections_merge_vote_fwd(&vote, S, m.cand.get(), m.cand_cap, n->det_host_dev, st));
     }
+    if (track)
+      track_enqueue(n, "detect_merge_end", m.images, m.slots, n->det_host_dev, S * m.cand_cap,
+                    reinterpret_cast<int*>(static_cast<char*>(n->det_host_dev) + tracks_at));
     HIP_CHECK(hipStreamSynchronize(st));
     // A stream-K hand-off that timed out in one of the forwards of this merge can not be answered by a re-run here: the input blob
     // holds the last forward only.  As mscnn_net_detect_end: whole tiles from now on, and the caller submits the forwards again.
@@ -1618,6 +1770,14 @@ int mscnn_net_detect_merge_end(mscnn_net* n, double* dets_host, int* pass_host, 
       for (int s = 0; s < S; ++s) n->seq_ids.insert(n->seq_ids.end(), qh + (size_t)s * m.cand_cap, qh + (size_t)s * m.cand_cap + seg_dets[s]);
       n->seq_seg_dets.assign(seg_dets, seg_dets + S);
       n->sequences_valid = true;
+    }
+    if (track) {      // the call has succeeded: commit the table, keep the track ids of the detections just returned (mscnn_net_detect_tracks)
+      track_commit(n, m.slots);
+      const int* th = reinterpret_cast<const int*>(static_cast<const char*>(n->det_host) + tracks_at);
+      n->track_ids.clear();
+      for (int s = 0; s < S; ++s) n->track_ids.insert(n->track_ids.end(), th + (size_t)s * m.cand_cap, th + (size_t)s * m.cand_cap + seg_dets[s]);
+      n->track_seg_dets.assign(seg_dets, seg_dets + S);
+      n->tracks_valid = true;
     }
   });
 }

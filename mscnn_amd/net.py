@@ -38,6 +38,19 @@ class PreprocessView(C.Structure):
     _fields_ = [("frame", C.c_int), ("x0", C.c_int), ("y0", C.c_int), ("w", C.c_int), ("h", C.c_int), ("flip_x", C.c_int)]
 
 
+class TrackParams(C.Structure):
+    """mscnn_track_params (include/mscnn_net.h): the tracker's thresholds, motion (1 none, 2 linear), max_age and min_hits."""
+    _fields_ = [("high_thr", C.c_double), ("low_thr", C.c_double), ("new_thr", C.c_double), ("match_thr", C.c_double),
+                ("match_thr_low", C.c_double), ("vel_gain", C.c_double), ("motion", C.c_int), ("max_age", C.c_int), ("min_hits", C.c_int)]
+
+
+TRACK_MOTIONS = {"none": 1, "linear": 2}
+# mscnn_track_record and a slot's header (include/mscnn_hip.h: mscnn_tracks_state_layout_of)
+TRACK_RECORD = np.dtype([("box", "<f8", 4), ("obs", "<f8", 4), ("vel", "<f8", 2), ("score", "<f8"), ("id", "<i4"), ("hits", "<i4"),
+                         ("misses", "<i4"), ("confirmed", "<i4")])
+TRACKS_HEADER_WORDS = 8
+
+
 NMS_TYPES = ("maxg", "max", "ms", "cover", "none")      # (the last three exist to be refused by name)
 OVR_DNMS = ("union", "min")
 
@@ -118,6 +131,8 @@ def lib():
             "mscnn_net_detect_merge_members": [vp, vp, ci, vp],
             "mscnn_net_set_seq_nms": [vp, C.c_double, C.c_double, ci, ci, ci], "mscnn_net_get_seq_nms": [vp, vp, vp, vp, vp, vp],
             "mscnn_net_detect_merge_sequences": [vp, vp, ci, vp],
+            "mscnn_net_set_tracker": [vp, vp, ci], "mscnn_net_get_tracker": [vp, vp, vp, vp, vp], "mscnn_net_tracker_reset": [vp],
+            "mscnn_net_detect_tracks": [vp, vp, ci, vp], "mscnn_net_tracker_state": [vp, vp, C.c_size_t],
         }
         for name, args in sig.items():
             getattr(L, name).argtypes = args
@@ -617,6 +632,73 @@ class Net:
             return None
         return dict(link_thr=lt.value, score_thr=st.value, top_k=tk.value, rescore={1: "avg", 2: "max"}[rs.value], max_out=mo.value)
 
+    def set_tracker(self, high_thr=0.5, low_thr=0.1, new_thr=None, match_thr=0.3, match_thr_low=0.5, motion="linear", vel_gain=0.5,
+                    max_age=30, min_hits=1, max_tracks=256):
+        """mscnn_net_set_tracker: from now on detect_multi, detect_cascade_multi and detect_merge_end step a table of tracks per slot
+        behind their pack (mscnn_tracks_update_fwd: BYTE's two passes -- detections with a score >= high_thr first, overlap >
+        match_thr, then those >= low_thr against the confirmed tracks seen in the frame before, overlap > match_thr_low --, motion
+        "linear" = a constant-velocity prediction of the centre smoothed by vel_gain, "none" = the box stays; an unmatched detection
+        >= new_thr (None: high_thr) starts a track, a track is shown once it has min_hits hits and dies after max_age missed frames),
+        and detect_tracks() gives a persistent id per detection.  The images of a call, or the frames of a merge, are consecutive
+        frames of the stream.  high_thr None = off (the default).  A successful call starts a fresh table (ids from 1).  Refused while
+        WBF is on; a refused value fails naming it and the setting stays as it was.  While it is on the single-segment and asynchronous
+        detect forms are refused."""
+        if high_thr is None:
+            _check(lib().mscnn_net_set_tracker(self._h, None, 0))
+            return
+        m = TRACK_MOTIONS.get(motion, motion) if isinstance(motion, str) else motion
+        if isinstance(m, str):
+            raise NetError(f"set_tracker: motion {motion!r} is none of 'none', 'linear'")
+        tp = TrackParams(float(high_thr), float(low_thr), float(high_thr if new_thr is None else new_thr), float(match_thr),
+                         float(match_thr_low), float(vel_gain), int(m), int(max_age), int(min_hits))
+        _check(lib().mscnn_net_set_tracker(self._h, C.byref(tp), int(max_tracks)))
+
+    def _tracker(self):
+        on, tp, mt, K = C.c_int(), TrackParams(), C.c_int(), C.c_int()
+        _check(lib().mscnn_net_get_tracker(self._h, C.byref(on), C.byref(tp), C.byref(mt), C.byref(K)))
+        return on.value, tp, mt.value, K.value
+
+    def get_tracker(self):
+        """mscnn_net_get_tracker: None = off, else dict(high_thr, low_thr, new_thr, match_thr, match_thr_low, motion, vel_gain, max_age,
+        min_hits, max_tracks)."""
+        on, tp, mt, _ = self._tracker()
+        if not on:
+            return None
+        return dict(high_thr=tp.high_thr, low_thr=tp.low_thr, new_thr=tp.new_thr, match_thr=tp.match_thr, match_thr_low=tp.match_thr_low,
+                    motion={1: "none", 2: "linear"}[tp.motion], vel_gain=tp.vel_gain, max_age=tp.max_age, min_hits=tp.min_hits, max_tracks=mt)
+
+    def tracker_reset(self):
+        """mscnn_net_tracker_reset: a new stream -- the next tracked call starts with an empty table and id 1, and fixes K again."""
+        _check(lib().mscnn_net_tracker_reset(self._h))
+
+    def detect_tracks(self):
+        """mscnn_net_detect_tracks: after a detect_multi, detect_cascade_multi or detect_merge_end that ran the tracker (set_tracker),
+        the track id of every detection it returned: [[ids[D] int32 per slot] per frame], in the order of its dets; 0 = no confirmed
+        track.  An error when the last of those calls ran no tracker."""
+        B, K, seg = getattr(self, "_track_seg", None) or (1, 1, np.zeros(1, np.int32))
+        D = int(seg.sum())
+        ids = np.zeros(max(D, 1), np.int32)
+        _check(lib().mscnn_net_detect_tracks(self._h, ids.ctypes.data_as(C.c_void_p), D, seg.ctypes.data_as(C.c_void_p)))
+        ends = np.cumsum(seg)
+        return [[ids[ends[i * K + k] - seg[i * K + k]:ends[i * K + k]].copy() for k in range(K)] for i in range(B)]
+
+    def tracker_state(self, raw=False):
+        """mscnn_net_tracker_state: the committed table, one dict per slot -- n, next_id, frame, dropped, skipped and tracks = the
+        first n records (a numpy record array: box, obs, vel, score, id, hits, misses, confirmed).  raw: the table's bytes (uint8)."""
+        _, _, mt, K = self._tracker()
+        slot = 4 * TRACKS_HEADER_WORDS + mt * TRACK_RECORD.itemsize
+        buf = np.zeros((max(K, 1) * slot + 15) // 16 * 16, np.uint8)
+        _check(lib().mscnn_net_tracker_state(self._h, buf.ctypes.data_as(C.c_void_p), buf.size))
+        if raw:
+            return buf
+        out = []
+        for k in range(K):
+            h = buf[k * slot:k * slot + 4 * TRACKS_HEADER_WORDS].view(np.int32)
+            at = k * slot + 4 * TRACKS_HEADER_WORDS
+            recs = buf[at:at + int(h[0]) * TRACK_RECORD.itemsize].view(TRACK_RECORD).copy()
+            out.append(dict(n=int(h[0]), next_id=int(h[1]), frame=int(h[2]), dropped=int(h[3]), skipped=int(h[4]), tracks=recs))
+        return out
+
     @staticmethod
     def _params(cls_id, ratios, org_hw, bbox_mean, bbox_std, proposal_thr, nms_overlap):
         p = DetectParams()
@@ -700,6 +782,7 @@ class Net:
         _check(lib().mscnn_net_detect_cascade_multi(self._h, p, B, O, Cn, bb, pb, qb, det_thr, dets.ctypes.data_as(C.c_void_p),
                                                     ids.ctypes.data_as(C.c_void_p), cap, seg.ctypes.data_as(C.c_void_p),
                                                     rois.ctypes.data_as(C.c_void_p)))
+        self._track_seg = (B, O * Cn, seg[:B * O * Cn].copy())
         flat = _split_segments(dets, ids, seg, B, O * Cn)
         return [[row[o * Cn:(o + 1) * Cn] for o in range(O)] for row in flat], rois[:B].tolist()
 
@@ -735,6 +818,7 @@ class Net:
         seg = np.zeros(B * Cn, np.int32); rois = np.zeros(B, np.int32)
         _check(lib().mscnn_net_detect_multi(self._h, p, B, Cn, dets.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p), cap,
                                             seg.ctypes.data_as(C.c_void_p), rois.ctypes.data_as(C.c_void_p)))
+        self._track_seg = (B, Cn, seg.copy())
         return _split_segments(dets, ids, seg, B, Cn), rois.tolist()
 
     # ---- several forwards of a frame, one NMS (mscnn_net_detect_merge_*)
@@ -800,6 +884,7 @@ class Net:
         _check(lib().mscnn_net_detect_merge_end(self._h, dets.ctypes.data_as(vp), pas.ctypes.data_as(vp), row.ctypes.data_as(vp), cap,
                                                 seg.ctypes.data_as(vp), cands.ctypes.data_as(vp)))
         self._merge_seg = (B, K, seg.copy())
+        self._track_seg = self._merge_seg
         out, o = [], 0
         for i in range(B):
             per = []

@@ -53,6 +53,12 @@ only route there was.  The table gives the boxes that entered, the iterations (s
 whether the op is below the host route by more than the two spreads; the rows are also written to --out
 (profiles/detect_merge_seq.txt).
 
+--track is the tracker behind the final stage (mscnn_tracks_update_fwd), on the clips of --merge --seq: the final stage alone (the hard
+merge of every frame of the clip, its pack read on the host), the final stage + the tracker over the clip's 8 frames in one launch
+behind it (the ids read on the host too), and the final stage + the numpy tracker of tests/track_witness.py on the host's copy of the
+pack -- the only route there was.  The table gives the detections, the tracks and the tracked detections, and every case says whether
+the op is below the host route by more than the two spreads; the rows are also written to --out (profiles/detect_track.txt).
+
 --lib path/to/libmscnn_hip.so runs whatever leg is selected with THAT build's kernels under the Net (it is loaded first, so the Net's
 calls bind to it; the per-range op calls of the batched cascade case's per-call form go through hipapi's own handle and stay this
 build's).  --parent-lib path/to/libmscnn_hip.so repeats the selected leg --rounds times in child processes, this build and
@@ -818,6 +824,95 @@ def merge_seq_leg(a):
             fh.write("\n".join(lines) + "\n")
 
 
+def track_leg(a):
+    """--track: on the clips --merge --seq uses, behind one add of a clip's T frames: the final stage alone (the hard merge, its pack read
+    on the host), the final stage + the tracker (mscnn_tracks_update_fwd over the clip's T frames in one launch behind the merge, on a
+    freshly reset table; the ids read on the host too), and the final stage + the witness-grade numpy tracker of tests/track_witness.py on
+    the host's copy of the pack -- the only route there was.  All forms end with the detections (and ids) on the host; they rotate within
+    a step."""
+    import torch
+    from mscnn_amd import hipapi
+    sys.path.insert(1, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import track_witness as tw
+    kw = dict(high_thr=0.5, low_thr=0.1, match_thr=0.3, match_thr_low=0.5, motion="linear", vel_gain=0.5, max_age=30, min_hits=1)
+    M = 256
+    p, cp = tw.params(**kw), hipapi.track_params(**kw)
+    names = ["final stage alone", "final stage + tracker", "pack to host + numpy tracker"]
+    lines = []
+
+    def say(line):
+        print(line, flush=True)
+        lines.append(line)
+
+    say(f"# the tracker behind the final stage (high_thr {kw['high_thr']:g}, low_thr {kw['low_thr']:g}, match_thr {kw['match_thr']:g}, match_thr_low "
+        f"{kw['match_thr_low']:g}, motion linear, max_tracks {M}) per clip, host wall ms from an idle device to the detections (and ids) on the host "
+        f"(median over {a.steps} steps after {a.warmup} warm-up; {a.rounds} rounds: median of the medians, spread = max - min), regime {a.regime}; "
+        f"dets = the detections of all frames; tracks = the table's tracks after the clip; tracked = the detections with an id > 0")
+    say(f"# {'case':24s} {'T':>2s} {'dets':>5s} {'tracks':>6s} {'tracked':>7s} | " + " | ".join(f"{nm:>28s} {'spread':>6s}" for nm in names) + " | tracker ms")
+    for name in a.case or list(SEQ_CASES):
+        T, K, cap, cand = seq_clip_lists(a, hipapi, name)
+        S = T * K
+        L = hipapi.lib()
+        pack = torch.zeros(L.mscnn_detections_multi_pack_bytes(S, S * cap), dtype=torch.uint8, device="cuda")
+        ws = torch.empty(max(L.mscnn_detections_merge_workspace_bytes(S, cap), 1), dtype=torch.uint8, device="cuda")
+        state = hipapi.tracks_state_new(K, M)
+        ids = torch.zeros(S * cap, dtype=torch.int32, device="cuda")
+
+        def alone():
+            return cand.merge(pack=pack, ws=ws), None, None
+
+        def on_device():
+            out = cand.merge(pack=pack, ws=ws)
+            hipapi.tracks_update(cp, T, K, pack, S * cap, state, M, None, ids)
+            h = ids.cpu().numpy()      # (synchronises: the ids are on the host)
+            return out, [h[s * cap:s * cap + len(d)] for s, (d, _, _) in enumerate(out)], None
+
+        def on_host():
+            out = cand.merge(pack=pack, ws=ws)
+            slots = [tw.new_slot() for _ in range(K)]
+            got = tw.run(slots, [[out[t * K + k][0] for k in range(K)] for t in range(T)], p, M)
+            return out, [got[s // K][s % K] for s in range(S)], slots
+
+        forms = [alone, on_device, on_host]
+        F = len(forms)
+        med = [[] for _ in range(F)]
+        for rnd in range(a.rounds):
+            t = [[] for _ in range(F)]
+            for step in range(a.warmup + a.steps):
+                res = [None] * F
+                for k in range(F):
+                    f = (k + step) % F
+                    hipapi._check(L.mscnn_tracks_state_reset(hipapi._dev(state), K, M, hipapi._stream()))      # (untimed: every clip starts a stream)
+                    torch.cuda.synchronize()      # (untimed: every form starts on an idle device)
+                    t0 = time.perf_counter()
+                    res[f] = forms[f]()
+                    dt = time.perf_counter() - t0
+                    if step >= a.warmup:
+                        t[f].append(dt)
+                assert all(np.array_equal(x, y) for x, y in zip(res[1][1], res[2][1])), (name, step)      # the op against the host form, bit for bit
+            for f in range(F):
+                med[f].append(1e3 * float(np.median(t[f])))
+        dets = sum(len(d) for d, _, _ in res[0][0])
+        tracks = sum(sl["n"] for sl in res[2][2])
+        tracked = sum(int(np.count_nonzero(i)) for i in res[1][1])
+        m = [float(np.median(v)) for v in med]
+        sp = [max(v) - min(v) for v in med]
+        say(f"  {name:24s} {T:2d} {dets:5d} {tracks:6d} {tracked:7d} | " + " | ".join(f"{m[f]:28.3f} {sp[f]:6.3f}" for f in range(F)) + f" | {m[1] - m[0]:10.3f}")
+        say(f"# {name}: (final stage + tracker) - final stage alone = {m[1] - m[0]:.3f} ms per clip of {T} frames; + tracker / + numpy tracker = {m[1] / m[2]:.3f} "
+            f"({'the op is below' if m[1] + sp[1] < m[2] - sp[2] else 'the op is NOT below'} the host route by more than the two spreads)")
+    say("# python tools/bench_final_stage.py --track" + f" --steps {a.steps} --warmup {a.warmup} --rounds {a.rounds}: MI355X (gfx950), one GPU, seeded weights; a "
+        "clip is ONE forward of T = 8 images, frame t the seeded synthetic frame shifted 4 t pixels (a panning camera); the forward and the add call are "
+        "not timed, the table is reset before every timed form.  The tracker's column is a difference of two host wall times: its launch is enqueued "
+        "behind the read of the pack, so it holds a second synchronisation and the copy of the id buffer (one int32 per pack row) as well.")
+    say("# every step asserts that the op's ids equal the host form's bit for bit.")
+    say("# NOT measured: the kernel alone (device events or a profiler), one frame per call (a stream), more than one class (slots run side by side, one "
+        "workgroup each), tables near max_tracks = 1024, the Net calls and the drivers end to end, real video, accuracy (no labels).")
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+
 def use_lib(path):
     """The kernels of another build of libmscnn_hip.so under this build's Net: loaded first and globally, the Net library's calls bind
     to it (checked on one final-stage symbol)."""
@@ -879,8 +974,10 @@ ap.add_argument("--wbf", action="store_true", help="with --merge: the hard merge
                 "walked candidate; the rows also go to --out")
 ap.add_argument("--seq", action="store_true", help="with --merge: per clip of 8 frames the hard merge, the Seq-NMS op (avg, top_k 300 and 1024) "
                 "and every candidate list to the host + a vectorised numpy Seq-NMS; us per iteration; the rows also go to --out")
-ap.add_argument("--out", default=None, help="--merge --wbf / --merge --seq: the file the rows are written to (default: "
-                "profiles/detect_merge_wbf.txt / profiles/detect_merge_seq.txt; '' = none)")
+ap.add_argument("--track", action="store_true", help="on the clips of --merge --seq: the final stage alone, the final stage + the tracker op, and "
+                "the pack on the host + the numpy tracker of tests/track_witness.py; the rows also go to --out")
+ap.add_argument("--out", default=None, help="--merge --wbf / --merge --seq / --track: the file the rows are written to (default: "
+                "profiles/detect_merge_wbf.txt / profiles/detect_merge_seq.txt / profiles/detect_track.txt; '' = none)")
 ap.add_argument("--soft-thr", type=float, default=0.001, help="--merge --soft / --matrix / --wbf: the score threshold of Soft-NMS and Matrix NMS")
 ap.add_argument("--rounds", type=int, default=3, help="--merge / --parent-lib: repetitions of the whole measurement")
 ap.add_argument("--lib", default="", help="run with the kernels of this libmscnn_hip.so under the Net")
@@ -898,12 +995,16 @@ ap.add_argument("--nms-type", default="maxg", choices=("maxg", "max"), help="bbN
 ap.add_argument("--ovr-dnm", default="union", choices=("union", "min"), help="bbNms's overlap denominator for both forms")
 a = ap.parse_args()
 if a.out is None:
-    a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "detect_merge_seq.txt" if a.seq else "detect_merge_wbf.txt")
+    a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                         "detect_track.txt" if a.track else "detect_merge_seq.txt" if a.seq else "detect_merge_wbf.txt")
 if a.parent_lib:
     ab_leg(a, sys.argv[1:])
     sys.exit(0)
 if a.lib:
     use_lib(a.lib)
+if a.track:
+    track_leg(a)
+    sys.exit(0)
 if a.merge and a.vote is not None:
     merge_vote_leg(a)
     sys.exit(0)

@@ -54,6 +54,13 @@ list_of naming its frames' places in the clip, the views of --flip / --scales / 
 and --vote serve it; not together with --soft-nms, --matrix-nms or --wbf.  As tools/run_mscnn_detection.py; the result files keep their
 format, --tubelets-out adds DIR/<comp_id>_<class>_<output>.txt with rows [image_index sequence x y w h score]; no pin on the reference,
 accuracy not evaluated.
+--track [--track-high T] [--track-low T] [--track-match THR] [--track-motion none|linear] [--track-max-age N] [--track-min-hits N]
+[--tracks-out DIR]: a persistent track id for every detection across the frames of the run, taken as consecutive frames of one stream
+(Net.set_tracker; BYTE's two association passes on the device behind every detect_cascade_multi and detect_merge_end, a table of
+tracks per (output, class)); alone, with --batch, with --orig-size (the boxes are original-image
+pixels whatever the input size) and with every merge flag but --wbf.  As tools/run_mscnn_detection.py; the result files are unchanged, --tracks-out adds
+DIR/<comp_id>_<class>_<output>.txt with rows [image_index track x y w h score], track 0 = no confirmed track; no pin on the reference,
+accuracy not evaluated.
 
 Everything here is host glue over calls the test-suite covers one by one (Net.set_images, forward, detect_cascade_multi,
 reshape_input, kitti.write_detections_dlm)."""
@@ -152,8 +159,8 @@ def main(argv=None):
     import numpy as np
     import torch
     from mscnn_amd import kitti, net as mnet, synth, zoo
-    from run_mscnn_detection import (apply_merge_settings, list_images, load_rgb_u8, merge_cand_cap, merge_passes, names_for, one_forward_merge,
-                                     run_frame_views, run_seq_clips, seq_on, views_per_frame, write_tubelets)
+    from run_mscnn_detection import (apply_merge_settings, apply_track_setting, frame_tracks, list_images, load_rgb_u8, merge_cand_cap, merge_passes,
+                                     names_for, one_forward_merge, run_frame_views, run_seq_clips, seq_on, track_on, views_per_frame, write_tubelets)
 
     if a.prototxt:
         text = open(a.prototxt).read()
@@ -175,6 +182,7 @@ def main(argv=None):
         net.set_precision(a.precision)
     if a.roialign_one_pass:
         net.set_roialign_one_pass(True)
+    apply_track_setting(net, a)                                               # --track: sticky, every final stage below steps the tracks
     out_names = [o for o in a.outputs.split(",") if o] or default_outputs(net.blob_names)
     outputs = [OUTPUT_BLOBS[o] for o in out_names]
     for o, triple in zip(out_names, outputs):
@@ -215,13 +223,16 @@ def main(argv=None):
                                      **({} if list_of is None else dict(list_of=list_of)))
 
     tubes = {key: [] for key in results}
+    tracks = {key: [] for key in results}                                     # --track: per frame the track ids of the key's detections
     if seq_on(a):
         frames, shape, used = run_seq_clips(a, net, text, files, tuple(shape[2:]), shape, len(outputs) * len(cls_ids), load_frame,
                                             lambda params, mviews, list_of: add(params, mviews, list_of))
-        for dets, seqs in frames:
+        for dets, seqs, trks in frames:
             for (o, c) in results:
                 results[(o, c)].append(dets[o * len(cls_ids) + c])
                 tubes[(o, c)].append(seqs[o * len(cls_ids) + c])
+                if trks is not None:
+                    tracks[(o, c)].append(trks[o * len(cls_ids) + c])
     for k, path in enumerate(files if passes else [], start=1):
         img = load_frame(path, k)
         net.detect_merge_begin(1, len(outputs) * len(cls_ids), merge_cand_cap(text, n_fwd, a.merge_cap))
@@ -242,8 +253,11 @@ def main(argv=None):
             net.detect_cascade_merge_add([dict(p, nms_overlap=a.nms_overlap) for p in params], outputs, cls_ids, det_thr=a.det_thr,
                                          views=[dict(flip_x=1)] if flipped else None)
         per_image, _ = net.detect_merge_end()
+        trks = frame_tracks(net, a)
         for (o, c) in results:
             results[(o, c)].append(per_image[0][o * len(cls_ids) + c][0])
+            if trks:
+                tracks[(o, c)].append(trks[0][o * len(cls_ids) + c])
         if k % 100 == 0 or k == len(files):
             what = f"{n_fwd} views per frame, batched" if a.views_batch else f"{n_fwd} forwards per frame"
             print(f"idx {k}/{len(files)}, avgtime={used / k:.4f}s ({what})")
@@ -267,9 +281,12 @@ def main(argv=None):
             blobs = {b: net.get_blob(b) for t in outputs for b in t}
             np.savez(os.path.join(a.dump_blobs, f"group_{g0 // a.batch:04d}.npz"), ratios=np.array([p["ratios"] for p in params], np.float64),
                      org_hw=np.array([p["org_hw"] for p in params], np.float64), **blobs)
+        trks = frame_tracks(net, a)
         for i in range(len(group)):
             for key in results:
                 results[key].append(per_image[i][key[0]][key[1]][0])
+                if trks:
+                    tracks[key].append(trks[i][key[0] * len(cls_ids) + key[1]])
         done += len(group)
         if done // 100 != (done - len(group)) // 100 or done == len(files):
             print(f"idx {done}/{len(files)}, avgtime={used / done:.4f}s")    # :145, per frame
@@ -279,6 +296,10 @@ def main(argv=None):
         print(f"{path}: {sum(len(d) for d in dets)} detections over {len(files)} images")
         if a.tubelets_out:
             write_tubelets(os.path.join(a.tubelets_out, f"{a.comp_id}_{names[cls_ids[c] - 1]}_{out_names[o]}.txt"), dets, tubes[(o, c)])
+        if track_on(a) and a.tracks_out:
+            out = os.path.join(a.tracks_out, f"{a.comp_id}_{names[cls_ids[c] - 1]}_{out_names[o]}.txt")
+            write_tubelets(out, dets, tracks[(o, c)])
+            print(f"{out}: {len(set(int(v) for t in tracks[(o, c)] for v in t) - {0})} tracks over {len(files)} images")
     return 0
 
 

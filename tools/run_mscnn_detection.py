@@ -20,6 +20,8 @@ examples/kitti_result/writeDetForEval.m.
          [--matrix-nms linear|gaussian[:SIGMA]]              # Matrix NMS in its place instead (Net.set_matrix_nms); --soft-thr / --max-dets serve it
          [--wbf [THR]] [--wbf-skip T] [--wbf-conf avg|max] [--wbf-expected N]      # weighted boxes fusion in its place instead (Net.set_wbf)
          [--seq-nms [avg|max]] [--clip T] [--seq-link THR] [--seq-top-k N] [--tubelets-out DIR]      # Seq-NMS over clips of T frames (Net.set_seq_nms)
+         [--track] [--track-high T] [--track-low T] [--track-match THR] [--track-motion none|linear] [--track-max-age N] [--track-min-hits N]
+         [--tracks-out DIR]                                  # track ids across the frames of the run (Net.set_tracker)
   python tools/run_mscnn_detection.py --model kitti_car/mscnn-7s-576 --synthetic 8      # no dataset / weights at hand: the generated
                                                                                         # deploy net, seeded weights, synthetic frames
 
@@ -92,6 +94,19 @@ T out, --seq-top-k N (default 300, at most 1024) bounds the candidates of a fram
 behind it.  Refused together with --soft-nms, --matrix-nms and --wbf.  The result files keep their format; --tubelets-out DIR adds
 DIR/<comp_id>_<class>.txt with rows [image_index sequence x y w h score], `sequence` unique within a clip and class.  No pin on the
 reference, whose scripts run one forward per image and look at no other frame; accuracy was not evaluated (no labels here).
+
+--track gives every detection a persistent track id across the frames of the run, which are taken as consecutive frames of one
+stream in file order (Net.set_tracker, once per run): behind every final stage a table of tracks per class is stepped on the device
+-- BYTE's two passes (Zhang et al., 2022): the detections with a score >= --track-high T (default 0.5) are associated first, IoU
+above --track-match THR (default 0.3), then those >= --track-low T (default 0.1) with the tracks still unmatched; a constant-velocity
+prediction of the centre (--track-motion linear, the default; none: the box stays) in place of the paper's Kalman filter, a greedy
+walk by descending IoU in place of its Hungarian solver.  An unmatched detection over --track-high starts a track, a track lives
+through --track-max-age N missed frames (default 30) and shows its id from its --track-min-hits N-th hit on (default 1).  Alone the
+frames run in groups of one through Net.detect_multi; with --batch a group is B consecutive frames; with --scales / --flip / --tiles /
+--vote / --soft-nms / --matrix-nms the tracker runs behind the frame's merge, with --seq-nms behind the clip's (the ids live on over
+the clip boundary).  Refused together with --wbf, --rois-in and --proposals-only.  The result files are unchanged; --tracks-out DIR
+adds DIR/<comp_id>_<class>.txt with rows [image_index track x y w h score], track 0 = no confirmed track.  No pin on the reference,
+whose scripts look at no other frame; accuracy was not evaluated (no labels here).
 
 Everything here is host glue over calls the test-suite covers one by one (Net.set_image / set_images / set_image_views, forward,
 detect / detect_multi, detect_merge_*, proposals_multi, kitti.write_*)."""
@@ -210,6 +225,21 @@ def add_merge_flags(ap):
                     "1 .. 1024 (default 300)")
     ap.add_argument("--tubelets-out", default=None, metavar="DIR", help="with --seq-nms: DIR/<comp_id>_<class>.txt with rows [image_index sequence "
                     "x y w h score]; sequence is unique within a clip and class")
+    ap.add_argument("--track", action="store_true", help="track ids across the frames of the run (Net.set_tracker): BYTE association on the "
+                    "device behind every final stage -- the frames are taken as consecutive frames of one stream, in file order; alone, with "
+                    "--batch, --seq-nms, --scales, --flip, --tiles, --vote, --soft-nms and --matrix-nms; not with --wbf.  The result files are unchanged")
+    ap.add_argument("--track-high", type=float, default=0.5, metavar="T", help="with --track: detections with a score >= T are associated first and "
+                    "may start a track (default 0.5)")
+    ap.add_argument("--track-low", type=float, default=0.1, metavar="T", help="with --track: detections with a score >= T (and below --track-high) are "
+                    "offered to the tracks the first pass left unmatched (default 0.1)")
+    ap.add_argument("--track-match", type=float, default=0.3, metavar="THR", help="with --track: a detection matches a track when their IoU is above "
+                    "THR (default 0.3)")
+    ap.add_argument("--track-motion", choices=["none", "linear"], default="linear", help="with --track: a track's box stays where it was seen "
+                    "(none) or moves on with its smoothed centre velocity (linear, the default)")
+    ap.add_argument("--track-max-age", type=int, default=30, metavar="N", help="with --track: a track lives through N missed frames (default 30)")
+    ap.add_argument("--track-min-hits", type=int, default=1, metavar="N", help="with --track: a track shows its id from its N-th hit on (default 1)")
+    ap.add_argument("--tracks-out", default=None, metavar="DIR", help="with --track: DIR/<comp_id>_<class>.txt with rows [image_index track x y w h "
+                    "score]; track 0 = no confirmed track")
     ap.add_argument("--soft-thr", type=float, default=0.001, metavar="T", help="with --soft-nms: stop picking when the best live score is below T; "
                     "with --matrix-nms: keep the scores >= T (default 0.001)")
     ap.add_argument("--max-dets", type=int, default=0, metavar="N", help="with --soft-nms / --matrix-nms / --wbf: at most N detections per class and "
@@ -237,6 +267,23 @@ def one_forward_merge(a):
 def seq_on(a):
     """--seq-nms: the run goes clip by clip (run_seq_clips), whatever else is set."""
     return getattr(a, "seq_nms", None) is not None
+
+
+def track_on(a):
+    """--track: every final stage of the run steps the tracker (Net.set_tracker)."""
+    return bool(getattr(a, "track", False))
+
+
+def apply_track_setting(net, a):
+    """The sticky tracker setting of the run, once, before its first frame."""
+    if track_on(a):
+        net.set_tracker(high_thr=a.track_high, low_thr=a.track_low, match_thr=a.track_match, motion=a.track_motion, max_age=a.track_max_age,
+                        min_hits=a.track_min_hits)
+
+
+def frame_tracks(net, a):
+    """Behind a detect call of the run: [[ids per slot] per frame of that call] with --track, else None."""
+    return net.detect_tracks() if track_on(a) else None
 
 
 def apply_merge_settings(net, a):
@@ -306,6 +353,18 @@ def check_merge_flags(ap, a):
             ap.error("--seq-nms with --tiles / --views-batch runs one frame's views per forward (drop --batch)")
     elif a.clip != 8 or a.seq_link != 0.5 or a.seq_top_k != 300 or a.tubelets_out is not None:
         ap.error("--clip / --seq-link / --seq-top-k / --tubelets-out belong to --seq-nms")
+    if track_on(a):
+        if a.wbf is not None:
+            ap.error("--track and --wbf exclude each other: the track ids come back where the fusion's member counts do")
+        if not a.track_low <= a.track_high:      # (a NaN fails)
+            ap.error(f"--track-low {a.track_low:g} must not be above --track-high {a.track_high:g}")
+        if not 0.0 <= a.track_match < 1.0:
+            ap.error(f"--track-match {a.track_match:g}: the threshold must lie inside [0, 1)")
+        if a.track_max_age < 0 or a.track_min_hits < 1:
+            ap.error(f"--track-max-age {a.track_max_age} must be >= 0, --track-min-hits {a.track_min_hits} >= 1")
+    elif (a.track_high != 0.5 or a.track_low != 0.1 or a.track_match != 0.3 or a.track_motion != "linear" or a.track_max_age != 30
+          or a.track_min_hits != 1 or a.tracks_out is not None):
+        ap.error("--track-high / --track-low / --track-match / --track-motion / --track-max-age / --track-min-hits / --tracks-out belong to --track")
     if not 0.0 <= a.soft_thr < float("inf"):
         ap.error(f"--soft-thr {a.soft_thr:g}: the threshold must be a finite value >= 0")
     if a.max_dets < 0:
@@ -376,7 +435,7 @@ def run_seq_clips(a, net, text, files, net_hw, shape, slots, load, add):
     (and mirror) one forward per --batch B frames of the clip, added with list_of = the frames' places in the clip -- with --tiles /
     --views-batch the views of every frame, to that frame's list --, one detect_merge_end and its detect_merge_sequences.
     add(params, merge views or None, list_of) is the driver's detect_merge_add.  Returns (per frame of the run ([dets per slot],
-    [sequence ids per slot]), the input's shape now, seconds in forwards)."""
+    [sequence ids per slot], [track ids per slot] or None without --track), the input's shape now, seconds in forwards)."""
     import torch
     passes = merge_passes(a, net_hw)
     by_views = bool(a.tiles or a.views_batch)
@@ -406,14 +465,16 @@ def run_seq_clips(a, net, text, files, net_hw, shape, slots, load, add):
                 add(params, [dict(flip_x=1)] * len(group) if flipped else None, list(range(g0, g0 + len(group))))
         per_image, _ = net.detect_merge_end()
         seqs = net.detect_merge_sequences()
-        out += [([per_image[t][s][0] for s in range(slots)], [seqs[t][s] for s in range(slots)]) for t in range(len(imgs))]
+        trks = frame_tracks(net, a)
+        out += [([per_image[t][s][0] for s in range(slots)], [seqs[t][s] for s in range(slots)], trks[t] if trks else None) for t in range(len(imgs))]
         k = c0 + len(imgs)
         print(f"idx {k}/{len(files)}, avgtime={used / k:.4f}s (clips of {a.clip} frames, {n_fwd} forwards per frame)")
     return out, shape, used
 
 
 def write_tubelets(path, per_frame_dets, per_frame_seq):
-    """--tubelets-out: rows [image_index sequence x y w h score] (1-based index, %.5g as the result files) of one class."""
+    """--tubelets-out, and --tracks-out with the track ids: rows [image_index sequence x y w h score] (1-based index, %.5g as the result
+    files) of one class."""
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "w") as f:
         for i, (dets, seq) in enumerate(zip(per_frame_dets, per_frame_seq), start=1):
@@ -450,6 +511,8 @@ def parse_args(argv=None):
     check_merge_flags(ap, a)
     if (a.scales or a.flip or a.tiles or one_forward_merge(a) or seq_on(a)) and (a.rois_in or a.proposals_out or a.proposals_only):
         ap.error("--scales / --flip / --tiles / --vote / --soft-nms / --matrix-nms merge detections: not with --rois-in, --proposals-out or --proposals-only")
+    if track_on(a) and (a.rois_in or a.proposals_only):
+        ap.error("--track follows the detections of every frame: not with --rois-in (frames without a box run no final stage) or --proposals-only")
     if a.proposals_only and not a.proposals_out:
         ap.error("--proposals-only needs --proposals-out DIR")
     if a.proposals_only and a.rois_in:
@@ -510,12 +573,16 @@ def main(argv=None):
     per_image_props = []
     forward = net.forward_proposals if a.proposals_only else net.forward
     rois = read_rois(a.rois_in, len(files)) if a.rois_in else None
+    apply_track_setting(net, a)
+    a.track_ids = []                                                          # --track: per frame of the run [ids per class]
     if seq_on(a):
         return run_seq(a, net, text, files, names, cls_ids, imgH, imgW, per_class)
     if a.batch > 1:
         return run_batched(a, net, files, names, cls_ids, imgH, imgW, per_class, per_image_props, forward, rois)
     if a.scales or a.flip or a.tiles or one_forward_merge(a):
         return run_merged(a, net, text, files, names, cls_ids, imgH, imgW, per_class)
+    if track_on(a):                                                           # --track alone: groups of one frame through detect_multi
+        return run_batched(a, net, files, names, cls_ids, imgH, imgW, per_class, per_image_props, forward, rois)      # (Net.detect is refused while it is on)
     used = 0.0
     for k, path in enumerate(files, start=1):
         img = load_frame(path, k)
@@ -561,7 +628,8 @@ def run_seq(a, net, text, files, names, cls_ids, imgH, imgW, per_class):
         net.detect_merge_add(p, cls_ids, views=mviews, list_of=list_of)
 
     frames, _, _ = run_seq_clips(a, net, text, files, (imgH, imgW), (1, 3, imgH, imgW), len(cls_ids), load_frame, add)
-    for k, (path, (dets, _)) in enumerate(zip(files, frames), start=1):
+    a.track_ids = [t for _, _, t in frames]
+    for k, (path, (dets, _, _)) in enumerate(zip(files, frames), start=1):
         by_type = {}
         for ci, c in enumerate(cls_ids):
             per_class[c].append(dets[ci])
@@ -571,8 +639,8 @@ def run_seq(a, net, text, files, names, cls_ids, imgH, imgW, per_class):
     finish(a, names, cls_ids, per_class, [], len(files))
     for ci, c in enumerate(cls_ids if a.tubelets_out else []):
         out = os.path.join(a.tubelets_out, f"{a.comp_id}_{names[c - 1]}.txt")
-        write_tubelets(out, [d[ci] for d, _ in frames], [q[ci] for _, q in frames])
-        print(f"{out}: {len(set((k // a.clip, int(v)) for k, (_, q) in enumerate(frames) for v in q[ci]))} tubelets over {len(files)} images")
+        write_tubelets(out, [d[ci] for d, _, _ in frames], [q[ci] for _, q, _ in frames])
+        print(f"{out}: {len(set((k // a.clip, int(v)) for k, (_, q, _) in enumerate(frames) for v in q[ci]))} tubelets over {len(files)} images")
     return 0
 
 
@@ -614,6 +682,7 @@ def run_merged(a, net, text, files, names, cls_ids, imgH, imgW, per_class):
             p = dict(ratios=(H / float(orgH), W / float(orgW)), org_hw=(orgH, orgW), proposal_thr=a.proposal_thr, nms_overlap=a.nms_overlap)
             net.detect_merge_add([p], cls_ids, views=[dict(flip_x=1)] if flipped else None)
         per_image, _ = net.detect_merge_end()
+        a.track_ids += frame_tracks(net, a) or []
         by_type = {}
         for ci, c in enumerate(cls_ids):
             dets = per_image[0][ci][0]
@@ -662,6 +731,7 @@ def run_batched(a, net, files, names, cls_ids, imgH, imgW, per_class, per_image_
             continue
         if ran:
             per_image, _ = net.detect_multi([dict(p, proposal_thr=a.proposal_thr, nms_overlap=a.nms_overlap) for p in params], cls_ids)
+            a.track_ids += frame_tracks(net, a) or []
         else:
             per_image = [[(np.zeros((0, 5)), None)] * len(cls_ids)] * len(group)
         for i, path in enumerate(group):
@@ -685,6 +755,10 @@ def finish(a, names, cls_ids, per_class, per_image_props, n_files):
     if a.proposals_out:
         out = write_proposals(a.proposals_out, a.comp_id, per_image_props)
         print(f"{out}: {sum(len(p) for p in per_image_props)} proposals over {n_files} images")
+    for ci, c in enumerate(cls_ids if track_on(a) and a.tracks_out else []):
+        out = os.path.join(a.tracks_out, f"{a.comp_id}_{names[c - 1]}.txt")
+        write_tubelets(out, per_class[c], [t[ci] for t in a.track_ids])
+        print(f"{out}: {len(set(int(v) for t in a.track_ids for v in t[ci]) - {0})} tracks over {n_files} images")
 
 
 def write_proposals(out_dir, comp_id, per_image_props):
