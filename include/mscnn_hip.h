@@ -281,6 +281,15 @@ MSCNN_API void mscnn_debug_wgemm_handoff_fault(int drop_publish, unsigned spin_l
  * info[8] = {tiles, MT, KI, G, full_q, planes, BN, ragged}.  Returns the number of segments (rows == NULL: count only), -1 when
  * max_rows is too small or the plan has no such GEMM. */
 MSCNN_API long mscnn_debug_wgemm_schedule(const mscnn_conv_plan* plan, int whole_tiles, int* rows, long max_rows, int info[8]);
+/* The plan's class (tests; launches nothing, allocates nothing on a device): every discrete decision the plan holds -- kernel family
+ * and table entry, operand type, the implicit-GEMM kernel's modes (several M tiles, a partial channel chunk, ROI tiles and a ragged
+ * last one, whole tiles / one tile per workgroup / stream-K remainder), the Winograd form (m, nested igemm or wgemm and its tile
+ * shape, several row tiles, whole / split remainder / all split, ragged mode, partial edge tiles, small-map transforms), the head
+ * kernels' chunk size and schedule, and the
+ * can_pool / can_pool_only / publishes_amax / ring / one-launch / Cin = 3 answers -- and nothing that merely scales with the shape.
+ * Two plans of one class run the same kernels in the same modes.  *field_names (may be NULL) receives a static comma-separated list
+ * naming the ints in order.  Returns the number of fields; fills out[] only when n is at least that. */
+MSCNN_API int mscnn_debug_conv_plan_class(const mscnn_conv_plan* plan, int* out, int n, const char** field_names);
 /* fp16-operand InnerProduct (the counterpart of MSCNN_CONV_ALGO_F16; no reference counterpart): w16 = the weights converted
  * once to fp16 [N][K] (mscnn_inner_product_pack_f16, N * K * 2 bytes), x rounded to fp16 on its way into LDS, fp32 accumulate.
  * Needs N >= 64 and K % 8 == 0 (mscnn_inner_product_f16_supported); smaller layers stay on the fp32 entry point. */

@@ -1495,6 +1495,69 @@ extern "C" long mscnn_debug_wgemm_schedule(const mscnn_conv_plan* p, int whole_t
   }
   return mscnn::wgemm_debug_schedule(p->wg, whole_tiles, rows, max_rows);
 }
+// The discrete decisions of a plan: which kernel build runs and in which mode -- nothing that merely scales with the shape.  The
+// fields follow kPlanClassFields (one name per int); host arithmetic on the plan only.
+static const char kPlanClassFields[] =
+    "family,entry,dtype,"
+    "ig_mt_gt1,ig_cin_rem,ig_roi,ig_roi_ragged,ig_sched,"
+    "wino_m,wino_gemm,wg_bm,wg_bn,wg_ck,wino_mt_gt1,wg_split,wg_ragged,ho_rem,wo_rem,small_map,"
+    "head_half,head_sched,"
+    "can_pool,can_pool_only,publishes_amax,wc_use,wf_use,c3";
+enum { kPlanClassN = 27 };
+extern "C" int mscnn_debug_conv_plan_class(const mscnn_conv_plan* p, int* out, int n, const char** field_names) {
+  if (field_names) *field_names = kPlanClassFields;
+  if (!p || !out || n < kPlanClassN) return kPlanClassN;
+  int v[kPlanClassN] = {0};
+  // family: 0 direct, 1 igemm, 2 head, 3 head GEMM over the taps, 4 head with folded columns, 5 split-fp16 head, 6 Winograd,
+  // 7 split-fp16 Winograd, 8 Cin = 3, 9 one-launch F(2x2,3x3), 10 ring kernel.  entry: the family's own table index (-1: none)
+  const mscnn_conv_plan* ig = nullptr;      // the implicit-GEMM plan that launches, if one does
+  int family = 0, entry = -1;
+  if (p->x3h.rows) family = 5;
+  else if (p->hg) { family = p->hg_kw ? 4 : 3; ig = p->hg; entry = p->hg->entry; }
+  else if (p->head.entry >= 0) { family = 2; head_entry_class(p->head, &entry, &v[19]); v[20] = p->head.G >= p->head.total_iters ? 1 : 2; }
+  else if (p->x3.BM) { family = 7; entry = p->x3.BM; }
+  else if (p->wino) { family = 6; if (p->use_wg) entry = p->wg.variant; else { ig = p->wino; entry = p->wino->entry; } }
+  else if (p->c3) family = 8;
+  else if (p->wf_use) family = 9;
+  else if (p->wc_use) { family = 10; entry = p->entry; }
+  else if (p->entry >= 0) { family = 1; ig = p; entry = p->entry; }
+  v[0] = family; v[1] = entry;
+  const char* dt = mscnn_conv2d_plan_dtype(p);
+  v[2] = strcmp(dt, "f16") == 0 ? 1 : strcmp(dt, "f16x3") == 0 ? 2 : 0;
+  if (ig && ig->entry >= 0) {
+    const KernelEntry& k = kTable[ig->entry];
+    const long tiles = (long)ig->MT * ig->NT, rem = tiles - (long)ig->full_q * ig->G;
+    v[3] = ig->MT > 1;
+    v[4] = ig->d.Cin % k.CK != 0;
+    v[5] = k.RH > 0;
+    v[6] = k.RH > 0 && ig->d.N % k.IPT != 0;
+    // 1 whole tiles, several per workgroup; 2 one whole tile per workgroup; 3 whole tiles + a stream-K remainder and fix-up;
+    // 4 stream-K only (no data-parallel phase) and fix-up
+    v[7] = rem == 0 ? (ig->full_q > 1 ? 1 : 2) : (ig->full_q > 0 ? 3 : 4);
+  }
+  if (p->wino || p->x3.BM) {
+    const int m = p->wino_m;
+    v[8] = m;
+    v[9] = p->x3.BM ? 3 : (p->use_wg ? 2 : 1);
+    if (p->wino && p->use_wg) {
+      v[10] = p->wg.BM; v[11] = p->wg.BN; v[12] = p->wg.CK;
+      v[13] = p->wg.MT > 1;
+      // 0 whole tiles; 1 whole rounds, then the last partial round split stream-K style; 2 every tile split (fewer tiles than workgroups)
+      v[14] = (long)p->wg.tiles > (long)p->wg.full_q * p->wg.G ? (p->wg.full_q > 0 ? 1 : 2) : 0;
+      v[15] = p->ragged;
+    }
+    if (p->x3.BM) v[13] = p->x3.MT > 1;
+    v[16] = p->Ho % m != 0;
+    v[17] = p->Wo % m != 0;
+    v[18] = m == 3 && p->d.H * p->d.W <= mscnn::kWino33SmallMapHW;
+  }
+  v[21] = mscnn_conv2d_plan_can_pool(p);
+  v[22] = mscnn_conv2d_plan_can_pool_only(p);
+  v[23] = mscnn_conv2d_plan_publishes_amax(p);
+  v[24] = p->wc_use; v[25] = p->wf_use; v[26] = p->c3;
+  for (int i = 0; i < kPlanClassN; ++i) out[i] = v[i];
+  return kPlanClassN;
+}
 extern "C" int mscnn_conv2d_plan_set_profiling(mscnn_conv_plan* p, int on) {
   MSCNN_REQUIRE(p, "conv plan: null");
   p->profiling = on != 0;

@@ -23,6 +23,8 @@ int headv_forward(const mscnn_conv_desc& d, const HeadPlan& hp, int Ho, int Wo, 
 
 bool head_plan(const mscnn_conv_desc& d, int Ho, int Wo, HeadPlan* hp);
 const char* head_kernel_name(const HeadPlan& hp);
+// the kernel a plan stands for beyond its name (mscnn_debug_conv_plan_class): the full-chunk entry of its shape, half chunks or not
+void head_entry_class(const HeadPlan& hp, int* base_entry, int* half);
 int head_pack(const mscnn_conv_desc& d, const HeadPlan& hp, const float* w, float* packed, hipStream_t st);
 int head_forward(const mscnn_conv_desc& d, const HeadPlan& hp, int Ho, int Wo, const float* x, const float* packed,
                  const float* bias, float* y, void* workspace, size_t workspace_bytes, hipStream_t st);

@@ -392,6 +392,12 @@ const char* head_kernel_name(const HeadPlan& hp) {
   return kHeads[hp.entry].name;
 }
 
+void head_entry_class(const HeadPlan& hp, int* base_entry, int* half) {
+  const bool table = hp.valu < 0 && hp.entry >= 0;
+  *base_entry = table ? hp.entry % kHalf : hp.entry;
+  *half = table && hp.entry >= kHalf ? 1 : 0;
+}
+
 int head_pack(const mscnn_conv_desc& d, const HeadPlan& hp, const float* w, float* packed, hipStream_t st) {
 #ifdef MSCNN_HEAD_VALU_WITNESS
   if (hp.valu >= 0) return headv_pack(d, hp, w, packed, st);

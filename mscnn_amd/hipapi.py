@@ -138,6 +138,7 @@ def lib():
         L.mscnn_conv2d_plan_plane_columns.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.mscnn_debug_wgemm_schedule.restype = C.c_long
         L.mscnn_debug_wgemm_schedule.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_long, C.c_void_p]
+        L.mscnn_debug_conv_plan_class.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.mscnn_conv2d_plan_stage_ms.argtypes = [C.c_void_p, C.c_void_p]
         for f in ("mscnn_conv2d_packed_weight_bytes", "mscnn_conv2d_workspace_bytes"):
             getattr(L, f).restype = C.c_size_t
@@ -340,6 +341,16 @@ class ConvPlan:
         assert got == n
         keys = ("tiles", "MT", "KI", "G", "full_q", "planes", "BN", "ragged")
         return {k: int(info[i]) for i, k in enumerate(keys)}, rows[:n]
+
+    def plan_class(self):
+        """The plan's discrete decisions (mscnn_debug_conv_plan_class) as a dict field name -> int, in the library's field order."""
+        names = C.c_char_p()
+        n = lib().mscnn_debug_conv_plan_class(self._p, None, 0, C.byref(names))
+        out = (C.c_int * n)()
+        assert lib().mscnn_debug_conv_plan_class(self._p, out, n, None) == n
+        fields = names.value.decode().split(",")
+        assert len(fields) == n
+        return {f: int(out[i]) for i, f in enumerate(fields)}
 
     def set_profiling(self, on=True):
         _check(lib().mscnn_conv2d_plan_set_profiling(self._p, int(on)))
