@@ -55,7 +55,8 @@
  *   detections_merge_matrix_fwd  cand, workspace, pack_dev 16: refuses
  *   detections_merge_wbf_fwd   cand, workspace, pack_dev 16, members_dev 4: refuses
  *   detections_merge_seq_fwd   cand, workspace, pack_dev 16, seq_dev 4: refuses
- *   tracks_update_fwd, tracks_state_reset   pack_dev, state_in, state_out (state) 16, track_ids_dev 4: refuses
+ *   tracks_update_fwd, tracks_update_streams_fwd, tracks_state_reset, tracks_state_reset_slots
+ *                              pack_dev, state_in, state_out (state) 16, track_ids_dev 4: refuses
  *   proposals_multi_fwd        props 8: refuses
  *   rois_ingest                rows 8: refuses; rois, props, image_rows, status 4
  */
@@ -1041,6 +1042,35 @@ MSCNN_API int mscnn_tracks_state_reset(void* state, int num_slots, int max_track
 MSCNN_API int mscnn_tracks_update_fwd(const mscnn_track_params* params, int num_frames, int num_slots, const void* pack_dev, int cap,
                                       const void* state_in, void* state_out, int max_tracks,
                                       int* track_ids_dev /* [cap] int32, one per pack row */, void* stream);
+
+/* The tracker for a batch of STREAMS (cameras): a batch in live video is one frame from each of several cameras, not several frames
+ * of one, and every camera needs a table of its own.  Frame t of the pack belongs to stream stream_of[t], inside [0, num_streams);
+ * the frames of stream s in this call are the t with stream_of[t] == s in ascending t, consecutive frames of that stream.  A stream
+ * may have no frame in a call.  state: mscnn_tracks_state_layout_of(num_streams * num_slots, max_tracks); the table of (stream s,
+ * slot k) is slot s * num_slots + k of it.  Per (stream, slot) the ten steps above run unchanged over that stream's frames: header,
+ * records and the frame counter are the stream's own, ids are unique within a (stream, slot) and start at 1 in each.  A stream with
+ * no frame in the call: its block of state_out equals its block of state_in in the header and the first n records (with two distinct
+ * buffers too), its frame counter does not move, no track of it ages.  track_ids_dev as above: every pack row < count of every frame
+ * of the call is written, nothing else.
+ * One launch: a workgroup of 1024 threads per (slot, stream), grid (num_slots, num_streams); every workgroup walks t = 0 ..
+ * num_frames - 1 and skips the frames of the other streams -- on a kernel argument and its own block index, a value every thread of
+ * the workgroup reads alike, so every barrier is still reached by all.  No atomics, nothing spins, no workgroup waits on another; the
+ * same 58 KB of LDS.  stream_of is a HOST array, read before the call returns; it travels BY VALUE in the kernel's arguments (256
+ * entries of 16 bits), so there is no allocation, no copy and no synchronisation inside the op -- hence, when num_streams > 1,
+ * num_frames <= 256 and num_streams <= 256.  mscnn_tracks_update_fwd is this op with num_streams = 1, on the same kernel.
+ * Refused before any launch, naming the value: everything mscnn_tracks_update_fwd refuses (with S * cap and num_streams * num_slots
+ * held below 2^31), a null stream_of, num_streams outside [1, 256], num_frames > 256 with more than one stream, an entry of stream_of
+ * outside [0, num_streams) (naming t and the entry).
+ * mscnn_tracks_state_reset_slots resets the tables [first_slot, first_slot + count) of a state of num_slots_total tables -- one
+ * camera starts again, the others keep their tracks -- and touches no other byte.  (mscnn_tracks_state_reset can not be pointed at a
+ * sub-block: a table is 32 + 104 * max_tracks bytes, 8-byte but not always 16-byte aligned.)  It refuses a null or unaligned state
+ * and a range outside [0, num_slots_total]; count 0 does nothing.
+ * No pin on the reference here either; the check is the same witness run per stream on that stream's frames
+ * (tests/track_streams_witness.py).  The accuracy was NOT evaluated. */
+MSCNN_API int mscnn_tracks_update_streams_fwd(const mscnn_track_params* params, int num_frames, int num_slots, int num_streams,
+                                              const int* stream_of /* HOST, [num_frames] */, const void* pack_dev, int cap,
+                                              const void* state_in, void* state_out, int max_tracks, int* track_ids_dev, void* stream);
+MSCNN_API int mscnn_tracks_state_reset_slots(void* state, int num_slots_total, int max_tracks, int first_slot, int count, void* stream);
 
 /* The proposal half of the scripts' result (run_mscnn_detection.m:75-91, `final_proposals{k}`) for every image of a batched forward
  * in one pass.  props [R_all][6] = BoxOutput's proposals_score, rows [img x1 y1 x2 y2 score] grouped by image in ascending order;

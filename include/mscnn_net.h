@@ -514,6 +514,28 @@ MSCNN_NET_API int mscnn_net_get_tracker(const mscnn_net* net, int* on, mscnn_tra
 MSCNN_NET_API int mscnn_net_tracker_reset(mscnn_net* net);
 MSCNN_NET_API int mscnn_net_detect_tracks(mscnn_net* net, int* ids_host, int cap, const int* seg_dets);
 MSCNN_NET_API int mscnn_net_tracker_state(mscnn_net* net, void* state_host, size_t bytes);
+/* The tracker for a batch of STREAMS (mscnn_hip.h: mscnn_tracks_update_streams_fwd): in live video a batch is one frame from each
+ * of several cameras, and every camera needs a table of its own.
+ * mscnn_net_set_tracker_streams: the frames of the tracked calls that follow belong to num_streams streams ([1, 256]).  It needs the
+ * tracker on, gives a FRESH table and leaves K unfixed (as mscnn_net_tracker_reset), and clears the frame mapping.
+ * mscnn_net_set_tracker puts it back to 1; with 1 every tracked call does exactly what it does without this call.
+ * mscnn_net_set_frame_streams: the sticky mapping for the tracked calls that follow -- image b of mscnn_net_detect_multi and
+ * mscnn_net_detect_cascade_multi, list f of mscnn_net_detect_merge_end, belongs to stream stream_of[b] resp. stream_of[f], inside
+ * [0, num_streams).  The images (lists) of one stream are consecutive frames of it in ascending order; a stream may have none in a
+ * call (nothing of it moves, no track of it ages).  NULL or count 0 clears it.  With num_streams > 1 a tracked call whose frame count
+ * differs from count -- or that has no mapping -- is refused before its final stage is enqueued, naming both numbers.
+ * mscnn_net_get_tracker_streams: num_streams, and the mapping (count entries into stream_of[cap]; count 0: none set).
+ * mscnn_net_tracker_reset_stream: the K tables of stream s are reset on the committed table, on the net's stream, in front of the
+ * next tracked call's update: that camera starts again at id 1, the others keep their tracks.  It succeeds and does nothing while K
+ * is not fixed; an s outside [0, num_streams) is refused.  The two-table rule holds: a call whose body runs twice or that fails steps
+ * nothing twice (a table reset twice is a table reset once).
+ * mscnn_net_tracker_state copies num_streams * K tables, (stream s, slot k) at s * K + k; mscnn_net_detect_tracks is unchanged.
+ * With num_streams > 1 Seq-NMS is refused in both directions, naming the setting: a clip links list t to list t - 1, so it is one
+ * stream.  set / get / reset work on a net built with device -1.  No pin on the reference; the accuracy was not evaluated. */
+MSCNN_NET_API int mscnn_net_set_tracker_streams(mscnn_net* net, int num_streams);
+MSCNN_NET_API int mscnn_net_set_frame_streams(mscnn_net* net, const int* stream_of /* HOST, [count]; NULL: clear */, int count);
+MSCNN_NET_API int mscnn_net_get_tracker_streams(const mscnn_net* net, int* num_streams, int* stream_of, int cap, int* count);
+MSCNN_NET_API int mscnn_net_tracker_reset_stream(mscnn_net* net, int s);
 /* The views of a frame as ONE batched forward (mscnn_hip.h: mscnn_detections_candidates_add_views): the merge was opened with
  * _begin(num_frames, ...), the input holds N images -- the views mscnn_net_set_image_views wrote --, p[N * K] and view[N] describe
  * them as in _add, and list_of[N] (host) names the frame of each: the rows of image b go to the lists of frame list_of[b].  One

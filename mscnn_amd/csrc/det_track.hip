@@ -3,6 +3,8 @@
 // slot kept in device memory from call to call, a persistent track id for every detection row.  Two deliberate departures from the
 // paper: the motion is a constant-velocity prediction of the box centre in place of the Kalman filter, and the matching is greedy by
 // descending overlap under a total order (larger r, then the lower track, then the lower detection) in place of the Hungarian solver.
+// The frames of a call may belong to several streams (cameras): mscnn_tracks_update_streams_fwd gives every (stream, slot) a table of
+// its own and one workgroup, side by side in one launch; the map frame -> stream travels by value in the kernel arguments.
 // ONE workgroup of kTrackThreads owns a slot for the whole call and loops over the call's frames; thread i is track i AND detection i
 // of the frame at hand (hence max_tracks <= 1024 and the 1024 detections that enter).  A thread keeps its track's record and its
 // detection's row in registers: the table is loaded once per call and stored once.
@@ -24,6 +26,7 @@ namespace {
 using namespace mscnn_dev;
 
 constexpr int kTrackThreads = 1024, kTrackWaves = kTrackThreads / 64;      // a thread is a track and a detection
+constexpr int kTrackStreams = 256;      // streams of a call, and frames of a call with more than one stream: stream_of rides in the arguments
 
 struct TrackArgs {
   mscnn_track_params p;
@@ -32,6 +35,8 @@ struct TrackArgs {
   const char* pack;
   const char* state_in; char* state_out;
   int* ids;
+  int num_streams;
+  unsigned short stream_of[kTrackStreams];      // frame t's stream; read only when num_streams > 1 (then num_frames <= kTrackStreams)
 };
 
 // the places of the set flags among the workgroup's threads, and their number (every thread calls it; two barriers)
@@ -116,19 +121,22 @@ __global__ __launch_bounds__(kTrackThreads) void det_track_kernel(TrackArgs a) {
   __shared__ int any;
   const int k = blockIdx.x, tid = threadIdx.x;
   const int K = a.num_slots;
+  const int strm = blockIdx.y;                                    // this workgroup's stream
+  const size_t tab = (size_t)strm * (size_t)K + (size_t)k;      // its table: slot strm * K + k of the state
   const int* hdr = reinterpret_cast<const int*>(a.pack);
   const double* rows = reinterpret_cast<const double*>(a.pack + a.dets_at);
   const bool linear = a.p.motion == MSCNN_TRACK_MOTION_LINEAR;
 
   // the slot's header and this thread's record
-  const int* hin = reinterpret_cast<const int*>(a.state_in + a.slot_bytes * (size_t)k);
+  const int* hin = reinterpret_cast<const int*>(a.state_in + a.slot_bytes * tab);
   int n = hin[MSCNN_TRACKS_N], next_id = hin[MSCNN_TRACKS_NEXT_ID], frame = hin[MSCNN_TRACKS_FRAME];
   int dropped = hin[MSCNN_TRACKS_DROPPED], skipped = hin[MSCNN_TRACKS_SKIPPED];
   n = n < 0 ? 0 : (n > a.max_tracks ? a.max_tracks : n);      // (a table that was never reset: nothing past max_tracks is touched)
   mscnn_track_record R = {};
-  if (tid < n) R = reinterpret_cast<const mscnn_track_record*>(a.state_in + a.slot_bytes * (size_t)k + a.records_at)[tid];
+  if (tid < n) R = reinterpret_cast<const mscnn_track_record*>(a.state_in + a.slot_bytes * tab + a.records_at)[tid];
 
   for (int t = 0; t < a.num_frames; ++t) {
+    if (a.num_streams > 1 && (int)a.stream_of[t] != strm) continue;      // another stream's frame (arguments and blockIdx only: every thread alike)
     frame += 1;                                                                               // step 1
     // step 2: the segment's entry and this thread's detection
     const int s = t * K + k;
@@ -236,7 +244,7 @@ __global__ __launch_bounds__(kTrackThreads) void det_track_kernel(TrackArgs a) {
     next_id += kept;
   }
 
-  char* so = a.state_out + a.slot_bytes * (size_t)k;
+  char* so = a.state_out + a.slot_bytes * tab;
   if (tid == 0) {
     int* h = reinterpret_cast<int*>(so);
     h[MSCNN_TRACKS_N] = n; h[MSCNN_TRACKS_NEXT_ID] = next_id; h[MSCNN_TRACKS_FRAME] = frame; h[MSCNN_TRACKS_DROPPED] = dropped;
@@ -245,10 +253,10 @@ __global__ __launch_bounds__(kTrackThreads) void det_track_kernel(TrackArgs a) {
   if (tid < n) reinterpret_cast<mscnn_track_record*>(so + a.records_at)[tid] = R;      // (records at index >= n stay as they were)
 }
 
-__global__ void det_track_reset_kernel(char* state, size_t slot_bytes, int num_slots) {
+__global__ void det_track_reset_kernel(char* state, size_t slot_bytes, int first_slot, int num_slots) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= num_slots) return;
-  int* h = reinterpret_cast<int*>(state + slot_bytes * (size_t)k);
+  int* h = reinterpret_cast<int*>(state + slot_bytes * ((size_t)first_slot + (size_t)k));
   h[MSCNN_TRACKS_N] = 0; h[MSCNN_TRACKS_NEXT_ID] = 1; h[MSCNN_TRACKS_FRAME] = 0; h[MSCNN_TRACKS_DROPPED] = 0; h[MSCNN_TRACKS_SKIPPED] = 0;
   h[5] = 0; h[6] = 0; h[7] = 0;
 }
@@ -269,48 +277,91 @@ extern "C" int mscnn_tracks_state_reset(void* state, int num_slots, int max_trac
   MSCNN_REQUIRE(max_tracks >= 1 && max_tracks <= kTrackThreads, "tracks_state_reset: max_tracks %d is outside [1, %d]", max_tracks, kTrackThreads);
   MSCNN_REQUIRE_ALIGNED(state, 16, "tracks_state_reset: state");
   const mscnn_tracks_state_layout L = mscnn_tracks_state_layout_of(num_slots, max_tracks);
-  det_track_reset_kernel<<<cdiv(num_slots, 256), 256, 0, as_stream(stream)>>>(static_cast<char*>(state), L.slot, num_slots);
+  det_track_reset_kernel<<<cdiv(num_slots, 256), 256, 0, as_stream(stream)>>>(static_cast<char*>(state), L.slot, 0, num_slots);
   MSCNN_POST_LAUNCH();
   return MSCNN_OK;
 }
 
-extern "C" int mscnn_tracks_update_fwd(const mscnn_track_params* p, int num_frames, int num_slots, const void* pack_dev, int cap,
-                                       const void* state_in, void* state_out, int max_tracks, int* track_ids_dev, void* stream) {
-  MSCNN_REQUIRE(p && pack_dev && state_in && state_out && track_ids_dev, "tracks_update: null pointer");
+extern "C" int mscnn_tracks_state_reset_slots(void* state, int num_slots_total, int max_tracks, int first_slot, int count, void* stream) {
+  MSCNN_REQUIRE(state, "tracks_state_reset_slots: null state");
+  MSCNN_REQUIRE(num_slots_total >= 1, "tracks_state_reset_slots: num_slots_total %d", num_slots_total);
+  MSCNN_REQUIRE(max_tracks >= 1 && max_tracks <= kTrackThreads, "tracks_state_reset_slots: max_tracks %d is outside [1, %d]", max_tracks, kTrackThreads);
+  MSCNN_REQUIRE(first_slot >= 0 && count >= 0 && (long)first_slot + (long)count <= (long)num_slots_total,
+                "tracks_state_reset_slots: slots [%d, %d + %d) are outside [0, %d]", first_slot, first_slot, count, num_slots_total);
+  MSCNN_REQUIRE_ALIGNED(state, 16, "tracks_state_reset_slots: state");
+  if (count == 0) return MSCNN_OK;
+  const mscnn_tracks_state_layout L = mscnn_tracks_state_layout_of(num_slots_total, max_tracks);
+  det_track_reset_kernel<<<cdiv(count, 256), 256, 0, as_stream(stream)>>>(static_cast<char*>(state), L.slot, first_slot, count);
+  MSCNN_POST_LAUNCH();
+  return MSCNN_OK;
+}
+
+// Both entry points: `op` names the one that was called in a refusal.  with_map false: one stream, no map (mscnn_tracks_update_fwd).
+static int tracks_update_any(const char* op, bool with_map, const mscnn_track_params* p, int num_frames, int num_slots, int num_streams, const int* stream_of,
+                             const void* pack_dev, int cap, const void* state_in, void* state_out, int max_tracks, int* track_ids_dev,
+                             void* stream) {
+  MSCNN_REQUIRE(p && pack_dev && state_in && state_out && track_ids_dev, "%s: null pointer", op);
   const int T = num_frames, K = num_slots;
-  MSCNN_REQUIRE(T >= 1, "tracks_update: num_frames %d", T);
-  MSCNN_REQUIRE(K >= 1, "tracks_update: num_slots %d", K);
-  MSCNN_REQUIRE(cap >= 1, "tracks_update: cap %d", cap);
+  MSCNN_REQUIRE(T >= 1, "%s: num_frames %d", op, T);
+  MSCNN_REQUIRE(K >= 1, "%s: num_slots %d", op, K);
+  MSCNN_REQUIRE(cap >= 1, "%s: cap %d", op, cap);
+  const int N = num_streams;
+  if (with_map) {
+    MSCNN_REQUIRE(stream_of, "%s: null stream_of", op);
+    MSCNN_REQUIRE(N >= 1 && N <= kTrackStreams, "%s: num_streams %d is outside [1, %d]", op, N, kTrackStreams);
+    MSCNN_REQUIRE(N == 1 || T <= kTrackStreams, "%s: num_frames %d is above %d with %d streams (the map rides in the kernel's arguments)", op, T,
+                  kTrackStreams, N);
+    for (int t = 0; t < T; ++t)
+      MSCNN_REQUIRE(stream_of[t] >= 0 && stream_of[t] < N, "%s: stream_of[%d] = %d is outside [0, %d)", op, t, stream_of[t], N);
+    MSCNN_REQUIRE((long)N * (long)K <= 0x7fffffffL, "%s: %d streams x %d slots is past 2^31 - 1", op, N, K);
+  }
   MSCNN_REQUIRE((long)T * (long)K <= 0x7fffffffL && (long)T * (long)K * (long)cap <= 0x7fffffffL,
-                "tracks_update: %d frames x %d slots x %d pack rows is past 2^31 - 1", T, K, cap);
-  MSCNN_REQUIRE(max_tracks >= 1 && max_tracks <= kTrackThreads, "tracks_update: max_tracks %d is outside [1, %d]", max_tracks, kTrackThreads);
-  MSCNN_REQUIRE(!(p->high_thr != p->high_thr), "tracks_update: high_thr is NaN");
-  MSCNN_REQUIRE(!(p->low_thr != p->low_thr), "tracks_update: low_thr is NaN");
-  MSCNN_REQUIRE(!(p->new_thr != p->new_thr), "tracks_update: new_thr is NaN");
-  MSCNN_REQUIRE(p->match_thr >= 0 && p->match_thr < 1, "tracks_update: match_thr %g is not inside [0, 1)", p->match_thr);      // (NaN included)
-  MSCNN_REQUIRE(p->match_thr_low >= 0 && p->match_thr_low < 1, "tracks_update: match_thr_low %g is not inside [0, 1)", p->match_thr_low);
-  MSCNN_REQUIRE(p->low_thr <= p->high_thr, "tracks_update: low_thr %g is above high_thr %g", p->low_thr, p->high_thr);
-  MSCNN_REQUIRE(p->new_thr >= p->high_thr, "tracks_update: new_thr %g is below high_thr %g", p->new_thr, p->high_thr);
-  MSCNN_REQUIRE(p->vel_gain > 0 && p->vel_gain <= 1, "tracks_update: vel_gain %g is not inside (0, 1]", p->vel_gain);
+                "%s: %d frames x %d slots x %d pack rows is past 2^31 - 1", op, T, K, cap);
+  MSCNN_REQUIRE(max_tracks >= 1 && max_tracks <= kTrackThreads, "%s: max_tracks %d is outside [1, %d]", op, max_tracks, kTrackThreads);
+  MSCNN_REQUIRE(!(p->high_thr != p->high_thr), "%s: high_thr is NaN", op);
+  MSCNN_REQUIRE(!(p->low_thr != p->low_thr), "%s: low_thr is NaN", op);
+  MSCNN_REQUIRE(!(p->new_thr != p->new_thr), "%s: new_thr is NaN", op);
+  MSCNN_REQUIRE(p->match_thr >= 0 && p->match_thr < 1, "%s: match_thr %g is not inside [0, 1)", op, p->match_thr);      // (NaN included)
+  MSCNN_REQUIRE(p->match_thr_low >= 0 && p->match_thr_low < 1, "%s: match_thr_low %g is not inside [0, 1)", op, p->match_thr_low);
+  MSCNN_REQUIRE(p->low_thr <= p->high_thr, "%s: low_thr %g is above high_thr %g", op, p->low_thr, p->high_thr);
+  MSCNN_REQUIRE(p->new_thr >= p->high_thr, "%s: new_thr %g is below high_thr %g", op, p->new_thr, p->high_thr);
+  MSCNN_REQUIRE(p->vel_gain > 0 && p->vel_gain <= 1, "%s: vel_gain %g is not inside (0, 1]", op, p->vel_gain);
   MSCNN_REQUIRE(p->motion == MSCNN_TRACK_MOTION_NONE || p->motion == MSCNN_TRACK_MOTION_LINEAR,
-                "tracks_update: motion %d is neither %d (none) nor %d (linear)", p->motion, MSCNN_TRACK_MOTION_NONE, MSCNN_TRACK_MOTION_LINEAR);
-  MSCNN_REQUIRE(p->max_age >= 0, "tracks_update: max_age %d", p->max_age);
-  MSCNN_REQUIRE(p->min_hits >= 1, "tracks_update: min_hits %d", p->min_hits);
-  MSCNN_REQUIRE_ALIGNED(pack_dev, 16, "tracks_update: pack_dev");
-  MSCNN_REQUIRE_ALIGNED(state_in, 16, "tracks_update: state_in");
-  MSCNN_REQUIRE_ALIGNED(state_out, 16, "tracks_update: state_out");
-  MSCNN_REQUIRE_ALIGNED(track_ids_dev, 4, "tracks_update: track_ids_dev");
-  const mscnn_tracks_state_layout SL = mscnn_tracks_state_layout_of(K, max_tracks);
+                "%s: motion %d is neither %d (none) nor %d (linear)", op, p->motion, MSCNN_TRACK_MOTION_NONE, MSCNN_TRACK_MOTION_LINEAR);
+  MSCNN_REQUIRE(p->max_age >= 0, "%s: max_age %d", op, p->max_age);
+  MSCNN_REQUIRE(p->min_hits >= 1, "%s: min_hits %d", op, p->min_hits);
+  MSCNN_REQUIRE(reinterpret_cast<uintptr_t>(pack_dev) % 16 == 0, "%s: pack_dev must be 16-byte aligned", op);
+  MSCNN_REQUIRE(reinterpret_cast<uintptr_t>(state_in) % 16 == 0, "%s: state_in must be 16-byte aligned", op);
+  MSCNN_REQUIRE(reinterpret_cast<uintptr_t>(state_out) % 16 == 0, "%s: state_out must be 16-byte aligned", op);
+  MSCNN_REQUIRE(reinterpret_cast<uintptr_t>(track_ids_dev) % 4 == 0, "%s: track_ids_dev must be 4-byte aligned", op);
+  const mscnn_tracks_state_layout SL = mscnn_tracks_state_layout_of(N * K, max_tracks);
   const size_t bytes = SL.total;
   const uintptr_t si = reinterpret_cast<uintptr_t>(state_in), so = reinterpret_cast<uintptr_t>(state_out);
-  MSCNN_REQUIRE(si == so || si + bytes <= so || so + bytes <= si, "tracks_update: state_in and state_out overlap (%zu bytes each) without being equal",
+  MSCNN_REQUIRE(si == so || si + bytes <= so || so + bytes <= si, "%s: state_in and state_out overlap (%zu bytes each) without being equal", op,
                 bytes);
   TrackArgs a = {};
   a.p = *p; a.num_frames = T; a.num_slots = K; a.cap = cap; a.max_tracks = max_tracks;
   a.pack = static_cast<const char*>(pack_dev); a.state_in = static_cast<const char*>(state_in); a.state_out = static_cast<char*>(state_out);
   a.ids = track_ids_dev;
   a.dets_at = mscnn_multi_pack_layout_of(T * K, cap).dets; a.slot_bytes = SL.slot; a.records_at = SL.records;
-  det_track_kernel<<<K, kTrackThreads, 0, as_stream(stream)>>>(a);
+  a.num_streams = N;
+  if (N > 1)
+    for (int t = 0; t < T; ++t) a.stream_of[t] = (unsigned short)stream_of[t];      // (read here, before the call returns; T <= kTrackStreams)
+  // the grid's y and z are bounded by 65535, x is not: the slots go to x
+  det_track_kernel<<<dim3((unsigned)K, (unsigned)N), kTrackThreads, 0, as_stream(stream)>>>(a);
   MSCNN_POST_LAUNCH();
   return MSCNN_OK;
+}
+
+extern "C" int mscnn_tracks_update_fwd(const mscnn_track_params* p, int num_frames, int num_slots, const void* pack_dev, int cap,
+                                       const void* state_in, void* state_out, int max_tracks, int* track_ids_dev, void* stream) {
+  return tracks_update_any("tracks_update", false, p, num_frames, num_slots, 1, nullptr, pack_dev, cap, state_in, state_out, max_tracks,
+                           track_ids_dev, stream);
+}
+
+extern "C" int mscnn_tracks_update_streams_fwd(const mscnn_track_params* p, int num_frames, int num_slots, int num_streams, const int* stream_of,
+                                               const void* pack_dev, int cap, const void* state_in, void* state_out, int max_tracks,
+                                               int* track_ids_dev, void* stream) {
+  return tracks_update_any("tracks_update_streams", true, p, num_frames, num_slots, num_streams, stream_of, pack_dev, cap, state_in, state_out,
+                           max_tracks, track_ids_dev, stream);
 }

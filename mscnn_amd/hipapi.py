@@ -254,6 +254,9 @@ def lib():
         L.mscnn_tracks_state_reset.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.mscnn_tracks_update_fwd.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                               C.c_void_p]
+        L.mscnn_tracks_state_reset_slots.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.mscnn_tracks_update_streams_fwd.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                      C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.mscnn_proposals_multi_pack_bytes.restype = C.c_size_t
         L.mscnn_proposals_multi_pack_bytes.argtypes = [C.c_int, C.c_int]
         L.mscnn_proposals_multi_fwd.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
@@ -1436,6 +1439,32 @@ def tracks_update(params, num_frames, num_slots, pack, cap, state_in, max_tracks
     _check(lib().mscnn_tracks_update_fwd(C.byref(params), num_frames, num_slots, _dev(pack), cap, _dev(state_in), _dev(state_out),
                                          max_tracks, _dev(ids), _stream()))
     return state_out, ids
+
+
+TRACKS_STREAMS_MAX = 256                      # streams of a call, and frames of a call with more than one stream
+
+
+def tracks_update_streams(params, num_frames, num_slots, num_streams, stream_of, pack, cap, state_in, max_tracks, state_out=None, ids=None):
+    """mscnn_tracks_update_streams_fwd: as tracks_update, frame t belonging to stream stream_of[t] (a host sequence of num_frames ints
+    inside [0, num_streams)); the state holds num_streams * num_slots tables, (stream s, slot k) at s * num_slots + k.  Every (stream,
+    slot) is stepped through its own frames only, all in one launch.  Returns (state_out, ids)."""
+    if state_out is None:
+        state_out = state_in
+    if ids is None:
+        ids = torch.zeros(max(cap, 1), dtype=torch.int32, device=pack.device)
+    so = np.ascontiguousarray(stream_of, dtype=np.int32).reshape(-1)
+    if so.size != num_frames:
+        raise MscnnError(f"tracker: stream_of names {so.size} frames, the call has {num_frames}")
+    _check(lib().mscnn_tracks_update_streams_fwd(C.byref(params), num_frames, num_slots, num_streams, so.ctypes.data_as(C.c_void_p), _dev(pack),
+                                                 cap, _dev(state_in), _dev(state_out), max_tracks, _dev(ids), _stream()))
+    return state_out, ids
+
+
+def tracks_state_reset_slots(state, num_slots_total, max_tracks, first_slot, count):
+    """mscnn_tracks_state_reset_slots: resets the tables [first_slot, first_slot + count) of a state of num_slots_total tables (one
+    stream of several starts again, the others keep their tracks).  Returns state."""
+    _check(lib().mscnn_tracks_state_reset_slots(_dev(state), num_slots_total, max_tracks, first_slot, count, _stream()))
+    return state
 
 
 # ---- health of the plane-GEMM kernel's stream-K hand-off (mscnn_hip.h) ----

@@ -61,6 +61,11 @@ struct mscnn_net {
   int track_cur = 0;
   caffe::DeviceBuffer track_state[2];
   bool tracks_valid = false;               // the last tracked call succeeded: track_ids are its detections' track ids
+  // mscnn_net_set_tracker_streams: the frames of a tracked call belong to track_streams streams (cameras), frame b to
+  // track_stream_of[b] (mscnn_net_set_frame_streams, sticky); the table holds track_streams * track_K slots.  1: exactly as without.
+  int track_streams = 1;
+  std::vector<int> track_stream_of;
+  std::vector<char> track_reset_pending;   // mscnn_net_tracker_reset_stream: streams to reset in front of the next tracked call's update
   std::vector<int> track_ids, track_seg_dets;
   // mscnn_net_detect_merge_*: the candidate lists of the forwards added since _begin (mscnn_hip.h: mscnn_detections_candidates_*)
   struct Merge {
@@ -625,6 +630,9 @@ int mscnn_net_set_seq_nms(mscnn_net* n, double link_thr, double score_thr, int t
                                         << n->matrix.method << "): the two exclude each other, turn that one off first";
     CHECK(!on || n->wbf.thr == 0.0) << "set_seq_nms: link_thr " << link_thr << " while weighted boxes fusion is on (set_wbf thr " << n->wbf.thr
                                     << "): the two exclude each other, turn that one off first";
+    CHECK(!on || !n->track_on || n->track_streams == 1)
+        << "set_seq_nms: link_thr " << link_thr << " while the tracker has " << n->track_streams
+        << " streams (set_tracker_streams): a clip links list t to list t - 1, so it is one stream; set that one to 1 first";
     n->seq = mscnn_seq_nms_params{on ? link_thr : 0.0, score_thr, top_k, rescore, max_out};      // (-0.0 is off too)
   });
 }
@@ -641,6 +649,7 @@ int mscnn_net_set_tracker(mscnn_net* n, const mscnn_track_params* p, int max_tra
     CHECK(n != nullptr);
     if (p == nullptr) {      // off: the state is dropped with the setting
       n->track_on = false; n->track_K = 0; n->tracks_valid = false;
+      n->track_streams = 1; n->track_stream_of.clear(); n->track_reset_pending.clear();
       return;
     }
     // (the op's own refusals, made here so that a refused value changes nothing and is named at the call that brought it)
@@ -660,6 +669,58 @@ int mscnn_net_set_tracker(mscnn_net* n, const mscnn_track_params* p, int max_tra
                              << "): the two exclude each other (the track ids go where WBF's member counts go), turn that one off first";
     n->track = *p; n->track_max = max_tracks; n->track_on = true;
     n->track_K = 0; n->tracks_valid = false;      // a new setting is a new stream: the next call starts at id 1
+    n->track_streams = 1; n->track_stream_of.clear(); n->track_reset_pending.clear();      // (and ONE stream: mscnn_net_set_tracker_streams)
+  });
+}
+
+int mscnn_net_set_tracker_streams(mscnn_net* n, int num_streams) {
+  return guarded([&] {
+    CHECK(n != nullptr);
+    CHECK(n->track_on) << "set_tracker_streams: the tracker is off (mscnn_net_set_tracker)";
+    CHECK(num_streams >= 1 && num_streams <= 256) << "set_tracker_streams: num_streams " << num_streams << " is outside [1, 256]";
+    CHECK(num_streams == 1 || n->seq.link_thr == 0.0)
+        << "set_tracker_streams: num_streams " << num_streams << " while Seq-NMS is on (set_seq_nms link_thr " << n->seq.link_thr
+        << "): a clip links list t to list t - 1, so it is one stream; turn that one off first";
+    n->track_streams = num_streams;
+    n->track_stream_of.clear(); n->track_reset_pending.clear();
+    n->track_K = 0; n->tracks_valid = false;      // a fresh table, K unfixed (as mscnn_net_tracker_reset)
+  });
+}
+
+int mscnn_net_set_frame_streams(mscnn_net* n, const int* stream_of, int count) {
+  return guarded([&] {
+    CHECK(n != nullptr);
+    if (stream_of == nullptr || count == 0) { n->track_stream_of.clear(); return; }
+    CHECK(n->track_on) << "set_frame_streams: the tracker is off (mscnn_net_set_tracker)";
+    CHECK(count >= 1 && count <= 256) << "set_frame_streams: count " << count << " is outside [0, 256]";
+    for (int b = 0; b < count; ++b)
+      CHECK(stream_of[b] >= 0 && stream_of[b] < n->track_streams)
+          << "set_frame_streams: stream_of[" << b << "] = " << stream_of[b] << " is outside [0, " << n->track_streams
+          << ") (mscnn_net_set_tracker_streams)";
+    n->track_stream_of.assign(stream_of, stream_of + count);
+  });
+}
+
+int mscnn_net_get_tracker_streams(const mscnn_net* n, int* num_streams, int* stream_of, int cap, int* count) {
+  return guarded([&] {
+    CHECK(n && num_streams && count);
+    const int c = (int)n->track_stream_of.size();
+    CHECK(c == 0 || (stream_of != nullptr && cap >= c)) << "get_tracker_streams: the buffer holds " << cap << " entries, the mapping has " << c;
+    *num_streams = n->track_streams; *count = c;
+    for (int b = 0; b < c; ++b) stream_of[b] = n->track_stream_of[b];
+  });
+}
+
+int mscnn_net_tracker_reset_stream(mscnn_net* n, int s) {
+  return guarded([&] {
+    CHECK(n != nullptr);
+    CHECK(n->track_on) << "tracker_reset_stream: the tracker is off (mscnn_net_set_tracker)";
+    CHECK(s >= 0 && s < n->track_streams) << "tracker_reset_stream: stream " << s << " is outside [0, " << n->track_streams << ")";
+    if (n->track_K == 0) return;      // (no table yet: the first tracked call makes a fresh one)
+    // the reset itself runs on the net's stream in front of the next tracked call's update, on the committed table: resetting a
+    // table twice is resetting it once, so a body that runs twice resets and steps what one run does; cleared by the commit
+    n->track_reset_pending.resize(n->track_streams, 0);
+    n->track_reset_pending[s] = 1;
   });
 }
 
@@ -675,6 +736,7 @@ int mscnn_net_tracker_reset(mscnn_net* n) {
     CHECK(n != nullptr);
     CHECK(n->track_on) << "tracker_reset: the tracker is off (mscnn_net_set_tracker)";
     n->track_K = 0; n->tracks_valid = false;      // (the next tracked call resets the table on its stream, in front of its update)
+    n->track_reset_pending.clear();
   });
 }
 
@@ -683,9 +745,9 @@ int mscnn_net_tracker_state(mscnn_net* n, void* state_host, size_t bytes) {
     CHECK(n != nullptr);
     CHECK(n->track_on) << "tracker_state: the tracker is off (mscnn_net_set_tracker)";
     CHECK(n->track_K >= 1) << "tracker_state: no tracked call has succeeded since the tracker was set or reset: the number of slots is not fixed yet";
-    const size_t need = mscnn_tracks_state_bytes(n->track_K, n->track_max);
-    CHECK(state_host != nullptr && bytes >= need) << "tracker_state: a buffer of " << bytes << " bytes, " << n->track_K << " slots x " << n->track_max
-                                                   << " tracks need " << need;
+    const size_t need = mscnn_tracks_state_layout_of(n->track_streams * n->track_K, n->track_max).total;
+    CHECK(state_host != nullptr && bytes >= need) << "tracker_state: a buffer of " << bytes << " bytes, " << n->track_streams * n->track_K
+                                                   << " slots x " << n->track_max << " tracks need " << need;
     hipStream_t st = (hipStream_t)Caffe::stream();
     HIP_CHECK(hipMemcpyAsync(state_host, n->track_state[n->track_cur].get(), need, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
@@ -715,28 +777,43 @@ static void track_refuses(const mscnn_net* n, const char* name) {
   CHECK(!n->track_on) << name << ": refused while the tracker is on (set_tracker high_thr " << n->track.high_thr
                       << "): only detect_multi, detect_cascade_multi and detect_merge_end step the tracks; turn the tracker off first";
 }
-// K of a tracked call against the K the first call after a reset fixed; before anything is enqueued
-static void track_slots_checked(const mscnn_net* n, const char* name, int K) {
+// K of a tracked call against the K the first call after a reset fixed, and with several streams its T frames against the mapping;
+// before anything is enqueued
+static void track_slots_checked(const mscnn_net* n, const char* name, int T, int K) {
   CHECK(!n->track_on || n->track_K == 0 || n->track_K == K)
       << name << ": " << K << " slots per frame, the tracker's table was made for " << n->track_K
       << " by the first call after its reset (mscnn_net_tracker_reset starts a new stream)";
+  CHECK(!n->track_on || n->track_streams == 1 || (int)n->track_stream_of.size() == T)
+      << name << ": " << T << " frames, the mapping of frames to the tracker's " << n->track_streams << " streams names "
+      << n->track_stream_of.size() << " (mscnn_net_set_frame_streams)";
 }
 // mscnn_tracks_update_fwd behind the pack of T frames x K slots with pack_rows rows at `pack` (device-addressable), ids to ids_dev:
 // reads the committed table, writes the other one.  The first call after a reset makes and resets the tables, on the same stream.
 static void track_enqueue(mscnn_net* n, const char* name, int T, int K, const void* pack, int pack_rows, int* ids_dev) {
-  track_slots_checked(n, name, K);
+  track_slots_checked(n, name, T, K);
   hipStream_t st = (hipStream_t)Caffe::stream();
-  const size_t bytes = mscnn_tracks_state_bytes(K, n->track_max);
-  CHECK_GT(bytes, 0u) << name << ": the tracker's table for " << K << " slots x " << n->track_max << " tracks";
+  const int N = n->track_streams;
+  CHECK_LE((long)N * (long)K, 0x7fffffffL) << name << ": " << N << " streams x " << K << " slots";
+  const size_t bytes = mscnn_tracks_state_bytes(N * K, n->track_max);
+  CHECK_GT(bytes, 0u) << name << ": the tracker's table for " << N * K << " slots x " << n->track_max << " tracks";
   if (n->track_K == 0) {
     for (caffe::DeviceBuffer& b : n->track_state) b.Reserve(bytes);
-    MSCNN_CHECK(mscnn_tracks_state_reset(n->track_state[n->track_cur].get(), K, n->track_max, st));
+    MSCNN_CHECK(mscnn_tracks_state_reset(n->track_state[n->track_cur].get(), N * K, n->track_max, st));
+  } else {
+    for (size_t s = 0; s < n->track_reset_pending.size(); ++s)      // mscnn_net_tracker_reset_stream, on the committed table
+      if (n->track_reset_pending[s])
+        MSCNN_CHECK(mscnn_tracks_state_reset_slots(n->track_state[n->track_cur].get(), N * K, n->track_max, (int)s * K, K, st));
   }
-  MSCNN_CHECK(mscnn_tracks_update_fwd(&n->track, T, K, pack, pack_rows, n->track_state[n->track_cur].get(),
-                                      n->track_state[n->track_cur ^ 1].get(), n->track_max, ids_dev, st));
+  if (N == 1)
+    MSCNN_CHECK(mscnn_tracks_update_fwd(&n->track, T, K, pack, pack_rows, n->track_state[n->track_cur].get(),
+                                        n->track_state[n->track_cur ^ 1].get(), n->track_max, ids_dev, st));
+  else
+    MSCNN_CHECK(mscnn_tracks_update_streams_fwd(&n->track, T, K, N, n->track_stream_of.data(), pack, pack_rows,
+                                                n->track_state[n->track_cur].get(), n->track_state[n->track_cur ^ 1].get(), n->track_max,
+                                                ids_dev, st));
 }
 // the call has succeeded: the table it wrote is the committed one
-static void track_commit(mscnn_net* n, int K) { n->track_cur ^= 1; n->track_K = K; }
+static void track_commit(mscnn_net* n, int K) { n->track_cur ^= 1; n->track_K = K; n->track_reset_pending.clear(); }
 
 size_t mscnn_net_detect_pack_bytes(int cap) {
   const size_t rows = (size_t)(cap > 0 ? cap : 1);
@@ -1137,7 +1214,7 @@ static void detect_segments_blocking(mscnn_net* n, const char* name, int num_ima
   // stream, its ids go behind the pack in the same pinned block and come over with it
   const bool track = tracked && n->track_on;
   if (tracked) n->tracks_valid = false;
-  if (track) track_slots_checked(n, name, K);
+  if (track) track_slots_checked(n, name, num_images, K);
   size_t ids_at = 0;
   auto run = [&]() {
     pcap = K * rows_all();
@@ -1717,7 +1794,7 @@ int mscnn_net_detect_merge_end(mscnn_net* n, double* dets_host, int* pass_host, 
     // the tracker (mscnn_net_set_tracker; never on together with WBF): the lists are consecutive frames of the stream; its ids go
     // behind the pack too, behind Seq-NMS's sequence ids when that is on
     const bool track = n->track_on;
-    if (track) track_slots_checked(n, "detect_merge_end", m.slots);
+    if (track) track_slots_checked(n, "detect_merge_end", m.images, m.slots);
     const size_t per_row = (size_t)S * m.cand_cap * sizeof(int);
     const size_t tracks_at = seq ? (members_at + per_row + 15) / 16 * 16 : members_at;
     ensure_det_host(n, track ? tracks_at + per_row : (wbf || seq) ? members_at + per_row : total);

@@ -133,6 +133,8 @@ def lib():
             "mscnn_net_detect_merge_sequences": [vp, vp, ci, vp],
             "mscnn_net_set_tracker": [vp, vp, ci], "mscnn_net_get_tracker": [vp, vp, vp, vp, vp], "mscnn_net_tracker_reset": [vp],
             "mscnn_net_detect_tracks": [vp, vp, ci, vp], "mscnn_net_tracker_state": [vp, vp, C.c_size_t],
+            "mscnn_net_set_tracker_streams": [vp, ci], "mscnn_net_set_frame_streams": [vp, vp, ci],
+            "mscnn_net_get_tracker_streams": [vp, vp, vp, ci, vp], "mscnn_net_tracker_reset_stream": [vp, ci],
         }
         for name, args in sig.items():
             getattr(L, name).argtypes = args
@@ -633,7 +635,7 @@ class Net:
         return dict(link_thr=lt.value, score_thr=st.value, top_k=tk.value, rescore={1: "avg", 2: "max"}[rs.value], max_out=mo.value)
 
     def set_tracker(self, high_thr=0.5, low_thr=0.1, new_thr=None, match_thr=0.3, match_thr_low=0.5, motion="linear", vel_gain=0.5,
-                    max_age=30, min_hits=1, max_tracks=256):
+                    max_age=30, min_hits=1, max_tracks=256, streams=1):
         """mscnn_net_set_tracker: from now on detect_multi, detect_cascade_multi and detect_merge_end step a table of tracks per slot
         behind their pack (mscnn_tracks_update_fwd: BYTE's two passes -- detections with a score >= high_thr first, overlap >
         match_thr, then those >= low_thr against the confirmed tracks seen in the frame before, overlap > match_thr_low --, motion
@@ -642,16 +644,53 @@ class Net:
         and detect_tracks() gives a persistent id per detection.  The images of a call, or the frames of a merge, are consecutive
         frames of the stream.  high_thr None = off (the default).  A successful call starts a fresh table (ids from 1).  Refused while
         WBF is on; a refused value fails naming it and the setting stays as it was.  While it is on the single-segment and asynchronous
-        detect forms are refused."""
+        detect forms are refused.
+        streams (mscnn_net_set_tracker_streams): the frames of a tracked call belong to that many streams (cameras), each with a
+        table of its own; set_frame_streams says which frame is whose.  1 (the default): one stream, exactly as without.  A refused
+        streams value leaves the settings as they were (the table starts afresh)."""
         if high_thr is None:
             _check(lib().mscnn_net_set_tracker(self._h, None, 0))
             return
+        before = (self.get_tracker(), self.get_tracker_streams(), self.get_frame_streams()) if int(streams) != 1 else None
         m = TRACK_MOTIONS.get(motion, motion) if isinstance(motion, str) else motion
         if isinstance(m, str):
             raise NetError(f"set_tracker: motion {motion!r} is none of 'none', 'linear'")
         tp = TrackParams(float(high_thr), float(low_thr), float(high_thr if new_thr is None else new_thr), float(match_thr),
                          float(match_thr_low), float(vel_gain), int(m), int(max_age), int(min_hits))
         _check(lib().mscnn_net_set_tracker(self._h, C.byref(tp), int(max_tracks)))
+        if before is not None:
+            try:
+                _check(lib().mscnn_net_set_tracker_streams(self._h, int(streams)))
+            except NetError:
+                old, old_streams, old_map = before
+                if old is None:
+                    self.set_tracker(None)
+                else:
+                    self.set_tracker(**old)
+                    _check(lib().mscnn_net_set_tracker_streams(self._h, old_streams))
+                    self.set_frame_streams(old_map)
+                raise
+
+    def get_tracker_streams(self):
+        """mscnn_net_get_tracker_streams: the number of streams the tracker keeps tables for (1 unless set_tracker(streams=...))."""
+        return self._tracker_streams()[0]
+
+    def _tracker_streams(self):
+        ns, cnt = C.c_int(), C.c_int()
+        so = (C.c_int * 256)()
+        _check(lib().mscnn_net_get_tracker_streams(self._h, C.byref(ns), so, 256, C.byref(cnt)))
+        return ns.value, [int(so[b]) for b in range(cnt.value)]
+
+    def set_frame_streams(self, stream_of):
+        """mscnn_net_set_frame_streams: the sticky mapping for the tracked calls that follow -- image b of detect_multi and
+        detect_cascade_multi, frame f of detect_merge_end, belongs to stream stream_of[b] (inside [0, streams)).  None or an empty
+        sequence clears it.  With streams > 1 a tracked call needs a mapping with one entry per frame."""
+        so = np.zeros(0, np.int32) if stream_of is None else np.ascontiguousarray(stream_of, dtype=np.int32).reshape(-1)
+        _check(lib().mscnn_net_set_frame_streams(self._h, so.ctypes.data_as(C.c_void_p) if so.size else None, int(so.size)))
+
+    def get_frame_streams(self):
+        """The mapping set_frame_streams set (a list of ints), None when there is none."""
+        return self._tracker_streams()[1] or None
 
     def _tracker(self):
         on, tp, mt, K = C.c_int(), TrackParams(), C.c_int(), C.c_int()
@@ -667,9 +706,14 @@ class Net:
         return dict(high_thr=tp.high_thr, low_thr=tp.low_thr, new_thr=tp.new_thr, match_thr=tp.match_thr, match_thr_low=tp.match_thr_low,
                     motion={1: "none", 2: "linear"}[tp.motion], vel_gain=tp.vel_gain, max_age=tp.max_age, min_hits=tp.min_hits, max_tracks=mt)
 
-    def tracker_reset(self):
-        """mscnn_net_tracker_reset: a new stream -- the next tracked call starts with an empty table and id 1, and fixes K again."""
-        _check(lib().mscnn_net_tracker_reset(self._h))
+    def tracker_reset(self, stream=None):
+        """mscnn_net_tracker_reset: a new stream -- the next tracked call starts with an empty table and id 1, and fixes K again.
+        stream (mscnn_net_tracker_reset_stream): only that stream's tables are reset, in front of the next tracked call's update; the
+        other streams keep their tracks."""
+        if stream is None:
+            _check(lib().mscnn_net_tracker_reset(self._h))
+        else:
+            _check(lib().mscnn_net_tracker_reset_stream(self._h, int(stream)))
 
     def detect_tracks(self):
         """mscnn_net_detect_tracks: after a detect_multi, detect_cascade_multi or detect_merge_end that ran the tracker (set_tracker),
@@ -684,8 +728,11 @@ class Net:
 
     def tracker_state(self, raw=False):
         """mscnn_net_tracker_state: the committed table, one dict per slot -- n, next_id, frame, dropped, skipped and tracks = the
-        first n records (a numpy record array: box, obs, vel, score, id, hits, misses, confirmed).  raw: the table's bytes (uint8)."""
+        first n records (a numpy record array: box, obs, vel, score, id, hits, misses, confirmed).  With streams > 1 one such list
+        per stream.  raw: the table's bytes (uint8), streams * K slots, (stream s, slot k) at s * K + k."""
         _, _, mt, K = self._tracker()
+        N = self.get_tracker_streams()
+        per_stream, K = K, N * K
         slot = 4 * TRACKS_HEADER_WORDS + mt * TRACK_RECORD.itemsize
         buf = np.zeros((max(K, 1) * slot + 15) // 16 * 16, np.uint8)
         _check(lib().mscnn_net_tracker_state(self._h, buf.ctypes.data_as(C.c_void_p), buf.size))
@@ -697,6 +744,8 @@ class Net:
             at = k * slot + 4 * TRACKS_HEADER_WORDS
             recs = buf[at:at + int(h[0]) * TRACK_RECORD.itemsize].view(TRACK_RECORD).copy()
             out.append(dict(n=int(h[0]), next_id=int(h[1]), frame=int(h[2]), dropped=int(h[3]), skipped=int(h[4]), tracks=recs))
+        if N > 1:
+            return [out[s * per_stream:(s + 1) * per_stream] for s in range(N)]
         return out
 
     @staticmethod

@@ -58,6 +58,10 @@ merge of every frame of the clip, its pack read on the host), the final stage + 
 behind it (the ids read on the host too), and the final stage + the numpy tracker of tests/track_witness.py on the host's copy of the
 pack -- the only route there was.  The table gives the detections, the tracks and the tracked detections, and every case says whether
 the op is below the host route by more than the two spreads; the rows are also written to --out (profiles/detect_track.txt).
+--track --streams N takes the images of ONE forward as one frame from each of N cameras (N = 0: as many as the forward has images):
+(a) the final stage alone, (b) + the one-launch stream tracker (mscnn_tracks_update_streams_fwd), (c) + N single-stream
+mscnn_tracks_update_fwd calls on N state buffers and N packs -- the only device route there was --, (d) the pack on the host + the
+numpy witness per stream; the rows go to --out (profiles/detect_track_streams.txt).
 
 --lib path/to/libmscnn_hip.so runs whatever leg is selected with THAT build's kernels under the Net (it is loaded first, so the Net's
 calls bind to it; the per-range op calls of the batched cascade case's per-call form go through hipapi's own handle and stay this
@@ -913,6 +917,146 @@ def track_leg(a):
             fh.write("\n".join(lines) + "\n")
 
 
+STREAM_CASES = {   # name: (a SEQ_CASES entry: model, images of the one forward = cameras, classes, original image size, net input size)
+    "caltech-7s480-b8": ("caltech/mscnn-7s-480", 8, [2], (480, 640), (480, 640)),
+    "kitti_car-7s576-b4": ("kitti_car/mscnn-7s-576", 4, [2], (375, 1242), (576, 1920)),
+}
+
+
+def track_streams_leg(a):
+    """--track --streams N: the images of ONE forward are one frame from each of N cameras (frame b belongs to stream b % N).  Behind one
+    add of the forward's images: (a) the final stage alone (the hard merge, its pack read on the host); (b) the final stage + the
+    stream tracker, ONE launch (mscnn_tracks_update_streams_fwd); (c) the final stage + N single-stream mscnn_tracks_update_fwd calls,
+    one per camera, each on a state buffer and a pack of its own -- the only device route the parent commit has; the N packs hold the
+    same rows and are made ahead, untimed, which favours (c) --; (d) the pack on the host + the numpy witness per stream.  Every form
+    starts from tables that have seen these frames once (a running system: every track finds its detection again); all forms end with
+    the detections (and ids) on the host; they rotate within a step."""
+    import copy
+    import torch
+    from mscnn_amd import hipapi
+    sys.path.insert(1, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import track_streams_witness as sw
+    import track_witness as tw
+    kw = dict(high_thr=0.5, low_thr=0.1, match_thr=0.3, match_thr_low=0.5, motion="linear", vel_gain=0.5, max_age=30, min_hits=1)
+    M = 256
+    p, cp = tw.params(**kw), hipapi.track_params(**kw)
+    names = ["(a) final stage alone", "(b) + stream tracker, 1 launch", "(c) + N single-stream calls", "(d) pack to host + numpy"]
+    lines = []
+
+    def say(line):
+        print(line, flush=True)
+        lines.append(line)
+
+    say(f"# the tracker for a batch of cameras behind the final stage (high_thr {kw['high_thr']:g}, low_thr {kw['low_thr']:g}, match_thr {kw['match_thr']:g}, "
+        f"match_thr_low {kw['match_thr_low']:g}, motion linear, max_tracks {M}) per forward, host wall ms from an idle device to the detections (and ids) "
+        f"on the host (median over {a.steps} steps after {a.warmup} warm-up; {a.rounds} rounds: median of the medians, spread = max - min), regime "
+        f"{a.regime}; B = the images of the forward; N = the streams; dets = the detections of all images; tracks = the tables' tracks; tracked = the "
+        f"detections with an id > 0")
+    say(f"# {'case':22s} {'B':>2s} {'N':>2s} {'dets':>5s} {'tracks':>6s} {'tracked':>7s} | " + " | ".join(f"{nm:>30s} {'spread':>6s}" for nm in names) +
+        " | (b)-(a) ms | (c)-(a) ms")
+    SEQ_CASES.update(STREAM_CASES)
+    for name in a.case or list(STREAM_CASES):
+        T, K, cap, cand = seq_clip_lists(a, hipapi, name)
+        N = a.streams or T
+        stream_of = [b % N for b in range(T)]
+        S = T * K
+        L = hipapi.lib()
+        pack = torch.zeros(L.mscnn_detections_multi_pack_bytes(S, S * cap), dtype=torch.uint8, device="cuda")
+        ws = torch.empty(max(L.mscnn_detections_merge_workspace_bytes(S, cap), 1), dtype=torch.uint8, device="cuda")
+        ids = torch.zeros(S * cap, dtype=torch.int32, device="cuda")
+        out0 = cand.merge(pack=pack, ws=ws)
+        frames = [[out0[t * K + k][0] for k in range(K)] for t in range(T)]
+        # the tables after these frames once: (b)'s state, (c)'s N states, (d)'s dicts
+        base = hipapi.tracks_state_new(N * K, M)
+        hipapi.tracks_update_streams(cp, T, K, N, stream_of, pack, S * cap, base, M)
+        state = base.clone()
+        base_tables = sw.new_tables(N, K)
+        sw.run(base_tables, frames, stream_of, p, M)
+        per, where = sw.split(frames, stream_of, N)
+        packs, base_n, state_n, ids_n = [], [], [], []
+        for s in range(N):      # stream s alone: its frames in a pack of their own (the same rows), its own state and ids
+            buf, _, rows_s = tw.pack_bytes(per[s], cap, "merge", fill=0)
+            packs.append((torch.from_numpy(buf).cuda(), rows_s))
+            b = hipapi.tracks_state_new(K, M)
+            hipapi.tracks_update(cp, len(per[s]), K, packs[s][0], rows_s, b, M)
+            base_n.append(b)
+            state_n.append(b.clone())
+            ids_n.append(torch.zeros(rows_s, dtype=torch.int32, device="cuda"))
+        tables = [None]
+
+        def alone():
+            return cand.merge(pack=pack, ws=ws), None
+
+        def one_launch():
+            out = cand.merge(pack=pack, ws=ws)
+            hipapi.tracks_update_streams(cp, T, K, N, stream_of, pack, S * cap, state, M, None, ids)
+            h = ids.cpu().numpy()      # (synchronises: the ids are on the host)
+            return out, [h[s * cap:s * cap + len(d)] for s, (d, _, _) in enumerate(out)]
+
+        def n_calls():
+            out = cand.merge(pack=pack, ws=ws)
+            for s in range(N):
+                hipapi.tracks_update(cp, len(per[s]), K, packs[s][0], packs[s][1], state_n[s], M, None, ids_n[s])
+            got = [None] * S
+            for s in range(N):
+                h = ids_n[s].cpu().numpy()
+                for i, t in enumerate(where[s]):
+                    for k in range(K):
+                        got[t * K + k] = h[(i * K + k) * cap:(i * K + k) * cap + len(out[t * K + k][0])]
+            return out, got
+
+        def on_host():
+            out = cand.merge(pack=pack, ws=ws)
+            got = sw.run(tables[0], [[out[t * K + k][0] for k in range(K)] for t in range(T)], stream_of, p, M)
+            return out, [got[s // K][s % K] for s in range(S)]
+
+        forms = [alone, one_launch, n_calls, on_host]
+        F = len(forms)
+        med = [[] for _ in range(F)]
+        for rnd in range(a.rounds):
+            t = [[] for _ in range(F)]
+            for step in range(a.warmup + a.steps):
+                res = [None] * F
+                for k in range(F):
+                    f = (k + step) % F
+                    state.copy_(base)      # (untimed: every form starts from the same tables)
+                    for s in range(N):
+                        state_n[s].copy_(base_n[s])
+                    tables[0] = copy.deepcopy(base_tables)
+                    torch.cuda.synchronize()      # (untimed: every form starts on an idle device)
+                    t0 = time.perf_counter()
+                    res[f] = forms[f]()
+                    dt = time.perf_counter() - t0
+                    if step >= a.warmup:
+                        t[f].append(dt)
+                for other in (2, 3):      # the one launch against the N calls and against the host form, bit for bit
+                    assert all(np.array_equal(x, y) for x, y in zip(res[1][1], res[other][1])), (name, step, other)
+            for f in range(F):
+                med[f].append(1e3 * float(np.median(t[f])))
+        dets = sum(len(d) for d, _, _ in res[0][0])
+        tracks = sum(sl["n"] for tab in tables[0] for sl in tab)
+        tracked = sum(int(np.count_nonzero(i)) for i in res[1][1])
+        m = [float(np.median(v)) for v in med]
+        sp = [max(v) - min(v) for v in med]
+        say(f"  {name:22s} {T:2d} {N:2d} {dets:5d} {tracks:6d} {tracked:7d} | " + " | ".join(f"{m[f]:30.3f} {sp[f]:6.3f}" for f in range(F)) +
+            f" | {m[1] - m[0]:10.3f} | {m[2] - m[0]:10.3f}")
+        say(f"# {name}: the one launch adds {m[1] - m[0]:.3f} ms to the final stage, the {N} single-stream calls add {m[2] - m[0]:.3f} ms; (b) / (c) = {m[1] / m[2]:.3f} "
+            f"({'(b) is below' if m[1] + sp[1] < m[2] - sp[2] else '(b) is NOT below'} (c) by more than the two spreads); (b) / (d) = {m[1] / m[3]:.3f}")
+    say("# python tools/bench_final_stage.py --track --streams " + f"{a.streams} --steps {a.steps} --warmup {a.warmup} --rounds {a.rounds}: MI355X (gfx950), one GPU, "
+        "seeded weights; ONE forward of B images, image b the seeded synthetic frame shifted 4 b pixels, stream b % N (--streams 0: N = B); the forward "
+        "and the add call are not timed; every form starts from tables that have seen the same frames once.  (b)-(a) and (c)-(a) are differences of "
+        "two host wall times: the launches are enqueued behind the read of the pack, so they hold a second synchronisation and the copy of the id "
+        "buffer(s) as well; (c) reads N id buffers, and its N packs were made ahead (untimed).")
+    say("# every step asserts that the ids of (b), (c) and (d) are equal bit for bit.")
+    say("# NOT measured: the kernel alone (device events or a profiler), more than one class (K = 1: one workgroup per stream), more than one frame per "
+        "stream in a call, streams without a frame, more than 8 streams, tables near max_tracks = 1024, the Net calls (set_frame_streams, detect_multi) "
+        "and the drivers end to end, real video, accuracy (no labels).")
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+
 def use_lib(path):
     """The kernels of another build of libmscnn_hip.so under this build's Net: loaded first and globally, the Net library's calls bind
     to it (checked on one final-stage symbol)."""
@@ -976,8 +1120,12 @@ ap.add_argument("--seq", action="store_true", help="with --merge: per clip of 8 
                 "and every candidate list to the host + a vectorised numpy Seq-NMS; us per iteration; the rows also go to --out")
 ap.add_argument("--track", action="store_true", help="on the clips of --merge --seq: the final stage alone, the final stage + the tracker op, and "
                 "the pack on the host + the numpy tracker of tests/track_witness.py; the rows also go to --out")
+ap.add_argument("--streams", type=int, default=None, metavar="N", help="with --track: the images of one forward as one frame from each of N "
+                "cameras (0: as many as images): the final stage alone, + the one-launch stream tracker, + N single-stream calls, the pack on "
+                "the host + the numpy witness per stream; the rows also go to --out")
 ap.add_argument("--out", default=None, help="--merge --wbf / --merge --seq / --track: the file the rows are written to (default: "
-                "profiles/detect_merge_wbf.txt / profiles/detect_merge_seq.txt / profiles/detect_track.txt; '' = none)")
+                "profiles/detect_merge_wbf.txt / profiles/detect_merge_seq.txt / profiles/detect_track.txt, with --streams "
+                "profiles/detect_track_streams.txt; '' = none)")
 ap.add_argument("--soft-thr", type=float, default=0.001, help="--merge --soft / --matrix / --wbf: the score threshold of Soft-NMS and Matrix NMS")
 ap.add_argument("--rounds", type=int, default=3, help="--merge / --parent-lib: repetitions of the whole measurement")
 ap.add_argument("--lib", default="", help="run with the kernels of this libmscnn_hip.so under the Net")
@@ -996,12 +1144,17 @@ ap.add_argument("--ovr-dnm", default="union", choices=("union", "min"), help="bb
 a = ap.parse_args()
 if a.out is None:
     a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                         "detect_track.txt" if a.track else "detect_merge_seq.txt" if a.seq else "detect_merge_wbf.txt")
+                         "detect_track_streams.txt" if a.track and a.streams is not None else "detect_track.txt" if a.track else "detect_merge_seq.txt" if a.seq else "detect_merge_wbf.txt")
 if a.parent_lib:
     ab_leg(a, sys.argv[1:])
     sys.exit(0)
 if a.lib:
     use_lib(a.lib)
+if a.streams is not None and not (a.track and 0 <= a.streams <= 256):
+    ap.error(f"--streams {a.streams} belongs to --track and lies inside [0, 256]")
+if a.track and a.streams is not None:
+    track_streams_leg(a)
+    sys.exit(0)
 if a.track:
     track_leg(a)
     sys.exit(0)

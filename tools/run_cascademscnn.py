@@ -59,7 +59,9 @@ accuracy not evaluated.
 (Net.set_tracker; BYTE's two association passes on the device behind every detect_cascade_multi and detect_merge_end, a table of
 tracks per (output, class)); alone, with --batch, with --orig-size (the boxes are original-image
 pixels whatever the input size) and with every merge flag but --wbf.  As tools/run_mscnn_detection.py; the result files are unchanged, --tracks-out adds
-DIR/<comp_id>_<class>_<output>.txt with rows [image_index track x y w h score], track 0 = no confirmed track; no pin on the reference,
+DIR/<comp_id>_<class>_<output>.txt with rows [image_index track x y w h score], track 0 = no confirmed track (--streams N with
+--track: the frames are N multiplexed cameras, frame i belongs to stream i % N and has that stream's tracks, --tracks-out writes
+..._stream<s>.txt per stream; not with --seq-nms); no pin on the reference,
 accuracy not evaluated.
 
 Everything here is host glue over calls the test-suite covers one by one (Net.set_images, forward, detect_cascade_multi,
@@ -160,7 +162,8 @@ def main(argv=None):
     import torch
     from mscnn_amd import kitti, net as mnet, synth, zoo
     from run_mscnn_detection import (apply_merge_settings, apply_track_setting, frame_tracks, list_images, load_rgb_u8, merge_cand_cap, merge_passes,
-                                     names_for, one_forward_merge, run_frame_views, run_seq_clips, seq_on, track_on, views_per_frame, write_tubelets)
+                                     names_for, one_forward_merge, run_frame_views, run_seq_clips, seq_on, set_group_streams, track_on, views_per_frame,
+                                     write_tracks, write_tubelets)
 
     if a.prototxt:
         text = open(a.prototxt).read()
@@ -252,6 +255,7 @@ def main(argv=None):
             used += time.perf_counter() - t0
             net.detect_cascade_merge_add([dict(p, nms_overlap=a.nms_overlap) for p in params], outputs, cls_ids, det_thr=a.det_thr,
                                          views=[dict(flip_x=1)] if flipped else None)
+        set_group_streams(net, a, k - 1, 1)
         per_image, _ = net.detect_merge_end()
         trks = frame_tracks(net, a)
         for (o, c) in results:
@@ -275,6 +279,7 @@ def main(argv=None):
         net.forward()
         torch.cuda.synchronize(a.device)
         used += time.perf_counter() - t0                                     # :88-89: forward only
+        set_group_streams(net, a, g0, len(group))
         per_image, _ = net.detect_cascade_multi([dict(p, nms_overlap=a.nms_overlap) for p in params], outputs, cls_ids, det_thr=a.det_thr)
         if a.dump_blobs:
             os.makedirs(a.dump_blobs, exist_ok=True)
@@ -298,7 +303,7 @@ def main(argv=None):
             write_tubelets(os.path.join(a.tubelets_out, f"{a.comp_id}_{names[cls_ids[c] - 1]}_{out_names[o]}.txt"), dets, tubes[(o, c)])
         if track_on(a) and a.tracks_out:
             out = os.path.join(a.tracks_out, f"{a.comp_id}_{names[cls_ids[c] - 1]}_{out_names[o]}.txt")
-            write_tubelets(out, dets, tracks[(o, c)])
+            out = ", ".join(write_tracks(out, dets, tracks[(o, c)], a.streams))
             print(f"{out}: {len(set(int(v) for t in tracks[(o, c)] for v in t) - {0})} tracks over {len(files)} images")
     return 0
 

@@ -22,6 +22,7 @@ examples/kitti_result/writeDetForEval.m.
          [--seq-nms [avg|max]] [--clip T] [--seq-link THR] [--seq-top-k N] [--tubelets-out DIR]      # Seq-NMS over clips of T frames (Net.set_seq_nms)
          [--track] [--track-high T] [--track-low T] [--track-match THR] [--track-motion none|linear] [--track-max-age N] [--track-min-hits N]
          [--tracks-out DIR]                                  # track ids across the frames of the run (Net.set_tracker)
+         [--track --streams N --batch B]                     # the frames are N multiplexed cameras: a table of tracks per camera
   python tools/run_mscnn_detection.py --model kitti_car/mscnn-7s-576 --synthetic 8      # no dataset / weights at hand: the generated
                                                                                         # deploy net, seeded weights, synthetic frames
 
@@ -105,7 +106,12 @@ through --track-max-age N missed frames (default 30) and shows its id from its -
 frames run in groups of one through Net.detect_multi; with --batch a group is B consecutive frames; with --scales / --flip / --tiles /
 --vote / --soft-nms / --matrix-nms the tracker runs behind the frame's merge, with --seq-nms behind the clip's (the ids live on over
 the clip boundary).  Refused together with --wbf, --rois-in and --proposals-only.  The result files are unchanged; --tracks-out DIR
-adds DIR/<comp_id>_<class>.txt with rows [image_index track x y w h score], track 0 = no confirmed track.  No pin on the reference,
+adds DIR/<comp_id>_<class>.txt with rows [image_index track x y w h score], track 0 = no confirmed track.
+--streams N (with --track): the input is N cameras multiplexed, frame i of the input order (0-based) belongs to stream i % N, and
+every stream has a table of tracks of its own (Net.set_tracker(streams=N); Net.set_frame_streams before every forward, from the
+frames' own indices, so --batch B need not be a multiple of N).  One launch steps all the streams of a forward side by side.  Not with
+--seq-nms (a clip is one stream).  --tracks-out then writes one file per stream, DIR/<comp_id>_<class>_stream<s>.txt, with the rows
+and the 1-based image index that stream alone would have.  No pin on the reference,
 whose scripts look at no other frame; accuracy was not evaluated (no labels here).
 
 Everything here is host glue over calls the test-suite covers one by one (Net.set_image / set_images / set_image_views, forward,
@@ -238,6 +244,9 @@ def add_merge_flags(ap):
                     "(none) or moves on with its smoothed centre velocity (linear, the default)")
     ap.add_argument("--track-max-age", type=int, default=30, metavar="N", help="with --track: a track lives through N missed frames (default 30)")
     ap.add_argument("--track-min-hits", type=int, default=1, metavar="N", help="with --track: a track shows its id from its N-th hit on (default 1)")
+    ap.add_argument("--streams", type=int, default=1, metavar="N", help="with --track: the frames are N multiplexed cameras, frame i of the "
+                    "input order belongs to stream i %% N and every stream has its own tracks (Net.set_tracker(streams=N), "
+                    "Net.set_frame_streams per forward); --tracks-out writes one file per stream.  Not with --seq-nms")
     ap.add_argument("--tracks-out", default=None, metavar="DIR", help="with --track: DIR/<comp_id>_<class>.txt with rows [image_index track x y w h "
                     "score]; track 0 = no confirmed track")
     ap.add_argument("--soft-thr", type=float, default=0.001, metavar="T", help="with --soft-nms: stop picking when the best live score is below T; "
@@ -278,7 +287,27 @@ def apply_track_setting(net, a):
     """The sticky tracker setting of the run, once, before its first frame."""
     if track_on(a):
         net.set_tracker(high_thr=a.track_high, low_thr=a.track_low, match_thr=a.track_match, motion=a.track_motion, max_age=a.track_max_age,
-                        min_hits=a.track_min_hits)
+                        min_hits=a.track_min_hits, streams=a.streams)
+
+
+def set_group_streams(net, a, first, count):
+    """--streams N: in front of a tracked call over the frames first .. first + count - 1 of the run (0-based), frame i is stream i % N."""
+    if track_on(a) and a.streams > 1:
+        net.set_frame_streams([(first + i) % a.streams for i in range(count)])
+
+
+def write_tracks(path, per_frame_dets, per_frame_ids, streams=1):
+    """--tracks-out: the file `path` (write_tubelets' rows); with --streams N > 1 one file per stream, `path` with _stream<s> in front of
+    its extension, holding the frames of that stream numbered from 1.  Returns the paths written."""
+    if streams <= 1:
+        write_tubelets(path, per_frame_dets, per_frame_ids)
+        return [path]
+    stem, ext = os.path.splitext(path)
+    out = []
+    for s in range(streams):
+        out.append(f"{stem}_stream{s}{ext}")
+        write_tubelets(out[-1], per_frame_dets[s::streams], per_frame_ids[s::streams])
+    return out
 
 
 def frame_tracks(net, a):
@@ -362,6 +391,12 @@ def check_merge_flags(ap, a):
             ap.error(f"--track-match {a.track_match:g}: the threshold must lie inside [0, 1)")
         if a.track_max_age < 0 or a.track_min_hits < 1:
             ap.error(f"--track-max-age {a.track_max_age} must be >= 0, --track-min-hits {a.track_min_hits} >= 1")
+        if not 1 <= a.streams <= 256:
+            ap.error(f"--streams {a.streams}: 1 .. 256 streams")
+        if a.streams > 1 and seq_on(a):
+            ap.error(f"--streams {a.streams} and --seq-nms exclude each other: a clip links every frame to the one before it, so it is one stream")
+    elif a.streams != 1:
+        ap.error(f"--streams {a.streams} belongs to --track")
     elif (a.track_high != 0.5 or a.track_low != 0.1 or a.track_match != 0.3 or a.track_motion != "linear" or a.track_max_age != 30
           or a.track_min_hits != 1 or a.tracks_out is not None):
         ap.error("--track-high / --track-low / --track-match / --track-motion / --track-max-age / --track-min-hits / --tracks-out belong to --track")
@@ -681,6 +716,7 @@ def run_merged(a, net, text, files, names, cls_ids, imgH, imgW, per_class):
             used += time.perf_counter() - t0                                  # forwards only, as :72-73
             p = dict(ratios=(H / float(orgH), W / float(orgW)), org_hw=(orgH, orgW), proposal_thr=a.proposal_thr, nms_overlap=a.nms_overlap)
             net.detect_merge_add([p], cls_ids, views=[dict(flip_x=1)] if flipped else None)
+        set_group_streams(net, a, k - 1, 1)
         per_image, _ = net.detect_merge_end()
         a.track_ids += frame_tracks(net, a) or []
         by_type = {}
@@ -730,6 +766,7 @@ def run_batched(a, net, files, names, cls_ids, imgH, imgW, per_class, per_image_
                 print(f"idx {k}/{len(files)}, avgtime={used / k:.4f}s")
             continue
         if ran:
+            set_group_streams(net, a, g0, len(group))
             per_image, _ = net.detect_multi([dict(p, proposal_thr=a.proposal_thr, nms_overlap=a.nms_overlap) for p in params], cls_ids)
             a.track_ids += frame_tracks(net, a) or []
         else:
@@ -757,7 +794,7 @@ def finish(a, names, cls_ids, per_class, per_image_props, n_files):
         print(f"{out}: {sum(len(p) for p in per_image_props)} proposals over {n_files} images")
     for ci, c in enumerate(cls_ids if track_on(a) and a.tracks_out else []):
         out = os.path.join(a.tracks_out, f"{a.comp_id}_{names[c - 1]}.txt")
-        write_tubelets(out, per_class[c], [t[ci] for t in a.track_ids])
+        out = ", ".join(write_tracks(out, per_class[c], [t[ci] for t in a.track_ids], a.streams))
         print(f"{out}: {len(set(int(v) for t in a.track_ids for v in t[ci]) - {0})} tracks over {n_files} images")
 
 
