@@ -1072,6 +1072,87 @@ MSCNN_API int mscnn_tracks_update_streams_fwd(const mscnn_track_params* params, 
                                               const void* state_in, void* state_out, int max_tracks, int* track_ids_dev, void* stream);
 MSCNN_API int mscnn_tracks_state_reset_slots(void* state, int num_slots_total, int max_tracks, int first_slot, int count, void* stream);
 
+/* The render stage: the `show` block at the end of the reference's demo scripts (examples/kitti_car/run_mscnn_detection.m,
+ * examples/caltech/run_mscnn_detection.m, examples/widerface/run_cascademscnn.m:136-150: every box with score >= show_thr drawn on
+ * the frame, its score at the top edge) for the frames of a multi pack, in one device pass: outlines, an optional fill, labels
+ * (score, track id) and an optional pixelation of the boxes' interiors (the face nets' use: anonymise a frame before it leaves the
+ * machine).  Out of place: frame b is read from src_rgb[b] and its annotated copy written to dst_rgb[b], both uint8
+ * [org_h[b]][org_w[b]][3] (RGB), every frame of its own size.  EVERY byte of every dst frame is written (a copy of src where nothing
+ * is painted) and no other byte; src, the pack and the ids are only read.
+ * The pack is the multi pack every final-stage op writes, mscnn_multi_pack_layout_of(num_frames * num_slots, cap); segment t * K + k
+ * (K = num_slots) is slot k of frame t, its rows found by the rule of mscnn_tracks_update_fwd's step 2: entry {count, rows, row0, 0};
+ * row offset = row0, unless K >= 2 and the entries of the frame's slots 0 and 1 hold the same row0 (the shared-row0 form of
+ * mscnn_detections_multi_fwd), then K * row0 + k * rows.  A segment with count < 0, a negative offset or offset + count > cap is
+ * empty.  Rows are [x y w h score] doubles in the frame's own pixels, as the scripts hand them to rectangle().  track_ids_dev[cap]
+ * (mscnn_tracks_update_fwd's output: one id per pack row, <= 0 = no confirmed track) may be NULL when nothing asks for an id.
+ * From the rounding on the semantics are integers only:
+ *   Footprint of a row.  L = floor(x + .5), T = floor(y + .5), R = floor((x + w) + .5) - 1, Bt = floor((y + h) + .5) - 1, in double.
+ *     A row is NOT DRAWN when !(score >= show_thr); when one of its five values is not finite; when |x|, |y|, |w| or |h| exceeds 2^30;
+ *     when R < L or Bt < T; or when its box [L, R] x [T, Bt] holds no pixel of the frame (then it has no label either).  Otherwise
+ *     clipping to the frame is implicit: pixels outside the frame do not exist.
+ *   Paint order within a frame.  Slots in ascending k; within a slot the rows in DESCENDING index, so that row 0, the best score, is
+ *     painted last and lies on top.  A pixel starts as the source pixel and takes from every drawn row, in that order:
+ *     (a) pixelate = P > 0 and the pixel inside the box: the value BECOMES the rounded mean (sum + n / 2) / n, per channel, of the
+ *         SOURCE frame over the pixel's block.  Blocks are P x P, anchored at (L, T) -- block (i, j) covers columns [L + i P,
+ *         L + i P + P) and rows [T + j P, T + j P + P) -- and clipped to the box and to the frame; n = the pixels left.  This
+ *         discards whatever earlier rows painted at that pixel (their outlines and labels too): the mosaic shows the source only.
+ *     (b) fill_alpha > 0 and the pixel inside the box: v = blend(v, col, fill_alpha).
+ *     (c) thickness > 0 and the pixel inside the box and less than `thickness` pixels from one of its four edges (px - L, R - px,
+ *         py - T or Bt - py < thickness): v = blend(v, col, outline_alpha).
+ *     (d) the pixel inside the row's label rectangle: v = col, opaque; a glyph pixel takes the ink instead, black (0, 0, 0) when
+ *         299 r + 587 g + 114 b >= 128000 for col = (r, g, b) and white (255, 255, 255) otherwise.
+ *     blend(v, c, a) = (v * (256 - a) + c * a + 128) >> 8 per channel.
+ *   Colour.  color_by 0: colors[k % num_colors].  color_by 1: colors[id % num_colors] when the row's id > 0, else the slot's colour.
+ *   Label text.  The score prints as the scripts' %.2f: c = floor(score * 100 + .5) clamped to [0, 100], "0.NN" or "1.00".  The id
+ *     prints as its decimal digits.  label 1: the score.  label 2: the id; a row with id <= 0 has no label.  label 3: "ID 0.NN", one
+ *     blank cell between the two; a row with id <= 0 has the score alone.
+ *   Label geometry.  A character is a cell of 6 x 8 (w x h) pixels, each magnified to label_scale x label_scale; the 5 x 7 glyph sits
+ *     in the cell's columns 1 .. 5 and rows 1 .. 7 (column 0 and row 0 stay blank).  The rectangle is chars * 6 * scale wide and
+ *     8 * scale high.  Its bottom row is T - 1 and its left column L; if that puts its top row above the frame (< 0), its top row is
+ *     T instead (inside the box); if its right end is past the frame's right edge, it is shifted left to end there, but not below
+ *     column 0.  The bitmaps (csrc/render_glyphs.h) were drawn for this project; mscnn_render_glyph_rows(ch, rows) returns the seven
+ *     rows of '0' .. '9', '.' or ' ' (bit 4 = the left column) and refuses every other ch.
+ * One launch per 32 frames, the frame table by value in the arguments, no workspace, no host read.  Parallel over PIXELS: a workgroup
+ * of 256 threads owns a 64 x 16 tile of a frame; its threads walk the frame's rows in paint order, 256 at a time, keep those whose
+ * box or label rectangle meets the tile -- compacted in order into LDS by ballots and popcounts --, and every pixel then walks that
+ * short list; chunk after chunk, so the order holds across chunks.  With pixelate on a pixel first looks for the LAST row of the chunk
+ * that pixelates it and starts there (what earlier rows painted is discarded anyway): one mean per pixel and chunk, read straight
+ * from the source.  Every loop bound and every value that guards a barrier is a kernel argument or a pack word clamped against cap, the
+ * same in every thread: a garbage pack draws garbage boxes but lengthens no loop past num_slots * cap rows and moves no read outside
+ * the pack or the ids.  No atomics, nothing spins, no workgroup waits on another; byte stores only (alignment 1).
+ * Refused before any launch, naming the value: a null params / src_rgb / dst_rgb / org_h / org_w / pack_dev, a null frame pointer
+ * (with its index), num_frames < 1, num_slots < 1, cap < 1 (or num_frames * num_slots * cap past 2^31 - 1), a frame size <= 0 or
+ * above 2^30, thickness outside [0, 64], an alpha outside [0, 256], label outside [0, 3], label_scale outside [1, 8], color_by
+ * outside {0, 1}, pixelate 1, negative or above 64, num_colors outside [1, 32], a NaN show_thr, label >= 2 or color_by 1 with a null
+ * track_ids_dev, pack_dev not 16-byte aligned, track_ids_dev not 4-byte aligned, a dst frame that overlaps a src frame or another
+ * dst frame (in place is refused too).
+ * No pin on the reference: MATLAB's rectangle() and text() draw through the figure's renderer, nothing a kernel could be held to
+ * bit for bit.  The check is tests/render_witness.py, a numpy restatement of the rules above with plain loops, byte for byte.  The
+ * look of the glyphs and of the palette is a matter of taste that no test judges. */
+#ifndef MSCNN_RENDER_PARAMS_DEFINED
+#define MSCNN_RENDER_PARAMS_DEFINED
+typedef struct {
+  double show_thr;        /* a row with !(score >= show_thr) is not drawn (NaN: not drawn) */
+  int thickness;          /* outline width in pixels, inwards from the box edge; 0: none; at most 64 */
+  int outline_alpha;      /* 0 .. 256 */
+  int fill_alpha;         /* 0 .. 256, the box's whole area under the outline; 0: none */
+  int label;              /* 0 none, 1 score, 2 track id, 3 id and score */
+  int label_scale;        /* integer glyph magnification, 1 .. 8 */
+  int color_by;           /* 0: the slot (class / output x class), 1: the track id */
+  int pixelate;           /* 0 off, else the mosaic block edge, 2 .. 64 */
+  int num_colors;         /* 1 .. 32 */
+  unsigned char colors[32][3];   /* RGB */
+} mscnn_render_params;
+#endif
+enum { MSCNN_RENDER_FRAMES_PER_LAUNCH = 32 };
+/* Alignment: pack_dev 16, track_ids_dev 4 (refused); frames 1. */
+MSCNN_API int mscnn_render_detections_u8(const mscnn_render_params* p,
+        const unsigned char* const* src_rgb /* HOST array of num_frames device pointers */,
+        unsigned char* const* dst_rgb       /* HOST array of num_frames device pointers */,
+        const int* org_h, const int* org_w, int num_frames, int num_slots,
+        const void* pack_dev, int cap, const int* track_ids_dev /* [cap] or NULL */, void* stream);
+MSCNN_API int mscnn_render_glyph_rows(int ch, unsigned char rows[7]);
+
 /* The proposal half of the scripts' result (run_mscnn_detection.m:75-91, `final_proposals{k}`) for every image of a batched forward
  * in one pass.  props [R_all][6] = BoxOutput's proposals_score, rows [img x1 y1 x2 y2 score] grouped by image in ascending order;
  * desc[num_images], one per image.  Per image, in the script's types and order: w = x2 - x1, h = y2 - y1 in fp32 (no + 1); a row

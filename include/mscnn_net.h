@@ -536,6 +536,41 @@ MSCNN_NET_API int mscnn_net_set_tracker_streams(mscnn_net* net, int num_streams)
 MSCNN_NET_API int mscnn_net_set_frame_streams(mscnn_net* net, const int* stream_of /* HOST, [count]; NULL: clear */, int count);
 MSCNN_NET_API int mscnn_net_get_tracker_streams(const mscnn_net* net, int* num_streams, int* stream_of, int cap, int* count);
 MSCNN_NET_API int mscnn_net_tracker_reset_stream(mscnn_net* net, int s);
+/* Draw the detections into the frames (mscnn_hip.h: mscnn_render_detections_u8, whose comment is the contract: footprints, paint
+ * order, blend, labels, pixelation): the `show` block at the end of the reference's demo scripts, on the device.  It renders the pack
+ * of the LAST mscnn_net_detect_multi, mscnn_net_detect_cascade_multi or mscnn_net_detect_merge_end on this net -- the Net still holds
+ * it, as mscnn_net_detect_tracks reads that call's ids -- and, if that call ran the tracker, the tracker's id buffer.  frames_rgb: a
+ * HOST array of count host pointers (device pointers when on_device != 0), frame b uint8 [org_h[b]][org_w[b]][3]: the frames that
+ * call detected on, in its order (image b, or list b of the merge).  out_rgb: count host pointers (device pointers when
+ * out_on_device != 0) to buffers of the same sizes, every byte of which is written; they must not overlap the frames or each other.
+ * The pack (and the ids) go to a device buffer of the render stage's own in one copy, host frames are staged through buffers of its
+ * own -- never through the buffer of mscnn_net_set_images, which may already hold the next forward's frames --, one launch per 32
+ * frames on the net's stream; host outputs come back behind ONE synchronisation, device outputs are left asynchronous on that
+ * stream.  It reads the pack and steps nothing: what mscnn_net_detect_tracks and mscnn_net_tracker_state return is unchanged.
+ * Refused, naming the values: before any of the three calls has succeeded, or when another call that lands its result in the same
+ * block (mscnn_net_detect, _detect_image, _detect_cascade, _proposals_multi, a failed call) has run since; a count that is not that
+ * call's number of images or lists (both numbers); label >= 2 or color_by 1 when that call ran no tracker; a null frame; and
+ * everything the op refuses.
+ * NOT covered: the single-pack calls mscnn_net_detect and mscnn_net_detect_begin / _end (and the _device forms, whose pack the caller
+ * owns: hand it to the op).  A batch of one through mscnn_net_detect_multi serves them. */
+#ifndef MSCNN_RENDER_PARAMS_DEFINED      /* include/mscnn_hip.h's struct, repeated here so that this header stands alone */
+#define MSCNN_RENDER_PARAMS_DEFINED
+typedef struct {
+  double show_thr;        /* a row with !(score >= show_thr) is not drawn (NaN: not drawn) */
+  int thickness;          /* outline width in pixels, inwards from the box edge; 0: none; at most 64 */
+  int outline_alpha;      /* 0 .. 256 */
+  int fill_alpha;         /* 0 .. 256, the box's whole area under the outline; 0: none */
+  int label;              /* 0 none, 1 score, 2 track id, 3 id and score */
+  int label_scale;        /* integer glyph magnification, 1 .. 8 */
+  int color_by;           /* 0: the slot (class / output x class), 1: the track id */
+  int pixelate;           /* 0 off, else the mosaic block edge, 2 .. 64 */
+  int num_colors;         /* 1 .. 32 */
+  unsigned char colors[32][3];   /* RGB */
+} mscnn_render_params;
+#endif
+MSCNN_NET_API int mscnn_net_render(mscnn_net* net, const unsigned char* const* frames_rgb, int on_device,
+                                   const int* org_h, const int* org_w, int count, const mscnn_render_params* p,
+                                   unsigned char* const* out_rgb, int out_on_device);
 /* The views of a frame as ONE batched forward (mscnn_hip.h: mscnn_detections_candidates_add_views): the merge was opened with
  * _begin(num_frames, ...), the input holds N images -- the views mscnn_net_set_image_views wrote --, p[N * K] and view[N] describe
  * them as in _add, and list_of[N] (host) names the frame of each: the rows of image b go to the lists of frame list_of[b].  One

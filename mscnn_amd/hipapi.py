@@ -257,6 +257,9 @@ def lib():
         L.mscnn_tracks_state_reset_slots.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.mscnn_tracks_update_streams_fwd.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                                       C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.mscnn_render_detections_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                                 C.c_void_p, C.c_void_p]
+        L.mscnn_render_glyph_rows.argtypes = [C.c_int, C.c_void_p]
         L.mscnn_proposals_multi_pack_bytes.restype = C.c_size_t
         L.mscnn_proposals_multi_pack_bytes.argtypes = [C.c_int, C.c_int]
         L.mscnn_proposals_multi_fwd.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
@@ -1465,6 +1468,65 @@ def tracks_state_reset_slots(state, num_slots_total, max_tracks, first_slot, cou
     stream of several starts again, the others keep their tracks).  Returns state."""
     _check(lib().mscnn_tracks_state_reset_slots(_dev(state), num_slots_total, max_tracks, first_slot, count, _stream()))
     return state
+
+
+# ---- the render stage (mscnn_hip.h: mscnn_render_detections_u8) ----
+RENDER_LABELS = {"none": 0, "score": 1, "id": 2, "both": 3}
+RENDER_COLOR_BY = {"slot": 0, "id": 1}
+RENDER_MAX_COLORS = 32
+
+
+class RenderParams(C.Structure):
+    """mscnn_render_params (136 bytes)."""
+    _fields_ = [("show_thr", C.c_double), ("thickness", C.c_int), ("outline_alpha", C.c_int), ("fill_alpha", C.c_int), ("label", C.c_int),
+                ("label_scale", C.c_int), ("color_by", C.c_int), ("pixelate", C.c_int), ("num_colors", C.c_int),
+                ("colors", (C.c_ubyte * 3) * RENDER_MAX_COLORS)]
+
+
+def render_params(colors, show_thr=0.3, thickness=2, outline_alpha=256, fill_alpha=0, label="score", label_scale=1, color_by="slot", pixelate=0):
+    """A RenderParams; label and color_by by name (RENDER_LABELS, RENDER_COLOR_BY) or by number, colors a sequence of 1 .. 32 RGB
+    triples.  The values are checked by the op, which names the one it refuses."""
+    for name, table, v in (("label", RENDER_LABELS, label), ("color_by", RENDER_COLOR_BY, color_by)):
+        if isinstance(v, str) and v not in table:
+            raise MscnnError(f"render: {name} {v!r} is none of {sorted(table)}")
+    cols = [tuple(int(v) for v in c) for c in colors]
+    if len(cols) > RENDER_MAX_COLORS or any(len(c) != 3 or min(c) < 0 or max(c) > 255 for c in cols):
+        raise MscnnError(f"render: colors holds {len(cols)} entries (at most {RENDER_MAX_COLORS} RGB triples of 0 .. 255)")
+    p = RenderParams(float(show_thr), int(thickness), int(outline_alpha), int(fill_alpha), int(RENDER_LABELS.get(label, label)),
+                     int(label_scale), int(RENDER_COLOR_BY.get(color_by, color_by)), int(pixelate), len(cols))
+    for i, c in enumerate(cols):
+        p.colors[i][:] = c
+    return p
+
+
+def render_glyph_rows(ch):
+    """mscnn_render_glyph_rows: the seven rows of the 5 x 7 glyph of ch ('0' .. '9', '.', ' '), bit 4 = the left column.  No device."""
+    rows = (C.c_ubyte * 7)()
+    _check(lib().mscnn_render_glyph_rows(ord(ch), rows))
+    return tuple(rows)
+
+
+def render_detections(params, frames, num_slots, pack, cap, ids=None, out=None):
+    """mscnn_render_detections_u8: the detections of a multi pack of len(frames) x num_slots segments with cap rows (a uint8 device
+    tensor) drawn into copies of frames (uint8 [h, w, 3] contiguous cuda tensors, each of its own size); ids: the tracker's int32
+    [cap] buffer or None.  out: the tensors to write (None: new ones).  Returns out."""
+    B = len(frames)
+    if out is None:
+        out = [torch.empty_like(f) for f in frames]
+    if len(out) != B:
+        raise MscnnError(f"render: {len(out)} output frames for {B} frames")
+    for b, (f, o) in enumerate(zip(frames, out)):
+        for t, what in ((f, "frame"), (o, "output frame")):
+            if t.dim() != 3 or t.shape[2] != 3 or t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous():
+                raise MscnnError(f"render: {what} {b} is not a contiguous uint8 [H, W, 3] cuda tensor")
+        if o.shape != f.shape:
+            raise MscnnError(f"render: output frame {b} is {tuple(o.shape)}, the frame {tuple(f.shape)}")
+    oh = (C.c_int * max(B, 1))(*[int(f.shape[0]) for f in frames])
+    ow = (C.c_int * max(B, 1))(*[int(f.shape[1]) for f in frames])
+    src = (C.c_void_p * max(B, 1))(*[f.data_ptr() for f in frames])
+    dst = (C.c_void_p * max(B, 1))(*[o.data_ptr() for o in out])
+    _check(lib().mscnn_render_detections_u8(C.byref(params), src, dst, oh, ow, B, num_slots, _dev(pack), cap, _dev(ids), _stream()))
+    return out
 
 
 # ---- health of the plane-GEMM kernel's stream-K hand-off (mscnn_hip.h) ----

@@ -67,6 +67,15 @@ struct mscnn_net {
   std::vector<int> track_stream_of;
   std::vector<char> track_reset_pending;   // mscnn_net_tracker_reset_stream: streams to reset in front of the next tracked call's update
   std::vector<int> track_ids, track_seg_dets;
+  // mscnn_net_render: what the last detect_multi / detect_cascade_multi / detect_merge_end left in det_host -- the pack of `frames` x
+  // `slots` segments with `cap` rows and, when that call ran the tracker, its ids at ids_at (bytes: both).  Any other user of det_host
+  // ends it (ensure_det_host).  The stage's own device buffers: the pack's copy, the staged host frames, the frames to hand back.
+  struct Render {
+    bool valid = false, ids = false;
+    int frames = 0, slots = 0, cap = 0;
+    size_t bytes = 0, ids_at = 0;
+    caffe::DeviceBuffer pack, in, out;
+  } render;
   // mscnn_net_detect_merge_*: the candidate lists of the forwards added since _begin (mscnn_hip.h: mscnn_detections_candidates_*)
   struct Merge {
     bool open = false;
@@ -824,6 +833,7 @@ size_t mscnn_net_detect_pack_bytes(int cap) {
 // [row0, row0 + rows) of the ROI blobs (rows < 0: all of them -- the batch-1 form)
 // the net's host-side landing place for packs: host-coherent pinned memory, also addressable by the device (det_host_dev)
 static void ensure_det_host(mscnn_net* n, size_t total) {
+  n->render.valid = false;      // (the block is about to be written again: mscnn_net_render has nothing to read until a call says so)
   if (n->det_host_bytes >= total) return;
   if (n->det_host) HIP_CHECK(hipHostFree(n->det_host));
   n->det_host = nullptr; n->det_host_bytes = 0; n->det_host_dev = nullptr;
@@ -1201,6 +1211,14 @@ static bool detect_multi_into_pack(mscnn_net* n, const mscnn_detect_params* p, i
                             pack_at, pack_out);
 }
 
+// mscnn_net_render's record of the pack a blocking call has just left in det_host (ids: the tracker's ids lie at ids_at behind it)
+static void render_keep(mscnn_net* n, int frames, int slots, int cap, bool ids, size_t ids_at) {
+  mscnn_net::Render& r = n->render;
+  r.frames = frames; r.slots = slots; r.cap = cap; r.ids = ids; r.ids_at = ids_at;
+  r.bytes = ids ? ids_at + (size_t)(cap > 0 ? cap : 1) * sizeof(int) : mscnn_multi_pack_layout_of(frames * slots, cap).total;
+  r.valid = true;
+}
+
 // The blocking form of both one-pass calls.  As mscnn_net_detect: the kernels write the pack straight into host-coherent pinned memory,
 // one stream synchronisation, no copy; the per-segment fallback leaves it in the device pack and copies it.  rows_all: validates and
 // returns R_all (the pack gets K R_all rows); into_pack(pack rows, pack_at, &pack): segments_into_pack's result.
@@ -1250,6 +1268,7 @@ static void detect_segments_blocking(mscnn_net* n, const char* name, int num_ima
     n->track_seg_dets.assign(seg_dets, seg_dets + S);
     n->tracks_valid = true;
   }
+  if (tracked) render_keep(n, num_images, K, pcap, track, ids_at);
 }
 
 size_t mscnn_net_detect_multi_pack_bytes(int num_images, int num_classes, int cap) {
@@ -1855,6 +1874,51 @@ int mscnn_net_detect_merge_end(mscnn_net* n, double* dets_host, int* pass_host, 
       for (int s = 0; s < S; ++s) n->track_ids.insert(n->track_ids.end(), th + (size_t)s * m.cand_cap, th + (size_t)s * m.cand_cap + seg_dets[s]);
       n->track_seg_dets.assign(seg_dets, seg_dets + S);
       n->tracks_valid = true;
+    }
+    render_keep(n, m.images, m.slots, S * m.cand_cap, track, tracks_at);
+  });
+}
+
+// The render stage (mscnn_hip.h: mscnn_render_detections_u8) on the pack the last blocking multi call left in det_host.  The pack and
+// the ids go to the stage's own device buffer in one copy (the kernel's workgroups each walk all its rows: not over the bus), host
+// frames are staged through the stage's own buffers -- img_in may already hold the next forward's frames.
+int mscnn_net_render(mscnn_net* n, const unsigned char* const* frames_rgb, int on_device, const int* org_h, const int* org_w, int count,
+                     const mscnn_render_params* p, unsigned char* const* out_rgb, int out_on_device) {
+  return guarded([&] {
+    CHECK(n && frames_rgb && org_h && org_w && p && out_rgb) << "render: null pointer";
+    mscnn_net::Render& r = n->render;
+    CHECK(r.valid) << "render: no pack to render: the last call that used the net's pack block was not a successful mscnn_net_detect_multi, "
+                      "mscnn_net_detect_cascade_multi or mscnn_net_detect_merge_end";
+    CHECK_EQ(count, r.frames) << "render: " << count << " frames, that call had " << r.frames << " images (lists)";
+    CHECK(r.ids || (p->label < 2 && p->color_by == 0))
+        << "render: label " << p->label << ", color_by " << p->color_by << " need track ids, and that call ran no tracker (mscnn_net_set_tracker)";
+    for (int b = 0; b < count; ++b)
+      CHECK(frames_rgb[b] && out_rgb[b] && org_h[b] > 0 && org_w[b] > 0)
+          << "render: frame " << b << " is " << org_h[b] << " x " << org_w[b] << (frames_rgb[b] && out_rgb[b] ? "" : " at a null pointer");
+    hipStream_t st = (hipStream_t)Caffe::stream();
+    char* pack = static_cast<char*>(r.pack.Reserve(r.bytes));
+    HIP_CHECK(hipMemcpyAsync(pack, n->det_host, r.bytes, hipMemcpyHostToDevice, st));
+    std::vector<size_t> off(count + 1, 0);
+    for (int b = 0; b < count; ++b) off[b + 1] = off[b] + (((size_t)org_h[b] * org_w[b] * 3 + 255) & ~(size_t)255);
+    std::vector<const unsigned char*> src(frames_rgb, frames_rgb + count);
+    std::vector<unsigned char*> dst(out_rgb, out_rgb + count);
+    if (!on_device) {
+      unsigned char* d = static_cast<unsigned char*>(r.in.Reserve(off[count]));
+      for (int b = 0; b < count; ++b) {
+        HIP_CHECK(hipMemcpyAsync(d + off[b], frames_rgb[b], (size_t)org_h[b] * org_w[b] * 3, hipMemcpyHostToDevice, st));
+        src[b] = d + off[b];
+      }
+    }
+    if (!out_on_device) {
+      unsigned char* d = static_cast<unsigned char*>(r.out.Reserve(off[count]));
+      for (int b = 0; b < count; ++b) dst[b] = d + off[b];
+    }
+    MSCNN_CHECK(mscnn_render_detections_u8(p, src.data(), dst.data(), org_h, org_w, count, r.slots, pack, r.cap,
+                                           r.ids ? reinterpret_cast<const int*>(pack + r.ids_at) : nullptr, st));
+    if (!out_on_device) {      // every frame's copy, then the one synchronisation
+      for (int b = 0; b < count; ++b)
+        HIP_CHECK(hipMemcpyAsync(out_rgb[b], dst[b], (size_t)org_h[b] * org_w[b] * 3, hipMemcpyDeviceToHost, st));
+      HIP_CHECK(hipStreamSynchronize(st));
     }
   });
 }

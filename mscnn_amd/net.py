@@ -44,6 +44,19 @@ class TrackParams(C.Structure):
                 ("match_thr_low", C.c_double), ("vel_gain", C.c_double), ("motion", C.c_int), ("max_age", C.c_int), ("min_hits", C.c_int)]
 
 
+class RenderParams(C.Structure):
+    """mscnn_render_params (include/mscnn_net.h; 136 bytes): what the render stage draws."""
+    _fields_ = [("show_thr", C.c_double), ("thickness", C.c_int), ("outline_alpha", C.c_int), ("fill_alpha", C.c_int), ("label", C.c_int),
+                ("label_scale", C.c_int), ("color_by", C.c_int), ("pixelate", C.c_int), ("num_colors", C.c_int),
+                ("colors", (C.c_ubyte * 3) * 32)]
+
+
+RENDER_LABELS = {"none": 0, "score": 1, "id": 2, "both": 3}
+RENDER_COLOR_BY = {"slot": 0, "id": 1}
+# the default palette of Net.render: eight hues that stay apart on a road scene, RGB (the look is a matter of taste no test judges)
+RENDER_PALETTE = ((230, 25, 75), (60, 180, 75), (255, 225, 25), (0, 130, 200), (245, 130, 48), (145, 30, 180), (70, 240, 240),
+                  (240, 50, 230))
+
 TRACK_MOTIONS = {"none": 1, "linear": 2}
 # mscnn_track_record and a slot's header (include/mscnn_hip.h: mscnn_tracks_state_layout_of)
 TRACK_RECORD = np.dtype([("box", "<f8", 4), ("obs", "<f8", 4), ("vel", "<f8", 2), ("score", "<f8"), ("id", "<i4"), ("hits", "<i4"),
@@ -135,6 +148,7 @@ def lib():
             "mscnn_net_detect_tracks": [vp, vp, ci, vp], "mscnn_net_tracker_state": [vp, vp, C.c_size_t],
             "mscnn_net_set_tracker_streams": [vp, ci], "mscnn_net_set_frame_streams": [vp, vp, ci],
             "mscnn_net_get_tracker_streams": [vp, vp, vp, ci, vp], "mscnn_net_tracker_reset_stream": [vp, ci],
+            "mscnn_net_render": [vp, vp, ci, vp, vp, ci, vp, vp, ci],
         }
         for name, args in sig.items():
             getattr(L, name).argtypes = args
@@ -725,6 +739,56 @@ class Net:
         _check(lib().mscnn_net_detect_tracks(self._h, ids.ctypes.data_as(C.c_void_p), D, seg.ctypes.data_as(C.c_void_p)))
         ends = np.cumsum(seg)
         return [[ids[ends[i * K + k] - seg[i * K + k]:ends[i * K + k]].copy() for k in range(K)] for i in range(B)]
+
+    def render(self, frames, thr=0.3, thickness=2, label="score", color_by="slot", pixelate=0, outline_alpha=256, fill_alpha=0,
+               label_scale=1, colors=RENDER_PALETTE, out=None):
+        """mscnn_net_render: the detections of the last detect_multi, detect_cascade_multi or detect_merge_end -- and its track ids, if
+        it ran the tracker -- drawn into copies of the frames it detected on: every box with score >= thr outlined (thickness pixels,
+        blended with outline_alpha of 256), filled with fill_alpha, labelled ("none", "score", "id", "both") in glyphs magnified
+        label_scale times, coloured by "slot" or by track "id" from colors (1 .. 32 RGB triples); pixelate = N replaces every box's
+        interior with an N x N mosaic of the source.  frames: uint8 [h, w, 3] numpy arrays, or contiguous uint8 CUDA tensors (then
+        nothing but the pack crosses the bus and the result is a list of CUDA tensors: out, or new ones); otherwise a list of numpy
+        arrays.  include/mscnn_hip.h (mscnn_render_detections_u8) states the pixels."""
+        for name, table, v in (("label", RENDER_LABELS, label), ("color_by", RENDER_COLOR_BY, color_by)):
+            if isinstance(v, str) and v not in table:
+                raise NetError(f"render: {name} {v!r} is none of {sorted(table)}")
+        cols = [tuple(int(v) for v in c) for c in colors]
+        if len(cols) > 32 or any(len(c) != 3 or min(c) < 0 or max(c) > 255 for c in cols):
+            raise NetError(f"render: colors holds {len(cols)} entries (at most 32 RGB triples of 0 .. 255)")
+        p = RenderParams(float(thr), int(thickness), int(outline_alpha), int(fill_alpha), int(RENDER_LABELS.get(label, label)),
+                         int(label_scale), int(RENDER_COLOR_BY.get(color_by, color_by)), int(pixelate), len(cols))
+        for i, c in enumerate(cols):
+            p.colors[i][:] = c
+        frames = list(frames)
+        on_dev = [hasattr(f, "is_cuda") and f.is_cuda for f in frames]
+        if any(on_dev) and not all(on_dev):
+            raise NetError("render: a list that mixes host and device frames")
+        device = any(on_dev)
+        if device:
+            import torch
+            for b, f in enumerate(frames):
+                if str(f.dtype) != "torch.uint8" or f.dim() != 3 or f.shape[2] != 3 or not f.is_contiguous():
+                    raise NetError(f"render: frame {b} is not a contiguous uint8 [h, w, 3] tensor")
+            keep = frames
+            outs = [torch.empty_like(f) for f in frames] if out is None else list(out)
+            if len(outs) != len(frames) or any(o.shape != f.shape or o.dtype != f.dtype or not o.is_cuda or not o.is_contiguous()
+                                               for o, f in zip(outs, frames)):
+                raise NetError("render: out does not hold one contiguous uint8 CUDA tensor of each frame's shape")
+            ptrs, optrs = [f.data_ptr() for f in frames], [o.data_ptr() for o in outs]
+        else:
+            keep = []
+            for b, f in enumerate(frames):
+                if not isinstance(f, np.ndarray) or f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3:
+                    raise NetError(f"render: frame {b} is not a uint8 [h, w, 3] array")
+                keep.append(np.ascontiguousarray(f))
+            outs = [np.empty_like(a) for a in keep]
+            ptrs, optrs = [a.ctypes.data for a in keep], [o.ctypes.data for o in outs]
+        B = len(frames)
+        hs = [int(f.shape[0]) for f in keep]
+        ws = [int(f.shape[1]) for f in keep]
+        _check(lib().mscnn_net_render(self._h, (C.c_void_p * max(B, 1))(*ptrs), 1 if device else 0, (C.c_int * max(B, 1))(*hs),
+                                      (C.c_int * max(B, 1))(*ws), B, C.byref(p), (C.c_void_p * max(B, 1))(*optrs), 1 if device else 0))
+        return outs
 
     def tracker_state(self, raw=False):
         """mscnn_net_tracker_state: the committed table, one dict per slot -- n, next_id, frame, dropped, skipped and tracks = the

@@ -63,6 +63,11 @@ DIR/<comp_id>_<class>_<output>.txt with rows [image_index track x y w h score], 
 --track: the frames are N multiplexed cameras, frame i belongs to stream i % N and has that stream's tracks, --tracks-out writes
 ..._stream<s>.txt per stream; not with --seq-nms); no pin on the reference,
 accuracy not evaluated.
+--render-out DIR [--show-thr T] [--render-label none|score|id|both] [--render-color slot|id] [--pixelate N]: the `show` block of
+run_cascademscnn.m:136-150 on the device (Net.render behind every detect_cascade_multi and detect_merge_end): DIR/<frame>.png with every
+box of every (output, class) with a score >= T (default 0.3, the script's show_thr) outlined and labelled; --pixelate N replaces the
+boxes' interiors with an N x N mosaic (anonymise the faces of a frame before it leaves the machine).  As tools/run_mscnn_detection.py;
+the result files are unchanged; the look of the glyphs and colours is nobody's pin.
 
 Everything here is host glue over calls the test-suite covers one by one (Net.set_images, forward, detect_cascade_multi,
 reshape_input, kitti.write_detections_dlm)."""
@@ -162,7 +167,7 @@ def main(argv=None):
     import torch
     from mscnn_amd import kitti, net as mnet, synth, zoo
     from run_mscnn_detection import (apply_merge_settings, apply_track_setting, frame_tracks, list_images, load_rgb_u8, merge_cand_cap, merge_passes,
-                                     names_for, one_forward_merge, run_frame_views, run_seq_clips, seq_on, set_group_streams, track_on, views_per_frame,
+                                     names_for, one_forward_merge, render_frames, run_frame_views, run_seq_clips, seq_on, set_group_streams, track_on, views_per_frame,
                                      write_tracks, write_tubelets)
 
     if a.prototxt:
@@ -258,6 +263,7 @@ def main(argv=None):
         set_group_streams(net, a, k - 1, 1)
         per_image, _ = net.detect_merge_end()
         trks = frame_tracks(net, a)
+        render_frames(net, a, [img], [path], k)
         for (o, c) in results:
             results[(o, c)].append(per_image[0][o * len(cls_ids) + c][0])
             if trks:
@@ -287,6 +293,7 @@ def main(argv=None):
             np.savez(os.path.join(a.dump_blobs, f"group_{g0 // a.batch:04d}.npz"), ratios=np.array([p["ratios"] for p in params], np.float64),
                      org_hw=np.array([p["org_hw"] for p in params], np.float64), **blobs)
         trks = frame_tracks(net, a)
+        render_frames(net, a, dev_imgs, group, g0 + 1)
         for i in range(len(group)):
             for key in results:
                 results[key].append(per_image[i][key[0]][key[1]][0])

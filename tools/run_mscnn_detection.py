@@ -23,6 +23,8 @@ examples/kitti_result/writeDetForEval.m.
          [--track] [--track-high T] [--track-low T] [--track-match THR] [--track-motion none|linear] [--track-max-age N] [--track-min-hits N]
          [--tracks-out DIR]                                  # track ids across the frames of the run (Net.set_tracker)
          [--track --streams N --batch B]                     # the frames are N multiplexed cameras: a table of tracks per camera
+         [--render-out DIR] [--show-thr T] [--render-label none|score|id|both] [--render-color slot|id] [--pixelate N]
+                                                             # the scripts' `show` block on the device (Net.render): annotated PNGs
   python tools/run_mscnn_detection.py --model kitti_car/mscnn-7s-576 --synthetic 8      # no dataset / weights at hand: the generated
                                                                                         # deploy net, seeded weights, synthetic frames
 
@@ -107,6 +109,13 @@ frames run in groups of one through Net.detect_multi; with --batch a group is B 
 --vote / --soft-nms / --matrix-nms the tracker runs behind the frame's merge, with --seq-nms behind the clip's (the ids live on over
 the clip boundary).  Refused together with --wbf, --rois-in and --proposals-only.  The result files are unchanged; --tracks-out DIR
 adds DIR/<comp_id>_<class>.txt with rows [image_index track x y w h score], track 0 = no confirmed track.
+--render-out DIR draws every frame's detections into a copy of the frame on the device (Net.render behind the frame's detect call:
+the `show` block at the end of the reference scripts) and writes DIR/<frame>.png: every box with a score >= --show-thr T (the
+scripts' show_thr: 0.3, and 0.1 for a Caltech model) outlined in its class's colour with --render-label score (the default: the
+scripts print the score at the top edge), id or both (the track id; these need --track) or none; --render-color id colours by track
+id (with --track); --pixelate N replaces every box's interior with an N x N mosaic (2 .. 64: anonymise the face nets' detections).
+It works with --batch, --streams, --track and the merge flags; without one of them the frames go through detect_multi in groups of
+one (Net.render reads the pack of a multi call).  The result files are unchanged.
 --streams N (with --track): the input is N cameras multiplexed, frame i of the input order (0-based) belongs to stream i % N, and
 every stream has a table of tracks of its own (Net.set_tracker(streams=N); Net.set_frame_streams before every forward, from the
 frames' own indices, so --batch B need not be a multiple of N).  One launch steps all the streams of a forward side by side.  Not with
@@ -249,6 +258,16 @@ def add_merge_flags(ap):
                     "Net.set_frame_streams per forward); --tracks-out writes one file per stream.  Not with --seq-nms")
     ap.add_argument("--tracks-out", default=None, metavar="DIR", help="with --track: DIR/<comp_id>_<class>.txt with rows [image_index track x y w h "
                     "score]; track 0 = no confirmed track")
+    ap.add_argument("--render-out", default=None, metavar="DIR", help="draw every frame's detections into a copy of the frame on the device "
+                    "(Net.render) and write DIR/<frame>.png")
+    ap.add_argument("--show-thr", type=float, default=None, metavar="T", help="with --render-out: draw the boxes with a score >= T (default: the "
+                    "scripts' show_thr, 0.3, and 0.1 for a Caltech model)")
+    ap.add_argument("--render-label", choices=["none", "score", "id", "both"], default="score", help="with --render-out: what is printed at a "
+                    "box's top edge (default score, as the scripts; id and both need --track)")
+    ap.add_argument("--render-color", choices=["slot", "id"], default="slot", help="with --render-out: a colour per class (slot, the default) "
+                    "or per track id (needs --track)")
+    ap.add_argument("--pixelate", type=int, default=0, metavar="N", help="with --render-out: replace every drawn box's interior with an N x N "
+                    "mosaic of the frame, 2 .. 64 (default 0: off)")
     ap.add_argument("--soft-thr", type=float, default=0.001, metavar="T", help="with --soft-nms: stop picking when the best live score is below T; "
                     "with --matrix-nms: keep the scores >= T (default 0.001)")
     ap.add_argument("--max-dets", type=int, default=0, metavar="N", help="with --soft-nms / --matrix-nms / --wbf: at most N detections per class and "
@@ -281,6 +300,32 @@ def seq_on(a):
 def track_on(a):
     """--track: every final stage of the run steps the tracker (Net.set_tracker)."""
     return bool(getattr(a, "track", False))
+
+
+def render_on(a):
+    """--render-out: every detect call of the run is followed by a Net.render of its frames."""
+    return getattr(a, "render_out", None) is not None
+
+
+def show_thr_of(a):
+    """--show-thr, or the scripts' show_thr: 0.1 in examples/caltech/run_mscnn_detection.m, 0.3 in the KITTI and WiderFace scripts."""
+    if a.show_thr is not None:
+        return a.show_thr
+    return 0.1 if "caltech" in (getattr(a, "model", None) or getattr(a, "prototxt", None) or "").lower() else 0.3
+
+
+def render_frames(net, a, frames, paths, first):
+    """--render-out behind a detect_multi / detect_cascade_multi / detect_merge_end over `frames` (numpy arrays, or the device tensors
+    the forward was fed from: then the frames never leave the device before they are drawn on): DIR/<frame>.png for each; `first` is
+    the 1-based number of frames[0] in the run."""
+    if not render_on(a):
+        return
+    from PIL import Image
+    outs = net.render(frames, thr=show_thr_of(a), label=a.render_label, color_by=a.render_color, pixelate=a.pixelate)
+    os.makedirs(a.render_out, exist_ok=True)
+    for i, (o, path) in enumerate(zip(outs, paths)):
+        arr = o if isinstance(o, np.ndarray) else o.cpu().numpy()
+        Image.fromarray(arr, "RGB").save(os.path.join(a.render_out, f"{frame_id(path, first + i):06d}.png"))
 
 
 def apply_track_setting(net, a):
@@ -400,6 +445,20 @@ def check_merge_flags(ap, a):
     elif (a.track_high != 0.5 or a.track_low != 0.1 or a.track_match != 0.3 or a.track_motion != "linear" or a.track_max_age != 30
           or a.track_min_hits != 1 or a.tracks_out is not None):
         ap.error("--track-high / --track-low / --track-match / --track-motion / --track-max-age / --track-min-hits / --tracks-out belong to --track")
+    if render_on(a):
+        if a.render_label in ("id", "both") and not track_on(a):
+            ap.error(f"--render-label {a.render_label} prints the track id: it needs --track")
+        if a.render_color == "id" and not track_on(a):
+            ap.error("--render-color id colours by track id: it needs --track")
+        if a.pixelate != 0 and not 2 <= a.pixelate <= 64:
+            ap.error(f"--pixelate {a.pixelate}: the mosaic's block edge, 2 .. 64 (0: off)")
+        if a.show_thr is not None and a.show_thr != a.show_thr:
+            ap.error("--show-thr nan: the threshold must be a number")
+        if getattr(a, "rois_in", "") or getattr(a, "proposals_only", False):
+            ap.error("--render-out draws the detections of every frame: not with --rois-in (frames without a box run no final stage) or "
+                     "--proposals-only")
+    elif a.show_thr is not None or a.render_label != "score" or a.render_color != "slot" or a.pixelate != 0:
+        ap.error("--show-thr / --render-label / --render-color / --pixelate belong to --render-out")
     if not 0.0 <= a.soft_thr < float("inf"):
         ap.error(f"--soft-thr {a.soft_thr:g}: the threshold must be a finite value >= 0")
     if a.max_dets < 0:
@@ -501,6 +560,7 @@ def run_seq_clips(a, net, text, files, net_hw, shape, slots, load, add):
         per_image, _ = net.detect_merge_end()
         seqs = net.detect_merge_sequences()
         trks = frame_tracks(net, a)
+        render_frames(net, a, imgs, files[c0:c0 + a.clip], c0 + 1)
         out += [([per_image[t][s][0] for s in range(slots)], [seqs[t][s] for s in range(slots)], trks[t] if trks else None) for t in range(len(imgs))]
         k = c0 + len(imgs)
         print(f"idx {k}/{len(files)}, avgtime={used / k:.4f}s (clips of {a.clip} frames, {n_fwd} forwards per frame)")
@@ -616,8 +676,8 @@ def main(argv=None):
         return run_batched(a, net, files, names, cls_ids, imgH, imgW, per_class, per_image_props, forward, rois)
     if a.scales or a.flip or a.tiles or one_forward_merge(a):
         return run_merged(a, net, text, files, names, cls_ids, imgH, imgW, per_class)
-    if track_on(a):                                                           # --track alone: groups of one frame through detect_multi
-        return run_batched(a, net, files, names, cls_ids, imgH, imgW, per_class, per_image_props, forward, rois)      # (Net.detect is refused while it is on)
+    if track_on(a) or render_on(a):                                           # --track / --render-out alone: groups of one frame through detect_multi
+        return run_batched(a, net, files, names, cls_ids, imgH, imgW, per_class, per_image_props, forward, rois)      # (Net.detect is refused while the tracker is on, and leaves Net.render no pack)
     used = 0.0
     for k, path in enumerate(files, start=1):
         img = load_frame(path, k)
@@ -719,6 +779,7 @@ def run_merged(a, net, text, files, names, cls_ids, imgH, imgW, per_class):
         set_group_streams(net, a, k - 1, 1)
         per_image, _ = net.detect_merge_end()
         a.track_ids += frame_tracks(net, a) or []
+        render_frames(net, a, [img], [path], k)
         by_type = {}
         for ci, c in enumerate(cls_ids):
             dets = per_image[0][ci][0]
@@ -769,6 +830,7 @@ def run_batched(a, net, files, names, cls_ids, imgH, imgW, per_class, per_image_
             set_group_streams(net, a, g0, len(group))
             per_image, _ = net.detect_multi([dict(p, proposal_thr=a.proposal_thr, nms_overlap=a.nms_overlap) for p in params], cls_ids)
             a.track_ids += frame_tracks(net, a) or []
+            render_frames(net, a, dev_imgs, group, g0 + 1)
         else:
             per_image = [[(np.zeros((0, 5)), None)] * len(cls_ids)] * len(group)
         for i, path in enumerate(group):
