@@ -20,6 +20,36 @@
  * returned, and none reads outside its inputs; no op writes through a const pointer.  Nothing waits on workspace contents of an
  * earlier call (the stream-K hand-off flags of the plane GEMM are tagged per launch and polled a bounded number of times).
  *
+ * STREAM CONTRACT (tests/test_gpu_stream_contract.py holds every op to it behind a gate on a non-blocking side stream;
+ * tests/test_stream_cases_cpu.py holds the list of ops against this header):
+ * 1. Ordering.  An op enqueues ALL of its device work on `stream`: every launch, hipMemsetAsync and copy, and the profiling events
+ *    of mscnn_conv2d_plan_set_profiling.  It reads its inputs, and writes its outputs and workspaces, only in stream order between
+ *    the call and the next thing the caller enqueues on `stream`: what `stream` wrote before the call is seen, and the caller may
+ *    overwrite an input or a workspace on `stream` as soon as the call has returned.  No op reads device memory from the host;
+ *    *_host arrays and descriptor structs are read before the call returns and may be freed then.
+ * 2. Asynchrony.  An op returns without waiting for `stream` or for the device.  Exceptions, all of them a first call of a kind:
+ *      mscnn_inner_product_fwd_f32 / _f16 on the MFMA GEMM path   the library's slab buffer of (thread, device, stream) is made or grown
+ *                                 with hipMalloc, behind a hipFree that waits for the device; a fifth stream on one thread takes over
+ *                                 the least recently used of four buffers the same way (below)
+ *      the plane GEMM with split tiles (Winograd wgemm plans, mscnn_inner_product_wg_fwd)   the process's hand-off word of the
+ *                                 device, one hipHostMalloc at the first such launch on it
+ *    and by its purpose mscnn_conv2d_plan_stage_ms, which waits for the plan's own events (hipEventSynchronize).  Plan creation,
+ *    mscnn_conv2d_plan_set_batch and mscnn_conv2d_plan_destroy are host work and touch no stream; the events of a profiled plan are
+ *    created by mscnn_conv2d_plan_set_profiling.
+ * 3. Concurrency.  Calls on different streams may be in flight at once, from one host thread or several, where their caller-owned
+ *    buffers are disjoint: outputs, workspace, packed weights being written, candidate buffer, pack, track state.  Inputs may be shared.
+ *      - A plan belongs to one call in flight at a time (mscnn_conv2d_plan_set_batch, _set_amax_io and the profiling events change
+ *        it), and so does a workspace, a candidate buffer, a pack and a track state.
+ *      - The stream-K slabs of mscnn_inner_product_fwd_f32 / _f16 are the library's: one buffer per (host thread, device, stream),
+ *        up to four streams per thread and device without a wait; calls on one stream share a buffer and are ordered by the stream.
+ *      - The persistent-grid plane GEMM with split tiles (wgemm plans, mscnn_inner_product_wg_fwd) needs its workgroups co-resident:
+ *        another stream's kernels can starve them, and then a launch may raise a hand-off event (mscnn_wgemm_handoff_event below) --
+ *        reported, never silent.  mscnn_wgemm_force_whole_tiles(1) takes the precondition away.
+ *      - mscnn_wgemm_force_whole_tiles, the mscnn_debug_* knobs and the hand-off event counter are per process, mscnn_last_error is
+ *        per thread: none of them is per stream.
+ *      - mscnn_sum_squares_f32 adds its partial sums with f64 atomics in the order the waves finish: its result is reproducible to
+ *        rounding, not to the bit, on any stream.  Every other op gives the same bits on every stream.
+ *
  * ALIGNMENT.  hipMalloc's 256 bytes satisfy every op.  Tighter than that, every pointer is in one of three classes: it needs only
  * its element type's own alignment (4 bytes for a float blob; "4" below); the op FALLS BACK to a slower kernel with the same result;
  * or the op REFUSES it with MSCNN_ERR_BAD_ARG before its first launch, so that nothing is stored through it and no workspace is touched.

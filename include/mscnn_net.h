@@ -40,7 +40,15 @@ MSCNN_NET_API void mscnn_net_destroy(mscnn_net* net);
 /* net.copy_from(weights) -- Net::CopyTrainedLayersFrom, net.cpp:750-803: a binary NetParameter (.caffemodel), or -- for a path
  * ending in ".h5", like the reference (net.cpp:788-795) -- an HDF5 snapshot (Net::CopyTrainedLayersFromHDF5, net.cpp:806-848). */
 MSCNN_NET_API int mscnn_net_load_caffemodel(mscnn_net* net, const char* path);
-/* HIP stream (hipStream_t as void*) for every subsequent call on this thread; NULL = default stream. */
+/* HIP stream (hipStream_t as void*) for every subsequent call on this thread; NULL = default stream.
+ * The setting is per host THREAD, not per net (it lives in the thread's Caffe singleton, as the reference's cuBLAS handle does).
+ * "The net's stream" below always means: the stream that is set on the calling thread at the time of the call.  A net's frame --
+ * set_blob / set_image*, forward, the detect and proposals calls, the pinned slots and events of detect_begin / detect_end, the
+ * numerics watch, the tracker, render -- is enqueued on that stream, under the STREAM CONTRACT of mscnn_hip.h; calls that return host
+ * data wait for that stream only, not for the device (a buffer that has to grow is the exception: hipFree waits for the device).  One thread may drive several nets on several streams by setting the stream
+ * in front of each net's calls (tests/test_gpu_net_streams.py).  A net must not be switched to another stream while work of its own
+ * is still in flight on the old one unless the caller orders the two streams (an event, or a synchronisation): its blobs, packs and
+ * tables are shared between its frames.  The caller keeps the stream alive while it is set.  mscnn_amd.net: set_stream, on_stream. */
 MSCNN_NET_API int mscnn_net_set_stream(void* stream);
 
 /* graph introspection (Net::layer_names / blob_names / layers()[i]->blobs()) */

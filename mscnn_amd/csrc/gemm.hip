@@ -13,6 +13,7 @@
 // (W for fc6 is 210 MB: it must stream from HBM once, not once per ROI tile).
 // cls_pred / bbox_pred (N = 5 / 20): one workgroup per row, lanes split K, wave reductions.
 #include "common.h"
+#include "slab_table.h"
 #include "wgemm.h"
 
 namespace {
@@ -401,26 +402,32 @@ __global__ __launch_bounds__(256) void ip_generic_kernel(const float* __restrict
 using namespace mscnn;
 
 // Workspace for the stream-K slabs is owned by the library because the Caffe layer interface has no workspace argument for
-// InnerProduct: one buffer per (host thread, device), grown on demand.  Per thread because the reference's execution model is one
-// thread per GPU with a thread-local Caffe singleton (common.cpp:13-20; host/tools/detect_multi_gpu.cpp runs one replica per
+// InnerProduct: one buffer per (host thread, device, stream), grown on demand.  Per thread because the reference's execution model
+// is one thread per GPU with a thread-local Caffe singleton (common.cpp:13-20; host/tools/detect_multi_gpu.cpp runs one replica per
 // thread), per device because a thread may switch devices; a buffer shared across threads would have concurrent replicas
-// writing their partial sums into each other's slabs.
+// writing their partial sums into each other's slabs.  Per stream for the same reason: one thread may have calls in flight on
+// two streams (two nets on one frame), and only calls on ONE stream are ordered -- main kernel, fix-up, next main kernel -- so
+// that a buffer can be reused without a wait.  The table (slab_table.h) holds kSlabSlots streams per (thread, device); a further
+// stream takes over the least recently used slot, whose buffer is freed first.  A hit costs a look through that table and no HIP
+// call beyond hipGetDevice, as before.
 namespace {
 constexpr int kMaxDevices = 64;
-struct SlabWs { float* p = nullptr; size_t bytes = 0; };
-int reserve_slabs(size_t need, float** out) {
-  static thread_local SlabWs ws[kMaxDevices];
+int reserve_slabs(size_t need, hipStream_t st, float** out) {
+  static thread_local SlabTable ws[kMaxDevices];
   int dev = 0;
   MSCNN_HIP_TRY(hipGetDevice(&dev));
   MSCNN_REQUIRE(dev >= 0 && dev < kMaxDevices, "inner_product: device index %d out of range", dev);
-  SlabWs& w = ws[dev];
-  if (need > w.bytes) {
-    if (w.p) MSCNN_HIP_TRY(hipFree(w.p));      // (synchronises the device: kernels still reading the old buffer have finished)
+  bool evicted = false;
+  SlabSlot& w = *slab_slot(ws[dev], st, &evicted);
+  if (need > w.bytes || evicted) {
+    // (hipFree synchronises the device: kernels still reading the old buffer, of this or of the evicted stream, have finished)
+    void* old = w.p;
     w.p = nullptr; w.bytes = 0;
-    MSCNN_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&w.p), need));
+    if (old) MSCNN_HIP_TRY(hipFree(old));
+    MSCNN_HIP_TRY(hipMalloc(&w.p, need));
     w.bytes = need;
   }
-  *out = w.p;
+  *out = static_cast<float*>(w.p);
   return MSCNN_OK;
 }
 }  // namespace
@@ -496,7 +503,7 @@ static int inner_product_gemm(const float* x, const void* w, bool w_is_f16, cons
   a.G = (int)G;
   const size_t need = (size_t)a.G * 2 * BM * BN * sizeof(float);
   {
-    const int rc = reserve_slabs(need, &a.ws);
+    const int rc = reserve_slabs(need, st, &a.ws);
     if (rc != MSCNN_OK) return rc;
   }
   if (w_is_f16) {

@@ -161,6 +161,30 @@ def _check(rc):
         raise NetError(lib().mscnn_net_last_error().decode())
 
 
+def set_stream(stream):
+    """mscnn_net_set_stream: the HIP stream of every following Net call on THIS host thread -- a torch stream (anything with a
+    cuda_stream attribute), a raw hipStream_t as an int, or None for the default stream.  Per thread, not per net: a net's frame
+    is enqueued on the stream that is set when its calls are made; the caller orders the streams where a net changes over between
+    frames, and keeps the stream alive while it is set."""
+    raw = getattr(stream, "cuda_stream", stream)
+    _check(lib().mscnn_net_set_stream(C.c_void_p(int(raw)) if raw else None))
+
+
+class on_stream:
+    """with net.on_stream(s): ... -- set_stream(s) for the block, the default stream again behind it (also when it raises)."""
+
+    def __init__(self, stream):
+        self.stream = stream
+
+    def __enter__(self):
+        set_stream(self.stream)
+        return self.stream
+
+    def __exit__(self, *exc):
+        set_stream(None)
+        return False
+
+
 def tile_views(org_hw, rows, cols, overlap=0, flip=False, input_hw=None, frame=0):
     """The views that cut a frame of org_hw = (h, w) into rows x cols tiles which overlap by `overlap` pixels, and with flip their
     mirrors behind them.  Pure: no net, no device.  Every window has ONE size -- ceil((extent + (n - 1) * overlap) / n) per axis --,
