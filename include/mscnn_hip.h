@@ -256,13 +256,20 @@ MSCNN_API int mscnn_conv2d_fwd_pool_f32(const mscnn_conv_plan* plan, const float
                               const float* bias, float* y, float* y_pool, void* workspace, size_t workspace_bytes,
                               void* stream);
 
-/* ReLU -- ReLULayer::Forward_gpu (relu_layer.cu:9-26); in place allowed (y == x). */
+/* ReLU -- y = max(x, 0) + negative_slope * min(x, 0) as ReLULayer::Forward_cpu writes it (relu_layer.cpp:9-19): NaN stays NaN and
+ * signed zeros come out as that layer has them; in place allowed (y == x). */
 /* Alignment: 4; falls back from the float4 kernel. */
 MSCNN_API int mscnn_relu_fwd_f32(const float* x, float* y, size_t count, float negative_slope, void* stream);
 
 /* Pooling -- PoolingLayer::Forward_gpu (pooling_layer.cu:11-47 MAX, :50-81 AVE; output size
  * pooling_layer.cpp:90-107, ceil mode).  method: 0 MAX, 1 AVE.  The argmax mask the reference
  * also writes is not produced (unused at TEST). */
+/* The output shape has one owner.  With either pad non-zero the reference clips the last window of BOTH dimensions
+ * (pooling_layer.cpp:94-102), so the two dimensions cannot be sized apart.  Returns MSCNN_ERR_BAD_ARG for what the reference's
+ * set-up refuses: pad >= kernel, a last window that still starts in the padding, an empty output. */
+MSCNN_API int mscnn_pool_out_dims(int H, int W, int kernel_h, int kernel_w, int pad_h, int pad_w, int stride_h, int stride_w,
+                                  int* out_h, int* out_w);
+/* One dimension of a pooling with equal pads (pad_h == pad_w); agrees with mscnn_pool_out_dims there. */
 MSCNN_API int mscnn_pool_out_dim(int in, int kernel, int pad, int stride);
 /* Alignment: 4; the 2x2 / stride 2 fast path (x 16, y 8) falls back. */
 MSCNN_API int mscnn_pool2d_fwd_f32(const float* x, float* y, int N, int C, int H, int W, int kernel_h, int kernel_w,

@@ -18,24 +18,27 @@ inline int grid_for(long work_items) {
   return (int)b;
 }
 
-// ---- ReLU: relu_layer.cu:9-14  y = x > 0 ? x : x * slope --------------------------------------
+// ---- ReLU: relu_layer.cpp:9-19  y = max(x, 0) + slope * min(x, 0), std::max / std::min as written there (the second
+// operand wins only on a strict compare), so NaN stays NaN and every signed zero comes out as the reference's CPU layer
+// has it: +0 for x < 0 at slope 0, +0 for x = +0 at a negative slope (x > 0 ? x : x * slope gives -0 for both).
+__device__ __forceinline__ float relu_value(float v, float slope) {
+  const float hi = v < 0.f ? 0.f : v, lo = 0.f < v ? 0.f : v;
+  return hi + slope * lo;
+}
 __global__ __launch_bounds__(kThreads) void relu_kernel_v4(const float4* __restrict__ x, float4* __restrict__ y,
                                                            size_t n4, float slope) {
   for (size_t i = blockIdx.x * (size_t)kThreads + threadIdx.x; i < n4; i += (size_t)gridDim.x * kThreads) {
     float4 v = x[i];
-    v.x = v.x > 0.f ? v.x : v.x * slope;
-    v.y = v.y > 0.f ? v.y : v.y * slope;
-    v.z = v.z > 0.f ? v.z : v.z * slope;
-    v.w = v.w > 0.f ? v.w : v.w * slope;
+    v.x = relu_value(v.x, slope);
+    v.y = relu_value(v.y, slope);
+    v.z = relu_value(v.z, slope);
+    v.w = relu_value(v.w, slope);
     y[i] = v;
   }
 }
 __global__ __launch_bounds__(kThreads) void relu_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                         size_t n, float slope) {
-  for (size_t i = blockIdx.x * (size_t)kThreads + threadIdx.x; i < n; i += (size_t)gridDim.x * kThreads) {
-    const float v = x[i];
-    y[i] = v > 0.f ? v : v * slope;
-  }
+  for (size_t i = blockIdx.x * (size_t)kThreads + threadIdx.x; i < n; i += (size_t)gridDim.x * kThreads) y[i] = relu_value(x[i], slope);
 }
 
 // ---- Pooling ------------------------------------------------------------------------------------
@@ -390,8 +393,28 @@ extern "C" int mscnn_relu_fwd_f32(const float* x, float* y, size_t count, float 
   return MSCNN_OK;
 }
 
+extern "C" int mscnn_pool_out_dims(int H, int W, int kernel_h, int kernel_w, int pad_h, int pad_w, int stride_h, int stride_w,
+                                   int* out_h, int* out_w) {
+  // pooling_layer.cpp:90-107: ceil mode; with EITHER pad non-zero the last window of BOTH dimensions is clipped when it
+  // would start at or past the padded edge, and a window that still starts there afterwards is refused (the CHECK_LT pair).
+  MSCNN_REQUIRE(out_h && out_w, "pool: null pointer");
+  MSCNN_REQUIRE(H > 0 && W > 0 && kernel_h > 0 && kernel_w > 0 && stride_h > 0 && stride_w > 0 && pad_h >= 0 && pad_w >= 0,
+                "pool: bad shape");
+  MSCNN_REQUIRE(pad_h < kernel_h && pad_w < kernel_w, "pool: pad must be smaller than kernel");   // pooling_layer.cpp:73-74
+  int ho = (int)ceilf((float)(H + 2 * pad_h - kernel_h) / stride_h) + 1;
+  int wo = (int)ceilf((float)(W + 2 * pad_w - kernel_w) / stride_w) + 1;
+  if (pad_h || pad_w) {
+    if ((ho - 1) * stride_h >= H + pad_h) --ho;
+    if ((wo - 1) * stride_w >= W + pad_w) --wo;
+    MSCNN_REQUIRE((ho - 1) * stride_h < H + pad_h && (wo - 1) * stride_w < W + pad_w, "pool: last window starts in the padding");
+  }
+  MSCNN_REQUIRE(ho > 0 && wo > 0, "pool: empty output");
+  *out_h = ho; *out_w = wo;
+  return MSCNN_OK;
+}
+
 extern "C" int mscnn_pool_out_dim(int in, int kernel, int pad, int stride) {
-  // pooling_layer.cpp:90-107
+  // one dimension of a pooling whose pads are equal (every deploy net): the same rule as mscnn_pool_out_dims
   int o = (int)ceilf((float)(in + 2 * pad - kernel) / stride) + 1;
   if (pad && (o - 1) * stride >= in + pad) --o;
   return o;
@@ -400,11 +423,11 @@ extern "C" int mscnn_pool_out_dim(int in, int kernel, int pad, int stride) {
 extern "C" int mscnn_pool2d_fwd_f32(const float* x, float* y, int N, int C, int H, int W, int kernel_h, int kernel_w,
                                     int pad_h, int pad_w, int stride_h, int stride_w, int method, void* stream) {
   MSCNN_REQUIRE(x && y, "pool: null pointer");
-  MSCNN_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0 && kernel_h > 0 && kernel_w > 0 && stride_h > 0 && stride_w > 0,
-                "pool: bad shape");
+  MSCNN_REQUIRE(N > 0 && C > 0, "pool: bad shape");
   MSCNN_REQUIRE(method == 0 || method == 1, "pool: method %d not supported (0 MAX, 1 AVE)", method);
-  MSCNN_REQUIRE(pad_h < kernel_h && pad_w < kernel_w, "pool: pad must be smaller than kernel");
-  const int Ho = mscnn_pool_out_dim(H, kernel_h, pad_h, stride_h), Wo = mscnn_pool_out_dim(W, kernel_w, pad_w, stride_w);
+  int Ho = 0, Wo = 0;
+  const int rc = mscnn_pool_out_dims(H, W, kernel_h, kernel_w, pad_h, pad_w, stride_h, stride_w, &Ho, &Wo);
+  if (rc != MSCNN_OK) return rc;
   const long planes = (long)N * C;
   const bool fast = method == 0 && kernel_h == 2 && kernel_w == 2 && stride_h == 2 && stride_w == 2 && pad_h == 0 &&
                     pad_w == 0 && (H % 2 == 0) && (W % 4 == 0) && (reinterpret_cast<uintptr_t>(x) % 16 == 0) &&

@@ -164,10 +164,12 @@ def lib():
         L.mscnn_conv2d_plan_weight_layout.argtypes = [C.c_void_p]
         L.mscnn_conv2d_plan_weight_layout.restype = C.c_ulonglong
         L.mscnn_relu_fwd_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p]
+        L.mscnn_pool_out_dims.argtypes = [C.c_int] * 8 + [C.c_void_p, C.c_void_p]
         L.mscnn_pool2d_fwd_f32.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 11 + [C.c_void_p]
         L.mscnn_inner_product_fwd_f32.argtypes = [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p]
         L.mscnn_concat_channels_f32.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]
         L.mscnn_deconv_depthwise_fwd_f32.argtypes = [C.c_void_p] * 4 + [C.c_int] * 10 + [C.c_void_p]
+        L.mscnn_deconv2d_fwd_f32.argtypes = [C.c_void_p] * 4 + [C.c_int] * 12 + [C.c_void_p]
         L.mscnn_softmax_fwd_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.mscnn_roipool_fwd_f32.argtypes = ([C.c_void_p] * 3 + [C.c_int] * 7 + [C.c_float, C.c_float] + [C.c_int] * 2
                                             + [C.c_void_p])
@@ -501,9 +503,16 @@ def pool_out_dim(i, k, p, s):
     return lib().mscnn_pool_out_dim(i, k, p, s)
 
 
+def pool_out_dims(H, W, kernel, pad, stride):
+    """(Ho, Wo) by mscnn_pool_out_dims, the one owner of the pooling output shape; MscnnError for what the reference's set-up refuses."""
+    ho, wo = C.c_int(), C.c_int()
+    _check(lib().mscnn_pool_out_dims(H, W, kernel[0], kernel[1], pad[0], pad[1], stride[0], stride[1], C.byref(ho), C.byref(wo)))
+    return ho.value, wo.value
+
+
 def pool2d(x, kernel=(2, 2), pad=(0, 0), stride=(2, 2), method="MAX"):
     N, Cc, H, W = x.shape
-    Ho, Wo = pool_out_dim(H, kernel[0], pad[0], stride[0]), pool_out_dim(W, kernel[1], pad[1], stride[1])
+    Ho, Wo = pool_out_dims(H, W, kernel, pad, stride)
     y = torch.empty((N, Cc, Ho, Wo), dtype=torch.float32, device=x.device)
     _check(lib().mscnn_pool2d_fwd_f32(_dev(x), _dev(y), N, Cc, H, W, kernel[0], kernel[1], pad[0], pad[1],
                                       stride[0], stride[1], 0 if method == "MAX" else 1, _stream()))
@@ -588,6 +597,19 @@ def deconv_depthwise(x, w, bias=None, pad=(0, 0), stride=(1, 1)):
     y = torch.empty((N, Cc, Ho, Wo), dtype=torch.float32, device=x.device)
     _check(lib().mscnn_deconv_depthwise_fwd_f32(_dev(x), _dev(w), _dev(bias), _dev(y), N, Cc, H, W, Kh, Kw,
                                                 pad[0], pad[1], stride[0], stride[1], _stream()))
+    return y
+
+
+def deconv2d(x, w, bias=None, pad=(0, 0), stride=(1, 1), group=1):
+    """mscnn_deconv2d_fwd_f32: transposed convolution with any group / kernel / stride / pad, w [Cin][Cout / group][Kh][Kw]
+    (group == Cin == Cout goes to the depthwise kernels inside the op)."""
+    N, Cin, H, W = x.shape
+    Kh, Kw = w.shape[2], w.shape[3]
+    Cout = w.shape[1] * group
+    Ho, Wo = stride[0] * (H - 1) + Kh - 2 * pad[0], stride[1] * (W - 1) + Kw - 2 * pad[1]
+    y = torch.empty((N, Cout, Ho, Wo), dtype=torch.float32, device=x.device)
+    _check(lib().mscnn_deconv2d_fwd_f32(_dev(x), _dev(w), _dev(bias), _dev(y), N, Cin, H, W, Cout, Kh, Kw, pad[0], pad[1],
+                                        stride[0], stride[1], group, _stream()))
     return y
 
 

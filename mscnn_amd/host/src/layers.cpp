@@ -626,8 +626,10 @@ void PoolingLayer<Dtype>::Reshape(const vector<Blob<Dtype>*>& bottom, const vect
   CHECK_EQ(4, bottom[0]->num_axes()) << "Input must have 4 axes, corresponding to (num, channels, height, width)";
   channels_ = bottom[0]->channels(); height_ = bottom[0]->height(); width_ = bottom[0]->width();
   if (global_pooling_) { kernel_h_ = height_; kernel_w_ = width_; }
-  pooled_height_ = mscnn_pool_out_dim(height_, kernel_h_, pad_h_, stride_h_);   // pooling_layer.cpp:90-107 (ceil)
-  pooled_width_ = mscnn_pool_out_dim(width_, kernel_w_, pad_w_, stride_w_);
+  // pooling_layer.cpp:90-107 (ceil mode; either pad clips the last window of both dimensions): the op owns the rule
+  CHECK_EQ(0, mscnn_pool_out_dims(height_, width_, kernel_h_, kernel_w_, pad_h_, pad_w_, stride_h_, stride_w_, &pooled_height_, &pooled_width_))
+      << "Pooling " << kernel_h_ << "x" << kernel_w_ << " pad " << pad_h_ << "," << pad_w_ << " stride " << stride_h_ << "," << stride_w_
+      << " on " << height_ << "x" << width_ << ": " << mscnn_last_error();
   top[0]->Reshape(bottom[0]->num(), channels_, pooled_height_, pooled_width_);
 }
 template <typename Dtype>

@@ -169,9 +169,12 @@ ORC_API int orc_conv2d(const float* x, const float* w, const float* b, float* y,
 /* ReLU: src/caffe/layers/relu_layer.cpp:9-19                           */
 /* ------------------------------------------------------------------ */
 ORC_API int orc_relu(const float* x, float* y, long n, float slope) {
+  /* std::max(x, 0) + slope * std::min(x, 0): the templates return their FIRST argument unless the strict compare picks
+   * the second, so NaN passes through both and -0 stays -0. */
   for (long i = 0; i < n; ++i) {
     const float v = x[i];
-    y[i] = (v > 0.f ? v : 0.f) + slope * (v < 0.f ? v : 0.f);
+    const float hi = v < 0.f ? 0.f : v, lo = 0.f < v ? 0.f : v;
+    y[i] = hi + slope * lo;
   }
   return 0;
 }
@@ -179,6 +182,25 @@ ORC_API int orc_relu(const float* x, float* y, long n, float slope) {
 /* ------------------------------------------------------------------ */
 /* Pooling: src/caffe/layers/pooling_layer.cpp:78-123 (shape), :140-222  */
 /* ------------------------------------------------------------------ */
+/* The output shape (:90-105).  With EITHER pad non-zero the last window of BOTH dimensions is clipped when it would start
+ * at or past the padded edge.  <0 for what the layer's set-up refuses: pad >= kernel (:73-74), a last window that still
+ * starts in the padding (:103-104), an empty output. */
+ORC_API int orc_pool_out_dims(int H, int W, int kh, int kw, int ph, int pw, int sh, int sw, int* out_h, int* out_w) {
+  if (H <= 0 || W <= 0 || kh <= 0 || kw <= 0 || sh <= 0 || sw <= 0 || ph < 0 || pw < 0) return -1;
+  if (ph >= kh || pw >= kw) return -1;
+  int ho = (int)ceilf((float)(H + 2 * ph - kh) / sh) + 1;
+  int wo = (int)ceilf((float)(W + 2 * pw - kw) / sw) + 1;
+  if (ph || pw) {
+    if ((ho - 1) * sh >= H + ph) --ho;
+    if ((wo - 1) * sw >= W + pw) --wo;
+    if ((ho - 1) * sh >= H + ph || (wo - 1) * sw >= W + pw) return -1;
+  }
+  if (ho <= 0 || wo <= 0) return -1;
+  *out_h = ho; *out_w = wo;
+  return 0;
+}
+
+/* one dimension of a pooling whose two pads are equal */
 ORC_API int orc_pool_out_dim(int in, int k, int pad, int stride) {
   int o = (int)ceilf((float)(in + 2 * pad - k) / stride) + 1;
   if (pad && (o - 1) * stride >= in + pad) --o;
@@ -188,7 +210,8 @@ ORC_API int orc_pool_out_dim(int in, int k, int pad, int stride) {
 /* method: 0 = MAX (first max wins, init -FLT_MAX; mask optional), 1 = AVE */
 ORC_API int orc_pool2d(const float* x, float* y, int* mask, int N, int C, int H, int W,
                        int kh, int kw, int ph, int pw, int sh, int sw, int method) {
-  const int Ho = orc_pool_out_dim(H, kh, ph, sh), Wo = orc_pool_out_dim(W, kw, pw, sw);
+  int Ho = 0, Wo = 0;
+  if (orc_pool_out_dims(H, W, kh, kw, ph, pw, sh, sw, &Ho, &Wo)) return -1;
   for (long nc = 0; nc < (long)N * C; ++nc) {
     const float* src = x + nc * H * W;
     float* dst = y + nc * Ho * Wo;

@@ -51,6 +51,43 @@ def _conv_geom(p):
     return kh, kw, ph, pw, sh, sw, int(_num(p, "group", 1))
 
 
+def _pool_geom(p, H, W):
+    """kernel, pad, stride of a pooling_param as PoolingLayer::LayerSetUp reads them (pooling_layer.cpp:17-66): kernel_size OR
+    kernel_h + kernel_w OR global_pooling; pad OR pad_h + pad_w (default 0); stride OR stride_h + stride_w (default 1)."""
+    def flag(key):
+        return key in p and p[key][0] in ("true", "1")
+    has = lambda *ks: [k in p for k in ks]                      # noqa: E731
+    if flag("global_pooling"):
+        if any(has("kernel_size", "kernel_h", "kernel_w")):
+            raise ValueError("With Global_pooling: true Filter size cannot specified")
+        kh, kw = H, W
+    else:
+        if ("kernel_size" in p) == all(has("kernel_h", "kernel_w")):
+            raise ValueError("Filter size is kernel_size OR kernel_h and kernel_w; not both")
+        kh, kw = (int(_num(p, "kernel_size", 0)),) * 2 if "kernel_size" in p else (int(_num(p, "kernel_h", 0)), int(_num(p, "kernel_w", 0)))
+    if not ((("pad" not in p) and all(has("pad_h", "pad_w"))) or not any(has("pad_h", "pad_w"))):
+        raise ValueError("pad is pad OR pad_h and pad_w are required.")
+    if not ((("stride" not in p) and all(has("stride_h", "stride_w"))) or not any(has("stride_h", "stride_w"))):
+        raise ValueError("Stride is stride OR stride_h and stride_w are required.")
+    ph, pw = (int(_num(p, "pad_h", 0)), int(_num(p, "pad_w", 0))) if "pad_h" in p else (int(_num(p, "pad", 0)),) * 2
+    sh, sw = (int(_num(p, "stride_h", 1)), int(_num(p, "stride_w", 1))) if "stride_h" in p else (int(_num(p, "stride", 1)),) * 2
+    if flag("global_pooling") and (ph, pw, sh, sw) != (0, 0, 1, 1):
+        raise ValueError("With Global_pooling: true; only pad = 0 and stride = 1")
+    return (kh, kw), (ph, pw), (sh, sw)
+
+
+def _axis_is_1(P, block, typ, ndim):
+    """Concat / Softmax / InnerProduct are modelled on axis 1 only: any other axis is refused, never computed as axis 1."""
+    p = P.get(block, [{}])[0]
+    axis = int(_num(p, "axis", 1))
+    if "concat_dim" in p:
+        axis = int(_num(p, "concat_dim", 1))
+    if axis < 0:
+        axis += ndim
+    if axis != 1:
+        raise NotImplementedError(f"{typ} on axis {axis}: the oracle executor models axis 1 only")
+
+
 def forward(layers, weights, inputs, stop_after=None, backend=None, timings=None):
     """layers: list of (name, type, bottoms, tops, param_text).  weights: {layer: [w, b]}.  inputs: {blob: array}.
     Returns {blob name: array} (in-place layers overwrite their blob, like the net) plus '__anchor_ids__'.
@@ -92,16 +129,24 @@ def _forward(layers, weights, inputs, stop_after, timings=None):
             blobs[tops[0]] = orc.relu(x[0], slope)
         elif typ == "Pooling":
             p = P["pooling_param"][0]
-            k = int(_num(p, "kernel_size", 0)); s = int(_num(p, "stride", 1)); pad = int(_num(p, "pad", 0))
-            blobs[tops[0]] = orc.pool2d(x[0], (k, k), (pad, pad), (s, s), p.get("pool", ["MAX"])[0])
+            k, pad, s = _pool_geom(p, x[0].shape[2], x[0].shape[3])
+            method = p.get("pool", ["MAX"])[0]
+            if method not in ("MAX", "AVE"):
+                raise NotImplementedError(f"Pooling method {method}")
+            blobs[tops[0]] = orc.pool2d(x[0], k, pad, s, method)
         elif typ == "InnerProduct":
+            _axis_is_1(P, "inner_product_param", typ, np.ndim(x[0]))
+            if P.get("inner_product_param", [{}])[0].get("transpose", ["false"])[0] in ("true", "1"):
+                raise NotImplementedError("InnerProduct transpose: true")
             w = weights[name]
             blobs[tops[0]] = orc.inner_product(x[0], w[0].reshape(w[0].shape[0], -1), w[1] if len(w) > 1 else None)
         elif typ == "Dropout":
             blobs[tops[0]] = x[0]
         elif typ == "Concat":
+            _axis_is_1(P, "concat_param", typ, np.ndim(x[0]))
             blobs[tops[0]] = np.concatenate([np.asarray(v, np.float32) for v in x], axis=1)
         elif typ == "Softmax":
+            _axis_is_1(P, "softmax_param", typ, np.ndim(x[0]))
             blobs[tops[0]] = orc.softmax(x[0], 1)
         elif typ == "ROIPooling":
             p = P["roi_pooling_param"][0]

@@ -82,10 +82,18 @@ def pool_out_dim(i, k, p, s):
     return lib().orc_pool_out_dim(i, k, p, s)
 
 
+def pool_out_dims(H, W, kernel, pad, stride):
+    """(Ho, Wo) of the reference's PoolingLayer::Reshape; ValueError for what its set-up refuses."""
+    ho, wo = C.c_int(), C.c_int()
+    if lib().orc_pool_out_dims(H, W, kernel[0], kernel[1], pad[0], pad[1], stride[0], stride[1], C.byref(ho), C.byref(wo)) != 0:
+        raise ValueError(f"pooling kernel {tuple(kernel)} pad {tuple(pad)} stride {tuple(stride)} on {H}x{W}: refused by the layer's set-up")
+    return ho.value, wo.value
+
+
 def pool2d(x, kernel=(2, 2), pad=(0, 0), stride=(2, 2), method="MAX", with_mask=False):
     x, xp = _f(x)
     N, Cc, H, W = x.shape
-    Ho, Wo = pool_out_dim(H, kernel[0], pad[0], stride[0]), pool_out_dim(W, kernel[1], pad[1], stride[1])
+    Ho, Wo = pool_out_dims(H, W, kernel, pad, stride)
     y = np.empty((N, Cc, Ho, Wo), np.float32)
     mask = np.empty((N, Cc, Ho, Wo), np.int32) if with_mask else None
     rc = lib().orc_pool2d(xp, y.ctypes.data_as(f32p), mask.ctypes.data_as(i32p) if with_mask else None,
@@ -254,8 +262,12 @@ def detections_cascade(boxes, cls_prob, props, cls_id, det_thr=0.0, ratios=(1.0,
     return dets[:D].copy(), ids[:D].copy()
 
 
+def concat(xs, axis=1):
+    return np.concatenate([np.asarray(x, np.float32) for x in xs], axis=axis)
+
+
 def concat_channels(xs):
-    return np.concatenate([np.asarray(x, np.float32) for x in xs], axis=1)
+    return concat(xs, 1)
 
 
 # ---------------------------------------------------------------------------------------------- pre-processing

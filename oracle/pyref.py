@@ -23,6 +23,12 @@ def available():
         return False
 
 
+def has(entry):
+    """True where the built library exports `entry` (an oracle/_ref built before an entry point was added lacks it and could
+    not be rebuilt where the reference checkout is absent)."""
+    return available() and hasattr(lib(), entry)
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -146,6 +152,17 @@ def eltwise(xs, op="SUM", coeffs=None):
     cf = (C.c_float * n)(*coeffs) if coeffs is not None and len(coeffs) else None
     y = np.empty_like(arrs[0])
     _ck(lib().ref_eltwise(ptrs, n, cf, y.ctypes.data_as(f32p), y.size, {"PROD": 0, "SUM": 1, "MAX": 2}[op]))
+    return y
+
+
+def concat(xs, axis=1):
+    arrs = [np.ascontiguousarray(x, np.float32) for x in xs]
+    n, nd = len(arrs), arrs[0].ndim
+    ptrs = (f32p * n)(*[a.ctypes.data_as(f32p) for a in arrs])
+    dims = (C.c_int * (n * nd))(*[d for a in arrs for d in a.shape])
+    shape = list(arrs[0].shape); shape[axis] = sum(a.shape[axis] for a in arrs)
+    y = np.empty(shape, np.float32)
+    assert _ck(lib().ref_concat(ptrs, dims, n, nd, axis, y.ctypes.data_as(f32p))) == y.size
     return y
 
 

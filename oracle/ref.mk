@@ -26,9 +26,14 @@ _ref/obj/$(subst /,_,$(1:.cpp=.o)): $(REF)/src/caffe/$(1) $(SHIM_HDRS)
 endef
 $(foreach s,$(REF_SRCS),$(eval $(call REF_RULE,$(s))))
 
-_ref/obj/harness.o: ref_harness.cpp $(SHIM_HDRS)
+# always recompiled (seconds): a checkout can date ref_harness.cpp before an object that was built from an earlier version of
+# it, and a library without a newer entry point would then pass for current
+_ref/obj/harness.o: ref_harness.cpp $(SHIM_HDRS) FORCE
 	@mkdir -p _ref/obj
 	$(CXX) $(REF_CXXFLAGS) -c $< -o $@
 
 _ref/libmscnn_ref.so: $(REF_OBJS) _ref/obj/harness.o
 	$(CXX) -shared -fPIC -o $@ $^ -L$(MKL_DIR) -l:libmkl_rt.so.1 -Wl,-rpath,$(MKL_DIR) -lpthread
+
+FORCE:
+.PHONY: FORCE

@@ -188,6 +188,28 @@ REF_API int ref_eltwise(const float* const* xs, int nb, const float* coeffs, flo
   })
 }
 
+// dims: nb rows of `ndim` extents.  Returns the number of floats written to y (the top's count).
+REF_API int ref_concat(const float* const* xs, const int* dims, int nb, int ndim, int axis, float* y) {
+  try {
+    LayerParameter lp;
+    lp.mutable_concat_param()->set_axis(axis);
+    ConcatLayer<float> layer(lp);
+    std::vector<shared_ptr<Blob<float> > > hold;
+    BV bv;
+    for (int b = 0; b < nb; ++b) {
+      hold.push_back(shared_ptr<Blob<float> >(new Blob<float>(std::vector<int>(dims + b * ndim, dims + (b + 1) * ndim))));
+      fill(hold.back().get(), xs[b]);
+      bv.push_back(hold.back().get());
+    }
+    Blob<float> top;
+    BV tv(1, &top);
+    layer.SetUp(bv, tv);
+    layer.Forward(bv, tv);
+    take(top, y);
+    return top.count();
+  } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+
 struct ref_boxoutput_params {
   float fg_thr, iou_thr;
   int nms_mode;

@@ -109,3 +109,83 @@ def test_hip_cascade_layers(hip):
     assert np.array_equal(hip.eltwise(xs, "MAX").cpu().numpy(), GB["elt_max"])
     close(hip.pool2d(dev(GB["ave_x"]), (2, 2), (0, 0), (1, 1), "AVE").cpu().numpy(), GB["ave_y"], 1e-6)
     close(hip.softmax(dev(GB["softmax_x"])).cpu().numpy(), GB["softmax_y"], 1e-6)
+
+
+# ---------------------------------------------------------------- third file: the stock layers (tests/golden/make_golden_c.py)
+import stock_cases as sc  # noqa: E402
+
+GC = np.load(os.path.join(os.path.dirname(__file__), "golden", "reference_layers_c.npz"))
+
+
+def _stock_layers_against_the_reference(ops, relu_x):
+    """ops: oracle.pyoracle, or the HIP front-end wrapped to take and return numpy (same signatures)."""
+    off = 0
+    for H, W, kh, kw, ph, pw, sh, sw, mi, Ho, Wo in GC["pool_cases"].tolist():
+        n = sc.POOL_PLANES[0] * sc.POOL_PLANES[1] * Ho * Wo
+        want = GC["pool_y"][off:off + n].reshape(sc.POOL_PLANES + (Ho, Wo)); off += n
+        y = ops.pool2d(sc.pool_input(H, W), (kh, kw), (ph, pw), (sh, sw), ("MAX", "AVE")[mi])
+        case = (H, W, kh, kw, ph, pw, sh, sw, mi)
+        assert y.shape == want.shape, case                                  # the shape rule first
+        if mi == 0:
+            assert np.array_equal(y, want), case
+        else:
+            assert np.array_equal(np.isnan(y), np.isnan(want)), case
+            assert np.allclose(y, want, rtol=0, atol=1e-6, equal_nan=True), case
+    assert off == GC["pool_y"].size
+    for slope, want in zip(sc.RELU_SLOPES, GC["relu_y"]):
+        n = relu_x.size                                                         # (the device's inputs are a prefix of the recorded ones)
+        assert np.array_equal(sc.bits(ops.relu(relu_x, slope)), sc.bits(want[:n])), slope
+    cases = sc.deconv_cases()
+    for i in GC["deconv_index"].tolist():
+        x, w, b, g = sc.deconv_inputs(cases[i], i)
+        close(ops.deconv2d(x, w, b, cases[i][3], cases[i][2], g), GC[f"deconv_y{i}"], 1e-6 if cases[i][0] == "dw" else 1e-4)
+    seen = 0
+    for tag, x in sc.softmax_inputs():
+        if f"softmax_{tag}" in GC.files:
+            want = GC[f"softmax_{tag}"]; y = ops.softmax(x); seen += 1
+            assert np.array_equal(np.isnan(y), np.isnan(want)), tag
+            assert np.allclose(y, want, rtol=0, atol=1e-6, equal_nan=True), tag
+    assert seen == 16
+    xs = sc.eltwise_inputs(8)
+    for op in ("PROD", "MAX", "SUM"):
+        assert np.array_equal(ops.eltwise(xs, op), GC[f"elt8_{op}"]), op
+    close(ops.eltwise(xs, "SUM", sc.ELTWISE_COEFFS[8]), GC["elt8_coeff"], 1e-6)          # reference: MKL saxpy (fma) -> 1 ulp
+    return True
+
+
+def test_oracle_stock_layers(orc):
+    """Pooling where the both-pads shape rule or an empty AVE window matters, ReLU specials (denormals included), one transposed
+    convolution per family, Softmax with special rows, Eltwise with 8 bottoms, Concat: the oracle against the reference's outputs."""
+    assert _stock_layers_against_the_reference(orc, sc.RELU_SPECIALS)
+    for j, (axis, arrs) in enumerate(sc.concat_cases()):
+        assert np.array_equal(orc.concat(arrs, axis), GC[f"concat_{j}"])
+
+
+class _HipOps:
+    """The HIP front-end behind the oracle's numpy signatures."""
+    def __init__(self, hip):
+        self.hip = hip
+
+    def pool2d(self, x, k, p, s, m):
+        return self.hip.pool2d(dev(x), k, p, s, m).cpu().numpy()
+
+    def relu(self, x, slope):
+        return self.hip.relu(dev(x), slope).cpu().numpy()
+
+    def deconv2d(self, x, w, b, pad, stride, group):
+        return self.hip.deconv2d(dev(x), dev(w), None if b is None else dev(b), pad, stride, group).cpu().numpy()
+
+    def softmax(self, x):
+        return self.hip.softmax(dev(x)).cpu().numpy()
+
+    def eltwise(self, xs, op, coeffs=None):
+        return self.hip.eltwise([dev(x) for x in xs], op, coeffs).cpu().numpy()
+
+
+@pytest.mark.gpu
+def test_hip_stock_layers(hip):
+    """The same file through the C ABI (ReLU on +-0, +-inf and NaN: what the device does with denormals is not measured)."""
+    assert _stock_layers_against_the_reference(_HipOps(hip), sc.RELU_SPECIALS_DEVICE)
+    for j, (axis, arrs) in enumerate(sc.concat_cases()):
+        if axis == 1:
+            assert np.array_equal(hip.concat_channels([dev(a) for a in arrs]).cpu().numpy(), GC[f"concat_{j}"])

@@ -335,3 +335,67 @@ def test_detections_cascade_stage(orc):
     assert dets[2].tolist() == [950.0, 280.0, 11.0, 9.0, np.float32(0.6)]       # clipped at org_w / org_h
     d2, i2 = orc.detections_cascade(boxes, prob, props, cls_id=2, det_thr=0.65, ratios=(2.0, 2.0), org_hw=(288, 960))
     assert i2.tolist() == [0, 2]
+
+
+def test_pool_out_dims_either_pad_clips_both_dimensions(orc):
+    """pooling_layer.cpp:94-102: H=3, W=4, kernel (1,2), pad (0,1), stride (3,1) is 1x5 -- the second row would pool a window that
+    lies wholly outside the map.  Equal pads: the one-dimension form agrees.  What the set-up refuses raises."""
+    assert orc.pool_out_dims(3, 4, (1, 2), (0, 1), (3, 1)) == (1, 5)
+    assert orc.pool_out_dims(3, 4, (1, 2), (0, 0), (3, 1)) == (2, 3)
+    for i, k, p, s in [(15, 2, 0, 2), (576, 2, 0, 2), (9, 2, 0, 2), (3, 3, 2, 2), (7, 3, 1, 2)]:
+        assert orc.pool_out_dims(i, i, (k, k), (p, p), (s, s)) == (orc.pool_out_dim(i, k, p, s),) * 2
+    for k, p in (((2, 2), (2, 0)), ((1, 3), (0, 3)), ((5, 2), (0, 0))):
+        with pytest.raises(ValueError):
+            orc.pool_out_dims(3, 4, k, p, (1, 1))
+
+
+def test_relu_keeps_nan_and_signed_zero(orc):
+    x = np.array([np.nan, -0.0, 0.0, -3.0], np.float32)
+    y = orc.relu(x)
+    assert np.isnan(y[0]) and np.signbit(y[1]) and not np.signbit(y[2]) and y[3] == 0 and not np.signbit(y[3])
+    assert not np.signbit(orc.relu(x, -0.5)[1:3]).any()
+
+
+def _one_layer(typ, param, bottoms=("data",)):
+    return [("l", typ, list(bottoms), ["top"], param)]
+
+
+def test_pynet_pooling_reads_every_parameter_form(orc):
+    from oracle import pynet
+    x = np.random.default_rng(5).standard_normal((1, 2, 3, 4)).astype(np.float32)
+    run = lambda text: pynet.forward(_one_layer("Pooling", "pooling_param { " + text + " }"), {}, {"data": x})["top"]      # noqa: E731
+    y = run("pool: MAX kernel_h: 1 kernel_w: 2 pad_h: 0 pad_w: 1 stride_h: 3 stride_w: 1")
+    assert y.shape == (1, 2, 1, 5) and np.array_equal(y, orc.pool2d(x, (1, 2), (0, 1), (3, 1)))
+    assert np.array_equal(run("pool: MAX global_pooling: true"), x.max((2, 3), keepdims=True))
+    assert np.allclose(run("pool: AVE global_pooling: true"), x.mean((2, 3), keepdims=True), atol=1e-6)
+    assert np.array_equal(run("pool: MAX kernel_size: 2"), orc.pool2d(x, (2, 2), (0, 0), (1, 1)))          # stride defaults to 1
+    for bad in ("pool: MAX kernel_size: 2 kernel_h: 2 kernel_w: 2", "pool: MAX kernel_h: 2", "pool: MAX kernel_size: 2 pad_h: 1",
+                "pool: MAX kernel_size: 2 stride: 1 stride_h: 1 stride_w: 1", "pool: MAX global_pooling: true kernel_size: 2",
+                "pool: MAX global_pooling: true stride: 2", "pool: MAX kernel_size: 2 pad: 2"):
+        with pytest.raises(ValueError):
+            run(bad)
+
+
+def test_pynet_refuses_the_axes_it_does_not_model():
+    from oracle import pynet
+    x = np.zeros((2, 3, 4, 5), np.float32)
+    for typ, param, bottoms in [("Concat", "concat_param { axis: 2 }", ("data", "data")), ("Concat", "concat_param { concat_dim: 0 }", ("data", "data")),
+                                ("Softmax", "softmax_param { axis: 2 }", ("data",)), ("Softmax", "softmax_param { axis: -1 }", ("data",)),
+                                ("InnerProduct", "inner_product_param { num_output: 2 axis: 2 }", ("data",))]:
+        with pytest.raises(NotImplementedError):
+            pynet.forward(_one_layer(typ, param, bottoms), {"l": [np.zeros((2, 20), np.float32)]}, {"data": x})
+    y = pynet.forward(_one_layer("Concat", "concat_param { axis: -3 }", ("data", "data")), {}, {"data": x})["top"]     # axis 1, counted from the end
+    assert y.shape == (2, 6, 4, 5)
+
+
+def test_pooling_host_layer_shape_and_refusal():
+    """The host layer takes its shape from the op (no device needed to reshape a net)."""
+    from mscnn_amd import net as mnet
+    text = 'name: "p" input: "data" input_dim: 1 input_dim: 2 input_dim: 3 input_dim: 4 layer { name: "pool" type: "Pooling" bottom: "data" ' \
+           'top: "pool" pooling_param { %s } }'
+    n = mnet.Net(prototxt_text=text % "pool: MAX kernel_h: 1 kernel_w: 2 pad_h: 0 pad_w: 1 stride_h: 3 stride_w: 1", device=-1)
+    assert tuple(n.blob_shape("pool")) == (1, 2, 1, 5)
+    n = mnet.Net(prototxt_text=text % "pool: AVE global_pooling: true", device=-1)
+    assert tuple(n.blob_shape("pool")) == (1, 2, 1, 1)
+    with pytest.raises(mnet.NetError):
+        mnet.Net(prototxt_text=text % "pool: MAX kernel_h: 5 kernel_w: 2 stride: 1", device=-1)

@@ -132,3 +132,92 @@ def test_small_net_end_to_end(orc):
     bo = [l for l in layers if l[1] == "BoxOutput"][0]
     a2 = pynet.forward([bo], ws, {k: r[k] for k in bo[2]})
     assert np.array_equal(a2["proposals"], r["proposals"]) and np.array_equal(a2["proposals_score"], r["proposals_score"])
+
+
+# ---------------------------------------------------------------- the stock layers over their whole parameter space
+import stock_cases as sc  # noqa: E402
+
+
+def test_pool_sweep_shape_rule_and_values(orc):
+    """Every kernel / pad < kernel / stride in {1,2,3} per dimension on 20 map sizes, MAX and AVE (12 960 combinations): the
+    output SHAPE first (the reference clips the last window of both dimensions when either pad is non-zero), MAX bit for bit,
+    AVE within 1e-6 with identical NaN positions (0 / 0 of a window that lies wholly past the map).  What the reference's
+    set-up refuses, the oracle refuses."""
+    total = refused = nan_cases = 0
+    for H, W in sc.POOL_SIZES:
+        x = sc.pool_input(H, W)
+        for k, p, s in sc.pool_params():
+            for m in ("MAX", "AVE"):
+                total += 1
+                try:
+                    r = pyref.pool2d(x, k, p, s, m)
+                except RuntimeError:
+                    refused += 1
+                    with pytest.raises(ValueError):
+                        orc.pool2d(x, k, p, s, m)
+                    continue
+                assert orc.pool_out_dims(H, W, k, p, s) == r.shape[2:], (H, W, k, p, s)
+                a = orc.pool2d(x, k, p, s, m)
+                assert a.shape == r.shape, (H, W, k, p, s, m)
+                if m == "MAX":
+                    assert np.array_equal(a, r), (H, W, k, p, s)
+                else:
+                    assert np.array_equal(np.isnan(a), np.isnan(r)), (H, W, k, p, s)
+                    assert np.allclose(a, r, rtol=0, atol=1e-6, equal_nan=True), (H, W, k, p, s)
+                    nan_cases += bool(np.isnan(r).any())
+    print(f"pool sweep: {total} combinations, {refused} refused by the reference, {nan_cases} AVE cases with NaN")
+    assert total == 12960 and nan_cases > 0
+
+
+def test_pool_refusals_match(orc):
+    """Outside the sweep (pad >= kernel, a kernel larger than the padded map): refused on both sides."""
+    x = sc.pool_input(3, 4)
+    for k, p, s in [((2, 2), (2, 0), (1, 1)), ((1, 3), (0, 3), (2, 2)), ((3, 3), (1, 4), (1, 1)), ((5, 2), (0, 0), (1, 1))]:
+        with pytest.raises(RuntimeError):
+            pyref.pool2d(x, k, p, s, "MAX")
+        with pytest.raises(ValueError):
+            orc.pool2d(x, k, p, s, "MAX")
+
+
+def test_relu_special_values_bit_patterns(orc):
+    for slope in sc.RELU_SLOPES:
+        a, r = orc.relu(sc.RELU_SPECIALS, slope), pyref.relu(sc.RELU_SPECIALS, slope)
+        assert np.array_equal(np.isnan(a), np.isnan(r)), slope
+        assert np.array_equal(sc.bits(a), sc.bits(r)), (slope, a, r)
+    x = np.random.default_rng(21).standard_normal(4099).astype(np.float32)
+    for slope in sc.RELU_SLOPES:
+        assert np.array_equal(sc.bits(orc.relu(x, slope)), sc.bits(pyref.relu(x, slope)))
+
+
+def test_softmax_shapes_scales_specials(orc):
+    for tag, x in sc.softmax_inputs():
+        a, r = orc.softmax(x), pyref.softmax(x)
+        assert np.array_equal(np.isnan(a), np.isnan(r)), tag
+        assert np.allclose(a, r, rtol=0, atol=1e-6, equal_nan=True), tag
+        if not tag.endswith(("x1", "x30", "x100", "pm1000")):
+            assert np.isnan(r).any(), tag                   # the special row is NaN in the reference (inf - inf)
+
+
+def test_deconv_generic_and_depthwise(orc):
+    for i, case in enumerate(sc.deconv_cases()):
+        x, w, b, g = sc.deconv_inputs(case, i)
+        a, r = orc.deconv2d(x, w, b, case[3], case[2], g), pyref.deconv2d(x, w, b, case[3], case[2], g)
+        assert a.shape == r.shape, case
+        assert np.allclose(a, r, atol=1e-6 if case[0] == "dw" else 1e-5), case
+
+
+def test_eltwise_bottom_counts(orc):
+    for nb in sc.ELTWISE_BOTTOMS:
+        xs = sc.eltwise_inputs(nb)
+        for op in ("PROD", "MAX", "SUM"):
+            assert np.array_equal(orc.eltwise(xs, op), pyref.eltwise(xs, op)), (nb, op)
+        cf = sc.ELTWISE_COEFFS[nb]
+        assert min(cf) < 0 and 0.0 in cf
+        assert np.allclose(orc.eltwise(xs, "SUM", cf), pyref.eltwise(xs, "SUM", cf), atol=1e-6), nb      # saxpy may fuse
+        assert (np.stack(xs).max(0) == xs[0]).reshape(-1)[::3].any()                                       # a tie wins somewhere
+
+
+@pytest.mark.skipif(not pyref.has("ref_concat"), reason="oracle/_ref predates ref_concat and was not rebuilt (make -C oracle ref needs the reference checkout)")
+def test_concat_axes(orc):
+    for axis, xs in sc.concat_cases():
+        assert np.array_equal(orc.concat(xs, axis), pyref.concat(xs, axis)), (axis, xs[0].shape)
