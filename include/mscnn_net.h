@@ -44,7 +44,7 @@ MSCNN_NET_API int mscnn_net_load_caffemodel(mscnn_net* net, const char* path);
  * The setting is per host THREAD, not per net (it lives in the thread's Caffe singleton, as the reference's cuBLAS handle does).
  * "The net's stream" below always means: the stream that is set on the calling thread at the time of the call.  A net's frame --
  * set_blob / set_image*, forward, the detect and proposals calls, the pinned slots and events of detect_begin / detect_end, the
- * numerics watch, the tracker, render -- is enqueued on that stream, under the STREAM CONTRACT of mscnn_hip.h; calls that return host
+ * numerics watch, the tracker, render, crops -- is enqueued on that stream, under the STREAM CONTRACT of mscnn_hip.h; calls that return host
  * data wait for that stream only, not for the device (a buffer that has to grow is the exception: hipFree waits for the device).  One thread may drive several nets on several streams by setting the stream
  * in front of each net's calls (tests/test_gpu_net_streams.py).  A net must not be switched to another stream while work of its own
  * is still in flight on the old one unless the caller orders the two streams (an event, or a synchronisation): its blobs, packs and
@@ -579,6 +579,76 @@ typedef struct {
 MSCNN_NET_API int mscnn_net_render(mscnn_net* net, const unsigned char* const* frames_rgb, int on_device,
                                    const int* org_h, const int* org_w, int count, const mscnn_render_params* p,
                                    unsigned char* const* out_rgb, int out_on_device);
+/* Every detection as a fixed-size, mean-subtracted patch, cut on the device: what a second stage -- a re-identification or attribute
+ * net, a face recogniser, a gallery of a track's sightings -- takes from a detector.  It reads the pack mscnn_net_render reads: the
+ * block the LAST successful mscnn_net_detect_multi, mscnn_net_detect_cascade_multi or mscnn_net_detect_merge_end left, with the
+ * tracker's ids behind it if that call ran the tracker; the same validity record (any other user of the block ends it) and the same
+ * rule for a segment's rows (entry {count, rows, row0, 0}; offset = row0, unless K >= 2 and the entries of the frame's slots 0 and 1
+ * hold the same row0, then K * row0 + k * rows; a segment with count < 0, a negative offset or offset + count > cap is empty).  It
+ * reads the pack and steps nothing: mscnn_net_detect_tracks, mscnn_net_tracker_state and a following mscnn_net_render are unchanged,
+ * and render and crops may both follow one detect call, in either order.
+ * No new device op: the pixels are mscnn_preprocess_views_u8_f32's (mscnn_hip.h), one call over all windows; the host computes the
+ * windows.  frames_rgb / on_device / org_h / org_w / count: as mscnn_net_render -- the frames that call detected on, in its order.
+ * The window of a row [x y w h s] in a frame of org_h x org_w.  Double arithmetic, one rounding per operation (no fused
+ * multiply-add), up to the four floors of step 4; from there on integers only, in 64 bits:
+ *   1. The row is SKIPPED when !(s >= thr); when one of its five values is not finite; when !(w > 0) or !(h > 0); when |x|, |y|, w or
+ *      h exceeds 2^30.
+ *   2. ww = w * context;  hh = h * context.
+ *   3. With fit == 1:  a = (double)out_w / (double)out_h;  t = hh * a;  if ww < t then ww = t, else hh = ww / a.
+ *   4. cx = x + w / 2;  cy = y + h / 2;  x0 = cx - ww / 2;  y0 = cy - hh / 2;  and, in the footprint rounding of the render stage,
+ *      L = floor(x0 + .5), T = floor(y0 + .5), R = floor((x0 + ww) + .5) - 1, B = floor((y0 + hh) + .5) - 1;
+ *      Wd = R - L + 1, Ht = B - T + 1.  The row is skipped when Wd < 1 or Ht < 1.
+ *   5. With border == 1 (shift; as mscnn_amd.net.tile_views: a window that fits is moved inwards, not shrunk), horizontally:
+ *      if Wd >= org_w then L = 0, Wd = org_w; else if L < 0 then L = 0; else if L + Wd > org_w then L = org_w - Wd.  Vertically the
+ *      same with T, Ht, org_h.
+ *   6. With border == 0 (clip): L' = max(L, 0), R' = min(R, org_w - 1), T' = max(T, 0), B' = min(B, org_h - 1).  The row is skipped
+ *      when the clipped window is empty (L' > R' or T' > B'); otherwise the window is the clipped one.
+ *   7. The row is skipped when Wd < min_size or Ht < min_size.
+ *   The window is {x0 = L, y0 = T, w = Wd, h = Ht} and lies inside the frame.
+ * Order and bound.  Crops come out in the order (frame, slot, row), each ascending; row 0 of a segment is its best score.  The slot
+ * filter and tracked_only (a row's track id > 0) apply before counting; the first max_crops rows in that order that give a crop are
+ * produced, *num_dropped = the further rows that would have given one (the call succeeds: a drop is never silent).  *num_crops may
+ * be 0; nothing is uploaded or launched then.
+ * Pixels.  out: [max_crops][3][out_h][out_w] floats in host memory, or in device memory when out_on_device != 0.  Slices
+ * [0, *num_crops) are written, later slices are left as they were.  Slice i is what the views op defines: bit-identical to
+ * mscnn_preprocess_u8_f32 on a contiguous copy of the window -- the scripts' imresize to out_h x out_w, planes B, G, R, mean_bgr
+ * subtracted per plane.  info_host[max_crops] (host): entry i = where crop i came from (row: its index inside its segment;
+ * track_id: 0 when that call ran no tracker) and its window in frame pixels; complete when the call returns, whatever out is.
+ * How it runs.  One mscnn_preprocess_views_u8_f32 call over all windows on the net's stream, its workspace
+ * (mscnn_preprocess_views_workspace_bytes) kept with the Net and grown when needed.  A host frame is uploaded once, whatever the
+ * number of its crops, and not at all when it has none.  Staging goes through buffers of this stage's own -- never through the buffer
+ * of mscnn_net_set_images, which may already hold the next forward's frames.  A device out is left asynchronous on the net's stream;
+ * a host out comes back behind ONE synchronisation.
+ * Refused before anything is uploaded or enqueued, naming the value: a null pointer; no valid pack (render's text, starting
+ * "crops:"); a count that is not that call's number of images or lists (both numbers); a null frame, a frame size <= 0 or above
+ * 2^30; a NaN thr; context outside [1, 16] (NaN included); fit or border outside {0, 1}; min_size < 1; out_h or out_w outside
+ * [1, 1024]; max_crops < 1; slot outside [-1, slots of that call); tracked_only outside {0, 1}, or 1 when that call ran no tracker; a
+ * mean that is not finite; a net built with device < 0.
+ * mscnn_net_crop_window: steps 1 - 7 for one row on the host -- no device, no net; it is the function mscnn_net_crops itself calls
+ * per row.  Returns 1 and win = {x0, y0, w, h} when the row gives a crop, 0 when it is skipped, < 0 (the text in
+ * mscnn_net_last_error) for params mscnn_net_crops would refuse -- of slot only "below -1" can be told here --, a null pointer or a
+ * frame size <= 0 or above 2^30.
+ * NOT covered, as for mscnn_net_render: the single-pack calls; a batch of one through mscnn_net_detect_multi serves them.  No uint8 /
+ * HWC patches, no padding of a window that leaves the frame, no rotation.
+ * No pin on the reference: its scripts cut no patches.  The windows' check is tests/crops_witness.py, a restatement of the rule
+ * above in plain Python numbers; the pixels' check is the single-frame op on a host copy of the window. */
+typedef struct {
+  double thr;          /* a row with !(score >= thr) gives no crop (NaN thr: refused) */
+  double context;      /* the window is the box scaled about its centre by this factor; 1 <= context <= 16 (MS-CNN's own ROI context is 1.5) */
+  int fit;             /* 0: the scaled box as it is (stretched to out_h x out_w); 1: grown to the aspect ratio out_w : out_h first */
+  int border;          /* 0: the window is clipped to the frame; 1: a window that fits is shifted inwards, not shrunk (as net.tile_views) */
+  int min_size;        /* >= 1: a window narrower or lower than this, after step 6, gives no crop */
+  int out_h, out_w;    /* 1 .. 1024 */
+  int max_crops;       /* >= 1: rows of `out` and of `info` */
+  int slot;            /* -1: every slot; else only this one, inside [0, slots of that call) */
+  int tracked_only;    /* 1: only rows whose track id is > 0 (needs a call that ran the tracker) */
+  float mean_bgr[3];   /* subtracted per plane; {0, 0, 0} gives the resized pixel values themselves */
+} mscnn_crops_params;
+typedef struct { int frame, slot, row, track_id; int x0, y0, w, h; } mscnn_crop_info;   /* row: index inside its segment; the window in frame pixels */
+MSCNN_NET_API int mscnn_net_crop_window(const mscnn_crops_params* p, const double row[5], int org_h, int org_w, int win[4]);
+MSCNN_NET_API int mscnn_net_crops(mscnn_net* net, const unsigned char* const* frames_rgb, int on_device, const int* org_h, const int* org_w,
+                                  int count, const mscnn_crops_params* p, float* out, int out_on_device,
+                                  mscnn_crop_info* info_host, int* num_crops, int* num_dropped);
 /* The views of a frame as ONE batched forward (mscnn_hip.h: mscnn_detections_candidates_add_views): the merge was opened with
  * _begin(num_frames, ...), the input holds N images -- the views mscnn_net_set_image_views wrote --, p[N * K] and view[N] describe
  * them as in _add, and list_of[N] (host) names the frame of each: the rows of image b go to the lists of frame list_of[b].  One

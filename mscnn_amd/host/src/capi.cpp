@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstring>
 #include <functional>
+#include <sstream>
 #include <string>
 #include <vector>
 
@@ -76,6 +77,8 @@ struct mscnn_net {
     size_t bytes = 0, ids_at = 0;
     caffe::DeviceBuffer pack, in, out;
   } render;
+  // mscnn_net_crops: the stage's own device buffers -- the staged host frames, the views op's workspace, the patches of a host `out`
+  struct Crops { caffe::DeviceBuffer in, ws, out; } crops;
   // mscnn_net_detect_merge_*: the candidate lists of the forwards added since _begin (mscnn_hip.h: mscnn_detections_candidates_*)
   struct Merge {
     bool open = false;
@@ -1918,6 +1921,173 @@ int mscnn_net_render(mscnn_net* n, const unsigned char* const* frames_rgb, int o
     if (!out_on_device) {      // every frame's copy, then the one synchronisation
       for (int b = 0; b < count; ++b)
         HIP_CHECK(hipMemcpyAsync(out_rgb[b], dst[b], (size_t)org_h[b] * org_w[b] * 3, hipMemcpyDeviceToHost, st));
+      HIP_CHECK(hipStreamSynchronize(st));
+    }
+  });
+}
+
+// What mscnn_net_crops and mscnn_net_crop_window refuse about the params alone ("" = nothing); of slot only the lower bound can be
+// told without a pack.
+static std::string crops_params_error(const mscnn_crops_params& p) {
+  std::ostringstream e;
+  if (p.thr != p.thr) e << "thr is NaN";
+  else if (!(p.context >= 1.0 && p.context <= 16.0)) e << "context " << p.context << " is outside [1, 16]";
+  else if (p.fit != 0 && p.fit != 1) e << "fit " << p.fit << " is neither 0 nor 1";
+  else if (p.border != 0 && p.border != 1) e << "border " << p.border << " is neither 0 (clip) nor 1 (shift)";
+  else if (p.min_size < 1) e << "min_size " << p.min_size << " is below 1";
+  else if (p.out_h < 1 || p.out_h > 1024) e << "out_h " << p.out_h << " is outside [1, 1024]";
+  else if (p.out_w < 1 || p.out_w > 1024) e << "out_w " << p.out_w << " is outside [1, 1024]";
+  else if (p.max_crops < 1) e << "max_crops " << p.max_crops << " is below 1";
+  else if (p.slot < -1) e << "slot " << p.slot << " is below -1";
+  else if (p.tracked_only != 0 && p.tracked_only != 1) e << "tracked_only " << p.tracked_only << " is neither 0 nor 1";
+  else
+    for (int c = 0; c < 3; ++c)
+      if (!std::isfinite(p.mean_bgr[c])) { e << "mean_bgr[" << c << "] " << p.mean_bgr[c] << " is not finite"; break; }
+  return e.str();
+}
+
+// Steps 1 - 7 of include/mscnn_net.h's comment on mscnn_net_crops, for checked params and a checked frame size.
+static int crop_window_of(const mscnn_crops_params& p, const double* row, int org_h, int org_w, int* win) {
+#pragma clang fp contract(off)      // one rounding per operation: (x0 + ww) must not become a fused multiply-add of w * context
+  const double kMax = 1073741824.0;      // 2^30
+  const double x = row[0], y = row[1], w = row[2], h = row[3], s = row[4];
+  if (!(s >= p.thr)) return 0;
+  if (!std::isfinite(x) || !std::isfinite(y) || !std::isfinite(w) || !std::isfinite(h) || !std::isfinite(s)) return 0;
+  if (!(w > 0.0) || !(h > 0.0)) return 0;
+  if (std::fabs(x) > kMax || std::fabs(y) > kMax || w > kMax || h > kMax) return 0;
+  double ww = w * p.context;
+  double hh = h * p.context;
+  if (p.fit == 1) {
+    const double a = (double)p.out_w / (double)p.out_h;
+    const double t = hh * a;
+    if (ww < t) ww = t;
+    else hh = ww / a;
+  }
+  const double hw = w / 2, hw2 = ww / 2;
+  const double cx = x + hw;
+  const double x0 = cx - hw2;
+  const double hv = h / 2, hv2 = hh / 2;
+  const double cy = y + hv;
+  const double y0 = cy - hv2;
+  const double xl = x0 + .5, yt = y0 + .5;
+  const double x1 = x0 + ww, y1 = y0 + hh;
+  const double xr = x1 + .5, yb = y1 + .5;
+  long long L = (long long)std::floor(xl), T = (long long)std::floor(yt);      // (|values| < 2^46: exact)
+  const long long R = (long long)std::floor(xr) - 1, B = (long long)std::floor(yb) - 1;
+  long long Wd = R - L + 1, Ht = B - T + 1;
+  if (Wd < 1 || Ht < 1) return 0;
+  if (p.border == 1) {
+    if (Wd >= org_w) { L = 0; Wd = org_w; }
+    else if (L < 0) L = 0;
+    else if (L + Wd > org_w) L = org_w - Wd;
+    if (Ht >= org_h) { T = 0; Ht = org_h; }
+    else if (T < 0) T = 0;
+    else if (T + Ht > org_h) T = org_h - Ht;
+  } else {
+    const long long L1 = std::max(L, 0LL), R1 = std::min(R, (long long)org_w - 1);
+    const long long T1 = std::max(T, 0LL), B1 = std::min(B, (long long)org_h - 1);
+    if (L1 > R1 || T1 > B1) return 0;
+    L = L1; T = T1; Wd = R1 - L1 + 1; Ht = B1 - T1 + 1;
+  }
+  if (Wd < p.min_size || Ht < p.min_size) return 0;
+  win[0] = (int)L; win[1] = (int)T; win[2] = (int)Wd; win[3] = (int)Ht;
+  return 1;
+}
+
+int mscnn_net_crop_window(const mscnn_crops_params* p, const double row[5], int org_h, int org_w, int win[4]) {
+  std::ostringstream e;
+  if (!p || !row || !win) e << "null pointer";
+  else if (org_h <= 0 || org_w <= 0 || org_h > (1 << 30) || org_w > (1 << 30)) e << "the frame is " << org_h << " x " << org_w;
+  else e << crops_params_error(*p);
+  if (!e.str().empty()) {
+    g_err = "crop_window: " + e.str();
+    return -1;
+  }
+  return crop_window_of(*p, row, org_h, org_w, win);
+}
+
+// Every detection of the pack the last blocking multi call left in det_host as a patch: the host walks the pack (it lies in pinned
+// host memory) and computes the windows, the views op cuts and resizes them in one call.  Host frames are staged through the stage's
+// own buffer -- img_in may already hold the next forward's frames -- and only those that have a crop.
+int mscnn_net_crops(mscnn_net* n, const unsigned char* const* frames_rgb, int on_device, const int* org_h, const int* org_w, int count,
+                    const mscnn_crops_params* p, float* out, int out_on_device, mscnn_crop_info* info_host, int* num_crops,
+                    int* num_dropped) {
+  return guarded([&] {
+    CHECK(n && frames_rgb && org_h && org_w && p && out && info_host && num_crops && num_dropped) << "crops: null pointer";
+    CHECK_GE(n->device, 0) << "crops: the net was built with device " << n->device << " (graph only)";
+    const mscnn_net::Render& r = n->render;
+    CHECK(r.valid) << "crops: no pack to cut from: the last call that used the net's pack block was not a successful mscnn_net_detect_multi, "
+                      "mscnn_net_detect_cascade_multi or mscnn_net_detect_merge_end";
+    CHECK_EQ(count, r.frames) << "crops: " << count << " frames, that call had " << r.frames << " images (lists)";
+    for (int b = 0; b < count; ++b)
+      CHECK(frames_rgb[b] && org_h[b] > 0 && org_w[b] > 0 && org_h[b] <= (1 << 30) && org_w[b] <= (1 << 30))
+          << "crops: frame " << b << " is " << org_h[b] << " x " << org_w[b] << (frames_rgb[b] ? "" : " at a null pointer");
+    const std::string bad = crops_params_error(*p);
+    CHECK(bad.empty()) << "crops: " << bad;
+    CHECK(p->slot < r.slots) << "crops: slot " << p->slot << " is outside [-1, " << r.slots << ")";
+    CHECK(r.ids || p->tracked_only == 0) << "crops: tracked_only " << p->tracked_only
+                                         << " needs track ids, and that call ran no tracker (mscnn_net_set_tracker)";
+    // the windows, in the order (frame, slot, row)
+    const int K = r.slots;
+    const char* pack = static_cast<const char*>(n->det_host);
+    const int* hdr = reinterpret_cast<const int*>(pack);
+    const double* rows = reinterpret_cast<const double*>(pack + mscnn_multi_pack_layout_of(r.frames * K, r.cap).dets);
+    const int* ids = r.ids ? reinterpret_cast<const int*>(pack + r.ids_at) : nullptr;
+    std::vector<mscnn_preprocess_view> views;
+    std::vector<int> place(count, -1);      // frame -> its place among the frames that have a crop
+    int dropped = 0;
+    for (int b = 0; b < count; ++b) {
+      const int* e0 = hdr + MSCNN_MULTI_PACK_WORDS * (size_t)(1 + b * K);
+      const bool shared = K >= 2 && e0[2] == e0[MSCNN_MULTI_PACK_WORDS + 2];
+      for (int k = p->slot < 0 ? 0 : p->slot; k < (p->slot < 0 ? K : p->slot + 1); ++k) {
+        const int* e = e0 + MSCNN_MULTI_PACK_WORDS * (size_t)k;
+        const long long cnt = e[0], off = shared ? (long long)K * e[2] + (long long)k * e[1] : (long long)e[2];
+        if (cnt < 0 || off < 0 || off + cnt > r.cap) continue;
+        for (long long j = 0; j < cnt; ++j) {
+          const int id = ids ? ids[off + j] : 0;
+          if (p->tracked_only && !(id > 0)) continue;
+          int win[4];
+          const int rc = mscnn_net_crop_window(p, rows + 5 * (off + j), org_h[b], org_w[b], win);
+          CHECK_GE(rc, 0) << g_err;
+          if (rc == 0) continue;
+          if ((int)views.size() >= p->max_crops) { ++dropped; continue; }
+          if (place[b] < 0) place[b] = 0;
+          info_host[views.size()] = mscnn_crop_info{b, k, (int)j, id, win[0], win[1], win[2], win[3]};
+          views.push_back(mscnn_preprocess_view{b, win[0], win[1], win[2], win[3], 0});
+        }
+      }
+    }
+    *num_crops = (int)views.size();
+    *num_dropped = dropped;
+    if (views.empty()) return;
+    // the frames that have a crop, each once
+    std::vector<const unsigned char*> src;
+    std::vector<int> hs, ws;
+    std::vector<size_t> off(1, 0);
+    for (int b = 0; b < count; ++b) {
+      if (place[b] < 0) continue;
+      place[b] = (int)src.size();
+      src.push_back(frames_rgb[b]); hs.push_back(org_h[b]); ws.push_back(org_w[b]);
+      off.push_back(off.back() + (((size_t)org_h[b] * org_w[b] * 3 + 255) & ~(size_t)255));
+    }
+    for (mscnn_preprocess_view& v : views) v.frame = place[v.frame];
+    hipStream_t st = (hipStream_t)Caffe::stream();
+    const int F = (int)src.size(), V = (int)views.size();
+    if (!on_device) {
+      unsigned char* d = static_cast<unsigned char*>(n->crops.in.Reserve(off[F]));
+      for (int f = 0; f < F; ++f) {
+        HIP_CHECK(hipMemcpyAsync(d + off[f], src[f], (size_t)hs[f] * ws[f] * 3, hipMemcpyHostToDevice, st));
+        src[f] = d + off[f];
+      }
+    }
+    const size_t wb = mscnn_preprocess_views_workspace_bytes(views.data(), V, p->out_h, p->out_w);
+    void* wsp = n->crops.ws.Reserve(wb);
+    const size_t bytes = (size_t)V * 3 * p->out_h * p->out_w * sizeof(float);
+    float* dst = out_on_device ? out : static_cast<float*>(n->crops.out.Reserve(bytes));
+    MSCNN_CHECK(mscnn_preprocess_views_u8_f32(src.data(), hs.data(), ws.data(), F, views.data(), V, dst, p->out_h, p->out_w, p->mean_bgr,
+                                              wsp, wb, st));
+    if (!out_on_device) {      // the patches in one copy, then the one synchronisation
+      HIP_CHECK(hipMemcpyAsync(out, dst, bytes, hipMemcpyDeviceToHost, st));
       HIP_CHECK(hipStreamSynchronize(st));
     }
   });

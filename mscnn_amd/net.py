@@ -51,6 +51,56 @@ class RenderParams(C.Structure):
                 ("colors", (C.c_ubyte * 3) * 32)]
 
 
+class CropsParams(C.Structure):
+    """mscnn_crops_params (include/mscnn_net.h; 64 bytes): which rows of the pack become patches, and how their windows are made."""
+    _fields_ = [("thr", C.c_double), ("context", C.c_double), ("fit", C.c_int), ("border", C.c_int), ("min_size", C.c_int),
+                ("out_h", C.c_int), ("out_w", C.c_int), ("max_crops", C.c_int), ("slot", C.c_int), ("tracked_only", C.c_int),
+                ("mean_bgr", C.c_float * 3)]
+
+
+class CropInfo(C.Structure):
+    """mscnn_crop_info (include/mscnn_net.h; 32 bytes): where a crop came from and its window in frame pixels."""
+    _fields_ = [(f, C.c_int) for f in ("frame", "slot", "row", "track_id", "x0", "y0", "w", "h")]
+
+
+CROP_INFO = np.dtype([(f, "<i4") for f in ("frame", "slot", "row", "track_id", "x0", "y0", "w", "h")])
+CROP_BORDERS = {"clip": 0, "shift": 1}
+
+
+class CropInfoArray(np.ndarray):
+    """Net.crops' second result: a CROP_INFO record array, one entry per patch, with .dropped = the rows that would have given a
+    crop past max_crops (mscnn_net_crops' num_dropped)."""
+    dropped = 0
+
+    def __array_finalize__(self, obj):
+        self.dropped = getattr(obj, "dropped", 0)
+
+
+def crops_params(size=(128, 64), thr=0.3, context=1.0, fit=False, border="clip", min_size=1, max_crops=1, slot=None, tracked_only=False,
+                 mean=(0, 0, 0)):
+    """The keywords of Net.crops as a CropsParams (size = (out_h, out_w); border "clip" or "shift"; slot None = every slot)."""
+    if isinstance(border, str) and border not in CROP_BORDERS:
+        raise NetError(f"crops: border {border!r} is none of {sorted(CROP_BORDERS)}")
+    mean = tuple(float(v) for v in mean)
+    if len(mean) != 3:
+        raise NetError(f"crops: mean holds {len(mean)} values (B, G, R)")
+    return CropsParams(float(thr), float(context), int(fit), int(CROP_BORDERS.get(border, border)), int(min_size), int(size[0]), int(size[1]),
+                       int(max_crops), -1 if slot is None else int(slot), int(tracked_only), (C.c_float * 3)(*mean))
+
+
+def crop_window(params, row, org_hw):
+    """mscnn_net_crop_window: the window (x0, y0, w, h) Net.crops cuts for the row [x y w h score] in a frame of org_hw = (h, w), or
+    None when the row gives no crop.  params: a CropsParams, or a dict of crops_params' keywords.  Pure host code: no net, no device.
+    Refused params raise NetError naming the value.  include/mscnn_net.h (mscnn_net_crops) states the rule."""
+    p = params if isinstance(params, CropsParams) else crops_params(**params)
+    r = (C.c_double * 5)(*[float(v) for v in row])
+    win = (C.c_int * 4)()
+    rc = lib().mscnn_net_crop_window(C.byref(p), r, int(org_hw[0]), int(org_hw[1]), win)
+    if rc < 0:
+        raise NetError(lib().mscnn_net_last_error().decode())
+    return tuple(win) if rc else None
+
+
 RENDER_LABELS = {"none": 0, "score": 1, "id": 2, "both": 3}
 RENDER_COLOR_BY = {"slot": 0, "id": 1}
 # the default palette of Net.render: eight hues that stay apart on a road scene, RGB (the look is a matter of taste no test judges)
@@ -149,6 +199,7 @@ def lib():
             "mscnn_net_set_tracker_streams": [vp, ci], "mscnn_net_set_frame_streams": [vp, vp, ci],
             "mscnn_net_get_tracker_streams": [vp, vp, vp, ci, vp], "mscnn_net_tracker_reset_stream": [vp, ci],
             "mscnn_net_render": [vp, vp, ci, vp, vp, ci, vp, vp, ci],
+            "mscnn_net_crop_window": [vp, vp, ci, ci, vp], "mscnn_net_crops": [vp, vp, ci, vp, vp, ci, vp, vp, ci, vp, vp, vp],
         }
         for name, args in sig.items():
             getattr(L, name).argtypes = args
@@ -813,6 +864,75 @@ class Net:
         _check(lib().mscnn_net_render(self._h, (C.c_void_p * max(B, 1))(*ptrs), 1 if device else 0, (C.c_int * max(B, 1))(*hs),
                                       (C.c_int * max(B, 1))(*ws), B, C.byref(p), (C.c_void_p * max(B, 1))(*optrs), 1 if device else 0))
         return outs
+
+    def crops(self, frames, size=(128, 64), thr=0.3, context=1.0, fit=False, border="clip", min_size=1, max_crops=None, slot=None,
+              tracked_only=False, mean=(0, 0, 0), out=None):
+        """mscnn_net_crops: every detection of the last detect_multi, detect_cascade_multi or detect_merge_end with score >= thr as a
+        float32 patch of size = (out_h, out_w), planes B, G, R with mean subtracted, cut out of the frames it detected on and resized on
+        the device (the scripts' imresize).  The window is the box scaled about its centre by context (1 .. 16), with fit grown to the
+        patch's aspect ratio, then clipped to the frame (border "clip") or moved inwards ("shift"); windows under min_size pixels give
+        no crop; slot = only that slot; tracked_only = only rows with a track id > 0 (needs set_tracker).  include/mscnn_net.h states
+        the window rule, crop_window() computes it for one row.
+        Returns (patches, info).  patches: [n, 3, out_h, out_w] -- a numpy array for host frames (uint8 [h, w, 3] arrays), a CUDA
+        tensor for contiguous uint8 CUDA tensors (then only the windows' table crosses the bus, and the call is asynchronous on the
+        net's stream).  out: a contiguous float32 buffer [>= max_crops, 3, out_h, out_w] to write into, numpy or CUDA whatever the
+        frames are; patches is then out[:n], and the slices behind it are untouched.  info: a CropInfoArray (records frame, slot, row,
+        track_id, x0, y0, w, h; row = the index in its segment), in the order (frame, slot, row); info.dropped = the rows that would
+        have given a crop past max_crops.  max_crops None: out's first dimension, else the number of rows that call returned, so that
+        nothing can be dropped.  Like render it reads the pack and steps nothing; both may follow one detect call in either order."""
+        frames = list(frames)
+        on_dev = [hasattr(f, "is_cuda") and f.is_cuda for f in frames]
+        if any(on_dev) and not all(on_dev):
+            raise NetError("crops: a list that mixes host and device frames")
+        device = any(on_dev)
+        if device:
+            for b, f in enumerate(frames):
+                if str(f.dtype) != "torch.uint8" or f.dim() != 3 or f.shape[2] != 3 or not f.is_contiguous():
+                    raise NetError(f"crops: frame {b} is not a contiguous uint8 [h, w, 3] tensor")
+            keep = frames
+            ptrs = [f.data_ptr() for f in frames]
+        else:
+            keep = []
+            for b, f in enumerate(frames):
+                if not isinstance(f, np.ndarray) or f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3:
+                    raise NetError(f"crops: frame {b} is not a uint8 [h, w, 3] array")
+                keep.append(np.ascontiguousarray(f))
+            ptrs = [a.ctypes.data for a in keep]
+        oh, ow = int(size[0]), int(size[1])
+        if max_crops is None:
+            seg = getattr(self, "_track_seg", None)
+            max_crops = int(out.shape[0]) if out is not None else max(1, int(seg[2].sum()) if seg else 1)
+        p = crops_params((oh, ow), thr, context, fit, border, min_size, max_crops, slot, tracked_only, mean)
+        rows = max(int(max_crops), 1)
+        out_dev = device if out is None else bool(getattr(out, "is_cuda", False))
+        if out is None:
+            if 1 <= oh <= 1024 and 1 <= ow <= 1024:
+                shape = (rows, 3, oh, ow)
+            else:
+                shape = (1, 3, 1, 1)      # (the call refuses the size, naming it)
+            if out_dev:
+                import torch
+                buf = torch.empty(shape, dtype=torch.float32, device=frames[0].device)
+            else:
+                buf = np.empty(shape, np.float32)
+        else:
+            buf = out
+            ok = (tuple(buf.shape[1:]) == (3, oh, ow) and buf.shape[0] >= rows and (
+                (str(buf.dtype) == "torch.float32" and buf.is_contiguous()) if out_dev else
+                (isinstance(buf, np.ndarray) and buf.dtype == np.float32 and buf.flags.c_contiguous)))
+            if not ok:
+                raise NetError(f"crops: out is not a contiguous float32 buffer of shape [>= {rows}, 3, {oh}, {ow}]")
+        info = np.zeros(rows, CROP_INFO)
+        n, dropped = C.c_int(0), C.c_int(0)
+        B = len(frames)
+        hs = [int(f.shape[0]) for f in keep]
+        ws = [int(f.shape[1]) for f in keep]
+        _check(lib().mscnn_net_crops(self._h, (C.c_void_p * max(B, 1))(*ptrs), 1 if device else 0, (C.c_int * max(B, 1))(*hs),
+                                     (C.c_int * max(B, 1))(*ws), B, C.byref(p), C.c_void_p(buf.data_ptr() if out_dev else buf.ctypes.data),
+                                     1 if out_dev else 0, info.ctypes.data_as(C.c_void_p), C.byref(n), C.byref(dropped)))
+        res = info[:n.value].view(CropInfoArray)
+        res.dropped = dropped.value
+        return buf[:n.value], res
 
     def tracker_state(self, raw=False):
         """mscnn_net_tracker_state: the committed table, one dict per slot -- n, next_id, frame, dropped, skipped and tracks = the

@@ -68,6 +68,11 @@ run_cascademscnn.m:136-150 on the device (Net.render behind every detect_cascade
 box of every (output, class) with a score >= T (default 0.3, the script's show_thr) outlined and labelled; --pixelate N replaces the
 boxes' interiors with an N x N mosaic (anonymise the faces of a frame before it leaves the machine).  As tools/run_mscnn_detection.py;
 the result files are unchanged; the look of the glyphs and colours is nobody's pin.
+--crops-out DIR [--crop-size HxW] [--crop-thr T] [--crop-context F] [--crop-fit] [--crop-border clip|shift] [--crop-min N]
+[--crop-tracked]: every detection of every (output, class) with a score >= T as a fixed-size patch, cut and resized on the device
+(Net.crops behind every detect_cascade_multi and detect_merge_end, next to the render call): DIR/<frame>_<slot>_<row>.png, slot =
+output x classes + class, with --track DIR/id<track>/<frame>_<slot>_<row>.png.  As tools/run_mscnn_detection.py; the result files are
+unchanged.
 
 Everything here is host glue over calls the test-suite covers one by one (Net.set_images, forward, detect_cascade_multi,
 reshape_input, kitti.write_detections_dlm)."""
@@ -166,7 +171,7 @@ def main(argv=None):
     import numpy as np
     import torch
     from mscnn_amd import kitti, net as mnet, synth, zoo
-    from run_mscnn_detection import (apply_merge_settings, apply_track_setting, frame_tracks, list_images, load_rgb_u8, merge_cand_cap, merge_passes,
+    from run_mscnn_detection import (apply_merge_settings, apply_track_setting, crop_frames, frame_tracks, list_images, load_rgb_u8, merge_cand_cap, merge_passes,
                                      names_for, one_forward_merge, render_frames, run_frame_views, run_seq_clips, seq_on, set_group_streams, track_on, views_per_frame,
                                      write_tracks, write_tubelets)
 
@@ -264,6 +269,7 @@ def main(argv=None):
         per_image, _ = net.detect_merge_end()
         trks = frame_tracks(net, a)
         render_frames(net, a, [img], [path], k)
+        crop_frames(net, a, [img], [path], k)
         for (o, c) in results:
             results[(o, c)].append(per_image[0][o * len(cls_ids) + c][0])
             if trks:
@@ -294,6 +300,7 @@ def main(argv=None):
                      org_hw=np.array([p["org_hw"] for p in params], np.float64), **blobs)
         trks = frame_tracks(net, a)
         render_frames(net, a, dev_imgs, group, g0 + 1)
+        crop_frames(net, a, dev_imgs, group, g0 + 1)
         for i in range(len(group)):
             for key in results:
                 results[key].append(per_image[i][key[0]][key[1]][0])

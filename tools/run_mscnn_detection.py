@@ -25,6 +25,8 @@ examples/kitti_result/writeDetForEval.m.
          [--track --streams N --batch B]                     # the frames are N multiplexed cameras: a table of tracks per camera
          [--render-out DIR] [--show-thr T] [--render-label none|score|id|both] [--render-color slot|id] [--pixelate N]
                                                              # the scripts' `show` block on the device (Net.render): annotated PNGs
+         [--crops-out DIR] [--crop-size HxW] [--crop-thr T] [--crop-context F] [--crop-fit] [--crop-border clip|shift] [--crop-min N]
+         [--crop-tracked]                                    # every detection as a fixed-size patch, cut on the device (Net.crops)
   python tools/run_mscnn_detection.py --model kitti_car/mscnn-7s-576 --synthetic 8      # no dataset / weights at hand: the generated
                                                                                         # deploy net, seeded weights, synthetic frames
 
@@ -116,6 +118,15 @@ scripts print the score at the top edge), id or both (the track id; these need -
 id (with --track); --pixelate N replaces every box's interior with an N x N mosaic (2 .. 64: anonymise the face nets' detections).
 It works with --batch, --streams, --track and the merge flags; without one of them the frames go through detect_multi in groups of
 one (Net.render reads the pack of a multi call).  The result files are unchanged.
+--crops-out DIR hands every detection to a second stage as a patch: behind the frame's detect call, next to the render call,
+Net.crops cuts the window of every box with a score >= --crop-thr T (default: the threshold above) out of the frame on the device and
+resizes it to --crop-size HxW (default 128x64, the scripts' imresize); the window is the box scaled about its centre by
+--crop-context F (default 1), with --crop-fit grown to the patch's aspect ratio instead of stretched, clipped to the frame or with
+--crop-border shift moved inwards; --crop-min N drops windows under N pixels.  Every patch is written as DIR/<frame>_<slot>_<row>.png
+(slot = the class's place in --cls-ids, row = the detection's place in its list, 0 = the best score), with --track as
+DIR/id<track>/<frame>_<slot>_<row>.png -- a gallery per track; --crop-tracked (with --track) keeps confirmed tracks only.  The patch
+is cut with mean 0, its planes reordered to RGB and every value v written as uint8(min(max(floor(v + .5), 0), 255)).  It works with
+--batch, --streams, --track, the merge flags and --render-out, and is refused where --render-out is.  The result files are unchanged.
 --streams N (with --track): the input is N cameras multiplexed, frame i of the input order (0-based) belongs to stream i % N, and
 every stream has a table of tracks of its own (Net.set_tracker(streams=N); Net.set_frame_streams before every forward, from the
 frames' own indices, so --batch B need not be a multiple of N).  One launch steps all the streams of a forward side by side.  Not with
@@ -268,6 +279,19 @@ def add_merge_flags(ap):
                     "or per track id (needs --track)")
     ap.add_argument("--pixelate", type=int, default=0, metavar="N", help="with --render-out: replace every drawn box's interior with an N x N "
                     "mosaic of the frame, 2 .. 64 (default 0: off)")
+    ap.add_argument("--crops-out", default=None, metavar="DIR", help="cut every detection out of its frame on the device as a fixed-size patch "
+                    "(Net.crops) and write DIR/<frame>_<slot>_<row>.png, with --track DIR/id<track>/<frame>_<slot>_<row>.png")
+    ap.add_argument("--crop-size", default="128x64", metavar="HxW", help="with --crops-out: the patch size, each 1 .. 1024 (default 128x64)")
+    ap.add_argument("--crop-thr", type=float, default=None, metavar="T", help="with --crops-out: cut the boxes with a score >= T (default: the "
+                    "threshold --render-out draws with)")
+    ap.add_argument("--crop-context", type=float, default=1.0, metavar="F", help="with --crops-out: the window is the box scaled about its centre "
+                    "by F, 1 .. 16 (default 1)")
+    ap.add_argument("--crop-fit", action="store_true", help="with --crops-out: grow the window to the patch's aspect ratio instead of stretching it")
+    ap.add_argument("--crop-border", choices=["clip", "shift"], default="clip", help="with --crops-out: a window that leaves the frame is clipped "
+                    "(the default) or moved inwards")
+    ap.add_argument("--crop-min", type=int, default=1, metavar="N", help="with --crops-out: no patch of a window narrower or lower than N pixels "
+                    "(default 1)")
+    ap.add_argument("--crop-tracked", action="store_true", help="with --crops-out and --track: only the detections of a confirmed track")
     ap.add_argument("--soft-thr", type=float, default=0.001, metavar="T", help="with --soft-nms: stop picking when the best live score is below T; "
                     "with --matrix-nms: keep the scores >= T (default 0.001)")
     ap.add_argument("--max-dets", type=int, default=0, metavar="N", help="with --soft-nms / --matrix-nms / --wbf: at most N detections per class and "
@@ -326,6 +350,49 @@ def render_frames(net, a, frames, paths, first):
     for i, (o, path) in enumerate(zip(outs, paths)):
         arr = o if isinstance(o, np.ndarray) else o.cpu().numpy()
         Image.fromarray(arr, "RGB").save(os.path.join(a.render_out, f"{frame_id(path, first + i):06d}.png"))
+
+
+def crops_on(a):
+    """--crops-out: every detect call of the run is followed by a Net.crops of its frames."""
+    return getattr(a, "crops_out", None) is not None
+
+
+def crop_thr_of(a):
+    """--crop-thr, or the threshold the `show` block would draw with (show_thr_of)."""
+    return a.crop_thr if a.crop_thr is not None else show_thr_of(a)
+
+
+def parse_crop_size(text):
+    """--crop-size HxW -> (H, W), each 1 .. 1024; raises ValueError on anything else."""
+    import re
+    m = re.fullmatch(r"(\d+)x(\d+)", text.strip())
+    if not m or not (1 <= int(m.group(1)) <= 1024 and 1 <= int(m.group(2)) <= 1024):
+        raise ValueError(f"--crop-size {text!r} is not HxW with both inside 1 .. 1024")
+    return int(m.group(1)), int(m.group(2))
+
+
+def patch_to_rgb_u8(patch):
+    """A float [3, h, w] patch of Net.crops with mean 0 (planes B, G, R) as a uint8 RGB image [h, w, 3]: every value v, in double,
+    becomes uint8(min(max(floor(v + .5), 0), 255)) -- the bicubic resize overshoots, hence the clamp."""
+    v = np.asarray(patch, np.float64)[::-1].transpose(1, 2, 0)
+    return np.ascontiguousarray(np.minimum(np.maximum(np.floor(v + .5), 0), 255).astype(np.uint8))
+
+
+def crop_frames(net, a, frames, paths, first):
+    """--crops-out behind a detect_multi / detect_cascade_multi / detect_merge_end over `frames` (numpy arrays or device tensors, as
+    render_frames): every detection with a score >= the threshold as DIR/<frame>_<slot>_<row>.png, with --track as
+    DIR/id<track>/<frame>_<slot>_<row>.png (id0: no confirmed track); `first` is the 1-based number of frames[0] in the run."""
+    if not crops_on(a):
+        return
+    from PIL import Image
+    patches, info = net.crops(frames, size=a.crop_size, thr=crop_thr_of(a), context=a.crop_context, fit=a.crop_fit, border=a.crop_border,
+                              min_size=a.crop_min, tracked_only=a.crop_tracked)
+    arr = patches if isinstance(patches, np.ndarray) else patches.cpu().numpy()
+    for patch, rec in zip(arr, info):
+        b = int(rec["frame"])
+        d = os.path.join(a.crops_out, f"id{int(rec['track_id'])}") if track_on(a) else a.crops_out
+        os.makedirs(d, exist_ok=True)
+        Image.fromarray(patch_to_rgb_u8(patch), "RGB").save(os.path.join(d, f"{frame_id(paths[b], first + b):06d}_{int(rec['slot'])}_{int(rec['row'])}.png"))
 
 
 def apply_track_setting(net, a):
@@ -459,6 +526,25 @@ def check_merge_flags(ap, a):
                      "--proposals-only")
     elif a.show_thr is not None or a.render_label != "score" or a.render_color != "slot" or a.pixelate != 0:
         ap.error("--show-thr / --render-label / --render-color / --pixelate belong to --render-out")
+    if crops_on(a):
+        try:
+            a.crop_size = parse_crop_size(a.crop_size)
+        except ValueError as e:
+            ap.error(str(e))
+        if a.crop_thr is not None and a.crop_thr != a.crop_thr:
+            ap.error("--crop-thr nan: the threshold must be a number")
+        if not 1.0 <= a.crop_context <= 16.0:      # (a NaN fails)
+            ap.error(f"--crop-context {a.crop_context:g}: the factor must lie inside [1, 16]")
+        if a.crop_min < 1:
+            ap.error(f"--crop-min {a.crop_min}: must be >= 1")
+        if a.crop_tracked and not track_on(a):
+            ap.error("--crop-tracked keeps the detections of confirmed tracks: it needs --track")
+        if getattr(a, "rois_in", "") or getattr(a, "proposals_only", False):
+            ap.error("--crops-out cuts the detections of every frame: not with --rois-in (frames without a box run no final stage) or "
+                     "--proposals-only")
+    elif (a.crop_size != "128x64" or a.crop_thr is not None or a.crop_context != 1.0 or a.crop_fit or a.crop_border != "clip" or a.crop_min != 1
+          or a.crop_tracked):
+        ap.error("--crop-size / --crop-thr / --crop-context / --crop-fit / --crop-border / --crop-min / --crop-tracked belong to --crops-out")
     if not 0.0 <= a.soft_thr < float("inf"):
         ap.error(f"--soft-thr {a.soft_thr:g}: the threshold must be a finite value >= 0")
     if a.max_dets < 0:
@@ -561,6 +647,7 @@ def run_seq_clips(a, net, text, files, net_hw, shape, slots, load, add):
         seqs = net.detect_merge_sequences()
         trks = frame_tracks(net, a)
         render_frames(net, a, imgs, files[c0:c0 + a.clip], c0 + 1)
+        crop_frames(net, a, imgs, files[c0:c0 + a.clip], c0 + 1)
         out += [([per_image[t][s][0] for s in range(slots)], [seqs[t][s] for s in range(slots)], trks[t] if trks else None) for t in range(len(imgs))]
         k = c0 + len(imgs)
         print(f"idx {k}/{len(files)}, avgtime={used / k:.4f}s (clips of {a.clip} frames, {n_fwd} forwards per frame)")
@@ -676,8 +763,8 @@ def main(argv=None):
         return run_batched(a, net, files, names, cls_ids, imgH, imgW, per_class, per_image_props, forward, rois)
     if a.scales or a.flip or a.tiles or one_forward_merge(a):
         return run_merged(a, net, text, files, names, cls_ids, imgH, imgW, per_class)
-    if track_on(a) or render_on(a):                                           # --track / --render-out alone: groups of one frame through detect_multi
-        return run_batched(a, net, files, names, cls_ids, imgH, imgW, per_class, per_image_props, forward, rois)      # (Net.detect is refused while the tracker is on, and leaves Net.render no pack)
+    if track_on(a) or render_on(a) or crops_on(a):                            # --track / --render-out / --crops-out alone: groups of one frame through detect_multi
+        return run_batched(a, net, files, names, cls_ids, imgH, imgW, per_class, per_image_props, forward, rois)      # (Net.detect is refused while the tracker is on, and leaves Net.render / Net.crops no pack)
     used = 0.0
     for k, path in enumerate(files, start=1):
         img = load_frame(path, k)
@@ -780,6 +867,7 @@ def run_merged(a, net, text, files, names, cls_ids, imgH, imgW, per_class):
         per_image, _ = net.detect_merge_end()
         a.track_ids += frame_tracks(net, a) or []
         render_frames(net, a, [img], [path], k)
+        crop_frames(net, a, [img], [path], k)
         by_type = {}
         for ci, c in enumerate(cls_ids):
             dets = per_image[0][ci][0]
@@ -831,6 +919,7 @@ def run_batched(a, net, files, names, cls_ids, imgH, imgW, per_class, per_image_
             per_image, _ = net.detect_multi([dict(p, proposal_thr=a.proposal_thr, nms_overlap=a.nms_overlap) for p in params], cls_ids)
             a.track_ids += frame_tracks(net, a) or []
             render_frames(net, a, dev_imgs, group, g0 + 1)
+            crop_frames(net, a, dev_imgs, group, g0 + 1)
         else:
             per_image = [[(np.zeros((0, 5)), None)] * len(cls_ids)] * len(group)
         for i, path in enumerate(group):
