@@ -87,6 +87,7 @@
  *   detections_merge_seq_fwd   cand, workspace, pack_dev 16, seq_dev 4: refuses
  *   tracks_update_fwd, tracks_update_streams_fwd, tracks_state_reset, tracks_state_reset_slots
  *                              pack_dev, state_in, state_out (state) 16, track_ids_dev 4: refuses
+ *   tracks_update_kalman_fwd   pack_dev, state_in, state_out, filter_in, filter_out 16, track_ids_dev 4: refuses
  *   proposals_multi_fwd        props 8: refuses
  *   rois_ingest                rows 8: refuses; rois, props, image_rows, status 4
  */
@@ -1002,9 +1003,10 @@ MSCNN_API int mscnn_detections_merge_seq_fwd(const double* nms_overlap /* HOST, 
  * Tracking by Associating Every Detection Box", 2022).  A small table of tracks per slot (class, or output x class) lives in device
  * memory from call to call; every new frame's detections are associated with the tracks in two passes -- the high-score detections
  * first, then the low-score detections against the tracks still unmatched -- and every detection row gets a persistent track id.
- * Two deliberate departures from the paper: the motion is a constant-velocity prediction of the box centre in place of the Kalman
- * filter, and the matching is greedy by descending overlap under a total order in place of the Hungarian solver.  Both make the
- * result independent of reduction shape and scheduling: bit-exact against tests/track_witness.py.
+ * Two deliberate departures from the paper: the motion of THIS op is a constant-velocity prediction of the box centre (the paper's
+ * Kalman filter is there on request, beside it: mscnn_tracks_update_kalman_fwd below), and the matching is greedy by descending
+ * overlap under a total order in place of the Hungarian solver.  Both make the result independent of reduction shape and scheduling:
+ * bit-exact against tests/track_witness.py.
  * pack_dev: a multi pack as mscnn_detections_multi_fwd, the merge ops and Seq-NMS write it, mscnn_multi_pack_layout_of(S, cap) with
  * S = num_frames * num_slots; segment s = t * K + k is frame t, slot k.  The op only reads it.  The segment's rows [x y w h score]
  * start at its ROW OFFSET: table word 2 as the merge ops write it (s * cand_cap); in the pack of a batched forward, where the K
@@ -1108,6 +1110,71 @@ MSCNN_API int mscnn_tracks_update_streams_fwd(const mscnn_track_params* params, 
                                               const int* stream_of /* HOST, [num_frames] */, const void* pack_dev, int cap,
                                               const void* state_in, void* state_out, int max_tracks, int* track_ids_dev, void* stream);
 MSCNN_API int mscnn_tracks_state_reset_slots(void* state, int num_slots_total, int max_tracks, int first_slot, int count, void* stream);
+
+/* The tracker with the paper's motion model: a constant-velocity Kalman filter per track on (cx, cy, a = w / h, h), as SORT, DeepSORT
+ * and ByteTrack run it, in the place of steps 3 and 6's linear prediction.  A second setting beside mscnn_track_params, a side table
+ * beside the track state, an entry point of its own: mscnn_track_params, mscnn_track_record and the two ops above do not change, and
+ * MSCNN_TRACK_MOTION_NONE / _LINEAR stay what they are (on a noise-free approaching box the linear rule overlaps better than the
+ * filter: the filter is an option, not a replacement).  The greedy walk in place of the Hungarian solver remains.
+ * ONE argument: the op would have 17, so it takes a pointer to a call struct that carries them all, the stream among them (`size`
+ * must be sizeof(mscnn_tracks_kalman_call)).  The stream contract binds it as every op: it waits for nothing and runs in the order of
+ * call->stream.  call->track, call->filter, call->stream_of are HOST and read before the call returns.
+ * With a diagonal start, diagonal noise and a position-only measurement the eight-state filter decouples exactly into four two-state
+ * filters (component c: position x[c], velocity v[c]), so a record holds per component the position's variance p, the covariance q and
+ * the velocity's variance r: 12 covariance numbers, no matrix is inverted.  mscnn_track_kalman_record: x = (cx, cy, a, h), v their
+ * velocities, (p, q, r) as said.  filter_in / filter_out: num_streams * num_slots * max_tracks records, the record of track i of
+ * table (s, k) at index (s * num_slots + k) * max_tracks + i -- beside record i of that table in the state.  There is no header and
+ * no reset op: a filter record is initialised at its track's birth, and a table with n = 0 has none.
+ * The ten steps of mscnn_tracks_update_streams_fwd run unchanged except as follows; track->motion must be MSCNN_TRACK_MOTION_NONE,
+ * vel_gain is not read.  With sp, sv, sa, sav, sam = std_position, std_velocity, std_aspect, std_aspect_velocity, std_aspect_measure,
+ * all in double, one rounding per operation, in exactly this order:
+ *   3'. Predict, every track.  freeze_lost_height != 0 and misses > 0: v[3] = 0.  h = x[3]; e = sp * h; g = sv * h;
+ *       sigp = {e, e, sa, e}, sigv = {g, g, sav, g}.  Per component:
+ *           x = x + v;  t0 = p + q;  t1 = q + r;  p = (t0 + t1) + sigp * sigp;  q = t1;  r = r + sigv * sigv
+ *       Then w = x[2] * x[3]; box = {x[0] - w / 2, x[1] - x[3] / 2, w, x[3]}; vel = {v[0], v[1]}.
+ *   6'. Matched with detection B.  z = {B.x + B.w / 2, B.y + B.h / 2, B.w / B.h, B.h}; h = x[3] (the predicted one); e = sp * h;
+ *       sigm = {e, e, sam, e}.  Per component:
+ *           s = p + sigm * sigm;  kx = p / s;  kv = q / s;  y = z - x;  x = x + kx * y;  v = v + kv * y;
+ *           r = r - kv * q;  p = p - kx * p;  q = q - kx * q                                   (r reads the old q)
+ *       box from x as in 3', obs = B bit for bit, vel = {v[0], v[1]}; score, hits, misses, confirmed as in step 6.
+ *   7'. An unmatched track keeps its predicted x, v, p, q, r and box.
+ *   8'. Birth from B.  x = z(B), v = 0, q = 0; h = B.h; e = (2 * sp) * h; g = (10 * sv) * h; p = {e * e, e * e, sa * sa, e * e},
+ *       r = {g * g, g * g, sav * sav, g * g}; box = obs = B bit for bit.
+ *   9'. Compaction moves a filter record with its track.
+ * A matched detection has w, h > 0 by the overlap statements (iw, ih > 0 with a finite box).  A birth with h <= 0 gets a NaN / inf
+ * aspect and from the next prediction on a NaN / inf box, which pairs with nothing (a NaN r is no pair): it ages out as step 7 says.
+ * filter_in == filter_out (in place) and two distinct buffers both work, as for the state; records at index >= n of a table of
+ * filter_out are left as they were; a stream with no frame in the call keeps its block (its first n records are copied).
+ * The kernel is the `true` instantiation of the tracker's kernel template (the `false` one is the two ops above, unchanged): the
+ * association passes are the same code.  A thread keeps its track's mean and velocity (x, v) in registers and the 12 covariance
+ * numbers in a column of LDS of its own, 96 KB beside the association's 58 KB -- 154 of gfx950's 160 KB per workgroup; 40 more
+ * registers do not fit beside the track record under the 128 a lane of a 1024-thread workgroup has.  At the compaction a thread
+ * sends its record a component at a time through the box buffer: it reads its column in front of the barrier and writes its column
+ * behind it.  No atomics, nothing spins, every barrier is reached by all threads on values they read alike.
+ * Refused before any launch, naming the value: everything mscnn_tracks_update_streams_fwd refuses (a null stream_of only with more
+ * than one stream), a null call, a size that is not sizeof(mscnn_tracks_kalman_call), a null track, a null filter, filter_in or
+ * filter_out (each by its name), a motion other than MSCNN_TRACK_MOTION_NONE, a std that is NaN, not finite or <= 0, filter_in /
+ * filter_out not 16-byte aligned, filter_in and filter_out overlapping without being equal, a filter buffer overlapping a state
+ * buffer.
+ * The check: tests/track_kalman_witness.py restates the steps in float64 numpy (bit for bit) and, independently, the textbook
+ * eight-state form (F, H, Q, R, K = P H^T S^-1), which agrees with the decoupled form to rounding with cross terms exactly 0.  The
+ * accuracy of the tracker was NOT evaluated: there are no labels here. */
+#ifndef MSCNN_TRACK_KALMAN_PARAMS_DEFINED
+#define MSCNN_TRACK_KALMAN_PARAMS_DEFINED
+typedef struct { double std_position, std_velocity;                              /* x h: 1/20, 1/160 */
+                 double std_aspect, std_aspect_velocity, std_aspect_measure;     /* 1e-2, 1e-5, 1e-1 */
+                 int freeze_lost_height; /* 1 */ } mscnn_track_kalman_params;
+#endif
+typedef struct { double x[4], v[4], p[4], q[4], r[4]; } mscnn_track_kalman_record;      /* 160 bytes */
+typedef struct { size_t size;      /* sizeof(mscnn_tracks_kalman_call), refused otherwise */
+                 const mscnn_track_params* track;  const mscnn_track_kalman_params* filter;
+                 int num_frames, num_slots, num_streams;  const int* stream_of;      /* HOST; NULL with one stream */
+                 const void* pack_dev;  int cap;
+                 const void* state_in;  void* state_out;
+                 const void* filter_in; void* filter_out;      /* num_streams * num_slots * max_tracks records, 16-byte aligned */
+                 int max_tracks;  int* track_ids_dev;  void* stream; } mscnn_tracks_kalman_call;
+MSCNN_API size_t mscnn_tracks_kalman_state_bytes(int num_slots, int max_tracks);      /* 0: refused */
+MSCNN_API int mscnn_tracks_update_kalman_fwd(const mscnn_tracks_kalman_call* call);
 
 /* The render stage: the `show` block at the end of the reference's demo scripts (examples/kitti_car/run_mscnn_detection.m,
  * examples/caltech/run_mscnn_detection.m, examples/widerface/run_cascademscnn.m:136-150: every box with score >= show_thr drawn on

@@ -487,7 +487,8 @@ MSCNN_NET_API int mscnn_net_set_seq_nms(mscnn_net* net, double link_thr, double 
 MSCNN_NET_API int mscnn_net_get_seq_nms(const mscnn_net* net, double* link_thr, double* score_thr, int* top_k, int* rescore, int* max_out);
 MSCNN_NET_API int mscnn_net_detect_merge_sequences(mscnn_net* net, int* seq_host, int cap, const int* seg_dets);
 /* Track ids across the frames of a stream (mscnn_hip.h: mscnn_tracks_update_fwd; BYTE association, Zhang et al., 2022, with a
- * constant-velocity prediction in place of the Kalman filter and a greedy walk under a total order in place of the Hungarian solver).
+ * constant-velocity prediction -- the paper's Kalman filter is there on request: mscnn_net_set_tracker_kalman below -- and a greedy
+ * walk under a total order in place of the Hungarian solver).
  * While the tracker is on, mscnn_net_detect_multi, mscnn_net_detect_cascade_multi and mscnn_net_detect_merge_end enqueue the update
  * behind their pack -- on _end behind whichever merge op is on, and behind the vote --, on the same stream, in front of the one
  * synchronisation those calls already have; the ids go behind the pack in the same pinned block, where WBF's member counts and (in
@@ -544,6 +545,32 @@ MSCNN_NET_API int mscnn_net_set_tracker_streams(mscnn_net* net, int num_streams)
 MSCNN_NET_API int mscnn_net_set_frame_streams(mscnn_net* net, const int* stream_of /* HOST, [count]; NULL: clear */, int count);
 MSCNN_NET_API int mscnn_net_get_tracker_streams(const mscnn_net* net, int* num_streams, int* stream_of, int cap, int* count);
 MSCNN_NET_API int mscnn_net_tracker_reset_stream(mscnn_net* net, int s);
+/* A Kalman filter per track (mscnn_hip.h: mscnn_tracks_update_kalman_fwd, whose comment holds the steps): a second setting beside
+ * the tracker's, so that mscnn_track_params and mscnn_net_set_tracker stay what they are.
+ * mscnn_net_set_tracker_kalman: params NULL = off.  Otherwise it needs the tracker on with MSCNN_TRACK_MOTION_NONE (the filter is the
+ * motion) and is refused otherwise, naming the motion; so is a std that is NaN, not finite or <= 0, naming it.  On, and off while
+ * it was on, give a FRESH table and leave K unfixed, exactly as mscnn_net_set_tracker_streams does, and keep the number of streams
+ * and the frame mapping; off while it is off changes nothing (the tracks live on).  mscnn_net_set_tracker turns the filter off, as it
+ * puts the streams back to 1.
+ * While it is on, every tracked call (mscnn_net_detect_multi, _detect_cascade_multi, _detect_merge_end) runs
+ * mscnn_tracks_update_kalman_fwd in the place of mscnn_tracks_update_fwd / _streams_fwd.  There are two filter tables beside the two
+ * track tables, swapped with them and only after success (the two-table rule).  mscnn_net_tracker_reset and _reset_stream work as
+ * before: a filter table needs no reset, a record is made at its track's birth.  Everything else about those calls is unchanged: the
+ * detections they return, where the ids land, mscnn_net_render and mscnn_net_crops behind them.
+ * mscnn_net_get_tracker_kalman: on (0 / 1) and the values (the defaults while it has never been set).
+ * mscnn_net_tracker_kalman_state: a host copy of the committed filter table, num_streams * K * max_tracks records of
+ * mscnn_track_kalman_record beside the records of mscnn_net_tracker_state; refused, naming the reason, while the filter is off or K
+ * is not fixed, and for a buffer that is too small.  set / get work on a net built with device -1.
+ * The check is tests/track_kalman_witness.py; the accuracy was not evaluated (no labels here). */
+#ifndef MSCNN_TRACK_KALMAN_PARAMS_DEFINED      /* include/mscnn_hip.h's struct, repeated here so that this header stands alone */
+#define MSCNN_TRACK_KALMAN_PARAMS_DEFINED
+typedef struct { double std_position, std_velocity;                              /* x h: 1/20, 1/160 */
+                 double std_aspect, std_aspect_velocity, std_aspect_measure;     /* 1e-2, 1e-5, 1e-1 */
+                 int freeze_lost_height; /* 1 */ } mscnn_track_kalman_params;
+#endif
+MSCNN_NET_API int mscnn_net_set_tracker_kalman(mscnn_net* net, const mscnn_track_kalman_params* params /* NULL: off */);
+MSCNN_NET_API int mscnn_net_get_tracker_kalman(const mscnn_net* net, int* on, mscnn_track_kalman_params* params);
+MSCNN_NET_API int mscnn_net_tracker_kalman_state(mscnn_net* net, void* filter_host, size_t bytes);
 /* Draw the detections into the frames (mscnn_hip.h: mscnn_render_detections_u8, whose comment is the contract: footprints, paint
  * order, blend, labels, pixelation): the `show` block at the end of the reference's demo scripts, on the device.  It renders the pack
  * of the LAST mscnn_net_detect_multi, mscnn_net_detect_cascade_multi or mscnn_net_detect_merge_end on this net -- the Net still holds

@@ -1,8 +1,9 @@
 // A streaming multi-object tracker behind the final stage (mscnn_tracks_update_fwd): BYTE's two association passes (Zhang et al.,
 // "ByteTrack: Multi-Object Tracking by Associating Every Detection Box", 2022) over the multi pack's rows, a small table of tracks per
 // slot kept in device memory from call to call, a persistent track id for every detection row.  Two deliberate departures from the
-// paper: the motion is a constant-velocity prediction of the box centre in place of the Kalman filter, and the matching is greedy by
-// descending overlap under a total order (larger r, then the lower track, then the lower detection) in place of the Hungarian solver.
+// paper: the motion is a constant-velocity prediction of the box centre (the paper's Kalman filter is there on request: the `true`
+// instantiation of the kernel, mscnn_tracks_update_kalman_fwd), and the matching is greedy by descending overlap under a total order
+// (larger r, then the lower track, then the lower detection) in place of the Hungarian solver.
 // The frames of a call may belong to several streams (cameras): mscnn_tracks_update_streams_fwd gives every (stream, slot) a table of
 // its own and one workgroup, side by side in one launch; the map frame -> stream travels by value in the kernel arguments.
 // ONE workgroup of kTrackThreads owns a slot for the whole call and loops over the call's frames; thread i is track i AND detection i
@@ -38,6 +39,57 @@ struct TrackArgs {
   int num_streams;
   unsigned short stream_of[kTrackStreams];      // frame t's stream; read only when num_streams > 1 (then num_frames <= kTrackStreams)
 };
+// the arguments of the Kalman instantiation (mscnn_tracks_update_kalman_fwd): the same, then the filter's setting and its two tables
+// The products that do not depend on a track are made once, on the host, in the same double arithmetic (one rounding each): in
+// the kernel they would be hoisted out of the frame loop into vector registers the kernel does not have.
+struct TrackKalmanArgs : TrackArgs {
+  double sp, sv;              // std_position, std_velocity
+  double sp2, sv10;           // 2 * std_position, 10 * std_velocity (step 8')
+  double a2, b2, m2;          // std_aspect, std_aspect_velocity, std_aspect_measure, each times itself
+  int freeze_lost_height;
+  const mscnn_track_kalman_record* filter_in;
+  mscnn_track_kalman_record* filter_out;
+};
+using KalmanRecord = mscnn_track_kalman_record;
+
+// Where a thread's filter record lives.  The track record, the detection and the association's scans fill the 128 VGPRs a lane of a
+// 1024-thread workgroup may have; 40 more for the filter record spill.  So the mean and its velocity (x, v: 16 VGPRs) stay in
+// registers and the 12 covariance numbers (p, q, r per component) lie in LDS between their uses, a column per thread: 96 KB beside the
+// 58 KB of the association, 154 of gfx950's 160 KB per workgroup -- in the Kalman instantiation only.  A column is touched by its own
+// thread only, except at the compaction, which reads, waits at a barrier, and writes.
+constexpr int kKalmanCov = 12;      // p[4], q[4], r[4]
+template <bool KF>
+__device__ __forceinline__ double* kalman_cov() {
+  if constexpr (KF) {
+    __shared__ double cov[kKalmanCov * kTrackThreads];
+    return cov + threadIdx.x;
+  } else {
+    return nullptr;
+  }
+}
+// number j of p / q / r (0 / 1 / 2) of component c in a thread's column
+__device__ __forceinline__ int kalman_at(int j, int c) { return (4 * j + c) * kTrackThreads; }
+
+// step 3': one component of the prediction (sp2 = sigp * sigp, sv2 = sigv * sigv)
+__device__ __forceinline__ void kalman_predict1(double& x, double v, double* cov, int c, double sp2, double sv2) {
+  const double p = cov[kalman_at(0, c)], q = cov[kalman_at(1, c)], r = cov[kalman_at(2, c)];
+  x = x + v;
+  const double t0 = p + q, t1 = q + r, t2 = t0 + t1;
+  cov[kalman_at(0, c)] = t2 + sp2; cov[kalman_at(1, c)] = t1; cov[kalman_at(2, c)] = r + sv2;
+}
+// step 6': one component of the update with the measurement z (sm2 = sigm * sigm)
+__device__ __forceinline__ void kalman_update1(double& x, double& v, double* cov, int c, double z, double sm2) {
+  const double p = cov[kalman_at(0, c)], q = cov[kalman_at(1, c)], r = cov[kalman_at(2, c)];
+  const double s = p + sm2, kx = p / s, kv = q / s, y = z - x;
+  const double ax = kx * y, av = kv * y, dr = kv * q, dp = kx * p, dq = kx * q;
+  x = x + ax; v = v + av;
+  cov[kalman_at(2, c)] = r - dr; cov[kalman_at(0, c)] = p - dp; cov[kalman_at(1, c)] = q - dq;
+}
+// the box of a filter's mean: (cx, cy, a, h) -> {x, y, w, h}
+__device__ __forceinline__ void kalman_box(const double* x, double* box) {
+  const double w = x[2] * x[3], hw = w / 2, hh = x[3] / 2;
+  box[0] = x[0] - hw; box[1] = x[1] - hh; box[2] = w; box[3] = x[3];
+}
 
 // the places of the set flags among the workgroup's threads, and their number (every thread calls it; two barriers)
 __device__ __forceinline__ int track_rank(bool on, int* wsum, int* total_out) {
@@ -112,7 +164,11 @@ __device__ __forceinline__ void track_pass(bool tact, bool dact, const DetBox& t
   __syncthreads();      // (the arrays are free again)
 }
 
-__global__ __launch_bounds__(kTrackThreads) void det_track_kernel(TrackArgs a) {
+// KF false: the motions none / linear of mscnn_tracks_update_fwd / _streams_fwd, Args = TrackArgs.  KF true: steps 3', 6', 8', 9' of
+// mscnn_tracks_update_kalman_fwd, Args = TrackKalmanArgs; the association passes, the ids and the compaction of the track records are
+// the same statements.  A thread's filter record F is touched by its own thread only, except at the compaction.
+template <bool KF, class Args>
+__global__ __launch_bounds__(kTrackThreads) void det_track_kernel(Args a) {
   __shared__ DetBox buf[kTrackThreads];
   __shared__ double sbuf[kTrackThreads];
   __shared__ int best_d[kTrackThreads], dmatch_l[kTrackThreads], xa[kTrackThreads], xb[kTrackThreads];
@@ -134,6 +190,20 @@ __global__ __launch_bounds__(kTrackThreads) void det_track_kernel(TrackArgs a) {
   n = n < 0 ? 0 : (n > a.max_tracks ? a.max_tracks : n);      // (a table that was never reset: nothing past max_tracks is touched)
   mscnn_track_record R = {};
   if (tid < n) R = reinterpret_cast<const mscnn_track_record*>(a.state_in + a.slot_bytes * tab + a.records_at)[tid];
+  double fx[4] = {0.0, 0.0, 0.0, 0.0}, fv[4] = {0.0, 0.0, 0.0, 0.0};      // the filter's mean and velocity; its covariance: cov
+  double* const cov = kalman_cov<KF>();
+  const int frame_in = frame;
+  if constexpr (KF) {
+    R.vel[0] = 0.0; R.vel[1] = 0.0;      // (not kept in registers: see where the record is stored)
+    if (tid < n) {
+      const KalmanRecord* f = a.filter_in + tab * (size_t)a.max_tracks + (size_t)tid;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        fx[c] = f->x[c]; fv[c] = f->v[c];
+        cov[kalman_at(0, c)] = f->p[c]; cov[kalman_at(1, c)] = f->q[c]; cov[kalman_at(2, c)] = f->r[c];
+      }
+    }
+  }
 
   for (int t = 0; t < a.num_frames; ++t) {
     if (a.num_streams > 1 && (int)a.stream_of[t] != strm) continue;      // another stream's frame (arguments and blockIdx only: every thread alike)
@@ -159,7 +229,19 @@ __global__ __launch_bounds__(kTrackThreads) void det_track_kernel(TrackArgs a) {
       cls = sc >= a.p.high_thr ? 1 : (sc >= a.p.low_thr ? 2 : 0);      // (a NaN score is in neither set)
     }
     const bool have = tid < n;
-    if (linear && have) { R.box[0] += R.vel[0]; R.box[1] += R.vel[1]; }                       // step 3
+    if constexpr (KF) {                                                                       // step 3'
+      if (have) {
+        if (a.freeze_lost_height != 0 && R.misses > 0) fv[3] = 0.0;
+        const double h = fx[3], e = a.sp * h, g = a.sv * h, e2 = e * e, g2 = g * g;
+        kalman_predict1(fx[0], fv[0], cov, 0, e2, g2);
+        kalman_predict1(fx[1], fv[1], cov, 1, e2, g2);
+        kalman_predict1(fx[2], fv[2], cov, 2, a.a2, a.b2);
+        kalman_predict1(fx[3], fv[3], cov, 3, e2, g2);
+        kalman_box(fx, R.box);      // (vel = {v[0], v[1]}: made where the record is stored)
+      }
+    } else {
+      if (linear && have) { R.box[0] += R.vel[0]; R.box[1] += R.vel[1]; }                     // step 3
+    }
     const DetBox T = {R.box[0], R.box[1], R.box[2], R.box[3]};
     int tmatch = -1, dmatch = -1;
     track_pass(have, cls == 1, T, B, n, m, a.p.match_thr, buf, best_d, dmatch_l, tfree, dfree, &any, &tmatch, &dmatch);      // step 4
@@ -188,7 +270,17 @@ __global__ __launch_bounds__(kTrackThreads) void det_track_kernel(TrackArgs a) {
             R.vel[1] = R.vel[1] + gy;
           }
         }
-        R.box[0] = D.x; R.box[1] = D.y; R.box[2] = D.w; R.box[3] = D.h;
+        if constexpr (KF) {                                                                   // step 6'
+          const double hw = D.w / 2, zx = D.x + hw, hh = D.h / 2, zy = D.y + hh, za = D.w / D.h;
+          const double h = fx[3], e = a.sp * h, e2 = e * e;
+          kalman_update1(fx[0], fv[0], cov, 0, zx, e2);
+          kalman_update1(fx[1], fv[1], cov, 1, zy, e2);
+          kalman_update1(fx[2], fv[2], cov, 2, za, a.m2);
+          kalman_update1(fx[3], fv[3], cov, 3, D.h, e2);
+          kalman_box(fx, R.box);
+        } else {
+          R.box[0] = D.x; R.box[1] = D.y; R.box[2] = D.w; R.box[3] = D.h;
+        }
         R.obs[0] = D.x; R.obs[1] = D.y; R.obs[2] = D.w; R.obs[3] = D.h;
         R.score = sbuf[tid];
         R.hits += 1; R.misses = 0;
@@ -227,17 +319,37 @@ __global__ __launch_bounds__(kTrackThreads) void det_track_kernel(TrackArgs a) {
       mscnn_track_record N = {};
       if (tid < n2) { const DetBox D = buf[tid]; N.box[0] = D.x; N.box[1] = D.y; N.box[2] = D.w; N.box[3] = D.h; N.score = sbuf[tid]; N.id = xa[tid]; N.hits = xb[tid]; }
       __syncthreads();
-      if (alive) { buf[ps] = DetBox{R.obs[0], R.obs[1], R.obs[2], R.obs[3]}; sbuf[ps] = R.vel[0]; xa[ps] = R.misses; xb[ps] = R.confirmed; }
-      if (born_kept) { buf[pd] = B; sbuf[pd] = 0.0; xa[pd] = 0; xb[pd] = a.p.min_hits <= 1 ? 1 : 0; }
+      if (alive) { buf[ps] = DetBox{R.obs[0], R.obs[1], R.obs[2], R.obs[3]}; if constexpr (!KF) sbuf[ps] = R.vel[0]; xa[ps] = R.misses; xb[ps] = R.confirmed; }
+      if (born_kept) { buf[pd] = B; if constexpr (!KF) sbuf[pd] = 0.0; xa[pd] = 0; xb[pd] = a.p.min_hits <= 1 ? 1 : 0; }
       __syncthreads();
-      if (tid < n2) { const DetBox D = buf[tid]; N.obs[0] = D.x; N.obs[1] = D.y; N.obs[2] = D.w; N.obs[3] = D.h; N.vel[0] = sbuf[tid]; N.misses = xa[tid]; N.confirmed = xb[tid]; }
+      if (tid < n2) { const DetBox D = buf[tid]; N.obs[0] = D.x; N.obs[1] = D.y; N.obs[2] = D.w; N.obs[3] = D.h; if constexpr (!KF) N.vel[0] = sbuf[tid]; N.misses = xa[tid]; N.confirmed = xb[tid]; }
       __syncthreads();
-      if (alive) sbuf[ps] = R.vel[1];
-      if (born_kept) sbuf[pd] = 0.0;
-      __syncthreads();
-      if (tid < n2) N.vel[1] = sbuf[tid];
-      __syncthreads();
+      if constexpr (!KF) {      // (the filter's tracks: vel is the filter's v[0], v[1], which moves below)
+        if (alive) sbuf[ps] = R.vel[1];
+        if (born_kept) sbuf[pd] = 0.0;
+        __syncthreads();
+        if (tid < n2) N.vel[1] = sbuf[tid];
+        __syncthreads();
+      }
       R = N;
+      if constexpr (KF) {      // step 9': the filter records move with their tracks, a component (x, v, p, q | r) at a time through
+        // the box buffer: a thread reads its own column in front of the barrier and writes its own column behind it, so a column
+        // stays its thread's.  Step 8': a birth's record is made where it is sent.
+        const double hw = B.w / 2, hh = B.h / 2;
+        const double z[4] = {B.x + hw, B.y + hh, B.w / B.h, B.h};
+        const double e = a.sp2 * B.h, e2 = e * e, g = a.sv10 * B.h, g2 = g * g;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          if (alive) { buf[ps] = DetBox{fx[c], fv[c], cov[kalman_at(0, c)], cov[kalman_at(1, c)]}; sbuf[ps] = cov[kalman_at(2, c)]; }
+          if (born_kept) { buf[pd] = DetBox{z[c], 0.0, c == 2 ? a.a2 : e2, 0.0}; sbuf[pd] = c == 2 ? a.b2 : g2; }
+          __syncthreads();
+          if (tid < n2) {
+            const DetBox D = buf[tid];
+            fx[c] = D.x; fv[c] = D.y; cov[kalman_at(0, c)] = D.w; cov[kalman_at(1, c)] = D.h; cov[kalman_at(2, c)] = sbuf[tid];
+          }
+          __syncthreads();
+        }
+      }
       n = n2;
     }
     dropped += nborn - kept;
@@ -250,7 +362,27 @@ __global__ __launch_bounds__(kTrackThreads) void det_track_kernel(TrackArgs a) {
     h[MSCNN_TRACKS_N] = n; h[MSCNN_TRACKS_NEXT_ID] = next_id; h[MSCNN_TRACKS_FRAME] = frame; h[MSCNN_TRACKS_DROPPED] = dropped;
     h[MSCNN_TRACKS_SKIPPED] = skipped; h[5] = 0; h[6] = 0; h[7] = 0;
   }
+  if constexpr (KF) {      // vel = {v[0], v[1]} behind every step 3', 6' and 8'; a table that was not stepped keeps the vel it came with
+    if (tid < n) {
+      if (frame != frame_in) {
+        R.vel[0] = fv[0]; R.vel[1] = fv[1];
+      } else {
+        const mscnn_track_record* in = reinterpret_cast<const mscnn_track_record*>(a.state_in + a.slot_bytes * tab + a.records_at) + tid;
+        R.vel[0] = in->vel[0]; R.vel[1] = in->vel[1];      // (in place: this thread's own record, which it writes below)
+      }
+    }
+  }
   if (tid < n) reinterpret_cast<mscnn_track_record*>(so + a.records_at)[tid] = R;      // (records at index >= n stay as they were)
+  if constexpr (KF) {
+    if (tid < n) {      // (records at index >= n stay as they were)
+      KalmanRecord* f = a.filter_out + tab * (size_t)a.max_tracks + (size_t)tid;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        f->x[c] = fx[c]; f->v[c] = fv[c];
+        f->p[c] = cov[kalman_at(0, c)]; f->q[c] = cov[kalman_at(1, c)]; f->r[c] = cov[kalman_at(2, c)];
+      }
+    }
+  }
 }
 
 __global__ void det_track_reset_kernel(char* state, size_t slot_bytes, int first_slot, int num_slots) {
@@ -296,22 +428,28 @@ extern "C" int mscnn_tracks_state_reset_slots(void* state, int num_slots_total, 
   return MSCNN_OK;
 }
 
-// Both entry points: `op` names the one that was called in a refusal.  with_map false: one stream, no map (mscnn_tracks_update_fwd).
+// All entry points: `op` names the one that was called in a refusal.  with_map false: one stream, no map (mscnn_tracks_update_fwd).
+// kc: the call of mscnn_tracks_update_kalman_fwd (the Kalman instantiation, its filter tables and setting), null for the other two.
 static int tracks_update_any(const char* op, bool with_map, const mscnn_track_params* p, int num_frames, int num_slots, int num_streams, const int* stream_of,
                              const void* pack_dev, int cap, const void* state_in, void* state_out, int max_tracks, int* track_ids_dev,
-                             void* stream) {
+                             void* stream, const mscnn_tracks_kalman_call* kc = nullptr) {
   MSCNN_REQUIRE(p && pack_dev && state_in && state_out && track_ids_dev, "%s: null pointer", op);
+  if (kc) {
+    MSCNN_REQUIRE(kc->filter, "%s: null filter", op);
+    MSCNN_REQUIRE(kc->filter_in, "%s: null filter_in", op);
+    MSCNN_REQUIRE(kc->filter_out, "%s: null filter_out", op);
+  }
   const int T = num_frames, K = num_slots;
   MSCNN_REQUIRE(T >= 1, "%s: num_frames %d", op, T);
   MSCNN_REQUIRE(K >= 1, "%s: num_slots %d", op, K);
   MSCNN_REQUIRE(cap >= 1, "%s: cap %d", op, cap);
   const int N = num_streams;
   if (with_map) {
-    MSCNN_REQUIRE(stream_of, "%s: null stream_of", op);
+    MSCNN_REQUIRE(stream_of || (kc && N == 1), "%s: null stream_of", op);
     MSCNN_REQUIRE(N >= 1 && N <= kTrackStreams, "%s: num_streams %d is outside [1, %d]", op, N, kTrackStreams);
     MSCNN_REQUIRE(N == 1 || T <= kTrackStreams, "%s: num_frames %d is above %d with %d streams (the map rides in the kernel's arguments)", op, T,
                   kTrackStreams, N);
-    for (int t = 0; t < T; ++t)
+    for (int t = 0; stream_of && t < T; ++t)
       MSCNN_REQUIRE(stream_of[t] >= 0 && stream_of[t] < N, "%s: stream_of[%d] = %d is outside [0, %d)", op, t, stream_of[t], N);
     MSCNN_REQUIRE((long)N * (long)K <= 0x7fffffffL, "%s: %d streams x %d slots is past 2^31 - 1", op, N, K);
   }
@@ -325,9 +463,19 @@ static int tracks_update_any(const char* op, bool with_map, const mscnn_track_pa
   MSCNN_REQUIRE(p->match_thr_low >= 0 && p->match_thr_low < 1, "%s: match_thr_low %g is not inside [0, 1)", op, p->match_thr_low);
   MSCNN_REQUIRE(p->low_thr <= p->high_thr, "%s: low_thr %g is above high_thr %g", op, p->low_thr, p->high_thr);
   MSCNN_REQUIRE(p->new_thr >= p->high_thr, "%s: new_thr %g is below high_thr %g", op, p->new_thr, p->high_thr);
-  MSCNN_REQUIRE(p->vel_gain > 0 && p->vel_gain <= 1, "%s: vel_gain %g is not inside (0, 1]", op, p->vel_gain);
-  MSCNN_REQUIRE(p->motion == MSCNN_TRACK_MOTION_NONE || p->motion == MSCNN_TRACK_MOTION_LINEAR,
-                "%s: motion %d is neither %d (none) nor %d (linear)", op, p->motion, MSCNN_TRACK_MOTION_NONE, MSCNN_TRACK_MOTION_LINEAR);
+  if (kc) {      // (vel_gain is not read)
+    MSCNN_REQUIRE(p->motion == MSCNN_TRACK_MOTION_NONE, "%s: motion %d is not %d (none): the filter is the motion", op, p->motion,
+                  MSCNN_TRACK_MOTION_NONE);
+    const mscnn_track_kalman_params& f = *kc->filter;
+    const double stds[5] = {f.std_position, f.std_velocity, f.std_aspect, f.std_aspect_velocity, f.std_aspect_measure};
+    const char* const names[5] = {"std_position", "std_velocity", "std_aspect", "std_aspect_velocity", "std_aspect_measure"};
+    for (int i = 0; i < 5; ++i)      // (NaN included)
+      MSCNN_REQUIRE(stds[i] > 0 && stds[i] <= 1.7976931348623157e308, "%s: %s %g is not a finite number above 0", op, names[i], stds[i]);
+  } else {
+    MSCNN_REQUIRE(p->vel_gain > 0 && p->vel_gain <= 1, "%s: vel_gain %g is not inside (0, 1]", op, p->vel_gain);
+    MSCNN_REQUIRE(p->motion == MSCNN_TRACK_MOTION_NONE || p->motion == MSCNN_TRACK_MOTION_LINEAR,
+                  "%s: motion %d is neither %d (none) nor %d (linear)", op, p->motion, MSCNN_TRACK_MOTION_NONE, MSCNN_TRACK_MOTION_LINEAR);
+  }
   MSCNN_REQUIRE(p->max_age >= 0, "%s: max_age %d", op, p->max_age);
   MSCNN_REQUIRE(p->min_hits >= 1, "%s: min_hits %d", op, p->min_hits);
   MSCNN_REQUIRE(reinterpret_cast<uintptr_t>(pack_dev) % 16 == 0, "%s: pack_dev must be 16-byte aligned", op);
@@ -339,7 +487,22 @@ static int tracks_update_any(const char* op, bool with_map, const mscnn_track_pa
   const uintptr_t si = reinterpret_cast<uintptr_t>(state_in), so = reinterpret_cast<uintptr_t>(state_out);
   MSCNN_REQUIRE(si == so || si + bytes <= so || so + bytes <= si, "%s: state_in and state_out overlap (%zu bytes each) without being equal", op,
                 bytes);
-  TrackArgs a = {};
+  size_t fbytes = 0;
+  if (kc) {
+    const uintptr_t fi = reinterpret_cast<uintptr_t>(kc->filter_in), fo = reinterpret_cast<uintptr_t>(kc->filter_out);
+    MSCNN_REQUIRE(fi % 16 == 0, "%s: filter_in must be 16-byte aligned", op);
+    MSCNN_REQUIRE(fo % 16 == 0, "%s: filter_out must be 16-byte aligned", op);
+    fbytes = (size_t)N * (size_t)K * (size_t)max_tracks * sizeof(mscnn_track_kalman_record);
+    MSCNN_REQUIRE(fi == fo || fi + fbytes <= fo || fo + fbytes <= fi, "%s: filter_in and filter_out overlap (%zu bytes each) without being equal", op,
+                  fbytes);
+    const uintptr_t fs[2] = {fi, fo}, ss[2] = {si, so};
+    for (int i = 0; i < 2; ++i)
+      for (int j = 0; j < 2; ++j)
+        MSCNN_REQUIRE(fs[i] + fbytes <= ss[j] || ss[j] + bytes <= fs[i], "%s: %s (%zu bytes) overlaps %s (%zu bytes)", op,
+                      i ? "filter_out" : "filter_in", fbytes, j ? "state_out" : "state_in", bytes);
+  }
+  TrackKalmanArgs ka = {};
+  TrackArgs& a = ka;
   a.p = *p; a.num_frames = T; a.num_slots = K; a.cap = cap; a.max_tracks = max_tracks;
   a.pack = static_cast<const char*>(pack_dev); a.state_in = static_cast<const char*>(state_in); a.state_out = static_cast<char*>(state_out);
   a.ids = track_ids_dev;
@@ -348,7 +511,17 @@ static int tracks_update_any(const char* op, bool with_map, const mscnn_track_pa
   if (N > 1)
     for (int t = 0; t < T; ++t) a.stream_of[t] = (unsigned short)stream_of[t];      // (read here, before the call returns; T <= kTrackStreams)
   // the grid's y and z are bounded by 65535, x is not: the slots go to x
-  det_track_kernel<<<dim3((unsigned)K, (unsigned)N), kTrackThreads, 0, as_stream(stream)>>>(a);
+  if (kc) {
+    const mscnn_track_kalman_params& f = *kc->filter;
+    ka.sp = f.std_position; ka.sv = f.std_velocity; ka.sp2 = 2 * f.std_position; ka.sv10 = 10 * f.std_velocity;
+    ka.a2 = f.std_aspect * f.std_aspect; ka.b2 = f.std_aspect_velocity * f.std_aspect_velocity; ka.m2 = f.std_aspect_measure * f.std_aspect_measure;
+    ka.freeze_lost_height = f.freeze_lost_height;
+    ka.filter_in = static_cast<const mscnn_track_kalman_record*>(kc->filter_in);
+    ka.filter_out = static_cast<mscnn_track_kalman_record*>(kc->filter_out);
+    det_track_kernel<true, TrackKalmanArgs><<<dim3((unsigned)K, (unsigned)N), kTrackThreads, 0, as_stream(stream)>>>(ka);
+  } else {
+    det_track_kernel<false, TrackArgs><<<dim3((unsigned)K, (unsigned)N), kTrackThreads, 0, as_stream(stream)>>>(a);
+  }
   MSCNN_POST_LAUNCH();
   return MSCNN_OK;
 }
@@ -364,4 +537,17 @@ extern "C" int mscnn_tracks_update_streams_fwd(const mscnn_track_params* p, int 
                                                int* track_ids_dev, void* stream) {
   return tracks_update_any("tracks_update_streams", true, p, num_frames, num_slots, num_streams, stream_of, pack_dev, cap, state_in, state_out,
                            max_tracks, track_ids_dev, stream);
+}
+
+extern "C" size_t mscnn_tracks_kalman_state_bytes(int num_slots, int max_tracks) {
+  if (!track_shape_ok(num_slots, max_tracks)) return 0;
+  return (size_t)num_slots * (size_t)max_tracks * sizeof(mscnn_track_kalman_record);
+}
+
+extern "C" int mscnn_tracks_update_kalman_fwd(const mscnn_tracks_kalman_call* c) {
+  MSCNN_REQUIRE(c, "tracks_update_kalman: null call");
+  MSCNN_REQUIRE(c->size == sizeof(mscnn_tracks_kalman_call), "tracks_update_kalman: size %zu is not sizeof(mscnn_tracks_kalman_call) = %zu", c->size,
+                sizeof(mscnn_tracks_kalman_call));
+  return tracks_update_any("tracks_update_kalman", true, c->track, c->num_frames, c->num_slots, c->num_streams, c->stream_of, c->pack_dev, c->cap,
+                           c->state_in, c->state_out, c->max_tracks, c->track_ids_dev, c->stream, c);
 }

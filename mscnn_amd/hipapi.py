@@ -259,6 +259,9 @@ def lib():
         L.mscnn_tracks_state_reset_slots.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.mscnn_tracks_update_streams_fwd.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                                       C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.mscnn_tracks_kalman_state_bytes.restype = C.c_size_t
+        L.mscnn_tracks_kalman_state_bytes.argtypes = [C.c_int, C.c_int]
+        L.mscnn_tracks_update_kalman_fwd.argtypes = [C.c_void_p]
         L.mscnn_render_detections_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                                  C.c_void_p, C.c_void_p]
         L.mscnn_render_glyph_rows.argtypes = [C.c_int, C.c_void_p]
@@ -1490,6 +1493,63 @@ def tracks_state_reset_slots(state, num_slots_total, max_tracks, first_slot, cou
     stream of several starts again, the others keep their tracks).  Returns state."""
     _check(lib().mscnn_tracks_state_reset_slots(_dev(state), num_slots_total, max_tracks, first_slot, count, _stream()))
     return state
+
+
+# ---- the tracker with a Kalman filter per track (mscnn_hip.h: mscnn_tracks_update_kalman_fwd) ----
+class TrackKalmanParams(C.Structure):
+    """mscnn_track_kalman_params: every std finite and > 0; std_position / std_velocity are times the track's height."""
+    _fields_ = [("std_position", C.c_double), ("std_velocity", C.c_double), ("std_aspect", C.c_double), ("std_aspect_velocity", C.c_double),
+                ("std_aspect_measure", C.c_double), ("freeze_lost_height", C.c_int)]
+
+
+class TracksKalmanCall(C.Structure):
+    """mscnn_tracks_kalman_call: the one argument of mscnn_tracks_update_kalman_fwd."""
+    _fields_ = [("size", C.c_size_t), ("track", C.c_void_p), ("filter", C.c_void_p), ("num_frames", C.c_int), ("num_slots", C.c_int),
+                ("num_streams", C.c_int), ("stream_of", C.c_void_p), ("pack_dev", C.c_void_p), ("cap", C.c_int), ("state_in", C.c_void_p),
+                ("state_out", C.c_void_p), ("filter_in", C.c_void_p), ("filter_out", C.c_void_p), ("max_tracks", C.c_int),
+                ("track_ids_dev", C.c_void_p), ("stream", C.c_void_p)]
+
+
+TRACK_KALMAN_RECORD = np.dtype([("x", "<f8", 4), ("v", "<f8", 4), ("p", "<f8", 4), ("q", "<f8", 4), ("r", "<f8", 4)])
+assert TRACK_KALMAN_RECORD.itemsize == 160      # mscnn_track_kalman_record
+
+
+def track_kalman_params(std_position=1 / 20, std_velocity=1 / 160, std_aspect=1e-2, std_aspect_velocity=1e-5, std_aspect_measure=1e-1,
+                        freeze_lost_height=True):
+    """A TrackKalmanParams with the defaults of SORT / DeepSORT / ByteTrack."""
+    return TrackKalmanParams(float(std_position), float(std_velocity), float(std_aspect), float(std_aspect_velocity),
+                             float(std_aspect_measure), int(bool(freeze_lost_height)))
+
+
+def tracks_kalman_state_bytes(num_slots, max_tracks):
+    """mscnn_tracks_kalman_state_bytes: the bytes of a filter table beside a state of num_slots tables (0: refused)."""
+    return int(lib().mscnn_tracks_kalman_state_bytes(num_slots, max_tracks))
+
+
+def tracks_update_kalman(params, kparams, num_frames, num_slots, num_streams, stream_of, pack, cap, state_in, filter_in, max_tracks,
+                         state_out=None, filter_out=None, ids=None):
+    """mscnn_tracks_update_kalman_fwd: as tracks_update_streams with params.motion none and a Kalman filter per track (kparams), its
+    records in filter_in / filter_out (uint8 device tensors of tracks_kalman_state_bytes(num_streams * num_slots, max_tracks); None:
+    in place) beside the state's.  stream_of may be None with one stream.  Returns (state_out, filter_out, ids)."""
+    if state_out is None:
+        state_out = state_in
+    if filter_out is None:
+        filter_out = filter_in
+    if ids is None:
+        ids = torch.zeros(max(cap, 1), dtype=torch.int32, device=pack.device)
+    so = None
+    if stream_of is not None:
+        so = np.ascontiguousarray(stream_of, dtype=np.int32).reshape(-1)
+        if so.size != num_frames:
+            raise MscnnError(f"tracker: stream_of names {so.size} frames, the call has {num_frames}")
+    def at(t):
+        p = _dev(t)
+        return None if p is None else p.value
+    call = TracksKalmanCall(C.sizeof(TracksKalmanCall), C.addressof(params), C.addressof(kparams), num_frames, num_slots, num_streams,
+                            None if so is None else so.ctypes.data, at(pack), cap, at(state_in), at(state_out), at(filter_in),
+                            at(filter_out), max_tracks, at(ids), _stream().value)
+    _check(lib().mscnn_tracks_update_kalman_fwd(C.byref(call)))
+    return state_out, filter_out, ids
 
 
 # ---- the render stage (mscnn_hip.h: mscnn_render_detections_u8) ----

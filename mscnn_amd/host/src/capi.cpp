@@ -68,6 +68,11 @@ struct mscnn_net {
   std::vector<int> track_stream_of;
   std::vector<char> track_reset_pending;   // mscnn_net_tracker_reset_stream: streams to reset in front of the next tracked call's update
   std::vector<int> track_ids, track_seg_dets;
+  // mscnn_net_set_tracker_kalman: a Kalman filter per track (the tracker on with motion none); the tracked calls run
+  // mscnn_tracks_update_kalman_fwd, and a filter table stands beside each of the two track tables, swapped with them (track_cur).
+  bool kalman_on = false;
+  mscnn_track_kalman_params kalman = {1.0 / 20, 1.0 / 160, 1e-2, 1e-5, 1e-1, 1};
+  caffe::DeviceBuffer track_filter[2];
   // mscnn_net_render: what the last detect_multi / detect_cascade_multi / detect_merge_end left in det_host -- the pack of `frames` x
   // `slots` segments with `cap` rows and, when that call ran the tracker, its ids at ids_at (bytes: both).  Any other user of det_host
   // ends it (ensure_det_host).  The stage's own device buffers: the pack's copy, the staged host frames, the frames to hand back.
@@ -660,7 +665,7 @@ int mscnn_net_set_tracker(mscnn_net* n, const mscnn_track_params* p, int max_tra
   return guarded([&] {
     CHECK(n != nullptr);
     if (p == nullptr) {      // off: the state is dropped with the setting
-      n->track_on = false; n->track_K = 0; n->tracks_valid = false;
+      n->track_on = false; n->track_K = 0; n->tracks_valid = false; n->kalman_on = false;
       n->track_streams = 1; n->track_stream_of.clear(); n->track_reset_pending.clear();
       return;
     }
@@ -682,6 +687,7 @@ int mscnn_net_set_tracker(mscnn_net* n, const mscnn_track_params* p, int max_tra
     n->track = *p; n->track_max = max_tracks; n->track_on = true;
     n->track_K = 0; n->tracks_valid = false;      // a new setting is a new stream: the next call starts at id 1
     n->track_streams = 1; n->track_stream_of.clear(); n->track_reset_pending.clear();      // (and ONE stream: mscnn_net_set_tracker_streams)
+    n->kalman_on = false;      // (and no filter: mscnn_net_set_tracker_kalman)
   });
 }
 
@@ -696,6 +702,48 @@ int mscnn_net_set_tracker_streams(mscnn_net* n, int num_streams) {
     n->track_streams = num_streams;
     n->track_stream_of.clear(); n->track_reset_pending.clear();
     n->track_K = 0; n->tracks_valid = false;      // a fresh table, K unfixed (as mscnn_net_tracker_reset)
+  });
+}
+
+int mscnn_net_set_tracker_kalman(mscnn_net* n, const mscnn_track_kalman_params* p) {
+  return guarded([&] {
+    CHECK(n != nullptr);
+    if (p != nullptr) {
+      CHECK(n->track_on) << "set_tracker_kalman: the tracker is off (mscnn_net_set_tracker)";
+      CHECK(n->track.motion == MSCNN_TRACK_MOTION_NONE)
+          << "set_tracker_kalman: the tracker's motion " << n->track.motion << " is not " << MSCNN_TRACK_MOTION_NONE
+          << " (none): the filter is the motion, set the tracker with motion none first";
+      const double stds[5] = {p->std_position, p->std_velocity, p->std_aspect, p->std_aspect_velocity, p->std_aspect_measure};
+      const char* const names[5] = {"std_position", "std_velocity", "std_aspect", "std_aspect_velocity", "std_aspect_measure"};
+      for (int i = 0; i < 5; ++i)      // (NaN included)
+        CHECK(stds[i] > 0 && stds[i] <= 1.7976931348623157e308) << "set_tracker_kalman: " << names[i] << " " << stds[i] << " is not a finite number above 0";
+      n->kalman = *p;
+    }
+    if (p == nullptr && !n->kalman_on) return;      // (off while it is off: nothing changes, the tracks live on)
+    n->kalman_on = p != nullptr;
+    n->track_reset_pending.clear();
+    n->track_K = 0; n->tracks_valid = false;      // a fresh table, K unfixed (as mscnn_net_set_tracker_streams); streams and mapping stay
+  });
+}
+
+int mscnn_net_get_tracker_kalman(const mscnn_net* n, int* on, mscnn_track_kalman_params* p) {
+  return guarded([&] {
+    CHECK(n && on && p);
+    *on = n->kalman_on ? 1 : 0; *p = n->kalman;
+  });
+}
+
+int mscnn_net_tracker_kalman_state(mscnn_net* n, void* filter_host, size_t bytes) {
+  return guarded([&] {
+    CHECK(n != nullptr);
+    CHECK(n->track_on && n->kalman_on) << "tracker_kalman_state: the filter is off (mscnn_net_set_tracker_kalman)";
+    CHECK(n->track_K >= 1) << "tracker_kalman_state: no tracked call has succeeded since the tracker was set or reset: the number of slots is not fixed yet";
+    const size_t need = mscnn_tracks_kalman_state_bytes(n->track_streams * n->track_K, n->track_max);
+    CHECK(filter_host != nullptr && bytes >= need) << "tracker_kalman_state: a buffer of " << bytes << " bytes, " << n->track_streams * n->track_K
+                                                    << " slots x " << n->track_max << " tracks need " << need;
+    hipStream_t st = (hipStream_t)Caffe::stream();
+    HIP_CHECK(hipMemcpyAsync(filter_host, n->track_filter[n->track_cur].get(), need, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
   });
 }
 
@@ -810,13 +858,24 @@ static void track_enqueue(mscnn_net* n, const char* name, int T, int K, const vo
   CHECK_GT(bytes, 0u) << name << ": the tracker's table for " << N * K << " slots x " << n->track_max << " tracks";
   if (n->track_K == 0) {
     for (caffe::DeviceBuffer& b : n->track_state) b.Reserve(bytes);
+    if (n->kalman_on)      // (no reset: a filter record is made at its track's birth)
+      for (caffe::DeviceBuffer& b : n->track_filter) b.Reserve(mscnn_tracks_kalman_state_bytes(N * K, n->track_max));
     MSCNN_CHECK(mscnn_tracks_state_reset(n->track_state[n->track_cur].get(), N * K, n->track_max, st));
   } else {
     for (size_t s = 0; s < n->track_reset_pending.size(); ++s)      // mscnn_net_tracker_reset_stream, on the committed table
       if (n->track_reset_pending[s])
         MSCNN_CHECK(mscnn_tracks_state_reset_slots(n->track_state[n->track_cur].get(), N * K, n->track_max, (int)s * K, K, st));
   }
-  if (N == 1)
+  if (n->kalman_on) {
+    mscnn_tracks_kalman_call c = {};
+    c.size = sizeof(c); c.track = &n->track; c.filter = &n->kalman;
+    c.num_frames = T; c.num_slots = K; c.num_streams = N; c.stream_of = N > 1 ? n->track_stream_of.data() : nullptr;
+    c.pack_dev = pack; c.cap = pack_rows;
+    c.state_in = n->track_state[n->track_cur].get(); c.state_out = n->track_state[n->track_cur ^ 1].get();
+    c.filter_in = n->track_filter[n->track_cur].get(); c.filter_out = n->track_filter[n->track_cur ^ 1].get();
+    c.max_tracks = n->track_max; c.track_ids_dev = ids_dev; c.stream = st;
+    MSCNN_CHECK(mscnn_tracks_update_kalman_fwd(&c));
+  } else if (N == 1)
     MSCNN_CHECK(mscnn_tracks_update_fwd(&n->track, T, K, pack, pack_rows, n->track_state[n->track_cur].get(),
                                         n->track_state[n->track_cur ^ 1].get(), n->track_max, ids_dev, st));
   else

@@ -44,6 +44,15 @@ class TrackParams(C.Structure):
                 ("match_thr_low", C.c_double), ("vel_gain", C.c_double), ("motion", C.c_int), ("max_age", C.c_int), ("min_hits", C.c_int)]
 
 
+class TrackKalmanParams(C.Structure):
+    """mscnn_track_kalman_params (include/mscnn_net.h): the standard deviations of the per-track Kalman filter."""
+    _fields_ = [("std_position", C.c_double), ("std_velocity", C.c_double), ("std_aspect", C.c_double), ("std_aspect_velocity", C.c_double),
+                ("std_aspect_measure", C.c_double), ("freeze_lost_height", C.c_int)]
+
+
+TRACK_KALMAN_RECORD = np.dtype([("x", "<f8", 4), ("v", "<f8", 4), ("p", "<f8", 4), ("q", "<f8", 4), ("r", "<f8", 4)])      # mscnn_track_kalman_record
+
+
 class RenderParams(C.Structure):
     """mscnn_render_params (include/mscnn_net.h; 136 bytes): what the render stage draws."""
     _fields_ = [("show_thr", C.c_double), ("thickness", C.c_int), ("outline_alpha", C.c_int), ("fill_alpha", C.c_int), ("label", C.c_int),
@@ -198,6 +207,8 @@ def lib():
             "mscnn_net_detect_tracks": [vp, vp, ci, vp], "mscnn_net_tracker_state": [vp, vp, C.c_size_t],
             "mscnn_net_set_tracker_streams": [vp, ci], "mscnn_net_set_frame_streams": [vp, vp, ci],
             "mscnn_net_get_tracker_streams": [vp, vp, vp, ci, vp], "mscnn_net_tracker_reset_stream": [vp, ci],
+            "mscnn_net_set_tracker_kalman": [vp, vp], "mscnn_net_get_tracker_kalman": [vp, vp, vp],
+            "mscnn_net_tracker_kalman_state": [vp, vp, C.c_size_t],
             "mscnn_net_render": [vp, vp, ci, vp, vp, ci, vp, vp, ci],
             "mscnn_net_crop_window": [vp, vp, ci, ci, vp], "mscnn_net_crops": [vp, vp, ci, vp, vp, ci, vp, vp, ci, vp, vp, vp],
         }
@@ -794,6 +805,47 @@ class Net:
             return None
         return dict(high_thr=tp.high_thr, low_thr=tp.low_thr, new_thr=tp.new_thr, match_thr=tp.match_thr, match_thr_low=tp.match_thr_low,
                     motion={1: "none", 2: "linear"}[tp.motion], vel_gain=tp.vel_gain, max_age=tp.max_age, min_hits=tp.min_hits, max_tracks=mt)
+
+    def set_tracker_kalman(self, std_position=1 / 20, std_velocity=1 / 160, std_aspect=1e-2, std_aspect_velocity=1e-5,
+                           std_aspect_measure=1e-1, freeze_lost_height=True):
+        """mscnn_net_set_tracker_kalman: a constant-velocity Kalman filter per track on (cx, cy, w / h, h), as SORT, DeepSORT and
+        ByteTrack run it, as the tracker's motion.  It needs set_tracker(motion="none") first and is refused otherwise, naming the
+        motion.  std_position / std_velocity are times the track's height; freeze_lost_height: a track that missed a frame keeps its
+        height.  std_position None = off (nothing changes while it is already off).  On and off start a fresh table (ids from 1) and
+        keep streams and the frame mapping; set_tracker turns the filter off.  Use it where the detector's boxes jitter: it smooths
+        the velocity and predicts a change of size.  On a clean, fast approaching box motion="linear" follows better."""
+        if std_position is None:
+            _check(lib().mscnn_net_set_tracker_kalman(self._h, None))
+            return
+        kp = TrackKalmanParams(float(std_position), float(std_velocity), float(std_aspect), float(std_aspect_velocity),
+                               float(std_aspect_measure), int(bool(freeze_lost_height)))
+        _check(lib().mscnn_net_set_tracker_kalman(self._h, C.byref(kp)))
+
+    def get_tracker_kalman(self):
+        """mscnn_net_get_tracker_kalman: None = off, else dict(std_position, std_velocity, std_aspect, std_aspect_velocity,
+        std_aspect_measure, freeze_lost_height)."""
+        on, kp = C.c_int(), TrackKalmanParams()
+        _check(lib().mscnn_net_get_tracker_kalman(self._h, C.byref(on), C.byref(kp)))
+        if not on.value:
+            return None
+        return dict(std_position=kp.std_position, std_velocity=kp.std_velocity, std_aspect=kp.std_aspect,
+                    std_aspect_velocity=kp.std_aspect_velocity, std_aspect_measure=kp.std_aspect_measure,
+                    freeze_lost_height=bool(kp.freeze_lost_height))
+
+    def tracker_kalman_state(self, raw=False):
+        """mscnn_net_tracker_kalman_state: the committed filter table beside tracker_state()'s: per slot a numpy record array (x, v, p,
+        q, r: mean, velocity, and per component the variances and the covariance) of that slot's n tracks; with streams > 1 one such
+        list per stream.  raw: the table's bytes (uint8), streams * K * max_tracks records."""
+        _, _, mt, K = self._tracker()
+        N = self.get_tracker_streams()
+        buf = np.zeros(max(N * K, 1) * mt * TRACK_KALMAN_RECORD.itemsize, np.uint8)
+        _check(lib().mscnn_net_tracker_kalman_state(self._h, buf.ctypes.data_as(C.c_void_p), buf.size))
+        if raw:
+            return buf
+        ns = [s["n"] for tab in (self.tracker_state() if N > 1 else [self.tracker_state()]) for s in tab]
+        recs = buf.view(TRACK_KALMAN_RECORD).reshape(N * K, mt)
+        out = [recs[k, :ns[k]].copy() for k in range(N * K)]
+        return [out[s * K:(s + 1) * K] for s in range(N)] if N > 1 else out
 
     def tracker_reset(self, stream=None):
         """mscnn_net_tracker_reset: a new stream -- the next tracked call starts with an empty table and id 1, and fixes K again.

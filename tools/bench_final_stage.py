@@ -58,6 +58,9 @@ merge of every frame of the clip, its pack read on the host), the final stage + 
 behind it (the ids read on the host too), and the final stage + the numpy tracker of tests/track_witness.py on the host's copy of the
 pack -- the only route there was.  The table gives the detections, the tracks and the tracked detections, and every case says whether
 the op is below the host route by more than the two spreads; the rows are also written to --out (profiles/detect_track.txt).
+--track --kalman, on the same clips: the final stage alone, + the tracker with motion linear, + the tracker with a Kalman filter per
+track (mscnn_tracks_update_kalman_fwd), and the pack on the host + the numpy witness of tests/track_kalman_witness.py; the filter op
+is reported against the linear op of the same run, spreads included; the rows go to --out (profiles/detect_track_kalman.txt).
 --track --streams N takes the images of ONE forward as one frame from each of N cameras (N = 0: as many as the forward has images):
 (a) the final stage alone, (b) + the one-launch stream tracker (mscnn_tracks_update_streams_fwd), (c) + N single-stream
 mscnn_tracks_update_fwd calls on N state buffers and N packs -- the only device route there was --, (d) the pack on the host + the
@@ -917,6 +920,107 @@ def track_leg(a):
             fh.write("\n".join(lines) + "\n")
 
 
+def track_kalman_leg(a):
+    """--track --kalman: on the clips of --track, behind one add of a clip's T frames: the final stage alone, + the tracker with motion
+    linear (mscnn_tracks_update_fwd), + the tracker with a Kalman filter per track (mscnn_tracks_update_kalman_fwd, motion none, the
+    default stds), and the pack on the host + the numpy witness of tests/track_kalman_witness.py.  Every form starts on an idle device
+    and a freshly reset table and ends with the detections (and ids) on the host; the forms rotate within a step."""
+    import torch
+    from mscnn_amd import hipapi
+    sys.path.insert(1, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import track_kalman_witness as kw
+    import track_witness as tw
+    kws = dict(high_thr=0.5, low_thr=0.1, match_thr=0.3, match_thr_low=0.5, vel_gain=0.5, max_age=30, min_hits=1)
+    M = 256
+    p_none, cp_lin, cp_none = tw.params(motion="none", **kws), hipapi.track_params(motion="linear", **kws), hipapi.track_params(motion="none", **kws)
+    kp, ckp = kw.kparams(), hipapi.track_kalman_params()
+    names = ["final stage alone", "+ tracker, motion linear", "+ tracker, Kalman filter", "pack to host + numpy witness"]
+    lines = []
+
+    def say(line):
+        print(line, flush=True)
+        lines.append(line)
+
+    say(f"# a Kalman filter per track behind the final stage (high_thr {kws['high_thr']:g}, low_thr {kws['low_thr']:g}, match_thr {kws['match_thr']:g}, "
+        f"match_thr_low {kws['match_thr_low']:g}, max_tracks {M}; the filter's default stds) per clip, host wall ms from an idle device to the detections "
+        f"(and ids) on the host (median over {a.steps} steps after {a.warmup} warm-up; {a.rounds} rounds: median of the medians, spread = max - min), "
+        f"regime {a.regime}; dets = the detections of all frames; tracks = the filter's table after the clip; tracked = its detections with an id > 0")
+    say(f"# {'case':24s} {'T':>2s} {'dets':>5s} {'tracks':>6s} {'tracked':>7s} | " + " | ".join(f"{nm:>28s} {'spread':>6s}" for nm in names) +
+        " | linear ms | kalman ms")
+    for name in a.case or list(SEQ_CASES):
+        T, K, cap, cand = seq_clip_lists(a, hipapi, name)
+        S = T * K
+        L = hipapi.lib()
+        pack = torch.zeros(L.mscnn_detections_multi_pack_bytes(S, S * cap), dtype=torch.uint8, device="cuda")
+        ws = torch.empty(max(L.mscnn_detections_merge_workspace_bytes(S, cap), 1), dtype=torch.uint8, device="cuda")
+        state = hipapi.tracks_state_new(K, M)
+        filt = torch.zeros(hipapi.tracks_kalman_state_bytes(K, M), dtype=torch.uint8, device="cuda")
+        ids = torch.zeros(S * cap, dtype=torch.int32, device="cuda")
+
+        def ids_of(out):
+            h = ids.cpu().numpy()      # (synchronises: the ids are on the host)
+            return [h[s * cap:s * cap + len(d)] for s, (d, _, _) in enumerate(out)]
+
+        def alone():
+            return cand.merge(pack=pack, ws=ws), None, None
+
+        def linear():
+            out = cand.merge(pack=pack, ws=ws)
+            hipapi.tracks_update(cp_lin, T, K, pack, S * cap, state, M, None, ids)
+            return out, ids_of(out), None
+
+        def kalman():
+            out = cand.merge(pack=pack, ws=ws)
+            hipapi.tracks_update_kalman(cp_none, ckp, T, K, 1, None, pack, S * cap, state, filt, M, None, None, ids)
+            return out, ids_of(out), None
+
+        def on_host():
+            out = cand.merge(pack=pack, ws=ws)
+            slots = [tw.new_slot() for _ in range(K)]
+            got = kw.run(slots, [[out[t * K + k][0] for k in range(K)] for t in range(T)], p_none, kp, M)
+            return out, [got[s // K][s % K] for s in range(S)], slots
+
+        forms = [alone, linear, kalman, on_host]
+        F = len(forms)
+        med = [[] for _ in range(F)]
+        for rnd in range(a.rounds):
+            t = [[] for _ in range(F)]
+            for step in range(a.warmup + a.steps):
+                res = [None] * F
+                for k in range(F):
+                    f = (k + step) % F
+                    hipapi._check(L.mscnn_tracks_state_reset(hipapi._dev(state), K, M, hipapi._stream()))      # (untimed: every clip starts a stream)
+                    torch.cuda.synchronize()      # (untimed: every form starts on an idle device)
+                    t0 = time.perf_counter()
+                    res[f] = forms[f]()
+                    dt = time.perf_counter() - t0
+                    if step >= a.warmup:
+                        t[f].append(dt)
+                assert all(np.array_equal(x, y) for x, y in zip(res[2][1], res[3][1])), (name, step)      # the filter op against the witness, bit for bit
+            for f in range(F):
+                med[f].append(1e3 * float(np.median(t[f])))
+        dets = sum(len(d) for d, _, _ in res[0][0])
+        tracks = sum(sl["n"] for sl in res[3][2])
+        tracked = sum(int(np.count_nonzero(i)) for i in res[2][1])
+        m = [float(np.median(v)) for v in med]
+        sp = [max(v) - min(v) for v in med]
+        lin, kal = m[1] - m[0], m[2] - m[0]
+        say(f"  {name:24s} {T:2d} {dets:5d} {tracks:6d} {tracked:7d} | " + " | ".join(f"{m[f]:28.3f} {sp[f]:6.3f}" for f in range(F)) +
+            f" | {lin:9.3f} | {kal:9.3f}")
+        say(f"# {name}: the filter op costs {kal:.3f} ms per clip of {T} frames on top of the final stage, the linear op {lin:.3f} ms: {kal / lin:.2f}x "
+            f"(spreads {sp[2]:.3f} and {sp[1]:.3f} ms); + Kalman filter / + numpy witness = {m[2] / m[3]:.3f}")
+    say("# python tools/bench_final_stage.py --track --kalman" + f" --steps {a.steps} --warmup {a.warmup} --rounds {a.rounds}: MI355X (gfx950), one GPU, seeded "
+        "weights; the clips, the add call and the resets as in profiles/detect_track.txt.  Both tracker columns are differences of two host wall times and "
+        "hold a second synchronisation and the copy of the id buffer.  Every step asserts that the filter op's ids equal the witness's bit for bit.")
+    say("# NOT measured: the kernels alone (device events or a profiler), one frame per call, more than one class, several streams, tables near "
+        "max_tracks = 1024 (the filter kernel's 154 KB of LDS allow one workgroup per CU), the Net calls and the drivers end to end, real video, "
+        "accuracy (no labels).")
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+
 STREAM_CASES = {   # name: (a SEQ_CASES entry: model, images of the one forward = cameras, classes, original image size, net input size)
     "caltech-7s480-b8": ("caltech/mscnn-7s-480", 8, [2], (480, 640), (480, 640)),
     "kitti_car-7s576-b4": ("kitti_car/mscnn-7s-576", 4, [2], (375, 1242), (576, 1920)),
@@ -1120,6 +1224,9 @@ ap.add_argument("--seq", action="store_true", help="with --merge: per clip of 8 
                 "and every candidate list to the host + a vectorised numpy Seq-NMS; us per iteration; the rows also go to --out")
 ap.add_argument("--track", action="store_true", help="on the clips of --merge --seq: the final stage alone, the final stage + the tracker op, and "
                 "the pack on the host + the numpy tracker of tests/track_witness.py; the rows also go to --out")
+ap.add_argument("--kalman", action="store_true", help="with --track: the final stage alone, + the tracker with motion linear, + the tracker with a "
+                "Kalman filter per track (mscnn_tracks_update_kalman_fwd), the pack on the host + tests/track_kalman_witness.py; the rows also go "
+                "to --out (profiles/detect_track_kalman.txt)")
 ap.add_argument("--streams", type=int, default=None, metavar="N", help="with --track: the images of one forward as one frame from each of N "
                 "cameras (0: as many as images): the final stage alone, + the one-launch stream tracker, + N single-stream calls, the pack on "
                 "the host + the numpy witness per stream; the rows also go to --out")
@@ -1144,7 +1251,7 @@ ap.add_argument("--ovr-dnm", default="union", choices=("union", "min"), help="bb
 a = ap.parse_args()
 if a.out is None:
     a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                         "detect_track_streams.txt" if a.track and a.streams is not None else "detect_track.txt" if a.track else "detect_merge_seq.txt" if a.seq else "detect_merge_wbf.txt")
+                         "detect_track_streams.txt" if a.track and a.streams is not None else "detect_track_kalman.txt" if a.track and a.kalman else "detect_track.txt" if a.track else "detect_merge_seq.txt" if a.seq else "detect_merge_wbf.txt")
 if a.parent_lib:
     ab_leg(a, sys.argv[1:])
     sys.exit(0)
@@ -1152,6 +1259,11 @@ if a.lib:
     use_lib(a.lib)
 if a.streams is not None and not (a.track and 0 <= a.streams <= 256):
     ap.error(f"--streams {a.streams} belongs to --track and lies inside [0, 256]")
+if a.kalman and not (a.track and a.streams is None):
+    ap.error("--kalman belongs to --track (without --streams)")
+if a.track and a.kalman:
+    track_kalman_leg(a)
+    sys.exit(0)
 if a.track and a.streams is not None:
     track_streams_leg(a)
     sys.exit(0)

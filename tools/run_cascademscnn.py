@@ -54,7 +54,9 @@ list_of naming its frames' places in the clip, the views of --flip / --scales / 
 and --vote serve it; not together with --soft-nms, --matrix-nms or --wbf.  As tools/run_mscnn_detection.py; the result files keep their
 format, --tubelets-out adds DIR/<comp_id>_<class>_<output>.txt with rows [image_index sequence x y w h score]; no pin on the reference,
 accuracy not evaluated.
---track [--track-high T] [--track-low T] [--track-match THR] [--track-motion none|linear] [--track-max-age N] [--track-min-hits N]
+--track [--track-high T] [--track-low T] [--track-match THR] [--track-motion none|linear|kalman] [--track-max-age N] [--track-min-hits N]
+[--track-kalman-pos S] [--track-kalman-vel S] [--track-kalman-keep-height 0|1] (with --track-motion kalman: a Kalman filter per track on
+centre, aspect and height, Net.set_tracker_kalman; for jittering boxes, not for clean fast approaching ones, where linear overlaps better)
 [--tracks-out DIR]: a persistent track id for every detection across the frames of the run, taken as consecutive frames of one stream
 (Net.set_tracker; BYTE's two association passes on the device behind every detect_cascade_multi and detect_merge_end, a table of
 tracks per (output, class)); alone, with --batch, with --orig-size (the boxes are original-image

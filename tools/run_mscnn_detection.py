@@ -20,7 +20,8 @@ examples/kitti_result/writeDetForEval.m.
          [--matrix-nms linear|gaussian[:SIGMA]]              # Matrix NMS in its place instead (Net.set_matrix_nms); --soft-thr / --max-dets serve it
          [--wbf [THR]] [--wbf-skip T] [--wbf-conf avg|max] [--wbf-expected N]      # weighted boxes fusion in its place instead (Net.set_wbf)
          [--seq-nms [avg|max]] [--clip T] [--seq-link THR] [--seq-top-k N] [--tubelets-out DIR]      # Seq-NMS over clips of T frames (Net.set_seq_nms)
-         [--track] [--track-high T] [--track-low T] [--track-match THR] [--track-motion none|linear] [--track-max-age N] [--track-min-hits N]
+         [--track] [--track-high T] [--track-low T] [--track-match THR] [--track-motion none|linear|kalman] [--track-max-age N] [--track-min-hits N]
+         [--track-kalman-pos S] [--track-kalman-vel S] [--track-kalman-keep-height 0|1]      # with --track-motion kalman (Net.set_tracker_kalman)
          [--tracks-out DIR]                                  # track ids across the frames of the run (Net.set_tracker)
          [--track --streams N --batch B]                     # the frames are N multiplexed cameras: a table of tracks per camera
          [--render-out DIR] [--show-thr T] [--render-label none|score|id|both] [--render-color slot|id] [--pixelate N]
@@ -104,9 +105,14 @@ reference, whose scripts run one forward per image and look at no other frame; a
 stream in file order (Net.set_tracker, once per run): behind every final stage a table of tracks per class is stepped on the device
 -- BYTE's two passes (Zhang et al., 2022): the detections with a score >= --track-high T (default 0.5) are associated first, IoU
 above --track-match THR (default 0.3), then those >= --track-low T (default 0.1) with the tracks still unmatched; a constant-velocity
-prediction of the centre (--track-motion linear, the default; none: the box stays) in place of the paper's Kalman filter, a greedy
-walk by descending IoU in place of its Hungarian solver.  An unmatched detection over --track-high starts a track, a track lives
-through --track-max-age N missed frames (default 30) and shows its id from its --track-min-hits N-th hit on (default 1).  Alone the
+prediction of the centre (--track-motion linear, the default; none: the box stays) or, on request, the paper's Kalman filter
+(--track-motion kalman: Net.set_tracker with motion none, then Net.set_tracker_kalman); a greedy walk by descending IoU in place of
+its Hungarian solver.  The filter keeps (centre, aspect, height) and their velocities per track, with --track-kalman-pos S (default
+0.05) and --track-kalman-vel S (default 0.00625) times the track's height as the standard deviations of position and velocity, and
+--track-kalman-keep-height 1 (the default) freezing a lost track's height: use it where the detector's boxes jitter -- it smooths
+the velocity and follows a change of size -- and not on clean, fast approaching boxes, where linear overlaps better.  An unmatched
+detection over --track-high starts a track, a track lives through --track-max-age N missed frames (default 30) and shows its id
+from its --track-min-hits N-th hit on (default 1).  Alone the
 frames run in groups of one through Net.detect_multi; with --batch a group is B consecutive frames; with --scales / --flip / --tiles /
 --vote / --soft-nms / --matrix-nms the tracker runs behind the frame's merge, with --seq-nms behind the clip's (the ids live on over
 the clip boundary).  Refused together with --wbf, --rois-in and --proposals-only.  The result files are unchanged; --tracks-out DIR
@@ -260,8 +266,15 @@ def add_merge_flags(ap):
                     "offered to the tracks the first pass left unmatched (default 0.1)")
     ap.add_argument("--track-match", type=float, default=0.3, metavar="THR", help="with --track: a detection matches a track when their IoU is above "
                     "THR (default 0.3)")
-    ap.add_argument("--track-motion", choices=["none", "linear"], default="linear", help="with --track: a track's box stays where it was seen "
-                    "(none) or moves on with its smoothed centre velocity (linear, the default)")
+    ap.add_argument("--track-motion", choices=["none", "linear", "kalman"], default="linear", help="with --track: a track's box stays where it was "
+                    "seen (none), moves on with its smoothed centre velocity (linear, the default), or follows a Kalman filter on centre, "
+                    "aspect and height (kalman: Net.set_tracker_kalman; for jittering boxes, not for clean fast approaching ones)")
+    ap.add_argument("--track-kalman-pos", type=float, default=1 / 20, metavar="S", help="with --track-motion kalman: the standard deviation of a "
+                    "position, times the track's height (default 0.05)")
+    ap.add_argument("--track-kalman-vel", type=float, default=1 / 160, metavar="S", help="with --track-motion kalman: the standard deviation of a "
+                    "velocity, times the track's height (default 0.00625)")
+    ap.add_argument("--track-kalman-keep-height", type=int, choices=[0, 1], default=1, metavar="0|1", help="with --track-motion kalman: a track that "
+                    "missed a frame keeps its height (1, the default) or goes on changing it (0)")
     ap.add_argument("--track-max-age", type=int, default=30, metavar="N", help="with --track: a track lives through N missed frames (default 30)")
     ap.add_argument("--track-min-hits", type=int, default=1, metavar="N", help="with --track: a track shows its id from its N-th hit on (default 1)")
     ap.add_argument("--streams", type=int, default=1, metavar="N", help="with --track: the frames are N multiplexed cameras, frame i of the "
@@ -398,8 +411,12 @@ def crop_frames(net, a, frames, paths, first):
 def apply_track_setting(net, a):
     """The sticky tracker setting of the run, once, before its first frame."""
     if track_on(a):
-        net.set_tracker(high_thr=a.track_high, low_thr=a.track_low, match_thr=a.track_match, motion=a.track_motion, max_age=a.track_max_age,
-                        min_hits=a.track_min_hits, streams=a.streams)
+        kalman = a.track_motion == "kalman"
+        net.set_tracker(high_thr=a.track_high, low_thr=a.track_low, match_thr=a.track_match, motion="none" if kalman else a.track_motion,
+                        max_age=a.track_max_age, min_hits=a.track_min_hits, streams=a.streams)
+        if kalman:      # (keeps the streams)
+            net.set_tracker_kalman(std_position=a.track_kalman_pos, std_velocity=a.track_kalman_vel,
+                                   freeze_lost_height=bool(a.track_kalman_keep_height))
 
 
 def set_group_streams(net, a, first, count):
@@ -505,13 +522,20 @@ def check_merge_flags(ap, a):
             ap.error(f"--track-max-age {a.track_max_age} must be >= 0, --track-min-hits {a.track_min_hits} >= 1")
         if not 1 <= a.streams <= 256:
             ap.error(f"--streams {a.streams}: 1 .. 256 streams")
+        if a.track_motion == "kalman":
+            if not (0.0 < a.track_kalman_pos < float("inf") and 0.0 < a.track_kalman_vel < float("inf")):      # (a NaN fails)
+                ap.error(f"--track-kalman-pos {a.track_kalman_pos:g} and --track-kalman-vel {a.track_kalman_vel:g} must be finite and above 0")
+        elif a.track_kalman_pos != 1 / 20 or a.track_kalman_vel != 1 / 160 or a.track_kalman_keep_height != 1:
+            ap.error("--track-kalman-pos / --track-kalman-vel / --track-kalman-keep-height belong to --track-motion kalman")
         if a.streams > 1 and seq_on(a):
             ap.error(f"--streams {a.streams} and --seq-nms exclude each other: a clip links every frame to the one before it, so it is one stream")
     elif a.streams != 1:
         ap.error(f"--streams {a.streams} belongs to --track")
     elif (a.track_high != 0.5 or a.track_low != 0.1 or a.track_match != 0.3 or a.track_motion != "linear" or a.track_max_age != 30
-          or a.track_min_hits != 1 or a.tracks_out is not None):
-        ap.error("--track-high / --track-low / --track-match / --track-motion / --track-max-age / --track-min-hits / --tracks-out belong to --track")
+          or a.track_min_hits != 1 or a.tracks_out is not None or a.track_kalman_pos != 1 / 20 or a.track_kalman_vel != 1 / 160
+          or a.track_kalman_keep_height != 1):
+        ap.error("--track-high / --track-low / --track-match / --track-motion / --track-max-age / --track-min-hits / --track-kalman-pos / "
+                 "--track-kalman-vel / --track-kalman-keep-height / --tracks-out belong to --track")
     if render_on(a):
         if a.render_label in ("id", "both") and not track_on(a):
             ap.error(f"--render-label {a.render_label} prints the track id: it needs --track")
