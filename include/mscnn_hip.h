@@ -88,6 +88,7 @@
  *   tracks_update_fwd, tracks_update_streams_fwd, tracks_state_reset, tracks_state_reset_slots
  *                              pack_dev, state_in, state_out (state) 16, track_ids_dev 4: refuses
  *   tracks_update_kalman_fwd   pack_dev, state_in, state_out, filter_in, filter_out 16, track_ids_dev 4: refuses
+ *   tracks_update_assign_fwd   as tracks_update_kalman_fwd (the filter tables only with a filter): refuses
  *   proposals_multi_fwd        props 8: refuses
  *   rois_ingest                rows 8: refuses; rois, props, image_rows, status 4
  */
@@ -1003,17 +1004,19 @@ MSCNN_API int mscnn_detections_merge_seq_fwd(const double* nms_overlap /* HOST, 
  * Tracking by Associating Every Detection Box", 2022).  A small table of tracks per slot (class, or output x class) lives in device
  * memory from call to call; every new frame's detections are associated with the tracks in two passes -- the high-score detections
  * first, then the low-score detections against the tracks still unmatched -- and every detection row gets a persistent track id.
- * Two deliberate departures from the paper: the motion of THIS op is a constant-velocity prediction of the box centre (the paper's
- * Kalman filter is there on request, beside it: mscnn_tracks_update_kalman_fwd below), and the matching is greedy by descending
- * overlap under a total order in place of the Hungarian solver.  Both make the result independent of reduction shape and scheduling:
- * bit-exact against tests/track_witness.py.
+ * Two things THIS op does in its own way, each with the paper's way on request beside it: its motion is a constant-velocity
+ * prediction of the box centre (the paper's Kalman filter: mscnn_tracks_update_kalman_fwd below), and its matching is greedy by
+ * descending overlap under a total order (the optimal assignment that SORT, DeepSORT and ByteTrack solve:
+ * mscnn_tracks_update_assign_fwd below).  Both make the result independent of reduction shape and scheduling: bit-exact against
+ * tests/track_witness.py.
  * pack_dev: a multi pack as mscnn_detections_multi_fwd, the merge ops and Seq-NMS write it, mscnn_multi_pack_layout_of(S, cap) with
  * S = num_frames * num_slots; segment s = t * K + k is frame t, slot k.  The op only reads it.  The segment's rows [x y w h score]
  * start at its ROW OFFSET: table word 2 as the merge ops write it (s * cand_cap); in the pack of a batched forward, where the K
  * slots of an image carry the same {rows, row0} -- told apart on the device by the first two entries of the frame having the same
  * word 2, which no merged pack has --, mscnn_multi_pack_slot(K, row0, k, rows).  The frames of a call are consecutive frames of the
  * stream in ascending t; the calls follow each other in stream order.  Slots never interact.
- * state: per slot a header of MSCNN_TRACKS_HEADER_WORDS int32 {n, next_id, frame, dropped, skipped, 0, 0, 0}, behind it max_tracks
+ * state: per slot a header of MSCNN_TRACKS_HEADER_WORDS int32 {n, next_id, frame, dropped, skipped, steps, 0, 0} (steps: word
+ * MSCNN_TRACKS_STEPS, written 0 by this op, see mscnn_tracks_update_assign_fwd), behind it max_tracks
  * records (mscnn_track_record); mscnn_tracks_state_layout_of names the offsets.  mscnn_tracks_state_reset sets n = 0, next_id = 1,
  * frame = 0, dropped = skipped = 0.  state_in == state_out (in place) and two distinct buffers both work; records at index >= n of
  * state_out are left as they were.  track_ids_dev: cap int32, one per pack row.
@@ -1064,7 +1067,7 @@ typedef struct { double high_thr, low_thr, new_thr, match_thr, match_thr_low, ve
                  int motion, max_age, min_hits; } mscnn_track_params;
 #endif
 enum { MSCNN_TRACKS_N = 0, MSCNN_TRACKS_NEXT_ID = 1, MSCNN_TRACKS_FRAME = 2, MSCNN_TRACKS_DROPPED = 3, MSCNN_TRACKS_SKIPPED = 4,
-       MSCNN_TRACKS_HEADER_WORDS = 8 };      /* int32 words of a slot's header */
+       MSCNN_TRACKS_STEPS = 5 /* mscnn_tracks_update_assign_fwd's optimal form; 0 otherwise */, MSCNN_TRACKS_HEADER_WORDS = 8 };      /* int32 words of a slot's header */
 typedef struct { double box[4], obs[4], vel[2], score; int32_t id, hits, misses, confirmed; } mscnn_track_record;      /* 104 bytes */
 typedef struct { size_t records, record, slot, total; } mscnn_tracks_state_layout;   /* byte offset of a slot's records, bytes of a record, of a slot, of the state */
 static inline mscnn_tracks_state_layout mscnn_tracks_state_layout_of(int num_slots, int max_tracks) {
@@ -1115,7 +1118,8 @@ MSCNN_API int mscnn_tracks_state_reset_slots(void* state, int num_slots_total, i
  * and ByteTrack run it, in the place of steps 3 and 6's linear prediction.  A second setting beside mscnn_track_params, a side table
  * beside the track state, an entry point of its own: mscnn_track_params, mscnn_track_record and the two ops above do not change, and
  * MSCNN_TRACK_MOTION_NONE / _LINEAR stay what they are (on a noise-free approaching box the linear rule overlaps better than the
- * filter: the filter is an option, not a replacement).  The greedy walk in place of the Hungarian solver remains.
+ * filter: the filter is an option, not a replacement).  The matching of THIS op is the greedy walk; mscnn_tracks_update_assign_fwd
+ * below runs the filter under either matching.
  * ONE argument: the op would have 17, so it takes a pointer to a call struct that carries them all, the stream among them (`size`
  * must be sizeof(mscnn_tracks_kalman_call)).  The stream contract binds it as every op: it waits for nothing and runs in the order of
  * call->stream.  call->track, call->filter, call->stream_of are HOST and read before the call returns.
@@ -1175,6 +1179,61 @@ typedef struct { size_t size;      /* sizeof(mscnn_tracks_kalman_call), refused 
                  int max_tracks;  int* track_ids_dev;  void* stream; } mscnn_tracks_kalman_call;
 MSCNN_API size_t mscnn_tracks_kalman_state_bytes(int num_slots, int max_tracks);      /* 0: refused */
 MSCNN_API int mscnn_tracks_update_kalman_fwd(const mscnn_tracks_kalman_call* call);
+
+/* The tracker with the matching as a choice: the greedy walk of steps 4 and 5, or the optimal assignment that SORT, DeepSORT and
+ * ByteTrack solve (lapjv(cost = 1 - IoU, extend_cost = True, cost_limit = 1 - thr), as ByteTrack calls it).  They differ exactly
+ * where a tracker is hard, on boxes that overlap each other: tracks A, B and detections a, b with r(A, b) = 0.65, r(A, a) = 0.60,
+ * r(B, b) = 0.50, r(B, a) = 0 -- the walk takes (A, b), B has nothing left and a starts a new id; the assignment takes (A, a) + (B, b).
+ * One entry point, one call struct in the pattern of mscnn_tracks_kalman_call (`size` must be sizeof(mscnn_tracks_assign_call));
+ * mscnn_track_params, mscnn_track_record, mscnn_tracks_kalman_call and the three ops above do not change.  call->filter NULL: the
+ * motion of call->track (none / linear), the ten steps of mscnn_tracks_update_streams_fwd; otherwise the Kalman filter with
+ * track->motion NONE, the steps of mscnn_tracks_update_kalman_fwd, and filter_in / filter_out as there.  call->assign:
+ * MSCNN_TRACK_ASSIGN_GREEDY is, byte for byte, the existing op for the same arguments (the same kernel instantiation).
+ * MSCNN_TRACK_ASSIGN_OPTIMAL gives steps 4 and 5 a second form; everything else -- H and L, the tracks that take part, r(i, j), the
+ * eligibility r > thr, steps 1 - 3 and 6 - 10 -- is unchanged:
+ *   4''. Pass 1 as an assignment.  A pair is matched only if matching it beats leaving both its ends unmatched: the pass finds a
+ *       maximum-WEIGHT matching over the eligible pairs (not necessarily of maximum cardinality).  Integer weights make the optimum
+ *       independent of summation order: q(x) = (int64)floor(x * 2^30), exact in double; w(i, j) = q(r(i, j)) - q(thr) + 1 >= 1 for
+ *       an eligible pair, every other pair is absent.  Shortest augmenting paths with potentials, all in int64:
+ *       Rows = the pass's a tracks in table order.  Columns = the pass's b detections in ascending j (the real columns), then one
+ *       private dummy column per row.  A real column costs -w and exists for eligible pairs only; a row's own dummy costs 0 and no
+ *       other row reaches it.  u (rows), v and p (columns) start at 0 and free.
+ *       For every row x in ascending order that has at least one eligible pair (the others stay unmatched and cost no step):
+ *       minv = +inf, way unset, used = false for every column; i0 = x, j0 = the virtual start.  Repeat, as ONE STEP:
+ *           for every unused column c row i0 has a cost for: cur = cost(i0, c) - u[i0] - v[c]; cur < minv[c]: minv[c] = cur, way[c] = j0;
+ *           delta = min minv over the unused columns, j1 its column -- the lowest column index among equals, real before dummy;
+ *           u[x] += delta; every used c: u[p[c]] += delta, v[c] -= delta; every unused c with a finite minv: minv[c] -= delta;
+ *           j1 is used, j0 = j1; stop if j1 is free, else i0 = p[j1].
+ *       Then augment back along way.  The matched pairs are the real columns that have a row.  A search takes at most min(a, b) + 1
+ *       steps (every step uses a new assigned column or ends; the loop carries that bound), a pass at most a * (min(a, b) + 1).
+ *   5''. Pass 2 (BYTE) likewise: the tracks of step 5 with every j in L, eligible iff r > match_thr_low, w with q(match_thr_low).
+ * Header word MSCNN_TRACKS_STEPS (5) of a table: under OPTIMAL the table's running total of steps over both passes, read from
+ * state_in, saturating at INT32_MAX, written to state_out; under GREEDY (and by the three ops above) it is written 0, as before.
+ * mscnn_tracks_state_reset and _reset_slots zero it.  On sparse frames -- what is left behind an NMS -- most searches end after one or
+ * two steps; a dense 1024 x 1024 table could take about 5 * 10^5.
+ * The kernel: the tracker's kernel template has a second parameter, four instantiations; the two greedy ones are the code they were.
+ * A thread is one row (its track), the real column of its detection and its row's dummy column; per step every thread does one
+ * overlap and the workgroup one minimum of the key minv * 2048 + column (potentials stay under about 2^41, a column index takes 11
+ * bits).  u, v, way, p and every track box lie in LDS arrays the greedy passes own and a pass leaves free (4 KB more for v's high
+ * words, 128 bytes for the minimum).  Every loop exit is a value every thread reads out of LDS behind a barrier; nothing spins, no
+ * atomics, no workgroup waits on another.
+ * Refused before any launch, naming the value: everything the corresponding existing op refuses (under the name
+ * tracks_update_assign; a null stream_of only with more than one stream), a null call, a size that is not
+ * sizeof(mscnn_tracks_assign_call), an assign outside {1, 2}, filter_in or filter_out given without filter.
+ * The check: tests/track_assign_witness.py restates 4'' in Python integers (bit for bit: ids, state, word 5, filter table) and is
+ * held to an exhaustive search and to scipy's linear_sum_assignment.  The accuracy of the tracker was NOT evaluated: there are no
+ * labels here. */
+enum { MSCNN_TRACK_ASSIGN_GREEDY = 1, MSCNN_TRACK_ASSIGN_OPTIMAL = 2 };
+typedef struct { size_t size;      /* sizeof(mscnn_tracks_assign_call), refused otherwise */
+                 const mscnn_track_params* track;
+                 const mscnn_track_kalman_params* filter;      /* NULL: the motion of track; else the Kalman filter, track->motion NONE */
+                 int assign;                                   /* MSCNN_TRACK_ASSIGN_* */
+                 int num_frames, num_slots, num_streams;  const int* stream_of;      /* HOST; NULL with one stream */
+                 const void* pack_dev;  int cap;
+                 const void* state_in;  void* state_out;
+                 const void* filter_in; void* filter_out;      /* with filter only: as mscnn_tracks_kalman_call; NULL otherwise */
+                 int max_tracks;  int* track_ids_dev;  void* stream; } mscnn_tracks_assign_call;
+MSCNN_API int mscnn_tracks_update_assign_fwd(const mscnn_tracks_assign_call* call);
 
 /* The render stage: the `show` block at the end of the reference's demo scripts (examples/kitti_car/run_mscnn_detection.m,
  * examples/caltech/run_mscnn_detection.m, examples/widerface/run_cascademscnn.m:136-150: every box with score >= show_thr drawn on

@@ -488,7 +488,8 @@ MSCNN_NET_API int mscnn_net_get_seq_nms(const mscnn_net* net, double* link_thr, 
 MSCNN_NET_API int mscnn_net_detect_merge_sequences(mscnn_net* net, int* seq_host, int cap, const int* seg_dets);
 /* Track ids across the frames of a stream (mscnn_hip.h: mscnn_tracks_update_fwd; BYTE association, Zhang et al., 2022, with a
  * constant-velocity prediction -- the paper's Kalman filter is there on request: mscnn_net_set_tracker_kalman below -- and a greedy
- * walk under a total order in place of the Hungarian solver).
+ * walk under a total order as the matching -- the optimal assignment SORT, DeepSORT and ByteTrack solve is there on request:
+ * mscnn_net_set_tracker_assign below).
  * While the tracker is on, mscnn_net_detect_multi, mscnn_net_detect_cascade_multi and mscnn_net_detect_merge_end enqueue the update
  * behind their pack -- on _end behind whichever merge op is on, and behind the vote --, on the same stream, in front of the one
  * synchronisation those calls already have; the ids go behind the pack in the same pinned block, where WBF's member counts and (in
@@ -571,6 +572,19 @@ typedef struct { double std_position, std_velocity;                             
 MSCNN_NET_API int mscnn_net_set_tracker_kalman(mscnn_net* net, const mscnn_track_kalman_params* params /* NULL: off */);
 MSCNN_NET_API int mscnn_net_get_tracker_kalman(const mscnn_net* net, int* on, mscnn_track_kalman_params* params);
 MSCNN_NET_API int mscnn_net_tracker_kalman_state(mscnn_net* net, void* filter_host, size_t bytes);
+/* The matching of the tracker's two passes (mscnn_hip.h: mscnn_tracks_update_assign_fwd, whose comment holds steps 4'' and 5''):
+ * method 1 (MSCNN_TRACK_ASSIGN_GREEDY, the default) is the walk by descending overlap, method 2 (MSCNN_TRACK_ASSIGN_OPTIMAL) the
+ * maximum-weight assignment over the eligible pairs.
+ * mscnn_net_set_tracker_assign needs the tracker on and refuses a method outside {1, 2}, naming it.  It touches NO table: both forms
+ * read and write the same ones, so the next tracked call goes on from the committed tracks with the other matching; the streams, the
+ * frame mapping and the Kalman filter stay as they are.  With method 2 every tracked call runs mscnn_tracks_update_assign_fwd in
+ * the place of the op it ran before; with method 1 it runs exactly what it ran before this call existed.  mscnn_net_set_tracker puts it
+ * back to 1, as it puts the streams back to 1.  Under method 2 header word 5 of a table (MSCNN_TRACKS_STEPS, in
+ * mscnn_net_tracker_state's copy) is the table's running total of search steps; a call under method 1 writes 0 there.
+ * mscnn_net_get_tracker_assign: the method, 0 while the tracker is off.  Both work on a net built with device -1.
+ * The check is tests/track_assign_witness.py; the accuracy was not evaluated (no labels here). */
+MSCNN_NET_API int mscnn_net_set_tracker_assign(mscnn_net* net, int method);
+MSCNN_NET_API int mscnn_net_get_tracker_assign(const mscnn_net* net, int* method);
 /* Draw the detections into the frames (mscnn_hip.h: mscnn_render_detections_u8, whose comment is the contract: footprints, paint
  * order, blend, labels, pixelation): the `show` block at the end of the reference's demo scripts, on the device.  It renders the pack
  * of the LAST mscnn_net_detect_multi, mscnn_net_detect_cascade_multi or mscnn_net_detect_merge_end on this net -- the Net still holds

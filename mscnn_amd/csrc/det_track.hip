@@ -1,9 +1,10 @@
 // A streaming multi-object tracker behind the final stage (mscnn_tracks_update_fwd): BYTE's two association passes (Zhang et al.,
 // "ByteTrack: Multi-Object Tracking by Associating Every Detection Box", 2022) over the multi pack's rows, a small table of tracks per
-// slot kept in device memory from call to call, a persistent track id for every detection row.  Two deliberate departures from the
-// paper: the motion is a constant-velocity prediction of the box centre (the paper's Kalman filter is there on request: the `true`
-// instantiation of the kernel, mscnn_tracks_update_kalman_fwd), and the matching is greedy by descending overlap under a total order
-// (larger r, then the lower track, then the lower detection) in place of the Hungarian solver.
+// slot kept in device memory from call to call, a persistent track id for every detection row.  Two things have the paper's way on
+// request beside the tracker's own: the motion is a constant-velocity prediction of the box centre (the paper's Kalman filter: the KF
+// instantiations of the kernel, mscnn_tracks_update_kalman_fwd), and the matching is greedy by descending overlap under a total order
+// (larger r, then the lower track, then the lower detection; the optimal assignment: the OPT instantiations,
+// mscnn_tracks_update_assign_fwd, track_pass_optimal below).
 // The frames of a call may belong to several streams (cameras): mscnn_tracks_update_streams_fwd gives every (stream, slot) a table of
 // its own and one workgroup, side by side in one launch; the map frame -> stream travels by value in the kernel arguments.
 // ONE workgroup of kTrackThreads owns a slot for the whole call and loops over the call's frames; thread i is track i AND detection i
@@ -92,8 +93,8 @@ __device__ __forceinline__ void kalman_box(const double* x, double* box) {
 }
 
 // the places of the set flags among the workgroup's threads, and their number (every thread calls it; two barriers)
-__device__ __forceinline__ int track_rank(bool on, int* wsum, int* total_out) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+__device__ __forceinline__ int track_rank(bool on, int* wsum, int* total_out, int tid = threadIdx.x) {
+  const int lane = tid & 63, wave = tid >> 6;
   const u64 bits = __ballot(on);
   if (lane == 0) wsum[wave] = __popcll(bits);
   __syncthreads();
@@ -164,10 +165,131 @@ __device__ __forceinline__ void track_pass(bool tact, bool dact, const DetBox& t
   __syncthreads();      // (the arrays are free again)
 }
 
+// ---- the optimal form of a pass (steps 4'' and 5'' of mscnn_tracks_update_assign_fwd): a maximum-weight matching over the eligible
+// pairs by shortest augmenting paths with potentials, all in int64.  Thread i is row i (its track) AND real column i (its detection) AND
+// row i's private dummy column.  In registers: minv and used of the real column, "reached" of the dummy.  A dummy is reached by its own
+// row only, so its v stays 0, it is never used before the step that ends a search, its way / p are its row's column, and its minv is
+// -u[row] from the step that reaches it on: it starts as that, and every later step takes delta from it and adds delta to u[row],
+// whose column is used by then (or whose row is x).  In LDS, all but 4 KB in arrays the greedy pass owns and a pass leaves free: every
+// track box for the whole pass (buf), u (sbuf's 8 KB), way and p of the real columns (best_d, dmatch_l), the column of every row (xa),
+// "takes part" and "has an eligible pair" per row (dfree, tfree), v of the real columns as two words (xb and 4 KB of its own: the
+// Kalman instantiation has no two registers left for it).  New beside that: the 16 wave minima of a step, 128 bytes.  A step: one det_overlap per thread, one workgroup-wide minimum of the key minv * 2048 + column
+// (the lower column among equal minv; a dummy's column is 1024 + its row, so real columns come first), two barriers.  i0, j0, delta, j1
+// and "j1 is free" are read out of LDS behind a barrier by every thread alike; the walk back is one thread's, behind a barrier.
+constexpr long long kAssignInf = 0x7fffffffffffffffLL;
+__device__ __forceinline__ long long track_q(double x) { return (long long)floor(x * 1073741824.0); }      // floor(x * 2^30): exact
+template <bool OPT>
+__device__ __forceinline__ long long* assign_red() {
+  if constexpr (OPT) {
+    __shared__ long long red[kTrackWaves];
+    return red;
+  } else {
+    return nullptr;
+  }
+}
+template <bool OPT>
+__device__ __forceinline__ int* assign_vhi() {
+  if constexpr (OPT) {
+    __shared__ int vhi[kTrackThreads];
+    return vhi;
+  } else {
+    return nullptr;
+  }
+}
+// Returns the pass's steps.  tmatch / dmatch as track_pass.  fill: buf gets the track boxes (pass 1); pass 2 finds them there.
+template <bool fill>
+__device__ __forceinline__ int track_pass_optimal(bool tact, bool dact, const DetBox& tbox, const DetBox& dbox, int n, int m, double thr,
+                                                  DetBox* buf, long long* u, int* way, int* prow, int* rcol, unsigned char* has,
+                                                  unsigned char* act, long long* red, int* vlo, int* vhi, int* tmatch, int* dmatch) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  has[tid] = 0;
+  act[tid] = tact ? 1 : 0;
+  if constexpr (fill) { if (tid < n) buf[tid] = tbox; }
+  u[tid] = 0; way[tid] = -1; prow[tid] = -1; rcol[tid] = -1; vlo[tid] = 0; vhi[tid] = 0;
+  __syncthreads();
+  if (dact) {      // the rows that have an eligible pair: the others stay unmatched and cost no step
+    for (int i = 0; i < n; ++i) {
+      if (!act[i]) continue;
+      const DetBox A = buf[i];
+      const double r = det_overlap<false>(A, A.w * A.h, A.x + A.w, A.y + A.h, dbox);
+      if (r > thr) has[i] = 1;      // (every writer stores the same byte)
+    }
+  }
+  __syncthreads();
+  const long long qthr = track_q(thr);
+  const int bound = (n < m ? n : m) + 1;      // (>= min(a, b) + 1: every step of a search uses a new assigned column or ends)
+  int steps = 0;
+  for (int x = 0; x < n; ++x) {
+    if (!has[x]) continue;      // (LDS behind a barrier: every thread alike)
+    long long minv_r = kAssignInf;
+    bool used_r = false, reached = false, ended = false;
+    int i0 = x, j0 = -1, j1 = -1;
+    for (int s = 0; s < bound; ++s) {
+      steps += steps < 0x7fffffff ? 1 : 0;
+      const long long ui = u[i0];
+      if (dact && !used_r) {
+        const DetBox A = buf[i0];
+        const double r = det_overlap<false>(A, A.w * A.h, A.x + A.w, A.y + A.h, dbox);
+        if (r > thr) {
+          const long long v_r = (long long)(((unsigned long long)(unsigned)vhi[tid] << 32) | (unsigned)vlo[tid]);
+          const long long cur = -(track_q(r) - qthr + 1) - ui - v_r;
+          if (cur < minv_r) { minv_r = cur; way[tid] = j0; }
+        }
+      }
+      if (tid == i0) reached = true;      // (its dummy: cost 0, v 0, way j0, minv = -u[tid] from here on)
+      long long key = (!used_r && minv_r != kAssignInf) ? minv_r * 2048 + tid : kAssignInf;
+      const long long kd = reached ? -u[tid] * 2048 + (kTrackThreads + tid) : kAssignInf;
+      key = kd < key ? kd : key;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) { const long long other = __shfl_xor(key, o); key = other < key ? other : key; }
+      if (lane == 0) red[wave] = key;
+      __syncthreads();
+#pragma unroll
+      for (int c = 0; c < kTrackWaves; ++c) { const long long other = red[c]; key = other < key ? other : key; }
+      const long long delta = key >> 11;      // (x's own dummy has a finite minv from the first step on: the key is never kAssignInf)
+      j1 = (int)(key & 2047);
+      const int nx = j1 < kTrackThreads ? prow[j1] : -1;      // (a dummy is free whenever it is reached)
+      if (tid == x) u[x] += delta;
+      if (used_r) {      // (the rows of the used columns are distinct, and none is x)
+        u[prow[tid]] += delta;
+        const long long v_r = (long long)(((unsigned long long)(unsigned)vhi[tid] << 32) | (unsigned)vlo[tid]) - delta;
+        vlo[tid] = (int)(unsigned)v_r; vhi[tid] = (int)(v_r >> 32);
+      } else if (minv_r != kAssignInf) {
+        minv_r -= delta;
+      }
+      if (tid == j1) used_r = true;
+      __syncthreads();      // (u is written, red is free again)
+      j0 = j1;
+      if (nx < 0) { ended = true; break; }
+      i0 = nx;
+    }
+    if (ended && tid == 0) {      // augment back along way
+      int j = j1;
+      for (int g = 0; g < bound && j >= 0; ++g) {
+        int jp;
+        if (j >= kTrackThreads) { const int row = j - kTrackThreads; jp = row == x ? -1 : rcol[row]; }
+        else jp = way[j];
+        // (a column inside a path is a real one and has a row; the masks keep the indices inside the arrays whatever happens)
+        const int row = (jp < 0 ? x : prow[jp & (kTrackThreads - 1)]) & (kTrackThreads - 1);
+        if (j < kTrackThreads) prow[j] = row;
+        rcol[row] = j;
+        j = jp;
+      }
+    }
+    __syncthreads();
+  }
+  if (dact && prow[tid] >= 0) *dmatch = prow[tid];
+  if (tact) { const int c = rcol[tid]; if (c >= 0 && c < kTrackThreads) *tmatch = c; }
+  __syncthreads();      // (the arrays are free again)
+  return steps;
+}
+
 // KF false: the motions none / linear of mscnn_tracks_update_fwd / _streams_fwd, Args = TrackArgs.  KF true: steps 3', 6', 8', 9' of
 // mscnn_tracks_update_kalman_fwd, Args = TrackKalmanArgs; the association passes, the ids and the compaction of the track records are
 // the same statements.  A thread's filter record F is touched by its own thread only, except at the compaction.
-template <bool KF, class Args>
+// OPT false: the greedy walk (track_pass), header word 5 is written 0.  OPT true: the optimal assignment (track_pass_optimal) in
+// both passes, header word 5 is the table's running total of steps.
+template <bool KF, bool OPT, class Args>
 __global__ __launch_bounds__(kTrackThreads) void det_track_kernel(Args a) {
   __shared__ DetBox buf[kTrackThreads];
   __shared__ double sbuf[kTrackThreads];
@@ -187,6 +309,10 @@ __global__ __launch_bounds__(kTrackThreads) void det_track_kernel(Args a) {
   const int* hin = reinterpret_cast<const int*>(a.state_in + a.slot_bytes * tab);
   int n = hin[MSCNN_TRACKS_N], next_id = hin[MSCNN_TRACKS_NEXT_ID], frame = hin[MSCNN_TRACKS_FRAME];
   int dropped = hin[MSCNN_TRACKS_DROPPED], skipped = hin[MSCNN_TRACKS_SKIPPED];
+  int steps = 0;
+  long long* const red = assign_red<OPT>();
+  int* const vhi = assign_vhi<OPT>();
+  if constexpr (OPT) { steps = hin[MSCNN_TRACKS_STEPS]; steps = steps < 0 ? 0 : steps; }
   n = n < 0 ? 0 : (n > a.max_tracks ? a.max_tracks : n);      // (a table that was never reset: nothing past max_tracks is touched)
   mscnn_track_record R = {};
   if (tid < n) R = reinterpret_cast<const mscnn_track_record*>(a.state_in + a.slot_bytes * tab + a.records_at)[tid];
@@ -244,17 +370,36 @@ __global__ __launch_bounds__(kTrackThreads) void det_track_kernel(Args a) {
     }
     const DetBox T = {R.box[0], R.box[1], R.box[2], R.box[3]};
     int tmatch = -1, dmatch = -1;
-    track_pass(have, cls == 1, T, B, n, m, a.p.match_thr, buf, best_d, dmatch_l, tfree, dfree, &any, &tmatch, &dmatch);      // step 4
-    if (a.p.low_thr < a.p.high_thr)                                                           // step 5 (L is empty otherwise)
-      track_pass(have && tmatch < 0 && R.misses == 0 && R.confirmed != 0, cls == 2, T, B, n, m, a.p.match_thr_low, buf, best_d,
-                 dmatch_l, tfree, dfree, &any, &tmatch, &dmatch);
+    if constexpr (OPT) {                                                                      // steps 4'' and 5''
+      long long* const u = reinterpret_cast<long long*>(sbuf);
+      int k = track_pass_optimal<true>(have, cls == 1, T, B, n, m, a.p.match_thr, buf, u, best_d, dmatch_l, xa, tfree, dfree, red, xb, vhi, &tmatch, &dmatch);
+      steps = k > 0x7fffffff - steps ? 0x7fffffff : steps + k;
+      if (a.p.low_thr < a.p.high_thr) {
+        k = track_pass_optimal<false>(have && tmatch < 0 && R.misses == 0 && R.confirmed != 0, cls == 2, T, B, n, m, a.p.match_thr_low, buf, u,
+                                      best_d, dmatch_l, xa, tfree, dfree, red, xb, vhi, &tmatch, &dmatch);
+        steps = k > 0x7fffffff - steps ? 0x7fffffff : steps + k;
+      }
+      // The track's box comes back out of buf, where it lay for both passes: so it holds no registers while the searches run (the
+      // Kalman instantiation has none to spare), and the second pass needs no copy of it either.
+      if (have) { const DetBox D = buf[tid]; R.box[0] = D.x; R.box[1] = D.y; R.box[2] = D.w; R.box[3] = D.h; }
+      __syncthreads();      // (buf is free again)
+    } else {
+      track_pass(have, cls == 1, T, B, n, m, a.p.match_thr, buf, best_d, dmatch_l, tfree, dfree, &any, &tmatch, &dmatch);      // step 4
+      if (a.p.low_thr < a.p.high_thr)                                                         // step 5 (L is empty otherwise)
+        track_pass(have && tmatch < 0 && R.misses == 0 && R.confirmed != 0, cls == 2, T, B, n, m, a.p.match_thr_low, buf, best_d,
+                   dmatch_l, tfree, dfree, &any, &tmatch, &dmatch);
+    }
+    // Behind the optimal passes the thread's index passes through an empty asm statement: what the rest of the frame derives from it
+    // (LDS and global addresses, lane masks) is then made here and holds no registers while the searches run.  tq == tid.
+    int tq = tid;
+    if constexpr (OPT) { asm volatile("" : "+v"(tq)); __builtin_assume(tq >= 0 && tq < kTrackThreads); }
     // steps 6 and 7: a matched detection hands its row to its track through LDS
     if (dmatch >= 0) { buf[dmatch] = B; sbuf[dmatch] = sc; }
     __syncthreads();
     bool alive = false;
     if (have) {
       if (tmatch >= 0) {
-        const DetBox D = buf[tid];
+        const DetBox D = buf[tq];
         if (linear) {
           const double g = (double)(R.misses + 1);
           const double hw = D.w / 2, hx = D.x + hw, ow = R.obs[2] / 2, ox = R.obs[0] + ow;
@@ -282,7 +427,7 @@ __global__ __launch_bounds__(kTrackThreads) void det_track_kernel(Args a) {
           R.box[0] = D.x; R.box[1] = D.y; R.box[2] = D.w; R.box[3] = D.h;
         }
         R.obs[0] = D.x; R.obs[1] = D.y; R.obs[2] = D.w; R.obs[3] = D.h;
-        R.score = sbuf[tid];
+        R.score = sbuf[tq];
         R.hits += 1; R.misses = 0;
         if (R.hits >= a.p.min_hits) R.confirmed |= 1;
         alive = true;
@@ -290,25 +435,25 @@ __global__ __launch_bounds__(kTrackThreads) void det_track_kernel(Args a) {
         R.misses += 1;
         alive = R.confirmed != 0 && R.misses <= a.p.max_age;
       }
-      xa[tid] = R.confirmed != 0 ? R.id : 0;      // what a detection matched to this track is given
+      xa[tq] = R.confirmed != 0 ? R.id : 0;      // what a detection matched to this track is given
     }
     const bool born = cls == 1 && dmatch < 0 && sc >= a.p.new_thr;                            // step 8
     // step 9: the survivors in their old order, then the births in ascending j; the first max_tracks
     int nsurv = 0, nborn = 0;
-    const int ps = track_rank(alive, wsum, &nsurv);      // (its barriers also publish xa)
-    const int pb = track_rank(born, wsum, &nborn);
+    const int ps = track_rank(alive, wsum, &nsurv, tq);      // (its barriers also publish xa)
+    const int pb = track_rank(born, wsum, &nborn, tq);
     const int room = a.max_tracks - nsurv;               // (>= 0: nsurv <= n <= max_tracks)
     const int kept = nborn < room ? nborn : room;
     const bool born_kept = born && pb < kept;
     // step 10
-    if (tid < m) {
+    if (tq < m) {
       int id = 0;
       if (dmatch >= 0) id = xa[dmatch];
       else if (born_kept && a.p.min_hits <= 1) id = next_id + pb;
-      a.ids[(size_t)off + (size_t)tid] = id;
+      a.ids[(size_t)off + (size_t)tq] = id;
     }
     if (fits)
-      for (int j = kTrackThreads + tid; j < count; j += kTrackThreads) a.ids[(size_t)off + (size_t)j] = 0;      // (never entered)
+      for (int j = kTrackThreads + tq; j < count; j += kTrackThreads) a.ids[(size_t)off + (size_t)j] = 0;      // (never entered)
     __syncthreads();      // (xa is free again)
     if (nsurv != n || kept > 0) {      // the records move to their new places, field by field through LDS
       const int pd = nsurv + pb;
@@ -317,18 +462,18 @@ __global__ __launch_bounds__(kTrackThreads) void det_track_kernel(Args a) {
       __syncthreads();
       const int n2 = nsurv + kept;
       mscnn_track_record N = {};
-      if (tid < n2) { const DetBox D = buf[tid]; N.box[0] = D.x; N.box[1] = D.y; N.box[2] = D.w; N.box[3] = D.h; N.score = sbuf[tid]; N.id = xa[tid]; N.hits = xb[tid]; }
+      if (tq < n2) { const DetBox D = buf[tq]; N.box[0] = D.x; N.box[1] = D.y; N.box[2] = D.w; N.box[3] = D.h; N.score = sbuf[tq]; N.id = xa[tq]; N.hits = xb[tq]; }
       __syncthreads();
       if (alive) { buf[ps] = DetBox{R.obs[0], R.obs[1], R.obs[2], R.obs[3]}; if constexpr (!KF) sbuf[ps] = R.vel[0]; xa[ps] = R.misses; xb[ps] = R.confirmed; }
       if (born_kept) { buf[pd] = B; if constexpr (!KF) sbuf[pd] = 0.0; xa[pd] = 0; xb[pd] = a.p.min_hits <= 1 ? 1 : 0; }
       __syncthreads();
-      if (tid < n2) { const DetBox D = buf[tid]; N.obs[0] = D.x; N.obs[1] = D.y; N.obs[2] = D.w; N.obs[3] = D.h; if constexpr (!KF) N.vel[0] = sbuf[tid]; N.misses = xa[tid]; N.confirmed = xb[tid]; }
+      if (tq < n2) { const DetBox D = buf[tq]; N.obs[0] = D.x; N.obs[1] = D.y; N.obs[2] = D.w; N.obs[3] = D.h; if constexpr (!KF) N.vel[0] = sbuf[tq]; N.misses = xa[tq]; N.confirmed = xb[tq]; }
       __syncthreads();
       if constexpr (!KF) {      // (the filter's tracks: vel is the filter's v[0], v[1], which moves below)
         if (alive) sbuf[ps] = R.vel[1];
         if (born_kept) sbuf[pd] = 0.0;
         __syncthreads();
-        if (tid < n2) N.vel[1] = sbuf[tid];
+        if (tq < n2) N.vel[1] = sbuf[tq];
         __syncthreads();
       }
       R = N;
@@ -338,14 +483,16 @@ __global__ __launch_bounds__(kTrackThreads) void det_track_kernel(Args a) {
         const double hw = B.w / 2, hh = B.h / 2;
         const double z[4] = {B.x + hw, B.y + hh, B.w / B.h, B.h};
         const double e = a.sp2 * B.h, e2 = e * e, g = a.sv10 * B.h, g2 = g * g;
+        double a2 = a.a2, b2 = a.b2;
+        if constexpr (OPT) asm volatile("" : "+s"(a2), "+s"(b2));      // (as tq: no copy of them in vector registers during the searches)
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
           if (alive) { buf[ps] = DetBox{fx[c], fv[c], cov[kalman_at(0, c)], cov[kalman_at(1, c)]}; sbuf[ps] = cov[kalman_at(2, c)]; }
-          if (born_kept) { buf[pd] = DetBox{z[c], 0.0, c == 2 ? a.a2 : e2, 0.0}; sbuf[pd] = c == 2 ? a.b2 : g2; }
+          if (born_kept) { buf[pd] = DetBox{z[c], 0.0, c == 2 ? a2 : e2, 0.0}; sbuf[pd] = c == 2 ? b2 : g2; }
           __syncthreads();
-          if (tid < n2) {
-            const DetBox D = buf[tid];
-            fx[c] = D.x; fv[c] = D.y; cov[kalman_at(0, c)] = D.w; cov[kalman_at(1, c)] = D.h; cov[kalman_at(2, c)] = sbuf[tid];
+          if (tq < n2) {
+            const DetBox D = buf[tq];
+            fx[c] = D.x; fv[c] = D.y; cov[kalman_at(0, c)] = D.w; cov[kalman_at(1, c)] = D.h; cov[kalman_at(2, c)] = sbuf[tq];
           }
           __syncthreads();
         }
@@ -360,7 +507,7 @@ __global__ __launch_bounds__(kTrackThreads) void det_track_kernel(Args a) {
   if (tid == 0) {
     int* h = reinterpret_cast<int*>(so);
     h[MSCNN_TRACKS_N] = n; h[MSCNN_TRACKS_NEXT_ID] = next_id; h[MSCNN_TRACKS_FRAME] = frame; h[MSCNN_TRACKS_DROPPED] = dropped;
-    h[MSCNN_TRACKS_SKIPPED] = skipped; h[5] = 0; h[6] = 0; h[7] = 0;
+    h[MSCNN_TRACKS_SKIPPED] = skipped; h[MSCNN_TRACKS_STEPS] = OPT ? steps : 0; h[6] = 0; h[7] = 0;
   }
   if constexpr (KF) {      // vel = {v[0], v[1]} behind every step 3', 6' and 8'; a table that was not stepped keeps the vel it came with
     if (tid < n) {
@@ -430,10 +577,14 @@ extern "C" int mscnn_tracks_state_reset_slots(void* state, int num_slots_total, 
 
 // All entry points: `op` names the one that was called in a refusal.  with_map false: one stream, no map (mscnn_tracks_update_fwd).
 // kc: the call of mscnn_tracks_update_kalman_fwd (the Kalman instantiation, its filter tables and setting), null for the other two.
+// assign: MSCNN_TRACK_ASSIGN_GREEDY for the three ops that have no say in it; map_optional: a null stream_of passes with one stream.
 static int tracks_update_any(const char* op, bool with_map, const mscnn_track_params* p, int num_frames, int num_slots, int num_streams, const int* stream_of,
                              const void* pack_dev, int cap, const void* state_in, void* state_out, int max_tracks, int* track_ids_dev,
-                             void* stream, const mscnn_tracks_kalman_call* kc = nullptr) {
+                             void* stream, const mscnn_tracks_kalman_call* kc = nullptr, int assign = MSCNN_TRACK_ASSIGN_GREEDY,
+                             bool map_optional = false) {
   MSCNN_REQUIRE(p && pack_dev && state_in && state_out && track_ids_dev, "%s: null pointer", op);
+  MSCNN_REQUIRE(assign == MSCNN_TRACK_ASSIGN_GREEDY || assign == MSCNN_TRACK_ASSIGN_OPTIMAL, "%s: assign %d is neither %d (greedy) nor %d (optimal)", op,
+                assign, MSCNN_TRACK_ASSIGN_GREEDY, MSCNN_TRACK_ASSIGN_OPTIMAL);
   if (kc) {
     MSCNN_REQUIRE(kc->filter, "%s: null filter", op);
     MSCNN_REQUIRE(kc->filter_in, "%s: null filter_in", op);
@@ -445,7 +596,7 @@ static int tracks_update_any(const char* op, bool with_map, const mscnn_track_pa
   MSCNN_REQUIRE(cap >= 1, "%s: cap %d", op, cap);
   const int N = num_streams;
   if (with_map) {
-    MSCNN_REQUIRE(stream_of || (kc && N == 1), "%s: null stream_of", op);
+    MSCNN_REQUIRE(stream_of || ((kc || map_optional) && N == 1), "%s: null stream_of", op);
     MSCNN_REQUIRE(N >= 1 && N <= kTrackStreams, "%s: num_streams %d is outside [1, %d]", op, N, kTrackStreams);
     MSCNN_REQUIRE(N == 1 || T <= kTrackStreams, "%s: num_frames %d is above %d with %d streams (the map rides in the kernel's arguments)", op, T,
                   kTrackStreams, N);
@@ -518,9 +669,15 @@ static int tracks_update_any(const char* op, bool with_map, const mscnn_track_pa
     ka.freeze_lost_height = f.freeze_lost_height;
     ka.filter_in = static_cast<const mscnn_track_kalman_record*>(kc->filter_in);
     ka.filter_out = static_cast<mscnn_track_kalman_record*>(kc->filter_out);
-    det_track_kernel<true, TrackKalmanArgs><<<dim3((unsigned)K, (unsigned)N), kTrackThreads, 0, as_stream(stream)>>>(ka);
+    if (assign == MSCNN_TRACK_ASSIGN_OPTIMAL)
+      det_track_kernel<true, true, TrackKalmanArgs><<<dim3((unsigned)K, (unsigned)N), kTrackThreads, 0, as_stream(stream)>>>(ka);
+    else
+      det_track_kernel<true, false, TrackKalmanArgs><<<dim3((unsigned)K, (unsigned)N), kTrackThreads, 0, as_stream(stream)>>>(ka);
   } else {
-    det_track_kernel<false, TrackArgs><<<dim3((unsigned)K, (unsigned)N), kTrackThreads, 0, as_stream(stream)>>>(a);
+    if (assign == MSCNN_TRACK_ASSIGN_OPTIMAL)
+      det_track_kernel<false, true, TrackArgs><<<dim3((unsigned)K, (unsigned)N), kTrackThreads, 0, as_stream(stream)>>>(a);
+    else
+      det_track_kernel<false, false, TrackArgs><<<dim3((unsigned)K, (unsigned)N), kTrackThreads, 0, as_stream(stream)>>>(a);
   }
   MSCNN_POST_LAUNCH();
   return MSCNN_OK;
@@ -550,4 +707,24 @@ extern "C" int mscnn_tracks_update_kalman_fwd(const mscnn_tracks_kalman_call* c)
                 sizeof(mscnn_tracks_kalman_call));
   return tracks_update_any("tracks_update_kalman", true, c->track, c->num_frames, c->num_slots, c->num_streams, c->stream_of, c->pack_dev, c->cap,
                            c->state_in, c->state_out, c->max_tracks, c->track_ids_dev, c->stream, c);
+}
+
+extern "C" int mscnn_tracks_update_assign_fwd(const mscnn_tracks_assign_call* c) {
+  MSCNN_REQUIRE(c, "tracks_update_assign: null call");
+  MSCNN_REQUIRE(c->size == sizeof(mscnn_tracks_assign_call), "tracks_update_assign: size %zu is not sizeof(mscnn_tracks_assign_call) = %zu", c->size,
+                sizeof(mscnn_tracks_assign_call));
+  MSCNN_REQUIRE(c->assign == MSCNN_TRACK_ASSIGN_GREEDY || c->assign == MSCNN_TRACK_ASSIGN_OPTIMAL,
+                "tracks_update_assign: assign %d is neither %d (greedy) nor %d (optimal)", c->assign, MSCNN_TRACK_ASSIGN_GREEDY, MSCNN_TRACK_ASSIGN_OPTIMAL);
+  if (!c->filter) {
+    MSCNN_REQUIRE(!c->filter_in && !c->filter_out, "tracks_update_assign: %s is given without a filter", c->filter_in ? "filter_in" : "filter_out");
+    return tracks_update_any("tracks_update_assign", true, c->track, c->num_frames, c->num_slots, c->num_streams, c->stream_of, c->pack_dev, c->cap,
+                             c->state_in, c->state_out, c->max_tracks, c->track_ids_dev, c->stream, nullptr, c->assign, true);
+  }
+  mscnn_tracks_kalman_call kc = {};
+  kc.size = sizeof(kc); kc.track = c->track; kc.filter = c->filter;
+  kc.num_frames = c->num_frames; kc.num_slots = c->num_slots; kc.num_streams = c->num_streams; kc.stream_of = c->stream_of;
+  kc.pack_dev = c->pack_dev; kc.cap = c->cap; kc.state_in = c->state_in; kc.state_out = c->state_out;
+  kc.filter_in = c->filter_in; kc.filter_out = c->filter_out; kc.max_tracks = c->max_tracks; kc.track_ids_dev = c->track_ids_dev; kc.stream = c->stream;
+  return tracks_update_any("tracks_update_assign", true, c->track, c->num_frames, c->num_slots, c->num_streams, c->stream_of, c->pack_dev, c->cap,
+                           c->state_in, c->state_out, c->max_tracks, c->track_ids_dev, c->stream, &kc, c->assign);
 }

@@ -262,6 +262,7 @@ def lib():
         L.mscnn_tracks_kalman_state_bytes.restype = C.c_size_t
         L.mscnn_tracks_kalman_state_bytes.argtypes = [C.c_int, C.c_int]
         L.mscnn_tracks_update_kalman_fwd.argtypes = [C.c_void_p]
+        L.mscnn_tracks_update_assign_fwd.argtypes = [C.c_void_p]
         L.mscnn_render_detections_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                                  C.c_void_p, C.c_void_p]
         L.mscnn_render_glyph_rows.argtypes = [C.c_int, C.c_void_p]
@@ -1549,6 +1550,63 @@ def tracks_update_kalman(params, kparams, num_frames, num_slots, num_streams, st
                             None if so is None else so.ctypes.data, at(pack), cap, at(state_in), at(state_out), at(filter_in),
                             at(filter_out), max_tracks, at(ids), _stream().value)
     _check(lib().mscnn_tracks_update_kalman_fwd(C.byref(call)))
+    return state_out, filter_out, ids
+
+
+# ---- the tracker's matching as a choice (mscnn_hip.h: mscnn_tracks_update_assign_fwd) ----
+TRACK_ASSIGNS = {"greedy": 1, "optimal": 2}      # MSCNN_TRACK_ASSIGN_*
+TRACKS_STEPS = 5                                 # MSCNN_TRACKS_STEPS: the header word of the optimal form's search steps
+
+
+class TracksAssignCall(C.Structure):
+    """mscnn_tracks_assign_call: the one argument of mscnn_tracks_update_assign_fwd."""
+    _fields_ = [("size", C.c_size_t), ("track", C.c_void_p), ("filter", C.c_void_p), ("assign", C.c_int), ("num_frames", C.c_int),
+                ("num_slots", C.c_int), ("num_streams", C.c_int), ("stream_of", C.c_void_p), ("pack_dev", C.c_void_p), ("cap", C.c_int),
+                ("state_in", C.c_void_p), ("state_out", C.c_void_p), ("filter_in", C.c_void_p), ("filter_out", C.c_void_p),
+                ("max_tracks", C.c_int), ("track_ids_dev", C.c_void_p), ("stream", C.c_void_p)]
+
+
+def track_assign(assign):
+    """An assignment's number from its name ("greedy", "optimal"); a number passes through for the library to judge."""
+    if isinstance(assign, str):
+        if assign not in TRACK_ASSIGNS:
+            raise MscnnError(f"tracker: assign {assign!r} is none of {sorted(TRACK_ASSIGNS)}")
+        return TRACK_ASSIGNS[assign]
+    return int(assign)
+
+
+def tracks_state_steps(state, num_slots, max_tracks):
+    """Header word 5 of every table of a state buffer (uint8, host): the optimal form's running total of search steps."""
+    rec_at, _, slot, total = tracks_state_layout(num_slots, max_tracks)
+    b = np.ascontiguousarray(state, dtype=np.uint8).reshape(-1)
+    if b.size < total:
+        raise MscnnError(f"tracker: a state of {b.size} bytes, {num_slots} slots x {max_tracks} tracks need {total}")
+    return [int(b[k * slot:k * slot + rec_at].view(np.int32)[TRACKS_STEPS]) for k in range(num_slots)]
+
+
+def tracks_update_assign(params, kparams, assign, num_frames, num_slots, num_streams, stream_of, pack, cap, state_in, max_tracks,
+                         filter_in=None, state_out=None, filter_out=None, ids=None):
+    """mscnn_tracks_update_assign_fwd: tracks_update_streams (kparams None) or tracks_update_kalman (kparams and filter tables given)
+    with the matching of both passes chosen: "greedy" is the existing op byte for byte, "optimal" the maximum-weight assignment, which
+    also counts its search steps into header word 5.  Returns (state_out, filter_out, ids)."""
+    if state_out is None:
+        state_out = state_in
+    if filter_out is None:
+        filter_out = filter_in
+    if ids is None:
+        ids = torch.zeros(max(cap, 1), dtype=torch.int32, device=pack.device)
+    so = None
+    if stream_of is not None:
+        so = np.ascontiguousarray(stream_of, dtype=np.int32).reshape(-1)
+        if so.size != num_frames:
+            raise MscnnError(f"tracker: stream_of names {so.size} frames, the call has {num_frames}")
+    def at(t):
+        p = _dev(t)
+        return None if p is None else p.value
+    call = TracksAssignCall(C.sizeof(TracksAssignCall), C.addressof(params), None if kparams is None else C.addressof(kparams),
+                            track_assign(assign), num_frames, num_slots, num_streams, None if so is None else so.ctypes.data, at(pack), cap,
+                            at(state_in), at(state_out), at(filter_in), at(filter_out), max_tracks, at(ids), _stream().value)
+    _check(lib().mscnn_tracks_update_assign_fwd(C.byref(call)))
     return state_out, filter_out, ids
 
 

@@ -72,6 +72,9 @@ struct mscnn_net {
   // mscnn_tracks_update_kalman_fwd, and a filter table stands beside each of the two track tables, swapped with them (track_cur).
   bool kalman_on = false;
   mscnn_track_kalman_params kalman = {1.0 / 20, 1.0 / 160, 1e-2, 1e-5, 1e-1, 1};
+  // mscnn_net_set_tracker_assign: the matching of the two passes.  Optimal: the tracked calls run mscnn_tracks_update_assign_fwd on the
+  // same tables (both forms read and write the same ones, so a switch touches nothing).
+  int track_assign = MSCNN_TRACK_ASSIGN_GREEDY;
   caffe::DeviceBuffer track_filter[2];
   // mscnn_net_render: what the last detect_multi / detect_cascade_multi / detect_merge_end left in det_host -- the pack of `frames` x
   // `slots` segments with `cap` rows and, when that call ran the tracker, its ids at ids_at (bytes: both).  Any other user of det_host
@@ -665,7 +668,7 @@ int mscnn_net_set_tracker(mscnn_net* n, const mscnn_track_params* p, int max_tra
   return guarded([&] {
     CHECK(n != nullptr);
     if (p == nullptr) {      // off: the state is dropped with the setting
-      n->track_on = false; n->track_K = 0; n->tracks_valid = false; n->kalman_on = false;
+      n->track_on = false; n->track_K = 0; n->tracks_valid = false; n->kalman_on = false; n->track_assign = MSCNN_TRACK_ASSIGN_GREEDY;
       n->track_streams = 1; n->track_stream_of.clear(); n->track_reset_pending.clear();
       return;
     }
@@ -688,6 +691,25 @@ int mscnn_net_set_tracker(mscnn_net* n, const mscnn_track_params* p, int max_tra
     n->track_K = 0; n->tracks_valid = false;      // a new setting is a new stream: the next call starts at id 1
     n->track_streams = 1; n->track_stream_of.clear(); n->track_reset_pending.clear();      // (and ONE stream: mscnn_net_set_tracker_streams)
     n->kalman_on = false;      // (and no filter: mscnn_net_set_tracker_kalman)
+    n->track_assign = MSCNN_TRACK_ASSIGN_GREEDY;      // (and the greedy walk: mscnn_net_set_tracker_assign)
+  });
+}
+
+int mscnn_net_set_tracker_assign(mscnn_net* n, int method) {
+  return guarded([&] {
+    CHECK(n != nullptr);
+    CHECK(n->track_on) << "set_tracker_assign: the tracker is off (mscnn_net_set_tracker)";
+    CHECK(method == MSCNN_TRACK_ASSIGN_GREEDY || method == MSCNN_TRACK_ASSIGN_OPTIMAL)
+        << "set_tracker_assign: assign " << method << " is neither " << MSCNN_TRACK_ASSIGN_GREEDY << " (greedy) nor " << MSCNN_TRACK_ASSIGN_OPTIMAL
+        << " (optimal)";
+    n->track_assign = method;      // (the tables, the streams, the mapping and the filter stay: the next call goes on from them)
+  });
+}
+
+int mscnn_net_get_tracker_assign(const mscnn_net* n, int* method) {
+  return guarded([&] {
+    CHECK(n && method);
+    *method = n->track_on ? n->track_assign : 0;
   });
 }
 
@@ -866,7 +888,16 @@ static void track_enqueue(mscnn_net* n, const char* name, int T, int K, const vo
       if (n->track_reset_pending[s])
         MSCNN_CHECK(mscnn_tracks_state_reset_slots(n->track_state[n->track_cur].get(), N * K, n->track_max, (int)s * K, K, st));
   }
-  if (n->kalman_on) {
+  if (n->track_assign == MSCNN_TRACK_ASSIGN_OPTIMAL) {
+    mscnn_tracks_assign_call c = {};
+    c.size = sizeof(c); c.track = &n->track; c.filter = n->kalman_on ? &n->kalman : nullptr; c.assign = n->track_assign;
+    c.num_frames = T; c.num_slots = K; c.num_streams = N; c.stream_of = N > 1 ? n->track_stream_of.data() : nullptr;
+    c.pack_dev = pack; c.cap = pack_rows;
+    c.state_in = n->track_state[n->track_cur].get(); c.state_out = n->track_state[n->track_cur ^ 1].get();
+    if (n->kalman_on) { c.filter_in = n->track_filter[n->track_cur].get(); c.filter_out = n->track_filter[n->track_cur ^ 1].get(); }
+    c.max_tracks = n->track_max; c.track_ids_dev = ids_dev; c.stream = st;
+    MSCNN_CHECK(mscnn_tracks_update_assign_fwd(&c));
+  } else if (n->kalman_on) {
     mscnn_tracks_kalman_call c = {};
     c.size = sizeof(c); c.track = &n->track; c.filter = &n->kalman;
     c.num_frames = T; c.num_slots = K; c.num_streams = N; c.stream_of = N > 1 ? n->track_stream_of.data() : nullptr;

@@ -117,6 +117,8 @@ RENDER_PALETTE = ((230, 25, 75), (60, 180, 75), (255, 225, 25), (0, 130, 200), (
                   (240, 50, 230))
 
 TRACK_MOTIONS = {"none": 1, "linear": 2}
+TRACK_ASSIGNS = {"greedy": 1, "optimal": 2}      # MSCNN_TRACK_ASSIGN_*
+TRACKS_STEPS = 5                                 # MSCNN_TRACKS_STEPS
 # mscnn_track_record and a slot's header (include/mscnn_hip.h: mscnn_tracks_state_layout_of)
 TRACK_RECORD = np.dtype([("box", "<f8", 4), ("obs", "<f8", 4), ("vel", "<f8", 2), ("score", "<f8"), ("id", "<i4"), ("hits", "<i4"),
                          ("misses", "<i4"), ("confirmed", "<i4")])
@@ -209,6 +211,7 @@ def lib():
             "mscnn_net_get_tracker_streams": [vp, vp, vp, ci, vp], "mscnn_net_tracker_reset_stream": [vp, ci],
             "mscnn_net_set_tracker_kalman": [vp, vp], "mscnn_net_get_tracker_kalman": [vp, vp, vp],
             "mscnn_net_tracker_kalman_state": [vp, vp, C.c_size_t],
+            "mscnn_net_set_tracker_assign": [vp, C.c_int], "mscnn_net_get_tracker_assign": [vp, vp],
             "mscnn_net_render": [vp, vp, ci, vp, vp, ci, vp, vp, ci],
             "mscnn_net_crop_window": [vp, vp, ci, ci, vp], "mscnn_net_crops": [vp, vp, ci, vp, vp, ci, vp, vp, ci, vp, vp, vp],
         }
@@ -832,6 +835,24 @@ class Net:
                     std_aspect_velocity=kp.std_aspect_velocity, std_aspect_measure=kp.std_aspect_measure,
                     freeze_lost_height=bool(kp.freeze_lost_height))
 
+    def set_tracker_assign(self, method):
+        """mscnn_net_set_tracker_assign: the matching of the tracker's two passes, "greedy" (the default: the walk by descending
+        overlap) or "optimal" (the maximum-weight assignment SORT, DeepSORT and ByteTrack solve).  It needs the tracker on, touches
+        no table -- the next tracked call goes on from the committed tracks -- and keeps streams, mapping and the Kalman filter;
+        set_tracker puts it back to "greedy".  They differ where boxes overlap each other: the walk takes the best pair first and may
+        leave a track with nothing that the assignment would have kept."""
+        if isinstance(method, str):
+            if method not in TRACK_ASSIGNS:
+                raise NetError(f"set_tracker_assign: assign {method!r} is none of 'greedy', 'optimal'")
+            method = TRACK_ASSIGNS[method]
+        _check(lib().mscnn_net_set_tracker_assign(self._h, int(method)))
+
+    def get_tracker_assign(self):
+        """mscnn_net_get_tracker_assign: "greedy" or "optimal", None while the tracker is off."""
+        m = C.c_int()
+        _check(lib().mscnn_net_get_tracker_assign(self._h, C.byref(m)))
+        return {1: "greedy", 2: "optimal"}.get(m.value)
+
     def tracker_kalman_state(self, raw=False):
         """mscnn_net_tracker_kalman_state: the committed filter table beside tracker_state()'s: per slot a numpy record array (x, v, p,
         q, r: mean, velocity, and per component the variances and the covariance) of that slot's n tracks; with streams > 1 one such
@@ -988,7 +1009,8 @@ class Net:
 
     def tracker_state(self, raw=False):
         """mscnn_net_tracker_state: the committed table, one dict per slot -- n, next_id, frame, dropped, skipped and tracks = the
-        first n records (a numpy record array: box, obs, vel, score, id, hits, misses, confirmed).  With streams > 1 one such list
+        first n records (a numpy record array: box, obs, vel, score, id, hits, misses, confirmed).  Under set_tracker_assign("optimal")
+        only, also steps = the table's running total of search steps (header word 5).  With streams > 1 one such list
         per stream.  raw: the table's bytes (uint8), streams * K slots, (stream s, slot k) at s * K + k."""
         _, _, mt, K = self._tracker()
         N = self.get_tracker_streams()
@@ -999,11 +1021,14 @@ class Net:
         if raw:
             return buf
         out = []
+        optimal = self.get_tracker_assign() == "optimal"
         for k in range(K):
             h = buf[k * slot:k * slot + 4 * TRACKS_HEADER_WORDS].view(np.int32)
             at = k * slot + 4 * TRACKS_HEADER_WORDS
             recs = buf[at:at + int(h[0]) * TRACK_RECORD.itemsize].view(TRACK_RECORD).copy()
             out.append(dict(n=int(h[0]), next_id=int(h[1]), frame=int(h[2]), dropped=int(h[3]), skipped=int(h[4]), tracks=recs))
+            if optimal:
+                out[-1]["steps"] = int(h[TRACKS_STEPS])
         if N > 1:
             return [out[s * per_stream:(s + 1) * per_stream] for s in range(N)]
         return out

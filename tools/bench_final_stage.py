@@ -61,6 +61,10 @@ the op is below the host route by more than the two spreads; the rows are also w
 --track --kalman, on the same clips: the final stage alone, + the tracker with motion linear, + the tracker with a Kalman filter per
 track (mscnn_tracks_update_kalman_fwd), and the pack on the host + the numpy witness of tests/track_kalman_witness.py; the filter op
 is reported against the linear op of the same run, spreads included; the rows go to --out (profiles/detect_track_kalman.txt).
+--track --assign, on the same clips: the final stage alone, + the tracker with the greedy walk, + the tracker with the optimal
+assignment (mscnn_tracks_update_assign_fwd), each with motion linear and with the Kalman filter, the optimal form's search steps per
+frame (header word 5), and one synthetic dense row, a 64 x 64 cluster; the optimal op is reported against the greedy op of the same
+run; the rows go to --out (profiles/detect_track_assign.txt).
 --track --streams N takes the images of ONE forward as one frame from each of N cameras (N = 0: as many as the forward has images):
 (a) the final stage alone, (b) + the one-launch stream tracker (mscnn_tracks_update_streams_fwd), (c) + N single-stream
 mscnn_tracks_update_fwd calls on N state buffers and N packs -- the only device route there was --, (d) the pack on the host + the
@@ -1021,6 +1025,125 @@ def track_kalman_leg(a):
             fh.write("\n".join(lines) + "\n")
 
 
+def track_assign_leg(a):
+    """--track --assign: on the clips of --track, behind one add of a clip's T frames: the final stage alone, + the tracker with the
+    greedy walk and + the tracker with the optimal assignment (mscnn_tracks_update_assign_fwd), each with motion linear and with a
+    Kalman filter per track; the optimal form's search steps per frame from header word 5.  Then one synthetic dense row: a 64 x 64
+    cluster (centres sigma 2 px, size 40 px), the two ops alone.  Every form starts on an idle device and a freshly reset table and
+    ends with the ids on the host; the forms rotate within a step."""
+    import torch
+    from mscnn_amd import hipapi
+    sys.path.insert(1, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import track_assign_witness as aw
+    import track_kalman_witness as kw
+    import track_witness as tw
+    kws = dict(high_thr=0.5, low_thr=0.1, match_thr=0.3, match_thr_low=0.5, vel_gain=0.5, max_age=30, min_hits=1)
+    M = 256
+    cp_lin, cp_none, ckp = hipapi.track_params(motion="linear", **kws), hipapi.track_params(motion="none", **kws), hipapi.track_kalman_params()
+    names = ["final stage alone", "+ greedy, linear", "+ optimal, linear", "+ greedy, Kalman", "+ optimal, Kalman"]
+    lines = []
+    L = hipapi.lib()
+
+    def say(line):
+        print(line, flush=True)
+        lines.append(line)
+
+    def measure(forms, reset, check):
+        F = len(forms)
+        med = [[] for _ in range(F)]
+        res = [None] * F
+        for rnd in range(a.rounds):
+            t = [[] for _ in range(F)]
+            for step in range(a.warmup + a.steps):
+                for k in range(F):
+                    f = (k + step) % F
+                    reset()                        # (untimed: every clip starts a stream)
+                    torch.cuda.synchronize()       # (untimed: every form starts on an idle device)
+                    t0 = time.perf_counter()
+                    res[f] = forms[f]()
+                    dt = time.perf_counter() - t0
+                    if step >= a.warmup:
+                        t[f].append(dt)
+                check(res)
+            for f in range(F):
+                med[f].append(1e3 * float(np.median(t[f])))
+        return [float(np.median(v)) for v in med], [max(v) - min(v) for v in med], res
+
+    say(f"# the optimal assignment beside the greedy walk behind the final stage (high_thr {kws['high_thr']:g}, low_thr {kws['low_thr']:g}, match_thr "
+        f"{kws['match_thr']:g}, match_thr_low {kws['match_thr_low']:g}, max_tracks {M}) per clip, host wall ms from an idle device to the ids on the host "
+        f"(median over {a.steps} steps after {a.warmup} warm-up; {a.rounds} rounds: median of the medians, spread = max - min), regime {a.regime}; "
+        "steps/frame = header word 5 after the clip over its frames, summed over the slots; differ = detections whose id differs between the two forms")
+    say(f"# {'case':24s} {'T':>2s} {'dets':>5s} | " + " | ".join(f"{nm:>18s} {'spread':>6s}" for nm in names) +
+        " | greedy ms | optimal ms | steps/frame | greedy K ms | optimal K ms | steps/frame K | differ")
+    for name in a.case or list(SEQ_CASES):
+        T, K, cap, cand = seq_clip_lists(a, hipapi, name)
+        S = T * K
+        pack = torch.zeros(L.mscnn_detections_multi_pack_bytes(S, S * cap), dtype=torch.uint8, device="cuda")
+        ws = torch.empty(max(L.mscnn_detections_merge_workspace_bytes(S, cap), 1), dtype=torch.uint8, device="cuda")
+        state = hipapi.tracks_state_new(K, M)
+        filt = torch.zeros(hipapi.tracks_kalman_state_bytes(K, M), dtype=torch.uint8, device="cuda")
+        ids = torch.zeros(S * cap, dtype=torch.int32, device="cuda")
+
+        def form(cp, kp_, assign):
+            def run():
+                out = cand.merge(pack=pack, ws=ws)
+                hipapi.tracks_update_assign(cp, kp_, assign, T, K, 1, None, pack, S * cap, state, M, filter_in=filt if kp_ is not None else None, ids=ids)
+                h = ids.cpu().numpy()      # (synchronises: the ids are on the host)
+                return out, [h[s * cap:s * cap + len(d)].copy() for s, (d, _, _) in enumerate(out)], sum(hipapi.tracks_state_steps(state.cpu().numpy(), K, M))
+            return run
+
+        forms = [lambda: (cand.merge(pack=pack, ws=ws), None, 0), form(cp_lin, None, "greedy"), form(cp_lin, None, "optimal"),
+                 form(cp_none, ckp, "greedy"), form(cp_none, ckp, "optimal")]
+
+        def check(res):
+            assert res[1][2] == 0 and res[3][2] == 0, "the greedy form wrote header word 5"
+
+        m, sp, res = measure(forms, lambda: hipapi._check(L.mscnn_tracks_state_reset(hipapi._dev(state), K, M, hipapi._stream())), check)
+        dets = sum(len(d) for d, _, _ in res[0][0])
+        differ = sum(int(np.count_nonzero(x != y)) for x, y in zip(res[1][1], res[2][1]))
+        say(f"  {name:24s} {T:2d} {dets:5d} | " + " | ".join(f"{m[f]:18.3f} {sp[f]:6.3f}" for f in range(5)) +
+            f" | {m[1] - m[0]:9.3f} | {m[2] - m[0]:10.3f} | {res[2][2] / T:11.1f} | {m[3] - m[0]:11.3f} | {m[4] - m[0]:12.3f} | {res[4][2] / T:13.1f} | {differ:6d}")
+        say(f"# {name}: the optimal op costs {m[2] - m[0]:.3f} ms per clip of {T} frames on top of the final stage where the greedy op costs {m[1] - m[0]:.3f} ms "
+            f"({(m[2] - m[0]) / (m[1] - m[0]):.2f}x); with the Kalman filter {m[4] - m[0]:.3f} against {m[3] - m[0]:.3f} ms ({(m[4] - m[0]) / (m[3] - m[0]):.2f}x)")
+    # the synthetic dense row: one slot, frame 1 = 64 boxes that start 64 tracks, frame 2 = 64 boxes around the same point
+    n = 64
+    A, B = aw.dense(np.random.default_rng(n), n)
+    rows = lambda b: np.concatenate([b, np.full((n, 1), 0.9)], axis=1)
+    frames = [[rows(A)], [rows(B)]]
+    buf, offs, cap = tw.pack_bytes(frames, n)
+    pack = torch.from_numpy(buf).cuda()
+    state = hipapi.tracks_state_new(1, M)
+    ids = torch.zeros(cap, dtype=torch.int32, device="cuda")
+
+    def dense_form(assign):
+        def run():
+            hipapi.tracks_update_assign(cp_none, None, assign, 2, 1, 1, None, pack, cap, state, M, ids=ids)
+            return ids.cpu().numpy().copy(), hipapi.tracks_state_steps(state.cpu().numpy(), 1, M)[0]
+        return run
+    slots = [tw.new_slot()]
+    want = aw.run(slots, frames, tw.params(motion="none", **kws), M)
+
+    def check_dense(res):
+        assert np.array_equal(res[1][0][offs[1]:offs[1] + n], want[1][0]) and res[1][1] == slots[0]["steps"], "the optimal op is not the witness"
+    m, sp, res = measure([dense_form("greedy"), dense_form("optimal")], lambda: hipapi._check(L.mscnn_tracks_state_reset(hipapi._dev(state), 1, M, hipapi._stream())),
+                         check_dense)
+    kept = [int(np.count_nonzero((r[0][offs[1]:offs[1] + n] > 0) & (r[0][offs[1]:offs[1] + n] <= n))) for r in res]
+    say(f"# synthetic dense cluster, {n} tracks x {n} detections (centres sigma 2 px around one point, size 40 px, motion none), the tracker op alone, two "
+        f"frames (the first starts the tracks): greedy {m[0]:.3f} ms (spread {sp[0]:.3f}), optimal {m[1]:.3f} ms (spread {sp[1]:.3f}), {res[1][1]} steps; "
+        f"detections of frame 2 that keep one of the {n} ids: greedy {kept[0]}, optimal {kept[1]}")
+    say("# python tools/bench_final_stage.py --track --assign" + f" --steps {a.steps} --warmup {a.warmup} --rounds {a.rounds}: MI355X (gfx950), one GPU, seeded "
+        "weights; the clips, the add call and the resets as in profiles/detect_track.txt.  The tracker columns are differences of two host wall times and "
+        "hold a second synchronisation, the copy of the id buffer and (all four alike) a copy of the state for word 5.  Every step asserts that the greedy "
+        "forms leave word 5 at 0 and that the dense row's optimal ids and steps equal tests/track_assign_witness.py.")
+    say("# NOT measured: the kernels alone (device events or a profiler), the cost of one step, one frame per call, more than one class, several streams, "
+        "tables near max_tracks = 1024, a dense table above 64 x 64 (a dense 1024 x 1024 one could take about 5e5 steps), the Net calls and the drivers end "
+        "to end, real video, accuracy (no labels).")
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+
 STREAM_CASES = {   # name: (a SEQ_CASES entry: model, images of the one forward = cameras, classes, original image size, net input size)
     "caltech-7s480-b8": ("caltech/mscnn-7s-480", 8, [2], (480, 640), (480, 640)),
     "kitti_car-7s576-b4": ("kitti_car/mscnn-7s-576", 4, [2], (375, 1242), (576, 1920)),
@@ -1227,6 +1350,9 @@ ap.add_argument("--track", action="store_true", help="on the clips of --merge --
 ap.add_argument("--kalman", action="store_true", help="with --track: the final stage alone, + the tracker with motion linear, + the tracker with a "
                 "Kalman filter per track (mscnn_tracks_update_kalman_fwd), the pack on the host + tests/track_kalman_witness.py; the rows also go "
                 "to --out (profiles/detect_track_kalman.txt)")
+ap.add_argument("--assign", action="store_true", help="with --track: the final stage alone, + the tracker with the greedy walk and + the tracker with "
+                "the optimal assignment (mscnn_tracks_update_assign_fwd), motion linear and Kalman filter, the search steps per frame, and one "
+                "synthetic dense 64 x 64 cluster; the rows also go to --out (profiles/detect_track_assign.txt)")
 ap.add_argument("--streams", type=int, default=None, metavar="N", help="with --track: the images of one forward as one frame from each of N "
                 "cameras (0: as many as images): the final stage alone, + the one-launch stream tracker, + N single-stream calls, the pack on "
                 "the host + the numpy witness per stream; the rows also go to --out")
@@ -1251,7 +1377,7 @@ ap.add_argument("--ovr-dnm", default="union", choices=("union", "min"), help="bb
 a = ap.parse_args()
 if a.out is None:
     a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                         "detect_track_streams.txt" if a.track and a.streams is not None else "detect_track_kalman.txt" if a.track and a.kalman else "detect_track.txt" if a.track else "detect_merge_seq.txt" if a.seq else "detect_merge_wbf.txt")
+                         "detect_track_streams.txt" if a.track and a.streams is not None else "detect_track_kalman.txt" if a.track and a.kalman else "detect_track_assign.txt" if a.track and a.assign else "detect_track.txt" if a.track else "detect_merge_seq.txt" if a.seq else "detect_merge_wbf.txt")
 if a.parent_lib:
     ab_leg(a, sys.argv[1:])
     sys.exit(0)
@@ -1261,6 +1387,11 @@ if a.streams is not None and not (a.track and 0 <= a.streams <= 256):
     ap.error(f"--streams {a.streams} belongs to --track and lies inside [0, 256]")
 if a.kalman and not (a.track and a.streams is None):
     ap.error("--kalman belongs to --track (without --streams)")
+if a.assign and not (a.track and a.streams is None and not a.kalman):
+    ap.error("--assign belongs to --track (without --streams and --kalman)")
+if a.track and a.assign:
+    track_assign_leg(a)
+    sys.exit(0)
 if a.track and a.kalman:
     track_kalman_leg(a)
     sys.exit(0)

@@ -57,6 +57,8 @@ accuracy not evaluated.
 --track [--track-high T] [--track-low T] [--track-match THR] [--track-motion none|linear|kalman] [--track-max-age N] [--track-min-hits N]
 [--track-kalman-pos S] [--track-kalman-vel S] [--track-kalman-keep-height 0|1] (with --track-motion kalman: a Kalman filter per track on
 centre, aspect and height, Net.set_tracker_kalman; for jittering boxes, not for clean fast approaching ones, where linear overlaps better)
+[--track-assign greedy|optimal] (the matching of both passes: the walk by descending IoU, the default, or the maximum-weight
+assignment, Net.set_tracker_assign)
 [--tracks-out DIR]: a persistent track id for every detection across the frames of the run, taken as consecutive frames of one stream
 (Net.set_tracker; BYTE's two association passes on the device behind every detect_cascade_multi and detect_merge_end, a table of
 tracks per (output, class)); alone, with --batch, with --orig-size (the boxes are original-image

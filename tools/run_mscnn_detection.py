@@ -22,6 +22,7 @@ examples/kitti_result/writeDetForEval.m.
          [--seq-nms [avg|max]] [--clip T] [--seq-link THR] [--seq-top-k N] [--tubelets-out DIR]      # Seq-NMS over clips of T frames (Net.set_seq_nms)
          [--track] [--track-high T] [--track-low T] [--track-match THR] [--track-motion none|linear|kalman] [--track-max-age N] [--track-min-hits N]
          [--track-kalman-pos S] [--track-kalman-vel S] [--track-kalman-keep-height 0|1]      # with --track-motion kalman (Net.set_tracker_kalman)
+         [--track-assign greedy|optimal]                                                     # with --track (Net.set_tracker_assign)
          [--tracks-out DIR]                                  # track ids across the frames of the run (Net.set_tracker)
          [--track --streams N --batch B]                     # the frames are N multiplexed cameras: a table of tracks per camera
          [--render-out DIR] [--show-thr T] [--render-label none|score|id|both] [--render-color slot|id] [--pixelate N]
@@ -106,8 +107,9 @@ stream in file order (Net.set_tracker, once per run): behind every final stage a
 -- BYTE's two passes (Zhang et al., 2022): the detections with a score >= --track-high T (default 0.5) are associated first, IoU
 above --track-match THR (default 0.3), then those >= --track-low T (default 0.1) with the tracks still unmatched; a constant-velocity
 prediction of the centre (--track-motion linear, the default; none: the box stays) or, on request, the paper's Kalman filter
-(--track-motion kalman: Net.set_tracker with motion none, then Net.set_tracker_kalman); a greedy walk by descending IoU in place of
-its Hungarian solver.  The filter keeps (centre, aspect, height) and their velocities per track, with --track-kalman-pos S (default
+(--track-motion kalman: Net.set_tracker with motion none, then Net.set_tracker_kalman); as the matching a greedy walk by descending IoU
+(--track-assign greedy, the default) or, on request, the optimal assignment the paper's solver finds (--track-assign optimal:
+Net.set_tracker_assign; they differ where boxes overlap each other, and the optimal form costs a search per track).  The filter keeps (centre, aspect, height) and their velocities per track, with --track-kalman-pos S (default
 0.05) and --track-kalman-vel S (default 0.00625) times the track's height as the standard deviations of position and velocity, and
 --track-kalman-keep-height 1 (the default) freezing a lost track's height: use it where the detector's boxes jitter -- it smooths
 the velocity and follows a change of size -- and not on clean, fast approaching boxes, where linear overlaps better.  An unmatched
@@ -275,6 +277,9 @@ def add_merge_flags(ap):
                     "velocity, times the track's height (default 0.00625)")
     ap.add_argument("--track-kalman-keep-height", type=int, choices=[0, 1], default=1, metavar="0|1", help="with --track-motion kalman: a track that "
                     "missed a frame keeps its height (1, the default) or goes on changing it (0)")
+    ap.add_argument("--track-assign", choices=["greedy", "optimal"], default="greedy", help="with --track: the matching of both passes is the walk "
+                    "by descending IoU (greedy, the default) or the maximum-weight assignment (optimal: Net.set_tracker_assign; keeps ids "
+                    "the walk loses where boxes overlap each other)")
     ap.add_argument("--track-max-age", type=int, default=30, metavar="N", help="with --track: a track lives through N missed frames (default 30)")
     ap.add_argument("--track-min-hits", type=int, default=1, metavar="N", help="with --track: a track shows its id from its N-th hit on (default 1)")
     ap.add_argument("--streams", type=int, default=1, metavar="N", help="with --track: the frames are N multiplexed cameras, frame i of the "
@@ -417,6 +422,8 @@ def apply_track_setting(net, a):
         if kalman:      # (keeps the streams)
             net.set_tracker_kalman(std_position=a.track_kalman_pos, std_velocity=a.track_kalman_vel,
                                    freeze_lost_height=bool(a.track_kalman_keep_height))
+        if a.track_assign != "greedy":
+            net.set_tracker_assign(a.track_assign)
 
 
 def set_group_streams(net, a, first, count):
@@ -533,9 +540,9 @@ def check_merge_flags(ap, a):
         ap.error(f"--streams {a.streams} belongs to --track")
     elif (a.track_high != 0.5 or a.track_low != 0.1 or a.track_match != 0.3 or a.track_motion != "linear" or a.track_max_age != 30
           or a.track_min_hits != 1 or a.tracks_out is not None or a.track_kalman_pos != 1 / 20 or a.track_kalman_vel != 1 / 160
-          or a.track_kalman_keep_height != 1):
+          or a.track_kalman_keep_height != 1 or a.track_assign != "greedy"):
         ap.error("--track-high / --track-low / --track-match / --track-motion / --track-max-age / --track-min-hits / --track-kalman-pos / "
-                 "--track-kalman-vel / --track-kalman-keep-height / --tracks-out belong to --track")
+                 "--track-kalman-vel / --track-kalman-keep-height / --track-assign / --tracks-out belong to --track")
     if render_on(a):
         if a.render_label in ("id", "both") and not track_on(a):
             ap.error(f"--render-label {a.render_label} prints the track id: it needs --track")
