@@ -545,7 +545,8 @@ MSCNN_API int mscnn_nms_greedy_f32(const float* boxes_xywh, int n, float iou_thr
 
 /* DecodeBBox (TEST phase) -- DecodeBBoxLayer<Dtype>::Forward_cpu (decode_bbox_layer.cpp:54-123,
  * DecodeBBoxesWithPrior math_functions.cpp:46-75); bbox[R][8] (columns 4..7 used), prior[R][5],
- * mean/std host arrays of 4. */
+ * mean/std host arrays of 4.  A std that is not > 0 (zero, negative, NaN) is refused with the value named, as the reference's
+ * set-up does (decode_bbox_layer.cpp:30). */
 /* Alignment: 4. */
 MSCNN_API int mscnn_decodebbox_fwd_f32(const float* bbox, const float* prior, float* out, int R, int bbox_dim,
                              const float* mean_host, const float* std_host, void* stream);

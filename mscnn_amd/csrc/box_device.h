@@ -18,7 +18,11 @@ constexpr int kSortCap = 4096;            // bitonic network size (power of two 
 // method: N = 32 table, degree-3 polynomial in double).  The reference's `exp(Dtype)` resolves to
 // libm expf on the host; device ocml expf is not bit-identical to it, this restatement is (checked
 // exhaustively on the host against libm for |x| <= 80: 2 differing inputs out of 2.2e9, none in the
-// clamp range [-ln 2, ln 2] used here).  Valid for |x| < 88 (the callers clamp).
+// clamp range [-ln 2, ln 2] BoxOutput uses).  The table method is taken for |x| < 87 only; everything else (|x| >= 87, inf,
+// NaN) goes to ocml's expf, which gives the right CLASS (finite / inf / 0 / NaN) but not glibc's bits.  Of the callers only
+// BoxOutput clamps its exponent (boxoutput.hip, to [min_whr, max_whr]; fmaxf / fminf also replace a NaN there); DecodeBBox
+// (detections.hip) and the final stage's box and softmax exponents (det_device.h) pass the network's values through unclamped.
+// On the device the |x| < 87 promise is held by tests/test_gpu_roi_layers.py (DecodeBBox sweep over (-87, 87)).
 __device__ __constant__ u64 kExp2fTab[32] = {
     0x3ff0000000000000ull, 0x3fefd9b0d3158574ull, 0x3fefb5586cf9890full, 0x3fef9301d0125b51ull, 0x3fef72b83c7d517bull,
     0x3fef54873168b9aaull, 0x3fef387a6e756238ull, 0x3fef1e9df51fdee1ull, 0x3fef06fe0a31b715ull, 0x3feef1a7373aa9cbull,

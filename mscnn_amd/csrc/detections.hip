@@ -334,6 +334,8 @@ extern "C" int mscnn_decodebbox_fwd_f32(const float* bbox, const float* prior, f
   MSCNN_REQUIRE(bbox_dim == 8, "decodebbox: bbox channels must be 8 (decode_bbox_layer.cpp:47), got %d", bbox_dim);
   if (R == 0) return MSCNN_OK;
   MSCNN_REQUIRE(bbox && prior && out && mean_host && std_host, "decodebbox: null pointer");
+  for (int k = 0; k < 4; ++k)      // decode_bbox_layer.cpp:30 (CHECK_GT: a NaN fails it too)
+    MSCNN_REQUIRE(std_host[k] > 0.f, "decodebbox: bbox_std[%d] = %g must be > 0", k, (double)std_host[k]);
   decode_bbox_kernel<<<cdiv(R, 256), 256, 0, as_stream(stream)>>>(bbox, prior, out, R, bbox_dim, mean_host[0], mean_host[1],
                                                                   mean_host[2], mean_host[3], std_host[0], std_host[1],
                                                                   std_host[2], std_host[3]);

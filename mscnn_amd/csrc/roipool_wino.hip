@@ -50,7 +50,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsig
 }
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 // max of three / two floats in one instruction.  Against the reference's `if (v > m) m = v` chain (roi_pooling_layer.cu:66-71): NaNs are
-// skipped by both; a tie between -0 and +0 may come out with the other sign (equal values; post-ReLU maps hold no -0 anyway).
+// skipped by both (and by sliding_max_kernel, which builds the squares these loads read); a tie between -0 and +0 may come out with the other sign (equal values; post-ReLU maps hold no -0 anyway).
 __device__ __forceinline__ float max3(float a, float b, float c) {
   float r;
   asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
@@ -320,7 +320,13 @@ __global__ __launch_bounds__(256) void sliding_max_kernel(const float* __restric
   const float4* s4 = reinterpret_cast<const float4*>(src) + n * H * W * C4;
   const float4 a = s4[((long)y * W + x) * C4 + c4], b = s4[((long)y * W + x2) * C4 + c4];
   const float4 c = s4[((long)y2 * W + x) * C4 + c4], d = s4[((long)y2 * W + x2) * C4 + c4];
-  float4 m = a;      // (the order of the comparisons does not matter: maxima of the same values; ties are equal bit patterns on post-ReLU maps)
+  // The reference's scan (maxval = -FLT_MAX; if (v > maxval) maxval = v) SKIPS a NaN cell and keeps the finite values around it, so
+  // a square's maximum must too: all four values are compared against -FLT_MAX (starting from m = a would keep a NaN anchor, and
+  // the pooling's v_max3_f32 would then drop the whole square).  A square of nothing but NaN is -FLT_MAX, as an all-NaN bin is.
+  // On finite maps this is the same chain as before: the order of the comparisons does not matter (maxima of the same values;
+  // ties are equal bit patterns on post-ReLU maps).
+  float4 m = make_float4(-FLT_MAX, -FLT_MAX, -FLT_MAX, -FLT_MAX);
+  m.x = a.x > m.x ? a.x : m.x; m.y = a.y > m.y ? a.y : m.y; m.z = a.z > m.z ? a.z : m.z; m.w = a.w > m.w ? a.w : m.w;
   m.x = b.x > m.x ? b.x : m.x; m.y = b.y > m.y ? b.y : m.y; m.z = b.z > m.z ? b.z : m.z; m.w = b.w > m.w ? b.w : m.w;
   m.x = c.x > m.x ? c.x : m.x; m.y = c.y > m.y ? c.y : m.y; m.z = c.z > m.z ? c.z : m.z; m.w = c.w > m.w ? c.w : m.w;
   m.x = d.x > m.x ? d.x : m.x; m.y = d.y > m.y ? d.y : m.y; m.z = d.z > m.z ? d.z : m.z; m.w = d.w > m.w ? d.w : m.w;

@@ -571,6 +571,8 @@ ORC_API int orc_roipool(const float* feat, const float* rois, float* out, int* a
 ORC_API int orc_decode_bbox(const float* bbox, const float* prior, float* out, int R, int bbox_dim,
                             const float* mean, const float* stdv) {
   if (bbox_dim != 8) return -1;
+  for (int k = 0; k < 4; ++k)
+    if (!(stdv[k] > 0)) return -2;      /* decode_bbox_layer.cpp:30, CHECK_GT(bbox_std, 0): zero, negative and NaN are refused */
   for (int i = 0; i < R; ++i) {
     const float xmin = prior[i * 5 + 1], ymin = prior[i * 5 + 2];
     const float xmax = prior[i * 5 + 3], ymax = prior[i * 5 + 4];

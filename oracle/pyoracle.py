@@ -233,6 +233,9 @@ def decode_bbox(bbox, prior, mean=(0, 0, 0, 0), std=(1, 1, 1, 1)):
     out = np.empty((R, 5), np.float32)
     m = (C.c_float * 4)(*mean); s = (C.c_float * 4)(*std)
     rc = lib().orc_decode_bbox(bp, pp, out.ctypes.data_as(f32p), R, bbox.shape[1], m, s)
+    if rc == -2:
+        k = next(k for k in range(4) if not s[k] > 0)
+        raise ValueError(f"decode_bbox: bbox_std[{k}] = {s[k]!r} must be > 0 (decode_bbox_layer.cpp:30)")
     assert rc == 0
     return out
 

@@ -107,3 +107,20 @@ def test_wgemm_is_refused_above_2gib_planes():
             L.mscnn_conv2d_plan_destroy(p)
     assert gemm_id(1) >= 200 and gemm_id(6) >= 200          # 36 x 128 x 103,680 x 4 B = 1.91 GB: still below the sentinel
     assert gemm_id(7) < 200 and gemm_id(8) < 200
+
+
+@pytest.mark.parametrize("std", [(0.0, 1.0, 1.0, 1.0), (1.0, 1.0, -0.5, 1.0), (1.0, 1.0, 1.0, float("nan"))])
+def test_decodebbox_refuses_std_not_above_zero_before_any_launch(std):
+    """decode_bbox_layer.cpp:30 (CHECK_GT(bbox_std, 0)): mscnn_decodebbox_fwd_f32 refuses a zero, negative or NaN std on the host,
+    naming the element and its value -- no device is needed to see it, the buffers are never touched."""
+    import ctypes as C
+    from mscnn_amd import hipapi as h
+    L = h.lib()
+    bbox, prior, out = (C.c_float * 32)(), (C.c_float * 20)(), (C.c_float * 20)(*([7.0] * 20))
+    mean, sd = (C.c_float * 4)(0, 0, 0, 0), (C.c_float * 4)(*std)
+    rc = L.mscnn_decodebbox_fwd_f32(C.cast(bbox, C.c_void_p), C.cast(prior, C.c_void_p), C.cast(out, C.c_void_p), 4, 8, mean, sd, None)
+    assert rc != 0
+    k = next(i for i in range(4) if not std[i] > 0)
+    msg = L.mscnn_last_error().decode()
+    assert f"bbox_std[{k}]" in msg and "must be > 0" in msg and ("nan" in msg.lower()) == (std[k] != std[k]), msg
+    assert list(out) == [7.0] * 20

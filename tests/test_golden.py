@@ -189,3 +189,53 @@ def test_hip_stock_layers(hip):
     for j, (axis, arrs) in enumerate(sc.concat_cases()):
         if axis == 1:
             assert np.array_equal(hip.concat_channels([dev(a) for a in arrs]).cpu().numpy(), GC[f"concat_{j}"])
+
+
+# ---------------------------------------------------------------- fourth file: the ROI layers and DecodeBBox (tests/golden/make_golden_d.py)
+import roi_cases as rc  # noqa: E402
+
+GD = np.load(os.path.join(os.path.dirname(__file__), "golden", "reference_layers_d.npz"))
+
+
+def test_oracle_roi_layers_and_decode(orc):
+    """ROIPooling / ROIAlign on both sides of the row kernel's limit, on maps with plateaus, NaN, +-inf and signed zeros, over ROIs that
+    leave the map, are inverted or land on .5; DecodeBBox at every parameter set with overflowing, NaN and inf rows: the oracle
+    against the reference's outputs, bit for bit (a NaN by position), and the reference's refusals of std <= 0 / NaN."""
+    cases = rc.golden_d_cases()
+    assert len(cases) == 20 and all(k in GD.files for k, *_ in cases)
+    for key, op, kind, PH, PW, scale, pad in cases:
+        feat = rc.feature_map(kind, rc.std_shape(rc.SWEEP_C))
+        y = getattr(orc, op)(feat, rc.golden_d_rois(scale), PH, PW, scale, pad)
+        assert y.shape == GD[key].shape, key
+        assert np.array_equal(np.isnan(y), np.isnan(GD[key])) and np.array_equal(rc.bits(y), rc.bits(GD[key])), key
+    assert any(np.isnan(GD[k]).any() for k, *_ in cases) and any(np.isinf(GD[k]).any() for k, *_ in cases)
+    bbox, prior = rc.decode_inputs(257)
+    for name, (mean, std) in rc.DECODE_PARAMS.items():
+        y, want = orc.decode_bbox(bbox, prior, mean, std), GD[f"decode_{name}"]
+        assert np.array_equal(np.isnan(y), np.isnan(want)) and np.array_equal(rc.bits(y), rc.bits(want)), name
+    assert GD["decode_refused"].tolist() == [1] * len(rc.DECODE_REFUSED_STD)
+    for std in rc.DECODE_REFUSED_STD:
+        with pytest.raises(ValueError, match=r"bbox_std\[\d\]"):
+            orc.decode_bbox(bbox, prior, (0, 0, 0, 0), std)
+
+
+@pytest.mark.gpu
+def test_hip_roi_layers_and_decode(hip):
+    """The same file through the C ABI.  Plain and post-ReLU maps bit for bit; on the special map NaN positions, values under == and
+    the bits of every non-zero value (the sign of a zero of a -0 / +0 tie is the row kernel's to choose).  DecodeBBox rows whose
+    exponents lie inside expf_libm's table range (-87, 87) bit for bit."""
+    for key, op, kind, PH, PW, scale, pad in rc.golden_d_cases():
+        feat = rc.feature_map(kind, rc.std_shape(rc.SWEEP_C))
+        y = getattr(hip, op)(dev(feat), dev(rc.golden_d_rois(scale)), PH, PW, scale, pad).cpu().numpy()
+        want = GD[key]
+        assert y.shape == want.shape and np.array_equal(np.isnan(y), np.isnan(want)), key
+        ok = ~np.isnan(want)
+        assert np.array_equal(y[ok], want[ok]), key
+        nz = ok & (want != 0) if kind == "special" else ok
+        assert np.array_equal(y[nz].view(np.uint32), want[nz].view(np.uint32)), key
+    bbox, prior = rc.decode_inputs(257)
+    for name, (mean, std) in rc.DECODE_PARAMS.items():
+        y, want = hip.decode_bbox(dev(bbox), dev(prior), mean, std).cpu().numpy(), GD[f"decode_{name}"]
+        e = bbox[:, 6:8] * np.array(std[2:], np.float32) + np.array(mean[2:], np.float32)
+        inside = (np.abs(e) < 87).all(1) & np.isfinite(bbox[:, 4:]).all(1)
+        assert inside.sum() > 200 and np.array_equal(rc.bits(y[inside]), rc.bits(want[inside])), name

@@ -221,3 +221,64 @@ def test_eltwise_bottom_counts(orc):
 def test_concat_axes(orc):
     for axis, xs in sc.concat_cases():
         assert np.array_equal(orc.concat(xs, axis), pyref.concat(xs, axis)), (axis, xs[0].shape)
+
+
+# ---------------------------------------------------------------- the ROI layers and DecodeBBox over their parameter space
+import roi_cases as rc  # noqa: E402
+
+
+def _same_but_nan_payloads(a, r, what):
+    """Bit for bit; a NaN is compared by position only."""
+    assert a.shape == r.shape, what
+    assert np.array_equal(np.isnan(a), np.isnan(r)), what
+    assert np.array_equal(rc.bits(a), rc.bits(r)), what
+
+
+@pytest.mark.parametrize("kind", rc.MAP_KINDS)
+@pytest.mark.parametrize("op", ["roipool", "roialign"])
+def test_roi_layers_sweep(orc, op, kind):
+    """ROIPooling / ROIAlign at every pooled size of roi_cases.sweep_sizes() (heights and widths 1 .. 20, 15 | 16 | 17 both ways), scales
+    1/16 .. 1, pads 0 .. 1, on the plain, the post-ReLU and the special map (NaN, +-inf, -FLT_MAX-scale, signed zeros), over the hand
+    rows (outside on every side, inverted, .5 edges, single point, whole map) and random ROIs."""
+    feat = rc.feature_map(kind, rc.std_shape(rc.SWEEP_C))
+    n = 0
+    for scale in rc.SWEEP_SCALES:
+        rois = rc.std_rois(*rc.STD_HW, 2, scale, n_random=25)
+        for pad in rc.SWEEP_PADS:
+            for PH, PW in rc.sweep_sizes():
+                a, r = getattr(orc, op)(feat, rois, PH, PW, scale, pad), getattr(pyref, op)(feat, rois, PH, PW, scale, pad)
+                _same_but_nan_payloads(a, r, (op, kind, PH, PW, scale, pad))
+                n += 1
+    print(f"{op} on {kind}: {n} combinations x {len(rois)} ROIs")
+    assert n == 25 * len(rc.sweep_sizes())
+
+
+def test_roipool_wide_and_tall_maps(orc):
+    """The maps of the row kernel's segment and row-tail cases: the oracle the GPU tests compare with, held to the reference there too."""
+    for tag, mk, rois, PH, PW, scale, pad in rc.row_cases():
+        if mk != "std":
+            for kind in rc.MAP_KINDS:
+                feat = rc.feature_map(kind, rc.case_shape(mk, 8))
+                _same_but_nan_payloads(orc.roipool(feat, rois, PH, PW, scale, pad), pyref.roipool(feat, rois, PH, PW, scale, pad), (tag, kind))
+
+
+def test_decode_bbox_sweep(orc):
+    """The zoo's three std sets, identity and a non-zero mean, at R = 1 .. 257 with exponents across (-104, 100), NaN / inf rows and
+    inverted priors; the dense exponent sweep over (-87, 87) and the rows beyond it."""
+    for R in rc.DECODE_ROWS:
+        bbox, prior = rc.decode_inputs(R)
+        for name, (mean, std) in rc.DECODE_PARAMS.items():
+            _same_but_nan_payloads(orc.decode_bbox(bbox, prior, mean, std), pyref.decode_bbox(bbox, prior, mean, std), (R, name))
+    for bbox, prior in (rc.decode_sweep(1 << 15)[:2], rc.decode_beyond()):
+        bbox, prior = bbox[:1 << 16], prior[:1 << 16]
+        _same_but_nan_payloads(orc.decode_bbox(bbox, prior), pyref.decode_bbox(bbox, prior), len(bbox))
+
+
+@pytest.mark.parametrize("std", rc.DECODE_REFUSED_STD)
+def test_decode_bbox_refusals_match(orc, std):
+    """std <= 0, -0 and NaN: refused by the reference's set-up (decode_bbox_layer.cpp:30), so refused by the oracle, naming the value."""
+    bbox, prior = rc.decode_inputs(4)
+    with pytest.raises(RuntimeError):
+        pyref.decode_bbox(bbox, prior, (0, 0, 0, 0), std)
+    with pytest.raises(ValueError, match=r"bbox_std\[\d\] = \S+ must be > 0"):
+        orc.decode_bbox(bbox, prior, (0, 0, 0, 0), std)
